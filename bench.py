@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VO frames/s of the MI355X hot path.
 
-  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|5] [--subseq L]
+  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|5] [--subseq L] [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 Default workload = BASELINE.json configs[1], the configuration the metric is quoted on: synthetic KITTI-like 1241x376 mono
@@ -14,8 +14,17 @@ A "step" is one pass of the whole pipeline over the rank's sequence(s): pyramid 
 re-detection, lag-2 PnP | triangulation, BA, poses back on the host. `value` (SURVEY.md §8d timed region) times K steps that start
 from gray frames in HOST memory (streamed ingest, ingest.hip) - barrier + device sync on both sides, max over ranks; the same K
 steps from HBM-resident frames are reported as `hbm_resident`. Sequences are independent: with N GPUs every rank runs its own
-(weak scaling, no data-path collective); the only collective is the RCCL all-gather of the pose arrays. Every rank also runs the
-`batched` leg (B distinct sequences per GPU through batched launches); rank 0 prints ONE JSON line with the job totals.
+(weak scaling, no data-path collective); the only collective is the RCCL all-gather of the pose arrays. Rank 0 prints ONE JSON line
+with the job totals.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...), nothing else. `--full` adds what
+takes passes of its own: the per-kernel tables and rooflines (HIP events in the last warm-up step, a diagnostic LM-chain pass, the
+critical-path kernel in the timed region), the `hbm_resident` leg, the `batched` leg on every rank (B distinct sequences per GPU through
+batched launches), the CPU baselines and the trajectory checks against ground truth.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step, rank 0's (sub)sequences in order: `poses.npy` (all poses
+stacked, f64 (n, 12)), `pose_counts.npy` (poses per (sub)sequence) and one `stat_<name>.npy` per deterministic pipeline counter
+(DUMP_STATS, one entry per (sub)sequence); run timings are left out, so two builds on the same arguments compare output for output.
 """
 import argparse
 import ctypes as C
@@ -44,6 +53,9 @@ INIT_FRAMES, BA_ITERATIONS = 5, 5
 # VALU rate is taken as the FP32 lane rate without FMA doubling (256 CU x 128 lanes x 2.4 GHz = 78.6 Top/s)
 PEAK_HBM_GBS, PEAK_FP64_MFMA_TFLOPS, PEAK_FP64_VALU_TFLOPS, PEAK_FP32_VALU_TFLOPS, PEAK_VALU_TOPS = 8000.0, 78.6, 78.6, 157.3, 78.6
 PNP_ITERS, EPNP_FLOP = 100, 15e3   # §8d: F_pnp = 40 * iters * M + iters * EPnP(~15 kflop)
+# counters of PipelineResult.stats that depend on the inputs only (the t_* / seconds entries are timings, tri_ahead depends on thread timing)
+DUMP_STATS = ("lk_calls", "lk_points", "detect_calls", "pnp_calls", "pnp_points", "tri_calls", "ba_calls", "ba_obs", "ba_points",
+              "heuristic_motion", "init_offset", "n_landmarks", "scale")
 
 
 def pyramid_levels(w, h):
@@ -115,9 +127,12 @@ def main():
     ap.add_argument("--batch-ba-mode", type=int, default=0, choices=(0, 1), help="LM implementation of the batched leg (pmv_set_ba_mode): 0 = the launch chain the "
                     "single-sequence legs use (default; measured faster: 56.2k vs 53.1k frames/s at B=192), 1 = one workgroup per solve, ONE launch per round")
     ap.add_argument("--batch-distinct", type=int, default=16, help="distinct sequences (4 seeds x start offsets) cycled over the B slots of the batched leg")
-    ap.add_argument("--batch-contexts", type=int, default=0, help="diagnostic: also run the round-1 form (B contexts x 2 host threads x 2 streams)")
+    ap.add_argument("--batch-contexts", type=int, default=0, help="diagnostic, with --full: also run the round-1 form (B contexts x 2 host threads x 2 streams)")
     ap.add_argument("--no-hbm-leg", action="store_true", help="skip the hbm_resident leg (frames already staged in HBM)")
     ap.add_argument("--no-cpu-multi", action="store_true", help="skip the same-cores multi-sequence CPU baseline of the batched leg")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel tables and rooflines, the hbm_resident and batched legs, the CPU "
+                                                        "baselines and the trajectory checks (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -278,11 +293,11 @@ def main():
                 r_.free()
         return el, total, kept[-1]
 
-    # ---- warm-up; the per-kernel HIP-event table is taken in the LAST warm-up step (two events per launch cost host time and a
-    # queue barrier, ~7000 per step), the timed region records only the critical-path kernel whose live average `roofline` reports
+    # ---- warm-up; with --full the per-kernel HIP-event table is taken in the LAST warm-up step (two events per launch cost host time
+    # and a queue barrier, ~7000 per step), the timed region records only the critical-path kernel whose live average `roofline` reports
     prof_warm, lk_work = None, None
     for i in range(args.warmup):
-        last = i == args.warmup - 1
+        last = args.full and i == args.warmup - 1
         if last:
             ctx.prof_enable(True)
             ctx.lk_counters(reset=True)
@@ -296,7 +311,7 @@ def main():
             r_.free()
     # second diagnostic pass: the kernels INSIDE the LM launch chain, one by one (their events lengthen the chain, so separately)
     prof_chain = None
-    if args.warmup > 0 and not multi:
+    if args.full and args.warmup > 0 and not multi:
         ctx.prof_enable(True)
         ctx.prof_select(["k_bam_eval0", "k_bam_campoint", "k_bam_gemm", "k_bam_solve", "k_bam_backsub", "k_bam_finish"])
         rs_ = step()
@@ -316,7 +331,8 @@ def main():
             if k_ in backend_kernels:
                 cand[k_] = v
     dom = max(cand.items(), key=lambda kv: kv[1][1])[0] if cand else None
-    ctx.prof_enable(True)
+    if args.full:
+        ctx.prof_enable(True)
     if dom:
         ctx.prof_select([dom] if not dom.startswith("k_bam_") else ["k_pnp_hyp"])   # never lengthen the timed chain with in-chain events
         dom_timed = dom if not dom.startswith("k_bam_") else "k_pnp_hyp"
@@ -325,11 +341,19 @@ def main():
     # headline: §8d's timed region - gray frames in host memory -> poses on the host (one sequence: streamed ingest; several
     # (sub)sequences per rank: frames staged beforehand, the line says so)
     elapsed, frames_total, last_res = timed(host=not multi)
-    ctx.prof_enable(False)
-    prof_timed = ctx.prof_read()
+    prof_timed = {}
+    if args.full:
+        ctx.prof_enable(False)
+        prof_timed = ctx.prof_read()
     res = last_res[0]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "poses.npy"), np.concatenate([r_.poses for r_ in last_res]))
+        np.save(os.path.join(args.dump_outputs, "pose_counts.npy"), np.array([len(r_.poses) for r_ in last_res], np.float64))
+        for k_ in DUMP_STATS:
+            np.save(os.path.join(args.dump_outputs, f"stat_{k_}.npy"), np.array([r_.stats[k_] for r_ in last_res], np.float64))
     hbm_leg = None
-    if not args.no_hbm_leg and not multi:
+    if args.full and not args.no_hbm_leg and not multi:
         el_h, tot_h, last_h = timed(host=False)
         if rank == 0:
             same = all(np.array_equal(a.poses, b.poses) for a, b in zip(last_h, last_res))
@@ -351,7 +375,7 @@ def main():
     # ---- batched leg, on EVERY rank: B independent, DISTINCT sequences per GPU through batched launches -----------
     batched = None
     bat_local = None
-    if args.batch > 1 and args.config == 1 and not kroot:
+    if args.full and args.batch > 1 and args.config == 1 and not kroot:
         B = args.batch
         n = args.frames or cfg["n_frames"]
         D = max(1, min(args.batch_distinct, B))
@@ -510,99 +534,100 @@ def main():
         return
 
     # ---- per-stage roofline entries ----------------------------------------------------------------------------
-    prof = dict(prof_warm or {})
-    prof.update(prof_chain or {})
-    prof.update({k_: v for k_, v in prof_timed.items()})
-    kern = {k_: dict(launches=v[0], total_ms=round(v[1], 4), avg_us=round(v[1] / v[0] * 1e3, 3), max_us=round(v[2] * 1e3, 3)) for k_, v in prof.items()}
-    levels = pyramid_levels(w, h)
-    pyr_px = sum(a * b for a, b in levels)
-    lk_n = st_sum["lk_points"] / max(st_sum["lk_calls"], 1)
-    pnp_m = st_sum["pnp_points"] / max(st_sum["pnp_calls"], 1)
-    ba_obs = st_sum["ba_obs"] / max(st_sum["ba_calls"], 1)
-    ba_pts = st_sum["ba_points"] / max(st_sum["ba_calls"], 1)
-    nc = min(cfg["bundle_size"], 32)
-    traffic_db = {}
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):   # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
-        with open(tpath) as f:
-            traffic_db = json.load(f)
+    if args.full:
+        prof = dict(prof_warm or {})
+        prof.update(prof_chain or {})
+        prof.update({k_: v for k_, v in prof_timed.items()})
+        kern = {k_: dict(launches=v[0], total_ms=round(v[1], 4), avg_us=round(v[1] / v[0] * 1e3, 3), max_us=round(v[2] * 1e3, 3)) for k_, v in prof.items()}
+        levels = pyramid_levels(w, h)
+        pyr_px = sum(a * b for a, b in levels)
+        lk_n = st_sum["lk_points"] / max(st_sum["lk_calls"], 1)
+        pnp_m = st_sum["pnp_points"] / max(st_sum["pnp_calls"], 1)
+        ba_obs = st_sum["ba_obs"] / max(st_sum["ba_calls"], 1)
+        ba_pts = st_sum["ba_points"] / max(st_sum["ba_calls"], 1)
+        nc = min(cfg["bundle_size"], 32)
+        traffic_db = {}
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):   # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
+            with open(tpath) as f:
+                traffic_db = json.load(f)
 
-    def avg_s(name):
-        return prof[name][1] / prof[name][0] * 1e-3 if name in prof and prof[name][0] else None
+        def avg_s(name):
+            return prof[name][1] / prof[name][0] * 1e-3 if name in prof and prof[name][0] else None
 
-    def entry(kernel, bound, work, peak, unit, note, extra=None):
-        t = avg_s(kernel)
-        if t is None:
-            return None
-        ach = work / t / (1e9 if unit == "GB/s" else 1e12)
-        tj = traffic_db.get("kernels", {}).get(kernel, {}) if traffic_db.get("config") == args.config else {}
-        e = dict(kernel=kernel, bound=bound, achieved=round(ach, 5), peak=peak, unit=unit, frac=ach / peak, avg_launch_us=round(t * 1e6, 3),
-                 algorithmic_per_launch=round(work, 1), traffic=tj.get("hbm_bytes_per_launch"), note=note)
-        if extra:
-            e.update(extra)
-        return e
+        def entry(kernel, bound, work, peak, unit, note, extra=None):
+            t = avg_s(kernel)
+            if t is None:
+                return None
+            ach = work / t / (1e9 if unit == "GB/s" else 1e12)
+            tj = traffic_db.get("kernels", {}).get(kernel, {}) if traffic_db.get("config") == args.config else {}
+            e = dict(kernel=kernel, bound=bound, achieved=round(ach, 5), peak=peak, unit=unit, frac=ach / peak, avg_launch_us=round(t * 1e6, 3),
+                     algorithmic_per_launch=round(work, 1), traffic=tj.get("hbm_bytes_per_launch"), note=note)
+            if extra:
+                e.update(extra)
+            return e
 
-    stages = []
-    # pyramid (HBM streaming stencil): 2.64*W*H per frame = read L0..L-1 + write padded L0..L; all n frames per launch set
-    pad_bytes = sum((a + 128) * (b + 128) for a, b in levels)
-    # (§8d counts the gray image once: write L0 + read L0..L-1 + write L1..L = 2.64 W*H; the kernels also read the tight gray copy)
-    pyr_alg = (w * h + sum(a * b for a, b in levels[:-1]) + sum(a * b for a, b in levels[1:])) * float(n0)
-    t_pyr = sum(prof[k_][1] for k_ in ("k_pad_level0", "k_pyrdown") if k_ in prof) * 1e-3 / max(1, prof.get("k_pad_level0", (1,))[0])
-    if t_pyr > 0 and not multi:
-        stages.append(dict(kernel="k_pad_level0+k_pyrdown", bound="hbm", achieved=round(pyr_alg / t_pyr / 1e9, 3), peak=PEAK_HBM_GBS, unit="GB/s",
-                           frac=pyr_alg / t_pyr / 1e9 / PEAK_HBM_GBS, avg_launch_us=round(t_pyr * 1e6, 1), algorithmic_per_launch=round(pyr_alg, 1),
-                           traffic=None, note=f"all {n0} frames per launch set; writes incl. the 64-px padding are {pad_bytes * n0} B"))
-    # k_lk: HBM view (both pyramids once + 13 B per track) and the VALU-integer view with MEASURED iteration counts (OPS_lk, §8d)
-    stages.append(entry("k_lk", "hbm", 2.0 * pyr_px + 13.0 * lk_n, PEAK_HBM_GBS, "GB/s",
-                        "latency-bound: one frame's tracks depend on the previous frame's result, ~300 blocks in flight; a launch ends with its slowest track"))
-    if lk_work and lk_work[2]:
-        it, lev, trk = lk_work
-        ops_per_launch = 1024.0 * (40.0 * lev + 14.0 * it) / max(1, prof.get("k_lk", (1,))[0])
-        e = entry("k_lk", "valu-int", ops_per_launch, PEAK_VALU_TOPS, "Top/s", "OPS_lk = sum over tracks and levels of 1024*(40 + 14*iterations), iterations measured in-kernel",
-                  dict(iterations_per_level_pass=round(it / max(lev, 1), 2), level_passes_per_track=round(lev / max(trk, 1), 2)))
-        if e:
-            stages.append(e)
-    # detectors: §8d's B_det = W*H read + 8 B per corner written, per launch over the whole grid (what a fused pass moves)
-    b_det = float(w * h) + 8.0 * cfg["min_tracked"]
-    for k_ in ("k_gftt_cand", "k_gftt_pick"):
-        stages.append(entry(k_, "hbm", b_det, PEAK_HBM_GBS, "GB/s", "B_det = W*H + 8 B/corner for the whole detector pass; every kernel of the pass is booked against it"))
-    # PnP: FP64 VALU work of §8d, F_pnp = 40*iters*M + iters*EPnP(15 kflop), all of it in k_pnp_hyp (one wavefront per hypothesis)
-    f_pnp = 40.0 * PNP_ITERS * pnp_m + PNP_ITERS * EPNP_FLOP
-    stages.append(entry("k_pnp_hyp", "valu-f64", f_pnp, PEAK_FP64_VALU_TFLOPS, "TFLOP/s",
-                        f"latency: serial FP64 algebra of 5-point EPnP (12x12 Jacobi, pseudo-inverses, Gauss-Newton), one wavefront per hypothesis; "
-                        f"F_pnp = 40*{PNP_ITERS}*M + {PNP_ITERS}*15e3 flop with M = {pnp_m:.0f}"))
-    stages.append(entry("k_pnp_select_refit", "valu-f64", 20 * 2.0 * 12 * 12 * pnp_m, PEAK_FP64_VALU_TFLOPS, "TFLOP/s",
-                        "latency: sequential LM passes of the refit (<= 20 x J^T J over the inliers, 2*12*12 flop per point and pass)"))
-    stages.append(entry("k_tri_dlt", "hbm", (33.0 + 132.0) * 1.5 * cfg["min_tracked"], PEAK_HBM_GBS, "GB/s", "one thread per (candidate, correspondence)"))
-    # BA: FP64 MFMA flops of the two matrix kernels; F_schur = 2*(6 nc)^2 * 3P (§8d), camera blocks U_c = F^T F: 2 * 8^2 * 2*obs (padded 6+rhs -> 8)
-    stages.append(entry("k_bam_gemm", "mfma", 2.0 * (6 * nc) * (6 * nc + 1) * 3.0 * ba_pts, PEAK_FP64_MFMA_TFLOPS, "TFLOP/s",
-                        f"Schur contraction S -= Y W^T on v_mfma_f64_16x16x4_f64: 2*(6nc)(6nc+1)*3P with nc={nc}, P={ba_pts:.0f} (avg)"))
-    stages.append(entry("k_bam_campoint", "mfma", 2.0 * 7 * 7 * 2.0 * ba_obs, PEAK_FP64_MFMA_TFLOPS, "TFLOP/s",
-                        "camera blocks U_c | rhs_c = F^T F on FP64 MFMA + per-point E, E^-1, W, Y on VALU"))
-    stages.append(entry("k_bam_solve", "hbm", 8.0 * ((6 * nc) ** 2 + 6 * nc), PEAK_HBM_GBS, "GB/s", "latency: blocked Cholesky of the reduced camera system in LDS, one workgroup"))
-    stages.append(entry("k_bam_backsub", "hbm", 96.0 * ba_obs, PEAK_HBM_GBS, "GB/s", "per point back-substitution + r, J at the candidate (B_ba = 96 B per observation)"))
-    stages.append(entry("ba_lm_chain", "hbm", 96.0 * ba_obs * BA_ITERATIONS, PEAK_HBM_GBS, "GB/s", "the whole LM launch chain of one solve (not a single kernel)"))
-    stages = [e for e in stages if e]
-    roofline = None
-    if dom:
-        roofline = next((dict(e) for e in stages if e["kernel"] == (dom_timed or dom) and e["bound"] in ("hbm", "mfma", "valu-f64")), None)
-        if roofline:
-            roofline["chosen_by"] = "largest single-kernel time on the critical path (back-end chain); candidates measured in the last warm-up step: " + \
-                ", ".join(f"{k_} {cand[k_][1]:.1f} ms" for k_ in sorted(cand, key=lambda x: -cand[x][1])[:4])
-            roofline["measured_in"] = "timed region (HIP events on the launching stream)" if (dom_timed or dom) in prof_timed else "last warm-up step"
-            roofline["traffic_source"] = traffic_db.get("source")
-    # §8d: frame-rate roofline fraction = sum over stages (algorithmic bytes or flops / peak) / measured time, per step of this rank
-    stage_s = stage_roofline_seconds(cfg, w, h, st_sum, lk_work, float(sum(f.shape[0] for f, _ in data)))
-    step_s = ms_per_step * 1e-3
-    frame_rate_roofline = dict(single=dict(frac=sum(stage_s.values()) / step_s, stage_seconds={k_: round(v, 6) for k_, v in stage_s.items()},
-                                           measured_seconds_per_step=round(step_s, 5)),
-                               batched=batched["frame_rate_roofline"] if batched else None,
-                               definition="SURVEY.md §8d: sum over stages of (algorithmic bytes or flops / the peak that bounds the stage: HBM 8 TB/s, integer VALU "
-                                          "78.6 Top/s with measured LK iterations, FP32 VALU 157.3 TFLOP/s, FP64 78.6 TFLOP/s) / measured time of the pass")
+        stages = []
+        # pyramid (HBM streaming stencil): 2.64*W*H per frame = read L0..L-1 + write padded L0..L; all n frames per launch set
+        pad_bytes = sum((a + 128) * (b + 128) for a, b in levels)
+        # (§8d counts the gray image once: write L0 + read L0..L-1 + write L1..L = 2.64 W*H; the kernels also read the tight gray copy)
+        pyr_alg = (w * h + sum(a * b for a, b in levels[:-1]) + sum(a * b for a, b in levels[1:])) * float(n0)
+        t_pyr = sum(prof[k_][1] for k_ in ("k_pad_level0", "k_pyrdown") if k_ in prof) * 1e-3 / max(1, prof.get("k_pad_level0", (1,))[0])
+        if t_pyr > 0 and not multi:
+            stages.append(dict(kernel="k_pad_level0+k_pyrdown", bound="hbm", achieved=round(pyr_alg / t_pyr / 1e9, 3), peak=PEAK_HBM_GBS, unit="GB/s",
+                               frac=pyr_alg / t_pyr / 1e9 / PEAK_HBM_GBS, avg_launch_us=round(t_pyr * 1e6, 1), algorithmic_per_launch=round(pyr_alg, 1),
+                               traffic=None, note=f"all {n0} frames per launch set; writes incl. the 64-px padding are {pad_bytes * n0} B"))
+        # k_lk: HBM view (both pyramids once + 13 B per track) and the VALU-integer view with MEASURED iteration counts (OPS_lk, §8d)
+        stages.append(entry("k_lk", "hbm", 2.0 * pyr_px + 13.0 * lk_n, PEAK_HBM_GBS, "GB/s",
+                            "latency-bound: one frame's tracks depend on the previous frame's result, ~300 blocks in flight; a launch ends with its slowest track"))
+        if lk_work and lk_work[2]:
+            it, lev, trk = lk_work
+            ops_per_launch = 1024.0 * (40.0 * lev + 14.0 * it) / max(1, prof.get("k_lk", (1,))[0])
+            e = entry("k_lk", "valu-int", ops_per_launch, PEAK_VALU_TOPS, "Top/s", "OPS_lk = sum over tracks and levels of 1024*(40 + 14*iterations), iterations measured in-kernel",
+                      dict(iterations_per_level_pass=round(it / max(lev, 1), 2), level_passes_per_track=round(lev / max(trk, 1), 2)))
+            if e:
+                stages.append(e)
+        # detectors: §8d's B_det = W*H read + 8 B per corner written, per launch over the whole grid (what a fused pass moves)
+        b_det = float(w * h) + 8.0 * cfg["min_tracked"]
+        for k_ in ("k_gftt_cand", "k_gftt_pick"):
+            stages.append(entry(k_, "hbm", b_det, PEAK_HBM_GBS, "GB/s", "B_det = W*H + 8 B/corner for the whole detector pass; every kernel of the pass is booked against it"))
+        # PnP: FP64 VALU work of §8d, F_pnp = 40*iters*M + iters*EPnP(15 kflop), all of it in k_pnp_hyp (one wavefront per hypothesis)
+        f_pnp = 40.0 * PNP_ITERS * pnp_m + PNP_ITERS * EPNP_FLOP
+        stages.append(entry("k_pnp_hyp", "valu-f64", f_pnp, PEAK_FP64_VALU_TFLOPS, "TFLOP/s",
+                            f"latency: serial FP64 algebra of 5-point EPnP (12x12 Jacobi, pseudo-inverses, Gauss-Newton), one wavefront per hypothesis; "
+                            f"F_pnp = 40*{PNP_ITERS}*M + {PNP_ITERS}*15e3 flop with M = {pnp_m:.0f}"))
+        stages.append(entry("k_pnp_select_refit", "valu-f64", 20 * 2.0 * 12 * 12 * pnp_m, PEAK_FP64_VALU_TFLOPS, "TFLOP/s",
+                            "latency: sequential LM passes of the refit (<= 20 x J^T J over the inliers, 2*12*12 flop per point and pass)"))
+        stages.append(entry("k_tri_dlt", "hbm", (33.0 + 132.0) * 1.5 * cfg["min_tracked"], PEAK_HBM_GBS, "GB/s", "one thread per (candidate, correspondence)"))
+        # BA: FP64 MFMA flops of the two matrix kernels; F_schur = 2*(6 nc)^2 * 3P (§8d), camera blocks U_c = F^T F: 2 * 8^2 * 2*obs (padded 6+rhs -> 8)
+        stages.append(entry("k_bam_gemm", "mfma", 2.0 * (6 * nc) * (6 * nc + 1) * 3.0 * ba_pts, PEAK_FP64_MFMA_TFLOPS, "TFLOP/s",
+                            f"Schur contraction S -= Y W^T on v_mfma_f64_16x16x4_f64: 2*(6nc)(6nc+1)*3P with nc={nc}, P={ba_pts:.0f} (avg)"))
+        stages.append(entry("k_bam_campoint", "mfma", 2.0 * 7 * 7 * 2.0 * ba_obs, PEAK_FP64_MFMA_TFLOPS, "TFLOP/s",
+                            "camera blocks U_c | rhs_c = F^T F on FP64 MFMA + per-point E, E^-1, W, Y on VALU"))
+        stages.append(entry("k_bam_solve", "hbm", 8.0 * ((6 * nc) ** 2 + 6 * nc), PEAK_HBM_GBS, "GB/s", "latency: blocked Cholesky of the reduced camera system in LDS, one workgroup"))
+        stages.append(entry("k_bam_backsub", "hbm", 96.0 * ba_obs, PEAK_HBM_GBS, "GB/s", "per point back-substitution + r, J at the candidate (B_ba = 96 B per observation)"))
+        stages.append(entry("ba_lm_chain", "hbm", 96.0 * ba_obs * BA_ITERATIONS, PEAK_HBM_GBS, "GB/s", "the whole LM launch chain of one solve (not a single kernel)"))
+        stages = [e for e in stages if e]
+        roofline = None
+        if dom:
+            roofline = next((dict(e) for e in stages if e["kernel"] == (dom_timed or dom) and e["bound"] in ("hbm", "mfma", "valu-f64")), None)
+            if roofline:
+                roofline["chosen_by"] = "largest single-kernel time on the critical path (back-end chain); candidates measured in the last warm-up step: " + \
+                    ", ".join(f"{k_} {cand[k_][1]:.1f} ms" for k_ in sorted(cand, key=lambda x: -cand[x][1])[:4])
+                roofline["measured_in"] = "timed region (HIP events on the launching stream)" if (dom_timed or dom) in prof_timed else "last warm-up step"
+                roofline["traffic_source"] = traffic_db.get("source")
+        # §8d: frame-rate roofline fraction = sum over stages (algorithmic bytes or flops / peak) / measured time, per step of this rank
+        stage_s = stage_roofline_seconds(cfg, w, h, st_sum, lk_work, float(sum(f.shape[0] for f, _ in data)))
+        step_s = ms_per_step * 1e-3
+        frame_rate_roofline = dict(single=dict(frac=sum(stage_s.values()) / step_s, stage_seconds={k_: round(v, 6) for k_, v in stage_s.items()},
+                                               measured_seconds_per_step=round(step_s, 5)),
+                                   batched=batched["frame_rate_roofline"] if batched else None,
+                                   definition="SURVEY.md §8d: sum over stages of (algorithmic bytes or flops / the peak that bounds the stage: HBM 8 TB/s, integer VALU "
+                                              "78.6 Top/s with measured LK iterations, FP32 VALU 157.3 TFLOP/s, FP64 78.6 TFLOP/s) / measured time of the pass")
 
     # ---- CPU baseline: the oracle pipeline, speed-oriented build (same results), on the GPU box's host cores -------------------
     cpu = None
-    if args.cpu_seconds > 0 and world == 1 and not multi:
+    if args.full and args.cpu_seconds > 0 and world == 1 and not multi:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import orc_binding as ob
         frames, gt = data[0]
@@ -642,7 +667,7 @@ def main():
             best = max(legs, key=lambda k_: legs[k_]["value"])
             batched["cpu_baseline_same_cores"].update(value=legs[best]["value"], best=best)
 
-    if args.batch_contexts > 1 and world == 1 and args.config == 1:
+    if args.full and args.batch_contexts > 1 and world == 1 and args.config == 1:
         B = args.batch_contexts
         frames, gt = data[0]
         n = frames.shape[0]
@@ -679,15 +704,6 @@ def main():
         for c in bctx[1:]:
             c.close()
 
-    # trajectory sanity vs synthetic ground truth (z flipped: the pipeline's forward axis is -z, quirk Q14)
-    gt0 = data[0][1]
-    off = int(st["init_offset"])
-    est = res.poses[:, 9:12]
-    Rg0 = gt0[off].reshape(3, 4)[:, :3]
-    g = (gt0[off: off + len(est), [3, 7, 11]] - gt0[off, [3, 7, 11]]) @ Rg0   # in the first frame's axes (a subsequence starts anywhere on the route)
-    g = g * np.array([1, 1, -1])
-    terr = np.linalg.norm(est - g, axis=1)
-
     what = "synthetic KITTI-like" if data_kind == "synthetic" else "KITTI " + args.kitti_seq
     if args.config == 5:
         n_pieces = len(pieces_all)
@@ -701,38 +717,49 @@ def main():
         "metric": "VO frames/sec on 1241x376 KITTI mono @400 tracks, bundle=5",
         "value": round(value, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "u8/int32 front-end, f64 back-end", "data": data_kind,
+        "dtype": "u8/int32 front-end, f64 back-end", "data": data_kind, "full": args.full,
         "config": {"workload": workload, "frames_per_step": frames_per_step, "pipeline_seconds_last_step": round(st["seconds"], 4),
                    "host_threads": 1 if args.sequential else 2 + (tri_threads - 1)},
-        "roofline": roofline,
-        "rooflines": stages,
-        "frame_rate_roofline": frame_rate_roofline,
-        "cpu_baseline": cpu,
-        "batched": batched,
-        "hbm_resident": hbm_leg,
         "timed_region": "SURVEY.md §8d: K x pmv_pipeline_run_streamed - decoded gray frames in pageable HOST memory -> pinned ring -> HBM on an ingest thread + "
                         "third stream, pyramids per 16-frame chunk, front-end + back-end, all poses back on the host (`hbm_resident`: the same K steps "
                         "from frames staged in HBM beforehand); freeing the native result objects (host containers, ~40 ms per run) happens after the "
                         "timed region for the GPU and is excluded from the CPU baseline too",
-        "kernels": kern, "kernels_measured_in": "all classes: last warm-up step; k_bam_*: separate diagnostic pass; " + (f"{dom_timed}: timed region" if dom_timed else ""),
         "pipeline_stats": {k_: st_sum[k_] for k_ in ("lk_calls", "lk_points", "detect_calls", "pnp_calls", "pnp_points", "tri_calls", "ba_calls",
                                                      "ba_obs", "ba_points", "heuristic_motion", "n_landmarks")},
         "host_stage_seconds_per_step": {k_: round(st_sum[k_], 4) for k_ in ("t_lk", "t_detect", "t_pnp", "t_tri", "t_ba", "t_pnp_kernel", "t_ba_kernel",
                                                                                "t_tri_essential", "t_tri_pose", "tri_hypotheses", "tri_ahead")},
-        "trajectory_error_m": {"mean": round(float(terr.mean()), 3), "max": round(float(terr.max()), 3),
-                               "travelled": round(float(np.linalg.norm(g[-1])), 1), "of": "rank 0's first (sub)sequence"},
         "input_generation_s": round(t_gen, 2),
     }
-    if cpu:
-        out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 2)
-    if batched and "cpu_baseline_same_cores" in batched:
-        # like for like: B sequences on the GPU + its 16 host CPUs against sequences side by side on the same 16 CPUs
-        out["batched_speedup_vs_cpu_same_cores"] = round(batched["per_gpu"] / batched["cpu_baseline_same_cores"]["value"], 2)
     if args.config != 1 or args.frames:
         out["note"] = "not the metric configuration: this line is a diagnostic for the named workload"
     kitti_mod = importlib.import_module("practical-multi-view_amd.kitti")
-    if args.config != 5:
-        out["reference_error_report"] = {k_: round(v, 4) for k_, v in kitti_mod.error_report(res.poses, gt0, off).items()}   # OdometryPipeline.cpp:267-296
+    if args.full:
+        # trajectory sanity vs synthetic ground truth (z flipped: the pipeline's forward axis is -z, quirk Q14)
+        gt0 = data[0][1]
+        off = int(st["init_offset"])
+        est = res.poses[:, 9:12]
+        Rg0 = gt0[off].reshape(3, 4)[:, :3]
+        g = (gt0[off: off + len(est), [3, 7, 11]] - gt0[off, [3, 7, 11]]) @ Rg0   # in the first frame's axes (a subsequence starts anywhere on the route)
+        g = g * np.array([1, 1, -1])
+        terr = np.linalg.norm(est - g, axis=1)
+        out.update({
+            "roofline": roofline,
+            "rooflines": stages,
+            "frame_rate_roofline": frame_rate_roofline,
+            "cpu_baseline": cpu,
+            "batched": batched,
+            "hbm_resident": hbm_leg,
+            "kernels": kern, "kernels_measured_in": "all classes: last warm-up step; k_bam_*: separate diagnostic pass; " + (f"{dom_timed}: timed region" if dom_timed else ""),
+            "trajectory_error_m": {"mean": round(float(terr.mean()), 3), "max": round(float(terr.max()), 3),
+                                   "travelled": round(float(np.linalg.norm(g[-1])), 1), "of": "rank 0's first (sub)sequence"},
+        })
+        if cpu:
+            out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 2)
+        if batched and "cpu_baseline_same_cores" in batched:
+            # like for like: B sequences on the GPU + its 16 host CPUs against sequences side by side on the same 16 CPUs
+            out["batched_speedup_vs_cpu_same_cores"] = round(batched["per_gpu"] / batched["cpu_baseline_same_cores"]["value"], 2)
+        if args.config != 5:
+            out["reference_error_report"] = {k_: round(v, 4) for k_, v in kitti_mod.error_report(res.poses, gt0, off).items()}   # OdometryPipeline.cpp:267-296
     if args.poses_out:
         kitti_mod.write_poses_kitti(args.poses_out, res.poses)
     print(json.dumps(out))

@@ -1,6 +1,6 @@
 """Per-kernel SQ counters (MFMA use, LDS bank conflicts) from one rocprofv3 --pmc pass:
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT \
-              SQ_ACTIVE_INST_LDS SQ_INSTS_VALU -d <dir> -o s --output-format csv -- python3 bench.py ...
+              SQ_ACTIVE_INST_LDS SQ_INSTS_VALU -d <dir> -o s --output-format csv -- python3 bench.py --full ...
 usage: python scripts/pmc_sq.py <counter_collection.csv> <out csv>"""
 import csv, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float))

@@ -1,7 +1,7 @@
 """HBM traffic per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs, see
 /opt/skills/guides/MI355X_MICROARCH.md 'HBM' and 'rocprofv3 PMC slots'):
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o f --output-format csv -- python3 bench.py ... --frames 300
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_write -o w --output-format csv -- python3 bench.py ... --frames 300
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir>/pmc_fetch -o f --output-format csv -- python3 bench.py --full ... --frames 300
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir>/pmc_write -o w --output-format csv -- python3 bench.py --full ... --frames 300
 FETCH_SIZE / WRITE_SIZE are in KiB (TCC_EA0 request counters x 64 B / 1024); on gfx950 FETCH_SIZE counts 128-B requests as
 64 B, so it is doubled. Writes profiles/pmc_traffic.json + a per-kernel CSV summary.
 usage: python scripts/pmc_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> <out json> <out csv> <note> [bench config, default 1]"""
