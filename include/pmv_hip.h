@@ -243,6 +243,34 @@ int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, c
  * thread (one HIP stream each); the combiners are the only threads that talk to the HIP runtime. out[b] is bit-identical to the same sequence's own pmv_pipeline_run. */
 int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                            const int* first_slot, pmv_pipeline_result** out);
+/* The same B sequences streamed from HOST memory through recycled frame slots (the reference loads one image per front-end iteration,
+ * Frame.cpp:31-42, OdometryPipeline.cpp:212-229, and tracking reads only frames k-1 and k), so that the batch size is not capped by frame
+ * storage: B x ring slots instead of the sum of all n_frames.
+ *   Frames: sequence b's params[b].n_frames tightly packed gray frames at host_frames[b], pageable or pinned / registered; read only, several
+ *     b may point at the same buffer; they stay valid until the call returns. A kernel never reads a pageable address: pinned memory
+ *     mapped at its host address (hipHostMalloc, torch pin_memory) is read in place, anything else is copied into pinned staging first.
+ *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot
+ *     first_slot[b] + f % ring. After the call each ring slot holds the last frame that went through it, pyramid built.
+ *   Shared rules: one frame size for all sequences; build_pyramids is ignored (an ingest thread builds every frame as it lands); the
+ *     parameters are validated as in pmv_pipeline_run_batch (LK with GFTT or ShiTomasi, bundle limits).
+ *   Minimum ring: ring >= init_frames + 1. initialise() holds frames 0 .. init_frames - 1 (OdometryPipeline.cpp:428-482), and the first
+ *     addFrame may need frame init_frames while frame init_offset is still live. A smaller ring is PMV_ERR_INVALID.
+ *   Release rule: once addFrame(image i) (OdometryPipeline.cpp:329-374) has returned, every frame below i is dead - addFrame(i + 1) reads
+ *     frames i (LK and the re-detection on the previous frame's cells) and i + 1 only - and its slot may be refilled. A sequence that
+ *     finishes or fails frees its whole ring.
+ *   Errors: a slot range outside n_slots is PMV_ERR_CAPACITY, overlapping ranges PMV_ERR_INVALID; a call while a pmv_frames_stream_begin
+ *     bracket is open on the context is PMV_ERR_INVALID (the call owns the context until it returns, so the reverse cannot arise).
+ *   Result: out[b] is bit-identical to the same sequence's pmv_pipeline_run_batch on staged frames and to its own pmv_pipeline_run: poses,
+ *     per-frame features and landmark ids, and every count of the statistics.
+ * Memory besides the rings: 4 pinned staging buffers of up to 64 frames (<= 32 MB) each; with PMV_BATCH_INGEST=copy as many HBM landing
+ * buffers. pmv_frames_stream_begin's landing area is not used. */
+int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
+                                    const uint8_t* const* host_frames, const int* first_slot, int ring, pmv_pipeline_result** out);
+/* Ingest counters of the last pmv_pipeline_run_batch_streamed call: writes PMV_BATCH_INGEST_STATS (= 6) doubles to out and returns that
+ * count (out = NULL: only the count, ctx may be NULL too): [0] ingest rounds [1] frames [2] bytes moved from host memory [3] seconds of host memcpy into the staging buffers
+ * [4] seconds the ingest thread waited for ring room [5] seconds the sequence threads waited for frames (summed over the threads). */
+#define PMV_BATCH_INGEST_STATS 6
+int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out);
 /* diagnostic, per combiner in the order LK, detectors, PnP, BA, DLT: counts10 = {launch rounds, requests served} x 5; times15 (may
  * be NULL) = seconds spent {CPU time of the combiner thread, wall time processing batches, of that waiting for the GPU} x 5 */
 int pmv_batch_stats(pmv_ctx* ctx, long long* counts10, double* times15);

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "pmv_lk_track", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
-    "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_batch_stats", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
+    "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
     "pmv_pipeline_frame_feature_count", "pmv_pipeline_get_frame_features", "pmv_pipeline_stats_count", "pmv_pipeline_get_stats",
 ]
 
@@ -57,6 +57,36 @@ class PipelineParams(C.Structure):
 STAT_KEYS = ["lk_calls", "lk_points", "detect_calls", "pnp_calls", "pnp_points", "tri_calls", "ba_calls", "ba_obs",
              "ba_points", "heuristic_motion", "seconds", "init_offset", "n_landmarks", "scale", "t_lk", "t_detect", "t_pnp", "t_tri",
              "t_ba", "t_pnp_kernel", "t_ba_kernel", "t_tri_essential", "t_tri_pose", "tri_hypotheses", "tri_ahead"]
+
+
+BATCH_INGEST_KEYS = ["rounds", "frames", "bytes", "memcpy_s", "ingest_wait_s", "seq_wait_s"]   # pmv_batch_ingest_stats, in order
+
+
+def _batch_streamed_args(seqs, w, h, ring, first_slot):
+    """shapes of pipeline_run_batch_streamed's arguments, checked before anything reaches the device: (frames, gt_poses, first_slot)"""
+    if len(seqs) < 1:
+        raise ValueError("pipeline_run_batch_streamed: no sequences")
+    if int(ring) != ring or ring < 1:
+        raise ValueError(f"pipeline_run_batch_streamed: ring must be a positive integer, got {ring!r}")
+    frames, gts = [], []
+    for b, seq in enumerate(seqs):
+        if len(seq) != 2:
+            raise ValueError(f"pipeline_run_batch_streamed: sequence {b} must be (frames, gt_poses)")
+        f, gt = seq
+        f = np.asarray(f)
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[1:] != (h, w):
+            raise ValueError(f"pipeline_run_batch_streamed: sequence {b}: frames must be (n, {h}, {w}) uint8, got {f.shape} {f.dtype}")
+        f = np.ascontiguousarray(f)   # (a contiguous array, pinned or not, is passed as it is)
+        g = np.ascontiguousarray(gt, np.float64)
+        if g.size != 12 * f.shape[0]:
+            raise ValueError(f"pipeline_run_batch_streamed: sequence {b}: {f.shape[0]} frames but {g.size / 12:g} pose rows")
+        frames.append(f)
+        gts.append(g.reshape(f.shape[0], 12))
+    B = len(frames)
+    first = [b * int(ring) for b in range(B)] if first_slot is None else [int(v) for v in first_slot]
+    if len(first) != B:
+        raise ValueError(f"pipeline_run_batch_streamed: {len(first)} first slots for {B} sequences")
+    return frames, gts, first
 
 
 class PipelineResult:
@@ -528,6 +558,49 @@ class Context:
                 self.lib.pmv_pipeline_free(hnd)
             res.append(r)
         return res
+
+    def pipeline_run_batch_streamed(self, seqs, w, h, K, ring=16, first_slot=None, min_tracked=400, tol=150, init_frames=5, bundle_size=5,
+                                    ba_iterations=5, extractor=0, build_pyramids=1, want_features=True, defer_free=False, threaded=1,
+                                    device_fivepoint=0):
+        """B sequences streamed from host memory through rings of `ring` frame slots (pmv_pipeline_run_batch_streamed). seqs: list of
+        (frames (n, h, w) uint8, gt_poses (n, 12)); the frames are read where they are (numpy arrays, also over pinned memory such as a
+        torch pin_memory() tensor's .numpy(); several entries may share one array) and must stay alive during the call. first_slot:
+        sequence b's ring starts there (default b * ring). Other arguments as pipeline_run_batch; build_pyramids is ignored. Returns one
+        PipelineResult per sequence, bit-identical to pipeline_run_batch on the same frames staged."""
+        frames, gts, first = _batch_streamed_args(seqs, w, h, ring, first_slot)
+        B = len(frames)
+        params = (PipelineParams * B)()
+        gt_ptrs = (_f64p * B)()
+        src = (_u8p * B)()
+        fs = (C.c_int * B)(*first)
+        Kd = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (B, 9)))
+        for b in range(B):
+            params[b] = PipelineParams(frames[b].shape[0], w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor, threaded, 1,
+                                       build_pyramids, 0, device_fivepoint)
+            gt_ptrs[b] = _p(gts[b], _f64p)
+            src[b] = _p(frames[b], _u8p)
+        outs = (C.c_void_p * B)()
+        self.lib.pmv_pipeline_run_batch_streamed.argtypes = [C.c_void_p, C.c_int, C.POINTER(PipelineParams), _f64p, C.POINTER(_f64p),
+                                                             C.POINTER(_u8p), _i32p, C.c_int, C.POINTER(C.c_void_p)]
+        self._ck(self.lib.pmv_pipeline_run_batch_streamed(self.h, B, params, _p(Kd, _f64p), gt_ptrs, src, fs, int(ring), outs))
+        res = []
+        for b in range(B):
+            hnd = C.c_void_p(outs[b])
+            r = PipelineResult(self.lib, hnd, want_features)
+            if defer_free:
+                r._deferred = (self.lib, hnd)
+            else:
+                self.lib.pmv_pipeline_free(hnd)
+            res.append(r)
+        return res
+
+    def batch_ingest_stats(self):
+        """ingest counters of the last pipeline_run_batch_streamed call (include/pmv_hip.h, pmv_batch_ingest_stats)"""
+        self.lib.pmv_batch_ingest_stats.argtypes = [C.c_void_p, _f64p]
+        n = self.lib.pmv_batch_ingest_stats(None, None)   # the count the library writes
+        out = np.zeros(n, np.float64)
+        self._ck(min(self.lib.pmv_batch_ingest_stats(self.h, _p(out, _f64p)), 0))
+        return dict(zip(BATCH_INGEST_KEYS, [float(v) for v in out]))
 
     def batch_stats(self):
         """per combiner of the batch engine (lk, det, pnp, ba, dlt): launch rounds, requests served, CPU seconds of the thread, wall seconds processing batches / of that waiting for the GPU"""

@@ -47,12 +47,14 @@ struct LKReq : Req {
     uint8_t* iters_out = nullptr;   // optional: LK iterations each track took (the caller's ordering hint for its next request)
     std::vector<int> order;   // block -> track order of THIS request (local indices, -1 = padding), built by the caller
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
+    int ring_round = -1;      // streamed batch: the ingest round that builds the two frames (-1 = nothing to wait for)
 };
 struct DetReq : Req {
     int slot, n_cells, max_per_cell, unlimited;
     const int* cells; double quality, min_dist;
     int* out_xy; double* out_score; int* out_count;
     int cell_base = 0;
+    int ring_round = -1;      // as LKReq::ring_round
 };
 struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
@@ -159,6 +161,11 @@ struct BatchEngine {
     std::atomic<int> build_enqueued{0};     // rounds whose launches and event are in the stream
     std::atomic<int> build_error{0};
     std::thread build_thread;
+    // Streamed batch (pmv_pipeline_run_batch_streamed, set for the duration of the call): the combiner of a launch that reads ring slots makes
+    // its stream wait for the newest ingest round the launch needs (batch_ingest_wait_gpu); the callers have already waited on the host until
+    // that round was enqueued.
+    hipError_t (*ring_wait)(void*, hipStream_t, int) = nullptr;
+    void* ring_arg = nullptr;
 };
 
 namespace {
@@ -236,7 +243,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<LKReq*> lk;
     for (Req* r : batch) lk.push_back((LKReq*)r);
     // ---- LK: one launch for the tracks of every requesting sequence
-    int total_tracks = 0, total_blocks = 0, need_round = -1;
+    int total_tracks = 0, total_blocks = 0, need_round = -1, need_ring = -1;
     PyrLayout L{};
     bool have_L = false;
     // (a slot whose pyramid the background build has not reached yet is "staged": n_levels < 0; the launch below waits for its round)
@@ -254,9 +261,11 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         total_tracks += r->n;
         total_blocks += (int)r->order.size();
         if (!E->slot_round.empty()) need_round = std::max(need_round, std::max(E->slot_round[(size_t)r->prev_slot], E->slot_round[(size_t)r->next_slot]));
+        need_ring = std::max(need_ring, r->ring_round);
     }
     if (total_tracks > 0) {
         EK(wait_built(E, s, need_round));
+        if (need_ring >= 0 && E->ring_wait) EK(E->ring_wait(E->ring_arg, s, need_ring));
         if ((size_t)total_tracks > E->cap_tracks) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
         const size_t bytes = sizeof(LKBlock) * (size_t)total_blocks;
         EK(C.h_front.ensure(bytes + 64));
@@ -352,9 +361,11 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 }
         EK(hipMemsetAsync(C.d_flags, 0, 16, s));
         {
-            int need_round = -1;
+            int need_round = -1, need_ring = -1;
             if (!E->slot_round.empty()) for (DetReq* r : det) need_round = std::max(need_round, E->slot_round[(size_t)r->slot]);
+            for (DetReq* r : det) if (r->rc == PMV_OK) need_ring = std::max(need_ring, r->ring_round);
             EK(wait_built(E, s, need_round));
+            if (need_ring >= 0 && E->ring_wait) EK(E->ring_wait(E->ring_arg, s, need_ring));
         }
         size_t c0 = 0;
         char* hd = (char*)C.h_det.p;
@@ -733,6 +744,8 @@ int engine_build_end(BatchEngine* E) {
     return E->build_error.load() ? PMV_ERR_HIP : PMV_OK;
 }
 
+void engine_set_ring(BatchEngine* E, hipError_t (*wait)(void*, hipStream_t, int), void* arg) { E->ring_wait = wait; E->ring_arg = arg; }
+
 void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15) {
     for (int r = 0; r < 5; r++) {   // the five classes every run uses; the optional five-point class is reported separately
 
@@ -748,7 +761,7 @@ void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15) {
 
 // ---- request entry points (called from the sequences' own host threads) ---------------------------------------------------------
 int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* status, float* err,
-              const uint8_t* predicted_iters, uint8_t* iters_out) {
+              const uint8_t* predicted_iters, uint8_t* iters_out, int ring_round) {
     pmv_ctx* ctx = E->ctx;
     REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
     REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
@@ -756,6 +769,7 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
     LKReq r;
     r.kind = 0; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = out_xy; r.status = status; r.err_out = err;
     r.iters_out = iters_out;
+    r.ring_round = ring_round;
     if (E->lk_lpt) {
         // most expensive first: a counting sort on the predicted iteration count (255 .. 0), ties in track order
         r.order.resize((size_t)n);
@@ -780,7 +794,7 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
 }
 
 int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
-                  double* out_score, int* out_count) {
+                  double* out_score, int* out_count, int ring_round) {
     pmv_ctx* ctx = E->ctx;
     REQ(cells && out_xy && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "detect: bad argument");
     if (kind == 2 && max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
@@ -796,6 +810,7 @@ int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_ce
             PMV_ERR_INVALID, "detect: cell %d invalid", i);
     }
     r.quality = quality; r.min_dist = min_dist; r.out_xy = out_xy; r.out_score = out_score; r.out_count = out_count;
+    r.ring_round = ring_round;
     return submit(ctx, E->queue[R_DET], &r);
 }
 

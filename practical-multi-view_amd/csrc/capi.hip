@@ -138,6 +138,7 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     hipSetDevice(c->device);
     batch_engine_destroy(c);
     ingest_destroy(c);
+    batch_ingest_destroy(c);
     if (c->s_front) hipStreamSynchronize(c->s_front);
     if (c->s_back) hipStreamSynchronize(c->s_back);
     backend_destroy(c);

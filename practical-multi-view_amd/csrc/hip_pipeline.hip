@@ -4,9 +4,11 @@
 // which the north star does not move to the device, is the host implementation in host/vo_fivepoint.cpp).
 #include "pmv_ctx.h"
 #include "batch_engine.h"
+#include "ingest_batch.h"
 #include <mutex>
 #include <thread>
 #include "vo_capi_impl.h"
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -128,8 +130,20 @@ struct HipBA : BundleAdjustmentBase {
     }
 };
 // ---- the same five roles served through the batch engine (several sequences per launch, batch_engine.hip) --------------------
+// Streamed batch: the frames live in a ring of slots that the ingest thread refills (ingest_batch.hip); before a request the sequence's
+// thread waits until the frames it reads have been enqueued, and the request carries the ingest round the combiner's stream must wait for.
+struct RingFrames {
+    pmv::BatchIngest* ing = nullptr; int seq = 0;
+    int round(pmv_ctx* ctx, int slot_a, int slot_b = -1) {
+        if (!ing) return -1;
+        int ra = -1, rb = -1;
+        ck(ctx, pmv::batch_ingest_acquire(ing, seq, slot_a, &ra));
+        if (slot_b >= 0) ck(ctx, pmv::batch_ingest_acquire(ing, seq, slot_b, &rb));
+        return std::max(ra, rb);
+    }
+};
 struct BatchGftt : GoodFeatureExtractorBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng;
+    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
     std::vector<int> rect, xy, cnt;
     void gftt(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out) override {
         out.assign(cells.size(), {});
@@ -138,13 +152,14 @@ struct BatchGftt : GoodFeatureExtractorBase {
         const size_t cap = max > 0 ? (size_t)max : (size_t)PMV_GFTT_UNLIMITED_CAP;
         xy.resize(cells.size() * cap * 2);
         cnt.resize(cells.size());
-        ck(ctx, pmv::engine_detect(eng, 1, cells[0].slot, rect.data(), (int)cells.size(), max, quality, min_distance, xy.data(), nullptr, cnt.data()));
+        const int rr = ring.round(ctx, cells[0].slot);
+        ck(ctx, pmv::engine_detect(eng, 1, cells[0].slot, rect.data(), (int)cells.size(), max, quality, min_distance, xy.data(), nullptr, cnt.data(), rr));
         for (size_t c = 0; c < cells.size(); c++)
             for (int i = 0; i < cnt[c]; i++) out[c].push_back({xy[(c * cap + i) * 2], xy[(c * cap + i) * 2 + 1]});
     }
 };
 struct BatchShiTomasi : ShiTomasiExtractorBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng;
+    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
     std::vector<int> rect, xy, cnt;
     std::vector<double> sc;
     void shitomasi(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
@@ -156,7 +171,8 @@ struct BatchShiTomasi : ShiTomasiExtractorBase {
         xy.resize(cells.size() * (size_t)max * 2);
         sc.resize(cells.size() * (size_t)max);
         cnt.resize(cells.size());
-        ck(ctx, pmv::engine_detect(eng, 2, cells[0].slot, rect.data(), (int)cells.size(), max, quality, 0.0, xy.data(), sc.data(), cnt.data()));
+        const int rr = ring.round(ctx, cells[0].slot);
+        ck(ctx, pmv::engine_detect(eng, 2, cells[0].slot, rect.data(), (int)cells.size(), max, quality, 0.0, xy.data(), sc.data(), cnt.data(), rr));
         for (size_t c = 0; c < cells.size(); c++)
             for (int i = 0; i < cnt[c]; i++) {
                 out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
@@ -165,7 +181,7 @@ struct BatchShiTomasi : ShiTomasiExtractorBase {
     }
 };
 struct BatchLK : LucasKanadeFMBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng;
+    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
     // Ordering hint for the batched launch (no effect on any result): a track that needed many LK iterations in the last frame pair tends
     // to need many again (weak texture, an edge along the motion), and a launch ends with its slowest track - so the engine starts the
     // expensive ones first. The cost of a track is remembered under the integer pixel it was tracked TO, which is where the next call
@@ -191,7 +207,8 @@ struct BatchLK : LucasKanadeFMBase {
             }
             pred[(size_t)i] = c;
         }
-        ck(ctx, pmv::engine_lk(eng, prev.slot, next.slot, prev_xy, n, next_xy, status, err, pred.data(), iters.data()));
+        const int rr = ring.round(ctx, prev.slot, next.slot);
+        ck(ctx, pmv::engine_lk(eng, prev.slot, next.slot, prev_xy, n, next_xy, status, err, pred.data(), iters.data(), rr));
         std::fill(tkey.begin(), tkey.end(), 0xffffffffu);
         if (!use) return;
         for (int i = 0; i < n; i++) {
@@ -253,6 +270,49 @@ static void host_allocator_setup() {
         mallopt(M_TOP_PAD, 16 << 20);
         mallopt(M_MMAP_THRESHOLD, 32 << 20);
     });
+}
+
+// Sequence b of a batched run, on the calling thread: the reference's pipeline with the batch engine's plugin set. Frame i lives in slot
+// first_slot + i, or with a ring (streamed batch) in first_slot + i % ring, refilled by `ing`: the sequence then reports every frame it has
+// finished with (OdometryPipeline::on_frame_added) and its end.
+static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const pmv_pipeline_params* P, const double* K9, const double* gt_poses12,
+                               int first_slot, pmv::BatchIngest* ing, int ring, pmv_pipeline_result** out, int& code, std::string& msg) {
+    auto* res = new pmv_pipeline_result();
+    vo::PipelineRun& run = res->run;
+    vo::PipelineParams vp;
+    vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
+    vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
+    vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
+    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = 0;
+    try {
+        vo::pipeline_setup(run, vp, nullptr, K9, gt_poses12);
+        for (auto& im : run.pipe.images) im.slot = first_slot + (ing ? im.slot % ring : im.slot);
+        if (ing) {
+            // on_frame_added(k) follows addFrame of frames[k] = image k + init_offset (initialise() keeps image init_offset as frames[0]):
+            // every image below that one is dead - addFrame(i + 1) reads images i and i + 1 only
+            vo::OdometryPipeline* pipe = &run.pipe;
+            run.pipe.on_frame_added = [ing, b, pipe](int k) { pmv::batch_ingest_release(ing, b, k + pipe->init_offset); };
+        }
+        RingFrames rf{ing, b};
+        vo::BaseFeatureExtractor* ex;
+        if (P->extractor == 1) { auto* e = new BatchShiTomasi(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
+        else { auto* e = new BatchGftt(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
+        run.owned_ex.push_back(ex);
+        auto* lk = new BatchLK(); lk->ctx = ctx; lk->eng = eng; lk->ring = rf;
+        auto* pnp = new BatchPnP(); pnp->ctx = ctx; pnp->eng = eng; pnp->seq = b; pnp->tracker = &run.pipe;
+        auto* tri = new BatchTri(); tri->ctx = ctx; tri->eng = eng; tri->seq = b; tri->tracker = &run.pipe; tri->workers = 1;
+        tri->use_hypothesis_hook = P->device_fivepoint != 0;
+        auto* ba = new BatchBA(); ba->ctx = ctx; ba->eng = eng; ba->seq = b; ba->tracker = &run.pipe;
+        run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
+        run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
+        vo::pipeline_execute(run, vp);
+        *out = res;
+    } catch (const HipError& e) {
+        code = e.code; msg = e.what(); delete res;
+    } catch (const std::exception& e) {
+        code = PMV_ERR_INVALID; msg = e.what(); delete res;
+    }
+    if (ing) pmv::batch_ingest_finish(ing, b);   // finished or failed: its whole ring is free
 }
 
 extern "C" {
@@ -369,37 +429,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
     std::vector<std::string> msgs(B);
     std::vector<std::thread> th;
     for (int b = 0; b < B; b++)
-        th.emplace_back([&, b] {
-            const pmv_pipeline_params* P = &params[b];
-            auto* res = new pmv_pipeline_result();
-            vo::PipelineRun& run = res->run;
-            vo::PipelineParams vp;
-            vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
-            vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
-            vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
-            vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = 0;
-            try {
-                vo::pipeline_setup(run, vp, nullptr, K9 + 9 * b, gt_poses12[b]);
-                for (auto& im : run.pipe.images) im.slot += first_slot[b];
-                vo::BaseFeatureExtractor* ex;
-                if (P->extractor == 1) { auto* e = new BatchShiTomasi(); e->ctx = ctx; e->eng = eng; ex = e; }
-                else { auto* e = new BatchGftt(); e->ctx = ctx; e->eng = eng; ex = e; }
-                run.owned_ex.push_back(ex);
-                auto* lk = new BatchLK(); lk->ctx = ctx; lk->eng = eng;
-                auto* pnp = new BatchPnP(); pnp->ctx = ctx; pnp->eng = eng; pnp->seq = b; pnp->tracker = &run.pipe;
-                auto* tri = new BatchTri(); tri->ctx = ctx; tri->eng = eng; tri->seq = b; tri->tracker = &run.pipe; tri->workers = 1;
-                tri->use_hypothesis_hook = P->device_fivepoint != 0;
-                auto* ba = new BatchBA(); ba->ctx = ctx; ba->eng = eng; ba->seq = b; ba->tracker = &run.pipe;
-                run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
-                run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
-                vo::pipeline_execute(run, vp);
-                out[b] = res;
-            } catch (const HipError& e) {
-                codes[b] = e.code; msgs[b] = e.what(); delete res;
-            } catch (const std::exception& e) {
-                codes[b] = PMV_ERR_INVALID; msgs[b] = e.what(); delete res;
-            }
-        });
+        th.emplace_back([&, b] { run_batch_sequence(ctx, eng, b, &params[b], K9 + 9 * b, gt_poses12[b], first_slot[b], nullptr, 0, &out[b], codes[b], msgs[b]); });
     for (auto& t : th) t.join();
     rc = pmv::engine_build_end(eng);
     if (rc != PMV_OK) { pmv::set_err(ctx, "pmv_pipeline_run_batch: the background pyramid build failed"); for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; } return rc; }
@@ -410,6 +440,86 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
             return codes[b];
         }
     return PMV_OK;
+}
+// The same B sequences from HOST memory through per-sequence rings of `ring` slots (ingest_batch.hip): sequence b owns slots
+// first_slot[b] .. first_slot[b] + ring - 1, frame f lives in first_slot[b] + f % ring. Validation as in pmv_pipeline_run_batch, plus the
+// ring rules of include/pmv_hip.h. out[b] is bit-identical to the staged batch's and to the sequence's own pmv_pipeline_run.
+int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
+                                    const uint8_t* const* host_frames, const int* first_slot, int ring, pmv_pipeline_result** out) {
+    if (!ctx || !params || !K9 || !gt_poses12 || !host_frames || !first_slot || !out || B < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bad argument"); return PMV_ERR_INVALID; }
+    if (pmv::ingest_open(ctx)) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: a pmv_frames_stream_begin bracket is open on this context"); return PMV_ERR_INVALID; }
+    host_allocator_setup();
+    for (int b = 0; b < B; b++) out[b] = nullptr;
+    std::vector<std::pair<int, int>> ranges;
+    for (int b = 0; b < B; b++) {
+        const pmv_pipeline_params& P = params[b];
+        if (!host_frames[b] || !gt_poses12[b]) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: null frames / poses", b); return PMV_ERR_INVALID; }
+        if (P.n_frames < P.init_frames + 2 || P.init_frames < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: %d frames, init_frames %d: too short", b, P.n_frames, P.init_frames); return PMV_ERR_CAPACITY; }
+        // initialise() holds frames 0 .. init_frames - 1, and the first addFrame may need frame init_frames while frame init_offset is live
+        if (ring < P.init_frames + 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: ring %d < init_frames + 1 = %d", ring, P.init_frames + 1); return PMV_ERR_INVALID; }
+        if (first_slot[b] < 0 || first_slot[b] > ctx->n_slots - ring) {
+            pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: ring [%d, %d) outside the %d slots", b, first_slot[b], first_slot[b] + ring, ctx->n_slots);
+            return PMV_ERR_CAPACITY;
+        }
+        ranges.push_back({first_slot[b], b});
+        if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bundle_size 1..2 divides by zero in the reference"); return PMV_ERR_INVALID; }
+        if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bundle_size exceeds max_ba_cams"); return PMV_ERR_CAPACITY; }
+        if (P.w != params[0].w || P.h != params[0].h) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: all sequences must share the frame size"); return PMV_ERR_INVALID; }
+        if (P.w < 40 || P.h < 40 || P.w > ctx->max_w || P.h > ctx->max_h) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: frame %dx%d outside capacity %dx%d", P.w, P.h, ctx->max_w, ctx->max_h); return PMV_ERR_CAPACITY; }
+        if (P.matcher != 0 || P.extractor > 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: the batch engine serves the reference's default plugins (LK; GFTT or ShiTomasi)"); return PMV_ERR_INVALID; }
+        hipPointerAttribute_t attr;
+        const bool device_mem = hipPointerGetAttributes(&attr, host_frames[b]) == hipSuccess && attr.type == hipMemoryTypeDevice;
+        (void)hipGetLastError();
+        if (device_mem) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: the frames are in device memory, not host memory", b); return PMV_ERR_INVALID; }
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++)
+        if (ranges[i].first < ranges[i - 1].first + ring) {
+            pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: the rings of sequences %d and %d overlap", ranges[i - 1].second, ranges[i].second);
+            return PMV_ERR_INVALID;
+        }
+    pmv::BatchEngine* eng = nullptr;
+    int rc = pmv::batch_engine_get(ctx, B, &eng);
+    if (rc != PMV_OK) return rc;
+    rc = pmv_sync(ctx);
+    if (rc != PMV_OK) return rc;
+    pmv::BatchIngest* ing = nullptr;
+    {
+        std::vector<int> nf((size_t)B);
+        for (int b = 0; b < B; b++) nf[(size_t)b] = params[b].n_frames;
+        rc = pmv::batch_ingest_begin(ctx, B, first_slot, nf.data(), host_frames, ring, params[0].w, params[0].h, &ing);
+        if (rc != PMV_OK) return rc;
+    }
+    // The ring slots carry the run's geometry from here on (written before any sequence thread exists, never during the run); which frame a
+    // slot holds, and whether it has been built, is the ingest's per-slot record.
+    {
+        const pmv::PyrLayout L = pmv::layout_for(ctx, params[0].w, params[0].h);
+        for (int b = 0; b < B; b++) for (int i = 0; i < ring; i++) ctx->slot_layout[(size_t)(first_slot[b] + i)] = L;
+    }
+    pmv::engine_set_ring(eng, pmv::batch_ingest_wait_gpu, ing);
+    std::vector<int> codes(B, PMV_OK);
+    std::vector<std::string> msgs(B);
+    std::vector<std::thread> th;
+    for (int b = 0; b < B; b++)
+        th.emplace_back([&, b] { run_batch_sequence(ctx, eng, b, &params[b], K9 + 9 * b, gt_poses12[b], first_slot[b], ing, ring, &out[b], codes[b], msgs[b]); });
+    for (auto& t : th) t.join();
+    pmv::engine_set_ring(eng, nullptr, nullptr);
+    rc = pmv::batch_ingest_end(ctx, ing);   // joins the ingest thread (also after a failed sequence: the sources are the caller's)
+    if (rc != PMV_OK) { for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; } return rc; }
+    for (int b = 0; b < B; b++)
+        if (codes[b] != PMV_OK) {
+            pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: %s", b, msgs[b].c_str());
+            for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; }
+            return codes[b];
+        }
+    return PMV_OK;
+}
+int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out) {
+    if (!out) return pmv::BATCH_INGEST_STATS;
+    if (!ctx) return PMV_ERR_INVALID;
+    for (int i = 0; i < pmv::BATCH_INGEST_STATS; i++) out[i] = 0;
+    if (ctx->bingest) pmv::batch_ingest_stats(ctx->bingest, out);
+    return pmv::BATCH_INGEST_STATS;
 }
 // diagnostic: what the five combiners (LK, detectors, PnP, BA, DLT) have served so far
 int pmv_batch_stats(pmv_ctx* ctx, long long* counts10, double* times15) {

@@ -100,6 +100,8 @@ static void ingest_close(pmv_ctx* ctx) {
     g->open = false;
 }
 
+bool ingest_open(pmv_ctx* ctx) { return ctx->ingest && ctx->ingest->open; }
+
 void ingest_destroy(pmv_ctx* ctx) {
     Ingest* g = ctx->ingest;
     if (!g) return;

@@ -10,6 +10,7 @@
 namespace pmv {
 struct Ingest;                      // streamed frame ingest (ingest.hip)
 struct BatchEngine;                 // multi-sequence combiners (batch_engine.hip)
+struct BatchIngest;                 // streamed ingest of a batched run into per-sequence slot rings (ingest_batch.hip)
 constexpr int MAX_CELLS = 64;       // 1920x1080 -> 8x5 = 40 cells of 255x255
 constexpr int MAX_PER_CELL = 4096;    // also the capacity of an "unlimited" (max_per_cell <= 0) goodFeaturesToTrack call
 struct BackendBuffers;              // PnP / BA device workspaces (backend.hip)
@@ -70,6 +71,7 @@ struct pmv_ctx {
     int ba_mode = 0;
     pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch
     pmv::Ingest* ingest = nullptr;      // non-null while a pmv_frames_stream_begin .. _end bracket is open
+    pmv::BatchIngest* bingest = nullptr; // created by the first pmv_pipeline_run_batch_streamed (stream, staging buffers kept across calls)
     pmv::Profiler prof;
     pmv_call_log log;
     std::mutex err_mu;                  // set_err from several host threads (batch engine)
@@ -90,6 +92,8 @@ int pmv_frames_build_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n)
 // streamed ingest: make the front-end stream wait until `slot` has been copied and its pyramid built (no-op without a stream)
 int ingest_require(pmv_ctx* ctx, int slot);
 void ingest_destroy(pmv_ctx* ctx);
+bool ingest_open(pmv_ctx* ctx);     // a pmv_frames_stream_begin bracket is open on the context
+void batch_ingest_destroy(pmv_ctx* ctx);
 void batch_engine_destroy(pmv_ctx* ctx);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
