@@ -68,11 +68,15 @@ int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int 
 int pmv_frames_stage(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h);
 int pmv_frames_build(pmv_ctx* ctx, int first_slot, int n);
 /* Streamed ingest (Frame::Frame / Frame::init + the front-end's per-frame load, Frame.cpp:31-42, OdometryPipeline.cpp:212-220):
- * n tightly packed gray frames in HOST memory (pageable, or pinned / registered: then DMA'ed in place) are copied into slots
- * first_slot.. by an ingest thread on its own HIP stream, chunk by chunk, each chunk's pyramids built as soon as it lands.
- * pmv_frames_stream_begin returns at once; until pmv_frames_stream_end, pmv_lk_track / pmv_detect_* on a slot of the range first
- * make the front-end stream wait for that slot's chunk (nothing else blocks), so tracking starts while later frames are still
- * on their way. `gray` must stay valid until pmv_frames_stream_end, which joins the ingest thread. One stream per context. */
+ * n tightly packed gray frames in HOST memory (pageable, or pinned: then DMA'd straight from it) are moved into slots first_slot.. by the
+ * context's feeder thread on its own HIP stream, round by round, each round's pyramids built as soon as its frames land.
+ * pmv_frames_stream_begin returns at once; until pmv_frames_stream_end, pmv_lk_track / pmv_detect_* / pmv_knn_match on a slot of the
+ * range first make the front-end stream wait for that slot's round (nothing else blocks), so tracking starts while later frames are
+ * still on their way. pmv_frame_upload* / pmv_frames_stage into slots outside the range may be called meanwhile: they use a landing
+ * area of their own. pmv_frame_num_levels / pmv_frame_get_level* do not wait: on a slot of the range they are meaningful only after a
+ * tracking or detection call on that slot, or after pmv_frames_stream_end. `gray` must stay valid until pmv_frames_stream_end, which
+ * joins the feeder thread. One stream per context. Memory: 4 pinned staging buffers of 16 frames and as many HBM landing buffers
+ * (7.5 MB each at 1241x376), kept by the context. */
 int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h);
 int pmv_frames_stream_end(pmv_ctx* ctx);
 /* Debug/parity: copy pyramid level `level` of `slot` (unpadded, tightly packed) back to host. Returns level dims. */
@@ -237,7 +241,8 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* params, const doub
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                               const uint8_t* host_frames, pmv_pipeline_result** out);
 /* B independent sequences through batched launches (SURVEY.md §8e "same kernels with a leading batch dimension"): sequence b =
- * frame slots first_slot[b] .. + params[b].n_frames - 1 (pmv_frames_stage; one frame size for all), intrinsics K9 + 9 b, ground
+ * frame slots first_slot[b] .. + params[b].n_frames - 1 (pmv_frames_stage; one frame size for all; ranges may overlap, a shared slot is
+ * built once), intrinsics K9 + 9 b, ground
  * truth gt_poses12[b]. Each sequence keeps the reference's front-end / back-end host threads; their plugin calls are merged into
  * one k_lk_batch / detector / k_pnp_*_batch / k_bamB_* / k_tri_dlt_batch launch per kernel class by that class's combiner
  * thread (one HIP stream each); the combiners are the only threads that talk to the HIP runtime. out[b] is bit-identical to the same sequence's own pmv_pipeline_run. */
@@ -251,7 +256,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
  *     mapped at its host address (hipHostMalloc, torch pin_memory) is read in place, anything else is copied into pinned staging first.
  *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot
  *     first_slot[b] + f % ring. After the call each ring slot holds the last frame that went through it, pyramid built.
- *   Shared rules: one frame size for all sequences; build_pyramids is ignored (an ingest thread builds every frame as it lands); the
+ *   Shared rules: one frame size for all sequences; build_pyramids is ignored (the feeder builds every frame as it lands); the
  *     parameters are validated as in pmv_pipeline_run_batch (LK with GFTT or ShiTomasi, bundle limits).
  *   Minimum ring: ring >= init_frames + 1. initialise() holds frames 0 .. init_frames - 1 (OdometryPipeline.cpp:428-482), and the first
  *     addFrame may need frame init_frames while frame init_offset is still live. A smaller ring is PMV_ERR_INVALID.
@@ -263,7 +268,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
  *   Result: out[b] is bit-identical to the same sequence's pmv_pipeline_run_batch on staged frames and to its own pmv_pipeline_run: poses,
  *     per-frame features and landmark ids, and every count of the statistics.
  * Memory besides the rings: 4 pinned staging buffers of up to 64 frames (<= 32 MB) each; with PMV_BATCH_INGEST=copy as many HBM landing
- * buffers. pmv_frames_stream_begin's landing area is not used. */
+ * buffers. These belong to the context's batch feeder: pmv_frames_stream_begin's landing area is not used. */
 int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                                     const uint8_t* const* host_frames, const int* first_slot, int ring, pmv_pipeline_result** out);
 /* Ingest counters of the last pmv_pipeline_run_batch_streamed call: writes PMV_BATCH_INGEST_STATS (= 6) doubles to out and returns that

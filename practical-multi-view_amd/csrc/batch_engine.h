@@ -7,19 +7,14 @@ namespace pmv {
 struct BatchEngine;
 int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out);   // creates (or grows) the context's engine for B concurrent sequences
 void batch_engine_destroy(pmv_ctx* ctx);
-// pyramids of the run's sequences built in the background while the sequences already track (see BatchEngine::slot_round)
-int engine_build_begin(BatchEngine* E, int B, const int* first_slot, const int* n_frames, const int* build);
-int engine_build_end(BatchEngine* E);
-// streamed batch: how a combiner makes its stream wait for an ingest round (batch_ingest_wait_gpu); null = no ring in use
-void engine_set_ring(BatchEngine* E, hipError_t (*wait)(void*, hipStream_t, int), void* arg);
 // per combiner (LK, detectors, PnP, BA, DLT): counts10 = {launch rounds, requests} x 5; times15 (may be null) = seconds spent
 // {CPU time of the combiner thread, wall time processing batches, of that waiting for the GPU} x 5
 void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
 // same contracts as pmv_lk_track / pmv_detect_* / pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates; `seq` selects the
 // sequence's back-end workspace set. Blocking; safe to call from many threads at once (one outstanding call per seq and stream role).
 // predicted_iters (optional): how many LK iterations the caller expects each track to take (0..255) - the launch starts the expensive
-// tracks first; iters_out (optional): what each track took. Neither changes a result. ring_round (streamed batch): the ingest round that
-// builds the request's frames, from batch_ingest_acquire; -1 = none.
+// tracks first; iters_out (optional): what each track took. Neither changes a result. ring_round: the round of the context's batch feeder
+// (ctx->bingest) that builds the request's frames, from slot_ready; -1 = none.
 int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* status, float* err,
               const uint8_t* predicted_iters = nullptr, uint8_t* iters_out = nullptr, int ring_round = -1);
 int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, const int* cells, int n_cells, int max_per_cell, double quality,

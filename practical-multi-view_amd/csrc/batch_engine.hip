@@ -15,6 +15,7 @@
 #include "pmv_ctx.h"
 #include "backend.h"
 #include "batch_engine.h"
+#include "ingest_batch.h"
 #include <sys/prctl.h>
 #include <linux/futex.h>
 #include <sys/syscall.h>
@@ -47,7 +48,7 @@ struct LKReq : Req {
     uint8_t* iters_out = nullptr;   // optional: LK iterations each track took (the caller's ordering hint for its next request)
     std::vector<int> order;   // block -> track order of THIS request (local indices, -1 = padding), built by the caller
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
-    int ring_round = -1;      // streamed batch: the ingest round that builds the two frames (-1 = nothing to wait for)
+    int ring_round = -1;      // the feed round that builds the two frames (-1 = nothing to wait for)
 };
 struct DetReq : Req {
     int slot, n_cells, max_per_cell, unlimited;
@@ -150,22 +151,10 @@ struct BatchEngine {
     bool lk_lpt = true;       // PMV_LK_LPT=0: the round-2 block order (x-sorted stripes per XCD, request after request)
     bool exclusive = false;
     std::mutex exclusive_mu;
-    // Pyramids of a batched run are built WHILE the sequences already track (engine_build_begin): round r = frames [r * BUILD_CHUNK,
-    // (r + 1) * BUILD_CHUNK) of every sequence, enqueued round by round on the context's front-end stream with an event after each.
-    // A front-end launch that touches slot s first makes its stream wait for the event of slot_round[s] (a GPU-side dependency; the host
-    // only waits until that round has been ENQUEUED, which is milliseconds after the start). Before this the 1.1 ms of pyramid kernels
-    // per sequence ran back to back in front of everything: 141 ms of a 3 s pass at B = 128 with nothing else on the GPU.
-    static constexpr int BUILD_CHUNK = 32;
-    std::vector<int> slot_round;            // per frame slot: its build round, -1 = nothing to wait for
-    std::vector<hipEvent_t> build_ev;       // per round
-    std::atomic<int> build_enqueued{0};     // rounds whose launches and event are in the stream
-    std::atomic<int> build_error{0};
-    std::thread build_thread;
-    // Streamed batch (pmv_pipeline_run_batch_streamed, set for the duration of the call): the combiner of a launch that reads ring slots makes
-    // its stream wait for the newest ingest round the launch needs (batch_ingest_wait_gpu); the callers have already waited on the host until
-    // that round was enqueued.
-    hipError_t (*ring_wait)(void*, hipStream_t, int) = nullptr;
-    void* ring_arg = nullptr;
+    // The frames of a batched run are built by the context's batch feeder (ctx->bingest) WHILE the sequences already track. A request
+    // carries the feed round that builds its frames (its caller has waited in slot_ready until that round was enqueued); the combiner of
+    // the launch makes its stream wait for the newest such round on the GPU. Before this the 1.1 ms of pyramid kernels per sequence ran back
+    // to back in front of everything: 141 ms of a 3 s pass at B = 128 with nothing else on the GPU.
 };
 
 namespace {
@@ -226,16 +215,6 @@ hipError_t wait_stream(BatchEngine* E, Combiner& C) {
     return hipSuccess;
 }
 
-// make stream `s` wait for the pyramid build round `need` (see BatchEngine::slot_round)
-hipError_t wait_built(BatchEngine* E, hipStream_t s, int need) {
-    if (need < 0 || need >= (int)E->build_ev.size()) return hipSuccess;
-    while (E->build_enqueued.load(std::memory_order_acquire) <= need) {
-        if (E->build_error.load()) return hipErrorUnknown;
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-    return hipStreamWaitEvent(s, E->build_ev[(size_t)need], 0);
-}
-
 // ---- LK -------------------------------------------------------------------------------------------------------------------------
 void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     pmv_ctx* ctx = E->ctx;
@@ -243,29 +222,22 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<LKReq*> lk;
     for (Req* r : batch) lk.push_back((LKReq*)r);
     // ---- LK: one launch for the tracks of every requesting sequence
-    int total_tracks = 0, total_blocks = 0, need_round = -1, need_ring = -1;
+    int total_tracks = 0, total_blocks = 0, need_ring = -1;
     PyrLayout L{};
     bool have_L = false;
-    // (a slot whose pyramid the background build has not reached yet is "staged": n_levels < 0; the launch below waits for its round)
     for (LKReq* r : lk) {
-        PyrLayout a = ctx->slot_layout[r->prev_slot];
+        const PyrLayout& a = ctx->slot_layout[r->prev_slot];
         const PyrLayout& b2 = ctx->slot_layout[r->next_slot];
-        // staged but not built, and not on the background build's list either: there is no pyramid to track on
-        const bool unbuilt = (a.n_levels < 0 && (E->slot_round.empty() || E->slot_round[(size_t)r->prev_slot] < 0)) ||
-                             (b2.n_levels < 0 && (E->slot_round.empty() || E->slot_round[(size_t)r->next_slot] < 0));
-        if (a.n_levels < 0) a.n_levels = -a.n_levels;
-        if (unbuilt || a.n_levels == 0 || b2.n_levels == 0 || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
+        if (slot_ready(ctx, r->prev_slot) || slot_ready(ctx, r->next_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
         if (!have_L) { L = a; have_L = true; }
         else if (a.w[0] != L.w[0] || a.h[0] != L.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: all sequences of a batch must share the frame size"); continue; }
         r->base = total_tracks;
         total_tracks += r->n;
         total_blocks += (int)r->order.size();
-        if (!E->slot_round.empty()) need_round = std::max(need_round, std::max(E->slot_round[(size_t)r->prev_slot], E->slot_round[(size_t)r->next_slot]));
         need_ring = std::max(need_ring, r->ring_round);
     }
     if (total_tracks > 0) {
-        EK(wait_built(E, s, need_round));
-        if (need_ring >= 0 && E->ring_wait) EK(E->ring_wait(E->ring_arg, s, need_ring));
+        if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         if ((size_t)total_tracks > E->cap_tracks) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
         const size_t bytes = sizeof(LKBlock) * (size_t)total_blocks;
         EK(C.h_front.ensure(bytes + 64));
@@ -331,11 +303,8 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; };
     std::vector<Group> groups;
     for (DetReq* r : det) {
-        PyrLayout Lr = ctx->slot_layout[r->slot];
-        if (Lr.n_levels < 0 && (E->slot_round.empty() || E->slot_round[(size_t)r->slot] < 0)) {
-            r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d was staged but its pyramid was never built", r->slot); continue;
-        }
-        if (Lr.n_levels < 0) Lr.n_levels = -Lr.n_levels;   // staged, its build round is awaited below
+        const PyrLayout& Lr = ctx->slot_layout[r->slot];
+        if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d holds no built pyramid", r->slot); continue; }
         Group* g = nullptr;
         for (Group& x : groups)
             if (x.kind == r->kind && x.max_per_cell == r->max_per_cell && x.unlimited == r->unlimited && x.quality == r->quality && x.min_dist == r->min_dist &&
@@ -361,11 +330,9 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 }
         EK(hipMemsetAsync(C.d_flags, 0, 16, s));
         {
-            int need_round = -1, need_ring = -1;
-            if (!E->slot_round.empty()) for (DetReq* r : det) need_round = std::max(need_round, E->slot_round[(size_t)r->slot]);
+            int need_ring = -1;
             for (DetReq* r : det) if (r->rc == PMV_OK) need_ring = std::max(need_ring, r->ring_round);
-            EK(wait_built(E, s, need_round));
-            if (need_ring >= 0 && E->ring_wait) EK(E->ring_wait(E->ring_arg, s, need_ring));
+            if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         }
         size_t c0 = 0;
         char* hd = (char*)C.h_det.p;
@@ -626,8 +593,6 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (C.h_work) (void)hipHostFree(C.h_work);
             if (C.d_flags) (void)hipFree(C.d_flags);
         }
-    if (E->build_thread.joinable()) E->build_thread.join();
-    for (hipEvent_t ev : E->build_ev) (void)hipEventDestroy(ev);
     for (BackendBuffers* b : E->slots) backend_free(b);
     delete E;
     ctx->engine = nullptr;
@@ -702,50 +667,6 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
     return PMV_OK;
 }
 
-// Start building the pyramids of B sequences (frames first_slot[b] .. + n_frames[b] - 1, only where build[b] != 0) in the background;
-// engine_build_end() joins. The slots must have been staged with one frame geometry.
-int engine_build_begin(BatchEngine* E, int B, const int* first_slot, const int* n_frames, const int* build) {
-    pmv_ctx* ctx = E->ctx;
-    CKC(hipSetDevice(ctx->device));
-    E->slot_round.assign((size_t)ctx->n_slots, -1);
-    int max_n = 0;
-    for (int b = 0; b < B; b++) if (build[b]) {
-        max_n = std::max(max_n, n_frames[b]);
-        for (int f = 0; f < n_frames[b]; f++) E->slot_round[(size_t)(first_slot[b] + f)] = f / BatchEngine::BUILD_CHUNK;
-    }
-    const int rounds = (max_n + BatchEngine::BUILD_CHUNK - 1) / BatchEngine::BUILD_CHUNK;
-    while ((int)E->build_ev.size() < rounds) {
-        hipEvent_t ev;
-        CKC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        E->build_ev.push_back(ev);
-    }
-    E->build_enqueued.store(0);
-    E->build_error.store(0);
-    if (rounds == 0) return PMV_OK;
-    std::vector<int> fs(first_slot, first_slot + B), nf(n_frames, n_frames + B), bd(build, build + B);
-    E->build_thread = std::thread([E, ctx, B, rounds, fs, nf, bd] {
-        (void)hipSetDevice(ctx->device);
-        tl_prof = &ctx->prof;
-        for (int r = 0; r < rounds; r++) {
-            for (int b = 0; b < B; b++) {
-                const int f0 = r * BatchEngine::BUILD_CHUNK, n = std::min(BatchEngine::BUILD_CHUNK, nf[(size_t)b] - f0);
-                if (!bd[(size_t)b] || n <= 0) continue;
-                if (pmv_frames_build_on(ctx, ctx->s_front, fs[(size_t)b] + f0, n) != PMV_OK) { E->build_error.store(1); return; }
-            }
-            if (hipEventRecord(E->build_ev[(size_t)r], ctx->s_front) != hipSuccess) { E->build_error.store(1); return; }
-            E->build_enqueued.store(r + 1, std::memory_order_release);
-        }
-    });
-    return PMV_OK;
-}
-int engine_build_end(BatchEngine* E) {
-    if (E->build_thread.joinable()) E->build_thread.join();
-    E->slot_round.clear();
-    return E->build_error.load() ? PMV_ERR_HIP : PMV_OK;
-}
-
-void engine_set_ring(BatchEngine* E, hipError_t (*wait)(void*, hipStream_t, int), void* arg) { E->ring_wait = wait; E->ring_arg = arg; }
-
 void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15) {
     for (int r = 0; r < 5; r++) {   // the five classes every run uses; the optional five-point class is reported separately
 
@@ -802,7 +723,9 @@ int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_ce
     r.kind = kind; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
     r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
     REQ(r.max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect: max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
-    REQ(slot >= 0 && slot < ctx->n_slots && ctx->slot_layout[slot].n_levels != 0, PMV_ERR_INVALID, "detect: slot %d has no frame", slot);
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_INVALID, "detect: slot %d out of range", slot);
+    const int rc = slot_ready(ctx, slot);
+    if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
     for (int i = 0; i < n_cells; i++) {
         const int* c = cells + 4 * i;

@@ -80,7 +80,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     c->max_ba_cams = max_ba_cams; c->max_ba_points = max_ba_points; c->max_ba_obs = max_ba_obs;
     c->cap = make_layout(max_w, max_h);
     c->slot_layout.assign(n_slots, PyrLayout());
-    for (auto& l : c->slot_layout) l.n_levels = 0;
+    c->slot_state.assign(n_slots, SLOT_EMPTY);
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(nullptr, "%s: %s", #x, hipGetErrorString(e_)); pmv_ctx_destroy(c); return PMV_ERR_HIP; } } while (0)
     CK(hipSetDevice(device));
     CK(frontend_prepare_device());
@@ -137,8 +137,8 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     batch_engine_destroy(c);
-    ingest_destroy(c);
-    batch_ingest_destroy(c);
+    batch_ingest_destroy(c->ingest);
+    batch_ingest_destroy(c->bingest);
     if (c->s_front) hipStreamSynchronize(c->s_front);
     if (c->s_back) hipStreamSynchronize(c->s_back);
     backend_destroy(c);
@@ -169,8 +169,9 @@ int pmv_sync(pmv_ctx* ctx) {
 }
 
 }  // extern "C"
-// tight != nullptr: level 0 comes from n tight gray frames at `tight` (device) instead of from the levels' own interior
-int pmv::build_levels_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n, const PyrLayout& L, const uint8_t* tight) {
+// pyramid levels of `n` consecutive slots with identical geometry L on `stream`; tight != nullptr: level 0 comes from n tight gray frames
+// at `tight` (device) instead of from the levels' own interior
+static int build_levels_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n, const PyrLayout& L, const uint8_t* tight = nullptr) {
     CKC(launch_pad_level0(stream, ctx->d_slots, L, first_slot, n, tight));
     for (int l = 1; l < L.n_levels; l++) CKC(launch_pyrdown(stream, ctx->d_slots, L, l, first_slot, n));
     return PMV_OK;
@@ -199,35 +200,29 @@ int pmv_frames_stage(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, i
         CKC(launch_pad_level0(ctx->s_front, ctx->d_slots, L, first_slot + i0, nb, ctx->d_tight));
     }
     CKC(hipStreamSynchronize(ctx->s_front));
-    for (int i = 0; i < n; i++) { ctx->slot_layout[first_slot + i] = L; ctx->slot_layout[first_slot + i].n_levels = -L.n_levels; }
+    for (int i = 0; i < n; i++) { ctx->slot_layout[first_slot + i] = L; ctx->slot_state[first_slot + i] = SLOT_STAGED; }
     return PMV_OK;
 }
 
 int pmv_frames_build(pmv_ctx* ctx, int first_slot, int n) {
     REQ(ctx, PMV_ERR_INVALID, "null ctx");
     tl_prof = &ctx->prof;
-    return pmv::pmv_frames_build_on(ctx, ctx->s_front, first_slot, n);
-}
-}  // extern "C"
-int pmv::pmv_frames_build_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n) {
     REQ(first_slot >= 0 && n >= 1 && first_slot + n <= ctx->n_slots, PMV_ERR_CAPACITY, "pmv_frames_build: slot range");
     CKC(hipSetDevice(ctx->device));
     // consecutive slots with identical geometry are built in one batched launch per level
     int i = 0;
     while (i < n) {
-        PyrLayout L = ctx->slot_layout[first_slot + i];
-        REQ(L.n_levels != 0, PMV_ERR_INVALID, "pmv_frames_build: slot %d was never staged", first_slot + i);
+        const PyrLayout& L = ctx->slot_layout[first_slot + i];
+        REQ(ctx->slot_state[first_slot + i] != SLOT_EMPTY, PMV_ERR_INVALID, "pmv_frames_build: slot %d was never staged", first_slot + i);
         int j = i + 1;
         while (j < n && ctx->slot_layout[first_slot + j].w[0] == L.w[0] && ctx->slot_layout[first_slot + j].h[0] == L.h[0]) j++;
-        if (L.n_levels < 0) L.n_levels = -L.n_levels;
-        int rc = build_levels_on(ctx, stream, first_slot + i, j - i, L);
+        int rc = build_levels_on(ctx, ctx->s_front, first_slot + i, j - i, L);
         if (rc) return rc;
-        for (int k = i; k < j; k++) ctx->slot_layout[first_slot + k].n_levels = L.n_levels;
+        for (int k = i; k < j; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
         i = j;
     }
     return PMV_OK;
 }
-extern "C" {
 
 int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, int stride) {
     REQ(ctx && gray, PMV_ERR_INVALID, "pmv_frame_upload: null argument");
@@ -241,6 +236,7 @@ int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, 
     if (rc) return rc;
     CKC(hipStreamSynchronize(ctx->s_front));   // the host buffer may be reused by the caller
     ctx->slot_layout[slot] = L;
+    ctx->slot_state[slot] = SLOT_BUILT;
     return PMV_OK;
 }
 
@@ -261,20 +257,20 @@ int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int 
     if (rc) return rc;
     CKC(hipStreamSynchronize(ctx->s_front));
     ctx->slot_layout[slot] = L;
+    ctx->slot_state[slot] = SLOT_BUILT;
     return PMV_OK;
 }
 
 int pmv_frame_num_levels(pmv_ctx* ctx, int slot) {
     if (!ctx || slot < 0 || slot >= ctx->n_slots) return PMV_ERR_INVALID;
-    const int n = ctx->slot_layout[slot].n_levels;
-    return n > 0 ? n - 1 : PMV_ERR_INVALID;
+    return ctx->slot_state[slot] == SLOT_BUILT ? ctx->slot_layout[slot].n_levels - 1 : PMV_ERR_INVALID;
 }
 
 int pmv_frame_get_level(pmv_ctx* ctx, int slot, int level, uint8_t* out, int* w, int* h) {
     REQ(ctx && out, PMV_ERR_INVALID, "null argument");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "slot out of range");
     const PyrLayout& L = ctx->slot_layout[slot];
-    REQ(L.n_levels > 0 && level >= 0 && level < L.n_levels, PMV_ERR_INVALID, "level %d not built for slot %d", level, slot);
+    REQ(ctx->slot_state[slot] == SLOT_BUILT && level >= 0 && level < L.n_levels, PMV_ERR_INVALID, "level %d not built for slot %d", level, slot);
     CKC(hipSetDevice(ctx->device));
     CKC(hipStreamSynchronize(ctx->s_front));
     const uint8_t* org = level_origin((const uint8_t*)ctx->d_slots + (size_t)slot * L.slot_bytes, L, level);
@@ -288,7 +284,7 @@ int pmv_frame_get_level_padded(pmv_ctx* ctx, int slot, int level, uint8_t* out, 
     REQ(ctx && out, PMV_ERR_INVALID, "null argument");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "slot out of range");
     const PyrLayout& L = ctx->slot_layout[slot];
-    REQ(L.n_levels > 0 && level >= 0 && level < L.n_levels, PMV_ERR_INVALID, "level %d not built for slot %d", level, slot);
+    REQ(ctx->slot_state[slot] == SLOT_BUILT && level >= 0 && level < L.n_levels, PMV_ERR_INVALID, "level %d not built for slot %d", level, slot);
     static_assert(PAD == PMV_PYR_PAD, "header constant");
     CKC(hipSetDevice(ctx->device));
     CKC(hipStreamSynchronize(ctx->s_front));
@@ -305,10 +301,9 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
     REQ(ctx && (n == 0 || (prev_xy && out_xy && out_status && out_err)), PMV_ERR_INVALID, "pmv_lk_track: null argument");
     REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
     REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
-    if (ctx->ingest) { int rc_ = ingest_require(ctx, prev_slot > next_slot ? prev_slot : next_slot); if (rc_) return rc_; }
+    for (int s : {prev_slot, next_slot}) { int rc_ = slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front); if (rc_) return rc_; }
     const PyrLayout& L = ctx->slot_layout[prev_slot];
     const PyrLayout& L2 = ctx->slot_layout[next_slot];
-    REQ(L.n_levels > 0 && L2.n_levels > 0, PMV_ERR_INVALID, "pmv_lk_track: slot has no pyramid");
     REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_lk_track: frame sizes differ");
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
@@ -357,9 +352,9 @@ static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "detect: slot out of range");
     REQ(n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_CAPACITY, "detect: n_cells=%d (max %d)", n_cells, MAX_CELLS);
     REQ(max_per_cell >= 1 && max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect: max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
-    if (ctx->ingest) { int rc_ = ingest_require(ctx, slot); if (rc_) return rc_; }
+    int rc = slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front);
+    if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
-    REQ(L.n_levels > 0, PMV_ERR_INVALID, "detect: slot %d has no frame", slot);
     for (int i = 0; i < n_cells; i++) {
         const int* c = cells + 4 * i;
         REQ(c[2] >= 3 && c[3] >= 3 && c[2] <= CELL_MAX && c[3] <= CELL_MAX && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0],

@@ -79,12 +79,20 @@ __device__ inline void write_padded_row(const uint8_t* lrow, int lead, int w, ui
 // another row's interior, which no block changes).
 constexpr int PAD0_T = 128, PAD0_R = 4;   // rows per workgroup: their loads are in flight together
 __host__ __device__ inline int pad0_row_lds(int w) { return ((w + 3 + 24 + 3) / 4) * 4; }
-// `tight` != nullptr: the frames come from a buffer of tight gray frames (frame z at tight + z * w * h: staging / upload / ingest; rows
-// generally unaligned, fetched as the aligned dwords that cover them) instead of from the level's own interior.
-__global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight) {
+// Workgroup column z builds one slot. Range form (list == nullptr): slot first_slot + z, level 0 from tight gray frame z at `tight` (staging
+// / upload: the 256-byte aligned landing area) or, with `tight` null too, from the level's own interior. List form (the feeder, ingest_batch.hip):
+// slot list[z].slot, level 0 from list[z].src (the HBM landing area or mapped pinned host memory, at any alignment), in place when that is null.
+// Tight rows are generally unaligned: they are fetched as the aligned dwords that hold the row's bytes and no others, so a source that ends at
+// the end of a host page is never over-read.
+__global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight,
+                                                        const PyrListEntry* __restrict__ list) {
     extern __shared__ __attribute__((aligned(16))) uint8_t srow_all[];   // PAD0_R x row_lds bytes
-    uint8_t* slot = slots + (size_t)(first_slot + blockIdx.z) * L.slot_bytes;
     const int w = L.w[0], h = L.h[0], stride = L.stride[0];
+    int s;
+    const uint8_t* frame;   // tight source frame, or null: in place (block-uniform)
+    if (list) { const PyrListEntry e = list[blockIdx.z]; s = e.slot; frame = e.src; }
+    else { s = first_slot + (int)blockIdx.z; frame = tight ? tight + (size_t)blockIdx.z * (size_t)w * (size_t)h : nullptr; }
+    uint8_t* slot = slots + (size_t)s * L.slot_bytes;
     const int row_lds = pad0_row_lds(w);
     const int ph = h + 2 * PAD;
     const int py0 = blockIdx.y * PAD0_R;
@@ -95,10 +103,10 @@ __global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout
         const int sy = reflect101(py - PAD, h);
         const uint32_t* src;
         int nd;
-        if (tight) {
-            const size_t b = (size_t)blockIdx.z * (size_t)w * (size_t)h + (size_t)sy * (size_t)w;   // byte offset of the source row (the buffer is 256-byte aligned and has slack behind it)
-            lead[r] = (unsigned)(b & 3u);
-            src = (const uint32_t*)(tight + (b & ~(size_t)3));
+        if (frame) {
+            const uintptr_t a = (uintptr_t)(frame + (size_t)sy * (size_t)w);
+            lead[r] = (unsigned)(a & 3u);
+            src = (const uint32_t*)(a & ~(uintptr_t)3);
             nd = (int)((lead[r] + (unsigned)w + 3u) >> 2);
         } else {
             lead[r] = 0u;                                   // interior rows start 64-byte aligned (PAD and the stride are multiples of 64)
@@ -127,105 +135,10 @@ __device__ inline uint32_t as_u32(pk_u16 x) { union { uint32_t u; pk_u16 p; } c;
 constexpr int PYR_T = 256, PYR_R = 4;   // output rows per workgroup
 __host__ __device__ inline int pyr_vs_row(int dw) { return (2 * dw + 24 + 3) & ~3; }        // uint16 entries
 __host__ __device__ inline int pyr_out_row(int dw) { return ((dw + 3 + 24 + 3) / 4) * 4; }  // bytes
-__global__ __launch_bounds__(PYR_T) void k_pyrdown(uint8_t* slots, PyrLayout L, int ld, int first_slot) {
+// (slot of workgroup column z as in k_pad_level0)
+__global__ __launch_bounds__(PYR_T) void k_pyrdown(uint8_t* slots, PyrLayout L, int ld, int first_slot, const PyrListEntry* __restrict__ list) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pyr_lds[];
-    uint8_t* slot = slots + (size_t)(first_slot + blockIdx.z) * L.slot_bytes;
-    const int ls = ld - 1;
-    const uint8_t* src = level_origin((const uint8_t*)slot, L, ls);
-    const int ss = L.stride[ls];
-    const int dw = L.w[ld], dh = L.h[ld], ds = L.stride[ld];
-    const int ph = dh + 2 * PAD;
-    const int py0 = blockIdx.y * PYR_R;
-    const int nd = (2 * dw + 8) >> 2;
-    const int vs_row = pyr_vs_row(dw), out_row = pyr_out_row(dw);
-    uint8_t* orow_all = pyr_lds + (size_t)PYR_R * vs_row * 2;
-#pragma unroll
-    for (int r = 0; r < PYR_R; r++) {
-        const int py = py0 + r < ph ? py0 + r : ph - 1;
-        const int ry = reflect101(py - PAD, dh);
-        const uint8_t* r0 = src + (ptrdiff_t)(2 * ry - 2) * ss - 4;
-        uint16_t* vs = (uint16_t*)pyr_lds + r * vs_row;      // vs[c + 4] = vertical sum of source column c
-        for (int d = threadIdx.x; d < nd; d += PYR_T) {
-            const uint32_t a = *(const uint32_t*)(r0 + 4 * d), b = *(const uint32_t*)(r0 + ss + 4 * d), c = *(const uint32_t*)(r0 + 2 * ss + 4 * d),
-                           e = *(const uint32_t*)(r0 + 3 * ss + 4 * d), f = *(const uint32_t*)(r0 + 4 * ss + 4 * d);
-            // bytes 0,2 and bytes 1,3 of each row as 16-bit pairs; (a + f) + 4 (b + e) + 6 c <= 4080
-            const uint32_t M = 0x00ff00ffu;
-            const pk_u16 lo = (as_pk(a & M) + as_pk(f & M)) + (pk_u16)(4) * (as_pk(b & M) + as_pk(e & M)) + (pk_u16)(6) * as_pk(c & M);
-            const pk_u16 hi = (as_pk((a >> 8) & M) + as_pk((f >> 8) & M)) + (pk_u16)(4) * (as_pk((b >> 8) & M) + as_pk((e >> 8) & M)) + (pk_u16)(6) * as_pk((c >> 8) & M);
-            const uint32_t l = as_u32(lo), hh = as_u32(hi);   // l = (col0, col2), hh = (col1, col3)
-            *(uint2*)(vs + 4 * d) = make_uint2((l & 0xffffu) | (hh << 16), (l >> 16) | (hh & 0xffff0000u));
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < PYR_R; r++) {
-        // D[j] = (E[j], O[j]) = vertical sums of source columns 2j, 2j+1 = dword j + 2 of the row; output pixel i:
-        // E[i-1] + E[i+1] + 4 (O[i-1] + O[i]) + 6 E[i]
-        const uint32_t* vsd = (const uint32_t*)((const uint16_t*)pyr_lds + r * vs_row) + 2;
-        uint32_t* orow = (uint32_t*)(orow_all + r * out_row);
-        for (int i = threadIdx.x * 4; i < dw; i += PYR_T * 4) {
-            uint32_t D[7];
-#pragma unroll
-            for (int q = 0; q < 7; q++) D[q] = vsd[i - 1 + q];   // D[q] = pair i - 1 + q
-            uint32_t res[2];
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                const int o = 2 * half;   // outputs i + o, i + o + 1
-                const pk_u16 Em = as_pk(__builtin_amdgcn_perm(D[o + 1], D[o], 0x05040100u)), E0 = as_pk(__builtin_amdgcn_perm(D[o + 2], D[o + 1], 0x05040100u)),
-                             Ep = as_pk(__builtin_amdgcn_perm(D[o + 3], D[o + 2], 0x05040100u));
-                const pk_u16 Om = as_pk(__builtin_amdgcn_perm(D[o + 1], D[o], 0x07060302u)), O0 = as_pk(__builtin_amdgcn_perm(D[o + 2], D[o + 1], 0x07060302u));
-                const pk_u16 t = ((Em + Ep) + (pk_u16)(4) * (Om + O0) + (pk_u16)(6) * E0 + (pk_u16)(128)) >> (pk_u16)(8);
-                res[half] = as_u32(t);   // two bytes in the 16-bit lanes
-            }
-            orow[i >> 2] = (res[0] & 0xffu) | ((res[0] >> 8) & 0xff00u) | ((res[1] & 0xffu) << 16) | ((res[1] & 0xff0000u) << 8);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < PYR_R; r++) {
-        if (py0 + r >= ph) break;
-        write_padded_row<PYR_T>(orow_all + r * out_row, 0, dw, slot + L.off[ld] + (size_t)(py0 + r) * ds);
-    }
-}
-
-// ---- slot-list forms (streamed batches, ingest_batch.hip) ----------------------------------------------------------------------------
-// Workgroup column z builds slot list[z].slot; level 0 comes from the tight gray frame at list[z].src (the HBM landing area, or mapped
-// pinned host memory through its device address), at any alignment. One ingest round of any number of sequences is then one
-// k_pad_level0_list launch plus one k_pyrdown_list launch per level. The bodies are copies of k_pad_level0 / k_pyrdown with only the
-// slot and source lookup changed: a shared inline body reorders operands in the ISA of the staged path's kernels, which stays as it is.
-__global__ __launch_bounds__(PAD0_T) void k_pad_level0_list(uint8_t* slots, PyrLayout L, const PyrListEntry* __restrict__ list) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t srow_all[];   // PAD0_R x row_lds bytes
-    const PyrListEntry ent = list[blockIdx.z];
-    uint8_t* slot = slots + (size_t)ent.slot * L.slot_bytes;
-    const int w = L.w[0], h = L.h[0], stride = L.stride[0];
-    const int row_lds = pad0_row_lds(w);
-    const int ph = h + 2 * PAD;
-    const int py0 = blockIdx.y * PAD0_R;
-    unsigned lead[PAD0_R];
-#pragma unroll
-    for (int r = 0; r < PAD0_R; r++) {
-        const int py = py0 + r < ph ? py0 + r : ph - 1;     // (rows past the end repeat the last one; they are not stored)
-        const int sy = reflect101(py - PAD, h);
-        // the aligned dwords that hold the row's bytes and no others: a source that ends at the end of a host page is never over-read
-        const uintptr_t a = (uintptr_t)(ent.src + (size_t)sy * (size_t)w);
-        lead[r] = (unsigned)(a & 3u);
-        const uint32_t* src = (const uint32_t*)(a & ~(uintptr_t)3);
-        const int nd = (int)((lead[r] + (unsigned)w + 3u) >> 2);
-        uint32_t* srow = (uint32_t*)(srow_all + r * row_lds);
-        for (int d = threadIdx.x; d < nd; d += PAD0_T) srow[d] = src[d];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < PAD0_R; r++) {
-        if (py0 + r >= ph) break;
-        write_padded_row<PAD0_T>(srow_all + r * row_lds, (int)lead[r], w, slot + L.off[0] + (size_t)(py0 + r) * stride);
-    }
-}
-
-
-__global__ __launch_bounds__(PYR_T) void k_pyrdown_list(uint8_t* slots, PyrLayout L, int ld, const PyrListEntry* __restrict__ list) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t pyr_lds[];
-    uint8_t* slot = slots + (size_t)list[blockIdx.z].slot * L.slot_bytes;
+    uint8_t* slot = slots + (size_t)(list ? list[blockIdx.z].slot : first_slot + (int)blockIdx.z) * L.slot_bytes;
     const int ls = ld - 1;
     const uint8_t* src = level_origin((const uint8_t*)slot, L, ls);
     const int ss = L.stride[ls];
@@ -308,37 +221,21 @@ hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, in
     return hipGetLastError();
 }
 
-hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight) {
-    if (!slots || n < 1 || first_slot < 0 || L.n_levels < 1) return hipErrorInvalidValue;
+// list != nullptr: n device-visible entries, first_slot and tight unused
+hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list) {
+    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0) || L.n_levels < 1) return hipErrorInvalidValue;
     dim3 grid(1, (L.h[0] + 2 * PAD + PAD0_R - 1) / PAD0_R, n);
     const size_t shm = (size_t)pad0_row_lds(L.w[0]) * PAD0_R;
     ProfScope ps(K_PAD0, s);
-    hipLaunchKernelGGL(k_pad_level0, grid, dim3(PAD0_T), shm, s, slots, L, first_slot, tight);
+    hipLaunchKernelGGL(k_pad_level0, grid, dim3(PAD0_T), shm, s, slots, L, first_slot, tight, list);
     return hipGetLastError();
 }
-// list forms: n table entries (device-visible), one workgroup column per entry; counted under the same profiler ids as the base kernels
-hipError_t launch_pad_level0_list(hipStream_t s, uint8_t* slots, const PyrLayout& L, const PyrListEntry* list, int n) {
-    if (!slots || !list || n < 1 || n > 65535 || L.n_levels < 1) return hipErrorInvalidValue;
-    dim3 grid(1, (L.h[0] + 2 * PAD + PAD0_R - 1) / PAD0_R, n);
-    const size_t shm = (size_t)pad0_row_lds(L.w[0]) * PAD0_R;
-    ProfScope ps(K_PAD0, s);
-    hipLaunchKernelGGL(k_pad_level0_list, grid, dim3(PAD0_T), shm, s, slots, L, list);
-    return hipGetLastError();
-}
-hipError_t launch_pyrdown_list(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, const PyrListEntry* list, int n) {
-    if (!slots || !list || n < 1 || n > 65535 || ld < 1 || ld >= L.n_levels) return hipErrorInvalidValue;
+hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, int first_slot, int n, const PyrListEntry* list) {
+    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0) || ld < 1 || ld >= L.n_levels) return hipErrorInvalidValue;
     dim3 grid(1, (L.h[ld] + 2 * PAD + PYR_R - 1) / PYR_R, n);
     const size_t shm = ((size_t)pyr_vs_row(L.w[ld]) * 2 + (size_t)pyr_out_row(L.w[ld])) * PYR_R;
     ProfScope ps(K_PYRDOWN, s);
-    hipLaunchKernelGGL(k_pyrdown_list, grid, dim3(PYR_T), shm, s, slots, L, ld, list);
-    return hipGetLastError();
-}
-hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, int first_slot, int n) {
-    if (!slots || n < 1 || first_slot < 0 || ld < 1 || ld >= L.n_levels) return hipErrorInvalidValue;
-    dim3 grid(1, (L.h[ld] + 2 * PAD + PYR_R - 1) / PYR_R, n);
-    const size_t shm = ((size_t)pyr_vs_row(L.w[ld]) * 2 + (size_t)pyr_out_row(L.w[ld])) * PYR_R;
-    ProfScope ps(K_PYRDOWN, s);
-    hipLaunchKernelGGL(k_pyrdown, grid, dim3(PYR_T), shm, s, slots, L, ld, first_slot);
+    hipLaunchKernelGGL(k_pyrdown, grid, dim3(PYR_T), shm, s, slots, L, ld, first_slot, list);
     return hipGetLastError();
 }
 

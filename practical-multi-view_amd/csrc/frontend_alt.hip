@@ -190,10 +190,10 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
     REQ(n >= 0 && n <= ctx->max_tracks && m >= 0 && m <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_knn_match: n=%d / m=%d exceed max_tracks=%d", n, m, ctx->max_tracks);
     REQ(n_neighbours >= 1 && n_neighbours <= KNN_MAX_NN && window >= 1 && window <= 63, PMV_ERR_INVALID, "pmv_knn_match: n_neighbours 1..%d, window 1..63", KNN_MAX_NN);
     REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
-    if (ctx->ingest) { int rc_ = ingest_require(ctx, src_slot > cmp_slot ? src_slot : cmp_slot); if (rc_) return rc_; }
+    for (int s : {src_slot, cmp_slot}) { int rc_ = slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front); if (rc_) return rc_; }
     const PyrLayout& L = ctx->slot_layout[src_slot];
     const PyrLayout& L2 = ctx->slot_layout[cmp_slot];
-    REQ(L.n_levels > 0 && L2.n_levels > 0 && L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_knn_match: slots have no frame / sizes differ");
+    REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_knn_match: frame sizes differ");
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
@@ -219,9 +219,9 @@ int pmv_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
     if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }   // OpenCVFASTFeatureExtractor.cpp:12 `if (i >= max) break`
     REQ(out_xy && out_response, PMV_ERR_INVALID, "pmv_detect_fast: null output");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_detect_fast: slot out of range");
-    if (ctx->ingest) { int rc_ = ingest_require(ctx, slot); if (rc_) return rc_; }
+    int rc = slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front);
+    if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
-    REQ(L.n_levels > 0, PMV_ERR_INVALID, "pmv_detect_fast: slot %d has no frame", slot);
     REQ((size_t)n_cells * max_per_cell <= (size_t)MAX_CELLS * MAX_PER_CELL, PMV_ERR_CAPACITY, "pmv_detect_fast: n_cells * max_per_cell = %zu exceeds %d",
         (size_t)n_cells * max_per_cell, MAX_CELLS * MAX_PER_CELL);
     // a FAST "cell" may be as large as the frame (kNNFeatureMatcher calls the extractor on the whole next frame, :11)

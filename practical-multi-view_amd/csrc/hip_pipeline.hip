@@ -130,15 +130,14 @@ struct HipBA : BundleAdjustmentBase {
     }
 };
 // ---- the same five roles served through the batch engine (several sequences per launch, batch_engine.hip) --------------------
-// Streamed batch: the frames live in a ring of slots that the ingest thread refills (ingest_batch.hip); before a request the sequence's
-// thread waits until the frames it reads have been enqueued, and the request carries the ingest round the combiner's stream must wait for.
+// The frames a request reads: slot_ready on the sequence's own thread (for a fed sequence it waits until the feeder has enqueued their
+// build); the request carries the feed round the combiner's stream must wait for.
 struct RingFrames {
-    pmv::BatchIngest* ing = nullptr; int seq = 0;
+    pmv::BatchIngest* feed = nullptr; int seq = -1;   // seq: the sequence's index in the feed, -1 = not fed (it may still read fed slots)
     int round(pmv_ctx* ctx, int slot_a, int slot_b = -1) {
-        if (!ing) return -1;
         int ra = -1, rb = -1;
-        ck(ctx, pmv::batch_ingest_acquire(ing, seq, slot_a, &ra));
-        if (slot_b >= 0) ck(ctx, pmv::batch_ingest_acquire(ing, seq, slot_b, &rb));
+        ck(ctx, pmv::slot_ready(ctx, slot_a, feed, seq, nullptr, &ra));
+        if (slot_b >= 0) ck(ctx, pmv::slot_ready(ctx, slot_b, feed, seq, nullptr, &rb));
         return std::max(ra, rb);
     }
 };
@@ -273,10 +272,10 @@ static void host_allocator_setup() {
 }
 
 // Sequence b of a batched run, on the calling thread: the reference's pipeline with the batch engine's plugin set. Frame i lives in slot
-// first_slot + i, or with a ring (streamed batch) in first_slot + i % ring, refilled by `ing`: the sequence then reports every frame it has
-// finished with (OdometryPipeline::on_frame_added) and its end.
+// first_slot + i % ring. A fed sequence (fed = its index in the feed `ing`, else -1) reports every frame it has finished with
+// (OdometryPipeline::on_frame_added) and its end.
 static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const pmv_pipeline_params* P, const double* K9, const double* gt_poses12,
-                               int first_slot, pmv::BatchIngest* ing, int ring, pmv_pipeline_result** out, int& code, std::string& msg) {
+                               int first_slot, pmv::BatchIngest* ing, int fed, int ring, pmv_pipeline_result** out, int& code, std::string& msg) {
     auto* res = new pmv_pipeline_result();
     vo::PipelineRun& run = res->run;
     vo::PipelineParams vp;
@@ -286,14 +285,14 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
     vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = 0;
     try {
         vo::pipeline_setup(run, vp, nullptr, K9, gt_poses12);
-        for (auto& im : run.pipe.images) im.slot = first_slot + (ing ? im.slot % ring : im.slot);
-        if (ing) {
+        for (auto& im : run.pipe.images) im.slot = first_slot + im.slot % ring;
+        if (fed >= 0) {
             // on_frame_added(k) follows addFrame of frames[k] = image k + init_offset (initialise() keeps image init_offset as frames[0]):
             // every image below that one is dead - addFrame(i + 1) reads images i and i + 1 only
             vo::OdometryPipeline* pipe = &run.pipe;
-            run.pipe.on_frame_added = [ing, b, pipe](int k) { pmv::batch_ingest_release(ing, b, k + pipe->init_offset); };
+            run.pipe.on_frame_added = [ing, fed, pipe](int k) { pmv::batch_ingest_release(ing, fed, k + pipe->init_offset); };
         }
-        RingFrames rf{ing, b};
+        RingFrames rf{ing, fed};
         vo::BaseFeatureExtractor* ex;
         if (P->extractor == 1) { auto* e = new BatchShiTomasi(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
         else { auto* e = new BatchGftt(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
@@ -312,13 +311,65 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
     } catch (const std::exception& e) {
         code = PMV_ERR_INVALID; msg = e.what(); delete res;
     }
-    if (ing) pmv::batch_ingest_finish(ing, b);   // finished or failed: its whole ring is free
+    if (fed >= 0) pmv::batch_ingest_finish(ing, fed);   // finished or failed: its whole ring is free
+}
+
+// The parameter rules the entry points share: bundle_size, and for a batch the frame size and the plugins the batch engine serves.
+static int check_params(pmv_ctx* ctx, const char* who, const pmv_pipeline_params& P, bool batch) {
+    if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "%s: bundle_size 1..2 divides by zero in the reference (OdometryPipeline.cpp:407)", who); return PMV_ERR_INVALID; }
+    if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "%s: bundle_size exceeds max_ba_cams", who); return PMV_ERR_CAPACITY; }
+    if (!batch) return PMV_OK;
+    if (P.w < 40 || P.h < 40 || P.w > ctx->max_w || P.h > ctx->max_h) { pmv::set_err(ctx, "%s: frame %dx%d outside capacity %dx%d", who, P.w, P.h, ctx->max_w, ctx->max_h); return PMV_ERR_CAPACITY; }
+    if (P.matcher != 0 || P.extractor > 1) { pmv::set_err(ctx, "%s: the batch engine serves the reference's default plugins (LK; GFTT or ShiTomasi)", who); return PMV_ERR_INVALID; }
+    return PMV_OK;
+}
+
+// Everything the two batched entry points share once each has validated its slots: sequence b reads slots first_slot[b] .. + ring[b] - 1,
+// fed from host_frames[b] (streamed batch), staged in place (host_frames null: the sequences with build_pyramids), or not at all.
+static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
+                     const uint8_t* const* host_frames, const int* first_slot, const int* ring, pmv_pipeline_result** out) {
+    for (int b = 0; b < B; b++) {
+        if (const int rc = check_params(ctx, who, params[b], true)) return rc;
+        if (params[b].w != params[0].w || params[b].h != params[0].h) { pmv::set_err(ctx, "%s: all sequences must share the frame size", who); return PMV_ERR_INVALID; }
+    }
+    pmv::BatchEngine* eng = nullptr;
+    int rc = pmv::batch_engine_get(ctx, B, &eng);
+    if (rc != PMV_OK) return rc;
+    rc = pmv_sync(ctx);
+    if (rc != PMV_OK) return rc;
+    std::vector<pmv::FeedSeq> feed;
+    std::vector<int> fed((size_t)B, -1);
+    for (int b = 0; b < B; b++)
+        if (host_frames || params[b].build_pyramids) {
+            fed[(size_t)b] = (int)feed.size();
+            feed.push_back({first_slot[b], params[b].n_frames, ring[b], host_frames ? host_frames[b] : nullptr});
+        }
+    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, params[0].w, params[0].h)) != PMV_OK)
+        return rc;
+    std::vector<int> codes(B, PMV_OK);
+    std::vector<std::string> msgs(B);
+    std::vector<std::thread> th;
+    for (int b = 0; b < B; b++)
+        th.emplace_back([&, b] { run_batch_sequence(ctx, eng, b, &params[b], K9 + 9 * b, gt_poses12[b], first_slot[b], ctx->bingest, fed[(size_t)b], ring[b], &out[b], codes[b], msgs[b]); });
+    for (auto& t : th) t.join();
+    if (!feed.empty()) {
+        rc = pmv::batch_ingest_end(ctx, ctx->bingest);   // joins the feeder thread (also after a failed sequence: the sources are the caller's)
+        if (host_frames) pmv::batch_ingest_stats(ctx->bingest, ctx->bingest_stats);
+        if (rc != PMV_OK) { for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; } return rc; }
+    }
+    for (int b = 0; b < B; b++)
+        if (codes[b] != PMV_OK) {
+            pmv::set_err(ctx, "%s: sequence %d: %s", who, b, msgs[b].c_str());
+            for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; }
+            return codes[b];
+        }
+    return PMV_OK;
 }
 
 extern "C" {
 
 // Same run from HOST frames (n_frames * w * h gray bytes, pageable or pinned): the frames are streamed into slots 0..n_frames-1 by
-// the ingest thread (ingest.hip) while the pipeline is already tracking the first ones. Results are identical to
+// the feeder (a pmv_frames_stream_begin bracket, ingest_batch.hip) while the pipeline is already tracking the first ones. Results are identical to
 // pmv_frames_stage + pmv_pipeline_run(build_pyramids = 1).
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K9, const double* gt_poses12,
                               const uint8_t* host_frames, pmv_pipeline_result** out) {
@@ -327,9 +378,9 @@ int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* P, const 
     int rc = pmv_frames_stream_begin(ctx, 0, P->n_frames, host_frames, P->w, P->h);
     if (rc != PMV_OK) return rc;
     pmv_pipeline_params Q = *P;
-    Q.build_pyramids = 0;   // the ingest stream builds them chunk by chunk
+    Q.build_pyramids = 0;   // the feeder builds them round by round
     rc = pmv_pipeline_run(ctx, &Q, K9, gt_poses12, out);
-    const int rc2 = pmv_frames_stream_end(ctx);   // joins the ingest thread (also after a failed run: the source buffer is the caller's)
+    const int rc2 = pmv_frames_stream_end(ctx);   // joins the feeder thread (also after a failed run: the source buffer is the caller's)
     if (rc == PMV_OK && rc2 != PMV_OK) { pmv_pipeline_free(*out); *out = nullptr; return rc2; }
     return rc;
 }
@@ -342,8 +393,7 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K
         pmv::set_err(ctx, "pmv_pipeline_run: n_frames=%d (slots %d, init_frames %d)", P->n_frames, ctx->n_slots, P->init_frames);
         return PMV_ERR_CAPACITY;
     }
-    if (P->bundle_size != 0 && P->bundle_size < 3) { pmv::set_err(ctx, "pmv_pipeline_run: bundle_size 1..2 divides by zero in the reference (OdometryPipeline.cpp:407)"); return PMV_ERR_INVALID; }
-    if (P->bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "pmv_pipeline_run: bundle_size exceeds max_ba_cams"); return PMV_ERR_CAPACITY; }
+    if (const int rc = check_params(ctx, "pmv_pipeline_run", *P, false)) return rc;
     auto* res = new pmv_pipeline_result();
     vo::PipelineRun& run = res->run;
     vo::PipelineParams vp;
@@ -394,6 +444,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
                            const int* first_slot, pmv_pipeline_result** out) {
     if (!ctx || !params || !K9 || !gt_poses12 || !first_slot || !out || B < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch: bad argument"); return PMV_ERR_INVALID; }
     host_allocator_setup();
+    std::vector<int> ring((size_t)B);
     for (int b = 0; b < B; b++) {
         const pmv_pipeline_params& P = params[b];
         out[b] = nullptr;
@@ -401,45 +452,19 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
             pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: frames [%d, %d) outside the %d slots / too short", b, first_slot[b], first_slot[b] + P.n_frames, ctx->n_slots);
             return PMV_ERR_CAPACITY;
         }
-        if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "pmv_pipeline_run_batch: bundle_size 1..2 divides by zero in the reference"); return PMV_ERR_INVALID; }
-        if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "pmv_pipeline_run_batch: bundle_size exceeds max_ba_cams"); return PMV_ERR_CAPACITY; }
-        if (P.w != params[0].w || P.h != params[0].h) { pmv::set_err(ctx, "pmv_pipeline_run_batch: all sequences must share the frame size"); return PMV_ERR_INVALID; }
         for (int i = 0; i < P.n_frames; i++) {   // the geometry actually staged in the slots, not only the parameter structs
             const pmv::PyrLayout& Ls = ctx->slot_layout[first_slot[b] + i];
-            if (Ls.n_levels == 0 || Ls.w[0] != P.w || Ls.h[0] != P.h) {
+            const bool empty = ctx->slot_state[first_slot[b] + i] == pmv::SLOT_EMPTY;
+            if (empty || Ls.w[0] != P.w || Ls.h[0] != P.h) {
                 pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: slot %d holds %s (%dx%d), the run is %dx%d", b, first_slot[b] + i,
-                             Ls.n_levels == 0 ? "no frame" : "a frame of another size", Ls.w[0], Ls.h[0], P.w, P.h);
+                             empty ? "no frame" : "a frame of another size", Ls.w[0], Ls.h[0], P.w, P.h);
                 return PMV_ERR_INVALID;
             }
         }
-        if (P.matcher != 0 || P.extractor > 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch: the batch engine serves the reference's default plugins (LK; GFTT or ShiTomasi)"); return PMV_ERR_INVALID; }
+        ring[(size_t)b] = P.n_frames;
     }
-    pmv::BatchEngine* eng = nullptr;
-    int rc = pmv::batch_engine_get(ctx, B, &eng);
-    if (rc != PMV_OK) return rc;
-    rc = pmv_sync(ctx);
-    if (rc != PMV_OK) return rc;
-    {   // the pyramids are built in the background, round by round, while the sequences already track
-        std::vector<int> nf((size_t)B), bd((size_t)B);
-        for (int b = 0; b < B; b++) { nf[(size_t)b] = params[b].n_frames; bd[(size_t)b] = params[b].build_pyramids; }
-        rc = pmv::engine_build_begin(eng, B, first_slot, nf.data(), bd.data());
-        if (rc != PMV_OK) return rc;
-    }
-    std::vector<int> codes(B, PMV_OK);
-    std::vector<std::string> msgs(B);
-    std::vector<std::thread> th;
-    for (int b = 0; b < B; b++)
-        th.emplace_back([&, b] { run_batch_sequence(ctx, eng, b, &params[b], K9 + 9 * b, gt_poses12[b], first_slot[b], nullptr, 0, &out[b], codes[b], msgs[b]); });
-    for (auto& t : th) t.join();
-    rc = pmv::engine_build_end(eng);
-    if (rc != PMV_OK) { pmv::set_err(ctx, "pmv_pipeline_run_batch: the background pyramid build failed"); for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; } return rc; }
-    for (int b = 0; b < B; b++)
-        if (codes[b] != PMV_OK) {
-            pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: %s", b, msgs[b].c_str());
-            for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; }
-            return codes[b];
-        }
-    return PMV_OK;
+    // the pyramids of the sequences with build_pyramids are built by the feeder, round by round, while the sequences already track
+    return run_batch(ctx, "pmv_pipeline_run_batch", B, params, K9, gt_poses12, nullptr, first_slot, ring.data(), out);
 }
 // The same B sequences from HOST memory through per-sequence rings of `ring` slots (ingest_batch.hip): sequence b owns slots
 // first_slot[b] .. first_slot[b] + ring - 1, frame f lives in first_slot[b] + f % ring. Validation as in pmv_pipeline_run_batch, plus the
@@ -447,7 +472,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
 int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                                     const uint8_t* const* host_frames, const int* first_slot, int ring, pmv_pipeline_result** out) {
     if (!ctx || !params || !K9 || !gt_poses12 || !host_frames || !first_slot || !out || B < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bad argument"); return PMV_ERR_INVALID; }
-    if (pmv::ingest_open(ctx)) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: a pmv_frames_stream_begin bracket is open on this context"); return PMV_ERR_INVALID; }
+    if (pmv::batch_ingest_active(ctx->ingest)) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: a pmv_frames_stream_begin bracket is open on this context"); return PMV_ERR_INVALID; }
     host_allocator_setup();
     for (int b = 0; b < B; b++) out[b] = nullptr;
     std::vector<std::pair<int, int>> ranges;
@@ -462,11 +487,6 @@ int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_para
             return PMV_ERR_CAPACITY;
         }
         ranges.push_back({first_slot[b], b});
-        if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bundle_size 1..2 divides by zero in the reference"); return PMV_ERR_INVALID; }
-        if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bundle_size exceeds max_ba_cams"); return PMV_ERR_CAPACITY; }
-        if (P.w != params[0].w || P.h != params[0].h) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: all sequences must share the frame size"); return PMV_ERR_INVALID; }
-        if (P.w < 40 || P.h < 40 || P.w > ctx->max_w || P.h > ctx->max_h) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: frame %dx%d outside capacity %dx%d", P.w, P.h, ctx->max_w, ctx->max_h); return PMV_ERR_CAPACITY; }
-        if (P.matcher != 0 || P.extractor > 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: the batch engine serves the reference's default plugins (LK; GFTT or ShiTomasi)"); return PMV_ERR_INVALID; }
         hipPointerAttribute_t attr;
         const bool device_mem = hipPointerGetAttributes(&attr, host_frames[b]) == hipSuccess && attr.type == hipMemoryTypeDevice;
         (void)hipGetLastError();
@@ -478,47 +498,13 @@ int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_para
             pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: the rings of sequences %d and %d overlap", ranges[i - 1].second, ranges[i].second);
             return PMV_ERR_INVALID;
         }
-    pmv::BatchEngine* eng = nullptr;
-    int rc = pmv::batch_engine_get(ctx, B, &eng);
-    if (rc != PMV_OK) return rc;
-    rc = pmv_sync(ctx);
-    if (rc != PMV_OK) return rc;
-    pmv::BatchIngest* ing = nullptr;
-    {
-        std::vector<int> nf((size_t)B);
-        for (int b = 0; b < B; b++) nf[(size_t)b] = params[b].n_frames;
-        rc = pmv::batch_ingest_begin(ctx, B, first_slot, nf.data(), host_frames, ring, params[0].w, params[0].h, &ing);
-        if (rc != PMV_OK) return rc;
-    }
-    // The ring slots carry the run's geometry from here on (written before any sequence thread exists, never during the run); which frame a
-    // slot holds, and whether it has been built, is the ingest's per-slot record.
-    {
-        const pmv::PyrLayout L = pmv::layout_for(ctx, params[0].w, params[0].h);
-        for (int b = 0; b < B; b++) for (int i = 0; i < ring; i++) ctx->slot_layout[(size_t)(first_slot[b] + i)] = L;
-    }
-    pmv::engine_set_ring(eng, pmv::batch_ingest_wait_gpu, ing);
-    std::vector<int> codes(B, PMV_OK);
-    std::vector<std::string> msgs(B);
-    std::vector<std::thread> th;
-    for (int b = 0; b < B; b++)
-        th.emplace_back([&, b] { run_batch_sequence(ctx, eng, b, &params[b], K9 + 9 * b, gt_poses12[b], first_slot[b], ing, ring, &out[b], codes[b], msgs[b]); });
-    for (auto& t : th) t.join();
-    pmv::engine_set_ring(eng, nullptr, nullptr);
-    rc = pmv::batch_ingest_end(ctx, ing);   // joins the ingest thread (also after a failed sequence: the sources are the caller's)
-    if (rc != PMV_OK) { for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; } return rc; }
-    for (int b = 0; b < B; b++)
-        if (codes[b] != PMV_OK) {
-            pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: sequence %d: %s", b, msgs[b].c_str());
-            for (int k = 0; k < B; k++) { delete out[k]; out[k] = nullptr; }
-            return codes[b];
-        }
-    return PMV_OK;
+    const std::vector<int> rings((size_t)B, ring);
+    return run_batch(ctx, "pmv_pipeline_run_batch_streamed", B, params, K9, gt_poses12, host_frames, first_slot, rings.data(), out);
 }
 int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out) {
     if (!out) return pmv::BATCH_INGEST_STATS;
     if (!ctx) return PMV_ERR_INVALID;
-    for (int i = 0; i < pmv::BATCH_INGEST_STATS; i++) out[i] = 0;
-    if (ctx->bingest) pmv::batch_ingest_stats(ctx->bingest, out);
+    for (int i = 0; i < pmv::BATCH_INGEST_STATS; i++) out[i] = ctx->bingest_stats[i];
     return pmv::BATCH_INGEST_STATS;
 }
 // diagnostic: what the five combiners (LK, detectors, PnP, BA, DLT) have served so far

@@ -1,27 +1,33 @@
-// Streamed ingest of a batched run (ingest_batch.hip): B sequences' gray frames move from host memory into per-sequence rings of
-// frame slots while the sequences track; pmv_pipeline_run_batch_streamed is its only user.
+// The feeder (ingest_batch.hip): builds the pyramids of B sequences' frame slots on its own stream while the sequences already read them.
+// Users: pmv_pipeline_run_batch_streamed (host frames through recycled rings), pmv_pipeline_run_batch (frames staged in place) and the
+// pmv_frames_stream_begin .. _end bracket (one sequence of host frames). Readers wait for a slot through pmv::slot_ready (pmv_ctx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/pmv_hip.h"
 struct pmv_ctx;
 namespace pmv {
 struct BatchIngest;
-// Validates nothing the caller has not (slot ranges, sizes); starts the ingest thread. `host_frames[b]`: n_frames[b] tight w x h frames.
-int batch_ingest_begin(pmv_ctx* ctx, int B, const int* first_slot, const int* n_frames, const uint8_t* const* host_frames, int ring, int w, int h,
-                       BatchIngest** out);
-// Sequence `seq`'s own front-end thread, before an LK / detect request on `slot`: waits on the host until the frame the sequence needs in
-// that slot has been enqueued, and returns the ingest round that builds it (for batch_ingest_wait_gpu).
-int batch_ingest_acquire(BatchIngest* g, int seq, int slot, int* round);
-// Combiner thread: make `s` wait on the GPU for ingest round `round` (the ingest stream is in order: every earlier round as well).
-hipError_t batch_ingest_wait_gpu(void* g, hipStream_t s, int round);
+// What a feed serves: it sets a sequence's frames per round (as each route had them before the feeder) and the default form.
+enum FeedKind { FEED_STREAMED, FEED_STAGED, FEED_BRACKET };
+// One sequence of a feed: frame f goes to slot first + f % ring. src: tight w x h host frames (pageable or pinned), or null: the frames are
+// already staged in their slots (ring = n), only the pad and the pyramid levels are left to do.
+struct FeedSeq { int first, n, ring; const uint8_t* src; };
+// Validates nothing the caller has not (slot ranges, sizes; the rings of a feed that recycles slots are disjoint); creates *g on first use,
+// marks every slot of the feed built with the feed's geometry (its readers wait in slot_ready for the round that builds it) and starts the
+// feeder thread. Staged ranges may overlap: a slot that several sequences cover is built once.
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h);
+bool batch_ingest_active(const BatchIngest* g);
+// Combiner thread: make `s` wait on the GPU for feed round `round` (the feeder's stream is in order: every earlier round as well).
+hipError_t batch_ingest_wait_gpu(BatchIngest* g, hipStream_t s, int round);
 // Sequence `seq` no longer reads frames below `frame` (its front-end thread, after addFrame returned).
 void batch_ingest_release(BatchIngest* g, int seq, int frame);
-// Sequence `seq` has ended (finished or failed): its whole ring is free, nothing more is ingested for it.
+// Sequence `seq` has ended (finished or failed): its ring is free; a ring that recycles slots receives nothing more.
 void batch_ingest_finish(BatchIngest* g, int seq);
-// Joins the ingest thread and waits for its stream; sets ctx->slot_layout of every ring slot (built, or empty if it never received a frame).
+// Joins the feeder thread (it ends once every frame that will be fed is enqueued) and waits for its stream. A slot that never received its
+// frame goes back to empty (host source) or staged (staged source).
 int batch_ingest_end(pmv_ctx* ctx, BatchIngest* g);
 constexpr int BATCH_INGEST_STATS = PMV_BATCH_INGEST_STATS;
 void batch_ingest_stats(const BatchIngest* g, double* out6);
-void batch_ingest_destroy(pmv_ctx* ctx);
 }  // namespace pmv

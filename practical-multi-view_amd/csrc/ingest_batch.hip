@@ -1,24 +1,30 @@
-// Streamed ingest of a batched run (pmv_pipeline_run_batch_streamed). The reference loads one image per front-end iteration
-// (Frame::Frame / Frame::init, Frame.cpp:31-42; featureExtractionThread, OdometryPipeline.cpp:212-229) and tracking touches only frames
-// k-1 and k, so a sequence needs a short RING of device slots instead of one slot per frame: frame f of sequence b lives in slot
-// first_slot[b] + f % ring. One ingest thread on its own HIP stream fills the rings of all B sequences:
+// The feeder: every background pyramid build of frame slots. The reference loads one image per front-end iteration (Frame::Frame /
+// Frame::init, Frame.cpp:31-42; featureExtractionThread, OdometryPipeline.cpp:212-229) and tracking touches only frames k-1 and k. Here a
+// FEED of B sequences is built on a HIP stream of its own while the sequences already track. Frame f of sequence b lives in slot
+// first + f % ring; its source is host memory or the slot itself (staged):
+//   * pmv_pipeline_run_batch_streamed: host frames, a short ring per sequence whose slots are recycled;
+//   * pmv_pipeline_run_batch: the sequences with build_pyramids, staged in place, ring = n_frames;
+//   * pmv_frames_stream_begin .. _end: one sequence of host frames, ring = n.
 //
 //   * Release. After addFrame(image i) has returned, the sequence's front-end thread reports (OdometryPipeline::on_frame_added) that
 //     frames below i are dead. Their kernels have finished: a request returns to its sequence only after the combiner has seen the
-//     completion word of its round, so the ingest stream may overwrite those slots without any GPU-side dependency.
+//     completion word of its round, so the feeder's stream may overwrite those slots without any GPU-side dependency.
 //   * Rounds. A round takes up to F frames from every sequence with room, most-starved first (fewest frames landed ahead of its
-//     release point), up to ROUND_FRAMES frames. It is one table + frames block in a pinned staging buffer, and then
+//     release point), up to a round's capacity. It is one table + frames block in a pinned staging buffer, and then for host frames
 //       copy:   one hipMemcpyAsync of the block into an HBM landing buffer; level 0 is read from there;
-//       mapped: no copy call; k_pad_level0_list reads level 0 straight from mapped pinned host memory (the staging buffer for a
-//               pageable source, the caller's own pinned buffer through its device address otherwise);
-//     then one k_pad_level0_list and one k_pyrdown_list launch per level for the whole round, and an event.
-//   * Acquire. Each slot carries (frame, round) of its last enqueued build, published with release / acquire atomics. Before an LK or
-//     detect request, the sequence thread waits on the host until the frame it needs is in the slot's record; the combiner then makes
-//     its stream wait for that round's event once per launch.
+//       mapped: no copy call; k_pad_level0 reads level 0 straight from mapped pinned host memory (the staging buffer for a pageable
+//               source, the caller's own pinned buffer through its device address otherwise);
+//     then one k_pad_level0 and one k_pyrdown launch per level for the whole round, and an event. The launches read the round's slot
+//     table (list form), unless the round is consecutive slots from consecutive frames (range form, as every round of a bracket). A bracket
+//     (copy form by default) DMAs a pinned source straight into HBM; a staged feed copies only its slot tables into HBM.
+//   * Acquire. Each slot carries (frame, round) of its last enqueued build, published with release / acquire atomics. Before a kernel
+//     reads a slot, its caller waits in slot_ready on the host until the frame it needs is in the slot's record; the stream of the kernel
+//     then waits for that round's event (a combiner once per launch).
 //
 // A sequence is served when it has room for F frames, or has no more than LOW frames landed ahead, or only its last frames remain, or its
 // thread is waiting for a frame: a round per released frame would be 5 launches per frame (the launch volume DESIGN §5 suspects behind
-// the bimodal throughput).
+// the bimodal throughput). A ring that is not recycled (ring >= n) has all its frames as room from the start: its sequence is fed CHUNK
+// frames per round until every frame is built, whether the sequence still runs or not.
 #include "pmv_ctx.h"
 #include "ingest_batch.h"
 #include <algorithm>
@@ -34,36 +40,47 @@ namespace pmv {
 
 struct BatchIngest {
     static constexpr int NBUF = 4;                      // staging (and landing) buffers: rounds in flight
-    static constexpr int NEV = 64;                      // round events (round % NEV): a combiner waits on its own round's, not on a later one's
-    static constexpr int ROUND_FRAMES = 64;             // frames per round at most ...
+    // Round events. A feed that recycles slots keeps a ring of NEV (round % NEV): its rounds wait for releases, so a combiner waits on its own
+    // round's event, not on a later one's. A feed that does not recycle (every ring >= n) may run any number of rounds ahead of its readers:
+    // it has one event per round (`per_round`), created as the rounds come and kept for later feeds.
+    static constexpr int NEV = 64;
+    static constexpr int ROUND_FRAMES = 64;             // host frames per round at most ...
     static constexpr size_t ROUND_BYTES = 32u << 20;    // ... and no more bytes than this (1241x376: 64 frames = 29.9 MB)
-    static constexpr size_t HDR = 4096;                 // the round's slot table in front of its frames
+    static constexpr size_t HDR = 16384;                // the round's slot table in front of its frames ...
+    static constexpr int TABLE = (int)(HDR / sizeof(PyrListEntry));   // ... and so the frames of a round of staged sources at most
     static constexpr int LOW = 2;                       // frames landed ahead of the release point below which a sequence is served at once
+    static constexpr int BRACKET_CHUNK = 16, STAGED_CHUNK = 32;   // frames of a sequence per round: bracket, staged batch (as before the feeder)
+    // slot_rec values besides (frame << 32) | round: no feed covers the slot / not built yet, by sequence b of the feed
+    static constexpr long long NONE = -1;
+    static long long pending(int b) { return -2 - (long long)b; }
     // kept across calls
     hipStream_t stream = nullptr;
-    hipEvent_t ev[NEV] = {};
+    std::vector<hipEvent_t> ev;
+    hipEvent_t copied[NBUF] = {};   // copy form: the round's DMA out of its staging buffer is done
     uint8_t* h_stage = nullptr;   // NBUF x buf_bytes, pinned + mapped
     uint8_t* dm_stage = nullptr;  // its device address
-    uint8_t* d_land = nullptr;    // NBUF x buf_bytes in HBM (copy mode only)
+    uint8_t* d_land = nullptr;    // NBUF x buf_bytes in HBM (copy form and staged feeds)
     size_t buf_bytes = 0, land_bytes = 0;
-    std::unique_ptr<std::atomic<long long>[]> slot_state;   // per slot: (frame << 32) | round of its last enqueued build, -1 = none
-    std::mutex ev_mu;             // hipEventRecord (ingest thread) vs hipStreamWaitEvent (combiners) on the same event
-    // one call
+    std::unique_ptr<std::atomic<long long>[]> slot_rec;   // per slot: (frame << 32) | round of its last enqueued build, or NONE / pending(b)
+    std::mutex ev_mu;             // hipEventRecord / growth of `ev` (feeder thread) vs hipStreamWaitEvent (readers)
+    // one feed
     struct Seq {
-        int first = 0, n = 0;
-        const uint8_t* src = nullptr;   // host address of frame 0
+        int first = 0, n = 0, ring = 0, F = 1;
+        const uint8_t* src = nullptr;   // host address of frame 0, null = staged in the slots
         const uint8_t* dev = nullptr;   // device address of frame 0 when the source is pinned, else null
         std::atomic<int> released{0};   // frames below this are dead
         std::atomic<int> finished{0};
-        std::atomic<int> waiting{0};    // its thread is blocked in batch_ingest_acquire
-        int next = 0;                   // next frame to ingest (ingest thread only)
+        std::atomic<int> waiting{0};    // its thread is blocked in acquire
+        int next = 0;                   // next frame to feed (feeder thread only)
     };
     std::unique_ptr<Seq[]> seq;
     pmv_ctx* ctx = nullptr;
-    int B = 0, ring = 0, F = 1, w = 0, h = 0, frames_per_round = 1;
+    int B = 0, w = 0, h = 0, frames_per_round = 1;
     size_t fb = 0;
     PyrLayout L{};
-    bool copy_mode = false;
+    bool copy_mode = false, per_round = false, open = false;
+    bool dma_release = false;   // copy form of a bracket or staged feed: a staging buffer is free once its DMA is done (else: once its round is)
+    std::atomic<int> front_waited{-1};   // newest round the synchronous callers' stream already waits for (slot_ready)
     std::thread th;
     std::atomic<bool> stop{false};
     std::atomic<int> error{0};
@@ -71,10 +88,11 @@ struct BatchIngest {
     std::mutex mu;                // sequence threads waiting for frames
     std::condition_variable cv;
     std::atomic<int> waiters{0};
-    // statistics of the call (pmv_batch_ingest_stats)
+    // statistics of the feed (pmv_batch_ingest_stats)
     long long rounds = 0, frames = 0, bytes = 0;
     double t_memcpy = 0, t_room = 0;
     std::atomic<long long> wait_ns{0};
+    size_t ev_index(long long round) const { return (size_t)(per_round ? round : round % NEV); }
 };
 
 namespace {
@@ -82,7 +100,7 @@ namespace {
 void fail(BatchIngest* g, int code, const char* what, hipError_t e) {
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        if (!g->error.load()) snprintf(g->err, sizeof(g->err), "batch ingest: %s: %s", what, hipGetErrorString(e));
+        if (!g->error.load()) snprintf(g->err, sizeof(g->err), "feeder: %s: %s", what, hipGetErrorString(e));
         g->error.store(code);
     }
     g->cv.notify_all();
@@ -100,13 +118,13 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         bool all_done = true;
         for (int b = 0; b < g->B; b++) {
             BatchIngest::Seq& S = g->seq[b];
-            if (S.finished.load() || S.next >= S.n) continue;
+            if ((S.ring < S.n && S.finished.load()) || S.next >= S.n) continue;
             all_done = false;
             const int rel = S.released.load();
-            const int room = std::min(rel + g->ring, S.n) - S.next;
+            const int room = std::min(rel + S.ring, S.n) - S.next;
             if (room <= 0) continue;
             const int ahead = S.next - rel;
-            if (room >= g->F || ahead <= BatchIngest::LOW || S.next + room == S.n || S.waiting.load()) cand.push_back({ahead, b});
+            if (room >= S.F || ahead <= BatchIngest::LOW || S.next + room == S.n || S.waiting.load()) cand.push_back({ahead, b});
         }
         if (all_done) return;
         if (cand.empty()) {   // no sequence has room: the only place this thread sleeps
@@ -119,76 +137,177 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         take.clear();
         for (auto& c : cand) {
             BatchIngest::Seq& S = g->seq[c.second];
-            const int room = std::min(S.released.load() + g->ring, S.n) - S.next;
-            const int k = std::min({room, g->F, g->frames_per_round - (int)take.size()});
-            for (int i = 0; i < k; i++) take.push_back({c.second, S.next + i});
-            S.next += std::max(k, 0);
+            const int end = std::min(S.released.load() + S.ring, S.n);
+            for (int k = std::min(S.F, g->frames_per_round - (int)take.size()); k > 0 && S.next < end; ) {
+                const int f = S.next++;
+                // a slot that several sequences of a non-recycled feed cover (overlapping staged ranges) is built once, by the first of them
+                if (S.ring >= S.n && g->slot_rec[(size_t)(S.first + f)].load() != BatchIngest::pending(c.second)) continue;
+                take.push_back({c.second, f});
+                k--;
+            }
             if ((int)take.size() >= g->frames_per_round) break;
         }
+        if (take.empty()) continue;
         const int n = (int)take.size(), buf = (int)(round % BatchIngest::NBUF);
-        // the buffer's previous round (round - NBUF) has finished reading it (its event is not re-recorded before round - NBUF + NEV)
-        if (round >= BatchIngest::NBUF && (e = hipEventSynchronize(g->ev[(round - BatchIngest::NBUF) % BatchIngest::NEV])) != hipSuccess) {
+        // The buffer's previous round (round - NBUF) has finished with it: its round is done (a ring event is not re-recorded before
+        // round - NBUF + NEV) or, with dma_release, its DMA has read the staging buffer (the landing buffer is overwritten by a later DMA on
+        // the same in-order stream, after that round's kernels).
+        if (round >= BatchIngest::NBUF &&
+            (e = hipEventSynchronize(g->dma_release ? g->copied[buf] : g->ev[g->ev_index(round - BatchIngest::NBUF)])) != hipSuccess) {
             fail(g, PMV_ERR_HIP, "hipEventSynchronize", e); return;
         }
         uint8_t* blk = g->h_stage + (size_t)buf * g->buf_bytes;
         PyrListEntry* tab = (PyrListEntry*)blk;
         // device address of the round's block as the kernels see it: the landing buffer (copy) or the mapped staging buffer
         const uint8_t* dblk = g->copy_mode ? g->d_land + (size_t)buf * g->buf_bytes : g->dm_stage + (size_t)buf * g->buf_bytes;
+        // Consecutive slots, all in place or one sequence's consecutive frames (every round of a bracket): the range form, no table lookup in
+        // the kernels; in the copy form a pinned source is then DMA'd straight into the landing buffer.
+        const BatchIngest::Seq& S0 = g->seq[take[0].first];
+        bool range = true;
+        for (int i = 1; i < n && range; i++) {
+            const BatchIngest::Seq& S = g->seq[take[(size_t)i].first];
+            range = S.first + take[(size_t)i].second % S.ring == S0.first + take[0].second % S0.ring + i &&
+                    (S0.src ? take[(size_t)i].first == take[0].first && take[(size_t)i].second == take[0].second + i : !S.src);
+        }
+        const bool direct = range && g->dma_release && S0.dev;
         const auto tm0 = std::chrono::steady_clock::now();
-        bool copied = false;
+        int nc = 0, nh = 0;   // frames copied into staging, frames from host memory
         for (int i = 0; i < n; i++) {
             const BatchIngest::Seq& S = g->seq[take[(size_t)i].first];
             const int f = take[(size_t)i].second;
-            tab[i].slot = S.first + f % g->ring;
+            tab[i].slot = S.first + f % S.ring;
             tab[i].pad = 0;
+            tab[i].src = nullptr;   // staged: level 0 in place
+            if (!S.src) continue;
+            nh++;
+            if (direct) { tab[i].src = dblk + BatchIngest::HDR + (size_t)i * g->fb; continue; }
             if (!g->copy_mode && S.dev) { tab[i].src = S.dev + (size_t)f * g->fb; continue; }   // the caller's pinned frame, in place
-            memcpy(blk + BatchIngest::HDR + (size_t)i * g->fb, S.src + (size_t)f * g->fb, g->fb);
-            tab[i].src = dblk + BatchIngest::HDR + (size_t)i * g->fb;
-            copied = true;
+            memcpy(blk + BatchIngest::HDR + (size_t)nc * g->fb, S.src + (size_t)f * g->fb, g->fb);
+            tab[i].src = dblk + BatchIngest::HDR + (size_t)nc * g->fb;
+            nc++;
         }
-        if (copied) g->t_memcpy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
-        if (g->copy_mode && (e = hipMemcpyAsync((void*)dblk, blk, BatchIngest::HDR + (size_t)n * g->fb, hipMemcpyHostToDevice, g->stream)) != hipSuccess) {
-            fail(g, PMV_ERR_HIP, "hipMemcpyAsync", e); return;
+        if (nc) g->t_memcpy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
+        if (g->copy_mode) {   // frames only for the range form; the table (+ frames) for the list form
+            const uint8_t* from = direct ? S0.src + (size_t)take[0].second * g->fb : range ? blk + BatchIngest::HDR : blk;
+            const size_t off = range ? BatchIngest::HDR : 0;
+            const size_t bytes = range ? (size_t)(direct ? n : nc) * g->fb : nc ? BatchIngest::HDR + (size_t)nc * g->fb : (size_t)n * sizeof(PyrListEntry);
+            if (bytes && (e = hipMemcpyAsync((void*)(dblk + off), from, bytes, hipMemcpyHostToDevice, g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipMemcpyAsync", e); return; }
+            if ((e = hipEventRecord(g->copied[buf], g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventRecord", e); return; }
         }
-        const PyrListEntry* dtab = (const PyrListEntry*)dblk;
-        if ((e = launch_pad_level0_list(g->stream, ctx->d_slots, g->L, dtab, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pad_level0_list", e); return; }
+        const int first = range ? tab[0].slot : 0;
+        const PyrListEntry* dtab = range ? nullptr : (const PyrListEntry*)dblk;
+        if ((e = launch_pad_level0(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pad_level0", e); return; }
         for (int l = 1; l < g->L.n_levels; l++)
-            if ((e = launch_pyrdown_list(g->stream, ctx->d_slots, g->L, l, dtab, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown_list", e); return; }
+            if ((e = launch_pyrdown(g->stream, ctx->d_slots, g->L, l, first, n, dtab)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
         {
             std::lock_guard<std::mutex> lk(g->ev_mu);
-            if ((e = hipEventRecord(g->ev[round % BatchIngest::NEV], g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventRecord", e); return; }
+            const size_t k = g->ev_index(round);
+            if (k == g->ev.size()) {   // (per_round only: the ring's NEV events exist)
+                hipEvent_t ev;
+                if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventCreateWithFlags", e); return; }
+                g->ev.push_back(ev);
+            }
+            if ((e = hipEventRecord(g->ev[k], g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventRecord", e); return; }
         }
         for (auto& t : take) {
             const BatchIngest::Seq& S = g->seq[t.first];
-            g->slot_state[(size_t)(S.first + t.second % g->ring)].store(((long long)t.second << 32) | round);   // (seq_cst: see acquire)
+            g->slot_rec[(size_t)(S.first + t.second % S.ring)].store(((long long)t.second << 32) | round);   // (seq_cst: see acquire)
         }
-        g->rounds++; g->frames += n; g->bytes += (long long)n * (long long)g->fb;
+        g->rounds++; g->frames += n; g->bytes += (long long)nh * (long long)g->fb;
         round++;
         if (g->waiters.load() > 0) { std::lock_guard<std::mutex> lk(g->mu); g->cv.notify_all(); }
     }
 }
 
+// Before a kernel reads `slot` (covered by the feed): waits on the host until its build has been enqueued, and returns the round that builds
+// it. A feed that recycles slots: the frame sequence `seq` (the caller's own thread) needs in that slot. Otherwise every slot is built once,
+// and any reader may wait for it.
+int acquire(BatchIngest* g, int seq, int slot, int* round) {
+    BatchIngest::Seq* S = seq >= 0 && seq < g->B ? &g->seq[seq] : nullptr;
+    int f = -1;   // the frame needed, -1 = any
+    if (!g->per_round) {
+        if (!S || slot < S->first || slot >= S->first + S->ring) {
+            set_err(g->ctx, "feeder: sequence %d asked for slot %d outside its ring", seq, slot);
+            return PMV_ERR_INVALID;
+        }
+        const int pos = slot - S->first, rel = S->released.load(std::memory_order_relaxed);   // (this thread is the only writer of `released`)
+        f = rel + ((pos - rel % S->ring) % S->ring + S->ring) % S->ring;   // the one frame of [rel, rel + ring) that lives in this slot
+        if (f >= S->n) {
+            set_err(g->ctx, "feeder: sequence %d asked for slot %d (frame %d): past its %d frames", seq, slot, f, S->n);
+            return PMV_ERR_INVALID;
+        }
+    }
+    auto have = [&](long long st) { return st >= 0 && (f < 0 || (int)(st >> 32) == f); };
+    long long st = g->slot_rec[(size_t)slot].load();
+    if (!have(st)) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::unique_lock<std::mutex> lk(g->mu);
+        if (S) S->waiting.store(1);   // served in the next round whatever its room (initialise() may need more frames than F at once)
+        g->waiters.fetch_add(1);
+        // (seq_cst on both sides: either this load sees the round's record, or the feeder thread sees the waiter and notifies)
+        while (!have(st = g->slot_rec[(size_t)slot].load()) && !g->error.load()) g->cv.wait_for(lk, std::chrono::milliseconds(2));
+        g->waiters.fetch_sub(1);
+        if (S) S->waiting.store(0);
+        lk.unlock();
+        g->wait_ns += (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        if (!have(st)) { set_err(g->ctx, "%s", g->err); return g->error.load(); }
+    }
+    *round = (int)(st & 0xffffffffll);
+    return PMV_OK;
+}
+
 }  // namespace
 
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
+#define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
-int batch_ingest_begin(pmv_ctx* ctx, int B, const int* first_slot, const int* n_frames, const uint8_t* const* host_frames, int ring, int w, int h,
-                       BatchIngest** out) {
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h) {
     CKC(hipSetDevice(ctx->device));
-    if (!ctx->bingest) {
+    if (!gp) {
         BatchIngest* g = new BatchIngest();
-        ctx->bingest = g;
+        gp = g;
         CKC(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+        g->ev.resize(BatchIngest::NEV);
         for (auto& ev : g->ev) CKC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        g->slot_state.reset(new std::atomic<long long>[(size_t)ctx->n_slots]);
+        for (auto& ev : g->copied) CKC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        g->slot_rec.reset(new std::atomic<long long>[(size_t)ctx->n_slots]);
+        for (int s = 0; s < ctx->n_slots; s++) g->slot_rec[(size_t)s].store(BatchIngest::NONE);
     }
-    BatchIngest* g = ctx->bingest;
+    BatchIngest* g = gp;
+    const int B = (int)seqs.size();
+    g->seq.reset(new BatchIngest::Seq[(size_t)B]);
+    bool host = false;
+    int sum_F = 0;
+    g->per_round = true;
+    for (int b = 0; b < B; b++) {
+        BatchIngest::Seq& S = g->seq[b];
+        const FeedSeq& q = seqs[(size_t)b];
+        S.first = q.first; S.n = q.n; S.ring = q.ring; S.src = q.src; S.dev = nullptr;
+        S.F = kind == FEED_BRACKET ? BatchIngest::BRACKET_CHUNK : kind == FEED_STAGED ? BatchIngest::STAGED_CHUNK : std::max(1, std::min(8, S.ring / 2));
+        sum_F += S.F;
+        g->per_round = g->per_round && S.ring >= S.n;
+        if (S.src) {
+            host = true;
+            // A kernel is never handed a pageable address (XNACK is off). Pinned memory whose device address is its host address (hipHostMalloc'ed,
+            // torch's pin_memory) is read in place; anything else - pageable, or registered under another device address - is copied into staging.
+            hipPointerAttribute_t attr;
+            if (hipPointerGetAttributes(&attr, S.src) == hipSuccess && attr.type == hipMemoryTypeHost && attr.hostPointer == (const void*)S.src &&
+                attr.devicePointer == attr.hostPointer)
+                S.dev = S.src;
+            (void)hipGetLastError();   // (a malloc'ed pointer makes hipPointerGetAttributes fail: that is the "pageable" answer)
+        }
+    }
     g->fb = (size_t)w * h;
-    g->frames_per_round = (int)std::max<size_t>(1, std::min<size_t>(BatchIngest::ROUND_FRAMES, BatchIngest::ROUND_BYTES / g->fb));
-    const size_t need = (BatchIngest::HDR + (size_t)g->frames_per_round * g->fb + 4095) & ~(size_t)4095;
-    static_assert(BatchIngest::ROUND_FRAMES * sizeof(PyrListEntry) <= BatchIngest::HDR, "the slot table fits its header block");
-    const char* mode = getenv("PMV_BATCH_INGEST");   // diagnostic: copy | mapped (default); no result depends on it
-    g->copy_mode = mode && !strcmp(mode, "copy");
+    g->frames_per_round = host ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)BatchIngest::ROUND_FRAMES, BatchIngest::ROUND_BYTES / g->fb, (size_t)sum_F}))
+                               : BatchIngest::TABLE;
+    const size_t need = (BatchIngest::HDR + (host ? (size_t)g->frames_per_round * g->fb : 0) + 4095) & ~(size_t)4095;
+    static_assert(BatchIngest::ROUND_FRAMES <= BatchIngest::TABLE, "a round's slot table fits its header block");
+    // How host frames reach level 0: PMV_BATCH_INGEST=copy | mapped; by default mapped for a streamed batch and copy for a bracket
+    // (the DMA into HBM the single-sequence path has always used). A staged feed's slot tables are always copied into HBM, so its kernels do
+    // not read them across the link. No result depends on it.
+    const char* mode = getenv("PMV_BATCH_INGEST");
+    g->copy_mode = !host || (mode ? !strcmp(mode, "copy") : kind == FEED_BRACKET);
+    g->dma_release = g->copy_mode && kind != FEED_STREAMED;   // (a streamed batch keeps the form it was measured with)
     if (g->buf_bytes < need) {
         if (g->h_stage) { CKC(hipHostFree(g->h_stage)); g->h_stage = nullptr; }
         if (g->d_land) { CKC(hipFree(g->d_land)); g->d_land = nullptr; g->land_bytes = 0; }
@@ -201,63 +320,47 @@ int batch_ingest_begin(pmv_ctx* ctx, int B, const int* first_slot, const int* n_
         CKC(hipMalloc(&g->d_land, BatchIngest::NBUF * g->buf_bytes));
         g->land_bytes = g->buf_bytes;
     }
-    g->seq.reset(new BatchIngest::Seq[(size_t)B]);
-    g->ctx = ctx; g->B = B; g->ring = ring; g->w = w; g->h = h;
-    g->F = std::max(1, std::min(8, ring / 2));
+    g->ctx = ctx; g->B = B; g->w = w; g->h = h;
     g->L = layout_for(ctx, w, h);
-    for (int b = 0; b < B; b++) {
-        BatchIngest::Seq& S = g->seq[b];
-        S.first = first_slot[b]; S.n = n_frames[b]; S.src = host_frames[b]; S.dev = nullptr;
-        // A kernel is never handed a pageable address (XNACK is off). Pinned memory whose device address is its host address (hipHostMalloc'ed,
-        // torch's pin_memory) is read in place; anything else - pageable, or registered under another device address - is copied into staging.
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, S.src) == hipSuccess && attr.type == hipMemoryTypeHost && attr.hostPointer == (const void*)S.src &&
-            attr.devicePointer == attr.hostPointer)
-            S.dev = S.src;
-        (void)hipGetLastError();   // (a malloc'ed pointer makes hipPointerGetAttributes fail: that is the "pageable" answer)
-        for (int i = 0; i < ring; i++) g->slot_state[(size_t)(S.first + i)].store(-1);
-    }
-    g->stop.store(false); g->error.store(0); g->err[0] = 0; g->waiters.store(0);
+    // every slot of the feed carries the feed's geometry and counts as built from here on: its readers wait for its round in slot_ready. The
+    // first sequence that covers a slot builds it.
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i < g->seq[b].ring; i++) {
+            const size_t s = (size_t)(g->seq[b].first + i);
+            ctx->slot_layout[s] = g->L;
+            ctx->slot_state[s] = SLOT_BUILT;
+            if (g->slot_rec[s].load() == BatchIngest::NONE) g->slot_rec[s].store(BatchIngest::pending(b));
+        }
+    g->stop.store(false); g->error.store(0); g->err[0] = 0; g->waiters.store(0); g->front_waited.store(-1);
     g->rounds = g->frames = g->bytes = 0; g->t_memcpy = g->t_room = 0; g->wait_ns.store(0);
+    g->open = true;
     g->th = std::thread(ingest_loop, ctx, g);
-    *out = g;
     return PMV_OK;
 }
 
-int batch_ingest_acquire(BatchIngest* g, int seq, int slot, int* round) {
-    BatchIngest::Seq& S = g->seq[seq];
-    const int pos = slot - S.first, rel = S.released.load(std::memory_order_relaxed);   // (this thread is the only writer of `released`)
-    // the one frame of [rel, rel + ring) that lives in this slot
-    const int f = rel + ((pos - rel % g->ring) % g->ring + g->ring) % g->ring;
-    if (pos < 0 || pos >= g->ring || f >= S.n) {
-        set_err(g->ctx, "batch ingest: sequence %d asked for slot %d (frame %d): outside its ring [%d, %d) or past its %d frames", seq, slot, f, S.first, S.first + g->ring, S.n);
-        return PMV_ERR_INVALID;
-    }
-    auto have = [&](long long st) { return st >= 0 && (int)(st >> 32) == f; };
-    long long st = g->slot_state[(size_t)slot].load();
-    if (!have(st)) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::unique_lock<std::mutex> lk(g->mu);
-        S.waiting.store(1);   // served in the next round whatever its room (initialise() may need more frames than F at once)
-        g->waiters.fetch_add(1);
-        // (seq_cst on both sides: either this load sees the round's record, or the ingest thread sees the waiter and notifies)
-        while (!have(st = g->slot_state[(size_t)slot].load()) && !g->error.load()) g->cv.wait_for(lk, std::chrono::milliseconds(2));
-        g->waiters.fetch_sub(1);
-        S.waiting.store(0);
-        lk.unlock();
-        g->wait_ns += (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (!have(st)) { set_err(g->ctx, "%s", g->err); return g->error.load(); }
-    }
-    *round = (int)(st & 0xffffffffll);
-    return PMV_OK;
-}
+bool batch_ingest_active(const BatchIngest* g) { return g && g->open; }
 
-hipError_t batch_ingest_wait_gpu(void* arg, hipStream_t s, int round) {
-    BatchIngest* g = (BatchIngest*)arg;
-    // The round's event: recorded for this round or, NEV rounds later, for a later round of the same in-order stream (already enqueued, and
-    // dependent on nothing but that stream): waiting for it waits at least for `round`.
+hipError_t batch_ingest_wait_gpu(BatchIngest* g, hipStream_t s, int round) {
+    // The round's event: recorded for this round or, in a ring, NEV rounds later for a later round of the same in-order stream (already
+    // enqueued, and dependent on nothing but that stream): waiting for it waits at least for `round`.
     std::lock_guard<std::mutex> lk(g->ev_mu);
-    return hipStreamWaitEvent(s, g->ev[round % BatchIngest::NEV], 0);
+    return hipStreamWaitEvent(s, g->ev[g->ev_index(round)], 0);
+}
+
+int slot_ready(pmv_ctx* ctx, int slot, BatchIngest* g, int seq, hipStream_t s, int* round) {
+    int r = -1;
+    if (g && g->open && g->slot_rec[(size_t)slot].load() != BatchIngest::NONE) {   // a slot of the feed
+        const int rc = acquire(g, seq, slot, &r);
+        if (rc != PMV_OK) return rc;
+        if (s && r > g->front_waited.load()) {   // (in-order stream: a wait for round r covers every earlier one)
+            CKC(batch_ingest_wait_gpu(g, s, r));
+            g->front_waited.store(r);
+        }
+    }
+    if (round) *round = r;
+    const uint8_t st = ctx->slot_state[(size_t)slot];
+    REQ(st == SLOT_BUILT, PMV_ERR_INVALID, "slot %d %s", slot, st == SLOT_EMPTY ? "holds no frame" : "was staged but its pyramid was never built");
+    return PMV_OK;
 }
 
 void batch_ingest_release(BatchIngest* g, int seq, int frame) {
@@ -271,17 +374,17 @@ void batch_ingest_finish(BatchIngest* g, int seq) {
 }
 
 int batch_ingest_end(pmv_ctx* ctx, BatchIngest* g) {
-    g->stop.store(true);
     if (g->th.joinable()) g->th.join();
     const hipError_t e = hipStreamSynchronize(g->stream);
     for (int b = 0; b < g->B; b++)
-        for (int i = 0; i < g->ring; i++) {
+        for (int i = 0; i < g->seq[b].ring; i++) {
             const int s = g->seq[b].first + i;
-            ctx->slot_layout[(size_t)s] = g->L;
-            if (g->slot_state[(size_t)s].load() < 0) ctx->slot_layout[(size_t)s].n_levels = 0;   // never received a frame
+            const long long rec = g->slot_rec[(size_t)s].exchange(BatchIngest::NONE);
+            if (rec != BatchIngest::NONE && rec < 0) ctx->slot_state[(size_t)s] = g->seq[b].src ? SLOT_EMPTY : SLOT_STAGED;   // never received its frame
         }
+    g->open = false;
     if (g->error.load()) { set_err(ctx, "%s", g->err); return g->error.load(); }
-    if (e != hipSuccess) { set_err(ctx, "batch ingest: hipStreamSynchronize: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
+    if (e != hipSuccess) { set_err(ctx, "feeder: hipStreamSynchronize: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
     return PMV_OK;
 }
 
@@ -290,17 +393,42 @@ void batch_ingest_stats(const BatchIngest* g, double* out) {
     out[3] = g->t_memcpy; out[4] = g->t_room; out[5] = 1e-9 * (double)g->wait_ns.load();
 }
 
-void batch_ingest_destroy(pmv_ctx* ctx) {
-    BatchIngest* g = ctx->bingest;
+void batch_ingest_destroy(BatchIngest*& g) {
     if (!g) return;
     g->stop.store(true);
     if (g->th.joinable()) g->th.join();
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
     for (auto& ev : g->ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : g->copied) if (ev) (void)hipEventDestroy(ev);
     if (g->h_stage) (void)hipHostFree(g->h_stage);
     if (g->d_land) (void)hipFree(g->d_land);
     delete g;
-    ctx->bingest = nullptr;
+    g = nullptr;
 }
 
 }  // namespace pmv
+
+using namespace pmv;
+
+extern "C" {
+
+// A bracket is a feed of one sequence from host memory whose ring is not recycled.
+int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h) {
+    REQ(ctx && gray, PMV_ERR_INVALID, "pmv_frames_stream_begin: null argument");
+    REQ(first_slot >= 0 && n >= 1 && first_slot + n <= ctx->n_slots, PMV_ERR_CAPACITY, "pmv_frames_stream_begin: slots [%d,%d) out of range (n_slots %d)", first_slot, first_slot + n, ctx->n_slots);
+    REQ(w >= 40 && h >= 40 && w <= ctx->max_w && h <= ctx->max_h, PMV_ERR_CAPACITY, "pmv_frames_stream_begin: frame %dx%d outside capacity %dx%d", w, h, ctx->max_w, ctx->max_h);
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_frames_stream_begin: a stream is already open (pmv_frames_stream_end first)");
+    CKC(hipSetDevice(ctx->device));
+    // frames in the slots about to be overwritten may still be read by work in flight on the front-end stream
+    CKC(hipStreamSynchronize(ctx->s_front));
+    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray}}, w, h);
+}
+
+int pmv_frames_stream_end(pmv_ctx* ctx) {
+    REQ(ctx, PMV_ERR_INVALID, "null ctx");
+    if (!batch_ingest_active(ctx->ingest)) return PMV_OK;
+    CKC(hipSetDevice(ctx->device));
+    return batch_ingest_end(ctx, ctx->ingest);
+}
+
+}  // extern "C"

@@ -8,9 +8,11 @@
 #include <mutex>
 
 namespace pmv {
-struct Ingest;                      // streamed frame ingest (ingest.hip)
 struct BatchEngine;                 // multi-sequence combiners (batch_engine.hip)
-struct BatchIngest;                 // streamed ingest of a batched run into per-sequence slot rings (ingest_batch.hip)
+struct BatchIngest;                 // the feeder: background pyramid builds of frame slots, from host memory or in place (ingest_batch.hip)
+// what a frame slot holds (pmv_ctx::slot_state); written only while the slot has no reader: by the synchronous calls, and by the feeder
+// before the sequences it serves start and after they end
+enum SlotState : uint8_t { SLOT_EMPTY = 0, SLOT_STAGED, SLOT_BUILT };   // SLOT_STAGED: level 0 only (pmv_frames_stage)
 constexpr int MAX_CELLS = 64;       // 1920x1080 -> 8x5 = 40 cells of 255x255
 constexpr int MAX_PER_CELL = 4096;    // also the capacity of an "unlimited" (max_per_cell <= 0) goodFeaturesToTrack call
 struct BackendBuffers;              // PnP / BA device workspaces (backend.hip)
@@ -31,9 +33,10 @@ struct pmv_ctx {
     int max_w = 0, max_h = 0, n_slots = 0, max_tracks = 0, max_ba_cams = 0, max_ba_points = 0, max_ba_obs = 0;
     hipStream_t s_front = nullptr, s_back = nullptr;
     pmv::PyrLayout cap;                       // geometry of the largest frame; cap.slot_bytes = slot pitch
-    std::vector<pmv::PyrLayout> slot_layout;  // per slot: n_levels 0 = empty, <0 = staged only, >0 = pyramid built
+    std::vector<pmv::PyrLayout> slot_layout;  // per slot: geometry of the frame it holds ...
+    std::vector<uint8_t> slot_state;          // ... and what of it is there (pmv::SlotState)
     uint8_t* d_slots = nullptr;
-    // landing area of host frames on their way into the slots: TIGHT_FRAMES tight gray frames (H2D copies are contiguous; k_pad_level0 takes
+    // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;
     uint8_t* d_tight = nullptr;
@@ -70,8 +73,9 @@ struct pmv_ctx {
     // bit for bit only within one mode.
     int ba_mode = 0;
     pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch
-    pmv::Ingest* ingest = nullptr;      // non-null while a pmv_frames_stream_begin .. _end bracket is open
-    pmv::BatchIngest* bingest = nullptr; // created by the first pmv_pipeline_run_batch_streamed (stream, staging buffers kept across calls)
+    pmv::BatchIngest* ingest = nullptr;  // feeder of pmv_frames_stream_begin .. _end brackets (created by the first; stream, buffers kept)
+    pmv::BatchIngest* bingest = nullptr; // feeder of pmv_pipeline_run_batch[_streamed] (created by the first that needs one)
+    double bingest_stats[PMV_BATCH_INGEST_STATS] = {};   // counters of the last pmv_pipeline_run_batch_streamed (pmv_batch_ingest_stats)
     pmv::Profiler prof;
     pmv_call_log log;
     std::mutex err_mu;                  // set_err from several host threads (batch engine)
@@ -84,16 +88,13 @@ const char* thread_error();         // the last message set_err wrote on the cal
 PyrLayout make_layout(int w, int h);
 int backend_create(pmv_ctx* c);     // allocates PnP/BA workspaces
 void backend_destroy(pmv_ctx* c);
-// pyramid levels of `n` consecutive slots with identical geometry L, on `stream` (pmv_frames_build and the ingest thread)
-int build_levels_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n, const PyrLayout& L, const uint8_t* tight = nullptr);
 PyrLayout layout_for(pmv_ctx* ctx, int w, int h);
-// pmv_frames_build on a given stream (no host synchronisation)
-int pmv_frames_build_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n);
-// streamed ingest: make the front-end stream wait until `slot` has been copied and its pyramid built (no-op without a stream)
-int ingest_require(pmv_ctx* ctx, int slot);
-void ingest_destroy(pmv_ctx* ctx);
-bool ingest_open(pmv_ctx* ctx);     // a pmv_frames_stream_begin bracket is open on the context
-void batch_ingest_destroy(pmv_ctx* ctx);
+// The readiness rule of frame slot `slot`: every reader of a pyramid goes through it (the synchronous calls, the batch engine's sequence
+// threads and its combiners). When `feed` covers the slot (for sequence `seq` of the feed), waits on the host until the feed round that
+// builds the frame is enqueued; then `s`, if given, waits for that round on the GPU, and *round, if given, receives it (-1: none). Then the
+// slot must hold a built pyramid (PMV_ERR_INVALID).
+int slot_ready(pmv_ctx* ctx, int slot, BatchIngest* feed = nullptr, int seq = 0, hipStream_t s = nullptr, int* round = nullptr);
+void batch_ingest_destroy(BatchIngest*& g);
 void batch_engine_destroy(pmv_ctx* ctx);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();

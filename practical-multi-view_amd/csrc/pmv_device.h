@@ -140,13 +140,13 @@ struct __attribute__((aligned(32))) LKBlock {
 hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout& L, const LKParams& P,
                            float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
 hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, int stride, uint8_t* d_gray);   // cv::cvtColor(BGR2GRAY), 8-bit
-hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight = nullptr /* tight gray frames to take level 0 from; null: in place */);
-hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, int first_slot, int n);
-// one entry of a slot-list pyramid build (k_pad_level0_list / k_pyrdown_list): destination slot and, for level 0, the device-visible
-// address of the tight gray frame (HBM landing area or mapped pinned host memory)
+// one entry of a slot-list pyramid build (the feeder): destination slot and, for level 0, the device-visible address of the tight gray
+// frame (HBM landing area or mapped pinned host memory), null = already staged in the slot
 struct PyrListEntry { const uint8_t* src; int slot; int pad; };
-hipError_t launch_pad_level0_list(hipStream_t s, uint8_t* slots, const PyrLayout& L, const PyrListEntry* list, int n);
-hipError_t launch_pyrdown_list(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, const PyrListEntry* list, int n);
+// Pyramid stages of n slots: the range first_slot .. first_slot + n - 1 (level 0 from n tight gray frames at `tight`, null: in place), or the n
+// entries of a device-visible `list`.
+hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight = nullptr, const PyrListEntry* list = nullptr);
+hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, int first_slot, int n, const PyrListEntry* list = nullptr);
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);

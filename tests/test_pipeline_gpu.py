@@ -238,11 +238,11 @@ def test_subsequences_are_independent_runs_over_their_image_range(pmv, gpu_ctx_f
 
 
 def test_streamed_ingest_is_bit_identical_to_staged_frames(pmv, gpu_ctx_factory):
-    """frames handed over in HOST memory and streamed into HBM chunk by chunk (ingest thread, third stream, pyramids
-    per chunk) while the pipeline is already tracking give the same features and poses as pmv_frames_stage + a run with all
-    pyramids built up front - from pageable memory (pinned ring) and from pinned memory (DMA in place), threaded and sequential,
-    also when the frame count is not a multiple of the chunk size and when the context is reused."""
-    cfg, n = K00, 75      # 4 full chunks of 16 + 11
+    """frames handed over in HOST memory and streamed into HBM round by round (the feeder thread, third stream, pyramids
+    per round) while the pipeline is already tracking give the same features and poses as pmv_frames_stage + a run with all
+    pyramids built up front - from pageable memory (pinned staging) and from pinned memory (read in place), threaded and sequential,
+    also when the frame count is not a multiple of the round size and when the context is reused."""
+    cfg, n = K00, 75      # 4 full rounds of 16 + 11
     frames, poses = pmv.synth_sequence(1002, 0, n, cfg["w"], cfg["h"], cfg["fx"], cfg["fy"], cfg["cx"], cfg["cy"], nthreads=16)
     K = np.array([cfg["fx"], 0, cfg["cx"], 0, cfg["fy"], cfg["cy"], 0, 0, 1.0])
     ctx = gpu_ctx_factory(cfg["w"], cfg["h"], n_slots=n, max_tracks=4096)
@@ -260,7 +260,7 @@ def test_streamed_ingest_is_bit_identical_to_staged_frames(pmv, gpu_ctx_factory)
     pinned.numpy()[:] = frames
     got = ctx2.pipeline_run(n, cfg["w"], cfg["h"], K, poses, threaded=1, n_threads=4, host_frames=pinned.numpy())
     assert np.array_equal(got.poses, ref.poses)
-    # the plain C-ABI calls on a streaming context: LK between two late slots waits for their chunk and matches the staged context
+    # the plain C-ABI calls on a streaming context: LK between two late slots waits for their round and matches the staged context
     ctx2.frames_stream_begin(0, frames)
     pts = np.stack(np.meshgrid(np.arange(100, 1100, 90), np.arange(60, 330, 70)), -1).reshape(-1, 2).astype(np.float32)
     a = ctx2.lk_track(n - 2, n - 1, pts)
@@ -270,6 +270,48 @@ def test_streamed_ingest_is_bit_identical_to_staged_frames(pmv, gpu_ctx_factory)
         assert np.array_equal(x, y)
     for l in range(ctx.num_levels(n - 1) + 1):
         assert np.array_equal(ctx2.get_level(n - 1, l, cfg["w"], cfg["h"]), ctx.get_level(n - 1, l, cfg["w"], cfg["h"]))
+
+
+@pytest.mark.timeout(600)
+def test_overlapping_staged_subsequences_in_one_batch(pmv, gpu_ctx_factory):
+    """pmv_pipeline_run_batch does not require disjoint slot ranges: subsequences that overlap at another offset ([0, 48) and [24, 72)) or
+    repeat a range exactly, all with their pyramids built inside the call, each equal their own single run - and the call returns"""
+    cfg = K00
+    frames, gt = pmv.synth_sequence(1005, 0, 72, cfg["w"], cfg["h"], cfg["fx"], cfg["fy"], cfg["cx"], cfg["cy"], nthreads=16)
+    K = np.array([cfg["fx"], 0, cfg["cx"], 0, cfg["fy"], cfg["cy"], 0, 0, 1.0])
+    pieces = [(0, 48), (24, 48), (0, 48)]
+    big = gpu_ctx_factory(cfg["w"], cfg["h"], n_slots=72, max_tracks=1024)
+    big.frames_stage(0, frames)
+    got = big.pipeline_run_batch([(st, n, gt[st: st + n]) for st, n in pieces], cfg["w"], cfg["h"], K, threaded=0)
+    one = gpu_ctx_factory(cfg["w"], cfg["h"], n_slots=48, max_tracks=1024)
+    for (st, n), g in zip(pieces, got):
+        one.frames_stage(0, frames[st: st + n])
+        s = one.pipeline_run(n, cfg["w"], cfg["h"], K, gt[st: st + n], threaded=1, n_threads=2)
+        assert np.array_equal(g.poses, s.poses), f"subsequence at {st} differs from its single run"
+        assert len(g.features) == len(s.features) and all(np.array_equal(a, b) for a, b in zip(g.features, s.features))
+    for sl in range(72):   # every slot holds the pyramid of its own frame
+        assert big.num_levels(sl) == one.num_levels(0)
+
+
+def test_upload_outside_an_open_bracket_keeps_both_intact(pmv, gpu_ctx_factory):
+    """pmv_frame_upload into a slot outside an open pmv_frames_stream_begin bracket, while the bracket's frames are on their way in: that
+    slot and every streamed slot hold exactly the padded pyramid levels of a fresh context that staged and built the same frames"""
+    cfg, n = K00, 48
+    w, h = cfg["w"], cfg["h"]
+    frames, _ = pmv.synth_sequence(1006, 0, n + 4, w, h, cfg["fx"], cfg["fy"], cfg["cx"], cfg["cy"], nthreads=16)
+    ctx = gpu_ctx_factory(w, h, n_slots=n + 1, max_tracks=1024)
+    ctx.frames_stream_begin(0, frames[:n])
+    for k in range(n, n + 4):      # several uploads while the bracket runs; the last one is what slot n must hold
+        ctx.frame_upload(n, frames[k])
+    ctx.frames_stream_end()
+    ref = gpu_ctx_factory(w, h, n_slots=n + 1, max_tracks=1024)
+    ref.frames_stage(0, frames[:n])
+    ref.frames_stage(n, frames[n + 3:n + 4])
+    ref.frames_build(0, n + 1)
+    for s in range(n + 1):
+        assert ctx.num_levels(s) == ref.num_levels(s) > 0
+        for l in range(ref.num_levels(s) + 1):
+            assert np.array_equal(ctx.get_level_padded(s, l, w, h), ref.get_level_padded(s, l, w, h)), f"slot {s} level {l}"
 
 
 def test_plugin_error_in_the_backend_thread_is_returned_not_fatal(pmv, gpu_ctx_factory):
