@@ -61,14 +61,30 @@ int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, 
 /* The same from a colour image as Frame::Frame(file) reads it (Frame.cpp:33: imread(IMREAD_COLOR) = 8-bit BGR, `stride` bytes per row):
  * cv::cvtColor(BGR2GRAY) (Frame.cpp:40-41) runs on the device, then the pyramid as above. Identity for B = G = R (KITTI's gray PNGs). */
 int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int h, int stride);
-/* Batch form: n frames, tightly packed (n*w*h bytes), into slots first_slot..first_slot+n-1. The gray data
+/* The format of the host frames that the throughput paths take: pmv_frames_stage, pmv_frames_stream_begin, pmv_pipeline_run_streamed and
+ * pmv_pipeline_run_batch_streamed (their `gray` / `host_frames` arguments). The reference never sees a gray image on input: Frame::Frame(file)
+ * reads with imread(IMREAD_COLOR) and Frame::init runs cvtColor(BGR2GRAY) (Frame.cpp:33,40-41).
+ *   PMV_FRAMES_GRAY  w * h bytes per frame (the default);
+ *   PMV_FRAMES_BGR   tight 8-bit BGR, 3 * w bytes per row and 3 * w * h per frame, at any alignment. The conversion
+ *                    gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 runs on the device inside the kernel that writes level 0
+ *                    (k_pad_level0_bgr), so a slot holds exactly what the gray path would have left for the converted image and every
+ *                    result is bit-identical to the gray run on cv::cvtColor's output. Identity for B = G = R (KITTI's gray PNGs).
+ * A context setting like pmv_set_ba_mode; pmv_frame_upload and pmv_frame_upload_bgr keep their own explicit formats, and
+ * pmv_pipeline_params is not involved. Wherever the calls above speak of w * h gray bytes, a BGR context reads three times as many: staging
+ * chunks, ingest rounds and landing buffers keep their byte sizes and hold a third as many frames, and pmv_batch_ingest_stats counts the
+ * BGR bytes.
+ *   Errors: a format other than the two above is PMV_ERR_INVALID; a call while a pmv_frames_stream_begin bracket or a batched run
+ *   (pmv_pipeline_run_batch, pmv_pipeline_run_batch_streamed) is open on the context is PMV_ERR_INVALID, and the format stays as it was. */
+enum pmv_frame_format { PMV_FRAMES_GRAY = 0, PMV_FRAMES_BGR = 1 };
+int pmv_set_frame_format(pmv_ctx* ctx, int format);
+/* Batch form: n frames, tightly packed (n*w*h bytes; BGR: n*3*w*h), into slots first_slot..first_slot+n-1. The gray data
  * is staged to HBM first (pmv_frames_stage: level 0 of each slot; a slot keeps no second copy of the frame), the pyramids are
  * built by pmv_frames_build (level 0's REFLECT_101 frame in place + the levels above) so that a benchmark can time the build with
  * inputs already resident in HBM. */
 int pmv_frames_stage(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h);
 int pmv_frames_build(pmv_ctx* ctx, int first_slot, int n);
 /* Streamed ingest (Frame::Frame / Frame::init + the front-end's per-frame load, Frame.cpp:31-42, OdometryPipeline.cpp:212-220):
- * n tightly packed gray frames in HOST memory (pageable, or pinned: then DMA'd straight from it) are moved into slots first_slot.. by the
+ * n tightly packed frames (gray, or BGR: pmv_set_frame_format) in HOST memory (pageable, or pinned: then DMA'd straight from it) are moved into slots first_slot.. by the
  * context's feeder thread on its own HIP stream, round by round, each round's pyramids built as soon as its frames land.
  * pmv_frames_stream_begin returns at once; until pmv_frames_stream_end, pmv_lk_track / pmv_detect_* / pmv_knn_match on a slot of the
  * range first make the front-end stream wait for that slot's round (nothing else blocks), so tracking starts while later frames are
@@ -236,7 +252,7 @@ typedef struct pmv_pipeline_result pmv_pipeline_result;
 
 int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                      pmv_pipeline_result** out);
-/* The same run from n_frames gray frames in HOST memory: pmv_frames_stream_begin(ctx, 0, n_frames, host_frames, w, h), the run
+/* The same run from n_frames frames (gray, or BGR: pmv_set_frame_format) in HOST memory: pmv_frames_stream_begin(ctx, 0, n_frames, host_frames, w, h), the run
  * (build_pyramids ignored), pmv_frames_stream_end. Identical results; copies and pyramid builds overlap the tracking. */
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                               const uint8_t* host_frames, pmv_pipeline_result** out);
@@ -251,7 +267,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
 /* The same B sequences streamed from HOST memory through recycled frame slots (the reference loads one image per front-end iteration,
  * Frame.cpp:31-42, OdometryPipeline.cpp:212-229, and tracking reads only frames k-1 and k), so that the batch size is not capped by frame
  * storage: B x ring slots instead of the sum of all n_frames.
- *   Frames: sequence b's params[b].n_frames tightly packed gray frames at host_frames[b], pageable or pinned / registered; read only, several
+ *   Frames: sequence b's params[b].n_frames tightly packed frames (gray, or BGR: pmv_set_frame_format) at host_frames[b], pageable or pinned / registered; read only, several
  *     b may point at the same buffer; they stay valid until the call returns. A kernel never reads a pageable address: pinned memory
  *     mapped at its host address (hipHostMalloc, torch pin_memory) is read in place, anything else is copied into pinned staging first.
  *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot

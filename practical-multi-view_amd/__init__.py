@@ -34,7 +34,7 @@ class BaSummary(C.Structure):
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_sync",
-    "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
+    "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_lk_track", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -62,7 +62,32 @@ STAT_KEYS = ["lk_calls", "lk_points", "detect_calls", "pnp_calls", "pnp_points",
 BATCH_INGEST_KEYS = ["rounds", "frames", "bytes", "memcpy_s", "ingest_wait_s", "seq_wait_s"]   # pmv_batch_ingest_stats, in order
 
 
-def _batch_streamed_args(seqs, w, h, ring, first_slot):
+FRAME_FORMATS = {"gray": 0, "bgr": 1}   # pmv_frame_format of include/pmv_hip.h
+
+
+def _host_frames(frames, fmt, who, h=None, w=None, n=None):
+    """the host frames of a staged / streamed call as the library reads them. "bgr" (Context.set_frame_format): (n, h, w, 3) uint8 or a
+    ValueError before anything reaches the device; "gray": as before, converted to contiguous uint8."""
+    if fmt != "bgr":
+        f = np.ascontiguousarray(frames, np.uint8)
+        if f.ndim != 3 or (h is not None and f.shape[1:] != (h, w)) or (n is not None and f.shape[0] != n):
+            # (n, h, w, 3) on a gray context is a forgotten set_frame_format("bgr"): the library would read the interleaved bytes as gray frames
+            want = f"({'n' if n is None else n}, {'h' if h is None else h}, {'w' if w is None else w})"
+            raise ValueError(f"{who}: the context's frame format is gray: frames must be {want} uint8, got {f.shape} (set_frame_format(\"bgr\") for colour frames)")
+        return f
+    f = np.asarray(frames)
+    ok = f.dtype == np.uint8 and f.ndim == 4 and f.shape[3] == 3 and f.shape[0] >= 1
+    if ok and h is not None:
+        ok = f.shape[1:3] == (h, w)
+    if ok and n is not None:
+        ok = f.shape[0] == n
+    if not ok:
+        want = f"({'n' if n is None else n}, {'h' if h is None else h}, {'w' if w is None else w}, 3)"
+        raise ValueError(f"{who}: the context's frame format is BGR: frames must be {want} uint8, got {f.shape} {f.dtype}")
+    return np.ascontiguousarray(f)   # (a contiguous array, pinned or not, is passed as it is)
+
+
+def _batch_streamed_args(seqs, w, h, ring, first_slot, fmt="gray"):
     """shapes of pipeline_run_batch_streamed's arguments, checked before anything reaches the device: (frames, gt_poses, first_slot)"""
     if len(seqs) < 1:
         raise ValueError("pipeline_run_batch_streamed: no sequences")
@@ -74,7 +99,9 @@ def _batch_streamed_args(seqs, w, h, ring, first_slot):
             raise ValueError(f"pipeline_run_batch_streamed: sequence {b} must be (frames, gt_poses)")
         f, gt = seq
         f = np.asarray(f)
-        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[1:] != (h, w):
+        if fmt == "bgr":
+            f = _host_frames(f, fmt, f"pipeline_run_batch_streamed: sequence {b}", h, w)
+        elif f.dtype != np.uint8 or f.ndim != 3 or f.shape[1:] != (h, w):
             raise ValueError(f"pipeline_run_batch_streamed: sequence {b}: frames must be (n, {h}, {w}) uint8, got {f.shape} {f.dtype}")
         f = np.ascontiguousarray(f)   # (a contiguous array, pinned or not, is passed as it is)
         g = np.ascontiguousarray(gt, np.float64)
@@ -268,13 +295,27 @@ class Context:
         assert b.ndim == 3 and b.shape[2] == 3
         self._ck(self.lib.pmv_frame_upload_bgr(self.h, slot, _p(b, _u8p), b.shape[1], b.shape[0], 3 * b.shape[1]))
 
+    def set_frame_format(self, fmt):
+        """"gray" (default) or "bgr": what the host frames of frames_stage, frames_stream_begin, pipeline_run(host_frames=...) and
+        pipeline_run_batch_streamed hold (pmv_set_frame_format). With "bgr" they take (n, h, w, 3) uint8 BGR frames, as cv::imread(IMREAD_COLOR)
+        gives them, and the conversion to gray runs on the device inside the level-0 kernel; frame_upload / frame_upload_bgr are not affected."""
+        if not isinstance(fmt, str) or fmt not in FRAME_FORMATS:
+            raise ValueError(f"set_frame_format: format must be one of {sorted(FRAME_FORMATS)}, got {fmt!r}")
+        self._ck(self.lib.pmv_set_frame_format(self.h, FRAME_FORMATS[fmt]))
+        self._frame_format = fmt
+
+    @property
+    def frame_format(self):
+        return getattr(self, "_frame_format", "gray")
+
     def frames_stage(self, first_slot, frames):
-        f = np.ascontiguousarray(frames, np.uint8)
+        f = _host_frames(frames, self.frame_format, "frames_stage")
         self._ck(self.lib.pmv_frames_stage(self.h, first_slot, f.shape[0], _p(f, _u8p), f.shape[2], f.shape[1]))
 
     def frames_stream_begin(self, first_slot, frames):
-        """start streaming host frames (n, h, w) uint8 into slots first_slot..; `frames` must stay alive until frames_stream_end()"""
-        f = np.ascontiguousarray(frames, np.uint8)
+        """start streaming host frames (n, h, w) uint8 ((n, h, w, 3) BGR after set_frame_format("bgr")) into slots first_slot..; `frames` must
+        stay alive until frames_stream_end()"""
+        f = _host_frames(frames, self.frame_format, "frames_stream_begin")
         self._stream_src = f
         self._ck(self.lib.pmv_frames_stream_begin(self.h, first_slot, f.shape[0], _p(f, _u8p), f.shape[2], f.shape[1]))
 
@@ -498,7 +539,8 @@ class Context:
     def pipeline_run(self, n_frames, w, h, K, gt_poses, min_tracked=400, tol=150, init_frames=5, bundle_size=5,
                      ba_iterations=5, extractor=0, threaded=0, build_pyramids=1, want_features=True, n_threads=1, async_free=False,
                      defer_free=False, host_frames=None, matcher=0, device_fivepoint=0):
-        """frames 0..n_frames-1 must be staged in slots 0..n_frames-1 (frames_stage) unless host_frames (n, h, w) uint8 is given:
+        """frames 0..n_frames-1 must be staged in slots 0..n_frames-1 (frames_stage) unless host_frames (n, h, w) uint8 ((n, h, w, 3) BGR after
+        set_frame_format("bgr")) is given:
         then they are streamed from host memory while the pipeline runs (pmv_pipeline_run_streamed). n_threads: host threads that
         evaluate the five-point RANSAC hypotheses of the triangulator side by side (the results do not depend on it)"""
         P = PipelineParams(n_frames, w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor, threaded,
@@ -507,8 +549,7 @@ class Context:
         gt = np.ascontiguousarray(gt_poses, np.float64).reshape(n_frames, 12)
         out = C.c_void_p()
         if host_frames is not None:
-            hf = np.ascontiguousarray(host_frames, np.uint8)
-            assert hf.shape == (n_frames, h, w)
+            hf = _host_frames(host_frames, self.frame_format, "pipeline_run: host_frames", h, w, n_frames)
             self._ck(self.lib.pmv_pipeline_run_streamed(self.h, C.byref(P), _p(Kd, _f64p), _p(gt, _f64p), _p(hf, _u8p), C.byref(out)))
         else:
             self._ck(self.lib.pmv_pipeline_run(self.h, C.byref(P), _p(Kd, _f64p), _p(gt, _f64p), C.byref(out)))
@@ -563,11 +604,11 @@ class Context:
                                     ba_iterations=5, extractor=0, build_pyramids=1, want_features=True, defer_free=False, threaded=1,
                                     device_fivepoint=0):
         """B sequences streamed from host memory through rings of `ring` frame slots (pmv_pipeline_run_batch_streamed). seqs: list of
-        (frames (n, h, w) uint8, gt_poses (n, 12)); the frames are read where they are (numpy arrays, also over pinned memory such as a
+        (frames (n, h, w) uint8 - (n, h, w, 3) BGR after set_frame_format("bgr") -, gt_poses (n, 12)); the frames are read where they are (numpy arrays, also over pinned memory such as a
         torch pin_memory() tensor's .numpy(); several entries may share one array) and must stay alive during the call. first_slot:
         sequence b's ring starts there (default b * ring). Other arguments as pipeline_run_batch; build_pyramids is ignored. Returns one
         PipelineResult per sequence, bit-identical to pipeline_run_batch on the same frames staged."""
-        frames, gts, first = _batch_streamed_args(seqs, w, h, ring, first_slot)
+        frames, gts, first = _batch_streamed_args(seqs, w, h, ring, first_slot, self.frame_format)
         B = len(frames)
         params = (PipelineParams * B)()
         gt_ptrs = (_f64p * B)()

@@ -1,5 +1,6 @@
 // C-ABI implementation (include/pmv_hip.h): context, frame slots, launches, D2H staging.
 #include "pmv_ctx.h"
+#include "ingest_batch.h"
 #include <algorithm>
 #include <vector>
 #include <cstdarg>
@@ -190,17 +191,34 @@ int pmv_frames_stage(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, i
     REQ(ctx && gray, PMV_ERR_INVALID, "pmv_frames_stage: null argument");
     REQ(first_slot >= 0 && n >= 1 && first_slot + n <= ctx->n_slots, PMV_ERR_CAPACITY, "pmv_frames_stage: slots [%d,%d) out of range (n_slots %d)", first_slot, first_slot + n, ctx->n_slots);
     REQ(w >= 40 && h >= 40 && w <= ctx->max_w && h <= ctx->max_h, PMV_ERR_CAPACITY, "pmv_frames_stage: frame %dx%d outside capacity %dx%d", w, h, ctx->max_w, ctx->max_h);
+    tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     PyrLayout L = layout_for(ctx, w, h);
-    // contiguous copies into the landing area, then level 0 (interior + REFLECT_101 frame) written by k_pad_level0 from there
-    const size_t fb = (size_t)w * h;
-    for (int i0 = 0; i0 < n; i0 += pmv_ctx::TIGHT_FRAMES) {
-        const int nb = std::min((int)pmv_ctx::TIGHT_FRAMES, n - i0);
+    // contiguous copies into the landing area, then level 0 (interior + REFLECT_101 frame) written by k_pad_level0 from there. Colour frames
+    // (tight BGR, pmv_set_frame_format) land as they are, a third as many per chunk, and k_pad_level0_bgr converts them on the way: the slot
+    // then holds what staging the converted image would have left.
+    const bool bgr = ctx->frame_format == PMV_FRAMES_BGR;
+    const size_t fb = (size_t)w * h * (bgr ? 3 : 1);
+    const int chunk = bgr ? pmv_ctx::TIGHT_FRAMES / 3 : pmv_ctx::TIGHT_FRAMES;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int nb = std::min(chunk, n - i0);
         CKC(hipMemcpyAsync(ctx->d_tight, gray + (size_t)i0 * fb, (size_t)nb * fb, hipMemcpyHostToDevice, ctx->s_front));
-        CKC(launch_pad_level0(ctx->s_front, ctx->d_slots, L, first_slot + i0, nb, ctx->d_tight));
+        if (bgr) CKC(launch_pad_level0_bgr(ctx->s_front, ctx->d_slots, L, first_slot + i0, nb, ctx->d_tight));
+        else CKC(launch_pad_level0(ctx->s_front, ctx->d_slots, L, first_slot + i0, nb, ctx->d_tight));
     }
     CKC(hipStreamSynchronize(ctx->s_front));
     for (int i = 0; i < n; i++) { ctx->slot_layout[first_slot + i] = L; ctx->slot_state[first_slot + i] = SLOT_STAGED; }
+    return PMV_OK;
+}
+
+// What the host frames of pmv_frames_stage, pmv_frames_stream_begin, pmv_pipeline_run_streamed and pmv_pipeline_run_batch_streamed hold: the
+// reference never sees a gray image on input (Frame.cpp:33,40-41). Not while a feed reads frames of the other format.
+int pmv_set_frame_format(pmv_ctx* ctx, int format) {
+    REQ(ctx, PMV_ERR_INVALID, "null ctx");
+    REQ(format == PMV_FRAMES_GRAY || format == PMV_FRAMES_BGR, PMV_ERR_INVALID, "pmv_set_frame_format: unknown format %d (PMV_FRAMES_GRAY = 0, PMV_FRAMES_BGR = 1)", format);
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_set_frame_format: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
+    REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_set_frame_format: a batched run is open on this context");
+    ctx->frame_format = format;
     return PMV_OK;
 }
 

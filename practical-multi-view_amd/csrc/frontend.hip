@@ -221,6 +221,81 @@ hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, in
     return hipGetLastError();
 }
 
+// Level 0 straight from a COLOUR frame (Frame::Frame / Frame::init, Frame.cpp:33,40-41: imread(IMREAD_COLOR) gives BGR, cvtColor(BGR2GRAY) the
+// u8 image everything else works on): k_bgr2gray followed by k_pad_level0 in one pass, no gray frame in HBM in between. The source is tight
+// BGR (3 w bytes per row, 3 w h per frame) in the HBM landing area, in mapped pinned host memory at any alignment or in the staging buffer;
+// the range and slot-list forms are those of k_pad_level0, except that there is no in-place form (an entry without a source is left alone).
+// Per padded output row: the source row as the aligned dwords that hold its 3 w bytes and no others (so a source that ends at the end of a
+// host page is never over-read) into LDS, each source byte once; then a thread converts 4 pixels = 12 bytes = the four LDS dwords around them
+// (lanes are 3 dwords apart: an odd stride, no bank conflicts) into one dword of the gray LDS row; then write_padded_row as for gray.
+// gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 as two v_dot4_u32_u8 per pixel on the packed (B, G, R, next B) bytes: the weights
+// do not fit in 8 bits, so they are split into high and low bytes (1868 = 7 * 256 + 76, 9617 = 37 * 256 + 145, 4899 = 19 * 256 + 35; the
+// fourth byte's weight is 0). Integer arithmetic: the bits are those of k_bgr2gray.
+constexpr int PAD0C_T = 256, PAD0C_R = 4;   // rows per workgroup: their loads are in flight together (1 for frames too wide for 4 rows of LDS)
+constexpr uint32_t BGR_W_HI = 7u | (37u << 8) | (19u << 16), BGR_W_LO = 76u | (145u << 8) | (35u << 16);
+static_assert(7 * 256 + 76 == 1868 && 37 * 256 + 145 == 9617 && 19 * 256 + 35 == 4899, "split BGR2GRAY weights");
+// bytes of one raw BGR row in LDS: the dwords that hold lead (<= 3) + 3 w bytes, and 16 more so that the last thread's four dwords exist
+__host__ __device__ inline int pad0c_raw_lds(int w) { return ((3 + 3 * w + 3) / 4) * 4 + 16; }
+__device__ inline uint32_t bgr_gray(uint32_t p) {   // p = B | G << 8 | R << 16 | (any byte) << 24
+    return ((__builtin_amdgcn_udot4(p, BGR_W_HI, 0u, false) << 8) + __builtin_amdgcn_udot4(p, BGR_W_LO, 8192u, false)) >> 14;
+}
+template <int R>
+__global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight,
+                                                            const PyrListEntry* __restrict__ list) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t crow_all[];   // R x raw_lds bytes of BGR, then R x row_lds bytes of gray
+    const int w = L.w[0], h = L.h[0], stride = L.stride[0];
+    int s;
+    const uint8_t* frame;   // tight BGR source frame (block-uniform)
+    if (list) { const PyrListEntry e = list[blockIdx.z]; s = e.slot; frame = e.src; }
+    else { s = first_slot + (int)blockIdx.z; frame = tight ? tight + (size_t)blockIdx.z * 3 * (size_t)w * (size_t)h : nullptr; }
+    if (!frame) return;
+    uint8_t* slot = slots + (size_t)s * L.slot_bytes;
+    const int raw_lds = pad0c_raw_lds(w), row_lds = pad0_row_lds(w);
+    uint8_t* gray_all = crow_all + R * raw_lds;
+    const int ph = h + 2 * PAD;
+    const int py0 = blockIdx.y * R;
+    unsigned lead[R];
+    const uint32_t* src[R];
+    int nd[R], nd_max = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int py = py0 + r < ph ? py0 + r : ph - 1;     // (rows past the end repeat the last one; they are not stored)
+        const int sy = reflect101(py - PAD, h);
+        const uintptr_t a = (uintptr_t)(frame + (size_t)sy * 3 * (size_t)w);
+        lead[r] = (unsigned)(a & 3u);
+        src[r] = (const uint32_t*)(a & ~(uintptr_t)3);
+        nd[r] = (int)((lead[r] + 3u * (unsigned)w + 3u) >> 2);   // the aligned dwords that hold the row's bytes and no others
+        nd_max = nd[r] > nd_max ? nd[r] : nd_max;
+    }
+    for (int d = threadIdx.x; d < nd_max; d += PAD0C_T) {   // the loads of the R rows are issued together, then stored
+        uint32_t v[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) v[r] = d < nd[r] ? src[r][d] : 0u;
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            if (d < nd[r]) ((uint32_t*)(crow_all + r * raw_lds))[d] = v[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const uint8_t* raw = crow_all + r * raw_lds;
+        uint32_t* grow = (uint32_t*)(gray_all + r * row_lds);
+        for (int x4 = threadIdx.x * 4; x4 < w; x4 += PAD0C_T * 4) {
+            uint32_t e[3];   // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3 (pixels past w: bytes nobody reads, their results land in the row's slack)
+            lds_bytes_aligned<12>(raw, (int)lead[r] + 3 * x4, e);
+            const uint32_t g0 = bgr_gray(e[0]), g1 = bgr_gray(__builtin_amdgcn_alignbyte(e[1], e[0], 3)),
+                           g2 = bgr_gray(__builtin_amdgcn_alignbyte(e[2], e[1], 2)), g3 = bgr_gray(e[2] >> 8);
+            grow[x4 >> 2] = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (py0 + r >= ph) break;
+        write_padded_row<PAD0C_T>(gray_all + r * row_lds, 0, w, slot + L.off[0] + (size_t)(py0 + r) * stride);
+    }
+}
+
 // list != nullptr: n device-visible entries, first_slot and tight unused
 hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list) {
     if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0) || L.n_levels < 1) return hipErrorInvalidValue;
@@ -228,6 +303,20 @@ hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, 
     const size_t shm = (size_t)pad0_row_lds(L.w[0]) * PAD0_R;
     ProfScope ps(K_PAD0, s);
     hipLaunchKernelGGL(k_pad_level0, grid, dim3(PAD0_T), shm, s, slots, L, first_slot, tight, list);
+    return hipGetLastError();
+}
+// colour form: level 0 of n slots from n tight BGR frames at `tight` (range form) or from the sources of `list`; one of the two is given
+hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list) {
+    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0 || !tight) || L.n_levels < 1) return hipErrorInvalidValue;
+    const size_t row = (size_t)pad0c_raw_lds(L.w[0]) + (size_t)pad0_row_lds(L.w[0]);
+    const int ph = L.h[0] + 2 * PAD;
+    ProfScope ps(K_PAD0_BGR, s);
+    if (row * PAD0C_R <= (64u << 10))
+        hipLaunchKernelGGL(k_pad_level0_bgr<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, L, first_slot, tight, list);
+    else if (row <= (64u << 10))   // frames wider than 4 k pixels: one row per workgroup
+        hipLaunchKernelGGL(k_pad_level0_bgr<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, L, first_slot, tight, list);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, int first_slot, int n, const PyrListEntry* list) {

@@ -332,6 +332,7 @@ static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_pa
         if (const int rc = check_params(ctx, who, params[b], true)) return rc;
         if (params[b].w != params[0].w || params[b].h != params[0].h) { pmv::set_err(ctx, "%s: all sequences must share the frame size", who); return PMV_ERR_INVALID; }
     }
+    struct Open { pmv_ctx* c; Open(pmv_ctx* c_) : c(c_) { c->batch_open++; } ~Open() { c->batch_open--; } } open(ctx);   // (pmv_set_frame_format)
     pmv::BatchEngine* eng = nullptr;
     int rc = pmv::batch_engine_get(ctx, B, &eng);
     if (rc != PMV_OK) return rc;
@@ -344,7 +345,7 @@ static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_pa
             fed[(size_t)b] = (int)feed.size();
             feed.push_back({first_slot[b], params[b].n_frames, ring[b], host_frames ? host_frames[b] : nullptr});
         }
-    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, params[0].w, params[0].h)) != PMV_OK)
+    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, params[0].w, params[0].h, host_frames ? ctx->frame_format : PMV_FRAMES_GRAY)) != PMV_OK)
         return rc;
     std::vector<int> codes(B, PMV_OK);
     std::vector<std::string> msgs(B);
@@ -368,7 +369,7 @@ static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_pa
 
 extern "C" {
 
-// Same run from HOST frames (n_frames * w * h gray bytes, pageable or pinned): the frames are streamed into slots 0..n_frames-1 by
+// Same run from HOST frames (n_frames frames of w * h gray or 3 * w * h BGR bytes, pmv_set_frame_format; pageable or pinned): the frames are streamed into slots 0..n_frames-1 by
 // the feeder (a pmv_frames_stream_begin bracket, ingest_batch.hip) while the pipeline is already tracking the first ones. Results are identical to
 // pmv_frames_stage + pmv_pipeline_run(build_pyramids = 1).
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K9, const double* gt_poses12,

@@ -11,13 +11,14 @@ namespace pmv {
 struct BatchIngest;
 // What a feed serves: it sets a sequence's frames per round (as each route had them before the feeder) and the default form.
 enum FeedKind { FEED_STREAMED, FEED_STAGED, FEED_BRACKET };
-// One sequence of a feed: frame f goes to slot first + f % ring. src: tight w x h host frames (pageable or pinned), or null: the frames are
+// One sequence of a feed: frame f goes to slot first + f % ring. src: tight w x h host frames (pageable or pinned) in the feed's format, or null: the frames are
 // already staged in their slots (ring = n), only the pad and the pyramid levels are left to do.
 struct FeedSeq { int first, n, ring; const uint8_t* src; };
 // Validates nothing the caller has not (slot ranges, sizes; the rings of a feed that recycles slots are disjoint); creates *g on first use,
 // marks every slot of the feed built with the feed's geometry (its readers wait in slot_ready for the round that builds it) and starts the
 // feeder thread. Staged ranges may overlap: a slot that several sequences cover is built once.
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h);
+// `format` (pmv_frame_format) is what the host frames hold: gray, or tight BGR (3 w h bytes a frame) that level 0 converts on the way in.
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h, int format = PMV_FRAMES_GRAY);
 bool batch_ingest_active(const BatchIngest* g);
 // Combiner thread: make `s` wait on the GPU for feed round `round` (the feeder's stream is in order: every earlier round as well).
 hipError_t batch_ingest_wait_gpu(BatchIngest* g, hipStream_t s, int round);

@@ -14,7 +14,9 @@
 //       copy:   one hipMemcpyAsync of the block into an HBM landing buffer; level 0 is read from there;
 //       mapped: no copy call; k_pad_level0 reads level 0 straight from mapped pinned host memory (the staging buffer for a pageable
 //               source, the caller's own pinned buffer through its device address otherwise);
-//     then one k_pad_level0 and one k_pyrdown launch per level for the whole round, and an event. The launches read the round's slot
+//     then one k_pad_level0 and one k_pyrdown launch per level for the whole round, and an event. A feed of COLOUR frames (tight BGR, Frame.cpp:33,40-41;
+//     pmv_set_frame_format) differs in two things only: a frame is 3 w h bytes, so a round under ROUND_BYTES holds about a third as many, and
+//     level 0 is written by k_pad_level0_bgr, which converts on the way - from the same three sources. The launches read the round's slot
 //     table (list form), unless the round is consecutive slots from consecutive frames (range form, as every round of a bracket). A bracket
 //     (copy form by default) DMAs a pinned source straight into HBM; a staged feed copies only its slot tables into HBM.
 //   * Acquire. Each slot carries (frame, round) of its last enqueued build, published with release / acquire atomics. Before a kernel
@@ -76,7 +78,8 @@ struct BatchIngest {
     std::unique_ptr<Seq[]> seq;
     pmv_ctx* ctx = nullptr;
     int B = 0, w = 0, h = 0, frames_per_round = 1;
-    size_t fb = 0;
+    size_t fb = 0;                // bytes of one host frame: w h (gray) or 3 w h (BGR)
+    bool bgr = false;             // the host frames are tight BGR: level 0 through k_pad_level0_bgr
     PyrLayout L{};
     bool copy_mode = false, per_round = false, open = false;
     bool dma_release = false;   // copy form of a bracket or staged feed: a staging buffer is free once its DMA is done (else: once its round is)
@@ -196,7 +199,9 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         }
         const int first = range ? tab[0].slot : 0;
         const PyrListEntry* dtab = range ? nullptr : (const PyrListEntry*)dblk;
-        if ((e = launch_pad_level0(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pad_level0", e); return; }
+        e = g->bgr ? launch_pad_level0_bgr(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab)   // (every frame of a colour feed has a source)
+                   : launch_pad_level0(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab);
+        if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
         for (int l = 1; l < g->L.n_levels; l++)
             if ((e = launch_pyrdown(g->stream, ctx->d_slots, g->L, l, first, n, dtab)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
         {
@@ -261,7 +266,7 @@ int acquire(BatchIngest* g, int seq, int slot, int* round) {
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h) {
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h, int format) {
     CKC(hipSetDevice(ctx->device));
     if (!gp) {
         BatchIngest* g = new BatchIngest();
@@ -297,7 +302,8 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
             (void)hipGetLastError();   // (a malloc'ed pointer makes hipPointerGetAttributes fail: that is the "pageable" answer)
         }
     }
-    g->fb = (size_t)w * h;
+    g->bgr = host && format == PMV_FRAMES_BGR;
+    g->fb = (size_t)w * h * (g->bgr ? 3 : 1);
     g->frames_per_round = host ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)BatchIngest::ROUND_FRAMES, BatchIngest::ROUND_BYTES / g->fb, (size_t)sum_F}))
                                : BatchIngest::TABLE;
     const size_t need = (BatchIngest::HDR + (host ? (size_t)g->frames_per_round * g->fb : 0) + 4095) & ~(size_t)4095;
@@ -412,7 +418,7 @@ using namespace pmv;
 
 extern "C" {
 
-// A bracket is a feed of one sequence from host memory whose ring is not recycled.
+// A bracket is a feed of one sequence from host memory whose ring is not recycled. `gray`: n frames in the context's frame format.
 int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h) {
     REQ(ctx && gray, PMV_ERR_INVALID, "pmv_frames_stream_begin: null argument");
     REQ(first_slot >= 0 && n >= 1 && first_slot + n <= ctx->n_slots, PMV_ERR_CAPACITY, "pmv_frames_stream_begin: slots [%d,%d) out of range (n_slots %d)", first_slot, first_slot + n, ctx->n_slots);
@@ -421,7 +427,7 @@ int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* 
     CKC(hipSetDevice(ctx->device));
     // frames in the slots about to be overwritten may still be read by work in flight on the front-end stream
     CKC(hipStreamSynchronize(ctx->s_front));
-    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray}}, w, h);
+    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray}}, w, h, ctx->frame_format);
 }
 
 int pmv_frames_stream_end(pmv_ctx* ctx) {

@@ -36,7 +36,7 @@ struct pmv_ctx {
     std::vector<pmv::PyrLayout> slot_layout;  // per slot: geometry of the frame it holds ...
     std::vector<uint8_t> slot_state;          // ... and what of it is there (pmv::SlotState)
     uint8_t* d_slots = nullptr;
-    // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames (H2D copies are contiguous; k_pad_level0 takes
+    // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames, or a third as many BGR ones (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;
     uint8_t* d_tight = nullptr;
@@ -72,6 +72,9 @@ struct pmv_ctx {
     // Both are checked against the oracle to the same bars; their floating-point sums are ordered differently, so runs are compared
     // bit for bit only within one mode.
     int ba_mode = 0;
+    // pmv_set_frame_format: what the host frames of pmv_frames_stage, pmv_frames_stream_begin and the streamed runs hold (pmv_frame_format)
+    int frame_format = PMV_FRAMES_GRAY;
+    std::atomic<int> batch_open{0};      // a batched run is inside run_batch (the format must not change under it)
     pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch
     pmv::BatchIngest* ingest = nullptr;  // feeder of pmv_frames_stream_begin .. _end brackets (created by the first; stream, buffers kept)
     pmv::BatchIngest* bingest = nullptr; // feeder of pmv_pipeline_run_batch[_streamed] (created by the first that needs one)

@@ -146,6 +146,8 @@ struct PyrListEntry { const uint8_t* src; int slot; int pad; };
 // Pyramid stages of n slots: the range first_slot .. first_slot + n - 1 (level 0 from n tight gray frames at `tight`, null: in place), or the n
 // entries of a device-visible `list`.
 hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight = nullptr, const PyrListEntry* list = nullptr);
+// The same level 0 from tight BGR frames (3 w h bytes each), converted on the way (k_pad_level0_bgr); every entry of `list` has a source.
+hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list = nullptr);
 hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, int first_slot, int n, const PyrListEntry* list = nullptr);
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,

@@ -53,19 +53,26 @@ def parse_calibration(path, num_calib=0):
     return K
 
 
-def load_sequence(root, seq="07", n=None, camera="image_0"):
-    """frames (n, h, w) uint8, poses (n, 12), K (3, 3). Gray PNGs: imread(COLOR) + BGR2GRAY is the identity."""
+def load_sequence(root, seq="07", n=None, camera=None, colour=False):
+    """frames (n, h, w) uint8, poses (n, 12), K (3, 3). Gray PNGs: imread(COLOR) + BGR2GRAY is the identity.
+    colour=True: frames (n, h, w, 3) uint8 in BGR channel order, as cv::imread(IMREAD_COLOR) gives them (Frame.cpp:33), from KITTI's colour
+    odometry set - camera "image_2" (the default then) or "image_3" - for Context.set_frame_format("bgr"). camera defaults to "image_0" otherwise."""
     from PIL import Image   # only needed for real data
+    if camera is None:
+        camera = "image_2" if colour else "image_0"
+
+    def read(fn):
+        return np.asarray(Image.open(fn).convert("RGB"))[..., ::-1] if colour else np.asarray(Image.open(fn).convert("L"))
     files = sorted(glob.glob(os.path.join(root, "sequences", seq, camera, "*.png")))   # cv::glob order (:62)
     if n is not None:
         files = files[:n]
     if not files:
         raise FileNotFoundError(f"no images under {root}/sequences/{seq}/{camera}")
-    first = np.asarray(Image.open(files[0]).convert("L"))
+    first = read(files[0])
     frames = np.empty((len(files),) + first.shape, np.uint8)
     frames[0] = first
     for i, fn in enumerate(files[1:], 1):
-        frames[i] = np.asarray(Image.open(fn).convert("L"))
+        frames[i] = read(fn)
     poses = parse_poses(os.path.join(root, "poses", f"{seq}.txt"), stop=len(files))
     K = parse_calibration(os.path.join(root, "sequences", seq, "calib.txt"), 0)
     return frames, poses, K
