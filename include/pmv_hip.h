@@ -261,7 +261,12 @@ int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, c
  * built once), intrinsics K9 + 9 b, ground
  * truth gt_poses12[b]. Each sequence keeps the reference's front-end / back-end host threads; their plugin calls are merged into
  * one k_lk_batch / detector / k_pnp_*_batch / k_bamB_* / k_tri_dlt_batch launch per kernel class by that class's combiner
- * thread (one HIP stream each); the combiners are the only threads that talk to the HIP runtime. out[b] is bit-identical to the same sequence's own pmv_pipeline_run. */
+ * thread (one HIP stream each); the combiners are the only threads that talk to the HIP runtime. out[b] is bit-identical to the same sequence's own pmv_pipeline_run.
+ *   Plugins: params[b] takes every pair pmv_pipeline_run takes - extractor 0, 1 or 2 with matcher 0 (LK), and matcher = 1 (kNN) with
+ *     extractor = 2 (FAST): the kNN matcher calls the extractor on whole frames (kNNFeatureMatcher.cpp:11). Sequences with different pairs may
+ *     share a batch: FAST requests go to the detector combiner (k_fast_score / k_fast_select over the cells of several frames), kNN requests
+ *     to the LK combiners (one k_knn_round launch per round; counted under LK in pmv_batch_stats). Any other value or pair is
+ *     PMV_ERR_INVALID before a sequence starts. */
 int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                            const int* first_slot, pmv_pipeline_result** out);
 /* The same B sequences streamed from HOST memory through recycled frame slots (the reference loads one image per front-end iteration,
@@ -273,7 +278,9 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
  *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot
  *     first_slot[b] + f % ring. After the call each ring slot holds the last frame that went through it, pyramid built.
  *   Shared rules: one frame size for all sequences; build_pyramids is ignored (the feeder builds every frame as it lands); the
- *     parameters are validated as in pmv_pipeline_run_batch (LK with GFTT or ShiTomasi, bundle limits).
+ *     parameters are validated as in pmv_pipeline_run_batch (bundle limits; the plugin pairs of pmv_pipeline_run: extractor 0, 1 or 2 with
+ *     matcher 0, and matcher = 1 (kNN) with extractor = 2 (FAST), per sequence). The feeder needs nothing new for them: the kNN matcher reads
+ *     frames k - 1 and k, FAST the whole frame k or the previous frame's cells, so the minimum ring and the release rule below hold as they are.
  *   Minimum ring: ring >= init_frames + 1. initialise() holds frames 0 .. init_frames - 1 (OdometryPipeline.cpp:428-482), and the first
  *     addFrame may need frame init_frames while frame init_offset is still live. A smaller ring is PMV_ERR_INVALID.
  *   Release rule: once addFrame(image i) (OdometryPipeline.cpp:329-374) has returned, every frame below i is dead - addFrame(i + 1) reads

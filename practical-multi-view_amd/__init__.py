@@ -116,6 +116,16 @@ def _batch_streamed_args(seqs, w, h, ring, first_slot, fmt="gray"):
     return frames, gts, first
 
 
+def _per_sequence(who, name, value, B):
+    """a plugin option of a batched call: one int for all B sequences or a sequence of B ints (checked before anything reaches the device)"""
+    if np.ndim(value) == 0:
+        return [int(value)] * B
+    v = [int(x) for x in value]
+    if len(v) != B:
+        raise ValueError(f"{who}: {name} has {len(v)} entries for {B} sequences")
+    return v
+
+
 class PipelineResult:
     """poses (n,12: R row-major then t), per-frame (column,row,landmark) triples in container order, run statistics"""
 
@@ -570,18 +580,23 @@ class Context:
         return r
 
     def pipeline_run_batch(self, seqs, w, h, K, min_tracked=400, tol=150, init_frames=5, bundle_size=5, ba_iterations=5, extractor=0,
-                           build_pyramids=1, want_features=True, defer_free=False, threaded=1, device_fivepoint=0):
+                           build_pyramids=1, want_features=True, defer_free=False, threaded=1, device_fivepoint=0, matcher=0):
         """B independent sequences through batched launches (pmv_pipeline_run_batch). seqs: list of (first_slot, n_frames, gt_poses);
-        the frames must be staged in slots first_slot..first_slot+n_frames-1. K: 9 values shared by all, or (B, 9). Returns one
-        PipelineResult per sequence (bit-identical to pipeline_run on the same sequence)."""
+        the frames must be staged in slots first_slot..first_slot+n_frames-1. K: 9 values shared by all, or (B, 9). extractor (0 GFTT,
+        1 ShiTomasi, 2 FAST) and matcher (0 LK, 1 kNN, which needs extractor 2): one int for all sequences or B ints, every pair
+        pipeline_run accepts; sequences with different pairs may share a batch. Returns one PipelineResult per sequence (bit-identical to
+        pipeline_run on the same sequence)."""
         B = len(seqs)
+        extractor = _per_sequence("pipeline_run_batch", "extractor", extractor, B)
+        matcher = _per_sequence("pipeline_run_batch", "matcher", matcher, B)
         params = (PipelineParams * B)()
         gts = []
         gt_ptrs = (_f64p * B)()
         first = (C.c_int * B)()
         Kd = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (B, 9)))
         for b, (fs, n, gt) in enumerate(seqs):
-            params[b] = PipelineParams(n, w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor, threaded, 1, build_pyramids, 0, device_fivepoint)
+            params[b] = PipelineParams(n, w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1, build_pyramids, matcher[b],
+                                       device_fivepoint)
             g = np.ascontiguousarray(gt, np.float64).reshape(n, 12)
             gts.append(g)
             gt_ptrs[b] = _p(g, _f64p)
@@ -602,7 +617,7 @@ class Context:
 
     def pipeline_run_batch_streamed(self, seqs, w, h, K, ring=16, first_slot=None, min_tracked=400, tol=150, init_frames=5, bundle_size=5,
                                     ba_iterations=5, extractor=0, build_pyramids=1, want_features=True, defer_free=False, threaded=1,
-                                    device_fivepoint=0):
+                                    device_fivepoint=0, matcher=0):
         """B sequences streamed from host memory through rings of `ring` frame slots (pmv_pipeline_run_batch_streamed). seqs: list of
         (frames (n, h, w) uint8 - (n, h, w, 3) BGR after set_frame_format("bgr") -, gt_poses (n, 12)); the frames are read where they are (numpy arrays, also over pinned memory such as a
         torch pin_memory() tensor's .numpy(); several entries may share one array) and must stay alive during the call. first_slot:
@@ -610,14 +625,16 @@ class Context:
         PipelineResult per sequence, bit-identical to pipeline_run_batch on the same frames staged."""
         frames, gts, first = _batch_streamed_args(seqs, w, h, ring, first_slot, self.frame_format)
         B = len(frames)
+        extractor = _per_sequence("pipeline_run_batch_streamed", "extractor", extractor, B)
+        matcher = _per_sequence("pipeline_run_batch_streamed", "matcher", matcher, B)
         params = (PipelineParams * B)()
         gt_ptrs = (_f64p * B)()
         src = (_u8p * B)()
         fs = (C.c_int * B)(*first)
         Kd = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (B, 9)))
         for b in range(B):
-            params[b] = PipelineParams(frames[b].shape[0], w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor, threaded, 1,
-                                       build_pyramids, 0, device_fivepoint)
+            params[b] = PipelineParams(frames[b].shape[0], w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1,
+                                       build_pyramids, matcher[b], device_fivepoint)
             gt_ptrs[b] = _p(gts[b], _f64p)
             src[b] = _p(frames[b], _u8p)
         outs = (C.c_void_p * B)()

@@ -19,6 +19,12 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
               const uint8_t* predicted_iters = nullptr, uint8_t* iters_out = nullptr, int ring_round = -1);
 int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                   double min_dist, int* out_xy, double* out_score, int* out_count, int ring_round = -1);
+// pmv_detect_fast's contract (a cell may be as large as the frame; max_per_cell <= 0: empty lists, no launch): a request of the detector combiner
+int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
+                       int* out_count, int ring_round = -1);
+// pmv_knn_match's contract: a request of the LK combiners (the matcher role), served by one k_knn_round launch per round; counted under LK
+int engine_knn(BatchEngine* E, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, int* out_best,
+               float* out_err, int ring_round = -1);
 int engine_pnp(BatchEngine* E, int seq, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,
                float reproj_err, double confidence, int* out_inliers, int* out_n_inliers);
 int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,

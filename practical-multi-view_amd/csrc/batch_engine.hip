@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <cstring>
 #include <thread>
@@ -33,7 +34,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi | 10 PnP, 11 BA, 12 DLT
+    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher (served by the LK combiners) | 10 PnP, 11 BA, 12 DLT
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -50,10 +51,17 @@ struct LKReq : Req {
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
     int ring_round = -1;      // the feed round that builds the two frames (-1 = nothing to wait for)
 };
+struct KnnReq : Req {         // kind 4: one kNNFeatureMatcher call (pmv_knn_match's contract)
+    int src_slot, cmp_slot, n, m, n_nn, window;
+    const int* src_xy; const int* cmp_xy; int* out_best; float* err_out;
+    int base = 0;             // filled by the combiner: first index in the round's result arrays (shared with the LK requests)
+    int ring_round = -1;
+};
 struct DetReq : Req {
     int slot, n_cells, max_per_cell, unlimited;
-    const int* cells; double quality, min_dist;
+    const int* cells; double quality, min_dist;   // FAST (kind 3): quality = threshold, min_dist = the non-max flag
     int* out_xy; double* out_score; int* out_count;
+    float* out_resp = nullptr;                    // FAST: KeyPoint::response per keypoint
     int cell_base = 0;
     int ring_round = -1;      // as LKReq::ring_round
 };
@@ -101,6 +109,8 @@ struct Combiner {
     double t_cpu = 0;                            // CPU seconds of the combiner thread itself
     // LK staging + mapped pinned result blocks; detector buffers (only used by combiners of those classes)
     Growable h_front{nullptr, 0, true}, d_front, h_cells{nullptr, 0, true}, d_cells, d_eig, d_cellmax, d_spill, d_det_xy, d_det_score, d_det_count, h_det{nullptr, 0, true};
+    // kNN matcher rounds (LK combiners): [stage-in job | request records | coordinate lists], pinned mirror and HBM copy; FAST score maps (detector combiner)
+    Growable h_knn{nullptr, 0, true}, d_knn, d_fast_score;
     float* h_out_xy = nullptr; float* h_err = nullptr; uint8_t* h_status = nullptr; uint16_t* h_work = nullptr;
     float* dm_out_xy = nullptr; float* dm_err = nullptr; uint8_t* dm_status = nullptr; uint16_t* dm_work = nullptr;
     int* d_flags = nullptr;
@@ -220,7 +230,8 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     pmv_ctx* ctx = E->ctx;
     hipStream_t s = C.s;
     std::vector<LKReq*> lk;
-    for (Req* r : batch) lk.push_back((LKReq*)r);
+    std::vector<KnnReq*> knn;   // (sequences that run the kNN matcher: the same role, the same round)
+    for (Req* r : batch) { if (r->kind == 4) knn.push_back((KnnReq*)r); else lk.push_back((LKReq*)r); }
     // ---- LK: one launch for the tracks of every requesting sequence
     int total_tracks = 0, total_blocks = 0, need_ring = -1;
     PyrLayout L{};
@@ -236,8 +247,49 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         total_blocks += (int)r->order.size();
         need_ring = std::max(need_ring, r->ring_round);
     }
+    // ---- kNN matcher: one k_knn_round launch for the requests of the round. Its results use the indices behind the LK tracks in the same
+    // mapped pinned result blocks (best index: the first n ints of the request's 2 n coordinate floats; window error: the error block).
+    int knn_tracks = 0, knn_max_n = 0;
+    size_t knn_bytes = 64 + sizeof(KnnRound) * knn.size();   // [stage-in job | records | lists, each a multiple of 16 bytes]
+    for (KnnReq* r : knn) {
+        const PyrLayout& a = ctx->slot_layout[r->src_slot];
+        const PyrLayout& b2 = ctx->slot_layout[r->cmp_slot];
+        if (slot_ready(ctx, r->src_slot) || slot_ready(ctx, r->cmp_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: slot has no pyramid / sizes differ"); continue; }
+        if (!have_L) { L = a; have_L = true; }
+        else if (a.w[0] != L.w[0] || a.h[0] != L.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: all sequences of a batch must share the frame size"); continue; }
+        r->base = total_tracks + knn_tracks;
+        knn_tracks += r->n;
+        knn_max_n = std::max(knn_max_n, r->n);
+        knn_bytes += (((size_t)r->n * 8 + 15) & ~(size_t)15) + (((size_t)r->m * 8 + 15) & ~(size_t)15);
+        need_ring = std::max(need_ring, r->ring_round);
+    }
+    bool ring_waited = false;
+    if (knn_tracks > 0) {
+        if (need_ring >= 0) { EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring)); ring_waited = true; }
+        if ((size_t)total_tracks + (size_t)knn_tracks > E->cap_tracks) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
+        EK(C.h_knn.ensure(knn_bytes + 64)); EK(C.d_knn.ensure(knn_bytes + 64));
+        char* hb = (char*)C.h_knn.p;
+        char* db = (char*)C.d_knn.p;
+        KnnRound* rec = (KnnRound*)(hb + 64);
+        size_t off = 64 + sizeof(KnnRound) * knn.size();
+        int n_rec = 0;
+        for (KnnReq* r : knn) {
+            if (r->rc != PMV_OK) continue;
+            KnnRound& k = rec[n_rec++];
+            k.src_off = (unsigned long long)r->src_slot * L.slot_bytes; k.cmp_off = (unsigned long long)r->cmp_slot * L.slot_bytes;
+            k.src_xy = (const int*)(db + off); memcpy(hb + off, r->src_xy, (size_t)r->n * 8); off += ((size_t)r->n * 8 + 15) & ~(size_t)15;
+            k.cmp_xy = (const int*)(db + off); if (r->m) memcpy(hb + off, r->cmp_xy, (size_t)r->m * 8); off += ((size_t)r->m * 8 + 15) & ~(size_t)15;
+            k.out_best = (int*)C.dm_out_xy + 2 * (size_t)r->base; k.out_err = C.dm_err + r->base;
+            k.n = r->n; k.m = r->m; k.n_nn = r->n_nn; k.window = r->window;
+        }
+        // one gather pulls records and lists into HBM (every workgroup of a request scans its whole candidate list): no DMA call
+        *(StageJob*)hb = StageJob{C.h_knn.dev + 64, db + 64, (unsigned)(off - 64), 0};
+        hipLaunchKernelGGL(k_stage_in, dim3(64, 1), dim3(256), 0, s, (const StageJob*)C.h_knn.dev);
+        EK(hipGetLastError());
+        EK(launch_knn_round(s, ctx->d_slots, L, (const KnnRound*)(db + 64), n_rec, knn_max_n));
+    }
     if (total_tracks > 0) {
-        if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
+        if (need_ring >= 0 && !ring_waited) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         if ((size_t)total_tracks > E->cap_tracks) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
         const size_t bytes = sizeof(LKBlock) * (size_t)total_blocks;
         EK(C.h_front.ensure(bytes + 64));
@@ -290,6 +342,11 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         if (r->iters_out) for (int i = 0; i < r->n; i++) r->iters_out[i] = (uint8_t)(C.h_work[(size_t)r->base + i] & 0xffu);
         ctx->add_lk_work(C.h_work + r->base, (size_t)r->n);
     }
+    for (KnnReq* r : knn) {
+        if (r->rc != PMV_OK) continue;
+        memcpy(r->out_best, (const int*)C.h_out_xy + 2 * (size_t)r->base, (size_t)r->n * 4);
+        memcpy(r->err_out, C.h_err + r->base, (size_t)r->n * 4);
+    }
 }
 
 // ---- detectors --------------------------------------------------------------------------------------------------------------------
@@ -300,11 +357,20 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (Req* r : batch) det.push_back((DetReq*)r);
     // ---- detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
     // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
-    struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; };
+    // FAST (kind 3; grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
+    // its score maps are sized by the pixels of the round (d_fast_score), the cell record's offset into them stays within int.
+    struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; int max_pix = 0; };
     std::vector<Group> groups;
+    size_t fast_pix = 0;
     for (DetReq* r : det) {
         const PyrLayout& Lr = ctx->slot_layout[r->slot];
         if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d holds no built pyramid", r->slot); continue; }
+        if (r->kind == 3) {
+            size_t pix = 0;
+            for (int i = 0; i < r->n_cells; i++) pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
+            if (fast_pix + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch FAST: the cells of the round cover more than 2^31 pixels"); continue; }
+            fast_pix += pix;
+        }
         Group* g = nullptr;
         for (Group& x : groups)
             if (x.kind == r->kind && x.max_per_cell == r->max_per_cell && x.unlimited == r->unlimited && x.quality == r->quality && x.min_dist == r->min_dist &&
@@ -317,24 +383,36 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     {
         size_t tot_cells = 0, tot_out = 0;
         for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
-        EK(C.h_cells.ensure(tot_cells * CELL_STRIDE * 4));
-        EK(C.d_eig.ensure(tot_cells * CELL_PIX * sizeof(double))); EK(C.d_cellmax.ensure(tot_cells * 8)); EK(C.d_spill.ensure(tot_cells * CELL_PIX * 4));
+        size_t eig_cells = 0;   // cells of the GFTT / ShiTomasi groups: the response, cell-maximum and spill areas are theirs alone
+        for (Group& g : groups) if (g.kind != 3) eig_cells += g.n_cells;
+        const size_t cells_bytes = tot_cells * CELL_STRIDE * 4;
+        EK(C.h_cells.ensure(cells_bytes + 64));   // (+ the stage-in job of a round with FAST cells)
+        EK(C.d_eig.ensure(eig_cells * CELL_PIX * sizeof(double))); EK(C.d_cellmax.ensure(eig_cells * 8)); EK(C.d_spill.ensure(eig_cells * CELL_PIX * 4));
         EK(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // [xy | score | count | flags], written by the kernels through the mapped alias
         int* hc = (int*)C.h_cells.p;
-        size_t cpos = 0;
+        size_t cpos = 0, fpos = 0;
         for (Group& g : groups)
             for (DetReq* r : g.reqs)
                 for (int i = 0; i < r->n_cells; i++, cpos++) {
                     int* d = hc + cpos * CELL_STRIDE;
                     d[0] = r->cells[4 * i]; d[1] = r->cells[4 * i + 1]; d[2] = r->cells[4 * i + 2]; d[3] = r->cells[4 * i + 3]; d[4] = r->slot; d[5] = d[6] = d[7] = 0;
+                    if (g.kind == 3) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
                 }
+        if (fast_pix > 0) {
+            // every thread of k_fast_score reads its cell record: the records of the round go to HBM by one gather (no DMA call)
+            EK(C.d_cells.ensure(cells_bytes + 64)); EK(C.d_fast_score.ensure(fast_pix + 64));
+            StageJob* job = (StageJob*)((char*)C.h_cells.p + ((cells_bytes + 15) & ~(size_t)15));
+            *job = StageJob{C.h_cells.dev, (char*)C.d_cells.p, (unsigned)cells_bytes, 0};
+            hipLaunchKernelGGL(k_stage_in, dim3(1, 1), dim3(256), 0, s, (const StageJob*)(C.h_cells.dev + ((cells_bytes + 15) & ~(size_t)15)));
+            EK(hipGetLastError());
+        }
         EK(hipMemsetAsync(C.d_flags, 0, 16, s));
         {
             int need_ring = -1;
             for (DetReq* r : det) if (r->rc == PMV_OK) need_ring = std::max(need_ring, r->ring_round);
             if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         }
-        size_t c0 = 0;
+        size_t c0 = 0, e0 = 0;   // first cell of the group among all cells of the round / among those with a response area (c0 = e0 in a round without FAST)
         char* hd = (char*)C.h_det.p;
         char* dd = C.h_det.dev;
         for (Group& g : groups) {
@@ -343,12 +421,16 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             double* dsc = (double*)(dd + tot_out * 8) + g.out_off;
             int* dcnt = (int*)(dd + tot_out * 16) + c0;
             if (g.kind == 1)
-                EK(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + c0 * CELL_PIX,
-                               (unsigned*)C.d_cellmax.p + 2 * c0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + c0 * CELL_PIX));
-            else
-                EK(launch_shitomasi(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, (double*)C.d_eig.p + c0 * CELL_PIX,
-                                    (unsigned long long*)C.d_cellmax.p + c0, dxy, dsc, dcnt, C.d_flags, (unsigned*)C.d_spill.p + c0 * CELL_PIX));
+                EK(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + e0 * CELL_PIX,
+                               (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+            else if (g.kind == 2)
+                EK(launch_shitomasi(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, (double*)C.d_eig.p + e0 * CELL_PIX,
+                                    (unsigned long long*)C.d_cellmax.p + e0, dxy, dsc, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+            else   // FAST: records from HBM, float responses in the group's share of the score block
+                EK(launch_fast(s, ctx->d_slots, g.L, (const int*)C.d_cells.p + c0 * CELL_STRIDE, g.n_cells, g.max_pix, g.max_per_cell, (int)g.quality, (int)g.min_dist,
+                               (uint8_t*)C.d_fast_score.p, dxy, (float*)dsc, dcnt));
             c0 += g.n_cells;
+            if (g.kind != 3) e0 += g.n_cells;
         }
         EK(hipMemcpyAsync(hd + tot_out * 16 + tot_cells * 4, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
     }
@@ -368,6 +450,7 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 const size_t o = g.out_off + (size_t)r->cell_base * g.max_per_cell;
                 memcpy(r->out_xy, hxy + o * 2, (size_t)r->n_cells * g.max_per_cell * 8);
                 if (r->out_score) memcpy(r->out_score, hsc + o, (size_t)r->n_cells * g.max_per_cell * 8);
+                if (g.kind == 3) memcpy(r->out_resp, (const float*)(hsc + g.out_off) + (size_t)r->cell_base * g.max_per_cell, (size_t)r->n_cells * g.max_per_cell * 4);
                 memcpy(r->out_count, hcnt + c0 + r->cell_base, (size_t)r->n_cells * 4);
             }
             c0 += g.n_cells;
@@ -586,7 +669,7 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
             if (C.h_done) (void)hipHostFree(C.h_done);
-            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det}) g->release();
+            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score}) g->release();
             if (C.h_out_xy) (void)hipHostFree(C.h_out_xy);
             if (C.h_err) (void)hipHostFree(C.h_err);
             if (C.h_status) (void)hipHostFree(C.h_status);
@@ -735,6 +818,44 @@ int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_ce
     r.quality = quality; r.min_dist = min_dist; r.out_xy = out_xy; r.out_score = out_score; r.out_count = out_count;
     r.ring_round = ring_round;
     return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
+                       int* out_count, int ring_round) {
+    pmv_ctx* ctx = E->ctx;
+    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "detect (FAST): bad argument");
+    if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }   // as pmv_detect_fast: empty lists, no launch
+    REQ(out_xy && out_response, PMV_ERR_INVALID, "detect (FAST): null output");
+    REQ(max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect (FAST): max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_INVALID, "detect (FAST): slot %d out of range", slot);
+    const int rc = slot_ready(ctx, slot);
+    if (rc) return rc;
+    const PyrLayout& L = ctx->slot_layout[slot];
+    for (int i = 0; i < n_cells; i++) {   // a FAST "cell" may be as large as the frame
+        const int* c = cells + 4 * i;
+        REQ(c[2] >= 1 && c[3] >= 1 && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0], PMV_ERR_INVALID, "detect (FAST): cell %d invalid", i);
+    }
+    DetReq r;
+    r.kind = 3; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = 0; r.max_per_cell = max_per_cell;
+    r.quality = threshold; r.min_dist = nonmax ? 1 : 0;   // (the group key of process_det)
+    r.out_xy = out_xy; r.out_score = nullptr; r.out_resp = out_response; r.out_count = out_count;
+    r.ring_round = ring_round;
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_knn(BatchEngine* E, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, int* out_best,
+               float* out_err, int ring_round) {
+    pmv_ctx* ctx = E->ctx;
+    REQ((n == 0 || (src_xy && out_best && out_err)) && (m == 0 || cmp_xy), PMV_ERR_INVALID, "pmv_knn_match: null argument");
+    REQ(n >= 0 && n <= ctx->max_tracks && m >= 0 && m <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_knn_match: n=%d / m=%d exceed max_tracks=%d", n, m, ctx->max_tracks);
+    REQ(n_neighbours >= 1 && n_neighbours <= 8 && window >= 1 && window <= 63, PMV_ERR_INVALID, "pmv_knn_match: n_neighbours 1..8, window 1..63");
+    REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
+    if (n == 0) return PMV_OK;
+    KnnReq r;
+    r.kind = 4; r.src_slot = src_slot; r.cmp_slot = cmp_slot; r.n = n; r.m = m; r.n_nn = n_neighbours; r.window = window;
+    r.src_xy = src_xy; r.cmp_xy = cmp_xy; r.out_best = out_best; r.err_out = out_err;
+    r.ring_round = ring_round;
+    return submit(ctx, E->queue[R_LK], &r);
 }
 
 int engine_pnp(BatchEngine* E, int seq, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,

@@ -9,9 +9,12 @@
 namespace pmv {
 
 // =========================================================================================================
-// kNN matcher: one wavefront per source feature
+// kNN matcher: one wavefront per source feature, one launch per ROUND of requests (pmv_knn_match: a round of one; the batch engine's LK
+// combiners: the requests of many sequences)
 // =========================================================================================================
 constexpr int KNN_MAX_NN = 8;
+constexpr int KNN_LDS_M = 1024;   // candidates a workgroup keeps in LDS (8 KB; the matcher asks the extractor for 1000): a longer list is read from HBM
+constexpr int KNN_WAVES = 4;      // source features per workgroup: they share the staged candidate list
 
 __device__ inline float knn_compare(const uint8_t* __restrict__ I, const uint8_t* __restrict__ J, int st, int w, int h, int sx, int sy, int cx, int cy, int win) {
     // kNNFeatureMatcher.cpp:103-122: x outer, y inner, pixels outside either image skipped; float accumulator fed through a double addition
@@ -25,54 +28,90 @@ __device__ inline float knn_compare(const uint8_t* __restrict__ I, const uint8_t
     return err;
 }
 
-__global__ __launch_bounds__(64) void k_knn_match(const uint8_t* __restrict__ slots, PyrLayout L, unsigned long long src_off, unsigned long long cmp_off,
-                                                  const int* __restrict__ src_xy, int n, const int* __restrict__ cmp_xy, int m, int n_nn, int window,
-                                                  int* __restrict__ out_best, float* __restrict__ out_err) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    const int fx = src_xy[2 * i], fy = src_xy[2 * i + 1];
-    int nnv[KNN_MAX_NN];
-    int nearest = -1;   // the default Feature: column 0, row 0
-    for (int k = 0; k < n_nn; k++) {
+// The same window error by the whole wavefront. Every term is a non-negative integer (a squared difference of two bytes), so while the
+// running sum stays <= 2^24 every partial sum of the reference's float accumulator is an integer that a float holds exactly, and the integer
+// total summed in ANY order converts to the same float. A total above 2^24 (289 * 255^2 = 18.8 M can be) was rounded on the way: that
+// window is walked again in the reference's order. The skip rule is per pixel pair. Wave-uniform arguments, EXEC full; every lane returns
+// the same value.
+__device__ inline float knn_window_error(const uint8_t* __restrict__ I, const uint8_t* __restrict__ J, int st, int w, int h, int sx, int sy, int cx, int cy, int win,
+                                         int lane) {
+    const int side = 2 * win + 1, pairs = side * side;
+    int part = 0;   // per window <= 65^2 * 255^2 = 2.7e8 (window <= 63): int32
+    for (int p = lane; p < pairs; p += 64) {
+        const int y = p / side - win, x = p - (p / side) * side - win;   // rows along the lanes: neighbouring lanes read neighbouring bytes
+        if (sx + x >= 0 && sy + y >= 0 && cx + x >= 0 && cy + y >= 0 && sx + x < w && sy + y < h && cx + x < w && cy + y < h) {
+            const int d = (int)I[(ptrdiff_t)(sy + y) * st + sx + x] - (int)J[(ptrdiff_t)(cy + y) * st + cx + x];
+            part += d * d;
+        }
+    }
+    const int total = wave_sum_i32(part);
+    if (total <= (1 << 24)) return (float)total;
+    float acc = 0.f;
+    if (lane == 0) acc = knn_compare(I, J, st, w, h, sx, sy, cx, cy, win);
+    return __shfl(acc, 0, 64);
+}
+
+// getNearestNeighbors + compareFeatures + the best-fit rule of ONE source feature, by one wavefront. `cmp`: the request's candidate
+// list, in LDS or in HBM (the address space is known after inlining).
+__device__ __forceinline__ void knn_one(const KnnRound& r, const int2* __restrict__ cmp, const uint8_t* __restrict__ slots, const PyrLayout& L, int i, int lane) {
+    const int fx = r.src_xy[2 * i], fy = r.src_xy[2 * i + 1];
+    const int m = r.m, n_nn = r.n_nn;
+    int nnv[KNN_MAX_NN], qx[KNN_MAX_NN], qy[KNN_MAX_NN];   // the chosen neighbours and their coordinates ((0,0): the default Feature)
+    int nearest = -1, nx = 0, ny = 0;
+#pragma unroll
+    for (int k = 0; k < KNN_MAX_NN; k++) {
+        nnv[k] = -1; qx[k] = 0; qy[k] = 0;
+        if (k >= n_nn) continue;
         unsigned long long best = ~0ull;   // (distance << 32) | index: the first candidate with the smallest distance wins
         for (int j = lane; j < m; j += 64) {
-            const int cx = cmp_xy[2 * j], cy = cmp_xy[2 * j + 1];
-            if (cx == fx && cy == fy) continue;
-            bool fresh = true;
-            for (int q = 0; q < k; q++) {
-                const int qx = nnv[q] < 0 ? 0 : cmp_xy[2 * nnv[q]], qy = nnv[q] < 0 ? 0 : cmp_xy[2 * nnv[q] + 1];
-                if (cx == qx && cy == qy) fresh = false;
-            }
-            if (!fresh) continue;
-            const int dx = abs(fx - cx), dy = abs(fy - cy);
-            const unsigned long long key = ((unsigned long long)(unsigned)(dx > dy ? dx : dy) << 32) | (unsigned)j;
-            best = key < best ? key : best;
-        }
+            const int2 c = cmp[j];
+            bool fresh = !(c.x == fx && c.y == fy);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(best, o, 64); best = t < best ? t : best; }
-        if (best != ~0ull) nearest = (int)(best & 0xffffffffu);
-        nnv[k] = nearest;
+            for (int q = 0; q < k; q++) fresh = fresh && !(c.x == qx[q] && c.y == qy[q]);
+            const int dx = abs(fx - c.x), dy = abs(fy - c.y);
+            const unsigned long long key = ((unsigned long long)(unsigned)(dx > dy ? dx : dy) << 32) | (unsigned)j;
+            best = fresh && key < best ? key : best;
+        }
+        best = ~wave_max_u64(~best);   // the minimum, in every lane
+        if (best != ~0ull) { nearest = (int)(best & 0xffffffffu); const int2 c = cmp[nearest]; nx = c.x; ny = c.y; }
+        nnv[k] = nearest; qx[k] = nx; qy[k] = ny;
     }
-    const uint8_t* I = level_origin(slots + src_off, L, 0);
-    const uint8_t* J = level_origin(slots + cmp_off, L, 0);
-    const int win = (int)ceilf((float)window / 2.f);
-    float e = 0.f;
-    int cand = -1;
-    if (lane < n_nn) {
-        cand = nnv[lane];
-        const int cx = cand < 0 ? 0 : cmp_xy[2 * cand], cy = cand < 0 ? 0 : cmp_xy[2 * cand + 1];
-        const float acc = knn_compare(I, J, L.stride[0], L.w[0], L.h[0], fx, fy, cx, cy, win);
-        e = (float)(sqrt((double)acc) / ((double)window * (double)window));
-    }
+    const uint8_t* I = level_origin(slots + r.src_off, L, 0);
+    const uint8_t* J = level_origin(slots + r.cmp_off, L, 0);
+    const int win = (int)ceilf((float)r.window / 2.f);
     // :19-31 sequential `_err < err || err == 0`
     float err = 0.f;
     int best_idx = -1;
-    for (int k = 0; k < n_nn; k++) {
-        const float ek = __shfl(e, k, 64);
-        const int ck = __shfl(cand, k, 64);
-        if (ek < err || err == 0.f) { err = ek; best_idx = ck; }
+#pragma unroll
+    for (int k = 0; k < KNN_MAX_NN; k++) {
+        if (k >= n_nn) continue;
+        const float acc = knn_window_error(I, J, L.stride[0], L.w[0], L.h[0], fx, fy, qx[k], qy[k], win, lane);
+        const float ek = (float)(sqrt((double)acc) / ((double)r.window * (double)r.window));
+        if (ek < err || err == 0.f) { err = ek; best_idx = nnv[k]; }
     }
-    if (lane == 0) { out_best[i] = best_idx; out_err[i] = err; }
+    if (lane == 0) { r.out_best[i] = best_idx; r.out_err[i] = err; }
+}
+
+// grid (ceil(max n / KNN_WAVES), requests): workgroup (x, y) serves source features KNN_WAVES x .. KNN_WAVES x + KNN_WAVES - 1 of request y
+__global__ __launch_bounds__(64 * KNN_WAVES) void k_knn_round(const uint8_t* __restrict__ slots, PyrLayout L, const KnnRound* __restrict__ recs) {
+    __shared__ int2 s_cmp[KNN_LDS_M];
+    const KnnRound r = recs[blockIdx.y];
+    if ((int)blockIdx.x * KNN_WAVES >= r.n) return;   // (the whole workgroup: before the barrier)
+    const int lane = threadIdx.x & 63, i = (int)blockIdx.x * KNN_WAVES + (int)(threadIdx.x >> 6);
+    const bool lds = r.m <= KNN_LDS_M;
+    if (lds) {
+        for (int j = threadIdx.x; j < r.m; j += 64 * KNN_WAVES) s_cmp[j] = ((const int2*)r.cmp_xy)[j];
+        __syncthreads();
+    }
+    if (i >= r.n) return;
+    if (lds) knn_one(r, s_cmp, slots, L, i, lane);
+    else knn_one(r, (const int2*)r.cmp_xy, slots, L, i, lane);
+}
+
+hipError_t launch_knn_round(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const KnnRound* d_recs, int n_requests, int max_n) {
+    if (n_requests <= 0 || max_n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_knn_round, dim3((max_n + KNN_WAVES - 1) / KNN_WAVES, n_requests), dim3(64 * KNN_WAVES), 0, s, slots, L, d_recs);
+    return hipGetLastError();
 }
 
 // =========================================================================================================
@@ -175,6 +214,15 @@ __global__ __launch_bounds__(256) void k_fast_select(const int* __restrict__ cel
     if (tid == 0) out_count[cell] = sbase < max_kp ? sbase : max_kp;
 }
 
+hipError_t launch_fast(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, int max_pix, int max_per_cell, int threshold,
+                       int nonmax, uint8_t* d_score, int* d_out_xy, float* d_out_resp, int* d_out_count) {
+    threshold = threshold < 0 ? 0 : threshold > 255 ? 255 : threshold;
+    hipLaunchKernelGGL(k_fast_score, dim3((max_pix + 255) / 256, 1, n_cells), dim3(256), 0, s, slots, L, d_cells, threshold, nonmax ? 1 : 0, d_score);
+    hipLaunchKernelGGL(k_fast_select, dim3(n_cells), dim3(256), 0, s, d_cells, (const uint8_t*)d_score, nonmax ? 1 : 0, max_per_cell, d_out_xy, d_out_resp,
+                       d_out_count);
+    return hipGetLastError();
+}
+
 }  // namespace pmv
 
 using namespace pmv;
@@ -197,16 +245,20 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
-    // staging: [src_xy 2n | cmp_xy 2m] ints in the LK coordinate buffers (sized 12 B per track + 64), results through the mapped LK result blocks
-    int* h = (int*)ctx->h_knn;
-    memcpy(h, src_xy, (size_t)n * 8);
-    if (m) memcpy(h + 2 * n, cmp_xy, (size_t)m * 8);
-    CKC(hipMemcpyAsync(ctx->d_knn, h, ((size_t)n + m) * 8, hipMemcpyHostToDevice, ctx->s_front));
-    const int* d_src = (const int*)ctx->d_knn;
-    const int* d_cmp = d_src + 2 * n;
-    hipLaunchKernelGGL(k_knn_match, dim3(n), dim3(64), 0, ctx->s_front, (const uint8_t*)ctx->d_slots, L, (unsigned long long)src_slot * L.slot_bytes,
-                       (unsigned long long)cmp_slot * L.slot_bytes, d_src, n, d_cmp, m, n_neighbours, window, (int*)ctx->dm_out_xy, ctx->dm_err);
-    CKC(hipGetLastError());
+    // a round of one request: [record (64 B) | src_xy 2n | cmp_xy 2m] ints, results through the mapped LK result blocks
+    static_assert(sizeof(KnnRound) == 64, "the staging buffers reserve 64 bytes for the record");
+    char* h = (char*)ctx->h_knn;
+    char* d = (char*)ctx->d_knn;
+    KnnRound rec;
+    rec.src_off = (unsigned long long)src_slot * L.slot_bytes; rec.cmp_off = (unsigned long long)cmp_slot * L.slot_bytes;
+    rec.src_xy = (const int*)(d + 64); rec.cmp_xy = rec.src_xy + 2 * (size_t)n;
+    rec.out_best = (int*)ctx->dm_out_xy; rec.out_err = ctx->dm_err;
+    rec.n = n; rec.m = m; rec.n_nn = n_neighbours; rec.window = window;
+    memcpy(h, &rec, sizeof(rec));
+    memcpy(h + 64, src_xy, (size_t)n * 8);
+    if (m) memcpy(h + 64 + (size_t)n * 8, cmp_xy, (size_t)m * 8);
+    CKC(hipMemcpyAsync(d, h, 64 + ((size_t)n + m) * 8, hipMemcpyHostToDevice, ctx->s_front));
+    CKC(launch_knn_round(ctx->s_front, (const uint8_t*)ctx->d_slots, L, (const KnnRound*)d, 1, n));
     CKC(hipStreamSynchronize(ctx->s_front));
     memcpy(out_best, ctx->h_out_xy, (size_t)n * 4);
     memcpy(out_err, ctx->h_err, (size_t)n * 4);
@@ -240,12 +292,8 @@ int pmv_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
-    threshold = threshold < 0 ? 0 : threshold > 255 ? 255 : threshold;
-    hipLaunchKernelGGL(k_fast_score, dim3((maxpix + 255) / 256, 1, n_cells), dim3(256), 0, ctx->s_front, (const uint8_t*)ctx->d_slots, L, ctx->d_cells, threshold,
-                       nonmax ? 1 : 0, (uint8_t*)ctx->d_eig);
-    hipLaunchKernelGGL(k_fast_select, dim3(n_cells), dim3(256), 0, ctx->s_front, ctx->d_cells, (const uint8_t*)ctx->d_eig, nonmax ? 1 : 0, max_per_cell,
-                       ctx->d_det_xy, (float*)ctx->d_det_score, ctx->d_det_count);
-    CKC(hipGetLastError());
+    CKC(launch_fast(ctx->s_front, (const uint8_t*)ctx->d_slots, L, ctx->d_cells, n_cells, maxpix, max_per_cell, threshold, nonmax, (uint8_t*)ctx->d_eig,
+                    ctx->d_det_xy, (float*)ctx->d_det_score, ctx->d_det_count));
     const size_t nk = (size_t)n_cells * max_per_cell;
     CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nk * 8, hipMemcpyDeviceToHost, ctx->s_front));
     CKC(hipMemcpyAsync(ctx->h_det_score, ctx->d_det_score, nk * 4, hipMemcpyDeviceToHost, ctx->s_front));

@@ -179,6 +179,33 @@ struct BatchShiTomasi : ShiTomasiExtractorBase {
             }
     }
 };
+struct BatchFast : FastExtractorBase {
+    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+    std::vector<int> rect, xy, cnt;
+    std::vector<float> rs;
+    void fast(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
+              std::vector<std::vector<float>>& response) override {
+        out.assign(cells.size(), {});
+        response.assign(cells.size(), {});
+        if (cells.empty() || max < 1) return;
+        cells_of(cells, rect);
+        xy.resize(cells.size() * (size_t)max * 2); rs.resize(cells.size() * (size_t)max); cnt.resize(cells.size());
+        const int rr = ring.round(ctx, cells[0].slot);
+        ck(ctx, pmv::engine_detect_fast(eng, cells[0].slot, rect.data(), (int)cells.size(), max, threshold, nonmax ? 1 : 0, xy.data(), rs.data(), cnt.data(), rr));
+        for (size_t c = 0; c < cells.size(); c++)
+            for (int i = 0; i < cnt[c]; i++) {
+                out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
+                response[c].push_back(rs[c * max + i]);
+            }
+    }
+};
+struct BatchKnn : KnnFeatureMatcherBase {   // (`extractor` = the sequence's BatchFast: matchFeatures calls it on the whole next frame)
+    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+    void knn(const ImageView& src, const ImageView& next, const int* src_xy, int n, const int* cmp_xy, int m, int* best, float* err) override {
+        const int rr = ring.round(ctx, src.slot, next.slot);
+        ck(ctx, pmv::engine_knn(eng, src.slot, next.slot, src_xy, n, cmp_xy, m, neighbours, window, best, err, rr));
+    }
+};
 struct BatchLK : LucasKanadeFMBase {
     pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
     // Ordering hint for the batched launch (no effect on any result): a track that needed many LK iterations in the last frame pair tends
@@ -282,7 +309,7 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
     vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
     vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
     vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
-    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = 0;
+    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = P->matcher;
     try {
         vo::pipeline_setup(run, vp, nullptr, K9, gt_poses12);
         for (auto& im : run.pipe.images) im.slot = first_slot + im.slot % ring;
@@ -295,9 +322,12 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
         RingFrames rf{ing, fed};
         vo::BaseFeatureExtractor* ex;
         if (P->extractor == 1) { auto* e = new BatchShiTomasi(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
+        else if (P->extractor == 2) { auto* e = new BatchFast(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
         else { auto* e = new BatchGftt(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
         run.owned_ex.push_back(ex);
-        auto* lk = new BatchLK(); lk->ctx = ctx; lk->eng = eng; lk->ring = rf;
+        vo::BaseFeatureMatcher* lk;
+        if (P->matcher == 1) { auto* k = new BatchKnn(); k->ctx = ctx; k->eng = eng; k->ring = rf; k->extractor = ex; lk = k; }   // (extractor = 2: check_params)
+        else { auto* l = new BatchLK(); l->ctx = ctx; l->eng = eng; l->ring = rf; lk = l; }
         auto* pnp = new BatchPnP(); pnp->ctx = ctx; pnp->eng = eng; pnp->seq = b; pnp->tracker = &run.pipe;
         auto* tri = new BatchTri(); tri->ctx = ctx; tri->eng = eng; tri->seq = b; tri->tracker = &run.pipe; tri->workers = 1;
         tri->use_hypothesis_hook = P->device_fivepoint != 0;
@@ -314,13 +344,19 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
     if (fed >= 0) pmv::batch_ingest_finish(ing, fed);   // finished or failed: its whole ring is free
 }
 
-// The parameter rules the entry points share: bundle_size, and for a batch the frame size and the plugins the batch engine serves.
+// The parameter rules the entry points share: bundle_size, and for a batch the frame size and the plugin pairs (those of the single run).
 static int check_params(pmv_ctx* ctx, const char* who, const pmv_pipeline_params& P, bool batch) {
     if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "%s: bundle_size 1..2 divides by zero in the reference (OdometryPipeline.cpp:407)", who); return PMV_ERR_INVALID; }
     if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "%s: bundle_size exceeds max_ba_cams", who); return PMV_ERR_CAPACITY; }
     if (!batch) return PMV_OK;
     if (P.w < 40 || P.h < 40 || P.w > ctx->max_w || P.h > ctx->max_h) { pmv::set_err(ctx, "%s: frame %dx%d outside capacity %dx%d", who, P.w, P.h, ctx->max_w, ctx->max_h); return PMV_ERR_CAPACITY; }
-    if (P.matcher != 0 || P.extractor > 1) { pmv::set_err(ctx, "%s: the batch engine serves the reference's default plugins (LK; GFTT or ShiTomasi)", who); return PMV_ERR_INVALID; }
+    // the plugin pairs pmv_pipeline_run serves, refused here before any sequence thread or feed starts (the single run finds the last one by exception)
+    if (P.extractor < 0 || P.extractor > 2) { pmv::set_err(ctx, "%s: extractor = %d: the extractor is 0 (GFTT), 1 (ShiTomasi) or 2 (FAST)", who, P.extractor); return PMV_ERR_INVALID; }
+    if (P.matcher < 0 || P.matcher > 1) { pmv::set_err(ctx, "%s: matcher = %d: the matcher is 0 (LK) or 1 (kNN)", who, P.matcher); return PMV_ERR_INVALID; }
+    if (P.matcher == 1 && P.extractor != 2) {
+        pmv::set_err(ctx, "%s: matcher = 1 needs extractor = 2: the kNN matcher calls the extractor on whole frames, which only FAST accepts (got extractor = %d)", who, P.extractor);
+        return PMV_ERR_INVALID;
+    }
     return PMV_OK;
 }
 

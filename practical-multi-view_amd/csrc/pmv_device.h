@@ -173,6 +173,23 @@ hipError_t launch_shitomasi(hipStream_t s, const uint8_t* slots, const PyrLayout
                             int max_per_cell, double quality, double* d_resp, unsigned long long* d_cellmax,
                             int* d_out_xy, double* d_out_score, int* d_out_count, int* d_flags, unsigned* d_spill);
 
+// ---- the reference's alternative plugins (frontend_alt.hip) ------------------------------------------------------
+// One request of a kNN matcher round: n source features of the frame at byte offset src_off of the slot array against m candidates of
+// the frame at cmp_off. The coordinate lists ((x, y) int pairs) are in device memory, the results may be mapped pinned host memory.
+struct __attribute__((aligned(64))) KnnRound {
+    unsigned long long src_off, cmp_off;
+    const int* src_xy; const int* cmp_xy;
+    int* out_best; float* out_err;       // per source feature: candidate index or -1 (the default Feature at (0,0)), its window error
+    int n, m, n_nn, window;
+};
+// k_knn_round over n_requests records in device memory (all frames share the geometry L); max_n = the largest n among them
+hipError_t launch_knn_round(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const KnnRound* d_recs, int n_requests, int max_n);
+// k_fast_score + k_fast_select over n_cells cell records (x0, y0, w, h, slot, byte offset of the cell's score map in d_score, 0, 0) in
+// device-visible memory; a "cell" may be as large as the frame. max_pix = the largest w * h among them. Outputs per cell: max_per_cell
+// (x, y) pairs, as many float responses, one count.
+hipError_t launch_fast(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, int max_pix, int max_per_cell, int threshold,
+                       int nonmax, uint8_t* d_score, int* d_out_xy, float* d_out_resp, int* d_out_count);
+
 hipError_t launch_gftt_response(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, float* d_eig, unsigned* d_cellmax);
 constexpr int CELL_MAX = 255;                 // OdometryPipeline.h:31 grid_size
 constexpr int CELL_PIX = CELL_MAX * CELL_MAX;
