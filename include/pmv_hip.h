@@ -257,9 +257,15 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* params, const doub
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                               const uint8_t* host_frames, pmv_pipeline_result** out);
 /* B independent sequences through batched launches (SURVEY.md §8e "same kernels with a leading batch dimension"): sequence b =
- * frame slots first_slot[b] .. + params[b].n_frames - 1 (pmv_frames_stage; one frame size for all; ranges may overlap, a shared slot is
+ * frame slots first_slot[b] .. + params[b].n_frames - 1 (pmv_frames_stage; ranges may overlap, a shared slot is
  * built once), intrinsics K9 + 9 b, ground
- * truth gt_poses12[b]. Each sequence keeps the reference's front-end / back-end host threads; their plugin calls are merged into
+ * truth gt_poses12[b].
+ *   Frame sizes: per sequence, from params[b].w / params[b].h - the reference takes whatever cv::imread returns (Frame.cpp:31-42) and KITTI
+ *     odometry comes in three sizes. Every size lies within the context's capacity (40 x 40 .. max_w x max_h, else PMV_ERR_CAPACITY); a batch
+ *     may hold any mix of them and still makes one k_lk_batch / k_knn_round launch per round and one k_pad_level0 / k_pyrdown launch per
+ *     feeder round and level (each track / request / frame record names its geometry in a small table in device memory). params[b].w / h must
+ *     equal the size staged in every slot of sequence b's range, so overlapping ranges must agree on the size of every shared slot: otherwise
+ *     PMV_ERR_INVALID, naming the sequence, before a sequence starts. Each sequence keeps the reference's front-end / back-end host threads; their plugin calls are merged into
  * one k_lk_batch / detector / k_pnp_*_batch / k_bamB_* / k_tri_dlt_batch launch per kernel class by that class's combiner
  * thread (one HIP stream each); the combiners are the only threads that talk to the HIP runtime. out[b] is bit-identical to the same sequence's own pmv_pipeline_run.
  *   Plugins: params[b] takes every pair pmv_pipeline_run takes - extractor 0, 1 or 2 with matcher 0 (LK), and matcher = 1 (kNN) with
@@ -269,6 +275,10 @@ int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, c
  *     PMV_ERR_INVALID before a sequence starts. */
 int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                            const int* first_slot, pmv_pipeline_result** out);
+/* diagnostic: launches of the batched legs since the context was created: out4 = {k_lk_batch, k_knn_round (LK combiners), k_pad_level0 /
+ * k_pad_level0_bgr, k_pyrdown (the feeder of the two batched entry points)}. Against the rounds of pmv_batch_stats / pmv_batch_ingest_stats
+ * it shows that a round is one launch (per level) whatever frame sizes it holds. */
+int pmv_debug_batch_launches(pmv_ctx* ctx, long long* out4);
 /* The same B sequences streamed from HOST memory through recycled frame slots (the reference loads one image per front-end iteration,
  * Frame.cpp:31-42, OdometryPipeline.cpp:212-229, and tracking reads only frames k-1 and k), so that the batch size is not capped by frame
  * storage: B x ring slots instead of the sum of all n_frames.
@@ -277,7 +287,10 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
  *     mapped at its host address (hipHostMalloc, torch pin_memory) is read in place, anything else is copied into pinned staging first.
  *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot
  *     first_slot[b] + f % ring. After the call each ring slot holds the last frame that went through it, pyramid built.
- *   Shared rules: one frame size for all sequences; build_pyramids is ignored (the feeder builds every frame as it lands); the
+ *   Frame sizes: per sequence, from params[b].w / params[b].h (Frame.cpp:31-42: a run takes whatever size its images have), each within
+ *     the context's capacity (else PMV_ERR_CAPACITY); host_frames[b] holds frames of that size, and every slot of sequence b's ring holds
+ *     that size. Staging buffers are sized for the largest frame of the batch; pmv_batch_ingest_stats counts the bytes actually moved.
+ *   Shared rules: build_pyramids is ignored (the feeder builds every frame as it lands); the
  *     parameters are validated as in pmv_pipeline_run_batch (bundle limits; the plugin pairs of pmv_pipeline_run: extractor 0, 1 or 2 with
  *     matcher 0, and matcher = 1 (kNN) with extractor = 2 (FAST), per sequence). The feeder needs nothing new for them: the kNN matcher reads
  *     frames k - 1 and k, FAST the whole frame k or the previous frame's cells, so the minimum ring and the release rule below hold as they are.

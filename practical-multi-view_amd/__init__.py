@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "pmv_lk_track", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
-    "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
+    "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
     "pmv_pipeline_frame_feature_count", "pmv_pipeline_get_frame_features", "pmv_pipeline_stats_count", "pmv_pipeline_get_stats",
 ]
 
@@ -88,11 +88,19 @@ def _host_frames(frames, fmt, who, h=None, w=None, n=None):
 
 
 def _batch_streamed_args(seqs, w, h, ring, first_slot, fmt="gray"):
-    """shapes of pipeline_run_batch_streamed's arguments, checked before anything reaches the device: (frames, gt_poses, first_slot)"""
+    """shapes of pipeline_run_batch_streamed's arguments, checked before anything reaches the device: (frames, gt_poses, first_slot). w, h:
+    one int for all sequences, one int per sequence, or None = each sequence's own array shape; the sizes the library is given are the arrays'
+    own (frames[b].shape[2], frames[b].shape[1]), which a given w, h must match."""
     if len(seqs) < 1:
         raise ValueError("pipeline_run_batch_streamed: no sequences")
     if int(ring) != ring or ring < 1:
         raise ValueError(f"pipeline_run_batch_streamed: ring must be a positive integer, got {ring!r}")
+    if (w is None) != (h is None):
+        raise ValueError("pipeline_run_batch_streamed: w and h are given together, or both None (each sequence's own array shape)")
+    ws = hs = [None] * len(seqs)
+    if w is not None:
+        ws = _per_sequence("pipeline_run_batch_streamed", "w", w, len(seqs))
+        hs = _per_sequence("pipeline_run_batch_streamed", "h", h, len(seqs))
     frames, gts = [], []
     for b, seq in enumerate(seqs):
         if len(seq) != 2:
@@ -100,9 +108,10 @@ def _batch_streamed_args(seqs, w, h, ring, first_slot, fmt="gray"):
         f, gt = seq
         f = np.asarray(f)
         if fmt == "bgr":
-            f = _host_frames(f, fmt, f"pipeline_run_batch_streamed: sequence {b}", h, w)
-        elif f.dtype != np.uint8 or f.ndim != 3 or f.shape[1:] != (h, w):
-            raise ValueError(f"pipeline_run_batch_streamed: sequence {b}: frames must be (n, {h}, {w}) uint8, got {f.shape} {f.dtype}")
+            f = _host_frames(f, fmt, f"pipeline_run_batch_streamed: sequence {b}", hs[b], ws[b])
+        elif f.dtype != np.uint8 or f.ndim != 3 or (ws[b] is not None and f.shape[1:] != (hs[b], ws[b])):
+            want = f"(n, {hs[b]}, {ws[b]})" if ws[b] is not None else "(n, h, w)"
+            raise ValueError(f"pipeline_run_batch_streamed: sequence {b}: frames must be {want} uint8, got {f.shape} {f.dtype}")
         f = np.ascontiguousarray(f)   # (a contiguous array, pinned or not, is passed as it is)
         g = np.ascontiguousarray(gt, np.float64)
         if g.size != 12 * f.shape[0]:
@@ -582,20 +591,23 @@ class Context:
     def pipeline_run_batch(self, seqs, w, h, K, min_tracked=400, tol=150, init_frames=5, bundle_size=5, ba_iterations=5, extractor=0,
                            build_pyramids=1, want_features=True, defer_free=False, threaded=1, device_fivepoint=0, matcher=0):
         """B independent sequences through batched launches (pmv_pipeline_run_batch). seqs: list of (first_slot, n_frames, gt_poses);
-        the frames must be staged in slots first_slot..first_slot+n_frames-1. K: 9 values shared by all, or (B, 9). extractor (0 GFTT,
+        the frames must be staged in slots first_slot..first_slot+n_frames-1. w, h: the frame size, one int for all sequences or B ints
+        (sequences of different sizes may share a batch; each must name the size staged in its slots). K: 9 values shared by all, or (B, 9). extractor (0 GFTT,
         1 ShiTomasi, 2 FAST) and matcher (0 LK, 1 kNN, which needs extractor 2): one int for all sequences or B ints, every pair
         pipeline_run accepts; sequences with different pairs may share a batch. Returns one PipelineResult per sequence (bit-identical to
         pipeline_run on the same sequence)."""
         B = len(seqs)
         extractor = _per_sequence("pipeline_run_batch", "extractor", extractor, B)
         matcher = _per_sequence("pipeline_run_batch", "matcher", matcher, B)
+        w = _per_sequence("pipeline_run_batch", "w", w, B)
+        h = _per_sequence("pipeline_run_batch", "h", h, B)
         params = (PipelineParams * B)()
         gts = []
         gt_ptrs = (_f64p * B)()
         first = (C.c_int * B)()
         Kd = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (B, 9)))
         for b, (fs, n, gt) in enumerate(seqs):
-            params[b] = PipelineParams(n, w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1, build_pyramids, matcher[b],
+            params[b] = PipelineParams(n, w[b], h[b], min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1, build_pyramids, matcher[b],
                                        device_fivepoint)
             g = np.ascontiguousarray(gt, np.float64).reshape(n, 12)
             gts.append(g)
@@ -615,14 +627,18 @@ class Context:
             res.append(r)
         return res
 
-    def pipeline_run_batch_streamed(self, seqs, w, h, K, ring=16, first_slot=None, min_tracked=400, tol=150, init_frames=5, bundle_size=5,
+    def pipeline_run_batch_streamed(self, seqs, w=None, h=None, K=None, ring=16, first_slot=None, min_tracked=400, tol=150, init_frames=5, bundle_size=5,
                                     ba_iterations=5, extractor=0, build_pyramids=1, want_features=True, defer_free=False, threaded=1,
                                     device_fivepoint=0, matcher=0):
         """B sequences streamed from host memory through rings of `ring` frame slots (pmv_pipeline_run_batch_streamed). seqs: list of
         (frames (n, h, w) uint8 - (n, h, w, 3) BGR after set_frame_format("bgr") -, gt_poses (n, 12)); the frames are read where they are (numpy arrays, also over pinned memory such as a
-        torch pin_memory() tensor's .numpy(); several entries may share one array) and must stay alive during the call. first_slot:
+        torch pin_memory() tensor's .numpy(); several entries may share one array) and must stay alive during the call. w, h: one int for
+        all sequences, B ints, or None = each sequence's own array shape (sequences of different sizes may share a batch); a given size
+        that an array does not match is a ValueError. first_slot:
         sequence b's ring starts there (default b * ring). Other arguments as pipeline_run_batch; build_pyramids is ignored. Returns one
         PipelineResult per sequence, bit-identical to pipeline_run_batch on the same frames staged."""
+        if K is None:
+            raise ValueError("pipeline_run_batch_streamed: K (9 values, or (B, 9)) is required")
         frames, gts, first = _batch_streamed_args(seqs, w, h, ring, first_slot, self.frame_format)
         B = len(frames)
         extractor = _per_sequence("pipeline_run_batch_streamed", "extractor", extractor, B)
@@ -633,7 +649,7 @@ class Context:
         fs = (C.c_int * B)(*first)
         Kd = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (B, 9)))
         for b in range(B):
-            params[b] = PipelineParams(frames[b].shape[0], w, h, min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1,
+            params[b] = PipelineParams(frames[b].shape[0], frames[b].shape[2], frames[b].shape[1], min_tracked, tol, init_frames, bundle_size, ba_iterations, extractor[b], threaded, 1,
                                        build_pyramids, matcher[b], device_fivepoint)
             gt_ptrs[b] = _p(gts[b], _f64p)
             src[b] = _p(frames[b], _u8p)
@@ -659,6 +675,14 @@ class Context:
         out = np.zeros(n, np.float64)
         self._ck(min(self.lib.pmv_batch_ingest_stats(self.h, _p(out, _f64p)), 0))
         return dict(zip(BATCH_INGEST_KEYS, [float(v) for v in out]))
+
+    def batch_launches(self):
+        """launches of the batched legs since the context was created (pmv_debug_batch_launches): k_lk_batch, k_knn_round, k_pad_level0
+        (gray or BGR), k_pyrdown"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_batch_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_batch_launches(self.h, out))
+        return dict(zip(("k_lk_batch", "k_knn_round", "k_pad_level0", "k_pyrdown"), [int(v) for v in out]))
 
     def batch_stats(self):
         """per combiner of the batch engine (lk, det, pnp, ba, dlt): launch rounds, requests served, CPU seconds of the thread, wall seconds processing batches / of that waiting for the GPU"""

@@ -49,12 +49,14 @@ struct LKReq : Req {
     uint8_t* iters_out = nullptr;   // optional: LK iterations each track took (the caller's ordering hint for its next request)
     std::vector<int> order;   // block -> track order of THIS request (local indices, -1 = padding), built by the caller
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
+    int geom = 0;             // filled by the combiner: the geometry-table entry of its two frames
     int ring_round = -1;      // the feed round that builds the two frames (-1 = nothing to wait for)
 };
 struct KnnReq : Req {         // kind 4: one kNNFeatureMatcher call (pmv_knn_match's contract)
     int src_slot, cmp_slot, n, m, n_nn, window;
     const int* src_xy; const int* cmp_xy; int* out_best; float* err_out;
     int base = 0;             // filled by the combiner: first index in the round's result arrays (shared with the LK requests)
+    int geom = 0;             // filled by the combiner: the geometry-table entry of its two frames
     int ring_round = -1;
 };
 struct DetReq : Req {
@@ -232,16 +234,15 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<LKReq*> lk;
     std::vector<KnnReq*> knn;   // (sequences that run the kNN matcher: the same role, the same round)
     for (Req* r : batch) { if (r->kind == 4) knn.push_back((KnnReq*)r); else lk.push_back((LKReq*)r); }
-    // ---- LK: one launch for the tracks of every requesting sequence
+    // ---- LK: one launch for the tracks of every requesting sequence, whatever their frame sizes: a request's geometry is the one staged in
+    // its prev slot (prev and next of ONE request must agree), carried by each of its track records as an index into the context's table
+    const unsigned long long pitch = ctx->cap.slot_bytes;
     int total_tracks = 0, total_blocks = 0, need_ring = -1;
-    PyrLayout L{};
-    bool have_L = false;
     for (LKReq* r : lk) {
         const PyrLayout& a = ctx->slot_layout[r->prev_slot];
         const PyrLayout& b2 = ctx->slot_layout[r->next_slot];
         if (slot_ready(ctx, r->prev_slot) || slot_ready(ctx, r->next_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
-        if (!have_L) { L = a; have_L = true; }
-        else if (a.w[0] != L.w[0] || a.h[0] != L.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: all sequences of a batch must share the frame size"); continue; }
+        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->prev_slot, a.w[0], a.h[0]); continue; }
         r->base = total_tracks;
         total_tracks += r->n;
         total_blocks += (int)r->order.size();
@@ -255,8 +256,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         const PyrLayout& a = ctx->slot_layout[r->src_slot];
         const PyrLayout& b2 = ctx->slot_layout[r->cmp_slot];
         if (slot_ready(ctx, r->src_slot) || slot_ready(ctx, r->cmp_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: slot has no pyramid / sizes differ"); continue; }
-        if (!have_L) { L = a; have_L = true; }
-        else if (a.w[0] != L.w[0] || a.h[0] != L.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: all sequences of a batch must share the frame size"); continue; }
+        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->src_slot, a.w[0], a.h[0]); continue; }
         r->base = total_tracks + knn_tracks;
         knn_tracks += r->n;
         knn_max_n = std::max(knn_max_n, r->n);
@@ -276,17 +276,18 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         for (KnnReq* r : knn) {
             if (r->rc != PMV_OK) continue;
             KnnRound& k = rec[n_rec++];
-            k.src_off = (unsigned long long)r->src_slot * L.slot_bytes; k.cmp_off = (unsigned long long)r->cmp_slot * L.slot_bytes;
+            k.src_off = (unsigned long long)r->src_slot * pitch; k.cmp_off = (unsigned long long)r->cmp_slot * pitch;
             k.src_xy = (const int*)(db + off); memcpy(hb + off, r->src_xy, (size_t)r->n * 8); off += ((size_t)r->n * 8 + 15) & ~(size_t)15;
             k.cmp_xy = (const int*)(db + off); if (r->m) memcpy(hb + off, r->cmp_xy, (size_t)r->m * 8); off += ((size_t)r->m * 8 + 15) & ~(size_t)15;
             k.out_best = (int*)C.dm_out_xy + 2 * (size_t)r->base; k.out_err = C.dm_err + r->base;
-            k.n = r->n; k.m = r->m; k.n_nn = r->n_nn; k.window = r->window;
+            k.n = r->n; k.m = r->m; k.nn_window = knn_pack(r->n_nn, r->window); k.geom = r->geom;
         }
         // one gather pulls records and lists into HBM (every workgroup of a request scans its whole candidate list): no DMA call
         *(StageJob*)hb = StageJob{C.h_knn.dev + 64, db + 64, (unsigned)(off - 64), 0};
         hipLaunchKernelGGL(k_stage_in, dim3(64, 1), dim3(256), 0, s, (const StageJob*)C.h_knn.dev);
         EK(hipGetLastError());
-        EK(launch_knn_round(s, ctx->d_slots, L, (const KnnRound*)(db + 64), n_rec, knn_max_n));
+        EK(launch_knn_round_geom(s, ctx->d_slots, ctx->d_geom, (const KnnRound*)(db + 64), n_rec, knn_max_n));
+        ctx->batch_launches[1]++;
     }
     if (total_tracks > 0) {
         if (need_ring >= 0 && !ring_waited) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
@@ -299,11 +300,11 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         auto put = [&](const LKReq* r, int o) {
             if (o < 0) return;   // (padding entries of the striped order: the launch carries real tracks only)
             LKBlock& k = hblk[bpos++];
-            k.prev_off = (unsigned long long)r->prev_slot * L.slot_bytes;
-            k.next_off = (unsigned long long)r->next_slot * L.slot_bytes;
+            k.prev_off = (unsigned long long)r->prev_slot * pitch;
+            k.next_off = (unsigned long long)r->next_slot * pitch;
             k.track = r->base + o;
             k.x = r->prev_xy[2 * (size_t)o]; k.y = r->prev_xy[2 * (size_t)o + 1];
-            k.pad = 0;
+            k.geom = r->geom;
         };
         for (LKReq* r : lk) {
             if (r->rc != PMV_OK) continue;
@@ -331,7 +332,8 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         }
         P.stamps = lk_stamps ? ctx->d_lk_stamps : nullptr;
         // mapped pinned: every workgroup reads its 32-byte record once, no copy launch
-        EK(launch_lk_batch(s, ctx->d_slots, (const LKBlock*)C.h_front.dev, bpos, L, P, C.dm_out_xy, C.dm_status, C.dm_err, C.dm_work));
+        EK(launch_lk_batch(s, ctx->d_slots, (const LKBlock*)C.h_front.dev, bpos, ctx->d_geom, P, C.dm_out_xy, C.dm_status, C.dm_err, C.dm_work));
+        ctx->batch_launches[0]++;
     }
     SYNC_TIMED(C);
     for (LKReq* r : lk) {

@@ -107,6 +107,9 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     CK(hipHostMalloc(&c->h_work, (size_t)nt * 2, hipHostMallocMapped | hipHostMallocCoherent));
     CK(hipHostGetDevicePointer((void**)&c->dm_work, c->h_work, 0));
     for (auto& a : c->lk_work) a.store(0);
+    for (auto& a : c->batch_launches) a.store(0);
+    CK(hipMalloc(&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
+    CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMalloc(&c->d_cells, MAX_CELLS * CELL_STRIDE * 4));
     CK(hipHostMalloc(&c->h_cells, MAX_CELLS * CELL_STRIDE * 4));
     CK(hipMalloc(&c->d_eig, (size_t)MAX_CELLS * CELL_PIX * sizeof(double)));   // shared by GFTT (f32) and ShiTomasi (f64)
@@ -145,6 +148,7 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     backend_destroy(c);
     c->prof.destroy();
     if (c->d_lk_stamps) hipFree(c->d_lk_stamps);
+    if (c->d_geom) hipFree(c->d_geom);
     if (c->h_work) hipHostFree(c->h_work);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
@@ -184,6 +188,17 @@ PyrLayout pmv::layout_for(pmv_ctx* ctx, int w, int h) {
     PyrLayout L = make_layout(w, h);
     L.slot_bytes = ctx->cap.slot_bytes;
     return L;
+}
+int pmv::geom_table_set(pmv_ctx* ctx, const int* w, const int* h, int B) {
+    ctx->geom.clear();
+    for (int b = 0; b < B; b++)
+        if (ctx->geom_index(w[b], h[b]) < 0) {
+            REQ((int)ctx->geom.size() < pmv_ctx::MAX_GEOM, PMV_ERR_CAPACITY, "more than %d distinct frame sizes in one batch", pmv_ctx::MAX_GEOM);
+            ctx->geom.push_back(layout_for(ctx, w[b], h[b]));
+        }
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipMemcpy(ctx->d_geom, ctx->geom.data(), sizeof(PyrLayout) * ctx->geom.size(), hipMemcpyHostToDevice));
+    return PMV_OK;
 }
 extern "C" {
 

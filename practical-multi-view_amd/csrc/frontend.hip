@@ -84,18 +84,17 @@ __host__ __device__ inline int pad0_row_lds(int w) { return ((w + 3 + 24 + 3) / 
 // slot list[z].slot, level 0 from list[z].src (the HBM landing area or mapped pinned host memory, at any alignment), in place when that is null.
 // Tight rows are generally unaligned: they are fetched as the aligned dwords that hold the row's bytes and no others, so a source that ends at
 // the end of a host page is never over-read.
-__global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight,
-                                                        const PyrListEntry* __restrict__ list) {
+// (LRef: const PyrLayout& = the launch's own geometry, GeomEntry& = the frame's entry of the geometry table; the grid of a list launch is
+// sized for the tallest frame of the round, so a workgroup below its own frame leaves before its first load or barrier)
+template <class LRef>
+__device__ __forceinline__ void pad_level0_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame) {
     extern __shared__ __attribute__((aligned(16))) uint8_t srow_all[];   // PAD0_R x row_lds bytes
     const int w = L.w[0], h = L.h[0], stride = L.stride[0];
-    int s;
-    const uint8_t* frame;   // tight source frame, or null: in place (block-uniform)
-    if (list) { const PyrListEntry e = list[blockIdx.z]; s = e.slot; frame = e.src; }
-    else { s = first_slot + (int)blockIdx.z; frame = tight ? tight + (size_t)blockIdx.z * (size_t)w * (size_t)h : nullptr; }
     uint8_t* slot = slots + (size_t)s * L.slot_bytes;
     const int row_lds = pad0_row_lds(w);
     const int ph = h + 2 * PAD;
     const int py0 = blockIdx.y * PAD0_R;
+    if (py0 >= ph) return;
     unsigned lead[PAD0_R];
 #pragma unroll
     for (int r = 0; r < PAD0_R; r++) {
@@ -123,6 +122,14 @@ __global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout
         write_padded_row<PAD0_T>(srow_all + r * row_lds, (int)lead[r], w, slot + L.off[0] + (size_t)(py0 + r) * stride);
     }
 }
+__global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight) {
+    // tight source frame z, or null: in place (block-uniform)
+    pad_level0_rows<const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * (size_t)L.w[0] * (size_t)L.h[0] : nullptr);
+}
+__global__ __launch_bounds__(PAD0_T) void k_pad_level0_list(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrListEntry* __restrict__ list) {
+    const PyrListEntry e = list[blockIdx.z];
+    pad_level0_rows<GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src);
+}
 
 // level l-1 (padded) -> level l (padded): cv::pyrDown [1 4 6 4 1]^2, (sum+128)>>8. A workgroup produces PYR_R padded output rows: per
 // row the vertical taps straight from coalesced dword loads of the five source rows (source columns -4 .. 2*dw+3: the level origin
@@ -135,16 +142,20 @@ __device__ inline uint32_t as_u32(pk_u16 x) { union { uint32_t u; pk_u16 p; } c;
 constexpr int PYR_T = 256, PYR_R = 4;   // output rows per workgroup
 __host__ __device__ inline int pyr_vs_row(int dw) { return (2 * dw + 24 + 3) & ~3; }        // uint16 entries
 __host__ __device__ inline int pyr_out_row(int dw) { return ((dw + 3 + 24 + 3) / 4) * 4; }  // bytes
-// (slot of workgroup column z as in k_pad_level0)
-__global__ __launch_bounds__(PYR_T) void k_pyrdown(uint8_t* slots, PyrLayout L, int ld, int first_slot, const PyrListEntry* __restrict__ list) {
+// (slot of workgroup column z and LRef as in k_pad_level0; in a list launch a frame whose pyramid has no level ld - 640x200 builds levels
+// 0-2, the KITTI sizes 0-3 - is skipped by all its workgroups, again before the first load or barrier)
+template <class LRef>
+__device__ __forceinline__ void pyrdown_rows(uint8_t* slots, LRef L, int ld, int s) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pyr_lds[];
-    uint8_t* slot = slots + (size_t)(list ? list[blockIdx.z].slot : first_slot + (int)blockIdx.z) * L.slot_bytes;
+    if (ld >= L.n_levels) return;
+    uint8_t* slot = slots + (size_t)s * L.slot_bytes;
     const int ls = ld - 1;
     const uint8_t* src = level_origin((const uint8_t*)slot, L, ls);
     const int ss = L.stride[ls];
     const int dw = L.w[ld], dh = L.h[ld], ds = L.stride[ld];
     const int ph = dh + 2 * PAD;
     const int py0 = blockIdx.y * PYR_R;
+    if (py0 >= ph) return;
     const int nd = (2 * dw + 8) >> 2;
     const int vs_row = pyr_vs_row(dw), out_row = pyr_out_row(dw);
     uint8_t* orow_all = pyr_lds + (size_t)PYR_R * vs_row * 2;
@@ -196,6 +207,13 @@ __global__ __launch_bounds__(PYR_T) void k_pyrdown(uint8_t* slots, PyrLayout L, 
         write_padded_row<PYR_T>(orow_all + r * out_row, 0, dw, slot + L.off[ld] + (size_t)(py0 + r) * ds);
     }
 }
+__global__ __launch_bounds__(PYR_T) void k_pyrdown(uint8_t* slots, PyrLayout L, int ld, int first_slot) {
+    pyrdown_rows<const PyrLayout&>(slots, L, ld, first_slot + (int)blockIdx.z);
+}
+__global__ __launch_bounds__(PYR_T) void k_pyrdown_list(uint8_t* slots, const PyrLayout* __restrict__ geom, int ld, const PyrListEntry* __restrict__ list) {
+    const PyrListEntry e = list[blockIdx.z];
+    pyrdown_rows<GeomEntry&>(slots, geom_entry(geom, e.geom), ld, __builtin_amdgcn_readfirstlane(e.slot));
+}
 
 // cv::cvtColor(BGR2GRAY) for 8-bit images (Frame::init, Frame.cpp:40-41): gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14, the 14-bit
 // fixed-point form of 0.114 B + 0.587 G + 0.299 R [mem: OpenCV 3.4 color.cpp]; identity for B = G = R (KITTI's gray PNGs, quirk Q2).
@@ -239,21 +257,17 @@ __host__ __device__ inline int pad0c_raw_lds(int w) { return ((3 + 3 * w + 3) / 
 __device__ inline uint32_t bgr_gray(uint32_t p) {   // p = B | G << 8 | R << 16 | (any byte) << 24
     return ((__builtin_amdgcn_udot4(p, BGR_W_HI, 0u, false) << 8) + __builtin_amdgcn_udot4(p, BGR_W_LO, 8192u, false)) >> 14;
 }
-template <int R>
-__global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight,
-                                                            const PyrListEntry* __restrict__ list) {
+template <int R, class LRef>   // (LRef as in k_pad_level0; `frame`: the tight BGR source frame, block-uniform)
+__device__ __forceinline__ void pad_level0_bgr_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame) {
     extern __shared__ __attribute__((aligned(16))) uint8_t crow_all[];   // R x raw_lds bytes of BGR, then R x row_lds bytes of gray
     const int w = L.w[0], h = L.h[0], stride = L.stride[0];
-    int s;
-    const uint8_t* frame;   // tight BGR source frame (block-uniform)
-    if (list) { const PyrListEntry e = list[blockIdx.z]; s = e.slot; frame = e.src; }
-    else { s = first_slot + (int)blockIdx.z; frame = tight ? tight + (size_t)blockIdx.z * 3 * (size_t)w * (size_t)h : nullptr; }
     if (!frame) return;
     uint8_t* slot = slots + (size_t)s * L.slot_bytes;
     const int raw_lds = pad0c_raw_lds(w), row_lds = pad0_row_lds(w);
     uint8_t* gray_all = crow_all + R * raw_lds;
     const int ph = h + 2 * PAD;
     const int py0 = blockIdx.y * R;
+    if (py0 >= ph) return;
     unsigned lead[R];
     const uint32_t* src[R];
     int nd[R], nd_max = 0;
@@ -295,36 +309,74 @@ __global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr(uint8_t* slots, PyrL
         write_padded_row<PAD0C_T>(gray_all + r * row_lds, 0, w, slot + L.off[0] + (size_t)(py0 + r) * stride);
     }
 }
+template <int R>
+__global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight) {
+    pad_level0_bgr_rows<R, const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * 3 * (size_t)L.w[0] * (size_t)L.h[0] : nullptr);
+}
+template <int R>
+__global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr_list(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrListEntry* __restrict__ list) {
+    const PyrListEntry e = list[blockIdx.z];
+    pad_level0_bgr_rows<R, GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src);
+}
 
-// list != nullptr: n device-visible entries, first_slot and tight unused
-hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list) {
-    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0) || L.n_levels < 1) return hipErrorInvalidValue;
+hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight) {
+    if (!slots || n < 1 || first_slot < 0 || L.n_levels < 1) return hipErrorInvalidValue;
     dim3 grid(1, (L.h[0] + 2 * PAD + PAD0_R - 1) / PAD0_R, n);
     const size_t shm = (size_t)pad0_row_lds(L.w[0]) * PAD0_R;
     ProfScope ps(K_PAD0, s);
-    hipLaunchKernelGGL(k_pad_level0, grid, dim3(PAD0_T), shm, s, slots, L, first_slot, tight, list);
+    hipLaunchKernelGGL(k_pad_level0, grid, dim3(PAD0_T), shm, s, slots, L, first_slot, tight);
     return hipGetLastError();
 }
-// colour form: level 0 of n slots from n tight BGR frames at `tight` (range form) or from the sources of `list`; one of the two is given
-hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list) {
-    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0 || !tight) || L.n_levels < 1) return hipErrorInvalidValue;
+// colour form: level 0 of n slots from n tight BGR frames at `tight`
+hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight) {
+    if (!slots || n < 1 || first_slot < 0 || !tight || L.n_levels < 1) return hipErrorInvalidValue;
     const size_t row = (size_t)pad0c_raw_lds(L.w[0]) + (size_t)pad0_row_lds(L.w[0]);
     const int ph = L.h[0] + 2 * PAD;
     ProfScope ps(K_PAD0_BGR, s);
     if (row * PAD0C_R <= (64u << 10))
-        hipLaunchKernelGGL(k_pad_level0_bgr<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, L, first_slot, tight, list);
+        hipLaunchKernelGGL(k_pad_level0_bgr<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, L, first_slot, tight);
     else if (row <= (64u << 10))   // frames wider than 4 k pixels: one row per workgroup
-        hipLaunchKernelGGL(k_pad_level0_bgr<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, L, first_slot, tight, list);
+        hipLaunchKernelGGL(k_pad_level0_bgr<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, L, first_slot, tight);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
-hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, int first_slot, int n, const PyrListEntry* list) {
-    if (!slots || n < 1 || (list ? n > 65535 : first_slot < 0) || ld < 1 || ld >= L.n_levels) return hipErrorInvalidValue;
+hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int ld, int first_slot, int n) {
+    if (!slots || n < 1 || first_slot < 0 || ld < 1 || ld >= L.n_levels) return hipErrorInvalidValue;
     dim3 grid(1, (L.h[ld] + 2 * PAD + PYR_R - 1) / PYR_R, n);
     const size_t shm = ((size_t)pyr_vs_row(L.w[ld]) * 2 + (size_t)pyr_out_row(L.w[ld])) * PYR_R;
     ProfScope ps(K_PYRDOWN, s);
-    hipLaunchKernelGGL(k_pyrdown, grid, dim3(PYR_T), shm, s, slots, L, ld, first_slot, list);
+    hipLaunchKernelGGL(k_pyrdown, grid, dim3(PYR_T), shm, s, slots, L, ld, first_slot);
+    return hipGetLastError();
+}
+// List forms: n device-visible entries, geometry per entry from the table; grid and dynamic LDS from Lmax (pmv_device.h)
+hipError_t launch_pad_level0_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n) {
+    if (!slots || !d_geom || !list || n < 1 || n > 65535 || Lmax.n_levels < 1) return hipErrorInvalidValue;
+    dim3 grid(1, (Lmax.h[0] + 2 * PAD + PAD0_R - 1) / PAD0_R, n);
+    const size_t shm = (size_t)pad0_row_lds(Lmax.w[0]) * PAD0_R;
+    ProfScope ps(K_PAD0, s);
+    hipLaunchKernelGGL(k_pad_level0_list, grid, dim3(PAD0_T), shm, s, slots, d_geom, list);
+    return hipGetLastError();
+}
+hipError_t launch_pad_level0_bgr_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n) {
+    if (!slots || !d_geom || !list || n < 1 || n > 65535 || Lmax.n_levels < 1) return hipErrorInvalidValue;
+    const size_t row = (size_t)pad0c_raw_lds(Lmax.w[0]) + (size_t)pad0_row_lds(Lmax.w[0]);
+    const int ph = Lmax.h[0] + 2 * PAD;
+    ProfScope ps(K_PAD0_BGR, s);
+    if (row * PAD0C_R <= (64u << 10))
+        hipLaunchKernelGGL(k_pad_level0_bgr_list<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, d_geom, list);
+    else if (row <= (64u << 10))   // frames wider than 4 k pixels: one row per workgroup
+        hipLaunchKernelGGL(k_pad_level0_bgr_list<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, d_geom, list);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_pyrdown_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, int ld, const PyrListEntry* list, int n) {
+    if (!slots || !d_geom || !list || n < 1 || n > 65535 || ld < 1 || ld >= Lmax.n_levels) return hipErrorInvalidValue;
+    dim3 grid(1, (Lmax.h[ld] + 2 * PAD + PYR_R - 1) / PYR_R, n);
+    const size_t shm = ((size_t)pyr_vs_row(Lmax.w[ld]) * 2 + (size_t)pyr_out_row(Lmax.w[ld])) * PYR_R;
+    ProfScope ps(K_PYRDOWN, s);
+    hipLaunchKernelGGL(k_pyrdown_list, grid, dim3(PYR_T), shm, s, slots, d_geom, ld, list);
     return hipGetLastError();
 }
 
@@ -467,8 +519,9 @@ __device__ inline void stage_J(uint8_t* sJ, const uint8_t* Jorg, int js, int tx0
 // One track through all pyramid levels; executed by one whole 256-thread block (every thread gets the same results). `stamp_on`:
 // this block feeds the diagnostic phase timers.
 struct LKResult { float x, y, err; int status, n_iter, n_lev; };
-template <int T, bool STAMPS>
-__device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, const PyrLayout& L,
+// LRef: const PyrLayout& (k_lk: the launch's by-value geometry) or GeomEntry& (k_lk_batch: the track's entry of the geometry table)
+template <int T, bool STAMPS, class LRef>
+__device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
                                                    const float px0, const float py0, const LKParams& P, const bool stamp_on) {
     constexpr int NPRE = 4;                       // I tiles staged per group (all levels of a 4-level pyramid at once)
     constexpr int SI_BYTES = 35 * SI_STRIDE + 8;   // + two dwords: the aligned loads of the last row may touch the first
@@ -798,24 +851,25 @@ __global__ __launch_bounds__(LK_T) void k_lk(const uint8_t* __restrict__ prevS, 
                                              float* __restrict__ out_err, uint16_t* __restrict__ out_work) {
     const int t = order[blockIdx.x];   // block -> track (XCD-aware order built by the host; -1 = no track)
     if (t < 0 || t >= n) return;
-    const LKResult r = lk_track_block<LK_T, STAMPS>(prevS, nextS, L, prev_xy[2 * t], prev_xy[2 * t + 1], P, t == 0);
+    const LKResult r = lk_track_block<LK_T, STAMPS, const PyrLayout&>(prevS, nextS, L, prev_xy[2 * t], prev_xy[2 * t + 1], P, t == 0);
     lk_store(r, t, out_xy, out_status, out_err, out_work);
 }
 
 // Batched form ("same kernels with a leading batch dimension"): the blocks of several independent sequences in one
-// launch. seqs[q] = byte offsets of the prev / next frame slots of sequence q inside `slots`; blocks[b] = (q, track) with track
-// indexing the concatenated coordinate / result arrays (-1 = padding block). All sequences share the frame geometry L.
+// launch. blocks[b] = the byte offsets of the track's prev / next frame slots inside `slots`, its position, its index into the
+// concatenated result arrays and the index of its frames' geometry in the table `geom` (pmv_device.h): the tracks of one launch may
+// belong to sequences of different frame sizes. The index is workgroup-uniform, the table is read with scalar loads.
 constexpr int LKB_T = 64;   // one wavefront per track: throughput form (see block_sum_exact)
 template <bool STAMPS>
 __global__ __launch_bounds__(LKB_T) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_lk_batch(const uint8_t* __restrict__ slots, const LKBlock* __restrict__ blocks,
-                                                   int n_blocks, PyrLayout L, LKParams P, float* __restrict__ out_xy,
+                                                   int n_blocks, const PyrLayout* __restrict__ geom, LKParams P, float* __restrict__ out_xy,
                                                    uint8_t* __restrict__ out_status, float* __restrict__ out_err, uint16_t* __restrict__ out_work) {
     // grid-stride over the track list: the launcher may cap the grid (PMV_LK_BATCH_BLOCKS) so that the tracks of a round do not occupy
     // every register-file slot of the chip while the short launches of the back-end chains wait for one
     for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
         const LKBlock bk = blocks[b];   // (every record is a real track: the host drops padding entries)
         const int2 bt = make_int2(0, bk.track);
-        const LKResult r = lk_track_block<LKB_T, STAMPS>(slots + bk.prev_off, slots + bk.next_off, L, bk.x, bk.y, P, (b & 63) == 17);
+        const LKResult r = lk_track_block<LKB_T, STAMPS, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), bk.x, bk.y, P, (b & 63) == 17);
         if (STAMPS && P.stamps && (b & 63) == 17 && threadIdx.x == 0) atomicAdd(&P.stamps[13], 1ull);   // diagnostic: sampled tracks
         lk_store(r, bt.y, out_xy, out_status, out_err, out_work);   // (out_work: what this track cost - the next launch's ordering hint, and OPS_lk)
         __syncthreads();
@@ -834,10 +888,10 @@ hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* nex
     return hipGetLastError();
 }
 
-hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout& L,
+hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout* d_geom,
                            const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work) {
     if (n_blocks <= 0) return hipSuccess;
-    if (!slots || !d_blocks || !d_out_xy || !d_status || !d_err || L.n_levels < 1 || L.n_levels > MAX_LEVELS) return hipErrorInvalidValue;
+    if (!slots || !d_blocks || !d_out_xy || !d_status || !d_err || !d_geom) return hipErrorInvalidValue;
     static const int cap = getenv("PMV_LK_BATCH_BLOCKS") ? atoi(getenv("PMV_LK_BATCH_BLOCKS")) : 0;
     // Occupancy cap of the bulk kernel: 13.9 KB of LDS per one-wavefront workgroup lets 11 of them share a CU (160 KB; the prefetch
     // registers of a track, ~150 per lane, allow 12), and then every short kernel of the other classes - the 23 launches of an LM solve,
@@ -850,8 +904,8 @@ hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d
     ProfScope ps(K_LK, s);
     const dim3 grid(cap > 0 && cap < n_blocks ? cap : n_blocks);
     const size_t pad = (size_t)(lds_pad > 0 ? lds_pad : 0);
-    if (P.stamps) hipLaunchKernelGGL(k_lk_batch<true>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, L, P, d_out_xy, d_status, d_err, d_work);
-    else hipLaunchKernelGGL(k_lk_batch<false>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, L, P, d_out_xy, d_status, d_err, d_work);
+    if (P.stamps) hipLaunchKernelGGL(k_lk_batch<true>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, d_geom, P, d_out_xy, d_status, d_err, d_work);
+    else hipLaunchKernelGGL(k_lk_batch<false>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, d_geom, P, d_out_xy, d_status, d_err, d_work);
     return hipGetLastError();
 }
 

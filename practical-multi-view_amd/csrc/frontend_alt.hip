@@ -53,9 +53,10 @@ __device__ inline float knn_window_error(const uint8_t* __restrict__ I, const ui
 
 // getNearestNeighbors + compareFeatures + the best-fit rule of ONE source feature, by one wavefront. `cmp`: the request's candidate
 // list, in LDS or in HBM (the address space is known after inlining).
-__device__ __forceinline__ void knn_one(const KnnRound& r, const int2* __restrict__ cmp, const uint8_t* __restrict__ slots, const PyrLayout& L, int i, int lane) {
+template <class LRef>   // const PyrLayout& (the launch's geometry) or GeomEntry& (the request's entry of the geometry table)
+__device__ __forceinline__ void knn_one(const KnnRound& r, const int2* __restrict__ cmp, const uint8_t* __restrict__ slots, LRef L, int i, int lane) {
     const int fx = r.src_xy[2 * i], fy = r.src_xy[2 * i + 1];
-    const int m = r.m, n_nn = r.n_nn;
+    const int m = r.m, n_nn = r.nn_window & 0xff, window = r.nn_window >> 8;
     int nnv[KNN_MAX_NN], qx[KNN_MAX_NN], qy[KNN_MAX_NN];   // the chosen neighbours and their coordinates ((0,0): the default Feature)
     int nearest = -1, nx = 0, ny = 0;
 #pragma unroll
@@ -78,7 +79,7 @@ __device__ __forceinline__ void knn_one(const KnnRound& r, const int2* __restric
     }
     const uint8_t* I = level_origin(slots + r.src_off, L, 0);
     const uint8_t* J = level_origin(slots + r.cmp_off, L, 0);
-    const int win = (int)ceilf((float)r.window / 2.f);
+    const int win = (int)ceilf((float)window / 2.f);
     // :19-31 sequential `_err < err || err == 0`
     float err = 0.f;
     int best_idx = -1;
@@ -86,14 +87,17 @@ __device__ __forceinline__ void knn_one(const KnnRound& r, const int2* __restric
     for (int k = 0; k < KNN_MAX_NN; k++) {
         if (k >= n_nn) continue;
         const float acc = knn_window_error(I, J, L.stride[0], L.w[0], L.h[0], fx, fy, qx[k], qy[k], win, lane);
-        const float ek = (float)(sqrt((double)acc) / ((double)r.window * (double)r.window));
+        const float ek = (float)(sqrt((double)acc) / ((double)window * (double)window));
         if (ek < err || err == 0.f) { err = ek; best_idx = nnv[k]; }
     }
     if (lane == 0) { r.out_best[i] = best_idx; r.out_err[i] = err; }
 }
 
 // grid (ceil(max n / KNN_WAVES), requests): workgroup (x, y) serves source features KNN_WAVES x .. KNN_WAVES x + KNN_WAVES - 1 of request y
-__global__ __launch_bounds__(64 * KNN_WAVES) void k_knn_round(const uint8_t* __restrict__ slots, PyrLayout L, const KnnRound* __restrict__ recs) {
+// TABLE: the geometry of request y is geom[recs[y].geom] (a round of the batch engine may hold any sizes), else the launch's own L
+template <bool TABLE>
+__global__ __launch_bounds__(64 * KNN_WAVES) void k_knn_round(const uint8_t* __restrict__ slots, PyrLayout L, const PyrLayout* __restrict__ geom,
+                                                              const KnnRound* __restrict__ recs) {
     __shared__ int2 s_cmp[KNN_LDS_M];
     const KnnRound r = recs[blockIdx.y];
     if ((int)blockIdx.x * KNN_WAVES >= r.n) return;   // (the whole workgroup: before the barrier)
@@ -104,13 +108,25 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void k_knn_round(const uint8_t* __r
         __syncthreads();
     }
     if (i >= r.n) return;
-    if (lds) knn_one(r, s_cmp, slots, L, i, lane);
-    else knn_one(r, (const int2*)r.cmp_xy, slots, L, i, lane);
+    if (TABLE) {
+        GeomEntry& G = geom_entry(geom, r.geom);
+        if (lds) knn_one<GeomEntry&>(r, s_cmp, slots, G, i, lane);
+        else knn_one<GeomEntry&>(r, (const int2*)r.cmp_xy, slots, G, i, lane);
+    } else {
+        if (lds) knn_one<const PyrLayout&>(r, s_cmp, slots, L, i, lane);
+        else knn_one<const PyrLayout&>(r, (const int2*)r.cmp_xy, slots, L, i, lane);
+    }
 }
 
 hipError_t launch_knn_round(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const KnnRound* d_recs, int n_requests, int max_n) {
     if (n_requests <= 0 || max_n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_knn_round, dim3((max_n + KNN_WAVES - 1) / KNN_WAVES, n_requests), dim3(64 * KNN_WAVES), 0, s, slots, L, d_recs);
+    hipLaunchKernelGGL(k_knn_round<false>, dim3((max_n + KNN_WAVES - 1) / KNN_WAVES, n_requests), dim3(64 * KNN_WAVES), 0, s, slots, L, (const PyrLayout*)nullptr, d_recs);
+    return hipGetLastError();
+}
+hipError_t launch_knn_round_geom(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const KnnRound* d_recs, int n_requests, int max_n) {
+    if (n_requests <= 0 || max_n <= 0) return hipSuccess;
+    if (!d_geom) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_knn_round<true>, dim3((max_n + KNN_WAVES - 1) / KNN_WAVES, n_requests), dim3(64 * KNN_WAVES), 0, s, slots, PyrLayout{}, d_geom, d_recs);
     return hipGetLastError();
 }
 
@@ -253,7 +269,7 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
     rec.src_off = (unsigned long long)src_slot * L.slot_bytes; rec.cmp_off = (unsigned long long)cmp_slot * L.slot_bytes;
     rec.src_xy = (const int*)(d + 64); rec.cmp_xy = rec.src_xy + 2 * (size_t)n;
     rec.out_best = (int*)ctx->dm_out_xy; rec.out_err = ctx->dm_err;
-    rec.n = n; rec.m = m; rec.n_nn = n_neighbours; rec.window = window;
+    rec.n = n; rec.m = m; rec.nn_window = knn_pack(n_neighbours, window); rec.geom = 0;
     memcpy(h, &rec, sizeof(rec));
     memcpy(h + 64, src_xy, (size_t)n * 8);
     if (m) memcpy(h + 64 + (size_t)n * 8, cmp_xy, (size_t)m * 8);

@@ -344,7 +344,8 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
     if (fed >= 0) pmv::batch_ingest_finish(ing, fed);   // finished or failed: its whole ring is free
 }
 
-// The parameter rules the entry points share: bundle_size, and for a batch the frame size and the plugin pairs (those of the single run).
+// The parameter rules the entry points share: bundle_size, and for a batch the sequence's own frame size (within the context's capacity) and
+// the plugin pairs (those of the single run).
 static int check_params(pmv_ctx* ctx, const char* who, const pmv_pipeline_params& P, bool batch) {
     if (P.bundle_size != 0 && P.bundle_size < 3) { pmv::set_err(ctx, "%s: bundle_size 1..2 divides by zero in the reference (OdometryPipeline.cpp:407)", who); return PMV_ERR_INVALID; }
     if (P.bundle_size > ctx->max_ba_cams) { pmv::set_err(ctx, "%s: bundle_size exceeds max_ba_cams", who); return PMV_ERR_CAPACITY; }
@@ -364,24 +365,28 @@ static int check_params(pmv_ctx* ctx, const char* who, const pmv_pipeline_params
 // fed from host_frames[b] (streamed batch), staged in place (host_frames null: the sequences with build_pyramids), or not at all.
 static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                      const uint8_t* const* host_frames, const int* first_slot, const int* ring, pmv_pipeline_result** out) {
-    for (int b = 0; b < B; b++) {
+    // every sequence has its own frame size (the reference takes whatever cv::imread returns, Frame.cpp:31-42; KITTI odometry comes in three)
+    for (int b = 0; b < B; b++)
         if (const int rc = check_params(ctx, who, params[b], true)) return rc;
-        if (params[b].w != params[0].w || params[b].h != params[0].h) { pmv::set_err(ctx, "%s: all sequences must share the frame size", who); return PMV_ERR_INVALID; }
-    }
     struct Open { pmv_ctx* c; Open(pmv_ctx* c_) : c(c_) { c->batch_open++; } ~Open() { c->batch_open--; } } open(ctx);   // (pmv_set_frame_format)
     pmv::BatchEngine* eng = nullptr;
     int rc = pmv::batch_engine_get(ctx, B, &eng);
     if (rc != PMV_OK) return rc;
     rc = pmv_sync(ctx);
     if (rc != PMV_OK) return rc;
+    {   // the geometry table of the run's batched launches: one entry per distinct frame size, before any feeder or sequence thread exists
+        std::vector<int> ws((size_t)B), hs((size_t)B);
+        for (int b = 0; b < B; b++) { ws[(size_t)b] = params[b].w; hs[(size_t)b] = params[b].h; }
+        if ((rc = pmv::geom_table_set(ctx, ws.data(), hs.data(), B)) != PMV_OK) return rc;
+    }
     std::vector<pmv::FeedSeq> feed;
     std::vector<int> fed((size_t)B, -1);
     for (int b = 0; b < B; b++)
         if (host_frames || params[b].build_pyramids) {
             fed[(size_t)b] = (int)feed.size();
-            feed.push_back({first_slot[b], params[b].n_frames, ring[b], host_frames ? host_frames[b] : nullptr});
+            feed.push_back({first_slot[b], params[b].n_frames, ring[b], host_frames ? host_frames[b] : nullptr, params[b].w, params[b].h});
         }
-    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, params[0].w, params[0].h, host_frames ? ctx->frame_format : PMV_FRAMES_GRAY)) != PMV_OK)
+    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, host_frames ? ctx->frame_format : PMV_FRAMES_GRAY)) != PMV_OK)
         return rc;
     std::vector<int> codes(B, PMV_OK);
     std::vector<std::string> msgs(B);
@@ -473,7 +478,7 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K
     return PMV_OK;
 }
 // B independent sequences in one go. Sequence b uses frame slots first_slot[b] .. first_slot[b] + params[b].n_frames - 1
-// (staged with pmv_frames_stage; all sequences share the frame size), its own K9 (9 doubles at K9 + 9 b) and ground-truth rows.
+// (staged with pmv_frames_stage, each sequence in its own frame size params[b].w x h), its own K9 (9 doubles at K9 + 9 b) and ground-truth rows.
 // Every sequence runs the reference's two host threads (front-end / back-end) with the unchanged adapters; their plugin calls are
 // merged by the context's batch engine into batched launches. out[b] receives sequence b's result, bit-identical to its own
 // pmv_pipeline_run. On error every result that exists is freed and the first error is returned.
@@ -489,11 +494,16 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
             pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: frames [%d, %d) outside the %d slots / too short", b, first_slot[b], first_slot[b] + P.n_frames, ctx->n_slots);
             return PMV_ERR_CAPACITY;
         }
+        if (P.w < 40 || P.h < 40 || P.w > ctx->max_w || P.h > ctx->max_h) {   // (before the slots are looked at: a size no slot can hold)
+            pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: frame %dx%d outside capacity %dx%d", b, P.w, P.h, ctx->max_w, ctx->max_h);
+            return PMV_ERR_CAPACITY;
+        }
         for (int i = 0; i < P.n_frames; i++) {   // the geometry actually staged in the slots, not only the parameter structs
             const pmv::PyrLayout& Ls = ctx->slot_layout[first_slot[b] + i];
             const bool empty = ctx->slot_state[first_slot[b] + i] == pmv::SLOT_EMPTY;
+            // (also what makes overlapping ranges agree: a shared slot holds one size, which every sequence over it must name)
             if (empty || Ls.w[0] != P.w || Ls.h[0] != P.h) {
-                pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: slot %d holds %s (%dx%d), the run is %dx%d", b, first_slot[b] + i,
+                pmv::set_err(ctx, "pmv_pipeline_run_batch: sequence %d: slot %d holds %s (%dx%d), the sequence is %dx%d", b, first_slot[b] + i,
                              empty ? "no frame" : "a frame of another size", Ls.w[0], Ls.h[0], P.w, P.h);
                 return PMV_ERR_INVALID;
             }
@@ -537,6 +547,12 @@ int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_para
         }
     const std::vector<int> rings((size_t)B, ring);
     return run_batch(ctx, "pmv_pipeline_run_batch_streamed", B, params, K9, gt_poses12, host_frames, first_slot, rings.data(), out);
+}
+// diagnostic: launches of the batched legs since the context was created (pmv_ctx::batch_launches)
+int pmv_debug_batch_launches(pmv_ctx* ctx, long long* out4) {
+    if (!ctx || !out4) return PMV_ERR_INVALID;
+    for (int i = 0; i < 4; i++) out4[i] = ctx->batch_launches[i].load();
+    return PMV_OK;
 }
 int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out) {
     if (!out) return pmv::BATCH_INGEST_STATS;

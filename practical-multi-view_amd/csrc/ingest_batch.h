@@ -12,13 +12,15 @@ struct BatchIngest;
 // What a feed serves: it sets a sequence's frames per round (as each route had them before the feeder) and the default form.
 enum FeedKind { FEED_STREAMED, FEED_STAGED, FEED_BRACKET };
 // One sequence of a feed: frame f goes to slot first + f % ring. src: tight w x h host frames (pageable or pinned) in the feed's format, or null: the frames are
-// already staged in their slots (ring = n), only the pad and the pyramid levels are left to do.
-struct FeedSeq { int first, n, ring; const uint8_t* src; };
+// already staged in their slots (ring = n), only the pad and the pyramid levels are left to do. w, h: the sequence's own frame size (the
+// sequences of a feed may differ: the reference takes whatever cv::imread returns, Frame.cpp:31-42).
+struct FeedSeq { int first, n, ring; const uint8_t* src; int w, h; };
 // Validates nothing the caller has not (slot ranges, sizes; the rings of a feed that recycles slots are disjoint); creates *g on first use,
-// marks every slot of the feed built with the feed's geometry (its readers wait in slot_ready for the round that builds it) and starts the
-// feeder thread. Staged ranges may overlap: a slot that several sequences cover is built once.
+// marks every slot of the feed built with its sequence's geometry (its readers wait in slot_ready for the round that builds it) and starts the
+// feeder thread. Staged ranges may overlap: a slot that several sequences cover is built once (the caller has checked that they agree on its
+// size). A feed of several sequences (FEED_STREAMED, FEED_STAGED) finds every sequence's size in the context's geometry table (geom_table_set).
 // `format` (pmv_frame_format) is what the host frames hold: gray, or tight BGR (3 w h bytes a frame) that level 0 converts on the way in.
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h, int format = PMV_FRAMES_GRAY);
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int format = PMV_FRAMES_GRAY);
 bool batch_ingest_active(const BatchIngest* g);
 // Combiner thread: make `s` wait on the GPU for feed round `round` (the feeder's stream is in order: every earlier round as well).
 hipError_t batch_ingest_wait_gpu(BatchIngest* g, hipStream_t s, int round);

@@ -14,7 +14,9 @@
 //       copy:   one hipMemcpyAsync of the block into an HBM landing buffer; level 0 is read from there;
 //       mapped: no copy call; k_pad_level0 reads level 0 straight from mapped pinned host memory (the staging buffer for a pageable
 //               source, the caller's own pinned buffer through its device address otherwise);
-//     then one k_pad_level0 and one k_pyrdown launch per level for the whole round, and an event. A feed of COLOUR frames (tight BGR, Frame.cpp:33,40-41;
+//     then one k_pad_level0 and one k_pyrdown launch per level for the whole round, and an event. The sequences of a feed may differ in frame
+//     size: a frame's bytes, its place in the staging block and its source address are its sequence's, and its entry of the slot table names
+//     its geometry in the context's table (pmv_device.h); grid and LDS of the round's launches are sized for the largest geometry in it. A feed of COLOUR frames (tight BGR, Frame.cpp:33,40-41;
 //     pmv_set_frame_format) differs in two things only: a frame is 3 w h bytes, so a round under ROUND_BYTES holds about a third as many, and
 //     level 0 is written by k_pad_level0_bgr, which converts on the way - from the same three sources. The launches read the round's slot
 //     table (list form), unless the round is consecutive slots from consecutive frames (range form, as every round of a bracket). A bracket
@@ -74,13 +76,17 @@ struct BatchIngest {
         std::atomic<int> finished{0};
         std::atomic<int> waiting{0};    // its thread is blocked in acquire
         int next = 0;                   // next frame to feed (feeder thread only)
+        int w = 0, h = 0, geom = 0;     // its frame size and that size's entry of the context's geometry table (0 in a bracket, which has no list rounds)
+        size_t fb = 0;                  // bytes of one of its host frames: w h (gray) or 3 w h (BGR)
+        PyrLayout L{};
     };
     std::unique_ptr<Seq[]> seq;
     pmv_ctx* ctx = nullptr;
-    int B = 0, w = 0, h = 0, frames_per_round = 1;
-    size_t fb = 0;                // bytes of one host frame: w h (gray) or 3 w h (BGR)
+    int B = 0, frames_per_round = 1;
+    size_t max_fb = 0;            // bytes of the largest host frame of the feed
     bool bgr = false;             // the host frames are tight BGR: level 0 through k_pad_level0_bgr
-    PyrLayout L{};
+    bool table = false;           // the sequences' geometries are in the context's table: list rounds are possible
+    bool count_launches = false;  // the feed of a batched run: its launches go into pmv_debug_batch_launches
     bool copy_mode = false, per_round = false, open = false;
     bool dma_release = false;   // copy form of a bracket or staged feed: a staging buffer is free once its DMA is done (else: once its round is)
     std::atomic<int> front_waited{-1};   // newest round the synchronous callers' stream already waits for (slot_ready)
@@ -169,41 +175,62 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         bool range = true;
         for (int i = 1; i < n && range; i++) {
             const BatchIngest::Seq& S = g->seq[take[(size_t)i].first];
-            range = S.first + take[(size_t)i].second % S.ring == S0.first + take[0].second % S0.ring + i &&
+            range = S.first + take[(size_t)i].second % S.ring == S0.first + take[0].second % S0.ring + i && S.geom == S0.geom &&
                     (S0.src ? take[(size_t)i].first == take[0].first && take[(size_t)i].second == take[0].second + i : !S.src);
         }
         const bool direct = range && g->dma_release && S0.dev;
         const auto tm0 = std::chrono::steady_clock::now();
-        int nc = 0, nh = 0;   // frames copied into staging, frames from host memory
+        int nc = 0;                  // frames copied into staging
+        size_t cb = 0, hb = 0;       // their bytes (frame after frame, each of its own size); bytes of all frames from host memory
         for (int i = 0; i < n; i++) {
             const BatchIngest::Seq& S = g->seq[take[(size_t)i].first];
             const int f = take[(size_t)i].second;
             tab[i].slot = S.first + f % S.ring;
-            tab[i].pad = 0;
+            tab[i].geom = S.geom;
             tab[i].src = nullptr;   // staged: level 0 in place
             if (!S.src) continue;
-            nh++;
-            if (direct) { tab[i].src = dblk + BatchIngest::HDR + (size_t)i * g->fb; continue; }
-            if (!g->copy_mode && S.dev) { tab[i].src = S.dev + (size_t)f * g->fb; continue; }   // the caller's pinned frame, in place
-            memcpy(blk + BatchIngest::HDR + (size_t)nc * g->fb, S.src + (size_t)f * g->fb, g->fb);
-            tab[i].src = dblk + BatchIngest::HDR + (size_t)nc * g->fb;
+            hb += S.fb;
+            if (direct) { tab[i].src = dblk + BatchIngest::HDR + (size_t)i * S.fb; continue; }   // (range form: the frames of one sequence)
+            if (!g->copy_mode && S.dev) { tab[i].src = S.dev + (size_t)f * S.fb; continue; }   // the caller's pinned frame, in place
+            memcpy(blk + BatchIngest::HDR + cb, S.src + (size_t)f * S.fb, S.fb);   // (cb + fb <= frames_per_round * max_fb: the buffer's size)
+            tab[i].src = dblk + BatchIngest::HDR + cb;
+            cb += S.fb;
             nc++;
         }
         if (nc) g->t_memcpy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
         if (g->copy_mode) {   // frames only for the range form; the table (+ frames) for the list form
-            const uint8_t* from = direct ? S0.src + (size_t)take[0].second * g->fb : range ? blk + BatchIngest::HDR : blk;
+            const uint8_t* from = direct ? S0.src + (size_t)take[0].second * S0.fb : range ? blk + BatchIngest::HDR : blk;
             const size_t off = range ? BatchIngest::HDR : 0;
-            const size_t bytes = range ? (size_t)(direct ? n : nc) * g->fb : nc ? BatchIngest::HDR + (size_t)nc * g->fb : (size_t)n * sizeof(PyrListEntry);
+            const size_t bytes = range ? (direct ? (size_t)n * S0.fb : cb) : nc ? BatchIngest::HDR + cb : (size_t)n * sizeof(PyrListEntry);
             if (bytes && (e = hipMemcpyAsync((void*)(dblk + off), from, bytes, hipMemcpyHostToDevice, g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipMemcpyAsync", e); return; }
             if ((e = hipEventRecord(g->copied[buf], g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventRecord", e); return; }
         }
-        const int first = range ? tab[0].slot : 0;
-        const PyrListEntry* dtab = range ? nullptr : (const PyrListEntry*)dblk;
-        e = g->bgr ? launch_pad_level0_bgr(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab)   // (every frame of a colour feed has a source)
-                   : launch_pad_level0(g->stream, ctx->d_slots, g->L, first, n, range ? tab[0].src : nullptr, dtab);
-        if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
-        for (int l = 1; l < g->L.n_levels; l++)
-            if ((e = launch_pyrdown(g->stream, ctx->d_slots, g->L, l, first, n, dtab)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
+        int n_levels;
+        if (range) {   // one geometry, by value
+            const int first = tab[0].slot;
+            n_levels = S0.L.n_levels;
+            e = g->bgr ? launch_pad_level0_bgr(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src)   // (every frame of a colour feed has a source)
+                       : launch_pad_level0(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src);
+            if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            for (int l = 1; l < n_levels; l++)
+                if ((e = launch_pyrdown(g->stream, ctx->d_slots, S0.L, l, first, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
+        } else {       // geometry per entry; grid, LDS and the levels launched from the largest geometry of THIS round
+            if (!g->table) { fail(g, PMV_ERR_INVALID, "a list round in a feed without a geometry table", hipSuccess); return; }
+            PyrLayout Lmax{};
+            for (int i = 0; i < n; i++) {
+                const PyrLayout& Ls = g->seq[take[(size_t)i].first].L;
+                Lmax.n_levels = std::max(Lmax.n_levels, Ls.n_levels);
+                for (int l = 0; l < Ls.n_levels; l++) { Lmax.w[l] = std::max(Lmax.w[l], Ls.w[l]); Lmax.h[l] = std::max(Lmax.h[l], Ls.h[l]); }
+            }
+            n_levels = Lmax.n_levels;
+            const PyrListEntry* dtab = (const PyrListEntry*)dblk;
+            e = g->bgr ? launch_pad_level0_bgr_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n)
+                       : launch_pad_level0_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n);
+            if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            for (int l = 1; l < n_levels; l++)
+                if ((e = launch_pyrdown_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, l, dtab, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
+        }
+        if (g->count_launches) { ctx->batch_launches[2]++; ctx->batch_launches[3] += n_levels - 1; }
         {
             std::lock_guard<std::mutex> lk(g->ev_mu);
             const size_t k = g->ev_index(round);
@@ -218,7 +245,7 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
             const BatchIngest::Seq& S = g->seq[t.first];
             g->slot_rec[(size_t)(S.first + t.second % S.ring)].store(((long long)t.second << 32) | round);   // (seq_cst: see acquire)
         }
-        g->rounds++; g->frames += n; g->bytes += (long long)nh * (long long)g->fb;
+        g->rounds++; g->frames += n; g->bytes += (long long)hb;
         round++;
         if (g->waiters.load() > 0) { std::lock_guard<std::mutex> lk(g->mu); g->cv.notify_all(); }
     }
@@ -266,7 +293,7 @@ int acquire(BatchIngest* g, int seq, int slot, int* round) {
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int w, int h, int format) {
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int format) {
     CKC(hipSetDevice(ctx->device));
     if (!gp) {
         BatchIngest* g = new BatchIngest();
@@ -284,10 +311,15 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
     bool host = false;
     int sum_F = 0;
     g->per_round = true;
+    g->table = kind != FEED_BRACKET;   // (a bracket is one sequence whose rounds are all ranges)
+    g->count_launches = kind != FEED_BRACKET;
     for (int b = 0; b < B; b++) {
         BatchIngest::Seq& S = g->seq[b];
         const FeedSeq& q = seqs[(size_t)b];
         S.first = q.first; S.n = q.n; S.ring = q.ring; S.src = q.src; S.dev = nullptr;
+        S.w = q.w; S.h = q.h; S.L = layout_for(ctx, q.w, q.h);
+        S.geom = g->table ? ctx->geom_index(q.w, q.h) : 0;
+        REQ(S.geom >= 0, PMV_ERR_INVALID, "feeder: sequence %d: no entry for %dx%d frames in the geometry table", b, q.w, q.h);
         S.F = kind == FEED_BRACKET ? BatchIngest::BRACKET_CHUNK : kind == FEED_STAGED ? BatchIngest::STAGED_CHUNK : std::max(1, std::min(8, S.ring / 2));
         sum_F += S.F;
         g->per_round = g->per_round && S.ring >= S.n;
@@ -303,10 +335,15 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
         }
     }
     g->bgr = host && format == PMV_FRAMES_BGR;
-    g->fb = (size_t)w * h * (g->bgr ? 3 : 1);
-    g->frames_per_round = host ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)BatchIngest::ROUND_FRAMES, BatchIngest::ROUND_BYTES / g->fb, (size_t)sum_F}))
+    g->max_fb = 1;
+    for (int b = 0; b < B; b++) {
+        g->seq[b].fb = (size_t)g->seq[b].w * g->seq[b].h * (g->bgr ? 3 : 1);
+        g->max_fb = std::max(g->max_fb, g->seq[b].fb);
+    }
+    // a round's frames and its buffer's bytes: both from the largest frame of the feed, so every round of frames_per_round frames fits
+    g->frames_per_round = host ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)BatchIngest::ROUND_FRAMES, BatchIngest::ROUND_BYTES / g->max_fb, (size_t)sum_F}))
                                : BatchIngest::TABLE;
-    const size_t need = (BatchIngest::HDR + (host ? (size_t)g->frames_per_round * g->fb : 0) + 4095) & ~(size_t)4095;
+    const size_t need = (BatchIngest::HDR + (host ? (size_t)g->frames_per_round * g->max_fb : 0) + 4095) & ~(size_t)4095;
     static_assert(BatchIngest::ROUND_FRAMES <= BatchIngest::TABLE, "a round's slot table fits its header block");
     // How host frames reach level 0: PMV_BATCH_INGEST=copy | mapped; by default mapped for a streamed batch and copy for a bracket
     // (the DMA into HBM the single-sequence path has always used). A staged feed's slot tables are always copied into HBM, so its kernels do
@@ -326,14 +363,13 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
         CKC(hipMalloc(&g->d_land, BatchIngest::NBUF * g->buf_bytes));
         g->land_bytes = g->buf_bytes;
     }
-    g->ctx = ctx; g->B = B; g->w = w; g->h = h;
-    g->L = layout_for(ctx, w, h);
-    // every slot of the feed carries the feed's geometry and counts as built from here on: its readers wait for its round in slot_ready. The
-    // first sequence that covers a slot builds it.
+    g->ctx = ctx; g->B = B;
+    // every slot of the feed carries its sequence's geometry and counts as built from here on: its readers wait for its round in slot_ready.
+    // The first sequence that covers a slot builds it.
     for (int b = 0; b < B; b++)
         for (int i = 0; i < g->seq[b].ring; i++) {
             const size_t s = (size_t)(g->seq[b].first + i);
-            ctx->slot_layout[s] = g->L;
+            ctx->slot_layout[s] = g->seq[b].L;
             ctx->slot_state[s] = SLOT_BUILT;
             if (g->slot_rec[s].load() == BatchIngest::NONE) g->slot_rec[s].store(BatchIngest::pending(b));
         }
@@ -427,7 +463,7 @@ int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* 
     CKC(hipSetDevice(ctx->device));
     // frames in the slots about to be overwritten may still be read by work in flight on the front-end stream
     CKC(hipStreamSynchronize(ctx->s_front));
-    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray}}, w, h, ctx->frame_format);
+    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray, w, h}}, ctx->frame_format);
 }
 
 int pmv_frames_stream_end(pmv_ctx* ctx) {

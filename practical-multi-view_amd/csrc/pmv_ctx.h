@@ -36,6 +36,16 @@ struct pmv_ctx {
     std::vector<pmv::PyrLayout> slot_layout;  // per slot: geometry of the frame it holds ...
     std::vector<uint8_t> slot_state;          // ... and what of it is there (pmv::SlotState)
     uint8_t* d_slots = nullptr;
+    // Geometry table of the batched launches (pmv_device.h): one PyrLayout per distinct frame size of the current batched run, slot_bytes =
+    // the capacity pitch; host mirror and device copy. Rewritten by run_batch before its feeder and sequence threads start (the context is
+    // synchronised there); during the run it is only read - by the combiners and the feeder on the host, by the kernels through scalar loads.
+    static constexpr int MAX_GEOM = 256;      // (a batch has at most 256 sequences)
+    std::vector<pmv::PyrLayout> geom;
+    pmv::PyrLayout* d_geom = nullptr;
+    int geom_index(int w, int h) const { for (size_t i = 0; i < geom.size(); i++) if (geom[i].w[0] == w && geom[i].h[0] == h) return (int)i; return -1; }
+    // launches of the batched legs since the context was created: k_lk_batch, k_knn_round (combiners), k_pad_level0[_bgr], k_pyrdown (feeder of
+    // pmv_pipeline_run_batch[_streamed]) - pmv_debug_batch_launches; the profiler's per-class event pools are not made for two LK lanes
+    std::atomic<long long> batch_launches[4];
     // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames, or a third as many BGR ones (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;
@@ -92,6 +102,8 @@ PyrLayout make_layout(int w, int h);
 int backend_create(pmv_ctx* c);     // allocates PnP/BA workspaces
 void backend_destroy(pmv_ctx* c);
 PyrLayout layout_for(pmv_ctx* ctx, int w, int h);
+// replaces the context's geometry table by the distinct sizes among (w[b], h[b]), b < B, on the host and on the device (synchronous)
+int geom_table_set(pmv_ctx* ctx, const int* w, const int* h, int B);
 // The readiness rule of frame slot `slot`: every reader of a pyramid goes through it (the synchronous calls, the batch engine's sequence
 // threads and its combiners). When `feed` covers the slot (for sequence `seq` of the feed), waits on the host until the feed round that
 // builds the frame is enqueued; then `s`, if given, waits for that round on the GPU, and *round, if given, receives it (-1: none). Then the

@@ -21,6 +21,23 @@ struct PyrLayout {
     uint32_t slot_bytes;
 };
 
+static_assert(sizeof(PyrLayout) == 92, "PyrLayout: 23 dwords, the entry of a geometry table");
+
+// ---- geometry table ---------------------------------------------------------------------------------------
+// A batch may hold sequences of different frame sizes (the reference takes whatever cv::imread returns, Frame.cpp:31-42). Its batched
+// launches then carry no PyrLayout of their own: the context keeps a small array of them in device memory, one entry per distinct frame
+// size of the run (slot_bytes = the capacity pitch in every entry), written before the sequence threads start, and every track / request /
+// frame record carries the index of its entry. The index is the same for the whole workgroup; it goes through readfirstlane, and the
+// table is read through the constant address space, so the level dimensions, strides and offsets arrive by scalar loads and stay in
+// scalar registers, exactly as the fields of a by-value kernel argument do (which is itself a scalar load from the kernarg segment).
+typedef const __attribute__((address_space(4))) PyrLayout GeomEntry;
+__device__ __forceinline__ GeomEntry& geom_entry(const PyrLayout* __restrict__ table, int index) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    index = __builtin_amdgcn_readfirstlane(index);
+#endif
+    return ((GeomEntry*)(uintptr_t)table)[index];
+}
+
 __host__ __device__ inline int reflect101(int p, int len) {
     if (len == 1) return 0;
     while (p < 0 || p >= len) {
@@ -35,6 +52,14 @@ __host__ __device__ inline const uint8_t* level_origin(const uint8_t* slot, cons
     return slot + L.off[l] + (size_t)PAD * L.stride[l] + PAD;
 }
 __host__ __device__ inline uint8_t* level_origin(uint8_t* slot, const PyrLayout& L, int l) {
+    return slot + L.off[l] + (size_t)PAD * L.stride[l] + PAD;
+}
+
+// (the same for an entry of the geometry table)
+__host__ __device__ inline const uint8_t* level_origin(const uint8_t* slot, GeomEntry& L, int l) {
+    return slot + L.off[l] + (size_t)PAD * L.stride[l] + PAD;
+}
+__host__ __device__ inline uint8_t* level_origin(uint8_t* slot, GeomEntry& L, int l) {
     return slot + L.off[l] + (size_t)PAD * L.stride[l] + PAD;
 }
 
@@ -135,20 +160,29 @@ struct __attribute__((aligned(32))) LKBlock {
     unsigned long long prev_off, next_off;   // byte offsets of the sequence's prev / next frame slot
     float x, y;                              // the track's position in the prev frame
     int track;                               // index into the concatenated result arrays
-    int pad;
+    int geom;                                // the sequence's entry of the geometry table
 };
-hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout& L, const LKParams& P,
+static_assert(sizeof(LKBlock) == 32, "LKBlock: one 32-byte record per workgroup");
+// d_geom: the geometry table in device memory; every record's `geom` is an entry of it (the caller's business, on the host)
+hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
                            float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
 hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, int stride, uint8_t* d_gray);   // cv::cvtColor(BGR2GRAY), 8-bit
 // one entry of a slot-list pyramid build (the feeder): destination slot and, for level 0, the device-visible address of the tight gray
-// frame (HBM landing area or mapped pinned host memory), null = already staged in the slot
-struct PyrListEntry { const uint8_t* src; int slot; int pad; };
-// Pyramid stages of n slots: the range first_slot .. first_slot + n - 1 (level 0 from n tight gray frames at `tight`, null: in place), or the n
-// entries of a device-visible `list`.
-hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight = nullptr, const PyrListEntry* list = nullptr);
-// The same level 0 from tight BGR frames (3 w h bytes each), converted on the way (k_pad_level0_bgr); every entry of `list` has a source.
-hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight, const PyrListEntry* list = nullptr);
-hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, int first_slot, int n, const PyrListEntry* list = nullptr);
+// frame (HBM landing area or mapped pinned host memory), null = already staged in the slot; `geom` = the frame's entry of the geometry table
+struct PyrListEntry { const uint8_t* src; int slot; int geom; };
+// Range form: pyramid stages of the n consecutive slots first_slot .. first_slot + n - 1, all of ONE geometry L (level 0 from n tight gray
+// frames at `tight`, null: in place).
+hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight = nullptr);
+// The same level 0 from tight BGR frames (3 w h bytes each), converted on the way (k_pad_level0_bgr).
+hipError_t launch_pad_level0_bgr(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight);
+hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int level_dst, int first_slot, int n);
+// List form (the feeder): the n entries of a device-visible `list`, each with its own geometry d_geom[list[i].geom] (device memory). Lmax: a
+// layout whose level count and level dimensions are, level by level, at least those of every entry in the list - it sizes the grid and the
+// dynamic LDS; a workgroup whose rows lie outside its own frame returns as a whole before its first load or barrier, and so does every
+// workgroup of k_pyrdown whose frame has no level `level_dst`. Every entry of a BGR list has a source.
+hipError_t launch_pad_level0_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n);
+hipError_t launch_pad_level0_bgr_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n);
+hipError_t launch_pyrdown_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, int level_dst, const PyrListEntry* list, int n);
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
@@ -180,10 +214,16 @@ struct __attribute__((aligned(64))) KnnRound {
     unsigned long long src_off, cmp_off;
     const int* src_xy; const int* cmp_xy;
     int* out_best; float* out_err;       // per source feature: candidate index or -1 (the default Feature at (0,0)), its window error
-    int n, m, n_nn, window;
+    int n, m;
+    int nn_window;                       // n_nn (1..8) | window (1..63) << 8: knn_pack
+    int geom;                            // the request's entry of the geometry table (table form)
 };
-// k_knn_round over n_requests records in device memory (all frames share the geometry L); max_n = the largest n among them
+static_assert(sizeof(KnnRound) == 64, "KnnRound: one 64-byte record per request");
+inline int knn_pack(int n_nn, int window) { return n_nn | (window << 8); }
+// k_knn_round over n_requests records in device memory; max_n = the largest n among them. Both frames of a request have the geometry L
+// (pmv_knn_match: a round of one) or, table form, d_geom[record.geom] (the batch engine: a round may hold any sizes).
 hipError_t launch_knn_round(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const KnnRound* d_recs, int n_requests, int max_n);
+hipError_t launch_knn_round_geom(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const KnnRound* d_recs, int n_requests, int max_n);
 // k_fast_score + k_fast_select over n_cells cell records (x0, y0, w, h, slot, byte offset of the cell's score map in d_score, 0, 0) in
 // device-visible memory; a "cell" may be as large as the frame. max_pix = the largest w * h among them. Outputs per cell: max_per_cell
 // (x, y) pairs, as many float responses, one count.
