@@ -52,6 +52,9 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
                    int max_ba_cams, int max_ba_points, int max_ba_obs);
 void pmv_ctx_destroy(pmv_ctx* ctx);
 const char* pmv_last_error(pmv_ctx* ctx); /* ctx may be NULL for create-time errors */
+/* The text of the last failing call made on the CALLING thread (any context; "" if none): what a caller reads when several of its
+ * threads use one context at once (the batch sessions below), where pmv_last_error may already hold another thread's message. */
+const char* pmv_thread_error(void);
 int pmv_sync(pmv_ctx* ctx);               /* waits for both streams */
 
 /* ---- frames / pyramids ----------------------------------------------------------------------- */
@@ -315,6 +318,89 @@ int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out);
 /* diagnostic, per combiner in the order LK, detectors, PnP, BA, DLT: counts10 = {launch rounds, requests served} x 5; times15 (may
  * be NULL) = seconds spent {CPU time of the combiner thread, wall time processing batches, of that waiting for the GPU} x 5 */
 int pmv_batch_stats(pmv_ctx* ctx, long long* counts10, double* times15);
+
+/* ---- batch sessions: the batch engine for callers who bring their own pipeline --------------------------------------------------------
+ * pmv_pipeline_run_batch[_streamed] run this library's own mirror of OdometryPipeline and need every frame of every sequence before the
+ * call. A session opens the same machinery - the combiners of the five kernel classes and the list-form pyramid kernels - to plugin-level
+ * callers: the reference's real OdometryPipeline behind the adapters of INTEGRATION.md, a live camera loop, a Python experiment. Frames
+ * arrive one at a time, the length of a sequence is not known in advance, and B callers' requests share batched launches.
+ *
+ * pmv_batch_open: n_seq (1..256, else PMV_ERR_INVALID) back-end workspace sets; sizes_wh holds n_sizes (1..256) distinct (w, h) pairs:
+ *   every frame that a session call will see has one of these sizes, each within 40x40 .. max_w x max_h (else PMV_ERR_CAPACITY; a pair named
+ *   twice is PMV_ERR_INVALID). They become the geometry table of the batched launches. Memory: one pinned staging pool of min(64, max(4,
+ *   2 n_seq)) blocks of the largest declared BGR frame (at most 256 MB), freed by pmv_batch_close.
+ *   Ownership of the context: a session owns the batch engine and the geometry table. While one is open, pmv_pipeline_run_batch,
+ *   pmv_pipeline_run_batch_streamed and a second pmv_batch_open return PMV_ERR_INVALID; pmv_batch_open during one of those runs returns
+ *   PMV_ERR_INVALID. The single-sequence pmv_* calls stay legal on slots that no session call is using; pmv_set_frame_format is unaffected,
+ *   because a session names the format per upload (a refused call changes nothing).
+ * pmv_batch_close: PMV_ERR_INVALID while session calls are still outstanding, and without an open session. Afterwards the context serves
+ *   batched runs again; the frame slots keep what they hold.
+ * Any session call (every pmv_batch_* below) without an open session is PMV_ERR_INVALID.
+ *
+ * Threads: every session call may be made from any thread at any time, by any number of threads (n_seq does not limit the front-end calls:
+ *   requests that do not fit a round's result blocks wait for the next round). Error text is per thread: read it with pmv_thread_error();
+ *   pmv_last_error(ctx) is one buffer per context and holds the last message of ANY thread. The callers' threads launch nothing and wait for no HIP stream: requests go to the
+ *   class's combiner thread, uploads to the upload thread. The four back-end calls (those that take `seq`) allow one outstanding call per
+ *   seq and call; the calls of one seq share that seq's pinned block, so the library makes them take turns. seq outside 0 .. n_seq - 1 is
+ *   PMV_ERR_INVALID.
+ * Results: each call returns exactly the bits the single-sequence pmv_* call of the same name returns for the same inputs, with the same
+ *   status codes raised in the same places (PMV_ERR_DEGENERATE of pmv_pnp_ransac, PMV_ERR_OVERFLOW of a no-limit pmv_detect_gftt, ...);
+ *   pmv_batch_ba_solve matches pmv_ba_solve in the context's current pmv_set_ba_mode. The LK ordering hint of the batched runs stays
+ *   internal: a session LK call uses the engine's default order, which changes no result.
+ * Slots are the caller's to manage, as with pmv_frame_upload: a slot must not be uploaded into while a call that reads it is outstanding
+ *   (for the reference's pipeline: frames k - 1 and k are live, so a ring of 3 slots per sequence is enough). This is the caller's rule;
+ *   the library does not police it. Session calls must not name slots of an open pmv_frames_stream_begin bracket. */
+int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes);
+int pmv_batch_close(pmv_ctx* ctx);
+/* Like pmv_frame_upload / pmv_frame_upload_bgr (format: pmv_frame_format; anything else is PMV_ERR_INVALID), with `stride` bytes per source
+ * row. Callable from any number of threads: the upload thread takes whatever requests accumulated while its previous round ran and builds
+ * them in ONE round - at most one gray and one BGR level-0 launch and one k_pyrdown launch per level, whatever the number of requests and
+ * the mix of sizes - on the upload stream.
+ *   Sources: `pixels` may be pageable host memory, pinned mapped host memory, or device memory of the context's device. Pinned memory mapped
+ *     at its host address (hipHostMalloc, torch pin_memory) and device memory are read IN PLACE by the kernel, at any base alignment and any
+ *     stride (a camera buffer with aligned rows, an ROI view into a larger image, a hipMallocPitch surface): a row is fetched as the aligned
+ *     dwords that hold its bytes and no others, so nothing past the last row's last byte is read. Anything else is copied by the calling
+ *     thread, row by row and tight, into a block of the session's pinned staging pool (the call waits for a free block). Device memory of
+ *     another device is PMV_ERR_INVALID, and so is a device frame that reaches past the end of its allocation.
+ *     A source read in place is read by a kernel on the session's own stream, which waits for no other stream: whatever produced the
+ *     pixels (a kernel or copy on the caller's stream, a decoder) must have COMPLETED before the call, e.g. by a stream synchronise.
+ *   Return of an upload: when the call returns, the source may be reused and the slot is built (its size and state recorded); a session call
+ *     on that slot from any thread needs no further ordering, because the request returned only after its round's completion word was seen.
+ *   Upload errors: a size not declared at pmv_batch_open is PMV_ERR_INVALID and the message names the size; stride below w (gray) or 3 w
+ *     (BGR) is PMV_ERR_CAPACITY; a slot outside n_slots is PMV_ERR_CAPACITY, as for pmv_frame_upload.
+ *   Two uploads into one slot that meet in a round are built one after the other, in arrival order. */
+int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format);
+/* The contracts of the pmv_* calls of the same name, argument for argument and status code for status code, served by the class's combiner
+ * in batched launches (LK and kNN: the LK combiners; the three detectors: the detector combiner). The slots must hold frames of a declared
+ * size (else PMV_ERR_INVALID). */
+int pmv_batch_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* out_status, float* out_err);
+int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
+                        int* out_best, float* out_err);
+int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
+                          int* out_count);
+int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
+                               int* out_count);
+int pmv_batch_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy,
+                          float* out_response, int* out_count);
+/* The same for the back-end: `seq` (0 .. n_seq - 1, else PMV_ERR_INVALID) selects the workspace set; one outstanding call per seq and call.
+ * pmv_batch_ba_solve runs in the context's current pmv_set_ba_mode; the calls are logged by pmv_record_enable like the single ones. */
+int pmv_batch_pnp_ransac(pmv_ctx* ctx, int seq, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec,
+                         int iterations, float reproj_err, double confidence, int* out_inliers, int* out_n_inliers);
+int pmv_batch_ba_solve(pmv_ctx* ctx, int seq, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx,
+                       int n_obs, const double* K, double huber_delta, int max_iterations, pmv_ba_summary* summary);
+int pmv_batch_triangulate_candidates(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
+                                     double* out_Q, uint8_t* out_mask, int* out_good);
+int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
+                                   double* models, int* n_models, int* counts);
+/* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds, and the
+ * pyrDown launches are the sum over the rounds of the levels above 0 of each round's tallest pyramid. */
+int pmv_batch_upload_stats(pmv_ctx* ctx, long long* out4);
+/* diagnostic: one record of 8 ints per upload round since pmv_batch_open (the first 65536 rounds), in order:
+ * [0..4] frames of the round whose pyramid has 1, 2, 3, 4, 5 levels; [5] level-0 launches and [6] pyrDown launches the round made, counted
+ * where they are made; [7] frames of the round that were read in place (the others came through the staging pool). Writes the first
+ * min(capacity, rounds) records to out8 and returns the number of rounds recorded (capacity 0: only the count). */
+int pmv_batch_upload_rounds(pmv_ctx* ctx, int* out8, int capacity);
+
 void pmv_pipeline_free(pmv_pipeline_result* r);
 /* Same, but the (host-container) teardown runs on a background thread; pmv_pipeline_drain() joins all of them. */
 void pmv_pipeline_release(pmv_pipeline_result* r);

@@ -33,7 +33,7 @@ class BaSummary(C.Structure):
 
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
-    "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_sync",
+    "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_thread_error", "pmv_sync",
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_lk_track", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
@@ -41,6 +41,9 @@ ABI_SYMBOLS = [
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
     "pmv_pipeline_frame_feature_count", "pmv_pipeline_get_frame_features", "pmv_pipeline_stats_count", "pmv_pipeline_get_stats",
+    "pmv_batch_open", "pmv_batch_close", "pmv_batch_frame_upload", "pmv_batch_upload_stats", "pmv_batch_upload_rounds",
+    "pmv_batch_lk_track", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
+    "pmv_batch_pnp_ransac", "pmv_batch_ba_solve", "pmv_batch_triangulate_candidates", "pmv_batch_fivepoint_hypotheses",
 ]
 
 
@@ -123,6 +126,57 @@ def _batch_streamed_args(seqs, w, h, ring, first_slot, fmt="gray"):
     if len(first) != B:
         raise ValueError(f"pipeline_run_batch_streamed: {len(first)} first slots for {B} sequences")
     return frames, gts, first
+
+
+BATCH_UPLOAD_KEYS = ["rounds", "frames", "level0_launches", "pyrdown_launches"]   # pmv_batch_upload_stats, in order
+
+
+def _session_sizes(sizes):
+    """the (w, h) pairs of batch_open as a flat int32 array, checked before anything reaches the library"""
+    try:
+        pairs = [tuple(p) for p in sizes]
+    except TypeError:
+        raise ValueError(f"batch_open: sizes must be a sequence of (w, h) integer pairs, got {sizes!r}") from None
+    if not pairs:
+        raise ValueError("batch_open: no sizes")
+    for p in pairs:
+        if len(p) != 2 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in p):
+            raise ValueError(f"batch_open: sizes must be (w, h) integer pairs, got {p!r}")
+    return np.asarray(pairs, np.int32).reshape(-1)
+
+
+def _upload_source(frame, fmt):
+    """what batch_frame_upload hands to pmv_batch_frame_upload: (address, w, h, stride in bytes, format, the object that keeps the memory
+    alive). frame: a uint8 numpy array - (h, w) for "gray", (h, w, 3) for "bgr" - whose pixel axis (gray: the columns; bgr: columns and
+    channels) is contiguous, with ANY row stride: a view into a larger image is passed in place with its own address and stride, it is not
+    copied tight. Or any object with data_ptr(), shape and stride() (a torch tensor, pageable, host-pinned or on the device; strides in
+    elements). Everything is checked here, before the library is touched."""
+    if not isinstance(fmt, str) or fmt not in FRAME_FORMATS:
+        raise ValueError(f"batch_frame_upload: fmt must be one of {sorted(FRAME_FORMATS)}, got {fmt!r}")
+    nd = 3 if fmt == "bgr" else 2
+    if isinstance(frame, np.ndarray):
+        if frame.dtype != np.uint8:
+            raise ValueError(f"batch_frame_upload: frames are uint8, got {frame.dtype}")
+        shape, strides, addr = tuple(frame.shape), tuple(frame.strides), frame.ctypes.data
+    elif all(hasattr(frame, a) for a in ("data_ptr", "shape", "stride")):
+        dt = str(getattr(frame, "dtype", "uint8"))
+        if not dt.endswith("uint8"):
+            raise ValueError(f"batch_frame_upload: frames are uint8, got {dt}")
+        shape, strides, addr = tuple(int(v) for v in frame.shape), tuple(int(v) for v in frame.stride()), int(frame.data_ptr())
+    else:
+        raise ValueError(f"batch_frame_upload: a uint8 numpy array or an object with data_ptr(), shape and stride() is needed, got {type(frame).__name__}")
+    if len(shape) != nd or (nd == 3 and shape[2] != 3):
+        want = "(h, w, 3)" if nd == 3 else "(h, w)"
+        raise ValueError(f"batch_frame_upload: a {fmt} frame is {want} uint8, got shape {shape}")
+    h, w = shape[0], shape[1]
+    if h < 1 or w < 1:
+        raise ValueError(f"batch_frame_upload: empty frame {shape}")
+    if (nd == 2 and strides[1] != 1) or (nd == 3 and (strides[2] != 1 or strides[1] != 3)):
+        raise ValueError(f"batch_frame_upload: the pixels of a row must be contiguous (strides {strides} for shape {shape}); only the row stride is free")
+    stride = strides[0] if h > 1 else max(strides[0], w * (nd == 3 and 3 or 1))
+    if stride < w * (3 if nd == 3 else 1) or stride >= 2 ** 31:
+        raise ValueError(f"batch_frame_upload: row stride {strides[0]} bytes for rows of {w * (3 if nd == 3 else 1)} bytes (overlapping or reversed rows)")
+    return addr, w, h, stride, FRAME_FORMATS[fmt], frame
 
 
 def _per_sequence(who, name, value, B):
@@ -224,6 +278,9 @@ def load_library():
         _lib = C.CDLL(p, mode=C.RTLD_GLOBAL)
         _lib.pmv_last_error.restype = C.c_char_p
         _lib.pmv_last_error.argtypes = [C.c_void_p]
+        if hasattr(_lib, "pmv_thread_error"):
+            _lib.pmv_thread_error.restype = C.c_char_p
+            _lib.pmv_thread_error.argtypes = []
         if hasattr(_lib, "pmv_pipeline_run"):
             _lib.pmv_pipeline_run.argtypes = [C.c_void_p, C.POINTER(PipelineParams), _f64p, _f64p, C.POINTER(C.c_void_p)]
             _lib.pmv_pipeline_run_streamed.argtypes = [C.c_void_p, C.POINTER(PipelineParams), _f64p, _f64p, _u8p, C.POINTER(C.c_void_p)]
@@ -299,6 +356,11 @@ class Context:
     def _ck(self, rc):
         if rc != 0:
             raise PmvError(rc, self.lib.pmv_last_error(self.h).decode())
+
+    def _ckt(self, rc):
+        """_ck for calls that several threads make on one context at once: the calling thread's own error text (pmv_thread_error)"""
+        if rc != 0:
+            raise PmvError(rc, self.lib.pmv_thread_error().decode())
 
     def sync(self):
         self._ck(self.lib.pmv_sync(self.h))
@@ -696,3 +758,151 @@ class Context:
 
     def pipeline_drain(self):
         self.lib.pmv_pipeline_drain()
+
+    # ---- batch sessions: the batch engine for callers who bring their own pipeline (include/pmv_hip.h, "batch sessions") ----
+    # Every batch_* call may be made from any Python thread: ctypes releases the GIL during a call, so the threads' requests do meet in
+    # the combiners' launches. Each returns exactly what the call without the prefix returns.
+    def batch_open(self, n_seq, sizes):
+        """opens a session: n_seq back-end workspace sets (seq = 0 .. n_seq - 1), sizes = the (w, h) pairs of every frame the session will see"""
+        if isinstance(n_seq, (bool, np.bool_)) or not isinstance(n_seq, (int, np.integer)) or n_seq < 1:
+            raise ValueError(f"batch_open: n_seq must be a positive integer, got {n_seq!r}")
+        wh = _session_sizes(sizes)
+        self._ckt(self.lib.pmv_batch_open(self.h, int(n_seq), _p(wh, _i32p), len(wh) // 2))
+
+    def batch_close(self):
+        self._ckt(self.lib.pmv_batch_close(self.h))
+
+    def batch_session(self, n_seq, sizes):
+        """with ctx.batch_session(n_seq, sizes): ... - batch_open on entry, batch_close on exit"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def session():
+            self.batch_open(n_seq, sizes)
+            try:
+                yield self
+            finally:
+                self.batch_close()
+        return session()
+
+    def batch_frame_upload(self, slot, frame, fmt="gray"):
+        """one frame into `slot` through the session's upload class (see _upload_source for what `frame` may be); returns when the slot's
+        pyramid is built. A pinned or device source is read in place by a kernel on the session's own stream: the work that produced it (a
+        torch op on torch's stream, say) must have completed - torch.cuda.synchronize() or a blocking copy - before this call"""
+        addr, w, h, stride, f, keep = _upload_source(frame, fmt)
+        self._ckt(self.lib.pmv_batch_frame_upload(self.h, int(slot), C.c_void_p(addr), w, h, stride, f))
+        del keep
+
+    def batch_upload_stats(self):
+        """{rounds, frames, level0_launches, pyrdown_launches} of the upload class since batch_open"""
+        out = (C.c_longlong * 4)()
+        self._ckt(self.lib.pmv_batch_upload_stats(self.h, out))
+        return dict(zip(BATCH_UPLOAD_KEYS, [int(v) for v in out]))
+
+    def batch_upload_rounds(self):
+        """one dict per upload round since batch_open (pmv_batch_upload_rounds): frames_by_levels (frames whose pyramid has 1..5 levels),
+        level0_launches, pyrdown_launches, in_place (frames read where the caller has them; the others came through the staging pool)"""
+        n = self.lib.pmv_batch_upload_rounds(self.h, None, 0)
+        self._ckt(min(n, 0))
+        out = np.zeros((max(n, 1), 8), np.int32)
+        self._ckt(min(self.lib.pmv_batch_upload_rounds(self.h, _p(out, _i32p), n), 0))
+        return [dict(frames_by_levels=[int(v) for v in r[:5]], level0_launches=int(r[5]), pyrdown_launches=int(r[6]), in_place=int(r[7])) for r in out[:n]]
+
+    def batch_detect_gftt(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0):
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
+        n = cells.shape[0]
+        cap = max_per_cell if max_per_cell > 0 else GFTT_UNLIMITED_CAP
+        xy = np.zeros((n, cap, 2), np.int32)
+        cnt = np.zeros(n, np.int32)
+        self._ckt(self.lib.pmv_batch_detect_gftt(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), C.c_double(min_dist),
+                                                _p(xy, _i32p), _p(cnt, _i32p)))
+        return [xy[i, : cnt[i]].copy() for i in range(n)]
+
+    def batch_detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
+        n = cells.shape[0]
+        xy = np.zeros((n, max(max_per_cell, 1), 2), np.int32)
+        sc = np.zeros((n, max(max_per_cell, 1)), np.float64)
+        cnt = np.zeros(n, np.int32)
+        self._ckt(self.lib.pmv_batch_detect_shitomasi(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), _p(xy, _i32p),
+                                                     _p(sc, _f64p), _p(cnt, _i32p)))
+        return [(xy[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(n)]
+
+    def batch_detect_fast(self, slot, cells, max_per_cell, threshold=10, nonmax=True):
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
+        n = cells.shape[0]
+        cap = max(max_per_cell, 1)
+        xy = np.zeros((n, cap, 2), np.int32)
+        rs = np.zeros((n, cap), np.float32)
+        cnt = np.zeros(n, np.int32)
+        self._ckt(self.lib.pmv_batch_detect_fast(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), int(threshold), 1 if nonmax else 0, _p(xy, _i32p),
+                                                _p(rs, _f32p), _p(cnt, _i32p)))
+        return [(xy[i, : cnt[i]].copy(), rs[i, : cnt[i]].copy()) for i in range(n)]
+
+    def batch_knn_match(self, src_slot, cmp_slot, src_xy, cmp_xy, neighbours=7, window=15):
+        s = np.ascontiguousarray(src_xy, np.int32).reshape(-1, 2)
+        c = np.ascontiguousarray(cmp_xy, np.int32).reshape(-1, 2)
+        best = np.zeros(max(len(s), 1), np.int32)
+        err = np.zeros(max(len(s), 1), np.float32)
+        self._ckt(self.lib.pmv_batch_knn_match(self.h, int(src_slot), int(cmp_slot), _p(s, _i32p), len(s), _p(c, _i32p), len(c), int(neighbours), int(window),
+                                              _p(best, _i32p), _p(err, _f32p)))
+        return best[: len(s)].copy(), err[: len(s)].copy()
+
+    def batch_lk_track(self, prev_slot, next_slot, prev_xy):
+        p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        n = p.shape[0]
+        out = np.zeros((n, 2), np.float32)
+        st = np.zeros(n, np.uint8)
+        err = np.zeros(n, np.float32)
+        self._ckt(self.lib.pmv_batch_lk_track(self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p), _p(err, _f32p)))
+        return out, st, err
+
+    def batch_pnp_ransac(self, seq, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):
+        o = np.ascontiguousarray(obj_xyz, np.float32).reshape(-1, 3)
+        i2 = np.ascontiguousarray(img_xy, np.float32).reshape(-1, 2)
+        m = o.shape[0]
+        Kd = np.ascontiguousarray(K, np.float64).reshape(9)
+        rv = np.array(rvec, np.float64).reshape(3).copy()
+        tv = np.array(tvec, np.float64).reshape(3).copy()
+        inl = np.zeros(max(m, 1), np.int32)
+        nin = C.c_int()
+        self._ckt(self.lib.pmv_batch_pnp_ransac(self.h, int(seq), _p(o, _f32p), _p(i2, _f32p), m, _p(Kd, _f64p), _p(rv, _f64p), _p(tv, _f64p), int(iterations),
+                                               C.c_float(reproj_err), C.c_double(confidence), _p(inl, _i32p), C.byref(nin)))
+        return rv, tv, inl[: nin.value].copy()
+
+    def batch_ba_solve(self, seq, cams, pts, obs_xy, cam_idx, pt_idx, K, huber=1.0, max_iterations=5):
+        cams = np.array(cams, np.float64).reshape(-1, 6).copy()
+        pts = np.array(pts, np.float64).reshape(-1, 3).copy()
+        obs = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+        ci = np.ascontiguousarray(cam_idx, np.int32)
+        pi = np.ascontiguousarray(pt_idx, np.int32)
+        Kd = np.ascontiguousarray(K, np.float64).reshape(9)
+        s = BaSummary()
+        self._ckt(self.lib.pmv_batch_ba_solve(self.h, int(seq), _p(cams, _f64p), cams.shape[0], _p(pts, _f64p), pts.shape[0], _p(obs, _f64p), _p(ci, _i32p),
+                                             _p(pi, _i32p), obs.shape[0], _p(Kd, _f64p), C.c_double(huber), int(max_iterations), C.byref(s)))
+        return cams, pts, s
+
+    def batch_triangulate_candidates(self, seq, q1, q2, P1x4, mask_in):
+        q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
+        q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
+        n = q1.shape[0]
+        P = np.ascontiguousarray(P1x4, np.float64).reshape(48)
+        mi = np.ascontiguousarray(mask_in, np.uint8).reshape(n)
+        Q = np.zeros((4, 4, n), np.float64)
+        mask = np.zeros((4, n), np.uint8)
+        good = np.zeros(4, np.int32)
+        self._ckt(self.lib.pmv_batch_triangulate_candidates(self.h, int(seq), _p(q1, _f64p), _p(q2, _f64p), n, _p(P, _f64p), _p(mi, _u8p), _p(Q, _f64p),
+                                                           _p(mask, _u8p), _p(good, _i32p)))
+        return Q, mask, good
+
+    def batch_fivepoint_hypotheses(self, seq, q1, q2, samples, thr):
+        q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
+        q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
+        s = np.ascontiguousarray(samples, np.int32).reshape(-1, 5)
+        nh = s.shape[0]
+        models = np.zeros((nh, 10, 9), np.float64)
+        nm = np.zeros(nh, np.int32)
+        counts = np.zeros((nh, 10), np.int32)
+        self._ckt(self.lib.pmv_batch_fivepoint_hypotheses(self.h, int(seq), _p(q1, _f64p), _p(q2, _f64p), q1.shape[0], _p(s, _i32p), nh, C.c_float(thr),
+                                                         _p(models, _f64p), _p(nm, _i32p), _p(counts, _i32p)))
+        return models, nm, counts

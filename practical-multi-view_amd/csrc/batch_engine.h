@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/pmv_hip.h"
 struct pmv_ctx;
 namespace pmv {
 struct BatchEngine;
@@ -28,7 +29,7 @@ int engine_knn(BatchEngine* E, int src_slot, int cmp_slot, const int* src_xy, in
 int engine_pnp(BatchEngine* E, int seq, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,
                float reproj_err, double confidence, int* out_inliers, int* out_n_inliers);
 int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
-              const double* K, double huber, int max_iterations);
+              const double* K, double huber, int max_iterations, pmv_ba_summary* summary = nullptr);
 int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                uint8_t* out_mask, int* out_good);
 int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,

@@ -607,6 +607,23 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
                 lk.lock();
             }
             batch.swap(Q->pending);
+            if (role == R_LK) {
+                // The result blocks of a lane hold cap_tracks = B * max_tracks tracks. The B sequences of a batched run never ask for more; the
+                // callers of a batch session may (any number of threads): a round takes the requests that fit, in arrival order, and the rest
+                // stay at the head of the queue for the next round (one request is at most max_tracks, so a round is never empty).
+                size_t total = 0, k = 0;
+                for (; k < batch.size(); k++) {
+                    const size_t n = batch[k]->kind == 4 ? (size_t)((KnnReq*)batch[k])->n : (size_t)((LKReq*)batch[k])->n;
+                    if (total + n > E->cap_tracks) break;
+                    total += n;
+                }
+                if (k < batch.size()) {
+                    Q->pending.assign(batch.begin() + (long)k, batch.end());
+                    batch.resize(k);
+                    Q->first_arrival = std::chrono::steady_clock::now();
+                    Q->cv_new.notify_all();   // (another lane of the class may take them at once)
+                }
+            }
         }
         const auto tw = std::chrono::steady_clock::now();
         C->t_idle += std::chrono::duration<double>(tw - ti).count();
@@ -875,11 +892,14 @@ int engine_pnp(BatchEngine* E, int seq, const float* obj_xyz, const float* img_x
 }
 
 int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
-              const double* K, double huber, int max_iterations) {
+              const double* K, double huber, int max_iterations, pmv_ba_summary* summary) {
     pmv_ctx* ctx = E->ctx;
     int rc = ba_check(ctx, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations);
     if (rc) return rc;
-    if (max_iterations == 0) return PMV_OK;
+    if (max_iterations == 0) {   // as pmv_ba_solve: the parameters stay untouched
+        if (summary) { summary->initial_cost = summary->final_cost = 0.0; summary->iterations = 0; summary->successful_steps = 0; summary->termination = 0; }
+        return PMV_OK;
+    }
     BAReq r;
     r.kind = 11; r.b = E->slots[seq]; r.max_iterations = max_iterations;
     rc = ba_prepare(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, ctx->ba_mode != 1, &r.A, &r.io_bytes);
@@ -887,7 +907,7 @@ int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np
     if (ctx->ba_mode == 1) r.A.out = (double*)r.b->d_h_stage;   // k_ba_lm_batch copies [summary | cams | pts] into the request's pinned block
     rc = submit(ctx, E->queue[R_BA], &r);
     if (rc) return rc;
-    ba_finish(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, nullptr);
+    ba_finish(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, summary);
     return PMV_OK;
 }
 

@@ -1,0 +1,479 @@
+// Batch sessions (include/pmv_hip.h, pmv_batch_*): the batch engine for callers who keep their own orchestrator - the reference's real
+// OdometryPipeline behind the INTEGRATION.md adapters, a live camera loop, a Python experiment. Their frames arrive one at a time and the
+// length of a sequence is not known in advance, so nothing here is declared up front except the frame sizes (the geometry table).
+//
+//   * The nine plugin calls are the engine's request entry points (batch_engine.h) behind the argument checks of the single-sequence call of
+//     the same name: the combiners merge whatever requests have accumulated into one launch per kernel class, exactly as for the sequences
+//     of pmv_pipeline_run_batch.
+//   * Uploads are one more kernel class: the UPLOAD thread (one thread, one HIP stream, one completion word) takes whatever upload requests
+//     accumulated while its previous round ran and issues the round as at most one gray and one BGR level-0 launch (pitched list forms,
+//     frontend.hip) and one k_pyrdown_list launch per level, whatever the number of requests and the mix of sizes; then it stores
+//     slot_layout / slot_state of the round's slots and wakes exactly the callers it served. A request returns only after its round's
+//     completion word was seen, so the slot may be read by any session call from any thread without further ordering - the argument the
+//     feeder's release rule uses (ingest_batch.hip).
+//   * Sources. Pinned memory mapped at its host address and device memory of the context's device are read in place by the kernel, with the
+//     caller's row stride as the entry's pitch. Anything else is copied by the CALLING thread, row by row and tight, into a block of the
+//     session's pinned staging pool; the kernel reads it from there. The callers' threads launch nothing and wait for no stream: their one
+//     runtime call is the address-range lookup that classifies the source (hipPointerGetAttributes, as batch_ingest_begin does).
+#include "pmv_ctx.h"
+#include "backend.h"
+#include "batch_engine.h"
+#include "ingest_batch.h"
+#include <linux/futex.h>
+#include <sys/prctl.h>
+#include <sys/syscall.h>
+#include <unistd.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <memory>
+#include <thread>
+
+namespace pmv {
+
+namespace {
+
+struct UpReq {
+    int slot = 0, geom = 0, format = 0;
+    const uint8_t* dsrc = nullptr;   // the address the kernel reads: the caller's own buffer (in place) or a staging block
+    unsigned pitch = 0;
+    bool in_place = false;           // dsrc is the caller's own buffer
+    int rc = PMV_OK;
+    char err[200] = "";
+    std::atomic<int> done{0};        // completion word of the request: the owner sleeps on it (futex), as in batch_engine.hip
+};
+
+__global__ void k_upload_signal(unsigned* done, unsigned seq) { __threadfence_system(); __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+
+inline void futex_wait_while(std::atomic<int>* w, int v) {
+    while (w->load(std::memory_order_acquire) == v) (void)syscall(SYS_futex, (int*)w, FUTEX_WAIT_PRIVATE, v, nullptr, nullptr, 0);
+}
+inline void futex_wake_one(std::atomic<int>* w) { (void)syscall(SYS_futex, (int*)w, FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0); }
+
+}  // namespace
+
+struct BatchSession {
+    static constexpr int ROUND = 1024;     // upload requests per round at most (the rest wait for the next one)
+    pmv_ctx* ctx = nullptr;
+    BatchEngine* eng = nullptr;
+    int n_seq = 0;
+    std::unique_ptr<std::mutex[]> seq_mu;  // one outstanding back-end call per seq: the four calls share the seq's pinned block
+    // the upload class
+    std::thread th;
+    hipStream_t stream = nullptr;
+    unsigned* h_done = nullptr; unsigned* dm_done = nullptr; unsigned done_seq = 0;   // completion word of a round (mapped pinned)
+    double ema_wait_us = 0;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<UpReq*> pending;
+    bool stop = false;
+    // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND]
+    char* h_tab = nullptr; char* dm_tab = nullptr;
+    // staging pool: n_blk blocks of blk_bytes (the largest BGR frame of the declared sizes), pinned + mapped
+    uint8_t* h_pool = nullptr; uint8_t* dm_pool = nullptr;
+    size_t blk_bytes = 0;
+    std::mutex pool_mu;
+    std::condition_variable pool_cv;
+    std::vector<int> free_blk;
+    std::atomic<long long> rounds{0}, frames{0}, l0_launches{0}, pyr_launches{0};   // launches: counted where they are made
+    // diagnostic (pmv_batch_upload_rounds): what each round held and launched, the first ROUND_LOG rounds of the session
+    static constexpr size_t ROUND_LOG = 1 << 16;
+    struct RoundRec { int by_levels[MAX_LEVELS]; int l0_launches, pyr_launches, in_place; };   // by_levels[i]: frames whose pyramid has i + 1 levels
+    std::mutex log_mu;
+    std::vector<RoundRec> log;
+};
+
+namespace {
+
+void fail_round(std::vector<UpReq*>& batch, const char* what, hipError_t e) {
+    for (UpReq* r : batch) { r->rc = PMV_ERR_HIP; snprintf(r->err, sizeof(r->err), "pmv_batch_frame_upload: %s: %s", what, hipGetErrorString(e)); }
+}
+
+// the completion word of wait_stream (batch_engine.hip): sleep through most of the expected duration, then look every ~10 us
+hipError_t wait_round(BatchSession* S) {
+    const unsigned seq = ++S->done_seq;
+    hipLaunchKernelGGL(k_upload_signal, dim3(1), dim3(1), 0, S->stream, S->dm_done, seq);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto done = [&] { return __atomic_load_n(S->h_done, __ATOMIC_ACQUIRE) == seq; };
+    if (!done()) {
+        const double first = 0.7 * S->ema_wait_us;
+        if (first > 25) std::this_thread::sleep_for(std::chrono::nanoseconds((long)(first * 1e3)));
+        int looks = 0;
+        while (!done()) {
+            std::this_thread::sleep_for(std::chrono::microseconds(10));
+            if ((++looks & 255) == 0) {   // a faulted launch never signals: ask the runtime now and then
+                e = hipStreamQuery(S->stream);
+                if (e != hipSuccess && e != hipErrorNotReady) return e;
+            }
+        }
+    }
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    S->ema_wait_us = S->ema_wait_us == 0 ? us : 0.8 * S->ema_wait_us + 0.2 * us;
+    e = hipStreamQuery(S->stream);   // lets the runtime retire the round's commands now
+    return e == hipErrorNotReady ? hipSuccess : e;
+}
+
+// one round: every request of `batch` (distinct slots, <= ROUND of them)
+void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
+    pmv_ctx* ctx = S->ctx;
+    PyrPitchEntry* tg = (PyrPitchEntry*)S->h_tab;
+    PyrPitchEntry* tc = tg + BatchSession::ROUND;
+    PyrListEntry* ta = (PyrListEntry*)(tc + BatchSession::ROUND);
+    const PyrPitchEntry* dg = (const PyrPitchEntry*)S->dm_tab;
+    const PyrPitchEntry* dc = dg + BatchSession::ROUND;
+    const PyrListEntry* da = (const PyrListEntry*)(dc + BatchSession::ROUND);
+    // grid and LDS of a launch from the largest geometry among ITS entries, level by level
+    PyrLayout Lg{}, Lc{}, La{};
+    auto widen = [](PyrLayout& M, const PyrLayout& L) {
+        M.n_levels = std::max(M.n_levels, L.n_levels);
+        for (int l = 0; l < L.n_levels; l++) { M.w[l] = std::max(M.w[l], L.w[l]); M.h[l] = std::max(M.h[l], L.h[l]); }
+    };
+    int ng = 0, nc = 0, na = 0;
+    for (UpReq* r : batch) {
+        const PyrLayout& L = ctx->geom[(size_t)r->geom];
+        PyrPitchEntry& e = r->format == PMV_FRAMES_BGR ? tc[nc++] : tg[ng++];
+        e.src = r->dsrc; e.pitch = r->pitch; e.slot = r->slot; e.geom = r->geom; e.reserved = 0;
+        widen(r->format == PMV_FRAMES_BGR ? Lc : Lg, L);
+        widen(La, L);
+        ta[na].src = nullptr; ta[na].slot = r->slot; ta[na].geom = r->geom;
+        na++;
+    }
+    // A round that fails after its first launch must not hand the sources back while a kernel still reads them: wait for the stream first.
+    auto fail = [&](const char* what, hipError_t err) { (void)hipStreamSynchronize(S->stream); fail_round(batch, what, err); };
+    BatchSession::RoundRec rec{};
+    hipError_t e = hipSuccess;
+    if (ng) {
+        if ((e = launch_pad_level0_pitched(S->stream, ctx->d_slots, ctx->d_geom, Lg, dg, ng)) != hipSuccess) { fail("k_pad_level0_pitched", e); return; }
+        rec.l0_launches++;
+    }
+    if (nc) {
+        if ((e = launch_pad_level0_bgr_pitched(S->stream, ctx->d_slots, ctx->d_geom, Lc, dc, nc)) != hipSuccess) { fail("k_pad_level0_bgr_pitched", e); return; }
+        rec.l0_launches++;
+    }
+    for (int l = 1; l < La.n_levels; l++) {
+        if ((e = launch_pyrdown_list(S->stream, ctx->d_slots, ctx->d_geom, La, l, da, na)) != hipSuccess) { fail("k_pyrdown", e); return; }
+        rec.pyr_launches++;
+    }
+    if ((e = wait_round(S)) != hipSuccess) { fail("waiting for the round", e); return; }
+    for (UpReq* r : batch) {
+        ctx->slot_layout[(size_t)r->slot] = ctx->geom[(size_t)r->geom];
+        ctx->slot_state[(size_t)r->slot] = SLOT_BUILT;
+        rec.by_levels[ctx->geom[(size_t)r->geom].n_levels - 1]++;
+        rec.in_place += r->in_place ? 1 : 0;
+    }
+    S->rounds++; S->frames += na; S->l0_launches += rec.l0_launches; S->pyr_launches += rec.pyr_launches;
+    std::lock_guard<std::mutex> lk(S->log_mu);
+    if (S->log.size() < BatchSession::ROUND_LOG) S->log.push_back(rec);
+}
+
+void upload_loop(BatchSession* S) {
+    (void)hipSetDevice(S->ctx->device);
+    tl_prof = &S->ctx->prof;
+    (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);   // 1 us: the timed sleeps of wait_round
+    std::vector<UpReq*> carry;   // requests put off by a round: a second upload into a slot of the round, or more than ROUND requests
+    for (;;) {
+        std::vector<UpReq*> got;
+        {
+            std::unique_lock<std::mutex> lk(S->mu);
+            if (carry.empty()) S->cv.wait(lk, [&] { return !S->pending.empty() || S->stop; });
+            if (S->pending.empty() && carry.empty() && S->stop) return;
+            got.swap(S->pending);
+        }
+        std::vector<UpReq*> batch, later;
+        carry.insert(carry.end(), got.begin(), got.end());
+        for (UpReq* r : carry) {
+            bool dup = (int)batch.size() >= BatchSession::ROUND;
+            for (size_t i = 0; i < batch.size() && !dup; i++) dup = batch[i]->slot == r->slot;
+            (dup ? later : batch).push_back(r);
+        }
+        carry.swap(later);
+        upload_round(S, batch);
+        for (UpReq* r : batch) {
+            std::atomic<int>* w = &r->done;   // (after the store the owner may return and the request, which lives on its stack, is gone)
+            w->store(1, std::memory_order_release);
+            futex_wake_one(w);
+        }
+    }
+}
+
+void session_free(BatchSession* S) {
+    if (!S) return;
+    { std::lock_guard<std::mutex> lk(S->mu); S->stop = true; }
+    S->cv.notify_all();
+    if (S->th.joinable()) S->th.join();
+    if (S->stream) { (void)hipStreamSynchronize(S->stream); (void)hipStreamDestroy(S->stream); }
+    if (S->h_done) (void)hipHostFree(S->h_done);
+    if (S->h_tab) (void)hipHostFree(S->h_tab);
+    if (S->h_pool) (void)hipHostFree(S->h_pool);
+    delete S;
+}
+
+}  // namespace
+
+void batch_session_destroy(pmv_ctx* ctx) {
+    session_free(ctx->session);
+    ctx->session = nullptr;
+    ctx->session_state.store(0);
+}
+
+}  // namespace pmv
+
+using namespace pmv;
+
+#define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
+#define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
+
+namespace {
+
+// A session call in flight: counted so that pmv_batch_close can refuse while one is outstanding. Either the call sees the session closing
+// (and fails) or pmv_batch_close sees the call (and fails): both sides use sequentially consistent atomics.
+struct InCall {
+    pmv_ctx* ctx; bool ok;
+    InCall(pmv_ctx* c, const char* who) : ctx(c), ok(false) {
+        if (!ctx) { set_err(nullptr, "%s: null ctx", who); return; }
+        ctx->session_calls.fetch_add(1);
+        int st;
+        while ((st = ctx->session_state.load()) == 2) std::this_thread::yield();   // a pmv_batch_close is deciding: it sees this call, or it wins
+        ok = st == 1;
+        if (!ok) { ctx->session_calls.fetch_sub(1); set_err(ctx, "%s: no batch session is open on this context (pmv_batch_open first)", who); }
+    }
+    ~InCall() { if (ok) ctx->session_calls.fetch_sub(1); }
+};
+#define SESSION(who) InCall in_(ctx, who); if (!in_.ok) return PMV_ERR_INVALID; BatchSession* S = ctx->session; (void)S
+
+int seq_check(pmv_ctx* ctx, BatchSession* S, const char* who, int seq) {
+    REQ(seq >= 0 && seq < S->n_seq, PMV_ERR_INVALID, "%s: seq %d outside 0..%d (n_seq of pmv_batch_open)", who, seq, S->n_seq - 1);
+    return PMV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes) {
+    REQ(ctx && sizes_wh, PMV_ERR_INVALID, "pmv_batch_open: null argument");
+    REQ(n_seq >= 1 && n_seq <= 256, PMV_ERR_INVALID, "pmv_batch_open: n_seq = %d (1..256)", n_seq);
+    REQ(n_sizes >= 1 && n_sizes <= pmv_ctx::MAX_GEOM, PMV_ERR_INVALID, "pmv_batch_open: n_sizes = %d (1..%d)", n_sizes, pmv_ctx::MAX_GEOM);
+    std::vector<int> ws((size_t)n_sizes), hs((size_t)n_sizes);
+    size_t max_fb = 0;
+    for (int i = 0; i < n_sizes; i++) {
+        const int w = sizes_wh[2 * i], h = sizes_wh[2 * i + 1];
+        REQ(w >= 40 && h >= 40 && w <= ctx->max_w && h <= ctx->max_h, PMV_ERR_CAPACITY, "pmv_batch_open: size %d: frame %dx%d outside capacity %dx%d", i, w, h, ctx->max_w, ctx->max_h);
+        for (int j = 0; j < i; j++) REQ(ws[(size_t)j] != w || hs[(size_t)j] != h, PMV_ERR_INVALID, "pmv_batch_open: size %dx%d is named twice (entries %d and %d)", w, h, j, i);
+        ws[(size_t)i] = w; hs[(size_t)i] = h;
+        max_fb = std::max(max_fb, (size_t)3 * w * h);
+    }
+    // the engine and the geometry table have one owner at a time: a session, or a batched run
+    std::lock_guard<std::mutex> own(ctx->owner_mu);
+    REQ(ctx->session_state.load() == 0, PMV_ERR_INVALID, "pmv_batch_open: a batch session is already open on this context (pmv_batch_close first)");
+    REQ(ctx->batch_open.load() == 0 && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_batch_open: a batched run (pmv_pipeline_run_batch / _streamed) is open on this context");
+    CKC(hipSetDevice(ctx->device));
+    BatchEngine* eng = nullptr;
+    int rc = batch_engine_get(ctx, n_seq, &eng);
+    if (rc != PMV_OK) return rc;
+    if ((rc = pmv_sync(ctx)) != PMV_OK) return rc;
+    if ((rc = geom_table_set(ctx, ws.data(), hs.data(), n_sizes)) != PMV_OK) return rc;
+    BatchSession* S = new BatchSession();
+    S->ctx = ctx; S->eng = eng; S->n_seq = n_seq;
+    S->seq_mu.reset(new std::mutex[(size_t)n_seq]);
+    hipError_t e = hipSuccess;
+    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + sizeof(PyrListEntry));
+    S->blk_bytes = (max_fb + 255) & ~(size_t)255;
+    // two blocks per sequence (frames k - 1 and k on their way), within 4 .. 64 blocks and 256 MB; an uploader without a block waits for one
+    const int n_blk = (int)std::max<size_t>(2, std::min<size_t>({(size_t)64, std::max<size_t>(4, 2 * (size_t)n_seq), ((size_t)256 << 20) / S->blk_bytes}));
+    if ((e = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)) == hipSuccess &&
+        (e = hipHostMalloc(&S->h_done, 64, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess &&
+        (e = hipHostGetDevicePointer((void**)&S->dm_done, S->h_done, 0)) == hipSuccess &&
+        (e = hipHostMalloc(&S->h_tab, tab_bytes, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess &&
+        (e = hipHostGetDevicePointer((void**)&S->dm_tab, S->h_tab, 0)) == hipSuccess &&
+        (e = hipHostMalloc(&S->h_pool, (size_t)n_blk * S->blk_bytes, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess)
+        e = hipHostGetDevicePointer((void**)&S->dm_pool, S->h_pool, 0);
+    if (e != hipSuccess) { set_err(ctx, "pmv_batch_open: %s", hipGetErrorString(e)); session_free(S); return PMV_ERR_HIP; }
+    *S->h_done = 0;
+    for (int i = n_blk - 1; i >= 0; i--) S->free_blk.push_back(i);
+    S->th = std::thread(upload_loop, S);
+    ctx->session = S;
+    ctx->session_state.store(1);
+    return PMV_OK;
+}
+
+int pmv_batch_close(pmv_ctx* ctx) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_batch_close: null ctx");
+    std::lock_guard<std::mutex> own(ctx->owner_mu);
+    REQ(ctx->session_state.load() == 1, PMV_ERR_INVALID, "pmv_batch_close: no batch session is open on this context");
+    ctx->session_state.store(2);   // closing: new session calls are refused from here on
+    const int n = ctx->session_calls.load();
+    if (n != 0) {
+        ctx->session_state.store(1);
+        set_err(ctx, "pmv_batch_close: %d session call%s still outstanding", n, n == 1 ? " is" : "s are");
+        return PMV_ERR_INVALID;
+    }
+    (void)hipSetDevice(ctx->device);
+    batch_session_destroy(ctx);
+    return PMV_OK;
+}
+
+int pmv_batch_upload_stats(pmv_ctx* ctx, long long* out4) {
+    SESSION("pmv_batch_upload_stats");
+    REQ(out4, PMV_ERR_INVALID, "pmv_batch_upload_stats: null argument");
+    out4[0] = S->rounds.load(); out4[1] = S->frames.load(); out4[2] = S->l0_launches.load(); out4[3] = S->pyr_launches.load();
+    return PMV_OK;
+}
+
+int pmv_batch_upload_rounds(pmv_ctx* ctx, int* out8, int capacity) {
+    SESSION("pmv_batch_upload_rounds");
+    REQ(capacity >= 0 && (out8 || capacity == 0), PMV_ERR_INVALID, "pmv_batch_upload_rounds: null argument");
+    std::lock_guard<std::mutex> lk(S->log_mu);
+    static_assert(sizeof(BatchSession::RoundRec) == 8 * sizeof(int) && MAX_LEVELS == 5, "a round's record is the 8 ints the header names");
+    const size_t n = std::min(S->log.size(), (size_t)capacity);
+    if (n) memcpy(out8, S->log.data(), n * sizeof(BatchSession::RoundRec));
+    return (int)S->log.size();
+}
+
+int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format) {
+    SESSION("pmv_batch_frame_upload");
+    REQ(pixels, PMV_ERR_INVALID, "pmv_batch_frame_upload: null argument");
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_batch_frame_upload: slot %d out of range", slot);
+    REQ(format == PMV_FRAMES_GRAY || format == PMV_FRAMES_BGR, PMV_ERR_INVALID, "pmv_batch_frame_upload: unknown format %d (PMV_FRAMES_GRAY = 0, PMV_FRAMES_BGR = 1)", format);
+    UpReq r;
+    r.slot = slot; r.format = format;
+    r.geom = ctx->geom_index(w, h);
+    REQ(r.geom >= 0, PMV_ERR_INVALID, "pmv_batch_frame_upload: a %dx%d frame: that size was not declared at pmv_batch_open", w, h);
+    const size_t row = (size_t)w * (format == PMV_FRAMES_BGR ? 3 : 1);
+    REQ(stride >= 0 && (size_t)stride >= row, PMV_ERR_CAPACITY, "pmv_batch_frame_upload: stride %d below the %zu bytes of a %s row of %d pixels", stride, row,
+        format == PMV_FRAMES_BGR ? "BGR" : "gray", w);
+    // A kernel is never handed a pageable address. Device memory of this device and pinned memory mapped at its host address are read in place;
+    // anything else - pageable, registered under another device address, managed - goes through the staging pool.
+    bool in_place = false;
+    {
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, pixels);
+        (void)hipGetLastError();   // (a malloc'ed pointer may make the lookup fail: that is the "pageable" answer)
+        if (e == hipSuccess && attr.type == hipMemoryTypeDevice) {
+            REQ(attr.device == ctx->device, PMV_ERR_INVALID, "pmv_batch_frame_upload: the frame is in memory of device %d, the context is on device %d", attr.device, ctx->device);
+            void* base = nullptr; size_t size = 0;   // the whole frame lies inside its allocation
+            if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)pixels) == hipSuccess)
+                REQ((const uint8_t*)pixels + (size_t)(h - 1) * (size_t)stride + row <= (const uint8_t*)base + size, PMV_ERR_INVALID,
+                    "pmv_batch_frame_upload: a %dx%d frame with stride %d reaches past the end of its device allocation", w, h, stride);
+            (void)hipGetLastError();
+            in_place = true;
+        } else if (e == hipSuccess && attr.type == hipMemoryTypeHost && attr.hostPointer == (const void*)pixels && attr.devicePointer == attr.hostPointer)
+            in_place = true;
+    }
+    int blk = -1;
+    r.in_place = in_place;
+    if (in_place) { r.dsrc = pixels; r.pitch = (unsigned)stride; }
+    else {
+        {
+            std::unique_lock<std::mutex> lk(S->pool_mu);
+            S->pool_cv.wait(lk, [&] { return !S->free_blk.empty(); });
+            blk = S->free_blk.back();
+            S->free_blk.pop_back();
+        }
+        uint8_t* dst = S->h_pool + (size_t)blk * S->blk_bytes;   // (row * h <= blk_bytes: the size is a declared one)
+        if ((size_t)stride == row) memcpy(dst, pixels, row * (size_t)h);
+        else for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * row, pixels + (size_t)y * (size_t)stride, row);
+        r.dsrc = S->dm_pool + (size_t)blk * S->blk_bytes;
+        r.pitch = (unsigned)row;
+    }
+    {
+        std::lock_guard<std::mutex> lk(S->mu);
+        S->pending.push_back(&r);
+    }
+    S->cv.notify_one();
+    futex_wait_while(&r.done, 0);
+    if (blk >= 0) {
+        { std::lock_guard<std::mutex> lk(S->pool_mu); S->free_blk.push_back(blk); }
+        S->pool_cv.notify_one();
+    }
+    if (r.rc != PMV_OK) set_err(ctx, "%s", r.err);
+    return r.rc;
+}
+
+// ---- front-end calls: the checks of the single call, then a request of the class's combiner ------------------------------------------
+int pmv_batch_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* out_status, float* out_err) {
+    SESSION("pmv_batch_lk_track");
+    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err)) return rc_;
+    if (n == 0) return PMV_OK;
+    return engine_lk(S->eng, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err);
+}
+
+int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
+                        int* out_best, float* out_err) {
+    SESSION("pmv_batch_knn_match");
+    if (const int rc_ = knn_check(ctx, false, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err)) return rc_;
+    if (n == 0) return PMV_OK;
+    return engine_knn(S->eng, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err);
+}
+
+int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy, int* out_count) {
+    SESSION("pmv_batch_detect_gftt");
+    const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell);
+    if (rc) return rc;
+    REQ(out_xy && out_count, PMV_ERR_INVALID, "pmv_detect_gftt: null output");
+    return engine_detect(S->eng, 1, slot, cells, n_cells, max_per_cell, quality, min_dist, out_xy, nullptr, out_count);
+}
+
+int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
+                               int* out_count) {
+    SESSION("pmv_batch_detect_shitomasi");
+    if (max_per_cell <= 0) {   // ShiTomasiFeatureExtractor.cpp:37-44: nothing
+        REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
+        for (int i = 0; i < n_cells; i++) out_count[i] = 0;
+        return PMV_OK;
+    }
+    const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell);
+    if (rc) return rc;
+    REQ(out_xy && out_score && out_count, PMV_ERR_INVALID, "pmv_detect_shitomasi: null output");
+    return engine_detect(S->eng, 2, slot, cells, n_cells, max_per_cell, quality, 0.0, out_xy, out_score, out_count);
+}
+
+int pmv_batch_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
+                          int* out_count) {
+    SESSION("pmv_batch_detect_fast");
+    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
+    if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
+    if (const int rc = fast_check(ctx, false, slot, cells, n_cells, max_per_cell, out_xy, out_response)) return rc;
+    return engine_detect_fast(S->eng, slot, cells, n_cells, max_per_cell, threshold, nonmax, out_xy, out_response, out_count);
+}
+
+// ---- back-end calls: seq selects the workspace set; its four calls share one pinned block, so they take turns ---------------------------
+int pmv_batch_pnp_ransac(pmv_ctx* ctx, int seq, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,
+                         float reproj_err, double confidence, int* out_inliers, int* out_n_inliers) {
+    SESSION("pmv_batch_pnp_ransac");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_pnp_ransac", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_pnp(S->eng, seq, obj_xyz, img_xy, m, K, rvec, tvec, iterations, reproj_err, confidence, out_inliers, out_n_inliers);
+}
+
+int pmv_batch_ba_solve(pmv_ctx* ctx, int seq, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
+                       const double* K, double huber_delta, int max_iterations, pmv_ba_summary* summary) {
+    SESSION("pmv_batch_ba_solve");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_ba_solve", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_ba(S->eng, seq, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber_delta, max_iterations, summary);
+}
+
+int pmv_batch_triangulate_candidates(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
+                                     uint8_t* out_mask, int* out_good) {
+    SESSION("pmv_batch_triangulate_candidates");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_triangulate_candidates", seq)) return rc;
+    REQ(q1 && q2 && P1x4 && mask_in && out_Q && out_mask && out_good, PMV_ERR_INVALID, "pmv_triangulate_candidates: null argument");
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_dlt(S->eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+}
+
+int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
+                                   int* n_models, int* counts) {
+    SESSION("pmv_batch_fivepoint_hypotheses");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_fivepoint_hypotheses", seq)) return rc;
+    REQ(models && n_models && counts, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_fivepoint(S->eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts);
+}
+
+}  // extern "C"

@@ -57,6 +57,7 @@ PyrLayout pmv::make_layout(int w, int h) {
 extern "C" {
 
 const char* pmv_last_error(pmv_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
+const char* pmv_thread_error(void) { return tl_err; }
 
 int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots, int max_tracks, int max_ba_cams,
                    int max_ba_points, int max_ba_obs) {
@@ -140,6 +141,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
 void pmv_ctx_destroy(pmv_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
+    batch_session_destroy(c);
     batch_engine_destroy(c);
     batch_ingest_destroy(c->ingest);
     batch_ingest_destroy(c->bingest);
@@ -331,13 +333,9 @@ int pmv_frame_get_level_padded(pmv_ctx* ctx, int slot, int level, uint8_t* out, 
 
 int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy,
                  uint8_t* out_status, float* out_err) {
-    REQ(ctx && (n == 0 || (prev_xy && out_xy && out_status && out_err)), PMV_ERR_INVALID, "pmv_lk_track: null argument");
-    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
-    REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
-    for (int s : {prev_slot, next_slot}) { int rc_ = slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front); if (rc_) return rc_; }
+    REQ(ctx, PMV_ERR_INVALID, "pmv_lk_track: null argument");
+    if (const int rc_ = lk_check(ctx, true, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err)) return rc_;
     const PyrLayout& L = ctx->slot_layout[prev_slot];
-    const PyrLayout& L2 = ctx->slot_layout[next_slot];
-    REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_lk_track: frame sizes differ");
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
@@ -380,12 +378,23 @@ static void pack_cells(int* dst, const int* cells, int n_cells, int slot) {   //
         d[0] = cells[4 * i]; d[1] = cells[4 * i + 1]; d[2] = cells[4 * i + 2]; d[3] = cells[4 * i + 3]; d[4] = slot; d[5] = d[6] = d[7] = 0;
     }
 }
-static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell) {   // max_per_cell: already >= 1
-    REQ(ctx && cells, PMV_ERR_INVALID, "detect: null argument");
+}  // extern "C"
+int pmv::lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* out_xy, const uint8_t* out_status, const float* out_err) {
+    REQ(n == 0 || (prev_xy && out_xy && out_status && out_err), PMV_ERR_INVALID, "pmv_lk_track: null argument");
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
+    REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
+    for (int s : {prev_slot, next_slot}) { int rc_ = bracket ? slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, s); if (rc_) return rc_; }
+    const PyrLayout& L = ctx->slot_layout[prev_slot];
+    const PyrLayout& L2 = ctx->slot_layout[next_slot];
+    REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_lk_track: frame sizes differ");
+    return PMV_OK;
+}
+int pmv::detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell) {
+    REQ(cells, PMV_ERR_INVALID, "detect: null argument");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "detect: slot out of range");
     REQ(n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_CAPACITY, "detect: n_cells=%d (max %d)", n_cells, MAX_CELLS);
     REQ(max_per_cell >= 1 && max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect: max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
-    int rc = slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front);
+    int rc = bracket ? slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, slot);
     if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
     for (int i = 0; i < n_cells; i++) {
@@ -395,6 +404,11 @@ static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
     }
     return PMV_OK;
 }
+static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell) {   // max_per_cell: already >= 1
+    REQ(ctx, PMV_ERR_INVALID, "detect: null argument");
+    return detect_check(ctx, true, slot, cells, n_cells, max_per_cell);
+}
+extern "C" {
 
 int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                     double min_dist, int* out_xy, int* out_count) {

@@ -86,8 +86,10 @@ __host__ __device__ inline int pad0_row_lds(int w) { return ((w + 3 + 24 + 3) / 
 // the end of a host page is never over-read.
 // (LRef: const PyrLayout& = the launch's own geometry, GeomEntry& = the frame's entry of the geometry table; the grid of a list launch is
 // sized for the tallest frame of the round, so a workgroup below its own frame leaves before its first load or barrier)
+// `pitch`: bytes from one source row to the next (block-uniform; w for a tight frame). The fetch rule holds for any pitch and base: the lead
+// offset is kept per row, and the last row's last dword is the one that holds its last byte.
 template <class LRef>
-__device__ __forceinline__ void pad_level0_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame) {
+__device__ __forceinline__ void pad_level0_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame, size_t pitch) {
     extern __shared__ __attribute__((aligned(16))) uint8_t srow_all[];   // PAD0_R x row_lds bytes
     const int w = L.w[0], h = L.h[0], stride = L.stride[0];
     uint8_t* slot = slots + (size_t)s * L.slot_bytes;
@@ -103,7 +105,7 @@ __device__ __forceinline__ void pad_level0_rows(uint8_t* slots, LRef L, int s, c
         const uint32_t* src;
         int nd;
         if (frame) {
-            const uintptr_t a = (uintptr_t)(frame + (size_t)sy * (size_t)w);
+            const uintptr_t a = (uintptr_t)(frame + (size_t)sy * pitch);
             lead[r] = (unsigned)(a & 3u);
             src = (const uint32_t*)(a & ~(uintptr_t)3);
             nd = (int)((lead[r] + (unsigned)w + 3u) >> 2);
@@ -124,11 +126,19 @@ __device__ __forceinline__ void pad_level0_rows(uint8_t* slots, LRef L, int s, c
 }
 __global__ __launch_bounds__(PAD0_T) void k_pad_level0(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight) {
     // tight source frame z, or null: in place (block-uniform)
-    pad_level0_rows<const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * (size_t)L.w[0] * (size_t)L.h[0] : nullptr);
+    pad_level0_rows<const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * (size_t)L.w[0] * (size_t)L.h[0] : nullptr, (size_t)L.w[0]);
 }
 __global__ __launch_bounds__(PAD0_T) void k_pad_level0_list(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrListEntry* __restrict__ list) {
     const PyrListEntry e = list[blockIdx.z];
-    pad_level0_rows<GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src);
+    GeomEntry& L = geom_entry(geom, e.geom);
+    pad_level0_rows<GeomEntry&>(slots, L, __builtin_amdgcn_readfirstlane(e.slot), e.src, (size_t)L.w[0]);
+}
+// Pitched list form (the upload class of a batch session, batch_session.hip): the source is read IN PLACE - a camera buffer with aligned
+// rows, an ROI view into a larger image, a hipMallocPitch surface - so the entry carries the bytes from row to row. The entry is the same
+// for the whole workgroup: slot and pitch go through readfirstlane and stay in scalar registers.
+__global__ __launch_bounds__(PAD0_T) void k_pad_level0_pitched(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrPitchEntry* __restrict__ list) {
+    const PyrPitchEntry e = list[blockIdx.z];
+    pad_level0_rows<GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src, (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)e.pitch));
 }
 
 // level l-1 (padded) -> level l (padded): cv::pyrDown [1 4 6 4 1]^2, (sum+128)>>8. A workgroup produces PYR_R padded output rows: per
@@ -257,8 +267,8 @@ __host__ __device__ inline int pad0c_raw_lds(int w) { return ((3 + 3 * w + 3) / 
 __device__ inline uint32_t bgr_gray(uint32_t p) {   // p = B | G << 8 | R << 16 | (any byte) << 24
     return ((__builtin_amdgcn_udot4(p, BGR_W_HI, 0u, false) << 8) + __builtin_amdgcn_udot4(p, BGR_W_LO, 8192u, false)) >> 14;
 }
-template <int R, class LRef>   // (LRef as in k_pad_level0; `frame`: the tight BGR source frame, block-uniform)
-__device__ __forceinline__ void pad_level0_bgr_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame) {
+template <int R, class LRef>   // (LRef as in k_pad_level0; `frame`: the BGR source frame, `pitch` bytes from row to row (3 w: tight), both block-uniform)
+__device__ __forceinline__ void pad_level0_bgr_rows(uint8_t* slots, LRef L, int s, const uint8_t* __restrict__ frame, size_t pitch) {
     extern __shared__ __attribute__((aligned(16))) uint8_t crow_all[];   // R x raw_lds bytes of BGR, then R x row_lds bytes of gray
     const int w = L.w[0], h = L.h[0], stride = L.stride[0];
     if (!frame) return;
@@ -275,7 +285,7 @@ __device__ __forceinline__ void pad_level0_bgr_rows(uint8_t* slots, LRef L, int 
     for (int r = 0; r < R; r++) {
         const int py = py0 + r < ph ? py0 + r : ph - 1;     // (rows past the end repeat the last one; they are not stored)
         const int sy = reflect101(py - PAD, h);
-        const uintptr_t a = (uintptr_t)(frame + (size_t)sy * 3 * (size_t)w);
+        const uintptr_t a = (uintptr_t)(frame + (size_t)sy * pitch);
         lead[r] = (unsigned)(a & 3u);
         src[r] = (const uint32_t*)(a & ~(uintptr_t)3);
         nd[r] = (int)((lead[r] + 3u * (unsigned)w + 3u) >> 2);   // the aligned dwords that hold the row's bytes and no others
@@ -311,12 +321,19 @@ __device__ __forceinline__ void pad_level0_bgr_rows(uint8_t* slots, LRef L, int 
 }
 template <int R>
 __global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr(uint8_t* slots, PyrLayout L, int first_slot, const uint8_t* __restrict__ tight) {
-    pad_level0_bgr_rows<R, const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * 3 * (size_t)L.w[0] * (size_t)L.h[0] : nullptr);
+    pad_level0_bgr_rows<R, const PyrLayout&>(slots, L, first_slot + (int)blockIdx.z, tight ? tight + (size_t)blockIdx.z * 3 * (size_t)L.w[0] * (size_t)L.h[0] : nullptr, 3 * (size_t)L.w[0]);
 }
 template <int R>
 __global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr_list(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrListEntry* __restrict__ list) {
     const PyrListEntry e = list[blockIdx.z];
-    pad_level0_bgr_rows<R, GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src);
+    GeomEntry& L = geom_entry(geom, e.geom);
+    pad_level0_bgr_rows<R, GeomEntry&>(slots, L, __builtin_amdgcn_readfirstlane(e.slot), e.src, 3 * (size_t)L.w[0]);
+}
+// Pitched list form, as k_pad_level0_pitched: with a pitch that is no multiple of 4 the lead offset differs from row to row (lead[r] above).
+template <int R>
+__global__ __launch_bounds__(PAD0C_T) void k_pad_level0_bgr_pitched(uint8_t* slots, const PyrLayout* __restrict__ geom, const PyrPitchEntry* __restrict__ list) {
+    const PyrPitchEntry e = list[blockIdx.z];
+    pad_level0_bgr_rows<R, GeomEntry&>(slots, geom_entry(geom, e.geom), __builtin_amdgcn_readfirstlane(e.slot), e.src, (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)e.pitch));
 }
 
 hipError_t launch_pad_level0(hipStream_t s, uint8_t* slots, const PyrLayout& L, int first_slot, int n, const uint8_t* tight) {
@@ -367,6 +384,29 @@ hipError_t launch_pad_level0_bgr_list(hipStream_t s, uint8_t* slots, const PyrLa
         hipLaunchKernelGGL(k_pad_level0_bgr_list<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, d_geom, list);
     else if (row <= (64u << 10))   // frames wider than 4 k pixels: one row per workgroup
         hipLaunchKernelGGL(k_pad_level0_bgr_list<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, d_geom, list);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// Pitched list forms: as the two above, every entry with a source and its own row pitch (the caller checks pitch >= w, or 3 w, per entry)
+hipError_t launch_pad_level0_pitched(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrPitchEntry* list, int n) {
+    if (!slots || !d_geom || !list || n < 1 || n > 65535 || Lmax.n_levels < 1 || Lmax.w[0] < 1 || Lmax.h[0] < 1) return hipErrorInvalidValue;
+    dim3 grid(1, (Lmax.h[0] + 2 * PAD + PAD0_R - 1) / PAD0_R, n);
+    const size_t shm = (size_t)pad0_row_lds(Lmax.w[0]) * PAD0_R;
+    if (shm > (64u << 10)) return hipErrorInvalidValue;
+    ProfScope ps(K_PAD0, s);
+    hipLaunchKernelGGL(k_pad_level0_pitched, grid, dim3(PAD0_T), shm, s, slots, d_geom, list);
+    return hipGetLastError();
+}
+hipError_t launch_pad_level0_bgr_pitched(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrPitchEntry* list, int n) {
+    if (!slots || !d_geom || !list || n < 1 || n > 65535 || Lmax.n_levels < 1 || Lmax.w[0] < 1 || Lmax.h[0] < 1) return hipErrorInvalidValue;
+    const size_t row = (size_t)pad0c_raw_lds(Lmax.w[0]) + (size_t)pad0_row_lds(Lmax.w[0]);
+    const int ph = Lmax.h[0] + 2 * PAD;
+    ProfScope ps(K_PAD0_BGR, s);
+    if (row * PAD0C_R <= (64u << 10))
+        hipLaunchKernelGGL(k_pad_level0_bgr_pitched<PAD0C_R>, dim3(1, (ph + PAD0C_R - 1) / PAD0C_R, n), dim3(PAD0C_T), row * PAD0C_R, s, slots, d_geom, list);
+    else if (row <= (64u << 10))   // frames wider than 4 k pixels: one row per workgroup
+        hipLaunchKernelGGL(k_pad_level0_bgr_pitched<1>, dim3(1, ph, n), dim3(PAD0C_T), row, s, slots, d_geom, list);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -246,18 +246,44 @@ using namespace pmv;
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
+int pmv::knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
+                   const int* out_best, const float* out_err) {
+    REQ((n == 0 || (src_xy && out_best && out_err)) && (m == 0 || cmp_xy), PMV_ERR_INVALID, "pmv_knn_match: null argument");
+    REQ(n >= 0 && n <= ctx->max_tracks && m >= 0 && m <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_knn_match: n=%d / m=%d exceed max_tracks=%d", n, m, ctx->max_tracks);
+    REQ(n_neighbours >= 1 && n_neighbours <= KNN_MAX_NN && window >= 1 && window <= 63, PMV_ERR_INVALID, "pmv_knn_match: n_neighbours 1..%d, window 1..63", KNN_MAX_NN);
+    REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
+    for (int s : {src_slot, cmp_slot}) { int rc_ = bracket ? slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, s); if (rc_) return rc_; }
+    const PyrLayout& L = ctx->slot_layout[src_slot];
+    const PyrLayout& L2 = ctx->slot_layout[cmp_slot];
+    REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_knn_match: frame sizes differ");
+    return PMV_OK;
+}
+int pmv::fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response) {
+    REQ(out_xy && out_response, PMV_ERR_INVALID, "pmv_detect_fast: null output");
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_detect_fast: slot out of range");
+    const int rc = bracket ? slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, slot);
+    if (rc) return rc;
+    const PyrLayout& L = ctx->slot_layout[slot];
+    REQ((size_t)n_cells * max_per_cell <= (size_t)MAX_CELLS * MAX_PER_CELL, PMV_ERR_CAPACITY, "pmv_detect_fast: n_cells * max_per_cell = %zu exceeds %d",
+        (size_t)n_cells * max_per_cell, MAX_CELLS * MAX_PER_CELL);
+    // a FAST "cell" may be as large as the frame (kNNFeatureMatcher calls the extractor on the whole next frame, :11)
+    size_t tot = 0;
+    for (int i = 0; i < n_cells; i++) {
+        const int* c = cells + 4 * i;
+        REQ(c[2] >= 1 && c[3] >= 1 && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0], PMV_ERR_INVALID,
+            "pmv_detect_fast: cell %d (%d,%d,%d,%d) invalid for %dx%d frame", i, c[0], c[1], c[2], c[3], L.w[0], L.h[0]);
+        tot += (size_t)c[2] * c[3];
+    }
+    REQ(tot <= (size_t)MAX_CELLS * CELL_PIX * sizeof(double), PMV_ERR_CAPACITY, "pmv_detect_fast: cells cover %zu pixels (max %zu)", tot, (size_t)MAX_CELLS * CELL_PIX * 8);
+    return PMV_OK;
+}
 extern "C" {
 
 int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
                   int* out_best, float* out_err) {
-    REQ(ctx && (n == 0 || (src_xy && out_best && out_err)) && (m == 0 || cmp_xy), PMV_ERR_INVALID, "pmv_knn_match: null argument");
-    REQ(n >= 0 && n <= ctx->max_tracks && m >= 0 && m <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_knn_match: n=%d / m=%d exceed max_tracks=%d", n, m, ctx->max_tracks);
-    REQ(n_neighbours >= 1 && n_neighbours <= KNN_MAX_NN && window >= 1 && window <= 63, PMV_ERR_INVALID, "pmv_knn_match: n_neighbours 1..%d, window 1..63", KNN_MAX_NN);
-    REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
-    for (int s : {src_slot, cmp_slot}) { int rc_ = slot_ready(ctx, s, ctx->ingest, 0, ctx->s_front); if (rc_) return rc_; }
+    REQ(ctx, PMV_ERR_INVALID, "pmv_knn_match: null argument");
+    if (const int rc_ = knn_check(ctx, true, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err)) return rc_;
     const PyrLayout& L = ctx->slot_layout[src_slot];
-    const PyrLayout& L2 = ctx->slot_layout[cmp_slot];
-    REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_knn_match: frame sizes differ");
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
@@ -285,26 +311,18 @@ int pmv_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
                     int* out_count) {
     REQ(ctx && cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
     if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }   // OpenCVFASTFeatureExtractor.cpp:12 `if (i >= max) break`
-    REQ(out_xy && out_response, PMV_ERR_INVALID, "pmv_detect_fast: null output");
-    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_detect_fast: slot out of range");
-    int rc = slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front);
+    int rc = fast_check(ctx, true, slot, cells, n_cells, max_per_cell, out_xy, out_response);
     if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
-    REQ((size_t)n_cells * max_per_cell <= (size_t)MAX_CELLS * MAX_PER_CELL, PMV_ERR_CAPACITY, "pmv_detect_fast: n_cells * max_per_cell = %zu exceeds %d",
-        (size_t)n_cells * max_per_cell, MAX_CELLS * MAX_PER_CELL);
-    // a FAST "cell" may be as large as the frame (kNNFeatureMatcher calls the extractor on the whole next frame, :11)
     size_t tot = 0;
     int maxpix = 0;
     for (int i = 0; i < n_cells; i++) {
         const int* c = cells + 4 * i;
-        REQ(c[2] >= 1 && c[3] >= 1 && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0], PMV_ERR_INVALID,
-            "pmv_detect_fast: cell %d (%d,%d,%d,%d) invalid for %dx%d frame", i, c[0], c[1], c[2], c[3], L.w[0], L.h[0]);
         int* d = ctx->h_cells + (size_t)i * CELL_STRIDE;
         d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = c[3]; d[4] = slot; d[5] = (int)tot; d[6] = d[7] = 0;
         tot += (size_t)c[2] * c[3];
         maxpix = std::max(maxpix, c[2] * c[3]);
     }
-    REQ(tot <= (size_t)MAX_CELLS * CELL_PIX * sizeof(double), PMV_ERR_CAPACITY, "pmv_detect_fast: cells cover %zu pixels (max %zu)", tot, (size_t)MAX_CELLS * CELL_PIX * 8);
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));

@@ -368,7 +368,14 @@ static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_pa
     // every sequence has its own frame size (the reference takes whatever cv::imread returns, Frame.cpp:31-42; KITTI odometry comes in three)
     for (int b = 0; b < B; b++)
         if (const int rc = check_params(ctx, who, params[b], true)) return rc;
-    struct Open { pmv_ctx* c; Open(pmv_ctx* c_) : c(c_) { c->batch_open++; } ~Open() { c->batch_open--; } } open(ctx);   // (pmv_set_frame_format)
+    // The run owns the engine and the geometry table until it returns: not while a batch session (pmv_batch_open) holds them. The count also
+    // keeps pmv_set_frame_format and pmv_batch_open away for the duration of the run.
+    struct Open {
+        pmv_ctx* c; bool ok;
+        Open(pmv_ctx* c_) : c(c_) { std::lock_guard<std::mutex> own(c->owner_mu); ok = c->session_state.load() == 0; if (ok) c->batch_open++; }
+        ~Open() { if (ok) c->batch_open--; }
+    } open(ctx);
+    if (!open.ok) { pmv::set_err(ctx, "%s: a batch session is open on this context (pmv_batch_close first): it owns the batch engine and the geometry table", who); return PMV_ERR_INVALID; }
     pmv::BatchEngine* eng = nullptr;
     int rc = pmv::batch_engine_get(ctx, B, &eng);
     if (rc != PMV_OK) return rc;
@@ -485,6 +492,7 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K
 int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                            const int* first_slot, pmv_pipeline_result** out) {
     if (!ctx || !params || !K9 || !gt_poses12 || !first_slot || !out || B < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch: bad argument"); return PMV_ERR_INVALID; }
+    if (ctx->session_state.load() != 0) { pmv::set_err(ctx, "pmv_pipeline_run_batch: a batch session is open on this context (pmv_batch_close first): it owns the batch engine and the geometry table"); return PMV_ERR_INVALID; }
     host_allocator_setup();
     std::vector<int> ring((size_t)B);
     for (int b = 0; b < B; b++) {
@@ -519,6 +527,7 @@ int pmv_pipeline_run_batch(pmv_ctx* ctx, int B, const pmv_pipeline_params* param
 int pmv_pipeline_run_batch_streamed(pmv_ctx* ctx, int B, const pmv_pipeline_params* params, const double* K9, const double* const* gt_poses12,
                                     const uint8_t* const* host_frames, const int* first_slot, int ring, pmv_pipeline_result** out) {
     if (!ctx || !params || !K9 || !gt_poses12 || !host_frames || !first_slot || !out || B < 1) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: bad argument"); return PMV_ERR_INVALID; }
+    if (ctx->session_state.load() != 0) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: a batch session is open on this context (pmv_batch_close first): it owns the batch engine and the geometry table"); return PMV_ERR_INVALID; }
     if (pmv::batch_ingest_active(ctx->ingest)) { pmv::set_err(ctx, "pmv_pipeline_run_batch_streamed: a pmv_frames_stream_begin bracket is open on this context"); return PMV_ERR_INVALID; }
     host_allocator_setup();
     for (int b = 0; b < B; b++) out[b] = nullptr;

@@ -9,6 +9,7 @@
 
 namespace pmv {
 struct BatchEngine;                 // multi-sequence combiners (batch_engine.hip)
+struct BatchSession;                // plugin-level callers of the engine: pmv_batch_open .. pmv_batch_close (batch_session.hip)
 struct BatchIngest;                 // the feeder: background pyramid builds of frame slots, from host memory or in place (ingest_batch.hip)
 // what a frame slot holds (pmv_ctx::slot_state); written only while the slot has no reader: by the synchronous calls, and by the feeder
 // before the sequences it serves start and after they end
@@ -85,7 +86,12 @@ struct pmv_ctx {
     // pmv_set_frame_format: what the host frames of pmv_frames_stage, pmv_frames_stream_begin and the streamed runs hold (pmv_frame_format)
     int frame_format = PMV_FRAMES_GRAY;
     std::atomic<int> batch_open{0};      // a batched run is inside run_batch (the format must not change under it)
-    pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch
+    pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch or pmv_batch_open
+    // The engine and the geometry table have ONE owner at a time: a batched run (batch_open > 0) or a batch session. owner_mu makes the
+    // two checks and the claim one step. session_state: 0 none, 1 open, 2 closing; session_calls: session calls in flight (pmv_batch_close).
+    std::mutex owner_mu;
+    pmv::BatchSession* session = nullptr;
+    std::atomic<int> session_state{0}, session_calls{0};
     pmv::BatchIngest* ingest = nullptr;  // feeder of pmv_frames_stream_begin .. _end brackets (created by the first; stream, buffers kept)
     pmv::BatchIngest* bingest = nullptr; // feeder of pmv_pipeline_run_batch[_streamed] (created by the first that needs one)
     double bingest_stats[PMV_BATCH_INGEST_STATS] = {};   // counters of the last pmv_pipeline_run_batch_streamed (pmv_batch_ingest_stats)
@@ -111,6 +117,16 @@ int geom_table_set(pmv_ctx* ctx, const int* w, const int* h, int B);
 int slot_ready(pmv_ctx* ctx, int slot, BatchIngest* feed = nullptr, int seq = 0, hipStream_t s = nullptr, int* round = nullptr);
 void batch_ingest_destroy(BatchIngest*& g);
 void batch_engine_destroy(pmv_ctx* ctx);
+void batch_session_destroy(pmv_ctx* ctx);   // joins the upload thread, frees the session (no session call may be in flight)
+// The argument checks of the front-end calls, shared by the single-sequence entry points (bracket = true: a slot of an open
+// pmv_frames_stream_begin bracket first waits for its round on the front-end stream) and the session calls of the same name (bracket =
+// false): the same status codes in the same places, from one copy. ctx is not null. max_per_cell of detect_check: already >= 1.
+int lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* out_xy, const uint8_t* out_status, const float* out_err);
+int knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, const int* out_best,
+              const float* out_err);
+int detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell);
+// after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
+int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
 }

@@ -183,6 +183,14 @@ hipError_t launch_pyrdown(hipStream_t s, uint8_t* slots, const PyrLayout& L, int
 hipError_t launch_pad_level0_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n);
 hipError_t launch_pad_level0_bgr_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrListEntry* list, int n);
 hipError_t launch_pyrdown_list(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, int level_dst, const PyrListEntry* list, int n);
+// One entry of a PITCHED level-0 list (the upload class of a batch session): the source is read in place, `pitch` bytes from one row to the
+// next (>= w for gray, >= 3 w for BGR; any value, any base alignment - rows are fetched as the aligned dwords that hold their bytes and no
+// others, so nothing past the last row's last byte is read). Every entry has a source. The level-0 kernels take the list; the levels above
+// are built by launch_pyrdown_list from a PyrListEntry list of the same slots.
+struct PyrPitchEntry { const uint8_t* src; unsigned pitch; int slot; int geom; int reserved; };
+static_assert(sizeof(PyrPitchEntry) == 24, "PyrPitchEntry: one 24-byte record per frame");
+hipError_t launch_pad_level0_pitched(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrPitchEntry* list, int n);
+hipError_t launch_pad_level0_bgr_pitched(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const PyrLayout& Lmax, const PyrPitchEntry* list, int n);
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
