@@ -59,7 +59,7 @@ int pmv_sync(pmv_ctx* ctx);               /* waits for both streams */
 
 /* ---- frames / pyramids ----------------------------------------------------------------------- */
 /* Copy one 8-bit gray frame (host) into `slot` and build its LK pyramid (levels as cv::buildOpticalFlowPyramid
- * with winSize 32, maxLevel 4). */
+ * with winSize 32, maxLevel 4, or with the values of pmv_set_lk_params). */
 int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, int stride);
 /* The same from a colour image as Frame::Frame(file) reads it (Frame.cpp:33: imread(IMREAD_COLOR) = 8-bit BGR, `stride` bytes per row):
  * cv::cvtColor(BGR2GRAY) (Frame.cpp:40-41) runs on the device, then the pyramid as above. Identity for B = G = R (KITTI's gray PNGs). */
@@ -144,6 +144,44 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
  * out_status n bytes, out_err n floats (exactly the three outputs of cv::calcOpticalFlowPyrLK). */
 int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy,
                  uint8_t* out_status, float* out_err);
+/* The caller's cv::calcOpticalFlowPyrLK arguments (OpenCVLucasKanadeFM.h:9-10 `win_size`, `pyr_size`; OpenCV's own defaults are winSize
+ * 21x21, maxLevel 3). A context setting like pmv_set_frame_format and pmv_set_ba_mode: no argument list changes, and a context that never
+ * calls the setter tracks with the reference's Size(32,32), 4, {COUNT+EPS, 30, 0.01}, 1e-4 through the kernels built for them.
+ *   What it governs:
+ *     Pyramid depth, on every route that builds a pyramid from then on (pmv_frame_upload[_bgr], pmv_frames_stage / pmv_frames_build, the
+ *       pmv_frames_stream_begin bracket, both batched runs, pmv_batch_frame_upload): cv::buildOpticalFlowPyramid's rule - after level k is
+ *       kept, stop if level k + 1 would be <= win in either dimension; never beyond max_level. pmv_frame_num_levels reports the result.
+ *     LK arithmetic of pmv_lk_track, pmv_batch_lk_track and the LK matcher inside pmv_pipeline_run, _run_streamed, _run_batch and
+ *       _run_batch_streamed: half = (win - 1) / 2, the window tests, minEig / (2 win^2), err / (32 win^2), the iteration cap, eps^2 (compared
+ *       in double with dx^2 + dy^2) and min_eig. Bit-exact against the CPU restatement for every accepted value. win = 32 runs the tuned
+ *       kernels (k_lk, k_lk_batch), any other window the general ones (k_lk_general, k_lk_batch_general: same profiling class).
+ *   Accepted ranges (anything else is PMV_ERR_INVALID, the setting stays as it was, nothing is clamped):
+ *     3 <= win <= 63         the template tile reads one pixel beyond the window: with PMV_PYR_PAD = 64 a window of 63 stays inside the frame
+ *     0 <= max_level <= 4    a pyramid has at most 5 levels (the 8-int record of pmv_batch_upload_rounds keeps its meaning)
+ *     1 <= max_iter <= 100, 0 <= eps <= 10      cv::calcOpticalFlowPyrLK's own clamps [mem: lkpyramid.cpp]
+ *     min_eig >= 0 and finite
+ *   Refused (PMV_ERR_INVALID, the setting stays as it was) while a pmv_frames_stream_begin bracket, a batched run or a batch session is open
+ *     on the context. Sessions: set the parameters before pmv_batch_open; all callers of a session share them.
+ *   Frame slots: a call that changes win or max_level EMPTIES EVERY FRAME SLOT - the slots are what they were after pmv_ctx_create, their
+ *     contents are lost, and their storage is laid out again (and reallocated if the new depth needs more room). pmv_lk_track and every
+ *     other reader then fail on such a slot as on a slot that was never uploaded, until it is uploaded again. A call that changes only
+ *     max_iter, eps or min_eig leaves the slots alone.
+ *   Frame sizes: 40x40 .. max_w x max_h as before. Level 0 may be narrower than the window and upper levels narrower than the 64-pixel
+ *     border (a 10x8 level at win = 5): the border is REFLECT_101 applied as often as needed.
+ *   pmv_lk_counters: the general kernels count at most 255 iterations per track (the tuned ones cannot reach that).
+ *   Out of scope: non-square windows, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS (the CPU restatement has none of them). */
+typedef struct pmv_lk_params {
+    int win;          /* square window side, cv::Size(win, win); default 32 */
+    int max_level;    /* maxLevel of buildOpticalFlowPyramid / calcOpticalFlowPyrLK; default 4 */
+    int max_iter;     /* TermCriteria COUNT; default 30 */
+    double eps;       /* TermCriteria EPS (the kernel compares dx^2 + dy^2 with eps^2); default 0.01 */
+    float min_eig;    /* minEigThreshold; default 1e-4f */
+} pmv_lk_params;
+int pmv_set_lk_params(pmv_ctx* ctx, const pmv_lk_params* p);
+int pmv_get_lk_params(pmv_ctx* ctx, pmv_lk_params* out);
+/* diagnostic: on != 0 sends the default window (32) through the general kernels as well, so that a test can compare the two code paths.
+ * It changes no result. */
+int pmv_debug_lk_general(pmv_ctx* ctx, int on);
 
 /* ---- PnP ------------------------------------------------------------------------------------------------ */
 /* obj_xyz m*3 float32, img_xy m*2 float32, K 9 doubles row-major, rvec/tvec 3 doubles in/out

@@ -31,12 +31,17 @@ class BaSummary(C.Structure):
                 ("successful_steps", C.c_int), ("termination", C.c_int)]
 
 
+class LKParams(C.Structure):
+    """pmv_lk_params of include/pmv_hip.h"""
+    _fields_ = [("win", C.c_int), ("max_level", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double), ("min_eig", C.c_float)]
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_thread_error", "pmv_sync",
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
-    "pmv_lk_track", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
+    "pmv_lk_track", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -487,6 +492,24 @@ class Context:
         self._ck(self.lib.pmv_lk_track(self.h, prev_slot, next_slot, _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p),
                                        _p(err, _f32p)))
         return out, st, err
+
+    def set_lk_params(self, win=32, max_level=4, max_iter=30, eps=0.01, min_eig=1e-4):
+        """cv::calcOpticalFlowPyrLK's winSize (square), maxLevel, criteria and minEigThreshold for every pyramid built and every LK call
+        made from now on (pmv_set_lk_params). A change of win or max_level empties every frame slot: upload the frames again."""
+        p = LKParams(int(win), int(max_level), int(max_iter), float(eps), float(min_eig))
+        self.lib.pmv_set_lk_params.argtypes = [C.c_void_p, C.POINTER(LKParams)]
+        self._ck(self.lib.pmv_set_lk_params(self.h, C.byref(p)))
+
+    def lk_params(self):
+        """the context's LK setting as a dict with the keyword names of set_lk_params"""
+        p = LKParams()
+        self.lib.pmv_get_lk_params.argtypes = [C.c_void_p, C.POINTER(LKParams)]
+        self._ck(self.lib.pmv_get_lk_params(self.h, C.byref(p)))
+        return dict(win=p.win, max_level=p.max_level, max_iter=p.max_iter, eps=p.eps, min_eig=p.min_eig)
+
+    def debug_lk_general(self, on):
+        """diagnostic: the default window through the general LK kernels as well (pmv_debug_lk_general); changes no result"""
+        self._ck(self.lib.pmv_debug_lk_general(self.h, 1 if on else 0))
 
     # ---- BasePnPSolver role ----
     def pnp_ransac(self, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):

@@ -322,8 +322,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 for (LKReq* r : live)
                     if (k < r->order.size()) put(r, r->order[k]);
         }
-        LKParams P;
-        P.max_iter = 30; P.eps2 = 1e-4f; P.eps2d = 0.01 * 0.01; P.min_eig = 1e-4f;
+        LKParams P = lk_launch_params(ctx);
         static const bool lk_stamps = getenv("PMV_LK_STAMPS") != nullptr;   // diagnostic: phase timers of every 64th track (pmv_debug_lk_stamps)
         if (lk_stamps) {
             static std::mutex stamps_mu;   // two LK lanes

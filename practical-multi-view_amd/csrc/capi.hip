@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <vector>
 #include <cstdarg>
+#include <cfloat>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -30,20 +31,20 @@ void pmv::set_err(pmv_ctx* c, const char* fmt, ...) {
     memcpy(c->err, tmp, sizeof(tmp));
 }
 
-PyrLayout pmv::make_layout(int w, int h) {
+PyrLayout pmv::make_layout(int w, int h, int win, int max_level) {
     PyrLayout L;
     memset(&L, 0, sizeof(L));
-    // cv::buildOpticalFlowPyramid(img, pyr, Size(32,32), maxLevel=4): stop when the next level would be <= winSize
+    // cv::buildOpticalFlowPyramid(img, pyr, Size(win,win), maxLevel): stop when the next level would be <= winSize (the reference: 32, 4)
     int lw = w, lh = h, n = 0;
     uint32_t off = 0;
-    for (int level = 0; level <= 4; level++) {
+    for (int level = 0; level <= max_level && level < MAX_LEVELS; level++) {
         L.w[level] = lw; L.h[level] = lh;
         L.stride[level] = (lw + 2 * PAD + 63) & ~63;
         L.off[level] = off;
         off += (uint32_t)L.stride[level] * (uint32_t)(lh + 2 * PAD);
         n = level + 1;
         lw = (lw + 1) / 2; lh = (lh + 1) / 2;
-        if (lw <= LK_WIN || lh <= LK_WIN) break;
+        if (lw <= win || lh <= win) break;
     }
     L.n_levels = n;
     // No separate copy of the gray frame: staging writes its rows into the interior of the padded level 0 and k_pad_level0 adds the
@@ -52,6 +53,14 @@ PyrLayout pmv::make_layout(int w, int h) {
     L.gray_off = L.off[0] + (uint32_t)PAD * (uint32_t)L.stride[0] + (uint32_t)PAD;
     L.slot_bytes = (off + 4095) & ~4095u;
     return L;
+}
+
+LKParams pmv::lk_launch_params(const pmv_ctx* ctx) {
+    LKParams P;
+    P.max_iter = ctx->lk.max_iter; P.eps2d = ctx->lk.eps * ctx->lk.eps; P.eps2 = (float)P.eps2d; P.min_eig = ctx->lk.min_eig;
+    P.stamps = nullptr;
+    P.win = ctx->lk.win; P.general = ctx->lk_general;
+    return P;
 }
 
 extern "C" {
@@ -80,7 +89,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     c->device = device;
     c->max_w = max_w; c->max_h = max_h; c->n_slots = n_slots; c->max_tracks = max_tracks;
     c->max_ba_cams = max_ba_cams; c->max_ba_points = max_ba_points; c->max_ba_obs = max_ba_obs;
-    c->cap = make_layout(max_w, max_h);
+    c->cap = make_layout(max_w, max_h, c->lk.win, c->lk.max_level);
     c->slot_layout.assign(n_slots, PyrLayout());
     c->slot_state.assign(n_slots, SLOT_EMPTY);
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(nullptr, "%s: %s", #x, hipGetErrorString(e_)); pmv_ctx_destroy(c); return PMV_ERR_HIP; } } while (0)
@@ -90,6 +99,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     CK(hipStreamCreateWithFlags(&c->s_front, hipStreamNonBlocking));
     CK(hipStreamCreateWithFlags(&c->s_back, hipStreamNonBlocking));
     CK(hipMalloc(&c->d_slots, (size_t)c->cap.slot_bytes * n_slots));
+    c->slots_alloc = (size_t)c->cap.slot_bytes * n_slots;
     CK(hipMalloc(&c->d_tight, (size_t)pmv_ctx::TIGHT_FRAMES * max_w * max_h + 256));
     const size_t nt = (size_t)max_tracks;
     CK(hipMalloc(&c->d_prev_xy, nt * 12 + 64));   // track coordinates followed by the block -> track order
@@ -187,7 +197,7 @@ static int build_levels_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int
 // NOTE: slots are addressed with the CAPACITY slot size (ctx->cap.slot_bytes); a frame smaller than max_w x max_h
 // uses its own level geometry inside the slot but the same slot pitch.
 PyrLayout pmv::layout_for(pmv_ctx* ctx, int w, int h) {
-    PyrLayout L = make_layout(w, h);
+    PyrLayout L = make_layout(w, h, ctx->lk.win, ctx->lk.max_level);
     L.slot_bytes = ctx->cap.slot_bytes;
     return L;
 }
@@ -236,6 +246,52 @@ int pmv_set_frame_format(pmv_ctx* ctx, int format) {
     REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_set_frame_format: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
     REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_set_frame_format: a batched run is open on this context");
     ctx->frame_format = format;
+    return PMV_OK;
+}
+
+// cv::calcOpticalFlowPyrLK's winSize, maxLevel, criteria and minEigThreshold (and buildOpticalFlowPyramid's winSize, maxLevel) for every
+// pyramid built and every LK call made on the context from now on. Not while a feeder, a batched run or a session holds layouts made
+// under the old values.
+int pmv_set_lk_params(pmv_ctx* ctx, const pmv_lk_params* p) {
+    REQ(ctx && p, PMV_ERR_INVALID, "pmv_set_lk_params: null argument");
+    REQ(p->win >= 3 && p->win <= 63, PMV_ERR_INVALID, "pmv_set_lk_params: win = %d outside 3..63", p->win);
+    REQ(p->max_level >= 0 && p->max_level <= MAX_LEVELS - 1, PMV_ERR_INVALID, "pmv_set_lk_params: max_level = %d outside 0..%d", p->max_level, MAX_LEVELS - 1);
+    REQ(p->max_iter >= 1 && p->max_iter <= 100, PMV_ERR_INVALID, "pmv_set_lk_params: max_iter = %d outside 1..100", p->max_iter);
+    REQ(p->eps >= 0.0 && p->eps <= 10.0, PMV_ERR_INVALID, "pmv_set_lk_params: eps = %g outside 0..10", p->eps);   // (a NaN fails the comparison too)
+    REQ(p->min_eig >= 0.f && p->min_eig <= FLT_MAX, PMV_ERR_INVALID, "pmv_set_lk_params: min_eig = %g is negative or not finite", (double)p->min_eig);
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_set_lk_params: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
+    std::lock_guard<std::mutex> own(ctx->owner_mu);
+    REQ(ctx->session_state.load() == 0, PMV_ERR_INVALID, "pmv_set_lk_params: a batch session is open on this context (set the parameters before pmv_batch_open)");
+    REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_set_lk_params: a batched run is open on this context");
+    if (p->win != ctx->lk.win || p->max_level != ctx->lk.max_level) {
+        // every layout changes: the slots go back to what they were after pmv_ctx_create, on a pitch sized for the new depth
+        CKC(hipSetDevice(ctx->device));
+        CKC(hipStreamSynchronize(ctx->s_front));
+        CKC(hipStreamSynchronize(ctx->s_back));
+        const PyrLayout cap = make_layout(ctx->max_w, ctx->max_h, p->win, p->max_level);
+        const size_t need = (size_t)cap.slot_bytes * ctx->n_slots;
+        if (need > ctx->slots_alloc) {   // (a failed allocation leaves storage, pitch and setting as they were)
+            uint8_t* d = nullptr;
+            CKC(hipMalloc(&d, need));
+            CKC(hipFree(ctx->d_slots));
+            ctx->d_slots = d; ctx->slots_alloc = need;
+        }
+        ctx->cap = cap;
+        ctx->slot_layout.assign(ctx->n_slots, PyrLayout());
+        ctx->slot_state.assign(ctx->n_slots, SLOT_EMPTY);
+    }
+    ctx->lk = *p;
+    return PMV_OK;
+}
+int pmv_get_lk_params(pmv_ctx* ctx, pmv_lk_params* out) {
+    REQ(ctx && out, PMV_ERR_INVALID, "pmv_get_lk_params: null argument");
+    *out = ctx->lk;
+    return PMV_OK;
+}
+// diagnostic: the default window through the general kernels as well (a test compares the two code paths; no result changes)
+int pmv_debug_lk_general(pmv_ctx* ctx, int on) {
+    REQ(ctx, PMV_ERR_INVALID, "null ctx");
+    ctx->lk_general = on != 0;
     return PMV_OK;
 }
 
@@ -357,8 +413,7 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
         }
     }
     CKC(hipMemcpyAsync(ctx->d_prev_xy, ctx->h_prev_xy, (size_t)n * 8 + (size_t)nb * 4, hipMemcpyHostToDevice, ctx->s_front));
-    LKParams P;
-    P.max_iter = 30; P.eps2 = 1e-4f; P.eps2d = 0.01 * 0.01; P.min_eig = 1e-4f;
+    LKParams P = lk_launch_params(ctx);
     static const bool lk_stamps = getenv("PMV_LK_STAMPS") != nullptr;   // read once per process
     if (!ctx->d_lk_stamps && lk_stamps) { CKC(hipMalloc(&ctx->d_lk_stamps, 16 * 8)); CKC(hipMemset(ctx->d_lk_stamps, 0, 16 * 8)); }
     P.stamps = ctx->d_lk_stamps;

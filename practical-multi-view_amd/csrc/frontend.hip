@@ -916,10 +916,255 @@ __global__ __launch_bounds__(LKB_T) __attribute__((amdgpu_waves_per_eu(3, 3))) v
     }
 }
 
+// ---- the general form: any square window 3 .. 63 (pmv_set_lk_params) ------------------------------------------------------------------
+// k_lk / k_lk_batch above are built around 32 window rows: thread = row, samples in registers, tiles of fixed size. A caller's
+// cv::calcOpticalFlowPyrLK arguments (OpenCV's default is 21 x 21) go through this form instead. The window side is a RUNTIME value: one
+// code object serves all 61 sides, and a round of the batch engine needs no kernel per window. The price is that a lane's samples cannot
+// live in registers (their count per lane, ceil(win^2 / T), would have to be a compile-time array bound): I (5 fractional bits) and the
+// packed (Ix, Iy) of the window are kept in LDS for the level, next to the tiles.
+//   Pixel-to-lane mapping: window pixel p = y * win + x goes to lane p % T, in steps of T (x and y advance incrementally: no division per
+//   pixel). Every window sum is an exact integer, so the mapping cannot change a bit.
+//   int32 partials: a lane adds at most ceil(63^2 / 64) = 63 products of |diff| <= 8160 and |Ix| <= 4080: 63 * 8160 * 4080 = 2 097 446 400
+//   < 2^31 = 2 147 483 648. 64 products would still fit, 65 would not - the window cap of 63 and T >= 64 are what keeps this true
+//   (static_assert below). The wave / block totals are formed exactly (wave_sum_i32_exact: doubles) and rounded once to float, like the
+//   oracle's (float)int64; that also covers the err sum, which passes 2^24 at win = 63 (3969 * 8160 = 3.2e7).
+//   Tiles (LDS, dynamic, sized by win - lkg_lds): the template tile of (win + 3)^2 bytes and the (win + 1)^2 Scharr pairs are dead once the
+//   samples are taken, so the search tile of TS x TS bytes (TS = win + 28 rounded up to 16: 64 at win = 32 as in k_lk, 96 at 63) shares
+//   their space. It is re-staged when the window walks out of it; its origin is clamped so that it never leaves the padded level buffer
+//   (the window itself reaches at most 63 pixels outside the image: one pixel beyond a window of 63 is column w + 63 of a 64-pixel frame).
+constexpr int LKG_MIN_WIN = 3, LKG_MAX_WIN = 63;
+static_assert((long long)((LKG_MAX_WIN * LKG_MAX_WIN + 63) / 64) * 8160 * 4080 < (1ll << 31), "a lane's int32 partial of diff * Ix at the largest window, one wavefront per track");
+struct LKGLds { int si_stride, sd_stride, ts, sj_stride, off_tiles, off_iw, off_dw, total; };
+__host__ __device__ inline LKGLds lkg_lds(int win) {
+    LKGLds G;
+    G.si_stride = ((win + 9) >> 2) << 2;          // the dwords that hold (<= 3 bytes of alignment) + win + 3 tile columns
+    G.sd_stride = (win + 1) | 1;                   // (dx, dy) pairs per row: odd
+    G.ts = (win + 28 + 15) & ~15;
+    G.sj_stride = G.ts + 4;
+    const int tmpl = (win + 3) * G.si_stride + (win + 1) * G.sd_stride * 4, srch = G.ts * G.sj_stride;
+    G.off_tiles = 2 * 4 * 4 * 8;                   // behind sred[2][<= 4 wavefronts][4] doubles
+    G.off_iw = G.off_tiles + (((tmpl > srch ? tmpl : srch) + 3) & ~3);
+    G.off_dw = G.off_iw + ((win * win * 2 + 3) & ~3);
+    G.total = G.off_dw + win * win * 4;
+    return G;
+}
+// One track through all pyramid levels, executed by one whole T-thread workgroup (T = 256: k_lk_general, T = 64: k_lk_batch_general);
+// every thread returns the same results. The arithmetic is orc_lk.cpp:92-209 with W = P.win.
+template <int T, class LRef>
+__device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
+                                                     const float px0, const float py0, const LKParams& P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lkg_smem[];
+    const int W = __builtin_amdgcn_readfirstlane(P.win);
+    const LKGLds G = lkg_lds(W);
+    double* sred = (double*)lkg_smem;
+    uint8_t* sI = lkg_smem + G.off_tiles;
+    short2* sD = (short2*)(sI + (W + 3) * G.si_stride);
+    uint8_t* sJ = lkg_smem + G.off_tiles;                    // shares the space of sI and sD (see above)
+    short* sIw = (short*)(lkg_smem + G.off_iw);
+    uint32_t* sDw = (uint32_t*)(lkg_smem + G.off_dw);      // Ix | Iy << 16
+    const int tid = threadIdx.x;
+    const int npix = W * W, TS = G.ts;
+    const int step_y = T / W, step_x = T - step_y * W;       // pixel p + T from pixel p
+    const int y_first = tid / W, x_first = tid - y_first * W;
+    const int slack = (TS - W - 4) >> 1;                     // search-tile columns left of the window when a tile is cut
+    const float half = (float)(W - 1) * 0.5f;
+    const float FLT_SCALE = 1.f / (1 << 20);
+    float outx = 0.f, outy = 0.f, err = 0.f;
+    int status = 1, slot = 0, n_iter = 0, n_lev = 0;
+    const int ml = L.n_levels - 1;
+    int tx0 = 0, ty0 = 0, tile_level = -1;
+
+    for (int level = ml; level >= 0; level--) {
+        const int lw = L.w[level], lh = L.h[level], ls = L.stride[level];
+        const uint8_t* Iorg = level_origin(prevS, L, level);
+        const uint8_t* Jorg = level_origin(nextS, L, level);
+        const float lscale = __int_as_float((127 - level) << 23);   // 2^-level, the value of (float)(1. / (1 << level))
+        const float prevx = px0 * lscale - half, prevy = py0 * lscale - half;
+        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
+        float nx, ny;
+        if (level == ml) { nx = px0 * lscale; ny = py0 * lscale; }
+        else { nx = outx * 2.f; ny = outy * 2.f; }
+        outx = nx; outy = ny;
+        if (ipx < -W || ipx >= lw || ipy < -W || ipy >= lh) {   // block-uniform
+            if (level == 0) { status = 0; err = 0.f; }
+            continue;
+        }
+        // search tile of level `level` with the window origin (inx, iny) `slack` pixels inside, clamped into the padded buffer: columns
+        // -PAD .. stride - PAD - 1 and rows -PAD .. lh + PAD - 1 exist (stride >= lw + 2 PAD, a multiple of 64; TS <= 96 <= 2 PAD, so
+        // the upper clamp is never below the lower one). A window origin in -W .. lw - 1 keeps its W + 1 columns inside either way.
+        auto stage_search = [&](int inx, int iny) {
+            int x0 = (inx - slack) & ~3, y0 = iny - slack;
+            x0 = x0 < -PAD ? -PAD : x0; x0 = x0 > ls - PAD - TS ? ls - PAD - TS : x0;
+            y0 = y0 < -PAD ? -PAD : y0; y0 = y0 > lh + PAD - TS ? lh + PAD - TS : y0;
+            tx0 = x0; ty0 = y0; tile_level = level;
+            const int per_row = TS >> 4;
+            __syncthreads();
+            for (int idx = tid; idx < TS * per_row; idx += T) {
+                const int row = idx / per_row, x16 = idx - row * per_row;
+                const U4A v = *(const U4A*)(Jorg + (ptrdiff_t)(y0 + row) * ls + x0 + 16 * x16);
+                uint32_t* d = (uint32_t*)(sJ + row * G.sj_stride) + 4 * x16;
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+            __syncthreads();
+        };
+        auto in_tile = [&](int inx, int iny) {
+            const int wx = inx - tx0, wy = iny - ty0;
+            return tile_level == level && wx >= 0 && wy >= 0 && wx + W + 1 <= TS && wy + W + 1 <= TS;
+        };
+        __syncthreads();   // the level above is done with the search tile, whose space the template tile takes
+        tile_level = -1;
+        // ---- template tile: rows ipy - 1 .. ipy + W + 1, columns ipx - 1 .. ipx + W + 1 (>= -PAD and <= lw + PAD - 1 for W <= 63), as the
+        // aligned dwords that hold them and no others
+        const int ax0 = (ipx - 1) & ~3, aoff = (ipx - 1) - ax0;
+        {
+            const int ndw = (aoff + W + 3 + 3) >> 2;   // <= si_stride / 4
+            for (int idx = tid; idx < (W + 3) * ndw; idx += T) {
+                const int y = idx / ndw, d = idx - y * ndw;
+                ((uint32_t*)(sI + y * G.si_stride))[d] = *(const uint32_t*)(Iorg + (ptrdiff_t)(ipy - 1 + y) * ls + ax0 + 4 * d);
+            }
+        }
+        __syncthreads();
+        // ---- Scharr (calcSharrDeriv) at the (W + 1)^2 sample positions: REFLECT_101 inside the image comes with the padded buffer, constant 0
+        // outside the image
+        for (int idx = tid; idx < (W + 1) * (W + 1); idx += T) {
+            const int y = idx / (W + 1), x = idx - y * (W + 1);
+            const int gx = ipx + x, gy = ipy + y;
+            short2 d = make_short2(0, 0);
+            if (gx >= 0 && gx < lw && gy >= 0 && gy < lh) {
+                const uint8_t* a = sI + y * G.si_stride + aoff + x;
+                const uint8_t* b = a + G.si_stride;
+                const uint8_t* c = b + G.si_stride;
+                const int S0 = (a[0] + c[0]) * 3 + b[0] * 10, S2 = (a[2] + c[2]) * 3 + b[2] * 10;
+                const int V0 = c[0] - a[0], V1 = c[1] - a[1], V2 = c[2] - a[2];
+                d.x = (short)(S2 - S0);
+                d.y = (short)((V2 + V0) * 3 + V1 * 10);
+            }
+            sD[y * G.sd_stride + x] = d;
+        }
+        __syncthreads();
+        // ---- window samples (I with 5 fractional bits, Ix, Iy) into LDS + exact A sums
+        int iw00, iw01, iw10, iw11;
+        bilinear_weights(prevx - ipx, prevy - ipy, iw00, iw01, iw10, iw11);
+        int apart[3] = {0, 0, 0};
+        for (int p = tid, x = x_first, y = y_first; p < npix; p += T) {
+            const uint8_t* i0 = sI + (y + 1) * G.si_stride + aoff + x + 1;
+            const uint8_t* i1 = i0 + G.si_stride;
+            const short2 d00 = sD[y * G.sd_stride + x], d01 = sD[y * G.sd_stride + x + 1], d10 = sD[(y + 1) * G.sd_stride + x], d11 = sD[(y + 1) * G.sd_stride + x + 1];
+            const int iv = descale(i0[0] * iw00 + i0[1] * iw01 + i1[0] * iw10 + i1[1] * iw11, 9);
+            const int ixv = descale(d00.x * iw00 + d01.x * iw01 + d10.x * iw10 + d11.x * iw11, 14);
+            const int iyv = descale(d00.y * iw00 + d01.y * iw01 + d10.y * iw10 + d11.y * iw11, 14);
+            sIw[p] = (short)iv;
+            sDw[p] = ((uint32_t)ixv & 0xffffu) | ((uint32_t)iyv << 16);
+            apart[0] += ixv * ixv; apart[1] += ixv * iyv; apart[2] += iyv * iyv;   // <= 63 x 4080^2 per lane
+            x += step_x; y += step_y;
+            if (x >= W) { x -= W; y++; }
+        }
+        double sA[3];
+        block_sum_exact<3, T>(apart, sA, sred, slot); slot ^= 1;
+        const float A11 = (float)sA[0] * FLT_SCALE, A12 = (float)sA[1] * FLT_SCALE, A22 = (float)sA[2] * FLT_SCALE;
+        float D = A11 * A22 - A12 * A12;
+        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * W * W);
+        if (minEig < P.min_eig || D < FLT_EPSILON) {   // block-uniform (computed from block-wide sums)
+            if (level == 0) status = 0;
+            continue;
+        }
+        D = 1.f / D;
+        nx -= half; ny -= half;
+        float pdx = 0.f, pdy = 0.f;
+        n_lev++;
+        // sum over the window of f(diff, Ix | Iy << 16) with diff = the search-side sample at window origin (wx, wy) of the tile minus I
+        auto window_pass = [&](int wx, int wy, auto&& f) {
+            for (int p = tid, x = x_first, y = y_first; p < npix; p += T) {
+                const uint8_t* j0 = sJ + (wy + y) * G.sj_stride + wx + x;
+                const uint8_t* j1 = j0 + G.sj_stride;
+                const int diff = descale(j0[0] * iw00 + j0[1] * iw01 + j1[0] * iw10 + j1[1] * iw11, 9) - sIw[p];
+                f(diff, sDw[p]);
+                x += step_x; y += step_y;
+                if (x >= W) { x -= W; y++; }
+            }
+        };
+        for (int j = 0; j < P.max_iter; j++) {
+            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+            if (inx < -W || inx >= lw || iny < -W || iny >= lh) {
+                if (level == 0) status = 0;
+                break;
+            }
+            if (!in_tile(inx, iny)) stage_search(inx, iny);   // block-uniform
+            bilinear_weights(nx - inx, ny - iny, iw00, iw01, iw10, iw11);
+            int bpart[2] = {0, 0};
+            window_pass(inx - tx0, iny - ty0, [&](int diff, uint32_t d) { bpart[0] += diff * (int)(short)(d & 0xffffu); bpart[1] += diff * ((int)d >> 16); });
+            double sB[2];
+            block_sum_exact<2, T>(bpart, sB, sred, slot); slot ^= 1;
+            const float fb1 = (float)sB[0] * FLT_SCALE, fb2 = (float)sB[1] * FLT_SCALE;
+            const float dx = (A12 * fb2 - A22 * fb1) * D;
+            const float dy = (A12 * fb1 - A11 * fb2) * D;
+            nx += dx; ny += dy;
+            outx = nx + half; outy = ny + half;
+            n_iter++;
+            if ((double)dx * dx + (double)dy * dy <= P.eps2d) break;
+            if (j > 0 && fabsf(dx + pdx) < 0.01 && fabsf(dy + pdy) < 0.01) {
+                outx -= dx * 0.5f; outy -= dy * 0.5f;
+                break;
+            }
+            pdx = dx; pdy = dy;
+        }
+        if (status && level == 0) {
+            const float fx = outx - half, fy = outy - half;
+            const int inx = (int)floorf(fx), iny = (int)floorf(fy);
+            if (inx < -W || inx >= lw || iny < -W || iny >= lh) {
+                status = 0;
+            } else {
+                if (!in_tile(inx, iny)) stage_search(inx, iny);
+                bilinear_weights(fx - inx, fy - iny, iw00, iw01, iw10, iw11);
+                int epart[1] = {0};
+                window_pass(inx - tx0, iny - ty0, [&](int diff, uint32_t) { epart[0] += diff < 0 ? -diff : diff; });
+                double sE[1];
+                block_sum_exact<1, T>(epart, sE, sred, slot); slot ^= 1;
+                err = (float)sE[0] * (1.f / (float)(32 * W * W));
+            }
+        }
+    }
+    LKResult res;
+    // the per-track work word has 8 bits for the iterations (lk_store): up to 5 x 100 here, so the count saturates
+    res.x = outx; res.y = outy; res.err = err; res.status = status; res.n_iter = n_iter > 255 ? 255 : n_iter; res.n_lev = n_lev;
+    return res;
+}
+
+__global__ __launch_bounds__(LK_T) void k_lk_general(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, PyrLayout L,
+                                                     const float* __restrict__ prev_xy, const int* __restrict__ order, int n, LKParams P,
+                                                     float* __restrict__ out_xy, uint8_t* __restrict__ out_status, float* __restrict__ out_err,
+                                                     uint16_t* __restrict__ out_work) {
+    const int t = order[blockIdx.x];   // as k_lk
+    if (t < 0 || t >= n) return;
+    const LKResult r = lk_track_general<LK_T, const PyrLayout&>(prevS, nextS, L, prev_xy[2 * t], prev_xy[2 * t + 1], P);
+    lk_store(r, t, out_xy, out_status, out_err, out_work);
+}
+__global__ __launch_bounds__(LKB_T) void k_lk_batch_general(const uint8_t* __restrict__ slots, const LKBlock* __restrict__ blocks, int n_blocks,
+                                                            const PyrLayout* __restrict__ geom, LKParams P, float* __restrict__ out_xy,
+                                                            uint8_t* __restrict__ out_status, float* __restrict__ out_err, uint16_t* __restrict__ out_work) {
+    for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {   // as k_lk_batch
+        const LKBlock bk = blocks[b];
+        const LKResult r = lk_track_general<LKB_T, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), bk.x, bk.y, P);
+        lk_store(r, bk.track, out_xy, out_status, out_err, out_work);
+        __syncthreads();
+    }
+}
+// which form a launch takes: the tuned kernels serve the window they were built for unless the diagnostic asks for the general form
+static bool lk_use_general(const LKParams& P) { return P.win != LK_WIN || P.general; }
+static bool lk_params_ok(const LKParams& P) {
+    return P.win >= LKG_MIN_WIN && P.win <= LKG_MAX_WIN && P.max_iter >= 1 && P.eps2d >= 0.0 && P.min_eig >= 0.f && lkg_lds(P.win).total <= (64 << 10);
+}
+
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work) {
     if (n <= 0) return hipSuccess;
+    if (lk_use_general(P)) {
+        if (!prev_slot || !next_slot || !d_prev_xy || !d_order || !d_out_xy || !d_status || !d_err || n_blocks < n || L.n_levels < 1 || L.n_levels > MAX_LEVELS || !lk_params_ok(P)) return hipErrorInvalidValue;
+        ProfScope ps(K_LK, s);
+        hipLaunchKernelGGL(k_lk_general, dim3(n_blocks), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_order, n, P, d_out_xy, d_status, d_err, d_work);
+        return hipGetLastError();
+    }
     // every pointer the kernel dereferences: a null base must come back as an error code, never reach a launch
     if (!prev_slot || !next_slot || !d_prev_xy || !d_order || !d_out_xy || !d_status || !d_err || n_blocks < n || L.n_levels < 1 || L.n_levels > MAX_LEVELS) return hipErrorInvalidValue;
     ProfScope ps(K_LK, s);
@@ -933,6 +1178,13 @@ hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d
     if (n_blocks <= 0) return hipSuccess;
     if (!slots || !d_blocks || !d_out_xy || !d_status || !d_err || !d_geom) return hipErrorInvalidValue;
     static const int cap = getenv("PMV_LK_BATCH_BLOCKS") ? atoi(getenv("PMV_LK_BATCH_BLOCKS")) : 0;
+    if (lk_use_general(P)) {   // (its own LDS, 6 .. 46 KB by window, already bounds the workgroups per CU: no padding on top)
+        if (!lk_params_ok(P)) return hipErrorInvalidValue;
+        ProfScope ps(K_LK, s);
+        hipLaunchKernelGGL(k_lk_batch_general, dim3(cap > 0 && cap < n_blocks ? cap : n_blocks), dim3(LKB_T), (size_t)lkg_lds(P.win).total, s, slots, d_blocks, n_blocks, d_geom, P,
+                           d_out_xy, d_status, d_err, d_work);
+        return hipGetLastError();
+    }
     // Occupancy cap of the bulk kernel: 13.9 KB of LDS per one-wavefront workgroup lets 11 of them share a CU (160 KB; the prefetch
     // registers of a track, ~150 per lane, allow 12), and then every short kernel of the other classes - the 23 launches of an LM solve,
     // the PnP stages, the detector - waits for LK wavefronts to drain before its workgroups fit anywhere. Unused dynamic LDS on top caps it:

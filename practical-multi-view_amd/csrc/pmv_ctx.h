@@ -85,6 +85,11 @@ struct pmv_ctx {
     int ba_mode = 0;
     // pmv_set_frame_format: what the host frames of pmv_frames_stage, pmv_frames_stream_begin and the streamed runs hold (pmv_frame_format)
     int frame_format = PMV_FRAMES_GRAY;
+    // pmv_set_lk_params: the window and level cap shape every layout made from now on (layout_for, cap), the stop criteria go to the LK
+    // launches as they are (lk_launch_params). Changed only while no bracket, batched run or session is open, so the launches read them freely.
+    pmv_lk_params lk = {pmv::LK_WIN, 4, 30, 0.01, 1e-4f};
+    int lk_general = 0;                  // pmv_debug_lk_general
+    size_t slots_alloc = 0;              // bytes behind d_slots (>= cap.slot_bytes * n_slots; grows when a deeper pyramid needs more)
     std::atomic<int> batch_open{0};      // a batched run is inside run_batch (the format must not change under it)
     pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch or pmv_batch_open
     // The engine and the geometry table have ONE owner at a time: a batched run (batch_open > 0) or a batch session. owner_mu makes the
@@ -104,7 +109,8 @@ struct pmv_ctx {
 namespace pmv {
 void set_err(pmv_ctx* c, const char* fmt, ...);
 const char* thread_error();         // the last message set_err wrote on the calling thread
-PyrLayout make_layout(int w, int h);
+PyrLayout make_layout(int w, int h, int win, int max_level);   // orc::build_pyramid's level rule for cv::Size(win, win), maxLevel
+LKParams lk_launch_params(const pmv_ctx* ctx);                 // the context's LK setting as the launchers take it (stamps = null)
 int backend_create(pmv_ctx* c);     // allocates PnP/BA workspaces
 void backend_destroy(pmv_ctx* c);
 PyrLayout layout_for(pmv_ctx* ctx, int w, int h);

@@ -11,7 +11,7 @@ namespace pmv {
 // row stride that is a multiple of 64 bytes, so every tile row starts dword-aligned and no kernel needs a border branch.
 constexpr int PAD = 64;
 constexpr int MAX_LEVELS = 5;   // maxLevel 4 -> levels 0..4
-constexpr int LK_WIN = 32;
+constexpr int LK_WIN = 32;       // the window k_lk / k_lk_batch are built around, and the default of pmv_set_lk_params
 
 struct PyrLayout {
     int n_levels;                 // levels actually built = maxLevel + 1
@@ -152,6 +152,8 @@ struct LKParams {
     double eps2d;     // epsilon^2 = 1e-4
     float min_eig;    // 1e-4
     unsigned long long* stamps;   // optional (diagnostic): 16 shader-clock phase timers accumulated by the block of track 0
+    int win;          // square window side (pmv_set_lk_params); k_lk / k_lk_batch are built for LK_WIN and serve only that
+    int general;      // diagnostic (pmv_debug_lk_general): the general kernels also at win == LK_WIN
 };
 
 // one workgroup of k_lk_batch: everything it needs to start in ONE 32-byte record (the records sit in mapped pinned host memory: a wave's
