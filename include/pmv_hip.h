@@ -16,6 +16,8 @@
  *   pmv_pnp_ransac                         cv::solvePnPRansac                            (OpenCVEPnPSolver.cpp:35-36) -> BasePnPSolver.h:19
  *   pmv_fivepoint_hypotheses               cv::findEssentialMat (RANSAC hypotheses)      (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
  *   pmv_triangulate_candidates             cv::recoverPose (triangulation + cheirality)  (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
+ *   pmv_find_essential_mat                 cv::findEssentialMat (the whole RANSAC)       (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
+ *   pmv_recover_pose                       cv::recoverPose (the whole call)              (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_ba_residuals / pmv_ba_solve        ProjectionResidual + ceres::Solve             (ProjectionResidual.h:38-58,
  *                                          CeresBundleAdjustment.cpp:50-61)              -> BaseOptimizer.h:15
  *
@@ -246,6 +248,31 @@ int pmv_triangulate_candidates(pmv_ctx* ctx, const double* q1, const double* q2,
 int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
                                      double* out_Q, uint8_t* out_mask, int* out_good);
 
+/* ---- the two calls of the triangulator, whole (OpenCVFivePointTri.cpp:24-27) ------------------------------------------------------------
+ * cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold, mask) (OpenCVFivePointTri.cpp:24). p1_xy, p2_xy: n pixel coordinates
+ * (x, y) as doubles; K: 9 doubles, row-major; E9 row-major; mask n bytes; *out_samples_drawn = RANSAC iterations made. *out_found 0 = no
+ * model (cv returns an empty Mat): E9 untouched, mask all 0. The whole adaptive RANSAC - cv::RNG((uint64)-1) sample stream, Nister's
+ * solver per sample, float32 Sampson scoring, best-so-far and RANSACUpdateNumIters, at most 1000 iterations - runs in ONE launch, one
+ * workgroup per call (k_essential_ransac); the result has the bits of the host code behind pmv_pipeline_run (device_fivepoint = 0).
+ *   n: 0 <= n <= max_tracks, else PMV_ERR_CAPACITY. n < 5: no model (nothing is launched); n == 5: one solve without RANSAC, the first
+ *   model wins, mask all 1, 0 samples drawn. Null pointers, prob outside [0, 1], a non-positive or non-finite threshold: PMV_ERR_INVALID.
+ *   On an error no output is written. Not logged by pmv_record_enable. */
+int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                           double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+/* cv::recoverPose(E, points1, points2, K, R, t, HUGE_VAL, mask, triangulatedPoints) (OpenCVFivePointTri.cpp:27): decomposeEssentialMat on
+ * the host, the four (R, t) candidates through the DLT kernel of pmv_triangulate_candidates (logged by pmv_record_enable as that call's DLT
+ * record), the candidate choice of cv::recoverPose. mask is in/out: n bytes, the inlier mask of pmv_find_essential_mat going in, the
+ * winning candidate's mask coming out; R9 row-major, t3 of unit length; tri4n: 4 x n homogeneous points, row-major (row k = coordinate k
+ * of every point); *out_good: the winning candidate's count. n: 0 <= n <= max_tracks, else PMV_ERR_CAPACITY; null pointers:
+ * PMV_ERR_INVALID; on an error no output is written. */
+int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
+                     uint8_t* mask, double* tri4n, int* out_good);
+/* diagnostic, ctx-free: how pmv_find_essential_mat splits RANSACUpdateNumIters(prob, (n - g) / n, 5, maxIters) between host and device for a
+ * call with n points. The host's libm gives *out_num = log(1 - prob) and, per inlier count g = 0..n, out_denoms[g] = log(1 - (1 - (n - g) /
+ * n)^5) (n + 1 doubles; -infinity where the function returns 0 before its logarithms); the kernel evaluates only the final expression
+ * `denom >= 0 || -num >= maxIters * (-denom) ? maxIters : lrint(num / denom)`. n < 0 or a null pointer: PMV_ERR_INVALID. */
+int pmv_debug_essential_iters_table(int n, double prob, double* out_denoms, double* out_num);
+
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those
  * made from inside pmv_pipeline_run) appends one blob holding its inputs and outputs, so that a test can replay the calls
@@ -287,7 +314,8 @@ typedef struct pmv_pipeline_params {
     int n_threads;      /* host threads that evaluate the triangulator's five-point RANSAC hypotheses side by side (>= 1; results do not depend on it) */
     int build_pyramids; /* rebuild the pyramids of slots 0..n_frames-1 inside the call */
     int matcher;        /* 0 = pyramidal LK (reference default), 1 = kNNFeatureMatcher over `extractor` */
-    int device_fivepoint; /* 0 = five-point RANSAC hypotheses on host threads, 1 = on the GPU (pmv_fivepoint_hypotheses); same results */
+    int device_fivepoint; /* 0 = five-point RANSAC on host threads, 1 = its hypotheses on the GPU, one launch per round of 32 (pmv_fivepoint_hypotheses),
+                           * 2 = the whole RANSAC of a call in one launch (pmv_find_essential_mat); same results, [23] included */
 } pmv_pipeline_params;
 typedef struct pmv_pipeline_result pmv_pipeline_result;
 
@@ -430,6 +458,17 @@ int pmv_batch_triangulate_candidates(pmv_ctx* ctx, int seq, const double* q1, co
                                      double* out_Q, uint8_t* out_mask, int* out_good);
 int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
                                    double* models, int* n_models, int* counts);
+/* The triangulator's two calls for a seq, argument for argument (rules above: the no-model convention, 0 <= n <= max_tracks else
+ * PMV_ERR_CAPACITY, mask in/out of pmv_recover_pose) with `seq` (0 .. n_seq - 1, else PMV_ERR_INVALID) after the context; the bits of the
+ * single calls. The five-point combiner serves a round of pmv_batch_find_essential_mat requests with ONE k_essential_ransac launch, one
+ * workgroup per request, and a call returns as soon as ITS request is complete (the workgroup's last store is the request's completion
+ * word): it does not wait for the slowest request of its round. One outstanding call per seq and call: the seq's next call may come at
+ * once, also while the round it left is still running - it waits inside the library until that round has released the seq's request
+ * record. pmv_batch_recover_pose is a request of the DLT combiner. */
+int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                                 double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
+                           uint8_t* mask, double* tri4n, int* out_good);
 /* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds, and the
  * pyrDown launches are the sum over the rounds of the levels above 0 of each round's tallest pyramid. */
 int pmv_batch_upload_stats(pmv_ctx* ctx, long long* out4);

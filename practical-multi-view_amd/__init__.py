@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_lk_track", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
+    "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -49,6 +50,7 @@ ABI_SYMBOLS = [
     "pmv_batch_open", "pmv_batch_close", "pmv_batch_frame_upload", "pmv_batch_upload_stats", "pmv_batch_upload_rounds",
     "pmv_batch_lk_track", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
     "pmv_batch_pnp_ransac", "pmv_batch_ba_solve", "pmv_batch_triangulate_candidates", "pmv_batch_fivepoint_hypotheses",
+    "pmv_batch_find_essential_mat", "pmv_batch_recover_pose",
 ]
 
 
@@ -592,6 +594,44 @@ class Context:
                                                      _p(Q, _f64p), _p(mask, _u8p), _p(good, _i32p)))
         return Q, mask, good
 
+    @staticmethod
+    def _two_view_args(p1, p2, K):
+        p1 = np.ascontiguousarray(p1, np.float64).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float64).reshape(-1, 2)
+        if p1.shape != p2.shape:
+            raise ValueError(f"p1 {p1.shape} and p2 {p2.shape}: one (x, y) pair per correspondence in each")
+        return p1, p2, np.ascontiguousarray(K, np.float64).reshape(9)
+
+    def _find_essential(self, call, ck, head, p1, p2, K, prob, threshold):
+        p1, p2, Kd = self._two_view_args(p1, p2, K)
+        n = p1.shape[0]
+        E = np.zeros(9, np.float64)
+        mask = np.zeros(n, np.uint8)
+        found, drawn = C.c_int(), C.c_int()
+        ck(call(self.h, *head, _p(p1, _f64p), _p(p2, _f64p), n, _p(Kd, _f64p), C.c_double(prob), C.c_double(threshold), _p(E, _f64p), _p(mask, _u8p),
+                C.byref(found), C.byref(drawn)))
+        return bool(found.value), E.reshape(3, 3), mask, drawn.value
+
+    def _recover_pose(self, call, ck, head, E, p1, p2, K, mask):
+        p1, p2, Kd = self._two_view_args(p1, p2, K)
+        n = p1.shape[0]
+        Ed = np.ascontiguousarray(E, np.float64).reshape(9)
+        m = np.array(mask, np.uint8).reshape(n).copy()
+        R, t, tri = np.zeros(9, np.float64), np.zeros(3, np.float64), np.zeros((4, n), np.float64)
+        good = C.c_int()
+        ck(call(self.h, *head, _p(Ed, _f64p), _p(p1, _f64p), _p(p2, _f64p), n, _p(Kd, _f64p), _p(R, _f64p), _p(t, _f64p), _p(m, _u8p), _p(tri, _f64p),
+                C.byref(good)))
+        return R.reshape(3, 3), t, m, tri, good.value
+
+    def find_essential_mat(self, p1, p2, K, prob=0.99, threshold=1.0):
+        """cv::findEssentialMat(p1, p2, K, RANSAC, prob, threshold, mask), the whole RANSAC in one launch: (found, E (3, 3), mask (n,), samples drawn);
+        found False = no model (E zeros, mask all 0)"""
+        return self._find_essential(self.lib.pmv_find_essential_mat, self._ck, (), p1, p2, K, prob, threshold)
+
+    def recover_pose(self, E, p1, p2, K, mask):
+        """cv::recoverPose(E, p1, p2, K, R, t, HUGE_VAL, mask, tri): (R (3, 3), t (3,), mask out (n,), tri (4, n) homogeneous, good)"""
+        return self._recover_pose(self.lib.pmv_recover_pose, self._ck, (), E, p1, p2, K, mask)
+
     # ---- call log (teacher-forced replay) ----
     def record_enable(self, on=True):
         self._ck(self.lib.pmv_record_enable(self.h, 1 if on else 0))
@@ -929,3 +969,10 @@ class Context:
         self._ckt(self.lib.pmv_batch_fivepoint_hypotheses(self.h, int(seq), _p(q1, _f64p), _p(q2, _f64p), q1.shape[0], _p(s, _i32p), nh, C.c_float(thr),
                                                          _p(models, _f64p), _p(nm, _i32p), _p(counts, _i32p)))
         return models, nm, counts
+
+    def batch_find_essential_mat(self, seq, p1, p2, K, prob=0.99, threshold=1.0):
+        """find_essential_mat for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""
+        return self._find_essential(self.lib.pmv_batch_find_essential_mat, self._ckt, (int(seq),), p1, p2, K, prob, threshold)
+
+    def batch_recover_pose(self, seq, E, p1, p2, K, mask):
+        return self._recover_pose(self.lib.pmv_batch_recover_pose, self._ckt, (int(seq),), E, p1, p2, K, mask)

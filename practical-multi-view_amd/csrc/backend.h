@@ -26,6 +26,8 @@ struct BackendBuffers {
     double* d_bapart = nullptr;
     char *d_tri_in = nullptr, *d_tri_out = nullptr;
     char* d_fp_work = nullptr;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in)
+    char* d_ess_in = nullptr;    // whole findEssentialMat RANSAC: [EssentialProblem 64 B | q1 2n | q2 2n | iteration table n + 2 doubles]
+    size_t ess_in_bytes = 0;
     char* d_h_stage = nullptr;   // device address of the pinned staging block: result blocks are written straight into it
     size_t tri_in_bytes = 0, tri_out_bytes = 0;
     // single-copy transfers: one pinned staging block and one device block per direction
@@ -102,6 +104,20 @@ struct FivePointProblem {
 };
 constexpr int FP_MAX_HYP = 64;   // hypotheses per round
 hipError_t launch_fivepoint_batch(hipStream_t s, const FivePointProblem* d_probs, int n_probs, int max_hyp);
+// one whole cv::findEssentialMat RANSAC (k_essential_ransac, backend_fivepoint.hip): one workgroup runs the adaptive loop of one request
+struct EssentialProblem {
+    const double* q1; const double* q2;   // device: n normalised points (x, y) each
+    const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^5), -inf where RANSACUpdateNumIters returns 0]
+    char* out;                            // mapped pinned result block: [E 9 doubles | at byte 80: found, samples drawn, best count, done_seq | at byte 128: mask n bytes]
+    int n, max_iters; float thr;
+    unsigned done_seq;                    // != 0; the kernel's last store, into the fourth word at byte 80 (the caller waits for it)
+};
+constexpr size_t ESS_HDR = 64, ESS_OUT_HDR = 128;   // bytes: the record in front of a request's input block / the result block in front of the mask
+static_assert(sizeof(EssentialProblem) <= ESS_HDR, "the record is the header of the input block");
+constexpr int ESS_MAX_WAVES = 16;   // hypotheses per in-kernel round at most (wavefronts of the workgroup)
+constexpr int ESS_DEFAULT_WAVES = 8;   // R of DESIGN.md §4: 8 x 6.2 KB = 49 KB of LDS, three workgroups per CU
+int essential_round_width();        // hypotheses per in-kernel round (PMV_ESSENTIAL_R overrides the default, 1..ESS_MAX_WAVES)
+hipError_t launch_essential_ransac(hipStream_t s, const EssentialProblem* d_probs, int n_probs);
 // one two-view problem of a batched DLT launch
 struct DltProblem { const double* P1x4; const double* q1; const double* q2; const uint8_t* mask_in; double* Q; uint8_t* mask; int n; };
 hipError_t launch_tri_dlt_batch(hipStream_t s, const DltProblem* d_probs, int n_probs, int max_n);
@@ -131,6 +147,17 @@ void ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, double* pt
 int fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
                       FivePointProblem* P, size_t* in_bytes);
 void fivepoint_finish(BackendBuffers* b, int n_hyp, size_t in_bytes, double* models, int* n_models, int* counts);
+// whole findEssentialMat: argument rules of pmv_find_essential_mat (outputs untouched on error); prepare normalises the points into b's pinned
+// block behind the problem record, builds the iteration table with the host's libm and clears the completion word; finish reads the result block
+int essential_check(pmv_ctx* ctx, const char* who, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                    double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+void essential_prepare(BackendBuffers* b, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                       EssentialProblem* P, size_t* in_bytes);
+volatile unsigned* essential_done_word(BackendBuffers* b, size_t in_bytes);
+void essential_finish(BackendBuffers* b, int n, size_t in_bytes, double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+// cv::recoverPose around a DLT launch: `dlt` is pmv_triangulate_candidates' contract on the caller's workspace set; PMV_OK or its error
+int recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
+                       double* t3, uint8_t* mask, double* tri4n, int* out_good);
 void dlt_prepare(BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
                  size_t* in_bytes);
 void dlt_finish(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,

@@ -1,6 +1,8 @@
 // C-ABI entry points of the back-end stream: pmv_pnp_ransac, pmv_ba_residuals, pmv_ba_solve (include/pmv_hip.h).
 #include "pmv_ctx.h"
 #include "backend.h"
+#include "vo_pipeline.h"
+#include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -63,9 +65,12 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
     CKB(hipMalloc(&b->d_tri_in, b->tri_in_bytes));
     CKB(hipMalloc(&b->d_tri_out, b->tri_out_bytes));
     CKB(hipMalloc(&b->d_fp_work, (size_t)FP_MAX_HYP * (90 * 8 + 4) + 64));
+    b->ess_in_bytes = ESS_HDR + (5 * mt + 2) * 8 + 64;
+    CKB(hipMalloc(&b->d_ess_in, b->ess_in_bytes));
     b->h_stage_bytes = std::max(b->h_stage_bytes, std::max(b->ba_io_bytes, b->pnp_in_bytes + b->pnp_out_bytes));
     b->h_stage_bytes = std::max(b->h_stage_bytes, b->tri_in_bytes + b->tri_out_bytes);
     b->h_stage_bytes = std::max(b->h_stage_bytes, b->tri_in_bytes + (size_t)FP_MAX_HYP * (90 * 8 + 44) + 256);   // five-point round in + out
+    b->h_stage_bytes = std::max(b->h_stage_bytes, b->ess_in_bytes + ESS_OUT_HDR + mt + 64);   // whole findEssentialMat in + out
     (void)hipHostFree(b->h_stage);
     CKB(hipHostMalloc(&b->h_stage, b->h_stage_bytes, hipHostMallocMapped | hipHostMallocCoherent));
     CKB(hipHostGetDevicePointer((void**)&b->d_h_stage, b->h_stage, 0));
@@ -73,7 +78,7 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
         const void* must[] = {b->d_x, b->d_cand, b->d_scale, b->d_diag, b->d_D2, b->d_step, b->d_res, b->d_J, b->d_Einv, b->d_gp, b->d_Yd, b->d_Wd,
                               b->d_S, b->d_rhs, b->d_Gpart, b->d_summary, b->d_stamps, b->d_bastate, b->d_bapart, b->d_counts, b->d_inliers,
                               b->d_info, b->d_models, b->d_rt, b->d_masks, b->d_ba_io, b->d_pnp_in, b->d_pnp_out, b->d_tri_in, b->d_tri_out,
-                              b->h_stage, b->d_h_stage};
+                              b->d_fp_work, b->d_ess_in, b->h_stage, b->d_h_stage};
         for (const void* p : must)
             if (!p) { set_err(c, "backend_create: internal error, a back-end buffer was not allocated"); return PMV_ERR_HIP; }
     }
@@ -88,7 +93,7 @@ void backend_free(BackendBuffers* b) {
                     b->d_cobs_list, b->d_x, b->d_cand, b->d_scale, b->d_diag, b->d_D2, b->d_step, b->d_res, b->d_J, b->d_Einv, b->d_gp,
                     b->d_Yd, b->d_Wd, b->d_S, b->d_rhs, b->d_Gpart, b->d_summary, b->d_obj, b->d_img, b->d_samples, b->d_counts,
                     b->d_inliers, b->d_info, b->d_models, b->d_rt, b->d_Kp, b->d_masks, b->d_ba_io, b->d_pnp_in, b->d_pnp_out, b->d_bastate, b->d_bapart, b->d_tri_in, b->d_tri_out,
-                    b->d_fp_work};
+                    b->d_fp_work, b->d_ess_in};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (b->d_stamps) (void)hipFree(b->d_stamps);
     if (b->h_stage) (void)hipHostFree(b->h_stage);
@@ -668,6 +673,128 @@ int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const doubl
         CKC(hipStreamCreateWithFlags(&ctx->s_ahead, hipStreamNonBlocking));
     }
     return triangulate_on(ctx, ctx->be_ahead, ctx->s_ahead, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+}
+
+}  // extern "C"
+
+// ---- whole findEssentialMat RANSAC on the device (k_essential_ransac): check / prepare / finish -----------------------------------------
+int pmv::essential_check(pmv_ctx* ctx, const char* who, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                         double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    REQ(ctx && p1_xy && p2_xy && K && E9 && mask && out_found && out_samples_drawn, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(prob >= 0 && prob <= 1, PMV_ERR_INVALID, "%s: prob = %g outside [0, 1]", who, prob);
+    REQ(threshold > 0 && std::isfinite(threshold), PMV_ERR_INVALID, "%s: threshold = %g (a positive finite number of pixels)", who, threshold);
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, ctx->max_tracks);
+    return PMV_OK;
+}
+// pinned in-block [EssentialProblem (ESS_HDR bytes) | q1 2n | q2 2n | log(1 - prob), n + 1 denominators], out-block [E 9 | .. | info at 80 | mask at 128]
+void pmv::essential_prepare(BackendBuffers* b, const double* p1, const double* p2, int n, const double* K, double prob, double threshold,
+                            EssentialProblem* P, size_t* in_bytes_out) {
+    char* hs = (char*)b->h_stage;
+    double* h_q1 = (double*)(hs + ESS_HDR);
+    double* h_q2 = h_q1 + (size_t)2 * n;
+    double* h_it = h_q2 + (size_t)2 * n;
+    const size_t in_bytes = ESS_HDR + ((size_t)5 * n + 2) * 8;
+    // the normalisation of vo_fivepoint.cpp:find_essential_mat, expression for expression
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    for (int i = 0; i < n; i++) {
+        h_q1[2 * i] = (p1[2 * i] - cx) / fx; h_q1[2 * i + 1] = (p1[2 * i + 1] - cy) / fy;
+        h_q2[2 * i] = (p2[2 * i] - cx) / fx; h_q2[2 * i + 1] = (p2[2 * i + 1] - cy) / fy;
+    }
+    threshold /= (fx + fy) / 2;
+    vo::five_point_iters_table(n, prob, h_it + 1, h_it);
+    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
+    P->q1 = (const double*)(b->d_ess_in + ESS_HDR);
+    P->q2 = P->q1 + (size_t)2 * n;
+    P->iters = P->q2 + (size_t)2 * n;
+    P->out = b->d_h_stage + (ho - hs);
+    P->n = n; P->max_iters = 1000;
+    P->thr = (float)(threshold * threshold);
+    if (++b->done_seq == 0) b->done_seq = 1;
+    P->done_seq = b->done_seq;
+    *(volatile unsigned*)(ho + 92) = 0;
+    *(EssentialProblem*)hs = *P;
+    *in_bytes_out = in_bytes;
+}
+volatile unsigned* pmv::essential_done_word(BackendBuffers* b, size_t in_bytes) {
+    return (volatile unsigned*)((char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63) + 92);
+}
+void pmv::essential_finish(BackendBuffers* b, int n, size_t in_bytes, double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    const char* ho = (const char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63);
+    const int* info = (const int*)(ho + 80);
+    *out_found = info[0]; *out_samples_drawn = info[1];
+    if (info[0]) memcpy(E9, ho, 72);
+    memcpy(mask, ho + ESS_OUT_HDR, (size_t)n);
+}
+int pmv::recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
+                            double* t3, uint8_t* mask, double* tri4n, int* out_good) {
+    REQ(ctx && E9 && p1_xy && p2_xy && K && R9 && t3 && mask && tri4n && out_good, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, ctx->max_tracks);
+    return PMV_OK;
+}
+
+extern "C" {
+
+int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
+                           uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    if (const int rc = essential_check(ctx, "pmv_find_essential_mat", p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn)) return rc;
+    *out_found = 0; *out_samples_drawn = 0;
+    if (n < 5) { memset(mask, 0, (size_t)n); return PMV_OK; }   // fewer points than a sample: no model
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    BackendBuffers* b = ctx->be;
+    hipStream_t s = ctx->s_back;
+    EssentialProblem P;
+    size_t in_bytes = 0;
+    essential_prepare(b, p1_xy, p2_xy, n, K, prob, threshold, &P, &in_bytes);
+    const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
+    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->d_h_stage, (uint4*)b->d_ess_in, n16);
+    CKC(hipGetLastError());
+    CKC(launch_essential_ransac(s, (const EssentialProblem*)b->d_ess_in, 1));
+    // the kernel's last store is this call's sequence number in the result block (PMV_BACK_WAIT=sync: hipStreamSynchronize instead; see pmv_pnp_ransac)
+    static const bool flag_wait = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
+    if (flag_wait) {
+        volatile unsigned* done_word = essential_done_word(b, in_bytes);
+        (void)hipStreamQuery(s);
+        for (unsigned spins = 1;; spins++) {
+            if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == P.done_seq) break;
+            if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
+                const hipError_t e = hipStreamQuery(s);
+                if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
+            }
+            __builtin_ia32_pause();
+        }
+    } else CKC(hipStreamSynchronize(s));
+    essential_finish(b, n, in_bytes, E9, mask, out_found, out_samples_drawn);
+    return PMV_OK;
+}
+
+int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3, uint8_t* mask,
+                     double* tri4n, int* out_good) {
+    if (const int rc = recover_pose_check(ctx, "pmv_recover_pose", E9, p1_xy, p2_xy, n, K, R9, t3, mask, tri4n, out_good)) return rc;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    struct Tri : vo::FivePointTri {   // the host half of cv::recoverPose (vo_fivepoint.cpp:recover_pose) around the context's DLT kernel
+        pmv_ctx* ctx; int rc = PMV_OK;
+        void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q, uint8_t* out_mask, int* out_good) override {
+            if (n > 0) rc = triangulate_on(ctx, ctx->be, ctx->s_back, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+        }
+    } tri;
+    tri.ctx = ctx;
+    std::vector<uint8_t> m(mask, mask + n);
+    std::vector<double> q;
+    double R[9], t[3];
+    const int good = vo::recover_pose(&tri, E9, p1_xy, p2_xy, n, K, R, t, m, q);
+    if (tri.rc != PMV_OK) return tri.rc;
+    memcpy(R9, R, 72); memcpy(t3, t, 24);
+    if (n > 0) { memcpy(mask, m.data(), (size_t)n); memcpy(tri4n, q.data(), (size_t)4 * n * 8); }
+    *out_good = good;
+    return PMV_OK;
+}
+
+int pmv_debug_essential_iters_table(int n, double prob, double* out_denoms, double* out_num) {
+    if (n < 0 || !out_denoms || !out_num) return PMV_ERR_INVALID;
+    vo::five_point_iters_table(n, prob, out_denoms, out_num);
+    return PMV_OK;
 }
 
 }  // extern "C"

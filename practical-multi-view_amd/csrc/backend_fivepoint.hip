@@ -10,11 +10,14 @@
 // both uses. The kernel exists as the measurement behind that statement and as the bit-exact device form of §8f #1.
 // k_fivepoint_score: Sampson error of every model on every correspondence (float32, <= thr) -> inlier counts; the sequential
 // RANSAC bookkeeping (best-so-far, adaptive iteration count) is replayed by the host in sample order, as for PnP.
+// k_essential_ransac: the whole adaptive RANSAC of one findEssentialMat call in one workgroup (sampling, the same solver, scoring and the
+// bookkeeping inside the kernel) - no host round trip per round, and a batched round no longer ends every request with its slowest one.
 #include "pmv_ctx.h"
 #include "backend.h"
 #include "pmv_prof.h"
 #include "pmv_dense.h"
 #include <float.h>
+#include <cstdlib>
 
 namespace pmv {
 
@@ -326,6 +329,16 @@ __global__ __launch_bounds__(64) void k_fivepoint_hyp(const FivePointProblem* __
     for (int k = 0; k < nm * 9; k++) { P.models_d[(size_t)h * 90 + k] = E[k]; P.models_h[(size_t)h * 90 + k] = E[k]; }
 }
 
+// EMEstimatorCallback::computeError of correspondence i: the Sampson distance as float32 (vo_fivepoint.cpp:sampson_errors)
+__device__ inline float fp_sampson(const double* E, const double* __restrict__ q1, const double* __restrict__ q2, int i) {
+    const double x1[3] = {q1[2 * i], q1[2 * i + 1], 1.}, x2[3] = {q2[2 * i], q2[2 * i + 1], 1.};
+    const double Ex1[3] = {E[0] * x1[0] + E[1] * x1[1] + E[2] * x1[2], E[3] * x1[0] + E[4] * x1[1] + E[5] * x1[2], E[6] * x1[0] + E[7] * x1[1] + E[8] * x1[2]};
+    const double Etx2[3] = {E[0] * x2[0] + E[3] * x2[1] + E[6] * x2[2], E[1] * x2[0] + E[4] * x2[1] + E[7] * x2[2], E[2] * x2[0] + E[5] * x2[1] + E[8] * x2[2]};
+    const double x2tEx1 = x2[0] * Ex1[0] + x2[1] * Ex1[1] + x2[2] * Ex1[2];
+    const double a = Ex1[0] * Ex1[0], b = Ex1[1] * Ex1[1], c = Etx2[0] * Etx2[0], d = Etx2[1] * Etx2[1];
+    return (float)(x2tEx1 * x2tEx1 / (a + b + c + d));
+}
+
 // EMEstimatorCallback::computeError (Sampson distance stored as float32) + inlier count per (hypothesis, model): one wavefront each
 __global__ __launch_bounds__(64) void k_fivepoint_score(const FivePointProblem* __restrict__ probs) { BACKEND_PRIO();
     const FivePointProblem P = probs[blockIdx.z];
@@ -336,18 +349,173 @@ __global__ __launch_bounds__(64) void k_fivepoint_score(const FivePointProblem* 
     for (int k = 0; k < 9; k++) E[k] = P.models_d[(size_t)h * 90 + mi * 9 + k];
     int good = 0;
     #pragma unroll 1
-    for (int i = threadIdx.x; i < P.n; i += 64) {
-        const double x1[3] = {P.q1[2 * i], P.q1[2 * i + 1], 1.}, x2[3] = {P.q2[2 * i], P.q2[2 * i + 1], 1.};
-        const double Ex1[3] = {E[0] * x1[0] + E[1] * x1[1] + E[2] * x1[2], E[3] * x1[0] + E[4] * x1[1] + E[5] * x1[2], E[6] * x1[0] + E[7] * x1[1] + E[8] * x1[2]};
-        const double Etx2[3] = {E[0] * x2[0] + E[3] * x2[1] + E[6] * x2[2], E[1] * x2[0] + E[4] * x2[1] + E[7] * x2[2], E[2] * x2[0] + E[5] * x2[1] + E[8] * x2[2]};
-        const double x2tEx1 = x2[0] * Ex1[0] + x2[1] * Ex1[1] + x2[2] * Ex1[2];
-        const double a = Ex1[0] * Ex1[0], b = Ex1[1] * Ex1[1], c = Etx2[0] * Etx2[0], d = Etx2[1] * Etx2[1];
-        const float err = (float)(x2tEx1 * x2tEx1 / (a + b + c + d));
-        good += err <= P.thr;
-    }
+    for (int i = threadIdx.x; i < P.n; i += 64) good += fp_sampson(E, P.q1, P.q2, i) <= P.thr;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) good += __shfl_xor(good, o, 64);
     if (threadIdx.x == 0) P.counts_h[h * 10 + mi] = good;
+}
+
+// ---- the whole adaptive RANSAC of one cv::findEssentialMat call in ONE workgroup (pmv_find_essential_mat) ---------------------------------
+// R wavefronts = R hypotheses per in-kernel round. A round: thread 0 draws the next min(R, niters - iter) 5-subsets from the request's MWC
+// stream (vo_fivepoint.cpp:draw_subset, integer arithmetic); lane 0 of wave w solves hypothesis w with fp_essentials on the wave's own FP_WS
+// doubles of LDS; all waves score the round's (hypothesis, model) pairs (the k_fivepoint_score expression, wave-reduced counts); thread 0
+// replays find_essential_mat's bookkeeping in sample order - count > max(maxGood, 4), best E, maxGood, the niters update - and drops the
+// speculative samples past niters. No host round trip per round, and a request is over when ITS loop is: the last store of the workgroup
+// is the request's sequence number in its mapped pinned result block, which is what its caller waits for.
+// RANSACUpdateNumIters calls pow and log; the device's libm is not glibc's, so the host tabulates both per inlier count (EssentialProblem::iters)
+// and the kernel evaluates only the final expression: IEEE multiply, divide, compare, round-half-even.
+struct EssShared {
+    double best[9];
+    unsigned long long rng;
+    int idx[ESS_MAX_WAVES * 5], nm[ESS_MAX_WAVES], counts[ESS_MAX_WAVES * 10];
+    int iter, niters, max_good, drawn;
+};
+__device__ inline int ess_update_iters(const double* __restrict__ tab, int good, int max_iters) {
+    const double num = tab[0], denom = tab[1 + good];
+    return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
+}
+__device__ inline unsigned ess_rng_next(unsigned long long& st) { st = (unsigned long long)(unsigned)st * 4164903690U + (unsigned)(st >> 32); return (unsigned)st; }
+
+__global__ __launch_bounds__(64 * ESS_MAX_WAVES) void k_essential_ransac(const EssentialProblem* __restrict__ probs) { BACKEND_PRIO();
+    extern __shared__ double ess_lds[];   // R solver workspaces of FP_WS doubles, then EssShared
+    const int R = (int)(blockDim.x >> 6), tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const EssentialProblem P = probs[blockIdx.x];
+    double* ws = ess_lds + wave * FP_WS;
+    EssShared& sh = *(EssShared*)(ess_lds + R * FP_WS);
+    const int n = P.n;
+    if (tid == 0) { sh.iter = 0; sh.niters = P.max_iters; sh.max_good = 0; sh.drawn = 0; sh.rng = ~0ull; }
+    __syncthreads();
+    if (n == 5) {   // one solve without RANSAC: the first model wins, every point is an inlier
+        if (tid == 0) {
+            double* s1 = ws + 750; double* s2 = ws + 760;
+            #pragma unroll 1
+            for (int k = 0; k < 10; k++) { s1[k] = P.q1[k]; s2[k] = P.q2[k]; }
+            const int nm = fp_essentials(s1, s2, ws + 660, ws);
+            if (nm > 0) {
+                #pragma unroll 1
+                for (int k = 0; k < 9; k++) sh.best[k] = ws[660 + k];
+                sh.max_good = 5;
+            }
+        }
+        __syncthreads();
+    } else {
+        for (;;) {
+            const int iter = sh.iter, niters = sh.niters;   // (written by thread 0 before the barrier that ended the previous round)
+            if (iter >= niters) break;
+            const int nb = min(R, niters - iter);
+            if (tid == 0) {
+                unsigned long long st = sh.rng;
+                #pragma unroll 1
+                for (int b = 0; b < nb; b++) {
+                    int* idx = sh.idx + 5 * b;
+                    #pragma unroll 1
+                    for (int i = 0; i < 5;) {
+                        const int v = (int)(ess_rng_next(st) % (unsigned)n);
+                        idx[i] = v;
+                        int j = 0;
+                        #pragma unroll 1
+                        for (; j < i; j++) if (v == idx[j]) break;
+                        if (j == i) i++;
+                    }
+                }
+                sh.rng = st;
+            }
+            __syncthreads();
+            if (lane == 0) {
+                int nm = 0;
+                if (wave < nb) {
+                    double* s1 = ws + 750; double* s2 = ws + 760;
+                    #pragma unroll 1
+                    for (int i = 0; i < 5; i++) {
+                        const int k = sh.idx[5 * wave + i];
+                        s1[2 * i] = P.q1[2 * k]; s1[2 * i + 1] = P.q1[2 * k + 1];
+                        s2[2 * i] = P.q2[2 * k]; s2[2 * i + 1] = P.q2[2 * k + 1];
+                    }
+                    nm = fp_essentials(s1, s2, ws + 660, ws);
+                }
+                sh.nm[wave] = nm;
+            }
+            __syncthreads();
+            #pragma unroll 1
+            for (int p = wave; p < nb * 10; p += R) {
+                const int b = p / 10, mi = p - 10 * b;
+                if (mi >= sh.nm[b]) continue;   // (uniform over the wave)
+                const double* Em = ess_lds + b * FP_WS + 660 + 9 * mi;
+                double E[9];
+#pragma unroll
+                for (int k = 0; k < 9; k++) E[k] = Em[k];
+                int good = 0;
+                #pragma unroll 1
+                for (int i = lane; i < n; i += 64) good += fp_sampson(E, P.q1, P.q2, i) <= P.thr;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) good += __shfl_xor(good, o, 64);
+                if (lane == 0) sh.counts[p] = good;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int it = iter, ni = niters, mg = sh.max_good;
+                #pragma unroll 1
+                for (int b = 0; b < nb && it < ni; b++, it++) {
+                    #pragma unroll 1
+                    for (int mi = 0; mi < sh.nm[b]; mi++) {
+                        const int c = sh.counts[10 * b + mi];
+                        if (c > max(mg, 4)) {
+                            const double* Em = ess_lds + b * FP_WS + 660 + 9 * mi;
+                            #pragma unroll 1
+                            for (int k = 0; k < 9; k++) sh.best[k] = Em[k];
+                            mg = c;
+                            ni = ess_update_iters(P.iters, mg, ni);
+                        }
+                    }
+                }
+                sh.drawn += it - iter;
+                sh.iter = it; sh.niters = ni; sh.max_good = mg;
+            }
+            __syncthreads();
+        }
+    }
+    // result block: mask of the best model (err <= thr, recomputed once), E, found, samples drawn; the sequence number last
+    const bool found = sh.max_good > 0;
+    uint8_t* mask = (uint8_t*)(P.out + ESS_OUT_HDR);
+    if (found && n > 5) {
+        double E[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) E[k] = sh.best[k];
+        #pragma unroll 1
+        for (int i = tid; i < n; i += (int)blockDim.x) mask[i] = (uint8_t)(fp_sampson(E, P.q1, P.q2, i) <= P.thr);
+    } else {
+        #pragma unroll 1
+        for (int i = tid; i < n; i += (int)blockDim.x) mask[i] = found ? 1 : 0;
+    }
+    if (tid == 0) {
+        double* Eo = (double*)P.out;
+        #pragma unroll 1
+        for (int k = 0; k < 9; k++) Eo[k] = found ? sh.best[k] : 0.0;
+        int* info = (int*)(P.out + 80);
+        info[0] = found ? 1 : 0; info[1] = sh.drawn; info[2] = sh.max_good;
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store((unsigned*)(P.out + 92), P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+int essential_round_width() {
+    static const int R = [] { const char* e = getenv("PMV_ESSENTIAL_R"); const int r = e ? atoi(e) : ESS_DEFAULT_WAVES; return r < 1 ? 1 : r > ESS_MAX_WAVES ? ESS_MAX_WAVES : r; }();
+    return R;
+}
+
+hipError_t launch_essential_ransac(hipStream_t s, const EssentialProblem* d_probs, int n_probs) {
+    if (n_probs <= 0) return hipSuccess;
+    if (!d_probs) return hipErrorInvalidValue;
+    const int R = essential_round_width();
+    const size_t lds = (size_t)R * FP_WS * sizeof(double) + sizeof(EssShared);
+    if (lds > 64 * 1024) {   // (above the default limit of a workgroup; the CU has 160 KiB)
+        static const hipError_t attr = hipFuncSetAttribute((const void*)k_essential_ransac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)ESS_MAX_WAVES * FP_WS * sizeof(double) + sizeof(EssShared)));
+        if (attr != hipSuccess) return attr;
+    }
+    ProfScope ps(K_FIVEPOINT, s);
+    hipLaunchKernelGGL(k_essential_ransac, dim3(n_probs), dim3(64 * R), lds, s, d_probs);
+    return hipGetLastError();
 }
 
 hipError_t launch_fivepoint_batch(hipStream_t s, const FivePointProblem* d_probs, int n_probs, int max_hyp) {

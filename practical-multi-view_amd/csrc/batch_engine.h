@@ -34,4 +34,8 @@ int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int 
                uint8_t* out_mask, int* out_good);
 int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
                      int* n_models, int* counts);
+// pmv_find_essential_mat's contract: one workgroup of the round's k_essential_ransac launch; returns when the request's own completion word is
+// seen (or, after a failed launch, with the combiner's error), which may be before the round's launch ends
+int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
+                     uint8_t* mask, int* out_found, int* out_samples_drawn);
 }  // namespace pmv

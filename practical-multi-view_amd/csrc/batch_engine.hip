@@ -26,6 +26,7 @@
 #include <climits>
 #include <condition_variable>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <time.h>
 
@@ -34,7 +35,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher (served by the LK combiners) | 10 PnP, 11 BA, 12 DLT
+    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher (served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -71,6 +72,11 @@ struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
 struct DltReq : Req { BackendBuffers* b; DltProblem P; size_t in_bytes; };
 struct FPReq : Req { BackendBuffers* b; FivePointProblem P; size_t in_bytes; };
+// kind 14: a whole findEssentialMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
+// before the round's launch ends (a round ends with its slowest request) - so the record cannot live on the caller's stack like the others:
+// the combiner's store into `done` after its stream sync would land in a dead frame. The engine owns one record per seq; `inflight` is 1 from
+// the submit until the combiner has released the record after the round, and the seq's next call waits for that before it fills the record again.
+struct EssReq : Req { BackendBuffers* b = nullptr; EssentialProblem P; size_t in_bytes = 0; std::atomic<int> inflight{0}; };
 
 struct Growable {   // device (or mapped pinned host) buffer that only grows; dev = the address kernels use (alias of a host buffer)
     void* p = nullptr; size_t cap = 0; bool host = false; char* dev = nullptr;
@@ -148,6 +154,7 @@ struct BatchEngine {
     int max_linger_us = 300;
     int wait_mode = 3;   // 0 spin (hipStreamSynchronize), 1 query + yield, 2 blocking event, 3 completion word + timed sleeps
     std::vector<BackendBuffers*> slots;   // one back-end workspace set per concurrent sequence
+    std::unique_ptr<EssReq[]> ess;        // one whole-findEssentialMat request record per concurrent sequence (see EssReq)
     // combiners (thread + stream) per class. Round 2, host-bound: 2 and 3 per class cost more host CPU (smaller batches) than they won in
     // latency (25.7k -> 23.3k -> 19.5k frames/s at B = 64). Round 3, with the track tables the host has headroom and the LK class is the one
     // that is busy all the time - a launch ends with its slowest track, so a single LK stream idles most SIMDs during every tail: PMV_BATCH_LANES
@@ -562,7 +569,7 @@ void process_dlt(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     SYNC_TIMED(C);
 }
 
-void process_fp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+void process_fp_rounds(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     DescBlock<FivePointProblem> D;
     EK(desc_block(C, batch.size(), D));
     int max_hyp = 0;
@@ -575,6 +582,28 @@ void process_fp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     EK(stage_in(C, D, batch.size(), 2));
     EK(launch_fivepoint_batch(C.s, D.dprob, (int)batch.size(), max_hyp));
     SYNC_TIMED(C);
+}
+
+// whole findEssentialMat calls: ONE k_essential_ransac launch for the round, one workgroup per request. Each workgroup signals its own
+// caller; the sync below is the fallback (a failed launch releases everyone with an error) and what makes the records reusable.
+void process_essential(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+    DescBlock<EssentialProblem> D;
+    EK(desc_block(C, batch.size(), D));
+    for (size_t i = 0; i < batch.size(); i++) {
+        EssReq* r = (EssReq*)batch[i];
+        D.hprob[i] = r->P;
+        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_ess_in, (unsigned)r->in_bytes, 0};
+    }
+    EK(stage_in(C, D, batch.size(), 2));
+    EK(launch_essential_ransac(C.s, D.dprob, (int)batch.size()));
+    SYNC_TIMED(C);
+}
+
+void process_fp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+    std::vector<Req*> rounds, whole;   // (the two forms share the class; a round that holds both serves them one after the other)
+    for (Req* r : batch) (r->kind == 14 ? whole : rounds).push_back(r);
+    if (!rounds.empty()) process_fp_rounds(E, C, rounds);
+    if (!whole.empty()) process_essential(E, C, whole);
 }
 
 static inline void futex_wait_while(std::atomic<int>* w, int v) {
@@ -641,23 +670,31 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
         C->batches++; C->requests += (long)batch.size();
         for (Req* r : batch) {
             std::atomic<int>* w = &r->done;   // (after the store the owner may return and the request, which lives on its stack, is gone)
+            const bool engine_owned = r->kind == 14;
             w->store(1, std::memory_order_release);
             futex_wake_one(w);
+            if (engine_owned) {   // the record may be filled again from here on
+                std::atomic<int>* f = &((EssReq*)r)->inflight;
+                f->store(0, std::memory_order_release);
+                futex_wake_one(f);
+            }
         }
         C->t_work += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
         { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); C->t_cpu = ts.tv_sec + 1e-9 * ts.tv_nsec; }
     }
 }
 
+void enqueue(Queue& Q, Req* r) {
+    std::lock_guard<std::mutex> lk(Q.mu);
+    if (Q.pending.empty()) Q.first_arrival = std::chrono::steady_clock::now();
+    Q.pending.push_back(r);
+    const int sz = (int)Q.pending.size();
+    if (sz == 1) Q.cv_new.notify_one();
+    else if (Q.min_batch <= 1 || sz == Q.min_batch) Q.cv_new.notify_all();   // (a lingering combiner is waiting for exactly this)
+}
+
 int submit(pmv_ctx* ctx, Queue& Q, Req* r) {
-    {
-        std::lock_guard<std::mutex> lk(Q.mu);
-        if (Q.pending.empty()) Q.first_arrival = std::chrono::steady_clock::now();
-        Q.pending.push_back(r);
-        const int sz = (int)Q.pending.size();
-        if (sz == 1) Q.cv_new.notify_one();
-        else if (Q.min_batch <= 1 || sz == Q.min_batch) Q.cv_new.notify_all();   // (a lingering combiner is waiting for exactly this)
-    }
+    enqueue(Q, r);
     futex_wait_while(&r->done, 0);
     if (r->rc != PMV_OK) set_err(ctx, "%s", r->err);
     return r->rc;
@@ -719,6 +756,7 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
         if (b) E->slots.push_back(b);
         if (rc != PMV_OK) { batch_engine_destroy(ctx); return rc; }
     }
+    E->ess.reset(new EssReq[(size_t)B]);
     E->cap_tracks = (size_t)B * ctx->max_tracks;
     if (const char* e = getenv("PMV_BATCH_EXCLUSIVE")) E->exclusive = atoi(e) != 0;
     if (const char* e = getenv("PMV_LK_LPT")) E->lk_lpt = atoi(e) != 0;
@@ -728,6 +766,7 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
     if (const char* e = getenv("PMV_BATCH_LANES_LK")) E->lanes[R_LK] = std::max(1, std::min(MAX_LANES, atoi(e)));
     if (const char* e = getenv("PMV_BATCH_LANES_PNP")) E->lanes[R_PNP] = std::max(1, std::min(MAX_LANES, atoi(e)));
     if (const char* e = getenv("PMV_BATCH_LANES_BA")) E->lanes[R_BA] = std::max(1, std::min(MAX_LANES, atoi(e)));
+    if (const char* e = getenv("PMV_BATCH_LANES_FP")) E->lanes[R_FP] = std::max(1, std::min(MAX_LANES, atoi(e)));
     if (const char* e = getenv("PMV_BATCH_STREAMS_LK")) E->streams[R_LK] = atoi(e);
     if (const char* e = getenv("PMV_BATCH_STREAMS_BA")) E->streams[R_BA] = atoi(e);
     if (const char* e = getenv("PMV_BATCH_STREAMS_PNP")) E->streams[R_PNP] = atoi(e);
@@ -933,6 +972,43 @@ int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2
     rc = submit(ctx, E->queue[R_FP], &r);
     if (rc) return rc;
     fivepoint_finish(r.b, n_hyp, r.in_bytes, models, n_models, counts);
+    return PMV_OK;
+}
+
+}  // namespace pmv
+
+namespace pmv {
+
+// pmv_find_essential_mat's contract through the five-point combiner. The caller waits for whichever comes first: the completion word that
+// its own workgroup stores last into the seq's pinned result block, or the combiner's done flag after the round's stream sync (the only
+// one a failed launch gives). After the word the workgroup touches nothing of the seq's blocks any more, so the seq's next call may use them
+// while the round's other workgroups are still running; only the request record stays taken until the combiner has released it.
+int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
+                     uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    pmv_ctx* ctx = E->ctx;
+    if (const int rc = essential_check(ctx, "pmv_find_essential_mat", p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn)) return rc;
+    *out_found = 0; *out_samples_drawn = 0;
+    if (n < 5) { memset(mask, 0, (size_t)n); return PMV_OK; }
+    EssReq& r = E->ess[(size_t)seq];
+    futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
+    r.kind = 14; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
+    essential_prepare(r.b, p1_xy, p2_xy, n, K, prob, threshold, &r.P, &r.in_bytes);
+    r.done.store(0, std::memory_order_relaxed);
+    r.inflight.store(1, std::memory_order_release);
+    enqueue(E->queue[R_FP], &r);
+    volatile unsigned* word = essential_done_word(r.b, r.in_bytes);
+    const unsigned want = r.P.done_seq;
+    for (;;) {
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) break;
+        if (r.done.load(std::memory_order_acquire)) {   // the round is over
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) break;
+            const int rc = r.rc != PMV_OK ? r.rc : PMV_ERR_HIP;
+            set_err(ctx, "%s", r.rc != PMV_OK ? r.err : "batch engine: the round ended without the request's completion word");
+            return rc;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    essential_finish(r.b, n, r.in_bytes, E9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "backend.h"
 #include "batch_engine.h"
 #include "ingest_batch.h"
+#include "vo_pipeline.h"
 #include <linux/futex.h>
 #include <sys/prctl.h>
 #include <sys/syscall.h>
@@ -474,6 +475,40 @@ int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, cons
     REQ(models && n_models && counts, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
     std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
     return engine_fivepoint(S->eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts);
+}
+
+// The whole two-view step of a seq: findEssentialMat as one workgroup of the round's k_essential_ransac launch (the call returns when ITS
+// request is done, not when the round is), recoverPose as the host half of the single call around a request of the DLT combiner.
+int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                                 double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    SESSION("pmv_batch_find_essential_mat");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_find_essential_mat", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_essential(S->eng, seq, p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn);
+}
+
+int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
+                           uint8_t* mask, double* tri4n, int* out_good) {
+    SESSION("pmv_batch_recover_pose");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_recover_pose", seq)) return rc;
+    if (const int rc = recover_pose_check(ctx, "pmv_recover_pose", E9, p1_xy, p2_xy, n, K, R9, t3, mask, tri4n, out_good)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    struct Tri : vo::FivePointTri {
+        BatchEngine* eng; int seq; int rc = PMV_OK;
+        void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q, uint8_t* out_mask, int* out_good) override {
+            if (n > 0) rc = engine_dlt(eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+        }
+    } tri;
+    tri.eng = S->eng; tri.seq = seq;
+    std::vector<uint8_t> m(mask, mask + n);
+    std::vector<double> q;
+    double R[9], t[3];
+    const int good = vo::recover_pose(&tri, E9, p1_xy, p2_xy, n, K, R, t, m, q);
+    if (tri.rc != PMV_OK) return tri.rc;
+    memcpy(R9, R, 72); memcpy(t3, t, 24);
+    if (n > 0) { memcpy(mask, m.data(), (size_t)n); memcpy(tri4n, q.data(), (size_t)4 * n * 8); }
+    *out_good = good;
+    return PMV_OK;
 }
 
 }  // extern "C"

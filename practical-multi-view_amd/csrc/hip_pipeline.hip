@@ -106,11 +106,18 @@ struct HipPnP : EPnPSolverBase {
         return n > 0;
     }
 };
-struct HipTri : vo::FivePointTri {   // five-point RANSAC hypotheses on host threads (default) or on the GPU, recoverPose's DLT + cheirality on the GPU
+struct HipTri : vo::FivePointTri {   // five-point RANSAC on host threads (default), its hypotheses round by round or the whole loop on the GPU; recoverPose's DLT + cheirality on the GPU
     pmv_ctx* ctx;
     bool essential_hypotheses(const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models, int* n_models,
                               int* counts) override {
         ck(ctx, pmv_fivepoint_hypotheses(ctx, q1, q2, n, samples, n_hyp, thr, models, n_models, counts));
+        return true;
+    }
+    bool essential_whole(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E, uint8_t* mask, bool* found,
+                         int* samples_drawn) override {
+        int f = 0;
+        ck(ctx, pmv_find_essential_mat(ctx, p1, p2, n, K, prob, threshold, E, mask, &f, samples_drawn));
+        *found = f != 0;
         return true;
     }
     void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
@@ -267,6 +274,13 @@ struct BatchTri : vo::FivePointTri {
         ck(ctx, pmv::engine_fivepoint(eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts));
         return true;
     }
+    bool essential_whole(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E, uint8_t* mask, bool* found,
+                         int* samples_drawn) override {
+        int f = 0;
+        ck(ctx, pmv::engine_essential(eng, seq, p1, p2, n, K, prob, threshold, E, mask, &f, samples_drawn));
+        *found = f != 0;
+        return true;
+    }
     void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                         uint8_t* out_mask, int* out_good) override {
         ck(ctx, pmv::engine_dlt(eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
@@ -330,7 +344,8 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
         else { auto* l = new BatchLK(); l->ctx = ctx; l->eng = eng; l->ring = rf; lk = l; }
         auto* pnp = new BatchPnP(); pnp->ctx = ctx; pnp->eng = eng; pnp->seq = b; pnp->tracker = &run.pipe;
         auto* tri = new BatchTri(); tri->ctx = ctx; tri->eng = eng; tri->seq = b; tri->tracker = &run.pipe; tri->workers = 1;
-        tri->use_hypothesis_hook = P->device_fivepoint != 0;
+        tri->use_whole_hook = P->device_fivepoint == 2;   // the whole findEssentialMat as one request of the five-point combiner
+        tri->use_hypothesis_hook = P->device_fivepoint != 0 && !tri->use_whole_hook;
         auto* ba = new BatchBA(); ba->ctx = ctx; ba->eng = eng; ba->seq = b; ba->tracker = &run.pipe;
         run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
         run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
@@ -465,8 +480,9 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K
         } else { auto* l = new HipLK(); l->ctx = ctx; lk = l; }
         auto* pnp = new HipPnP(); pnp->ctx = ctx; pnp->tracker = &run.pipe;
         auto* tri = new HipTri(); tri->ctx = ctx; tri->tracker = &run.pipe; tri->workers = std::max(1, P->n_threads);
-        tri->use_hypothesis_hook = P->device_fivepoint != 0;
-        tri->prefetch_threads = (P->n_threads > 1 && !tri->use_hypothesis_hook) ? 2 : 0;   // only the two-thread pipeline calls prefetch()
+        tri->use_whole_hook = P->device_fivepoint == 2;   // pmv_find_essential_mat: the whole RANSAC in one launch
+        tri->use_hypothesis_hook = P->device_fivepoint != 0 && !tri->use_whole_hook;
+        tri->prefetch_threads = (P->n_threads > 1 && P->device_fivepoint == 0) ? 2 : 0;   // only the two-thread pipeline calls prefetch()
         auto* ba = new HipBA(); ba->ctx = ctx; ba->tracker = &run.pipe;
         run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
         run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;

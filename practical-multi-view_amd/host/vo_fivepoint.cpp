@@ -330,6 +330,21 @@ void five_point_sample_stream(int n, int count, int* out5) {
     for (int k = 0; k < count; k++) draw_subset(rng, n, 5, out5 + 5 * k);
 }
 int five_point_update_num_iters(double p, double ep, int model_points, int max_iters) { return ransac_update_num_iters(p, ep, model_points, max_iters); }
+// ransac_update_num_iters(p, (n - g) / n, 5, maxIters) split for a caller without this libm (the device loop of pmv_find_essential_mat): the
+// two logarithms per inlier count g = 0..n here, the final expression `denom >= 0 || -num >= maxIters * (-denom) ? maxIters :
+// lrint(num / denom)` there. Where the function returns 0 before its logarithms (denom < DBL_MIN) the entry is -infinity, for which the
+// final expression gives 0 as well: -num >= maxIters * inf is false (also for maxIters = 0: NaN), and num / -inf rounds to 0.
+void five_point_iters_table(int n, double p, double* out_denoms, double* out_num) {
+    const int modelPoints = 5;
+    p = std::max(p, 0.); p = std::min(p, 1.);
+    *out_num = std::log(std::max(1. - p, DBL_MIN));
+    for (int g = 0; g <= n; g++) {
+        double ep = n > 0 ? (double)(n - g) / n : 0.;
+        ep = std::max(ep, 0.); ep = std::min(ep, 1.);
+        const double denom = 1. - std::pow(1. - ep, modelPoints);
+        out_denoms[g] = denom < DBL_MIN ? -HUGE_VAL : std::log(denom);
+    }
+}
 
 // Helper threads for the five-point RANSAC: the hypotheses of a batch are independent, so they are evaluated side by side and
 // the sequential bookkeeping (best-so-far, adaptive iteration count) is replayed in sample order afterwards — the outcome is
@@ -392,6 +407,16 @@ std::shared_ptr<SpinPool> make_spin_pool(int workers) { return std::make_shared<
 
 bool find_essential_mat(const double* p1, const double* p2, int n, const double* K, double prob, double threshold,
                         double* E, std::vector<uint8_t>& mask, int* samples_drawn, SpinPool* pool, int pool_width, FivePointTri* hook) {
+    if (hook && hook->use_whole_hook) {   // the whole call behind one plugin hook: same E, mask and sample count, or "not served"
+        bool found = false;
+        int drawn = 0;
+        mask.assign(n, 0);
+        if (hook->essential_whole(p1, p2, n, K, prob, threshold, E, mask.data(), &found, &drawn)) {
+            if (samples_drawn) *samples_drawn += drawn;
+            return found;
+        }
+    }
+    if (hook && !hook->use_hypothesis_hook) hook = nullptr;
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     std::vector<double> q1(2 * n), q2(2 * n);
     for (int i = 0; i < n; i++) {
@@ -608,7 +633,7 @@ void dlt_candidates_host(const double* q1, const double* q2, int n, const double
 
 // ---- findEssentialMat ahead of time (see vo_pipeline.h) ----------------------------------------------------------------
 void FivePointTri::prefetch(const Frame& prev, const Frame& next) {
-    if (prefetch_threads <= 0 || use_hypothesis_hook) return;
+    if (prefetch_threads <= 0 || use_hypothesis_hook || use_whole_hook) return;
     auto job = std::make_shared<EssentialJob>();
     job->frame = prev.frame;
     const FeatureCorr& fc = prev.feat_corr;
@@ -715,7 +740,7 @@ void FivePointTri::triangulate(Frame& src, Frame& next, Mat3& R_out, Vec3& t_out
         tracker->stats.tri_ahead++;
     } else {
         ok = find_essential_mat(p1.data(), p2.data(), n, tracker->camera, 0.99, 1.0, E, mask, &drawn, inline_e ? pool.get() : nullptr, inline_e ? workers : 1,
-                                use_hypothesis_hook ? this : nullptr);
+                                (use_hypothesis_hook || use_whole_hook) ? this : nullptr);
         prefetch_inline++;
     }
     delete cpu_e;

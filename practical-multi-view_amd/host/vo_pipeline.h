@@ -119,6 +119,15 @@ public:
         (void)q1; (void)q2; (void)n; (void)samples; (void)n_hyp; (void)thr; (void)models; (void)n_models; (void)counts;
         return false;
     }
+    // optional hook for the WHOLE findEssentialMat call (pixel coordinates, K, prob, threshold as cv takes them): E (9, written only when
+    // *found), mask (n bytes, all 0 without a model), *found, *samples_drawn as find_essential_mat gives them. Return false (default) for
+    // "not served": find_essential_mat then goes on as without it. Tried first when use_whole_hook is set.
+    bool use_whole_hook = false;           // set by plugins that implement essential_whole
+    virtual bool essential_whole(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E,
+                                 uint8_t* mask, bool* found, int* samples_drawn) {
+        (void)p1; (void)p2; (void)n; (void)K; (void)prob; (void)threshold; (void)E; (void)mask; (void)found; (void)samples_drawn;
+        return false;
+    }
     // kernel hook (same contract as dlt_candidates_host); the HIP plugin overrides it with pmv_triangulate_candidates
     virtual void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                                 uint8_t* out_mask, int* out_good) {
@@ -263,6 +272,9 @@ public:
 int five_point_essentials(const double* q1, const double* q2, double* E_out);
 void five_point_sample_stream(int n, int count, int* out5);   // the RANSAC's index stream (getSubset on cv::RNG((uint64)-1))
 int five_point_update_num_iters(double p, double ep, int model_points, int max_iters);   // cv::RANSACUpdateNumIters
+// its two logarithms for n correspondences: out_num = log(1 - p), out_denoms[g] (g = 0..n inliers) = log(1 - (1 - (n - g) / n)^5), -infinity
+// where the function returns 0 early; the final expression over them is five_point_update_num_iters(p, (n - g) / n, 5, max_iters) exactly
+void five_point_iters_table(int n, double p, double* out_denoms, double* out_num);
 // cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold, mask) on pixel coordinates; samples_drawn counts RANSAC
 // iterations; pool/pool_width: helper threads (results do not depend on them)
 bool find_essential_mat(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E,

@@ -1,6 +1,8 @@
 """throughput of pmv_pipeline_run_batch for several batch sizes (diagnostic; bench.py reports the chosen one)
-usage: python scripts/bench_batch.py [B ...]"""
-import importlib, os, sys, time
+usage: python scripts/bench_batch.py [B ...]
+environment: DISTINCT=16 the distinct-sequence leg of bench.py; DEVFP=0|1|2 the triangulator's five-point RANSAC on host threads, round by
+round on the GPU, or whole on the GPU (pmv_pipeline_params::device_fivepoint); PASSES=k timed passes per B (frames/s: their median)"""
+import importlib, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
@@ -31,21 +33,31 @@ if os.environ.get("BA_MODE"):
 ref = None
 THREADED = int(os.environ.get("THREADED", "1"))
 DEVFP = int(os.environ.get("DEVFP", "0"))
+PASSES = max(1, int(os.environ.get("PASSES", "1")))
 BA_IT = int(os.environ.get("BA_ITERS", "5"))   # diagnostic: how sensitive is the throughput to the length of the BA launch chain
 print("wait mode", os.environ.get("PMV_BATCH_WAIT", "flag"), "threaded", THREADED, flush=True)
 for B in Bs:
     seqs = [(b * n, n, distinct[b % len(distinct)][1]) for b in range(B)]
     r = ctx.pipeline_run_batch(seqs, cfg["w"], cfg["h"], K, want_features=False, defer_free=True, threaded=THREADED, device_fivepoint=DEVFP, ba_iterations=BA_IT)   # warm-up
     ctx.sync()
-    s0 = ctx.batch_stats()
-    t0 = time.perf_counter()
-    c0 = time.process_time()
-    r2 = ctx.pipeline_run_batch(seqs, cfg["w"], cfg["h"], K, want_features=False, defer_free=True, threaded=THREADED, device_fivepoint=DEVFP, ba_iterations=BA_IT)
-    ctx.sync()
-    dt = time.perf_counter() - t0
-    cpu = time.process_time() - c0
-    s1 = ctx.batch_stats()
-    fr = sum(n - int(x.stats["init_offset"]) for x in r2)
+    rates, cpus = [], []
+    for p in range(PASSES):   # the last pass is the one reported in detail
+        if p:
+            for x in r2:
+                x.free()
+        s0 = ctx.batch_stats()
+        t0 = time.perf_counter()
+        c0 = time.process_time()
+        r2 = ctx.pipeline_run_batch(seqs, cfg["w"], cfg["h"], K, want_features=False, defer_free=True, threaded=THREADED, device_fivepoint=DEVFP, ba_iterations=BA_IT)
+        ctx.sync()
+        dt = time.perf_counter() - t0
+        cpu = time.process_time() - c0
+        s1 = ctx.batch_stats()
+        fr = sum(n - int(x.stats["init_offset"]) for x in r2)
+        rates.append(fr / dt); cpus.append(cpu / fr * 1e6)
+    if PASSES > 1:
+        print(f"B={B:3d} device_fivepoint={DEVFP}: median of {PASSES} passes {statistics.median(rates):9.1f} frames/s (min {min(rates):.1f}, max {max(rates):.1f}), "
+              f"host CPU {statistics.median(cpus):.0f} us per frame; all: {[round(x, 1) for x in rates]}", flush=True)
     if ref is None:
         ref = r2[0].poses
     same = all(np.array_equal(x.poses, r2[i % len(distinct)].poses) for i, x in enumerate(r2))   # (every copy of a distinct sequence gives the same poses)
