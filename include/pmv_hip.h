@@ -171,7 +171,8 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
  *   Frame sizes: 40x40 .. max_w x max_h as before. Level 0 may be narrower than the window and upper levels narrower than the 64-pixel
  *     border (a 10x8 level at win = 5): the border is REFLECT_101 applied as often as needed.
  *   pmv_lk_counters: the general kernels count at most 255 iterations per track (the tuned ones cannot reach that).
- *   Out of scope: non-square windows, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS (the CPU restatement has none of them). */
+ *   Out of scope: non-square windows. OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_LK_GET_MIN_EIGENVALS are no context settings: they are the
+ *     per-call `flags` argument of pmv_lk_track_ex (below), as in cv. */
 typedef struct pmv_lk_params {
     int win;          /* square window side, cv::Size(win, win); default 32 */
     int max_level;    /* maxLevel of buildOpticalFlowPyramid / calcOpticalFlowPyrLK; default 4 */
@@ -181,6 +182,37 @@ typedef struct pmv_lk_params {
 } pmv_lk_params;
 int pmv_set_lk_params(pmv_ctx* ctx, const pmv_lk_params* p);
 int pmv_get_lk_params(pmv_ctx* ctx, pmv_lk_params* out);
+/* cv::calcOpticalFlowPyrLK with its `flags` argument (cv's values). Window, depth, criteria and minEigThreshold come from the context
+ * (pmv_set_lk_params) as for pmv_lk_track; the flags are per call.
+ *   next_xy: n*2 floats, in/out. With PMV_LK_USE_INITIAL_FLOW the top level's search of point i starts at next_xy[i] * 2^-level instead of
+ *     prev_xy[i] * 2^-level; next_xy is read, then overwritten with the result. Without the flag it is output only. A guess may lie anywhere,
+ *     outside the frame too (the point then ends with status 0 like a point that walks out of the frame).
+ *   PMV_LK_GET_MIN_EIGENVALS: out_err[i] = the smaller eigenvalue of the point's 2x2 normal matrix divided by 2 win^2 - the value the
+ *     minEigThreshold test looks at - instead of the L1 residual. It is stored at every level whose template window passes the bounds
+ *     test, before the threshold test, and the final residual is not computed: out_err is level 0's value for every point whose level-0
+ *     template is in range, points that end with status 0 included, and 0 otherwise. Positions and status are those of the call without
+ *     the flag.
+ *   flags = 0: the bytes of pmv_lk_track in all three outputs. An initial flow equal to prev_xy: the same bytes again.
+ *   [mem: OpenCV 3.4 lkpyramid.cpp; parity unpinned like the rest of LK - tests/twin/lkx_twin.cpp is the CPU restatement that fixes it.]
+ * Errors (nothing is written on any of them): PMV_ERR_INVALID - a null pointer, flag bits other than the two, with
+ *   PMV_LK_USE_INITIAL_FLOW an initial coordinate that is not finite or beyond 1e6 in magnitude (the message names the point);
+ *   PMV_ERR_CAPACITY - n above max_tracks; the slot errors of pmv_lk_track.
+ * The device buffers of the extra inputs and outputs are made by the first extended call on a context. pmv_lk_counters: as pmv_lk_track
+ * (a track counts once, at most 255 iterations per track). The launches run under the LK profiling class. */
+enum { PMV_LK_USE_INITIAL_FLOW = 4, PMV_LK_GET_MIN_EIGENVALS = 8 };
+int pmv_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
+                    uint8_t* out_status, float* out_err);
+/* Forward-backward check (the outlier filter of a KLT front end) in ONE launch: the workgroup that tracked a point forward tracks the
+ * result back into the first frame. Defined as a composition, bit for bit:
+ *   1. forward: pmv_lk_track_ex(prev_slot, next_slot, prev_xy, next_xy, flags);
+ *   2. backward, for the tracks with forward status 1: pmv_lk_track_ex(next_slot, prev_slot, points = the forward result, initial flow =
+ *      prev_xy, flags = PMV_LK_USE_INITIAL_FLOW | (flags & PMV_LK_GET_MIN_EIGENVALS)) -> back_xy, back_status, back_err;
+ *   3. a track whose forward status is 0 runs no backward pass: back_status 0, back_err 0, back_xy = the bits of its forward next_xy.
+ * The library does not threshold |back_xy - prev_xy|: that is the caller's policy. Errors: those of pmv_lk_track_ex; the three back
+ * outputs must not be null. pmv_lk_counters adds the iterations (saturating at 255 per track) and (track, level) passes of both directions;
+ * a track counts once. */
+int pmv_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
+                    uint8_t* out_status, float* out_err, float* back_xy, uint8_t* back_status, float* back_err);
 /* diagnostic: on != 0 sends the default window (32) through the general kernels as well, so that a test can compare the two code paths.
  * It changes no result. */
 int pmv_debug_lk_general(pmv_ctx* ctx, int on);
@@ -440,6 +472,14 @@ int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w,
  * in batched launches (LK and kNN: the LK combiners; the three detectors: the detector combiner). The slots must hold frames of a declared
  * size (else PMV_ERR_INVALID). */
 int pmv_batch_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* out_status, float* out_err);
+/* pmv_lk_track_ex and pmv_lk_track_fb as session calls: same arguments, same checks, same bytes. A round of the LK combiner serves all its
+ * extended requests with ONE launch on top of the k_lk_batch launch of its plain requests (counted in pmv_debug_batch_launches out4[0]); a
+ * round without extended requests launches what it always did. An fb request counts n tracks against the round's capacity. The tracks go
+ * in the engine's default order. */
+int pmv_batch_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
+                          uint8_t* out_status, float* out_err);
+int pmv_batch_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
+                          uint8_t* out_status, float* out_err, float* back_xy, uint8_t* back_status, float* back_err);
 int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
                         int* out_best, float* out_err);
 int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,

@@ -37,18 +37,22 @@ class LKParams(C.Structure):
 
 
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
+# the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
+LK_USE_INITIAL_FLOW = 4
+LK_GET_MIN_EIGENVALS = 8
+
 ABI_SYMBOLS = [
     "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_thread_error", "pmv_sync",
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
-    "pmv_lk_track", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
+    "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
     "pmv_pipeline_frame_feature_count", "pmv_pipeline_get_frame_features", "pmv_pipeline_stats_count", "pmv_pipeline_get_stats",
     "pmv_batch_open", "pmv_batch_close", "pmv_batch_frame_upload", "pmv_batch_upload_stats", "pmv_batch_upload_rounds",
-    "pmv_batch_lk_track", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
+    "pmv_batch_lk_track", "pmv_batch_lk_track_ex", "pmv_batch_lk_track_fb", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
     "pmv_batch_pnp_ransac", "pmv_batch_ba_solve", "pmv_batch_triangulate_candidates", "pmv_batch_fivepoint_hypotheses",
     "pmv_batch_find_essential_mat", "pmv_batch_recover_pose",
 ]
@@ -495,6 +499,36 @@ class Context:
                                        _p(err, _f32p)))
         return out, st, err
 
+    def _lk_ex(self, fn, ck, fb, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals):
+        p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        n = p.shape[0]
+        flags = (LK_USE_INITIAL_FLOW if init_xy is not None else 0) | (LK_GET_MIN_EIGENVALS if min_eigenvals else 0)
+        # the in/out array of the call: the initial flow on the way in, the tracked positions on the way out
+        nxt = np.zeros((n, 2), np.float32) if init_xy is None else np.array(init_xy, np.float32).reshape(-1, 2)
+        if nxt.shape[0] != n:
+            raise ValueError(f"init_xy has {nxt.shape[0]} points, prev_xy {n}")
+        st = np.zeros(n, np.uint8)
+        err = np.zeros(n, np.float32)
+        args = [self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(nxt, _f32p), flags, _p(st, _u8p), _p(err, _f32p)]
+        if not fb:
+            ck(fn(*args))
+            return nxt, st, err
+        bxy = np.zeros((n, 2), np.float32)
+        bst = np.zeros(n, np.uint8)
+        berr = np.zeros(n, np.float32)
+        ck(fn(*args, _p(bxy, _f32p), _p(bst, _u8p), _p(berr, _f32p)))
+        return nxt, st, err, bxy, bst, berr
+
+    def lk_track_ex(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False):
+        """pmv_lk_track_ex: lk_track with cv's flags. init_xy (n x 2): OPTFLOW_USE_INITIAL_FLOW, the search of point i starts there;
+        min_eigenvals: OPTFLOW_LK_GET_MIN_EIGENVALS, err is the minimum eigenvalue measure instead of the residual. Returns (xy, status, err)."""
+        return self._lk_ex(self.lib.pmv_lk_track_ex, self._ck, False, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
+
+    def lk_track_fb(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False):
+        """pmv_lk_track_fb: lk_track_ex and, in the same launch, every tracked point back into the first frame. Returns
+        (xy, status, err, back_xy, back_status, back_err); thresholding |back_xy - prev_xy| is the caller's policy."""
+        return self._lk_ex(self.lib.pmv_lk_track_fb, self._ck, True, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
+
     def set_lk_params(self, win=32, max_level=4, max_iter=30, eps=0.01, min_eig=1e-4):
         """cv::calcOpticalFlowPyrLK's winSize (square), maxLevel, criteria and minEigThreshold for every pyramid built and every LK call
         made from now on (pmv_set_lk_params). A change of win or max_level empties every frame slot: upload the frames again."""
@@ -919,6 +953,14 @@ class Context:
         err = np.zeros(n, np.float32)
         self._ckt(self.lib.pmv_batch_lk_track(self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p), _p(err, _f32p)))
         return out, st, err
+
+    def batch_lk_track_ex(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False):
+        """lk_track_ex as a session call (pmv_batch_lk_track_ex)"""
+        return self._lk_ex(self.lib.pmv_batch_lk_track_ex, self._ckt, False, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
+
+    def batch_lk_track_fb(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False):
+        """lk_track_fb as a session call (pmv_batch_lk_track_fb)"""
+        return self._lk_ex(self.lib.pmv_batch_lk_track_fb, self._ckt, True, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
 
     def batch_pnp_ransac(self, seq, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):
         o = np.ascontiguousarray(obj_xyz, np.float32).reshape(-1, 3)

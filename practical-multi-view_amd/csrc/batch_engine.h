@@ -18,6 +18,11 @@ void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
 // (ctx->bingest) that builds the request's frames, from slot_ready; -1 = none.
 int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* status, float* err,
               const uint8_t* predicted_iters = nullptr, uint8_t* iters_out = nullptr, int ring_round = -1);
+// pmv_lk_track_ex's / pmv_lk_track_fb's (fb) contract, arguments already checked: a request of the LK combiners. A round serves all its
+// extended requests with one launch of the extended batch kernels, next to the k_lk_batch launch of its plain ones; an fb request counts
+// n tracks against the round's capacity. Tracks go in the engine's default order. next_xy: in (with PMV_LK_USE_INITIAL_FLOW) and out.
+int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status, float* err, bool fb,
+                 float* back_xy, uint8_t* back_status, float* back_err);
 int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                   double min_dist, int* out_xy, double* out_score, int* out_count, int ring_round = -1);
 // pmv_detect_fast's contract (a cell may be as large as the frame; max_per_cell <= 0: empty lists, no launch): a request of the detector combiner

@@ -35,7 +35,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher (served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
+    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -52,6 +52,9 @@ struct LKReq : Req {
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
     int geom = 0;             // filled by the combiner: the geometry-table entry of its two frames
     int ring_round = -1;      // the feed round that builds the two frames (-1 = nothing to wait for)
+    // kind 5 (pmv_lk_track_ex / _fb): out_xy is in/out, flags = LKX_*; with LKX_FB the three back outputs
+    int flags = 0;
+    float* back_xy = nullptr; uint8_t* back_status = nullptr; float* back_err = nullptr;
 };
 struct KnnReq : Req {         // kind 4: one kNNFeatureMatcher call (pmv_knn_match's contract)
     int src_slot, cmp_slot, n, m, n_nn, window;
@@ -119,6 +122,9 @@ struct Combiner {
     Growable h_front{nullptr, 0, true}, d_front, h_cells{nullptr, 0, true}, d_cells, d_eig, d_cellmax, d_spill, d_det_xy, d_det_score, d_det_count, h_det{nullptr, 0, true};
     // kNN matcher rounds (LK combiners): [stage-in job | request records | coordinate lists], pinned mirror and HBM copy; FAST score maps (detector combiner)
     Growable h_knn{nullptr, 0, true}, d_knn, d_fast_score;
+    // extended LK requests (LK combiners, made by the first round that has one): [LKBlock | LKExt] records of a round; back results of
+    // cap_tracks tracks as [positions | err | status], indexed like the forward results
+    Growable h_lkx{nullptr, 0, true}, h_back{nullptr, 0, true};
     float* h_out_xy = nullptr; float* h_err = nullptr; uint8_t* h_status = nullptr; uint16_t* h_work = nullptr;
     float* dm_out_xy = nullptr; float* dm_err = nullptr; uint8_t* dm_status = nullptr; uint16_t* dm_work = nullptr;
     int* d_flags = nullptr;
@@ -240,7 +246,8 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     hipStream_t s = C.s;
     std::vector<LKReq*> lk;
     std::vector<KnnReq*> knn;   // (sequences that run the kNN matcher: the same role, the same round)
-    for (Req* r : batch) { if (r->kind == 4) knn.push_back((KnnReq*)r); else lk.push_back((LKReq*)r); }
+    std::vector<LKReq*> lkx;    // (extended LK requests: one more launch for all of them)
+    for (Req* r : batch) { if (r->kind == 4) knn.push_back((KnnReq*)r); else if (r->kind == 5) lkx.push_back((LKReq*)r); else lk.push_back((LKReq*)r); }
     // ---- LK: one launch for the tracks of every requesting sequence, whatever their frame sizes: a request's geometry is the one staged in
     // its prev slot (prev and next of ONE request must agree), carried by each of its track records as an index into the context's table
     const unsigned long long pitch = ctx->cap.slot_bytes;
@@ -341,7 +348,56 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         EK(launch_lk_batch(s, ctx->d_slots, (const LKBlock*)C.h_front.dev, bpos, ctx->d_geom, P, C.dm_out_xy, C.dm_status, C.dm_err, C.dm_work));
         ctx->batch_launches[0]++;
     }
+    // ---- extended LK: the round's pmv_lk_track_ex / _fb requests in ONE launch of the extended batch kernels; their results take the
+    // indices behind the plain tracks and the matcher's in the same result blocks, the back results the same indices of the back block
+    int ext_tracks = 0;
+    for (LKReq* r : lkx) {
+        const PyrLayout& a = ctx->slot_layout[r->prev_slot];
+        const PyrLayout& b2 = ctx->slot_layout[r->next_slot];
+        if (slot_ready(ctx, r->prev_slot) || slot_ready(ctx, r->next_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
+        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->prev_slot, a.w[0], a.h[0]); continue; }
+        r->base = total_tracks + knn_tracks + ext_tracks;
+        ext_tracks += r->n;
+    }
+    if (ext_tracks > 0) {
+        const size_t cap = E->cap_tracks;
+        if ((size_t)total_tracks + (size_t)knn_tracks + (size_t)ext_tracks > cap) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
+        EK(C.h_lkx.ensure((sizeof(LKBlock) + sizeof(LKExt)) * (size_t)ext_tracks + 64));
+        EK(C.h_back.ensure(cap * 13 + 64));
+        LKBlock* hblk = (LKBlock*)C.h_lkx.p;
+        LKExt* hext = (LKExt*)(hblk + ext_tracks);
+        int bpos = 0;
+        size_t kmax = 0;
+        for (LKReq* r : lkx) if (r->rc == PMV_OK) kmax = std::max(kmax, (size_t)r->n);
+        for (size_t k = 0; k < kmax; k++)   // the engine's default order: track k of every request before any track k + 1
+            for (LKReq* r : lkx) {
+                if (r->rc != PMV_OK || k >= (size_t)r->n) continue;
+                LKBlock& b = hblk[bpos];
+                b.prev_off = (unsigned long long)r->prev_slot * pitch; b.next_off = (unsigned long long)r->next_slot * pitch;
+                b.track = r->base + (int)k; b.x = r->prev_xy[2 * k]; b.y = r->prev_xy[2 * k + 1]; b.geom = r->geom;
+                LKExt& x = hext[bpos++];
+                const bool init = (r->flags & LKX_INIT) != 0;
+                x.ix = init ? r->out_xy[2 * k] : 0.f; x.iy = init ? r->out_xy[2 * k + 1] : 0.f; x.flags = r->flags; x.reserved = 0;
+            }
+        const LKParams P = lk_launch_params(ctx);
+        EK(launch_lk_batch_ex(s, ctx->d_slots, (const LKBlock*)C.h_lkx.dev, (const LKExt*)(C.h_lkx.dev + sizeof(LKBlock) * (size_t)ext_tracks), bpos, ctx->d_geom, P, C.dm_out_xy,
+                              C.dm_status, C.dm_err, C.dm_work, (float*)C.h_back.dev, (uint8_t*)(C.h_back.dev + cap * 12), (float*)(C.h_back.dev + cap * 8)));
+        ctx->batch_launches[0]++;
+    }
     SYNC_TIMED(C);
+    for (LKReq* r : lkx) {
+        if (r->rc != PMV_OK) continue;
+        memcpy(r->out_xy, C.h_out_xy + (size_t)2 * r->base, (size_t)r->n * 8);
+        memcpy(r->status, C.h_status + r->base, (size_t)r->n);
+        memcpy(r->err_out, C.h_err + r->base, (size_t)r->n * 4);
+        if (r->flags & LKX_FB) {
+            const char* hb = (const char*)C.h_back.p;
+            memcpy(r->back_xy, hb + (size_t)8 * r->base, (size_t)r->n * 8);
+            memcpy(r->back_err, hb + E->cap_tracks * 8 + (size_t)4 * r->base, (size_t)r->n * 4);
+            memcpy(r->back_status, hb + E->cap_tracks * 12 + r->base, (size_t)r->n);
+        }
+        ctx->add_lk_work(C.h_work + r->base, (size_t)r->n);
+    }
     for (LKReq* r : lk) {
         if (r->rc != PMV_OK) continue;
         memcpy(r->out_xy, C.h_out_xy + (size_t)2 * r->base, (size_t)r->n * 8);
@@ -724,7 +780,7 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
             if (C.h_done) (void)hipHostFree(C.h_done);
-            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score}) g->release();
+            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back}) g->release();
             if (C.h_out_xy) (void)hipHostFree(C.h_out_xy);
             if (C.h_err) (void)hipHostFree(C.h_err);
             if (C.h_status) (void)hipHostFree(C.h_status);
@@ -851,6 +907,19 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
         const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);
         r.order[(i - first) * 8 + s8] = byx[i].second;
     }
+    return submit(ctx, E->queue[R_LK], &r);
+}
+
+int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status, float* err, bool fb,
+                 float* back_xy, uint8_t* back_status, float* back_err) {
+    pmv_ctx* ctx = E->ctx;
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
+    REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
+    if (n == 0) return PMV_OK;
+    LKReq r;
+    r.kind = 5; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = next_xy; r.status = status; r.err_out = err;
+    r.flags = (flags & (LKX_INIT | LKX_EIG)) | (fb ? LKX_FB : 0);
+    r.back_xy = back_xy; r.back_status = back_status; r.back_err = back_err;
     return submit(ctx, E->queue[R_LK], &r);
 }
 

@@ -403,6 +403,23 @@ int pmv_batch_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* 
     return engine_lk(S->eng, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err);
 }
 
+int pmv_batch_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err) {
+    SESSION("pmv_batch_lk_track_ex");
+    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
+    if (const int rc_ = lkx_check(ctx, "pmv_batch_lk_track_ex", flags, next_xy, n, false, nullptr, nullptr, nullptr)) return rc_;
+    if (n == 0) return PMV_OK;
+    return engine_lk_ex(S->eng, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, false, nullptr, nullptr, nullptr);
+}
+int pmv_batch_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
+                          float* back_xy, uint8_t* back_status, float* back_err) {
+    SESSION("pmv_batch_lk_track_fb");
+    REQ(n <= 0 || (back_xy && back_status && back_err), PMV_ERR_INVALID, "pmv_batch_lk_track_fb: null argument");
+    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
+    if (const int rc_ = lkx_check(ctx, "pmv_batch_lk_track_fb", flags, next_xy, n, true, back_xy, back_status, back_err)) return rc_;
+    if (n == 0) return PMV_OK;
+    return engine_lk_ex(S->eng, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
+}
+
 int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
                         int* out_best, float* out_err) {
     SESSION("pmv_batch_knn_match");

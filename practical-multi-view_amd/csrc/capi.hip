@@ -162,6 +162,7 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->d_lk_stamps) hipFree(c->d_lk_stamps);
     if (c->d_geom) hipFree(c->d_geom);
     if (c->h_work) hipHostFree(c->h_work);
+    if (c->h_lkx) hipHostFree(c->h_lkx);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
     hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
@@ -427,6 +428,63 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
     return PMV_OK;
 }
 
+// pmv_lk_track_ex and pmv_lk_track_fb: pmv_lk_track's steps around ONE launch of the extended kernels
+static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
+                        bool fb, float* back_xy, uint8_t* back_status, float* back_err) {
+    REQ(ctx, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(n <= 0 || !fb || (back_xy && back_status && back_err), PMV_ERR_INVALID, "%s: null argument", who);
+    if (const int rc_ = lk_check(ctx, true, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
+    if (const int rc_ = lkx_check(ctx, who, flags, next_xy, n, fb, back_xy, back_status, back_err)) return rc_;
+    const PyrLayout& L = ctx->slot_layout[prev_slot];
+    if (n == 0) return PMV_OK;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const size_t nt = (size_t)ctx->max_tracks;
+    if (!ctx->h_lkx) {
+        CKC(hipHostMalloc(&ctx->h_lkx, nt * 21 + 64, hipHostMallocMapped | hipHostMallocCoherent));
+        CKC(hipHostGetDevicePointer((void**)&ctx->dm_lkx, ctx->h_lkx, 0));
+    }
+    const size_t off_bxy = nt * 8, off_berr = nt * 16, off_bst = nt * 20;
+    if (flags & PMV_LK_USE_INITIAL_FLOW) memcpy(ctx->h_lkx, next_xy, (size_t)n * 8);
+    memcpy(ctx->h_prev_xy, prev_xy, (size_t)n * 8);
+    int* order = (int*)(ctx->h_prev_xy + (size_t)2 * n);   // the XCD-aware block order of pmv_lk_track
+    const int nb = (n + 7) / 8 * 8;
+    {
+        static thread_local std::vector<std::pair<float, int>> byx;
+        byx.resize(n);
+        for (int i = 0; i < n; i++) byx[i] = {prev_xy[2 * i], i};
+        std::sort(byx.begin(), byx.end());
+        for (int b = 0; b < nb; b++) order[b] = -1;
+        for (int i = 0; i < n; i++) {
+            const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);
+            order[(i - first) * 8 + s8] = byx[i].second;
+        }
+    }
+    CKC(hipMemcpyAsync(ctx->d_prev_xy, ctx->h_prev_xy, (size_t)n * 8 + (size_t)nb * 4, hipMemcpyHostToDevice, ctx->s_front));
+    const LKParams P = lk_launch_params(ctx);
+    CKC(launch_lk_ex(ctx->s_front, ctx->d_slots + (size_t)prev_slot * L.slot_bytes, ctx->d_slots + (size_t)next_slot * L.slot_bytes, L, ctx->d_prev_xy,
+                     (const float*)ctx->dm_lkx, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->dm_out_xy, ctx->dm_status,
+                     ctx->dm_err, ctx->dm_work, (float*)(ctx->dm_lkx + off_bxy), ctx->dm_lkx + off_bst, (float*)(ctx->dm_lkx + off_berr)));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    memcpy(next_xy, ctx->h_out_xy, (size_t)n * 8);
+    memcpy(out_status, ctx->h_status, (size_t)n);
+    memcpy(out_err, ctx->h_err, (size_t)n * 4);
+    if (fb) {
+        memcpy(back_xy, ctx->h_lkx + off_bxy, (size_t)n * 8);
+        memcpy(back_status, ctx->h_lkx + off_bst, (size_t)n);
+        memcpy(back_err, ctx->h_lkx + off_berr, (size_t)n * 4);
+    }
+    ctx->add_lk_work(ctx->h_work, (size_t)n);
+    return PMV_OK;
+}
+int pmv_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err) {
+    return lk_single_ex(ctx, "pmv_lk_track_ex", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, false, nullptr, nullptr, nullptr);
+}
+int pmv_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
+                    float* back_xy, uint8_t* back_status, float* back_err) {
+    return lk_single_ex(ctx, "pmv_lk_track_fb", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
+}
+
 static void pack_cells(int* dst, const int* cells, int n_cells, int slot) {   // (x0, y0, w, h) -> device cell records of that frame slot
     for (int i = 0; i < n_cells; i++) {
         int* d = dst + (size_t)i * CELL_STRIDE;
@@ -442,6 +500,15 @@ int pmv::lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, cons
     const PyrLayout& L = ctx->slot_layout[prev_slot];
     const PyrLayout& L2 = ctx->slot_layout[next_slot];
     REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_lk_track: frame sizes differ");
+    return PMV_OK;
+}
+int pmv::lkx_check(pmv_ctx* ctx, const char* who, int flags, const float* next_xy, int n, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err) {
+    static_assert(PMV_LK_USE_INITIAL_FLOW == LKX_INIT && PMV_LK_GET_MIN_EIGENVALS == LKX_EIG, "the kernels take cv's flag values as they are");
+    REQ(!(flags & ~(PMV_LK_USE_INITIAL_FLOW | PMV_LK_GET_MIN_EIGENVALS)), PMV_ERR_INVALID, "%s: flags = 0x%x has bits other than PMV_LK_USE_INITIAL_FLOW (4) and PMV_LK_GET_MIN_EIGENVALS (8)", who, (unsigned)flags);
+    REQ(n == 0 || !fb || (back_xy && back_status && back_err), PMV_ERR_INVALID, "%s: null argument", who);
+    if (flags & PMV_LK_USE_INITIAL_FLOW)
+        for (int i = 0; i < 2 * n; i++)   // (a NaN fails the comparison too)
+            REQ(fabsf(next_xy[i]) <= 1e6f, PMV_ERR_INVALID, "%s: initial flow of point %d (%g, %g) is not finite or beyond 1e6", who, i / 2, (double)next_xy[i & ~1], (double)next_xy[i | 1]);
     return PMV_OK;
 }
 int pmv::detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell) {

@@ -560,9 +560,13 @@ __device__ inline void stage_J(uint8_t* sJ, const uint8_t* Jorg, int js, int tx0
 // this block feeds the diagnostic phase timers.
 struct LKResult { float x, y, err; int status, n_iter, n_lev; };
 // LRef: const PyrLayout& (k_lk: the launch's by-value geometry) or GeomEntry& (k_lk_batch: the track's entry of the geometry table)
-template <int T, bool STAMPS, class LRef>
+// EX (pmv_lk_track_ex / _fb, the k_lk*_ex kernels): `flags` of LKX_INIT - the top level's search starts at (ix0, iy0) * 2^-level instead of
+// the template position - and LKX_EIG - err = the level's minEig, stored before the threshold test, and no final residual. The plain
+// instantiations (EX = false) never look at the three arguments: they generate the code they generated without them.
+template <int T, bool STAMPS, class LRef, bool EX = false>
 __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
-                                                   const float px0, const float py0, const LKParams& P, const bool stamp_on) {
+                                                   const float px0, const float py0, const LKParams& P, const bool stamp_on,
+                                                   const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0) {
     constexpr int NPRE = 4;                       // I tiles staged per group (all levels of a 4-level pyramid at once)
     constexpr int SI_BYTES = 35 * SI_STRIDE + 8;   // + two dwords: the aligned loads of the last row may touch the first
     __shared__ __attribute__((aligned(16))) uint8_t sIall[NPRE * SI_BYTES];
@@ -617,7 +621,15 @@ __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ p
         }
         if (with_search_tile) {   // the top level's search starts at the template position: its tile rides along
             float fx, fy; int inx, iny;
-            if (template_origin(top, fx, fy, inx, iny)) {
+            bool first_ok = template_origin(top, fx, fy, inx, iny);
+            if constexpr (EX) {
+                if (flags & LKX_INIT) {   // ... or at the caller's guess, wherever that lies: the first iteration's own position and bounds test
+                    const float lscale = __int_as_float((127 - top) << 23);
+                    inx = (int)floorf(ix0 * lscale - half); iny = (int)floorf(iy0 * lscale - half);
+                    first_ok = first_ok && !(inx < -W || inx >= L.w[top] || iny < -W || iny >= L.h[top]);
+                }
+            }
+            if (first_ok) {
                 tx0 = (inx - 16) & ~3; ty0 = iny - 16;
                 tile_issue<T>(jreg, level_origin(nextS, L, top), L.stride[top], tx0, ty0, tid);
                 j_ok = true;
@@ -655,7 +667,11 @@ __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ p
         int ipx, ipy;
         const bool inside = template_origin(level, prevx, prevy, ipx, ipy);
         float nx, ny;
-        if (level == ml) { const float lscale = __int_as_float((127 - level) << 23); nx = px0 * lscale; ny = py0 * lscale; }
+        if (level == ml) {
+            const float lscale = __int_as_float((127 - level) << 23);
+            if (EX && (flags & LKX_INIT)) { nx = ix0 * lscale; ny = iy0 * lscale; }
+            else { nx = px0 * lscale; ny = py0 * lscale; }
+        }
         else { nx = outx * 2.f; ny = outy * 2.f; }
         outx = nx; outy = ny;
         if (!inside) {   // block-uniform
@@ -745,6 +761,7 @@ __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ p
         const float A11 = (float)sA[0] * FLT_SCALE, A12 = (float)sA[1] * FLT_SCALE, A22 = (float)sA[2] * FLT_SCALE;
         float D = A11 * A22 - A12 * A12;
         const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * W * W);
+        if (EX && (flags & LKX_EIG)) err = minEig;
         if (minEig < P.min_eig || D < FLT_EPSILON) {   // block-uniform (computed from block-wide sums)
             if (level == 0) status = 0;
             continue;
@@ -836,7 +853,7 @@ __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ p
             const int inx = (int)floorf(fx), iny = (int)floorf(fy);
             if (inx < -W || inx >= lw || iny < -W || iny >= lh) {
                 status = 0;
-            } else {
+            } else if (!(EX && (flags & LKX_EIG))) {
                 int wx = inx - tx0, wy = iny - ty0;
                 if (tile_level != 0 || wx < 0 || wx > 31 || wy < 0 || wy > 31) {
                     tx0 = (inx - 16) & ~3; ty0 = iny - 16;
@@ -950,9 +967,11 @@ __host__ __device__ inline LKGLds lkg_lds(int win) {
 }
 // One track through all pyramid levels, executed by one whole T-thread workgroup (T = 256: k_lk_general, T = 64: k_lk_batch_general);
 // every thread returns the same results. The arithmetic is orc_lk.cpp:92-209 with W = P.win.
-template <int T, class LRef>
+// EX, ix0, iy0, flags: as lk_track_block.
+template <int T, class LRef, bool EX = false>
 __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
-                                                     const float px0, const float py0, const LKParams& P) {
+                                                     const float px0, const float py0, const LKParams& P,
+                                                     const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lkg_smem[];
     const int W = __builtin_amdgcn_readfirstlane(P.win);
     const LKGLds G = lkg_lds(W);
@@ -982,7 +1001,10 @@ __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__
         const float prevx = px0 * lscale - half, prevy = py0 * lscale - half;
         const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
         float nx, ny;
-        if (level == ml) { nx = px0 * lscale; ny = py0 * lscale; }
+        if (level == ml) {
+            if (EX && (flags & LKX_INIT)) { nx = ix0 * lscale; ny = iy0 * lscale; }
+            else { nx = px0 * lscale; ny = py0 * lscale; }
+        }
         else { nx = outx * 2.f; ny = outy * 2.f; }
         outx = nx; outy = ny;
         if (ipx < -W || ipx >= lw || ipy < -W || ipy >= lh) {   // block-uniform
@@ -1064,6 +1086,7 @@ __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__
         const float A11 = (float)sA[0] * FLT_SCALE, A12 = (float)sA[1] * FLT_SCALE, A22 = (float)sA[2] * FLT_SCALE;
         float D = A11 * A22 - A12 * A12;
         const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * W * W);
+        if (EX && (flags & LKX_EIG)) err = minEig;
         if (minEig < P.min_eig || D < FLT_EPSILON) {   // block-uniform (computed from block-wide sums)
             if (level == 0) status = 0;
             continue;
@@ -1113,7 +1136,7 @@ __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__
             const int inx = (int)floorf(fx), iny = (int)floorf(fy);
             if (inx < -W || inx >= lw || iny < -W || iny >= lh) {
                 status = 0;
-            } else {
+            } else if (!(EX && (flags & LKX_EIG))) {
                 if (!in_tile(inx, iny)) stage_search(inx, iny);
                 bilinear_weights(fx - inx, fy - iny, iw00, iw01, iw10, iw11);
                 int epart[1] = {0};
@@ -1146,6 +1169,66 @@ __global__ __launch_bounds__(LKB_T) void k_lk_batch_general(const uint8_t* __res
         const LKBlock bk = blocks[b];
         const LKResult r = lk_track_general<LKB_T, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), bk.x, bk.y, P);
         lk_store(r, bk.track, out_xy, out_status, out_err, out_work);
+        __syncthreads();
+    }
+}
+// ---- the extended calls (pmv_lk_track_ex, pmv_lk_track_fb and their session forms) -----------------------------------------------------
+// The same two device functions with EX = true: an initial flow, minEig as the error measure, and - LKX_FB - the forward-backward check as a
+// mode: the workgroup that took the track forward takes the result back into the first frame, slot pointers swapped, the original position
+// as its initial flow. ONE call site of the tracker in a two-trip loop; the second trip is a workgroup-uniform decision (flags and the
+// forward status are the same in every lane). A track whose forward status is 0 makes no second trip: back status 0, back err 0, back
+// position = the bits of its forward position.
+struct LKExOut { float* xy; uint8_t* status; float* err; uint16_t* work; float* back_xy; uint8_t* back_status; float* back_err; };
+__device__ __forceinline__ float uniform_f32(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+template <int T, bool GENERAL, class LRef>
+__device__ __forceinline__ void lk_track_ex(const uint8_t* a, const uint8_t* b, LRef L, float px, float py, float ix, float iy, int flags,
+                                            const LKParams& P, const int t, const LKExOut& O) {
+    const bool fb = (flags & LKX_FB) != 0;
+    int n_iter = 0, n_lev = 0;
+#pragma nounroll
+    for (int trip = 0; trip < 2; trip++) {
+        LKResult r;
+        if constexpr (GENERAL) r = lk_track_general<T, LRef, true>(a, b, L, px, py, P, ix, iy, flags);
+        else r = lk_track_block<T, false, LRef, true>(a, b, L, px, py, P, false, ix, iy, flags);
+        n_iter += r.n_iter; n_lev += r.n_lev;
+        if (trip == 1) {
+            if (threadIdx.x == 0) { O.back_xy[2 * t] = r.x; O.back_xy[2 * t + 1] = r.y; O.back_status[t] = (uint8_t)r.status; O.back_err[t] = r.err; }
+            break;
+        }
+        if (threadIdx.x == 0) {
+            O.xy[2 * t] = r.x; O.xy[2 * t + 1] = r.y; O.status[t] = (uint8_t)r.status; O.err[t] = r.err;
+            if (fb && !r.status) { O.back_xy[2 * t] = r.x; O.back_xy[2 * t + 1] = r.y; O.back_status[t] = 0; O.back_err[t] = 0.f; }
+        }
+        if (!fb || !r.status) break;   // workgroup-uniform
+        const uint8_t* const a0 = a; a = b; b = a0;
+        ix = px; iy = py; px = r.x; py = r.y;
+        flags = LKX_INIT | (flags & LKX_EIG);
+        __syncthreads();   // the forward trip is done with the tiles
+    }
+    // both directions in the track's one work word: 8 bits of iterations (saturating), <= 10 level passes
+    if (threadIdx.x == 0 && O.work) O.work[t] = (uint16_t)((n_iter > 255 ? 255 : n_iter) | (n_lev << 8));
+}
+// init_xy is read only with LKX_INIT; back_* only written with LKX_FB
+template <bool GENERAL>
+__global__ __launch_bounds__(LK_T) void k_lk_ex(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, PyrLayout L,
+                                                const float* __restrict__ prev_xy, const float* __restrict__ init_xy, const int* __restrict__ order,
+                                                int n, int flags, LKParams P, LKExOut O) {
+    const int t = order[blockIdx.x];   // as k_lk
+    if (t < 0 || t >= n) return;
+    float ix = 0.f, iy = 0.f;
+    if (flags & LKX_INIT) { ix = init_xy[2 * t]; iy = init_xy[2 * t + 1]; }
+    lk_track_ex<LK_T, GENERAL, const PyrLayout&>(prevS, nextS, L, uniform_f32(prev_xy[2 * t]), uniform_f32(prev_xy[2 * t + 1]), uniform_f32(ix), uniform_f32(iy), flags, P, t, O);
+}
+// the batched form: ext[b] belongs to blocks[b]
+template <bool GENERAL>
+__global__ __launch_bounds__(LKB_T) void k_lk_batch_ex(const uint8_t* __restrict__ slots, const LKBlock* __restrict__ blocks, const LKExt* __restrict__ ext,
+                                                       int n_blocks, const PyrLayout* __restrict__ geom, LKParams P, LKExOut O) {
+    for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {   // as k_lk_batch
+        const LKBlock bk = blocks[b];
+        const LKExt ex = ext[b];
+        lk_track_ex<LKB_T, GENERAL, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), uniform_f32(bk.x), uniform_f32(bk.y),
+                                                uniform_f32(ex.ix), uniform_f32(ex.iy), __builtin_amdgcn_readfirstlane(ex.flags), P,
+                                                __builtin_amdgcn_readfirstlane(bk.track), O);
         __syncthreads();
     }
 }
@@ -1198,6 +1281,40 @@ hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d
     const size_t pad = (size_t)(lds_pad > 0 ? lds_pad : 0);
     if (P.stamps) hipLaunchKernelGGL(k_lk_batch<true>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, d_geom, P, d_out_xy, d_status, d_err, d_work);
     else hipLaunchKernelGGL(k_lk_batch<false>, grid, dim3(LKB_T), pad, s, slots, d_blocks, n_blocks, d_geom, P, d_out_xy, d_status, d_err, d_work);
+    return hipGetLastError();
+}
+
+static bool lk_ex_args_ok(int flags, const float* d_xy, const uint8_t* d_status, const float* d_err, const float* d_back_xy, const uint8_t* d_back_status, const float* d_back_err) {
+    return !(flags & ~(LKX_INIT | LKX_EIG | LKX_FB)) && d_xy && d_status && d_err && (!(flags & LKX_FB) || (d_back_xy && d_back_status && d_back_err));
+}
+hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const float* d_init_xy,
+                        const int* d_order, int n_blocks, int n, int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work,
+                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err) {
+    if (n <= 0) return hipSuccess;
+    if (!prev_slot || !next_slot || !d_prev_xy || !d_order || n_blocks < n || L.n_levels < 1 || L.n_levels > MAX_LEVELS || ((flags & LKX_INIT) && !d_init_xy) ||
+        !lk_ex_args_ok(flags, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
+    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err};
+    if (lk_use_general(P)) {
+        if (!lk_params_ok(P)) return hipErrorInvalidValue;
+        ProfScope ps(K_LK, s);
+        hipLaunchKernelGGL(k_lk_ex<true>, dim3(n_blocks), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O);
+        return hipGetLastError();
+    }
+    ProfScope ps(K_LK, s);
+    hipLaunchKernelGGL(k_lk_ex<false>, dim3(n_blocks), dim3(LK_T), 0, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O);
+    return hipGetLastError();
+}
+hipError_t launch_lk_batch_ex(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, const LKExt* d_ext, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
+                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err) {
+    if (n_blocks <= 0) return hipSuccess;
+    // (the records carry the flags: a launch that may hold LKX_FB records needs the three back arrays)
+    if (!slots || !d_blocks || !d_ext || !d_geom || !lk_ex_args_ok(LKX_FB, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
+    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err};
+    ProfScope ps(K_LK, s);
+    if (lk_use_general(P)) {
+        if (!lk_params_ok(P)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_lk_batch_ex<true>, dim3(n_blocks), dim3(LKB_T), (size_t)lkg_lds(P.win).total, s, slots, d_blocks, d_ext, n_blocks, d_geom, P, O);
+    } else hipLaunchKernelGGL(k_lk_batch_ex<false>, dim3(n_blocks), dim3(LKB_T), 0, s, slots, d_blocks, d_ext, n_blocks, d_geom, P, O);
     return hipGetLastError();
 }
 

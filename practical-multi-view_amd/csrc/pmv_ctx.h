@@ -61,6 +61,9 @@ struct pmv_ctx {
     int *h_knn = nullptr, *d_knn = nullptr;      // kNN matcher coordinates: [src 2n | cmp 2m] ints, 2 * max_tracks pairs
     unsigned long long* d_lk_stamps = nullptr;   // diagnostic (PMV_LK_STAMPS=1)
     uint16_t* h_work = nullptr; uint16_t* dm_work = nullptr;   // per-track LK work of pmv_lk_track (mapped pinned, see launch_lk)
+    // pmv_lk_track_ex / _fb: the extra inputs and outputs, one mapped pinned block made by the first such call (a context that never makes
+    // one pays nothing): [initial flow 2 nt floats | back positions 2 nt floats | back err nt floats | back status nt bytes], nt = max_tracks
+    uint8_t* h_lkx = nullptr; uint8_t* dm_lkx = nullptr;
     std::atomic<unsigned long long> lk_work[3];  // host-side sums: LK iterations, level passes, tracks (pmv_lk_counters)
     void add_lk_work(const uint16_t* w, size_t n) { unsigned long long it = 0, lv = 0; for (size_t i = 0; i < n; i++) { it += w[i] & 0xffu; lv += w[i] >> 8; } lk_work[0] += it; lk_work[1] += lv; lk_work[2] += n; }
     // detectors
@@ -127,6 +130,9 @@ void batch_session_destroy(pmv_ctx* ctx);   // joins the upload thread, frees th
 // The argument checks of the front-end calls, shared by the single-sequence entry points (bracket = true: a slot of an open
 // pmv_frames_stream_begin bracket first waits for its round on the front-end stream) and the session calls of the same name (bracket =
 // false): the same status codes in the same places, from one copy. ctx is not null. max_per_cell of detect_check: already >= 1.
+// what the extended calls check on top of lk_check (`who` names the call in the messages): the flag bits, the back outputs of a
+// forward-backward call (fb), and with PMV_LK_USE_INITIAL_FLOW every initial coordinate (finite, |v| <= 1e6). Before lk_check: null back pointers.
+int lkx_check(pmv_ctx* ctx, const char* who, int flags, const float* next_xy, int n, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err);
 int lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* out_xy, const uint8_t* out_status, const float* out_err);
 int knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, const int* out_best,
               const float* out_err);

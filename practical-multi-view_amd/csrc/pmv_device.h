@@ -165,9 +165,21 @@ struct __attribute__((aligned(32))) LKBlock {
     int geom;                                // the sequence's entry of the geometry table
 };
 static_assert(sizeof(LKBlock) == 32, "LKBlock: one 32-byte record per workgroup");
+// The extended calls (pmv_lk_track_ex / _fb): the two cv flag values, and the forward-backward mode as an internal third bit. A workgroup of
+// the extended batch kernels reads, next to its LKBlock, the record of the same index in a second array: LKBlock keeps its 32 bytes and
+// k_lk_batch its records. An LKX_FB record's back results go to index `track` of the launch's three back arrays.
+constexpr int LKX_INIT = 4, LKX_EIG = 8, LKX_FB = 0x100;
+struct __attribute__((aligned(16))) LKExt {
+    float ix, iy;      // where the top level's search starts (level-0 coordinates), read with LKX_INIT
+    int flags;         // LKX_*
+    int reserved;
+};
+static_assert(sizeof(LKExt) == 16, "LKExt: one 16-byte record per workgroup");
 // d_geom: the geometry table in device memory; every record's `geom` is an entry of it (the caller's business, on the host)
 hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
                            float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
+hipError_t launch_lk_batch_ex(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, const LKExt* d_ext, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
+                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
 hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, int stride, uint8_t* d_gray);   // cv::cvtColor(BGR2GRAY), 8-bit
 // one entry of a slot-list pyramid build (the feeder): destination slot and, for level 0, the device-visible address of the tight gray
 // frame (HBM landing area or mapped pinned host memory), null = already staged in the slot; `geom` = the frame's entry of the geometry table
@@ -196,6 +208,10 @@ hipError_t launch_pad_level0_bgr_pitched(hipStream_t s, uint8_t* slots, const Py
 hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L,
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
+// One launch of the extended form: `flags` (LKX_*) holds for every track, d_init_xy is read with LKX_INIT, the back arrays are written with LKX_FB.
+hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const float* d_init_xy,
+                        const int* d_order, int n_blocks, int n, int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work,
+                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
 // d_work (optional), per track: LK iterations executed over all levels | (level passes that iterated) << 8 - what the track cost. The
 // roofline's OPS_lk is summed from these on the host (three atomics per track on shared counters cost the batched launch 14 % of the
 // whole run's throughput: every wavefront of the chip ended on the same three L2 lines).
