@@ -8,6 +8,8 @@
  *                                          implicit inside OpenCVLucasKanadeFM.cpp:15)
  *   pmv_detect_gftt                        cv::goodFeaturesToTrack per grid cell         (OpenCVGoodFeatureExtractor.cpp:7,
  *                                          called from OdometryPipeline.cpp:357 / :450)  -> BaseFeatureExtractor.h:21
+ *   pmv_detect_gftt_ex                     cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector, k (a KLT front end
+ *                                          of the caller's own; the reference passes cv::Mat(), 3, 3, false, 0.04)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -117,6 +119,45 @@ int pmv_frame_get_level_padded(pmv_ctx* ctx, int slot, int level, uint8_t* out, 
 #define PMV_GFTT_UNLIMITED_CAP 4096
 int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                     double min_dist, int* out_xy, int* out_count);
+/* cv::goodFeaturesToTrack with the caller's remaining arguments: mask, blockSize, useHarrisDetector, k. pmv_detect_gftt is this call
+ * frozen at the reference's `cv::Mat(), 3, 3, false, 0.04` (OpenCVGoodFeatureExtractor.cpp:7); a KLT loop that refills its tracks calls
+ * the detector with a mask that keeps new corners away from the tracks it has, often with a larger block or the Harris response.
+ *   Cells, outputs and limits: exactly those of pmv_detect_gftt - sub-views of the frame in `slot`, at most 255x255 and at least 3x3,
+ *     cell-local coordinates in cv's order, max_per_cell <= 0 = no limit with PMV_GFTT_UNLIMITED_CAP and PMV_ERR_OVERFLOW.
+ *   mask: NULL = no mask. Otherwise host memory of the size of the slot's level-0 frame, mask_stride bytes per row; a non-zero byte
+ *     allows the pixel. A cell sees the sub-view of the mask at its own rectangle: what cv::goodFeaturesToTrack(cell, ..., mask(cellRect),
+ *     ...) sees. The mask cannot be applied afterwards: the quality threshold is quality x the maximum over the ALLOWED pixels (a cell
+ *     without one has maximum 0 and returns nothing), the 3x3 non-maximum test still looks at every neighbour, masked-out ones included,
+ *     and a pixel becomes a corner candidate only if its own byte is non-zero.
+ *   block_size: the un-normalised block_size x block_size box over cov = (dx^2, dx dy, dy^2), anchor block_size / 2 (offsets -b/2 ..
+ *     b-1-b/2: an even size leans to the upper left), REFLECT_101 on the CELL as often as needed; Sobel 3x3 with the scale
+ *     1 / (4 block_size 255), its border the parent frame's as in pmv_detect_gftt.
+ *   use_harris: the response is (float)(a c - b b - k (a + c)(a + c)) over the un-halved sums instead of the smaller eigenvalue. With
+ *     quality in (0, 1] only responses above 0 can be selected, so a cell whose Harris response is nowhere positive returns nothing.
+ *   Defaults: {q, d, 3, 0, any k} with a NULL mask returns the bytes of pmv_detect_gftt(q, d) and runs the tuned kernels (k_gftt_cand);
+ *     everything else runs k_gftt_cand_general. Both feed the same k_gftt_pick, under the same two profiling classes.
+ *   [mem: OpenCV 3.4 cornerEigenValsVecs, calcMinEigenVal, calcHarris, goodFeaturesToTrack; parity unpinned like the rest of the
+ *   detector - tests/twin/gftt_twin.cpp is the CPU restatement that fixes the arithmetic, bit for bit.]
+ * Errors (nothing is written on any of them): PMV_ERR_INVALID - null p or null outputs, block_size outside 1..15, quality outside (0, 1]
+ *   or not finite, min_dist negative or not finite, k not finite while use_harris is set; PMV_ERR_CAPACITY - mask_stride below the frame
+ *   width while a mask is given (as for the upload strides); the cell and slot errors of pmv_detect_gftt.
+ * The device buffers of the mask are made by the first extended call with a mask on a context: the host packs the cells' mask sub-views
+ *   tightly into pinned memory, so only the bytes under the cells cross the bus.
+ * Out of scope: the Sobel aperture (gradientSize) stays 3; corner sub-pixel refinement is the caller's (cv::cornerSubPix). */
+typedef struct pmv_gftt_params {
+    double quality;      /* qualityLevel, 0 < quality <= 1 */
+    double min_dist;     /* minDistance, as pmv_detect_gftt */
+    int    block_size;   /* blockSize, 1 .. 15; default 3 */
+    int    use_harris;   /* useHarrisDetector */
+    double k;            /* Harris k, finite; ignored without use_harris */
+} pmv_gftt_params;
+int pmv_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                       int mask_stride, int* out_xy, int* out_count);
+/* Debug/parity: the float32 response map of one cell for p's block_size, use_harris and k (quality and min_dist are checked, not used). */
+int pmv_debug_gftt_response_ex(pmv_ctx* ctx, int slot, const int* cell, const pmv_gftt_params* p, float* out);
+/* diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex (block 3, no Harris, no mask) through the general kernels as
+ * well, single and session calls alike, so that a test can compare the two code paths. It changes no result. */
+int pmv_debug_gftt_general(pmv_ctx* ctx, int on);
 /* Same geometry; out_score: n_cells * max_per_cell doubles (the reference fills Feature::score). max_per_cell <= 0 returns no
  * features (ShiTomasiFeatureExtractor.cpp:37-44). */
 int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
@@ -484,6 +525,11 @@ int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src
                         int* out_best, float* out_err);
 int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
                           int* out_count);
+/* pmv_detect_gftt_ex as a session call: the same arguments, bits and status codes. Requests that agree in block_size, use_harris, k and
+ * has-mask (and, as before, in quality, min_dist, max_per_cell and frame size) share a launch; a round without extended requests launches
+ * what it launched before. The mask is read before the call returns. */
+int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                             int mask_stride, int* out_xy, int* out_count);
 int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
                                int* out_count);
 int pmv_batch_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy,

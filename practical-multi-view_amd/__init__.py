@@ -36,6 +36,11 @@ class LKParams(C.Structure):
     _fields_ = [("win", C.c_int), ("max_level", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double), ("min_eig", C.c_float)]
 
 
+class GfttParams(C.Structure):
+    """pmv_gftt_params of include/pmv_hip.h"""
+    _fields_ = [("quality", C.c_double), ("min_dist", C.c_double), ("block_size", C.c_int), ("use_harris", C.c_int), ("k", C.c_double)]
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 # the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
 LK_USE_INITIAL_FLOW = 4
@@ -45,6 +50,7 @@ ABI_SYMBOLS = [
     "pmv_ctx_create", "pmv_ctx_destroy", "pmv_last_error", "pmv_thread_error", "pmv_sync",
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
+    "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -444,6 +450,45 @@ class Context:
         self._ck(self.lib.pmv_detect_gftt(self.h, slot, _p(cells, _i32p), n, max_per_cell, C.c_double(quality),
                                           C.c_double(min_dist), _p(xy, _i32p), _p(cnt, _i32p)))
         return [xy[i, : cnt[i]].copy() for i in range(n)]
+
+    def _gftt_ex(self, fn, ck, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k):
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
+        n = cells.shape[0]
+        cap = max_per_cell if max_per_cell > 0 else GFTT_UNLIMITED_CAP
+        xy = np.zeros((n, cap, 2), np.int32)
+        cnt = np.zeros(n, np.int32)
+        p = GfttParams(float(quality), float(min_dist), int(block_size), 1 if use_harris else 0, float(k))
+        mptr, mstride = None, 0
+        if mask is not None:
+            # passed in place with its own row stride (a view into a larger array is not copied tight); the library checks it against the frame
+            if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.ndim != 2 or (mask.shape[1] > 1 and mask.strides[1] != 1):
+                raise ValueError("detect_gftt_ex: mask must be an (h, w) uint8 array whose rows are contiguous (any row stride)")
+            # the library reads the mask under the cells only: a mask smaller than the frame must still cover every cell
+            if n and ((cells[:, 0] + cells[:, 2]).max() > mask.shape[1] or (cells[:, 1] + cells[:, 3]).max() > mask.shape[0] or cells[:, :2].min() < 0):
+                raise ValueError(f"detect_gftt_ex: a cell lies outside the {mask.shape[1]}x{mask.shape[0]} mask (the mask has the frame's size)")
+            mptr, mstride = C.cast(C.c_void_p(mask.ctypes.data), _u8p), int(mask.strides[0]) if mask.shape[0] > 1 else max(int(mask.strides[0]), mask.shape[1])
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(GfttParams), _u8p, C.c_int, _i32p, _i32p]
+        ck(fn(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.byref(p), mptr, mstride, _p(xy, _i32p), _p(cnt, _i32p)))
+        return [xy[i, : cnt[i]].copy() for i in range(n)]
+
+    def detect_gftt_ex(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04):
+        """pmv_detect_gftt_ex: detect_gftt with cv::goodFeaturesToTrack's remaining arguments. mask: None or an (h, w) uint8 array of the frame's
+        size (non-zero = allowed; any row stride), each cell sees its own rectangle of it; block_size 1..15; use_harris with k. The defaults
+        return detect_gftt's arrays."""
+        return self._gftt_ex(self.lib.pmv_detect_gftt_ex, self._ck, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k)
+
+    def gftt_response_ex(self, slot, cell, block_size=3, use_harris=False, k=0.04):
+        """pmv_debug_gftt_response_ex: the float32 response map of one cell for this block size and response kind"""
+        cell = np.ascontiguousarray(cell, np.int32)
+        out = np.zeros((cell[3], cell[2]), np.float32)
+        p = GfttParams(0.01, 5.0, int(block_size), 1 if use_harris else 0, float(k))
+        self.lib.pmv_debug_gftt_response_ex.argtypes = [C.c_void_p, C.c_int, _i32p, C.POINTER(GfttParams), _f32p]
+        self._ck(self.lib.pmv_debug_gftt_response_ex(self.h, int(slot), _p(cell, _i32p), C.byref(p), _p(out, _f32p)))
+        return out
+
+    def debug_gftt_general(self, on):
+        """diagnostic: detect_gftt_ex's default arguments through the general kernels as well (pmv_debug_gftt_general); changes no result"""
+        self._ck(self.lib.pmv_debug_gftt_general(self.h, 1 if on else 0))
 
     def detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
@@ -914,6 +959,10 @@ class Context:
         self._ckt(self.lib.pmv_batch_detect_gftt(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), C.c_double(min_dist),
                                                 _p(xy, _i32p), _p(cnt, _i32p)))
         return [xy[i, : cnt[i]].copy() for i in range(n)]
+
+    def batch_detect_gftt_ex(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04):
+        """pmv_batch_detect_gftt_ex: detect_gftt_ex as a session call (same arguments, same arrays)"""
+        return self._gftt_ex(self.lib.pmv_batch_detect_gftt_ex, self._ckt, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k)
 
     def batch_detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)

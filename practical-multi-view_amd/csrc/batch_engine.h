@@ -25,6 +25,11 @@ int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev
                  float* back_xy, uint8_t* back_status, float* back_err);
 int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                   double min_dist, int* out_xy, double* out_score, int* out_count, int ring_round = -1);
+// pmv_detect_gftt_ex's contract, arguments already checked: a GFTT request that carries the caller's block size, response kind, k and optional
+// mask (host memory, read by the combiner before the call returns). The reference's arguments without a mask are a plain GFTT request unless
+// pmv_debug_gftt_general is on.
+int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                          int mask_stride, int* out_xy, int* out_count);
 // pmv_detect_fast's contract (a cell may be as large as the frame; max_per_cell <= 0: empty lists, no launch): a request of the detector combiner
 int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                        int* out_count, int ring_round = -1);

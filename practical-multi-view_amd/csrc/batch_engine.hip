@@ -35,7 +35,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT, 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
+    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -70,6 +70,9 @@ struct DetReq : Req {
     float* out_resp = nullptr;                    // FAST: KeyPoint::response per keypoint
     int cell_base = 0;
     int ring_round = -1;      // as LKReq::ring_round
+    // GFTT through the general kernels (pmv_batch_detect_gftt_ex): the caller's block size, response kind and k, and the optional host mask
+    int ext = 0, block_size = 3, use_harris = 0; double k = 0.0;
+    const uint8_t* mask = nullptr; int mask_stride = 0;
 };
 struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
@@ -120,6 +123,9 @@ struct Combiner {
     double t_cpu = 0;                            // CPU seconds of the combiner thread itself
     // LK staging + mapped pinned result blocks; detector buffers (only used by combiners of those classes)
     Growable h_front{nullptr, 0, true}, d_front, h_cells{nullptr, 0, true}, d_cells, d_eig, d_cellmax, d_spill, d_det_xy, d_det_score, d_det_count, h_det{nullptr, 0, true};
+    // masks of the extended GFTT requests of a round (detector combiner, made by the first round that has one): the cells' mask sub-views
+    // packed one after the other, pinned mirror and HBM copy
+    Growable h_gmask{nullptr, 0, true}, d_gmask;
     // kNN matcher rounds (LK combiners): [stage-in job | request records | coordinate lists], pinned mirror and HBM copy; FAST score maps (detector combiner)
     Growable h_knn{nullptr, 0, true}, d_knn, d_fast_score;
     // extended LK requests (LK combiners, made by the first round that has one): [LKBlock | LKExt] records of a round; back results of
@@ -423,9 +429,11 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
     // FAST (kind 3; grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
     // its score maps are sized by the pixels of the round (d_fast_score), the cell record's offset into them stays within int.
-    struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; int max_pix = 0; };
+    // Extended GFTT requests (ext) also agree in block size, response kind, k and has-mask; a round without one launches what it always did.
+    struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; int max_pix = 0;
+                   int ext = 0, block_size = 3, use_harris = 0; double k = 0.0; bool has_mask = false; };
     std::vector<Group> groups;
-    size_t fast_pix = 0;
+    size_t fast_pix = 0, mask_bytes = 0;
     for (DetReq* r : det) {
         const PyrLayout& Lr = ctx->slot_layout[r->slot];
         if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d holds no built pyramid", r->slot); continue; }
@@ -435,11 +443,20 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             if (fast_pix + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch FAST: the cells of the round cover more than 2^31 pixels"); continue; }
             fast_pix += pix;
         }
+        size_t mask_pix = 0;
+        if (r->mask) for (int i = 0; i < r->n_cells; i++) mask_pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
+        if (mask_bytes + mask_pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
+        mask_bytes += mask_pix;
         Group* g = nullptr;
         for (Group& x : groups)
             if (x.kind == r->kind && x.max_per_cell == r->max_per_cell && x.unlimited == r->unlimited && x.quality == r->quality && x.min_dist == r->min_dist &&
+                x.ext == r->ext && (!r->ext || (x.block_size == r->block_size && x.use_harris == r->use_harris && x.k == r->k && x.has_mask == (r->mask != nullptr))) &&
                 x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
-        if (!g) { groups.push_back(Group{r->kind, r->max_per_cell, r->unlimited, r->quality, r->min_dist, Lr, {}, 0, 0}); g = &groups.back(); }
+        if (!g) {
+            groups.push_back(Group{r->kind, r->max_per_cell, r->unlimited, r->quality, r->min_dist, Lr, {}, 0, 0});
+            g = &groups.back();
+            if (r->ext) { g->ext = 1; g->block_size = r->block_size; g->use_harris = r->use_harris; g->k = r->k; g->has_mask = r->mask != nullptr; }
+        }
         r->cell_base = g->n_cells;
         g->n_cells += r->n_cells;
         g->reqs.push_back(r);
@@ -453,15 +470,21 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         EK(C.h_cells.ensure(cells_bytes + 64));   // (+ the stage-in job of a round with FAST cells)
         EK(C.d_eig.ensure(eig_cells * CELL_PIX * sizeof(double))); EK(C.d_cellmax.ensure(eig_cells * 8)); EK(C.d_spill.ensure(eig_cells * CELL_PIX * 4));
         EK(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // [xy | score | count | flags], written by the kernels through the mapped alias
+        if (mask_bytes) { EK(C.h_gmask.ensure(mask_bytes + 64)); EK(C.d_gmask.ensure(mask_bytes + 64)); }
         int* hc = (int*)C.h_cells.p;
-        size_t cpos = 0, fpos = 0;
+        size_t cpos = 0, fpos = 0, mpos = 0;
         for (Group& g : groups)
-            for (DetReq* r : g.reqs)
+            for (DetReq* r : g.reqs) {
+                if (r->mask) mpos = gftt_pack_mask((uint8_t*)C.h_gmask.p, mpos, hc + cpos * CELL_STRIDE, r->cells, r->n_cells, r->mask, r->mask_stride);
+                const bool masked = r->mask != nullptr;
                 for (int i = 0; i < r->n_cells; i++, cpos++) {
                     int* d = hc + cpos * CELL_STRIDE;
-                    d[0] = r->cells[4 * i]; d[1] = r->cells[4 * i + 1]; d[2] = r->cells[4 * i + 2]; d[3] = r->cells[4 * i + 3]; d[4] = r->slot; d[5] = d[6] = d[7] = 0;
+                    d[0] = r->cells[4 * i]; d[1] = r->cells[4 * i + 1]; d[2] = r->cells[4 * i + 2]; d[3] = r->cells[4 * i + 3]; d[4] = r->slot; d[6] = d[7] = 0;
+                    if (!masked) d[5] = 0;   // (a masked cell's int 5 = the offset of its mask bytes, written by gftt_pack_mask)
                     if (g.kind == 3) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
                 }
+            }
+        if (mask_bytes) EK(hipMemcpyAsync(C.d_gmask.p, C.h_gmask.p, mask_bytes, hipMemcpyHostToDevice, s));
         if (fast_pix > 0) {
             // every thread of k_fast_score reads its cell record: the records of the round go to HBM by one gather (no DMA call)
             EK(C.d_cells.ensure(cells_bytes + 64)); EK(C.d_fast_score.ensure(fast_pix + 64));
@@ -484,7 +507,11 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             int* dxy = (int*)dd + g.out_off * 2;
             double* dsc = (double*)(dd + tot_out * 8) + g.out_off;
             int* dcnt = (int*)(dd + tot_out * 16) + c0;
-            if (g.kind == 1)
+            if (g.kind == 1 && g.ext)
+                EK(launch_gftt_ex(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, gftt_ext(g.block_size, g.use_harris, g.k),
+                                  g.has_mask ? (const uint8_t*)C.d_gmask.p : nullptr, (float*)C.d_eig.p + e0 * CELL_PIX, (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt,
+                                  C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+            else if (g.kind == 1)
                 EK(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + e0 * CELL_PIX,
                                (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
             else if (g.kind == 2)
@@ -780,7 +807,7 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
             if (C.h_done) (void)hipHostFree(C.h_done);
-            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back}) g->release();
+            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back, &C.h_gmask, &C.d_gmask}) g->release();
             if (C.h_out_xy) (void)hipHostFree(C.h_out_xy);
             if (C.h_err) (void)hipHostFree(C.h_err);
             if (C.h_status) (void)hipHostFree(C.h_status);
@@ -943,6 +970,20 @@ int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_ce
     }
     r.quality = quality; r.min_dist = min_dist; r.out_xy = out_xy; r.out_score = out_score; r.out_count = out_count;
     r.ring_round = ring_round;
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                          int mask_stride, int* out_xy, int* out_count) {
+    pmv_ctx* ctx = E->ctx;
+    if (p->block_size == 3 && !p->use_harris && !mask && !ctx->gftt_general)
+        return engine_detect(E, 1, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, nullptr, out_count);
+    DetReq r;
+    r.kind = 1; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
+    r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
+    r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count;
+    r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
+    r.mask = mask; r.mask_stride = mask_stride;
     return submit(ctx, E->queue[R_DET], &r);
 }
 

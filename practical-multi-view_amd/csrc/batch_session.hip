@@ -436,6 +436,15 @@ int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells,
     return engine_detect(S->eng, 1, slot, cells, n_cells, max_per_cell, quality, min_dist, out_xy, nullptr, out_count);
 }
 
+int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                             int mask_stride, int* out_xy, int* out_count) {
+    SESSION("pmv_batch_detect_gftt_ex");
+    if (const int rc = gftt_ex_check(ctx, "pmv_batch_detect_gftt_ex", p, out_xy, out_count)) return rc;
+    if (const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell)) return rc;
+    if (const int rc = gftt_mask_check(ctx, "pmv_batch_detect_gftt_ex", slot, mask, mask_stride)) return rc;
+    return engine_detect_gftt_ex(S->eng, slot, cells, n_cells, max_per_cell, p, mask, mask_stride, out_xy, out_count);
+}
+
 int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
                                int* out_count) {
     SESSION("pmv_batch_detect_shitomasi");

@@ -5,6 +5,7 @@
 #include <vector>
 #include <cstdarg>
 #include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -163,6 +164,8 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->d_geom) hipFree(c->d_geom);
     if (c->h_work) hipHostFree(c->h_work);
     if (c->h_lkx) hipHostFree(c->h_lkx);
+    if (c->h_gmask) hipHostFree(c->h_gmask);
+    if (c->d_gmask) hipFree(c->d_gmask);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
     hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
@@ -526,6 +529,27 @@ int pmv::detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, in
     }
     return PMV_OK;
 }
+int pmv::gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, const int* out_xy, const int* out_count) {
+    REQ(p && out_xy && out_count, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(p->block_size >= 1 && p->block_size <= GFTT_MAX_BLOCK, PMV_ERR_INVALID, "%s: block_size = %d is outside 1..%d", who, p->block_size, GFTT_MAX_BLOCK);
+    REQ(p->quality > 0.0 && p->quality <= 1.0, PMV_ERR_INVALID, "%s: quality = %g is outside (0, 1]", who, p->quality);   // (a NaN fails the comparison too)
+    REQ(p->min_dist >= 0.0 && std::isfinite(p->min_dist), PMV_ERR_INVALID, "%s: min_dist = %g is negative or not finite", who, p->min_dist);
+    REQ(!p->use_harris || std::isfinite(p->k), PMV_ERR_INVALID, "%s: k = %g is not finite", who, p->k);
+    return PMV_OK;
+}
+int pmv::gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t* mask, int mask_stride) {   // after detect_check: the slot is valid
+    REQ(!mask || mask_stride >= ctx->slot_layout[slot].w[0], PMV_ERR_CAPACITY, "%s: mask_stride = %d is below the frame width %d", who, mask_stride, ctx->slot_layout[slot].w[0]);
+    return PMV_OK;
+}
+// the cells' mask sub-views one after the other (cw * ch bytes each); the byte offset of each goes into int 5 of its device cell record
+size_t pmv::gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* cells, int n_cells, const uint8_t* mask, int mask_stride) {
+    for (int i = 0; i < n_cells; i++) {
+        const int* c = cells + 4 * i;
+        cell_recs[(size_t)i * CELL_STRIDE + 5] = (int)pos;
+        for (int y = 0; y < c[3]; y++, pos += (size_t)c[2]) memcpy(dst + pos, mask + (size_t)(c[1] + y) * (size_t)mask_stride + c[0], (size_t)c[2]);
+    }
+    return pos;
+}
 static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell) {   // max_per_cell: already >= 1
     REQ(ctx, PMV_ERR_INVALID, "detect: null argument");
     return detect_check(ctx, true, slot, cells, n_cells, max_per_cell);
@@ -565,6 +589,54 @@ int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
     REQ((ctx->h_det_count[MAX_CELLS] & 4) == 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt: more than %d corners in a cell with max_per_cell <= 0 (no limit)", MAX_PER_CELL);
     memcpy(out_xy, ctx->h_det_xy, nxy);
     memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
+    return PMV_OK;
+}
+
+// cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector and k. The reference's arguments (3, false, no mask) are
+// pmv_detect_gftt itself - the tuned kernels - unless pmv_debug_gftt_general sends them through the general ones.
+int pmv_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
+                       int mask_stride, int* out_xy, int* out_count) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_detect_gftt_ex: null argument");
+    int rc = gftt_ex_check(ctx, "pmv_detect_gftt_ex", p, out_xy, out_count);
+    if (rc) return rc;
+    const int unlimited = max_per_cell <= 0;
+    const int cap = unlimited ? MAX_PER_CELL : max_per_cell;
+    rc = check_cells(ctx, slot, cells, n_cells, cap);
+    if (rc) return rc;
+    rc = gftt_mask_check(ctx, "pmv_detect_gftt_ex", slot, mask, mask_stride);
+    if (rc) return rc;
+    if (p->block_size == 3 && !p->use_harris && !mask && !ctx->gftt_general)
+        return pmv_detect_gftt(ctx, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, out_count);
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const PyrLayout& L = ctx->slot_layout[slot];
+    pack_cells(ctx->h_cells, cells, n_cells, slot);
+    if (mask) {
+        if (!ctx->h_gmask) {
+            CKC(hipHostMalloc(&ctx->h_gmask, (size_t)MAX_CELLS * CELL_PIX, hipHostMallocDefault));
+            CKC(hipMalloc(&ctx->d_gmask, (size_t)MAX_CELLS * CELL_PIX));
+        }
+        const size_t nb = gftt_pack_mask(ctx->h_gmask, 0, ctx->h_cells, cells, n_cells, mask, mask_stride);
+        CKC(hipMemcpyAsync(ctx->d_gmask, ctx->h_gmask, nb, hipMemcpyHostToDevice, ctx->s_front));
+    }
+    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
+    CKC(hipMemsetAsync(ctx->d_flags, 0, 16, ctx->s_front));
+    CKC(launch_gftt_ex(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, cap, p->quality, p->min_dist, unlimited, gftt_ext(p->block_size, p->use_harris, p->k),
+                       mask ? ctx->d_gmask : nullptr, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill));
+    const size_t nxy = (size_t)n_cells * cap * 8;
+    CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nxy, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipMemcpyAsync(ctx->h_det_count, ctx->d_det_count, (size_t)n_cells * 4, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipMemcpyAsync(ctx->h_det_count + MAX_CELLS, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    REQ((ctx->h_det_count[MAX_CELLS] & 4) == 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt_ex: more than %d corners in a cell with max_per_cell <= 0 (no limit)", MAX_PER_CELL);
+    memcpy(out_xy, ctx->h_det_xy, nxy);
+    memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
+    return PMV_OK;
+}
+// diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex through the general kernels as well (no result changes)
+int pmv_debug_gftt_general(pmv_ctx* ctx, int on) {
+    REQ(ctx, PMV_ERR_INVALID, "null ctx");
+    ctx->gftt_general = on != 0;
     return PMV_OK;
 }
 
@@ -666,6 +738,23 @@ int pmv_debug_gftt_response(pmv_ctx* ctx, int slot, const int* cell, float* out)
     pack_cells(ctx->h_cells, cell, 1, slot);
     CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
     CKC(launch_gftt_response(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], ctx->d_cells, 1, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    CKC(hipMemcpy(out, ctx->d_eig, (size_t)cell[2] * cell[3] * sizeof(float), hipMemcpyDeviceToHost));
+    return PMV_OK;
+}
+
+int pmv_debug_gftt_response_ex(pmv_ctx* ctx, int slot, const int* cell, const pmv_gftt_params* p, float* out) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_debug_gftt_response_ex: null argument");
+    int dummy = 0;
+    int rc = gftt_ex_check(ctx, "pmv_debug_gftt_response_ex", p, &dummy, &dummy);
+    if (rc) return rc;
+    rc = check_cells(ctx, slot, cell, 1, 1);
+    if (rc) return rc;
+    REQ(out, PMV_ERR_INVALID, "null output");
+    CKC(hipSetDevice(ctx->device));
+    pack_cells(ctx->h_cells, cell, 1, slot);
+    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
+    CKC(launch_gftt_response_ex(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], ctx->d_cells, 1, gftt_ext(p->block_size, p->use_harris, p->k), (float*)ctx->d_eig));
     CKC(hipStreamSynchronize(ctx->s_front));
     CKC(hipMemcpy(out, ctx->d_eig, (size_t)cell[2] * cell[3] * sizeof(float), hipMemcpyDeviceToHost));
     return PMV_OK;

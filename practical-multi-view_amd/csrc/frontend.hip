@@ -3,6 +3,7 @@
 // All integer results (track coordinates after truncation, status bytes, corner lists) are bit-exact with oracle/:
 //   * LK: every window sum is an exact integer (per-lane int32 partials, 64-bit wave reduction), rounded once to f32;
 //   * GFTT: float32 ops in a fixed order, compiled with -ffp-contract=off; the 3x3 box sum is a 9-term double sum.
+//     pmv_detect_gftt_ex (block size 1..15, Harris, mask): the b*b-term double sum in raster order of tests/twin/gftt_twin.cpp.
 #include "pmv_device.h"
 #include "pmv_prof.h"
 #include <float.h>
@@ -1722,6 +1723,178 @@ hipError_t launch_gftt_response(hipStream_t s, const uint8_t* slots, const PyrLa
     hipError_t e = hipMemsetAsync(d_cellmax, 0, 2 * sizeof(unsigned) * n_cells, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_gftt_eig, dim3(8, 8, n_cells), dim3(256), 0, s, slots, L, d_cells, d_eig, d_cellmax);
+    return hipGetLastError();
+}
+
+// ---- the caller's goodFeaturesToTrack arguments (pmv_detect_gftt_ex): blockSize 1..15, Harris response, mask ------------------------
+// The general kernels keep k_gftt_cand's shape - a 32x32 tile per workgroup, the tile row on blockIdx.x, the response on 34x34, the
+// non-maximum test on the raw response, ballot-compacted records, one global atomic per workgroup - with the block size, the response
+// kind and the mask as RUNTIME arguments (one code object, no spills: the b x b sum is a plain nested loop over LDS). cov lives on a
+// (34 + b - 1)^2 halo in dynamic LDS as three PLANES, not as float3 records: consecutive lanes then read consecutive dwords of a plane
+// whatever the halo width, and a 32-lane group spans at most two halo rows (a gap of b - 1 dwords: at worst two lanes on one bank).
+// Window of the box filter: anchor b / 2, so offsets -b/2 .. b-1-b/2 (an even size leans to the upper left), REFLECT_101 of the CELL
+// coordinate as often as needed; the sum is the b*b-term double sum in raster order that tests/twin/gftt_twin.cpp states.
+// mask (optional): the cells' mask sub-views, cw*ch bytes each at byte offset cells[.. + 5], indexed with the y*cw+x of a record. Only
+// allowed pixels count in the tile's and the cell's maximum and only they become records; the 3x3 test looks at every neighbour.
+__device__ inline void gftt_cov_k(const uint8_t* __restrict__ p, int st, float k1, float k2, float& c0, float& c1, float& c2) {
+    const float p00 = p[-st - 1], p01 = p[-st], p02 = p[-st + 1];
+    const float p10 = p[-1], p12 = p[1];
+    const float p20 = p[st - 1], p21 = p[st], p22 = p[st + 1];
+    const float rt = p02 - p00, rm = p12 - p10, rb = p22 - p20;
+    const float dx = (rt + rb) * k1 + rm * k2;
+    float s_t = k1 * p00; s_t += k2 * p01; s_t += k1 * p02;
+    float s_b = k1 * p20; s_b += k2 * p21; s_b += k1 * p22;
+    const float dy = s_b - s_t;
+    c0 = dx * dx; c1 = dx * dy; c2 = dy * dy;
+}
+// cov planes of the tile at (tx0, ty0): halo position (hx, hy) = cell position (tx0 - 1 - b/2 + hx, ty0 - 1 - b/2 + hy), reflected
+__device__ inline void gfttg_fill(const uint8_t* __restrict__ img, int st, int cx0, int cy0, int cw, int ch, int tx0, int ty0, const GfttExt& X,
+                                  float* __restrict__ sC0, float* __restrict__ sC1, float* __restrict__ sC2) {
+    const int HS = 34 + X.bs - 1, org = 1 + X.bs / 2;
+    for (int idx = threadIdx.x; idx < HS * HS; idx += 256) {
+        const int hy = idx / HS, hx = idx - hy * HS;
+        const int lx = reflect101(tx0 - org + hx, cw), ly = reflect101(ty0 - org + hy, ch);   // inside the cell, whatever b: the loads stay in the frame
+        gftt_cov_k(img + (ptrdiff_t)(cy0 + ly) * st + (cx0 + lx), st, X.k1, X.k2, sC0[idx], sC1[idx], sC2[idx]);
+    }
+}
+// response at position (ex, ey) of the 34x34 grid (cell position (tx0 - 1 + ex, ty0 - 1 + ey)): its window starts at halo (ex, ey)
+__device__ inline float gfttg_resp(const float* __restrict__ sC0, const float* __restrict__ sC1, const float* __restrict__ sC2, int ex, int ey, const GfttExt& X) {
+    const int HS = 34 + X.bs - 1;
+    double s0 = 0, s1 = 0, s2 = 0;
+    for (int j = 0; j < X.bs; j++) {
+        const int row = (ey + j) * HS + ex;
+        for (int i = 0; i < X.bs; i++) { s0 += sC0[row + i]; s1 += sC1[row + i]; s2 += sC2[row + i]; }
+    }
+    if (X.harris) {   // (float)(a*c - b*b - k*(a + c)*(a + c)) with C++'s types: float products and difference, the k term and the last subtraction in double
+        const float a = (float)s0, b = (float)s1, c = (float)s2;
+        return (float)(a * c - b * b - X.k * (a + c) * (a + c));
+    }
+    const float a = (float)s0 * 0.5f, b = (float)s1, c2 = (float)s2 * 0.5f;
+    return (a + c2) - sqrtf((a - c2) * (a - c2) + b * b);
+}
+__global__ __launch_bounds__(256) void k_gftt_cand_general(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
+                                                           float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ cellinfo,
+                                                           double quality, GfttExt X, const uint8_t* __restrict__ mask) {
+    extern __shared__ float gfttg_lds[];
+    const int HP = (34 + X.bs - 1) * (34 + X.bs - 1);
+    float* sC0 = gfttg_lds; float* sC1 = sC0 + HP; float* sC2 = sC1 + HP;
+    float* sE = sC2 + HP;                            // [34 * 34]
+    unsigned* smax = (unsigned*)(sE + 34 * 34);      // [4]
+    BACKEND_PRIO();
+    const int cell = blockIdx.z;
+    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
+    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;   // blockIdx.x = the tile ROW: see k_gftt_cand
+    if (tx0 >= cw || ty0 >= ch) return;
+    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
+    const uint8_t* cmask = mask ? mask + (size_t)cells[CELL_STRIDE * cell + 5] : nullptr;
+    gfttg_fill(img, L.stride[0], cx0, cy0, cw, ch, tx0, ty0, X, sC0, sC1, sC2);
+    __syncthreads();
+    unsigned mk = 0;   // key 0 is below every real float key
+    for (int idx = threadIdx.x; idx < 34 * 34; idx += 256) {
+        const int ey = idx / 34, ex = idx - ey * 34;
+        const int x = tx0 - 1 + ex, y = ty0 - 1 + ey;
+        float e = -1.f;   // outside the cell: never consulted, never counted
+        if (x >= 0 && y >= 0 && x < cw && y < ch) {
+            e = gfttg_resp(sC0, sC1, sC2, ex, ey, X);
+            // every cell pixel once, and only the allowed ones: the threshold follows the MASKED maximum (cv::minMaxLoc with the mask)
+            if (ex >= 1 && ex <= 32 && ey >= 1 && ey <= 32 && e == e && (!cmask || cmask[y * cw + x])) { const unsigned k = f32_key(e); mk = k > mk ? k : mk; }
+        }
+        sE[idx] = e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = __shfl_xor(mk, o, 64); mk = t > mk ? t : mk; }
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mk;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned m = smax[0];
+        for (int i = 1; i < 4; i++) m = smax[i] > m ? smax[i] : m;
+        if (m) atomicMax(&cellinfo[2 * cell], m);   // (a tile without an allowed pixel has nothing to publish)
+    }
+    // the early drop of k_gftt_cand, against the tile's own MASKED maximum: the cell's masked maximum is at least that
+    unsigned seen = smax[0];
+    for (int i = 1; i < 4; i++) seen = smax[i] > seen ? smax[i] : seen;
+    const float thr_now = seen ? (float)((double)f32_unkey(seen) * quality) : 0.f;
+    unsigned* s_cnt = smax;                          // [0] tile count, [1] base in the cell's list
+    float* lv = sC0;                                 // up to 1024 values and pixel indices: 2048 dwords of the >= 3 * 34 * 34 of the planes
+    unsigned* li = (unsigned*)(sC0 + 1024);
+    __syncthreads();
+    if (threadIdx.x == 0) s_cnt[0] = 0;
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 32 * 32; idx += 256) {   // (every lane takes all four turns: the ballot below is wave-wide)
+        const int oy = idx >> 5, ox = idx & 31;
+        const int x = tx0 + ox, y = ty0 + oy;
+        bool cand = false;
+        float v = 0.f;
+        if (x >= 1 && y >= 1 && x < cw - 1 && y < ch - 1) {
+            v = sE[(oy + 1) * 34 + ox + 1];
+            cand = v > 0.f && v > thr_now && (!cmask || cmask[y * cw + x]);
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+#pragma unroll
+                for (int i = 0; i < 3; i++) cand = cand && !(sE[(oy + j) * 34 + ox + i] > v);
+        }
+        const unsigned long long bal = __ballot(cand);
+        if (bal) {   // one LDS atomic per wavefront
+            const int lane = threadIdx.x & 63;
+            unsigned base = 0;
+            if (lane == 0) base = atomicAdd(&s_cnt[0], (unsigned)__popcll(bal));
+            base = __shfl(base, 0, 64);
+            if (cand) {
+                const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+                lv[slot] = v; li[slot] = (unsigned)(y * cw + x);
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned nt = s_cnt[0];
+    if (nt == 0) return;
+    if (threadIdx.x == 0) s_cnt[1] = atomicAdd(&cellinfo[2 * cell + 1], nt);
+    __syncthreads();
+    const unsigned gbase = s_cnt[1];
+    float* cv = cand_val + (size_t)cell * CELL_PIX + gbase;
+    unsigned* ci = cand_idx + (size_t)cell * CELL_PIX + gbase;
+    for (unsigned i = threadIdx.x; i < nt; i += 256) { cv[i] = lv[i]; ci[i] = li[i]; }
+}
+// diagnostic / parity (pmv_debug_gftt_response_ex): the response map of the same arithmetic, the only general launch that writes one
+__global__ __launch_bounds__(256) void k_gftt_eig_general(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
+                                                          float* __restrict__ eig, GfttExt X) {
+    extern __shared__ float gfttg_lds[];
+    const int HP = (34 + X.bs - 1) * (34 + X.bs - 1);
+    float* sC0 = gfttg_lds; float* sC1 = sC0 + HP; float* sC2 = sC1 + HP;
+    const int cell = blockIdx.z;
+    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
+    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;
+    if (tx0 >= cw || ty0 >= ch) return;
+    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
+    gfttg_fill(img, L.stride[0], cx0, cy0, cw, ch, tx0, ty0, X, sC0, sC1, sC2);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 32 * 32; idx += 256) {
+        const int oy = idx >> 5, ox = idx & 31;
+        const int x = tx0 + ox, y = ty0 + oy;
+        if (x < cw && y < ch) eig[(size_t)cell * CELL_PIX + y * cw + x] = gfttg_resp(sC0, sC1, sC2, ox + 1, oy + 1, X);
+    }
+}
+static size_t gfttg_lds_bytes(int bs) { const size_t hs = 34 + (size_t)bs - 1; return (3 * hs * hs + 34 * 34 + 4) * sizeof(float); }
+static bool gftt_ext_ok(const GfttExt& X) { return X.bs >= 1 && X.bs <= GFTT_MAX_BLOCK && (!X.harris || std::isfinite(X.k)); }
+
+hipError_t launch_gftt_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, int max_per_cell, double quality,
+                          double min_dist, int unlimited, const GfttExt& X, const uint8_t* d_mask, float* d_eig, unsigned* d_cellmax, int* d_out_xy,
+                          int* d_out_count, int* d_flags, unsigned* d_spill) {
+    if (!slots || !d_cells || !d_eig || !d_cellmax || !d_out_xy || !d_out_count || !d_flags || !d_spill || n_cells < 1 || max_per_cell < 1 || max_per_cell > GP_MAXOUT ||
+        !gftt_ext_ok(X)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_cellmax, 0, 2 * sizeof(unsigned) * n_cells, s);
+    if (e != hipSuccess) return e;
+    { ProfScope ps(K_GFTT_CAND, s);
+    hipLaunchKernelGGL(k_gftt_cand_general, dim3(8, 8, n_cells), dim3(256), gfttg_lds_bytes(X.bs), s, slots, L, d_cells, d_eig, d_spill, d_cellmax, quality, X, d_mask); }
+    // the selection does not depend on the block size, the response kind or the mask: only values > 0 reach it (quality in (0, 1])
+    ProfScope ps2(K_GFTT_PICK, s);
+    hipLaunchKernelGGL(k_gftt_pick, dim3(n_cells), dim3(GP_T), 0, s, d_cells, d_eig, d_spill, d_cellmax, max_per_cell,
+                       quality, min_dist, unlimited, d_out_xy, d_out_count, d_flags);
+    return hipGetLastError();
+}
+hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, const GfttExt& X, float* d_eig) {
+    if (!slots || !d_cells || !d_eig || n_cells < 1 || !gftt_ext_ok(X)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gftt_eig_general, dim3(8, 8, n_cells), dim3(256), gfttg_lds_bytes(X.bs), s, slots, L, d_cells, d_eig, X);
     return hipGetLastError();
 }
 

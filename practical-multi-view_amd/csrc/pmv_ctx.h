@@ -76,6 +76,10 @@ struct pmv_ctx {
     double* d_det_score = nullptr;
     int *h_det_xy = nullptr, *h_det_count = nullptr;
     double* h_det_score = nullptr;
+    // pmv_detect_gftt_ex: the cells' mask sub-views, packed tightly one after the other by the host (pinned) and copied to HBM - only the
+    // bytes under the cells cross the bus. MAX_CELLS * CELL_PIX bytes each, made by the first extended call with a mask.
+    uint8_t* h_gmask = nullptr; uint8_t* d_gmask = nullptr;
+    int gftt_general = 0;                // pmv_debug_gftt_general
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -137,6 +141,11 @@ int lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const flo
 int knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, const int* out_best,
               const float* out_err);
 int detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell);
+// pmv_detect_gftt_ex / pmv_batch_detect_gftt_ex: the parameter checks (before detect_check), the mask stride against the slot's frame (after
+// it), and the packing of the cells' mask sub-views behind byte `pos` of dst (returns the new end; writes each offset into its cell record)
+int gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, const int* out_xy, const int* out_count);
+int gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t* mask, int mask_stride);
+size_t gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* cells, int n_cells, const uint8_t* mask, int mask_stride);
 // after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current

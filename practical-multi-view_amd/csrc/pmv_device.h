@@ -260,4 +260,20 @@ hipError_t launch_gftt_response(hipStream_t s, const uint8_t* slots, const PyrLa
 constexpr int CELL_MAX = 255;                 // OdometryPipeline.h:31 grid_size
 constexpr int CELL_PIX = CELL_MAX * CELL_MAX;
 
+// pmv_detect_gftt_ex: cv::goodFeaturesToTrack's blockSize, useHarrisDetector and k as the general kernels take them. k1, k2 = the taps of
+// the Sobel smoothing kernel [1 2 1] with the scale 1 / (4 * blockSize * 255) folded in, as floats (gftt_ext computes them on the host
+// the way tests/twin/gftt_twin.cpp does; at blockSize 3 they are k_gftt_cand's 1/3060 and 2/3060).
+constexpr int GFTT_MAX_BLOCK = 15;
+struct GfttExt { int bs, harris; double k; float k1, k2; };
+inline GfttExt gftt_ext(int block_size, int use_harris, double k) {
+    const double dscale = 1.0 / ((double)(1 << 2) * block_size * 255.0);
+    return GfttExt{block_size, use_harris ? 1 : 0, use_harris ? k : 0.0, (float)(1.0 * dscale), (float)(2.0 * dscale)};
+}
+// launch_gftt through k_gftt_cand_general. d_mask: null, or the cells' packed mask sub-views (cw * ch bytes per cell at the byte offset in
+// int 5 of its cell record, non-zero = allowed). Booked under the same two profiling classes.
+hipError_t launch_gftt_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, int max_per_cell, double quality,
+                          double min_dist, int unlimited, const GfttExt& X, const uint8_t* d_mask, float* d_eig, unsigned* d_cellmax, int* d_out_xy,
+                          int* d_out_count, int* d_flags, unsigned* d_spill);
+hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, const GfttExt& X, float* d_eig);
+
 }  // namespace pmv
