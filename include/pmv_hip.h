@@ -10,6 +10,8 @@
  *                                          called from OdometryPipeline.cpp:357 / :450)  -> BaseFeatureExtractor.h:21
  *   pmv_detect_gftt_ex                     cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector, k (a KLT front end
  *                                          of the caller's own; the reference passes cv::Mat(), 3, 3, false, 0.04)
+ *   pmv_corner_subpix                      cv::cornerSubPix on level 0 of a slot (the step between the detector and LK in the caller's own
+ *                                          KLT front end; the reference hands integer corners on, OpenCVGoodFeatureExtractor.cpp:7)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -143,7 +145,7 @@ int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
  *   width while a mask is given (as for the upload strides); the cell and slot errors of pmv_detect_gftt.
  * The device buffers of the mask are made by the first extended call with a mask on a context: the host packs the cells' mask sub-views
  *   tightly into pinned memory, so only the bytes under the cells cross the bus.
- * Out of scope: the Sobel aperture (gradientSize) stays 3; corner sub-pixel refinement is the caller's (cv::cornerSubPix). */
+ * Out of scope: the Sobel aperture (gradientSize) stays 3. Corner sub-pixel refinement (cv::cornerSubPix) is pmv_corner_subpix below. */
 typedef struct pmv_gftt_params {
     double quality;      /* qualityLevel, 0 < quality <= 1 */
     double min_dist;     /* minDistance, as pmv_detect_gftt */
@@ -165,6 +167,57 @@ int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, 
 /* Debug/parity: response map of one cell (GFTT: float32 min-eigenvalue map before thresholding). */
 int pmv_debug_gftt_response(pmv_ctx* ctx, int slot, const int* cell, float* out);
 int pmv_debug_shitomasi_response(pmv_ctx* ctx, int slot, const int* cell, double* out);
+
+/* cv::cornerSubPix(level 0 of `slot`, corners, Size(win_w, win_h), Size(zero_w, zero_h), criteria): the step between pmv_detect_gftt[_ex],
+ * which returns integer pixel corners, and pmv_lk_track*, which takes float positions - so that a KLT front end of the caller's own
+ * (goodFeaturesToTrack -> cornerSubPix -> calcOpticalFlowPyrLK) never needs the frame in host memory. The reference itself never refines
+ * (OpenCVGoodFeatureExtractor.cpp:7 hands integer corners on); the whole-sequence drivers do not call this.
+ *   xy: n * 2 floats, in/out, FRAME coordinates of level 0 (the detectors return cell-local corners: add the cell origin). The call works
+ *     on the whole frame; points may lie anywhere within the coordinate limit, outside the frame too (they take the general sampling path).
+ *   Weight table: mask[i][j] = (float)(vy * expf(-x*x)) with x = (float)(j - win_w) / win_w and vy = expf(-y*y), y formed likewise from i and
+ *     win_h. The zero zone is cleared only when zero_w >= 0 && zero_h >= 0 && 2 zero_w + 1 < 2 win_w + 1 && 2 zero_h + 1 < 2 win_h + 1;
+ *     otherwise it is ignored and is not an error. The table is computed on the HOST with libm and handed to the kernel (a device expf does
+ *     not have libm's bits).
+ *   Patch, per iteration: getRectSubPix(src, (2 win_w + 3) x (2 win_h + 3), cI) from 8-bit to float, with both of cv's paths. ip =
+ *     floor(cI - (win + 1)). Interior fast path, when 0 <= ip.x && ip.x + W < cols && 0 <= ip.y && ip.y + H < rows: a = max(a, 0.0001f),
+ *     a12 = a (1 - b), a22 = a b, b1 = 1 - b, b2 = b, and along a row dst[j] = prev + t with t = a12 src[j+1] + a22 src[j+1+step] and the
+ *     running prev = (float)(t * s), s = (1. - a) / a in double, starting from prev = (1 - a)(b1 src[0] + b2 src[step]); element j needs
+ *     only t[j] and t[j-1]. General path otherwise: the four float weights a11..a22 (a not floored), added left to right, rows and columns
+ *     with replicated borders; where both sample columns clamp to the same column (x0 < 0 or x0 >= cols - 1) the two-weight form
+ *     src*b1 + src2*b2 applies. Level 0 of a slot is stored with a 64-pixel REFLECT_101 frame: the kernel does NOT sample it,
+ *     out-of-image samples are replicate-clamped to the real w x h image.
+ *   Normal equations: tgx, tgy are float differences of patch neighbours; gxx = tgx*tgx*m, gxy = tgx*tgy*m, gyy = tgy*tgy*m in double; the
+ *     sums a, b, c, bb1, bb2 in double; stop without an update when fabs(det) <= DBL_EPSILON^2; otherwise cI2 = (float)(cI + ...) with
+ *     scale = 1.0 / det, and err is the squared float step; stop when the new cI lies outside [0, cols) x [0, rows); loop
+ *     while (++iter < max_iter && err > eps*eps), eps squared and compared in double. Afterwards the point returns to its input when
+ *     |cI.x - cT.x| > win_w or |cI.y - cT.y| > win_h.
+ *   Order of the five double sums: a wavefront cannot add in cv's raster order. ONE order is fixed, by tests/twin/subpix_twin.cpp, and the
+ *     kernel follows it: lane l of 64 adds the window pixels k = l, l + 64, l + 128, ... (k = i (2 win_w + 1) + j, rows outer) in ascending
+ *     k into accumulators that start at +0.0, then the 64 lane values are added as a binary tree of neighbours ((0,1), (2,3), ..., then
+ *     pairs of pairs, up to the two halves). The order does not depend on n, on the point's position in the launch, or on single versus
+ *     session form; the two orders differ by double rounding noise before the one rounding to float of an update.
+ *   out_iters (n bytes, may be NULL): the number of position updates made, 0..100.
+ *   out_flags (n bytes, may be NULL): bit 1 = stopped on the determinant test; 2 = left the frame; 4 = the iteration cap ended the loop with
+ *     err > eps^2; 8 = reverted to the input position.
+ *   Frames are at least 40x40 and win <= 15, so cv's own assertion cols >= 2 win_w + 5 (rows likewise) cannot fire.
+ *   [mem: OpenCV 3.4 cornersubpix.cpp, samplers.cpp; parity unpinned like the rest of the front end - tests/twin/subpix_twin.cpp is the
+ *   CPU restatement that fixes the arithmetic, bit for bit.]
+ * Errors (nothing is written on any of them): PMV_ERR_INVALID - a null p, a null xy with n != 0, win_w or win_h outside 1..15, max_iter
+ *   outside 1..100 (nothing is clamped, as for pmv_set_lk_params), eps negative or not finite, a coordinate that is not finite or beyond
+ *   1e6 in magnitude (the message names the point, as for pmv_lk_track_ex); PMV_ERR_CAPACITY - n above max_tracks; the slot errors of
+ *   pmv_lk_track. n == 0 is PMV_OK and launches nothing.
+ * The device buffers are made by the first call on a context. Out of scope: ROI sub-views as the image, windows above 15, refinement on
+ *   the levels above 0. */
+typedef struct pmv_subpix_params {
+    int win_w, win_h;     /* cv's `winSize` HALF sizes: the search window is (2 win_w + 1) x (2 win_h + 1); 1 .. 15 each */
+    int zero_w, zero_h;   /* cv's `zeroZone` half sizes; (-1, -1) = none */
+    int max_iter;         /* TermCriteria COUNT, 1 .. 100 (cv clamps to that range; a caller without COUNT passes 100) */
+    double eps;           /* TermCriteria EPS, >= 0 and finite (compared squared, in double; no EPS criterion = 0) */
+} pmv_subpix_params;
+int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);
+/* diagnostic: {launches of pmv_corner_subpix, session rounds that held at least one pmv_batch_corner_subpix request, launches made for
+ * them} since the context was created. */
+int pmv_debug_subpix_launches(pmv_ctx* ctx, long long* out3);
 
 /* cv::FAST(cell, kp, threshold, nonmax) (OpenCVFASTFeatureExtractor.cpp:8; 9_16 pattern) on sub-views of the frame in `slot`; a
  * "cell" here may be as large as the frame (kNNFeatureMatcher.cpp:11 calls the extractor on the whole next frame). out_xy:
@@ -530,6 +583,11 @@ int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells,
  * what it launched before. The mask is read before the call returns. */
 int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
                              int mask_stride, int* out_xy, int* out_count);
+/* pmv_corner_subpix as a session call: the same arguments, bits and status codes. It is served by the detector combiner: requests of a
+ * round that agree in the six parameters share ONE launch, whatever their slots and declared frame sizes (every point's record names its
+ * geometry); a round without such requests launches exactly what it launched before. A round's result block holds at least
+ * n_seq * max_tracks points, as for LK: requests that do not fit wait for the next round. */
+int pmv_batch_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);
 int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
                                int* out_count);
 int pmv_batch_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy,

@@ -41,6 +41,11 @@ class GfttParams(C.Structure):
     _fields_ = [("quality", C.c_double), ("min_dist", C.c_double), ("block_size", C.c_int), ("use_harris", C.c_int), ("k", C.c_double)]
 
 
+class SubpixParams(C.Structure):
+    """pmv_subpix_params of include/pmv_hip.h"""
+    _fields_ = [("win_w", C.c_int), ("win_h", C.c_int), ("zero_w", C.c_int), ("zero_h", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double)]
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 # the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
 LK_USE_INITIAL_FLOW = 4
@@ -51,6 +56,7 @@ ABI_SYMBOLS = [
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
+    "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -489,6 +495,34 @@ class Context:
     def debug_gftt_general(self, on):
         """diagnostic: detect_gftt_ex's default arguments through the general kernels as well (pmv_debug_gftt_general); changes no result"""
         self._ck(self.lib.pmv_debug_gftt_general(self.h, 1 if on else 0))
+
+    def _corner_subpix(self, fn, ck, slot, xy, win, zero_zone, max_iter, eps, return_info):
+        # refused before the library is touched: the library takes n * 2 float32 values in place
+        if not isinstance(xy, np.ndarray) or xy.dtype != np.float32 or xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("corner_subpix: xy must be an (n, 2) float32 array")
+        if len(win) != 2 or len(zero_zone) != 2:
+            raise ValueError("corner_subpix: win and zero_zone are (w, h) pairs of half sizes")
+        out = np.ascontiguousarray(xy).copy()
+        n = out.shape[0]
+        iters = np.zeros(n, np.uint8)
+        flags = np.zeros(n, np.uint8)
+        p = SubpixParams(int(win[0]), int(win[1]), int(zero_zone[0]), int(zero_zone[1]), int(max_iter), float(eps))
+        fn.argtypes = [C.c_void_p, C.c_int, _f32p, C.c_int, C.POINTER(SubpixParams), _u8p, _u8p]
+        ck(fn(self.h, int(slot), _p(out, _f32p), n, C.byref(p), _p(iters, _u8p) if return_info else None, _p(flags, _u8p) if return_info else None))
+        return (out, iters, flags) if return_info else out
+
+    def corner_subpix(self, slot, xy, win=(5, 5), zero_zone=(-1, -1), max_iter=30, eps=0.01, return_info=False):
+        """pmv_corner_subpix: cv::cornerSubPix on level 0 of `slot`. xy: (n, 2) float32 FRAME coordinates (detect_gftt* returns cell-local
+        corners: add the cell origin); win / zero_zone: cv's half sizes. Returns a new (n, 2) float32 array; with return_info also the
+        position updates made per point and the flag bits (1 determinant, 2 left the frame, 4 iteration cap, 8 reverted)."""
+        return self._corner_subpix(self.lib.pmv_corner_subpix, self._ck, slot, xy, win, zero_zone, max_iter, eps, return_info)
+
+    def debug_subpix_launches(self):
+        """pmv_debug_subpix_launches: [launches of corner_subpix, session rounds with a subpix request, launches made for them]"""
+        out = (C.c_longlong * 3)()
+        self.lib.pmv_debug_subpix_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_subpix_launches(self.h, out))
+        return [int(v) for v in out]
 
     def detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
@@ -963,6 +997,10 @@ class Context:
     def batch_detect_gftt_ex(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04):
         """pmv_batch_detect_gftt_ex: detect_gftt_ex as a session call (same arguments, same arrays)"""
         return self._gftt_ex(self.lib.pmv_batch_detect_gftt_ex, self._ckt, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k)
+
+    def batch_corner_subpix(self, slot, xy, win=(5, 5), zero_zone=(-1, -1), max_iter=30, eps=0.01, return_info=False):
+        """pmv_batch_corner_subpix: corner_subpix as a session call (same arguments, same arrays)"""
+        return self._corner_subpix(self.lib.pmv_batch_corner_subpix, self._ckt, slot, xy, win, zero_zone, max_iter, eps, return_info)
 
     def batch_detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)

@@ -30,6 +30,9 @@ int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, 
 // pmv_debug_gftt_general is on.
 int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
                           int mask_stride, int* out_xy, int* out_count);
+// pmv_corner_subpix's contract, arguments already checked (subpix_check): a request of the detector combiner. Requests of a round that agree
+// in the six parameters share one launch, whatever their slots and frame sizes.
+int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);
 // pmv_detect_fast's contract (a cell may be as large as the frame; max_per_cell <= 0: empty lists, no launch): a request of the detector combiner
 int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                        int* out_count, int ring_round = -1);

@@ -35,7 +35,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
+    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners), 6 corner sub-pixel refinement (the detector combiner) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -73,6 +73,13 @@ struct DetReq : Req {
     // GFTT through the general kernels (pmv_batch_detect_gftt_ex): the caller's block size, response kind and k, and the optional host mask
     int ext = 0, block_size = 3, use_harris = 0; double k = 0.0;
     const uint8_t* mask = nullptr; int mask_stride = 0;
+};
+struct SubpixReq : Req {      // kind 6: one pmv_batch_corner_subpix call; p's zero zone is the effective one (subpix_zero_zone)
+    int slot, n;
+    float* xy; uint8_t* iters_out; uint8_t* flags_out;
+    pmv_subpix_params p;
+    int base = 0;             // filled by the combiner: first index in the round's record and result arrays
+    int geom = 0;             // filled by the combiner: the geometry-table entry of its frame
 };
 struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
@@ -126,6 +133,9 @@ struct Combiner {
     // masks of the extended GFTT requests of a round (detector combiner, made by the first round that has one): the cells' mask sub-views
     // packed one after the other, pinned mirror and HBM copy
     Growable h_gmask{nullptr, 0, true}, d_gmask;
+    // corner sub-pixel requests of a round (detector combiner, made by the first round that has one): [point records | positions | updates |
+    // flags] in one mapped pinned block; the weight tables of the round's parameter groups, pinned mirror and HBM copy
+    Growable h_spx{nullptr, 0, true}, h_spx_tab{nullptr, 0, true}, d_spx_tab;
     // kNN matcher rounds (LK combiners): [stage-in job | request records | coordinate lists], pinned mirror and HBM copy; FAST score maps (detector combiner)
     Growable h_knn{nullptr, 0, true}, d_knn, d_fast_score;
     // extended LK requests (LK combiners, made by the first round that has one): [LKBlock | LKExt] records of a round; back results of
@@ -424,7 +434,8 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     pmv_ctx* ctx = E->ctx;
     hipStream_t s = C.s;
     std::vector<DetReq*> det;
-    for (Req* r : batch) det.push_back((DetReq*)r);
+    std::vector<SubpixReq*> spx;   // (corner sub-pixel requests: the same role, the same round, one more launch per parameter set)
+    for (Req* r : batch) { if (r->kind == 6) spx.push_back((SubpixReq*)r); else det.push_back((DetReq*)r); }
     // ---- detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
     // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
     // FAST (kind 3; grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
@@ -461,7 +472,7 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         g->n_cells += r->n_cells;
         g->reqs.push_back(r);
     }
-    {
+    if (!det.empty()) {   // (a round of sub-pixel requests alone has no detector launch)
         size_t tot_cells = 0, tot_out = 0;
         for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
         size_t eig_cells = 0;   // cells of the GFTT / ShiTomasi groups: the response, cell-maximum and spill areas are theirs alone
@@ -525,8 +536,61 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         }
         EK(hipMemcpyAsync(hd + tot_out * 16 + tot_cells * 4, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
     }
+    // ---- corner sub-pixel refinement: requests that agree in the six parameters share ONE launch, whatever their slots and frame sizes -
+    // every point's record names its slot and its entry of the geometry table. A round without such a request adds nothing here.
+    struct SGroup { pmv_subpix_params p; std::vector<SubpixReq*> reqs; int n = 0, base = 0; };
+    std::vector<SGroup> sgroups;
+    size_t spx_total = 0;
+    for (SubpixReq* r : spx) {
+        const PyrLayout& Lr = ctx->slot_layout[r->slot];
+        if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch corner subpix: slot %d holds no built pyramid", r->slot); continue; }
+        if ((r->geom = ctx->geom_index(Lr.w[0], Lr.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch corner subpix: slot %d holds a %dx%d frame, which is no declared size of this session", r->slot, Lr.w[0], Lr.h[0]); continue; }
+        if (spx_total + (size_t)r->n > E->cap_tracks) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch corner subpix: more points than n_seq * max_tracks in a round"); continue; }
+        SGroup* g = nullptr;
+        for (SGroup& x : sgroups)
+            if (x.p.win_w == r->p.win_w && x.p.win_h == r->p.win_h && x.p.zero_w == r->p.zero_w && x.p.zero_h == r->p.zero_h && x.p.max_iter == r->p.max_iter && x.p.eps == r->p.eps) { g = &x; break; }
+        if (!g) { sgroups.push_back(SGroup{r->p, {}, 0, 0}); g = &sgroups.back(); }
+        g->reqs.push_back(r);
+        g->n += r->n;
+        spx_total += (size_t)r->n;
+    }
+    if (spx_total > 0) {
+        const size_t off_xy = spx_total * sizeof(SubpixRec), off_it = off_xy + spx_total * 8, off_fl = off_it + spx_total;
+        const size_t tab_bytes = sgroups.size() * SUBPIX_TABLE_MAX * sizeof(float);
+        EK(C.h_spx.ensure(off_fl + spx_total + 64)); EK(C.h_spx_tab.ensure(tab_bytes)); EK(C.d_spx_tab.ensure(tab_bytes));
+        SubpixRec* rec = (SubpixRec*)C.h_spx.p;
+        int pos = 0;
+        for (size_t gi = 0; gi < sgroups.size(); gi++) {
+            SGroup& g = sgroups[gi];
+            g.base = pos;
+            for (SubpixReq* r : g.reqs) {
+                r->base = pos;
+                for (int i = 0; i < r->n; i++) rec[pos++] = SubpixRec{r->xy[2 * i], r->xy[2 * i + 1], r->slot, r->geom};
+            }
+            subpix_table(g.p.win_w, g.p.win_h, g.p.zero_w, g.p.zero_h, (float*)C.h_spx_tab.p + gi * SUBPIX_TABLE_MAX);
+        }
+        EK(hipMemcpyAsync(C.d_spx_tab.p, C.h_spx_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        for (size_t gi = 0; gi < sgroups.size(); gi++) {
+            const SGroup& g = sgroups[gi];
+            const SubpixArgs A{g.p.win_w, g.p.win_h, g.p.max_iter, g.p.eps * g.p.eps};
+            EK(launch_corner_subpix_geom(s, ctx->d_slots, ctx->d_geom, (const SubpixRec*)C.h_spx.dev + g.base, g.n, (const float*)C.d_spx_tab.p + gi * SUBPIX_TABLE_MAX, A,
+                                         (float*)(C.h_spx.dev + off_xy) + 2 * (size_t)g.base, (uint8_t*)C.h_spx.dev + off_it + g.base, (uint8_t*)C.h_spx.dev + off_fl + g.base));
+            ctx->subpix_launches[2]++;
+        }
+        ctx->subpix_launches[1]++;
+    }
     SYNC_TIMED(C);
-    {
+    if (spx_total > 0) {
+        const char* hb = (const char*)C.h_spx.p;
+        const size_t off_xy = spx_total * sizeof(SubpixRec), off_it = off_xy + spx_total * 8, off_fl = off_it + spx_total;
+        for (SGroup& g : sgroups)
+            for (SubpixReq* r : g.reqs) {
+                memcpy(r->xy, hb + off_xy + (size_t)8 * r->base, (size_t)r->n * 8);
+                if (r->iters_out) memcpy(r->iters_out, hb + off_it + r->base, (size_t)r->n);
+                if (r->flags_out) memcpy(r->flags_out, hb + off_fl + r->base, (size_t)r->n);
+            }
+    }
+    if (!det.empty()) {
         size_t tot_cells = 0, tot_out = 0;
         for (Group& g : groups) { tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
         const char* hd = (const char*)C.h_det.p;
@@ -735,6 +799,22 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
                     Q->cv_new.notify_all();   // (another lane of the class may take them at once)
                 }
             }
+            if (role == R_DET) {
+                // the same for the corner sub-pixel requests of the detector class: a round's result block holds cap_tracks points
+                size_t total = 0, k = 0;
+                for (; k < batch.size(); k++) {
+                    if (batch[k]->kind != 6) continue;
+                    const size_t n = (size_t)((SubpixReq*)batch[k])->n;
+                    if (total + n > E->cap_tracks) break;
+                    total += n;
+                }
+                if (k < batch.size()) {
+                    Q->pending.assign(batch.begin() + (long)k, batch.end());
+                    batch.resize(k);
+                    Q->first_arrival = std::chrono::steady_clock::now();
+                    Q->cv_new.notify_all();
+                }
+            }
         }
         const auto tw = std::chrono::steady_clock::now();
         C->t_idle += std::chrono::duration<double>(tw - ti).count();
@@ -807,7 +887,7 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
             if (C.h_done) (void)hipHostFree(C.h_done);
-            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back, &C.h_gmask, &C.d_gmask}) g->release();
+            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back, &C.h_gmask, &C.d_gmask, &C.h_spx, &C.h_spx_tab, &C.d_spx_tab}) g->release();
             if (C.h_out_xy) (void)hipHostFree(C.h_out_xy);
             if (C.h_err) (void)hipHostFree(C.h_err);
             if (C.h_status) (void)hipHostFree(C.h_status);
@@ -984,6 +1064,16 @@ int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cell
     r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count;
     r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
     r.mask = mask; r.mask_stride = mask_stride;
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
+    pmv_ctx* ctx = E->ctx;
+    if (n == 0) return PMV_OK;
+    SubpixReq r;
+    r.kind = 6; r.slot = slot; r.n = n; r.xy = xy; r.iters_out = out_iters; r.flags_out = out_flags;
+    r.p = *p;
+    subpix_zero_zone(p, &r.p.zero_w, &r.p.zero_h);
     return submit(ctx, E->queue[R_DET], &r);
 }
 

@@ -445,6 +445,13 @@ int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cel
     return engine_detect_gftt_ex(S->eng, slot, cells, n_cells, max_per_cell, p, mask, mask_stride, out_xy, out_count);
 }
 
+int pmv_batch_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
+    SESSION("pmv_batch_corner_subpix");
+    if (const int rc = subpix_check(ctx, "pmv_batch_corner_subpix", false, slot, xy, n, p)) return rc;
+    if (n == 0) return PMV_OK;
+    return engine_corner_subpix(S->eng, slot, xy, n, p, out_iters, out_flags);
+}
+
 int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
                                int* out_count) {
     SESSION("pmv_batch_detect_shitomasi");

@@ -120,6 +120,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     CK(hipHostGetDevicePointer((void**)&c->dm_work, c->h_work, 0));
     for (auto& a : c->lk_work) a.store(0);
     for (auto& a : c->batch_launches) a.store(0);
+    for (auto& a : c->subpix_launches) a.store(0);
     CK(hipMalloc(&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMalloc(&c->d_cells, MAX_CELLS * CELL_STRIDE * 4));
@@ -166,6 +167,9 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->h_lkx) hipHostFree(c->h_lkx);
     if (c->h_gmask) hipHostFree(c->h_gmask);
     if (c->d_gmask) hipFree(c->d_gmask);
+    if (c->h_subpix) hipHostFree(c->h_subpix);
+    if (c->h_subpix_tab) hipHostFree(c->h_subpix_tab);
+    if (c->d_subpix_tab) hipFree(c->d_subpix_tab);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
     hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
@@ -550,6 +554,18 @@ size_t pmv::gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* 
     }
     return pos;
 }
+int pmv::subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p) {
+    REQ(p && (n == 0 || xy), PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(p->win_w >= 1 && p->win_w <= SUBPIX_MAX_WIN && p->win_h >= 1 && p->win_h <= SUBPIX_MAX_WIN, PMV_ERR_INVALID, "%s: win = (%d, %d) is outside 1..%d", who, p->win_w, p->win_h, SUBPIX_MAX_WIN);
+    REQ(p->max_iter >= 1 && p->max_iter <= 100, PMV_ERR_INVALID, "%s: max_iter = %d is outside 1..100", who, p->max_iter);
+    REQ(p->eps >= 0.0 && std::isfinite(p->eps), PMV_ERR_INVALID, "%s: eps = %g is negative or not finite", who, p->eps);   // (a NaN fails the comparison too)
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d exceeds max_tracks=%d", who, n, ctx->max_tracks);
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "%s: slot out of range", who);
+    if (const int rc_ = bracket ? slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, slot)) return rc_;
+    for (int i = 0; i < 2 * n; i++)   // (a NaN fails the comparison too)
+        REQ(fabsf(xy[i]) <= 1e6f, PMV_ERR_INVALID, "%s: point %d (%g, %g) is not finite or beyond 1e6", who, i / 2, (double)xy[i & ~1], (double)xy[i | 1]);
+    return PMV_OK;
+}
 static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell) {   // max_per_cell: already >= 1
     REQ(ctx, PMV_ERR_INVALID, "detect: null argument");
     return detect_check(ctx, true, slot, cells, n_cells, max_per_cell);
@@ -637,6 +653,48 @@ int pmv_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
 int pmv_debug_gftt_general(pmv_ctx* ctx, int on) {
     REQ(ctx, PMV_ERR_INVALID, "null ctx");
     ctx->gftt_general = on != 0;
+    return PMV_OK;
+}
+
+// cv::cornerSubPix on level 0 of the slot: point records and results in one mapped pinned block, ONE launch
+int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_corner_subpix: null argument");
+    if (const int rc_ = subpix_check(ctx, "pmv_corner_subpix", true, slot, xy, n, p)) return rc_;
+    if (n == 0) return PMV_OK;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const size_t nt = (size_t)ctx->max_tracks;
+    if (!ctx->h_subpix) {
+        CKC(hipHostMalloc(&ctx->h_subpix, nt * 26 + 64, hipHostMallocMapped | hipHostMallocCoherent));
+        CKC(hipHostGetDevicePointer((void**)&ctx->dm_subpix, ctx->h_subpix, 0));
+    }
+    if (!ctx->h_subpix_tab) CKC(hipHostMalloc(&ctx->h_subpix_tab, SUBPIX_TABLE_MAX * sizeof(float), hipHostMallocDefault));
+    if (!ctx->d_subpix_tab) CKC(hipMalloc(&ctx->d_subpix_tab, SUBPIX_TABLE_MAX * sizeof(float)));
+    int zw, zh;
+    subpix_zero_zone(p, &zw, &zh);
+    const int key[4] = {p->win_w, p->win_h, zw, zh};
+    if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
+        CKC(hipStreamSynchronize(ctx->s_front));   // (the pinned mirror may still be on its way from the last change)
+        subpix_table(p->win_w, p->win_h, zw, zh, ctx->h_subpix_tab);
+        CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * p->win_w + 1) * (2 * p->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
+        memcpy(ctx->subpix_tab_key, key, sizeof(key));
+    }
+    const size_t off_xy = nt * 16, off_it = nt * 24, off_fl = nt * 25;
+    SubpixRec* rec = (SubpixRec*)ctx->h_subpix;
+    for (int i = 0; i < n; i++) rec[i] = SubpixRec{xy[2 * i], xy[2 * i + 1], slot, 0};
+    const SubpixArgs A{p->win_w, p->win_h, p->max_iter, p->eps * p->eps};
+    CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], (const SubpixRec*)ctx->dm_subpix, n, ctx->d_subpix_tab, A, (float*)(ctx->dm_subpix + off_xy),
+                             ctx->dm_subpix + off_it, ctx->dm_subpix + off_fl));
+    ctx->subpix_launches[0]++;
+    CKC(hipStreamSynchronize(ctx->s_front));
+    memcpy(xy, ctx->h_subpix + off_xy, (size_t)n * 8);
+    if (out_iters) memcpy(out_iters, ctx->h_subpix + off_it, (size_t)n);
+    if (out_flags) memcpy(out_flags, ctx->h_subpix + off_fl, (size_t)n);
+    return PMV_OK;
+}
+int pmv_debug_subpix_launches(pmv_ctx* ctx, long long* out3) {
+    REQ(ctx && out3, PMV_ERR_INVALID, "pmv_debug_subpix_launches: null argument");
+    for (int i = 0; i < 3; i++) out3[i] = ctx->subpix_launches[i].load();
     return PMV_OK;
 }
 

@@ -80,6 +80,14 @@ struct pmv_ctx {
     // bytes under the cells cross the bus. MAX_CELLS * CELL_PIX bytes each, made by the first extended call with a mask.
     uint8_t* h_gmask = nullptr; uint8_t* d_gmask = nullptr;
     int gftt_general = 0;                // pmv_debug_gftt_general
+    // pmv_corner_subpix, made by the first call (a context that never makes one pays nothing): one mapped pinned block [point records nt x 16 |
+    // positions 2 nt floats | updates nt bytes | flags nt bytes], nt = max_tracks, and the weight table in HBM with the window and (effective)
+    // zero zone it was computed for - a caller keeps its parameters, so the table crosses the bus once
+    uint8_t* h_subpix = nullptr; uint8_t* dm_subpix = nullptr;
+    float* d_subpix_tab = nullptr; float* h_subpix_tab = nullptr;
+    int subpix_tab_key[4] = {0, 0, 0, 0};
+    // pmv_debug_subpix_launches: launches of the single call | session rounds with a subpix request | launches made for them
+    std::atomic<long long> subpix_launches[3];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -146,6 +154,13 @@ int detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_c
 int gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, const int* out_xy, const int* out_count);
 int gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t* mask, int mask_stride);
 size_t gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* cells, int n_cells, const uint8_t* mask, int mask_stride);
+// pmv_corner_subpix / pmv_batch_corner_subpix: every check of the contract, in its order (`who` names the call in the messages)
+int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p);
+// the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
+inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
+    const bool on = p->zero_w >= 0 && p->zero_h >= 0 && 2 * p->zero_w + 1 < 2 * p->win_w + 1 && 2 * p->zero_h + 1 < 2 * p->win_h + 1;
+    *zw = on ? p->zero_w : -1; *zh = on ? p->zero_h : -1;
+}
 // after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current

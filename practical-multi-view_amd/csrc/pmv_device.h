@@ -276,4 +276,22 @@ hipError_t launch_gftt_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& 
                           int* d_out_count, int* d_flags, unsigned* d_spill);
 hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, const GfttExt& X, float* d_eig);
 
+// ---- corner sub-pixel refinement (frontend_subpix.hip) -----------------------------------------------------------
+// pmv_corner_subpix / pmv_batch_corner_subpix: one point of a launch names its frame slot and, in the table form, its entry of the geometry
+// table, as LK's track records do: one launch serves points of several slots and frame sizes. Results go to the record's own index.
+constexpr int SUBPIX_MAX_WIN = 15;
+constexpr int SUBPIX_TABLE_MAX = (2 * SUBPIX_MAX_WIN + 1) * (2 * SUBPIX_MAX_WIN + 1);
+struct __attribute__((aligned(16))) SubpixRec { float x, y; int slot; int geom; };
+static_assert(sizeof(SubpixRec) == 16, "SubpixRec: one 16-byte record per point");
+struct SubpixArgs { int win_w, win_h, max_iter; double eps2; };   // cv's half sizes, TermCriteria COUNT, EPS squared (in double)
+// cv::cornerSubPix's weight table, (2 win_h + 1) rows of (2 win_w + 1) floats, with the zero zone cleared where cv clears it: computed on the
+// HOST with libm (a device expf does not have libm's bits) and handed to the kernel
+void subpix_table(int win_w, int win_h, int zero_w, int zero_h, float* out);
+// k_corner_subpix over n records in device-visible memory. Every record has the geometry L (the single call) or d_geom[record.geom] (the
+// batch engine). d_table: subpix_table's floats in device-visible memory. Booked under the detector's selection class.
+hipError_t launch_corner_subpix(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const SubpixRec* d_recs, int n, const float* d_table, const SubpixArgs& A,
+                                float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
+hipError_t launch_corner_subpix_geom(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const SubpixRec* d_recs, int n, const float* d_table,
+                                     const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
+
 }  // namespace pmv
