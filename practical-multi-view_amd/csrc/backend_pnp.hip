@@ -18,8 +18,6 @@ namespace pmv {
 struct EpnpShared {
     double A[144], V[144];
     double M[10 * 12];
-    double C[6], S[6];
-    int P[6], Q[6];
     double pws[15], us[10], alphas[20], cws[12];
     double v4[48];
     double L[60], rho[6];
@@ -154,6 +152,19 @@ __device__ double epnp_R_and_t(const EpnpShared& sh, const double* betas, double
     return sum2 / n;
 }
 
+// Jacobi rotation (c, s) that annihilates a_pq; a pair with |a_pq| <= tol_abs does not rotate: c = 1, s = 0, returns false. Straight-line:
+// the angle chain is evaluated either way and dropped by a select (the six pairs of a round share one wavefront: a branch would run both sides anyway).
+__device__ __forceinline__ bool d_jacobi_rotation(double apq, double app, double aqq, double tol_abs, double& c_out, double& s_out) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0);
+    const double s = t * c;
+    const bool rot = !(fabs(apq) <= tol_abs);
+    c_out = rot ? c : 1.0;
+    s_out = rot ? s : 0.0;
+    return rot;
+}
+
 // hypothesis h of one RANSAC problem, executed by one wavefront. models: n_hyp x 6 (rvec, tvec)
 // LDS_L: the Gauss-Newton passes read L_6x10 / rho from LDS instead of a register copy - 130 fewer registers (two wavefronts per SIMD
 // instead of one) for a longer chain; the throughput form used by the batched launch. Same expressions either way.
@@ -244,64 +255,72 @@ __device__ __forceinline__ void pnp_hyp_body(const float* __restrict__ obj, cons
         sh.V[idx] = (a == b) ? 1.0 : 0.0;
     }
     __syncthreads();
-    // parallel-order (round-robin) Jacobi: 6 disjoint rotations per round. The block is one wavefront, so LDS ordering
-    // (s_waitcnt) is all the synchronisation needed. A <- J^T A J is applied in one pass: the item (g, g') owns the 2x2
-    // block {p,q} x {p',q'} (pairs partition the indices, so items touch disjoint elements and update in place), computing
-    // first the column rotation of pair g' and then the row rotation of pair g — the same expressions, in the same order,
-    // as B = A J followed by A = J^T B. A round in which no pair rotates is skipped (it would multiply by the identity).
+    // parallel-order (round-robin) Jacobi: 6 disjoint rotations per round. The block is one wavefront and the LDS serves a wavefront's
+    // accesses in program order, so a round is ONE read phase and ONE write phase with nothing handed over in between:
+    //  * the pairs of round r are a function of (r, g) alone: every lane derives the (p, q) of its row pair g and column pair g' for
+    //    the 11 rounds once, before the sweeps (4 x 4 bits per round, six registers);
+    //  * the rotation of a pair is a function of three entries of A: each of the 36 lanes (g, g') reads them for its COLUMN pair g' in
+    //    the same phase as its block and evaluates the angle chain itself (six lanes per pair, the same expressions on the same inputs:
+    //    the same bits); the (c, s) of its ROW pair g comes from lane (0, g) by one cross-lane move - no store, wait and load. (Both
+    //    chains in every lane, which needs no move at all, measured no faster than the LDS hand-over it replaces: the FP64 pipe of a
+    //    single wavefront does not overlap two division/square-root chains.)
+    //  * A <- J^T A J in one pass: the lane owns the 2x2 block {p,q} x {p',q'} (pairs partition the indices, so lanes touch disjoint
+    //    elements and update in place), computing first the column rotation of pair g' and then the row rotation of pair g — the
+    //    same expressions, in the same order, as B = A J followed by A = J^T B;
+    //  * V <- V J in the same phases: lane (g, g') takes rows g and g + 6 of column pair g' with the (c, s) it already holds.
+    // A round in which no pair rotates is skipped (it would multiply by the identity).
     double tol_abs = 0;
     for (int i = 0; i < 12; i++) tol_abs += fabs(sh.A[i * 13]);
     tol_abs *= 1e-17;
+    const int jg = lane / 6, jg2 = lane - jg * 6;
+    unsigned sched[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int r = 0; r < 11; r++) {
+        int a = 11, b = r, a2 = 11, b2 = r;
+        if (jg != 0) { a = (r + jg) % 11; b = (r - jg + 11) % 11; }
+        if (jg2 != 0) { a2 = (r + jg2) % 11; b2 = (r - jg2 + 11) % 11; }
+        const int p = a < b ? a : b, q = a < b ? b : a, p2 = a2 < b2 ? a2 : b2, q2 = a2 < b2 ? b2 : a2;
+        sched[r >> 1] |= (unsigned)((p & 15) | ((q & 15) << 4) | (p2 << 8) | (q2 << 12)) << ((r & 1) * 16);
+    }
+    const unsigned long long t_jac0 = __builtin_readcyclecounter();
+    int n_rounds = 0;
     for (int sweep = 0; sweep < 30; sweep++) {
         int rotated = 0;
+#pragma unroll
         for (int r = 0; r < 11; r++) {
-            bool rot = false;
-            if (lane < 6) {
-                const int g = lane;
-                int a, b;
-                if (g == 0) { a = 11; b = r; }
-                else { a = (r + g) % 11; b = (r - g + 11) % 11; }
-                const int p = a < b ? a : b, q = a < b ? b : a;
-                sh.P[g] = p; sh.Q[g] = q;
-                const double apq = sh.A[p * 12 + q], app = sh.A[p * 12 + p], aqq = sh.A[q * 12 + q];
-                if (fabs(apq) <= tol_abs) { sh.C[g] = 1.0; sh.S[g] = 0.0; }
-                else {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0);
-                    sh.C[g] = c;
-                    sh.S[g] = t * c;
-                    rot = true;
-                }
-            }
-            const int nrot = __popcll(__ballot(rot));
-            rotated += nrot;
-            WAVE_SYNC_PNP();
-            if (nrot == 0) continue;   // wave-uniform
+            const unsigned w = sched[r >> 1] >> ((r & 1) * 16);
+            const int p = w & 15, q = (w >> 4) & 15, p2 = (w >> 8) & 15, q2 = (w >> 12) & 15;
+            bool rot2 = false;
+            double c2 = 1.0, sn2 = 0.0;
+            double app = 0, apq = 0, aqp = 0, aqq = 0, v0p = 0, v0q = 0, v1p = 0, v1q = 0;
             if (lane < 36) {
-                const int g = lane / 6, g2 = lane - g * 6;
-                const int p = sh.P[g], q = sh.Q[g], p2 = sh.P[g2], q2 = sh.Q[g2];
-                const double c = sh.C[g], sn = sh.S[g], c2 = sh.C[g2], sn2 = sh.S[g2];
-                const double app = sh.A[p * 12 + p2], apq = sh.A[p * 12 + q2], aqp = sh.A[q * 12 + p2], aqq = sh.A[q * 12 + q2];
+                const double hpq = sh.A[p2 * 12 + q2], hpp = sh.A[p2 * 12 + p2], hqq = sh.A[q2 * 12 + q2];
+                app = sh.A[p * 12 + p2]; apq = sh.A[p * 12 + q2]; aqp = sh.A[q * 12 + p2]; aqq = sh.A[q * 12 + q2];
+                v0p = sh.V[jg * 12 + p2]; v0q = sh.V[jg * 12 + q2]; v1p = sh.V[(jg + 6) * 12 + p2]; v1q = sh.V[(jg + 6) * 12 + q2];
+                rot2 = d_jacobi_rotation(hpq, hpp, hqq, tol_abs, c2, sn2);
+            }
+            const int nrot = __popcll(__ballot(rot2 && lane < 6));   // lanes (0, g'): each pair once
+            rotated += nrot;
+            n_rounds++;
+            if (nrot == 0) continue;   // wave-uniform; nothing was written
+            const double c = __shfl(c2, jg), sn = __shfl(sn2, jg);   // row pair g: what lane (0, g) holds for its column pair (all lanes take part)
+            if (lane < 36) {
                 const double bpp = c2 * app - sn2 * apq, bpq = sn2 * app + c2 * apq;   // B = A J, rows p and q
                 const double bqp = c2 * aqp - sn2 * aqq, bqq = sn2 * aqp + c2 * aqq;
                 sh.A[p * 12 + p2] = c * bpp - sn * bqp;                                 // A = J^T B
                 sh.A[q * 12 + p2] = sn * bpp + c * bqp;
                 sh.A[p * 12 + q2] = c * bpq - sn * bqq;
                 sh.A[q * 12 + q2] = sn * bpq + c * bqq;
-            }
-            for (int idx = lane; idx < 72; idx += 64) {   // V = V J, item = (row i, pair g)
-                const int i = idx / 6, g = idx - i * 6;
-                const int p = sh.P[g], q = sh.Q[g];
-                const double c = sh.C[g], sn = sh.S[g];
-                const double x = sh.V[i * 12 + p], y = sh.V[i * 12 + q];
-                sh.V[i * 12 + p] = c * x - sn * y;
-                sh.V[i * 12 + q] = sn * x + c * y;
+                sh.V[jg * 12 + p2] = c2 * v0p - sn2 * v0q;                              // V = V J, rows g and g + 6
+                sh.V[jg * 12 + q2] = sn2 * v0p + c2 * v0q;
+                sh.V[(jg + 6) * 12 + p2] = c2 * v1p - sn2 * v1q;
+                sh.V[(jg + 6) * 12 + q2] = sn2 * v1p + c2 * v1q;
             }
             WAVE_SYNC_PNP();
         }
         if (!rotated) break;
     }
+    if (stamps && h == 0 && lane == 0) { stamps[19] += __builtin_readcyclecounter() - t_jac0; stamps[20] += n_rounds; }   // diagnostic: Jacobi cycles, rounds
     HSTAMP(23);
     if (lane == 0) {
         // ascending selection sort on the diagonal, keep the 4 smallest eigenvectors
@@ -586,13 +605,16 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
         keepX[q][0] = (double)obj[3 * i]; keepX[q][1] = (double)obj[3 * i + 1]; keepX[q][2] = (double)obj[3 * i + 2];
         keepU[q][0] = (double)img[2 * i]; keepU[q][1] = (double)img[2 * i + 1];
     }
-    // state 0: compute J & err at param, step; state 1: check err at new param
+    // CvLevMarq's state machine with one pass per step. Every pass computes err AND the J sums at param. state 0 (the first pass only):
+    // take J, step. state 1: check err at the new param; a rejected step raises lambda and steps again from prev with the J it has;
+    // an accepted step that does not end the loop takes, in this same pass, the actions of the state-0 pass that would follow at these
+    // very parameters (lower lambda, termination test, prevErr2, J from sh.red, prev = param, step) - that pass would sum the same
+    // per-thread expressions in the same order, so it is not run. The J sums of a rejected or final step are dropped.
     t_lm0 = __builtin_readcyclecounter();
     for (;;) {
         n_pass++;
         unsigned long long t_p = __builtin_readcyclecounter();
 #define RSTAMP(k) do { if (stamps && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); stamps[k] += t_ - t_p; t_p = t_; } } while (0)
-        const bool jac = (sh.state == 0);
         double acc[28];
 #pragma unroll
         for (int k = 0; k < 28; k++) acc[k] = 0;
@@ -608,13 +630,13 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
                 U[0] = (double)img[2 * i]; U[1] = (double)img[2 * i + 1];
             }
             double Xc[3], dpdw[9];
-            d_angle_axis_rotate_jac(pa, X, Xc, jac ? dpdw : nullptr);
+            d_angle_axis_rotate_jac(pa, X, Xc, dpdw);
             Xc[0] += p3; Xc[1] += p4; Xc[2] += p5;
             const double z = Xc[2] ? 1. / Xc[2] : 1;
             const double x = Xc[0] * z, y = Xc[1] * z;
             const double ex = x * fx + cx - U[0], ey = y * fy + cy - U[1];
             acc[27] += ex * ex + ey * ey;
-            if (jac) {
+            {
                 double Ju[6], Jv[6];
                 const double du[3] = {fx * z, 0, -fx * x * z}, dv[3] = {0, fy * z, -fy * y * z};
 #pragma unroll
@@ -639,14 +661,10 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
         RSTAMP(11);
         if (tid == 0) {
             const double err2 = sh.red[27];
-            bool do_step = false;
+            bool do_step = false, take_j = false;
             if (sh.state == 0) {
-                int k = 0;
-                for (int a = 0; a < 6; a++)
-                    for (int b = a; b < 6; b++) { sh.JtJ[a * 6 + b] = sh.JtJ[b * 6 + a] = sh.red[k]; k++; }
-                for (int a = 0; a < 6; a++) { sh.JtErr[a] = sh.red[21 + a]; sh.prev[a] = sh.param[a]; }
                 if (sh.iters == 0) sh.prevErr2 = err2;
-                do_step = true;
+                take_j = do_step = true;
                 sh.state = 1;
             } else {
                 bool retry = false;
@@ -658,8 +676,14 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
                     double dn = 0, pn = 0;
                     for (int i = 0; i < 6; i++) { dn += (sh.param[i] - sh.prev[i]) * (sh.param[i] - sh.prev[i]); pn += sh.prev[i] * sh.prev[i]; }
                     if (++sh.iters >= 20 || sqrt(dn) / sqrt(pn) < (double)FLT_EPSILON) sh.done = 1;
-                    else { sh.prevErr2 = err2; sh.state = 0; }
+                    else { sh.prevErr2 = err2; take_j = do_step = true; }   // state 0's actions, now
                 }
+            }
+            if (take_j) {
+                int k = 0;
+                for (int a = 0; a < 6; a++)
+                    for (int b = a; b < 6; b++) { sh.JtJ[a * 6 + b] = sh.JtJ[b * 6 + a] = sh.red[k]; k++; }
+                for (int a = 0; a < 6; a++) { sh.JtErr[a] = sh.red[21 + a]; sh.prev[a] = sh.param[a]; }
             }
             if (do_step) {
                 // (JtJ + lambda diag(JtJ)) x = JtErr by Gaussian elimination with partial pivoting on [A | b], entirely in this
