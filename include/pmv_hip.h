@@ -12,6 +12,8 @@
  *                                          of the caller's own; the reference passes cv::Mat(), 3, 3, false, 0.04)
  *   pmv_corner_subpix                      cv::cornerSubPix on level 0 of a slot (the step between the detector and LK in the caller's own
  *                                          KLT front end; the reference hands integer corners on, OpenCVGoodFeatureExtractor.cpp:7)
+ *   pmv_frames_clahe                       cv::CLAHE::apply on level 0 of slots (the contrast equalisation a KLT front end of the caller's own runs
+ *                                          in front of the pyramid; the reference tracks the plain gray image, Frame.cpp:40-41)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -111,6 +113,54 @@ int pmv_frame_num_levels(pmv_ctx* ctx, int slot); /* maxLevel actually built (>=
  * lkpyramid.cpp, here PMV_PYR_PAD wide): (w + 128) x (h + 128) bytes, tightly packed; returns the padded dims. */
 #define PMV_PYR_PAD 64
 int pmv_frame_get_level_padded(pmv_ctx* ctx, int slot, int level, uint8_t* out, int* pw, int* ph);
+
+/* cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(level 0, level 0) on the slots first_slot .. first_slot + n - 1, then the
+ * 64-pixel REFLECT_101 frame of level 0 and every level above rebuilt from the equalised image: the step a KLT front end of the caller's
+ * own (VINS-style trackers by default) runs on every frame in front of the pyramid - so that such a front end never needs the frame in
+ * host memory. The reference never equalises (Frame.cpp:40-41 hands the gray image on); the whole-sequence drivers do not call this.
+ *   Slots: staged (pmv_frames_stage) or built (any upload, pmv_frames_build, a finished pmv_frames_stream_begin bracket); the slots of a
+ *     range may differ in size. Afterwards every slot is built and holds byte for byte what pmv_frame_upload of the equalised image would
+ *     have left, at every level with its border: pmv_frames_stage -> pmv_frames_clahe -> pmv_pipeline_run is the equalised run, whatever
+ *     build_pyramids says. A second call equalises again, as cv would. The launches go on the front-end stream and the call returns after
+ *     they complete. During a batch session the call stays legal under the caller's slot rule, like the other single calls.
+ *   Arithmetic, for a w x h level 0 and histSize 256:
+ *     1. Extended image: if w % tiles_x == 0 && h % tiles_y == 0 the image itself; otherwise the image extended on the right by
+ *        tiles_x - w % tiles_x columns and at the bottom by tiles_y - h % tiles_y rows with REFLECT_101 - cv's quirk included: a dimension
+ *        that DOES divide still gets a full extra tiles_x or tiles_y when the other one does not. tile size = (ext_w / tiles_x,
+ *        ext_h / tiles_y), area = their product. The kernels take the extension from the INTERIOR of level 0, never from the slot's own
+ *        border (a staged slot has none yet).
+ *     2. Constants, computed once per frame on the host: lutScale = (float)255 / area (a float division); cl = clip_limit > 0 ?
+ *        max((int)(clip_limit * area / 256), 1) : 0, evaluated in double and clamped to area before the cast (no bin can exceed area, so
+ *        this changes no result); inv_tw = 1.0f / tile_w, inv_th = 1.0f / tile_h.
+ *     3. Per tile: 256 int bins of the tile's area pixels. If cl > 0: clipped = sum of max(hist[i] - cl, 0), the bins are cut to cl,
+ *        batch = clipped / 256, residual = clipped - 256 batch, every bin += batch, and if residual != 0: step = max(256 / residual, 1),
+ *        for (i = 0; i < 256 && residual > 0; i += step, residual--) hist[i]++ (bin i gets the increment iff i % step == 0 &&
+ *        i / step < residual).
+ *     4. Per tile: lut[i] = saturate_u8(rint((float)sum * lutScale)) over the running int sum of the bins, rounding half to even (cvRound).
+ *     5. Per pixel (x, y) of value v: txf = x * inv_tw - 0.5f, tx1 = floor(txf), tx2 = tx1 + 1, xa = txf - tx1, xa1 = 1.0f - xa, then
+ *        tx1 = max(tx1, 0), tx2 = min(tx2, tiles_x - 1); the same for y; res = (lut[ty1][tx1][v] * xa1 + lut[ty1][tx2][v] * xa) * ya1 +
+ *        (lut[ty2][tx1][v] * xa1 + lut[ty2][tx2][v] * xa) * ya in float, in this order, without contraction; dst = saturate_u8(rint(res)).
+ *     Histograms are integer sums, so their order is free; nothing else needs one.
+ *   Kernels: k_clahe_lut (one workgroup per tile and frame, a histogram per wavefront in LDS, one thread per bin for the rest) and
+ *     k_clahe_apply (a pixel is read once and written once by the same thread, so it works in place), both driven by one record per frame:
+ *     ONE pair of launches per 64 frames whatever their sizes, then pmv_frames_build's launches. The scratch (records and 64 x 64 KB of
+ *     LUTs) is made by the first call on a context and is not sized by n. Booked under the level-0 profiling class.
+ *   [mem: OpenCV 3.4 clahe.cpp; parity unpinned like the rest of the front end - tests/twin/clahe_twin.cpp is the CPU restatement that
+ *   fixes the arithmetic, bit for bit.]
+ * Errors (nothing is written, nothing is clamped): PMV_ERR_INVALID - a null ctx or p, tiles_x or tiles_y outside 1..16, clip_limit negative
+ *   or not finite, an empty slot (the message names it), a call while a pmv_frames_stream_begin bracket or a batched run is open on the
+ *   context; PMV_ERR_CAPACITY - a slot range outside n_slots, as for pmv_frames_build.
+ * Out of scope: cv::equalizeHist, 16-bit images, more than 16 tiles in a direction, equalisation inside a pmv_frames_stream_begin bracket
+ *   or inside the feeder of the two batched runs (staged runs get it through pmv_frames_stage -> pmv_frames_clahe). pmv_frame_upload
+ *   followed by pmv_frames_clahe builds the pyramid twice; the session form pmv_batch_frame_upload_clahe does not. */
+typedef struct pmv_clahe_params {
+    double clip_limit;   /* cv's clipLimit; 0 = no clipping; 0 <= clip_limit, finite */
+    int tiles_x, tiles_y;/* cv's tileGridSize (width, height); 1 .. 16 each */
+} pmv_clahe_params;
+int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params* p);
+/* diagnostic: {LUT + apply launch pairs of pmv_frames_clahe, session upload rounds that held at least one pmv_batch_frame_upload_clahe
+ * request, launch pairs made for them} since the context was created. */
+int pmv_debug_clahe_launches(pmv_ctx* ctx, long long* out3);
 
 /* ---- feature extraction ------------------------------------------------------------------------ */
 /* cells: n_cells * 4 ints (x0, y0, w, h), each <= 255x255, sub-views of the frame in `slot`.
@@ -562,6 +612,17 @@ int pmv_batch_close(pmv_ctx* ctx);
  *     (BGR) is PMV_ERR_CAPACITY; a slot outside n_slots is PMV_ERR_CAPACITY, as for pmv_frame_upload.
  *   Two uploads into one slot that meet in a round are built one after the other, in arrival order. */
 int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format);
+/* pmv_batch_frame_upload with the equalisation of pmv_frames_clahe inside the same upload round: the arguments, sources (pageable, pinned in
+ * place, device in place, any stride), errors and return rule of pmv_batch_frame_upload, plus p (NULL is PMV_ERR_INVALID - the plain call
+ * stays the way to upload without equalisation; the parameter errors of pmv_frames_clahe). The slot then holds the bytes of
+ * pmv_frame_upload[_bgr] followed by pmv_frames_clahe with the same p, and the pyramid is built once.
+ *   The upload thread serves these requests in the same round as plain uploads. A round with at least one of them runs, in this order: the
+ *   level-0 launches it always makes; ONE k_clahe_lut launch and ONE k_clahe_apply launch for all its CLAHE requests, whatever their frame
+ *   sizes and parameters (each record names its own); ONE in-place k_pad_level0 launch over those slots, which rebuilds their REFLECT_101
+ *   frame and is counted as a level-0 launch of the round (pmv_batch_upload_stats out4[2], pmv_batch_upload_rounds [5]); the k_pyrdown
+ *   launches it always makes. A round without CLAHE requests launches exactly what it launched before, and its records are what they were.
+ *   The LUT scratch of a round (256 bytes per tile) is the session's own and grows to the largest round seen. */
+int pmv_batch_frame_upload_clahe(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* p);
 /* The contracts of the pmv_* calls of the same name, argument for argument and status code for status code, served by the class's combiner
  * in batched launches (LK and kNN: the LK combiners; the three detectors: the detector combiner). The slots must hold frames of a declared
  * size (else PMV_ERR_INVALID). */
@@ -613,7 +674,8 @@ int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, con
                                  double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
                            uint8_t* mask, double* tri4n, int* out_good);
-/* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds, and the
+/* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds (+ 1 for a
+ * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation), and the
  * pyrDown launches are the sum over the rounds of the levels above 0 of each round's tallest pyramid. */
 int pmv_batch_upload_stats(pmv_ctx* ctx, long long* out4);
 /* diagnostic: one record of 8 ints per upload round since pmv_batch_open (the first 65536 rounds), in order:

@@ -46,6 +46,25 @@ class SubpixParams(C.Structure):
     _fields_ = [("win_w", C.c_int), ("win_h", C.c_int), ("zero_w", C.c_int), ("zero_h", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double)]
 
 
+class ClaheParams(C.Structure):
+    """pmv_clahe_params of include/pmv_hip.h"""
+    _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
+
+
+def _clahe_params(who, clip_limit, tiles):
+    # refused before the library is touched: what the struct cannot hold as the caller meant it
+    if isinstance(clip_limit, (bool, np.bool_)) or not isinstance(clip_limit, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}: clip_limit must be a number, got {clip_limit!r}")
+    try:
+        tx, ty = tiles
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: tiles is a (tiles_x, tiles_y) pair, got {tiles!r}") from None
+    for t in (tx, ty):
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"{who}: tiles is a pair of integers, got {tiles!r}")
+    return ClaheParams(float(clip_limit), int(tx), int(ty))
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 # the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
 LK_USE_INITIAL_FLOW = 4
@@ -57,6 +76,7 @@ ABI_SYMBOLS = [
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
+    "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -429,6 +449,20 @@ class Context:
 
     def frames_build(self, first_slot, n):
         self._ck(self.lib.pmv_frames_build(self.h, first_slot, n))
+
+    def frames_clahe(self, first_slot, n, clip_limit=40.0, tiles=(8, 8)):
+        """pmv_frames_clahe: cv::createCLAHE(clip_limit, tiles)->apply on level 0 of the staged or built slots first_slot .. first_slot + n - 1,
+        in place, then the border and the levels above rebuilt; the defaults are cv's. tiles = (tiles_x, tiles_y), 1..16 each."""
+        p = _clahe_params("frames_clahe", clip_limit, tiles)
+        self.lib.pmv_frames_clahe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ClaheParams)]
+        self._ck(self.lib.pmv_frames_clahe(self.h, int(first_slot), int(n), C.byref(p)))
+
+    def debug_clahe_launches(self):
+        """pmv_debug_clahe_launches: [launch pairs of frames_clahe, session upload rounds with a CLAHE request, launch pairs made for them]"""
+        out = (C.c_longlong * 3)()
+        self.lib.pmv_debug_clahe_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_clahe_launches(self.h, out))
+        return [int(v) for v in out]
 
     def num_levels(self, slot):
         return self.lib.pmv_frame_num_levels(self.h, slot)
@@ -961,12 +995,24 @@ class Context:
                 self.batch_close()
         return session()
 
-    def batch_frame_upload(self, slot, frame, fmt="gray"):
+    def batch_frame_upload(self, slot, frame, fmt="gray", clahe=None):
         """one frame into `slot` through the session's upload class (see _upload_source for what `frame` may be); returns when the slot's
         pyramid is built. A pinned or device source is read in place by a kernel on the session's own stream: the work that produced it (a
-        torch op on torch's stream, say) must have completed - torch.cuda.synchronize() or a blocking copy - before this call"""
+        torch op on torch's stream, say) must have completed - torch.cuda.synchronize() or a blocking copy - before this call.
+        clahe: None, or (clip_limit, (tiles_x, tiles_y)) - level 0 is equalised inside the same upload round (pmv_batch_frame_upload_clahe)"""
+        p = None
+        if clahe is not None:
+            try:
+                clip_limit, tiles = clahe
+            except (TypeError, ValueError):
+                raise ValueError(f"batch_frame_upload: clahe is None or (clip_limit, (tiles_x, tiles_y)), got {clahe!r}") from None
+            p = _clahe_params("batch_frame_upload", clip_limit, tiles)
         addr, w, h, stride, f, keep = _upload_source(frame, fmt)
-        self._ckt(self.lib.pmv_batch_frame_upload(self.h, int(slot), C.c_void_p(addr), w, h, stride, f))
+        if p is None:
+            self._ckt(self.lib.pmv_batch_frame_upload(self.h, int(slot), C.c_void_p(addr), w, h, stride, f))
+        else:
+            self.lib.pmv_batch_frame_upload_clahe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ClaheParams)]
+            self._ckt(self.lib.pmv_batch_frame_upload_clahe(self.h, int(slot), C.c_void_p(addr), w, h, stride, f, C.byref(p)))
         del keep
 
     def batch_upload_stats(self):

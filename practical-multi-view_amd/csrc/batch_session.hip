@@ -11,6 +11,9 @@
 //     slot_layout / slot_state of the round's slots and wakes exactly the callers it served. A request returns only after its round's
 //     completion word was seen, so the slot may be read by any session call from any thread without further ordering - the argument the
 //     feeder's release rule uses (ingest_batch.hip).
+//     A request of pmv_batch_frame_upload_clahe rides in the same round: behind the level-0 launches the round makes ONE k_clahe_lut and ONE
+//     k_clahe_apply launch for all such requests (frontend_clahe.hip: a record per frame names its size and parameters) and ONE in-place
+//     k_pad_level0_list launch over their slots, in front of the k_pyrdown launches. A round without such a request launches what it always did.
 //   * Sources. Pinned memory mapped at its host address and device memory of the context's device are read in place by the kernel, with the
 //     caller's row stride as the entry's pitch. Anything else is copied by the CALLING thread, row by row and tight, into a block of the
 //     session's pinned staging pool; the kernel reads it from there. The callers' threads launch nothing and wait for no stream: their one
@@ -41,6 +44,8 @@ struct UpReq {
     const uint8_t* dsrc = nullptr;   // the address the kernel reads: the caller's own buffer (in place) or a staging block
     unsigned pitch = 0;
     bool in_place = false;           // dsrc is the caller's own buffer
+    bool clahe = false;              // pmv_batch_frame_upload_clahe: level 0 is equalised with `cp` inside the round
+    pmv_clahe_params cp = {0.0, 0, 0};
     int rc = PMV_OK;
     char err[200] = "";
     std::atomic<int> done{0};        // completion word of the request: the owner sleeps on it (futex), as in batch_engine.hip
@@ -70,8 +75,11 @@ struct BatchSession {
     std::condition_variable cv;
     std::vector<UpReq*> pending;
     bool stop = false;
-    // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND]
+    // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND |
+    // CLAHE PyrListEntry x ROUND | ClaheRec x ROUND] (the last two are written only by a round with CLAHE requests)
     char* h_tab = nullptr; char* dm_tab = nullptr;
+    // LUT blocks of a round's CLAHE requests (HBM): made by the first such round, grown to the largest round seen
+    uint8_t* d_lut = nullptr; size_t lut_cap = 0;
     // staging pool: n_blk blocks of blk_bytes (the largest BGR frame of the declared sizes), pinned + mapped
     uint8_t* h_pool = nullptr; uint8_t* dm_pool = nullptr;
     size_t blk_bytes = 0;
@@ -127,13 +135,18 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     const PyrPitchEntry* dg = (const PyrPitchEntry*)S->dm_tab;
     const PyrPitchEntry* dc = dg + BatchSession::ROUND;
     const PyrListEntry* da = (const PyrListEntry*)(dc + BatchSession::ROUND);
+    PyrListEntry* te = ta + BatchSession::ROUND;                 // the slots of the round's CLAHE requests (in-place entries)
+    ClaheRec* tr = (ClaheRec*)(te + BatchSession::ROUND);
+    const PyrListEntry* de = da + BatchSession::ROUND;
+    const ClaheRec* dr = (const ClaheRec*)(de + BatchSession::ROUND);
     // grid and LDS of a launch from the largest geometry among ITS entries, level by level
-    PyrLayout Lg{}, Lc{}, La{};
+    PyrLayout Lg{}, Lc{}, La{}, Le{};
     auto widen = [](PyrLayout& M, const PyrLayout& L) {
         M.n_levels = std::max(M.n_levels, L.n_levels);
         for (int l = 0; l < L.n_levels; l++) { M.w[l] = std::max(M.w[l], L.w[l]); M.h[l] = std::max(M.h[l], L.h[l]); }
     };
-    int ng = 0, nc = 0, na = 0;
+    int ng = 0, nc = 0, na = 0, ne = 0, max_tiles = 0;
+    size_t lut_bytes = 0;
     for (UpReq* r : batch) {
         const PyrLayout& L = ctx->geom[(size_t)r->geom];
         PyrPitchEntry& e = r->format == PMV_FRAMES_BGR ? tc[nc++] : tg[ng++];
@@ -142,6 +155,15 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
         widen(La, L);
         ta[na].src = nullptr; ta[na].slot = r->slot; ta[na].geom = r->geom;
         na++;
+        if (r->clahe) {
+            tr[ne] = clahe_record(r->slot, r->geom, L.w[0], L.h[0], r->cp.clip_limit, r->cp.tiles_x, r->cp.tiles_y);
+            tr[ne].lut_off = (unsigned)lut_bytes;
+            lut_bytes += (size_t)(r->cp.tiles_x * r->cp.tiles_y) * 256;
+            max_tiles = std::max(max_tiles, r->cp.tiles_x * r->cp.tiles_y);
+            te[ne].src = nullptr; te[ne].slot = r->slot; te[ne].geom = r->geom;
+            widen(Le, L);
+            ne++;
+        }
     }
     // A round that fails after its first launch must not hand the sources back while a kernel still reads them: wait for the stream first.
     auto fail = [&](const char* what, hipError_t err) { (void)hipStreamSynchronize(S->stream); fail_round(batch, what, err); };
@@ -155,6 +177,19 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
         if ((e = launch_pad_level0_bgr_pitched(S->stream, ctx->d_slots, ctx->d_geom, Lc, dc, nc)) != hipSuccess) { fail("k_pad_level0_bgr_pitched", e); return; }
         rec.l0_launches++;
     }
+    if (ne) {
+        // level 0 of the round's CLAHE requests is equalised where the launches above left it, then its REFLECT_101 frame is rebuilt in place
+        if (lut_bytes > S->lut_cap) {   // (the stream is idle between rounds: the previous round was waited for)
+            if (S->d_lut) (void)hipFree(S->d_lut);
+            S->d_lut = nullptr; S->lut_cap = 0;
+            if ((e = hipMalloc(&S->d_lut, lut_bytes)) != hipSuccess) { fail("the LUT scratch", e); return; }
+            S->lut_cap = lut_bytes;
+        }
+        if ((e = launch_clahe(S->stream, ctx->d_slots, ctx->d_geom, dr, ne, max_tiles, Le.w[0], Le.h[0], S->d_lut)) != hipSuccess) { fail("k_clahe_lut / k_clahe_apply", e); return; }
+        ctx->clahe_launches[2]++;
+        if ((e = launch_pad_level0_list(S->stream, ctx->d_slots, ctx->d_geom, Le, de, ne)) != hipSuccess) { fail("k_pad_level0_list", e); return; }
+        rec.l0_launches++;
+    }
     for (int l = 1; l < La.n_levels; l++) {
         if ((e = launch_pyrdown_list(S->stream, ctx->d_slots, ctx->d_geom, La, l, da, na)) != hipSuccess) { fail("k_pyrdown", e); return; }
         rec.pyr_launches++;
@@ -166,6 +201,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
         rec.by_levels[ctx->geom[(size_t)r->geom].n_levels - 1]++;
         rec.in_place += r->in_place ? 1 : 0;
     }
+    if (ne) ctx->clahe_launches[1]++;
     S->rounds++; S->frames += na; S->l0_launches += rec.l0_launches; S->pyr_launches += rec.pyr_launches;
     std::lock_guard<std::mutex> lk(S->log_mu);
     if (S->log.size() < BatchSession::ROUND_LOG) S->log.push_back(rec);
@@ -210,6 +246,7 @@ void session_free(BatchSession* S) {
     if (S->h_done) (void)hipHostFree(S->h_done);
     if (S->h_tab) (void)hipHostFree(S->h_tab);
     if (S->h_pool) (void)hipHostFree(S->h_pool);
+    if (S->d_lut) (void)hipFree(S->d_lut);
     delete S;
 }
 
@@ -282,7 +319,7 @@ int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes) {
     S->ctx = ctx; S->eng = eng; S->n_seq = n_seq;
     S->seq_mu.reset(new std::mutex[(size_t)n_seq]);
     hipError_t e = hipSuccess;
-    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + sizeof(PyrListEntry));
+    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + 2 * sizeof(PyrListEntry) + sizeof(ClaheRec));
     S->blk_bytes = (max_fb + 255) & ~(size_t)255;
     // two blocks per sequence (frames k - 1 and k on their way), within 4 .. 64 blocks and 256 MB; an uploader without a block waits for one
     const int n_blk = (int)std::max<size_t>(2, std::min<size_t>({(size_t)64, std::max<size_t>(4, 2 * (size_t)n_seq), ((size_t)256 << 20) / S->blk_bytes}));
@@ -335,13 +372,15 @@ int pmv_batch_upload_rounds(pmv_ctx* ctx, int* out8, int capacity) {
     return (int)S->log.size();
 }
 
-int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format) {
+// pmv_batch_frame_upload and, with cp, pmv_batch_frame_upload_clahe (cp: checked by the caller): one request of the upload class
+static int session_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* cp) {
     SESSION("pmv_batch_frame_upload");
     REQ(pixels, PMV_ERR_INVALID, "pmv_batch_frame_upload: null argument");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_batch_frame_upload: slot %d out of range", slot);
     REQ(format == PMV_FRAMES_GRAY || format == PMV_FRAMES_BGR, PMV_ERR_INVALID, "pmv_batch_frame_upload: unknown format %d (PMV_FRAMES_GRAY = 0, PMV_FRAMES_BGR = 1)", format);
     UpReq r;
     r.slot = slot; r.format = format;
+    if (cp) { r.clahe = true; r.cp = *cp; }
     r.geom = ctx->geom_index(w, h);
     REQ(r.geom >= 0, PMV_ERR_INVALID, "pmv_batch_frame_upload: a %dx%d frame: that size was not declared at pmv_batch_open", w, h);
     const size_t row = (size_t)w * (format == PMV_FRAMES_BGR ? 3 : 1);
@@ -393,6 +432,16 @@ int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w,
     }
     if (r.rc != PMV_OK) set_err(ctx, "%s", r.err);
     return r.rc;
+}
+
+int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format) {
+    return session_upload(ctx, slot, pixels, w, h, stride, format, nullptr);
+}
+
+int pmv_batch_frame_upload_clahe(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* p) {
+    if (!ctx) { set_err(nullptr, "pmv_batch_frame_upload_clahe: null ctx"); return PMV_ERR_INVALID; }
+    if (const int rc = clahe_check(ctx, "pmv_batch_frame_upload_clahe", p)) return rc;
+    return session_upload(ctx, slot, pixels, w, h, stride, format, p);
 }
 
 // ---- front-end calls: the checks of the single call, then a request of the class's combiner ------------------------------------------

@@ -121,6 +121,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->lk_work) a.store(0);
     for (auto& a : c->batch_launches) a.store(0);
     for (auto& a : c->subpix_launches) a.store(0);
+    for (auto& a : c->clahe_launches) a.store(0);
     CK(hipMalloc(&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMalloc(&c->d_cells, MAX_CELLS * CELL_STRIDE * 4));
@@ -170,6 +171,9 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->h_subpix) hipHostFree(c->h_subpix);
     if (c->h_subpix_tab) hipHostFree(c->h_subpix_tab);
     if (c->d_subpix_tab) hipFree(c->d_subpix_tab);
+    if (c->h_clahe) hipHostFree(c->h_clahe);
+    if (c->d_clahe) hipFree(c->d_clahe);
+    if (c->d_clahe_lut) hipFree(c->d_clahe_lut);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
     hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
@@ -359,6 +363,80 @@ int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int 
     ctx->slot_state[slot] = SLOT_BUILT;
     return PMV_OK;
 }
+
+}  // extern "C"
+
+int pmv::clahe_check(pmv_ctx* ctx, const char* who, const pmv_clahe_params* p) {
+    REQ(p, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(p->tiles_x >= 1 && p->tiles_x <= CLAHE_MAX_TILES && p->tiles_y >= 1 && p->tiles_y <= CLAHE_MAX_TILES, PMV_ERR_INVALID, "%s: tiles = (%d, %d) is outside 1..%d", who,
+        p->tiles_x, p->tiles_y, CLAHE_MAX_TILES);
+    REQ(p->clip_limit >= 0.0 && std::isfinite(p->clip_limit), PMV_ERR_INVALID, "%s: clip_limit = %g is negative or not finite", who, p->clip_limit);   // (a NaN fails the comparison too)
+    return PMV_OK;
+}
+
+extern "C" {
+
+// cv::CLAHE::apply on level 0 of the slots, in place, then the REFLECT_101 frame and the levels above through pmv_frames_build's launches.
+// A chunk of CLAHE_CHUNK frames is ONE pair of launches whatever its sizes: every record names its entry of the chunk's own geometry table.
+int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params* p) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_frames_clahe: null argument");
+    if (const int rc_ = clahe_check(ctx, "pmv_frames_clahe", p)) return rc_;
+    REQ(first_slot >= 0 && n >= 1 && first_slot <= ctx->n_slots - n, PMV_ERR_CAPACITY, "pmv_frames_clahe: slots [%d,%d) out of range (n_slots %d)", first_slot, first_slot + n, ctx->n_slots);
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_frames_clahe: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
+    REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_frames_clahe: a batched run is open on this context");
+    for (int i = 0; i < n; i++) REQ(ctx->slot_state[first_slot + i] != SLOT_EMPTY, PMV_ERR_INVALID, "pmv_frames_clahe: slot %d is empty (never staged or uploaded)", first_slot + i);
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    constexpr int CH = pmv_ctx::CLAHE_CHUNK;
+    constexpr size_t tab_bytes = (size_t)CH * (sizeof(ClaheRec) + sizeof(PyrLayout));
+    if (!ctx->h_clahe) CKC(hipHostMalloc(&ctx->h_clahe, tab_bytes, hipHostMallocDefault));
+    if (!ctx->d_clahe) CKC(hipMalloc(&ctx->d_clahe, tab_bytes));
+    if (!ctx->d_clahe_lut) CKC(hipMalloc(&ctx->d_clahe_lut, (size_t)CH * CLAHE_LUT_MAX));
+    ClaheRec* recs = (ClaheRec*)ctx->h_clahe;
+    PyrLayout* tab = (PyrLayout*)(recs + CH);
+    for (int i0 = 0; i0 < n; i0 += CH) {
+        const int nb = std::min(CH, n - i0);
+        int n_geom = 0, max_tiles = 0, max_w = 0, max_h = 0;
+        unsigned lut_off = 0;
+        for (int i = 0; i < nb; i++) {
+            const int slot = first_slot + i0 + i;
+            const PyrLayout& L = ctx->slot_layout[slot];
+            int g = 0;
+            while (g < n_geom && (tab[g].w[0] != L.w[0] || tab[g].h[0] != L.h[0])) g++;
+            if (g == n_geom) tab[n_geom++] = L;
+            recs[i] = clahe_record(slot, g, L.w[0], L.h[0], p->clip_limit, p->tiles_x, p->tiles_y);
+            recs[i].lut_off = lut_off;
+            lut_off += (unsigned)(p->tiles_x * p->tiles_y) * 256u;
+            max_tiles = p->tiles_x * p->tiles_y; max_w = std::max(max_w, L.w[0]); max_h = std::max(max_h, L.h[0]);
+        }
+        CKC(hipMemcpyAsync(ctx->d_clahe, ctx->h_clahe, tab_bytes, hipMemcpyHostToDevice, ctx->s_front));
+        CKC(launch_clahe(ctx->s_front, ctx->d_slots, (const PyrLayout*)(ctx->d_clahe + (size_t)CH * sizeof(ClaheRec)), (const ClaheRec*)ctx->d_clahe, nb, max_tiles, max_w, max_h,
+                         ctx->d_clahe_lut));
+        ctx->clahe_launches[0]++;
+        CKC(hipStreamSynchronize(ctx->s_front));   // (the next chunk rewrites the pinned tables)
+    }
+    // the REFLECT_101 frame of level 0 in place and the levels above: consecutive slots of one geometry in one launch per level
+    int i = 0;
+    while (i < n) {
+        const PyrLayout& L = ctx->slot_layout[first_slot + i];
+        int j = i + 1;
+        while (j < n && ctx->slot_layout[first_slot + j].w[0] == L.w[0] && ctx->slot_layout[first_slot + j].h[0] == L.h[0]) j++;
+        if (const int rc_ = build_levels_on(ctx, ctx->s_front, first_slot + i, j - i, L)) return rc_;
+        i = j;
+    }
+    CKC(hipStreamSynchronize(ctx->s_front));
+    for (int k = 0; k < n; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
+    return PMV_OK;
+}
+int pmv_debug_clahe_launches(pmv_ctx* ctx, long long* out3) {
+    REQ(ctx && out3, PMV_ERR_INVALID, "pmv_debug_clahe_launches: null argument");
+    for (int i = 0; i < 3; i++) out3[i] = ctx->clahe_launches[i].load();
+    return PMV_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int pmv_frame_num_levels(pmv_ctx* ctx, int slot) {
     if (!ctx || slot < 0 || slot >= ctx->n_slots) return PMV_ERR_INVALID;

@@ -88,6 +88,13 @@ struct pmv_ctx {
     int subpix_tab_key[4] = {0, 0, 0, 0};
     // pmv_debug_subpix_launches: launches of the single call | session rounds with a subpix request | launches made for them
     std::atomic<long long> subpix_launches[3];
+    // pmv_frames_clahe, made by the first call (a context that never makes one pays nothing): a chunk's frame records and the geometry table
+    // they index, [ClaheRec x CLAHE_CHUNK | PyrLayout x CLAHE_CHUNK], in pinned host memory and in HBM, and the chunk's LUT blocks in HBM. The
+    // table is the call's own: the context's geometry table belongs to a session or a batched run, and this call stays legal beside a session.
+    static constexpr int CLAHE_CHUNK = 64;   // frames per pair of launches: the scratch is sized by this, not by the call's n
+    uint8_t* h_clahe = nullptr; uint8_t* d_clahe = nullptr; uint8_t* d_clahe_lut = nullptr;
+    // pmv_debug_clahe_launches: LUT + apply launch pairs of pmv_frames_clahe | session upload rounds with a CLAHE request | launch pairs made for them
+    std::atomic<long long> clahe_launches[3];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -161,6 +168,8 @@ inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
     const bool on = p->zero_w >= 0 && p->zero_h >= 0 && 2 * p->zero_w + 1 < 2 * p->win_w + 1 && 2 * p->zero_h + 1 < 2 * p->win_h + 1;
     *zw = on ? p->zero_w : -1; *zh = on ? p->zero_h : -1;
 }
+// pmv_frames_clahe / pmv_batch_frame_upload_clahe: the parameter checks of the contract (`who` names the call in the messages)
+int clahe_check(pmv_ctx* ctx, const char* who, const pmv_clahe_params* p);
 // after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current

@@ -294,4 +294,29 @@ hipError_t launch_corner_subpix(hipStream_t s, const uint8_t* slots, const PyrLa
 hipError_t launch_corner_subpix_geom(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const SubpixRec* d_recs, int n, const float* d_table,
                                      const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
 
+// ---- contrast-limited equalisation of level 0 (frontend_clahe.hip) -------------------------------------------------
+// pmv_frames_clahe / pmv_batch_frame_upload_clahe: cv::CLAHE::apply on the interior of level 0, in place. One record per frame names its
+// slot, its entry of a geometry table, its tile grid and the constants of include/pmv_hip.h (computed once on the host: clahe_record), and
+// where its LUT block starts in the launch's LUT scratch, so ONE pair of launches serves any number of frames of any sizes and parameters.
+constexpr int CLAHE_MAX_TILES = 16;                                        // per direction
+constexpr size_t CLAHE_LUT_MAX = (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256;   // bytes of a frame's LUT block at most
+struct __attribute__((aligned(16))) ClaheRec {
+    int slot, geom;               // frame slot, entry of the launch's geometry table
+    int tiles_x, tiles_y;         // cv's tileGridSize
+    int tile_w, tile_h;           // tile size on the extended image
+    int clip;                     // cl: the bins' ceiling, 0 = no clipping
+    float lut_scale;              // (float)255 / (tile_w * tile_h)
+    float inv_tw, inv_th;         // 1.0f / tile_w, 1.0f / tile_h
+    unsigned lut_off;             // byte offset of the frame's tiles_x * tiles_y * 256 LUT bytes in the LUT scratch
+    int reserved;
+};
+static_assert(sizeof(ClaheRec) == 48, "ClaheRec: one 48-byte record per frame");
+// the record of a w x h frame (lut_off left 0): cv's extension rule and constants, in the contract's arithmetic
+ClaheRec clahe_record(int slot, int geom, int w, int h, double clip_limit, int tiles_x, int tiles_y);
+// k_clahe_lut then k_clahe_apply over n records in device-visible memory; d_geom[record.geom] (device memory) is the record's frame.
+// max_tiles, max_w, max_h: the largest tiles_x * tiles_y, level-0 width and height among the records - they size the grids; a workgroup
+// beyond its own frame's tiles or rows leaves before its first load or barrier. d_lut: the LUT scratch (device memory) that holds every
+// record's block. Both launches are booked under the level-0 profiling class.
+hipError_t launch_clahe(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const ClaheRec* d_recs, int n, int max_tiles, int max_w, int max_h, uint8_t* d_lut);
+
 }  // namespace pmv
