@@ -14,6 +14,8 @@
  *                                          KLT front end; the reference hands integer corners on, OpenCVGoodFeatureExtractor.cpp:7)
  *   pmv_frames_clahe                       cv::CLAHE::apply on level 0 of slots (the contrast equalisation a KLT front end of the caller's own runs
  *                                          in front of the pyramid; the reference tracks the plain gray image, Frame.cpp:40-41)
+ *   pmv_frames_remap                       cv::remap(INTER_LINEAR, BORDER_CONSTANT) on level 0 of slots: the lens undistortion every camera but a
+ *                                          rectified one needs in front of everything else (the reference takes K alone: a pinhole camera)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -161,6 +163,66 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
 /* diagnostic: {LUT + apply launch pairs of pmv_frames_clahe, session upload rounds that held at least one pmv_batch_frame_upload_clahe
  * request, launch pairs made for them} since the context was created. */
 int pmv_debug_clahe_launches(pmv_ctx* ctx, long long* out3);
+
+/* ---- lens undistortion: cv::remap of frame slots ------------------------------------------------ */
+/* A remap map, created once per camera: map_x and map_y are the tight w x h CV_32FC1 maps of cv::remap, dst(x, y) = src(map_x(x, y),
+ * map_y(x, y)) - from pmv_undistort_map_build, cv::initUndistortRectifyMap, cv::fisheye::initUndistortRectifyMap or the caller's own model.
+ * The call converts them ONCE, on the host, into cv's fixed-point form and keeps the packed map in device memory; map_x and map_y may be
+ * freed when it returns. At most 16 maps per context; a map's memory is sized by w h.
+ *   Conversion per element (INTER_BITS 5): sx = cvRound(map_x * 32.0f) - a float product, which is exact, rounded half to even; a NaN or a
+ *     value beyond int32 gives INT_MIN, as cvtss2si does; ix = saturate_s16(sx >> 5) with an arithmetic shift, fx = sx & 31. The same for y.
+ *   Packing (private): two planes over the linear pixel index y w + x, each padded to a multiple of four entries - a dword (ix & 0xffff) |
+ *     iy << 16 and a halfword fx | fy << 5: 6 bytes per pixel.
+ *   [mem: OpenCV 3.4 imgwarp.cpp, remap with INTER_LINEAR, the CV_32FC1 pair converted as convertMaps does]
+ * Errors: PMV_ERR_INVALID - a null argument, or w, h outside 1 .. the context's max_w, max_h; PMV_ERR_CAPACITY - a 17th map.
+ * pmv_remap_map_destroy: PMV_ERR_INVALID for an unknown id, and while a batch session is open on the context (its upload rounds read the
+ * maps of their requests). pmv_ctx_destroy frees the maps that are left. */
+int pmv_remap_map_create(pmv_ctx* ctx, int w, int h, const float* map_x, const float* map_y, int* out_id);
+int pmv_remap_map_destroy(pmv_ctx* ctx, int id);
+/* cv::remap(level 0, level 0, map, INTER_LINEAR, BORDER_CONSTANT, Scalar(border_value)) on the slots first_slot .. first_slot + n - 1, then the
+ * 64-pixel REFLECT_101 frame of level 0 and every level above rebuilt from the remapped image: with an undistortion map, cv::undistort on
+ * the device, the first link of pmv_frames_remap -> pmv_frames_clahe -> pmv_detect_gftt_ex -> pmv_corner_subpix -> pmv_lk_track_fb. The
+ * reference never undistorts (it takes K alone and KITTI's images are rectified); the whole-sequence drivers do not call this.
+ *   Slots: the rules of pmv_frames_clahe - staged (pmv_frames_stage) or built; afterwards every slot is built and holds byte for byte what
+ *     pmv_frame_upload of the remapped image would have left, at every level with its border, whatever build_pyramids says. A second call
+ *     remaps again. The launches go on the front-end stream and the call returns after they complete. During a batch session the call
+ *     stays legal under the caller's slot rule.
+ *   Source and destination have the same size (cv::undistort's case): every slot's level-0 size must equal the map's size.
+ *   Arithmetic per destination pixel, with (ix, iy, fx, fy) of the map: tap(x, y) = src(x, y) inside the w x h interior of level 0, else
+ *     border_value - the taps are never read from the slot's own border (a staged slot has none yet);
+ *     D = ((32 - fy)(32 - fx) tap(ix, iy) + (32 - fy) fx tap(ix + 1, iy) + fy (32 - fx) tap(ix, iy + 1) + fy fx tap(ix + 1, iy + 1) + 512) >> 10.
+ *     This equals cv's (sum of w tap + 2^14) >> 15, because every weight of cv's table is 32 times the one above; it copies the source
+ *     exactly where fx = fy = 0, and it covers cv's three branches (all taps inside, all outside, mixed) with one rule. Integer arithmetic:
+ *     no order to fix.
+ *   Kernel: k_remap, driven by one record per frame (slot, geometry entry, packed map, border value, scratch offset): ONE launch per 64
+ *     frames. A gather cannot run in place: k_remap reads the raw interior of level 0 and writes a tight frame into a scratch area (made by
+ *     the first call, 64 frames of the context's capacity, and is not sized by n); the list-form k_pad_level0 launch with that frame as its
+ *     source writes level 0 and its border, the k_pyrdown launches the levels above. Booked under the level-0 profiling class.
+ *   [mem: OpenCV 3.4 imgwarp.cpp, remapBilinear; parity with a real OpenCV is unpinned like the rest of the front end -
+ *   tests/twin/remap_twin.cpp is the CPU restatement that fixes the bits.]
+ * Errors (nothing is written, nothing is clamped): PMV_ERR_INVALID - a null ctx, an unknown map_id, border_value outside 0..255, an empty
+ *   slot (the message names it), a slot whose level-0 size is not the map's (the message names the slot and both sizes), a call while a
+ *   pmv_frames_stream_begin bracket or a batched run is open on the context; PMV_ERR_CAPACITY - a slot range outside n_slots, as for
+ *   pmv_frames_build.
+ * Out of scope: other interpolations and border modes, a destination size different from the source size, 16-bit images, remap inside a
+ *   pmv_frames_stream_begin bracket or inside the feeder of the two batched runs. pmv_frame_upload followed by pmv_frames_remap builds the
+ *   pyramid twice; the session form pmv_batch_frame_upload_remap does not. */
+int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border_value);
+/* diagnostic: {k_remap launches of pmv_frames_remap, session upload rounds that held at least one pmv_batch_frame_upload_remap request,
+ * k_remap launches made for them} since the context was created. */
+int pmv_debug_remap_launches(pmv_ctx* ctx, long long* out3);
+/* The map of cv::initUndistortRectifyMap(K, dist, R, newK, Size(w, h), CV_32FC1), on the host; needs no context (pmv_last_error(NULL) has
+ * the message of a refusal). K9, R9, newK9: row-major 3 x 3; dist8 = (k1, k2, p1, p2, k3, k4, k5, k6); a null R is the identity, a null newK
+ * is K. map_x, map_y: w h floats each, for pmv_remap_map_create.
+ *   In double, for column j and row i: (X, Y, W) = (newK R)^-1 (j, i, 1), the inverse by adjugate and determinant; x = X / W, y = Y / W,
+ *   r2 = x^2 + y^2; kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2); xd = x kr + p1 (2xy) + p2 (r2 + 2x^2);
+ *   yd = y kr + p1 (r2 + 2y^2) + p2 (2xy); map_x = (float)(fx xd + cx), map_y = (float)(fy yd + cy) with K's fx, fy, cx, cy.
+ *   cv walks the ray incrementally along a row, so its last double bits differ: this helper is held to a tolerance (one float ulp of the
+ *   coordinate), not to bits; the bits that matter are those of pmv_frames_remap given the float maps. cv::fisheye models are out of scope
+ *   (a caller's own float maps serve them).
+ * Errors: PMV_ERR_INVALID - a null K9, dist8, map_x or map_y, a singular newK R, w or h < 1. */
+int pmv_undistort_map_build(const double* K9, const double* dist8, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x,
+                            float* map_y);
 
 /* ---- feature extraction ------------------------------------------------------------------------ */
 /* cells: n_cells * 4 ints (x0, y0, w, h), each <= 255x255, sub-views of the frame in `slot`.
@@ -623,6 +685,19 @@ int pmv_batch_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w,
  *   launches it always makes. A round without CLAHE requests launches exactly what it launched before, and its records are what they were.
  *   The LUT scratch of a round (256 bytes per tile) is the session's own and grows to the largest round seen. */
 int pmv_batch_frame_upload_clahe(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* p);
+/* pmv_batch_frame_upload with the remap of pmv_frames_remap inside the same upload round, and the equalisation of pmv_frames_clahe behind
+ * it when clahe_or_null is set: the arguments, sources, errors and return rule of pmv_batch_frame_upload, plus the map and border errors of
+ * pmv_frames_remap (w x h must be the map's size: PMV_ERR_INVALID, the message names the slot and both sizes) and, with clahe_or_null, the
+ * parameter errors of pmv_frames_clahe. The slot then holds the bytes of pmv_frame_upload[_bgr], pmv_frames_remap, and with parameters
+ * pmv_frames_clahe, in this order, and the pyramid is built once. A colour source is converted by the level-0 kernel first: the remap always
+ * sees gray - conversion, then remap, then equalisation. A host source is never gathered over the bus: the gather reads HBM only.
+ *   A round launches in this order: the level-0 launches it always makes; ONE k_remap launch for all remap requests of the round, from the
+ *   slots into a session scratch (a tight frame per request; the scratch grows to the largest round seen); ONE list-form k_pad_level0
+ *   launch from that scratch, counted as a level-0 launch of the round; the CLAHE stage of pmv_batch_frame_upload_clahe for the requests
+ *   that carry parameters, of either call; the k_pyrdown launches, once. A round without remap requests launches and records exactly what
+ *   it did before. */
+int pmv_batch_frame_upload_remap(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, int map_id, int border_value,
+                                 const pmv_clahe_params* clahe_or_null);
 /* The contracts of the pmv_* calls of the same name, argument for argument and status code for status code, served by the class's combiner
  * in batched launches (LK and kNN: the LK combiners; the three detectors: the detector combiner). The slots must hold frames of a declared
  * size (else PMV_ERR_INVALID). */
@@ -675,7 +750,8 @@ int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, con
 int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
                            uint8_t* mask, double* tri4n, int* out_good);
 /* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds (+ 1 for a
- * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation), and the
+ * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation; + 1 for a round with
+ * pmv_batch_frame_upload_remap requests: the launch from the remap scratch), and the
  * pyrDown launches are the sum over the rounds of the levels above 0 of each round's tallest pyramid. */
 int pmv_batch_upload_stats(pmv_ctx* ctx, long long* out4);
 /* diagnostic: one record of 8 ints per upload round since pmv_batch_open (the first 65536 rounds), in order:

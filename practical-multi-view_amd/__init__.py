@@ -65,6 +65,55 @@ def _clahe_params(who, clip_limit, tiles):
     return ClaheParams(float(clip_limit), int(tx), int(ty))
 
 
+def _remap_arg(who, remap):
+    """remap= of the session upload: a map id, or (map_id, border_value)"""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if is_int(remap):
+        return int(remap), 0
+    try:
+        map_id, border = remap
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: remap is a map id or (map_id, border_value), got {remap!r}") from None
+    if not is_int(map_id) or not is_int(border):
+        raise ValueError(f"{who}: remap is a map id or (map_id, border_value) of integers, got {remap!r}")
+    return int(map_id), int(border)
+
+
+def undistort_map(K, dist, size, R=None, new_K=None):
+    """pmv_undistort_map_build: the (map_x, map_y) float32 (h, w) maps of cv::initUndistortRectifyMap(K, dist, R, new_K, size, CV_32FC1), on
+    the host. dist: up to 8 coefficients (k1, k2, p1, p2, k3, k4, k5, k6), the missing ones 0; size = (w, h); R None = identity, new_K None = K."""
+    def mat(m, name):
+        a = np.ascontiguousarray(m, np.float64)
+        if a.shape != (3, 3):
+            raise ValueError(f"undistort_map: {name} is 3 x 3, got shape {a.shape}")
+        return a
+    Km = mat(K, "K")
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if d.size > 8:
+        raise ValueError(f"undistort_map: at most 8 distortion coefficients (k1, k2, p1, p2, k3, k4, k5, k6), got {d.size}")
+    d8 = np.zeros(8, np.float64)
+    d8[:d.size] = d
+    try:
+        w, h = size
+    except (TypeError, ValueError):
+        raise ValueError(f"undistort_map: size is (w, h), got {size!r}") from None
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"undistort_map: size {size!r}")
+    Rm = None if R is None else mat(R, "R")
+    Nm = None if new_K is None else mat(new_K, "new_K")
+    mx, my = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    lib = load_library()
+    _f32p = C.POINTER(C.c_float)
+    lib.pmv_undistort_map_build.argtypes = [_f64p, _f64p, _f64p, _f64p, C.c_int, C.c_int, _f32p, _f32p]
+    rc = lib.pmv_undistort_map_build(_p(Km, _f64p), _p(d8, _f64p), None if Rm is None else _p(Rm, _f64p), None if Nm is None else _p(Nm, _f64p), w, h,
+                                     _p(mx, _f32p), _p(my, _f32p))
+    if rc != 0:
+        raise PmvError(rc, lib.pmv_last_error(None).decode())
+    return mx, my
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 # the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
 LK_USE_INITIAL_FLOW = 4
@@ -77,6 +126,7 @@ ABI_SYMBOLS = [
     "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
+    "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -462,6 +512,35 @@ class Context:
         out = (C.c_longlong * 3)()
         self.lib.pmv_debug_clahe_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         self._ck(self.lib.pmv_debug_clahe_launches(self.h, out))
+        return [int(v) for v in out]
+
+    def remap_map_create(self, map_x, map_y):
+        """pmv_remap_map_create: the (h, w) float32 maps of cv::remap (undistort_map, or the caller's own), converted once into cv's fixed-point
+        form and kept on the device; returns the map's id. At most 16 per context."""
+        mx, my = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+        if mx.ndim != 2 or mx.shape != my.shape:
+            raise ValueError(f"remap_map_create: map_x and map_y are (h, w) float32 arrays of one shape, got {mx.shape} and {my.shape}")
+        out = C.c_int(-1)
+        f32p = C.POINTER(C.c_float)
+        self.lib.pmv_remap_map_create.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int)]
+        self._ck(self.lib.pmv_remap_map_create(self.h, mx.shape[1], mx.shape[0], _p(mx, f32p), _p(my, f32p), C.byref(out)))
+        return int(out.value)
+
+    def remap_map_destroy(self, map_id):
+        self.lib.pmv_remap_map_destroy.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.lib.pmv_remap_map_destroy(self.h, int(map_id)))
+
+    def frames_remap(self, first_slot, n, map_id, border_value=0):
+        """pmv_frames_remap: cv::remap(INTER_LINEAR, BORDER_CONSTANT, border_value) through map `map_id` on level 0 of the staged or built slots
+        first_slot .. first_slot + n - 1, then the border and the levels above rebuilt"""
+        self.lib.pmv_frames_remap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        self._ck(self.lib.pmv_frames_remap(self.h, int(first_slot), int(n), int(map_id), int(border_value)))
+
+    def debug_remap_launches(self):
+        """pmv_debug_remap_launches: [k_remap launches of frames_remap, session upload rounds with a remap request, k_remap launches made for them]"""
+        out = (C.c_longlong * 3)()
+        self.lib.pmv_debug_remap_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_remap_launches(self.h, out))
         return [int(v) for v in out]
 
     def num_levels(self, slot):
@@ -1013,6 +1092,23 @@ class Context:
         else:
             self.lib.pmv_batch_frame_upload_clahe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ClaheParams)]
             self._ckt(self.lib.pmv_batch_frame_upload_clahe(self.h, int(slot), C.c_void_p(addr), w, h, stride, f, C.byref(p)))
+        del keep
+
+    def batch_frame_upload_remap(self, slot, frame, remap, fmt="gray", clahe=None):
+        """batch_frame_upload with the remap of frames_remap inside the same upload round (pmv_batch_frame_upload_remap). remap: a map id or
+        (map_id, border_value). clahe: None, or (clip_limit, (tiles_x, tiles_y)) - equalised behind the remap, in the same round. A colour frame
+        is converted first: conversion, remap, equalisation."""
+        map_id, border = _remap_arg("batch_frame_upload_remap", remap)
+        p = None
+        if clahe is not None:
+            try:
+                clip_limit, tiles = clahe
+            except (TypeError, ValueError):
+                raise ValueError(f"batch_frame_upload_remap: clahe is None or (clip_limit, (tiles_x, tiles_y)), got {clahe!r}") from None
+            p = _clahe_params("batch_frame_upload_remap", clip_limit, tiles)
+        addr, w, h, stride, f, keep = _upload_source(frame, fmt)
+        self.lib.pmv_batch_frame_upload_remap.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ClaheParams)]
+        self._ckt(self.lib.pmv_batch_frame_upload_remap(self.h, int(slot), C.c_void_p(addr), w, h, stride, f, map_id, border, None if p is None else C.byref(p)))
         del keep
 
     def batch_upload_stats(self):

@@ -14,6 +14,10 @@
 //     A request of pmv_batch_frame_upload_clahe rides in the same round: behind the level-0 launches the round makes ONE k_clahe_lut and ONE
 //     k_clahe_apply launch for all such requests (frontend_clahe.hip: a record per frame names its size and parameters) and ONE in-place
 //     k_pad_level0_list launch over their slots, in front of the k_pyrdown launches. A round without such a request launches what it always did.
+//     A request of pmv_batch_frame_upload_remap rides there too: behind the level-0 launches (which leave the gray image in the slot, colour
+//     sources converted) the round makes ONE k_remap launch for all such requests, from the slots into the session's remap scratch
+//     (frontend_remap.hip: a record per frame names its size, map and border value), and ONE k_pad_level0_list launch from that scratch back
+//     into the slots; then the CLAHE stage, which also serves the remap requests that carry parameters, then the k_pyrdown launches.
 //   * Sources. Pinned memory mapped at its host address and device memory of the context's device are read in place by the kernel, with the
 //     caller's row stride as the entry's pitch. Anything else is copied by the CALLING thread, row by row and tight, into a block of the
 //     session's pinned staging pool; the kernel reads it from there. The callers' threads launch nothing and wait for no stream: their one
@@ -46,6 +50,8 @@ struct UpReq {
     bool in_place = false;           // dsrc is the caller's own buffer
     bool clahe = false;              // pmv_batch_frame_upload_clahe: level 0 is equalised with `cp` inside the round
     pmv_clahe_params cp = {0.0, 0, 0};
+    const uint8_t* remap = nullptr;  // pmv_batch_frame_upload_remap: the packed map (device memory) level 0 is gathered through inside the round
+    int border = 0;
     int rc = PMV_OK;
     char err[200] = "";
     std::atomic<int> done{0};        // completion word of the request: the owner sleeps on it (futex), as in batch_engine.hip
@@ -76,10 +82,13 @@ struct BatchSession {
     std::vector<UpReq*> pending;
     bool stop = false;
     // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND |
-    // CLAHE PyrListEntry x ROUND | ClaheRec x ROUND] (the last two are written only by a round with CLAHE requests)
+    // CLAHE PyrListEntry x ROUND | ClaheRec x ROUND | remap PyrListEntry x ROUND | RemapRec x ROUND] (the last four are written only by a
+    // round with such requests)
     char* h_tab = nullptr; char* dm_tab = nullptr;
     // LUT blocks of a round's CLAHE requests (HBM): made by the first such round, grown to the largest round seen
     uint8_t* d_lut = nullptr; size_t lut_cap = 0;
+    // tight destination frames of a round's remap requests (HBM): made by the first such round, grown to the largest round seen
+    uint8_t* d_rscratch = nullptr; size_t rscratch_cap = 0;
     // staging pool: n_blk blocks of blk_bytes (the largest BGR frame of the declared sizes), pinned + mapped
     uint8_t* h_pool = nullptr; uint8_t* dm_pool = nullptr;
     size_t blk_bytes = 0;
@@ -139,14 +148,18 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     ClaheRec* tr = (ClaheRec*)(te + BatchSession::ROUND);
     const PyrListEntry* de = da + BatchSession::ROUND;
     const ClaheRec* dr = (const ClaheRec*)(de + BatchSession::ROUND);
+    PyrListEntry* tm = (PyrListEntry*)(tr + BatchSession::ROUND);   // the slots of the round's remap requests (sources: their scratch frames)
+    RemapRec* tq = (RemapRec*)(tm + BatchSession::ROUND);
+    const PyrListEntry* dm = (const PyrListEntry*)(dr + BatchSession::ROUND);
+    const RemapRec* dq = (const RemapRec*)(dm + BatchSession::ROUND);
     // grid and LDS of a launch from the largest geometry among ITS entries, level by level
-    PyrLayout Lg{}, Lc{}, La{}, Le{};
+    PyrLayout Lg{}, Lc{}, La{}, Le{}, Lm{};
     auto widen = [](PyrLayout& M, const PyrLayout& L) {
         M.n_levels = std::max(M.n_levels, L.n_levels);
         for (int l = 0; l < L.n_levels; l++) { M.w[l] = std::max(M.w[l], L.w[l]); M.h[l] = std::max(M.h[l], L.h[l]); }
     };
-    int ng = 0, nc = 0, na = 0, ne = 0, max_tiles = 0;
-    size_t lut_bytes = 0;
+    int ng = 0, nc = 0, na = 0, ne = 0, max_tiles = 0, nm = 0;
+    size_t lut_bytes = 0, rscratch_bytes = 0;
     for (UpReq* r : batch) {
         const PyrLayout& L = ctx->geom[(size_t)r->geom];
         PyrPitchEntry& e = r->format == PMV_FRAMES_BGR ? tc[nc++] : tg[ng++];
@@ -164,6 +177,14 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
             widen(Le, L);
             ne++;
         }
+        if (r->remap) {
+            tq[nm].map = (const uint32_t*)r->remap; tq[nm].dst_off = (unsigned long long)rscratch_bytes;
+            tq[nm].slot = r->slot; tq[nm].geom = r->geom; tq[nm].border = r->border; tq[nm].reserved = 0;
+            tm[nm].src = nullptr; tm[nm].slot = r->slot; tm[nm].geom = r->geom;   // (src: below, once the scratch is there)
+            rscratch_bytes += remap_frame_bytes(L.w[0], L.h[0]);
+            widen(Lm, L);
+            nm++;
+        }
     }
     // A round that fails after its first launch must not hand the sources back while a kernel still reads them: wait for the stream first.
     auto fail = [&](const char* what, hipError_t err) { (void)hipStreamSynchronize(S->stream); fail_round(batch, what, err); };
@@ -175,6 +196,21 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     }
     if (nc) {
         if ((e = launch_pad_level0_bgr_pitched(S->stream, ctx->d_slots, ctx->d_geom, Lc, dc, nc)) != hipSuccess) { fail("k_pad_level0_bgr_pitched", e); return; }
+        rec.l0_launches++;
+    }
+    if (nm) {
+        // level 0 of the round's remap requests is gathered from where the launches above left it into the scratch, then written back with its
+        // REFLECT_101 frame by the list form, whose sources are the scratch frames
+        if (rscratch_bytes > S->rscratch_cap) {   // (the stream is idle between rounds: the previous round was waited for)
+            if (S->d_rscratch) (void)hipFree(S->d_rscratch);
+            S->d_rscratch = nullptr; S->rscratch_cap = 0;
+            if ((e = hipMalloc(&S->d_rscratch, rscratch_bytes)) != hipSuccess) { fail("the remap scratch", e); return; }
+            S->rscratch_cap = rscratch_bytes;
+        }
+        for (int i = 0; i < nm; i++) tm[i].src = S->d_rscratch + tq[i].dst_off;
+        if ((e = launch_remap(S->stream, ctx->d_slots, ctx->d_geom, dq, nm, Lm.w[0], Lm.h[0], S->d_rscratch)) != hipSuccess) { fail("k_remap", e); return; }
+        ctx->remap_launches[2]++;
+        if ((e = launch_pad_level0_list(S->stream, ctx->d_slots, ctx->d_geom, Lm, dm, nm)) != hipSuccess) { fail("k_pad_level0_list", e); return; }
         rec.l0_launches++;
     }
     if (ne) {
@@ -202,6 +238,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
         rec.in_place += r->in_place ? 1 : 0;
     }
     if (ne) ctx->clahe_launches[1]++;
+    if (nm) ctx->remap_launches[1]++;
     S->rounds++; S->frames += na; S->l0_launches += rec.l0_launches; S->pyr_launches += rec.pyr_launches;
     std::lock_guard<std::mutex> lk(S->log_mu);
     if (S->log.size() < BatchSession::ROUND_LOG) S->log.push_back(rec);
@@ -247,6 +284,7 @@ void session_free(BatchSession* S) {
     if (S->h_tab) (void)hipHostFree(S->h_tab);
     if (S->h_pool) (void)hipHostFree(S->h_pool);
     if (S->d_lut) (void)hipFree(S->d_lut);
+    if (S->d_rscratch) (void)hipFree(S->d_rscratch);
     delete S;
 }
 
@@ -319,7 +357,7 @@ int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes) {
     S->ctx = ctx; S->eng = eng; S->n_seq = n_seq;
     S->seq_mu.reset(new std::mutex[(size_t)n_seq]);
     hipError_t e = hipSuccess;
-    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + 2 * sizeof(PyrListEntry) + sizeof(ClaheRec));
+    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + 3 * sizeof(PyrListEntry) + sizeof(ClaheRec) + sizeof(RemapRec));
     S->blk_bytes = (max_fb + 255) & ~(size_t)255;
     // two blocks per sequence (frames k - 1 and k on their way), within 4 .. 64 blocks and 256 MB; an uploader without a block waits for one
     const int n_blk = (int)std::max<size_t>(2, std::min<size_t>({(size_t)64, std::max<size_t>(4, 2 * (size_t)n_seq), ((size_t)256 << 20) / S->blk_bytes}));
@@ -372,8 +410,10 @@ int pmv_batch_upload_rounds(pmv_ctx* ctx, int* out8, int capacity) {
     return (int)S->log.size();
 }
 
-// pmv_batch_frame_upload and, with cp, pmv_batch_frame_upload_clahe (cp: checked by the caller): one request of the upload class
-static int session_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* cp) {
+// pmv_batch_frame_upload and, with cp, pmv_batch_frame_upload_clahe, with map, pmv_batch_frame_upload_remap (cp, map, border: checked by the
+// caller): one request of the upload class
+static int session_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, const pmv_clahe_params* cp,
+                          const pmv_ctx::RemapMap* map = nullptr, int map_id = 0, int border = 0) {
     SESSION("pmv_batch_frame_upload");
     REQ(pixels, PMV_ERR_INVALID, "pmv_batch_frame_upload: null argument");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_batch_frame_upload: slot %d out of range", slot);
@@ -381,6 +421,10 @@ static int session_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, 
     UpReq r;
     r.slot = slot; r.format = format;
     if (cp) { r.clahe = true; r.cp = *cp; }
+    if (map) {
+        REQ(w == map->w && h == map->h, PMV_ERR_INVALID, "pmv_batch_frame_upload_remap: slot %d: a %dx%d frame, map %d is %dx%d", slot, w, h, map_id, map->w, map->h);
+        r.remap = map->d; r.border = border;
+    }
     r.geom = ctx->geom_index(w, h);
     REQ(r.geom >= 0, PMV_ERR_INVALID, "pmv_batch_frame_upload: a %dx%d frame: that size was not declared at pmv_batch_open", w, h);
     const size_t row = (size_t)w * (format == PMV_FRAMES_BGR ? 3 : 1);
@@ -442,6 +486,16 @@ int pmv_batch_frame_upload_clahe(pmv_ctx* ctx, int slot, const uint8_t* pixels, 
     if (!ctx) { set_err(nullptr, "pmv_batch_frame_upload_clahe: null ctx"); return PMV_ERR_INVALID; }
     if (const int rc = clahe_check(ctx, "pmv_batch_frame_upload_clahe", p)) return rc;
     return session_upload(ctx, slot, pixels, w, h, stride, format, p);
+}
+
+int pmv_batch_frame_upload_remap(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, int h, int stride, int format, int map_id, int border_value,
+                                 const pmv_clahe_params* clahe_or_null) {
+    if (!ctx) { set_err(nullptr, "pmv_batch_frame_upload_remap: null ctx"); return PMV_ERR_INVALID; }
+    pmv_ctx::RemapMap map;
+    if (const int rc = remap_check(ctx, "pmv_batch_frame_upload_remap", map_id, border_value, &map)) return rc;
+    if (clahe_or_null)
+        if (const int rc = clahe_check(ctx, "pmv_batch_frame_upload_remap", clahe_or_null)) return rc;
+    return session_upload(ctx, slot, pixels, w, h, stride, format, clahe_or_null, &map, map_id, border_value);
 }
 
 // ---- front-end calls: the checks of the single call, then a request of the class's combiner ------------------------------------------

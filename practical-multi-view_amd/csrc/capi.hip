@@ -122,6 +122,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->batch_launches) a.store(0);
     for (auto& a : c->subpix_launches) a.store(0);
     for (auto& a : c->clahe_launches) a.store(0);
+    for (auto& a : c->remap_launches) a.store(0);
     CK(hipMalloc(&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
     CK(hipMalloc(&c->d_cells, MAX_CELLS * CELL_STRIDE * 4));
@@ -174,6 +175,10 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->h_clahe) hipHostFree(c->h_clahe);
     if (c->d_clahe) hipFree(c->d_clahe);
     if (c->d_clahe_lut) hipFree(c->d_clahe_lut);
+    for (auto& m : c->remap_maps) if (m.d) hipFree(m.d);
+    if (c->h_remap) hipHostFree(c->h_remap);
+    if (c->d_remap) hipFree(c->d_remap);
+    if (c->d_remap_scratch) hipFree(c->d_remap_scratch);
     if (c->d_knn) hipFree(c->d_knn);
     if (c->h_knn) hipHostFree(c->h_knn);
     hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
@@ -431,6 +436,117 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
 int pmv_debug_clahe_launches(pmv_ctx* ctx, long long* out3) {
     REQ(ctx && out3, PMV_ERR_INVALID, "pmv_debug_clahe_launches: null argument");
     for (int i = 0; i < 3; i++) out3[i] = ctx->clahe_launches[i].load();
+    return PMV_OK;
+}
+
+}  // extern "C"
+
+int pmv::remap_check(pmv_ctx* ctx, const char* who, int map_id, int border_value, pmv_ctx::RemapMap* map) {
+    REQ(border_value >= 0 && border_value <= 255, PMV_ERR_INVALID, "%s: border_value = %d is outside 0..255", who, border_value);
+    std::lock_guard<std::mutex> lk(ctx->remap_mu);
+    REQ(map_id >= 0 && map_id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[map_id].d, PMV_ERR_INVALID, "%s: map %d does not exist (pmv_remap_map_create)", who, map_id);
+    *map = ctx->remap_maps[map_id];
+    return PMV_OK;
+}
+
+extern "C" {
+
+// cv's fixed-point form of a pair of CV_32FC1 maps, converted ONCE on the host and kept in HBM (remap_pack, pmv_device.h: 6 bytes per pixel)
+int pmv_remap_map_create(pmv_ctx* ctx, int w, int h, const float* map_x, const float* map_y, int* out_id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_remap_map_create: null argument");
+    REQ(map_x && map_y && out_id, PMV_ERR_INVALID, "pmv_remap_map_create: null argument");
+    REQ(w >= 1 && h >= 1 && w <= ctx->max_w && h <= ctx->max_h, PMV_ERR_INVALID, "pmv_remap_map_create: a %dx%d map is outside the context's %dx%d", w, h, ctx->max_w, ctx->max_h);
+    std::lock_guard<std::mutex> lk(ctx->remap_mu);
+    int id = 0;
+    while (id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[id].d) id++;
+    REQ(id < pmv_ctx::MAX_REMAP_MAPS, PMV_ERR_CAPACITY, "pmv_remap_map_create: the context holds %d maps already (pmv_remap_map_destroy one)", pmv_ctx::MAX_REMAP_MAPS);
+    CKC(hipSetDevice(ctx->device));
+    const size_t bytes = remap_map_bytes(w, h);
+    std::vector<uint32_t> packed(bytes / 4);
+    remap_pack(map_x, map_y, w, h, (uint8_t*)packed.data());
+    uint8_t* d = nullptr;
+    CKC(hipMalloc(&d, bytes));
+    const hipError_t e = hipMemcpy(d, packed.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); set_err(ctx, "pmv_remap_map_create: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
+    ctx->remap_maps[id].w = w; ctx->remap_maps[id].h = h; ctx->remap_maps[id].d = d;
+    *out_id = id;
+    return PMV_OK;
+}
+
+int pmv_remap_map_destroy(pmv_ctx* ctx, int id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_remap_map_destroy: null argument");
+    // a session's upload rounds read the maps of their requests: none may go while one is open
+    std::lock_guard<std::mutex> own(ctx->owner_mu);
+    REQ(ctx->session_state.load() == 0, PMV_ERR_INVALID, "pmv_remap_map_destroy: a batch session is open on this context (pmv_batch_close first)");
+    std::lock_guard<std::mutex> lk(ctx->remap_mu);
+    REQ(id >= 0 && id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[id].d, PMV_ERR_INVALID, "pmv_remap_map_destroy: map %d does not exist", id);
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    CKC(hipFree(ctx->remap_maps[id].d));
+    ctx->remap_maps[id] = pmv_ctx::RemapMap();
+    return PMV_OK;
+}
+
+// cv::remap on level 0 of the slots: k_remap from the slots' interiors into the chunk's scratch frames, the list-form level-0 launch from
+// there, the k_pyrdown launches. A chunk of REMAP_CHUNK frames is ONE k_remap launch whatever its sizes (one map size per call, though:
+// every slot must have it).
+int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border_value) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_frames_remap: null argument");
+    pmv_ctx::RemapMap map;
+    if (const int rc_ = remap_check(ctx, "pmv_frames_remap", map_id, border_value, &map)) return rc_;
+    REQ(first_slot >= 0 && n >= 1 && first_slot <= ctx->n_slots - n, PMV_ERR_CAPACITY, "pmv_frames_remap: slots [%d,%d) out of range (n_slots %d)", first_slot, first_slot + n, ctx->n_slots);
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_frames_remap: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
+    REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_frames_remap: a batched run is open on this context");
+    for (int i = 0; i < n; i++) REQ(ctx->slot_state[first_slot + i] != SLOT_EMPTY, PMV_ERR_INVALID, "pmv_frames_remap: slot %d is empty (never staged or uploaded)", first_slot + i);
+    for (int i = 0; i < n; i++) {
+        const PyrLayout& L = ctx->slot_layout[first_slot + i];
+        REQ(L.w[0] == map.w && L.h[0] == map.h, PMV_ERR_INVALID, "pmv_frames_remap: slot %d holds a %dx%d frame, map %d is %dx%d", first_slot + i, L.w[0], L.h[0], map_id, map.w, map.h);
+    }
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    constexpr int CH = pmv_ctx::REMAP_CHUNK;
+    constexpr size_t tab_bytes = (size_t)CH * (sizeof(RemapRec) + sizeof(PyrListEntry) + sizeof(PyrLayout));
+    if (!ctx->h_remap) CKC(hipHostMalloc(&ctx->h_remap, tab_bytes, hipHostMallocDefault));
+    if (!ctx->d_remap) CKC(hipMalloc(&ctx->d_remap, tab_bytes));
+    if (!ctx->d_remap_scratch) CKC(hipMalloc(&ctx->d_remap_scratch, (size_t)CH * remap_frame_bytes(ctx->max_w, ctx->max_h)));
+    RemapRec* recs = (RemapRec*)ctx->h_remap;
+    PyrListEntry* list = (PyrListEntry*)(recs + CH);
+    PyrLayout* tab = (PyrLayout*)(list + CH);
+    const RemapRec* d_recs = (const RemapRec*)ctx->d_remap;
+    const PyrListEntry* d_list = (const PyrListEntry*)(d_recs + CH);
+    const PyrLayout* d_tab = (const PyrLayout*)(d_list + CH);
+    const PyrLayout L = ctx->slot_layout[first_slot];   // (one size per call: the map's)
+    const size_t fb = remap_frame_bytes(L.w[0], L.h[0]);
+    tab[0] = L;
+    for (int i0 = 0; i0 < n; i0 += CH) {
+        const int nb = std::min(CH, n - i0);
+        for (int i = 0; i < nb; i++) {
+            recs[i].map = (const uint32_t*)map.d; recs[i].dst_off = (unsigned long long)((size_t)i * fb);
+            recs[i].slot = first_slot + i0 + i; recs[i].geom = 0; recs[i].border = border_value; recs[i].reserved = 0;
+            list[i].src = ctx->d_remap_scratch + (size_t)i * fb; list[i].slot = first_slot + i0 + i; list[i].geom = 0;
+        }
+        CKC(hipMemcpyAsync(ctx->d_remap, ctx->h_remap, tab_bytes, hipMemcpyHostToDevice, ctx->s_front));
+        CKC(launch_remap(ctx->s_front, ctx->d_slots, d_tab, d_recs, nb, L.w[0], L.h[0], ctx->d_remap_scratch));
+        ctx->remap_launches[0]++;
+        CKC(launch_pad_level0_list(ctx->s_front, ctx->d_slots, d_tab, L, d_list, nb));
+        for (int l = 1; l < L.n_levels; l++) CKC(launch_pyrdown_list(ctx->s_front, ctx->d_slots, d_tab, L, l, d_list, nb));
+        CKC(hipStreamSynchronize(ctx->s_front));   // (the next chunk rewrites the pinned tables and the scratch frames)
+    }
+    for (int k = 0; k < n; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
+    return PMV_OK;
+}
+int pmv_debug_remap_launches(pmv_ctx* ctx, long long* out3) {
+    REQ(ctx && out3, PMV_ERR_INVALID, "pmv_debug_remap_launches: null argument");
+    for (int i = 0; i < 3; i++) out3[i] = ctx->remap_launches[i].load();
+    return PMV_OK;
+}
+
+// cv::initUndistortRectifyMap(.., CV_32FC1) on the host; no context (the message goes where pmv_last_error(NULL) finds it)
+int pmv_undistort_map_build(const double* K9, const double* dist8, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x, float* map_y) {
+    pmv_ctx* ctx = nullptr;
+    REQ(K9 && dist8 && map_x && map_y, PMV_ERR_INVALID, "pmv_undistort_map_build: null argument");
+    REQ(w >= 1 && h >= 1, PMV_ERR_INVALID, "pmv_undistort_map_build: size %dx%d", w, h);
+    REQ(undistort_map(K9, dist8, R9_or_null, newK9_or_null, w, h, map_x, map_y), PMV_ERR_INVALID, "pmv_undistort_map_build: newK R is singular");
     return PMV_OK;
 }
 

@@ -95,6 +95,19 @@ struct pmv_ctx {
     uint8_t* h_clahe = nullptr; uint8_t* d_clahe = nullptr; uint8_t* d_clahe_lut = nullptr;
     // pmv_debug_clahe_launches: LUT + apply launch pairs of pmv_frames_clahe | session upload rounds with a CLAHE request | launch pairs made for them
     std::atomic<long long> clahe_launches[3];
+    // pmv_remap_map_create: at most MAX_REMAP_MAPS packed maps (remap_pack's layout, pmv_device.h) in HBM, one per camera; id = index. remap_mu
+    // guards the table: a session's callers look a map up while another thread may create one (destroy is refused while a session is open).
+    static constexpr int MAX_REMAP_MAPS = 16;
+    struct RemapMap { int w = 0, h = 0; uint8_t* d = nullptr; };
+    RemapMap remap_maps[MAX_REMAP_MAPS];
+    std::mutex remap_mu;
+    // pmv_frames_remap, made by the first call: a chunk's tables [RemapRec x REMAP_CHUNK | PyrListEntry x REMAP_CHUNK | PyrLayout x REMAP_CHUNK]
+    // in pinned host memory and in HBM (the call's own geometry table, as for pmv_frames_clahe), and the chunk's tight destination frames in
+    // HBM: REMAP_CHUNK blocks of remap_frame_bytes(max_w, max_h), not sized by the call's n
+    static constexpr int REMAP_CHUNK = 64;
+    uint8_t* h_remap = nullptr; uint8_t* d_remap = nullptr; uint8_t* d_remap_scratch = nullptr;
+    // pmv_debug_remap_launches: k_remap launches of pmv_frames_remap | session upload rounds with a remap request | k_remap launches made for them
+    std::atomic<long long> remap_launches[3];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -170,6 +183,8 @@ inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
 }
 // pmv_frames_clahe / pmv_batch_frame_upload_clahe: the parameter checks of the contract (`who` names the call in the messages)
 int clahe_check(pmv_ctx* ctx, const char* who, const pmv_clahe_params* p);
+// pmv_frames_remap / pmv_batch_frame_upload_remap: the map id and the border value of the contract; on success *map is a copy of the map's entry
+int remap_check(pmv_ctx* ctx, const char* who, int map_id, int border_value, pmv_ctx::RemapMap* map);
 // after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current

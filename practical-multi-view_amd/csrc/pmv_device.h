@@ -319,4 +319,33 @@ ClaheRec clahe_record(int slot, int geom, int w, int h, double clip_limit, int t
 // record's block. Both launches are booked under the level-0 profiling class.
 hipError_t launch_clahe(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const ClaheRec* d_recs, int n, int max_tiles, int max_w, int max_h, uint8_t* d_lut);
 
+// ---- cv::remap of level 0 (frontend_remap.hip) ----------------------------------------------------------------------
+// pmv_frames_remap / pmv_batch_frame_upload_remap: bilinear, constant border, cv's fixed-point arithmetic. One record per frame names its
+// slot, its entry of a geometry table, its packed map (device memory, remap_pack's layout), the border value and the byte offset of its
+// tight w x h destination frame in the launch's scratch area (a multiple of 256), so ONE launch serves any number of frames of any sizes
+// and maps. The kernel reads the interior of level 0 and writes the scratch frame; the list-form level-0 launch with that frame as its
+// source and the k_pyrdown launches finish the slot.
+struct __attribute__((aligned(16))) RemapRec {
+    const uint32_t* map;          // the packed map of the frame's size
+    unsigned long long dst_off;   // byte offset of the frame in the scratch area
+    int slot, geom;               // frame slot, entry of the launch's geometry table
+    int border;                   // cv's borderValue, 0..255
+    int reserved;
+};
+static_assert(sizeof(RemapRec) == 32, "RemapRec: one 32-byte record per frame");
+// bytes of a frame in a remap scratch area: the tight frame rounded up, so that every frame starts 256-byte aligned and the dword fetches of
+// the level-0 kernel behind it (the aligned dwords that hold a row's bytes) stay inside the frame's own block
+inline size_t remap_frame_bytes(int w, int h) { return ((size_t)w * (size_t)h + 255) & ~(size_t)255; }
+// the packed form of a w x h pair of CV_32FC1 maps: two planes over the linear pixel index, each padded to a multiple of four entries -
+// (ix & 0xffff) | iy << 16 as dwords, then fx | fy << 5 as halfwords; 6 bytes per pixel. remap_pack converts on the host (cv's conversion,
+// include/pmv_hip.h) into `out` (remap_map_bytes(w, h) bytes, 4-byte aligned).
+size_t remap_map_bytes(int w, int h);
+void remap_pack(const float* map_x, const float* map_y, int w, int h, uint8_t* out);
+// cv::initUndistortRectifyMap(K, dist8, R or identity, newK or K, (w, h), CV_32FC1), evaluated per pixel in double; false: newK R is singular
+bool undistort_map(const double* K, const double* dist8, const double* R, const double* newK, int w, int h, float* map_x, float* map_y);
+// k_remap over n records in device-visible memory; d_geom[record.geom] (device memory) is the record's frame. max_w, max_h: the largest
+// level-0 width and height among the records - they size the grid; a thread beyond its own frame leaves before its first load. Booked under
+// the level-0 profiling class.
+hipError_t launch_remap(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const RemapRec* d_recs, int n, int max_w, int max_h, uint8_t* d_scratch);
+
 }  // namespace pmv
