@@ -211,6 +211,10 @@ int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border
 /* diagnostic: {k_remap launches of pmv_frames_remap, session upload rounds that held at least one pmv_batch_frame_upload_remap request,
  * k_remap launches made for them} since the context was created. */
 int pmv_debug_remap_launches(pmv_ctx* ctx, long long* out3);
+/* diagnostic: bytes the library currently holds, over every context of the process: out2 = {device memory, pinned host memory}. Needs no
+ * context. Every allocation has one owner that frees it, and these two counters are written where a block is made and where it is freed,
+ * so the pair returns to its earlier value once everything made in between has been closed - whatever other processes do to the card. */
+int pmv_debug_mem_live(long long* out2);
 /* The map of cv::initUndistortRectifyMap(K, dist, R, newK, Size(w, h), CV_32FC1), on the host; needs no context (pmv_last_error(NULL) has
  * the message of a refusal). K9, R9, newK9: row-major 3 x 3; dist8 = (k1, k2, p1, p2, k3, k4, k5, k6); a null R is the identity, a null newK
  * is K. map_x, map_y: w h floats each, for pmv_remap_map_create.

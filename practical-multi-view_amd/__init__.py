@@ -114,6 +114,17 @@ def undistort_map(K, dist, size, R=None, new_K=None):
     return mx, my
 
 
+def mem_live():
+    """pmv_debug_mem_live: (device bytes, pinned host bytes) the library holds right now, over every context of the process"""
+    lib = load_library()
+    out = (C.c_longlong * 2)()
+    lib.pmv_debug_mem_live.argtypes = [C.POINTER(C.c_longlong)]
+    rc = lib.pmv_debug_mem_live(out)
+    if rc != 0:
+        raise PmvError(rc, lib.pmv_last_error(None).decode())
+    return int(out[0]), int(out[1])
+
+
 # every symbol include/pmv_hip.h declares (tests check the library exports all of them)
 # the `flags` of pmv_lk_track_ex / pmv_lk_track_fb (cv's values)
 LK_USE_INITIAL_FLOW = 4
@@ -127,6 +138,7 @@ ABI_SYMBOLS = [
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
     "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
+    "pmv_debug_mem_live",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",

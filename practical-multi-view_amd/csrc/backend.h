@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/pmv_hip.h"
+#include "pmv_mem.h"
 
 namespace pmv {
 
@@ -11,38 +12,31 @@ namespace pmv {
 // context owns one (the plain C-ABI calls); the batch engine owns one per concurrent sequence.
 constexpr int MAX_HYP = 1024;
 
-struct BackendBuffers {
+struct BackendBuffers {   // every buffer: one row of backend_alloc's table; freed with the set (backend_free)
     unsigned done_seq = 0;   // sequence number of the last call that signals its completion through the result block
     // BA problem
-    double *d_cams = nullptr, *d_pts = nullptr, *d_obs = nullptr, *d_K = nullptr;
-    int *d_cam_idx = nullptr, *d_pt_idx = nullptr, *d_pobs_start = nullptr, *d_pobs_list = nullptr, *d_cobs_start = nullptr, *d_cobs_list = nullptr;
+    Buf<double> d_cams, d_pts, d_obs, d_K;
+    Buf<int> d_cam_idx, d_pt_idx, d_pobs_start, d_pobs_list, d_cobs_start, d_cobs_list;
     // BA workspaces
-    double *d_x = nullptr, *d_cand = nullptr, *d_scale = nullptr, *d_diag = nullptr, *d_D2 = nullptr, *d_step = nullptr, *d_res = nullptr,
-           *d_J = nullptr, *d_Einv = nullptr, *d_gp = nullptr, *d_Yd = nullptr, *d_Wd = nullptr, *d_S = nullptr, *d_rhs = nullptr,
-           *d_Gpart = nullptr, *d_summary = nullptr;
+    Buf<double> d_x, d_cand, d_scale, d_diag, d_D2, d_step, d_res, d_J, d_Einv, d_gp, d_Yd, d_Wd, d_S, d_rhs, d_Gpart, d_summary;
     size_t ydwd_elems = 0, gpart_elems = 0;
-    unsigned long long* d_stamps = nullptr;
-    void* d_bastate = nullptr;
-    double* d_bapart = nullptr;
-    char *d_tri_in = nullptr, *d_tri_out = nullptr;
-    char* d_fp_work = nullptr;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in)
-    char* d_ess_in = nullptr;    // whole findEssentialMat RANSAC: [EssentialProblem 64 B | q1 2n | q2 2n | iteration table n + 2 doubles]
-    size_t ess_in_bytes = 0;
-    char* d_h_stage = nullptr;   // device address of the pinned staging block: result blocks are written straight into it
-    size_t tri_in_bytes = 0, tri_out_bytes = 0;
-    // single-copy transfers: one pinned staging block and one device block per direction
-    void* h_stage = nullptr;
-    size_t h_stage_bytes = 0;
-    char* d_ba_io = nullptr;   // [summary 8 | cams | pts | obs | K | cam_idx | pt_idx | pobs_start | pobs_list | cobs_start | cobs_list]
-    size_t ba_io_bytes = 0;
-    char* d_pnp_in = nullptr;  // [K 10 doubles | obj | img | samples]
-    char* d_pnp_out = nullptr; // [rt 6 doubles | info 4 ints | inliers]
-    size_t pnp_in_bytes = 0, pnp_out_bytes = 0;
+    Buf<unsigned long long> d_stamps;
+    Buf<void> d_bastate;
+    Buf<double> d_bapart;
+    Buf<char> d_tri_in, d_tri_out;
+    Buf<char> d_fp_work;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in)
+    Buf<char> d_ess_in;    // whole findEssentialMat RANSAC: [EssentialProblem 64 B | q1 2n | q2 2n | iteration table n + 2 doubles]
+    // single-copy transfers: one mapped pinned staging block (result blocks are written straight into it through .dm()) and one device
+    // block per direction
+    Buf<char> h_stage;
+    Buf<char> d_ba_io;     // [summary 8 | cams | pts | obs | K | cam_idx | pt_idx | pobs_start | pobs_list | cobs_start | cobs_list]
+    Buf<char> d_pnp_in;    // [K 10 doubles | obj | img | samples]
+    Buf<char> d_pnp_out;   // [rt 6 doubles | info 4 ints | inliers]
     // PnP
-    float *d_obj = nullptr, *d_img = nullptr;
-    int *d_samples = nullptr, *d_counts = nullptr, *d_inliers = nullptr, *d_info = nullptr;
-    double *d_models = nullptr, *d_rt = nullptr, *d_Kp = nullptr;
-    uint8_t* d_masks = nullptr;
+    Buf<float> d_obj, d_img;
+    Buf<int> d_samples, d_counts, d_inliers, d_info;
+    Buf<double> d_models, d_rt, d_Kp;
+    Buf<uint8_t> d_masks;
 };
 
 constexpr size_t PNP_HDR = 384;   // bytes: K (10 doubles) + 33 powers of ten + padding

@@ -26,83 +26,60 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
     const size_t nc = (size_t)std::max(c->max_ba_cams, 1), np = (size_t)std::max(c->max_ba_points, 1), no = (size_t)std::max(c->max_ba_obs, 1);
     const size_t n = 6 * nc + 3 * np, m = 6 * nc;
     const size_t ldw = (size_t)round_up((int)m + 1, 16), krows = (size_t)round_up((int)(3 * np), 16);
-#define CKB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(c, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
-    CKB(hipMalloc(&b->d_cams, nc * 6 * 8)); CKB(hipMalloc(&b->d_pts, np * 3 * 8)); CKB(hipMalloc(&b->d_obs, no * 2 * 8)); CKB(hipMalloc(&b->d_K, 9 * 8));
-    CKB(hipMalloc(&b->d_cam_idx, no * 4)); CKB(hipMalloc(&b->d_pt_idx, no * 4));
-    CKB(hipMalloc(&b->d_pobs_start, (np + 1) * 4)); CKB(hipMalloc(&b->d_pobs_list, no * 4));
-    CKB(hipMalloc(&b->d_cobs_start, (nc + 1) * 4)); CKB(hipMalloc(&b->d_cobs_list, no * 4));
-    CKB(hipMalloc(&b->d_x, 2 * n * 8)); CKB(hipMalloc(&b->d_cand, n * 8)); CKB(hipMalloc(&b->d_scale, n * 8)); CKB(hipMalloc(&b->d_diag, n * 8));
-    CKB(hipMalloc(&b->d_D2, n * 8)); CKB(hipMalloc(&b->d_step, n * 8));
-    CKB(hipMalloc(&b->d_res, 2 * no * 2 * 8)); CKB(hipMalloc(&b->d_J, 2 * no * 18 * 8));   // two buffers: current point / candidate
-    CKB(hipMalloc(&b->d_Einv, np * 9 * 8)); CKB(hipMalloc(&b->d_gp, np * 3 * 8));
     b->ydwd_elems = krows * ldw;
-    CKB(hipMalloc(&b->d_Yd, 2 * b->ydwd_elems * 8));   // Yt | [Wt | g] adjacent: one clear per solve (multi-kernel LM)
-    CKB(hipMalloc(&b->d_Wd, b->ydwd_elems * 8));       // [Wt | g] of the single-workgroup LM
-    CKB(hipMalloc(&b->d_S, m * m * 8)); CKB(hipMalloc(&b->d_rhs, m * 8));
     b->gpart_elems = (size_t)8 * ldw * ldw;   // up to 8 K-slices of an (ldw x ldw) tile grid
-    CKB(hipMalloc(&b->d_Gpart, b->gpart_elems * 8));
-    CKB(hipMalloc(&b->d_summary, 8 * 8));
-    CKB(hipMalloc(&b->d_stamps, 32 * 8));
-    CKB(hipMalloc(&b->d_bastate, 512 + 4 * BA_MAX_ITERATIONS));
-    CKB(hipMalloc(&b->d_bapart, ((size_t)(no + 255) / 256 + 5 * ((size_t)(np + 63) / 64) + 64 * (size_t)nc + 3 * (size_t)no + 64) * 8));
-    CKB(hipMemset(b->d_stamps, 0, 32 * 8));
     const size_t mt = (size_t)c->max_tracks;
-    b->h_stage_bytes = std::max<size_t>(no * 18 * 8 + no * 2 * 8, std::max<size_t>(n * 8 + no * 32 + (np + nc + 2) * 4, mt * 32 + MAX_HYP * 20 + 4096));
-    CKB(hipHostMalloc(&b->h_stage, b->h_stage_bytes));
-    CKB(hipMalloc(&b->d_obj, mt * 12)); CKB(hipMalloc(&b->d_img, mt * 8));
-    CKB(hipMalloc(&b->d_samples, MAX_HYP * 5 * 4)); CKB(hipMalloc(&b->d_counts, MAX_HYP * 4));
-    CKB(hipMalloc(&b->d_inliers, mt * 4)); CKB(hipMalloc(&b->d_info, 16));
-    CKB(hipMalloc(&b->d_models, MAX_HYP * 6 * 8)); CKB(hipMalloc(&b->d_rt, 6 * 8)); CKB(hipMalloc(&b->d_Kp, 9 * 8));
-    CKB(hipMalloc(&b->d_masks, (size_t)MAX_HYP * mt));
-    b->ba_io_bytes = (8 + nc * 6 + np * 3 + no * 2 + 10) * 8 + (no * 8 + np + nc + 8) * 4 + 128;
-    CKB(hipMalloc(&b->d_ba_io, b->ba_io_bytes));
-    b->pnp_in_bytes = PNP_HDR + mt * 20 + (size_t)MAX_HYP * 20 + 64;
-    b->pnp_out_bytes = 48 + 16 + mt * 4 + 64;
-    CKB(hipMalloc(&b->d_pnp_in, b->pnp_in_bytes));
-    CKB(hipMalloc(&b->d_pnp_out, b->pnp_out_bytes));
-    b->tri_in_bytes = 48 * 8 + mt * 32 + mt + 64;
-    b->tri_out_bytes = mt * 16 * 8 + mt * 4 + 64;
-    CKB(hipMalloc(&b->d_tri_in, b->tri_in_bytes));
-    CKB(hipMalloc(&b->d_tri_out, b->tri_out_bytes));
-    CKB(hipMalloc(&b->d_fp_work, (size_t)FP_MAX_HYP * (90 * 8 + 4) + 64));
-    b->ess_in_bytes = ESS_HDR + (5 * mt + 2) * 8 + 64;
-    CKB(hipMalloc(&b->d_ess_in, b->ess_in_bytes));
-    b->h_stage_bytes = std::max(b->h_stage_bytes, std::max(b->ba_io_bytes, b->pnp_in_bytes + b->pnp_out_bytes));
-    b->h_stage_bytes = std::max(b->h_stage_bytes, b->tri_in_bytes + b->tri_out_bytes);
-    b->h_stage_bytes = std::max(b->h_stage_bytes, b->tri_in_bytes + (size_t)FP_MAX_HYP * (90 * 8 + 44) + 256);   // five-point round in + out
-    b->h_stage_bytes = std::max(b->h_stage_bytes, b->ess_in_bytes + ESS_OUT_HDR + mt + 64);   // whole findEssentialMat in + out
-    (void)hipHostFree(b->h_stage);
-    CKB(hipHostMalloc(&b->h_stage, b->h_stage_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    CKB(hipHostGetDevicePointer((void**)&b->d_h_stage, b->h_stage, 0));
-    {   // every buffer a kernel may touch exists (a missed allocation must fail here, not as a GPU fault later)
-        const void* must[] = {b->d_x, b->d_cand, b->d_scale, b->d_diag, b->d_D2, b->d_step, b->d_res, b->d_J, b->d_Einv, b->d_gp, b->d_Yd, b->d_Wd,
-                              b->d_S, b->d_rhs, b->d_Gpart, b->d_summary, b->d_stamps, b->d_bastate, b->d_bapart, b->d_counts, b->d_inliers,
-                              b->d_info, b->d_models, b->d_rt, b->d_masks, b->d_ba_io, b->d_pnp_in, b->d_pnp_out, b->d_tri_in, b->d_tri_out,
-                              b->d_fp_work, b->d_ess_in, b->h_stage, b->d_h_stage};
-        for (const void* p : must)
-            if (!p) { set_err(c, "backend_create: internal error, a back-end buffer was not allocated"); return PMV_ERR_HIP; }
-    }
-#undef CKB
+    const size_t ba_io_bytes = (8 + nc * 6 + np * 3 + no * 2 + 10) * 8 + (no * 8 + np + nc + 8) * 4 + 128;
+    const size_t pnp_in_bytes = PNP_HDR + mt * 20 + (size_t)MAX_HYP * 20 + 64, pnp_out_bytes = 48 + 16 + mt * 4 + 64;
+    const size_t tri_in_bytes = 48 * 8 + mt * 32 + mt + 64, tri_out_bytes = mt * 16 * 8 + mt * 4 + 64;
+    const size_t ess_in_bytes = ESS_HDR + (5 * mt + 2) * 8 + 64;
+    // the staging block holds the largest in + out pair of any call
+    const size_t h_stage_bytes = std::max<size_t>({no * 18 * 8 + no * 2 * 8, n * 8 + no * 32 + (np + nc + 2) * 4, mt * 32 + MAX_HYP * 20 + 4096,
+                                                   ba_io_bytes, pnp_in_bytes + pnp_out_bytes, tri_in_bytes + tri_out_bytes,
+                                                   tri_in_bytes + (size_t)FP_MAX_HYP * (90 * 8 + 44) + 256,   // five-point round in + out
+                                                   ess_in_bytes + ESS_OUT_HDR + mt + 64});                    // whole findEssentialMat in + out
+    // THE list of a workspace set's buffers
+    const MemRow rows[] = {
+        {&b->d_cams, nc * 6 * 8, MEM_DEVICE}, {&b->d_pts, np * 3 * 8, MEM_DEVICE}, {&b->d_obs, no * 2 * 8, MEM_DEVICE}, {&b->d_K, 9 * 8, MEM_DEVICE},
+        {&b->d_cam_idx, no * 4, MEM_DEVICE}, {&b->d_pt_idx, no * 4, MEM_DEVICE},
+        {&b->d_pobs_start, (np + 1) * 4, MEM_DEVICE}, {&b->d_pobs_list, no * 4, MEM_DEVICE},
+        {&b->d_cobs_start, (nc + 1) * 4, MEM_DEVICE}, {&b->d_cobs_list, no * 4, MEM_DEVICE},
+        {&b->d_x, 2 * n * 8, MEM_DEVICE}, {&b->d_cand, n * 8, MEM_DEVICE}, {&b->d_scale, n * 8, MEM_DEVICE}, {&b->d_diag, n * 8, MEM_DEVICE},
+        {&b->d_D2, n * 8, MEM_DEVICE}, {&b->d_step, n * 8, MEM_DEVICE},
+        {&b->d_res, 2 * no * 2 * 8, MEM_DEVICE}, {&b->d_J, 2 * no * 18 * 8, MEM_DEVICE},   // two buffers: current point / candidate
+        {&b->d_Einv, np * 9 * 8, MEM_DEVICE}, {&b->d_gp, np * 3 * 8, MEM_DEVICE},
+        {&b->d_Yd, 2 * b->ydwd_elems * 8, MEM_DEVICE},   // Yt | [Wt | g] adjacent: one clear per solve (multi-kernel LM)
+        {&b->d_Wd, b->ydwd_elems * 8, MEM_DEVICE},       // [Wt | g] of the single-workgroup LM
+        {&b->d_S, m * m * 8, MEM_DEVICE}, {&b->d_rhs, m * 8, MEM_DEVICE},
+        {&b->d_Gpart, b->gpart_elems * 8, MEM_DEVICE},
+        {&b->d_summary, 8 * 8, MEM_DEVICE},
+        {&b->d_stamps, 32 * 8, MEM_DEVICE},
+        {&b->d_bastate, 512 + 4 * BA_MAX_ITERATIONS, MEM_DEVICE},
+        {&b->d_bapart, ((size_t)(no + 255) / 256 + 5 * ((size_t)(np + 63) / 64) + 64 * (size_t)nc + 3 * (size_t)no + 64) * 8, MEM_DEVICE},
+        {&b->d_obj, mt * 12, MEM_DEVICE}, {&b->d_img, mt * 8, MEM_DEVICE},
+        {&b->d_samples, MAX_HYP * 5 * 4, MEM_DEVICE}, {&b->d_counts, MAX_HYP * 4, MEM_DEVICE},
+        {&b->d_inliers, mt * 4, MEM_DEVICE}, {&b->d_info, 16, MEM_DEVICE},
+        {&b->d_models, MAX_HYP * 6 * 8, MEM_DEVICE}, {&b->d_rt, 6 * 8, MEM_DEVICE}, {&b->d_Kp, 9 * 8, MEM_DEVICE},
+        {&b->d_masks, (size_t)MAX_HYP * mt, MEM_DEVICE},
+        {&b->d_ba_io, ba_io_bytes, MEM_DEVICE},
+        {&b->d_pnp_in, pnp_in_bytes, MEM_DEVICE}, {&b->d_pnp_out, pnp_out_bytes, MEM_DEVICE},
+        {&b->d_tri_in, tri_in_bytes, MEM_DEVICE}, {&b->d_tri_out, tri_out_bytes, MEM_DEVICE},
+        {&b->d_fp_work, (size_t)FP_MAX_HYP * (90 * 8 + 4) + 64, MEM_DEVICE},
+        {&b->d_ess_in, ess_in_bytes, MEM_DEVICE},
+        {&b->h_stage, h_stage_bytes, MEM_MAPPED},
+    };
+    hipError_t e = mem_alloc_table(rows, sizeof(rows) / sizeof(rows[0]));
+    if (e == hipSuccess) e = hipMemset(b->d_stamps, 0, 32 * 8);
+    if (e != hipSuccess) { set_err(c, "backend_alloc: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
     return PMV_OK;
 }
 int backend_create(pmv_ctx* c) { return backend_alloc(c, &c->be); }
 
-void backend_free(BackendBuffers* b) {
-    if (!b) return;
-    void* ptrs[] = {b->d_cams, b->d_pts, b->d_obs, b->d_K, b->d_cam_idx, b->d_pt_idx, b->d_pobs_start, b->d_pobs_list, b->d_cobs_start,
-                    b->d_cobs_list, b->d_x, b->d_cand, b->d_scale, b->d_diag, b->d_D2, b->d_step, b->d_res, b->d_J, b->d_Einv, b->d_gp,
-                    b->d_Yd, b->d_Wd, b->d_S, b->d_rhs, b->d_Gpart, b->d_summary, b->d_obj, b->d_img, b->d_samples, b->d_counts,
-                    b->d_inliers, b->d_info, b->d_models, b->d_rt, b->d_Kp, b->d_masks, b->d_ba_io, b->d_pnp_in, b->d_pnp_out, b->d_bastate, b->d_bapart, b->d_tri_in, b->d_tri_out,
-                    b->d_fp_work, b->d_ess_in};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (b->d_stamps) (void)hipFree(b->d_stamps);
-    if (b->h_stage) (void)hipHostFree(b->h_stage);
-    delete b;
-}
+void backend_free(BackendBuffers* b) { delete b; }
 void backend_destroy(pmv_ctx* c) {
+    if (c->s_ahead) { (void)hipStreamSynchronize(c->s_ahead); (void)hipStreamDestroy(c->s_ahead); c->s_ahead = nullptr; }   // (before its workspaces go)
     backend_free(c->be); c->be = nullptr;
-    if (c->be_ahead) { backend_free(c->be_ahead); c->be_ahead = nullptr; }
-    if (c->s_ahead) { (void)hipStreamSynchronize(c->s_ahead); (void)hipStreamDestroy(c->s_ahead); c->s_ahead = nullptr; }
+    backend_free(c->be_ahead); c->be_ahead = nullptr;
 }
 
 // cv::RNG (multiply-with-carry) and RANSACPointSetRegistrator::getSubset (5 distinct indices)
@@ -175,7 +152,7 @@ void pmv::pnp_prepare(BackendBuffers* b, const float* obj_xyz, const float* img_
     P->rt_out = (double*)b->d_pnp_out;
     P->info = (int*)(b->d_pnp_out + 48);
     P->inliers = (int*)(b->d_pnp_out + 64);
-    P->host_out = b->d_h_stage + (ho - hs);   // the refit kernel writes [rt 48 B | info 16 B | inliers] straight into the pinned block
+    P->host_out = b->h_stage.dm() + (ho - hs);   // the refit kernel writes [rt 48 B | info 16 B | inliers] straight into the pinned block
     P->m = m; P->n_hyp = iterations;
     P->thr = (float)((double)reproj_err * (double)reproj_err);
     P->confidence = confidence;
@@ -228,7 +205,7 @@ int pmv_pnp_ransac(pmv_ctx* ctx, const float* obj_xyz, const float* img_xy, int 
     static const bool stage_by_kernel = !(getenv("PMV_BA_STAGE") && !strcmp(getenv("PMV_BA_STAGE"), "dma"));
     if (stage_by_kernel) {
         const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
-        hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->d_h_stage, (uint4*)b->d_pnp_in, n16);
+        hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_pnp_in, n16);
         CKC(hipGetLastError());
     } else CKC(hipMemcpyAsync(b->d_pnp_in, b->h_stage, in_bytes, hipMemcpyHostToDevice, s));
     // the refit kernel writes [rt | info | inliers] straight into the pinned block and, last, this call's sequence number into the
@@ -345,7 +322,7 @@ int pmv::ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc,
     int* pstart = h_pi + n_obs; int* plist = pstart + (np + 1); int* cstart = plist + n_obs; int* clist = cstart + (nc + 1);
     int* odup = (int*)(((uintptr_t)(clist + n_obs) + 15) & ~(uintptr_t)15);   // 16-byte records (observation, camera, point, dup flag)
     const size_t io_bytes = (size_t)((char*)(odup + (size_t)4 * n_obs) - hs);
-    REQ(io_bytes <= b->ba_io_bytes, PMV_ERR_CAPACITY, "pmv_ba_solve: io block too small");
+    REQ(io_bytes <= b->d_ba_io.cap, PMV_ERR_CAPACITY, "pmv_ba_solve: io block too small");
     memcpy(h_cams, cams, (size_t)nc * 48); memcpy(h_pts, pts, (size_t)np * 24); memcpy(h_obs, obs_xy, (size_t)n_obs * 16);
     memcpy(h_K, K, 72); memcpy(h_ci, cam_idx, (size_t)n_obs * 4); memcpy(h_pi, pt_idx, (size_t)n_obs * 4);
     // observation lists per point / per camera (counting sort, observation order preserved)
@@ -402,7 +379,7 @@ int pmv::ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc,
     REQ((size_t)A.krows * A.ldw <= b->ydwd_elems && (size_t)A.kslices * A.gp_rows * A.ldw <= b->gpart_elems, PMV_ERR_CAPACITY, "pmv_ba_solve: workspace too small");
     if (multi) {
         A.Wd = A.Yd + (size_t)A.krows * A.ldw;
-        A.out = (double*)b->d_h_stage;   // [summary 8 | cams | pts] of the result, straight into the pinned block
+        A.out = (double*)b->h_stage.dm();   // [summary 8 | cams | pts] of the result, straight into the pinned block
     }
     *Aout = A;
     *io_bytes_out = io_bytes;
@@ -483,7 +460,7 @@ int pmv_ba_solve(pmv_ctx* ctx, double* cams, int nc, double* pts, int np, const 
     static const bool stage_by_kernel = !(getenv("PMV_BA_STAGE") && !strcmp(getenv("PMV_BA_STAGE"), "dma"));
     if (stage_by_kernel && !check) {   // (h_stage and d_ba_io are 16-byte aligned and have >= 16 B of slack)
         const unsigned n16 = (unsigned)((io_bytes + 15) >> 4);
-        hipLaunchKernelGGL(k_stage_block, dim3(std::min(64u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->d_h_stage, (uint4*)b->d_ba_io, n16);
+        hipLaunchKernelGGL(k_stage_block, dim3(std::min(64u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_ba_io, n16);
         CKC(hipGetLastError());
     } else CKC(hipMemcpyAsync(b->d_ba_io, hs, io_bytes, hipMemcpyHostToDevice, s));
     std::vector<char> saved;
@@ -548,7 +525,7 @@ int pmv::fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, co
     double* h_q2 = h_q1 + (size_t)2 * n;
     int* h_s = (int*)(h_q2 + (size_t)2 * n);
     const size_t in_bytes = (size_t)4 * n * 8 + (size_t)5 * n_hyp * 4;
-    REQ(in_bytes <= b->tri_in_bytes, PMV_ERR_CAPACITY, "five-point round: input block too small");
+    REQ(in_bytes <= b->d_tri_in.cap, PMV_ERR_CAPACITY, "five-point round: input block too small");
     memcpy(h_q1, q1, (size_t)n * 16); memcpy(h_q2, q2, (size_t)n * 16); memcpy(h_s, samples, (size_t)5 * n_hyp * 4);
     P->q1 = (const double*)b->d_tri_in;
     P->q2 = P->q1 + (size_t)2 * n;
@@ -556,7 +533,7 @@ int pmv::fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, co
     P->models_d = (double*)b->d_fp_work;
     P->n_models_d = (int*)(b->d_fp_work + (size_t)FP_MAX_HYP * 90 * 8);
     char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    char* dho = b->d_h_stage + (ho - hs);
+    char* dho = b->h_stage.dm() + (ho - hs);
     P->models_h = (double*)dho;
     P->n_models_h = (int*)(dho + (size_t)n_hyp * 90 * 8);
     P->counts_h = P->n_models_h + n_hyp;
@@ -589,7 +566,7 @@ void pmv::dlt_prepare(BackendBuffers* b, const double* q1, const double* q2, int
     P->q2 = P->q1 + (size_t)2 * n;
     P->mask_in = (const uint8_t*)(P->q2 + (size_t)2 * n);
     char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    P->Q = (double*)(b->d_h_stage + (ho - hs));   // results go straight into the pinned block (coalesced 8-byte stores)
+    P->Q = (double*)(b->h_stage.dm() + (ho - hs));   // results go straight into the pinned block (coalesced 8-byte stores)
     P->mask = (uint8_t*)(P->Q + (size_t)16 * n);
     P->n = n;
     *in_bytes_out = in_bytes;
@@ -706,7 +683,7 @@ void pmv::essential_prepare(BackendBuffers* b, const double* p1, const double* p
     P->q1 = (const double*)(b->d_ess_in + ESS_HDR);
     P->q2 = P->q1 + (size_t)2 * n;
     P->iters = P->q2 + (size_t)2 * n;
-    P->out = b->d_h_stage + (ho - hs);
+    P->out = b->h_stage.dm() + (ho - hs);
     P->n = n; P->max_iters = 1000;
     P->thr = (float)(threshold * threshold);
     if (++b->done_seq == 0) b->done_seq = 1;
@@ -747,7 +724,7 @@ int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_x
     size_t in_bytes = 0;
     essential_prepare(b, p1_xy, p2_xy, n, K, prob, threshold, &P, &in_bytes);
     const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
-    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->d_h_stage, (uint4*)b->d_ess_in, n16);
+    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_ess_in, n16);
     CKC(hipGetLastError());
     CKC(launch_essential_ransac(s, (const EssentialProblem*)b->d_ess_in, 1));
     // the kernel's last store is this call's sequence number in the result block (PMV_BACK_WAIT=sync: hipStreamSynchronize instead; see pmv_pnp_ransac)

@@ -91,21 +91,9 @@ struct FPReq : Req { BackendBuffers* b; FivePointProblem P; size_t in_bytes; };
 // the submit until the combiner has released the record after the round, and the seq's next call waits for that before it fills the record again.
 struct EssReq : Req { BackendBuffers* b = nullptr; EssentialProblem P; size_t in_bytes = 0; std::atomic<int> inflight{0}; };
 
-struct Growable {   // device (or mapped pinned host) buffer that only grows; dev = the address kernels use (alias of a host buffer)
-    void* p = nullptr; size_t cap = 0; bool host = false; char* dev = nullptr;
-    hipError_t ensure(size_t need) {
-        if (need <= cap) return hipSuccess;
-        if (p) { hipError_t e = host ? hipHostFree(p) : hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-        need = (need * 5 / 4 + 4095) & ~(size_t)4095;
-        hipError_t e = host ? hipHostMalloc(&p, need, hipHostMallocMapped | hipHostMallocCoherent) : hipMalloc(&p, need);
-        if (e != hipSuccess) return e;
-        cap = need;
-        dev = (char*)p;
-        if (host) e = hipHostGetDevicePointer((void**)&dev, p, 0);
-        return e;
-    }
-    void release() { if (p) { (void)(host ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; } }
-};
+// per-round scratch of a combiner: grows with slack (GROW_SLACK), in HBM or in mapped pinned memory (.dev = the address kernels use)
+struct DScratch : Growable { DScratch() : Growable(MEM_DEVICE, GROW_SLACK) {} };
+struct HScratch : Growable { HScratch() : Growable(MEM_MAPPED, GROW_SLACK) {} };
 
 enum Role { R_LK = 0, R_DET, R_PNP, R_BA, R_DLT, R_FP, R_COUNT };
 struct Queue {   // pending requests of one kernel class
@@ -124,28 +112,28 @@ struct Combiner {
     hipStream_t s = nullptr;           // this combiner's stream (lanes of a class may share one: BatchEngine::streams)
     bool owns_stream = true;
     hipEvent_t ev = nullptr;           // blocking-sync event for the interrupt-driven wait
-    Growable h_desc{nullptr, 0, true}, d_desc;   // per-batch descriptors (+ stage-in jobs), pinned mirror and device copy
+    HScratch h_desc; DScratch d_desc;   // per-batch descriptors (+ stage-in jobs), pinned mirror and device copy
     long batches = 0, requests = 0;
     double t_idle = 0, t_work = 0, t_sync = 0;   // seconds: waiting for requests / processing a batch / inside hipStreamSynchronize
     double t_cpu = 0;                            // CPU seconds of the combiner thread itself
     // LK staging + mapped pinned result blocks; detector buffers (only used by combiners of those classes)
-    Growable h_front{nullptr, 0, true}, d_front, h_cells{nullptr, 0, true}, d_cells, d_eig, d_cellmax, d_spill, d_det_xy, d_det_score, d_det_count, h_det{nullptr, 0, true};
+    HScratch h_front, h_cells, h_det; DScratch d_front, d_cells, d_eig, d_cellmax, d_spill, d_det_xy, d_det_score, d_det_count;
     // masks of the extended GFTT requests of a round (detector combiner, made by the first round that has one): the cells' mask sub-views
     // packed one after the other, pinned mirror and HBM copy
-    Growable h_gmask{nullptr, 0, true}, d_gmask;
+    HScratch h_gmask; DScratch d_gmask;
     // corner sub-pixel requests of a round (detector combiner, made by the first round that has one): [point records | positions | updates |
     // flags] in one mapped pinned block; the weight tables of the round's parameter groups, pinned mirror and HBM copy
-    Growable h_spx{nullptr, 0, true}, h_spx_tab{nullptr, 0, true}, d_spx_tab;
+    HScratch h_spx, h_spx_tab; DScratch d_spx_tab;
     // kNN matcher rounds (LK combiners): [stage-in job | request records | coordinate lists], pinned mirror and HBM copy; FAST score maps (detector combiner)
-    Growable h_knn{nullptr, 0, true}, d_knn, d_fast_score;
+    HScratch h_knn; DScratch d_knn, d_fast_score;
     // extended LK requests (LK combiners, made by the first round that has one): [LKBlock | LKExt] records of a round; back results of
     // cap_tracks tracks as [positions | err | status], indexed like the forward results
-    Growable h_lkx{nullptr, 0, true}, h_back{nullptr, 0, true};
-    float* h_out_xy = nullptr; float* h_err = nullptr; uint8_t* h_status = nullptr; uint16_t* h_work = nullptr;
-    float* dm_out_xy = nullptr; float* dm_err = nullptr; uint8_t* dm_status = nullptr; uint16_t* dm_work = nullptr;
-    int* d_flags = nullptr;
+    HScratch h_lkx, h_back;
+    // results of cap_tracks tracks (LK combiners; mapped pinned, the kernels write them through .dm()); the detector combiner's overflow bits
+    Buf<float> h_out_xy{MEM_MAPPED}, h_err{MEM_MAPPED}; Buf<uint8_t> h_status{MEM_MAPPED}; Buf<uint16_t> h_work{MEM_MAPPED};
+    Buf<int> d_flags;
     // completion word of the "flag" wait: the last launch of a round is k_signal, which stores the round number into mapped pinned memory
-    unsigned* h_done = nullptr; unsigned* dm_done = nullptr; unsigned done_seq = 0;
+    Buf<unsigned> h_done{MEM_MAPPED}; unsigned done_seq = 0;
     double ema_wait_us = 0;            // smoothed duration of the wait of a round (how long to sleep before the first look)
     long n_polls = 0; double t_first_sleep = 0, t_prep = 0, t_post = 0;   // diagnostic (PMV_BATCH_TIMING=1, printed when the engine goes)
 };
@@ -229,11 +217,11 @@ hipError_t wait_stream(BatchEngine* E, Combiner& C) {
     }
     // completion word: sleep through most of the expected duration, then look every ~10 us (timer slack of the thread is 1 us)
     const unsigned seq = ++C.done_seq;
-    hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, C.s, C.dm_done, seq);
+    hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, C.s, C.h_done.dm(), seq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const auto t0 = std::chrono::steady_clock::now();
-    auto done = [&] { return __atomic_load_n(C.h_done, __ATOMIC_ACQUIRE) == seq; };
+    auto done = [&] { return __atomic_load_n(C.h_done.get(), __ATOMIC_ACQUIRE) == seq; };
     if (!done()) {
         const double first = 0.7 * C.ema_wait_us;
         if (first > 25) { std::this_thread::sleep_for(std::chrono::nanoseconds((long)(first * 1e3))); C.t_first_sleep += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
@@ -309,7 +297,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             k.src_off = (unsigned long long)r->src_slot * pitch; k.cmp_off = (unsigned long long)r->cmp_slot * pitch;
             k.src_xy = (const int*)(db + off); memcpy(hb + off, r->src_xy, (size_t)r->n * 8); off += ((size_t)r->n * 8 + 15) & ~(size_t)15;
             k.cmp_xy = (const int*)(db + off); if (r->m) memcpy(hb + off, r->cmp_xy, (size_t)r->m * 8); off += ((size_t)r->m * 8 + 15) & ~(size_t)15;
-            k.out_best = (int*)C.dm_out_xy + 2 * (size_t)r->base; k.out_err = C.dm_err + r->base;
+            k.out_best = (int*)C.h_out_xy.dm() + 2 * (size_t)r->base; k.out_err = C.h_err.dm() + r->base;
             k.n = r->n; k.m = r->m; k.nn_window = knn_pack(r->n_nn, r->window); k.geom = r->geom;
         }
         // one gather pulls records and lists into HBM (every workgroup of a request scans its whole candidate list): no DMA call
@@ -357,11 +345,11 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         if (lk_stamps) {
             static std::mutex stamps_mu;   // two LK lanes
             std::lock_guard<std::mutex> lk_(stamps_mu);
-            if (!ctx->d_lk_stamps && hipMalloc(&ctx->d_lk_stamps, 16 * 8) == hipSuccess) (void)hipMemset(ctx->d_lk_stamps, 0, 16 * 8);
+            if (!ctx->d_lk_stamps && ctx->d_lk_stamps.ensure(16 * 8) == hipSuccess) (void)hipMemset(ctx->d_lk_stamps, 0, 16 * 8);
         }
         P.stamps = lk_stamps ? ctx->d_lk_stamps : nullptr;
         // mapped pinned: every workgroup reads its 32-byte record once, no copy launch
-        EK(launch_lk_batch(s, ctx->d_slots, (const LKBlock*)C.h_front.dev, bpos, ctx->d_geom, P, C.dm_out_xy, C.dm_status, C.dm_err, C.dm_work));
+        EK(launch_lk_batch(s, ctx->d_slots, (const LKBlock*)C.h_front.dev, bpos, ctx->d_geom, P, C.h_out_xy.dm(), C.h_status.dm(), C.h_err.dm(), C.h_work.dm()));
         ctx->batch_launches[0]++;
     }
     // ---- extended LK: the round's pmv_lk_track_ex / _fb requests in ONE launch of the extended batch kernels; their results take the
@@ -396,8 +384,8 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 x.ix = init ? r->out_xy[2 * k] : 0.f; x.iy = init ? r->out_xy[2 * k + 1] : 0.f; x.flags = r->flags; x.reserved = 0;
             }
         const LKParams P = lk_launch_params(ctx);
-        EK(launch_lk_batch_ex(s, ctx->d_slots, (const LKBlock*)C.h_lkx.dev, (const LKExt*)(C.h_lkx.dev + sizeof(LKBlock) * (size_t)ext_tracks), bpos, ctx->d_geom, P, C.dm_out_xy,
-                              C.dm_status, C.dm_err, C.dm_work, (float*)C.h_back.dev, (uint8_t*)(C.h_back.dev + cap * 12), (float*)(C.h_back.dev + cap * 8)));
+        EK(launch_lk_batch_ex(s, ctx->d_slots, (const LKBlock*)C.h_lkx.dev, (const LKExt*)(C.h_lkx.dev + sizeof(LKBlock) * (size_t)ext_tracks), bpos, ctx->d_geom, P, C.h_out_xy.dm(),
+                              C.h_status.dm(), C.h_err.dm(), C.h_work.dm(), (float*)C.h_back.dev, (uint8_t*)(C.h_back.dev + cap * 12), (float*)(C.h_back.dev + cap * 8)));
         ctx->batch_launches[0]++;
     }
     SYNC_TIMED(C);
@@ -646,7 +634,7 @@ void process_pnp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (size_t i = 0; i < batch.size(); i++) {
         PnPReq* r = (PnPReq*)batch[i];
         D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_pnp_in, (unsigned)r->in_bytes, 0};
+        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_pnp_in, (unsigned)r->in_bytes, 0};
         max_hyp = std::max(max_hyp, r->P.n_hyp);
     }
     EK(stage_in(C, D, batch.size(), 2));
@@ -662,7 +650,7 @@ void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         for (size_t i = 0; i < batch.size(); i++) {
             BAReq* r = (BAReq*)batch[i];
             D.hprob[i] = r->A;
-            D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_ba_io, (unsigned)r->io_bytes, 0};
+            D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->io_bytes, 0};
             max_m = std::max(max_m, 6 * r->A.nc);
         }
         EK(stage_in(C, D, batch.size(), 8));
@@ -680,7 +668,7 @@ void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (size_t i = 0; i < sorted.size(); i++) {
         BAReq* r = sorted[i];
         ba_fill_prob(D.hprob[i], r->A, r->b->d_bastate, r->b->d_bapart);
-        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_ba_io, (unsigned)r->io_bytes, 0};
+        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->io_bytes, 0};
     }
     EK(stage_in(C, D, sorted.size(), 8));
     size_t i0 = 0;
@@ -708,7 +696,7 @@ void process_dlt(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (size_t i = 0; i < batch.size(); i++) {
         DltReq* r = (DltReq*)batch[i];
         D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_tri_in, (unsigned)r->in_bytes, 0};
+        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->in_bytes, 0};
         max_n = std::max(max_n, r->P.n);
     }
     EK(stage_in(C, D, batch.size(), 2));
@@ -723,7 +711,7 @@ void process_fp_rounds(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (size_t i = 0; i < batch.size(); i++) {
         FPReq* r = (FPReq*)batch[i];
         D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_tri_in, (unsigned)r->in_bytes, 0};
+        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->in_bytes, 0};
         max_hyp = std::max(max_hyp, r->P.n_hyp);
     }
     EK(stage_in(C, D, batch.size(), 2));
@@ -739,7 +727,7 @@ void process_essential(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (size_t i = 0; i < batch.size(); i++) {
         EssReq* r = (EssReq*)batch[i];
         D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->d_h_stage, r->b->d_ess_in, (unsigned)r->in_bytes, 0};
+        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ess_in, (unsigned)r->in_bytes, 0};
     }
     EK(stage_in(C, D, batch.size(), 2));
     EK(launch_essential_ransac(C.s, D.dprob, (int)batch.size()));
@@ -886,16 +874,9 @@ void batch_engine_destroy(pmv_ctx* ctx) {
                         C.t_first_sleep / C.batches * 1e6, (double)C.n_polls / C.batches, C.t_cpu / C.batches * 1e6, C.ema_wait_us);
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
-            if (C.h_done) (void)hipHostFree(C.h_done);
-            for (Growable* g : {&C.h_desc, &C.d_desc, &C.h_front, &C.d_front, &C.h_cells, &C.d_cells, &C.d_eig, &C.d_cellmax, &C.d_spill, &C.d_det_xy, &C.d_det_score, &C.d_det_count, &C.h_det, &C.h_knn, &C.d_knn, &C.d_fast_score, &C.h_lkx, &C.h_back, &C.h_gmask, &C.d_gmask, &C.h_spx, &C.h_spx_tab, &C.d_spx_tab}) g->release();
-            if (C.h_out_xy) (void)hipHostFree(C.h_out_xy);
-            if (C.h_err) (void)hipHostFree(C.h_err);
-            if (C.h_status) (void)hipHostFree(C.h_status);
-            if (C.h_work) (void)hipHostFree(C.h_work);
-            if (C.d_flags) (void)hipFree(C.d_flags);
         }
     for (BackendBuffers* b : E->slots) backend_free(b);
-    delete E;
+    delete E;   // the combiners' buffers go with it: their threads are joined and their streams idle
     ctx->engine = nullptr;
 }
 
@@ -949,20 +930,10 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
             if (l < n_streams) CKC(hipStreamCreateWithPriority(&C.s, hipStreamNonBlocking, prio));
             else { C.s = E->comb[r][l % n_streams].s; C.owns_stream = false; }
             CKC(hipEventCreateWithFlags(&C.ev, hipEventBlockingSync | hipEventDisableTiming));
-            CKC(hipHostMalloc(&C.h_done, 64, hipHostMallocMapped | hipHostMallocCoherent));
+            CKC(C.h_done.ensure(64));
             *C.h_done = 0;
-            CKC(hipHostGetDevicePointer((void**)&C.dm_done, C.h_done, 0));
-            if (r == R_LK) {
-                CKC(hipHostMalloc(&C.h_out_xy, E->cap_tracks * 8, hipHostMallocMapped | hipHostMallocCoherent));
-                CKC(hipHostMalloc(&C.h_status, E->cap_tracks, hipHostMallocMapped | hipHostMallocCoherent));
-                CKC(hipHostMalloc(&C.h_err, E->cap_tracks * 4, hipHostMallocMapped | hipHostMallocCoherent));
-                CKC(hipHostMalloc(&C.h_work, E->cap_tracks * 2, hipHostMallocMapped | hipHostMallocCoherent));
-                CKC(hipHostGetDevicePointer((void**)&C.dm_work, C.h_work, 0));
-                CKC(hipHostGetDevicePointer((void**)&C.dm_out_xy, C.h_out_xy, 0));
-                CKC(hipHostGetDevicePointer((void**)&C.dm_status, C.h_status, 0));
-                CKC(hipHostGetDevicePointer((void**)&C.dm_err, C.h_err, 0));
-            }
-            if (r == R_DET) CKC(hipMalloc(&C.d_flags, 16));
+            if (r == R_LK) { CKC(C.h_out_xy.ensure(E->cap_tracks * 8)); CKC(C.h_status.ensure(E->cap_tracks)); CKC(C.h_err.ensure(E->cap_tracks * 4)); CKC(C.h_work.ensure(E->cap_tracks * 2)); }
+            if (r == R_DET) CKC(C.d_flags.ensure(16));
         }
     for (int r = 0; r < R_COUNT; r++)
         for (int l = 0; l < E->lanes[r]; l++) E->comb[r][l].th = std::thread(combiner_loop, E, r, l);
@@ -1005,15 +976,8 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
     }
     // the same XCD-aware dealing as pmv_lk_track (stripe s of the x-sorted tracks -> blocks 8k + s); a request's block range starts at
     // a multiple of 8 in the concatenated launch, so block % 8 (= XCD) is preserved
-    const int nb = (n + 7) / 8 * 8;
-    r.order.assign(nb, -1);
-    std::vector<std::pair<float, int>> byx(n);
-    for (int i = 0; i < n; i++) byx[i] = {prev_xy[2 * i], i};
-    std::sort(byx.begin(), byx.end());
-    for (int i = 0; i < n; i++) {
-        const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);
-        r.order[(i - first) * 8 + s8] = byx[i].second;
-    }
+    r.order.resize((size_t)((n + 7) / 8 * 8));
+    lk_xcd_order(prev_xy, n, r.order.data());
     return submit(ctx, E->queue[R_LK], &r);
 }
 
@@ -1142,7 +1106,7 @@ int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np
     r.kind = 11; r.b = E->slots[seq]; r.max_iterations = max_iterations;
     rc = ba_prepare(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, ctx->ba_mode != 1, &r.A, &r.io_bytes);
     if (rc) return rc;
-    if (ctx->ba_mode == 1) r.A.out = (double*)r.b->d_h_stage;   // k_ba_lm_batch copies [summary | cams | pts] into the request's pinned block
+    if (ctx->ba_mode == 1) r.A.out = (double*)r.b->h_stage.dm();   // k_ba_lm_batch copies [summary | cams | pts] into the request's pinned block
     rc = submit(ctx, E->queue[R_BA], &r);
     if (rc) return rc;
     ba_finish(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, summary);

@@ -75,7 +75,7 @@ struct BatchSession {
     // the upload class
     std::thread th;
     hipStream_t stream = nullptr;
-    unsigned* h_done = nullptr; unsigned* dm_done = nullptr; unsigned done_seq = 0;   // completion word of a round (mapped pinned)
+    Buf<unsigned> h_done{MEM_MAPPED}; unsigned done_seq = 0;   // completion word of a round (mapped pinned)
     double ema_wait_us = 0;
     std::mutex mu;
     std::condition_variable cv;
@@ -84,13 +84,13 @@ struct BatchSession {
     // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND |
     // CLAHE PyrListEntry x ROUND | ClaheRec x ROUND | remap PyrListEntry x ROUND | RemapRec x ROUND] (the last four are written only by a
     // round with such requests)
-    char* h_tab = nullptr; char* dm_tab = nullptr;
+    Buf<char> h_tab{MEM_MAPPED};
     // LUT blocks of a round's CLAHE requests (HBM): made by the first such round, grown to the largest round seen
-    uint8_t* d_lut = nullptr; size_t lut_cap = 0;
+    Buf<uint8_t> d_lut;
     // tight destination frames of a round's remap requests (HBM): made by the first such round, grown to the largest round seen
-    uint8_t* d_rscratch = nullptr; size_t rscratch_cap = 0;
+    Buf<uint8_t> d_rscratch;
     // staging pool: n_blk blocks of blk_bytes (the largest BGR frame of the declared sizes), pinned + mapped
-    uint8_t* h_pool = nullptr; uint8_t* dm_pool = nullptr;
+    Buf<uint8_t> h_pool{MEM_MAPPED};
     size_t blk_bytes = 0;
     std::mutex pool_mu;
     std::condition_variable pool_cv;
@@ -112,11 +112,11 @@ void fail_round(std::vector<UpReq*>& batch, const char* what, hipError_t e) {
 // the completion word of wait_stream (batch_engine.hip): sleep through most of the expected duration, then look every ~10 us
 hipError_t wait_round(BatchSession* S) {
     const unsigned seq = ++S->done_seq;
-    hipLaunchKernelGGL(k_upload_signal, dim3(1), dim3(1), 0, S->stream, S->dm_done, seq);
+    hipLaunchKernelGGL(k_upload_signal, dim3(1), dim3(1), 0, S->stream, S->h_done.dm(), seq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const auto t0 = std::chrono::steady_clock::now();
-    auto done = [&] { return __atomic_load_n(S->h_done, __ATOMIC_ACQUIRE) == seq; };
+    auto done = [&] { return __atomic_load_n(S->h_done.get(), __ATOMIC_ACQUIRE) == seq; };
     if (!done()) {
         const double first = 0.7 * S->ema_wait_us;
         if (first > 25) std::this_thread::sleep_for(std::chrono::nanoseconds((long)(first * 1e3)));
@@ -141,7 +141,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     PyrPitchEntry* tg = (PyrPitchEntry*)S->h_tab;
     PyrPitchEntry* tc = tg + BatchSession::ROUND;
     PyrListEntry* ta = (PyrListEntry*)(tc + BatchSession::ROUND);
-    const PyrPitchEntry* dg = (const PyrPitchEntry*)S->dm_tab;
+    const PyrPitchEntry* dg = (const PyrPitchEntry*)S->h_tab.dm();
     const PyrPitchEntry* dc = dg + BatchSession::ROUND;
     const PyrListEntry* da = (const PyrListEntry*)(dc + BatchSession::ROUND);
     PyrListEntry* te = ta + BatchSession::ROUND;                 // the slots of the round's CLAHE requests (in-place entries)
@@ -201,12 +201,8 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     if (nm) {
         // level 0 of the round's remap requests is gathered from where the launches above left it into the scratch, then written back with its
         // REFLECT_101 frame by the list form, whose sources are the scratch frames
-        if (rscratch_bytes > S->rscratch_cap) {   // (the stream is idle between rounds: the previous round was waited for)
-            if (S->d_rscratch) (void)hipFree(S->d_rscratch);
-            S->d_rscratch = nullptr; S->rscratch_cap = 0;
-            if ((e = hipMalloc(&S->d_rscratch, rscratch_bytes)) != hipSuccess) { fail("the remap scratch", e); return; }
-            S->rscratch_cap = rscratch_bytes;
-        }
+        // (growing frees the old block: the stream is idle between rounds, the previous round was waited for)
+        if ((e = S->d_rscratch.ensure(rscratch_bytes)) != hipSuccess) { fail("the remap scratch", e); return; }
         for (int i = 0; i < nm; i++) tm[i].src = S->d_rscratch + tq[i].dst_off;
         if ((e = launch_remap(S->stream, ctx->d_slots, ctx->d_geom, dq, nm, Lm.w[0], Lm.h[0], S->d_rscratch)) != hipSuccess) { fail("k_remap", e); return; }
         ctx->remap_launches[2]++;
@@ -215,12 +211,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     }
     if (ne) {
         // level 0 of the round's CLAHE requests is equalised where the launches above left it, then its REFLECT_101 frame is rebuilt in place
-        if (lut_bytes > S->lut_cap) {   // (the stream is idle between rounds: the previous round was waited for)
-            if (S->d_lut) (void)hipFree(S->d_lut);
-            S->d_lut = nullptr; S->lut_cap = 0;
-            if ((e = hipMalloc(&S->d_lut, lut_bytes)) != hipSuccess) { fail("the LUT scratch", e); return; }
-            S->lut_cap = lut_bytes;
-        }
+        if ((e = S->d_lut.ensure(lut_bytes)) != hipSuccess) { fail("the LUT scratch", e); return; }   // (as above)
         if ((e = launch_clahe(S->stream, ctx->d_slots, ctx->d_geom, dr, ne, max_tiles, Le.w[0], Le.h[0], S->d_lut)) != hipSuccess) { fail("k_clahe_lut / k_clahe_apply", e); return; }
         ctx->clahe_launches[2]++;
         if ((e = launch_pad_level0_list(S->stream, ctx->d_slots, ctx->d_geom, Le, de, ne)) != hipSuccess) { fail("k_pad_level0_list", e); return; }
@@ -280,11 +271,6 @@ void session_free(BatchSession* S) {
     S->cv.notify_all();
     if (S->th.joinable()) S->th.join();
     if (S->stream) { (void)hipStreamSynchronize(S->stream); (void)hipStreamDestroy(S->stream); }
-    if (S->h_done) (void)hipHostFree(S->h_done);
-    if (S->h_tab) (void)hipHostFree(S->h_tab);
-    if (S->h_pool) (void)hipHostFree(S->h_pool);
-    if (S->d_lut) (void)hipFree(S->d_lut);
-    if (S->d_rscratch) (void)hipFree(S->d_rscratch);
     delete S;
 }
 
@@ -362,12 +348,8 @@ int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes) {
     // two blocks per sequence (frames k - 1 and k on their way), within 4 .. 64 blocks and 256 MB; an uploader without a block waits for one
     const int n_blk = (int)std::max<size_t>(2, std::min<size_t>({(size_t)64, std::max<size_t>(4, 2 * (size_t)n_seq), ((size_t)256 << 20) / S->blk_bytes}));
     if ((e = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)) == hipSuccess &&
-        (e = hipHostMalloc(&S->h_done, 64, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess &&
-        (e = hipHostGetDevicePointer((void**)&S->dm_done, S->h_done, 0)) == hipSuccess &&
-        (e = hipHostMalloc(&S->h_tab, tab_bytes, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess &&
-        (e = hipHostGetDevicePointer((void**)&S->dm_tab, S->h_tab, 0)) == hipSuccess &&
-        (e = hipHostMalloc(&S->h_pool, (size_t)n_blk * S->blk_bytes, hipHostMallocMapped | hipHostMallocCoherent)) == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&S->dm_pool, S->h_pool, 0);
+        (e = S->h_done.ensure(64)) == hipSuccess && (e = S->h_tab.ensure(tab_bytes)) == hipSuccess)
+        e = S->h_pool.ensure((size_t)n_blk * S->blk_bytes);
     if (e != hipSuccess) { set_err(ctx, "pmv_batch_open: %s", hipGetErrorString(e)); session_free(S); return PMV_ERR_HIP; }
     *S->h_done = 0;
     for (int i = n_blk - 1; i >= 0; i--) S->free_blk.push_back(i);
@@ -461,7 +443,7 @@ static int session_upload(pmv_ctx* ctx, int slot, const uint8_t* pixels, int w, 
         uint8_t* dst = S->h_pool + (size_t)blk * S->blk_bytes;   // (row * h <= blk_bytes: the size is a declared one)
         if ((size_t)stride == row) memcpy(dst, pixels, row * (size_t)h);
         else for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * row, pixels + (size_t)y * (size_t)stride, row);
-        r.dsrc = S->dm_pool + (size_t)blk * S->blk_bytes;
+        r.dsrc = S->h_pool.dm() + (size_t)blk * S->blk_bytes;
         r.pitch = (unsigned)row;
     }
     {

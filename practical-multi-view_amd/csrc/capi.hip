@@ -99,54 +99,47 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     CK(backend_prepare_device());
     CK(hipStreamCreateWithFlags(&c->s_front, hipStreamNonBlocking));
     CK(hipStreamCreateWithFlags(&c->s_back, hipStreamNonBlocking));
-    CK(hipMalloc(&c->d_slots, (size_t)c->cap.slot_bytes * n_slots));
-    c->slots_alloc = (size_t)c->cap.slot_bytes * n_slots;
-    CK(hipMalloc(&c->d_tight, (size_t)pmv_ctx::TIGHT_FRAMES * max_w * max_h + 256));
     const size_t nt = (size_t)max_tracks;
-    CK(hipMalloc(&c->d_prev_xy, nt * 12 + 64));   // track coordinates followed by the block -> track order
-    CK(hipMalloc(&c->d_out_xy, nt * 8));
-    CK(hipMalloc(&c->d_status, nt)); CK(hipMalloc(&c->d_err, nt * 4));
-    CK(hipHostMalloc(&c->h_prev_xy, nt * 12 + 64));
-    // LK results: 13 bytes per track, written by the kernel through the device aliases of these mapped pinned buffers (no D2H copies)
-    CK(hipHostMalloc(&c->h_out_xy, nt * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    CK(hipHostMalloc(&c->h_status, nt, hipHostMallocMapped | hipHostMallocCoherent));
-    CK(hipHostMalloc(&c->h_err, nt * 4, hipHostMallocMapped | hipHostMallocCoherent));
-    CK(hipHostGetDevicePointer((void**)&c->dm_out_xy, c->h_out_xy, 0));
-    CK(hipHostGetDevicePointer((void**)&c->dm_status, c->h_status, 0));
-    CK(hipHostGetDevicePointer((void**)&c->dm_err, c->h_err, 0));
-    CK(hipMalloc(&c->d_knn, nt * 16 + 64));
-    CK(hipHostMalloc(&c->h_knn, nt * 16 + 64));
-    CK(hipHostMalloc(&c->h_work, (size_t)nt * 2, hipHostMallocMapped | hipHostMallocCoherent));
-    CK(hipHostGetDevicePointer((void**)&c->dm_work, c->h_work, 0));
+    // THE list of the context's fixed buffers (the lazily made ones are an ensure() at their first use; the back-end's own table: backend_alloc)
+    const MemRow rows[] = {
+        {&c->d_slots, (size_t)c->cap.slot_bytes * n_slots, MEM_DEVICE},
+        {&c->d_tight, (size_t)pmv_ctx::TIGHT_FRAMES * max_w * max_h + 256, MEM_DEVICE},
+        {&c->d_prev_xy, nt * 12 + 64, MEM_DEVICE},   // track coordinates followed by the block -> track order
+        {&c->d_out_xy, nt * 8, MEM_DEVICE},
+        {&c->d_status, nt, MEM_DEVICE},
+        {&c->d_err, nt * 4, MEM_DEVICE},
+        {&c->h_prev_xy, nt * 12 + 64, MEM_PINNED},
+        // LK results: 13 bytes per track, written by the kernel through the device aliases of these mapped pinned buffers (no D2H copies)
+        {&c->h_out_xy, nt * 8, MEM_MAPPED},
+        {&c->h_status, nt, MEM_MAPPED},
+        {&c->h_err, nt * 4, MEM_MAPPED},
+        {&c->d_knn, nt * 16 + 64, MEM_DEVICE},
+        {&c->h_knn, nt * 16 + 64, MEM_PINNED},
+        {&c->h_work, nt * 2, MEM_MAPPED},
+        {&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM, MEM_DEVICE},
+        {&c->d_cells, MAX_CELLS * CELL_STRIDE * 4, MEM_DEVICE},
+        {&c->h_cells, MAX_CELLS * CELL_STRIDE * 4, MEM_PINNED},
+        {&c->d_eig, (size_t)MAX_CELLS * CELL_PIX * sizeof(double), MEM_DEVICE},   // shared by GFTT (f32) and ShiTomasi (f64)
+        {&c->d_cellmax, MAX_CELLS * 8, MEM_DEVICE},
+        {&c->d_spill, (size_t)MAX_CELLS * CELL_PIX * 4, MEM_DEVICE},
+        {&c->d_det_xy, (size_t)MAX_CELLS * MAX_PER_CELL * 8, MEM_DEVICE},
+        {&c->d_det_score, (size_t)MAX_CELLS * MAX_PER_CELL * 8, MEM_DEVICE},
+        {&c->d_det_count, MAX_CELLS * 4, MEM_DEVICE},
+        {&c->d_flags, 16, MEM_DEVICE},
+        {&c->h_det_xy, (size_t)MAX_CELLS * MAX_PER_CELL * 8, MEM_PINNED},
+        {&c->h_det_score, (size_t)MAX_CELLS * MAX_PER_CELL * 8, MEM_PINNED},
+        {&c->h_det_count, MAX_CELLS * 4 + 16, MEM_PINNED},
+    };
+    CK(mem_alloc_table(rows, sizeof(rows) / sizeof(rows[0])));
+    CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
+    CK(hipMemset(c->d_flags, 0, 16));
     for (auto& a : c->lk_work) a.store(0);
     for (auto& a : c->batch_launches) a.store(0);
     for (auto& a : c->subpix_launches) a.store(0);
     for (auto& a : c->clahe_launches) a.store(0);
     for (auto& a : c->remap_launches) a.store(0);
-    CK(hipMalloc(&c->d_geom, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
-    CK(hipMemset(c->d_geom, 0, sizeof(PyrLayout) * pmv_ctx::MAX_GEOM));
-    CK(hipMalloc(&c->d_cells, MAX_CELLS * CELL_STRIDE * 4));
-    CK(hipHostMalloc(&c->h_cells, MAX_CELLS * CELL_STRIDE * 4));
-    CK(hipMalloc(&c->d_eig, (size_t)MAX_CELLS * CELL_PIX * sizeof(double)));   // shared by GFTT (f32) and ShiTomasi (f64)
-    CK(hipMalloc(&c->d_cellmax, MAX_CELLS * 8));
-    CK(hipMalloc(&c->d_spill, (size_t)MAX_CELLS * CELL_PIX * 4));
-    CK(hipMalloc(&c->d_det_xy, (size_t)MAX_CELLS * MAX_PER_CELL * 8));
-    CK(hipMalloc(&c->d_det_score, (size_t)MAX_CELLS * MAX_PER_CELL * 8));
-    CK(hipMalloc(&c->d_det_count, MAX_CELLS * 4));
-    CK(hipMalloc(&c->d_flags, 16));
-    CK(hipMemset(c->d_flags, 0, 16));
-    CK(hipHostMalloc(&c->h_det_xy, (size_t)MAX_CELLS * MAX_PER_CELL * 8));
-    CK(hipHostMalloc(&c->h_det_score, (size_t)MAX_CELLS * MAX_PER_CELL * 8));
-    CK(hipHostMalloc(&c->h_det_count, MAX_CELLS * 4 + 16));
     int rc = backend_create(c);
     if (rc != PMV_OK) { snprintf(g_create_err, sizeof(g_create_err), "%s", c->err); pmv_ctx_destroy(c); return rc; }
-    {   // every buffer a kernel may touch exists (a missed allocation must fail here, not as a GPU fault later)
-        const void* must[] = {c->dm_out_xy, c->dm_status, c->dm_err, c->d_slots, c->d_tight, c->d_prev_xy, c->d_out_xy, c->d_status, c->d_err, c->h_prev_xy, c->h_out_xy, c->h_status, c->h_err,
-                              c->d_cells, c->d_eig, c->d_cellmax, c->d_det_xy, c->d_det_score, c->d_det_count, c->d_flags, c->h_det_xy,
-                              c->h_det_score, c->h_det_count};
-        for (const void* p : must)
-            if (!p) { snprintf(g_create_err, sizeof(g_create_err), "pmv_ctx_create: internal error, a front-end buffer was not allocated"); pmv_ctx_destroy(c); return PMV_ERR_HIP; }
-    }
 #undef CK
     *out = c;
     return PMV_OK;
@@ -163,37 +156,20 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     if (c->s_back) hipStreamSynchronize(c->s_back);
     backend_destroy(c);
     c->prof.destroy();
-    if (c->d_lk_stamps) hipFree(c->d_lk_stamps);
-    if (c->d_geom) hipFree(c->d_geom);
-    if (c->h_work) hipHostFree(c->h_work);
-    if (c->h_lkx) hipHostFree(c->h_lkx);
-    if (c->h_gmask) hipHostFree(c->h_gmask);
-    if (c->d_gmask) hipFree(c->d_gmask);
-    if (c->h_subpix) hipHostFree(c->h_subpix);
-    if (c->h_subpix_tab) hipHostFree(c->h_subpix_tab);
-    if (c->d_subpix_tab) hipFree(c->d_subpix_tab);
-    if (c->h_clahe) hipHostFree(c->h_clahe);
-    if (c->d_clahe) hipFree(c->d_clahe);
-    if (c->d_clahe_lut) hipFree(c->d_clahe_lut);
-    for (auto& m : c->remap_maps) if (m.d) hipFree(m.d);
-    if (c->h_remap) hipHostFree(c->h_remap);
-    if (c->d_remap) hipFree(c->d_remap);
-    if (c->d_remap_scratch) hipFree(c->d_remap_scratch);
-    if (c->d_knn) hipFree(c->d_knn);
-    if (c->h_knn) hipHostFree(c->h_knn);
-    hipFree(c->d_slots); hipFree(c->d_prev_xy); hipFree(c->d_out_xy); hipFree(c->d_status); hipFree(c->d_err);
-    hipHostFree(c->h_prev_xy); hipHostFree(c->h_out_xy); hipHostFree(c->h_status); hipHostFree(c->h_err);
-    hipFree(c->d_tight);
-    hipFree(c->d_cells); hipFree(c->d_eig); hipFree(c->d_cellmax); hipFree(c->d_det_xy); hipFree(c->d_det_score);
-    hipFree(c->d_det_count); hipFree(c->d_flags); hipFree(c->d_spill);
-    hipHostFree(c->h_det_xy); hipHostFree(c->h_det_score); hipHostFree(c->h_det_count); hipHostFree(c->h_cells);
     if (c->s_front) hipStreamDestroy(c->s_front);
     if (c->s_back) hipStreamDestroy(c->s_back);
-    delete c;
+    delete c;   // the buffers go with it: every stream that could use one was synchronised above
 }
 
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
+
+int pmv_debug_mem_live(long long* out2) {
+    pmv_ctx* ctx = nullptr;
+    REQ(out2, PMV_ERR_INVALID, "pmv_debug_mem_live: null argument");
+    for (int i = 0; i < 2; i++) out2[i] = g_mem_live[i].load();
+    return PMV_OK;
+}
 
 int pmv_sync(pmv_ctx* ctx) {
     REQ(ctx, PMV_ERR_INVALID, "null ctx");
@@ -208,6 +184,31 @@ int pmv_sync(pmv_ctx* ctx) {
 static int build_levels_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n, const PyrLayout& L, const uint8_t* tight = nullptr) {
     CKC(launch_pad_level0(stream, ctx->d_slots, L, first_slot, n, tight));
     for (int l = 1; l < L.n_levels; l++) CKC(launch_pyrdown(stream, ctx->d_slots, L, l, first_slot, n));
+    return PMV_OK;
+}
+
+// build_levels_on over slots [first_slot, first_slot + n): consecutive slots of equal geometry go into one launch per level. With `who`, an
+// empty slot is that call's PMV_ERR_INVALID and every built run is marked SLOT_BUILT at once.
+static int build_runs_on(pmv_ctx* ctx, hipStream_t stream, int first_slot, int n, const char* who = nullptr) {
+    int i = 0;
+    while (i < n) {
+        const PyrLayout& L = ctx->slot_layout[first_slot + i];
+        if (who) REQ(ctx->slot_state[first_slot + i] != SLOT_EMPTY, PMV_ERR_INVALID, "%s: slot %d was never staged", who, first_slot + i);
+        int j = i + 1;
+        while (j < n && ctx->slot_layout[first_slot + j].w[0] == L.w[0] && ctx->slot_layout[first_slot + j].h[0] == L.h[0]) j++;
+        if (const int rc = build_levels_on(ctx, stream, first_slot + i, j - i, L)) return rc;
+        if (who) for (int k = i; k < j; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
+        i = j;
+    }
+    return PMV_OK;
+}
+
+// the tail pmv_frame_upload and pmv_frame_upload_bgr share once the gray frame is in the landing area
+static int upload_from_tight(pmv_ctx* ctx, int slot, const PyrLayout& L) {
+    if (const int rc = build_levels_on(ctx, ctx->s_front, slot, 1, L, ctx->d_tight)) return rc;
+    CKC(hipStreamSynchronize(ctx->s_front));   // the host buffer may be reused by the caller
+    ctx->slot_layout[slot] = L;
+    ctx->slot_state[slot] = SLOT_BUILT;
     return PMV_OK;
 }
 
@@ -287,11 +288,10 @@ int pmv_set_lk_params(pmv_ctx* ctx, const pmv_lk_params* p) {
         CKC(hipStreamSynchronize(ctx->s_back));
         const PyrLayout cap = make_layout(ctx->max_w, ctx->max_h, p->win, p->max_level);
         const size_t need = (size_t)cap.slot_bytes * ctx->n_slots;
-        if (need > ctx->slots_alloc) {   // (a failed allocation leaves storage, pitch and setting as they were)
-            uint8_t* d = nullptr;
-            CKC(hipMalloc(&d, need));
-            CKC(hipFree(ctx->d_slots));
-            ctx->d_slots = d; ctx->slots_alloc = need;
+        if (need > ctx->d_slots.cap) {   // new before old, not ensure(): a failed allocation leaves storage, pitch and setting as they were
+            Buf<uint8_t> d;
+            CKC(d.ensure(need));
+            ctx->d_slots = std::move(d);
         }
         ctx->cap = cap;
         ctx->slot_layout.assign(ctx->n_slots, PyrLayout());
@@ -317,19 +317,7 @@ int pmv_frames_build(pmv_ctx* ctx, int first_slot, int n) {
     tl_prof = &ctx->prof;
     REQ(first_slot >= 0 && n >= 1 && first_slot + n <= ctx->n_slots, PMV_ERR_CAPACITY, "pmv_frames_build: slot range");
     CKC(hipSetDevice(ctx->device));
-    // consecutive slots with identical geometry are built in one batched launch per level
-    int i = 0;
-    while (i < n) {
-        const PyrLayout& L = ctx->slot_layout[first_slot + i];
-        REQ(ctx->slot_state[first_slot + i] != SLOT_EMPTY, PMV_ERR_INVALID, "pmv_frames_build: slot %d was never staged", first_slot + i);
-        int j = i + 1;
-        while (j < n && ctx->slot_layout[first_slot + j].w[0] == L.w[0] && ctx->slot_layout[first_slot + j].h[0] == L.h[0]) j++;
-        int rc = build_levels_on(ctx, ctx->s_front, first_slot + i, j - i, L);
-        if (rc) return rc;
-        for (int k = i; k < j; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
-        i = j;
-    }
-    return PMV_OK;
+    return build_runs_on(ctx, ctx->s_front, first_slot, n, "pmv_frames_build");
 }
 
 int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, int stride) {
@@ -340,12 +328,7 @@ int pmv_frame_upload(pmv_ctx* ctx, int slot, const uint8_t* gray, int w, int h, 
     CKC(hipSetDevice(ctx->device));
     PyrLayout L = layout_for(ctx, w, h);
     CKC(hipMemcpy2DAsync(ctx->d_tight, (size_t)w, gray, stride, w, h, hipMemcpyHostToDevice, ctx->s_front));
-    int rc = build_levels_on(ctx, ctx->s_front, slot, 1, L, ctx->d_tight);
-    if (rc) return rc;
-    CKC(hipStreamSynchronize(ctx->s_front));   // the host buffer may be reused by the caller
-    ctx->slot_layout[slot] = L;
-    ctx->slot_state[slot] = SLOT_BUILT;
-    return PMV_OK;
+    return upload_from_tight(ctx, slot, L);
 }
 
 // Frame::Frame(file) + Frame::init for a COLOUR image (Frame.cpp:33,40-41: imread(IMREAD_COLOR) gives BGR, cvtColor(BGR2GRAY) the u8 `bw`
@@ -361,12 +344,7 @@ int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int 
     uint8_t* d_bgr = ctx->d_tight + (size_t)ctx->max_w * ctx->max_h;
     CKC(hipMemcpy2DAsync(d_bgr, (size_t)3 * w, bgr, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, ctx->s_front));
     CKC(launch_bgr2gray(ctx->s_front, d_bgr, w, h, 3 * w, ctx->d_tight));
-    int rc = build_levels_on(ctx, ctx->s_front, slot, 1, L, ctx->d_tight);
-    if (rc) return rc;
-    CKC(hipStreamSynchronize(ctx->s_front));
-    ctx->slot_layout[slot] = L;
-    ctx->slot_state[slot] = SLOT_BUILT;
-    return PMV_OK;
+    return upload_from_tight(ctx, slot, L);
 }
 
 }  // extern "C"
@@ -394,9 +372,7 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
     CKC(hipSetDevice(ctx->device));
     constexpr int CH = pmv_ctx::CLAHE_CHUNK;
     constexpr size_t tab_bytes = (size_t)CH * (sizeof(ClaheRec) + sizeof(PyrLayout));
-    if (!ctx->h_clahe) CKC(hipHostMalloc(&ctx->h_clahe, tab_bytes, hipHostMallocDefault));
-    if (!ctx->d_clahe) CKC(hipMalloc(&ctx->d_clahe, tab_bytes));
-    if (!ctx->d_clahe_lut) CKC(hipMalloc(&ctx->d_clahe_lut, (size_t)CH * CLAHE_LUT_MAX));
+    CKC(ctx->h_clahe.ensure(tab_bytes)); CKC(ctx->d_clahe.ensure(tab_bytes)); CKC(ctx->d_clahe_lut.ensure((size_t)CH * CLAHE_LUT_MAX));
     ClaheRec* recs = (ClaheRec*)ctx->h_clahe;
     PyrLayout* tab = (PyrLayout*)(recs + CH);
     for (int i0 = 0; i0 < n; i0 += CH) {
@@ -420,15 +396,8 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
         ctx->clahe_launches[0]++;
         CKC(hipStreamSynchronize(ctx->s_front));   // (the next chunk rewrites the pinned tables)
     }
-    // the REFLECT_101 frame of level 0 in place and the levels above: consecutive slots of one geometry in one launch per level
-    int i = 0;
-    while (i < n) {
-        const PyrLayout& L = ctx->slot_layout[first_slot + i];
-        int j = i + 1;
-        while (j < n && ctx->slot_layout[first_slot + j].w[0] == L.w[0] && ctx->slot_layout[first_slot + j].h[0] == L.h[0]) j++;
-        if (const int rc_ = build_levels_on(ctx, ctx->s_front, first_slot + i, j - i, L)) return rc_;
-        i = j;
-    }
+    // the REFLECT_101 frame of level 0 in place and the levels above
+    if (const int rc_ = build_runs_on(ctx, ctx->s_front, first_slot, n)) return rc_;
     CKC(hipStreamSynchronize(ctx->s_front));
     for (int k = 0; k < n; k++) ctx->slot_state[first_slot + k] = SLOT_BUILT;
     return PMV_OK;
@@ -464,10 +433,10 @@ int pmv_remap_map_create(pmv_ctx* ctx, int w, int h, const float* map_x, const f
     const size_t bytes = remap_map_bytes(w, h);
     std::vector<uint32_t> packed(bytes / 4);
     remap_pack(map_x, map_y, w, h, (uint8_t*)packed.data());
-    uint8_t* d = nullptr;
-    CKC(hipMalloc(&d, bytes));
+    Buf<uint8_t>& d = ctx->remap_mem[id];
+    CKC(d.ensure(bytes));
     const hipError_t e = hipMemcpy(d, packed.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); set_err(ctx, "pmv_remap_map_create: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
+    if (e != hipSuccess) { (void)d.release(); set_err(ctx, "pmv_remap_map_create: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
     ctx->remap_maps[id].w = w; ctx->remap_maps[id].h = h; ctx->remap_maps[id].d = d;
     *out_id = id;
     return PMV_OK;
@@ -482,7 +451,7 @@ int pmv_remap_map_destroy(pmv_ctx* ctx, int id) {
     REQ(id >= 0 && id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[id].d, PMV_ERR_INVALID, "pmv_remap_map_destroy: map %d does not exist", id);
     CKC(hipSetDevice(ctx->device));
     CKC(hipStreamSynchronize(ctx->s_front));
-    CKC(hipFree(ctx->remap_maps[id].d));
+    CKC(ctx->remap_mem[id].release());
     ctx->remap_maps[id] = pmv_ctx::RemapMap();
     return PMV_OK;
 }
@@ -506,9 +475,7 @@ int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border
     CKC(hipSetDevice(ctx->device));
     constexpr int CH = pmv_ctx::REMAP_CHUNK;
     constexpr size_t tab_bytes = (size_t)CH * (sizeof(RemapRec) + sizeof(PyrListEntry) + sizeof(PyrLayout));
-    if (!ctx->h_remap) CKC(hipHostMalloc(&ctx->h_remap, tab_bytes, hipHostMallocDefault));
-    if (!ctx->d_remap) CKC(hipMalloc(&ctx->d_remap, tab_bytes));
-    if (!ctx->d_remap_scratch) CKC(hipMalloc(&ctx->d_remap_scratch, (size_t)CH * remap_frame_bytes(ctx->max_w, ctx->max_h)));
+    CKC(ctx->h_remap.ensure(tab_bytes)); CKC(ctx->d_remap.ensure(tab_bytes)); CKC(ctx->d_remap_scratch.ensure((size_t)CH * remap_frame_bytes(ctx->max_w, ctx->max_h)));
     RemapRec* recs = (RemapRec*)ctx->h_remap;
     PyrListEntry* list = (PyrListEntry*)(recs + CH);
     PyrLayout* tab = (PyrLayout*)(list + CH);
@@ -598,29 +565,15 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     memcpy(ctx->h_prev_xy, prev_xy, (size_t)n * 8);
-    // XCD-aware block order: workgroup b runs on XCD b % 8 and every XCD has its own L2, so the tracks (which arrive in hash
-    // order, i.e. spatially random) are dealt out by x position: the k-th track of equal-count stripe s goes to block 8k + s.
-    // Each L2 then fetches one vertical stripe of the two pyramids instead of all of them (measured: 5x less HBM traffic).
-    int* order = (int*)(ctx->h_prev_xy + (size_t)2 * n);
     const int nb = (n + 7) / 8 * 8;
-    {
-        static thread_local std::vector<std::pair<float, int>> byx;
-        byx.resize(n);
-        for (int i = 0; i < n; i++) byx[i] = {prev_xy[2 * i], i};
-        std::sort(byx.begin(), byx.end());
-        for (int b = 0; b < nb; b++) order[b] = -1;
-        for (int i = 0; i < n; i++) {
-            const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);   // stripe and its first sorted index
-            order[(i - first) * 8 + s8] = byx[i].second;
-        }
-    }
+    lk_xcd_order(prev_xy, n, (int*)(ctx->h_prev_xy + (size_t)2 * n));
     CKC(hipMemcpyAsync(ctx->d_prev_xy, ctx->h_prev_xy, (size_t)n * 8 + (size_t)nb * 4, hipMemcpyHostToDevice, ctx->s_front));
     LKParams P = lk_launch_params(ctx);
     static const bool lk_stamps = getenv("PMV_LK_STAMPS") != nullptr;   // read once per process
-    if (!ctx->d_lk_stamps && lk_stamps) { CKC(hipMalloc(&ctx->d_lk_stamps, 16 * 8)); CKC(hipMemset(ctx->d_lk_stamps, 0, 16 * 8)); }
+    if (!ctx->d_lk_stamps && lk_stamps) { CKC(ctx->d_lk_stamps.ensure(16 * 8)); CKC(hipMemset(ctx->d_lk_stamps, 0, 16 * 8)); }
     P.stamps = ctx->d_lk_stamps;
     CKC(launch_lk(ctx->s_front, ctx->d_slots + (size_t)prev_slot * L.slot_bytes, ctx->d_slots + (size_t)next_slot * L.slot_bytes,
-                  L, ctx->d_prev_xy, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, P, ctx->dm_out_xy, ctx->dm_status, ctx->dm_err, ctx->dm_work));
+                  L, ctx->d_prev_xy, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, P, ctx->h_out_xy.dm(), ctx->h_status.dm(), ctx->h_err.dm(), ctx->h_work.dm()));
     CKC(hipStreamSynchronize(ctx->s_front));   // the kernel wrote positions / status / err straight into mapped pinned memory
     memcpy(out_xy, ctx->h_out_xy, (size_t)n * 8);
     memcpy(out_status, ctx->h_status, (size_t)n);
@@ -641,31 +594,17 @@ static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_s
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     const size_t nt = (size_t)ctx->max_tracks;
-    if (!ctx->h_lkx) {
-        CKC(hipHostMalloc(&ctx->h_lkx, nt * 21 + 64, hipHostMallocMapped | hipHostMallocCoherent));
-        CKC(hipHostGetDevicePointer((void**)&ctx->dm_lkx, ctx->h_lkx, 0));
-    }
+    CKC(ctx->h_lkx.ensure(nt * 21 + 64));
     const size_t off_bxy = nt * 8, off_berr = nt * 16, off_bst = nt * 20;
     if (flags & PMV_LK_USE_INITIAL_FLOW) memcpy(ctx->h_lkx, next_xy, (size_t)n * 8);
     memcpy(ctx->h_prev_xy, prev_xy, (size_t)n * 8);
-    int* order = (int*)(ctx->h_prev_xy + (size_t)2 * n);   // the XCD-aware block order of pmv_lk_track
     const int nb = (n + 7) / 8 * 8;
-    {
-        static thread_local std::vector<std::pair<float, int>> byx;
-        byx.resize(n);
-        for (int i = 0; i < n; i++) byx[i] = {prev_xy[2 * i], i};
-        std::sort(byx.begin(), byx.end());
-        for (int b = 0; b < nb; b++) order[b] = -1;
-        for (int i = 0; i < n; i++) {
-            const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);
-            order[(i - first) * 8 + s8] = byx[i].second;
-        }
-    }
+    lk_xcd_order(prev_xy, n, (int*)(ctx->h_prev_xy + (size_t)2 * n));
     CKC(hipMemcpyAsync(ctx->d_prev_xy, ctx->h_prev_xy, (size_t)n * 8 + (size_t)nb * 4, hipMemcpyHostToDevice, ctx->s_front));
     const LKParams P = lk_launch_params(ctx);
     CKC(launch_lk_ex(ctx->s_front, ctx->d_slots + (size_t)prev_slot * L.slot_bytes, ctx->d_slots + (size_t)next_slot * L.slot_bytes, L, ctx->d_prev_xy,
-                     (const float*)ctx->dm_lkx, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->dm_out_xy, ctx->dm_status,
-                     ctx->dm_err, ctx->dm_work, (float*)(ctx->dm_lkx + off_bxy), ctx->dm_lkx + off_bst, (float*)(ctx->dm_lkx + off_berr)));
+                     (const float*)ctx->h_lkx.dm(), (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->h_out_xy.dm(), ctx->h_status.dm(),
+                     ctx->h_err.dm(), ctx->h_work.dm(), (float*)(ctx->h_lkx.dm() + off_bxy), ctx->h_lkx.dm() + off_bst, (float*)(ctx->h_lkx.dm() + off_berr)));
     CKC(hipStreamSynchronize(ctx->s_front));
     memcpy(next_xy, ctx->h_out_xy, (size_t)n * 8);
     memcpy(out_status, ctx->h_status, (size_t)n);
@@ -764,6 +703,27 @@ static int check_cells(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
     REQ(ctx, PMV_ERR_INVALID, "detect: null argument");
     return detect_check(ctx, true, slot, cells, n_cells, max_per_cell);
 }
+// What the three detector entry points do around their launch: the packed cell records (ctx->h_cells) go up, the overflow bits are cleared
+// (they are per call: one overflow must not poison later calls), `launch` enqueues the kernels, then lists, counts and flags come back in one
+// wait. out_score may be null. overflow_who: the call whose "no limit" form fails with PMV_ERR_OVERFLOW, outputs untouched.
+template <class Launch>
+static int detect_run(pmv_ctx* ctx, int n_cells, int per_cell, Launch launch, const char* overflow_who, int* out_xy, double* out_score, int* out_count) {
+    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
+    CKC(hipMemsetAsync(ctx->d_flags, 0, 16, ctx->s_front));
+    CKC(launch());
+    const size_t nxy = (size_t)n_cells * per_cell * 8;
+    CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nxy, hipMemcpyDeviceToHost, ctx->s_front));
+    if (out_score) CKC(hipMemcpyAsync(ctx->h_det_score, ctx->d_det_score, nxy, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipMemcpyAsync(ctx->h_det_count, ctx->d_det_count, (size_t)n_cells * 4, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipMemcpyAsync(ctx->h_det_count + MAX_CELLS, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->s_front));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    REQ(!overflow_who || (ctx->h_det_count[MAX_CELLS] & 4) == 0, PMV_ERR_OVERFLOW, "%s: more than %d corners in a cell with max_per_cell <= 0 (no limit)", overflow_who, MAX_PER_CELL);
+    memcpy(out_xy, ctx->h_det_xy, nxy);
+    if (out_score) memcpy(out_score, ctx->h_det_score, nxy);
+    memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
+    return PMV_OK;
+}
+
 extern "C" {
 
 int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
@@ -779,27 +739,18 @@ int pmv_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
     CKC(hipSetDevice(ctx->device));
     const PyrLayout& L = ctx->slot_layout[slot];
     pack_cells(ctx->h_cells, cells, n_cells, slot);
-    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
-    CKC(hipMemsetAsync(ctx->d_flags, 0, 16, ctx->s_front));   // overflow bits are per call: one overflow must not poison later calls
     static const bool gftt_dbg = getenv("PMV_GFTT_DBG") != nullptr;
-    if (gftt_dbg) { const int on = 0x40000000; CKC(hipMemcpyAsync(ctx->d_flags, &on, 4, hipMemcpyHostToDevice, ctx->s_front)); }
-    CKC(launch_gftt(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, max_per_cell, quality,
-                    min_dist, unlimited, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill));
-    const size_t nxy = (size_t)n_cells * max_per_cell * 8;
-    CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nxy, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count, ctx->d_det_count, (size_t)n_cells * 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count + MAX_CELLS, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipStreamSynchronize(ctx->s_front));
-    if (gftt_dbg) {
+    rc = detect_run(ctx, n_cells, max_per_cell, [&] {
+        if (gftt_dbg) { static const int on = 0x40000000; if (hipError_t e = hipMemcpyAsync(ctx->d_flags, &on, 4, hipMemcpyHostToDevice, ctx->s_front)) return e; }
+        return launch_gftt(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, max_per_cell, quality, min_dist, unlimited, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax,
+                           ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill);
+    }, "pmv_detect_gftt", out_xy, nullptr, out_count);
+    if (gftt_dbg && (rc == PMV_OK || rc == PMV_ERR_OVERFLOW)) {
         int f[4];
         CKC(hipMemcpy(f, ctx->d_flags, 16, hipMemcpyDeviceToHost));
         fprintf(stderr, "[gftt-dbg] cell 0: %d raw records, %d above the threshold; cycles: compaction %d, key set-up %d, rounds %d\n", f[0] & 0xffff, (f[0] >> 16) & 0x3fff, f[1], f[2], f[3]);
-        ctx->h_det_count[MAX_CELLS] &= ~0x40000000;
     }
-    REQ((ctx->h_det_count[MAX_CELLS] & 4) == 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt: more than %d corners in a cell with max_per_cell <= 0 (no limit)", MAX_PER_CELL);
-    memcpy(out_xy, ctx->h_det_xy, nxy);
-    memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
-    return PMV_OK;
+    return rc;
 }
 
 // cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector and k. The reference's arguments (3, false, no mask) are
@@ -822,26 +773,14 @@ int pmv_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
     const PyrLayout& L = ctx->slot_layout[slot];
     pack_cells(ctx->h_cells, cells, n_cells, slot);
     if (mask) {
-        if (!ctx->h_gmask) {
-            CKC(hipHostMalloc(&ctx->h_gmask, (size_t)MAX_CELLS * CELL_PIX, hipHostMallocDefault));
-            CKC(hipMalloc(&ctx->d_gmask, (size_t)MAX_CELLS * CELL_PIX));
-        }
+        CKC(ctx->h_gmask.ensure((size_t)MAX_CELLS * CELL_PIX)); CKC(ctx->d_gmask.ensure((size_t)MAX_CELLS * CELL_PIX));
         const size_t nb = gftt_pack_mask(ctx->h_gmask, 0, ctx->h_cells, cells, n_cells, mask, mask_stride);
         CKC(hipMemcpyAsync(ctx->d_gmask, ctx->h_gmask, nb, hipMemcpyHostToDevice, ctx->s_front));
     }
-    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
-    CKC(hipMemsetAsync(ctx->d_flags, 0, 16, ctx->s_front));
-    CKC(launch_gftt_ex(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, cap, p->quality, p->min_dist, unlimited, gftt_ext(p->block_size, p->use_harris, p->k),
-                       mask ? ctx->d_gmask : nullptr, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill));
-    const size_t nxy = (size_t)n_cells * cap * 8;
-    CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nxy, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count, ctx->d_det_count, (size_t)n_cells * 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count + MAX_CELLS, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipStreamSynchronize(ctx->s_front));
-    REQ((ctx->h_det_count[MAX_CELLS] & 4) == 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt_ex: more than %d corners in a cell with max_per_cell <= 0 (no limit)", MAX_PER_CELL);
-    memcpy(out_xy, ctx->h_det_xy, nxy);
-    memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
-    return PMV_OK;
+    return detect_run(ctx, n_cells, cap, [&] {
+        return launch_gftt_ex(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, cap, p->quality, p->min_dist, unlimited, gftt_ext(p->block_size, p->use_harris, p->k),
+                              mask ? ctx->d_gmask.get() : nullptr, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill);
+    }, "pmv_detect_gftt_ex", out_xy, nullptr, out_count);
 }
 // diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex through the general kernels as well (no result changes)
 int pmv_debug_gftt_general(pmv_ctx* ctx, int on) {
@@ -858,12 +797,7 @@ int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     const size_t nt = (size_t)ctx->max_tracks;
-    if (!ctx->h_subpix) {
-        CKC(hipHostMalloc(&ctx->h_subpix, nt * 26 + 64, hipHostMallocMapped | hipHostMallocCoherent));
-        CKC(hipHostGetDevicePointer((void**)&ctx->dm_subpix, ctx->h_subpix, 0));
-    }
-    if (!ctx->h_subpix_tab) CKC(hipHostMalloc(&ctx->h_subpix_tab, SUBPIX_TABLE_MAX * sizeof(float), hipHostMallocDefault));
-    if (!ctx->d_subpix_tab) CKC(hipMalloc(&ctx->d_subpix_tab, SUBPIX_TABLE_MAX * sizeof(float)));
+    CKC(ctx->h_subpix.ensure(nt * 26 + 64)); CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
     int zw, zh;
     subpix_zero_zone(p, &zw, &zh);
     const int key[4] = {p->win_w, p->win_h, zw, zh};
@@ -877,8 +811,8 @@ int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix
     SubpixRec* rec = (SubpixRec*)ctx->h_subpix;
     for (int i = 0; i < n; i++) rec[i] = SubpixRec{xy[2 * i], xy[2 * i + 1], slot, 0};
     const SubpixArgs A{p->win_w, p->win_h, p->max_iter, p->eps * p->eps};
-    CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], (const SubpixRec*)ctx->dm_subpix, n, ctx->d_subpix_tab, A, (float*)(ctx->dm_subpix + off_xy),
-                             ctx->dm_subpix + off_it, ctx->dm_subpix + off_fl));
+    CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], (const SubpixRec*)ctx->h_subpix.dm(), n, ctx->d_subpix_tab, A, (float*)(ctx->h_subpix.dm() + off_xy),
+                             ctx->h_subpix.dm() + off_it, ctx->h_subpix.dm() + off_fl));
     ctx->subpix_launches[0]++;
     CKC(hipStreamSynchronize(ctx->s_front));
     memcpy(xy, ctx->h_subpix + off_xy, (size_t)n * 8);
@@ -906,20 +840,10 @@ int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, 
     CKC(hipSetDevice(ctx->device));
     const PyrLayout& L = ctx->slot_layout[slot];
     pack_cells(ctx->h_cells, cells, n_cells, slot);
-    CKC(hipMemcpyAsync(ctx->d_cells, ctx->h_cells, (size_t)n_cells * CELL_STRIDE * 4, hipMemcpyHostToDevice, ctx->s_front));
-    CKC(hipMemsetAsync(ctx->d_flags, 0, 16, ctx->s_front));
-    CKC(launch_shitomasi(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, max_per_cell, quality,
-                         ctx->d_eig, (unsigned long long*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_score, ctx->d_det_count, ctx->d_flags, ctx->d_spill));
-    const size_t nxy = (size_t)n_cells * max_per_cell * 8;
-    CKC(hipMemcpyAsync(ctx->h_det_xy, ctx->d_det_xy, nxy, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_score, ctx->d_det_score, nxy, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count, ctx->d_det_count, (size_t)n_cells * 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipMemcpyAsync(ctx->h_det_count + MAX_CELLS, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->s_front));
-    CKC(hipStreamSynchronize(ctx->s_front));
-    memcpy(out_xy, ctx->h_det_xy, nxy);
-    memcpy(out_score, ctx->h_det_score, nxy);
-    memcpy(out_count, ctx->h_det_count, (size_t)n_cells * 4);
-    return PMV_OK;
+    return detect_run(ctx, n_cells, max_per_cell, [&] {
+        return launch_shitomasi(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, max_per_cell, quality, ctx->d_eig, (unsigned long long*)ctx->d_cellmax, ctx->d_det_xy,
+                                ctx->d_det_score, ctx->d_det_count, ctx->d_flags, ctx->d_spill);
+    }, nullptr, out_xy, out_score, out_count);
 }
 
 // ---- per-kernel HIP-event timing -------------------------------------------------------------------------------------

@@ -294,7 +294,7 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
     KnnRound rec;
     rec.src_off = (unsigned long long)src_slot * L.slot_bytes; rec.cmp_off = (unsigned long long)cmp_slot * L.slot_bytes;
     rec.src_xy = (const int*)(d + 64); rec.cmp_xy = rec.src_xy + 2 * (size_t)n;
-    rec.out_best = (int*)ctx->dm_out_xy; rec.out_err = ctx->dm_err;
+    rec.out_best = (int*)ctx->h_out_xy.dm(); rec.out_err = ctx->h_err.dm();
     rec.n = n; rec.m = m; rec.nn_window = knn_pack(n_neighbours, window); rec.geom = 0;
     memcpy(h, &rec, sizeof(rec));
     memcpy(h + 64, src_xy, (size_t)n * 8);

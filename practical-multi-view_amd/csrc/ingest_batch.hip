@@ -61,10 +61,9 @@ struct BatchIngest {
     hipStream_t stream = nullptr;
     std::vector<hipEvent_t> ev;
     hipEvent_t copied[NBUF] = {};   // copy form: the round's DMA out of its staging buffer is done
-    uint8_t* h_stage = nullptr;   // NBUF x buf_bytes, pinned + mapped
-    uint8_t* dm_stage = nullptr;  // its device address
-    uint8_t* d_land = nullptr;    // NBUF x buf_bytes in HBM (copy form and staged feeds)
-    size_t buf_bytes = 0, land_bytes = 0;
+    Buf<uint8_t> h_stage{MEM_MAPPED};   // NBUF x buf_bytes, pinned + mapped
+    Buf<uint8_t> d_land;                // NBUF x buf_bytes in HBM (copy form and staged feeds: made by the first that needs it)
+    size_t buf_bytes = 0;
     std::unique_ptr<std::atomic<long long>[]> slot_rec;   // per slot: (frame << 32) | round of its last enqueued build, or NONE / pending(b)
     std::mutex ev_mu;             // hipEventRecord / growth of `ev` (feeder thread) vs hipStreamWaitEvent (readers)
     // one feed
@@ -168,7 +167,7 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         uint8_t* blk = g->h_stage + (size_t)buf * g->buf_bytes;
         PyrListEntry* tab = (PyrListEntry*)blk;
         // device address of the round's block as the kernels see it: the landing buffer (copy) or the mapped staging buffer
-        const uint8_t* dblk = g->copy_mode ? g->d_land + (size_t)buf * g->buf_bytes : g->dm_stage + (size_t)buf * g->buf_bytes;
+        const uint8_t* dblk = g->copy_mode ? g->d_land + (size_t)buf * g->buf_bytes : g->h_stage.dm() + (size_t)buf * g->buf_bytes;
         // Consecutive slots, all in place or one sequence's consecutive frames (every round of a bracket): the range form, no table lookup in
         // the kernels; in the copy form a pinned source is then DMA'd straight into the landing buffer.
         const BatchIngest::Seq& S0 = g->seq[take[0].first];
@@ -351,18 +350,13 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
     const char* mode = getenv("PMV_BATCH_INGEST");
     g->copy_mode = !host || (mode ? !strcmp(mode, "copy") : kind == FEED_BRACKET);
     g->dma_release = g->copy_mode && kind != FEED_STREAMED;   // (a streamed batch keeps the form it was measured with)
-    if (g->buf_bytes < need) {
-        if (g->h_stage) { CKC(hipHostFree(g->h_stage)); g->h_stage = nullptr; }
-        if (g->d_land) { CKC(hipFree(g->d_land)); g->d_land = nullptr; g->land_bytes = 0; }
+    if (g->buf_bytes < need) {   // both buffers are NBUF x buf_bytes: a landing area of the old size goes with the old staging
         g->buf_bytes = 0;
-        CKC(hipHostMalloc(&g->h_stage, BatchIngest::NBUF * need, hipHostMallocMapped | hipHostMallocCoherent));
-        CKC(hipHostGetDevicePointer((void**)&g->dm_stage, g->h_stage, 0));
+        CKC(g->d_land.release());
+        CKC(g->h_stage.ensure(BatchIngest::NBUF * need));
         g->buf_bytes = need;
     }
-    if (g->copy_mode && g->land_bytes < g->buf_bytes) {
-        CKC(hipMalloc(&g->d_land, BatchIngest::NBUF * g->buf_bytes));
-        g->land_bytes = g->buf_bytes;
-    }
+    if (g->copy_mode) CKC(g->d_land.ensure(BatchIngest::NBUF * g->buf_bytes));
     g->ctx = ctx; g->B = B;
     // every slot of the feed carries its sequence's geometry and counts as built from here on: its readers wait for its round in slot_ready.
     // The first sequence that covers a slot builds it.
@@ -442,8 +436,6 @@ void batch_ingest_destroy(BatchIngest*& g) {
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
     for (auto& ev : g->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : g->copied) if (ev) (void)hipEventDestroy(ev);
-    if (g->h_stage) (void)hipHostFree(g->h_stage);
-    if (g->d_land) (void)hipFree(g->d_land);
     delete g;
     g = nullptr;
 }

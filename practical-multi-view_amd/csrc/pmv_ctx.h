@@ -2,8 +2,11 @@
 #pragma once
 #include <atomic>
 #include "pmv_device.h"
+#include "pmv_mem.h"
 #include "pmv_prof.h"
 #include "../../include/pmv_hip.h"
+#include <algorithm>
+#include <utility>
 #include <vector>
 #include <mutex>
 
@@ -36,13 +39,13 @@ struct pmv_ctx {
     pmv::PyrLayout cap;                       // geometry of the largest frame; cap.slot_bytes = slot pitch
     std::vector<pmv::PyrLayout> slot_layout;  // per slot: geometry of the frame it holds ...
     std::vector<uint8_t> slot_state;          // ... and what of it is there (pmv::SlotState)
-    uint8_t* d_slots = nullptr;
+    pmv::Buf<uint8_t> d_slots;                // cap >= cap.slot_bytes * n_slots; grows when pmv_set_lk_params asks for a deeper pyramid
     // Geometry table of the batched launches (pmv_device.h): one PyrLayout per distinct frame size of the current batched run, slot_bytes =
     // the capacity pitch; host mirror and device copy. Rewritten by run_batch before its feeder and sequence threads start (the context is
     // synchronised there); during the run it is only read - by the combiners and the feeder on the host, by the kernels through scalar loads.
     static constexpr int MAX_GEOM = 256;      // (a batch has at most 256 sequences)
     std::vector<pmv::PyrLayout> geom;
-    pmv::PyrLayout* d_geom = nullptr;
+    pmv::Buf<pmv::PyrLayout> d_geom;
     int geom_index(int w, int h) const { for (size_t i = 0; i < geom.size(); i++) if (geom[i].w[0] == w && geom[i].h[0] == h) return (int)i; return -1; }
     // launches of the batched legs since the context was created: k_lk_batch, k_knn_round (combiners), k_pad_level0[_bgr], k_pyrdown (feeder of
     // pmv_pipeline_run_batch[_streamed]) - pmv_debug_batch_launches; the profiler's per-class event pools are not made for two LK lanes
@@ -50,41 +53,39 @@ struct pmv_ctx {
     // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames, or a third as many BGR ones (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;
-    uint8_t* d_tight = nullptr;
+    pmv::Buf<uint8_t> d_tight;
     // LK
-    float *d_prev_xy = nullptr, *d_out_xy = nullptr, *d_err = nullptr;
-    uint8_t* d_status = nullptr;
-    float *h_prev_xy = nullptr, *h_out_xy = nullptr, *h_err = nullptr;
-    uint8_t* h_status = nullptr;
-    float *dm_out_xy = nullptr, *dm_err = nullptr;   // device aliases of the mapped pinned result buffers
-    uint8_t* dm_status = nullptr;
-    int *h_knn = nullptr, *d_knn = nullptr;      // kNN matcher coordinates: [src 2n | cmp 2m] ints, 2 * max_tracks pairs
-    unsigned long long* d_lk_stamps = nullptr;   // diagnostic (PMV_LK_STAMPS=1)
-    uint16_t* h_work = nullptr; uint16_t* dm_work = nullptr;   // per-track LK work of pmv_lk_track (mapped pinned, see launch_lk)
+    pmv::Buf<float> d_prev_xy, d_out_xy, d_err;
+    pmv::Buf<uint8_t> d_status;
+    pmv::Buf<float> h_prev_xy, h_out_xy, h_err;  // h_out_xy, h_status, h_err: mapped pinned, the kernels write the results through .dm()
+    pmv::Buf<uint8_t> h_status;
+    pmv::Buf<int> h_knn, d_knn;                  // kNN matcher coordinates: [src 2n | cmp 2m] ints, 2 * max_tracks pairs
+    pmv::Buf<unsigned long long> d_lk_stamps;    // diagnostic (PMV_LK_STAMPS=1), made by the first LK call that finds it set
+    pmv::Buf<uint16_t> h_work;                   // per-track LK work of pmv_lk_track (mapped pinned, see launch_lk)
     // pmv_lk_track_ex / _fb: the extra inputs and outputs, one mapped pinned block made by the first such call (a context that never makes
     // one pays nothing): [initial flow 2 nt floats | back positions 2 nt floats | back err nt floats | back status nt bytes], nt = max_tracks
-    uint8_t* h_lkx = nullptr; uint8_t* dm_lkx = nullptr;
+    pmv::Buf<uint8_t> h_lkx{pmv::MEM_MAPPED};
     std::atomic<unsigned long long> lk_work[3];  // host-side sums: LK iterations, level passes, tracks (pmv_lk_counters)
     void add_lk_work(const uint16_t* w, size_t n) { unsigned long long it = 0, lv = 0; for (size_t i = 0; i < n; i++) { it += w[i] & 0xffu; lv += w[i] >> 8; } lk_work[0] += it; lk_work[1] += lv; lk_work[2] += n; }
     // detectors
-    int* d_cells = nullptr;
-    int* h_cells = nullptr;   // pinned staging of the device cell records
-    double* d_eig = nullptr;
-    void* d_cellmax = nullptr;
-    unsigned* d_spill = nullptr;   // detector candidates beyond the LDS lists: MAX_CELLS * CELL_PIX pixel indices
-    int *d_det_xy = nullptr, *d_det_count = nullptr, *d_flags = nullptr;
-    double* d_det_score = nullptr;
-    int *h_det_xy = nullptr, *h_det_count = nullptr;
-    double* h_det_score = nullptr;
+    pmv::Buf<int> d_cells;
+    pmv::Buf<int> h_cells;    // pinned staging of the device cell records
+    pmv::Buf<double> d_eig;
+    pmv::Buf<void> d_cellmax;
+    pmv::Buf<unsigned> d_spill;    // detector candidates beyond the LDS lists: MAX_CELLS * CELL_PIX pixel indices
+    pmv::Buf<int> d_det_xy, d_det_count, d_flags;
+    pmv::Buf<double> d_det_score;
+    pmv::Buf<int> h_det_xy, h_det_count;
+    pmv::Buf<double> h_det_score;
     // pmv_detect_gftt_ex: the cells' mask sub-views, packed tightly one after the other by the host (pinned) and copied to HBM - only the
     // bytes under the cells cross the bus. MAX_CELLS * CELL_PIX bytes each, made by the first extended call with a mask.
-    uint8_t* h_gmask = nullptr; uint8_t* d_gmask = nullptr;
+    pmv::Buf<uint8_t> h_gmask{pmv::MEM_PINNED}, d_gmask;
     int gftt_general = 0;                // pmv_debug_gftt_general
     // pmv_corner_subpix, made by the first call (a context that never makes one pays nothing): one mapped pinned block [point records nt x 16 |
     // positions 2 nt floats | updates nt bytes | flags nt bytes], nt = max_tracks, and the weight table in HBM with the window and (effective)
     // zero zone it was computed for - a caller keeps its parameters, so the table crosses the bus once
-    uint8_t* h_subpix = nullptr; uint8_t* dm_subpix = nullptr;
-    float* d_subpix_tab = nullptr; float* h_subpix_tab = nullptr;
+    pmv::Buf<uint8_t> h_subpix{pmv::MEM_MAPPED};
+    pmv::Buf<float> d_subpix_tab, h_subpix_tab{pmv::MEM_PINNED};
     int subpix_tab_key[4] = {0, 0, 0, 0};
     // pmv_debug_subpix_launches: launches of the single call | session rounds with a subpix request | launches made for them
     std::atomic<long long> subpix_launches[3];
@@ -92,20 +93,21 @@ struct pmv_ctx {
     // they index, [ClaheRec x CLAHE_CHUNK | PyrLayout x CLAHE_CHUNK], in pinned host memory and in HBM, and the chunk's LUT blocks in HBM. The
     // table is the call's own: the context's geometry table belongs to a session or a batched run, and this call stays legal beside a session.
     static constexpr int CLAHE_CHUNK = 64;   // frames per pair of launches: the scratch is sized by this, not by the call's n
-    uint8_t* h_clahe = nullptr; uint8_t* d_clahe = nullptr; uint8_t* d_clahe_lut = nullptr;
+    pmv::Buf<uint8_t> h_clahe{pmv::MEM_PINNED}, d_clahe, d_clahe_lut;
     // pmv_debug_clahe_launches: LUT + apply launch pairs of pmv_frames_clahe | session upload rounds with a CLAHE request | launch pairs made for them
     std::atomic<long long> clahe_launches[3];
     // pmv_remap_map_create: at most MAX_REMAP_MAPS packed maps (remap_pack's layout, pmv_device.h) in HBM, one per camera; id = index. remap_mu
     // guards the table: a session's callers look a map up while another thread may create one (destroy is refused while a session is open).
     static constexpr int MAX_REMAP_MAPS = 16;
-    struct RemapMap { int w = 0, h = 0; uint8_t* d = nullptr; };
+    struct RemapMap { int w = 0, h = 0; const uint8_t* d = nullptr; };   // what a caller of remap_check takes away
     RemapMap remap_maps[MAX_REMAP_MAPS];
+    pmv::Buf<uint8_t> remap_mem[MAX_REMAP_MAPS];   // the storage behind remap_maps[i].d
     std::mutex remap_mu;
     // pmv_frames_remap, made by the first call: a chunk's tables [RemapRec x REMAP_CHUNK | PyrListEntry x REMAP_CHUNK | PyrLayout x REMAP_CHUNK]
     // in pinned host memory and in HBM (the call's own geometry table, as for pmv_frames_clahe), and the chunk's tight destination frames in
     // HBM: REMAP_CHUNK blocks of remap_frame_bytes(max_w, max_h), not sized by the call's n
     static constexpr int REMAP_CHUNK = 64;
-    uint8_t* h_remap = nullptr; uint8_t* d_remap = nullptr; uint8_t* d_remap_scratch = nullptr;
+    pmv::Buf<uint8_t> h_remap{pmv::MEM_PINNED}, d_remap, d_remap_scratch;
     // pmv_debug_remap_launches: k_remap launches of pmv_frames_remap | session upload rounds with a remap request | k_remap launches made for them
     std::atomic<long long> remap_launches[3];
     pmv::BackendBuffers* be = nullptr;
@@ -124,7 +126,6 @@ struct pmv_ctx {
     // launches as they are (lk_launch_params). Changed only while no bracket, batched run or session is open, so the launches read them freely.
     pmv_lk_params lk = {pmv::LK_WIN, 4, 30, 0.01, 1e-4f};
     int lk_general = 0;                  // pmv_debug_lk_general
-    size_t slots_alloc = 0;              // bytes behind d_slots (>= cap.slot_bytes * n_slots; grows when a deeper pyramid needs more)
     std::atomic<int> batch_open{0};      // a batched run is inside run_batch (the format must not change under it)
     pmv::BatchEngine* engine = nullptr; // created by the first pmv_pipeline_run_batch or pmv_batch_open
     // The engine and the geometry table have ONE owner at a time: a batched run (batch_open > 0) or a batch session. owner_mu makes the
@@ -187,6 +188,22 @@ int clahe_check(pmv_ctx* ctx, const char* who, const pmv_clahe_params* p);
 int remap_check(pmv_ctx* ctx, const char* who, int map_id, int border_value, pmv_ctx::RemapMap* map);
 // after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
+// XCD-aware block order of an LK launch: workgroup b runs on XCD b % 8 and every XCD has its own L2, so the tracks (which arrive in hash
+// order, i.e. spatially random) are dealt out by x position: the k-th track of equal-count stripe s goes to block 8k + s. Each L2 then
+// fetches one vertical stripe of the two pyramids instead of all of them (measured: 5x less HBM traffic). order: (n + 7) / 8 * 8 entries,
+// -1 = padding.
+inline void lk_xcd_order(const float* prev_xy, int n, int* order) {
+    static thread_local std::vector<std::pair<float, int>> byx;
+    const int nb = (n + 7) / 8 * 8;
+    byx.resize(n);
+    for (int i = 0; i < n; i++) byx[i] = {prev_xy[2 * i], i};
+    std::sort(byx.begin(), byx.end());
+    for (int b = 0; b < nb; b++) order[b] = -1;
+    for (int i = 0; i < n; i++) {
+        const int s8 = (int)((long)i * 8 / n), first = (int)(((long)s8 * n + 7) / 8);   // stripe and its first sorted index
+        order[(i - first) * 8 + s8] = byx[i].second;
+    }
+}
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
 }
