@@ -86,6 +86,7 @@ int pmv_frame_upload_bgr(pmv_ctx* ctx, int slot, const uint8_t* bgr, int w, int 
  * pmv_pipeline_params is not involved. Wherever the calls above speak of w * h gray bytes, a BGR context reads three times as many: staging
  * chunks, ingest rounds and landing buffers keep their byte sizes and hold a third as many frames, and pmv_batch_ingest_stats counts the
  * BGR bytes.
+ * Lens undistortion and equalisation of the same host frames on their way in: pmv_set_frame_preproc, below the remap calls.
  *   Errors: a format other than the two above is PMV_ERR_INVALID; a call while a pmv_frames_stream_begin bracket or a batched run
  *   (pmv_pipeline_run_batch, pmv_pipeline_run_batch_streamed) is open on the context is PMV_ERR_INVALID, and the format stays as it was. */
 enum pmv_frame_format { PMV_FRAMES_GRAY = 0, PMV_FRAMES_BGR = 1 };
@@ -97,7 +98,7 @@ int pmv_set_frame_format(pmv_ctx* ctx, int format);
 int pmv_frames_stage(pmv_ctx* ctx, int first_slot, int n, const uint8_t* gray, int w, int h);
 int pmv_frames_build(pmv_ctx* ctx, int first_slot, int n);
 /* Streamed ingest (Frame::Frame / Frame::init + the front-end's per-frame load, Frame.cpp:31-42, OdometryPipeline.cpp:212-220):
- * n tightly packed frames (gray, or BGR: pmv_set_frame_format) in HOST memory (pageable, or pinned: then DMA'd straight from it) are moved into slots first_slot.. by the
+ * n tightly packed frames (gray, or BGR: pmv_set_frame_format; remapped / equalised on the way in: pmv_set_frame_preproc) in HOST memory (pageable, or pinned: then DMA'd straight from it) are moved into slots first_slot.. by the
  * context's feeder thread on its own HIP stream, round by round, each round's pyramids built as soon as its frames land.
  * pmv_frames_stream_begin returns at once; until pmv_frames_stream_end, pmv_lk_track / pmv_detect_* / pmv_knn_match on a slot of the
  * range first make the front-end stream wait for that slot's round (nothing else blocks), so tracking starts while later frames are
@@ -152,9 +153,10 @@ int pmv_frame_get_level_padded(pmv_ctx* ctx, int slot, int level, uint8_t* out, 
  * Errors (nothing is written, nothing is clamped): PMV_ERR_INVALID - a null ctx or p, tiles_x or tiles_y outside 1..16, clip_limit negative
  *   or not finite, an empty slot (the message names it), a call while a pmv_frames_stream_begin bracket or a batched run is open on the
  *   context; PMV_ERR_CAPACITY - a slot range outside n_slots, as for pmv_frames_build.
- * Out of scope: cv::equalizeHist, 16-bit images, more than 16 tiles in a direction, equalisation inside a pmv_frames_stream_begin bracket
- *   or inside the feeder of the two batched runs (staged runs get it through pmv_frames_stage -> pmv_frames_clahe). pmv_frame_upload
- *   followed by pmv_frames_clahe builds the pyramid twice; the session form pmv_batch_frame_upload_clahe does not. */
+ * Out of scope: cv::equalizeHist, 16-bit images, more than 16 tiles in a direction. Host frames that enter through a feeder (the
+ *   pmv_frames_stream_begin bracket and the two streamed runs) are equalised on their way in by pmv_set_frame_preproc; staged runs get it
+ *   through pmv_frames_stage -> pmv_frames_clahe. pmv_frame_upload followed by pmv_frames_clahe builds the pyramid twice; the session form
+ *   pmv_batch_frame_upload_clahe and the feeder form do not. */
 typedef struct pmv_clahe_params {
     double clip_limit;   /* cv's clipLimit; 0 = no clipping; 0 <= clip_limit, finite */
     int tiles_x, tiles_y;/* cv's tileGridSize (width, height); 1 .. 16 each */
@@ -175,8 +177,9 @@ int pmv_debug_clahe_launches(pmv_ctx* ctx, long long* out3);
  *     iy << 16 and a halfword fx | fy << 5: 6 bytes per pixel.
  *   [mem: OpenCV 3.4 imgwarp.cpp, remap with INTER_LINEAR, the CV_32FC1 pair converted as convertMaps does]
  * Errors: PMV_ERR_INVALID - a null argument, or w, h outside 1 .. the context's max_w, max_h; PMV_ERR_CAPACITY - a 17th map.
- * pmv_remap_map_destroy: PMV_ERR_INVALID for an unknown id, and while a batch session is open on the context (its upload rounds read the
- * maps of their requests). pmv_ctx_destroy frees the maps that are left. */
+ * pmv_remap_map_destroy: PMV_ERR_INVALID for an unknown id, while a batch session is open on the context (its upload rounds read the
+ * maps of their requests), and for a map that the current pmv_set_frame_preproc setting names (clear the setting first).
+ * pmv_ctx_destroy frees the maps that are left. */
 int pmv_remap_map_create(pmv_ctx* ctx, int w, int h, const float* map_x, const float* map_y, int* out_id);
 int pmv_remap_map_destroy(pmv_ctx* ctx, int id);
 /* cv::remap(level 0, level 0, map, INTER_LINEAR, BORDER_CONSTANT, Scalar(border_value)) on the slots first_slot .. first_slot + n - 1, then the
@@ -204,13 +207,70 @@ int pmv_remap_map_destroy(pmv_ctx* ctx, int id);
  *   slot (the message names it), a slot whose level-0 size is not the map's (the message names the slot and both sizes), a call while a
  *   pmv_frames_stream_begin bracket or a batched run is open on the context; PMV_ERR_CAPACITY - a slot range outside n_slots, as for
  *   pmv_frames_build.
- * Out of scope: other interpolations and border modes, a destination size different from the source size, 16-bit images, remap inside a
- *   pmv_frames_stream_begin bracket or inside the feeder of the two batched runs. pmv_frame_upload followed by pmv_frames_remap builds the
- *   pyramid twice; the session form pmv_batch_frame_upload_remap does not. */
+ * Out of scope: other interpolations and border modes, a destination size different from the source size, 16-bit images. Host frames that
+ *   enter through a feeder (the pmv_frames_stream_begin bracket and the two streamed runs) are remapped on their way in by
+ *   pmv_set_frame_preproc. pmv_frame_upload followed by pmv_frames_remap builds the pyramid twice; the session form
+ *   pmv_batch_frame_upload_remap and the feeder form do not. */
 int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border_value);
 /* diagnostic: {k_remap launches of pmv_frames_remap, session upload rounds that held at least one pmv_batch_frame_upload_remap request,
  * k_remap launches made for them} since the context was created. */
 int pmv_debug_remap_launches(pmv_ctx* ctx, long long* out3);
+/* ---- remap and equalisation inside the feeder: real cameras on the streamed runs --------------------- */
+/* Preprocessing of the host frames that the throughput paths take: a context setting next to pmv_set_frame_format, for callers whose camera
+ * has a real lens and real exposure. It governs every frame that enters a slot from HOST memory through the feeder:
+ *   the pmv_frames_stream_begin .. _end bracket, pmv_pipeline_run_streamed and pmv_pipeline_run_batch_streamed.
+ * Per frame, in this order: BGR -> remap -> CLAHE -> border, that is
+ *   1. cv::cvtColor(BGR2GRAY) if the context's format is PMV_FRAMES_BGR (pmv_set_frame_format);
+ *   2. cv::remap(INTER_LINEAR, BORDER_CONSTANT, Scalar(border_value)) through the map whose size equals the frame's size (n_maps > 0);
+ *   3. cv::CLAHE::apply with clahe_params (clahe != 0);
+ *   4. the 64-pixel REFLECT_101 border of level 0 and the levels above.
+ * Result: the slot holds, at every level with its border, byte for byte what pmv_frame_upload of the preprocessed gray image would have
+ *   left - hence what pmv_frames_stage -> pmv_frames_remap -> pmv_frames_clahe leaves - and every pipeline result is bit-identical to the
+ *   same run with the setting off on host frames preprocessed by tests/twin/remap_twin.cpp / clahe_twin.cpp. The caller passes the camera
+ *   matrix that goes with the map (newK of pmv_undistort_map_build) as K9; the library does not touch K9.
+ * Arithmetic: that of pmv_frames_remap and pmv_frames_clahe above, statement for statement (integer rule and float order included); a BGR
+ *   tap is converted with (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 before the weights, the value k_pad_level0_bgr would have stored.
+ * Staged feeds are untouched: frames already in slots - the staged feeds of pmv_pipeline_run_batch and of pmv_pipeline_run with
+ *   build_pyramids, pmv_frames_stage, pmv_frames_build - are not preprocessed; the caller runs pmv_frames_remap / pmv_frames_clahe over
+ *   them, as before. pmv_frame_upload* and the session uploads (pmv_batch_frame_upload_remap / _clahe) keep their own per-call forms.
+ * Sizes: a feed may mix frame sizes; each sequence uses the map of its own size, so the maps of a setting have pairwise different sizes
+ *   (a batch has one K9 per sequence, hence one camera per size). With n_maps > 0, a sequence with a host source and no map of its size is
+ *   PMV_ERR_INVALID; the message names the sequence and the size, and it is raised before any thread starts or any slot changes.
+ * Kernels and launches: a round of the feeder with preprocessing makes, after its copy, ONE k_remap_src launch in place of the level-0
+ *   launch (remap on: the gather reads the round's tight source frames in the HBM landing buffer and writes the interior of level 0
+ *   directly - one read of the taps, one write, no scratch frame; counted in pmv_debug_batch_launches where the level-0 launch it replaces
+ *   is) or the level-0 launch as always (remap off); ONE k_clahe_lut + k_clahe_apply pair over the round's slots (CLAHE on; the LUT scratch
+ *   is the feeder's, 256 bytes per tile and frame of a round, made by the first such feed); ONE in-place k_pad_level0 launch for the
+ *   border; the k_pyrdown launches as always. One record per frame names its source, map, slot and geometry, so one launch serves a round
+ *   of any sizes and maps. All are booked under the level-0 profiling class. k_remap_src keeps k_remap's map loads (16 + 8 bytes per four
+ *   pixels, aligned); it stores one aligned dword where a thread's four pixels lie in one row at a column that is a multiple of 4 (always
+ *   when w % 4 == 0) and bytes elsewhere.
+ * No gather from host memory: a 2 x 2 byte gather across the host link is a link transaction per tap, so a feed with n_maps > 0 brings
+ *   every host frame into HBM through the copy form first - whatever PMV_BATCH_INGEST says, and for a caller's pinned buffer as well
+ *   (NBUF landing buffers in HBM, as PMV_BATCH_INGEST=copy). pmv_batch_ingest_stats keeps counting the bytes moved. A CLAHE-only feed keeps
+ *   whichever form it would have had.
+ * Off (the default; p_or_null == NULL, or n_maps == 0 && clahe == 0): the feeder makes exactly the launches it made before this setting
+ *   existed and allocates nothing new.
+ * Errors: PMV_ERR_INVALID - a null ctx; n_maps outside 0..PMV_PREPROC_MAX_MAPS; an unknown map id, or two maps of one size;
+ *   border_value outside 0..255; with clahe != 0, parameters that pmv_frames_clahe would refuse; a call while a pmv_frames_stream_begin
+ *   bracket or a batched run is open on the context. The setting then stays as it was, and nothing is clamped.
+ * pmv_get_frame_preproc returns the setting in force (unused map_ids and, with clahe == 0, clahe_params are zero).
+ * Out of scope: preprocessing of staged feeds; several maps of one size (per-sequence cameras of one size); other interpolations and border
+ *   modes, 16-bit images, cv::equalizeHist; pmv_batch_frame_upload_remap and pmv_frames_remap keep their own launches. */
+#define PMV_PREPROC_MAX_MAPS 8
+typedef struct pmv_frame_preproc {
+    int n_maps;                          /* 0 = no remap */
+    int map_ids[PMV_PREPROC_MAX_MAPS];   /* ids of pmv_remap_map_create, pairwise different sizes */
+    int border_value;                    /* 0..255, as pmv_frames_remap */
+    int clahe;                           /* 0 = no equalisation */
+    pmv_clahe_params clahe_params;       /* read only if clahe != 0; the ranges of pmv_frames_clahe */
+} pmv_frame_preproc;
+int pmv_set_frame_preproc(pmv_ctx* ctx, const pmv_frame_preproc* p_or_null);   /* null: off (the default) */
+int pmv_get_frame_preproc(pmv_ctx* ctx, pmv_frame_preproc* out);
+/* diagnostic: out4 = {feeder rounds that preprocessed, k_remap_src launches, k_clahe_lut + k_clahe_apply launch pairs, in-place
+ * k_pad_level0 border launches made for them} since the context was created, over the bracket's and the batched runs' feeders. The border
+ * launches are counted here only: pmv_debug_batch_launches keeps its meaning. */
+int pmv_debug_preproc_launches(pmv_ctx* ctx, long long* out4);
 /* diagnostic: bytes the library currently holds, over every context of the process: out2 = {device memory, pinned host memory}. Needs no
  * context. Every allocation has one owner that frees it, and these two counters are written where a block is made and where it is freed,
  * so the pair returns to its earlier value once everything made in between has been closed - whatever other processes do to the card. */
@@ -563,7 +623,7 @@ typedef struct pmv_pipeline_result pmv_pipeline_result;
 
 int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                      pmv_pipeline_result** out);
-/* The same run from n_frames frames (gray, or BGR: pmv_set_frame_format) in HOST memory: pmv_frames_stream_begin(ctx, 0, n_frames, host_frames, w, h), the run
+/* The same run from n_frames frames (gray, or BGR: pmv_set_frame_format; remapped / equalised on the way in: pmv_set_frame_preproc) in HOST memory: pmv_frames_stream_begin(ctx, 0, n_frames, host_frames, w, h), the run
  * (build_pyramids ignored), pmv_frames_stream_end. Identical results; copies and pyramid builds overlap the tracking. */
 int pmv_pipeline_run_streamed(pmv_ctx* ctx, const pmv_pipeline_params* params, const double* K9, const double* gt_poses12,
                               const uint8_t* host_frames, pmv_pipeline_result** out);
@@ -593,7 +653,7 @@ int pmv_debug_batch_launches(pmv_ctx* ctx, long long* out4);
 /* The same B sequences streamed from HOST memory through recycled frame slots (the reference loads one image per front-end iteration,
  * Frame.cpp:31-42, OdometryPipeline.cpp:212-229, and tracking reads only frames k-1 and k), so that the batch size is not capped by frame
  * storage: B x ring slots instead of the sum of all n_frames.
- *   Frames: sequence b's params[b].n_frames tightly packed frames (gray, or BGR: pmv_set_frame_format) at host_frames[b], pageable or pinned / registered; read only, several
+ *   Frames: sequence b's params[b].n_frames tightly packed frames (gray, or BGR: pmv_set_frame_format; remapped / equalised on the way in: pmv_set_frame_preproc) at host_frames[b], pageable or pinned / registered; read only, several
  *     b may point at the same buffer; they stay valid until the call returns. A kernel never reads a pageable address: pinned memory
  *     mapped at its host address (hipHostMalloc, torch pin_memory) is read in place, anything else is copied into pinned staging first.
  *   Slots: sequence b owns slots first_slot[b] .. first_slot[b] + ring - 1 (disjoint ranges inside n_slots); frame f lives in slot

@@ -65,6 +65,56 @@ def _clahe_params(who, clip_limit, tiles):
     return ClaheParams(float(clip_limit), int(tx), int(ty))
 
 
+PREPROC_MAX_MAPS = 8   # PMV_PREPROC_MAX_MAPS of include/pmv_hip.h
+
+
+class FramePreproc(C.Structure):
+    """pmv_frame_preproc of include/pmv_hip.h"""
+    _fields_ = [("n_maps", C.c_int), ("map_ids", C.c_int * PREPROC_MAX_MAPS), ("border_value", C.c_int), ("clahe", C.c_int), ("clahe_params", ClaheParams)]
+
+
+def _preproc_arg(who, remap, border_value, clahe):
+    """set_frame_preproc's arguments as a FramePreproc, or None when everything is off; wrong types and ranges are refused here"""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if remap is None:
+        ids = []
+    elif is_int(remap):
+        ids = [int(remap)]
+    else:
+        try:
+            ids = list(remap)
+        except TypeError:
+            raise ValueError(f"{who}: remap is a map id or a sequence of map ids, got {remap!r}") from None
+        if isinstance(remap, (str, bytes)) or not all(is_int(i) for i in ids):
+            raise ValueError(f"{who}: remap is a map id or a sequence of integer map ids, got {remap!r}")
+        ids = [int(i) for i in ids]
+    if len(ids) > PREPROC_MAX_MAPS:
+        raise ValueError(f"{who}: at most {PREPROC_MAX_MAPS} maps, got {len(ids)}")
+    if not is_int(border_value) or not 0 <= int(border_value) <= 255:
+        raise ValueError(f"{who}: border_value is an integer in 0..255, got {border_value!r}")
+    p = FramePreproc()
+    p.n_maps = len(ids)
+    for k, i in enumerate(ids):
+        p.map_ids[k] = i
+    p.border_value = int(border_value)
+    if clahe is not None:
+        try:
+            clip, tiles = clahe
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: clahe is None or (clip_limit, (tiles_x, tiles_y)), got {clahe!r}") from None
+        cp = _clahe_params(who, clip, tiles)
+        if not (cp.clip_limit >= 0.0 and np.isfinite(cp.clip_limit)):
+            raise ValueError(f"{who}: clip_limit is a finite number >= 0, got {clip!r}")
+        if not (1 <= cp.tiles_x <= 16 and 1 <= cp.tiles_y <= 16):
+            raise ValueError(f"{who}: tiles are in 1..16 each, got {tiles!r}")
+        p.clahe = 1
+        p.clahe_params = cp
+    if not ids and clahe is None and int(border_value) == 0:
+        return None
+    return p
+
+
 def _remap_arg(who, remap):
     """remap= of the session upload: a map id, or (map_id, border_value)"""
     def is_int(v):
@@ -138,6 +188,7 @@ ABI_SYMBOLS = [
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
     "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
+    "pmv_set_frame_preproc", "pmv_get_frame_preproc", "pmv_debug_preproc_launches",
     "pmv_debug_mem_live",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
@@ -493,6 +544,32 @@ class Context:
     @property
     def frame_format(self):
         return getattr(self, "_frame_format", "gray")
+
+    def set_frame_preproc(self, remap=None, border_value=0, clahe=None):
+        """pmv_set_frame_preproc: lens undistortion and / or CLAHE of every HOST frame that enters a slot through the feeder - frames_stream_begin,
+        pipeline_run(host_frames=...) and pipeline_run_batch_streamed - in the order BGR -> remap -> CLAHE -> border. remap: a map id of
+        remap_map_create or a sequence of ids (at most 8, pairwise different sizes: each sequence uses the map of its own frame size);
+        border_value: cv's borderValue, 0..255; clahe: None or (clip_limit, (tiles_x, tiles_y)). No arguments: off (the default). Frames
+        already in slots (frames_stage, staged batches) are not touched. Pass the camera matrix that goes with the map as K."""
+        p = _preproc_arg("set_frame_preproc", remap, border_value, clahe)
+        self.lib.pmv_set_frame_preproc.argtypes = [C.c_void_p, C.POINTER(FramePreproc)]
+        self._ck(self.lib.pmv_set_frame_preproc(self.h, None if p is None else C.byref(p)))
+
+    def get_frame_preproc(self):
+        """pmv_get_frame_preproc: dict(remap=[map ids], border_value=int, clahe=None or (clip_limit, (tiles_x, tiles_y)))"""
+        p = FramePreproc()
+        self.lib.pmv_get_frame_preproc.argtypes = [C.c_void_p, C.POINTER(FramePreproc)]
+        self._ck(self.lib.pmv_get_frame_preproc(self.h, C.byref(p)))
+        cp = p.clahe_params
+        return dict(remap=[int(p.map_ids[k]) for k in range(p.n_maps)], border_value=int(p.border_value),
+                    clahe=(float(cp.clip_limit), (int(cp.tiles_x), int(cp.tiles_y))) if p.clahe else None)
+
+    def debug_preproc_launches(self):
+        """pmv_debug_preproc_launches: [feeder rounds that preprocessed, gather launches, CLAHE launch pairs, in-place border launches]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_preproc_launches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_preproc_launches(self.h, out))
+        return [int(v) for v in out]
 
     def frames_stage(self, first_slot, frames):
         f = _host_frames(frames, self.frame_format, "frames_stage")

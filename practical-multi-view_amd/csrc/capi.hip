@@ -138,6 +138,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->subpix_launches) a.store(0);
     for (auto& a : c->clahe_launches) a.store(0);
     for (auto& a : c->remap_launches) a.store(0);
+    for (auto& a : c->preproc_launches) a.store(0);
     int rc = backend_create(c);
     if (rc != PMV_OK) { snprintf(g_create_err, sizeof(g_create_err), "%s", c->err); pmv_ctx_destroy(c); return rc; }
 #undef CK
@@ -449,6 +450,9 @@ int pmv_remap_map_destroy(pmv_ctx* ctx, int id) {
     REQ(ctx->session_state.load() == 0, PMV_ERR_INVALID, "pmv_remap_map_destroy: a batch session is open on this context (pmv_batch_close first)");
     std::lock_guard<std::mutex> lk(ctx->remap_mu);
     REQ(id >= 0 && id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[id].d, PMV_ERR_INVALID, "pmv_remap_map_destroy: map %d does not exist", id);
+    // the feeders resolve the setting's maps whenever a feed begins
+    for (int k = 0; k < ctx->preproc.n_maps; k++)
+        REQ(ctx->preproc.map_ids[k] != id, PMV_ERR_INVALID, "pmv_remap_map_destroy: map %d is named by the frame preprocessing setting (clear it with pmv_set_frame_preproc first)", id);
     CKC(hipSetDevice(ctx->device));
     CKC(hipStreamSynchronize(ctx->s_front));
     CKC(ctx->remap_mem[id].release());
@@ -505,6 +509,48 @@ int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border
 int pmv_debug_remap_launches(pmv_ctx* ctx, long long* out3) {
     REQ(ctx && out3, PMV_ERR_INVALID, "pmv_debug_remap_launches: null argument");
     for (int i = 0; i < 3; i++) out3[i] = ctx->remap_launches[i].load();
+    return PMV_OK;
+}
+
+// Remap and / or CLAHE of every host frame that a feeder moves into a slot (ingest_batch.hip): validated here, read by batch_ingest_begin.
+// Not while a feed is open: a feed works from its own snapshot, and the maps it reads must stay.
+int pmv_set_frame_preproc(pmv_ctx* ctx, const pmv_frame_preproc* p) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_set_frame_preproc: null ctx");
+    pmv_frame_preproc q = {};
+    if (p) {
+        REQ(p->n_maps >= 0 && p->n_maps <= PMV_PREPROC_MAX_MAPS, PMV_ERR_INVALID, "pmv_set_frame_preproc: n_maps = %d is outside 0..%d", p->n_maps, PMV_PREPROC_MAX_MAPS);
+        REQ(p->border_value >= 0 && p->border_value <= 255, PMV_ERR_INVALID, "pmv_set_frame_preproc: border_value = %d is outside 0..255", p->border_value);
+        if (p->clahe) {
+            if (const int rc_ = clahe_check(ctx, "pmv_set_frame_preproc", &p->clahe_params)) return rc_;
+            q.clahe = 1; q.clahe_params = p->clahe_params;
+        }
+        std::lock_guard<std::mutex> lk(ctx->remap_mu);
+        for (int k = 0; k < p->n_maps; k++) {
+            const int id = p->map_ids[k];
+            REQ(id >= 0 && id < pmv_ctx::MAX_REMAP_MAPS && ctx->remap_maps[id].d, PMV_ERR_INVALID, "pmv_set_frame_preproc: map %d does not exist (pmv_remap_map_create)", id);
+            for (int j = 0; j < k; j++) {
+                const pmv_ctx::RemapMap &a = ctx->remap_maps[p->map_ids[j]], &b = ctx->remap_maps[id];
+                REQ(a.w != b.w || a.h != b.h, PMV_ERR_INVALID, "pmv_set_frame_preproc: maps %d and %d are both %dx%d: one map per frame size", p->map_ids[j], id, b.w, b.h);
+            }
+            q.map_ids[k] = id;
+        }
+        q.n_maps = p->n_maps;
+        q.border_value = p->border_value;
+    }
+    REQ(!batch_ingest_active(ctx->ingest), PMV_ERR_INVALID, "pmv_set_frame_preproc: a pmv_frames_stream_begin bracket is open (pmv_frames_stream_end first)");
+    REQ(!ctx->batch_open.load() && !batch_ingest_active(ctx->bingest), PMV_ERR_INVALID, "pmv_set_frame_preproc: a batched run is open on this context");
+    std::lock_guard<std::mutex> lk(ctx->remap_mu);   // (pmv_remap_map_destroy reads the setting under it)
+    ctx->preproc = q;
+    return PMV_OK;
+}
+int pmv_get_frame_preproc(pmv_ctx* ctx, pmv_frame_preproc* out) {
+    REQ(ctx && out, PMV_ERR_INVALID, "pmv_get_frame_preproc: null argument");
+    *out = ctx->preproc;
+    return PMV_OK;
+}
+int pmv_debug_preproc_launches(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_preproc_launches: null argument");
+    for (int i = 0; i < 4; i++) out4[i] = ctx->preproc_launches[i].load();
     return PMV_OK;
 }
 

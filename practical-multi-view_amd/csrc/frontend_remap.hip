@@ -10,6 +10,8 @@
 // a thread takes p = 4 t .. 4 t + 3: one 16-byte and one 8-byte map load, both aligned and coalesced, and one aligned dword store, whatever w
 // is; with w % 4 != 0 its four pixels may sit on two rows, which only the row / column split below has to know. The 2 x 2 taps are plain
 // cached byte loads. Vector loads and stores only, no LDS.
+// pmv_set_frame_preproc (the feeder, ingest_batch.hip) runs the same gather as k_remap_src: its taps come from the round's landing buffer,
+// not from a slot, so it writes level 0 of the slot directly and needs neither the scratch frame nor the list-form level-0 pass.
 #include "pmv_device.h"
 #include "pmv_prof.h"
 #include <climits>
@@ -58,6 +60,69 @@ __global__ __launch_bounds__(RM_T) void k_remap(const uint8_t* __restrict__ slot
     uint8_t* dst = scratch + r.dst_off + p0;   // dst_off is a multiple of 256: a dword-aligned address
     if (p0 + RM_PX <= npix) *(uint32_t*)dst = out;
     else for (unsigned k = 0; p0 + k < npix; k++) dst[k] = (uint8_t)(out >> (8 * k));   // byte tail of a frame with w h % 4 != 0
+}
+
+// The feeder's form: k_remap's arithmetic, statement for statement, on a tight source frame (gray bytes, or BGR triples converted per tap)
+// with the interior of level 0 as the destination. The thread / pixel assignment stays linear in p, so the map loads stay one aligned 16-byte
+// and one aligned 8-byte load per four pixels whatever w is. The destination is NOT linear in p any more (row pitch stride[0] >= w + 128), so
+// the stores split: a thread whose four pixels lie in one row at a column that is a multiple of 4 (every thread when w % 4 == 0; with an
+// odd w the rows y with y w % 4 == 0, one in four) makes ONE aligned dword store - interior rows start 64-byte aligned; every other thread,
+// including the one that straddles a row end and the tail of a frame with w h % 4 != 0, makes up to four byte stores.
+template <bool BGR>
+__device__ __forceinline__ int remap_src_tap(const uint8_t* __restrict__ src, ptrdiff_t o) {
+    if (!BGR) return (int)src[o];
+    const uint8_t* q = src + 3 * o;            // cvtColor(BGR2GRAY), as k_pad_level0_bgr stores it
+    return ((int)q[0] * 1868 + (int)q[1] * 9617 + (int)q[2] * 4899 + 8192) >> 14;
+}
+template <bool BGR>
+__device__ __forceinline__ void remap_src_body(uint8_t* __restrict__ slots, GeomEntry& L, const RemapSrcRec& r) {
+    const int w = L.w[0], h = L.h[0], stride = L.stride[0];
+    const unsigned npix = (unsigned)w * (unsigned)h;
+    const unsigned p0 = (blockIdx.x * (unsigned)RM_T + threadIdx.x) * RM_PX;
+    if (p0 >= npix) return;                    // (the grid is sized for the largest frame of the list; no barrier in this kernel)
+    const uint8_t* __restrict__ src = r.src;
+    const unsigned n4 = (npix + 3u) & ~3u;     // entries per plane of the packed map
+    const uint32_t* plane_xy = r.map;
+    const uint16_t* plane_f = (const uint16_t*)(r.map + n4);
+    const uint4 cq = *(const uint4*)(plane_xy + p0);   // p0 is a multiple of 4 and the planes are padded to one: inside the map
+    const uint2 fq = *(const uint2*)(plane_f + p0);
+    const uint32_t c[RM_PX] = {cq.x, cq.y, cq.z, cq.w};
+    const uint32_t f[RM_PX] = {fq.x & 0xffffu, fq.x >> 16, fq.y & 0xffffu, fq.y >> 16};
+    const int bv = r.border;
+    uint32_t out = 0;
+#pragma unroll
+    for (int k = 0; k < RM_PX; k++) {
+        if (p0 + k >= npix) break;             // (the padding entries of the last dword)
+        const int ix = (int)(short)(c[k] & 0xffffu), iy = (int)(short)(c[k] >> 16);
+        const int fx = (int)(f[k] & 31u), fy = (int)((f[k] >> 5) & 31u);
+        // a tap is read only where it lies inside the w x h frame; everywhere else it is the border value
+        const bool x0 = (unsigned)ix < (unsigned)w, x1 = (unsigned)(ix + 1) < (unsigned)w;
+        const bool y0 = (unsigned)iy < (unsigned)h, y1 = (unsigned)(iy + 1) < (unsigned)h;
+        const ptrdiff_t o = (ptrdiff_t)iy * (ptrdiff_t)w + (ptrdiff_t)ix;   // the source is tight: its row pitch is w pixels
+        const int t00 = (x0 && y0) ? remap_src_tap<BGR>(src, o) : bv;
+        const int t01 = (x1 && y0) ? remap_src_tap<BGR>(src, o + 1) : bv;
+        const int t10 = (x0 && y1) ? remap_src_tap<BGR>(src, o + w) : bv;
+        const int t11 = (x1 && y1) ? remap_src_tap<BGR>(src, o + w + 1) : bv;
+        const int d = ((32 - fy) * (32 - fx) * t00 + (32 - fy) * fx * t01 + fy * (32 - fx) * t10 + fy * fx * t11 + 512) >> 10;
+        out |= (uint32_t)d << (8 * k);
+    }
+    uint8_t* img = slots + (size_t)__builtin_amdgcn_readfirstlane(r.slot) * L.slot_bytes + L.gray_off;
+    const unsigned y = p0 / (unsigned)w, x = p0 - y * (unsigned)w;
+    if (p0 + RM_PX <= npix && x + RM_PX <= (unsigned)w && (x & 3u) == 0u) {
+        *(uint32_t*)(img + (size_t)y * (size_t)stride + x) = out;
+    } else {
+        for (unsigned k = 0; k < RM_PX && p0 + k < npix; k++) {
+            unsigned xk = x + k, yk = y;
+            if (xk >= (unsigned)w) { xk -= (unsigned)w; yk++; }   // (w >= 40: four pixels cross one row end at most)
+            img[(size_t)yk * (size_t)stride + xk] = (uint8_t)(out >> (8 * k));
+        }
+    }
+}
+__global__ __launch_bounds__(RM_T) void k_remap_src(uint8_t* __restrict__ slots, const PyrLayout* __restrict__ geom, const RemapSrcRec* __restrict__ recs) {
+    const RemapSrcRec r = recs[blockIdx.y];
+    GeomEntry& L = geom_entry(geom, r.geom);
+    if (__builtin_amdgcn_readfirstlane(r.bgr)) remap_src_body<true>(slots, L, r);   // (the record is the workgroup's: a uniform branch)
+    else remap_src_body<false>(slots, L, r);
 }
 
 // cvRound of a float as cvtss2si does it: half to even, and the "integer indefinite" INT_MIN for a NaN or a value beyond int32
@@ -121,6 +186,16 @@ hipError_t launch_remap(hipStream_t s, const uint8_t* slots, const PyrLayout* d_
     if (gx > 0x7fffffffu / per_block) return hipErrorInvalidValue;   // (the kernel's pixel index is 32 bits)
     ProfScope ps(K_PAD0, s);
     hipLaunchKernelGGL(k_remap, dim3((unsigned)gx, n), dim3(RM_T), 0, s, slots, d_geom, d_recs, d_scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_remap_src(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const RemapSrcRec* d_recs, int n, int max_w, int max_h) {
+    if (!slots || !d_geom || !d_recs || n < 1 || n > 65535 || max_w < 1 || max_h < 1) return hipErrorInvalidValue;
+    const size_t per_block = (size_t)RM_T * RM_PX;
+    const size_t gx = ((size_t)max_w * (size_t)max_h + per_block - 1) / per_block;
+    if (gx > 0x7fffffffu / per_block) return hipErrorInvalidValue;   // (the kernel's pixel index is 32 bits)
+    ProfScope ps(K_PAD0, s);
+    hipLaunchKernelGGL(k_remap_src, dim3((unsigned)gx, n), dim3(RM_T), 0, s, slots, d_geom, d_recs);
     return hipGetLastError();
 }
 

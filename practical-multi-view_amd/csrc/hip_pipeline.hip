@@ -408,7 +408,8 @@ static int run_batch(pmv_ctx* ctx, const char* who, int B, const pmv_pipeline_pa
             fed[(size_t)b] = (int)feed.size();
             feed.push_back({first_slot[b], params[b].n_frames, ring[b], host_frames ? host_frames[b] : nullptr, params[b].w, params[b].h});
         }
-    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, host_frames ? ctx->frame_format : PMV_FRAMES_GRAY)) != PMV_OK)
+    if (!feed.empty() && (rc = pmv::batch_ingest_begin(ctx, ctx->bingest, host_frames ? pmv::FEED_STREAMED : pmv::FEED_STAGED, feed, host_frames ? ctx->frame_format : PMV_FRAMES_GRAY,
+                                                       host_frames ? &ctx->preproc : nullptr)) != PMV_OK)
         return rc;
     std::vector<int> codes(B, PMV_OK);
     std::vector<std::string> msgs(B);

@@ -20,7 +20,11 @@ struct FeedSeq { int first, n, ring; const uint8_t* src; int w, h; };
 // feeder thread. Staged ranges may overlap: a slot that several sequences cover is built once (the caller has checked that they agree on its
 // size). A feed of several sequences (FEED_STREAMED, FEED_STAGED) finds every sequence's size in the context's geometry table (geom_table_set).
 // `format` (pmv_frame_format) is what the host frames hold: gray, or tight BGR (3 w h bytes a frame) that level 0 converts on the way in.
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int format = PMV_FRAMES_GRAY);
+// `pre` (pmv_set_frame_preproc; null or all zero: off) is copied: it governs the sequences with a host source. Each of them finds the map of
+// its own size once, here; one without a map is PMV_ERR_INVALID before a slot changes or the thread starts. With a remap the feed takes the
+// copy form whatever PMV_BATCH_INGEST says: the gather reads HBM only.
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& g, FeedKind kind, const std::vector<FeedSeq>& seqs, int format = PMV_FRAMES_GRAY,
+                       const pmv_frame_preproc* pre = nullptr);
 bool batch_ingest_active(const BatchIngest* g);
 // Combiner thread: make `s` wait on the GPU for feed round `round` (the feeder's stream is in order: every earlier round as well).
 hipError_t batch_ingest_wait_gpu(BatchIngest* g, hipStream_t s, int round);

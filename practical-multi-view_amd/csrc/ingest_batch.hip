@@ -25,6 +25,14 @@
 //     reads a slot, its caller waits in slot_ready on the host until the frame it needs is in the slot's record; the stream of the kernel
 //     then waits for that round's event (a combiner once per launch).
 //
+//   * Preprocessing (pmv_set_frame_preproc; a snapshot per feed, host sources only). A round of such a feed carries, in its header block
+//     behind the slot table, a second slot table without sources, its RemapSrcRec and ClaheRec records and - in a bracket, which has no
+//     geometry table - the one-entry table they index. With a remap every host frame lands in HBM first (the copy form, whatever
+//     PMV_BATCH_INGEST says and for a caller's pinned buffer too: a 2 x 2 byte gather across the host link is a link transaction per tap), and
+//     ONE k_remap_src launch takes the place of the level-0 launch: it gathers from the landing buffer straight into level 0 of the slots.
+//     With CLAHE, ONE k_clahe_lut + k_clahe_apply pair follows over the round's slots. Then ONE in-place k_pad_level0 launch (no source)
+//     builds the REFLECT_101 frame, and the k_pyrdown launches follow as always. A feed without preprocessing launches what it always did.
+//
 // A sequence is served when it has room for F frames, or has no more than LOW frames landed ahead, or only its last frames remain, or its
 // thread is waiting for a frame: a round per released frame would be 5 launches per frame (the launch volume DESIGN §5 suspects behind
 // the bimodal throughput). A ring that is not recycled (ring >= n) has all its frames as room from the start: its sequence is fed CHUNK
@@ -52,6 +60,14 @@ struct BatchIngest {
     static constexpr size_t ROUND_BYTES = 32u << 20;    // ... and no more bytes than this (1241x376: 64 frames = 29.9 MB)
     static constexpr size_t HDR = 16384;                // the round's slot table in front of its frames ...
     static constexpr int TABLE = (int)(HDR / sizeof(PyrListEntry));   // ... and so the frames of a round of staged sources at most
+    // a preprocessing round (host frames: ROUND_FRAMES at most) keeps behind its slot table: the same slots without sources (the in-place
+    // border launch of a list round), the gather records, the CLAHE records, a bracket's one-entry geometry table
+    static constexpr size_t OFF_INPLACE = (size_t)ROUND_FRAMES * sizeof(PyrListEntry);
+    static constexpr size_t OFF_REMAP = OFF_INPLACE + (size_t)ROUND_FRAMES * sizeof(PyrListEntry);
+    static constexpr size_t OFF_CLAHE = OFF_REMAP + (size_t)ROUND_FRAMES * sizeof(RemapSrcRec);
+    static constexpr size_t OFF_GEOM = OFF_CLAHE + (size_t)ROUND_FRAMES * sizeof(ClaheRec);
+    static constexpr size_t HDR_PRE = OFF_GEOM + sizeof(PyrLayout);   // bytes of a preprocessing round's header that are in use
+    static_assert(HDR_PRE <= HDR && OFF_REMAP % 16 == 0 && OFF_CLAHE % 16 == 0 && OFF_GEOM % 4 == 0, "a preprocessing round's tables fit its header block");
     static constexpr int LOW = 2;                       // frames landed ahead of the release point below which a sequence is served at once
     static constexpr int BRACKET_CHUNK = 16, STAGED_CHUNK = 32;   // frames of a sequence per round: bracket, staged batch (as before the feeder)
     // slot_rec values besides (frame << 32) | round: no feed covers the slot / not built yet, by sequence b of the feed
@@ -64,6 +80,7 @@ struct BatchIngest {
     Buf<uint8_t> h_stage{MEM_MAPPED};   // NBUF x buf_bytes, pinned + mapped
     Buf<uint8_t> d_land;                // NBUF x buf_bytes in HBM (copy form and staged feeds: made by the first that needs it)
     size_t buf_bytes = 0;
+    Buf<uint8_t> d_lut;                 // CLAHE of a preprocessing feed: frames_per_round LUT blocks (made by the first such feed)
     std::unique_ptr<std::atomic<long long>[]> slot_rec;   // per slot: (frame << 32) | round of its last enqueued build, or NONE / pending(b)
     std::mutex ev_mu;             // hipEventRecord / growth of `ev` (feeder thread) vs hipStreamWaitEvent (readers)
     // one feed
@@ -78,12 +95,17 @@ struct BatchIngest {
         int w = 0, h = 0, geom = 0;     // its frame size and that size's entry of the context's geometry table (0 in a bracket, which has no list rounds)
         size_t fb = 0;                  // bytes of one of its host frames: w h (gray) or 3 w h (BGR)
         PyrLayout L{};
+        const uint32_t* map = nullptr;  // preprocessing with a remap: the packed map of its size (device memory)
     };
     std::unique_ptr<Seq[]> seq;
     pmv_ctx* ctx = nullptr;
     int B = 0, frames_per_round = 1;
     size_t max_fb = 0;            // bytes of the largest host frame of the feed
     bool bgr = false;             // the host frames are tight BGR: level 0 through k_pad_level0_bgr
+    // the feed's snapshot of pmv_set_frame_preproc (host sources only; a feed with either has nothing but host sources)
+    bool remap = false, clahe = false;
+    int border = 0;
+    pmv_clahe_params cp{};
     bool table = false;           // the sequences' geometries are in the context's table: list rounds are possible
     bool count_launches = false;  // the feed of a batched run: its launches go into pmv_debug_batch_launches
     bool copy_mode = false, per_round = false, open = false;
@@ -179,6 +201,7 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
         }
         const bool direct = range && g->dma_release && S0.dev;
         const auto tm0 = std::chrono::steady_clock::now();
+        const bool pre = g->remap || g->clahe;
         int nc = 0;                  // frames copied into staging
         size_t cb = 0, hb = 0;       // their bytes (frame after frame, each of its own size); bytes of all frames from host memory
         for (int i = 0; i < n; i++) {
@@ -197,20 +220,66 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
             nc++;
         }
         if (nc) g->t_memcpy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
-        if (g->copy_mode) {   // frames only for the range form; the table (+ frames) for the list form
-            const uint8_t* from = direct ? S0.src + (size_t)take[0].second * S0.fb : range ? blk + BatchIngest::HDR : blk;
-            const size_t off = range ? BatchIngest::HDR : 0;
-            const size_t bytes = range ? (direct ? (size_t)n * S0.fb : cb) : nc ? BatchIngest::HDR + cb : (size_t)n * sizeof(PyrListEntry);
+        int pre_w = 0, pre_h = 0;    // preprocessing: the largest level 0 of the round
+        if (pre) {   // the round's extra tables, behind its slot table
+            PyrListEntry* inplace = (PyrListEntry*)(blk + BatchIngest::OFF_INPLACE);
+            RemapSrcRec* rr = (RemapSrcRec*)(blk + BatchIngest::OFF_REMAP);
+            ClaheRec* cr = (ClaheRec*)(blk + BatchIngest::OFF_CLAHE);
+            const unsigned lut_block = (unsigned)(g->cp.tiles_x * g->cp.tiles_y) * 256u;
+            for (int i = 0; i < n; i++) {
+                const BatchIngest::Seq& S = g->seq[take[(size_t)i].first];
+                inplace[i].src = nullptr; inplace[i].slot = tab[i].slot; inplace[i].geom = tab[i].geom;
+                if (g->remap) { rr[i].map = S.map; rr[i].src = tab[i].src; rr[i].slot = tab[i].slot; rr[i].geom = tab[i].geom; rr[i].border = g->border; rr[i].bgr = g->bgr ? 1 : 0; }
+                if (g->clahe) {
+                    cr[i] = clahe_record(tab[i].slot, tab[i].geom, S.w, S.h, g->cp.clip_limit, g->cp.tiles_x, g->cp.tiles_y);
+                    cr[i].lut_off = (unsigned)i * lut_block;   // (i < frames_per_round: inside d_lut)
+                }
+                pre_w = std::max(pre_w, S.w); pre_h = std::max(pre_h, S.h);
+            }
+            if (!g->table) memcpy(blk + BatchIngest::OFF_GEOM, &S0.L, sizeof(PyrLayout));   // a bracket: its records name entry 0 of this table
+        }
+        if (g->copy_mode) {   // frames only for the range form; the table (+ frames) for the list form and for a preprocessing round
+            const bool whole = !range || (pre && !direct);   // header and frames in one copy (a preprocessing round has host frames only: nc > 0 unless direct)
+            if (pre && direct && (e = hipMemcpyAsync((void*)dblk, blk, BatchIngest::HDR_PRE, hipMemcpyHostToDevice, g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipMemcpyAsync", e); return; }
+            const uint8_t* from = direct ? S0.src + (size_t)take[0].second * S0.fb : whole ? blk : blk + BatchIngest::HDR;
+            const size_t off = whole ? 0 : BatchIngest::HDR;
+            const size_t bytes = whole ? (nc ? BatchIngest::HDR + cb : (size_t)n * sizeof(PyrListEntry)) : direct ? (size_t)n * S0.fb : cb;
             if (bytes && (e = hipMemcpyAsync((void*)(dblk + off), from, bytes, hipMemcpyHostToDevice, g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipMemcpyAsync", e); return; }
             if ((e = hipEventRecord(g->copied[buf], g->stream)) != hipSuccess) { fail(g, PMV_ERR_HIP, "hipEventRecord", e); return; }
         }
+        // Preprocessing: the gather in place of the level-0 launch, then the CLAHE pair, then the border in place - each ONE launch for the whole
+        // round, whatever sizes and maps it holds (the records name them). Their geometry table: the context's, or a bracket's own single entry.
+        const PyrLayout* pre_geom = g->table ? (const PyrLayout*)ctx->d_geom : (const PyrLayout*)(dblk + BatchIngest::OFF_GEOM);
+        auto gather = [&]() {   // level 0's interior from the landing buffer through the maps (counted where the level-0 launch it replaces is)
+            if ((e = launch_remap_src(g->stream, ctx->d_slots, pre_geom, (const RemapSrcRec*)(dblk + BatchIngest::OFF_REMAP), n, pre_w, pre_h)) != hipSuccess) {
+                fail(g, PMV_ERR_HIP, "k_remap_src", e); return false;
+            }
+            ctx->preproc_launches[1]++;
+            return true;
+        };
+        auto finish_level0 = [&](const PyrLayout* Lmax) {   // level 0's interior is in the slots; Lmax: of a list round, null: a range round
+            if (g->clahe) {
+                if ((e = launch_clahe(g->stream, ctx->d_slots, pre_geom, (const ClaheRec*)(dblk + BatchIngest::OFF_CLAHE), n, g->cp.tiles_x * g->cp.tiles_y, pre_w, pre_h,
+                                      g->d_lut)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_clahe_lut / k_clahe_apply", e); return false; }
+                ctx->preproc_launches[2]++;
+            }
+            e = Lmax ? launch_pad_level0_list(g->stream, ctx->d_slots, pre_geom, *Lmax, (const PyrListEntry*)(dblk + BatchIngest::OFF_INPLACE), n)
+                     : launch_pad_level0(g->stream, ctx->d_slots, S0.L, tab[0].slot, n, nullptr);
+            if (e != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pad_level0 (in place)", e); return false; }
+            ctx->preproc_launches[0]++; ctx->preproc_launches[3]++;
+            return true;
+        };
         int n_levels;
         if (range) {   // one geometry, by value
             const int first = tab[0].slot;
             n_levels = S0.L.n_levels;
-            e = g->bgr ? launch_pad_level0_bgr(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src)   // (every frame of a colour feed has a source)
-                       : launch_pad_level0(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src);
-            if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            if (g->remap) { if (!gather()) return; }
+            else {
+                e = g->bgr ? launch_pad_level0_bgr(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src)   // (every frame of a colour feed has a source)
+                           : launch_pad_level0(g->stream, ctx->d_slots, S0.L, first, n, tab[0].src);
+                if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            }
+            if (pre && !finish_level0(nullptr)) return;
             for (int l = 1; l < n_levels; l++)
                 if ((e = launch_pyrdown(g->stream, ctx->d_slots, S0.L, l, first, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
         } else {       // geometry per entry; grid, LDS and the levels launched from the largest geometry of THIS round
@@ -223,9 +292,13 @@ void ingest_loop(pmv_ctx* ctx, BatchIngest* g) {
             }
             n_levels = Lmax.n_levels;
             const PyrListEntry* dtab = (const PyrListEntry*)dblk;
-            e = g->bgr ? launch_pad_level0_bgr_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n)
-                       : launch_pad_level0_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n);
-            if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            if (g->remap) { if (!gather()) return; }
+            else {
+                e = g->bgr ? launch_pad_level0_bgr_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n)
+                           : launch_pad_level0_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, dtab, n);
+                if (e != hipSuccess) { fail(g, PMV_ERR_HIP, g->bgr ? "k_pad_level0_bgr" : "k_pad_level0", e); return; }
+            }
+            if (pre && !finish_level0(&Lmax)) return;
             for (int l = 1; l < n_levels; l++)
                 if ((e = launch_pyrdown_list(g->stream, ctx->d_slots, ctx->d_geom, Lmax, l, dtab, n)) != hipSuccess) { fail(g, PMV_ERR_HIP, "k_pyrdown", e); return; }
         }
@@ -292,8 +365,24 @@ int acquire(BatchIngest* g, int seq, int slot, int* round) {
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
-int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int format) {
+int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std::vector<FeedSeq>& seqs, int format, const pmv_frame_preproc* pre) {
     CKC(hipSetDevice(ctx->device));
+    // The preprocessing snapshot: every sequence with a host source finds the map of its size, before anything of the feed exists. (The
+    // setting's maps have pairwise different sizes and cannot be destroyed while it names them.)
+    std::vector<const uint32_t*> maps(seqs.size(), nullptr);
+    const bool pre_remap = pre && pre->n_maps > 0, pre_clahe = pre && pre->clahe != 0;
+    if (pre_remap) {
+        std::lock_guard<std::mutex> lk(ctx->remap_mu);
+        for (size_t b = 0; b < seqs.size(); b++) {
+            if (!seqs[b].src) continue;
+            for (int k = 0; k < pre->n_maps; k++) {
+                const pmv_ctx::RemapMap& m = ctx->remap_maps[pre->map_ids[k]];
+                if (m.d && m.w == seqs[b].w && m.h == seqs[b].h) maps[b] = (const uint32_t*)m.d;
+            }
+            REQ(maps[b], PMV_ERR_INVALID, "feeder: sequence %d: its frames are %dx%d and the frame preprocessing setting has no remap map of that size (pmv_set_frame_preproc)",
+                (int)b, seqs[b].w, seqs[b].h);
+        }
+    }
     if (!gp) {
         BatchIngest* g = new BatchIngest();
         gp = g;
@@ -315,7 +404,7 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
     for (int b = 0; b < B; b++) {
         BatchIngest::Seq& S = g->seq[b];
         const FeedSeq& q = seqs[(size_t)b];
-        S.first = q.first; S.n = q.n; S.ring = q.ring; S.src = q.src; S.dev = nullptr;
+        S.first = q.first; S.n = q.n; S.ring = q.ring; S.src = q.src; S.dev = nullptr; S.map = maps[(size_t)b];
         S.w = q.w; S.h = q.h; S.L = layout_for(ctx, q.w, q.h);
         S.geom = g->table ? ctx->geom_index(q.w, q.h) : 0;
         REQ(S.geom >= 0, PMV_ERR_INVALID, "feeder: sequence %d: no entry for %dx%d frames in the geometry table", b, q.w, q.h);
@@ -334,6 +423,9 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
         }
     }
     g->bgr = host && format == PMV_FRAMES_BGR;
+    g->remap = host && pre_remap; g->clahe = host && pre_clahe;   // (a feed with host sources has no others)
+    g->border = g->remap ? pre->border_value : 0;
+    if (g->clahe) g->cp = pre->clahe_params;
     g->max_fb = 1;
     for (int b = 0; b < B; b++) {
         g->seq[b].fb = (size_t)g->seq[b].w * g->seq[b].h * (g->bgr ? 3 : 1);
@@ -348,7 +440,8 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
     // (the DMA into HBM the single-sequence path has always used). A staged feed's slot tables are always copied into HBM, so its kernels do
     // not read them across the link. No result depends on it.
     const char* mode = getenv("PMV_BATCH_INGEST");
-    g->copy_mode = !host || (mode ? !strcmp(mode, "copy") : kind == FEED_BRACKET);
+    // A remap gathers 2 x 2 bytes per pixel: never across the host link, so such a feed lands every frame in HBM first.
+    g->copy_mode = !host || g->remap || (mode ? !strcmp(mode, "copy") : kind == FEED_BRACKET);
     g->dma_release = g->copy_mode && kind != FEED_STREAMED;   // (a streamed batch keeps the form it was measured with)
     if (g->buf_bytes < need) {   // both buffers are NBUF x buf_bytes: a landing area of the old size goes with the old staging
         g->buf_bytes = 0;
@@ -357,6 +450,7 @@ int batch_ingest_begin(pmv_ctx* ctx, BatchIngest*& gp, FeedKind kind, const std:
         g->buf_bytes = need;
     }
     if (g->copy_mode) CKC(g->d_land.ensure(BatchIngest::NBUF * g->buf_bytes));
+    if (g->clahe) CKC(g->d_lut.ensure((size_t)g->frames_per_round * (size_t)(g->cp.tiles_x * g->cp.tiles_y) * 256));
     g->ctx = ctx; g->B = B;
     // every slot of the feed carries its sequence's geometry and counts as built from here on: its readers wait for its round in slot_ready.
     // The first sequence that covers a slot builds it.
@@ -455,7 +549,7 @@ int pmv_frames_stream_begin(pmv_ctx* ctx, int first_slot, int n, const uint8_t* 
     CKC(hipSetDevice(ctx->device));
     // frames in the slots about to be overwritten may still be read by work in flight on the front-end stream
     CKC(hipStreamSynchronize(ctx->s_front));
-    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray, w, h}}, ctx->frame_format);
+    return batch_ingest_begin(ctx, ctx->ingest, FEED_BRACKET, {FeedSeq{first_slot, n, n, gray, w, h}}, ctx->frame_format, &ctx->preproc);
 }
 
 int pmv_frames_stream_end(pmv_ctx* ctx) {

@@ -122,6 +122,12 @@ struct pmv_ctx {
     int ba_mode = 0;
     // pmv_set_frame_format: what the host frames of pmv_frames_stage, pmv_frames_stream_begin and the streamed runs hold (pmv_frame_format)
     int frame_format = PMV_FRAMES_GRAY;
+    // pmv_set_frame_preproc: remap and / or CLAHE of every host frame that enters a slot through a feeder (the bracket and the two streamed
+    // runs); all zero = off. A feed takes a snapshot (batch_ingest_begin); changed only while no bracket or batched run is open. A map that it
+    // names cannot be destroyed.
+    pmv_frame_preproc preproc = {};
+    // pmv_debug_preproc_launches: feeder rounds that preprocessed | gather launches | CLAHE launch pairs | in-place border launches made for them
+    std::atomic<long long> preproc_launches[4];
     // pmv_set_lk_params: the window and level cap shape every layout made from now on (layout_for, cap), the stop criteria go to the LK
     // launches as they are (lk_launch_params). Changed only while no bracket, batched run or session is open, so the launches read them freely.
     pmv_lk_params lk = {pmv::LK_WIN, 4, 30, 0.01, 1e-4f};

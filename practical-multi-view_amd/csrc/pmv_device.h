@@ -347,5 +347,20 @@ bool undistort_map(const double* K, const double* dist8, const double* R, const 
 // level-0 width and height among the records - they size the grid; a thread beyond its own frame leaves before its first load. Booked under
 // the level-0 profiling class.
 hipError_t launch_remap(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const RemapRec* d_recs, int n, int max_w, int max_h, uint8_t* d_scratch);
+// The feeder's form (pmv_set_frame_preproc): the same gather with its taps in a TIGHT source frame at a device address - the round's
+// landing buffer in HBM - instead of a slot, and the interior of level 0 of the slot as its destination (row pitch stride[0], base gray_off),
+// so source and destination are different memory and no scratch frame exists. bgr != 0: the source is tight BGR (3 w h bytes) and every tap
+// is converted with cvtColor's integer rule before the weights - the value k_pad_level0_bgr would have stored. The in-place level-0 launch
+// behind it adds the REFLECT_101 frame.
+struct __attribute__((aligned(16))) RemapSrcRec {
+    const uint32_t* map;          // the packed map of the frame's size
+    const uint8_t* src;           // the tight source frame (device memory)
+    int slot, geom;               // destination slot, entry of the launch's geometry table
+    int border;                   // cv's borderValue, 0..255
+    int bgr;                      // 0: w h gray bytes, else 3 w h BGR bytes
+};
+static_assert(sizeof(RemapSrcRec) == 32, "RemapSrcRec: one 32-byte record per frame");
+// k_remap_src over n records in device-visible memory; max_w, max_h as for launch_remap. Booked under the level-0 profiling class.
+hipError_t launch_remap_src(hipStream_t s, uint8_t* slots, const PyrLayout* d_geom, const RemapSrcRec* d_recs, int n, int max_w, int max_h);
 
 }  // namespace pmv
