@@ -25,6 +25,7 @@
  *   pmv_fivepoint_hypotheses               cv::findEssentialMat (RANSAC hypotheses)      (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
  *   pmv_triangulate_candidates             cv::recoverPose (triangulation + cheirality)  (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_find_essential_mat                 cv::findEssentialMat (the whole RANSAC)       (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
+ *   pmv_find_fundamental_mat               cv::findFundamentalMat, FM_RANSAC (a KLT loop's rejectWithF; not a call of the reference)
  *   pmv_recover_pose                       cv::recoverPose (the whole call)              (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_ba_residuals / pmv_ba_solve        ProjectionResidual + ceres::Solve             (ProjectionResidual.h:38-58,
  *                                          CeresBundleAdjustment.cpp:50-61)              -> BaseOptimizer.h:15
@@ -575,6 +576,62 @@ int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const 
  * `denom >= 0 || -num >= maxIters * (-denom) ? maxIters : lrint(num / denom)`. n < 0 or a null pointer: PMV_ERR_INVALID. */
 int pmv_debug_essential_iters_table(int n, double prob, double* out_denoms, double* out_num);
 
+/* ---- fundamental-matrix RANSAC: the rejectWithF of a KLT loop ------------------------------------------------------------------------------
+ * cv::findFundamentalMat(points1, points2, FM_RANSAC, threshold, confidence, mask) for n >= 15 correspondences, the step of a VINS-style
+ * tracker between pmv_lk_track_fb and the masked re-detection: the tracks that survive the forward-backward check but violate the epipolar
+ * geometry are masked out. p1_xy, p2_xy: n pixel positions (x, y) as float32 (cv converts its input to CV_32F; the LK calls return float32, so
+ * the outputs of pmv_lk_track_fb go in directly); F9 row-major; mask n bytes; *out_samples_drawn = RANSAC iterations made. *out_found 0 = no
+ * model (cv returns an empty Mat): F9 untouched, mask all 0. The whole adaptive RANSAC runs in ONE launch, one workgroup per call
+ * (k_fundamental_ransac); the result has the bits of tests/twin/fundamental_twin.cpp.
+ * [mem: OpenCV 3.4 fundam.cpp, ptsetreg.cpp; parity with a real OpenCV unpinned like the rest - tests/twin/fundamental_twin.cpp is the CPU
+ * restatement that fixes the bits]
+ *   Branch by n. cv runs the RANSAC only for n >= 15; at n = 7 it returns up to three stacked matrices, for 8..14 it switches to LMedS.
+ *     Neither is built (nor FM_8POINT, FM_LMEDS or a normalised eight-point refit): n < 15 is PMV_ERR_DEGENERATE and the message says why - a
+ *     KLT loop with that few tracks re-detects anyway. n < 0 or n > max_tracks: PMV_ERR_CAPACITY.
+ *   Sampling: RANSACPointSetRegistrator::getSubset with 7 model points. rng = cv::RNG((uint64)-1) per call; a draw is rng % n; a duplicate is
+ *     redrawn without counting an attempt; a full subset goes through FMEstimatorCallback::checkSubset and is refused if haveCollinearPoints
+ *     holds for either image. haveCollinearPoints has cv's quirk: only the LAST point of the subset is tested, against every pair (j, k < j)
+ *     of the earlier ones, fabs(dx2*dy1 - dy2*dx1) <= FLT_EPSILON*(fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2)) with the differences taken as
+ *     float subtractions widened to double. Attempts per subset: 10000 - getSubset's default is 1000, but RANSACPointSetRegistrator::run passes
+ *     10000, and that is followed here. No subset at iteration 0: no model, 0 samples drawn; at a later iteration: the loop ends there.
+ *   Seven-point solver (run7Point): no normalisation; row i of the 7x9 system is [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1]; f1, f2 a
+ *     basis of its null space; the cubic is det(lambda f1 + (1 - lambda) f2) = 0. As in cv, f1 -= f2 comes first and everything after it is
+ *     written in that difference: det(lambda f1 + f2) with cv's expressions for the four coefficients; per real root s = f1[8] lambda + f2[8]; fabs(s) > DBL_EPSILON:
+ *     mu = 1 / s, lambda *= mu, F[8] = 1, else mu = 1 and F[8] = 0; F[i] = f1[i] lambda + f2[i] mu for i < 8. Up to three models.
+ *     Two places cannot have cv's bits on a device, the twin fixes both. The null space: cv takes it from its SVD; here Gauss-Jordan with
+ *     complete pivoting on the 7x9 system, then the two vectors of the free columns normalised to unit length (the construction of the
+ *     five-point solver's 5x9 case). The cubic: cv's solveCubic calls acos, cos and pow, and the device's libm is not glibc's; its case
+ *     analysis is kept exactly - leading coefficients that are zero (quadratic, linear, none), then Q, R and the sign of Q^3 - R^2 - because it
+ *     decides HOW MANY roots there are; their VALUES come from IEEE + - * / sqrt only: one real root inside the Cauchy bound 1 + max |a_i| by
+ *     Newton's iteration kept inside a shrinking bracket (bisection where it leaves; at most 200 steps, over when the iterate no longer
+ *     changes), deflation to a quadratic solved in its stable form, two Newton steps per root on the undeflated cubic (a step is taken only
+ *     where |f| does not grow). Order of three roots: smallest, largest, middle, which is the order of cv's cos(t), cos(t + 2 pi / 3),
+ *     cos(t + 4 pi / 3), so that "the first model that beats the best wins" breaks ties as cv does. Q^3 - R^2 == 0: cv's pow(R, 1/3) is
+ *     sign(R) sqrt(Q) there.
+ *   Error and inliers (FMEstimatorCallback::computeError): err = (float)max(d1^2 s1, d2^2 s2), the two squared point-to-epipolar-line
+ *     distances in double from the float points; inlier iff err <= (float)(threshold * threshold). A model becomes the best iff its count >
+ *     max(maxGood, 6); then niters = RANSACUpdateNumIters(confidence, (n - count) / n, 7, niters), starting from 1000, with pow and log on
+ *     the host (pmv_debug_fundamental_iters_table). No refit on the inliers: cv has none for F.
+ *   Errors: null pointers, a threshold that is not positive and finite, a confidence outside (0, 1) or not finite (cv silently substitutes
+ *     3 and 0.99 for such values; here they are refused), a coordinate that is not finite or beyond 1e6 in magnitude (the message names the
+ *     point): PMV_ERR_INVALID. On an error nothing is written and nothing is clamped. Not logged by pmv_record_enable; the whole-sequence
+ *     drivers do not call this. */
+int pmv_find_fundamental_mat(pmv_ctx* ctx, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9,
+                             uint8_t* mask, int* out_found, int* out_samples_drawn);
+/* diagnostic, ctx-free: pmv_debug_essential_iters_table for the 7 model points of pmv_find_fundamental_mat: *out_num = log(1 - confidence),
+ * out_denoms[g] = log(1 - (1 - (n - g) / n)^7) for g = 0..n (n + 1 doubles; -infinity where RANSACUpdateNumIters returns 0 before its
+ * logarithms). n < 0 or a null pointer: PMV_ERR_INVALID. */
+int pmv_debug_fundamental_iters_table(int n, double confidence, double* out_denoms, double* out_num);
+/* diagnostic, process-wide: hypotheses per in-kernel round of k_fundamental_ransac from the next launch on, 1..64; 0 = back to PMV_FUNDAMENTAL_R
+ * or the default (64). The results do not depend on it. Outside 0..64: PMV_ERR_INVALID. */
+int pmv_debug_set_fundamental_r(int r);
+/* diagnostic, process-wide: the round width the next k_fundamental_ransac launch takes (the setter's value, else PMV_FUNDAMENTAL_R clamped to
+ * 1..64, else 64). */
+int pmv_debug_fundamental_r(void);
+/* diagnostic: out3 = {k_fundamental_ransac launches, k_essential_ransac launches, rounds that made both} of the five-point combiner's
+ * whole-RANSAC rounds (pmv_batch_find_fundamental_mat, pmv_batch_find_essential_mat, device_fivepoint = 2) since the context was created. */
+int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3);
+
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those
  * made from inside pmv_pipeline_run) appends one blob holding its inputs and outputs, so that a test can replay the calls
@@ -813,6 +870,13 @@ int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, con
                                  double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
                            uint8_t* mask, double* tri4n, int* out_good);
+/* pmv_find_fundamental_mat for a seq, argument for argument (its rules: n >= 15 else PMV_ERR_DEGENERATE, n <= max_tracks else
+ * PMV_ERR_CAPACITY, the no-model convention) with `seq` (0 .. n_seq - 1, else PMV_ERR_INVALID) after the context; the bits of the single call.
+ * A request of the five-point combiner: a round serves all its fundamental requests with ONE k_fundamental_ransac launch, one workgroup per
+ * request, on top of the launch for the round's essential requests, and a call returns as soon as ITS request is complete. One outstanding
+ * call per seq and call, as for pmv_batch_find_essential_mat. */
+int pmv_batch_find_fundamental_mat(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence,
+                                   double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 /* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds (+ 1 for a
  * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation; + 1 for a round with
  * pmv_batch_frame_upload_remap requests: the launch from the remap scratch), and the

@@ -192,6 +192,7 @@ ABI_SYMBOLS = [
     "pmv_debug_mem_live",
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
+    "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -199,7 +200,7 @@ ABI_SYMBOLS = [
     "pmv_batch_open", "pmv_batch_close", "pmv_batch_frame_upload", "pmv_batch_upload_stats", "pmv_batch_upload_rounds",
     "pmv_batch_lk_track", "pmv_batch_lk_track_ex", "pmv_batch_lk_track_fb", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
     "pmv_batch_pnp_ransac", "pmv_batch_ba_solve", "pmv_batch_triangulate_candidates", "pmv_batch_fivepoint_hypotheses",
-    "pmv_batch_find_essential_mat", "pmv_batch_recover_pose",
+    "pmv_batch_find_essential_mat", "pmv_batch_recover_pose", "pmv_batch_find_fundamental_mat",
 ]
 
 
@@ -947,6 +948,24 @@ class Context:
         """cv::recoverPose(E, p1, p2, K, R, t, HUGE_VAL, mask, tri): (R (3, 3), t (3,), mask out (n,), tri (4, n) homogeneous, good)"""
         return self._recover_pose(self.lib.pmv_recover_pose, self._ck, (), E, p1, p2, K, mask)
 
+    def _find_fundamental(self, call, ck, head, p1, p2, threshold, confidence):
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        if p1.shape != p2.shape:
+            raise ValueError(f"p1 {p1.shape} and p2 {p2.shape}: one (x, y) pair per correspondence in each")
+        n = p1.shape[0]
+        F = np.zeros(9, np.float64)
+        mask = np.zeros(n, np.uint8)
+        found, drawn = C.c_int(), C.c_int()
+        ck(call(self.h, *head, _p(p1, _f32p), _p(p2, _f32p), n, C.c_double(threshold), C.c_double(confidence), _p(F, _f64p), _p(mask, _u8p),
+                C.byref(found), C.byref(drawn)))
+        return bool(found.value), F.reshape(3, 3), mask, drawn.value
+
+    def find_fundamental_mat(self, p1, p2, threshold=1.0, confidence=0.99):
+        """cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence, mask) for n >= 15 float32 correspondences, the whole RANSAC in one
+        launch (a KLT loop's rejectWithF): (found, F (3, 3), mask (n,), samples drawn); found False = no model (F zeros, mask all 0)"""
+        return self._find_fundamental(self.lib.pmv_find_fundamental_mat, self._ck, (), p1, p2, threshold, confidence)
+
     # ---- call log (teacher-forced replay) ----
     def record_enable(self, on=True):
         self._ck(self.lib.pmv_record_enable(self.h, 1 if on else 0))
@@ -1333,6 +1352,10 @@ class Context:
     def batch_find_essential_mat(self, seq, p1, p2, K, prob=0.99, threshold=1.0):
         """find_essential_mat for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""
         return self._find_essential(self.lib.pmv_batch_find_essential_mat, self._ckt, (int(seq),), p1, p2, K, prob, threshold)
+
+    def batch_find_fundamental_mat(self, seq, p1, p2, threshold=1.0, confidence=0.99):
+        """find_fundamental_mat for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""
+        return self._find_fundamental(self.lib.pmv_batch_find_fundamental_mat, self._ckt, (int(seq),), p1, p2, threshold, confidence)
 
     def batch_recover_pose(self, seq, E, p1, p2, K, mask):
         return self._recover_pose(self.lib.pmv_batch_recover_pose, self._ckt, (int(seq),), E, p1, p2, K, mask)

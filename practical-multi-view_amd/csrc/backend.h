@@ -26,6 +26,8 @@ struct BackendBuffers {   // every buffer: one row of backend_alloc's table; fre
     Buf<char> d_tri_in, d_tri_out;
     Buf<char> d_fp_work;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in)
     Buf<char> d_ess_in;    // whole findEssentialMat RANSAC: [EssentialProblem 64 B | q1 2n | q2 2n | iteration table n + 2 doubles]
+    Buf<char> d_fund_in;   // whole findFundamentalMat RANSAC: [FundamentalProblem 64 B | p1 2n floats | p2 2n floats | iteration table n + 2 doubles];
+                           // sized by max_tracks, made by the set's first such call (fundamental_prepare)
     // single-copy transfers: one mapped pinned staging block (result blocks are written straight into it through .dm()) and one device
     // block per direction
     Buf<char> h_stage;
@@ -112,6 +114,20 @@ constexpr int ESS_MAX_WAVES = 16;   // hypotheses per in-kernel round at most (w
 constexpr int ESS_DEFAULT_WAVES = 8;   // R of DESIGN.md §4: 8 x 6.2 KB = 49 KB of LDS, three workgroups per CU
 int essential_round_width();        // hypotheses per in-kernel round (PMV_ESSENTIAL_R overrides the default, 1..ESS_MAX_WAVES)
 hipError_t launch_essential_ransac(hipStream_t s, const EssentialProblem* d_probs, int n_probs);
+// one whole cv::findFundamentalMat RANSAC (k_fundamental_ransac, backend_fundamental.hip): one workgroup runs the adaptive loop of one request
+struct FundamentalProblem {
+    const float* p1; const float* p2;     // device: n pixel positions (x, y) each
+    const double* iters;                  // device: the table of EssentialProblem::iters for 7 model points
+    char* out;                            // mapped pinned result block in EssentialProblem::out's layout, F in the place of E
+    int n, max_iters; float thr;
+    unsigned done_seq;                    // != 0; the kernel's last store, as EssentialProblem::done_seq
+};
+static_assert(sizeof(FundamentalProblem) <= ESS_HDR, "the record is the header of the input block");
+constexpr int FUND_MAX_R = 64;       // hypotheses per in-kernel round at most (one lane of a wavefront each)
+constexpr int FUND_DEFAULT_R = 64;   // R of DESIGN.md §4 (measured: the widest round is the fastest on eight of nine ubench rows)
+int fundamental_round_width();       // hypotheses per in-kernel round (PMV_FUNDAMENTAL_R overrides the default, 1..FUND_MAX_R)
+void fundamental_set_round_width(int r);   // pmv_debug_set_fundamental_r: r in 1..FUND_MAX_R from the next launch on, 0 = back to the above
+hipError_t launch_fundamental_ransac(hipStream_t s, const FundamentalProblem* d_probs, int n_probs);
 // one two-view problem of a batched DLT launch
 struct DltProblem { const double* P1x4; const double* q1; const double* q2; const uint8_t* mask_in; double* Q; uint8_t* mask; int n; };
 hipError_t launch_tri_dlt_batch(hipStream_t s, const DltProblem* d_probs, int n_probs, int max_n);
@@ -149,6 +165,14 @@ void essential_prepare(BackendBuffers* b, const double* p1_xy, const double* p2_
                        EssentialProblem* P, size_t* in_bytes);
 volatile unsigned* essential_done_word(BackendBuffers* b, size_t in_bytes);
 void essential_finish(BackendBuffers* b, int n, size_t in_bytes, double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+// whole findFundamentalMat: argument rules of pmv_find_fundamental_mat (outputs untouched on error); prepare makes b's d_fund_in on first use,
+// copies the points into b's pinned block behind the problem record, builds the iteration table with the host's libm and clears the completion
+// word (essential_done_word serves both calls: the result blocks share their layout); finish reads the result block
+int fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9,
+                      uint8_t* mask, int* out_found, int* out_samples_drawn);
+int fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence,
+                        FundamentalProblem* P, size_t* in_bytes);
+void fundamental_finish(BackendBuffers* b, int n, size_t in_bytes, double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 // cv::recoverPose around a DLT launch: `dlt` is pmv_triangulate_candidates' contract on the caller's workspace set; PMV_OK or its error
 int recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
                        double* t3, uint8_t* mask, double* tri4n, int* out_good);

@@ -709,6 +709,74 @@ int pmv::recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, con
     return PMV_OK;
 }
 
+// Waits for a whole-RANSAC kernel's last store, the call's sequence number in its result block (PMV_BACK_WAIT=sync: hipStreamSynchronize
+// instead; see pmv_pnp_ransac). Shared by pmv_find_essential_mat and pmv_find_fundamental_mat.
+static int wait_done_word(pmv_ctx* ctx, hipStream_t s, volatile unsigned* done_word, unsigned done_seq) {
+    static const bool flag_wait = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
+    if (!flag_wait) { CKC(hipStreamSynchronize(s)); return PMV_OK; }
+    (void)hipStreamQuery(s);
+    for (unsigned spins = 1;; spins++) {
+        if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == done_seq) break;
+        if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
+            const hipError_t e = hipStreamQuery(s);
+            if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
+        }
+        __builtin_ia32_pause();
+    }
+    return PMV_OK;
+}
+
+// ---- whole findFundamentalMat RANSAC on the device (k_fundamental_ransac): check / prepare / finish -------------------------------------
+int pmv::fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9,
+                           uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    REQ(ctx && p1_xy && p2_xy && F9 && mask && out_found && out_samples_drawn, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(threshold > 0 && std::isfinite(threshold), PMV_ERR_INVALID, "%s: threshold = %g (a positive finite number of pixels)", who, threshold);
+    REQ(confidence > 0 && confidence < 1, PMV_ERR_INVALID, "%s: confidence = %g outside (0, 1)", who, confidence);   // (a NaN fails the comparison too)
+    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, ctx->max_tracks);
+    // cv::findFundamentalMat runs RANSAC only from 15 points on: LMedS for 8..14, up to three stacked matrices for 7 - neither is built
+    REQ(n >= 15, PMV_ERR_DEGENERATE, "%s: %d correspondences (the RANSAC needs >= 15; cv switches to LMedS or the plain 7-point result below, which are not built)", who, n);
+    for (int k = 0; k < 2; k++) {
+        const float* p = k ? p2_xy : p1_xy;
+        for (int i = 0; i < 2 * n; i++)
+            REQ(fabsf(p[i]) <= 1e6f, PMV_ERR_INVALID, "%s: point %d of image %d (%g, %g) is not finite or beyond 1e6", who, i / 2, k + 1, (double)p[i & ~1], (double)p[i | 1]);
+    }
+    return PMV_OK;
+}
+// pinned in-block [FundamentalProblem (ESS_HDR bytes) | p1 2n floats | p2 2n floats | log(1 - confidence), n + 1 denominators], out-block as
+// essential_prepare's with F in the place of E
+int pmv::fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, const float* p2, int n, double threshold, double confidence,
+                             FundamentalProblem* P, size_t* in_bytes_out) {
+    const size_t fund_in_bytes = ESS_HDR + (size_t)ctx->max_tracks * 24 + 16 + 64;
+    if (b->d_fund_in.cap < fund_in_bytes) {   // the set's first such call: a session caller's thread has not chosen the context's device yet
+        CKC(hipSetDevice(ctx->device));
+        CKC(b->d_fund_in.ensure(fund_in_bytes));
+    }
+    char* hs = (char*)b->h_stage;
+    float* h_p1 = (float*)(hs + ESS_HDR);
+    float* h_p2 = h_p1 + (size_t)2 * n;
+    double* h_it = (double*)(h_p2 + (size_t)2 * n);
+    const size_t in_bytes = ESS_HDR + (size_t)n * 16 + ((size_t)n + 2) * 8;
+    memcpy(h_p1, p1, (size_t)n * 8);
+    memcpy(h_p2, p2, (size_t)n * 8);
+    vo::ransac_iters_table(n, confidence, 7, h_it + 1, h_it);
+    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
+    P->p1 = (const float*)(b->d_fund_in + ESS_HDR);
+    P->p2 = P->p1 + (size_t)2 * n;
+    P->iters = (const double*)(P->p2 + (size_t)2 * n);
+    P->out = b->h_stage.dm() + (ho - hs);
+    P->n = n; P->max_iters = 1000;
+    P->thr = (float)(threshold * threshold);
+    if (++b->done_seq == 0) b->done_seq = 1;
+    P->done_seq = b->done_seq;
+    *(volatile unsigned*)(ho + 92) = 0;
+    *(FundamentalProblem*)hs = *P;
+    *in_bytes_out = in_bytes;
+    return PMV_OK;
+}
+void pmv::fundamental_finish(BackendBuffers* b, int n, size_t in_bytes, double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    essential_finish(b, n, in_bytes, F9, mask, out_found, out_samples_drawn);   // (the same result block)
+}
+
 extern "C" {
 
 int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
@@ -727,20 +795,7 @@ int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_x
     hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_ess_in, n16);
     CKC(hipGetLastError());
     CKC(launch_essential_ransac(s, (const EssentialProblem*)b->d_ess_in, 1));
-    // the kernel's last store is this call's sequence number in the result block (PMV_BACK_WAIT=sync: hipStreamSynchronize instead; see pmv_pnp_ransac)
-    static const bool flag_wait = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
-    if (flag_wait) {
-        volatile unsigned* done_word = essential_done_word(b, in_bytes);
-        (void)hipStreamQuery(s);
-        for (unsigned spins = 1;; spins++) {
-            if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == P.done_seq) break;
-            if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
-                const hipError_t e = hipStreamQuery(s);
-                if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
-            }
-            __builtin_ia32_pause();
-        }
-    } else CKC(hipStreamSynchronize(s));
+    if (const int rc = wait_done_word(ctx, s, essential_done_word(b, in_bytes), P.done_seq)) return rc;
     essential_finish(b, n, in_bytes, E9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
@@ -765,6 +820,39 @@ int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const 
     memcpy(R9, R, 72); memcpy(t3, t, 24);
     if (n > 0) { memcpy(mask, m.data(), (size_t)n); memcpy(tri4n, q.data(), (size_t)4 * n * 8); }
     *out_good = good;
+    return PMV_OK;
+}
+
+int pmv_find_fundamental_mat(pmv_ctx* ctx, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
+                             int* out_found, int* out_samples_drawn) {
+    if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    BackendBuffers* b = ctx->be;
+    hipStream_t s = ctx->s_back;
+    FundamentalProblem P;
+    size_t in_bytes = 0;
+    if (const int rc = fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, &P, &in_bytes)) return rc;
+    const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
+    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_fund_in, n16);
+    CKC(hipGetLastError());
+    CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)b->d_fund_in, 1));
+    if (const int rc = wait_done_word(ctx, s, essential_done_word(b, in_bytes), P.done_seq)) return rc;
+    fundamental_finish(b, n, in_bytes, F9, mask, out_found, out_samples_drawn);
+    return PMV_OK;
+}
+
+int pmv_debug_fundamental_iters_table(int n, double confidence, double* out_denoms, double* out_num) {
+    if (n < 0 || !out_denoms || !out_num) return PMV_ERR_INVALID;
+    vo::ransac_iters_table(n, confidence, 7, out_denoms, out_num);
+    return PMV_OK;
+}
+
+int pmv_debug_fundamental_r(void) { return fundamental_round_width(); }
+
+int pmv_debug_set_fundamental_r(int r) {
+    if (r < 0 || r > FUND_MAX_R) return PMV_ERR_INVALID;
+    fundamental_set_round_width(r);
     return PMV_OK;
 }
 

@@ -51,4 +51,7 @@ int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2
 // seen (or, after a failed launch, with the combiner's error), which may be before the round's launch ends
 int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
                      uint8_t* mask, int* out_found, int* out_samples_drawn);
+// pmv_find_fundamental_mat's contract, in the same form: one workgroup of the round's k_fundamental_ransac launch
+int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
+                       int* out_found, int* out_samples_drawn);
 }  // namespace pmv

@@ -35,7 +35,7 @@ namespace pmv {
 namespace {
 
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners), 6 corner sub-pixel refinement (the detector combiner) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat
+    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners), 6 corner sub-pixel refinement (the detector combiner) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat, 15 whole findFundamentalMat
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -85,11 +85,14 @@ struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
 struct DltReq : Req { BackendBuffers* b; DltProblem P; size_t in_bytes; };
 struct FPReq : Req { BackendBuffers* b; FivePointProblem P; size_t in_bytes; };
-// kind 14: a whole findEssentialMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
+// kinds 14, 15: a whole findEssentialMat / findFundamentalMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
 // before the round's launch ends (a round ends with its slowest request) - so the record cannot live on the caller's stack like the others:
-// the combiner's store into `done` after its stream sync would land in a dead frame. The engine owns one record per seq; `inflight` is 1 from
-// the submit until the combiner has released the record after the round, and the seq's next call waits for that before it fills the record again.
-struct EssReq : Req { BackendBuffers* b = nullptr; EssentialProblem P; size_t in_bytes = 0; std::atomic<int> inflight{0}; };
+// the combiner's store into `done` after its stream sync would land in a dead frame. The engine owns one record per seq and kind; `inflight` is 1
+// from the submit until the combiner has released the record after the round, and the seq's next call of that kind waits for that before it
+// fills the record again.
+struct WholeReq : Req { BackendBuffers* b = nullptr; size_t in_bytes = 0; std::atomic<int> inflight{0}; };
+struct EssReq : WholeReq { EssentialProblem P; };
+struct FundReq : WholeReq { FundamentalProblem P; };
 
 // per-round scratch of a combiner: grows with slack (GROW_SLACK), in HBM or in mapped pinned memory (.dev = the address kernels use)
 struct DScratch : Growable { DScratch() : Growable(MEM_DEVICE, GROW_SLACK) {} };
@@ -164,7 +167,8 @@ struct BatchEngine {
     int max_linger_us = 300;
     int wait_mode = 3;   // 0 spin (hipStreamSynchronize), 1 query + yield, 2 blocking event, 3 completion word + timed sleeps
     std::vector<BackendBuffers*> slots;   // one back-end workspace set per concurrent sequence
-    std::unique_ptr<EssReq[]> ess;        // one whole-findEssentialMat request record per concurrent sequence (see EssReq)
+    std::unique_ptr<EssReq[]> ess;        // one whole-findEssentialMat request record per concurrent sequence (see WholeReq)
+    std::unique_ptr<FundReq[]> fund;      // ... and one whole-findFundamentalMat record
     // combiners (thread + stream) per class. Round 2, host-bound: 2 and 3 per class cost more host CPU (smaller batches) than they won in
     // latency (25.7k -> 23.3k -> 19.5k frames/s at B = 64). Round 3, with the track tables the host has headroom and the LK class is the one
     // that is busy all the time - a launch ends with its slowest track, so a single LK stream idles most SIMDs during every tail: PMV_BATCH_LANES
@@ -719,26 +723,46 @@ void process_fp_rounds(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     SYNC_TIMED(C);
 }
 
-// whole findEssentialMat calls: ONE k_essential_ransac launch for the round, one workgroup per request. Each workgroup signals its own
-// caller; the sync below is the fallback (a failed launch releases everyone with an error) and what makes the records reusable.
-void process_essential(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    DescBlock<EssentialProblem> D;
-    EK(desc_block(C, batch.size(), D));
-    for (size_t i = 0; i < batch.size(); i++) {
-        EssReq* r = (EssReq*)batch[i];
-        D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ess_in, (unsigned)r->in_bytes, 0};
+// whole findEssentialMat and findFundamentalMat calls: ONE k_essential_ransac launch for the round's requests of the first kind, ONE
+// k_fundamental_ransac launch for those of the second, one workgroup per request, behind one k_stage_in launch for both. The descriptor block
+// is [EssentialProblem records | FundamentalProblem records | stage-in jobs]. The fundamental launch goes first: its requests take a fraction
+// of a five-point request's time and would otherwise wait on the stream behind all of them. Each workgroup signals its own caller; the sync
+// below is the fallback (a failed launch releases everyone with an error) and what makes the records reusable.
+void process_whole(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+    std::vector<EssReq*> ess; std::vector<FundReq*> fund;
+    for (Req* r : batch) { if (r->kind == 14) ess.push_back((EssReq*)r); else fund.push_back((FundReq*)r); }
+    const size_t ne = ess.size(), nf = fund.size();
+    const size_t off_f = (sizeof(EssentialProblem) * ne + 255) & ~(size_t)255;
+    const size_t off_jobs = (off_f + sizeof(FundamentalProblem) * nf + 255) & ~(size_t)255;
+    EK(C.h_desc.ensure(off_jobs + sizeof(StageJob) * (ne + nf + 1) + 256));
+    EK(C.d_desc.ensure(off_jobs + 256));
+    char* hd = (char*)C.h_desc.p;
+    EssentialProblem* hess = (EssentialProblem*)hd; FundamentalProblem* hfund = (FundamentalProblem*)(hd + off_f);
+    StageJob* hjobs = (StageJob*)(hd + off_jobs);
+    hjobs[0] = StageJob{C.h_desc.dev, (char*)C.d_desc.p, (unsigned)off_jobs, 0};   // job 0: the records themselves
+    for (size_t i = 0; i < ne; i++) {
+        hess[i] = ess[i]->P;
+        hjobs[1 + i] = StageJob{(const char*)ess[i]->b->h_stage.dm(), ess[i]->b->d_ess_in, (unsigned)ess[i]->in_bytes, 0};
     }
-    EK(stage_in(C, D, batch.size(), 2));
-    EK(launch_essential_ransac(C.s, D.dprob, (int)batch.size()));
+    for (size_t i = 0; i < nf; i++) {
+        hfund[i] = fund[i]->P;
+        hjobs[1 + ne + i] = StageJob{(const char*)fund[i]->b->h_stage.dm(), fund[i]->b->d_fund_in, (unsigned)fund[i]->in_bytes, 0};
+    }
+    hipLaunchKernelGGL(k_stage_in, dim3(2, (unsigned)(ne + nf + 1)), dim3(256), 0, C.s, (const StageJob*)(C.h_desc.dev + off_jobs));
+    EK(hipGetLastError());
+    EK(launch_fundamental_ransac(C.s, (const FundamentalProblem*)((char*)C.d_desc.p + off_f), (int)nf));
+    EK(launch_essential_ransac(C.s, (const EssentialProblem*)C.d_desc.p, (int)ne));
+    if (nf) E->ctx->whole_rounds[0]++;
+    if (ne) E->ctx->whole_rounds[1]++;
+    if (nf && ne) E->ctx->whole_rounds[2]++;
     SYNC_TIMED(C);
 }
 
 void process_fp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    std::vector<Req*> rounds, whole;   // (the two forms share the class; a round that holds both serves them one after the other)
-    for (Req* r : batch) (r->kind == 14 ? whole : rounds).push_back(r);
+    std::vector<Req*> rounds, whole;   // (the forms share the class; a round that holds both serves them one after the other)
+    for (Req* r : batch) (r->kind >= 14 ? whole : rounds).push_back(r);
     if (!rounds.empty()) process_fp_rounds(E, C, rounds);
-    if (!whole.empty()) process_essential(E, C, whole);
+    if (!whole.empty()) process_whole(E, C, whole);
 }
 
 static inline void futex_wait_while(std::atomic<int>* w, int v) {
@@ -821,11 +845,11 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
         C->batches++; C->requests += (long)batch.size();
         for (Req* r : batch) {
             std::atomic<int>* w = &r->done;   // (after the store the owner may return and the request, which lives on its stack, is gone)
-            const bool engine_owned = r->kind == 14;
+            const bool engine_owned = r->kind >= 14;
             w->store(1, std::memory_order_release);
             futex_wake_one(w);
             if (engine_owned) {   // the record may be filled again from here on
-                std::atomic<int>* f = &((EssReq*)r)->inflight;
+                std::atomic<int>* f = &((WholeReq*)r)->inflight;
                 f->store(0, std::memory_order_release);
                 futex_wake_one(f);
             }
@@ -901,6 +925,7 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
         if (rc != PMV_OK) { batch_engine_destroy(ctx); return rc; }
     }
     E->ess.reset(new EssReq[(size_t)B]);
+    E->fund.reset(new FundReq[(size_t)B]);
     E->cap_tracks = (size_t)B * ctx->max_tracks;
     if (const char* e = getenv("PMV_BATCH_EXCLUSIVE")) E->exclusive = atoi(e) != 0;
     if (const char* e = getenv("PMV_LK_LPT")) E->lk_lpt = atoi(e) != 0;
@@ -1143,6 +1168,21 @@ int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2
 
 namespace pmv {
 
+// The wait of a whole-RANSAC request: whichever comes first, the completion word that its own workgroup stores last into the seq's pinned
+// result block, or the combiner's done flag after the round's stream sync (the only one a failed launch gives).
+static int wait_whole(pmv_ctx* ctx, WholeReq& r, volatile unsigned* word, unsigned want) {
+    for (;;) {
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return PMV_OK;
+        if (r.done.load(std::memory_order_acquire)) {   // the round is over
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return PMV_OK;
+            const int rc = r.rc != PMV_OK ? r.rc : PMV_ERR_HIP;
+            set_err(ctx, "%s", r.rc != PMV_OK ? r.err : "batch engine: the round ended without the request's completion word");
+            return rc;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+}
+
 // pmv_find_essential_mat's contract through the five-point combiner. The caller waits for whichever comes first: the completion word that
 // its own workgroup stores last into the seq's pinned result block, or the combiner's done flag after the round's stream sync (the only
 // one a failed launch gives). After the word the workgroup touches nothing of the seq's blocks any more, so the seq's next call may use them
@@ -1160,19 +1200,26 @@ int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double*
     r.done.store(0, std::memory_order_relaxed);
     r.inflight.store(1, std::memory_order_release);
     enqueue(E->queue[R_FP], &r);
-    volatile unsigned* word = essential_done_word(r.b, r.in_bytes);
-    const unsigned want = r.P.done_seq;
-    for (;;) {
-        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) break;
-        if (r.done.load(std::memory_order_acquire)) {   // the round is over
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) break;
-            const int rc = r.rc != PMV_OK ? r.rc : PMV_ERR_HIP;
-            set_err(ctx, "%s", r.rc != PMV_OK ? r.err : "batch engine: the round ended without the request's completion word");
-            return rc;
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
+    if (const int rc = wait_whole(ctx, r, essential_done_word(r.b, r.in_bytes), r.P.done_seq)) return rc;
     essential_finish(r.b, n, r.in_bytes, E9, mask, out_found, out_samples_drawn);
+    return PMV_OK;
+}
+
+// pmv_find_fundamental_mat's contract through the five-point combiner, in engine_essential's form: the request is one workgroup of the round's
+// k_fundamental_ransac launch and its caller returns with its own completion word.
+int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
+                       int* out_found, int* out_samples_drawn) {
+    pmv_ctx* ctx = E->ctx;
+    if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
+    FundReq& r = E->fund[(size_t)seq];
+    futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
+    r.kind = 15; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
+    if (const int rc = fundamental_prepare(ctx, r.b, p1_xy, p2_xy, n, threshold, confidence, &r.P, &r.in_bytes)) return rc;
+    r.done.store(0, std::memory_order_relaxed);
+    r.inflight.store(1, std::memory_order_release);
+    enqueue(E->queue[R_FP], &r);
+    if (const int rc = wait_whole(ctx, r, essential_done_word(r.b, r.in_bytes), r.P.done_seq)) return rc;
+    fundamental_finish(r.b, n, r.in_bytes, F9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 

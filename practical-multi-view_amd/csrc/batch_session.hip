@@ -605,6 +605,15 @@ int pmv_batch_find_essential_mat(pmv_ctx* ctx, int seq, const double* p1_xy, con
     return engine_essential(S->eng, seq, p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn);
 }
 
+// rejectWithF of a seq's KLT loop: findFundamentalMat as one workgroup of the round's k_fundamental_ransac launch (engine_fundamental)
+int pmv_batch_find_fundamental_mat(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9,
+                                   uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    SESSION("pmv_batch_find_fundamental_mat");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_find_fundamental_mat", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_fundamental(S->eng, seq, p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn);
+}
+
 int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
                            uint8_t* mask, double* tri4n, int* out_good) {
     SESSION("pmv_batch_recover_pose");

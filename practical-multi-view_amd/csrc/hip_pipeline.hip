@@ -580,6 +580,11 @@ int pmv_debug_batch_launches(pmv_ctx* ctx, long long* out4) {
     for (int i = 0; i < 4; i++) out4[i] = ctx->batch_launches[i].load();
     return PMV_OK;
 }
+int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3) {
+    if (!ctx || !out3) return PMV_ERR_INVALID;
+    for (int i = 0; i < 3; i++) out3[i] = ctx->whole_rounds[i].load();
+    return PMV_OK;
+}
 int pmv_batch_ingest_stats(pmv_ctx* ctx, double* out) {
     if (!out) return pmv::BATCH_INGEST_STATS;
     if (!ctx) return PMV_ERR_INVALID;

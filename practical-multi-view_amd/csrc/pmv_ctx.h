@@ -50,6 +50,9 @@ struct pmv_ctx {
     // launches of the batched legs since the context was created: k_lk_batch, k_knn_round (combiners), k_pad_level0[_bgr], k_pyrdown (feeder of
     // pmv_pipeline_run_batch[_streamed]) - pmv_debug_batch_launches; the profiler's per-class event pools are not made for two LK lanes
     std::atomic<long long> batch_launches[4];
+    // rounds of whole-RANSAC requests the five-point combiner has served since the context was created (pmv_debug_whole_rounds):
+    // k_fundamental_ransac launches, k_essential_ransac launches, rounds that made both
+    std::atomic<long long> whole_rounds[3];
     // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames, or a third as many BGR ones (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;

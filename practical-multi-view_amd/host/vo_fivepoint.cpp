@@ -330,21 +330,22 @@ void five_point_sample_stream(int n, int count, int* out5) {
     for (int k = 0; k < count; k++) draw_subset(rng, n, 5, out5 + 5 * k);
 }
 int five_point_update_num_iters(double p, double ep, int model_points, int max_iters) { return ransac_update_num_iters(p, ep, model_points, max_iters); }
-// ransac_update_num_iters(p, (n - g) / n, 5, maxIters) split for a caller without this libm (the device loop of pmv_find_essential_mat): the
-// two logarithms per inlier count g = 0..n here, the final expression `denom >= 0 || -num >= maxIters * (-denom) ? maxIters :
-// lrint(num / denom)` there. Where the function returns 0 before its logarithms (denom < DBL_MIN) the entry is -infinity, for which the
-// final expression gives 0 as well: -num >= maxIters * inf is false (also for maxIters = 0: NaN), and num / -inf rounds to 0.
-void five_point_iters_table(int n, double p, double* out_denoms, double* out_num) {
-    const int modelPoints = 5;
+// ransac_update_num_iters(p, (n - g) / n, model_points, maxIters) split for a caller without this libm (the device loops of
+// pmv_find_essential_mat, 5 model points, and pmv_find_fundamental_mat, 7): the two logarithms per inlier count g = 0..n here, the final
+// expression `denom >= 0 || -num >= maxIters * (-denom) ? maxIters : lrint(num / denom)` there. Where the function returns 0 before its
+// logarithms (denom < DBL_MIN) the entry is -infinity, for which the final expression gives 0 as well: -num >= maxIters * inf is false
+// (also for maxIters = 0: NaN), and num / -inf rounds to 0.
+void ransac_iters_table(int n, double p, int model_points, double* out_denoms, double* out_num) {
     p = std::max(p, 0.); p = std::min(p, 1.);
     *out_num = std::log(std::max(1. - p, DBL_MIN));
     for (int g = 0; g <= n; g++) {
         double ep = n > 0 ? (double)(n - g) / n : 0.;
         ep = std::max(ep, 0.); ep = std::min(ep, 1.);
-        const double denom = 1. - std::pow(1. - ep, modelPoints);
+        const double denom = 1. - std::pow(1. - ep, model_points);
         out_denoms[g] = denom < DBL_MIN ? -HUGE_VAL : std::log(denom);
     }
 }
+void five_point_iters_table(int n, double p, double* out_denoms, double* out_num) { ransac_iters_table(n, p, 5, out_denoms, out_num); }
 
 // Helper threads for the five-point RANSAC: the hypotheses of a batch are independent, so they are evaluated side by side and
 // the sequential bookkeeping (best-so-far, adaptive iteration count) is replayed in sample order afterwards — the outcome is

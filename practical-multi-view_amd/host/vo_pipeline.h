@@ -275,6 +275,8 @@ int five_point_update_num_iters(double p, double ep, int model_points, int max_i
 // its two logarithms for n correspondences: out_num = log(1 - p), out_denoms[g] (g = 0..n inliers) = log(1 - (1 - (n - g) / n)^5), -infinity
 // where the function returns 0 early; the final expression over them is five_point_update_num_iters(p, (n - g) / n, 5, max_iters) exactly
 void five_point_iters_table(int n, double p, double* out_denoms, double* out_num);
+// the same table for any model size: out_denoms[g] = log(1 - (1 - (n - g) / n)^model_points) (five_point_iters_table is model_points = 5)
+void ransac_iters_table(int n, double p, int model_points, double* out_denoms, double* out_num);
 // cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold, mask) on pixel coordinates; samples_drawn counts RANSAC
 // iterations; pool/pool_width: helper threads (results do not depend on them)
 bool find_essential_mat(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E,
