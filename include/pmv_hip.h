@@ -410,7 +410,8 @@ int pmv_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int m
  * repeat-the-last-pick and default-(0,0) quirks) are compared through compareFeatures' pixel window (:103-122) and the best fit is
  * chosen by the sequential `_err < err || err == 0` rule. out_best: n indices into the candidates (-1 = the default Feature at
  * (0,0)); out_err: n floats. Thresholding, displacement statistics and the maps stay in the caller's adapter (:32-60).
- * The reference's constants: n_neighbours 7, window 15. */
+ * The reference's constants: n_neighbours 7, window 15. Source and candidate coordinates may lie outside the frame: a pixel is read
+ * only where both ends of a pair are inside both images (the reference skips the others, :109-112), so such a call is defined. */
 int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
                   int* out_best, float* out_err);
 /* Pyramidal LK from frame slot `prev_slot` to `next_slot`. prev_xy: n*2 floats. out_xy n*2 floats,

@@ -71,6 +71,28 @@ def test_knn_matches_twin_written_from_the_reference(orc, seed, m):
     assert np.array_equal(got_err, want_err)
 
 
+@pytest.mark.parametrize("window", [1, 2, 3, 16, 63])
+@pytest.mark.parametrize("n", [1, 2, 8])
+def test_knn_matches_twin_off_the_reference_constants(orc, n, window):
+    """neighbour counts and windows other than 7 and 15 (even windows: win = ceil(window / 2); 63: a 65x65 window larger than the image is
+    high), on a candidate list that is NOT unique: one duplicated row, one row at a source's own coordinates, sources in two corners"""
+    import alt_common as ac
+    w, h = 64, 48
+    a, b = ac.noise(w, h), ac.shifted(w, h)
+    src_xy, cmp_xy = ac.points(21, w, h, 12), ac.points(22, w, h, 40).copy()
+    src_xy = src_xy.copy()
+    src_xy[0] = (0, 0); src_xy[1] = (w - 1, h - 1)
+    cmp_xy[17] = cmp_xy[3]                                              # a duplicate: `ff != fff` compares coordinates
+    cmp_xy[5] = src_xy[4]                                               # skipped for that source (f != ff)
+    got_best, got_err = orc.knn_match(a, b, src_xy, cmp_xy, neighbours=n, window=window)
+    want_best, want_err = knn_twin(a, b, src_xy, cmp_xy, n, window)
+    for i, (g, wb) in enumerate(zip(got_best, want_best)):
+        gxy = (0, 0) if g < 0 else tuple(int(v) for v in cmp_xy[g])
+        assert gxy == wb, f"feature {i}: best fit {gxy} vs {wb}"
+    assert np.array_equal(got_err, want_err)
+    assert (got_best >= 0).all() and (got_err > 0).any()
+
+
 def test_knn_window_error_float_semantics(orc):
     """the accumulator is a float fed through double additions: sums above 2^24 round per term, in x-outer / y-inner order"""
     import ctypes as C
@@ -144,6 +166,37 @@ def test_fast_matches_the_definition(orc, seed, shape, t):
     b = orc.fast9_cell(crop, (0, 0, cell[2], cell[3]), 1000, threshold=t)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     assert len(orc.fast9_cell(img, cell, 0, threshold=t)[0]) == 0
+
+
+@pytest.mark.parametrize("t", [0, 254])
+def test_fast_matches_the_definition_on_a_binary_image(orc, t):
+    """0 or 255 per pixel: every difference on the circle is 0 or +-255, so every corner passes at any threshold below 255 and scores 254;
+    the strict `>` of the non-max rule then removes corners that touch another one"""
+    import alt_common as ac
+    img = ac.binary(35, 33)
+    cell = (0, 0, 35, 33)
+    for nonmax in (True, False):
+        want = fast_definition(img, t, nonmax)
+        xy, rs = orc.fast9_cell(img, cell, 100000, threshold=t, nonmax=nonmax)
+        assert [(int(x), int(y), float(r)) for (x, y), r in zip(xy, rs)] == want
+        assert len(want) > 0 and (not nonmax or {r for _, _, r in want} == {254.0})
+    full, kept = len(fast_definition(img, t, False)), len(fast_definition(img, t, True))
+    assert kept < full, "no two corners touch: the tie rule of the non-max step is not exercised"
+
+
+def test_fast_threshold_255_and_the_clamp(orc):
+    """no difference of two bytes exceeds 255: nothing at t = 255; cv::FAST clamps the threshold to 0..255"""
+    import alt_common as ac
+    for img in (ac.noise(52, 40), ac.binary(35, 33)):
+        h, w = img.shape
+        cell = (0, 0, w, h)
+        for nonmax in (True, False):
+            assert fast_definition(img, 255, nonmax) == []
+            assert len(orc.fast9_cell(img, cell, 100000, threshold=255, nonmax=nonmax)[0]) == 0
+            for t, same in ((300, 255), (-5, 0)):
+                a, b = orc.fast9_cell(img, cell, 100000, threshold=t, nonmax=nonmax), orc.fast9_cell(img, cell, 100000, threshold=same, nonmax=nonmax)
+                assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+            assert len(orc.fast9_cell(img, cell, 100000, threshold=-5, nonmax=nonmax)[0]) > 0
 
 
 def test_cpu_pipeline_with_fast_and_knn_plugins(pmv):

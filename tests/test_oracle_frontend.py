@@ -225,6 +225,31 @@ def test_shitomasi_matches_in_repo_arithmetic(orc, seed):
     assert (np.diff(sc) <= 0).all()
 
 
+@pytest.mark.parametrize("cell", [(5, 3, 35, 34), (9, 11, 3, 3), (0, 0, 110, 80)])
+def test_shitomasi_cell_shapes_and_qualities(orc, cell):
+    """a cell that leaves three columns and two rows beyond a 32x32 tile, the smallest cell, the whole image; qualities 0.05, 0.0 (every positive
+    response) and 1.0 (nothing: the threshold is the maximum and the comparison is strict). Response map against the numpy twin; lists and
+    scores: threshold, descending score, ties in raster order, at most `max`, restated here on the response map."""
+    img = np.random.default_rng(3).integers(0, 256, (80, 110), dtype=np.uint8)
+    x0, y0, cw, ch = cell
+    ref = np_shitomasi(img[y0:y0 + ch, x0:x0 + cw])
+    for quality in (0.4, 0.05, 0.0, 1.0):
+        for mx in (1, 25, 4096):
+            xy, sc, R = orc.shitomasi_cell(img, cell, mx, quality=quality, want_resp=True)
+            assert np.array_equal(np.isnan(R), np.isnan(ref))
+            np.testing.assert_allclose(np.nan_to_num(R), np.nan_to_num(ref), rtol=1e-13, atol=1e-12)
+            thr = np.nanmax(R) * quality
+            cand = sorted((-R[y, x], y * cw + x) for y in range(ch) for x in range(cw) if R[y, x] > thr)
+            want = np.array([[i % cw, i // cw] for _, i in cand[:mx]], np.int32).reshape(-1, 2)
+            assert np.array_equal(xy, want), (quality, mx)
+            assert np.array_equal(sc, np.array([-v for v, _ in cand[:mx]]))
+        if quality == 1.0:
+            assert len(xy) == 0
+        elif quality == 0.0:
+            assert len(xy) == min(4096, int((np.nan_to_num(R) > 0).sum()))
+            assert len(xy) > 0 or cw == 3   # (3x3: one gradient sample, a rank-1 structure tensor, smaller eigenvalue 0 everywhere)
+
+
 def test_shitomasi_signed_char_quirk_q1(orc):
     """KA4: the same edge gives a different response once pixel values cross 127 (they wrap negative)."""
     lo = np.zeros((40, 40), np.uint8); lo[20:, 20:] = 100     # 0 -> 100: gradient +50
