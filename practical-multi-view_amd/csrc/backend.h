@@ -5,12 +5,12 @@
 #include <stddef.h>
 #include "../../include/pmv_hip.h"
 #include "pmv_mem.h"
+#include "backend_layout.h"   // MAX_HYP, FP_MAX_HYP, PNP_HDR, ESS_HDR, the result-block headers and every staging block's layout
 
 namespace pmv {
 
 // Device / pinned buffers of ONE back-end problem slot (PnP, BA, two-view DLT workspaces and the single-copy staging blocks). The
 // context owns one (the plain C-ABI calls); the batch engine owns one per concurrent sequence.
-constexpr int MAX_HYP = 1024;
 
 struct BackendBuffers {   // every buffer: one row of backend_alloc's table; freed with the set (backend_free)
     unsigned done_seq = 0;   // sequence number of the last call that signals its completion through the result block
@@ -24,24 +24,21 @@ struct BackendBuffers {   // every buffer: one row of backend_alloc's table; fre
     Buf<void> d_bastate;
     Buf<double> d_bapart;
     Buf<char> d_tri_in, d_tri_out;
-    Buf<char> d_fp_work;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in)
-    Buf<char> d_ess_in;    // whole findEssentialMat RANSAC: [EssentialProblem 64 B | q1 2n | q2 2n | iteration table n + 2 doubles]
-    Buf<char> d_fund_in;   // whole findFundamentalMat RANSAC: [FundamentalProblem 64 B | p1 2n floats | p2 2n floats | iteration table n + 2 doubles];
-                           // sized by max_tracks, made by the set's first such call (fundamental_prepare)
+    Buf<char> d_fp_work;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in: fivepoint_layout)
+    Buf<char> d_ess_in;    // whole findEssentialMat RANSAC: the in-block of essential_layout
+    Buf<char> d_fund_in;   // whole findFundamentalMat RANSAC: the in-block of fundamental_layout; made by the set's first such call (fundamental_prepare)
     // single-copy transfers: one mapped pinned staging block (result blocks are written straight into it through .dm()) and one device
     // block per direction
     Buf<char> h_stage;
-    Buf<char> d_ba_io;     // [summary 8 | cams | pts | obs | K | cam_idx | pt_idx | pobs_start | pobs_list | cobs_start | cobs_list]
-    Buf<char> d_pnp_in;    // [K 10 doubles | obj | img | samples]
-    Buf<char> d_pnp_out;   // [rt 6 doubles | info 4 ints | inliers]
+    Buf<char> d_ba_io;     // ba_io_layout
+    Buf<char> d_pnp_in;    // the in-block of pnp_layout
+    Buf<char> d_pnp_out;   // [PnPResultHdr | inliers]
     // PnP
     Buf<float> d_obj, d_img;
     Buf<int> d_samples, d_counts, d_inliers, d_info;
     Buf<double> d_models, d_rt, d_Kp;
     Buf<uint8_t> d_masks;
 };
-
-constexpr size_t PNP_HDR = 384;   // bytes: K (10 doubles) + 33 powers of ten + padding
 
 struct BAArgs {
     // problem (device)
@@ -55,8 +52,8 @@ struct BAArgs {
     double *x, *cand, *scale, *diag, *D2, *step, *res, *J, *Einv, *gp, *Yd, *Wd, *S, *rhs, *Gpart, *summary;
     int ldw, krows, tiles_r, tiles_c, kslices, kper, gp_rows;
     unsigned long long* stamps;   // optional (diagnostic): 32 accumulated shader-clock phase timers
-    double* out;                  // optional: host-mapped result block [summary 8 | cams 6*nc | pts 3*np] (multi-kernel LM)
-    unsigned done_seq;            // != 0 (with `out`): the finish kernel stores it last into the low word of summary slot 7 (the host spins on it)
+    double* out;                  // optional: host-mapped result block [summary BA_SUM_SLOTS | cams 6*nc | pts 3*np] (multi-kernel LM)
+    unsigned done_seq;            // != 0 (with `out`): the finish kernel stores it last into the low word of summary slot BA_SUM_DONE (the host spins on it)
 };
 
 hipError_t launch_ba_residuals(hipStream_t s, const double* cams, const double* pts, const double* obs, const int* cam_idx,
@@ -67,7 +64,7 @@ constexpr int BA_MAX_ITERATIONS = 512;   // per-iteration flags of the multi-ker
 hipError_t launch_ba_multi(hipStream_t s, const BAArgs& A, void* d_state, double* d_part);
 hipError_t launch_pnp(hipStream_t s, const float* d_obj, const float* d_img, int m, const double* d_K, const int* d_samples,
                       int n_hyp, float thr, double confidence, double* d_models, uint8_t* d_masks, int* d_counts,
-                      double* d_rt_out, int* d_inliers, int* d_info, char* host_out /* mapped pinned [rt 48 B | info 16 B | inliers] */,
+                      double* d_rt_out, int* d_inliers, int* d_info, char* host_out /* mapped pinned [PnPResultHdr | inliers] */,
                       unsigned long long* d_stamps /* diagnostic, may be null */, unsigned done_seq = 0 /* see pnp_select_refit_body */);
 
 // one problem of a batched multi-kernel LM launch chain: the arguments launch_ba_multi derives for a single solve, kept in device memory
@@ -98,17 +95,15 @@ struct FivePointProblem {
     double* models_h; int* n_models_h; int* counts_h;         // mapped pinned results: models, model counts, n_hyp x 10 inlier counts
     int n, n_hyp; float thr;
 };
-constexpr int FP_MAX_HYP = 64;   // hypotheses per round
 hipError_t launch_fivepoint_batch(hipStream_t s, const FivePointProblem* d_probs, int n_probs, int max_hyp);
 // one whole cv::findEssentialMat RANSAC (k_essential_ransac, backend_fivepoint.hip): one workgroup runs the adaptive loop of one request
 struct EssentialProblem {
     const double* q1; const double* q2;   // device: n normalised points (x, y) each
     const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^5), -inf where RANSACUpdateNumIters returns 0]
-    char* out;                            // mapped pinned result block: [E 9 doubles | at byte 80: found, samples drawn, best count, done_seq | at byte 128: mask n bytes]
+    char* out;                            // mapped pinned result block: [WholeResultHdr (E, found, samples drawn, best count, done_seq) | mask n bytes]
     int n, max_iters; float thr;
-    unsigned done_seq;                    // != 0; the kernel's last store, into the fourth word at byte 80 (the caller waits for it)
+    unsigned done_seq;                    // != 0; the kernel's last store, into WholeResultHdr::done (the caller waits for it)
 };
-constexpr size_t ESS_HDR = 64, ESS_OUT_HDR = 128;   // bytes: the record in front of a request's input block / the result block in front of the mask
 static_assert(sizeof(EssentialProblem) <= ESS_HDR, "the record is the header of the input block");
 constexpr int ESS_MAX_WAVES = 16;   // hypotheses per in-kernel round at most (wavefronts of the workgroup)
 constexpr int ESS_DEFAULT_WAVES = 8;   // R of DESIGN.md §4: 8 x 6.2 KB = 49 KB of LDS, three workgroups per CU
@@ -143,41 +138,41 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out);
 void backend_free(BackendBuffers* b);
 int pnp_check(pmv_ctx* ctx, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,
               double confidence, int* out_inliers, int* out_n_inliers);
-void pnp_prepare(BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, int iterations, float reproj_err,
-                 double confidence, PnPProblem* P, size_t* in_bytes);
+// Every *_prepare carves b's blocks by the call's layout (backend_layout.h), refuses with PMV_ERR_CAPACITY what does not fit them and hands
+// the layout back; the stage-in copy, the completion word and *_finish use that same value.
+int pnp_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, int iterations, float reproj_err,
+                double confidence, PnPProblem* P, PnPLayout* L);
 void pnp_finish(pmv_ctx* ctx, BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec,
-                int iterations, float reproj_err, double confidence, size_t in_bytes, int* out_inliers, int* out_n_inliers);
+                int iterations, float reproj_err, double confidence, const PnPLayout& L, int* out_inliers, int* out_n_inliers);
 int ba_check(pmv_ctx* ctx, const double* cams, int nc, const double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx,
              int n_obs, const double* K, double huber_delta, int max_iterations);
 int ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc, const double* pts, int np, const double* obs_xy, const int* cam_idx,
-               const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, bool multi, BAArgs* A, size_t* io_bytes);
+               const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, bool multi, BAArgs* A, BaIoLayout* L);
 void ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx,
-               const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, pmv_ba_summary* summary);
+               const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, const BaIoLayout& L, pmv_ba_summary* summary);
 // five-point round: samples (5 n_hyp ints) of n normalised correspondences; thr = squared Sampson threshold as float
 int fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
-                      FivePointProblem* P, size_t* in_bytes);
-void fivepoint_finish(BackendBuffers* b, int n_hyp, size_t in_bytes, double* models, int* n_models, int* counts);
+                      FivePointProblem* P, FivePointLayout* L);
+void fivepoint_finish(BackendBuffers* b, int n_hyp, const FivePointLayout& L, double* models, int* n_models, int* counts);
 // whole findEssentialMat: argument rules of pmv_find_essential_mat (outputs untouched on error); prepare normalises the points into b's pinned
 // block behind the problem record, builds the iteration table with the host's libm and clears the completion word; finish reads the result block
 int essential_check(pmv_ctx* ctx, const char* who, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
                     double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
-void essential_prepare(BackendBuffers* b, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
-                       EssentialProblem* P, size_t* in_bytes);
-volatile unsigned* essential_done_word(BackendBuffers* b, size_t in_bytes);
-void essential_finish(BackendBuffers* b, int n, size_t in_bytes, double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+int essential_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
+                      EssentialProblem* P, WholeLayout* L);
+volatile unsigned* whole_done_word(BackendBuffers* b, const WholeLayout& L);   // of either whole-RANSAC call: the result blocks share their header
+void whole_finish(BackendBuffers* b, int n, const WholeLayout& L, double* M9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 // whole findFundamentalMat: argument rules of pmv_find_fundamental_mat (outputs untouched on error); prepare makes b's d_fund_in on first use,
-// copies the points into b's pinned block behind the problem record, builds the iteration table with the host's libm and clears the completion
-// word (essential_done_word serves both calls: the result blocks share their layout); finish reads the result block
+// copies the points into b's pinned block behind the problem record, builds the iteration table with the host's libm and clears the completion word
 int fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9,
                       uint8_t* mask, int* out_found, int* out_samples_drawn);
 int fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence,
-                        FundamentalProblem* P, size_t* in_bytes);
-void fundamental_finish(BackendBuffers* b, int n, size_t in_bytes, double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+                        FundamentalProblem* P, WholeLayout* L);
 // cv::recoverPose around a DLT launch: `dlt` is pmv_triangulate_candidates' contract on the caller's workspace set; PMV_OK or its error
 int recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
                        double* t3, uint8_t* mask, double* tri4n, int* out_good);
-void dlt_prepare(BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
-                 size_t* in_bytes);
+int dlt_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
+                DltLayout* L);
 void dlt_finish(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
-                size_t in_bytes, double* out_Q, uint8_t* out_mask, int* out_good);
+                const DltLayout& L, double* out_Q, uint8_t* out_mask, int* out_good);
 }  // namespace pmv

@@ -1,6 +1,7 @@
 // C-ABI entry points of the back-end stream: pmv_pnp_ransac, pmv_ba_residuals, pmv_ba_solve (include/pmv_hip.h).
 #include "pmv_ctx.h"
 #include "backend.h"
+#include "pmv_wait.h"
 #include "vo_pipeline.h"
 #include <cmath>
 #include <cstring>
@@ -16,7 +17,13 @@ namespace pmv {
 __global__ __launch_bounds__(256) void k_stage_block(const uint4* __restrict__ src, uint4* __restrict__ dst, unsigned n16) { BACKEND_PRIO();
     for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
 }
-
+hipError_t stage_block(hipStream_t s, const void* mapped_src, void* dst, size_t bytes, unsigned max_blocks) {
+    const unsigned n16 = (unsigned)((bytes + 15) >> 4);
+    hipLaunchKernelGGL(k_stage_block, dim3(std::min(max_blocks, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)mapped_src, (uint4*)dst, n16);
+    return hipGetLastError();
+}
+// PMV_BA_STAGE=dma: PnP and BA stage their input block with hipMemcpyAsync instead (read once per process)
+static bool stage_by_kernel() { static const bool on = !(getenv("PMV_BA_STAGE") && !strcmp(getenv("PMV_BA_STAGE"), "dma")); return on; }
 
 static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
@@ -29,15 +36,7 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
     b->ydwd_elems = krows * ldw;
     b->gpart_elems = (size_t)8 * ldw * ldw;   // up to 8 K-slices of an (ldw x ldw) tile grid
     const size_t mt = (size_t)c->max_tracks;
-    const size_t ba_io_bytes = (8 + nc * 6 + np * 3 + no * 2 + 10) * 8 + (no * 8 + np + nc + 8) * 4 + 128;
-    const size_t pnp_in_bytes = PNP_HDR + mt * 20 + (size_t)MAX_HYP * 20 + 64, pnp_out_bytes = 48 + 16 + mt * 4 + 64;
-    const size_t tri_in_bytes = 48 * 8 + mt * 32 + mt + 64, tri_out_bytes = mt * 16 * 8 + mt * 4 + 64;
-    const size_t ess_in_bytes = ESS_HDR + (5 * mt + 2) * 8 + 64;
-    // the staging block holds the largest in + out pair of any call
-    const size_t h_stage_bytes = std::max<size_t>({no * 18 * 8 + no * 2 * 8, n * 8 + no * 32 + (np + nc + 2) * 4, mt * 32 + MAX_HYP * 20 + 4096,
-                                                   ba_io_bytes, pnp_in_bytes + pnp_out_bytes, tri_in_bytes + tri_out_bytes,
-                                                   tri_in_bytes + (size_t)FP_MAX_HYP * (90 * 8 + 44) + 256,   // five-point round in + out
-                                                   ess_in_bytes + ESS_OUT_HDR + mt + 64});                    // whole findEssentialMat in + out
+    const BackendCaps caps = backend_caps(c->max_tracks, c->max_ba_cams, c->max_ba_points, c->max_ba_obs);   // the staging blocks: the layouts at capacity
     // THE list of a workspace set's buffers
     const MemRow rows[] = {
         {&b->d_cams, nc * 6 * 8, MEM_DEVICE}, {&b->d_pts, np * 3 * 8, MEM_DEVICE}, {&b->d_obs, no * 2 * 8, MEM_DEVICE}, {&b->d_K, 9 * 8, MEM_DEVICE},
@@ -61,12 +60,12 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
         {&b->d_inliers, mt * 4, MEM_DEVICE}, {&b->d_info, 16, MEM_DEVICE},
         {&b->d_models, MAX_HYP * 6 * 8, MEM_DEVICE}, {&b->d_rt, 6 * 8, MEM_DEVICE}, {&b->d_Kp, 9 * 8, MEM_DEVICE},
         {&b->d_masks, (size_t)MAX_HYP * mt, MEM_DEVICE},
-        {&b->d_ba_io, ba_io_bytes, MEM_DEVICE},
-        {&b->d_pnp_in, pnp_in_bytes, MEM_DEVICE}, {&b->d_pnp_out, pnp_out_bytes, MEM_DEVICE},
-        {&b->d_tri_in, tri_in_bytes, MEM_DEVICE}, {&b->d_tri_out, tri_out_bytes, MEM_DEVICE},
+        {&b->d_ba_io, caps.ba_io, MEM_DEVICE},
+        {&b->d_pnp_in, caps.pnp_in, MEM_DEVICE}, {&b->d_pnp_out, caps.pnp_out, MEM_DEVICE},
+        {&b->d_tri_in, caps.tri_in, MEM_DEVICE}, {&b->d_tri_out, caps.tri_out, MEM_DEVICE},
         {&b->d_fp_work, (size_t)FP_MAX_HYP * (90 * 8 + 4) + 64, MEM_DEVICE},
-        {&b->d_ess_in, ess_in_bytes, MEM_DEVICE},
-        {&b->h_stage, h_stage_bytes, MEM_MAPPED},
+        {&b->d_ess_in, caps.ess_in, MEM_DEVICE},
+        {&b->h_stage, caps.h_stage, MEM_MAPPED},
     };
     hipError_t e = mem_alloc_table(rows, sizeof(rows) / sizeof(rows[0]));
     if (e == hipSuccess) e = hipMemset(b->d_stamps, 0, 32 * 8);
@@ -97,10 +96,6 @@ using namespace pmv;
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
-extern "C" {
-
-}  // extern "C"
-
 // ---- PnP: prepare (host slab + device problem record) / finish (results out of the pinned block), shared by the single call
 // and by the batch engine (several sequences' calls in one launch) ------------------------------------------------------------
 int pmv::pnp_check(pmv_ctx* ctx, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec, int iterations,
@@ -115,20 +110,20 @@ int pmv::pnp_check(pmv_ctx* ctx, const float* obj_xyz, const float* img_xy, int 
     REQ(confidence > 0 && confidence < 1, PMV_ERR_INVALID, "pmv_pnp_ransac: confidence must be in (0,1)");
     return PMV_OK;
 }
-// packs [K 10 doubles, 10^k for k = -16..16 (CvLevMarq's lambda) | obj 3m floats | img 2m floats | samples 5*iterations ints] into b's
-// pinned block and describes the problem with b's device buffers; *in_bytes = bytes to copy h_stage -> d_pnp_in
-void pmv::pnp_prepare(BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, int iterations, float reproj_err,
-                      double confidence, PnPProblem* P, size_t* in_bytes_out) {
+// packs pnp_layout's in-block [K 10 doubles, 10^k for k = -16..16 (CvLevMarq's lambda) | obj 3m floats | img 2m floats | samples 5*iterations
+// ints] into b's pinned block and describes the problem with b's device buffers; L->in_bytes = bytes to copy h_stage -> d_pnp_in
+int pmv::pnp_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, int iterations, float reproj_err,
+                     double confidence, PnPProblem* P, PnPLayout* Lout) {
+    const PnPLayout L = pnp_layout((size_t)m, (size_t)iterations);
+    REQ(L.total <= b->h_stage.cap && L.in_bytes <= b->d_pnp_in.cap && L.total - L.out <= b->d_pnp_out.cap, PMV_ERR_CAPACITY,
+        "pmv_pnp_ransac: m=%d with %d iterations does not fit the staging blocks", m, iterations);
     char* hs = (char*)b->h_stage;
-    double* h_K = (double*)hs;
-    float* h_obj = (float*)(hs + PNP_HDR);
-    float* h_img = h_obj + (size_t)3 * m;
-    int* h_samples = (int*)(h_img + (size_t)2 * m);
-    const size_t in_bytes = PNP_HDR + (size_t)m * 20 + (size_t)iterations * 20;
+    double* h_K = (double*)(hs + L.K);
+    int* h_samples = (int*)(hs + L.samples);
     memcpy(h_K, K, 72);
     for (int k = -16; k <= 16; k++) h_K[10 + 16 + k] = std::exp(k * std::log(10.));   // as CvLevMarq::step evaluates it (host libm)
-    memcpy(h_obj, obj_xyz, (size_t)m * 12);
-    memcpy(h_img, img_xy, (size_t)m * 8);
+    memcpy(hs + L.obj, obj_xyz, (size_t)m * 12);
+    memcpy(hs + L.img, img_xy, (size_t)m * 8);
     CvRNG rng((uint64_t)-1);
     for (int it = 0; it < iterations; it++) {
         int* idx = h_samples + it * 5;
@@ -143,28 +138,27 @@ void pmv::pnp_prepare(BackendBuffers* b, const float* obj_xyz, const float* img_
             i++;
         }
     }
-    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    P->K = (const double*)b->d_pnp_in;
-    P->obj = (const float*)(b->d_pnp_in + PNP_HDR);
-    P->img = P->obj + (size_t)3 * m;
-    P->samples = (const int*)(P->img + (size_t)2 * m);
+    P->K = (const double*)(b->d_pnp_in + L.K);
+    P->obj = (const float*)(b->d_pnp_in + L.obj);
+    P->img = (const float*)(b->d_pnp_in + L.img);
+    P->samples = (const int*)(b->d_pnp_in + L.samples);
     P->models = b->d_models; P->masks = b->d_masks; P->counts = b->d_counts;
     P->rt_out = (double*)b->d_pnp_out;
-    P->info = (int*)(b->d_pnp_out + 48);
-    P->inliers = (int*)(b->d_pnp_out + 64);
-    P->host_out = b->h_stage.dm() + (ho - hs);   // the refit kernel writes [rt 48 B | info 16 B | inliers] straight into the pinned block
+    P->info = (int*)(b->d_pnp_out + PNP_OUT_INFO);
+    P->inliers = (int*)(b->d_pnp_out + PNP_OUT_INLIERS);
+    P->host_out = b->h_stage.dm() + L.out;   // the refit kernel writes [PnPResultHdr | inliers] straight into the pinned block
     P->m = m; P->n_hyp = iterations;
     P->thr = (float)((double)reproj_err * (double)reproj_err);
     P->confidence = confidence;
-    *in_bytes_out = in_bytes;
+    *Lout = L;
+    return PMV_OK;
 }
 void pmv::pnp_finish(pmv_ctx* ctx, BackendBuffers* b, const float* obj_xyz, const float* img_xy, int m, const double* K, double* rvec, double* tvec,
-                     int iterations, float reproj_err, double confidence, size_t in_bytes, int* out_inliers, int* out_n_inliers) {
-    const char* ho = (const char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63);
-    const double* h_rt = (const double*)ho;
-    const int* h_info = (const int*)(ho + 48);
-    const int* h_inl = (const int*)(ho + 64);
-    const int n = h_info[0];
+                     int iterations, float reproj_err, double confidence, const PnPLayout& L, int* out_inliers, int* out_n_inliers) {
+    const PnPResultHdr* R = (const PnPResultHdr*)((const char*)b->h_stage + L.out);
+    const double* h_rt = R->rt;
+    const int* h_inl = (const int*)((const char*)b->h_stage + L.inliers);
+    const int n = R->info[0];
     if (ctx->log.on) {   // [kind 0, m, iterations, n_inliers | obj 3m f32 | img 2m f32 | K 9, rvec_in 3, tvec_in 3, reproj_err, confidence f64 | rvec_out 3, tvec_out 3 f64 | inliers]
         std::lock_guard<std::mutex> lk(ctx->log.mu);
         ctx->log.blobs.emplace_back();
@@ -178,6 +172,13 @@ void pmv::pnp_finish(pmv_ctx* ctx, BackendBuffers* b, const float* obj_xyz, cons
     for (int i = 0; i < 3; i++) { rvec[i] = h_rt[i]; tvec[i] = h_rt[3 + i]; }
     *out_n_inliers = n;
     if (n > 0) memcpy(out_inliers, h_inl, (size_t)n * 4);
+}
+
+// Waits for a kernel's last store, the call's sequence number in its result block (spin_for_word), or, with by_word false, for the stream
+static int wait_done_word(pmv_ctx* ctx, hipStream_t s, volatile unsigned* done_word, unsigned done_seq, bool by_word) {
+    if (by_word) CKC(spin_for_word(s, done_word, done_seq));
+    else CKC(hipStreamSynchronize(s));
+    return PMV_OK;
 }
 
 extern "C" {
@@ -200,34 +201,20 @@ int pmv_pnp_ransac(pmv_ctx* ctx, const float* obj_xyz, const float* img_xy, int 
     BackendBuffers* b = ctx->be;
     hipStream_t s = ctx->s_back;
     PnPProblem P;
-    size_t in_bytes = 0;
-    pnp_prepare(b, obj_xyz, img_xy, m, K, iterations, reproj_err, confidence, &P, &in_bytes);
-    static const bool stage_by_kernel = !(getenv("PMV_BA_STAGE") && !strcmp(getenv("PMV_BA_STAGE"), "dma"));
-    if (stage_by_kernel) {
-        const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
-        hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_pnp_in, n16);
-        CKC(hipGetLastError());
-    } else CKC(hipMemcpyAsync(b->d_pnp_in, b->h_stage, in_bytes, hipMemcpyHostToDevice, s));
-    // the refit kernel writes [rt | info | inliers] straight into the pinned block and, last, this call's sequence number into the
-    // block's fourth info word: the result is read as soon as that store lands (PMV_BACK_WAIT=sync: hipStreamSynchronize instead)
-    static const bool flag_wait = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
-    volatile unsigned* done_word = (volatile unsigned*)((char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63) + 60);
+    PnPLayout L;
+    if ((rc = pnp_prepare(ctx, b, obj_xyz, img_xy, m, K, iterations, reproj_err, confidence, &P, &L))) return rc;
+    if (stage_by_kernel()) CKC(stage_block(s, b->h_stage.dm(), b->d_pnp_in, L.in_bytes, 8));
+    else CKC(hipMemcpyAsync(b->d_pnp_in, b->h_stage, L.in_bytes, hipMemcpyHostToDevice, s));
+    // the refit kernel writes [PnPResultHdr | inliers] straight into the pinned block and, last, this call's sequence number into the
+    // header's done word: the result is read as soon as that store lands (PMV_BACK_WAIT=sync: hipStreamSynchronize instead)
+    const bool flag_wait = back_wait_by_word();
+    volatile unsigned* done_word = (volatile unsigned*)((char*)b->h_stage + L.done);
     if (++b->done_seq == 0) b->done_seq = 1;
     *done_word = 0;
     CKC(launch_pnp(s, P.obj, P.img, m, P.K, P.samples, iterations, P.thr, confidence, P.models, P.masks, P.counts,
                    P.rt_out, P.inliers, P.info, P.host_out, stamps_on() ? b->d_stamps : nullptr, flag_wait ? b->done_seq : 0u));
-    if (flag_wait) {
-        (void)hipStreamQuery(s);   // lets the runtime retire the commands of earlier calls now, while the GPU works on this one
-        for (unsigned spins = 1;; spins++) {
-            if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == b->done_seq) break;
-            if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
-                const hipError_t e = hipStreamQuery(s);
-                if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
-            }
-            __builtin_ia32_pause();
-        }
-    } else CKC(hipStreamSynchronize(s));
-    pnp_finish(ctx, b, obj_xyz, img_xy, m, K, rvec, tvec, iterations, reproj_err, confidence, in_bytes, out_inliers, out_n_inliers);
+    if ((rc = wait_done_word(ctx, s, done_word, b->done_seq, flag_wait))) return rc;
+    pnp_finish(ctx, b, obj_xyz, img_xy, m, K, rvec, tvec, iterations, reproj_err, confidence, L, out_inliers, out_n_inliers);
     return PMV_OK;
 }
 
@@ -309,20 +296,15 @@ int pmv::ba_check(pmv_ctx* ctx, const double* cams, int nc, const double* pts, i
     return PMV_OK;
 }
 int pmv::ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc, const double* pts, int np, const double* obs_xy, const int* cam_idx,
-                    const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, bool multi, BAArgs* Aout, size_t* io_bytes_out) {
-    // one pinned block mirrors the device block: [summary 8 | cams | pts | obs | K 10 | cam_idx | pt_idx | pstart | plist | cstart | clist]
+                    const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, bool multi, BAArgs* Aout, BaIoLayout* Lout) {
+    // one pinned block mirrors the device block (ba_io_layout)
+    const BaIoLayout L = ba_io_layout((size_t)nc, (size_t)np, (size_t)n_obs);
+    REQ(L.total <= b->d_ba_io.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_ba_solve: io block too small");
     char* hs = (char*)b->h_stage;
-    double* h_sum = (double*)hs;
-    double* h_cams = h_sum + 8;
-    double* h_pts = h_cams + (size_t)nc * 6;
-    double* h_obs = h_pts + (size_t)np * 3;
-    double* h_K = h_obs + (size_t)n_obs * 2;
-    int* h_ci = (int*)(h_K + 10);
-    int* h_pi = h_ci + n_obs;
-    int* pstart = h_pi + n_obs; int* plist = pstart + (np + 1); int* cstart = plist + n_obs; int* clist = cstart + (nc + 1);
-    int* odup = (int*)(((uintptr_t)(clist + n_obs) + 15) & ~(uintptr_t)15);   // 16-byte records (observation, camera, point, dup flag)
-    const size_t io_bytes = (size_t)((char*)(odup + (size_t)4 * n_obs) - hs);
-    REQ(io_bytes <= b->d_ba_io.cap, PMV_ERR_CAPACITY, "pmv_ba_solve: io block too small");
+    double* h_cams = (double*)(hs + L.cams); double* h_pts = (double*)(hs + L.pts); double* h_obs = (double*)(hs + L.obs); double* h_K = (double*)(hs + L.K);
+    int* h_ci = (int*)(hs + L.cam_idx); int* h_pi = (int*)(hs + L.pt_idx);
+    int* pstart = (int*)(hs + L.pstart); int* plist = (int*)(hs + L.plist); int* cstart = (int*)(hs + L.cstart); int* clist = (int*)(hs + L.clist);
+    int* odup = (int*)(hs + L.erec);
     memcpy(h_cams, cams, (size_t)nc * 48); memcpy(h_pts, pts, (size_t)np * 24); memcpy(h_obs, obs_xy, (size_t)n_obs * 16);
     memcpy(h_K, K, 72); memcpy(h_ci, cam_idx, (size_t)n_obs * 4); memcpy(h_pi, pt_idx, (size_t)n_obs * 4);
     // observation lists per point / per camera (counting sort, observation order preserved)
@@ -348,21 +330,14 @@ int pmv::ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc,
     const int m = 6 * nc;
     const int tiles_r = (m + 15) / 16, tiles_c = (m + 1 + 15) / 16;
     char* dio = b->d_ba_io;
-    double* d_sum = (double*)dio;
-    double* d_cams = d_sum + 8;
-    double* d_pts = d_cams + (size_t)nc * 6;
-    double* d_obs = d_pts + (size_t)np * 3;
-    double* d_K = d_obs + (size_t)n_obs * 2;
-    int* d_ci = (int*)(d_K + 10);
-    int* d_pi = d_ci + n_obs;
-    int* d_pstart = d_pi + n_obs; int* d_plist = d_pstart + (np + 1); int* d_cstart = d_plist + n_obs; int* d_clist = d_cstart + (nc + 1);
-    const int4* d_erec = (const int4*)(dio + ((char*)odup - hs));
     BAArgs A;
-    A.cams = d_cams; A.pts = d_pts; A.obs = d_obs; A.cam_idx = d_ci; A.pt_idx = d_pi; A.K = d_K;
-    A.pobs_start = d_pstart; A.pobs_list = d_plist; A.cobs_start = d_cstart; A.cobs_list = d_clist; A.erec = d_erec;
+    A.cams = (double*)(dio + L.cams); A.pts = (double*)(dio + L.pts); A.obs = (const double*)(dio + L.obs); A.K = (const double*)(dio + L.K);
+    A.cam_idx = (const int*)(dio + L.cam_idx); A.pt_idx = (const int*)(dio + L.pt_idx);
+    A.pobs_start = (const int*)(dio + L.pstart); A.pobs_list = (const int*)(dio + L.plist); A.cobs_start = (const int*)(dio + L.cstart); A.cobs_list = (const int*)(dio + L.clist);
+    A.erec = (const int4*)(dio + L.erec);
     A.nc = nc; A.np = np; A.nobs = n_obs; A.max_iterations = max_iterations; A.huber = huber_delta;
     A.x = b->d_x; A.cand = b->d_cand; A.scale = b->d_scale; A.diag = b->d_diag; A.D2 = b->d_D2; A.step = b->d_step; A.res = b->d_res; A.J = b->d_J;
-    A.Einv = b->d_Einv; A.gp = b->d_gp; A.Yd = b->d_Yd; A.Wd = b->d_Wd; A.S = b->d_S; A.rhs = b->d_rhs; A.Gpart = b->d_Gpart; A.summary = d_sum;
+    A.Einv = b->d_Einv; A.gp = b->d_gp; A.Yd = b->d_Yd; A.Wd = b->d_Wd; A.S = b->d_S; A.rhs = b->d_rhs; A.Gpart = b->d_Gpart; A.summary = (double*)(dio + L.summary);
     A.stamps = stamps_on() ? b->d_stamps : nullptr;
     A.out = nullptr;
     A.done_seq = 0;
@@ -379,15 +354,17 @@ int pmv::ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc,
     REQ((size_t)A.krows * A.ldw <= b->ydwd_elems && (size_t)A.kslices * A.gp_rows * A.ldw <= b->gpart_elems, PMV_ERR_CAPACITY, "pmv_ba_solve: workspace too small");
     if (multi) {
         A.Wd = A.Yd + (size_t)A.krows * A.ldw;
-        A.out = (double*)b->h_stage.dm();   // [summary 8 | cams | pts] of the result, straight into the pinned block
+        A.out = (double*)b->h_stage.dm();   // [summary | cams | pts] of the result, straight into the pinned block
     }
     *Aout = A;
-    *io_bytes_out = io_bytes;
+    *Lout = L;
     return PMV_OK;
 }
 void pmv::ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx,
-                    const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, pmv_ba_summary* summary) {
-    const double* h_out = (const double*)b->h_stage;
+                    const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, const BaIoLayout& L, pmv_ba_summary* summary) {
+    const char* hs = (const char*)b->h_stage;
+    const double* h_out = (const double*)(hs + L.summary);
+    const double* h_cams = (const double*)(hs + L.cams);
     static const bool ba_trace = getenv("PMV_BA_TRACE") != nullptr;
     if (ba_trace) {   // diagnostic: first / last camera before and after the solve
         fprintf(stderr, "[ba-trace] nc=%d np=%d nobs=%d cost %.15g -> %.15g it %d ok %d\n", nc, np, n_obs, h_out[0], h_out[1], (int)h_out[2], (int)h_out[3]);
@@ -395,7 +372,7 @@ void pmv::ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, doubl
             fprintf(stderr, "[ba-trace]   cam %d in ", c);
             for (int k = 0; k < 6; k++) fprintf(stderr, " %.15g", cams[6 * c + k]);
             fprintf(stderr, "\n[ba-trace]   cam %d out", c);
-            for (int k = 0; k < 6; k++) fprintf(stderr, " %.15g", h_out[8 + 6 * c + k]);
+            for (int k = 0; k < 6; k++) fprintf(stderr, " %.15g", h_cams[6 * c + k]);
             fprintf(stderr, "\n");
         }
     }
@@ -407,10 +384,10 @@ void pmv::ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, doubl
         pmv_call_log::put(bl, hdr, 20); pmv_call_log::put(bl, cams, (size_t)nc * 48); pmv_call_log::put(bl, pts, (size_t)np * 24);
         pmv_call_log::put(bl, obs_xy, (size_t)n_obs * 16); pmv_call_log::put(bl, K, 72); pmv_call_log::put(bl, &huber_delta, 8);
         pmv_call_log::put(bl, cam_idx, (size_t)n_obs * 4); pmv_call_log::put(bl, pt_idx, (size_t)n_obs * 4);
-        pmv_call_log::put(bl, h_out + 8, ((size_t)nc * 6 + (size_t)np * 3) * 8); pmv_call_log::put(bl, h_out, 40);
+        pmv_call_log::put(bl, h_cams, L.out_bytes - L.cams); pmv_call_log::put(bl, h_out, 40);
     }
-    memcpy(cams, h_out + 8, (size_t)nc * 48);
-    memcpy(pts, h_out + 8 + (size_t)nc * 6, (size_t)np * 24);
+    memcpy(cams, h_cams, (size_t)nc * 48);
+    memcpy(pts, hs + L.pts, (size_t)np * 24);
     if (summary) {
         summary->initial_cost = h_out[0]; summary->final_cost = h_out[1]; summary->iterations = (int)h_out[2];
         summary->successful_steps = (int)h_out[3]; summary->termination = (int)h_out[4];
@@ -442,44 +419,30 @@ int pmv_ba_solve(pmv_ctx* ctx, double* cams, int nc, double* pts, int np, const 
                                  return (e && !strcmp(e, "single")) ? 0 : 1; }();
     const bool single = mode == 0 || ctx->ba_mode == 1;
     BAArgs A;
-    size_t io_bytes = 0;
-    rc = ba_prepare(ctx, b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber_delta, max_iterations, !single, &A, &io_bytes);
+    BaIoLayout L;
+    rc = ba_prepare(ctx, b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber_delta, max_iterations, !single, &A, &L);
     if (rc) return rc;
+    const size_t io_bytes = L.io_bytes;
     char* hs = (char*)b->h_stage;
     static const bool check = getenv("PMV_BA_CHECK") != nullptr;
     // multi-kernel chain: the finish kernel writes the result into hs and, last, this call's sequence number into the low word of summary
-    // slot 7; the result is read as soon as that store lands (PMV_BACK_WAIT=sync: hipStreamSynchronize instead; see pmv_pnp_ransac)
-    static const bool flag_wait_env = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
-    const bool flag_wait = flag_wait_env && !single && !check;
-    volatile unsigned* done_word = (volatile unsigned*)((double*)hs + 7);
+    // slot BA_SUM_DONE; the result is read as soon as that store lands (PMV_BACK_WAIT=sync: hipStreamSynchronize instead; see pmv_pnp_ransac)
+    const bool flag_wait = back_wait_by_word() && !single && !check;
+    volatile unsigned* done_word = (volatile unsigned*)(hs + L.done);
     if (flag_wait) {
         if (++b->done_seq == 0) b->done_seq = 1;
-        ((double*)hs)[7] = 0.0;
+        *(double*)(hs + L.done) = 0.0;
         A.done_seq = b->done_seq;
     }
-    static const bool stage_by_kernel = !(getenv("PMV_BA_STAGE") && !strcmp(getenv("PMV_BA_STAGE"), "dma"));
-    if (stage_by_kernel && !check) {   // (h_stage and d_ba_io are 16-byte aligned and have >= 16 B of slack)
-        const unsigned n16 = (unsigned)((io_bytes + 15) >> 4);
-        hipLaunchKernelGGL(k_stage_block, dim3(std::min(64u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_ba_io, n16);
-        CKC(hipGetLastError());
-    } else CKC(hipMemcpyAsync(b->d_ba_io, hs, io_bytes, hipMemcpyHostToDevice, s));
+    if (stage_by_kernel() && !check) CKC(stage_block(s, b->h_stage.dm(), b->d_ba_io, io_bytes, 64));   // (h_stage and d_ba_io are 16-byte aligned and have >= 16 B of slack)
+    else CKC(hipMemcpyAsync(b->d_ba_io, hs, io_bytes, hipMemcpyHostToDevice, s));
     std::vector<char> saved;
     if (check) saved.assign(hs, hs + io_bytes);
     if (single) CKC(launch_ba_lm(s, A));
     else CKC(launch_ba_multi(s, A, b->d_bastate, b->d_bapart));
-    const size_t out_bytes = (8 + (size_t)nc * 6 + (size_t)np * 3) * 8;
+    const size_t out_bytes = L.out_bytes;
     if (single) CKC(hipMemcpyAsync(hs, b->d_ba_io, out_bytes, hipMemcpyDeviceToHost, s));   // (multi: the finish kernel wrote into hs)
-    if (flag_wait) {
-        (void)hipStreamQuery(s);   // lets the runtime retire the commands of earlier calls while the GPU works on this one
-        for (unsigned spins = 1;; spins++) {
-            if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == b->done_seq) break;
-            if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
-                const hipError_t e = hipStreamQuery(s);
-                if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
-            }
-            __builtin_ia32_pause();
-        }
-    } else CKC(hipStreamSynchronize(s));
+    if ((rc = wait_done_word(ctx, s, done_word, b->done_seq, flag_wait))) return rc;
     const double* h_out = (const double*)hs;
     if (!single && check) {   // diagnostic: the same problem through the one-workgroup kernel, differences to stderr
         std::vector<double> got(h_out, h_out + out_bytes / 8);
@@ -489,26 +452,26 @@ int pmv_ba_solve(pmv_ctx* ctx, double* cams, int nc, double* pts, int np, const 
         CKC(hipMemcpyAsync(hs, b->d_ba_io, out_bytes, hipMemcpyDeviceToHost, s));
         CKC(hipStreamSynchronize(s));
         double dmax = 0;
-        for (size_t i = 8; i < out_bytes / 8; i++) dmax = std::max(dmax, fabs(got[i] - h_out[i]));
+        for (size_t i = BA_SUM_SLOTS; i < out_bytes / 8; i++) dmax = std::max(dmax, fabs(got[i] - h_out[i]));
         fprintf(stderr, "[ba-check] nc=%d np=%d nobs=%d multi: cost %.12g -> %.12g it %d ok %d term %d | single: %.12g -> %.12g it %d ok %d term %d | max|dx| %.3e\n",
                 nc, np, n_obs, got[0], got[1], (int)got[2], (int)got[3], (int)got[4], h_out[0], h_out[1], (int)h_out[2], (int)h_out[3],
                 (int)h_out[4], dmax);
         {   // sensitivity: the same problem with the cameras perturbed by 1e-9 (how much does one solve amplify?)
             std::vector<double> base(h_out, h_out + out_bytes / 8);
             std::vector<char> pert(saved);
-            double* pc = (double*)pert.data() + 8;
+            double* pc = (double*)(pert.data() + L.cams);
             for (int i = 0; i < 6 * nc; i++) pc[i] += 1e-9 * ((i * 2654435761u >> 7) % 3 - 1.0);
             CKC(hipMemcpyAsync(b->d_ba_io, pert.data(), io_bytes, hipMemcpyHostToDevice, s));
             CKC(launch_ba_lm(s, A));
             CKC(hipMemcpyAsync(hs, b->d_ba_io, out_bytes, hipMemcpyDeviceToHost, s));
             CKC(hipStreamSynchronize(s));
             double d2 = 0;
-            for (size_t i = 8; i < out_bytes / 8; i++) d2 = std::max(d2, fabs(base[i] - h_out[i]));
+            for (size_t i = BA_SUM_SLOTS; i < out_bytes / 8; i++) d2 = std::max(d2, fabs(base[i] - h_out[i]));
             fprintf(stderr, "[ba-check]    input perturbed by 1e-9 -> single-kernel output moves by %.3e\n", d2);
         }
         memcpy(hs, got.data(), out_bytes);
     }
-    ba_finish(ctx, b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber_delta, max_iterations, summary);
+    ba_finish(ctx, b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber_delta, max_iterations, L, summary);
     return PMV_OK;
 }
 
@@ -516,66 +479,57 @@ int pmv_ba_solve(pmv_ctx* ctx, double* cams, int nc, double* pts, int np, const 
 
 // ---- five-point RANSAC round: prepare / finish ----------------------------------------------------------------------------------
 int pmv::fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
-                           FivePointProblem* P, size_t* in_bytes_out) {
+                           FivePointProblem* P, FivePointLayout* Lout) {
     REQ(q1 && q2 && samples && n >= 5 && n <= ctx->max_tracks && n_hyp >= 1 && n_hyp <= FP_MAX_HYP, PMV_ERR_INVALID,
         "five-point round: n=%d (5..max_tracks=%d), n_hyp=%d (1..%d)", n, ctx->max_tracks, n_hyp, FP_MAX_HYP);
+    const FivePointLayout L = fivepoint_layout((size_t)n, (size_t)n_hyp);
+    REQ(L.in_bytes <= b->d_tri_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "five-point round: input block too small");
     char* hs = (char*)b->h_stage;
-    // pinned in-block [q1 2n | q2 2n doubles | samples 5 n_hyp ints], out-block [models 90 n_hyp doubles | n_models n_hyp | counts 10 n_hyp ints]
-    double* h_q1 = (double*)hs;
-    double* h_q2 = h_q1 + (size_t)2 * n;
-    int* h_s = (int*)(h_q2 + (size_t)2 * n);
-    const size_t in_bytes = (size_t)4 * n * 8 + (size_t)5 * n_hyp * 4;
-    REQ(in_bytes <= b->d_tri_in.cap, PMV_ERR_CAPACITY, "five-point round: input block too small");
-    memcpy(h_q1, q1, (size_t)n * 16); memcpy(h_q2, q2, (size_t)n * 16); memcpy(h_s, samples, (size_t)5 * n_hyp * 4);
-    P->q1 = (const double*)b->d_tri_in;
-    P->q2 = P->q1 + (size_t)2 * n;
-    P->samples = (const int*)(P->q2 + (size_t)2 * n);
+    memcpy(hs + L.q1, q1, (size_t)n * 16); memcpy(hs + L.q2, q2, (size_t)n * 16); memcpy(hs + L.samples, samples, (size_t)5 * n_hyp * 4);
+    P->q1 = (const double*)(b->d_tri_in + L.q1);
+    P->q2 = (const double*)(b->d_tri_in + L.q2);
+    P->samples = (const int*)(b->d_tri_in + L.samples);
     P->models_d = (double*)b->d_fp_work;
     P->n_models_d = (int*)(b->d_fp_work + (size_t)FP_MAX_HYP * 90 * 8);
-    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    char* dho = b->h_stage.dm() + (ho - hs);
-    P->models_h = (double*)dho;
-    P->n_models_h = (int*)(dho + (size_t)n_hyp * 90 * 8);
-    P->counts_h = P->n_models_h + n_hyp;
+    char* dh = b->h_stage.dm();
+    P->models_h = (double*)(dh + L.models);
+    P->n_models_h = (int*)(dh + L.n_models);
+    P->counts_h = (int*)(dh + L.counts);
     P->n = n; P->n_hyp = n_hyp; P->thr = thr;
     // hypotheses whose sample is degenerate write no models: clear the counts the host will read
-    memset(ho + (size_t)n_hyp * 90 * 8, 0, (size_t)n_hyp * 44);
-    *in_bytes_out = in_bytes;
+    memset(hs + L.n_models, 0, L.total - L.n_models);
+    *Lout = L;
     return PMV_OK;
 }
-void pmv::fivepoint_finish(BackendBuffers* b, int n_hyp, size_t in_bytes, double* models, int* n_models, int* counts) {
-    const char* ho = (const char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63);
-    memcpy(models, ho, (size_t)n_hyp * 90 * 8);
-    memcpy(n_models, ho + (size_t)n_hyp * 90 * 8, (size_t)n_hyp * 4);
-    memcpy(counts, ho + (size_t)n_hyp * 90 * 8 + (size_t)n_hyp * 4, (size_t)n_hyp * 40);
+void pmv::fivepoint_finish(BackendBuffers* b, int n_hyp, const FivePointLayout& L, double* models, int* n_models, int* counts) {
+    const char* hs = (const char*)b->h_stage;
+    memcpy(models, hs + L.models, (size_t)n_hyp * 90 * 8);
+    memcpy(n_models, hs + L.n_models, (size_t)n_hyp * 4);
+    memcpy(counts, hs + L.counts, (size_t)n_hyp * 40);
 }
 
 // ---- two-view DLT: prepare / finish -------------------------------------------------------------------------------------------
-void pmv::dlt_prepare(BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
-                      size_t* in_bytes_out) {
+int pmv::dlt_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
+                     DltLayout* Lout) {
+    const DltLayout L = dlt_layout((size_t)n);
+    REQ(L.in_bytes <= b->d_tri_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_triangulate_candidates: n=%d does not fit the staging blocks", n);
     char* hs = (char*)b->h_stage;
-    // pinned in-block [P1x4 48 | q1 2n | q2 2n | mask n bytes], out-block [Q 16n doubles | mask 4n bytes]
-    double* h_P = (double*)hs;
-    double* h_q1 = h_P + 48;
-    double* h_q2 = h_q1 + (size_t)2 * n;
-    uint8_t* h_m = (uint8_t*)(h_q2 + (size_t)2 * n);
-    const size_t in_bytes = (48 + (size_t)4 * n) * 8 + (size_t)n;
-    memcpy(h_P, P1x4, 48 * 8); memcpy(h_q1, q1, (size_t)n * 16); memcpy(h_q2, q2, (size_t)n * 16); memcpy(h_m, mask_in, (size_t)n);
-    P->P1x4 = (const double*)b->d_tri_in;
-    P->q1 = P->P1x4 + 48;
-    P->q2 = P->q1 + (size_t)2 * n;
-    P->mask_in = (const uint8_t*)(P->q2 + (size_t)2 * n);
-    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    P->Q = (double*)(b->h_stage.dm() + (ho - hs));   // results go straight into the pinned block (coalesced 8-byte stores)
-    P->mask = (uint8_t*)(P->Q + (size_t)16 * n);
+    memcpy(hs + L.P, P1x4, 48 * 8); memcpy(hs + L.q1, q1, (size_t)n * 16); memcpy(hs + L.q2, q2, (size_t)n * 16); memcpy(hs + L.mask_in, mask_in, (size_t)n);
+    P->P1x4 = (const double*)(b->d_tri_in + L.P);
+    P->q1 = (const double*)(b->d_tri_in + L.q1);
+    P->q2 = (const double*)(b->d_tri_in + L.q2);
+    P->mask_in = (const uint8_t*)(b->d_tri_in + L.mask_in);
+    P->Q = (double*)(b->h_stage.dm() + L.Q);   // results go straight into the pinned block (coalesced 8-byte stores)
+    P->mask = (uint8_t*)(b->h_stage.dm() + L.mask);
     P->n = n;
-    *in_bytes_out = in_bytes;
+    *Lout = L;
+    return PMV_OK;
 }
 void pmv::dlt_finish(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
-                     size_t in_bytes, double* out_Q, uint8_t* out_mask, int* out_good) {
-    const char* ho = (const char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63);
-    memcpy(out_Q, ho, (size_t)16 * n * 8);
-    memcpy(out_mask, ho + (size_t)16 * n * 8, (size_t)4 * n);
+                     const DltLayout& L, double* out_Q, uint8_t* out_mask, int* out_good) {
+    const char* hs = (const char*)b->h_stage;
+    memcpy(out_Q, hs + L.Q, (size_t)16 * n * 8);
+    memcpy(out_mask, hs + L.mask, (size_t)4 * n);
     for (int c = 0; c < 4; c++) {
         int g = 0;
         for (int i = 0; i < n; i++) g += out_mask[(size_t)c * n + i];
@@ -603,14 +557,14 @@ int pmv_fivepoint_hypotheses(pmv_ctx* ctx, const double* q1, const double* q2, i
     BackendBuffers* b = ctx->be;
     hipStream_t s = ctx->s_back;
     FivePointProblem P;
-    size_t in_bytes = 0;
-    int rc = fivepoint_prepare(ctx, b, q1, q2, n, samples, n_hyp, thr, &P, &in_bytes);
+    FivePointLayout L;
+    int rc = fivepoint_prepare(ctx, b, q1, q2, n, samples, n_hyp, thr, &P, &L);
     if (rc) return rc;
-    CKC(hipMemcpyAsync(b->d_tri_in, b->h_stage, in_bytes, hipMemcpyHostToDevice, s));
+    CKC(hipMemcpyAsync(b->d_tri_in, b->h_stage, L.in_bytes, hipMemcpyHostToDevice, s));
     CKC(hipMemcpyAsync(b->d_tri_out, &P, sizeof(P), hipMemcpyHostToDevice, s));   // the problem record (d_tri_out is free during a five-point round)
     CKC(launch_fivepoint_batch(s, (const FivePointProblem*)b->d_tri_out, 1, n_hyp));
     CKC(hipStreamSynchronize(s));
-    fivepoint_finish(b, n_hyp, in_bytes, models, n_models, counts);
+    fivepoint_finish(b, n_hyp, L, models, n_models, counts);
     return PMV_OK;
 }
 
@@ -618,12 +572,12 @@ int pmv_fivepoint_hypotheses(pmv_ctx* ctx, const double* q1, const double* q2, i
 static int triangulate_on(pmv_ctx* ctx, BackendBuffers* b, hipStream_t s, const double* q1, const double* q2, int n, const double* P1x4,
                           const uint8_t* mask_in, double* out_Q, uint8_t* out_mask, int* out_good) {
     DltProblem P;
-    size_t in_bytes = 0;
-    dlt_prepare(b, q1, q2, n, P1x4, mask_in, &P, &in_bytes);
-    CKC(hipMemcpyAsync(b->d_tri_in, b->h_stage, in_bytes, hipMemcpyHostToDevice, s));
+    DltLayout L;
+    if (const int rc = dlt_prepare(ctx, b, q1, q2, n, P1x4, mask_in, &P, &L)) return rc;
+    CKC(hipMemcpyAsync(b->d_tri_in, b->h_stage, L.in_bytes, hipMemcpyHostToDevice, s));
     CKC(launch_tri_dlt(s, P.P1x4, P.q1, P.q2, P.mask_in, n, P.Q, P.mask));
     CKC(hipStreamSynchronize(s));
-    dlt_finish(ctx, b, q1, q2, n, P1x4, mask_in, in_bytes, out_Q, out_mask, out_good);
+    dlt_finish(ctx, b, q1, q2, n, P1x4, mask_in, L, out_Q, out_mask, out_good);
     return PMV_OK;
 }
 
@@ -663,14 +617,15 @@ int pmv::essential_check(pmv_ctx* ctx, const char* who, const double* p1_xy, con
     REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, ctx->max_tracks);
     return PMV_OK;
 }
-// pinned in-block [EssentialProblem (ESS_HDR bytes) | q1 2n | q2 2n | log(1 - prob), n + 1 denominators], out-block [E 9 | .. | info at 80 | mask at 128]
-void pmv::essential_prepare(BackendBuffers* b, const double* p1, const double* p2, int n, const double* K, double prob, double threshold,
-                            EssentialProblem* P, size_t* in_bytes_out) {
+// essential_layout: pinned in-block [EssentialProblem | q1 2n | q2 2n | log(1 - prob), n + 1 denominators], out-block [WholeResultHdr | mask]
+int pmv::essential_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* p1, const double* p2, int n, const double* K, double prob, double threshold,
+                           EssentialProblem* P, WholeLayout* Lout) {
+    const WholeLayout L = essential_layout((size_t)n);
+    REQ(L.in_bytes <= b->d_ess_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_find_essential_mat: n=%d does not fit the staging blocks", n);
     char* hs = (char*)b->h_stage;
-    double* h_q1 = (double*)(hs + ESS_HDR);
-    double* h_q2 = h_q1 + (size_t)2 * n;
-    double* h_it = h_q2 + (size_t)2 * n;
-    const size_t in_bytes = ESS_HDR + ((size_t)5 * n + 2) * 8;
+    double* h_q1 = (double*)(hs + L.p1);
+    double* h_q2 = (double*)(hs + L.p2);
+    double* h_it = (double*)(hs + L.iters);
     // the normalisation of vo_fivepoint.cpp:find_essential_mat, expression for expression
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     for (int i = 0; i < n; i++) {
@@ -679,50 +634,30 @@ void pmv::essential_prepare(BackendBuffers* b, const double* p1, const double* p
     }
     threshold /= (fx + fy) / 2;
     vo::five_point_iters_table(n, prob, h_it + 1, h_it);
-    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    P->q1 = (const double*)(b->d_ess_in + ESS_HDR);
-    P->q2 = P->q1 + (size_t)2 * n;
-    P->iters = P->q2 + (size_t)2 * n;
-    P->out = b->h_stage.dm() + (ho - hs);
+    P->q1 = (const double*)(b->d_ess_in + L.p1);
+    P->q2 = (const double*)(b->d_ess_in + L.p2);
+    P->iters = (const double*)(b->d_ess_in + L.iters);
+    P->out = b->h_stage.dm() + L.out;
     P->n = n; P->max_iters = 1000;
     P->thr = (float)(threshold * threshold);
     if (++b->done_seq == 0) b->done_seq = 1;
     P->done_seq = b->done_seq;
-    *(volatile unsigned*)(ho + 92) = 0;
-    *(EssentialProblem*)hs = *P;
-    *in_bytes_out = in_bytes;
+    *whole_done_word(b, L) = 0;
+    *(EssentialProblem*)(hs + L.rec) = *P;
+    *Lout = L;
+    return PMV_OK;
 }
-volatile unsigned* pmv::essential_done_word(BackendBuffers* b, size_t in_bytes) {
-    return (volatile unsigned*)((char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63) + 92);
-}
-void pmv::essential_finish(BackendBuffers* b, int n, size_t in_bytes, double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
-    const char* ho = (const char*)b->h_stage + ((in_bytes + 63) & ~(size_t)63);
-    const int* info = (const int*)(ho + 80);
-    *out_found = info[0]; *out_samples_drawn = info[1];
-    if (info[0]) memcpy(E9, ho, 72);
-    memcpy(mask, ho + ESS_OUT_HDR, (size_t)n);
+volatile unsigned* pmv::whole_done_word(BackendBuffers* b, const WholeLayout& L) { return (volatile unsigned*)((char*)b->h_stage + L.done); }
+void pmv::whole_finish(BackendBuffers* b, int n, const WholeLayout& L, double* M9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    const WholeResultHdr* R = (const WholeResultHdr*)((const char*)b->h_stage + L.out);
+    *out_found = R->found; *out_samples_drawn = R->samples_drawn;
+    if (R->found) memcpy(M9, R->M, 72);
+    memcpy(mask, (const char*)b->h_stage + L.mask, (size_t)n);
 }
 int pmv::recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
                             double* t3, uint8_t* mask, double* tri4n, int* out_good) {
     REQ(ctx && E9 && p1_xy && p2_xy && K && R9 && t3 && mask && tri4n && out_good, PMV_ERR_INVALID, "%s: null argument", who);
     REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, ctx->max_tracks);
-    return PMV_OK;
-}
-
-// Waits for a whole-RANSAC kernel's last store, the call's sequence number in its result block (PMV_BACK_WAIT=sync: hipStreamSynchronize
-// instead; see pmv_pnp_ransac). Shared by pmv_find_essential_mat and pmv_find_fundamental_mat.
-static int wait_done_word(pmv_ctx* ctx, hipStream_t s, volatile unsigned* done_word, unsigned done_seq) {
-    static const bool flag_wait = !(getenv("PMV_BACK_WAIT") && !strcmp(getenv("PMV_BACK_WAIT"), "sync"));
-    if (!flag_wait) { CKC(hipStreamSynchronize(s)); return PMV_OK; }
-    (void)hipStreamQuery(s);
-    for (unsigned spins = 1;; spins++) {
-        if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == done_seq) break;
-        if ((spins & 0xffffu) == 0) {   // a faulted launch never signals: ask the runtime now and then
-            const hipError_t e = hipStreamQuery(s);
-            if (e != hipSuccess && e != hipErrorNotReady) CKC(e);
-        }
-        __builtin_ia32_pause();
-    }
     return PMV_OK;
 }
 
@@ -742,39 +677,34 @@ int pmv::fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, co
     }
     return PMV_OK;
 }
-// pinned in-block [FundamentalProblem (ESS_HDR bytes) | p1 2n floats | p2 2n floats | log(1 - confidence), n + 1 denominators], out-block as
-// essential_prepare's with F in the place of E
+// fundamental_layout: pinned in-block [FundamentalProblem | p1 2n floats | p2 2n floats | log(1 - confidence), n + 1 denominators], out-block
+// as essential_prepare's with F in the place of E
 int pmv::fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, const float* p2, int n, double threshold, double confidence,
-                             FundamentalProblem* P, size_t* in_bytes_out) {
-    const size_t fund_in_bytes = ESS_HDR + (size_t)ctx->max_tracks * 24 + 16 + 64;
+                             FundamentalProblem* P, WholeLayout* Lout) {
+    const size_t fund_in_bytes = fund_in_cap((size_t)ctx->max_tracks);
     if (b->d_fund_in.cap < fund_in_bytes) {   // the set's first such call: a session caller's thread has not chosen the context's device yet
         CKC(hipSetDevice(ctx->device));
         CKC(b->d_fund_in.ensure(fund_in_bytes));
     }
+    const WholeLayout L = fundamental_layout((size_t)n);
+    REQ(L.in_bytes <= b->d_fund_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_find_fundamental_mat: n=%d does not fit the staging blocks", n);
     char* hs = (char*)b->h_stage;
-    float* h_p1 = (float*)(hs + ESS_HDR);
-    float* h_p2 = h_p1 + (size_t)2 * n;
-    double* h_it = (double*)(h_p2 + (size_t)2 * n);
-    const size_t in_bytes = ESS_HDR + (size_t)n * 16 + ((size_t)n + 2) * 8;
-    memcpy(h_p1, p1, (size_t)n * 8);
-    memcpy(h_p2, p2, (size_t)n * 8);
+    double* h_it = (double*)(hs + L.iters);
+    memcpy(hs + L.p1, p1, (size_t)n * 8);
+    memcpy(hs + L.p2, p2, (size_t)n * 8);
     vo::ransac_iters_table(n, confidence, 7, h_it + 1, h_it);
-    char* ho = hs + ((in_bytes + 63) & ~(size_t)63);
-    P->p1 = (const float*)(b->d_fund_in + ESS_HDR);
-    P->p2 = P->p1 + (size_t)2 * n;
-    P->iters = (const double*)(P->p2 + (size_t)2 * n);
-    P->out = b->h_stage.dm() + (ho - hs);
+    P->p1 = (const float*)(b->d_fund_in + L.p1);
+    P->p2 = (const float*)(b->d_fund_in + L.p2);
+    P->iters = (const double*)(b->d_fund_in + L.iters);
+    P->out = b->h_stage.dm() + L.out;
     P->n = n; P->max_iters = 1000;
     P->thr = (float)(threshold * threshold);
     if (++b->done_seq == 0) b->done_seq = 1;
     P->done_seq = b->done_seq;
-    *(volatile unsigned*)(ho + 92) = 0;
-    *(FundamentalProblem*)hs = *P;
-    *in_bytes_out = in_bytes;
+    *whole_done_word(b, L) = 0;
+    *(FundamentalProblem*)(hs + L.rec) = *P;
+    *Lout = L;
     return PMV_OK;
-}
-void pmv::fundamental_finish(BackendBuffers* b, int n, size_t in_bytes, double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
-    essential_finish(b, n, in_bytes, F9, mask, out_found, out_samples_drawn);   // (the same result block)
 }
 
 extern "C" {
@@ -789,14 +719,12 @@ int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_x
     BackendBuffers* b = ctx->be;
     hipStream_t s = ctx->s_back;
     EssentialProblem P;
-    size_t in_bytes = 0;
-    essential_prepare(b, p1_xy, p2_xy, n, K, prob, threshold, &P, &in_bytes);
-    const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
-    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_ess_in, n16);
-    CKC(hipGetLastError());
+    WholeLayout L;
+    if (const int rc = essential_prepare(ctx, b, p1_xy, p2_xy, n, K, prob, threshold, &P, &L)) return rc;
+    CKC(stage_block(s, b->h_stage.dm(), b->d_ess_in, L.in_bytes, 8));
     CKC(launch_essential_ransac(s, (const EssentialProblem*)b->d_ess_in, 1));
-    if (const int rc = wait_done_word(ctx, s, essential_done_word(b, in_bytes), P.done_seq)) return rc;
-    essential_finish(b, n, in_bytes, E9, mask, out_found, out_samples_drawn);
+    if (const int rc = wait_done_word(ctx, s, whole_done_word(b, L), P.done_seq, back_wait_by_word())) return rc;
+    whole_finish(b, n, L, E9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 
@@ -831,14 +759,12 @@ int pmv_find_fundamental_mat(pmv_ctx* ctx, const float* p1_xy, const float* p2_x
     BackendBuffers* b = ctx->be;
     hipStream_t s = ctx->s_back;
     FundamentalProblem P;
-    size_t in_bytes = 0;
-    if (const int rc = fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, &P, &in_bytes)) return rc;
-    const unsigned n16 = (unsigned)((in_bytes + 15) >> 4);
-    hipLaunchKernelGGL(k_stage_block, dim3(std::min(8u, (n16 + 255u) / 256u)), dim3(256), 0, s, (const uint4*)b->h_stage.dm(), (uint4*)b->d_fund_in, n16);
-    CKC(hipGetLastError());
+    WholeLayout L;
+    if (const int rc = fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, &P, &L)) return rc;
+    CKC(stage_block(s, b->h_stage.dm(), b->d_fund_in, L.in_bytes, 8));
     CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)b->d_fund_in, 1));
-    if (const int rc = wait_done_word(ctx, s, essential_done_word(b, in_bytes), P.done_seq)) return rc;
-    fundamental_finish(b, n, in_bytes, F9, mask, out_found, out_samples_drawn);
+    if (const int rc = wait_done_word(ctx, s, whole_done_word(b, L), P.done_seq, back_wait_by_word())) return rc;
+    whole_finish(b, n, L, F9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 

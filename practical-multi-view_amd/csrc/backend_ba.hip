@@ -1531,8 +1531,8 @@ __device__ inline void bam_finish_role(const BAArgs& A, const BAGState* __restri
     __syncthreads();
     const int n = 6 * A.nc + 3 * A.np;
     const double* x = A.x + (size_t)ss.cur * n;
-    double* ocams = A.out ? A.out + 8 : A.cams;
-    double* opts = A.out ? A.out + 8 + 6 * A.nc : A.pts;
+    double* ocams = A.out ? A.out + BA_SUM_SLOTS : A.cams;
+    double* opts = A.out ? A.out + BA_SUM_SLOTS + 6 * A.nc : A.pts;
     double* osum = A.out ? A.out : A.summary;
     for (int i = threadIdx.x; i < 6 * A.nc; i += BM_T) ocams[i] = x[i];
     for (int i = threadIdx.x; i < 3 * A.np; i += BM_T) opts[i] = x[6 * A.nc + i];
@@ -1543,7 +1543,7 @@ __device__ inline void bam_finish_role(const BAArgs& A, const BAGState* __restri
     if (A.out && A.done_seq) {   // the result block is complete: publish this call's sequence number (see pmv_ba_solve)
         __threadfence_system();
         __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store((unsigned*)(A.out + 7), A.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (threadIdx.x == 0) __hip_atomic_store((unsigned*)(A.out + BA_SUM_DONE), A.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 

@@ -371,12 +371,12 @@ __global__ __launch_bounds__(FD_THREADS) void k_fundamental_ransac(const Fundame
         double* Fo = (double*)P.out;
         #pragma unroll 1
         for (int k = 0; k < 9; k++) Fo[k] = found ? sh.best[k] : 0.0;
-        int* info = (int*)(P.out + 80);
+        int* info = (int*)(P.out + ESS_OUT_INFO);
         info[0] = found ? 1 : 0; info[1] = sh.drawn; info[2] = sh.max_good;
     }
     __threadfence_system();
     __syncthreads();
-    if (tid == 0) __hip_atomic_store((unsigned*)(P.out + 92), P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (tid == 0) __hip_atomic_store((unsigned*)(P.out + ESS_OUT_DONE), P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 namespace {

@@ -564,8 +564,8 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
             for (int i = 0; i < 6; i++) rt_out[i] = models[l * 6 + i];
             if (host_out) {
                 for (int i = 0; i < 6; i++) ((double*)host_out)[i] = models[l * 6 + i];
-                ((int*)(host_out + 48))[0] = 0; ((int*)(host_out + 48))[1] = sh.last + 1;
-                if (done_seq) { __threadfence_system(); __hip_atomic_store((unsigned*)(host_out + 60), done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+                ((int*)(host_out + PNP_OUT_INFO))[0] = 0; ((int*)(host_out + PNP_OUT_INFO))[1] = sh.last + 1;
+                if (done_seq) { __threadfence_system(); __hip_atomic_store((unsigned*)(host_out + PNP_OUT_DONE), done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
             }
         }
         return;
@@ -749,13 +749,13 @@ __device__ __forceinline__ void pnp_select_refit_body(const float* __restrict__ 
     if (tid < 6) rt_out[tid] = sh.param[tid];
     if (host_out) {   // the result block in mapped pinned host memory: no device-to-host copy afterwards
         if (tid < 6) ((double*)host_out)[tid] = sh.param[tid];
-        if (tid == 0) { ((int*)(host_out + 48))[0] = n; ((int*)(host_out + 48))[1] = sh.last + 1; }
-        int* hin = (int*)(host_out + 64);
+        if (tid == 0) { ((int*)(host_out + PNP_OUT_INFO))[0] = n; ((int*)(host_out + PNP_OUT_INFO))[1] = sh.last + 1; }
+        int* hin = (int*)(host_out + PNP_OUT_INLIERS);
         for (int e = tid; e < n; e += RF_T) hin[e] = inliers[e];
         if (done_seq) {
             __threadfence_system();
             __syncthreads();
-            if (tid == 0) __hip_atomic_store((unsigned*)(host_out + 60), done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (tid == 0) __hip_atomic_store((unsigned*)(host_out + PNP_OUT_DONE), done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

@@ -16,10 +16,9 @@
 #include "backend.h"
 #include "batch_engine.h"
 #include "ingest_batch.h"
+#include "pmv_block.h"
+#include "pmv_wait.h"
 #include <sys/prctl.h>
-#include <linux/futex.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -34,8 +33,15 @@ namespace pmv {
 
 namespace {
 
+// What a request asks for. The detector values are the `kind` argument of engine_detect (batch_engine.h); from Q_WHOLE_FIRST on the engine
+// owns the request record (WholeReq).
+enum ReqKind {
+    Q_LK = 0, Q_GFTT = 1 /* plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments */, Q_SHITOMASI = 2, Q_FAST = 3,
+    Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6 /* the detector combiner */,
+    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_WHOLE_FIRST = Q_ESSENTIAL
+};
 struct Req {
-    int kind = 0;          // 0 LK, 1 GFTT (plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments), 2 ShiTomasi, 3 FAST, 4 kNN matcher, 5 extended LK (both served by the LK combiners), 6 corner sub-pixel refinement (the detector combiner) | 10 PnP, 11 BA, 12 DLT, 13 five-point round, 14 whole findEssentialMat, 15 whole findFundamentalMat
+    int kind = Q_LK;
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -52,11 +58,11 @@ struct LKReq : Req {
     int base = 0;             // filled by the combiner: first index in the concatenated arrays
     int geom = 0;             // filled by the combiner: the geometry-table entry of its two frames
     int ring_round = -1;      // the feed round that builds the two frames (-1 = nothing to wait for)
-    // kind 5 (pmv_lk_track_ex / _fb): out_xy is in/out, flags = LKX_*; with LKX_FB the three back outputs
+    // Q_LK_EX (pmv_lk_track_ex / _fb): out_xy is in/out, flags = LKX_*; with LKX_FB the three back outputs
     int flags = 0;
     float* back_xy = nullptr; uint8_t* back_status = nullptr; float* back_err = nullptr;
 };
-struct KnnReq : Req {         // kind 4: one kNNFeatureMatcher call (pmv_knn_match's contract)
+struct KnnReq : Req {         // Q_KNN: one kNNFeatureMatcher call (pmv_knn_match's contract)
     int src_slot, cmp_slot, n, m, n_nn, window;
     const int* src_xy; const int* cmp_xy; int* out_best; float* err_out;
     int base = 0;             // filled by the combiner: first index in the round's result arrays (shared with the LK requests)
@@ -65,7 +71,7 @@ struct KnnReq : Req {         // kind 4: one kNNFeatureMatcher call (pmv_knn_mat
 };
 struct DetReq : Req {
     int slot, n_cells, max_per_cell, unlimited;
-    const int* cells; double quality, min_dist;   // FAST (kind 3): quality = threshold, min_dist = the non-max flag
+    const int* cells; double quality, min_dist;   // FAST: quality = threshold, min_dist = the non-max flag
     int* out_xy; double* out_score; int* out_count;
     float* out_resp = nullptr;                    // FAST: KeyPoint::response per keypoint
     int cell_base = 0;
@@ -74,23 +80,23 @@ struct DetReq : Req {
     int ext = 0, block_size = 3, use_harris = 0; double k = 0.0;
     const uint8_t* mask = nullptr; int mask_stride = 0;
 };
-struct SubpixReq : Req {      // kind 6: one pmv_batch_corner_subpix call; p's zero zone is the effective one (subpix_zero_zone)
+struct SubpixReq : Req {      // Q_SUBPIX: one pmv_batch_corner_subpix call; p's zero zone is the effective one (subpix_zero_zone)
     int slot, n;
     float* xy; uint8_t* iters_out; uint8_t* flags_out;
     pmv_subpix_params p;
     int base = 0;             // filled by the combiner: first index in the round's record and result arrays
     int geom = 0;             // filled by the combiner: the geometry-table entry of its frame
 };
-struct PnPReq : Req { BackendBuffers* b; PnPProblem P; size_t in_bytes; };
-struct BAReq : Req { BackendBuffers* b; BAArgs A; size_t io_bytes; int max_iterations; };
-struct DltReq : Req { BackendBuffers* b; DltProblem P; size_t in_bytes; };
-struct FPReq : Req { BackendBuffers* b; FivePointProblem P; size_t in_bytes; };
-// kinds 14, 15: a whole findEssentialMat / findFundamentalMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
+struct PnPReq : Req { BackendBuffers* b; PnPProblem P; PnPLayout L; };
+struct BAReq : Req { BackendBuffers* b; BAArgs A; BaIoLayout L; int max_iterations; };
+struct DltReq : Req { BackendBuffers* b; DltProblem P; DltLayout L; };
+struct FPReq : Req { BackendBuffers* b; FivePointProblem P; FivePointLayout L; };
+// Q_ESSENTIAL, Q_FUNDAMENTAL: a whole findEssentialMat / findFundamentalMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
 // before the round's launch ends (a round ends with its slowest request) - so the record cannot live on the caller's stack like the others:
 // the combiner's store into `done` after its stream sync would land in a dead frame. The engine owns one record per seq and kind; `inflight` is 1
 // from the submit until the combiner has released the record after the round, and the seq's next call of that kind waits for that before it
 // fills the record again.
-struct WholeReq : Req { BackendBuffers* b = nullptr; size_t in_bytes = 0; std::atomic<int> inflight{0}; };
+struct WholeReq : Req { BackendBuffers* b = nullptr; WholeLayout L{}; std::atomic<int> inflight{0}; };
 struct EssReq : WholeReq { EssentialProblem P; };
 struct FundReq : WholeReq { FundamentalProblem P; };
 
@@ -135,13 +141,9 @@ struct Combiner {
     // results of cap_tracks tracks (LK combiners; mapped pinned, the kernels write them through .dm()); the detector combiner's overflow bits
     Buf<float> h_out_xy{MEM_MAPPED}, h_err{MEM_MAPPED}; Buf<uint8_t> h_status{MEM_MAPPED}; Buf<uint16_t> h_work{MEM_MAPPED};
     Buf<int> d_flags;
-    // completion word of the "flag" wait: the last launch of a round is k_signal, which stores the round number into mapped pinned memory
-    Buf<unsigned> h_done{MEM_MAPPED}; unsigned done_seq = 0;
-    double ema_wait_us = 0;            // smoothed duration of the wait of a round (how long to sleep before the first look)
-    long n_polls = 0; double t_first_sleep = 0, t_prep = 0, t_post = 0;   // diagnostic (PMV_BATCH_TIMING=1, printed when the engine goes)
+    RoundSignal sig;                   // completion word of the "flag" wait (pmv_wait.h)
+    RoundSignal::Diag sig_diag;        // diagnostic (PMV_BATCH_TIMING=1, printed when the engine goes)
 };
-
-__global__ void k_signal(unsigned* done, unsigned seq) { BACKEND_PRIO(); __threadfence_system(); __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 
 // one input block to pull from mapped pinned host memory into HBM (16-byte granules; both buffers have >= 16 B of slack)
 struct StageJob { const char* src; char* dst; unsigned bytes, pad; };
@@ -219,43 +221,23 @@ hipError_t wait_stream(BatchEngine* E, Combiner& C) {
         if (e != hipSuccess) return e;
         return hipEventSynchronize(C.ev);
     }
-    // completion word: sleep through most of the expected duration, then look every ~10 us (timer slack of the thread is 1 us)
-    const unsigned seq = ++C.done_seq;
-    hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, C.s, C.h_done.dm(), seq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto done = [&] { return __atomic_load_n(C.h_done.get(), __ATOMIC_ACQUIRE) == seq; };
-    if (!done()) {
-        const double first = 0.7 * C.ema_wait_us;
-        if (first > 25) { std::this_thread::sleep_for(std::chrono::nanoseconds((long)(first * 1e3))); C.t_first_sleep += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-        int looks = 0;
-        while (!done()) {
-            C.n_polls++;
-            std::this_thread::sleep_for(std::chrono::microseconds(10));
-            if ((++looks & 255) == 0) {   // a faulted launch never signals: ask the runtime now and then
-                e = hipStreamQuery(C.s);
-                if (e != hipSuccess && e != hipErrorNotReady) return e;
-            }
-        }
-    }
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    C.ema_wait_us = C.ema_wait_us == 0 ? us : 0.8 * C.ema_wait_us + 0.2 * us;
-    // The completion word tells US that the round is over; the runtime has not been asked anything about this stream since the launches.
-    // One query per round lets it retire the round's commands now instead of finding them all still on its books at some later launch.
+    // completion word (the signal kernel raises its priority as the back-end kernels do). It tells US that the round is over; the runtime has
+    // not been asked anything about this stream since the launches: one query per round lets it retire the round's commands now.
     static const bool query_each_round = !(getenv("PMV_BATCH_QUERY") && atoi(getenv("PMV_BATCH_QUERY")) == 0);
-    if (query_each_round) { e = hipStreamQuery(C.s); if (e != hipSuccess && e != hipErrorNotReady) return e; }
-    return hipSuccess;
+    return C.sig.signal_and_wait<true>(C.s, query_each_round, &C.sig_diag);
 }
 
 // ---- LK -------------------------------------------------------------------------------------------------------------------------
+// back results of a round's forward-backward tracks: lk_back_block over the lane's h_back at cap_tracks tracks
+size_t back_bytes(size_t cap) { Carve c; lk_back_block(c, cap); return c.bytes() + 64; }
+LkBackBlock back_block(const Combiner& C, size_t cap) { Carve c = carve_of(C.h_back); return lk_back_block(c, cap); }
 void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     pmv_ctx* ctx = E->ctx;
     hipStream_t s = C.s;
     std::vector<LKReq*> lk;
     std::vector<KnnReq*> knn;   // (sequences that run the kNN matcher: the same role, the same round)
     std::vector<LKReq*> lkx;    // (extended LK requests: one more launch for all of them)
-    for (Req* r : batch) { if (r->kind == 4) knn.push_back((KnnReq*)r); else if (r->kind == 5) lkx.push_back((LKReq*)r); else lk.push_back((LKReq*)r); }
+    for (Req* r : batch) { if (r->kind == Q_KNN) knn.push_back((KnnReq*)r); else if (r->kind == Q_LK_EX) lkx.push_back((LKReq*)r); else lk.push_back((LKReq*)r); }
     // ---- LK: one launch for the tracks of every requesting sequence, whatever their frame sizes: a request's geometry is the one staged in
     // its prev slot (prev and next of ONE request must agree), carried by each of its track records as an index into the context's table
     const unsigned long long pitch = ctx->cap.slot_bytes;
@@ -272,8 +254,16 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     }
     // ---- kNN matcher: one k_knn_round launch for the requests of the round. Its results use the indices behind the LK tracks in the same
     // mapped pinned result blocks (best index: the first n ints of the request's 2 n coordinate floats; window error: the error block).
+    // The round block, pinned mirror and HBM copy: [stage-in job | at byte 64: KnnRound x requests | src list, cmp list of every live request,
+    // each a multiple of 16 bytes]. The same two functions size it (dry run) and carve it.
     int knn_tracks = 0, knn_max_n = 0;
-    size_t knn_bytes = 64 + sizeof(KnnRound) * knn.size();   // [stage-in job | records | lists, each a multiple of 16 bytes]
+    auto knn_head = [&](Carve& c) { c.take<StageJob>(1); return c.take<KnnRound>(knn.size(), 64); };
+    auto knn_lists = [](Carve& c, const KnnReq* r, Carved<int>* src, Carved<int>* cmp) {
+        *src = c.take<int>(2 * (size_t)r->n, 16); *cmp = c.take<int>(2 * (size_t)r->m, 16); c.skip_to(16);
+    };
+    Carved<int> l_src, l_cmp;
+    Carve knn_need;
+    knn_head(knn_need);
     for (KnnReq* r : knn) {
         const PyrLayout& a = ctx->slot_layout[r->src_slot];
         const PyrLayout& b2 = ctx->slot_layout[r->cmp_slot];
@@ -282,33 +272,32 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         r->base = total_tracks + knn_tracks;
         knn_tracks += r->n;
         knn_max_n = std::max(knn_max_n, r->n);
-        knn_bytes += (((size_t)r->n * 8 + 15) & ~(size_t)15) + (((size_t)r->m * 8 + 15) & ~(size_t)15);
+        knn_lists(knn_need, r, &l_src, &l_cmp);
         need_ring = std::max(need_ring, r->ring_round);
     }
     bool ring_waited = false;
     if (knn_tracks > 0) {
         if (need_ring >= 0) { EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring)); ring_waited = true; }
         if ((size_t)total_tracks + (size_t)knn_tracks > E->cap_tracks) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
-        EK(C.h_knn.ensure(knn_bytes + 64)); EK(C.d_knn.ensure(knn_bytes + 64));
-        char* hb = (char*)C.h_knn.p;
-        char* db = (char*)C.d_knn.p;
-        KnnRound* rec = (KnnRound*)(hb + 64);
-        size_t off = 64 + sizeof(KnnRound) * knn.size();
+        EK(C.h_knn.ensure(knn_need.bytes() + 64)); EK(C.d_knn.ensure(knn_need.bytes() + 64));
+        Carve c(C.h_knn.p, C.d_knn.p, C.h_knn.cap);
+        const Carved<KnnRound> rec = knn_head(c);
         int n_rec = 0;
         for (KnnReq* r : knn) {
             if (r->rc != PMV_OK) continue;
-            KnnRound& k = rec[n_rec++];
+            KnnRound& k = rec.h[n_rec++];
             k.src_off = (unsigned long long)r->src_slot * pitch; k.cmp_off = (unsigned long long)r->cmp_slot * pitch;
-            k.src_xy = (const int*)(db + off); memcpy(hb + off, r->src_xy, (size_t)r->n * 8); off += ((size_t)r->n * 8 + 15) & ~(size_t)15;
-            k.cmp_xy = (const int*)(db + off); if (r->m) memcpy(hb + off, r->cmp_xy, (size_t)r->m * 8); off += ((size_t)r->m * 8 + 15) & ~(size_t)15;
+            knn_lists(c, r, &l_src, &l_cmp);
+            k.src_xy = l_src.d; memcpy(l_src.h, r->src_xy, (size_t)r->n * 8);
+            k.cmp_xy = l_cmp.d; if (r->m) memcpy(l_cmp.h, r->cmp_xy, (size_t)r->m * 8);
             k.out_best = (int*)C.h_out_xy.dm() + 2 * (size_t)r->base; k.out_err = C.h_err.dm() + r->base;
             k.n = r->n; k.m = r->m; k.nn_window = knn_pack(r->n_nn, r->window); k.geom = r->geom;
         }
         // one gather pulls records and lists into HBM (every workgroup of a request scans its whole candidate list): no DMA call
-        *(StageJob*)hb = StageJob{C.h_knn.dev + 64, db + 64, (unsigned)(off - 64), 0};
+        *(StageJob*)C.h_knn.p = StageJob{C.h_knn.dev + rec.off, (char*)rec.d, (unsigned)(c.bytes() - rec.off), 0};
         hipLaunchKernelGGL(k_stage_in, dim3(64, 1), dim3(256), 0, s, (const StageJob*)C.h_knn.dev);
         EK(hipGetLastError());
-        EK(launch_knn_round_geom(s, ctx->d_slots, ctx->d_geom, (const KnnRound*)(db + 64), n_rec, knn_max_n));
+        EK(launch_knn_round_geom(s, ctx->d_slots, ctx->d_geom, rec.d, n_rec, knn_max_n));
         ctx->batch_launches[1]++;
     }
     if (total_tracks > 0) {
@@ -371,9 +360,12 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         const size_t cap = E->cap_tracks;
         if ((size_t)total_tracks + (size_t)knn_tracks + (size_t)ext_tracks > cap) { fail_all(batch, PMV_ERR_CAPACITY, "more tracks than B * max_tracks", hipSuccess); return; }
         EK(C.h_lkx.ensure((sizeof(LKBlock) + sizeof(LKExt)) * (size_t)ext_tracks + 64));
-        EK(C.h_back.ensure(cap * 13 + 64));
-        LKBlock* hblk = (LKBlock*)C.h_lkx.p;
-        LKExt* hext = (LKExt*)(hblk + ext_tracks);
+        EK(C.h_back.ensure(back_bytes(cap)));
+        Carve cx = carve_of(C.h_lkx);   // [LKBlock | LKExt] records of the round, read through the mapped alias
+        const Carved<LKBlock> blk = cx.take<LKBlock>((size_t)ext_tracks);
+        const Carved<LKExt> ext = cx.take<LKExt>((size_t)ext_tracks);
+        LKBlock* hblk = blk.h;
+        LKExt* hext = ext.h;
         int bpos = 0;
         size_t kmax = 0;
         for (LKReq* r : lkx) if (r->rc == PMV_OK) kmax = std::max(kmax, (size_t)r->n);
@@ -388,8 +380,9 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 x.ix = init ? r->out_xy[2 * k] : 0.f; x.iy = init ? r->out_xy[2 * k + 1] : 0.f; x.flags = r->flags; x.reserved = 0;
             }
         const LKParams P = lk_launch_params(ctx);
-        EK(launch_lk_batch_ex(s, ctx->d_slots, (const LKBlock*)C.h_lkx.dev, (const LKExt*)(C.h_lkx.dev + sizeof(LKBlock) * (size_t)ext_tracks), bpos, ctx->d_geom, P, C.h_out_xy.dm(),
-                              C.h_status.dm(), C.h_err.dm(), C.h_work.dm(), (float*)C.h_back.dev, (uint8_t*)(C.h_back.dev + cap * 12), (float*)(C.h_back.dev + cap * 8)));
+        const LkBackBlock back = back_block(C, cap);
+        EK(launch_lk_batch_ex(s, ctx->d_slots, blk.d, ext.d, bpos, ctx->d_geom, P, C.h_out_xy.dm(),
+                              C.h_status.dm(), C.h_err.dm(), C.h_work.dm(), back.xy.d, back.status.d, back.err.d));
         ctx->batch_launches[0]++;
     }
     SYNC_TIMED(C);
@@ -399,10 +392,10 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         memcpy(r->status, C.h_status + r->base, (size_t)r->n);
         memcpy(r->err_out, C.h_err + r->base, (size_t)r->n * 4);
         if (r->flags & LKX_FB) {
-            const char* hb = (const char*)C.h_back.p;
-            memcpy(r->back_xy, hb + (size_t)8 * r->base, (size_t)r->n * 8);
-            memcpy(r->back_err, hb + E->cap_tracks * 8 + (size_t)4 * r->base, (size_t)r->n * 4);
-            memcpy(r->back_status, hb + E->cap_tracks * 12 + r->base, (size_t)r->n);
+            const LkBackBlock back = back_block(C, E->cap_tracks);
+            memcpy(r->back_xy, back.xy.h + (size_t)2 * r->base, (size_t)r->n * 8);
+            memcpy(r->back_err, back.err.h + r->base, (size_t)r->n * 4);
+            memcpy(r->back_status, back.status.h + r->base, (size_t)r->n);
         }
         ctx->add_lk_work(C.h_work + r->base, (size_t)r->n);
     }
@@ -422,15 +415,21 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
 }
 
 // ---- detectors --------------------------------------------------------------------------------------------------------------------
+// result block of a round's detector launches, written by the kernels through the mapped alias: [xy | score | count | overflow flags]
+struct DetBlock { Carved<int> xy; Carved<double> score; Carved<int> count, flags; };
+DetBlock det_block(const Combiner& C, size_t tot_out, size_t tot_cells) {
+    Carve c = carve_of(C.h_det);
+    return {c.take<int>(2 * tot_out), c.take<double>(tot_out), c.take<int>(tot_cells), c.take<int>(1)};
+}
 void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     pmv_ctx* ctx = E->ctx;
     hipStream_t s = C.s;
     std::vector<DetReq*> det;
     std::vector<SubpixReq*> spx;   // (corner sub-pixel requests: the same role, the same round, one more launch per parameter set)
-    for (Req* r : batch) { if (r->kind == 6) spx.push_back((SubpixReq*)r); else det.push_back((DetReq*)r); }
+    for (Req* r : batch) { if (r->kind == Q_SUBPIX) spx.push_back((SubpixReq*)r); else det.push_back((DetReq*)r); }
     // ---- detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
     // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
-    // FAST (kind 3; grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
+    // FAST (grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
     // its score maps are sized by the pixels of the round (d_fast_score), the cell record's offset into them stays within int.
     // Extended GFTT requests (ext) also agree in block size, response kind, k and has-mask; a round without one launches what it always did.
     struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; int max_pix = 0;
@@ -440,7 +439,7 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (DetReq* r : det) {
         const PyrLayout& Lr = ctx->slot_layout[r->slot];
         if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d holds no built pyramid", r->slot); continue; }
-        if (r->kind == 3) {
+        if (r->kind == Q_FAST) {
             size_t pix = 0;
             for (int i = 0; i < r->n_cells; i++) pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
             if (fast_pix + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch FAST: the cells of the round cover more than 2^31 pixels"); continue; }
@@ -464,15 +463,15 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         g->n_cells += r->n_cells;
         g->reqs.push_back(r);
     }
+    size_t tot_cells = 0, tot_out = 0;
+    for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
     if (!det.empty()) {   // (a round of sub-pixel requests alone has no detector launch)
-        size_t tot_cells = 0, tot_out = 0;
-        for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
         size_t eig_cells = 0;   // cells of the GFTT / ShiTomasi groups: the response, cell-maximum and spill areas are theirs alone
-        for (Group& g : groups) if (g.kind != 3) eig_cells += g.n_cells;
+        for (Group& g : groups) if (g.kind != Q_FAST) eig_cells += g.n_cells;
         const size_t cells_bytes = tot_cells * CELL_STRIDE * 4;
         EK(C.h_cells.ensure(cells_bytes + 64));   // (+ the stage-in job of a round with FAST cells)
         EK(C.d_eig.ensure(eig_cells * CELL_PIX * sizeof(double))); EK(C.d_cellmax.ensure(eig_cells * 8)); EK(C.d_spill.ensure(eig_cells * CELL_PIX * 4));
-        EK(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // [xy | score | count | flags], written by the kernels through the mapped alias
+        EK(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // (det_block)
         if (mask_bytes) { EK(C.h_gmask.ensure(mask_bytes + 64)); EK(C.d_gmask.ensure(mask_bytes + 64)); }
         int* hc = (int*)C.h_cells.p;
         size_t cpos = 0, fpos = 0, mpos = 0;
@@ -484,7 +483,7 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                     int* d = hc + cpos * CELL_STRIDE;
                     d[0] = r->cells[4 * i]; d[1] = r->cells[4 * i + 1]; d[2] = r->cells[4 * i + 2]; d[3] = r->cells[4 * i + 3]; d[4] = r->slot; d[6] = d[7] = 0;
                     if (!masked) d[5] = 0;   // (a masked cell's int 5 = the offset of its mask bytes, written by gftt_pack_mask)
-                    if (g.kind == 3) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
+                    if (g.kind == Q_FAST) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
                 }
             }
         if (mask_bytes) EK(hipMemcpyAsync(C.d_gmask.p, C.h_gmask.p, mask_bytes, hipMemcpyHostToDevice, s));
@@ -503,30 +502,29 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         }
         size_t c0 = 0, e0 = 0;   // first cell of the group among all cells of the round / among those with a response area (c0 = e0 in a round without FAST)
-        char* hd = (char*)C.h_det.p;
-        char* dd = C.h_det.dev;
+        const DetBlock D = det_block(C, tot_out, tot_cells);
         for (Group& g : groups) {
             const int* dc = (const int*)C.h_cells.dev + c0 * CELL_STRIDE;
-            int* dxy = (int*)dd + g.out_off * 2;
-            double* dsc = (double*)(dd + tot_out * 8) + g.out_off;
-            int* dcnt = (int*)(dd + tot_out * 16) + c0;
-            if (g.kind == 1 && g.ext)
+            int* dxy = D.xy.d + g.out_off * 2;
+            double* dsc = D.score.d + g.out_off;
+            int* dcnt = D.count.d + c0;
+            if (g.kind == Q_GFTT && g.ext)
                 EK(launch_gftt_ex(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, gftt_ext(g.block_size, g.use_harris, g.k),
                                   g.has_mask ? (const uint8_t*)C.d_gmask.p : nullptr, (float*)C.d_eig.p + e0 * CELL_PIX, (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt,
                                   C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
-            else if (g.kind == 1)
+            else if (g.kind == Q_GFTT)
                 EK(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + e0 * CELL_PIX,
                                (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
-            else if (g.kind == 2)
+            else if (g.kind == Q_SHITOMASI)
                 EK(launch_shitomasi(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, (double*)C.d_eig.p + e0 * CELL_PIX,
                                     (unsigned long long*)C.d_cellmax.p + e0, dxy, dsc, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
             else   // FAST: records from HBM, float responses in the group's share of the score block
                 EK(launch_fast(s, ctx->d_slots, g.L, (const int*)C.d_cells.p + c0 * CELL_STRIDE, g.n_cells, g.max_pix, g.max_per_cell, (int)g.quality, (int)g.min_dist,
                                (uint8_t*)C.d_fast_score.p, dxy, (float*)dsc, dcnt));
             c0 += g.n_cells;
-            if (g.kind != 3) e0 += g.n_cells;
+            if (g.kind != Q_FAST) e0 += g.n_cells;
         }
-        EK(hipMemcpyAsync(hd + tot_out * 16 + tot_cells * 4, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
+        EK(hipMemcpyAsync(D.flags.h, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
     }
     // ---- corner sub-pixel refinement: requests that agree in the six parameters share ONE launch, whatever their slots and frame sizes -
     // every point's record names its slot and its entry of the geometry table. A round without such a request adds nothing here.
@@ -547,10 +545,13 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         spx_total += (size_t)r->n;
     }
     if (spx_total > 0) {
-        const size_t off_xy = spx_total * sizeof(SubpixRec), off_it = off_xy + spx_total * 8, off_fl = off_it + spx_total;
         const size_t tab_bytes = sgroups.size() * SUBPIX_TABLE_MAX * sizeof(float);
-        EK(C.h_spx.ensure(off_fl + spx_total + 64)); EK(C.h_spx_tab.ensure(tab_bytes)); EK(C.d_spx_tab.ensure(tab_bytes));
-        SubpixRec* rec = (SubpixRec*)C.h_spx.p;
+        Carve spx_need;
+        subpix_block(spx_need, spx_total);
+        EK(C.h_spx.ensure(spx_need.bytes() + 64)); EK(C.h_spx_tab.ensure(tab_bytes)); EK(C.d_spx_tab.ensure(tab_bytes));
+        Carve c = carve_of(C.h_spx);
+        const SubpixBlock S = subpix_block(c, spx_total);
+        SubpixRec* rec = S.rec.h;
         int pos = 0;
         for (size_t gi = 0; gi < sgroups.size(); gi++) {
             SGroup& g = sgroups[gi];
@@ -565,39 +566,37 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         for (size_t gi = 0; gi < sgroups.size(); gi++) {
             const SGroup& g = sgroups[gi];
             const SubpixArgs A{g.p.win_w, g.p.win_h, g.p.max_iter, g.p.eps * g.p.eps};
-            EK(launch_corner_subpix_geom(s, ctx->d_slots, ctx->d_geom, (const SubpixRec*)C.h_spx.dev + g.base, g.n, (const float*)C.d_spx_tab.p + gi * SUBPIX_TABLE_MAX, A,
-                                         (float*)(C.h_spx.dev + off_xy) + 2 * (size_t)g.base, (uint8_t*)C.h_spx.dev + off_it + g.base, (uint8_t*)C.h_spx.dev + off_fl + g.base));
+            EK(launch_corner_subpix_geom(s, ctx->d_slots, ctx->d_geom, S.rec.d + g.base, g.n, (const float*)C.d_spx_tab.p + gi * SUBPIX_TABLE_MAX, A,
+                                         S.xy.d + 2 * (size_t)g.base, S.iters.d + g.base, S.flags.d + g.base));
             ctx->subpix_launches[2]++;
         }
         ctx->subpix_launches[1]++;
     }
     SYNC_TIMED(C);
     if (spx_total > 0) {
-        const char* hb = (const char*)C.h_spx.p;
-        const size_t off_xy = spx_total * sizeof(SubpixRec), off_it = off_xy + spx_total * 8, off_fl = off_it + spx_total;
+        Carve c = carve_of(C.h_spx);
+        const SubpixBlock S = subpix_block(c, spx_total);
         for (SGroup& g : sgroups)
             for (SubpixReq* r : g.reqs) {
-                memcpy(r->xy, hb + off_xy + (size_t)8 * r->base, (size_t)r->n * 8);
-                if (r->iters_out) memcpy(r->iters_out, hb + off_it + r->base, (size_t)r->n);
-                if (r->flags_out) memcpy(r->flags_out, hb + off_fl + r->base, (size_t)r->n);
+                memcpy(r->xy, S.xy.h + (size_t)2 * r->base, (size_t)r->n * 8);
+                if (r->iters_out) memcpy(r->iters_out, S.iters.h + r->base, (size_t)r->n);
+                if (r->flags_out) memcpy(r->flags_out, S.flags.h + r->base, (size_t)r->n);
             }
     }
     if (!det.empty()) {
-        size_t tot_cells = 0, tot_out = 0;
-        for (Group& g : groups) { tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
-        const char* hd = (const char*)C.h_det.p;
-        const int flags = *(const int*)(hd + tot_out * 16 + tot_cells * 4);
-        const int* hxy = (const int*)hd;
-        const double* hsc = (const double*)(hd + tot_out * 8);
-        const int* hcnt = (const int*)(hd + tot_out * 16);
+        const DetBlock D = det_block(C, tot_out, tot_cells);
+        const int flags = *D.flags.h;
+        const int* hxy = D.xy.h;
+        const double* hsc = D.score.h;
+        const int* hcnt = D.count.h;
         size_t c0 = 0;
         for (Group& g : groups) {
             for (DetReq* r : g.reqs) {
-                if (g.kind == 1 && (flags & 4)) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "more corners than the no-limit capacity in a cell (batched launch)"); continue; }
+                if (g.kind == Q_GFTT && (flags & 4)) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "more corners than the no-limit capacity in a cell (batched launch)"); continue; }
                 const size_t o = g.out_off + (size_t)r->cell_base * g.max_per_cell;
                 memcpy(r->out_xy, hxy + o * 2, (size_t)r->n_cells * g.max_per_cell * 8);
                 if (r->out_score) memcpy(r->out_score, hsc + o, (size_t)r->n_cells * g.max_per_cell * 8);
-                if (g.kind == 3) memcpy(r->out_resp, (const float*)(hsc + g.out_off) + (size_t)r->cell_base * g.max_per_cell, (size_t)r->n_cells * g.max_per_cell * 4);
+                if (g.kind == Q_FAST) memcpy(r->out_resp, (const float*)(hsc + g.out_off) + (size_t)r->cell_base * g.max_per_cell, (size_t)r->n_cells * g.max_per_cell * 4);
                 memcpy(r->out_count, hcnt + c0 + r->cell_base, (size_t)r->n_cells * 4);
             }
             c0 += g.n_cells;
@@ -606,59 +605,67 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
 }
 
 // ---- back-end classes: the callers prepared their inputs in their slot's pinned block; one gather kernel pulls them into HBM ----
-// Descriptor block of a batch in mapped pinned memory: [problem records | stage-in jobs]. No DMA call is made: k_stage_in reads
+// Descriptor block of a batch in mapped pinned memory: [problem records | problem records of a second kind (process_whole) | stage-in jobs],
+// each part at a multiple of 256 bytes. No DMA call is made: k_stage_in reads
 // its job list through the host alias; job 0 copies the problem records into device memory (the back-end chains read them in every
 // launch), jobs 1..n pull the requests' input blocks. (A hipMemcpyAsync is a blit kernel of its own: 83 k of them, 15 us each in
 // stream time, in a B = 64 run before this.)
-template <class Prob> struct DescBlock { Prob* hprob; StageJob* hjobs; const Prob* dprob; const StageJob* djobs; size_t bytes; };
-template <class Prob>
-hipError_t desc_block(Combiner& C, size_t n, DescBlock<Prob>& D) {
-    const size_t off_jobs = (sizeof(Prob) * n + 255) & ~(size_t)255;
-    D.bytes = off_jobs + sizeof(StageJob) * (n + 1);
+template <class A, class B> struct DescBlock { Carved<A> a; Carved<B> b; Carved<StageJob> jobs; size_t rec_bytes, bytes; };   // .d: records in d_desc, jobs through the mapped alias
+template <class A, class B> DescBlock<A, B> desc_carve(Carve c, size_t na, size_t nb) {
+    DescBlock<A, B> D;
+    D.a = c.take<A>(na); D.rec_bytes = c.bytes();
+    D.b = c.take<B>(nb, 256); if (nb) D.rec_bytes = c.bytes();   // (the end of the last record: what job 0 copies)
+    D.jobs = c.take<StageJob>(1 + na + nb, 256);
+    D.bytes = c.bytes();
+    return D;
+}
+template <class A, class B = char>
+hipError_t desc_block(Combiner& C, size_t na, size_t nb, DescBlock<A, B>& D) {
+    D = desc_carve<A, B>(Carve(), na, nb);   // (dry run: the sizes)
     hipError_t e = C.h_desc.ensure(D.bytes + 256);
     if (e != hipSuccess) return e;
-    e = C.d_desc.ensure(off_jobs + 256);
+    e = C.d_desc.ensure(D.jobs.off + 256);
     if (e != hipSuccess) return e;
-    D.hprob = (Prob*)C.h_desc.p; D.hjobs = (StageJob*)((char*)C.h_desc.p + off_jobs);
-    D.dprob = (const Prob*)C.d_desc.p; D.djobs = (const StageJob*)(C.h_desc.dev + off_jobs);
-    D.hjobs[0] = StageJob{C.h_desc.dev, (char*)C.d_desc.p, (unsigned)(sizeof(Prob) * n), 0};
-    D.hjobs += 1;   // the callers fill jobs 1..n
+    D = desc_carve<A, B>(Carve(C.h_desc.p, C.d_desc.p, C.h_desc.cap), na, nb);
+    D.jobs.d = (StageJob*)(C.h_desc.dev + D.jobs.off);
+    D.jobs.h[0] = StageJob{C.h_desc.dev, (char*)C.d_desc.p, (unsigned)D.rec_bytes, 0};   // job 0: the records themselves
+    D.jobs.h += 1;   // the callers fill jobs 1..n
     return hipSuccess;
 }
-template <class Prob>
-hipError_t stage_in(Combiner& C, const DescBlock<Prob>& D, size_t n, int blocks_per_job) {
-    hipLaunchKernelGGL(k_stage_in, dim3(blocks_per_job, (unsigned)(n + 1)), dim3(256), 0, C.s, D.djobs);
+template <class A, class B>
+hipError_t stage_in(Combiner& C, const DescBlock<A, B>& D, size_t n, int blocks_per_job) {
+    hipLaunchKernelGGL(k_stage_in, dim3(blocks_per_job, (unsigned)(n + 1)), dim3(256), 0, C.s, D.jobs.d);
     return hipGetLastError();
 }
 
 void process_pnp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    DescBlock<PnPProblem> D;
-    EK(desc_block(C, batch.size(), D));
+    DescBlock<PnPProblem, char> D;
+    EK(desc_block(C, batch.size(), 0, D));
     int max_hyp = 0;
     for (size_t i = 0; i < batch.size(); i++) {
         PnPReq* r = (PnPReq*)batch[i];
-        D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_pnp_in, (unsigned)r->in_bytes, 0};
+        D.a.h[i] = r->P;
+        D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_pnp_in, (unsigned)r->L.in_bytes, 0};
         max_hyp = std::max(max_hyp, r->P.n_hyp);
     }
     EK(stage_in(C, D, batch.size(), 2));
-    EK(launch_pnp_batch(C.s, D.dprob, (int)batch.size(), max_hyp));
+    EK(launch_pnp_batch(C.s, D.a.d, (int)batch.size(), max_hyp));
     SYNC_TIMED(C);   // the refit kernel wrote every result straight into the request's pinned block
 }
 
 void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     if (E->ctx->ba_mode == 1) {   // one workgroup per problem: ONE launch for the whole round (pmv_set_ba_mode)
-        DescBlock<BAArgs> D;
-        EK(desc_block(C, batch.size(), D));
+        DescBlock<BAArgs, char> D;
+        EK(desc_block(C, batch.size(), 0, D));
         int max_m = 6;
         for (size_t i = 0; i < batch.size(); i++) {
             BAReq* r = (BAReq*)batch[i];
-            D.hprob[i] = r->A;
-            D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->io_bytes, 0};
+            D.a.h[i] = r->A;
+            D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->L.io_bytes, 0};
             max_m = std::max(max_m, 6 * r->A.nc);
         }
         EK(stage_in(C, D, batch.size(), 8));
-        EK(launch_ba_lm_batch(C.s, D.dprob, (int)batch.size(), max_m));
+        EK(launch_ba_lm_batch(C.s, D.a.d, (int)batch.size(), max_m));
         SYNC_TIMED(C);
         return;
     }
@@ -667,12 +674,12 @@ void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     for (Req* q : batch) { const int it = ((BAReq*)q)->max_iterations; if (std::find(iters.begin(), iters.end(), it) == iters.end()) iters.push_back(it); }
     std::vector<BAReq*> sorted;
     for (int it : iters) for (Req* q : batch) if (((BAReq*)q)->max_iterations == it) sorted.push_back((BAReq*)q);
-    DescBlock<BAProb> D;
-    EK(desc_block(C, sorted.size(), D));
+    DescBlock<BAProb, char> D;
+    EK(desc_block(C, sorted.size(), 0, D));
     for (size_t i = 0; i < sorted.size(); i++) {
         BAReq* r = sorted[i];
-        ba_fill_prob(D.hprob[i], r->A, r->b->d_bastate, r->b->d_bapart);
-        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->io_bytes, 0};
+        ba_fill_prob(D.a.h[i], r->A, r->b->d_bastate, r->b->d_bapart);
+        D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_ba_io, (unsigned)r->L.io_bytes, 0};
     }
     EK(stage_in(C, D, sorted.size(), 8));
     size_t i0 = 0;
@@ -680,78 +687,71 @@ void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         BABatchDims dims{0, 0, 0, 0, 0, 0, it};
         size_t i1 = i0;
         while (i1 < sorted.size() && sorted[i1]->max_iterations == it) {
-            const BAProb& P = D.hprob[i1];
+            const BAProb& P = D.a.h[i1];
             dims.max_eval_blocks = std::max(dims.max_eval_blocks, P.nbo + P.clear_blocks);
             dims.max_nc = std::max(dims.max_nc, P.A.nc); dims.max_nbp = std::max(dims.max_nbp, P.nbp); dims.max_tiles = std::max(dims.max_tiles, P.tiles);
             dims.max_m = std::max(dims.max_m, 6 * P.A.nc);
             i1++;
         }
         dims.n_probs = (int)(i1 - i0);
-        EK(launch_ba_multi_batch(C.s, D.dprob + i0, dims));
+        EK(launch_ba_multi_batch(C.s, D.a.d + i0, dims));
         i0 = i1;
     }
     SYNC_TIMED(C);
 }
 
 void process_dlt(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    DescBlock<DltProblem> D;
-    EK(desc_block(C, batch.size(), D));
+    DescBlock<DltProblem, char> D;
+    EK(desc_block(C, batch.size(), 0, D));
     int max_n = 0;
     for (size_t i = 0; i < batch.size(); i++) {
         DltReq* r = (DltReq*)batch[i];
-        D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->in_bytes, 0};
+        D.a.h[i] = r->P;
+        D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->L.in_bytes, 0};
         max_n = std::max(max_n, r->P.n);
     }
     EK(stage_in(C, D, batch.size(), 2));
-    EK(launch_tri_dlt_batch(C.s, D.dprob, (int)batch.size(), max_n));
+    EK(launch_tri_dlt_batch(C.s, D.a.d, (int)batch.size(), max_n));
     SYNC_TIMED(C);
 }
 
 void process_fp_rounds(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    DescBlock<FivePointProblem> D;
-    EK(desc_block(C, batch.size(), D));
+    DescBlock<FivePointProblem, char> D;
+    EK(desc_block(C, batch.size(), 0, D));
     int max_hyp = 0;
     for (size_t i = 0; i < batch.size(); i++) {
         FPReq* r = (FPReq*)batch[i];
-        D.hprob[i] = r->P;
-        D.hjobs[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->in_bytes, 0};
+        D.a.h[i] = r->P;
+        D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->L.in_bytes, 0};
         max_hyp = std::max(max_hyp, r->P.n_hyp);
     }
     EK(stage_in(C, D, batch.size(), 2));
-    EK(launch_fivepoint_batch(C.s, D.dprob, (int)batch.size(), max_hyp));
+    EK(launch_fivepoint_batch(C.s, D.a.d, (int)batch.size(), max_hyp));
     SYNC_TIMED(C);
 }
 
 // whole findEssentialMat and findFundamentalMat calls: ONE k_essential_ransac launch for the round's requests of the first kind, ONE
 // k_fundamental_ransac launch for those of the second, one workgroup per request, behind one k_stage_in launch for both. The descriptor block
-// is [EssentialProblem records | FundamentalProblem records | stage-in jobs]. The fundamental launch goes first: its requests take a fraction
+// is desc_block's with both kinds of records. The fundamental launch goes first: its requests take a fraction
 // of a five-point request's time and would otherwise wait on the stream behind all of them. Each workgroup signals its own caller; the sync
 // below is the fallback (a failed launch releases everyone with an error) and what makes the records reusable.
 void process_whole(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<EssReq*> ess; std::vector<FundReq*> fund;
-    for (Req* r : batch) { if (r->kind == 14) ess.push_back((EssReq*)r); else fund.push_back((FundReq*)r); }
+    for (Req* r : batch) { if (r->kind == Q_ESSENTIAL) ess.push_back((EssReq*)r); else fund.push_back((FundReq*)r); }
     const size_t ne = ess.size(), nf = fund.size();
-    const size_t off_f = (sizeof(EssentialProblem) * ne + 255) & ~(size_t)255;
-    const size_t off_jobs = (off_f + sizeof(FundamentalProblem) * nf + 255) & ~(size_t)255;
-    EK(C.h_desc.ensure(off_jobs + sizeof(StageJob) * (ne + nf + 1) + 256));
-    EK(C.d_desc.ensure(off_jobs + 256));
-    char* hd = (char*)C.h_desc.p;
-    EssentialProblem* hess = (EssentialProblem*)hd; FundamentalProblem* hfund = (FundamentalProblem*)(hd + off_f);
-    StageJob* hjobs = (StageJob*)(hd + off_jobs);
-    hjobs[0] = StageJob{C.h_desc.dev, (char*)C.d_desc.p, (unsigned)off_jobs, 0};   // job 0: the records themselves
+    DescBlock<EssentialProblem, FundamentalProblem> D;
+    EK(desc_block(C, ne, nf, D));
     for (size_t i = 0; i < ne; i++) {
-        hess[i] = ess[i]->P;
-        hjobs[1 + i] = StageJob{(const char*)ess[i]->b->h_stage.dm(), ess[i]->b->d_ess_in, (unsigned)ess[i]->in_bytes, 0};
+        D.a.h[i] = ess[i]->P;
+        D.jobs.h[i] = StageJob{(const char*)ess[i]->b->h_stage.dm(), ess[i]->b->d_ess_in, (unsigned)ess[i]->L.in_bytes, 0};
     }
     for (size_t i = 0; i < nf; i++) {
-        hfund[i] = fund[i]->P;
-        hjobs[1 + ne + i] = StageJob{(const char*)fund[i]->b->h_stage.dm(), fund[i]->b->d_fund_in, (unsigned)fund[i]->in_bytes, 0};
+        D.b.h[i] = fund[i]->P;
+        D.jobs.h[ne + i] = StageJob{(const char*)fund[i]->b->h_stage.dm(), fund[i]->b->d_fund_in, (unsigned)fund[i]->L.in_bytes, 0};
     }
-    hipLaunchKernelGGL(k_stage_in, dim3(2, (unsigned)(ne + nf + 1)), dim3(256), 0, C.s, (const StageJob*)(C.h_desc.dev + off_jobs));
-    EK(hipGetLastError());
-    EK(launch_fundamental_ransac(C.s, (const FundamentalProblem*)((char*)C.d_desc.p + off_f), (int)nf));
-    EK(launch_essential_ransac(C.s, (const EssentialProblem*)C.d_desc.p, (int)ne));
+    EK(stage_in(C, D, ne + nf, 2));
+    EK(launch_fundamental_ransac(C.s, D.b.d, (int)nf));
+    EK(launch_essential_ransac(C.s, D.a.d, (int)ne));
     if (nf) E->ctx->whole_rounds[0]++;
     if (ne) E->ctx->whole_rounds[1]++;
     if (nf && ne) E->ctx->whole_rounds[2]++;
@@ -760,15 +760,28 @@ void process_whole(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
 
 void process_fp(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<Req*> rounds, whole;   // (the forms share the class; a round that holds both serves them one after the other)
-    for (Req* r : batch) (r->kind >= 14 ? whole : rounds).push_back(r);
+    for (Req* r : batch) (r->kind >= Q_WHOLE_FIRST ? whole : rounds).push_back(r);
     if (!rounds.empty()) process_fp_rounds(E, C, rounds);
     if (!whole.empty()) process_whole(E, C, whole);
 }
 
-static inline void futex_wait_while(std::atomic<int>* w, int v) {
-    while (w->load(std::memory_order_acquire) == v) (void)syscall(SYS_futex, (int*)w, FUTEX_WAIT_PRIVATE, v, nullptr, nullptr, 0);
+// The result blocks of a lane hold cap_tracks = B * max_tracks tracks (LK, kNN) or points (sub-pixel). The B sequences of a batched run never
+// ask for more; the callers of a batch session may (any number of threads): a round takes the requests that fit, in arrival order, and the
+// rest stay at the head of the queue for the next round (one request is at most max_tracks, so a round is never empty). weight(r): what a
+// request takes of the block. Called under Q's mutex.
+template <class Weight> void take_what_fits(Queue* Q, std::vector<Req*>& batch, size_t cap, Weight weight) {
+    size_t total = 0, k = 0;
+    for (; k < batch.size(); k++) {
+        const size_t n = weight(batch[k]);
+        if (total + n > cap) break;
+        total += n;
+    }
+    if (k == batch.size()) return;
+    Q->pending.assign(batch.begin() + (long)k, batch.end());
+    batch.resize(k);
+    Q->first_arrival = std::chrono::steady_clock::now();
+    Q->cv_new.notify_all();   // (another lane of the class may take them at once)
 }
-static inline void futex_wake_one(std::atomic<int>* w) { (void)syscall(SYS_futex, (int*)w, FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0); }
 
 void combiner_loop(BatchEngine* E, int role, int lane) {
     Combiner* C = &E->comb[role][lane];
@@ -794,39 +807,8 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
                 lk.lock();
             }
             batch.swap(Q->pending);
-            if (role == R_LK) {
-                // The result blocks of a lane hold cap_tracks = B * max_tracks tracks. The B sequences of a batched run never ask for more; the
-                // callers of a batch session may (any number of threads): a round takes the requests that fit, in arrival order, and the rest
-                // stay at the head of the queue for the next round (one request is at most max_tracks, so a round is never empty).
-                size_t total = 0, k = 0;
-                for (; k < batch.size(); k++) {
-                    const size_t n = batch[k]->kind == 4 ? (size_t)((KnnReq*)batch[k])->n : (size_t)((LKReq*)batch[k])->n;
-                    if (total + n > E->cap_tracks) break;
-                    total += n;
-                }
-                if (k < batch.size()) {
-                    Q->pending.assign(batch.begin() + (long)k, batch.end());
-                    batch.resize(k);
-                    Q->first_arrival = std::chrono::steady_clock::now();
-                    Q->cv_new.notify_all();   // (another lane of the class may take them at once)
-                }
-            }
-            if (role == R_DET) {
-                // the same for the corner sub-pixel requests of the detector class: a round's result block holds cap_tracks points
-                size_t total = 0, k = 0;
-                for (; k < batch.size(); k++) {
-                    if (batch[k]->kind != 6) continue;
-                    const size_t n = (size_t)((SubpixReq*)batch[k])->n;
-                    if (total + n > E->cap_tracks) break;
-                    total += n;
-                }
-                if (k < batch.size()) {
-                    Q->pending.assign(batch.begin() + (long)k, batch.end());
-                    batch.resize(k);
-                    Q->first_arrival = std::chrono::steady_clock::now();
-                    Q->cv_new.notify_all();
-                }
-            }
+            if (role == R_LK) take_what_fits(Q, batch, E->cap_tracks, [](Req* r) { return r->kind == Q_KNN ? (size_t)((KnnReq*)r)->n : (size_t)((LKReq*)r)->n; });
+            if (role == R_DET) take_what_fits(Q, batch, E->cap_tracks, [](Req* r) { return r->kind == Q_SUBPIX ? (size_t)((SubpixReq*)r)->n : (size_t)0; });
         }
         const auto tw = std::chrono::steady_clock::now();
         C->t_idle += std::chrono::duration<double>(tw - ti).count();
@@ -845,7 +827,7 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
         C->batches++; C->requests += (long)batch.size();
         for (Req* r : batch) {
             std::atomic<int>* w = &r->done;   // (after the store the owner may return and the request, which lives on its stack, is gone)
-            const bool engine_owned = r->kind >= 14;
+            const bool engine_owned = r->kind >= Q_WHOLE_FIRST;
             w->store(1, std::memory_order_release);
             futex_wake_one(w);
             if (engine_owned) {   // the record may be filled again from here on
@@ -895,7 +877,7 @@ void batch_engine_destroy(pmv_ctx* ctx) {
             if (getenv("PMV_BATCH_TIMING") && C.batches)
                 fprintf(stderr, "[batch-timing] class %d lane %d: %ld rounds, %.1f req/round, per round: work %.0f us, sync %.0f us (first sleep %.0f us, then %.1f polls), cpu %.0f us, ema %.0f us\n",
                         (int)(&role - &E->comb[0]), (int)(&C - &role[0]), C.batches, (double)C.requests / C.batches, C.t_work / C.batches * 1e6, C.t_sync / C.batches * 1e6,
-                        C.t_first_sleep / C.batches * 1e6, (double)C.n_polls / C.batches, C.t_cpu / C.batches * 1e6, C.ema_wait_us);
+                        C.sig_diag.t_first_sleep / C.batches * 1e6, (double)C.sig_diag.n_polls / C.batches, C.t_cpu / C.batches * 1e6, C.sig.ema_us);
             if (C.s && C.owns_stream) { (void)hipStreamSynchronize(C.s); (void)hipStreamDestroy(C.s); }
             if (C.ev) (void)hipEventDestroy(C.ev);
         }
@@ -955,8 +937,7 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
             if (l < n_streams) CKC(hipStreamCreateWithPriority(&C.s, hipStreamNonBlocking, prio));
             else { C.s = E->comb[r][l % n_streams].s; C.owns_stream = false; }
             CKC(hipEventCreateWithFlags(&C.ev, hipEventBlockingSync | hipEventDisableTiming));
-            CKC(C.h_done.ensure(64));
-            *C.h_done = 0;
+            CKC(C.sig.init());
             if (r == R_LK) { CKC(C.h_out_xy.ensure(E->cap_tracks * 8)); CKC(C.h_status.ensure(E->cap_tracks)); CKC(C.h_err.ensure(E->cap_tracks * 4)); CKC(C.h_work.ensure(E->cap_tracks * 2)); }
             if (r == R_DET) CKC(C.d_flags.ensure(16));
         }
@@ -987,7 +968,7 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
     REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
     if (n == 0) return PMV_OK;
     LKReq r;
-    r.kind = 0; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = out_xy; r.status = status; r.err_out = err;
+    r.kind = Q_LK; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = out_xy; r.status = status; r.err_out = err;
     r.iters_out = iters_out;
     r.ring_round = ring_round;
     if (E->lk_lpt) {
@@ -1013,7 +994,7 @@ int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev
     REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
     if (n == 0) return PMV_OK;
     LKReq r;
-    r.kind = 5; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = next_xy; r.status = status; r.err_out = err;
+    r.kind = Q_LK_EX; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = next_xy; r.status = status; r.err_out = err;
     r.flags = (flags & (LKX_INIT | LKX_EIG)) | (fb ? LKX_FB : 0);
     r.back_xy = back_xy; r.back_status = back_status; r.back_err = back_err;
     return submit(ctx, E->queue[R_LK], &r);
@@ -1023,7 +1004,7 @@ int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_ce
                   double* out_score, int* out_count, int ring_round) {
     pmv_ctx* ctx = E->ctx;
     REQ(cells && out_xy && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "detect: bad argument");
-    if (kind == 2 && max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
+    if (kind == Q_SHITOMASI && max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
     DetReq r;
     r.kind = kind; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
     r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
@@ -1046,9 +1027,9 @@ int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cell
                           int mask_stride, int* out_xy, int* out_count) {
     pmv_ctx* ctx = E->ctx;
     if (p->block_size == 3 && !p->use_harris && !mask && !ctx->gftt_general)
-        return engine_detect(E, 1, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, nullptr, out_count);
+        return engine_detect(E, Q_GFTT, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, nullptr, out_count);
     DetReq r;
-    r.kind = 1; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
+    r.kind = Q_GFTT; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
     r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
     r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count;
     r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
@@ -1060,7 +1041,7 @@ int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_s
     pmv_ctx* ctx = E->ctx;
     if (n == 0) return PMV_OK;
     SubpixReq r;
-    r.kind = 6; r.slot = slot; r.n = n; r.xy = xy; r.iters_out = out_iters; r.flags_out = out_flags;
+    r.kind = Q_SUBPIX; r.slot = slot; r.n = n; r.xy = xy; r.iters_out = out_iters; r.flags_out = out_flags;
     r.p = *p;
     subpix_zero_zone(p, &r.p.zero_w, &r.p.zero_h);
     return submit(ctx, E->queue[R_DET], &r);
@@ -1082,7 +1063,7 @@ int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, 
         REQ(c[2] >= 1 && c[3] >= 1 && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0], PMV_ERR_INVALID, "detect (FAST): cell %d invalid", i);
     }
     DetReq r;
-    r.kind = 3; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = 0; r.max_per_cell = max_per_cell;
+    r.kind = Q_FAST; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = 0; r.max_per_cell = max_per_cell;
     r.quality = threshold; r.min_dist = nonmax ? 1 : 0;   // (the group key of process_det)
     r.out_xy = out_xy; r.out_score = nullptr; r.out_resp = out_response; r.out_count = out_count;
     r.ring_round = ring_round;
@@ -1098,7 +1079,7 @@ int engine_knn(BatchEngine* E, int src_slot, int cmp_slot, const int* src_xy, in
     REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
     if (n == 0) return PMV_OK;
     KnnReq r;
-    r.kind = 4; r.src_slot = src_slot; r.cmp_slot = cmp_slot; r.n = n; r.m = m; r.n_nn = n_neighbours; r.window = window;
+    r.kind = Q_KNN; r.src_slot = src_slot; r.cmp_slot = cmp_slot; r.n = n; r.m = m; r.n_nn = n_neighbours; r.window = window;
     r.src_xy = src_xy; r.cmp_xy = cmp_xy; r.out_best = out_best; r.err_out = out_err;
     r.ring_round = ring_round;
     return submit(ctx, E->queue[R_LK], &r);
@@ -1110,11 +1091,11 @@ int engine_pnp(BatchEngine* E, int seq, const float* obj_xyz, const float* img_x
     int rc = pnp_check(ctx, obj_xyz, img_xy, m, K, rvec, tvec, iterations, confidence, out_inliers, out_n_inliers);
     if (rc) return rc;
     PnPReq r;
-    r.kind = 10; r.b = E->slots[seq];
-    pnp_prepare(r.b, obj_xyz, img_xy, m, K, iterations, reproj_err, confidence, &r.P, &r.in_bytes);
+    r.kind = Q_PNP; r.b = E->slots[seq];
+    if ((rc = pnp_prepare(ctx, r.b, obj_xyz, img_xy, m, K, iterations, reproj_err, confidence, &r.P, &r.L))) return rc;
     rc = submit(ctx, E->queue[R_PNP], &r);
     if (rc) return rc;
-    pnp_finish(ctx, r.b, obj_xyz, img_xy, m, K, rvec, tvec, iterations, reproj_err, confidence, r.in_bytes, out_inliers, out_n_inliers);
+    pnp_finish(ctx, r.b, obj_xyz, img_xy, m, K, rvec, tvec, iterations, reproj_err, confidence, r.L, out_inliers, out_n_inliers);
     return PMV_OK;
 }
 
@@ -1128,13 +1109,13 @@ int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np
         return PMV_OK;
     }
     BAReq r;
-    r.kind = 11; r.b = E->slots[seq]; r.max_iterations = max_iterations;
-    rc = ba_prepare(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, ctx->ba_mode != 1, &r.A, &r.io_bytes);
+    r.kind = Q_BA; r.b = E->slots[seq]; r.max_iterations = max_iterations;
+    rc = ba_prepare(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, ctx->ba_mode != 1, &r.A, &r.L);
     if (rc) return rc;
     if (ctx->ba_mode == 1) r.A.out = (double*)r.b->h_stage.dm();   // k_ba_lm_batch copies [summary | cams | pts] into the request's pinned block
     rc = submit(ctx, E->queue[R_BA], &r);
     if (rc) return rc;
-    ba_finish(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, summary);
+    ba_finish(ctx, r.b, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, r.L, summary);
     return PMV_OK;
 }
 
@@ -1143,11 +1124,12 @@ int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int 
     pmv_ctx* ctx = E->ctx;
     REQ(n >= 1 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_triangulate_candidates: n=%d (1..max_tracks=%d)", n, ctx->max_tracks);
     DltReq r;
-    r.kind = 12; r.b = E->slots[seq];
-    dlt_prepare(r.b, q1, q2, n, P1x4, mask_in, &r.P, &r.in_bytes);
-    const int rc = submit(ctx, E->queue[R_DLT], &r);
+    r.kind = Q_DLT; r.b = E->slots[seq];
+    int rc = dlt_prepare(ctx, r.b, q1, q2, n, P1x4, mask_in, &r.P, &r.L);
     if (rc) return rc;
-    dlt_finish(ctx, r.b, q1, q2, n, P1x4, mask_in, r.in_bytes, out_Q, out_mask, out_good);
+    rc = submit(ctx, E->queue[R_DLT], &r);
+    if (rc) return rc;
+    dlt_finish(ctx, r.b, q1, q2, n, P1x4, mask_in, r.L, out_Q, out_mask, out_good);
     return PMV_OK;
 }
 
@@ -1155,12 +1137,12 @@ int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2
                      int* n_models, int* counts) {
     pmv_ctx* ctx = E->ctx;
     FPReq r;
-    r.kind = 13; r.b = E->slots[seq];
-    int rc = fivepoint_prepare(ctx, r.b, q1, q2, n, samples, n_hyp, thr, &r.P, &r.in_bytes);
+    r.kind = Q_FIVEPOINT; r.b = E->slots[seq];
+    int rc = fivepoint_prepare(ctx, r.b, q1, q2, n, samples, n_hyp, thr, &r.P, &r.L);
     if (rc) return rc;
     rc = submit(ctx, E->queue[R_FP], &r);
     if (rc) return rc;
-    fivepoint_finish(r.b, n_hyp, r.in_bytes, models, n_models, counts);
+    fivepoint_finish(r.b, n_hyp, r.L, models, n_models, counts);
     return PMV_OK;
 }
 
@@ -1195,13 +1177,13 @@ int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double*
     if (n < 5) { memset(mask, 0, (size_t)n); return PMV_OK; }
     EssReq& r = E->ess[(size_t)seq];
     futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
-    r.kind = 14; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
-    essential_prepare(r.b, p1_xy, p2_xy, n, K, prob, threshold, &r.P, &r.in_bytes);
+    r.kind = Q_ESSENTIAL; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
+    if (const int rc = essential_prepare(ctx, r.b, p1_xy, p2_xy, n, K, prob, threshold, &r.P, &r.L)) return rc;
     r.done.store(0, std::memory_order_relaxed);
     r.inflight.store(1, std::memory_order_release);
     enqueue(E->queue[R_FP], &r);
-    if (const int rc = wait_whole(ctx, r, essential_done_word(r.b, r.in_bytes), r.P.done_seq)) return rc;
-    essential_finish(r.b, n, r.in_bytes, E9, mask, out_found, out_samples_drawn);
+    if (const int rc = wait_whole(ctx, r, whole_done_word(r.b, r.L), r.P.done_seq)) return rc;
+    whole_finish(r.b, n, r.L, E9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 
@@ -1213,13 +1195,13 @@ int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float*
     if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
     FundReq& r = E->fund[(size_t)seq];
     futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
-    r.kind = 15; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
-    if (const int rc = fundamental_prepare(ctx, r.b, p1_xy, p2_xy, n, threshold, confidence, &r.P, &r.in_bytes)) return rc;
+    r.kind = Q_FUNDAMENTAL; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
+    if (const int rc = fundamental_prepare(ctx, r.b, p1_xy, p2_xy, n, threshold, confidence, &r.P, &r.L)) return rc;
     r.done.store(0, std::memory_order_relaxed);
     r.inflight.store(1, std::memory_order_release);
     enqueue(E->queue[R_FP], &r);
-    if (const int rc = wait_whole(ctx, r, essential_done_word(r.b, r.in_bytes), r.P.done_seq)) return rc;
-    fundamental_finish(r.b, n, r.in_bytes, F9, mask, out_found, out_samples_drawn);
+    if (const int rc = wait_whole(ctx, r, whole_done_word(r.b, r.L), r.P.done_seq)) return rc;
+    whole_finish(r.b, n, r.L, F9, mask, out_found, out_samples_drawn);
     return PMV_OK;
 }
 

@@ -27,10 +27,9 @@
 #include "batch_engine.h"
 #include "ingest_batch.h"
 #include "vo_pipeline.h"
-#include <linux/futex.h>
+#include "pmv_block.h"
+#include "pmv_wait.h"
 #include <sys/prctl.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -57,13 +56,6 @@ struct UpReq {
     std::atomic<int> done{0};        // completion word of the request: the owner sleeps on it (futex), as in batch_engine.hip
 };
 
-__global__ void k_upload_signal(unsigned* done, unsigned seq) { __threadfence_system(); __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-
-inline void futex_wait_while(std::atomic<int>* w, int v) {
-    while (w->load(std::memory_order_acquire) == v) (void)syscall(SYS_futex, (int*)w, FUTEX_WAIT_PRIVATE, v, nullptr, nullptr, 0);
-}
-inline void futex_wake_one(std::atomic<int>* w) { (void)syscall(SYS_futex, (int*)w, FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0); }
-
 }  // namespace
 
 struct BatchSession {
@@ -75,15 +67,13 @@ struct BatchSession {
     // the upload class
     std::thread th;
     hipStream_t stream = nullptr;
-    Buf<unsigned> h_done{MEM_MAPPED}; unsigned done_seq = 0;   // completion word of a round (mapped pinned)
-    double ema_wait_us = 0;
+    RoundSignal sig;                       // completion word of a round (pmv_wait.h)
+    int linger_us = 0;                     // diagnostic (PMV_BATCH_LINGER_US, as the engine's combiners): a round with fewer than n_seq requests waits that long for more
     std::mutex mu;
     std::condition_variable cv;
     std::vector<UpReq*> pending;
     bool stop = false;
-    // round tables in mapped pinned memory: [gray PyrPitchEntry x ROUND | BGR PyrPitchEntry x ROUND | all PyrListEntry x ROUND |
-    // CLAHE PyrListEntry x ROUND | ClaheRec x ROUND | remap PyrListEntry x ROUND | RemapRec x ROUND] (the last four are written only by a
-    // round with such requests)
+    // round tables in mapped pinned memory (round_tables; the last four are written only by a round with such requests)
     Buf<char> h_tab{MEM_MAPPED};
     // LUT blocks of a round's CLAHE requests (HBM): made by the first such round, grown to the largest round seen
     Buf<uint8_t> d_lut;
@@ -109,49 +99,33 @@ void fail_round(std::vector<UpReq*>& batch, const char* what, hipError_t e) {
     for (UpReq* r : batch) { r->rc = PMV_ERR_HIP; snprintf(r->err, sizeof(r->err), "pmv_batch_frame_upload: %s: %s", what, hipGetErrorString(e)); }
 }
 
-// the completion word of wait_stream (batch_engine.hip): sleep through most of the expected duration, then look every ~10 us
-hipError_t wait_round(BatchSession* S) {
-    const unsigned seq = ++S->done_seq;
-    hipLaunchKernelGGL(k_upload_signal, dim3(1), dim3(1), 0, S->stream, S->h_done.dm(), seq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto done = [&] { return __atomic_load_n(S->h_done.get(), __ATOMIC_ACQUIRE) == seq; };
-    if (!done()) {
-        const double first = 0.7 * S->ema_wait_us;
-        if (first > 25) std::this_thread::sleep_for(std::chrono::nanoseconds((long)(first * 1e3)));
-        int looks = 0;
-        while (!done()) {
-            std::this_thread::sleep_for(std::chrono::microseconds(10));
-            if ((++looks & 255) == 0) {   // a faulted launch never signals: ask the runtime now and then
-                e = hipStreamQuery(S->stream);
-                if (e != hipSuccess && e != hipErrorNotReady) return e;
-            }
-        }
-    }
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    S->ema_wait_us = S->ema_wait_us == 0 ? us : 0.8 * S->ema_wait_us + 0.2 * us;
-    e = hipStreamQuery(S->stream);   // lets the runtime retire the round's commands now
-    return e == hipErrorNotReady ? hipSuccess : e;
+// The seven tables of a round, ROUND entries each, host side and device side in step: level-0 entries of the gray and of the BGR requests, the
+// list entries of all requests, the slots and records of the CLAHE requests, the slots (sources: their scratch frames) and records of the
+// remap requests. A dry run gives the block's size.
+struct RoundTables {
+    Carved<PyrPitchEntry> gray, bgr;
+    Carved<PyrListEntry> all, clahe_slots; Carved<ClaheRec> clahe;
+    Carved<PyrListEntry> remap_slots; Carved<RemapRec> remap;
+    size_t bytes;
+};
+RoundTables round_tables(Carve c) {
+    constexpr size_t N = BatchSession::ROUND;
+    RoundTables T{c.take<PyrPitchEntry>(N), c.take<PyrPitchEntry>(N), c.take<PyrListEntry>(N), c.take<PyrListEntry>(N), c.take<ClaheRec>(N),
+                  c.take<PyrListEntry>(N), c.take<RemapRec>(N), 0};
+    T.bytes = c.bytes();
+    return T;
 }
 
 // one round: every request of `batch` (distinct slots, <= ROUND of them)
 void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
     pmv_ctx* ctx = S->ctx;
-    PyrPitchEntry* tg = (PyrPitchEntry*)S->h_tab;
-    PyrPitchEntry* tc = tg + BatchSession::ROUND;
-    PyrListEntry* ta = (PyrListEntry*)(tc + BatchSession::ROUND);
-    const PyrPitchEntry* dg = (const PyrPitchEntry*)S->h_tab.dm();
-    const PyrPitchEntry* dc = dg + BatchSession::ROUND;
-    const PyrListEntry* da = (const PyrListEntry*)(dc + BatchSession::ROUND);
-    PyrListEntry* te = ta + BatchSession::ROUND;                 // the slots of the round's CLAHE requests (in-place entries)
-    ClaheRec* tr = (ClaheRec*)(te + BatchSession::ROUND);
-    const PyrListEntry* de = da + BatchSession::ROUND;
-    const ClaheRec* dr = (const ClaheRec*)(de + BatchSession::ROUND);
-    PyrListEntry* tm = (PyrListEntry*)(tr + BatchSession::ROUND);   // the slots of the round's remap requests (sources: their scratch frames)
-    RemapRec* tq = (RemapRec*)(tm + BatchSession::ROUND);
-    const PyrListEntry* dm = (const PyrListEntry*)(dr + BatchSession::ROUND);
-    const RemapRec* dq = (const RemapRec*)(dm + BatchSession::ROUND);
+    const RoundTables T = round_tables(Carve(S->h_tab.p, S->h_tab.dev, S->h_tab.cap));
+    PyrPitchEntry* tg = T.gray.h; PyrPitchEntry* tc = T.bgr.h; PyrListEntry* ta = T.all.h;
+    PyrListEntry* te = T.clahe_slots.h; ClaheRec* tr = T.clahe.h;   // the slots of the round's CLAHE requests (in-place entries)
+    PyrListEntry* tm = T.remap_slots.h; RemapRec* tq = T.remap.h;   // the slots of the round's remap requests (sources: their scratch frames)
+    const PyrPitchEntry* dg = T.gray.d; const PyrPitchEntry* dc = T.bgr.d; const PyrListEntry* da = T.all.d;
+    const PyrListEntry* de = T.clahe_slots.d; const ClaheRec* dr = T.clahe.d;
+    const PyrListEntry* dm = T.remap_slots.d; const RemapRec* dq = T.remap.d;
     // grid and LDS of a launch from the largest geometry among ITS entries, level by level
     PyrLayout Lg{}, Lc{}, La{}, Le{}, Lm{};
     auto widen = [](PyrLayout& M, const PyrLayout& L) {
@@ -221,7 +195,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
         if ((e = launch_pyrdown_list(S->stream, ctx->d_slots, ctx->d_geom, La, l, da, na)) != hipSuccess) { fail("k_pyrdown", e); return; }
         rec.pyr_launches++;
     }
-    if ((e = wait_round(S)) != hipSuccess) { fail("waiting for the round", e); return; }
+    if ((e = S->sig.signal_and_wait<false>(S->stream, true)) != hipSuccess) { fail("waiting for the round", e); return; }
     for (UpReq* r : batch) {
         ctx->slot_layout[(size_t)r->slot] = ctx->geom[(size_t)r->geom];
         ctx->slot_state[(size_t)r->slot] = SLOT_BUILT;
@@ -238,7 +212,7 @@ void upload_round(BatchSession* S, std::vector<UpReq*>& batch) {
 void upload_loop(BatchSession* S) {
     (void)hipSetDevice(S->ctx->device);
     tl_prof = &S->ctx->prof;
-    (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);   // 1 us: the timed sleeps of wait_round
+    (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);   // 1 us: the timed sleeps of RoundSignal
     std::vector<UpReq*> carry;   // requests put off by a round: a second upload into a slot of the round, or more than ROUND requests
     for (;;) {
         std::vector<UpReq*> got;
@@ -246,6 +220,11 @@ void upload_loop(BatchSession* S) {
             std::unique_lock<std::mutex> lk(S->mu);
             if (carry.empty()) S->cv.wait(lk, [&] { return !S->pending.empty() || S->stop; });
             if (S->pending.empty() && carry.empty() && S->stop) return;
+            if (S->linger_us > 0 && (int)S->pending.size() < S->n_seq && !S->stop) {
+                lk.unlock();
+                std::this_thread::sleep_for(std::chrono::microseconds(S->linger_us));
+                lk.lock();
+            }
             got.swap(S->pending);
         }
         std::vector<UpReq*> batch, later;
@@ -342,16 +321,16 @@ int pmv_batch_open(pmv_ctx* ctx, int n_seq, const int* sizes_wh, int n_sizes) {
     BatchSession* S = new BatchSession();
     S->ctx = ctx; S->eng = eng; S->n_seq = n_seq;
     S->seq_mu.reset(new std::mutex[(size_t)n_seq]);
+    if (const char* e = getenv("PMV_BATCH_LINGER_US")) S->linger_us = atoi(e);
     hipError_t e = hipSuccess;
-    const size_t tab_bytes = (size_t)BatchSession::ROUND * (2 * sizeof(PyrPitchEntry) + 3 * sizeof(PyrListEntry) + sizeof(ClaheRec) + sizeof(RemapRec));
+    const size_t tab_bytes = round_tables(Carve()).bytes;
     S->blk_bytes = (max_fb + 255) & ~(size_t)255;
     // two blocks per sequence (frames k - 1 and k on their way), within 4 .. 64 blocks and 256 MB; an uploader without a block waits for one
     const int n_blk = (int)std::max<size_t>(2, std::min<size_t>({(size_t)64, std::max<size_t>(4, 2 * (size_t)n_seq), ((size_t)256 << 20) / S->blk_bytes}));
     if ((e = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)) == hipSuccess &&
-        (e = S->h_done.ensure(64)) == hipSuccess && (e = S->h_tab.ensure(tab_bytes)) == hipSuccess)
+        (e = S->sig.init()) == hipSuccess && (e = S->h_tab.ensure(tab_bytes)) == hipSuccess)
         e = S->h_pool.ensure((size_t)n_blk * S->blk_bytes);
     if (e != hipSuccess) { set_err(ctx, "pmv_batch_open: %s", hipGetErrorString(e)); session_free(S); return PMV_ERR_HIP; }
-    *S->h_done = 0;
     for (int i = n_blk - 1; i >= 0; i--) S->free_blk.push_back(i);
     S->th = std::thread(upload_loop, S);
     ctx->session = S;

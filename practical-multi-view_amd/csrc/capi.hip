@@ -375,8 +375,11 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
     constexpr int CH = pmv_ctx::CLAHE_CHUNK;
     constexpr size_t tab_bytes = (size_t)CH * (sizeof(ClaheRec) + sizeof(PyrLayout));
     CKC(ctx->h_clahe.ensure(tab_bytes)); CKC(ctx->d_clahe.ensure(tab_bytes)); CKC(ctx->d_clahe_lut.ensure((size_t)CH * CLAHE_LUT_MAX));
-    ClaheRec* recs = (ClaheRec*)ctx->h_clahe;
-    PyrLayout* tab = (PyrLayout*)(recs + CH);
+    Carve c(ctx->h_clahe.p, ctx->d_clahe.p, tab_bytes);   // chunk tables, pinned mirror and HBM copy: [records | the chunk's geometry table]
+    const Carved<ClaheRec> c_recs = c.take<ClaheRec>(CH);
+    const Carved<PyrLayout> c_tab = c.take<PyrLayout>(CH);
+    ClaheRec* recs = c_recs.h;
+    PyrLayout* tab = c_tab.h;
     for (int i0 = 0; i0 < n; i0 += CH) {
         const int nb = std::min(CH, n - i0);
         int n_geom = 0, max_tiles = 0, max_w = 0, max_h = 0;
@@ -393,8 +396,7 @@ int pmv_frames_clahe(pmv_ctx* ctx, int first_slot, int n, const pmv_clahe_params
             max_tiles = p->tiles_x * p->tiles_y; max_w = std::max(max_w, L.w[0]); max_h = std::max(max_h, L.h[0]);
         }
         CKC(hipMemcpyAsync(ctx->d_clahe, ctx->h_clahe, tab_bytes, hipMemcpyHostToDevice, ctx->s_front));
-        CKC(launch_clahe(ctx->s_front, ctx->d_slots, (const PyrLayout*)(ctx->d_clahe + (size_t)CH * sizeof(ClaheRec)), (const ClaheRec*)ctx->d_clahe, nb, max_tiles, max_w, max_h,
-                         ctx->d_clahe_lut));
+        CKC(launch_clahe(ctx->s_front, ctx->d_slots, c_tab.d, c_recs.d, nb, max_tiles, max_w, max_h, ctx->d_clahe_lut));
         ctx->clahe_launches[0]++;
         CKC(hipStreamSynchronize(ctx->s_front));   // (the next chunk rewrites the pinned tables)
     }
@@ -481,12 +483,12 @@ int pmv_frames_remap(pmv_ctx* ctx, int first_slot, int n, int map_id, int border
     constexpr int CH = pmv_ctx::REMAP_CHUNK;
     constexpr size_t tab_bytes = (size_t)CH * (sizeof(RemapRec) + sizeof(PyrListEntry) + sizeof(PyrLayout));
     CKC(ctx->h_remap.ensure(tab_bytes)); CKC(ctx->d_remap.ensure(tab_bytes)); CKC(ctx->d_remap_scratch.ensure((size_t)CH * remap_frame_bytes(ctx->max_w, ctx->max_h)));
-    RemapRec* recs = (RemapRec*)ctx->h_remap;
-    PyrListEntry* list = (PyrListEntry*)(recs + CH);
-    PyrLayout* tab = (PyrLayout*)(list + CH);
-    const RemapRec* d_recs = (const RemapRec*)ctx->d_remap;
-    const PyrListEntry* d_list = (const PyrListEntry*)(d_recs + CH);
-    const PyrLayout* d_tab = (const PyrLayout*)(d_list + CH);
+    Carve c(ctx->h_remap.p, ctx->d_remap.p, tab_bytes);   // chunk tables, pinned mirror and HBM copy: [records | list entries | geometry table]
+    const Carved<RemapRec> c_recs = c.take<RemapRec>(CH);
+    const Carved<PyrListEntry> c_list = c.take<PyrListEntry>(CH);
+    const Carved<PyrLayout> c_tab = c.take<PyrLayout>(CH);
+    RemapRec* recs = c_recs.h; PyrListEntry* list = c_list.h; PyrLayout* tab = c_tab.h;
+    const RemapRec* d_recs = c_recs.d; const PyrListEntry* d_list = c_list.d; const PyrLayout* d_tab = c_tab.d;
     const PyrLayout L = ctx->slot_layout[first_slot];   // (one size per call: the map's)
     const size_t fb = remap_frame_bytes(L.w[0], L.h[0]);
     tab[0] = L;
@@ -641,25 +643,28 @@ static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_s
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     const size_t nt = (size_t)ctx->max_tracks;
-    CKC(ctx->h_lkx.ensure(nt * 21 + 64));
-    const size_t off_bxy = nt * 8, off_berr = nt * 16, off_bst = nt * 20;
-    if (flags & PMV_LK_USE_INITIAL_FLOW) memcpy(ctx->h_lkx, next_xy, (size_t)n * 8);
+    // [initial flow of max_tracks tracks | their back block]
+    Carved<float> init; LkBackBlock back;
+    auto lkx_block = [&](Carve c) { init = c.take<float>(2 * nt); back = lk_back_block(c, nt); return c.bytes(); };
+    CKC(ctx->h_lkx.ensure(lkx_block(Carve()) + 64));
+    lkx_block(carve_of(ctx->h_lkx));
+    if (flags & PMV_LK_USE_INITIAL_FLOW) memcpy(init.h, next_xy, (size_t)n * 8);
     memcpy(ctx->h_prev_xy, prev_xy, (size_t)n * 8);
     const int nb = (n + 7) / 8 * 8;
     lk_xcd_order(prev_xy, n, (int*)(ctx->h_prev_xy + (size_t)2 * n));
     CKC(hipMemcpyAsync(ctx->d_prev_xy, ctx->h_prev_xy, (size_t)n * 8 + (size_t)nb * 4, hipMemcpyHostToDevice, ctx->s_front));
     const LKParams P = lk_launch_params(ctx);
     CKC(launch_lk_ex(ctx->s_front, ctx->d_slots + (size_t)prev_slot * L.slot_bytes, ctx->d_slots + (size_t)next_slot * L.slot_bytes, L, ctx->d_prev_xy,
-                     (const float*)ctx->h_lkx.dm(), (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->h_out_xy.dm(), ctx->h_status.dm(),
-                     ctx->h_err.dm(), ctx->h_work.dm(), (float*)(ctx->h_lkx.dm() + off_bxy), ctx->h_lkx.dm() + off_bst, (float*)(ctx->h_lkx.dm() + off_berr)));
+                     init.d, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->h_out_xy.dm(), ctx->h_status.dm(),
+                     ctx->h_err.dm(), ctx->h_work.dm(), back.xy.d, back.status.d, back.err.d));
     CKC(hipStreamSynchronize(ctx->s_front));
     memcpy(next_xy, ctx->h_out_xy, (size_t)n * 8);
     memcpy(out_status, ctx->h_status, (size_t)n);
     memcpy(out_err, ctx->h_err, (size_t)n * 4);
     if (fb) {
-        memcpy(back_xy, ctx->h_lkx + off_bxy, (size_t)n * 8);
-        memcpy(back_status, ctx->h_lkx + off_bst, (size_t)n);
-        memcpy(back_err, ctx->h_lkx + off_berr, (size_t)n * 4);
+        memcpy(back_xy, back.xy.h, (size_t)n * 8);
+        memcpy(back_status, back.status.h, (size_t)n);
+        memcpy(back_err, back.err.h, (size_t)n * 4);
     }
     ctx->add_lk_work(ctx->h_work, (size_t)n);
     return PMV_OK;
@@ -844,7 +849,9 @@ int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     const size_t nt = (size_t)ctx->max_tracks;
-    CKC(ctx->h_subpix.ensure(nt * 26 + 64)); CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
+    Carve spx_need, spx;
+    subpix_block(spx_need, nt);
+    CKC(ctx->h_subpix.ensure(spx_need.bytes() + 64)); CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
     int zw, zh;
     subpix_zero_zone(p, &zw, &zh);
     const int key[4] = {p->win_w, p->win_h, zw, zh};
@@ -854,17 +861,17 @@ int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix
         CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * p->win_w + 1) * (2 * p->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
         memcpy(ctx->subpix_tab_key, key, sizeof(key));
     }
-    const size_t off_xy = nt * 16, off_it = nt * 24, off_fl = nt * 25;
-    SubpixRec* rec = (SubpixRec*)ctx->h_subpix;
+    spx = carve_of(ctx->h_subpix);
+    const SubpixBlock S = subpix_block(spx, nt);   // at max_tracks points (the engine's round carves the same block at its round's points)
+    SubpixRec* rec = S.rec.h;
     for (int i = 0; i < n; i++) rec[i] = SubpixRec{xy[2 * i], xy[2 * i + 1], slot, 0};
     const SubpixArgs A{p->win_w, p->win_h, p->max_iter, p->eps * p->eps};
-    CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], (const SubpixRec*)ctx->h_subpix.dm(), n, ctx->d_subpix_tab, A, (float*)(ctx->h_subpix.dm() + off_xy),
-                             ctx->h_subpix.dm() + off_it, ctx->h_subpix.dm() + off_fl));
+    CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], S.rec.d, n, ctx->d_subpix_tab, A, S.xy.d, S.iters.d, S.flags.d));
     ctx->subpix_launches[0]++;
     CKC(hipStreamSynchronize(ctx->s_front));
-    memcpy(xy, ctx->h_subpix + off_xy, (size_t)n * 8);
-    if (out_iters) memcpy(out_iters, ctx->h_subpix + off_it, (size_t)n);
-    if (out_flags) memcpy(out_flags, ctx->h_subpix + off_fl, (size_t)n);
+    memcpy(xy, S.xy.h, (size_t)n * 8);
+    if (out_iters) memcpy(out_iters, S.iters.h, (size_t)n);
+    if (out_flags) memcpy(out_flags, S.flags.h, (size_t)n);
     return PMV_OK;
 }
 int pmv_debug_subpix_launches(pmv_ctx* ctx, long long* out3) {

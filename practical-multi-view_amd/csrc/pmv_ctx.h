@@ -3,6 +3,7 @@
 #include <atomic>
 #include "pmv_device.h"
 #include "pmv_mem.h"
+#include "pmv_block.h"
 #include "pmv_prof.h"
 #include "../../include/pmv_hip.h"
 #include <algorithm>
@@ -213,6 +214,16 @@ inline void lk_xcd_order(const float* prev_xy, int n, int* order) {
         order[(i - first) * 8 + s8] = byx[i].second;
     }
 }
+// ---- mapped pinned blocks that a launch fills and the host reads after the wait: described once, for the single call and the engine's round.
+// Each carves from the caller's cursor: a dry run (Carve()) gives the bytes to ensure(), carve_of(block) the pointers; the kernels get .d, the
+// host reads .h.
+inline Carve carve_of(const Growable& g) { return Carve(g.p, g.dev, g.cap); }
+// corner sub-pixel block of `cap` points: [point records | positions | iterations | flags]
+struct SubpixBlock { Carved<SubpixRec> rec; Carved<float> xy; Carved<uint8_t> iters, flags; };
+inline SubpixBlock subpix_block(Carve& c, size_t cap) { return {c.take<SubpixRec>(cap), c.take<float>(2 * cap), c.take<uint8_t>(cap), c.take<uint8_t>(cap)}; }
+// back results of `cap` forward-backward tracks: [positions | err | status]
+struct LkBackBlock { Carved<float> xy, err; Carved<uint8_t> status; };
+inline LkBackBlock lk_back_block(Carve& c, size_t cap) { return {c.take<float>(2 * cap), c.take<float>(cap), c.take<uint8_t>(cap)}; }
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
 }
