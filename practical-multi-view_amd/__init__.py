@@ -650,15 +650,19 @@ class Context:
         return out[: w.value * h.value].reshape(h.value, w.value).copy()
 
     # ---- BaseFeatureExtractor role ----
-    def detect_gftt(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0):
+    # Each plugin call is marshalled once, in a private method that takes the library function and the error check: the single call (pmv_*,
+    # _ck) and the session call (pmv_batch_*, _ckt: the calling thread's own error text) share it. `head`: () or (seq,) of a back-end call.
+    def _detect_gftt(self, fn, ck, slot, cells, max_per_cell, quality, min_dist):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
         n = cells.shape[0]
         cap = max_per_cell if max_per_cell > 0 else GFTT_UNLIMITED_CAP   # max_per_cell <= 0: no limit (cv::goodFeaturesToTrack)
         xy = np.zeros((n, cap, 2), np.int32)
         cnt = np.zeros(n, np.int32)
-        self._ck(self.lib.pmv_detect_gftt(self.h, slot, _p(cells, _i32p), n, max_per_cell, C.c_double(quality),
-                                          C.c_double(min_dist), _p(xy, _i32p), _p(cnt, _i32p)))
+        ck(fn(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), C.c_double(min_dist), _p(xy, _i32p), _p(cnt, _i32p)))
         return [xy[i, : cnt[i]].copy() for i in range(n)]
+
+    def detect_gftt(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0):
+        return self._detect_gftt(self.lib.pmv_detect_gftt, self._ck, slot, cells, max_per_cell, quality, min_dist)
 
     def _gftt_ex(self, fn, ck, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
@@ -727,36 +731,43 @@ class Context:
         self._ck(self.lib.pmv_debug_subpix_launches(self.h, out))
         return [int(v) for v in out]
 
-    def detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
+    def _detect_shitomasi(self, fn, ck, slot, cells, max_per_cell, quality):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
         n = cells.shape[0]
         xy = np.zeros((n, max(max_per_cell, 1), 2), np.int32)
         sc = np.zeros((n, max(max_per_cell, 1)), np.float64)
         cnt = np.zeros(n, np.int32)
-        self._ck(self.lib.pmv_detect_shitomasi(self.h, slot, _p(cells, _i32p), n, max_per_cell, C.c_double(quality),
-                                               _p(xy, _i32p), _p(sc, _f64p), _p(cnt, _i32p)))
+        ck(fn(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), _p(xy, _i32p), _p(sc, _f64p), _p(cnt, _i32p)))
         return [(xy[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(n)]
 
-    def detect_fast(self, slot, cells, max_per_cell, threshold=10, nonmax=True):
-        """cv::FAST per view (views may be as large as the frame): [(xy (k,2) int32, response (k,) float32)] per cell"""
+    def detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
+        return self._detect_shitomasi(self.lib.pmv_detect_shitomasi, self._ck, slot, cells, max_per_cell, quality)
+
+    def _detect_fast(self, fn, ck, slot, cells, max_per_cell, threshold, nonmax):
         cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
         n = cells.shape[0]
         cap = max(max_per_cell, 1)
         xy = np.zeros((n, cap, 2), np.int32)
         rs = np.zeros((n, cap), np.float32)
         cnt = np.zeros(n, np.int32)
-        self._ck(self.lib.pmv_detect_fast(self.h, slot, _p(cells, _i32p), n, max_per_cell, threshold, 1 if nonmax else 0, _p(xy, _i32p), _p(rs, _f32p),
-                                          _p(cnt, _i32p)))
+        ck(fn(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), int(threshold), 1 if nonmax else 0, _p(xy, _i32p), _p(rs, _f32p), _p(cnt, _i32p)))
         return [(xy[i, : cnt[i]].copy(), rs[i, : cnt[i]].copy()) for i in range(n)]
 
-    def knn_match(self, src_slot, cmp_slot, src_xy, cmp_xy, neighbours=7, window=15):
-        """kNNFeatureMatcher's arithmetic: (best candidate index or -1, window error) per source feature"""
+    def detect_fast(self, slot, cells, max_per_cell, threshold=10, nonmax=True):
+        """cv::FAST per view (views may be as large as the frame): [(xy (k,2) int32, response (k,) float32)] per cell"""
+        return self._detect_fast(self.lib.pmv_detect_fast, self._ck, slot, cells, max_per_cell, threshold, nonmax)
+
+    def _knn_match(self, fn, ck, src_slot, cmp_slot, src_xy, cmp_xy, neighbours, window):
         s = np.ascontiguousarray(src_xy, np.int32).reshape(-1, 2)
         c = np.ascontiguousarray(cmp_xy, np.int32).reshape(-1, 2)
         best = np.zeros(max(len(s), 1), np.int32)
         err = np.zeros(max(len(s), 1), np.float32)
-        self._ck(self.lib.pmv_knn_match(self.h, src_slot, cmp_slot, _p(s, _i32p), len(s), _p(c, _i32p), len(c), neighbours, window, _p(best, _i32p), _p(err, _f32p)))
+        ck(fn(self.h, int(src_slot), int(cmp_slot), _p(s, _i32p), len(s), _p(c, _i32p), len(c), int(neighbours), int(window), _p(best, _i32p), _p(err, _f32p)))
         return best[: len(s)].copy(), err[: len(s)].copy()
+
+    def knn_match(self, src_slot, cmp_slot, src_xy, cmp_xy, neighbours=7, window=15):
+        """kNNFeatureMatcher's arithmetic: (best candidate index or -1, window error) per source feature"""
+        return self._knn_match(self.lib.pmv_knn_match, self._ck, src_slot, cmp_slot, src_xy, cmp_xy, neighbours, window)
 
     def gftt_response(self, slot, cell):
         cell = np.ascontiguousarray(cell, np.int32)
@@ -771,15 +782,17 @@ class Context:
         return out
 
     # ---- BaseFeatureMatcher role ----
-    def lk_track(self, prev_slot, next_slot, prev_xy):
+    def _lk_track(self, fn, ck, prev_slot, next_slot, prev_xy):
         p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
         n = p.shape[0]
         out = np.zeros((n, 2), np.float32)
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32)
-        self._ck(self.lib.pmv_lk_track(self.h, prev_slot, next_slot, _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p),
-                                       _p(err, _f32p)))
+        ck(fn(self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p), _p(err, _f32p)))
         return out, st, err
+
+    def lk_track(self, prev_slot, next_slot, prev_xy):
+        return self._lk_track(self.lib.pmv_lk_track, self._ck, prev_slot, next_slot, prev_xy)
 
     def _lk_ex(self, fn, ck, fb, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals):
         p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
@@ -830,7 +843,7 @@ class Context:
         self._ck(self.lib.pmv_debug_lk_general(self.h, 1 if on else 0))
 
     # ---- BasePnPSolver role ----
-    def pnp_ransac(self, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):
+    def _pnp_ransac(self, fn, ck, head, obj_xyz, img_xy, K, rvec, tvec, iterations, reproj_err, confidence):
         o = np.ascontiguousarray(obj_xyz, np.float32).reshape(-1, 3)
         i2 = np.ascontiguousarray(img_xy, np.float32).reshape(-1, 2)
         m = o.shape[0]
@@ -839,10 +852,12 @@ class Context:
         tv = np.array(tvec, np.float64).reshape(3).copy()
         inl = np.zeros(max(m, 1), np.int32)
         nin = C.c_int()
-        self._ck(self.lib.pmv_pnp_ransac(self.h, _p(o, _f32p), _p(i2, _f32p), m, _p(Kd, _f64p), _p(rv, _f64p),
-                                         _p(tv, _f64p), iterations, C.c_float(reproj_err), C.c_double(confidence),
-                                         _p(inl, _i32p), C.byref(nin)))
+        ck(fn(self.h, *head, _p(o, _f32p), _p(i2, _f32p), m, _p(Kd, _f64p), _p(rv, _f64p), _p(tv, _f64p), int(iterations), C.c_float(reproj_err),
+              C.c_double(confidence), _p(inl, _i32p), C.byref(nin)))
         return rv, tv, inl[: nin.value].copy()
+
+    def pnp_ransac(self, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):
+        return self._pnp_ransac(self.lib.pmv_pnp_ransac, self._ck, (), obj_xyz, img_xy, K, rvec, tvec, iterations, reproj_err, confidence)
 
     def pnp_hypotheses(self, n=100):
         models = np.zeros((n, 6), np.float64)
@@ -870,7 +885,7 @@ class Context:
         """0 = multi-kernel LM chain (default), 1 = one workgroup per solve / one launch per batched round"""
         self._ck(self.lib.pmv_set_ba_mode(self.h, int(mode)))
 
-    def ba_solve(self, cams, pts, obs_xy, cam_idx, pt_idx, K, huber=1.0, max_iterations=5):
+    def _ba_solve(self, fn, ck, head, cams, pts, obs_xy, cam_idx, pt_idx, K, huber, max_iterations):
         cams = np.array(cams, np.float64).reshape(-1, 6).copy()
         pts = np.array(pts, np.float64).reshape(-1, 3).copy()
         obs = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
@@ -878,13 +893,14 @@ class Context:
         pi = np.ascontiguousarray(pt_idx, np.int32)
         Kd = np.ascontiguousarray(K, np.float64).reshape(9)
         s = BaSummary()
-        self._ck(self.lib.pmv_ba_solve(self.h, _p(cams, _f64p), cams.shape[0], _p(pts, _f64p), pts.shape[0],
-                                       _p(obs, _f64p), _p(ci, _i32p), _p(pi, _i32p), obs.shape[0], _p(Kd, _f64p),
-                                       C.c_double(huber), max_iterations, C.byref(s)))
+        ck(fn(self.h, *head, _p(cams, _f64p), cams.shape[0], _p(pts, _f64p), pts.shape[0], _p(obs, _f64p), _p(ci, _i32p), _p(pi, _i32p), obs.shape[0],
+              _p(Kd, _f64p), C.c_double(huber), int(max_iterations), C.byref(s)))
         return cams, pts, s
 
-    def fivepoint_hypotheses(self, q1, q2, samples, thr):
-        """one RANSAC round of findEssentialMat on the GPU: models (n_hyp, 10, 9), n_models (n_hyp,), counts (n_hyp, 10)"""
+    def ba_solve(self, cams, pts, obs_xy, cam_idx, pt_idx, K, huber=1.0, max_iterations=5):
+        return self._ba_solve(self.lib.pmv_ba_solve, self._ck, (), cams, pts, obs_xy, cam_idx, pt_idx, K, huber, max_iterations)
+
+    def _fivepoint_hypotheses(self, fn, ck, head, q1, q2, samples, thr):
         q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
         q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
         s = np.ascontiguousarray(samples, np.int32).reshape(-1, 5)
@@ -892,12 +908,14 @@ class Context:
         models = np.zeros((nh, 10, 9), np.float64)
         nm = np.zeros(nh, np.int32)
         counts = np.zeros((nh, 10), np.int32)
-        self._ck(self.lib.pmv_fivepoint_hypotheses(self.h, _p(q1, _f64p), _p(q2, _f64p), q1.shape[0], _p(s, _i32p), nh, C.c_float(thr), _p(models, _f64p),
-                                                   _p(nm, _i32p), _p(counts, _i32p)))
+        ck(fn(self.h, *head, _p(q1, _f64p), _p(q2, _f64p), q1.shape[0], _p(s, _i32p), nh, C.c_float(thr), _p(models, _f64p), _p(nm, _i32p), _p(counts, _i32p)))
         return models, nm, counts
 
-    def triangulate_candidates(self, q1, q2, P1x4, mask_in):
-        """DLT triangulation + cheirality of cv::recoverPose's four candidates: returns Q (4,4,n), mask (4,n), good (4,)"""
+    def fivepoint_hypotheses(self, q1, q2, samples, thr):
+        """one RANSAC round of findEssentialMat on the GPU: models (n_hyp, 10, 9), n_models (n_hyp,), counts (n_hyp, 10)"""
+        return self._fivepoint_hypotheses(self.lib.pmv_fivepoint_hypotheses, self._ck, (), q1, q2, samples, thr)
+
+    def _triangulate_candidates(self, fn, ck, head, q1, q2, P1x4, mask_in):
         q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
         q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
         n = q1.shape[0]
@@ -906,9 +924,12 @@ class Context:
         Q = np.zeros((4, 4, n), np.float64)
         mask = np.zeros((4, n), np.uint8)
         good = np.zeros(4, np.int32)
-        self._ck(self.lib.pmv_triangulate_candidates(self.h, _p(q1, _f64p), _p(q2, _f64p), n, _p(P, _f64p), _p(mi, _u8p),
-                                                     _p(Q, _f64p), _p(mask, _u8p), _p(good, _i32p)))
+        ck(fn(self.h, *head, _p(q1, _f64p), _p(q2, _f64p), n, _p(P, _f64p), _p(mi, _u8p), _p(Q, _f64p), _p(mask, _u8p), _p(good, _i32p)))
         return Q, mask, good
+
+    def triangulate_candidates(self, q1, q2, P1x4, mask_in):
+        """DLT triangulation + cheirality of cv::recoverPose's four candidates: returns Q (4,4,n), mask (4,n), good (4,)"""
+        return self._triangulate_candidates(self.lib.pmv_triangulate_candidates, self._ck, (), q1, q2, P1x4, mask_in)
 
     @staticmethod
     def _two_view_args(p1, p2, K):
@@ -1234,15 +1255,9 @@ class Context:
         self._ckt(min(self.lib.pmv_batch_upload_rounds(self.h, _p(out, _i32p), n), 0))
         return [dict(frames_by_levels=[int(v) for v in r[:5]], level0_launches=int(r[5]), pyrdown_launches=int(r[6]), in_place=int(r[7])) for r in out[:n]]
 
+    # ---- the plugin calls as session calls: the single call's marshalling (same arguments, same arrays), the thread's own error text
     def batch_detect_gftt(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0):
-        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
-        n = cells.shape[0]
-        cap = max_per_cell if max_per_cell > 0 else GFTT_UNLIMITED_CAP
-        xy = np.zeros((n, cap, 2), np.int32)
-        cnt = np.zeros(n, np.int32)
-        self._ckt(self.lib.pmv_batch_detect_gftt(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), C.c_double(min_dist),
-                                                _p(xy, _i32p), _p(cnt, _i32p)))
-        return [xy[i, : cnt[i]].copy() for i in range(n)]
+        return self._detect_gftt(self.lib.pmv_batch_detect_gftt, self._ckt, slot, cells, max_per_cell, quality, min_dist)
 
     def batch_detect_gftt_ex(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04):
         """pmv_batch_detect_gftt_ex: detect_gftt_ex as a session call (same arguments, same arrays)"""
@@ -1253,43 +1268,16 @@ class Context:
         return self._corner_subpix(self.lib.pmv_batch_corner_subpix, self._ckt, slot, xy, win, zero_zone, max_iter, eps, return_info)
 
     def batch_detect_shitomasi(self, slot, cells, max_per_cell, quality=0.4):
-        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
-        n = cells.shape[0]
-        xy = np.zeros((n, max(max_per_cell, 1), 2), np.int32)
-        sc = np.zeros((n, max(max_per_cell, 1)), np.float64)
-        cnt = np.zeros(n, np.int32)
-        self._ckt(self.lib.pmv_batch_detect_shitomasi(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), C.c_double(quality), _p(xy, _i32p),
-                                                     _p(sc, _f64p), _p(cnt, _i32p)))
-        return [(xy[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(n)]
+        return self._detect_shitomasi(self.lib.pmv_batch_detect_shitomasi, self._ckt, slot, cells, max_per_cell, quality)
 
     def batch_detect_fast(self, slot, cells, max_per_cell, threshold=10, nonmax=True):
-        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 4)
-        n = cells.shape[0]
-        cap = max(max_per_cell, 1)
-        xy = np.zeros((n, cap, 2), np.int32)
-        rs = np.zeros((n, cap), np.float32)
-        cnt = np.zeros(n, np.int32)
-        self._ckt(self.lib.pmv_batch_detect_fast(self.h, int(slot), _p(cells, _i32p), n, int(max_per_cell), int(threshold), 1 if nonmax else 0, _p(xy, _i32p),
-                                                _p(rs, _f32p), _p(cnt, _i32p)))
-        return [(xy[i, : cnt[i]].copy(), rs[i, : cnt[i]].copy()) for i in range(n)]
+        return self._detect_fast(self.lib.pmv_batch_detect_fast, self._ckt, slot, cells, max_per_cell, threshold, nonmax)
 
     def batch_knn_match(self, src_slot, cmp_slot, src_xy, cmp_xy, neighbours=7, window=15):
-        s = np.ascontiguousarray(src_xy, np.int32).reshape(-1, 2)
-        c = np.ascontiguousarray(cmp_xy, np.int32).reshape(-1, 2)
-        best = np.zeros(max(len(s), 1), np.int32)
-        err = np.zeros(max(len(s), 1), np.float32)
-        self._ckt(self.lib.pmv_batch_knn_match(self.h, int(src_slot), int(cmp_slot), _p(s, _i32p), len(s), _p(c, _i32p), len(c), int(neighbours), int(window),
-                                              _p(best, _i32p), _p(err, _f32p)))
-        return best[: len(s)].copy(), err[: len(s)].copy()
+        return self._knn_match(self.lib.pmv_batch_knn_match, self._ckt, src_slot, cmp_slot, src_xy, cmp_xy, neighbours, window)
 
     def batch_lk_track(self, prev_slot, next_slot, prev_xy):
-        p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
-        n = p.shape[0]
-        out = np.zeros((n, 2), np.float32)
-        st = np.zeros(n, np.uint8)
-        err = np.zeros(n, np.float32)
-        self._ckt(self.lib.pmv_batch_lk_track(self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(out, _f32p), _p(st, _u8p), _p(err, _f32p)))
-        return out, st, err
+        return self._lk_track(self.lib.pmv_batch_lk_track, self._ckt, prev_slot, next_slot, prev_xy)
 
     def batch_lk_track_ex(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False):
         """lk_track_ex as a session call (pmv_batch_lk_track_ex)"""
@@ -1300,54 +1288,16 @@ class Context:
         return self._lk_ex(self.lib.pmv_batch_lk_track_fb, self._ckt, True, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
 
     def batch_pnp_ransac(self, seq, obj_xyz, img_xy, K, rvec, tvec, iterations=100, reproj_err=8.0, confidence=0.99):
-        o = np.ascontiguousarray(obj_xyz, np.float32).reshape(-1, 3)
-        i2 = np.ascontiguousarray(img_xy, np.float32).reshape(-1, 2)
-        m = o.shape[0]
-        Kd = np.ascontiguousarray(K, np.float64).reshape(9)
-        rv = np.array(rvec, np.float64).reshape(3).copy()
-        tv = np.array(tvec, np.float64).reshape(3).copy()
-        inl = np.zeros(max(m, 1), np.int32)
-        nin = C.c_int()
-        self._ckt(self.lib.pmv_batch_pnp_ransac(self.h, int(seq), _p(o, _f32p), _p(i2, _f32p), m, _p(Kd, _f64p), _p(rv, _f64p), _p(tv, _f64p), int(iterations),
-                                               C.c_float(reproj_err), C.c_double(confidence), _p(inl, _i32p), C.byref(nin)))
-        return rv, tv, inl[: nin.value].copy()
+        return self._pnp_ransac(self.lib.pmv_batch_pnp_ransac, self._ckt, (int(seq),), obj_xyz, img_xy, K, rvec, tvec, iterations, reproj_err, confidence)
 
     def batch_ba_solve(self, seq, cams, pts, obs_xy, cam_idx, pt_idx, K, huber=1.0, max_iterations=5):
-        cams = np.array(cams, np.float64).reshape(-1, 6).copy()
-        pts = np.array(pts, np.float64).reshape(-1, 3).copy()
-        obs = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
-        ci = np.ascontiguousarray(cam_idx, np.int32)
-        pi = np.ascontiguousarray(pt_idx, np.int32)
-        Kd = np.ascontiguousarray(K, np.float64).reshape(9)
-        s = BaSummary()
-        self._ckt(self.lib.pmv_batch_ba_solve(self.h, int(seq), _p(cams, _f64p), cams.shape[0], _p(pts, _f64p), pts.shape[0], _p(obs, _f64p), _p(ci, _i32p),
-                                             _p(pi, _i32p), obs.shape[0], _p(Kd, _f64p), C.c_double(huber), int(max_iterations), C.byref(s)))
-        return cams, pts, s
+        return self._ba_solve(self.lib.pmv_batch_ba_solve, self._ckt, (int(seq),), cams, pts, obs_xy, cam_idx, pt_idx, K, huber, max_iterations)
 
     def batch_triangulate_candidates(self, seq, q1, q2, P1x4, mask_in):
-        q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
-        q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
-        n = q1.shape[0]
-        P = np.ascontiguousarray(P1x4, np.float64).reshape(48)
-        mi = np.ascontiguousarray(mask_in, np.uint8).reshape(n)
-        Q = np.zeros((4, 4, n), np.float64)
-        mask = np.zeros((4, n), np.uint8)
-        good = np.zeros(4, np.int32)
-        self._ckt(self.lib.pmv_batch_triangulate_candidates(self.h, int(seq), _p(q1, _f64p), _p(q2, _f64p), n, _p(P, _f64p), _p(mi, _u8p), _p(Q, _f64p),
-                                                           _p(mask, _u8p), _p(good, _i32p)))
-        return Q, mask, good
+        return self._triangulate_candidates(self.lib.pmv_batch_triangulate_candidates, self._ckt, (int(seq),), q1, q2, P1x4, mask_in)
 
     def batch_fivepoint_hypotheses(self, seq, q1, q2, samples, thr):
-        q1 = np.ascontiguousarray(q1, np.float64).reshape(-1, 2)
-        q2 = np.ascontiguousarray(q2, np.float64).reshape(-1, 2)
-        s = np.ascontiguousarray(samples, np.int32).reshape(-1, 5)
-        nh = s.shape[0]
-        models = np.zeros((nh, 10, 9), np.float64)
-        nm = np.zeros(nh, np.int32)
-        counts = np.zeros((nh, 10), np.int32)
-        self._ckt(self.lib.pmv_batch_fivepoint_hypotheses(self.h, int(seq), _p(q1, _f64p), _p(q2, _f64p), q1.shape[0], _p(s, _i32p), nh, C.c_float(thr),
-                                                         _p(models, _f64p), _p(nm, _i32p), _p(counts, _i32p)))
-        return models, nm, counts
+        return self._fivepoint_hypotheses(self.lib.pmv_batch_fivepoint_hypotheses, self._ckt, (int(seq),), q1, q2, samples, thr)
 
     def batch_find_essential_mat(self, seq, p1, p2, K, prob=0.99, threshold=1.0):
         """find_essential_mat for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""

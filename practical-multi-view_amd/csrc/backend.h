@@ -151,6 +151,8 @@ int ba_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* cams, int nc, cons
 void ba_finish(pmv_ctx* ctx, BackendBuffers* b, double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx,
                const int* pt_idx, int n_obs, const double* K, double huber_delta, int max_iterations, const BaIoLayout& L, pmv_ba_summary* summary);
 // five-point round: samples (5 n_hyp ints) of n normalised correspondences; thr = squared Sampson threshold as float
+// (the outputs of pmv_fivepoint_hypotheses are checked by fivepoint_check, everything else by fivepoint_prepare)
+int fivepoint_check(pmv_ctx* ctx, const double* models, const int* n_models, const int* counts);
 int fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
                       FivePointProblem* P, FivePointLayout* L);
 void fivepoint_finish(BackendBuffers* b, int n_hyp, const FivePointLayout& L, double* models, int* n_models, int* counts);
@@ -171,6 +173,9 @@ int fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1_xy, con
 // cv::recoverPose around a DLT launch: `dlt` is pmv_triangulate_candidates' contract on the caller's workspace set; PMV_OK or its error
 int recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
                        double* t3, uint8_t* mask, double* tri4n, int* out_good);
+// argument rules of pmv_triangulate_candidates and, under its own name, of the _ahead form (ctx is not null)
+int dlt_check(pmv_ctx* ctx, const char* who, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, const double* out_Q,
+              const uint8_t* out_mask, const int* out_good);
 int dlt_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
                 DltLayout* L);
 void dlt_finish(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,

@@ -478,6 +478,10 @@ int pmv_ba_solve(pmv_ctx* ctx, double* cams, int nc, double* pts, int np, const 
 }  // extern "C"
 
 // ---- five-point RANSAC round: prepare / finish ----------------------------------------------------------------------------------
+int pmv::fivepoint_check(pmv_ctx* ctx, const double* models, const int* n_models, const int* counts) {
+    REQ(models && n_models && counts, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
+    return PMV_OK;
+}
 int pmv::fivepoint_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr,
                            FivePointProblem* P, FivePointLayout* Lout) {
     REQ(q1 && q2 && samples && n >= 5 && n <= ctx->max_tracks && n_hyp >= 1 && n_hyp <= FP_MAX_HYP, PMV_ERR_INVALID,
@@ -509,6 +513,12 @@ void pmv::fivepoint_finish(BackendBuffers* b, int n_hyp, const FivePointLayout& 
 }
 
 // ---- two-view DLT: prepare / finish -------------------------------------------------------------------------------------------
+int pmv::dlt_check(pmv_ctx* ctx, const char* who, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, const double* out_Q,
+                   const uint8_t* out_mask, const int* out_good) {
+    REQ(q1 && q2 && P1x4 && mask_in && out_Q && out_mask && out_good, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(n >= 1 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (1..max_tracks=%d)", who, n, ctx->max_tracks);
+    return PMV_OK;
+}
 int pmv::dlt_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, DltProblem* P,
                      DltLayout* Lout) {
     const DltLayout L = dlt_layout((size_t)n);
@@ -551,7 +561,8 @@ extern "C" {
 // one round of cv::findEssentialMat's RANSAC (OpenCVFivePointTri.cpp:24) on the device: see include/pmv_hip.h
 int pmv_fivepoint_hypotheses(pmv_ctx* ctx, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
                              int* n_models, int* counts) {
-    REQ(ctx && models && n_models && counts, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
+    REQ(ctx, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
+    if (const int rc = fivepoint_check(ctx, models, n_models, counts)) return rc;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     BackendBuffers* b = ctx->be;
@@ -583,8 +594,8 @@ static int triangulate_on(pmv_ctx* ctx, BackendBuffers* b, hipStream_t s, const 
 
 int pmv_triangulate_candidates(pmv_ctx* ctx, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
                                double* out_Q, uint8_t* out_mask, int* out_good) {
-    REQ(ctx && q1 && q2 && P1x4 && mask_in && out_Q && out_mask && out_good, PMV_ERR_INVALID, "pmv_triangulate_candidates: null argument");
-    REQ(n >= 1 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_triangulate_candidates: n=%d (1..max_tracks=%d)", n, ctx->max_tracks);
+    REQ(ctx, PMV_ERR_INVALID, "pmv_triangulate_candidates: null argument");
+    if (const int rc = dlt_check(ctx, "pmv_triangulate_candidates", q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good)) return rc;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     return triangulate_on(ctx, ctx->be, ctx->s_back, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
@@ -592,8 +603,8 @@ int pmv_triangulate_candidates(pmv_ctx* ctx, const double* q1, const double* q2,
 
 int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
                                      double* out_Q, uint8_t* out_mask, int* out_good) {
-    REQ(ctx && q1 && q2 && P1x4 && mask_in && out_Q && out_mask && out_good, PMV_ERR_INVALID, "pmv_triangulate_candidates_ahead: null argument");
-    REQ(n >= 1 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_triangulate_candidates_ahead: n=%d (1..max_tracks=%d)", n, ctx->max_tracks);
+    REQ(ctx, PMV_ERR_INVALID, "pmv_triangulate_candidates_ahead: null argument");
+    if (const int rc = dlt_check(ctx, "pmv_triangulate_candidates_ahead", q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good)) return rc;
     std::lock_guard<std::mutex> lk(ctx->ahead_mu);   // one call at a time on the auxiliary lane (its callers are helper threads)
     CKC(hipSetDevice(ctx->device));
     if (!ctx->be_ahead) {

@@ -1,4 +1,5 @@
-// Batch engine interface (batch_engine.hip): request entry points used by the batched pipeline's plugin set.
+// Batch engine interface (batch_engine.hip): the request entry points behind the batched pipelines' plugin set (hip_pipeline.hip) and the
+// session calls (batch_session.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,29 +12,43 @@ void batch_engine_destroy(pmv_ctx* ctx);
 // per combiner (LK, detectors, PnP, BA, DLT): counts10 = {launch rounds, requests} x 5; times15 (may be null) = seconds spent
 // {CPU time of the combiner thread, wall time processing batches, of that waiting for the GPU} x 5
 void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
-// same contracts as pmv_lk_track / pmv_detect_* / pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates; `seq` selects the
-// sequence's back-end workspace set. Blocking; safe to call from many threads at once (one outstanding call per seq and stream role).
+// What a request asks for. Callers name Q_GFTT or Q_SHITOMASI as the `kind` of engine_detect; from Q_WHOLE_FIRST on the engine owns the
+// request record.
+enum ReqKind {
+    Q_LK = 0, Q_GFTT = 1 /* plain or, with the caller's goodFeaturesToTrack arguments, extended */, Q_SHITOMASI = 2, Q_FAST = 3,
+    Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6 /* the detector combiner */,
+    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_WHOLE_FIRST = Q_ESSENTIAL
+};
+// ---- request entry points: one per plugin call, with the contract of the single call of the same name (include/pmv_hip.h) -------------
+// Who checks what. Each entry runs the check function of its single call (pmv_ctx.h, backend.h; bracket = false) and then forms its
+// request, so the single call, the session call and the batched pipelines refuse the same arguments with the same status code and text.
+// `who` is the name the check's messages carry. A session wrapper (batch_session.hip) adds only what the session owns: that one is open,
+// the seq index and the seq's lock. The combiners look at a request's frames once more when they form a round (admit_frames): a slot may
+// have been re-used since, and the frame size must be one the batch declared.
+// Blocking; safe to call from many threads at once (one outstanding call per seq and stream role). `seq` selects the sequence's back-end
+// workspace set. ring_round: the round of the context's batch feeder (ctx->bingest) that builds the request's frames, from slot_ready;
+// -1 = none.
 // predicted_iters (optional): how many LK iterations the caller expects each track to take (0..255) - the launch starts the expensive
-// tracks first; iters_out (optional): what each track took. Neither changes a result. ring_round: the round of the context's batch feeder
-// (ctx->bingest) that builds the request's frames, from slot_ready; -1 = none.
+// tracks first; iters_out (optional): what each track took. Neither changes a result.
 int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* status, float* err,
               const uint8_t* predicted_iters = nullptr, uint8_t* iters_out = nullptr, int ring_round = -1);
-// pmv_lk_track_ex's / pmv_lk_track_fb's (fb) contract, arguments already checked: a request of the LK combiners. A round serves all its
-// extended requests with one launch of the extended batch kernels, next to the k_lk_batch launch of its plain ones; an fb request counts
-// n tracks against the round's capacity. Tracks go in the engine's default order. next_xy: in (with PMV_LK_USE_INITIAL_FLOW) and out.
-int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status, float* err, bool fb,
-                 float* back_xy, uint8_t* back_status, float* back_err);
-int engine_detect(BatchEngine* E, int kind /* 1 GFTT, 2 ShiTomasi */, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
-                  double min_dist, int* out_xy, double* out_score, int* out_count, int ring_round = -1);
-// pmv_detect_gftt_ex's contract, arguments already checked: a GFTT request that carries the caller's block size, response kind, k and optional
-// mask (host memory, read by the combiner before the call returns). The reference's arguments without a mask are a plain GFTT request unless
+// pmv_lk_track_ex's / pmv_lk_track_fb's (fb) contract: a request of the LK combiners. A round serves all its extended requests with one
+// launch of the extended batch kernels, next to the k_lk_batch launch of its plain ones; an fb request counts n tracks against the round's
+// capacity. Tracks go in the engine's default order. next_xy: in (with PMV_LK_USE_INITIAL_FLOW) and out.
+int engine_lk_ex(BatchEngine* E, const char* who, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status,
+                 float* err, bool fb, float* back_xy, uint8_t* back_status, float* back_err);
+// pmv_detect_gftt's (kind = Q_GFTT; out_score null) or pmv_detect_shitomasi's (Q_SHITOMASI) contract
+int engine_detect(BatchEngine* E, ReqKind kind, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
+                  double* out_score, int* out_count, int ring_round = -1);
+// pmv_detect_gftt_ex's contract: a GFTT request that carries the caller's block size, response kind, k and optional mask (host memory,
+// read by the combiner before the call returns). The reference's arguments without a mask are a plain GFTT request unless
 // pmv_debug_gftt_general is on.
-int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
-                          int mask_stride, int* out_xy, int* out_count);
-// pmv_corner_subpix's contract, arguments already checked (subpix_check): a request of the detector combiner. Requests of a round that agree
-// in the six parameters share one launch, whatever their slots and frame sizes.
-int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);
-// pmv_detect_fast's contract (a cell may be as large as the frame; max_per_cell <= 0: empty lists, no launch): a request of the detector combiner
+int engine_detect_gftt_ex(BatchEngine* E, const char* who, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p,
+                          const uint8_t* mask, int mask_stride, int* out_xy, int* out_count);
+// pmv_corner_subpix's contract: a request of the detector combiner. Requests of a round that agree in the six parameters share one
+// launch, whatever their slots and frame sizes.
+int engine_corner_subpix(BatchEngine* E, const char* who, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);
+// pmv_detect_fast's contract (a cell may be as large as the frame): a request of the detector combiner
 int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                        int* out_count, int ring_round = -1);
 // pmv_knn_match's contract: a request of the LK combiners (the matcher role), served by one k_knn_round launch per round; counted under LK

@@ -33,15 +33,8 @@ namespace pmv {
 
 namespace {
 
-// What a request asks for. The detector values are the `kind` argument of engine_detect (batch_engine.h); from Q_WHOLE_FIRST on the engine
-// owns the request record (WholeReq).
-enum ReqKind {
-    Q_LK = 0, Q_GFTT = 1 /* plain or, DetReq::ext, with the caller's goodFeaturesToTrack arguments */, Q_SHITOMASI = 2, Q_FAST = 3,
-    Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6 /* the detector combiner */,
-    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_WHOLE_FIRST = Q_ESSENTIAL
-};
 struct Req {
-    int kind = Q_LK;
+    int kind = Q_LK;   // a ReqKind (batch_engine.h)
     int rc = PMV_OK;
     // completion word: the owner sleeps on it (futex), the combiner stores 1 and wakes that one sleeper. No lock is involved: with a
     // condition variable under the queue's mutex the 50-70 owners of a round woke up one by one into a fight for that mutex, while the
@@ -227,6 +220,27 @@ hipError_t wait_stream(BatchEngine* E, Combiner& C) {
     return C.sig.signal_and_wait<true>(C.s, query_each_round, &C.sig_diag);
 }
 
+// Admission of a request into a round: its frame (slot_b < 0) or frame pair still holds built pyramids, a pair agrees in size, and - where
+// the launch takes the geometry from the context's table (geom given) - the size is one the batch declared. On refusal the request carries
+// rc and err, and the round goes on without it. `what` names the kernel class in the message.
+bool admit_frames(pmv_ctx* ctx, Req* r, const char* what, int slot_a, int slot_b, int* geom) {
+    const PyrLayout& a = ctx->slot_layout[slot_a];
+    r->rc = PMV_ERR_INVALID;
+    if (slot_b < 0) {
+        if (slot_ready(ctx, slot_a)) { snprintf(r->err, sizeof(r->err), "batch %s: slot %d holds no built pyramid", what, slot_a); return false; }
+    } else {
+        const PyrLayout& b = ctx->slot_layout[slot_b];
+        if (slot_ready(ctx, slot_a) || slot_ready(ctx, slot_b) || a.w[0] != b.w[0] || a.h[0] != b.h[0]) { snprintf(r->err, sizeof(r->err), "batch %s: slot has no pyramid / sizes differ", what); return false; }
+    }
+    if (geom && (*geom = ctx->geom_index(a.w[0], a.h[0])) < 0) {
+        snprintf(r->err, sizeof(r->err), "batch %s: slot %d holds a %dx%d frame, which is %s", what, slot_a, a.w[0], a.h[0],
+                 slot_b < 0 ? "no declared size of this session" : "no sequence's size in this batch");
+        return false;
+    }
+    r->rc = PMV_OK;
+    return true;
+}
+
 // ---- LK -------------------------------------------------------------------------------------------------------------------------
 // back results of a round's forward-backward tracks: lk_back_block over the lane's h_back at cap_tracks tracks
 size_t back_bytes(size_t cap) { Carve c; lk_back_block(c, cap); return c.bytes() + 64; }
@@ -243,10 +257,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     const unsigned long long pitch = ctx->cap.slot_bytes;
     int total_tracks = 0, total_blocks = 0, need_ring = -1;
     for (LKReq* r : lk) {
-        const PyrLayout& a = ctx->slot_layout[r->prev_slot];
-        const PyrLayout& b2 = ctx->slot_layout[r->next_slot];
-        if (slot_ready(ctx, r->prev_slot) || slot_ready(ctx, r->next_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
-        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->prev_slot, a.w[0], a.h[0]); continue; }
+        if (!admit_frames(ctx, r, "LK", r->prev_slot, r->next_slot, &r->geom)) continue;
         r->base = total_tracks;
         total_tracks += r->n;
         total_blocks += (int)r->order.size();
@@ -265,10 +276,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     Carve knn_need;
     knn_head(knn_need);
     for (KnnReq* r : knn) {
-        const PyrLayout& a = ctx->slot_layout[r->src_slot];
-        const PyrLayout& b2 = ctx->slot_layout[r->cmp_slot];
-        if (slot_ready(ctx, r->src_slot) || slot_ready(ctx, r->cmp_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: slot has no pyramid / sizes differ"); continue; }
-        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch kNN: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->src_slot, a.w[0], a.h[0]); continue; }
+        if (!admit_frames(ctx, r, "kNN", r->src_slot, r->cmp_slot, &r->geom)) continue;
         r->base = total_tracks + knn_tracks;
         knn_tracks += r->n;
         knn_max_n = std::max(knn_max_n, r->n);
@@ -349,10 +357,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     // indices behind the plain tracks and the matcher's in the same result blocks, the back results the same indices of the back block
     int ext_tracks = 0;
     for (LKReq* r : lkx) {
-        const PyrLayout& a = ctx->slot_layout[r->prev_slot];
-        const PyrLayout& b2 = ctx->slot_layout[r->next_slot];
-        if (slot_ready(ctx, r->prev_slot) || slot_ready(ctx, r->next_slot) || a.w[0] != b2.w[0] || a.h[0] != b2.h[0]) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot has no pyramid / sizes differ"); continue; }
-        if ((r->geom = ctx->geom_index(a.w[0], a.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch LK: slot %d holds a %dx%d frame, which is no sequence's size in this batch", r->prev_slot, a.w[0], a.h[0]); continue; }
+        if (!admit_frames(ctx, r, "LK", r->prev_slot, r->next_slot, &r->geom)) continue;
         r->base = total_tracks + knn_tracks + ext_tracks;
         ext_tracks += r->n;
     }
@@ -437,8 +442,8 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<Group> groups;
     size_t fast_pix = 0, mask_bytes = 0;
     for (DetReq* r : det) {
+        if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
         const PyrLayout& Lr = ctx->slot_layout[r->slot];
-        if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch detect: slot %d holds no built pyramid", r->slot); continue; }
         if (r->kind == Q_FAST) {
             size_t pix = 0;
             for (int i = 0; i < r->n_cells; i++) pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
@@ -477,14 +482,13 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         size_t cpos = 0, fpos = 0, mpos = 0;
         for (Group& g : groups)
             for (DetReq* r : g.reqs) {
-                if (r->mask) mpos = gftt_pack_mask((uint8_t*)C.h_gmask.p, mpos, hc + cpos * CELL_STRIDE, r->cells, r->n_cells, r->mask, r->mask_stride);
-                const bool masked = r->mask != nullptr;
-                for (int i = 0; i < r->n_cells; i++, cpos++) {
-                    int* d = hc + cpos * CELL_STRIDE;
-                    d[0] = r->cells[4 * i]; d[1] = r->cells[4 * i + 1]; d[2] = r->cells[4 * i + 2]; d[3] = r->cells[4 * i + 3]; d[4] = r->slot; d[6] = d[7] = 0;
-                    if (!masked) d[5] = 0;   // (a masked cell's int 5 = the offset of its mask bytes, written by gftt_pack_mask)
-                    if (g.kind == Q_FAST) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
-                }
+                int* recs = hc + cpos * CELL_STRIDE;
+                pack_cells(recs, r->cells, r->n_cells, r->slot);
+                // int 5 of a record: the offset of a masked cell's mask bytes, of a FAST cell's score bytes
+                if (r->mask) mpos = gftt_pack_mask((uint8_t*)C.h_gmask.p, mpos, recs, r->cells, r->n_cells, r->mask, r->mask_stride);
+                if (g.kind == Q_FAST)
+                    for (int* d = recs; d < recs + (size_t)r->n_cells * CELL_STRIDE; d += CELL_STRIDE) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
+                cpos += (size_t)r->n_cells;
             }
         if (mask_bytes) EK(hipMemcpyAsync(C.d_gmask.p, C.h_gmask.p, mask_bytes, hipMemcpyHostToDevice, s));
         if (fast_pix > 0) {
@@ -532,9 +536,7 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     std::vector<SGroup> sgroups;
     size_t spx_total = 0;
     for (SubpixReq* r : spx) {
-        const PyrLayout& Lr = ctx->slot_layout[r->slot];
-        if (slot_ready(ctx, r->slot)) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch corner subpix: slot %d holds no built pyramid", r->slot); continue; }
-        if ((r->geom = ctx->geom_index(Lr.w[0], Lr.h[0])) < 0) { r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch corner subpix: slot %d holds a %dx%d frame, which is no declared size of this session", r->slot, Lr.w[0], Lr.h[0]); continue; }
+        if (!admit_frames(ctx, r, "corner subpix", r->slot, -1, &r->geom)) continue;
         if (spx_total + (size_t)r->n > E->cap_tracks) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch corner subpix: more points than n_seq * max_tracks in a round"); continue; }
         SGroup* g = nullptr;
         for (SGroup& x : sgroups)
@@ -964,8 +966,7 @@ void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15) {
 int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* status, float* err,
               const uint8_t* predicted_iters, uint8_t* iters_out, int ring_round) {
     pmv_ctx* ctx = E->ctx;
-    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
-    REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
+    if (const int rc = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, out_xy, status, err)) return rc;
     if (n == 0) return PMV_OK;
     LKReq r;
     r.kind = Q_LK; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = out_xy; r.status = status; r.err_out = err;
@@ -987,11 +988,10 @@ int engine_lk(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy
     return submit(ctx, E->queue[R_LK], &r);
 }
 
-int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status, float* err, bool fb,
-                 float* back_xy, uint8_t* back_status, float* back_err) {
+int engine_lk_ex(BatchEngine* E, const char* who, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* status,
+                 float* err, bool fb, float* back_xy, uint8_t* back_status, float* back_err) {
     pmv_ctx* ctx = E->ctx;
-    REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_lk_track: n=%d exceeds max_tracks=%d", n, ctx->max_tracks);
-    REQ(prev_slot >= 0 && prev_slot < ctx->n_slots && next_slot >= 0 && next_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_lk_track: slot out of range");
+    if (const int rc = lkx_check(ctx, who, false, prev_slot, next_slot, prev_xy, n, next_xy, flags, status, err, fb, back_xy, back_status, back_err)) return rc;
     if (n == 0) return PMV_OK;
     LKReq r;
     r.kind = Q_LK_EX; r.prev_slot = prev_slot; r.next_slot = next_slot; r.n = n; r.prev_xy = prev_xy; r.out_xy = next_xy; r.status = status; r.err_out = err;
@@ -1000,45 +1000,45 @@ int engine_lk_ex(BatchEngine* E, int prev_slot, int next_slot, const float* prev
     return submit(ctx, E->queue[R_LK], &r);
 }
 
-int engine_detect(BatchEngine* E, int kind, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
-                  double* out_score, int* out_count, int ring_round) {
-    pmv_ctx* ctx = E->ctx;
-    REQ(cells && out_xy && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "detect: bad argument");
-    if (kind == Q_SHITOMASI && max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
-    DetReq r;
+// a GFTT or ShiTomasi request as every form of the call makes it; max_per_cell <= 0: no limit (GFTT)
+static void det_fill(DetReq& r, ReqKind kind, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
+                     double* out_score, int* out_count, int ring_round) {
     r.kind = kind; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
     r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
-    REQ(r.max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect: max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
-    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_INVALID, "detect: slot %d out of range", slot);
-    const int rc = slot_ready(ctx, slot);
-    if (rc) return rc;
-    const PyrLayout& L = ctx->slot_layout[slot];
-    for (int i = 0; i < n_cells; i++) {
-        const int* c = cells + 4 * i;
-        REQ(c[2] >= 3 && c[3] >= 3 && c[2] <= CELL_MAX && c[3] <= CELL_MAX && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0],
-            PMV_ERR_INVALID, "detect: cell %d invalid", i);
-    }
     r.quality = quality; r.min_dist = min_dist; r.out_xy = out_xy; r.out_score = out_score; r.out_count = out_count;
     r.ring_round = ring_round;
-    return submit(ctx, E->queue[R_DET], &r);
 }
 
-int engine_detect_gftt_ex(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
-                          int mask_stride, int* out_xy, int* out_count) {
+int engine_detect(BatchEngine* E, ReqKind kind, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy,
+                  double* out_score, int* out_count, int ring_round) {
     pmv_ctx* ctx = E->ctx;
-    if (p->block_size == 3 && !p->use_harris && !mask && !ctx->gftt_general)
-        return engine_detect(E, Q_GFTT, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, nullptr, out_count);
+    const bool st = kind == Q_SHITOMASI;
+    if (st && max_per_cell <= 0) return shitomasi_nothing(ctx, cells, n_cells, out_count);
+    if (const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell)) return rc;
+    REQ(out_xy && out_count && (out_score || !st), PMV_ERR_INVALID, "%s: null output", st ? "pmv_detect_shitomasi" : "pmv_detect_gftt");
     DetReq r;
-    r.kind = Q_GFTT; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = max_per_cell <= 0;
-    r.max_per_cell = r.unlimited ? MAX_PER_CELL : max_per_cell;
-    r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count;
-    r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
-    r.mask = mask; r.mask_stride = mask_stride;
+    det_fill(r, kind, slot, cells, n_cells, max_per_cell, quality, min_dist, out_xy, out_score, out_count, ring_round);
     return submit(ctx, E->queue[R_DET], &r);
 }
 
-int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
+int engine_detect_gftt_ex(BatchEngine* E, const char* who, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p,
+                          const uint8_t* mask, int mask_stride, int* out_xy, int* out_count) {
     pmv_ctx* ctx = E->ctx;
+    if (const int rc = gftt_ex_check(ctx, who, p, out_xy, out_count)) return rc;
+    if (const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell)) return rc;
+    if (const int rc = gftt_mask_check(ctx, who, slot, mask, mask_stride)) return rc;
+    DetReq r;
+    det_fill(r, Q_GFTT, slot, cells, n_cells, max_per_cell, p->quality, p->min_dist, out_xy, nullptr, out_count, -1);
+    if (p->block_size != 3 || p->use_harris || mask || ctx->gftt_general) {   // (else: a plain GFTT request)
+        r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
+        r.mask = mask; r.mask_stride = mask_stride;
+    }
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_corner_subpix(BatchEngine* E, const char* who, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
+    pmv_ctx* ctx = E->ctx;
+    if (const int rc = subpix_check(ctx, who, false, slot, xy, n, p)) return rc;
     if (n == 0) return PMV_OK;
     SubpixReq r;
     r.kind = Q_SUBPIX; r.slot = slot; r.n = n; r.xy = xy; r.iters_out = out_iters; r.flags_out = out_flags;
@@ -1050,18 +1050,9 @@ int engine_corner_subpix(BatchEngine* E, int slot, float* xy, int n, const pmv_s
 int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                        int* out_count, int ring_round) {
     pmv_ctx* ctx = E->ctx;
-    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "detect (FAST): bad argument");
-    if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }   // as pmv_detect_fast: empty lists, no launch
-    REQ(out_xy && out_response, PMV_ERR_INVALID, "detect (FAST): null output");
-    REQ(max_per_cell <= MAX_PER_CELL, PMV_ERR_CAPACITY, "detect (FAST): max_per_cell=%d (max %d)", max_per_cell, MAX_PER_CELL);
-    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_INVALID, "detect (FAST): slot %d out of range", slot);
-    const int rc = slot_ready(ctx, slot);
-    if (rc) return rc;
-    const PyrLayout& L = ctx->slot_layout[slot];
-    for (int i = 0; i < n_cells; i++) {   // a FAST "cell" may be as large as the frame
-        const int* c = cells + 4 * i;
-        REQ(c[2] >= 1 && c[3] >= 1 && c[0] >= 0 && c[1] >= 0 && c[0] + c[2] <= L.w[0] && c[1] + c[3] <= L.h[0], PMV_ERR_INVALID, "detect (FAST): cell %d invalid", i);
-    }
+    int rc = fast_counts(ctx, cells, n_cells, max_per_cell, out_count);
+    if (rc || max_per_cell <= 0) return rc;
+    if ((rc = fast_check(ctx, false, slot, cells, n_cells, max_per_cell, out_xy, out_response))) return rc;
     DetReq r;
     r.kind = Q_FAST; r.slot = slot; r.cells = cells; r.n_cells = n_cells; r.unlimited = 0; r.max_per_cell = max_per_cell;
     r.quality = threshold; r.min_dist = nonmax ? 1 : 0;   // (the group key of process_det)
@@ -1073,10 +1064,7 @@ int engine_detect_fast(BatchEngine* E, int slot, const int* cells, int n_cells, 
 int engine_knn(BatchEngine* E, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, int* out_best,
                float* out_err, int ring_round) {
     pmv_ctx* ctx = E->ctx;
-    REQ((n == 0 || (src_xy && out_best && out_err)) && (m == 0 || cmp_xy), PMV_ERR_INVALID, "pmv_knn_match: null argument");
-    REQ(n >= 0 && n <= ctx->max_tracks && m >= 0 && m <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_knn_match: n=%d / m=%d exceed max_tracks=%d", n, m, ctx->max_tracks);
-    REQ(n_neighbours >= 1 && n_neighbours <= 8 && window >= 1 && window <= 63, PMV_ERR_INVALID, "pmv_knn_match: n_neighbours 1..8, window 1..63");
-    REQ(src_slot >= 0 && src_slot < ctx->n_slots && cmp_slot >= 0 && cmp_slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_knn_match: slot out of range");
+    if (const int rc = knn_check(ctx, false, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err)) return rc;
     if (n == 0) return PMV_OK;
     KnnReq r;
     r.kind = Q_KNN; r.src_slot = src_slot; r.cmp_slot = cmp_slot; r.n = n; r.m = m; r.n_nn = n_neighbours; r.window = window;
@@ -1122,10 +1110,11 @@ int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np
 int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                uint8_t* out_mask, int* out_good) {
     pmv_ctx* ctx = E->ctx;
-    REQ(n >= 1 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "pmv_triangulate_candidates: n=%d (1..max_tracks=%d)", n, ctx->max_tracks);
+    int rc = dlt_check(ctx, "pmv_triangulate_candidates", q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+    if (rc) return rc;
     DltReq r;
     r.kind = Q_DLT; r.b = E->slots[seq];
-    int rc = dlt_prepare(ctx, r.b, q1, q2, n, P1x4, mask_in, &r.P, &r.L);
+    rc = dlt_prepare(ctx, r.b, q1, q2, n, P1x4, mask_in, &r.P, &r.L);
     if (rc) return rc;
     rc = submit(ctx, E->queue[R_DLT], &r);
     if (rc) return rc;
@@ -1136,9 +1125,11 @@ int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int 
 int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
                      int* n_models, int* counts) {
     pmv_ctx* ctx = E->ctx;
+    int rc = fivepoint_check(ctx, models, n_models, counts);
+    if (rc) return rc;
     FPReq r;
     r.kind = Q_FIVEPOINT; r.b = E->slots[seq];
-    int rc = fivepoint_prepare(ctx, r.b, q1, q2, n, samples, n_hyp, thr, &r.P, &r.L);
+    rc = fivepoint_prepare(ctx, r.b, q1, q2, n, samples, n_hyp, thr, &r.P, &r.L);
     if (rc) return rc;
     rc = submit(ctx, E->queue[R_FP], &r);
     if (rc) return rc;

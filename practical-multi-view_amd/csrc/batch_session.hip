@@ -2,8 +2,8 @@
 // OdometryPipeline behind the INTEGRATION.md adapters, a live camera loop, a Python experiment. Their frames arrive one at a time and the
 // length of a sequence is not known in advance, so nothing here is declared up front except the frame sizes (the geometry table).
 //
-//   * The nine plugin calls are the engine's request entry points (batch_engine.h) behind the argument checks of the single-sequence call of
-//     the same name: the combiners merge whatever requests have accumulated into one launch per kernel class, exactly as for the sequences
+//   * The plugin calls are the engine's request entry points (batch_engine.h), which run the argument checks of the single-sequence call of
+//     the same name; a wrapper here adds the session, the seq index and the seq's lock: the combiners merge whatever requests have accumulated into one launch per kernel class, exactly as for the sequences
 //     of pmv_pipeline_run_batch.
 //   * Uploads are one more kernel class: the UPLOAD thread (one thread, one HIP stream, one completion word) takes whatever upload requests
 //     accumulated while its previous round ran and issues the round as at most one gray and one BGR level-0 launch (pitched list forms,
@@ -459,83 +459,53 @@ int pmv_batch_frame_upload_remap(pmv_ctx* ctx, int slot, const uint8_t* pixels, 
     return session_upload(ctx, slot, pixels, w, h, stride, format, clahe_or_null, &map, map_id, border_value);
 }
 
-// ---- front-end calls: the checks of the single call, then a request of the class's combiner ------------------------------------------
+// ---- front-end calls: a request of the class's combiner; the engine entry runs the checks of the single call (batch_engine.h) ----------
 int pmv_batch_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* out_xy, uint8_t* out_status, float* out_err) {
     SESSION("pmv_batch_lk_track");
-    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err)) return rc_;
-    if (n == 0) return PMV_OK;
     return engine_lk(S->eng, prev_slot, next_slot, prev_xy, n, out_xy, out_status, out_err);
 }
 
 int pmv_batch_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err) {
     SESSION("pmv_batch_lk_track_ex");
-    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
-    if (const int rc_ = lkx_check(ctx, "pmv_batch_lk_track_ex", flags, next_xy, n, false, nullptr, nullptr, nullptr)) return rc_;
-    if (n == 0) return PMV_OK;
-    return engine_lk_ex(S->eng, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, false, nullptr, nullptr, nullptr);
+    return engine_lk_ex(S->eng, "pmv_batch_lk_track_ex", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, false, nullptr, nullptr, nullptr);
 }
 int pmv_batch_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
                           float* back_xy, uint8_t* back_status, float* back_err) {
     SESSION("pmv_batch_lk_track_fb");
-    REQ(n <= 0 || (back_xy && back_status && back_err), PMV_ERR_INVALID, "pmv_batch_lk_track_fb: null argument");
-    if (const int rc_ = lk_check(ctx, false, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
-    if (const int rc_ = lkx_check(ctx, "pmv_batch_lk_track_fb", flags, next_xy, n, true, back_xy, back_status, back_err)) return rc_;
-    if (n == 0) return PMV_OK;
-    return engine_lk_ex(S->eng, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
+    return engine_lk_ex(S->eng, "pmv_batch_lk_track_fb", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
 }
 
 int pmv_batch_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window,
                         int* out_best, float* out_err) {
     SESSION("pmv_batch_knn_match");
-    if (const int rc_ = knn_check(ctx, false, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err)) return rc_;
-    if (n == 0) return PMV_OK;
     return engine_knn(S->eng, src_slot, cmp_slot, src_xy, n, cmp_xy, m, n_neighbours, window, out_best, out_err);
 }
 
 int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, double min_dist, int* out_xy, int* out_count) {
     SESSION("pmv_batch_detect_gftt");
-    const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell);
-    if (rc) return rc;
-    REQ(out_xy && out_count, PMV_ERR_INVALID, "pmv_detect_gftt: null output");
-    return engine_detect(S->eng, 1, slot, cells, n_cells, max_per_cell, quality, min_dist, out_xy, nullptr, out_count);
+    return engine_detect(S->eng, Q_GFTT, slot, cells, n_cells, max_per_cell, quality, min_dist, out_xy, nullptr, out_count);
 }
 
 int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
                              int mask_stride, int* out_xy, int* out_count) {
     SESSION("pmv_batch_detect_gftt_ex");
-    if (const int rc = gftt_ex_check(ctx, "pmv_batch_detect_gftt_ex", p, out_xy, out_count)) return rc;
-    if (const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell <= 0 ? MAX_PER_CELL : max_per_cell)) return rc;
-    if (const int rc = gftt_mask_check(ctx, "pmv_batch_detect_gftt_ex", slot, mask, mask_stride)) return rc;
-    return engine_detect_gftt_ex(S->eng, slot, cells, n_cells, max_per_cell, p, mask, mask_stride, out_xy, out_count);
+    return engine_detect_gftt_ex(S->eng, "pmv_batch_detect_gftt_ex", slot, cells, n_cells, max_per_cell, p, mask, mask_stride, out_xy, out_count);
 }
 
 int pmv_batch_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
     SESSION("pmv_batch_corner_subpix");
-    if (const int rc = subpix_check(ctx, "pmv_batch_corner_subpix", false, slot, xy, n, p)) return rc;
-    if (n == 0) return PMV_OK;
-    return engine_corner_subpix(S->eng, slot, xy, n, p, out_iters, out_flags);
+    return engine_corner_subpix(S->eng, "pmv_batch_corner_subpix", slot, xy, n, p, out_iters, out_flags);
 }
 
 int pmv_batch_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality, int* out_xy, double* out_score,
                                int* out_count) {
     SESSION("pmv_batch_detect_shitomasi");
-    if (max_per_cell <= 0) {   // ShiTomasiFeatureExtractor.cpp:37-44: nothing
-        REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
-        for (int i = 0; i < n_cells; i++) out_count[i] = 0;
-        return PMV_OK;
-    }
-    const int rc = detect_check(ctx, false, slot, cells, n_cells, max_per_cell);
-    if (rc) return rc;
-    REQ(out_xy && out_score && out_count, PMV_ERR_INVALID, "pmv_detect_shitomasi: null output");
-    return engine_detect(S->eng, 2, slot, cells, n_cells, max_per_cell, quality, 0.0, out_xy, out_score, out_count);
+    return engine_detect(S->eng, Q_SHITOMASI, slot, cells, n_cells, max_per_cell, quality, 0.0, out_xy, out_score, out_count);
 }
 
 int pmv_batch_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                           int* out_count) {
     SESSION("pmv_batch_detect_fast");
-    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
-    if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }
-    if (const int rc = fast_check(ctx, false, slot, cells, n_cells, max_per_cell, out_xy, out_response)) return rc;
     return engine_detect_fast(S->eng, slot, cells, n_cells, max_per_cell, threshold, nonmax, out_xy, out_response, out_count);
 }
 
@@ -560,7 +530,6 @@ int pmv_batch_triangulate_candidates(pmv_ctx* ctx, int seq, const double* q1, co
                                      uint8_t* out_mask, int* out_good) {
     SESSION("pmv_batch_triangulate_candidates");
     if (const int rc = seq_check(ctx, S, "pmv_batch_triangulate_candidates", seq)) return rc;
-    REQ(q1 && q2 && P1x4 && mask_in && out_Q && out_mask && out_good, PMV_ERR_INVALID, "pmv_triangulate_candidates: null argument");
     std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
     return engine_dlt(S->eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
 }
@@ -569,7 +538,6 @@ int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, cons
                                    int* n_models, int* counts) {
     SESSION("pmv_batch_fivepoint_hypotheses");
     if (const int rc = seq_check(ctx, S, "pmv_batch_fivepoint_hypotheses", seq)) return rc;
-    REQ(models && n_models && counts, PMV_ERR_INVALID, "pmv_fivepoint_hypotheses: null argument");
     std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
     return engine_fivepoint(S->eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts);
 }

@@ -635,9 +635,7 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
 static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
                         bool fb, float* back_xy, uint8_t* back_status, float* back_err) {
     REQ(ctx, PMV_ERR_INVALID, "%s: null argument", who);
-    REQ(n <= 0 || !fb || (back_xy && back_status && back_err), PMV_ERR_INVALID, "%s: null argument", who);
-    if (const int rc_ = lk_check(ctx, true, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
-    if (const int rc_ = lkx_check(ctx, who, flags, next_xy, n, fb, back_xy, back_status, back_err)) return rc_;
+    if (const int rc_ = lkx_check(ctx, who, true, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, fb, back_xy, back_status, back_err)) return rc_;
     const PyrLayout& L = ctx->slot_layout[prev_slot];
     if (n == 0) return PMV_OK;
     tl_prof = &ctx->prof;
@@ -677,12 +675,6 @@ int pmv_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* pre
     return lk_single_ex(ctx, "pmv_lk_track_fb", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
 }
 
-static void pack_cells(int* dst, const int* cells, int n_cells, int slot) {   // (x0, y0, w, h) -> device cell records of that frame slot
-    for (int i = 0; i < n_cells; i++) {
-        int* d = dst + (size_t)i * CELL_STRIDE;
-        d[0] = cells[4 * i]; d[1] = cells[4 * i + 1]; d[2] = cells[4 * i + 2]; d[3] = cells[4 * i + 3]; d[4] = slot; d[5] = d[6] = d[7] = 0;
-    }
-}
 }  // extern "C"
 int pmv::lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* out_xy, const uint8_t* out_status, const float* out_err) {
     REQ(n == 0 || (prev_xy && out_xy && out_status && out_err), PMV_ERR_INVALID, "pmv_lk_track: null argument");
@@ -694,10 +686,12 @@ int pmv::lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, cons
     REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_lk_track: frame sizes differ");
     return PMV_OK;
 }
-int pmv::lkx_check(pmv_ctx* ctx, const char* who, int flags, const float* next_xy, int n, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err) {
+int pmv::lkx_check(pmv_ctx* ctx, const char* who, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* next_xy, int flags,
+                   const uint8_t* out_status, const float* out_err, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err) {
     static_assert(PMV_LK_USE_INITIAL_FLOW == LKX_INIT && PMV_LK_GET_MIN_EIGENVALS == LKX_EIG, "the kernels take cv's flag values as they are");
+    REQ(n <= 0 || !fb || (back_xy && back_status && back_err), PMV_ERR_INVALID, "%s: null argument", who);
+    if (const int rc_ = lk_check(ctx, bracket, prev_slot, next_slot, prev_xy, n, next_xy, out_status, out_err)) return rc_;
     REQ(!(flags & ~(PMV_LK_USE_INITIAL_FLOW | PMV_LK_GET_MIN_EIGENVALS)), PMV_ERR_INVALID, "%s: flags = 0x%x has bits other than PMV_LK_USE_INITIAL_FLOW (4) and PMV_LK_GET_MIN_EIGENVALS (8)", who, (unsigned)flags);
-    REQ(n == 0 || !fb || (back_xy && back_status && back_err), PMV_ERR_INVALID, "%s: null argument", who);
     if (flags & PMV_LK_USE_INITIAL_FLOW)
         for (int i = 0; i < 2 * n; i++)   // (a NaN fails the comparison too)
             REQ(fabsf(next_xy[i]) <= 1e6f, PMV_ERR_INVALID, "%s: initial flow of point %d (%g, %g) is not finite or beyond 1e6", who, i / 2, (double)next_xy[i & ~1], (double)next_xy[i | 1]);
@@ -729,6 +723,17 @@ int pmv::gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, 
 int pmv::gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t* mask, int mask_stride) {   // after detect_check: the slot is valid
     REQ(!mask || mask_stride >= ctx->slot_layout[slot].w[0], PMV_ERR_CAPACITY, "%s: mask_stride = %d is below the frame width %d", who, mask_stride, ctx->slot_layout[slot].w[0]);
     return PMV_OK;
+}
+int pmv::shitomasi_nothing(pmv_ctx* ctx, const int* cells, int n_cells, int* out_count) {   // ShiTomasiFeatureExtractor.cpp:37-44: `if (i >= max) break` before the first feature
+    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
+    for (int i = 0; i < n_cells; i++) out_count[i] = 0;
+    return PMV_OK;
+}
+void pmv::pack_cells(int* dst, const int* cells, int n_cells, int slot) {
+    for (int i = 0; i < n_cells; i++) {
+        int* d = dst + (size_t)i * CELL_STRIDE;
+        d[0] = cells[4 * i]; d[1] = cells[4 * i + 1]; d[2] = cells[4 * i + 2]; d[3] = cells[4 * i + 3]; d[4] = slot; d[5] = d[6] = d[7] = 0;
+    }
 }
 // the cells' mask sub-views one after the other (cw * ch bytes each); the byte offset of each goes into int 5 of its device cell record
 size_t pmv::gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* cells, int n_cells, const uint8_t* mask, int mask_stride) {
@@ -882,10 +887,9 @@ int pmv_debug_subpix_launches(pmv_ctx* ctx, long long* out3) {
 
 int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
                          int* out_xy, double* out_score, int* out_count) {
-    if (max_per_cell <= 0) {   // ShiTomasiFeatureExtractor.cpp:37-44: `if (i >= max) break` before the first feature -> nothing
-        REQ(ctx && cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
-        for (int i = 0; i < n_cells; i++) out_count[i] = 0;
-        return PMV_OK;
+    if (max_per_cell <= 0) {
+        REQ(ctx, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
+        return shitomasi_nothing(ctx, cells, n_cells, out_count);
     }
     int rc = check_cells(ctx, slot, cells, n_cells, max_per_cell);
     if (rc) return rc;

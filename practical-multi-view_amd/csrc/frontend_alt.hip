@@ -258,6 +258,11 @@ int pmv::knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const
     REQ(L.w[0] == L2.w[0] && L.h[0] == L2.h[0], PMV_ERR_INVALID, "pmv_knn_match: frame sizes differ");
     return PMV_OK;
 }
+int pmv::fast_counts(pmv_ctx* ctx, const int* cells, int n_cells, int max_per_cell, int* out_count) {
+    REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
+    if (max_per_cell <= 0) for (int i = 0; i < n_cells; i++) out_count[i] = 0;   // OpenCVFASTFeatureExtractor.cpp:12 `if (i >= max) break`
+    return PMV_OK;
+}
 int pmv::fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response) {
     REQ(out_xy && out_response, PMV_ERR_INVALID, "pmv_detect_fast: null output");
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "pmv_detect_fast: slot out of range");
@@ -309,9 +314,10 @@ int pmv_knn_match(pmv_ctx* ctx, int src_slot, int cmp_slot, const int* src_xy, i
 
 int pmv_detect_fast(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, int threshold, int nonmax, int* out_xy, float* out_response,
                     int* out_count) {
-    REQ(ctx && cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
-    if (max_per_cell <= 0) { for (int i = 0; i < n_cells; i++) out_count[i] = 0; return PMV_OK; }   // OpenCVFASTFeatureExtractor.cpp:12 `if (i >= max) break`
-    int rc = fast_check(ctx, true, slot, cells, n_cells, max_per_cell, out_xy, out_response);
+    REQ(ctx, PMV_ERR_INVALID, "pmv_detect_fast: bad argument");
+    int rc = fast_counts(ctx, cells, n_cells, max_per_cell, out_count);
+    if (rc || max_per_cell <= 0) return rc;
+    rc = fast_check(ctx, true, slot, cells, n_cells, max_per_cell, out_xy, out_response);
     if (rc) return rc;
     const PyrLayout& L = ctx->slot_layout[slot];
     size_t tot = 0;

@@ -1,5 +1,5 @@
-// HIP plugin set: the reference's five plugin roles served through the C ABI of this library, plugged into the host
-// pipeline mirror (host/vo_pipeline.*). This is the drop-in: OdometryPipeline/addFrame/estimatePose stay host C++,
+// HIP plugin set: the reference's five plugin roles served by this library - through its C ABI or, for the sequences of a batched run,
+// through the batch engine (Route) - plugged into the host pipeline mirror (host/vo_pipeline.*). This is the drop-in: OdometryPipeline/addFrame/estimatePose stay host C++,
 // every numerically heavy call crosses into the gfx950 kernels. No CPU fallback exists on this path (the triangulator,
 // which the north star does not move to the device, is the host implementation in host/vo_fivepoint.cpp).
 #include "pmv_ctx.h"
@@ -25,120 +25,8 @@ static void cells_of(const std::vector<ImageView>& cells, std::vector<int>& out)
     for (auto& c : cells) { out.push_back(c.x0); out.push_back(c.y0); out.push_back(c.w); out.push_back(c.h); }
 }
 
-struct HipGftt : GoodFeatureExtractorBase {
-    pmv_ctx* ctx;
-    std::vector<int> rect, xy, cnt;
-    void gftt(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out) override {
-        out.assign(cells.size(), {});
-        if (cells.empty()) return;
-        cells_of(cells, rect);
-        const size_t cap = max > 0 ? (size_t)max : (size_t)PMV_GFTT_UNLIMITED_CAP;   // max <= 0: no limit (cv::goodFeaturesToTrack)
-        xy.resize(cells.size() * cap * 2);
-        cnt.resize(cells.size());
-        ck(ctx, pmv_detect_gftt(ctx, cells[0].slot, rect.data(), (int)cells.size(), max, quality, min_distance, xy.data(), cnt.data()));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) out[c].push_back({xy[(c * cap + i) * 2], xy[(c * cap + i) * 2 + 1]});
-    }
-};
-struct HipShiTomasi : ShiTomasiExtractorBase {
-    pmv_ctx* ctx;
-    std::vector<int> rect, xy, cnt;
-    std::vector<double> sc;
-    void shitomasi(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
-                   std::vector<std::vector<double>>& score) override {
-        out.assign(cells.size(), {});
-        score.assign(cells.size(), {});
-        if (cells.empty() || max < 1) return;
-        cells_of(cells, rect);
-        xy.resize(cells.size() * (size_t)max * 2);
-        sc.resize(cells.size() * (size_t)max);
-        cnt.resize(cells.size());
-        ck(ctx, pmv_detect_shitomasi(ctx, cells[0].slot, rect.data(), (int)cells.size(), max, quality, xy.data(), sc.data(), cnt.data()));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) {
-                out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
-                score[c].push_back(sc[c * max + i]);
-            }
-    }
-};
-struct HipFast : FastExtractorBase {
-    pmv_ctx* ctx;
-    std::vector<int> rect, xy, cnt;
-    std::vector<float> rs;
-    void fast(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
-              std::vector<std::vector<float>>& response) override {
-        out.assign(cells.size(), {});
-        response.assign(cells.size(), {});
-        if (cells.empty() || max < 1) return;
-        cells_of(cells, rect);
-        xy.resize(cells.size() * (size_t)max * 2); rs.resize(cells.size() * (size_t)max); cnt.resize(cells.size());
-        ck(ctx, pmv_detect_fast(ctx, cells[0].slot, rect.data(), (int)cells.size(), max, threshold, nonmax ? 1 : 0, xy.data(), rs.data(), cnt.data()));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) {
-                out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
-                response[c].push_back(rs[c * max + i]);
-            }
-    }
-};
-struct HipKnn : KnnFeatureMatcherBase {
-    pmv_ctx* ctx;
-    void knn(const ImageView& src, const ImageView& next, const int* src_xy, int n, const int* cmp_xy, int m, int* best, float* err) override {
-        ck(ctx, pmv_knn_match(ctx, src.slot, next.slot, src_xy, n, cmp_xy, m, neighbours, window, best, err));
-    }
-};
-struct HipLK : LucasKanadeFMBase {
-    pmv_ctx* ctx;
-    void pyrlk(const ImageView& prev, const ImageView& next, const float* prev_xy, int n, float* next_xy, uint8_t* status,
-               float* err) override {
-        ck(ctx, pmv_lk_track(ctx, prev.slot, next.slot, prev_xy, n, next_xy, status, err));
-    }
-};
-struct HipPnP : EPnPSolverBase {
-    pmv_ctx* ctx;
-    bool pnp_ransac(const float* obj, const float* img, int m, const double* K, double* rvec, double* tvec,
-                    std::vector<int>& inliers) override {
-        inliers.assign(m > 0 ? m : 1, 0);
-        int n = 0;
-        const int rc = pmv_pnp_ransac(ctx, obj, img, m, K, rvec, tvec, 100, 8.f, .99, inliers.data(), &n);
-        if (rc == PMV_ERR_DEGENERATE) { inliers.clear(); return false; }   // cv::Exception in the reference
-        ck(ctx, rc);
-        inliers.resize(n);
-        return n > 0;
-    }
-};
-struct HipTri : vo::FivePointTri {   // five-point RANSAC on host threads (default), its hypotheses round by round or the whole loop on the GPU; recoverPose's DLT + cheirality on the GPU
-    pmv_ctx* ctx;
-    bool essential_hypotheses(const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models, int* n_models,
-                              int* counts) override {
-        ck(ctx, pmv_fivepoint_hypotheses(ctx, q1, q2, n, samples, n_hyp, thr, models, n_models, counts));
-        return true;
-    }
-    bool essential_whole(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E, uint8_t* mask, bool* found,
-                         int* samples_drawn) override {
-        int f = 0;
-        ck(ctx, pmv_find_essential_mat(ctx, p1, p2, n, K, prob, threshold, E, mask, &f, samples_drawn));
-        *found = f != 0;
-        return true;
-    }
-    void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
-                        uint8_t* out_mask, int* out_good) override {
-        ck(ctx, pmv_triangulate_candidates(ctx, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
-    }
-    void dlt_candidates_ahead(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
-                              uint8_t* out_mask, int* out_good) override {
-        ck(ctx, pmv_triangulate_candidates_ahead(ctx, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
-    }
-};
-struct HipBA : BundleAdjustmentBase {
-    pmv_ctx* ctx;
-    void ba_solve(double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
-                  const double* K, double huber, int max_iterations) override {
-        ck(ctx, pmv_ba_solve(ctx, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, nullptr));
-    }
-};
-// ---- the same five roles served through the batch engine (several sequences per launch, batch_engine.hip) --------------------
-// The frames a request reads: slot_ready on the sequence's own thread (for a fed sequence it waits until the feeder has enqueued their
-// build); the request carries the feed round the combiner's stream must wait for.
+// The frames a request of the batch engine reads: slot_ready on the sequence's own thread (for a fed sequence it waits until the feeder has
+// enqueued their build); the request carries the feed round the combiner's stream must wait for.
 struct RingFrames {
     pmv::BatchIngest* feed = nullptr; int seq = -1;   // seq: the sequence's index in the feed, -1 = not fed (it may still read fed slots)
     int round(pmv_ctx* ctx, int slot_a, int slot_b = -1) {
@@ -148,24 +36,83 @@ struct RingFrames {
         return std::max(ra, rb);
     }
 };
-struct BatchGftt : GoodFeatureExtractorBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+// How a plugin call travels: as the single call of the C ABI (eng null: pmv_pipeline_run), or as a request of the batch engine
+// (batch_engine.hip: several sequences per launch) for sequence `seq` of a batched run, whose frames `ring` waits for. Each member has
+// the contract of the pmv_* call it names and returns its status.
+struct Route {
+    pmv_ctx* ctx = nullptr; pmv::BatchEngine* eng = nullptr; RingFrames ring; int seq = 0;
+    int gftt(int slot, const int* cells, int n_cells, int max, double quality, double min_dist, int* xy, int* cnt) {
+        return eng ? pmv::engine_detect(eng, pmv::Q_GFTT, slot, cells, n_cells, max, quality, min_dist, xy, nullptr, cnt, ring.round(ctx, slot))
+                   : pmv_detect_gftt(ctx, slot, cells, n_cells, max, quality, min_dist, xy, cnt);
+    }
+    int shitomasi(int slot, const int* cells, int n_cells, int max, double quality, int* xy, double* score, int* cnt) {
+        return eng ? pmv::engine_detect(eng, pmv::Q_SHITOMASI, slot, cells, n_cells, max, quality, 0.0, xy, score, cnt, ring.round(ctx, slot))
+                   : pmv_detect_shitomasi(ctx, slot, cells, n_cells, max, quality, xy, score, cnt);
+    }
+    int fast(int slot, const int* cells, int n_cells, int max, int threshold, int nonmax, int* xy, float* response, int* cnt) {
+        return eng ? pmv::engine_detect_fast(eng, slot, cells, n_cells, max, threshold, nonmax, xy, response, cnt, ring.round(ctx, slot))
+                   : pmv_detect_fast(ctx, slot, cells, n_cells, max, threshold, nonmax, xy, response, cnt);
+    }
+    int knn(int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int neighbours, int window, int* best, float* err) {
+        return eng ? pmv::engine_knn(eng, src_slot, cmp_slot, src_xy, n, cmp_xy, m, neighbours, window, best, err, ring.round(ctx, src_slot, cmp_slot))
+                   : pmv_knn_match(ctx, src_slot, cmp_slot, src_xy, n, cmp_xy, m, neighbours, window, best, err);
+    }
+    // predicted, iters: the engine's ordering hint (batch_engine.h); the single call deals its tracks by position alone
+    int lk(int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, uint8_t* status, float* err, const uint8_t* predicted, uint8_t* iters) {
+        return eng ? pmv::engine_lk(eng, prev_slot, next_slot, prev_xy, n, next_xy, status, err, predicted, iters, ring.round(ctx, prev_slot, next_slot))
+                   : pmv_lk_track(ctx, prev_slot, next_slot, prev_xy, n, next_xy, status, err);
+    }
+    int pnp(const float* obj, const float* img, int m, const double* K, double* rvec, double* tvec, int iterations, float reproj_err, double confidence,
+            int* inliers, int* n_inliers) {
+        return eng ? pmv::engine_pnp(eng, seq, obj, img, m, K, rvec, tvec, iterations, reproj_err, confidence, inliers, n_inliers)
+                   : pmv_pnp_ransac(ctx, obj, img, m, K, rvec, tvec, iterations, reproj_err, confidence, inliers, n_inliers);
+    }
+    int ba(double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, const double* K, double huber,
+           int max_iterations) {
+        return eng ? pmv::engine_ba(eng, seq, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations)
+                   : pmv_ba_solve(ctx, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations, nullptr);
+    }
+    int dlt(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q, uint8_t* out_mask, int* out_good) {
+        return eng ? pmv::engine_dlt(eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good)
+                   : pmv_triangulate_candidates(ctx, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
+    }
+    int fivepoint(const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models, int* n_models, int* counts) {
+        return eng ? pmv::engine_fivepoint(eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts)
+                   : pmv_fivepoint_hypotheses(ctx, q1, q2, n, samples, n_hyp, thr, models, n_models, counts);
+    }
+    int essential(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E, uint8_t* mask, int* found, int* samples_drawn) {
+        return eng ? pmv::engine_essential(eng, seq, p1, p2, n, K, prob, threshold, E, mask, found, samples_drawn)
+                   : pmv_find_essential_mat(ctx, p1, p2, n, K, prob, threshold, E, mask, found, samples_drawn);
+    }
+};
+
+// per-cell lists of a detector call: `per` entries per cell, cnt[c] of them filled; val (with vals) runs beside xy
+template <class T>
+static void lists_of(size_t n_cells, size_t per, const std::vector<int>& xy, const std::vector<int>& cnt, std::vector<std::vector<std::pair<int, int>>>& out,
+                     const std::vector<T>* val = nullptr, std::vector<std::vector<T>>* vals = nullptr) {
+    for (size_t c = 0; c < n_cells; c++)
+        for (int i = 0; i < cnt[c]; i++) {
+            out[c].push_back({xy[(c * per + i) * 2], xy[(c * per + i) * 2 + 1]});
+            if (vals) (*vals)[c].push_back((*val)[c * per + i]);
+        }
+}
+
+struct HipGftt : GoodFeatureExtractorBase {
+    Route via;
     std::vector<int> rect, xy, cnt;
     void gftt(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out) override {
         out.assign(cells.size(), {});
         if (cells.empty()) return;
         cells_of(cells, rect);
-        const size_t cap = max > 0 ? (size_t)max : (size_t)PMV_GFTT_UNLIMITED_CAP;
+        const size_t cap = max > 0 ? (size_t)max : (size_t)PMV_GFTT_UNLIMITED_CAP;   // max <= 0: no limit (cv::goodFeaturesToTrack)
         xy.resize(cells.size() * cap * 2);
         cnt.resize(cells.size());
-        const int rr = ring.round(ctx, cells[0].slot);
-        ck(ctx, pmv::engine_detect(eng, 1, cells[0].slot, rect.data(), (int)cells.size(), max, quality, min_distance, xy.data(), nullptr, cnt.data(), rr));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) out[c].push_back({xy[(c * cap + i) * 2], xy[(c * cap + i) * 2 + 1]});
+        ck(via.ctx, via.gftt(cells[0].slot, rect.data(), (int)cells.size(), max, quality, min_distance, xy.data(), cnt.data()));
+        lists_of<int>(cells.size(), cap, xy, cnt, out);
     }
 };
-struct BatchShiTomasi : ShiTomasiExtractorBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+struct HipShiTomasi : ShiTomasiExtractorBase {
+    Route via;
     std::vector<int> rect, xy, cnt;
     std::vector<double> sc;
     void shitomasi(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
@@ -177,17 +124,12 @@ struct BatchShiTomasi : ShiTomasiExtractorBase {
         xy.resize(cells.size() * (size_t)max * 2);
         sc.resize(cells.size() * (size_t)max);
         cnt.resize(cells.size());
-        const int rr = ring.round(ctx, cells[0].slot);
-        ck(ctx, pmv::engine_detect(eng, 2, cells[0].slot, rect.data(), (int)cells.size(), max, quality, 0.0, xy.data(), sc.data(), cnt.data(), rr));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) {
-                out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
-                score[c].push_back(sc[c * max + i]);
-            }
+        ck(via.ctx, via.shitomasi(cells[0].slot, rect.data(), (int)cells.size(), max, quality, xy.data(), sc.data(), cnt.data()));
+        lists_of(cells.size(), (size_t)max, xy, cnt, out, &sc, &score);
     }
 };
-struct BatchFast : FastExtractorBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+struct HipFast : FastExtractorBase {
+    Route via;
     std::vector<int> rect, xy, cnt;
     std::vector<float> rs;
     void fast(const std::vector<ImageView>& cells, int max, std::vector<std::vector<std::pair<int, int>>>& out,
@@ -197,27 +139,21 @@ struct BatchFast : FastExtractorBase {
         if (cells.empty() || max < 1) return;
         cells_of(cells, rect);
         xy.resize(cells.size() * (size_t)max * 2); rs.resize(cells.size() * (size_t)max); cnt.resize(cells.size());
-        const int rr = ring.round(ctx, cells[0].slot);
-        ck(ctx, pmv::engine_detect_fast(eng, cells[0].slot, rect.data(), (int)cells.size(), max, threshold, nonmax ? 1 : 0, xy.data(), rs.data(), cnt.data(), rr));
-        for (size_t c = 0; c < cells.size(); c++)
-            for (int i = 0; i < cnt[c]; i++) {
-                out[c].push_back({xy[(c * max + i) * 2], xy[(c * max + i) * 2 + 1]});
-                response[c].push_back(rs[c * max + i]);
-            }
+        ck(via.ctx, via.fast(cells[0].slot, rect.data(), (int)cells.size(), max, threshold, nonmax ? 1 : 0, xy.data(), rs.data(), cnt.data()));
+        lists_of(cells.size(), (size_t)max, xy, cnt, out, &rs, &response);
     }
 };
-struct BatchKnn : KnnFeatureMatcherBase {   // (`extractor` = the sequence's BatchFast: matchFeatures calls it on the whole next frame)
-    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
+struct HipKnn : KnnFeatureMatcherBase {   // (`extractor` = the sequence's HipFast: matchFeatures calls it on the whole next frame)
+    Route via;
     void knn(const ImageView& src, const ImageView& next, const int* src_xy, int n, const int* cmp_xy, int m, int* best, float* err) override {
-        const int rr = ring.round(ctx, src.slot, next.slot);
-        ck(ctx, pmv::engine_knn(eng, src.slot, next.slot, src_xy, n, cmp_xy, m, neighbours, window, best, err, rr));
+        ck(via.ctx, via.knn(src.slot, next.slot, src_xy, n, cmp_xy, m, neighbours, window, best, err));
     }
 };
-struct BatchLK : LucasKanadeFMBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; RingFrames ring;
-    // Ordering hint for the batched launch (no effect on any result): a track that needed many LK iterations in the last frame pair tends
-    // to need many again (weak texture, an edge along the motion), and a launch ends with its slowest track - so the engine starts the
-    // expensive ones first. The cost of a track is remembered under the integer pixel it was tracked TO, which is where the next call
+struct HipLK : LucasKanadeFMBase {
+    Route via;
+    // Ordering hint for the batched launch (engine route only; no effect on any result): a track that needed many LK iterations in the last
+    // frame pair tends to need many again (weak texture, an edge along the motion), and a launch ends with its slowest track - so the engine
+    // starts the expensive ones first. The cost of a track is remembered under the integer pixel it was tracked TO, which is where the next call
     // starts it from (the adapter truncates exactly like this: OpenCVLucasKanadeFM.cpp:25); re-detected features are new: default cost.
     static constexpr int TBL = 2048, DEFAULT_COST = 24;   // open addressing, > 2 x the tracks of a frame (1024 max)
     std::vector<uint32_t> tkey = std::vector<uint32_t>(TBL, 0xffffffffu);
@@ -227,6 +163,7 @@ struct BatchLK : LucasKanadeFMBase {
     static uint32_t slot_of(uint32_t k) { return (k * 2654435761u) >> 21; }   // 11 bits
     void pyrlk(const ImageView& prev, const ImageView& next, const float* prev_xy, int n, float* next_xy, uint8_t* status,
                float* err) override {
+        if (!via.eng) { ck(via.ctx, via.lk(prev.slot, next.slot, prev_xy, n, next_xy, status, err, nullptr, nullptr)); return; }
         pred.resize((size_t)n); iters.resize((size_t)n);
         const bool use = n <= TBL / 2;
         for (int i = 0; i < n; i++) {
@@ -240,8 +177,7 @@ struct BatchLK : LucasKanadeFMBase {
             }
             pred[(size_t)i] = c;
         }
-        const int rr = ring.round(ctx, prev.slot, next.slot);
-        ck(ctx, pmv::engine_lk(eng, prev.slot, next.slot, prev_xy, n, next_xy, status, err, pred.data(), iters.data(), rr));
+        ck(via.ctx, via.lk(prev.slot, next.slot, prev_xy, n, next_xy, status, err, pred.data(), iters.data()));
         std::fill(tkey.begin(), tkey.end(), 0xffffffffu);
         if (!use) return;
         for (int i = 0; i < n; i++) {
@@ -254,45 +190,83 @@ struct BatchLK : LucasKanadeFMBase {
         }
     }
 };
-struct BatchPnP : EPnPSolverBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; int seq;
+struct HipPnP : EPnPSolverBase {
+    Route via;
     bool pnp_ransac(const float* obj, const float* img, int m, const double* K, double* rvec, double* tvec,
                     std::vector<int>& inliers) override {
         inliers.assign(m > 0 ? m : 1, 0);
         int n = 0;
-        const int rc = pmv::engine_pnp(eng, seq, obj, img, m, K, rvec, tvec, 100, 8.f, .99, inliers.data(), &n);
-        if (rc == PMV_ERR_DEGENERATE) { inliers.clear(); return false; }
-        ck(ctx, rc);
+        const int rc = via.pnp(obj, img, m, K, rvec, tvec, 100, 8.f, .99, inliers.data(), &n);
+        if (rc == PMV_ERR_DEGENERATE) { inliers.clear(); return false; }   // cv::Exception in the reference
+        ck(via.ctx, rc);
         inliers.resize(n);
         return n > 0;
     }
 };
-struct BatchTri : vo::FivePointTri {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; int seq;
+struct HipTri : vo::FivePointTri {   // five-point RANSAC on host threads (default), its hypotheses round by round or the whole loop on the GPU; recoverPose's DLT + cheirality on the GPU
+    Route via;
     bool essential_hypotheses(const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models, int* n_models,
                               int* counts) override {
-        ck(ctx, pmv::engine_fivepoint(eng, seq, q1, q2, n, samples, n_hyp, thr, models, n_models, counts));
+        ck(via.ctx, via.fivepoint(q1, q2, n, samples, n_hyp, thr, models, n_models, counts));
         return true;
     }
     bool essential_whole(const double* p1, const double* p2, int n, const double* K, double prob, double threshold, double* E, uint8_t* mask, bool* found,
                          int* samples_drawn) override {
         int f = 0;
-        ck(ctx, pmv::engine_essential(eng, seq, p1, p2, n, K, prob, threshold, E, mask, &f, samples_drawn));
+        ck(via.ctx, via.essential(p1, p2, n, K, prob, threshold, E, mask, &f, samples_drawn));
         *found = f != 0;
         return true;
     }
     void dlt_candidates(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                         uint8_t* out_mask, int* out_good) override {
-        ck(ctx, pmv::engine_dlt(eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
+        ck(via.ctx, via.dlt(q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
+    }
+    // (single route only: the context's auxiliary lane. A sequence of a batched run has no prefetch helpers.)
+    void dlt_candidates_ahead(const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
+                              uint8_t* out_mask, int* out_good) override {
+        if (via.eng) { FivePointTri::dlt_candidates_ahead(q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good); return; }
+        ck(via.ctx, pmv_triangulate_candidates_ahead(via.ctx, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good));
     }
 };
-struct BatchBA : BundleAdjustmentBase {
-    pmv_ctx* ctx; pmv::BatchEngine* eng; int seq;
+struct HipBA : BundleAdjustmentBase {
+    Route via;
     void ba_solve(double* cams, int nc, double* pts, int np, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
                   const double* K, double huber, int max_iterations) override {
-        ck(ctx, pmv::engine_ba(eng, seq, cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations));
+        ck(via.ctx, via.ba(cams, nc, pts, np, obs_xy, cam_idx, pt_idx, n_obs, K, huber, max_iterations));
     }
 };
+
+vo::PipelineParams params_of(const pmv_pipeline_params* P, int n_threads) {
+    vo::PipelineParams vp;
+    vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
+    vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
+    vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
+    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = n_threads; vp.reserved = 0; vp.matcher = P->matcher;
+    return vp;
+}
+
+// The five plugins of a run, all travelling `via`, wired into run.pipe (after pipeline_setup). tri_workers: threads of the host five-point
+// RANSAC; the two-thread single pipeline also gets its prefetch helpers.
+void plug_in(vo::PipelineRun& run, const pmv_pipeline_params* P, const Route& via, int tri_workers) {
+    vo::BaseFeatureExtractor* ex;
+    if (P->extractor == 1) { auto* e = new HipShiTomasi(); e->via = via; ex = e; }
+    else if (P->extractor == 2) { auto* e = new HipFast(); e->via = via; ex = e; }
+    else { auto* e = new HipGftt(); e->via = via; ex = e; }
+    run.owned_ex.push_back(ex);
+    vo::BaseFeatureMatcher* lk;
+    if (P->matcher == 1) {   // kNNFeatureMatcher(extractor): the reference's alternative matcher; it calls the extractor on whole frames
+        if (P->extractor != 2) throw std::runtime_error("the kNN matcher needs an extractor that accepts whole frames: extractor = 2 (FAST)");   // (a batch: check_params)
+        auto* k = new HipKnn(); k->via = via; k->extractor = ex; lk = k;
+    } else { auto* l = new HipLK(); l->via = via; lk = l; }
+    auto* pnp = new HipPnP(); pnp->via = via; pnp->tracker = &run.pipe;
+    auto* tri = new HipTri(); tri->via = via; tri->tracker = &run.pipe; tri->workers = tri_workers;
+    tri->use_whole_hook = P->device_fivepoint == 2;   // the whole findEssentialMat: one launch, or one request of the five-point combiner
+    tri->use_hypothesis_hook = P->device_fivepoint != 0 && !tri->use_whole_hook;
+    tri->prefetch_threads = (!via.eng && P->n_threads > 1 && P->device_fivepoint == 0) ? 2 : 0;   // only the two-thread pipeline calls prefetch()
+    auto* ba = new HipBA(); ba->via = via; ba->tracker = &run.pipe;
+    run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
+    run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
+}
 }  // namespace
 
 struct pmv_pipeline_result { vo::PipelineRun run; };
@@ -319,11 +293,7 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
                                int first_slot, pmv::BatchIngest* ing, int fed, int ring, pmv_pipeline_result** out, int& code, std::string& msg) {
     auto* res = new pmv_pipeline_result();
     vo::PipelineRun& run = res->run;
-    vo::PipelineParams vp;
-    vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
-    vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
-    vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
-    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = 1; vp.reserved = 0; vp.matcher = P->matcher;
+    const vo::PipelineParams vp = params_of(P, 1);
     try {
         vo::pipeline_setup(run, vp, nullptr, K9, gt_poses12);
         for (auto& im : run.pipe.images) im.slot = first_slot + im.slot % ring;
@@ -333,22 +303,7 @@ static void run_batch_sequence(pmv_ctx* ctx, pmv::BatchEngine* eng, int b, const
             vo::OdometryPipeline* pipe = &run.pipe;
             run.pipe.on_frame_added = [ing, fed, pipe](int k) { pmv::batch_ingest_release(ing, fed, k + pipe->init_offset); };
         }
-        RingFrames rf{ing, fed};
-        vo::BaseFeatureExtractor* ex;
-        if (P->extractor == 1) { auto* e = new BatchShiTomasi(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
-        else if (P->extractor == 2) { auto* e = new BatchFast(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
-        else { auto* e = new BatchGftt(); e->ctx = ctx; e->eng = eng; e->ring = rf; ex = e; }
-        run.owned_ex.push_back(ex);
-        vo::BaseFeatureMatcher* lk;
-        if (P->matcher == 1) { auto* k = new BatchKnn(); k->ctx = ctx; k->eng = eng; k->ring = rf; k->extractor = ex; lk = k; }   // (extractor = 2: check_params)
-        else { auto* l = new BatchLK(); l->ctx = ctx; l->eng = eng; l->ring = rf; lk = l; }
-        auto* pnp = new BatchPnP(); pnp->ctx = ctx; pnp->eng = eng; pnp->seq = b; pnp->tracker = &run.pipe;
-        auto* tri = new BatchTri(); tri->ctx = ctx; tri->eng = eng; tri->seq = b; tri->tracker = &run.pipe; tri->workers = 1;
-        tri->use_whole_hook = P->device_fivepoint == 2;   // the whole findEssentialMat as one request of the five-point combiner
-        tri->use_hypothesis_hook = P->device_fivepoint != 0 && !tri->use_whole_hook;
-        auto* ba = new BatchBA(); ba->ctx = ctx; ba->eng = eng; ba->seq = b; ba->tracker = &run.pipe;
-        run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
-        run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
+        plug_in(run, P, Route{ctx, eng, RingFrames{ing, fed}, b}, 1);
         vo::pipeline_execute(run, vp);
         *out = res;
     } catch (const HipError& e) {
@@ -461,32 +416,11 @@ int pmv_pipeline_run(pmv_ctx* ctx, const pmv_pipeline_params* P, const double* K
     if (const int rc = check_params(ctx, "pmv_pipeline_run", *P, false)) return rc;
     auto* res = new pmv_pipeline_result();
     vo::PipelineRun& run = res->run;
-    vo::PipelineParams vp;
-    vp.n_frames = P->n_frames; vp.w = P->w; vp.h = P->h;
-    vp.min_tracked_features = P->min_tracked_features; vp.tracked_features_tol = P->tracked_features_tol;
-    vp.init_frames = P->init_frames; vp.bundle_size = P->bundle_size; vp.ba_iterations = P->ba_iterations;
-    vp.extractor = P->extractor; vp.threaded = P->threaded; vp.n_threads = P->n_threads; vp.reserved = 0; vp.matcher = P->matcher;
+    const vo::PipelineParams vp = params_of(P, P->n_threads);
     try {
         if (P->build_pyramids) ck(ctx, pmv_frames_build(ctx, 0, P->n_frames));
         vo::pipeline_setup(run, vp, nullptr, K9, gt_poses12);
-        vo::BaseFeatureExtractor* ex;
-        if (P->extractor == 1) { auto* e = new HipShiTomasi(); e->ctx = ctx; ex = e; }
-        else if (P->extractor == 2) { auto* e = new HipFast(); e->ctx = ctx; ex = e; }
-        else { auto* e = new HipGftt(); e->ctx = ctx; ex = e; }
-        run.owned_ex.push_back(ex);
-        vo::BaseFeatureMatcher* lk;
-        if (P->matcher == 1) {   // kNNFeatureMatcher(extractor): the reference's alternative matcher; it calls the extractor on whole frames
-            if (P->extractor != 2) throw std::runtime_error("the kNN matcher needs an extractor that accepts whole frames: extractor = 2 (FAST)");
-            auto* k = new HipKnn(); k->ctx = ctx; k->extractor = ex; lk = k;
-        } else { auto* l = new HipLK(); l->ctx = ctx; lk = l; }
-        auto* pnp = new HipPnP(); pnp->ctx = ctx; pnp->tracker = &run.pipe;
-        auto* tri = new HipTri(); tri->ctx = ctx; tri->tracker = &run.pipe; tri->workers = std::max(1, P->n_threads);
-        tri->use_whole_hook = P->device_fivepoint == 2;   // pmv_find_essential_mat: the whole RANSAC in one launch
-        tri->use_hypothesis_hook = P->device_fivepoint != 0 && !tri->use_whole_hook;
-        tri->prefetch_threads = (P->n_threads > 1 && P->device_fivepoint == 0) ? 2 : 0;   // only the two-thread pipeline calls prefetch()
-        auto* ba = new HipBA(); ba->ctx = ctx; ba->tracker = &run.pipe;
-        run.m = lk; run.p = pnp; run.tr = tri; run.b = ba;
-        run.pipe.extractor = ex; run.pipe.matcher = lk; run.pipe.pnpsolver = pnp; run.pipe.triangulator = tri; run.pipe.ba = ba;
+        plug_in(run, P, Route{ctx}, std::max(1, P->n_threads));
         vo::pipeline_execute(run, vp);
     } catch (const HipError& e) {
         pmv::set_err(ctx, "pmv_pipeline_run: %s", e.what());

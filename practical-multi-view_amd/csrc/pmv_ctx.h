@@ -170,16 +170,21 @@ int slot_ready(pmv_ctx* ctx, int slot, BatchIngest* feed = nullptr, int seq = 0,
 void batch_ingest_destroy(BatchIngest*& g);
 void batch_engine_destroy(pmv_ctx* ctx);
 void batch_session_destroy(pmv_ctx* ctx);   // joins the upload thread, frees the session (no session call may be in flight)
-// The argument checks of the front-end calls, shared by the single-sequence entry points (bracket = true: a slot of an open
-// pmv_frames_stream_begin bracket first waits for its round on the front-end stream) and the session calls of the same name (bracket =
-// false): the same status codes in the same places, from one copy. ctx is not null. max_per_cell of detect_check: already >= 1.
-// what the extended calls check on top of lk_check (`who` names the call in the messages): the flag bits, the back outputs of a
-// forward-backward call (fb), and with PMV_LK_USE_INITIAL_FLOW every initial coordinate (finite, |v| <= 1e6). Before lk_check: null back pointers.
-int lkx_check(pmv_ctx* ctx, const char* who, int flags, const float* next_xy, int n, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err);
+// The argument checks of the front-end calls, one copy for every form of a call: the single-sequence entry points (bracket = true: a slot
+// of an open pmv_frames_stream_begin bracket first waits for its round on the front-end stream) and the engine's request entries (bracket =
+// false; batch_engine.h, "who checks what"). ctx is not null. max_per_cell of detect_check: already >= 1.
 int lk_check(pmv_ctx* ctx, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* out_xy, const uint8_t* out_status, const float* out_err);
+// the extended calls (`who` names the call in the messages): the back outputs of a forward-backward call (fb), lk_check, the flag bits, and
+// with PMV_LK_USE_INITIAL_FLOW every initial coordinate (finite, |v| <= 1e6)
+int lkx_check(pmv_ctx* ctx, const char* who, bool bracket, int prev_slot, int next_slot, const float* prev_xy, int n, const float* next_xy, int flags,
+              const uint8_t* out_status, const float* out_err, bool fb, const float* back_xy, const uint8_t* back_status, const float* back_err);
 int knn_check(pmv_ctx* ctx, bool bracket, int src_slot, int cmp_slot, const int* src_xy, int n, const int* cmp_xy, int m, int n_neighbours, int window, const int* out_best,
               const float* out_err);
 int detect_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell);
+// pmv_detect_shitomasi with max_per_cell <= 0 (the reference takes nothing then): the counts are checked and zeroed, nothing is launched
+int shitomasi_nothing(pmv_ctx* ctx, const int* cells, int n_cells, int* out_count);
+// (x0, y0, w, h) -> device cell records of that frame slot
+void pack_cells(int* dst, const int* cells, int n_cells, int slot);
 // pmv_detect_gftt_ex / pmv_batch_detect_gftt_ex: the parameter checks (before detect_check), the mask stride against the slot's frame (after
 // it), and the packing of the cells' mask sub-views behind byte `pos` of dst (returns the new end; writes each offset into its cell record)
 int gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, const int* out_xy, const int* out_count);
@@ -196,7 +201,9 @@ inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
 int clahe_check(pmv_ctx* ctx, const char* who, const pmv_clahe_params* p);
 // pmv_frames_remap / pmv_batch_frame_upload_remap: the map id and the border value of the contract; on success *map is a copy of the map's entry
 int remap_check(pmv_ctx* ctx, const char* who, int map_id, int border_value, pmv_ctx::RemapMap* map);
-// after the count / null checks and the max_per_cell <= 0 shortcut of pmv_detect_fast
+// pmv_detect_fast: the count / null checks and, for max_per_cell <= 0 (the reference takes nothing then), zero counts - the caller returns
+// without a launch; then, for max_per_cell >= 1, the rest of the checks
+int fast_counts(pmv_ctx* ctx, const int* cells, int n_cells, int max_per_cell, int* out_count);
 int fast_check(pmv_ctx* ctx, bool bracket, int slot, const int* cells, int n_cells, int max_per_cell, const int* out_xy, const float* out_response);
 // XCD-aware block order of an LK launch: workgroup b runs on XCD b % 8 and every XCD has its own L2, so the tracks (which arrive in hash
 // order, i.e. spatially random) are dealt out by x position: the k-th track of equal-count stripe s goes to block 8k + s. Each L2 then

@@ -137,6 +137,25 @@ def test_the_session_calls_are_declared_exported_and_bound(pmv):
     assert callable(pmv.Context.batch_session)
 
 
+# the calls that exist as X and batch_X; the back-end ones take the sequence first
+FRONT_END_PAIRS = ["detect_gftt", "detect_gftt_ex", "corner_subpix", "detect_shitomasi", "detect_fast", "knn_match", "lk_track", "lk_track_ex", "lk_track_fb"]
+BACK_END_PAIRS = ["pnp_ransac", "ba_solve", "triangulate_candidates", "fivepoint_hypotheses", "find_essential_mat", "find_fundamental_mat", "recover_pose"]
+SIGNATURE_EXCEPTIONS = {}   # name -> why batch_X may differ from X (none does)
+
+
+def test_every_session_method_has_the_signature_of_its_single_method(pmv):
+    """batch_X takes X's arguments under X's names with X's defaults; a back-end call takes `seq` in front of them"""
+    import inspect
+    for name in FRONT_END_PAIRS + BACK_END_PAIRS:
+        if name in SIGNATURE_EXCEPTIONS:
+            continue
+        single = inspect.signature(getattr(pmv.Context, name))
+        params = list(single.parameters.values())
+        if name in BACK_END_PAIRS:
+            params.insert(1, inspect.Parameter("seq", inspect.Parameter.POSITIONAL_OR_KEYWORD))   # (behind self)
+        assert inspect.signature(getattr(pmv.Context, "batch_" + name)) == single.replace(parameters=params), name
+
+
 def _doc_before(src, decl):
     """the comment block that precedes a declaration, flattened"""
     end = src.index(decl)
