@@ -8,6 +8,7 @@
  *                                          implicit inside OpenCVLucasKanadeFM.cpp:15)
  *   pmv_detect_gftt                        cv::goodFeaturesToTrack per grid cell         (OpenCVGoodFeatureExtractor.cpp:7,
  *                                          called from OdometryPipeline.cpp:357 / :450)  -> BaseFeatureExtractor.h:21
+ *   pmv_detect_gftt_frame                  cv::goodFeaturesToTrack on the whole frame or one region of any size, one call per frame
  *   pmv_detect_gftt_ex                     cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector, k (a KLT front end
  *                                          of the caller's own; the reference passes cv::Mat(), 3, 3, false, 0.04)
  *   pmv_corner_subpix                      cv::cornerSubPix on level 0 of a slot (the step between the detector and LK in the caller's own
@@ -337,6 +338,42 @@ int pmv_debug_gftt_response_ex(pmv_ctx* ctx, int slot, const int* cell, const pm
 /* diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex (block 3, no Harris, no mask) through the general kernels as
  * well, single and session calls alike, so that a test can compare the two code paths. It changes no result. */
 int pmv_debug_gftt_general(pmv_ctx* ctx, int on);
+/* cv::goodFeaturesToTrack(frame(roi), corners, max_corners, p->quality, p->min_dist, mask(roi), p->block_size, p->use_harris, p->k) on
+ * level 0 of `slot`, for ONE region of any size up to the frame: what a KLT loop calls once per frame to refill its tracks. It is not the
+ * union of per-cell calls: the quality threshold is quality x the maximum over the whole allowed region, the order and the max_corners cut
+ * are global, and min_dist acts across what would be cell borders.
+ *   roi4_or_null: (x0, y0, w, h), at least 3x3 and inside the frame; NULL = the whole frame.
+ *   Arithmetic: exactly that of pmv_detect_gftt_ex with the region as its cell (see there) - the Sobel border is the parent frame's, the
+ *     box border REFLECT_101 of the region, the maximum is taken over the allowed pixels, the 3x3 test runs on the raw response and looks at
+ *     masked-out neighbours too, threshold (float)(max * quality), order (value, address) descending, greedy min_dist. The yardstick is the
+ *     bytes of gftt_twin_cell (tests/twin/gftt_twin.cpp) with the region as its cell.
+ *   mask: as for pmv_detect_gftt_ex - NULL, or host memory of the frame's size, mask_stride bytes per row, non-zero = allowed; the region
+ *     sees its own rectangle. Only the bytes under the region cross the bus, packed tight into pinned memory.
+ *   out_xy: out_cap * 2 ints, REGION-LOCAL (x, y) in cv's order; *out_count: the number of corners written.
+ *   cap = max_corners > 0 ? max_corners : out_cap must satisfy 1 <= cap <= min(out_cap, PMV_GFTT_FRAME_MAX_CORNERS).
+ *   No limit: max_corners <= 0 is cv's "no limit"; if more than out_cap corners would be selected the call returns PMV_ERR_OVERFLOW and
+ *     writes nothing. Status bits of one call never leak into the next.
+ *   Kernels: pass 1 is the per-tile work of k_gftt_cand - for (3, no Harris, no mask) unless pmv_debug_gftt_general is on - or of
+ *     k_gftt_cand_general, over ceil(h / 32) x ceil(w / 32) tiles; pass 2 (k_gftt_pick_frame) makes the selection over the frame's records in
+ *     one launch: up to PMV_GFTT_FRAME_MAX_CORNERS records above the threshold are sorted and walked on chip, more take the same steps in
+ *     HBM (exact, slower). Both are booked under the profiling classes of pmv_detect_gftt (k_gftt_cand, k_gftt_pick).
+ * Errors (nothing is written and nothing is clamped on any of them): the parameter errors of pmv_detect_gftt_ex with the same codes
+ *   (PMV_ERR_INVALID: null p or null outputs, block_size, quality, min_dist, k; PMV_ERR_CAPACITY: mask_stride below the frame width);
+ *   PMV_ERR_INVALID - a region smaller than 3x3 or not inside the frame (the message names the region and the frame size);
+ *   PMV_ERR_CAPACITY - a bad cap, a slot out of range, a frame with a side above 32767; the slot-state and bracket rules of the other
+ *   detectors.
+ * The device buffers are made by the first frame call on a context, sized for max_w x max_h (a flat plateau makes every pixel a record).
+ * pmv_detect_gftt and pmv_detect_gftt_ex keep their 255x255 cells and every refusal: this is a new entry point, not a lifted limit.
+ * Out of scope: Sobel apertures other than 3; building the keep-away mask on the device from a track list (cv::circle's rasterisation) -
+ *   the mask still comes from the host; more than PMV_GFTT_FRAME_MAX_CORNERS corners; the whole-sequence drivers (pmv_pipeline_run*) and
+ *   bench.py do not call this. */
+#define PMV_GFTT_FRAME_MAX_CORNERS 16384
+int pmv_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
+                          const uint8_t* mask, int mask_stride, int* out_xy, int out_cap, int* out_count);
+/* diagnostic: out6 = {frame calls served by the single entry point, session rounds that held at least one frame request, launch pairs
+ * made for those rounds, records above the threshold in the last request served, of those the number kept off-chip, on-chip record
+ * capacity of the selection kernel}. */
+int pmv_debug_gftt_frame_stats(pmv_ctx* ctx, long long* out6);
 /* Same geometry; out_score: n_cells * max_per_cell doubles (the reference fills Feature::score). max_per_cell <= 0 returns no
  * features (ShiTomasiFeatureExtractor.cpp:37-44). */
 int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
@@ -841,6 +878,13 @@ int pmv_batch_detect_gftt(pmv_ctx* ctx, int slot, const int* cells, int n_cells,
  * what it launched before. The mask is read before the call returns. */
 int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p, const uint8_t* mask,
                              int mask_stride, int* out_xy, int* out_count);
+/* pmv_detect_gftt_frame as a session call: the same arguments, bytes and status codes, served by the detector combiner. The frame requests
+ * of a round share ONE pass-1 launch and ONE pass-2 launch if they agree in block_size, use_harris, k, has-mask, quality, min_dist, cap, the
+ * no-limit flag and the frame layout (the grouping rules of pmv_batch_detect_gftt_ex): each request's records sit at their own offset and
+ * pass 2 runs one workgroup per request. A round without frame requests launches exactly what it launched before. The mask is read before
+ * the call returns; record space grows to the largest round seen. */
+int pmv_batch_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
+                                const uint8_t* mask, int mask_stride, int* out_xy, int out_cap, int* out_count);
 /* pmv_corner_subpix as a session call: the same arguments, bits and status codes. It is served by the detector combiner: requests of a
  * round that agree in the six parameters share ONE launch, whatever their slots and declared frame sizes (every point's record names its
  * geometry); a round without such requests launches exactly what it launched before. A round's result block holds at least

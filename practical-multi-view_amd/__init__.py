@@ -185,6 +185,7 @@ ABI_SYMBOLS = [
     "pmv_frame_upload", "pmv_frame_upload_bgr", "pmv_set_frame_format", "pmv_frames_stage", "pmv_frames_build", "pmv_frames_stream_begin", "pmv_frames_stream_end", "pmv_frame_get_level", "pmv_frame_get_level_padded", "pmv_frame_num_levels",
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
+    "pmv_detect_gftt_frame", "pmv_batch_detect_gftt_frame", "pmv_debug_gftt_frame_stats",
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
     "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
@@ -205,6 +206,7 @@ ABI_SYMBOLS = [
 
 
 GFTT_UNLIMITED_CAP = 4096   # PMV_GFTT_UNLIMITED_CAP of include/pmv_hip.h
+GFTT_FRAME_MAX_CORNERS = 16384   # PMV_GFTT_FRAME_MAX_CORNERS of include/pmv_hip.h
 
 
 class PipelineParams(C.Structure):
@@ -689,6 +691,45 @@ class Context:
         size (non-zero = allowed; any row stride), each cell sees its own rectangle of it; block_size 1..15; use_harris with k. The defaults
         return detect_gftt's arrays."""
         return self._gftt_ex(self.lib.pmv_detect_gftt_ex, self._ck, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k)
+
+    def _gftt_frame(self, fn, ck, slot, max_corners, quality, min_dist, mask, block_size, use_harris, k, roi, out_cap):
+        if out_cap is None:
+            out_cap = int(max_corners) if max_corners > 0 else GFTT_FRAME_MAX_CORNERS
+        xy = np.zeros((max(int(out_cap), 1), 2), np.int32)
+        cnt = C.c_int(0)
+        p = GfttParams(float(quality), float(min_dist), int(block_size), 1 if use_harris else 0, float(k))
+        rptr = None
+        if roi is not None:
+            roi = np.ascontiguousarray(roi, np.int32).reshape(-1)
+            if roi.size != 4:
+                raise ValueError("detect_gftt_frame: roi is (x0, y0, w, h)")
+            rptr = _p(roi, _i32p)
+        mptr, mstride = None, 0
+        if mask is not None:
+            # passed in place with its own row stride; the library reads the bytes under the region only, so the mask must cover it
+            if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.ndim != 2 or (mask.shape[1] > 1 and mask.strides[1] != 1):
+                raise ValueError("detect_gftt_frame: mask must be an (h, w) uint8 array whose rows are contiguous (any row stride)")
+            if roi is not None and (roi[0] < 0 or roi[1] < 0 or roi[0] + roi[2] > mask.shape[1] or roi[1] + roi[3] > mask.shape[0]):
+                raise ValueError(f"detect_gftt_frame: the region lies outside the {mask.shape[1]}x{mask.shape[0]} mask (the mask has the frame's size)")
+            mptr, mstride = C.cast(C.c_void_p(mask.ctypes.data), _u8p), int(mask.strides[0]) if mask.shape[0] > 1 else max(int(mask.strides[0]), mask.shape[1])
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, C.POINTER(GfttParams), _u8p, C.c_int, _i32p, C.c_int, C.POINTER(C.c_int)]
+        ck(fn(self.h, int(slot), rptr, int(max_corners), C.byref(p), mptr, mstride, _p(xy, _i32p), int(out_cap), C.byref(cnt)))
+        return xy[: cnt.value].copy()
+
+    def detect_gftt_frame(self, slot, max_corners, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04, roi=None, out_cap=None):
+        """pmv_detect_gftt_frame: cv::goodFeaturesToTrack on the whole frame in `slot` (roi None) or on one region (x0, y0, w, h) of any size.
+        Returns (n, 2) int32 region-local corners in cv's order. max_corners <= 0: no limit; out_cap (default max_corners, or
+        GFTT_FRAME_MAX_CORNERS without a limit) is the list's capacity - more corners than that raise PmvError (PMV_ERR_OVERFLOW). With a
+        mask of a frame that is smaller than the mask's array, pass roi."""
+        return self._gftt_frame(self.lib.pmv_detect_gftt_frame, self._ck, slot, max_corners, quality, min_dist, mask, block_size, use_harris, k, roi, out_cap)
+
+    def debug_gftt_frame_stats(self):
+        """pmv_debug_gftt_frame_stats: [frame calls of the single entry point, session rounds with a frame request, launch pairs made for them,
+        records above the threshold in the last request served, of those kept off-chip, on-chip record capacity of the selection kernel]"""
+        out = (C.c_longlong * 6)()
+        self.lib.pmv_debug_gftt_frame_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_gftt_frame_stats(self.h, out))
+        return [int(v) for v in out]
 
     def gftt_response_ex(self, slot, cell, block_size=3, use_harris=False, k=0.04):
         """pmv_debug_gftt_response_ex: the float32 response map of one cell for this block size and response kind"""
@@ -1262,6 +1303,10 @@ class Context:
     def batch_detect_gftt_ex(self, slot, cells, max_per_cell, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04):
         """pmv_batch_detect_gftt_ex: detect_gftt_ex as a session call (same arguments, same arrays)"""
         return self._gftt_ex(self.lib.pmv_batch_detect_gftt_ex, self._ckt, slot, cells, max_per_cell, quality, min_dist, mask, block_size, use_harris, k)
+
+    def batch_detect_gftt_frame(self, slot, max_corners, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04, roi=None, out_cap=None):
+        """pmv_batch_detect_gftt_frame: detect_gftt_frame as a session call (same arguments, same array)"""
+        return self._gftt_frame(self.lib.pmv_batch_detect_gftt_frame, self._ckt, slot, max_corners, quality, min_dist, mask, block_size, use_harris, k, roi, out_cap)
 
     def batch_corner_subpix(self, slot, xy, win=(5, 5), zero_zone=(-1, -1), max_iter=30, eps=0.01, return_info=False):
         """pmv_batch_corner_subpix: corner_subpix as a session call (same arguments, same arrays)"""

@@ -16,7 +16,7 @@ void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
 // request record.
 enum ReqKind {
     Q_LK = 0, Q_GFTT = 1 /* plain or, with the caller's goodFeaturesToTrack arguments, extended */, Q_SHITOMASI = 2, Q_FAST = 3,
-    Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6 /* the detector combiner */,
+    Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6, Q_GFTT_FRAME = 7 /* the detector combiner */,
     Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_WHOLE_FIRST = Q_ESSENTIAL
 };
 // ---- request entry points: one per plugin call, with the contract of the single call of the same name (include/pmv_hip.h) -------------
@@ -45,6 +45,11 @@ int engine_detect(BatchEngine* E, ReqKind kind, int slot, const int* cells, int 
 // pmv_debug_gftt_general is on.
 int engine_detect_gftt_ex(BatchEngine* E, const char* who, int slot, const int* cells, int n_cells, int max_per_cell, const pmv_gftt_params* p,
                           const uint8_t* mask, int mask_stride, int* out_xy, int* out_count);
+// pmv_detect_gftt_frame's contract: a request of the detector combiner (the mask is read by the combiner before the call returns). The frame
+// requests of a round that agree in block size, response kind, k, has-mask, quality, min_dist, capacity, the no-limit flag and the frame
+// layout share ONE pass-1 and ONE pass-2 launch: each has its own record list, pass 2 runs one workgroup per request.
+int engine_detect_gftt_frame(BatchEngine* E, const char* who, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask,
+                             int mask_stride, int* out_xy, int out_cap, int* out_count);
 // pmv_corner_subpix's contract: a request of the detector combiner. Requests of a round that agree in the six parameters share one
 // launch, whatever their slots and frame sizes.
 int engine_corner_subpix(BatchEngine* E, const char* who, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);

@@ -72,6 +72,10 @@ struct DetReq : Req {
     // GFTT through the general kernels (pmv_batch_detect_gftt_ex): the caller's block size, response kind and k, and the optional host mask
     int ext = 0, block_size = 3, use_harris = 0; double k = 0.0;
     const uint8_t* mask = nullptr; int mask_stride = 0;
+    // Q_GFTT_FRAME (pmv_batch_detect_gftt_frame): the region (cells points at it, n_cells = 1, max_per_cell = the capacity of the corner list);
+    // filled by the combiner: the first entry of its record list among the round's, its index in its group
+    int roi[4] = {0, 0, 0, 0};
+    size_t list_off = 0;
 };
 struct SubpixReq : Req {      // Q_SUBPIX: one pmv_batch_corner_subpix call; p's zero zone is the effective one (subpix_zero_zone)
     int slot, n;
@@ -123,6 +127,10 @@ struct Combiner {
     // masks of the extended GFTT requests of a round (detector combiner, made by the first round that has one): the cells' mask sub-views
     // packed one after the other, pinned mirror and HBM copy
     HScratch h_gmask; DScratch d_gmask;
+    // whole-frame GFTT requests of a round (detector combiner, made by the first round that has one, grown to the largest round seen): the
+    // groups' blocks (gftt_frame_block) in mapped pinned memory, the regions' packed masks, and in HBM the record lists, the key lists of the
+    // selection's slower path (one entry per pixel of the round's regions) and the (maximum, count) pairs
+    HScratch h_gfr, h_gfr_mask; DScratch d_gfr_mask, d_gfr_val, d_gfr_idx, d_gfr_keys, d_gfr_info;
     // corner sub-pixel requests of a round (detector combiner, made by the first round that has one): [point records | positions | updates |
     // flags] in one mapped pinned block; the weight tables of the round's parameter groups, pinned mirror and HBM copy
     HScratch h_spx, h_spx_tab; DScratch d_spx_tab;
@@ -431,7 +439,8 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     hipStream_t s = C.s;
     std::vector<DetReq*> det;
     std::vector<SubpixReq*> spx;   // (corner sub-pixel requests: the same role, the same round, one more launch per parameter set)
-    for (Req* r : batch) { if (r->kind == Q_SUBPIX) spx.push_back((SubpixReq*)r); else det.push_back((DetReq*)r); }
+    std::vector<DetReq*> fr;       // (whole-frame GFTT requests: one more launch pair per parameter set)
+    for (Req* r : batch) { if (r->kind == Q_SUBPIX) spx.push_back((SubpixReq*)r); else if (r->kind == Q_GFTT_FRAME) fr.push_back((DetReq*)r); else det.push_back((DetReq*)r); }
     // ---- detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
     // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
     // FAST (grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
@@ -530,6 +539,64 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         }
         EK(hipMemcpyAsync(D.flags.h, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
     }
+    // ---- whole-frame GFTT: requests that agree in every argument but the slot, the region and the mask's bytes, on frames of one layout,
+    // share ONE pass-1 and ONE pass-2 launch (launch_gftt_frame). A round without such a request adds nothing here.
+    struct FGroup { DetReq* key; PyrLayout L; std::vector<DetReq*> reqs; int grid_x = 0; size_t info_base = 0; GfttFrameBlock B{}; };
+    std::vector<FGroup> fgroups;
+    size_t f_pix = 0, f_mask = 0, f_n = 0;
+    for (DetReq* r : fr) {
+        if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
+        const PyrLayout& Lr = ctx->slot_layout[r->slot];
+        if (r->roi[0] + r->roi[2] > Lr.w[0] || r->roi[1] + r->roi[3] > Lr.h[0]) {   // (the slot was re-used since the call's check)
+            r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch GFTT: region (%d,%d,%d,%d) is not inside the %dx%d frame", r->roi[0], r->roi[1], r->roi[2], r->roi[3], Lr.w[0], Lr.h[0]);
+            continue;
+        }
+        const size_t pix = (size_t)r->roi[2] * r->roi[3];
+        if (r->mask && f_mask + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
+        if (r->mask) f_mask += pix;
+        FGroup* g = nullptr;
+        for (FGroup& x : fgroups) {
+            const DetReq* k = x.key;
+            if (k->max_per_cell == r->max_per_cell && k->unlimited == r->unlimited && k->quality == r->quality && k->min_dist == r->min_dist && k->ext == r->ext &&
+                k->block_size == r->block_size && k->use_harris == r->use_harris && k->k == r->k && (k->mask != nullptr) == (r->mask != nullptr) &&
+                x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
+        }
+        if (!g) { fgroups.push_back(FGroup{r, Lr, {}}); g = &fgroups.back(); }
+        r->list_off = f_pix;
+        f_pix += pix;
+        f_n++;
+        g->grid_x = std::max(g->grid_x, gftt_frame_grid_x(r->roi[2], r->roi[3]));
+        g->reqs.push_back(r);
+    }
+    if (!fgroups.empty()) {
+        Carve need;
+        for (FGroup& g : fgroups) gftt_frame_block(need, g.reqs.size(), (size_t)g.key->max_per_cell);
+        EK(C.h_gfr.ensure(need.bytes() + 64));
+        EK(C.d_gfr_val.ensure(f_pix * sizeof(float))); EK(C.d_gfr_idx.ensure(f_pix * sizeof(unsigned))); EK(C.d_gfr_keys.ensure(f_pix * sizeof(unsigned long long)));
+        EK(C.d_gfr_info.ensure(f_n * 2 * sizeof(unsigned)));
+        if (f_mask) { EK(C.h_gfr_mask.ensure(f_mask + 64)); EK(C.d_gfr_mask.ensure(f_mask + 64)); }
+        Carve c = carve_of(C.h_gfr);
+        size_t mpos = 0, ibase = 0;
+        for (FGroup& g : fgroups) {
+            g.B = gftt_frame_block(c, g.reqs.size(), (size_t)g.key->max_per_cell);
+            g.info_base = ibase;
+            ibase += g.reqs.size();
+            for (size_t i = 0; i < g.reqs.size(); i++) {
+                DetReq* r = g.reqs[i];
+                mpos = gftt_frame_record(g.B.rec.h + i * CELL_STRIDE, r->roi, r->slot, r->list_off, (uint8_t*)C.h_gfr_mask.p, mpos, r->mask, r->mask_stride);
+            }
+        }
+        if (f_mask) EK(hipMemcpyAsync(C.d_gfr_mask.p, C.h_gfr_mask.p, f_mask, hipMemcpyHostToDevice, s));
+        for (FGroup& g : fgroups) {
+            const DetReq* k = g.key;
+            const GfttExt X = gftt_ext(k->block_size, k->use_harris, k->k);
+            EK(launch_gftt_frame(s, ctx->d_slots, g.L, g.B.rec.d, (int)g.reqs.size(), g.grid_x, k->max_per_cell, k->quality, k->min_dist, k->unlimited, k->ext ? &X : nullptr,
+                                 k->mask ? (const uint8_t*)C.d_gfr_mask.p : nullptr, (float*)C.d_gfr_val.p, (unsigned*)C.d_gfr_idx.p, (unsigned*)C.d_gfr_info.p + 2 * g.info_base,
+                                 (unsigned long long*)C.d_gfr_keys.p, g.B.xy.d, g.B.count.d, g.B.stats.d));
+            ctx->gftt_frame_stats[2]++;
+        }
+        ctx->gftt_frame_stats[1]++;
+    }
     // ---- corner sub-pixel refinement: requests that agree in the six parameters share ONE launch, whatever their slots and frame sizes -
     // every point's record names its slot and its entry of the geometry table. A round without such a request adds nothing here.
     struct SGroup { pmv_subpix_params p; std::vector<SubpixReq*> reqs; int n = 0, base = 0; };
@@ -585,6 +652,15 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 if (r->flags_out) memcpy(r->flags_out, S.flags.h + r->base, (size_t)r->n);
             }
     }
+    for (FGroup& g : fgroups)
+        for (size_t i = 0; i < g.reqs.size(); i++) {
+            DetReq* r = g.reqs[i];
+            const int n = g.B.count.h[i];
+            ctx->gftt_frame_stats[3] = g.B.stats.h[2 * i]; ctx->gftt_frame_stats[4] = g.B.stats.h[2 * i + 1];
+            if (n < 0) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "pmv_batch_detect_gftt_frame: more than out_cap = %d corners with max_corners <= 0 (no limit)", r->max_per_cell); continue; }
+            memcpy(r->out_xy, g.B.xy.h + i * (size_t)r->max_per_cell * 2, (size_t)n * 8);
+            *r->out_count = n;
+        }
     if (!det.empty()) {
         const DetBlock D = det_block(C, tot_out, tot_cells);
         const int flags = *D.flags.h;
@@ -1033,6 +1109,20 @@ int engine_detect_gftt_ex(BatchEngine* E, const char* who, int slot, const int* 
         r.ext = 1; r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
         r.mask = mask; r.mask_stride = mask_stride;
     }
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_detect_gftt_frame(BatchEngine* E, const char* who, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask,
+                             int mask_stride, int* out_xy, int out_cap, int* out_count) {
+    pmv_ctx* ctx = E->ctx;
+    DetReq r;
+    int cap = 0;
+    if (const int rc = gftt_frame_check(ctx, who, false, slot, roi4_or_null, max_corners, p, mask, mask_stride, out_xy, out_cap, out_count, r.roi, &cap)) return rc;
+    r.kind = Q_GFTT_FRAME; r.slot = slot; r.cells = r.roi; r.n_cells = 1; r.unlimited = max_corners <= 0; r.max_per_cell = cap;
+    r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count; r.ring_round = -1;
+    r.ext = p->block_size != 3 || p->use_harris || mask || ctx->gftt_general;   // the general pass-1 kernel, as in the single call
+    r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
+    r.mask = mask; r.mask_stride = mask_stride;
     return submit(ctx, E->queue[R_DET], &r);
 }
 

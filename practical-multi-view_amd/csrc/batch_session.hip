@@ -492,6 +492,12 @@ int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cel
     return engine_detect_gftt_ex(S->eng, "pmv_batch_detect_gftt_ex", slot, cells, n_cells, max_per_cell, p, mask, mask_stride, out_xy, out_count);
 }
 
+int pmv_batch_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask, int mask_stride,
+                                int* out_xy, int out_cap, int* out_count) {
+    SESSION("pmv_batch_detect_gftt_frame");
+    return engine_detect_gftt_frame(S->eng, "pmv_batch_detect_gftt_frame", slot, roi4_or_null, max_corners, p, mask, mask_stride, out_xy, out_cap, out_count);
+}
+
 int pmv_batch_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
     SESSION("pmv_batch_corner_subpix");
     return engine_corner_subpix(S->eng, "pmv_batch_corner_subpix", slot, xy, n, p, out_iters, out_flags);

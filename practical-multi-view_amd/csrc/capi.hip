@@ -5,6 +5,7 @@
 #include <vector>
 #include <cstdarg>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -724,6 +725,32 @@ int pmv::gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t*
     REQ(!mask || mask_stride >= ctx->slot_layout[slot].w[0], PMV_ERR_CAPACITY, "%s: mask_stride = %d is below the frame width %d", who, mask_stride, ctx->slot_layout[slot].w[0]);
     return PMV_OK;
 }
+// The record of a corner, (y << 16) | x, the 31-bit pixel index y * w + x of a pass-1 record and the int distances of the selection hold
+// for every region this check lets through: sides up to GFTT_FRAME_MAX_SIDE, fewer than 2^31 pixels.
+int pmv::gftt_frame_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask,
+                          int mask_stride, const int* out_xy, int out_cap, const int* out_count, int* roi4, int* cap) {
+    static_assert(PMV_GFTT_FRAME_MAX_CORNERS == GFTT_FRAME_ONCHIP, "a call may return as many corners as the selection kernel sorts on chip");
+    static_assert(GFTT_FRAME_MAX_SIDE <= 0xffff && 2ll * GFTT_FRAME_MAX_SIDE * GFTT_FRAME_MAX_SIDE <= INT_MAX, "(y << 16) | x; dx * dx + dy * dy in an int");
+    if (const int rc = gftt_ex_check(ctx, who, p, out_xy, out_count)) return rc;
+    REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "%s: slot out of range", who);
+    *cap = max_corners > 0 ? max_corners : out_cap;
+    REQ(*cap >= 1 && *cap <= out_cap && *cap <= PMV_GFTT_FRAME_MAX_CORNERS, PMV_ERR_CAPACITY, "%s: max_corners = %d with out_cap = %d: the list must hold 1..%d corners",
+        who, max_corners, out_cap, PMV_GFTT_FRAME_MAX_CORNERS);
+    if (const int rc = bracket ? slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, slot)) return rc;
+    const PyrLayout& L = ctx->slot_layout[slot];
+    if (roi4_or_null) memcpy(roi4, roi4_or_null, 4 * sizeof(int));
+    else { roi4[0] = 0; roi4[1] = 0; roi4[2] = L.w[0]; roi4[3] = L.h[0]; }
+    REQ(roi4[2] >= 3 && roi4[3] >= 3 && roi4[0] >= 0 && roi4[1] >= 0 && roi4[2] <= L.w[0] - roi4[0] && roi4[3] <= L.h[0] - roi4[1], PMV_ERR_INVALID,
+        "%s: region (%d,%d,%d,%d) is smaller than 3x3 or not inside the %dx%d frame", who, roi4[0], roi4[1], roi4[2], roi4[3], L.w[0], L.h[0]);
+    REQ(L.w[0] <= GFTT_FRAME_MAX_SIDE && L.h[0] <= GFTT_FRAME_MAX_SIDE && (long long)ctx->max_w * ctx->max_h <= INT_MAX, PMV_ERR_CAPACITY,
+        "%s: a %dx%d frame is beyond the %d pixels a side (2^31 a frame) the corner records hold", who, L.w[0], L.h[0], GFTT_FRAME_MAX_SIDE);
+    return gftt_mask_check(ctx, who, slot, mask, mask_stride);
+}
+size_t pmv::gftt_frame_record(int* rec, const int* roi4, int slot, size_t list_off, uint8_t* dst, size_t pos, const uint8_t* mask, int mask_stride) {
+    pack_cells(rec, roi4, 1, slot);
+    rec[6] = (int)(unsigned)(list_off & 0xffffffffu); rec[7] = (int)(unsigned)(list_off >> 32);
+    return mask ? gftt_pack_mask(dst, pos, rec, roi4, 1, mask, mask_stride) : pos;
+}
 int pmv::shitomasi_nothing(pmv_ctx* ctx, const int* cells, int n_cells, int* out_count) {   // ShiTomasiFeatureExtractor.cpp:37-44: `if (i >= max) break` before the first feature
     REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
     for (int i = 0; i < n_cells; i++) out_count[i] = 0;
@@ -838,6 +865,45 @@ int pmv_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cells, in
         return launch_gftt_ex(ctx->s_front, ctx->d_slots, L, ctx->d_cells, n_cells, cap, p->quality, p->min_dist, unlimited, gftt_ext(p->block_size, p->use_harris, p->k),
                               mask ? ctx->d_gmask.get() : nullptr, (float*)ctx->d_eig, (unsigned*)ctx->d_cellmax, ctx->d_det_xy, ctx->d_det_count, ctx->d_flags, ctx->d_spill);
     }, "pmv_detect_gftt_ex", out_xy, nullptr, out_count);
+}
+// cv::goodFeaturesToTrack on one region of any size: ONE request of the frame kernels (k_gftt_cand_frame or k_gftt_cand_general_frame, then
+// k_gftt_pick_frame). Record, count, statistics and the corner list live in one mapped pinned block: one wait, no copy calls.
+int pmv_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask, int mask_stride,
+                          int* out_xy, int out_cap, int* out_count) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_detect_gftt_frame: null argument");
+    int roi[4], cap;
+    if (const int rc = gftt_frame_check(ctx, "pmv_detect_gftt_frame", true, slot, roi4_or_null, max_corners, p, mask, mask_stride, out_xy, out_cap, out_count, roi, &cap)) return rc;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const PyrLayout& L = ctx->slot_layout[slot];
+    const size_t pix = (size_t)ctx->max_w * ctx->max_h;
+    Carve need;
+    gftt_frame_block(need, 1, PMV_GFTT_FRAME_MAX_CORNERS);
+    CKC(ctx->h_gfr.ensure(need.bytes() + 64));
+    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
+    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
+    if (mask) { CKC(ctx->h_gfr_mask.ensure(pix)); CKC(ctx->d_gfr_mask.ensure(pix)); }
+    Carve c = carve_of(ctx->h_gfr);
+    const GfttFrameBlock B = gftt_frame_block(c, 1, (size_t)cap);
+    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, ctx->h_gfr_mask, 0, mask, mask_stride);
+    if (mask) CKC(hipMemcpyAsync(ctx->d_gfr_mask, ctx->h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front));
+    const bool general = p->block_size != 3 || p->use_harris || mask || ctx->gftt_general;
+    const GfttExt X = gftt_ext(p->block_size, p->use_harris, p->k);
+    CKC(launch_gftt_frame(ctx->s_front, ctx->d_slots, L, B.rec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p->quality, p->min_dist, max_corners <= 0, general ? &X : nullptr,
+                          mask ? ctx->d_gfr_mask.get() : nullptr, ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    ctx->gftt_frame_stats[0]++; ctx->gftt_frame_stats[3] = B.stats.h[0]; ctx->gftt_frame_stats[4] = B.stats.h[1];
+    const int n = B.count.h[0];
+    REQ(n >= 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt_frame: more than out_cap = %d corners with max_corners <= 0 (no limit)", out_cap);
+    memcpy(out_xy, B.xy.h, (size_t)n * 8);
+    *out_count = n;
+    return PMV_OK;
+}
+int pmv_debug_gftt_frame_stats(pmv_ctx* ctx, long long* out6) {
+    REQ(ctx && out6, PMV_ERR_INVALID, "pmv_debug_gftt_frame_stats: null argument");
+    for (int i = 0; i < 5; i++) out6[i] = ctx->gftt_frame_stats[i].load();
+    out6[5] = GFTT_FRAME_ONCHIP;
+    return PMV_OK;
 }
 // diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex through the general kernels as well (no result changes)
 int pmv_debug_gftt_general(pmv_ctx* ctx, int on) {

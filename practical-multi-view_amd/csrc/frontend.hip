@@ -1417,21 +1417,12 @@ __device__ inline void gftt_cov(const uint8_t* __restrict__ p, int st, float& c0
 // (a neighbour at or below the threshold became 0), so the test needs no threshold - which is only known once the whole cell has been
 // seen (0.01 x the cell's maximum, cellinfo[2 cell] by atomicMax). Pass 2 drops the records at or below it. Only values > 0 can ever be
 // selected. HBM traffic: the cell's pixels once (+ halo), 8 B per local maximum - no 4 W H map.
-__global__ __launch_bounds__(256) void k_gftt_cand(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
-                                                   float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ cellinfo, double quality) {
-    __shared__ float sC[36 * 36 * 3];
-    __shared__ float sE[34 * 34];
-    __shared__ unsigned smax[4];
-    BACKEND_PRIO();   // a short pass between two LK launches of its sequence: ahead of the bulk LK waves it shares SIMDs with
-    const int cell = blockIdx.z;
-    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
-    // Consecutive workgroup ids go round the 8 XCDs, each with its own L2: blockIdx.x (8 values = the XCD) is the tile ROW, so the eight
-    // tiles that share the 128-byte lines of a 32-row band of the image run on ONE XCD and the band is fetched from HBM once (with
-    // blockIdx.x as the tile column every line was fetched by four XCDs: 2.75 MB of HBM reads per 0.47 MB frame by the PMC counters)
-    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;
-    if (tx0 >= cw || ty0 >= ch) return;
-    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
-    const int st = L.stride[0];
+// The work of one 32x32 tile at (tx0, ty0) of the cell (cx0, cy0, cw, ch) of `img` (level 0 of the cell's slot, row stride st), shared by
+// k_gftt_cand (a cell of the grid) and k_gftt_cand_frame (a region of any size). list_val / list_idx: the cell's record list; info: its
+// (maximum key, record count) pair; sC [36 * 36 * 3], sE [34 * 34], smax [4]: the workgroup's LDS.
+__device__ __forceinline__ void gftt_cand_tile(const uint8_t* __restrict__ img, int st, int cx0, int cy0, int cw, int ch, int tx0, int ty0,
+                                               float* __restrict__ list_val, unsigned* __restrict__ list_idx, unsigned* __restrict__ info, double quality,
+                                               float* sC, float* sE, unsigned* smax) {
     for (int idx = threadIdx.x; idx < 36 * 36; idx += 256) {
         const int hy = idx / 36, hx = idx - hy * 36;
         // the box filter's border is the CELL's (REFLECT_101 of the cell coordinate); the Sobel's is the parent image's (= the padded level)
@@ -1466,7 +1457,7 @@ __global__ __launch_bounds__(256) void k_gftt_cand(const uint8_t* __restrict__ s
     if (threadIdx.x == 0) {
         unsigned m = smax[0];
         for (int i = 1; i < 4; i++) m = smax[i] > m ? smax[i] : m;
-        atomicMax(&cellinfo[2 * cell], m);
+        atomicMax(&info[0], m);
     }
     // the tile's records are collected in LDS first (sC is free now), then ONE global atomic per workgroup reserves their place in the
     // cell's list (640 workgroups bumping 10 counters per wavefront and turn serialised in L2: 82 us per launch instead of 15)
@@ -1511,12 +1502,29 @@ __global__ __launch_bounds__(256) void k_gftt_cand(const uint8_t* __restrict__ s
     __syncthreads();
     const unsigned nt = s_cnt[0];
     if (nt == 0) return;
-    if (threadIdx.x == 0) s_cnt[1] = atomicAdd(&cellinfo[2 * cell + 1], nt);
+    if (threadIdx.x == 0) s_cnt[1] = atomicAdd(&info[1], nt);
     __syncthreads();
     const unsigned gbase = s_cnt[1];
-    float* cv = cand_val + (size_t)cell * CELL_PIX + gbase;
-    unsigned* ci = cand_idx + (size_t)cell * CELL_PIX + gbase;
+    float* cv = list_val + gbase;
+    unsigned* ci = list_idx + gbase;
     for (unsigned i = threadIdx.x; i < nt; i += 256) { cv[i] = lv[i]; ci[i] = li[i]; }
+}
+__global__ __launch_bounds__(256) void k_gftt_cand(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
+                                                   float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ cellinfo, double quality) {
+    __shared__ float sC[36 * 36 * 3];
+    __shared__ float sE[34 * 34];
+    __shared__ unsigned smax[4];
+    BACKEND_PRIO();   // a short pass between two LK launches of its sequence: ahead of the bulk LK waves it shares SIMDs with
+    const int cell = blockIdx.z;
+    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
+    // Consecutive workgroup ids go round the 8 XCDs, each with its own L2: blockIdx.x (8 values = the XCD) is the tile ROW, so the eight
+    // tiles that share the 128-byte lines of a 32-row band of the image run on ONE XCD and the band is fetched from HBM once (with
+    // blockIdx.x as the tile column every line was fetched by four XCDs: 2.75 MB of HBM reads per 0.47 MB frame by the PMC counters)
+    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;
+    if (tx0 >= cw || ty0 >= ch) return;
+    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
+    gftt_cand_tile(img, L.stride[0], cx0, cy0, cw, ch, tx0, ty0, cand_val + (size_t)cell * CELL_PIX, cand_idx + (size_t)cell * CELL_PIX, cellinfo + 2 * cell,
+                   quality, sC, sE, smax);
 }
 
 // Pass 2, one 256-thread workgroup per cell: records above the threshold are compacted into LDS and dealt to the lanes' REGISTERS; the
@@ -1772,22 +1780,16 @@ __device__ inline float gfttg_resp(const float* __restrict__ sC0, const float* _
     const float a = (float)s0 * 0.5f, b = (float)s1, c2 = (float)s2 * 0.5f;
     return (a + c2) - sqrtf((a - c2) * (a - c2) + b * b);
 }
-__global__ __launch_bounds__(256) void k_gftt_cand_general(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
-                                                           float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ cellinfo,
-                                                           double quality, GfttExt X, const uint8_t* __restrict__ mask) {
-    extern __shared__ float gfttg_lds[];
+// gftt_cand_tile's counterpart for the general kernels (k_gftt_cand_general, k_gftt_cand_general_frame). cmask: null, or the cell's packed
+// mask sub-view; lds: the workgroup's dynamic LDS (gfttg_lds_bytes).
+__device__ __forceinline__ void gfttg_cand_tile(const uint8_t* __restrict__ img, int st, int cx0, int cy0, int cw, int ch, int tx0, int ty0, const GfttExt& X,
+                                                const uint8_t* __restrict__ cmask, float* __restrict__ list_val, unsigned* __restrict__ list_idx,
+                                                unsigned* __restrict__ info, double quality, float* lds) {
     const int HP = (34 + X.bs - 1) * (34 + X.bs - 1);
-    float* sC0 = gfttg_lds; float* sC1 = sC0 + HP; float* sC2 = sC1 + HP;
+    float* sC0 = lds; float* sC1 = sC0 + HP; float* sC2 = sC1 + HP;
     float* sE = sC2 + HP;                            // [34 * 34]
     unsigned* smax = (unsigned*)(sE + 34 * 34);      // [4]
-    BACKEND_PRIO();
-    const int cell = blockIdx.z;
-    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
-    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;   // blockIdx.x = the tile ROW: see k_gftt_cand
-    if (tx0 >= cw || ty0 >= ch) return;
-    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
-    const uint8_t* cmask = mask ? mask + (size_t)cells[CELL_STRIDE * cell + 5] : nullptr;
-    gfttg_fill(img, L.stride[0], cx0, cy0, cw, ch, tx0, ty0, X, sC0, sC1, sC2);
+    gfttg_fill(img, st, cx0, cy0, cw, ch, tx0, ty0, X, sC0, sC1, sC2);
     __syncthreads();
     unsigned mk = 0;   // key 0 is below every real float key
     for (int idx = threadIdx.x; idx < 34 * 34; idx += 256) {
@@ -1808,7 +1810,7 @@ __global__ __launch_bounds__(256) void k_gftt_cand_general(const uint8_t* __rest
     if (threadIdx.x == 0) {
         unsigned m = smax[0];
         for (int i = 1; i < 4; i++) m = smax[i] > m ? smax[i] : m;
-        if (m) atomicMax(&cellinfo[2 * cell], m);   // (a tile without an allowed pixel has nothing to publish)
+        if (m) atomicMax(&info[0], m);   // (a tile without an allowed pixel has nothing to publish)
     }
     // the early drop of k_gftt_cand, against the tile's own MASKED maximum: the cell's masked maximum is at least that
     unsigned seen = smax[0];
@@ -1848,12 +1850,26 @@ __global__ __launch_bounds__(256) void k_gftt_cand_general(const uint8_t* __rest
     __syncthreads();
     const unsigned nt = s_cnt[0];
     if (nt == 0) return;
-    if (threadIdx.x == 0) s_cnt[1] = atomicAdd(&cellinfo[2 * cell + 1], nt);
+    if (threadIdx.x == 0) s_cnt[1] = atomicAdd(&info[1], nt);
     __syncthreads();
     const unsigned gbase = s_cnt[1];
-    float* cv = cand_val + (size_t)cell * CELL_PIX + gbase;
-    unsigned* ci = cand_idx + (size_t)cell * CELL_PIX + gbase;
+    float* cv = list_val + gbase;
+    unsigned* ci = list_idx + gbase;
     for (unsigned i = threadIdx.x; i < nt; i += 256) { cv[i] = lv[i]; ci[i] = li[i]; }
+}
+__global__ __launch_bounds__(256) void k_gftt_cand_general(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
+                                                           float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ cellinfo,
+                                                           double quality, GfttExt X, const uint8_t* __restrict__ mask) {
+    extern __shared__ float gfttg_lds[];
+    BACKEND_PRIO();
+    const int cell = blockIdx.z;
+    const int cx0 = cells[CELL_STRIDE * cell], cy0 = cells[CELL_STRIDE * cell + 1], cw = cells[CELL_STRIDE * cell + 2], ch = cells[CELL_STRIDE * cell + 3];
+    const int tx0 = blockIdx.y * 32, ty0 = blockIdx.x * 32;   // blockIdx.x = the tile ROW: see k_gftt_cand
+    if (tx0 >= cw || ty0 >= ch) return;
+    const uint8_t* img = level_origin(slots + (size_t)cells[CELL_STRIDE * cell + 4] * L.slot_bytes, L, 0);
+    const uint8_t* cmask = mask ? mask + (size_t)cells[CELL_STRIDE * cell + 5] : nullptr;
+    gfttg_cand_tile(img, L.stride[0], cx0, cy0, cw, ch, tx0, ty0, X, cmask, cand_val + (size_t)cell * CELL_PIX, cand_idx + (size_t)cell * CELL_PIX,
+                    cellinfo + 2 * cell, quality, gfttg_lds);
 }
 // diagnostic / parity (pmv_debug_gftt_response_ex): the response map of the same arithmetic, the only general launch that writes one
 __global__ __launch_bounds__(256) void k_gftt_eig_general(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ cells,
@@ -1895,6 +1911,257 @@ hipError_t launch_gftt_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& 
 hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, const GfttExt& X, float* d_eig) {
     if (!slots || !d_cells || !d_eig || n_cells < 1 || !gftt_ext_ok(X)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_gftt_eig_general, dim3(8, 8, n_cells), dim3(256), gfttg_lds_bytes(X.bs), s, slots, L, d_cells, d_eig, X);
+    return hipGetLastError();
+}
+
+// ---- cv::goodFeaturesToTrack on a region of any size (pmv_detect_gftt_frame) ---------------------------------------------------------
+// A request record is a cell record (x0, y0, w, h, slot, byte offset of the region's packed mask) whose ints 6 and 7 hold the first entry
+// of the request's record list, low and high word: the lists of a launch lie one after the other, each as long as its region has pixels (a
+// flat positive plateau makes every pixel a record). info: (maximum key, record count) per request, as cellinfo.
+// Pass 1 is gftt_cand_tile / gfttg_cand_tile over ceil(h / 32) x ceil(w / 32) tiles. The tiles of one 32-row band share the band's cache
+// lines, so they should run on one XCD (the measurement above k_gftt_cand); consecutive workgroup ids go round the 8 XCDs, and with more
+// than 8 tile rows blockIdx.x = tile row no longer says which. The launch is (8 * ceil(tiles_y / 8) * tiles_x, requests): its x extent is a
+// multiple of 8, so workgroup (b, r) runs on XCD b % 8 whatever r, and the k = b / 8-th workgroup of XCD x takes tile row x + 8 * (k /
+// tiles_x), column k % tiles_x: row t of every request lands on XCD t % 8. Workgroups past a request's last row leave at once.
+constexpr int GF_T = 1024;        // threads of the selection workgroup
+constexpr int GF_CAP = GFTT_FRAME_ONCHIP;   // records it sorts on chip: 128 KiB of the CU's 160 KiB of LDS as 64-bit keys
+constexpr size_t GF_LDS = (size_t)GF_CAP * 8 + (size_t)(2 * GF_T + 32) * 4;   // keys | survivors of a chunk | its accepted corners | counters
+__device__ __forceinline__ size_t gf_list_off(const int* __restrict__ r) { return (size_t)(unsigned)r[6] | ((size_t)(unsigned)r[7] << 32); }
+__device__ __forceinline__ bool gf_tile_of_block(int cw, int ch, int& tx0, int& ty0) {
+    const int tiles_x = (cw + 31) >> 5, tiles_y = (ch + 31) >> 5;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int band = k / tiles_x;
+    tx0 = (k - band * tiles_x) * 32; ty0 = (xcd + 8 * band) * 32;
+    return xcd + 8 * band < tiles_y;
+}
+__global__ __launch_bounds__(256) void k_gftt_cand_frame(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ recs,
+                                                         float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ info, double quality) {
+    __shared__ float sC[36 * 36 * 3];
+    __shared__ float sE[34 * 34];
+    __shared__ unsigned smax[4];
+    BACKEND_PRIO();
+    const int* __restrict__ r = recs + CELL_STRIDE * blockIdx.y;
+    const int cw = r[2], ch = r[3];
+    int tx0, ty0;
+    if (!gf_tile_of_block(cw, ch, tx0, ty0)) return;
+    const uint8_t* img = level_origin(slots + (size_t)r[4] * L.slot_bytes, L, 0);
+    const size_t off = gf_list_off(r);
+    gftt_cand_tile(img, L.stride[0], r[0], r[1], cw, ch, tx0, ty0, cand_val + off, cand_idx + off, info + 2 * blockIdx.y, quality, sC, sE, smax);
+}
+__global__ __launch_bounds__(256) void k_gftt_cand_general_frame(const uint8_t* __restrict__ slots, PyrLayout L, const int* __restrict__ recs,
+                                                                 float* __restrict__ cand_val, unsigned* __restrict__ cand_idx, unsigned* __restrict__ info,
+                                                                 double quality, GfttExt X, const uint8_t* __restrict__ mask) {
+    extern __shared__ float gfttg_lds[];
+    BACKEND_PRIO();
+    const int* __restrict__ r = recs + CELL_STRIDE * blockIdx.y;
+    const int cw = r[2], ch = r[3];
+    int tx0, ty0;
+    if (!gf_tile_of_block(cw, ch, tx0, ty0)) return;
+    const uint8_t* img = level_origin(slots + (size_t)r[4] * L.slot_bytes, L, 0);
+    const uint8_t* cmask = mask ? mask + (size_t)(unsigned)r[5] : nullptr;
+    const size_t off = gf_list_off(r);
+    gfttg_cand_tile(img, L.stride[0], r[0], r[1], cw, ch, tx0, ty0, X, cmask, cand_val + off, cand_idx + off, info + 2 * blockIdx.y, quality, gfttg_lds);
+}
+
+// Pass 2, ONE launch, one 1024-thread workgroup per request, no host round trip and nothing another workgroup writes is waited for.
+//   1. The records above the threshold become 64-bit keys (value bits << 32 | y << 16 | x): for values > 0 and x < w the key orders like cv's
+//      (value, address y * w + x), and it is unique, so the order of the keys is total and the place a record had in the list (which depends
+//      on the order the tiles of pass 1 finished in) cannot show in the result. Up to GF_CAP keys stay in LDS.
+//   2. The keys are sorted, descending, by a bitonic network whose comparators all point the same way (each merge begins with the mirrored
+//      "flip" step), so a partner index beyond n stands for a key below every real one and is skipped: any n, no padding. A stage with its
+//      barrier costs ~1 us whatever its instruction count (the measurement above k_gftt_pick) - of the 105 stages of 16 k keys the 95 whose
+//      comparators span at most 1024 keys are run by ONE wavefront per 1024-key block, with no workgroup barrier between them: the LDS
+//      operations of a wavefront complete in order. 10 stages keep their barrier.
+//   3. min_dist < 1: the first `cap` keys are cv's answer (its loop accepts every record then). Otherwise the sorted list is walked in
+//      chunks of 1024 records, one per thread: (a) every thread tests its record against all corners accepted from earlier chunks; (b) the
+//      survivors are compacted in order; (c) wavefront 0 takes them 64 at a time - each against the corners accepted earlier in this chunk,
+//      then the wavefront accepts the first live lane and kills the lanes within min_dist of it until none is left. That IS cv's loop
+//      (walk the list in order, accept a record unless an accepted corner is closer than min_dist): a record is dropped only because of a
+//      corner that precedes it in the order and was accepted, and every such corner is seen in (a), in (c)'s test or in (c)'s in-wave loop
+//      before the record's turn. Stated as the fixed point: the accepted set is the set of records that outrank every ACCEPTED record within
+//      min_dist of them; accepting at once every live record that outranks all LIVE records within min_dist of it and killing their
+//      neighbourhoods reaches the same set, because the top live record is always such a record and a kill is only ever made by an accepted
+//      one - the in-wave loop is that step on 64 records. The first `cap` accepted, in rank order, are the answer: the walk stops there.
+//      Accepted corners are kept in the memory of the keys themselves (32-bit slot a lies inside key a / 2, and a <= the number of records
+//      already held in registers), written to the caller's list once at the end - no global store in front of a barrier.
+//   More than GF_CAP records above the threshold (noise at block size 1): the same steps over the key list in HBM (gkeys, as long as the
+//   record list) with a workgroup barrier after every stage - exact, slower, reported in stats[1].
+//   distances: dx * dx + dy * dy is an integer, (double)d2 < min_dist^2 <=> d2 < ceil(min_dist^2); frames up to 32767 x 32767 keep it in an int.
+// out_count[request]: the number of corners, or -1 for a no-limit request (cap + 1 corners were looked for) that has more than cap.
+// stats: (records above the threshold, of those kept in HBM) per request.
+__device__ __forceinline__ void gf_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+// comparator q of a stage whose comparators span 2 << lh keys: (i, i + half), or in a flip stage (i, mirror image of i in its block)
+__device__ __forceinline__ void gf_cmpx(unsigned long long* keys, int n, int q, int lh, bool flip) {
+    const int half = 1 << lh;
+    const int i = ((q >> lh) << (lh + 1)) | (q & (half - 1));
+    const int l = flip ? (i ^ (2 * half - 1)) : (i + half);
+    if (l < n) {
+        const unsigned long long a = keys[i], b = keys[l];
+        if (a < b) { keys[i] = b; keys[l] = a; }
+    }
+}
+template <bool ONCHIP> __device__ __forceinline__ void gf_sort(unsigned long long* keys, int n, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    int ln2 = 1;
+    while ((1 << ln2) < n) ln2++;
+    const int pairs = 1 << (ln2 - 1);
+    for (int lk = 1; lk <= ln2; lk++) {              // merges of blocks of 2^lk keys: flip (lh = lk - 1), then lh = lk - 2 .. 0
+        int lh = lk - 1;
+        if (ONCHIP) {
+            for (; lh >= 10; lh--) {                 // comparators that cross the 1024-key blocks
+                for (int q = tid; q < pairs; q += GF_T) gf_cmpx(keys, n, q, lh, lh == lk - 1);
+                __syncthreads();
+            }
+            for (int b = wave; b * 1024 < n; b += GF_T / 64) {   // block b, 512 comparators a stage, is wavefront b % 16's in every such stage
+                for (int l2 = lh; l2 >= 0; l2--) {
+#pragma unroll
+                    for (int e = 0; e < 8; e++) gf_cmpx(keys, n, b * 512 + e * 64 + lane, l2, l2 == lk - 1);
+                    gf_wave_sync();
+                }
+            }
+            if (lk >= 10 || lk == ln2) __syncthreads();   // (merges below 1024 keys stay inside the blocks: nothing to wait for)
+        } else {
+            for (; lh >= 0; lh--) {
+                for (int q = tid; q < pairs; q += GF_T) gf_cmpx(keys, n, q, lh, lh == lk - 1);
+                __syncthreads();
+            }
+        }
+    }
+}
+// step 3 for min_dist >= 1; returns the number of accepted corners (<= limit), their (y << 16) | x in ((unsigned*)keys)[0 .. ), visible to all
+__device__ __forceinline__ int gf_walk(unsigned long long* keys, int n, int limit, int md2i, unsigned* s_surv, unsigned* s_new, unsigned* s_w, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    typedef unsigned __attribute__((may_alias)) acc_t;   // (32-bit slots inside the memory of the 64-bit keys)
+    acc_t* acc = (acc_t*)keys;
+    int na = 0;
+    for (int base = 0; base < n && na < limit; base += GF_T) {
+        const int i = base + tid;
+        bool alive = i < n;
+        const unsigned p = alive ? (unsigned)keys[i] : 0u;
+        const int px = (int)(p & 0xffffu), py = (int)(p >> 16);
+        for (int a = 0; a < na; a++) {               // (a) every lane reads the same word
+            const unsigned q = acc[a];
+            const int dx = (int)(q & 0xffffu) - px, dy = (int)(q >> 16) - py;
+            alive = alive && !(dx * dx + dy * dy < md2i);
+        }
+        const unsigned long long bal = __ballot(alive);   // (b)
+        if (lane == 0) s_w[wave] = (unsigned)__popcll(bal);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w2 = 0; w2 < GF_T / 64; w2++) { const int c = (int)s_w[w2]; off += w2 < wave ? c : 0; tot += c; }
+        if (alive) s_surv[off + __popcll(bal & ((1ull << lane) - 1ull))] = p;
+        __syncthreads();
+        if (wave == 0) {                             // (c)
+            int nn = 0;                              // corners accepted in this chunk: s_new[0 .. nn)
+            for (int sub = 0; sub < tot && na + nn < limit; sub += 64) {
+                const bool valid = sub + lane < tot;
+                const unsigned sp = valid ? s_surv[sub + lane] : 0u;
+                const int sx = (int)(sp & 0xffffu), sy = (int)(sp >> 16);
+                bool live = valid;
+                for (int a = 0; a < nn; a++) {
+                    const unsigned q = s_new[a];
+                    const int dx = (int)(q & 0xffffu) - sx, dy = (int)(q >> 16) - sy;
+                    live = live && !(dx * dx + dy * dy < md2i);
+                }
+                unsigned long long lm = __ballot(live);
+                while (lm && na + nn < limit) {
+                    const int j = __builtin_ctzll(lm);
+                    const unsigned pj = (unsigned)__shfl((int)sp, j, 64);
+                    if (lane == 0) { s_new[nn] = pj; acc[na + nn] = pj; }
+                    nn++;
+                    const int dx = (int)(pj & 0xffffu) - sx, dy = (int)(pj >> 16) - sy;
+                    lm &= ~__ballot(dx * dx + dy * dy < md2i);   // (lane j itself: distance 0, min_dist >= 1)
+                }
+                gf_wave_sync();
+            }
+            if (lane == 0) s_w[GF_T / 64] = (unsigned)(na + nn);
+        }
+        __syncthreads();
+        na = (int)s_w[GF_T / 64];
+    }
+    return na;
+}
+
+__global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict__ recs, const float* __restrict__ cand_val, const unsigned* __restrict__ cand_idx,
+                                                          const unsigned* __restrict__ info, unsigned long long* __restrict__ gkeys, int cap, double quality,
+                                                          double min_dist, int unlimited, int* __restrict__ out_xy, int* __restrict__ out_count,
+                                                          int* __restrict__ stats) {
+    extern __shared__ unsigned long long gf_lds[];
+    unsigned long long* lkey = gf_lds;                    // [GF_CAP]
+    unsigned* s_surv = (unsigned*)(lkey + GF_CAP);        // [GF_T]
+    unsigned* s_new = s_surv + GF_T;                      // [GF_T]
+    unsigned* s_w = s_new + GF_T;                         // [32]: per-wavefront counts, [16] accepted so far, [20] keys
+    BACKEND_PRIO();
+    const int req = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int* __restrict__ r = recs + CELL_STRIDE * req;
+    const int cw = r[2];
+    const size_t off = gf_list_off(r);
+    const float* __restrict__ cv = cand_val + off;
+    const unsigned* __restrict__ ci = cand_idx + off;
+    unsigned long long* gk = gkeys + off;
+    const int nraw = (int)info[2 * req + 1];
+    const float thr = (float)((double)f32_unkey(info[2 * req]) * quality);
+    if (tid == 0) s_w[20] = 0;
+    __syncthreads();
+    for (int base = 0; base < nraw; base += GF_T) {   // step 1; the place of a key among the keys is whatever the atomic gives: the sort follows
+        const int i = base + tid;
+        float v = 0.f; unsigned px = 0;
+        if (i < nraw) { v = cv[i]; px = ci[i]; }
+        const bool keep = i < nraw && v > thr;
+        const unsigned long long bal = __ballot(keep);
+        if (bal) {
+            unsigned b0 = 0;
+            if (lane == 0) b0 = atomicAdd(&s_w[20], (unsigned)__popcll(bal));
+            b0 = __shfl(b0, 0, 64);
+            if (keep) {
+                const unsigned slot = b0 + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+                const int y = (int)px / cw;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | ((unsigned)y << 16) | (unsigned)((int)px - y * cw);
+                if (slot < (unsigned)GF_CAP) lkey[slot] = key; else gk[slot] = key;
+            }
+        }
+    }
+    __syncthreads();
+    const int n = (int)s_w[20];
+    const bool use_dist = min_dist >= 1.0;
+    const double md2 = min_dist * min_dist;
+    const int md2i = (int)(md2 < 2.0e9 ? ceil(md2) : 2.0e9);
+    const int limit = unlimited ? cap + 1 : cap;
+    int na;
+    if (n <= GF_CAP) {
+        if (n > 1) gf_sort<true>(lkey, n, tid);
+        na = use_dist ? gf_walk(lkey, n, limit, md2i, s_surv, s_new, s_w, tid) : (n < limit ? n : limit);
+    } else {
+        for (int i = tid; i < GF_CAP; i += GF_T) gk[i] = lkey[i];
+        __syncthreads();
+        gf_sort<false>(gk, n, tid);
+        na = use_dist ? gf_walk(gk, n, limit, md2i, s_surv, s_new, s_w, tid) : (n < limit ? n : limit);
+    }
+    const unsigned long long* keys = n <= GF_CAP ? lkey : gk;
+    const bool over = unlimited && na > cap;
+    if (!over)
+        for (int i = tid; i < na; i += GF_T) {
+            typedef unsigned __attribute__((may_alias)) acc_t;
+            const unsigned a = use_dist ? ((const acc_t*)keys)[i] : (unsigned)keys[i];   // (y << 16) | x
+            *(int2*)&out_xy[((size_t)req * cap + i) * 2] = make_int2((int)(a & 0xffffu), (int)(a >> 16));
+        }
+    if (tid == 0) { out_count[req] = over ? -1 : na; stats[2 * req] = n; stats[2 * req + 1] = n > GF_CAP ? n : 0; }
+}
+
+int gftt_frame_grid_x(int w, int h) { const int tx = (w + 31) / 32, ty = (h + 31) / 32; return 8 * ((ty + 7) / 8) * tx; }
+hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_recs, int n_req, int grid_x, int cap, double quality,
+                             double min_dist, int unlimited, const GfttExt* X, const uint8_t* d_mask, float* d_val, unsigned* d_idx, unsigned* d_info,
+                             unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats) {
+    if (!slots || !d_recs || !d_val || !d_idx || !d_info || !d_keys || !d_out_xy || !d_out_count || !d_stats || n_req < 1 || n_req > 65535 || grid_x < 8 || (grid_x & 7) ||
+        cap < 1 || cap > GF_CAP || (X && !gftt_ext_ok(*X)) || (d_mask && !X)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_info, 0, 2 * sizeof(unsigned) * n_req, s);
+    if (e != hipSuccess) return e;
+    { ProfScope ps(K_GFTT_CAND, s);
+    if (X) hipLaunchKernelGGL(k_gftt_cand_general_frame, dim3(grid_x, n_req), dim3(256), gfttg_lds_bytes(X->bs), s, slots, L, d_recs, d_val, d_idx, d_info, quality, *X, d_mask);
+    else hipLaunchKernelGGL(k_gftt_cand_frame, dim3(grid_x, n_req), dim3(256), 0, s, slots, L, d_recs, d_val, d_idx, d_info, quality); }
+    ProfScope ps2(K_GFTT_PICK, s);
+    hipLaunchKernelGGL(k_gftt_pick_frame, dim3(n_req), dim3(GF_T), GF_LDS, s, d_recs, d_val, d_idx, d_info, d_keys, cap, quality, min_dist, unlimited, d_out_xy,
+                       d_out_count, d_stats);
     return hipGetLastError();
 }
 
@@ -2050,7 +2317,8 @@ hipError_t launch_shitomasi(hipStream_t s, const uint8_t* slots, const PyrLayout
 // Kernels that need more than the default 64 KB of dynamic LDS opt in per DEVICE (function attributes are per device in HIP):
 // called by pmv_ctx_create after hipSetDevice, so a second context on another GPU of the same process is set up as well.
 hipError_t frontend_prepare_device() {
-    return hipFuncSetAttribute((const void*)k_st_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST_SELECT_SHM);
+    if (hipError_t e = hipFuncSetAttribute((const void*)k_st_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST_SELECT_SHM)) return e;
+    return hipFuncSetAttribute((const void*)k_gftt_pick_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS);
 }
 
 }  // namespace pmv

@@ -85,6 +85,17 @@ struct pmv_ctx {
     // bytes under the cells cross the bus. MAX_CELLS * CELL_PIX bytes each, made by the first extended call with a mask.
     pmv::Buf<uint8_t> h_gmask{pmv::MEM_PINNED}, d_gmask;
     int gftt_general = 0;                // pmv_debug_gftt_general
+    // pmv_detect_gftt_frame, made by the first call (a context that never makes one pays nothing): the request's block in mapped pinned
+    // memory (gftt_frame_block at one request of PMV_GFTT_FRAME_MAX_CORNERS corners), the region's packed mask (pinned mirror and HBM copy)
+    // and, in HBM, the record list (value, pixel index), the key list of the selection's slower path and the (maximum, count) pair - the
+    // lists sized for max_w x max_h, since a flat positive plateau makes every pixel a record
+    pmv::Buf<uint8_t> h_gfr{pmv::MEM_MAPPED}, h_gfr_mask{pmv::MEM_PINNED}, d_gfr_mask;
+    pmv::Buf<float> d_gfr_val;
+    pmv::Buf<unsigned> d_gfr_idx, d_gfr_info;
+    pmv::Buf<unsigned long long> d_gfr_keys;
+    // pmv_debug_gftt_frame_stats: frame calls served by the single entry point | session rounds with a frame request | launch pairs made for
+    // them | records above the threshold in the last request served | of those kept off-chip
+    std::atomic<long long> gftt_frame_stats[5];
     // pmv_corner_subpix, made by the first call (a context that never makes one pays nothing): one mapped pinned block [point records nt x 16 |
     // positions 2 nt floats | updates nt bytes | flags nt bytes], nt = max_tracks, and the weight table in HBM with the window and (effective)
     // zero zone it was computed for - a caller keeps its parameters, so the table crosses the bus once
@@ -190,6 +201,12 @@ void pack_cells(int* dst, const int* cells, int n_cells, int slot);
 int gftt_ex_check(pmv_ctx* ctx, const char* who, const pmv_gftt_params* p, const int* out_xy, const int* out_count);
 int gftt_mask_check(pmv_ctx* ctx, const char* who, int slot, const uint8_t* mask, int mask_stride);
 size_t gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* cells, int n_cells, const uint8_t* mask, int mask_stride);
+// pmv_detect_gftt_frame / pmv_batch_detect_gftt_frame: every check of the contract, in its order (`who` names the call in the messages). On
+// success roi4 holds the region (the whole frame for a null roi4_or_null) and *cap the capacity of the call's corner list.
+int gftt_frame_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask,
+                     int mask_stride, const int* out_xy, int out_cap, const int* out_count, int* roi4, int* cap);
+// a frame request's device record at list entry `list_off`; with a mask its region's bytes go behind byte `pos` of dst (returns the new end)
+size_t gftt_frame_record(int* rec, const int* roi4, int slot, size_t list_off, uint8_t* dst, size_t pos, const uint8_t* mask, int mask_stride);
 // pmv_corner_subpix / pmv_batch_corner_subpix: every check of the contract, in its order (`who` names the call in the messages)
 int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p);
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
@@ -231,6 +248,11 @@ inline SubpixBlock subpix_block(Carve& c, size_t cap) { return {c.take<SubpixRec
 // back results of `cap` forward-backward tracks: [positions | err | status]
 struct LkBackBlock { Carved<float> xy, err; Carved<uint8_t> status; };
 inline LkBackBlock lk_back_block(Carve& c, size_t cap) { return {c.take<float>(2 * cap), c.take<float>(cap), c.take<uint8_t>(cap)}; }
+// block of a launch of n_req frame requests of `cap` corners each: [request records | counts | (records, off-chip) pairs | corner lists]
+struct GfttFrameBlock { Carved<int> rec, count, stats, xy; };
+inline GfttFrameBlock gftt_frame_block(Carve& c, size_t n_req, size_t cap) {
+    return {c.take<int>(n_req * CELL_STRIDE), c.take<int>(n_req), c.take<int>(2 * n_req), c.take<int>(2 * n_req * cap, 16)};
+}
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
 }

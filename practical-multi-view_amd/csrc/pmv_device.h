@@ -275,6 +275,18 @@ hipError_t launch_gftt_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& 
                           double min_dist, int unlimited, const GfttExt& X, const uint8_t* d_mask, float* d_eig, unsigned* d_cellmax, int* d_out_xy,
                           int* d_out_count, int* d_flags, unsigned* d_spill);
 hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_cells, int n_cells, const GfttExt& X, float* d_eig);
+// pmv_detect_gftt_frame: k_gftt_cand_frame (X null) or k_gftt_cand_general_frame, then k_gftt_pick_frame, over n_req request records in
+// device-visible memory: (x0, y0, w, h, slot, byte offset of the region's packed mask in d_mask, first entry of the request's record list as
+// low and high word). d_val / d_idx / d_keys: the record lists and the key lists of the slower path, each as long as the regions have
+// pixels; d_info: 2 words per request. grid_x = the largest gftt_frame_grid_x(w, h) among the requests. Outputs per request: cap (x, y)
+// pairs, a count (-1: a no-limit request with more than cap corners) and (records above the threshold, of those kept in HBM). Booked under
+// K_GFTT_CAND and K_GFTT_PICK. The packing (y << 16) | x and the int distances need w, h <= GFTT_FRAME_MAX_SIDE.
+constexpr int GFTT_FRAME_MAX_SIDE = 32767;
+int gftt_frame_grid_x(int w, int h);
+constexpr int GFTT_FRAME_ONCHIP = 16384;   // records the selection kernel sorts on chip (= PMV_GFTT_FRAME_MAX_CORNERS, capi.hip)
+hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_recs, int n_req, int grid_x, int cap, double quality,
+                             double min_dist, int unlimited, const GfttExt* X, const uint8_t* d_mask, float* d_val, unsigned* d_idx, unsigned* d_info,
+                             unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats);
 
 // ---- corner sub-pixel refinement (frontend_subpix.hip) -----------------------------------------------------------
 // pmv_corner_subpix / pmv_batch_corner_subpix: one point of a launch names its frame slot and, in the table form, its entry of the geometry
