@@ -764,9 +764,10 @@ __global__ __launch_bounds__(BA_T) void k_ba_lm_batch(const BAArgs* __restrict__
 // one CU moves only ~10 B/clk and an FP64 dependency chain costs ~18 clk/op, so a single workgroup is bound by its own
 // bandwidth and latency. All decisions stay on the device: the host enqueues a fixed chain of launches
 //     E (accept/reject of the previous step + r, J at the new point)  ->  C|P (camera blocks on MFMA | point blocks)  ->
-//     G (Schur contraction on MFMA, one wavefront per tile x K-slice)  ->  S (reduced system, Cholesky)  ->  B (back-
-//     substitution, candidate, model-cost and candidate-cost terms)
-// per LM iteration; every kernel reads the device-side state and returns at once when the solve has terminated. Kernel
+//     G (Schur contraction on MFMA, one wavefront per tile x K-slice)  ->  S|B (reduced system and Cholesky, redundantly in
+//     every block, then back-substitution, candidate, model-cost and candidate-cost terms)
+// per LM iteration (single chain, from the second iteration on, small problems: C|P and G are one launch, k_bam_pointgemm; the batched
+// chain k_bamB_* runs S and B as two launches); every kernel reads the device-side state and returns at once when the solve has terminated. Kernel
 // boundaries are the only grid-wide synchronisation (no cooperative launch, no spinning), all sums have a fixed order.
 // The state is double-buffered so that E can evaluate the decision redundantly in every block while block 0 publishes it.
 // =========================================================================================================================
@@ -917,11 +918,142 @@ __device__ inline void bam_cam_role(const BAArgs& A, const BAGState& st, int c, 
     }
 }
 
+constexpr int BM_OB = 8;    // observations of a point handled per register batch
+constexpr int BM_PB = 64;   // points per block
+// One point's block of the normal equations (one thread): E and g from its observations, (first iteration: the Jacobi scale of the point's
+// columns, into sSp3), the LM diagonal, E^-1 (zero when E is not positive definite: returns false). Writes the point's entries of A.scale
+// and A.diag only as `owner`: a point that two K-slice blocks of k_bam_pointgemm both need is computed by both, same expressions, same bits.
+__device__ inline bool bam_point_block(const BAArgs& A, const BAGState& st, const double* __restrict__ Jb, const double* __restrict__ resb, int p,
+                                       bool first, bool owner, double* sSp3, double Ei[9], double gv[3], double& gmax_p) {
+    const int m = 6 * A.nc;
+    const int e0 = A.pobs_start[p], e1 = A.pobs_start[p + 1];
+    double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double sp[3] = {1, 1, 1};
+#pragma unroll
+    for (int k = 0; k < 3; k++) gv[k] = 0;
+    for (int eb = e0; eb < e1; eb += BM_OB) {   // index loads, then value loads, then arithmetic: independent loads in flight
+        int oi[BM_OB];
+#pragma unroll
+        for (int u = 0; u < BM_OB; u++) oi[u] = (eb + u < e1) ? A.pobs_list[eb + u] : -1;
+        double jp[BM_OB][6], rr[BM_OB][2];
+#pragma unroll
+        for (int u = 0; u < BM_OB; u++) {
+            if (oi[u] >= 0) {
+                const double* Jp = Jb + (size_t)oi[u] * 18 + 12;
+#pragma unroll
+                for (int k = 0; k < 6; k++) jp[u][k] = Jp[k];
+                rr[u][0] = resb[2 * oi[u]]; rr[u][1] = resb[2 * oi[u] + 1];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; k++) jp[u][k] = 0;
+                rr[u][0] = rr[u][1] = 0;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < BM_OB; u++) {
+            if (oi[u] >= 0) {
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+#pragma unroll
+                    for (int b = 0; b < 3; b++) E[a * 3 + b] += jp[u][a] * jp[u][b] + jp[u][3 + a] * jp[u][3 + b];
+                    gv[a] += jp[u][a] * rr[u][0] + jp[u][3 + a] * rr[u][1];
+                }
+            }
+        }
+    }
+    if (first) {
+        // Jacobi scaling of the point's columns: their squared norms are the diagonal of the unscaled E; E and g of the
+        // scaled problem follow by scaling (the Jacobian rows themselves are rescaled by the per-observation pass below)
+#pragma unroll
+        for (int k = 0; k < 3; k++) { sp[k] = 1.0 / (1.0 + sqrt(E[k * 3 + k])); if (owner) A.scale[m + 3 * p + k] = sp[k]; sSp3[k] = sp[k]; }
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+#pragma unroll
+            for (int b = 0; b < 3; b++) E[a * 3 + b] = E[a * 3 + b] * sp[a] * sp[b];
+            gv[a] = gv[a] * sp[a];
+        }
+    }
+    const double radius = st.radius;
+    const bool reuse = st.reuse_diag != 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        double dg;
+        if (!reuse) { dg = fmin(fmax(E[a * 3 + a], 1e-6), 1e32); if (owner) A.diag[m + 3 * p + a] = dg; }
+        else dg = A.diag[m + 3 * p + a];
+        E[a * 3 + a] += dg / radius;
+        gmax_p = fmax(gmax_p, fabs(gv[a] / (first ? sp[a] : A.scale[m + 3 * p + a])));
+    }
+    double L[9];
+    bool ok = true;
+    double r0 = 0, r1 = 0, r2 = 0;   // reciprocals of the diagonal of L (rsqrt + Newton: no division on the chain)
+    {
+        double d = E[0];
+        ok = ok && (d > 0.0); r0 = rsqrt_nr(ok ? d : 1.0);
+        L[3] = E[3] * r0; L[6] = E[6] * r0;
+        d = E[4] - L[3] * L[3];
+        ok = ok && (d > 0.0); r1 = rsqrt_nr(ok ? d : 1.0);
+        L[7] = (E[7] - L[6] * L[3]) * r1;
+        d = E[8] - L[6] * L[6] - L[7] * L[7];
+        ok = ok && (d > 0.0); r2 = rsqrt_nr(ok ? d : 1.0);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) Ei[k] = 0;
+    if (ok) {
+#pragma unroll
+        for (int cI = 0; cI < 3; cI++) {
+            double q0 = (cI == 0) ? 1.0 : 0.0, q1 = (cI == 1) ? 1.0 : 0.0, q2 = (cI == 2) ? 1.0 : 0.0;
+            q0 = q0 * r0;
+            q1 = (q1 - L[3] * q0) * r1;
+            q2 = (q2 - L[6] * q0 - L[7] * q1) * r2;
+            q2 = q2 * r2;
+            q1 = (q1 - L[7] * q2) * r1;
+            q0 = (q0 - L[6] * q2 - L[3] * q1) * r0;
+            Ei[0 * 3 + cI] = q0; Ei[1 * 3 + cI] = q1; Ei[2 * 3 + cI] = q2;
+        }
+    }
+    return ok;
+}
+
+// One observation's 6x3 blocks W = Jc^T Jp (with the later observations of the same (point, camera) folded in when rec.w == 1) and
+// Y = W E^-1 of its point (Ei: 9 doubles in LDS).
+__device__ inline void bam_obs_wy(const BAArgs& A, const double* __restrict__ Jb, int e, const int4 rec, const double* Ei, double w[18], double y[18]) {
+    const int i = rec.x, c = rec.y, pp = rec.z;
+    const double* Jr = Jb + (size_t)i * 18;
+    double jc[12], jp[6];
+#pragma unroll
+    for (int k = 0; k < 12; k++) jc[k] = Jr[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) jp[k] = Jr[12 + k];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int b = 0; b < 3; b++) w[a * 3 + b] = jc[a] * jp[b] + jc[6 + a] * jp[3 + b];
+    }
+    if (rec.w == 1) {
+        for (int e2 = e + 1; e2 < A.pobs_start[pp + 1]; e2++) {
+            const int i2 = A.pobs_list[e2];
+            if (A.cam_idx[i2] != c) continue;
+            const double* J2 = Jb + (size_t)i2 * 18;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+#pragma unroll
+                for (int b = 0; b < 3; b++) w[a * 3 + b] += J2[a] * J2[12 + b] + J2[6 + a] * J2[15 + b];
+            }
+        }
+    }
+    double ei[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) ei[k] = Ei[k];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int b = 0; b < 3; b++) y[a * 3 + b] = w[a * 3] * ei[0 * 3 + b] + w[a * 3 + 1] * ei[1 * 3 + b] + w[a * 3 + 2] * ei[2 * 3 + b];
+    }
+}
+
 // P role: one block per BM_PB points. Phase 1, one thread per point: (first iteration: Jacobi scale of the point and
 // scaling of the Jacobian rows of its observations), E, g, LM diagonal, E^-1 (LDS + global). Phase 2, one thread per
 // observation of the block's points: the observation's 6x3 blocks of Wt and Yt = W E^-1. Gradient-max partial per block.
-constexpr int BM_OB = 8;    // observations of a point handled per register batch
-constexpr int BM_PB = 64;   // points per block
 __device__ inline void bam_point_role(const BAArgs& A, const BAGState& st, int* __restrict__ chol_flag, int pb,
                                       double* __restrict__ part_gmax, double* sEi /* [BM_PB][9] */) {
     if (st.done) return;
@@ -936,89 +1068,9 @@ __device__ inline void bam_point_role(const BAArgs& A, const BAGState& st, int* 
     double* sSp = sEi + BM_PB * 9;   // [BM_PB][3] point scales (first iteration)
     double gmax_p = 0;
     if (tid < BM_PB && p < p1) {
-        const int e0 = A.pobs_start[p], e1 = A.pobs_start[p + 1];
-        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gv[3] = {0, 0, 0};
-        for (int eb = e0; eb < e1; eb += BM_OB) {   // index loads, then value loads, then arithmetic: independent loads in flight
-            int oi[BM_OB];
-#pragma unroll
-            for (int u = 0; u < BM_OB; u++) oi[u] = (eb + u < e1) ? A.pobs_list[eb + u] : -1;
-            double jp[BM_OB][6], rr[BM_OB][2];
-#pragma unroll
-            for (int u = 0; u < BM_OB; u++) {
-                if (oi[u] >= 0) {
-                    const double* Jp = Jb + (size_t)oi[u] * 18 + 12;
-#pragma unroll
-                    for (int k = 0; k < 6; k++) jp[u][k] = Jp[k];
-                    rr[u][0] = resb[2 * oi[u]]; rr[u][1] = resb[2 * oi[u] + 1];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 6; k++) jp[u][k] = 0;
-                    rr[u][0] = rr[u][1] = 0;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < BM_OB; u++) {
-                if (oi[u] >= 0) {
-#pragma unroll
-                    for (int a = 0; a < 3; a++) {
-#pragma unroll
-                        for (int b = 0; b < 3; b++) E[a * 3 + b] += jp[u][a] * jp[u][b] + jp[u][3 + a] * jp[u][3 + b];
-                        gv[a] += jp[u][a] * rr[u][0] + jp[u][3 + a] * rr[u][1];
-                    }
-                }
-            }
-        }
-        if (st.first) {
-            // Jacobi scaling of the point's columns: their squared norms are the diagonal of the unscaled E; E and g of the
-            // scaled problem follow by scaling (the Jacobian rows themselves are rescaled by the per-observation pass below)
-            double sp[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) { sp[k] = 1.0 / (1.0 + sqrt(E[k * 3 + k])); A.scale[m + 3 * p + k] = sp[k]; sSp[tid * 3 + k] = sp[k]; }
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-#pragma unroll
-                for (int b = 0; b < 3; b++) E[a * 3 + b] = E[a * 3 + b] * sp[a] * sp[b];
-                gv[a] = gv[a] * sp[a];
-            }
-        }
-        const double radius = st.radius;
-        const bool reuse = st.reuse_diag != 0;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            double dg;
-            if (!reuse) { dg = fmin(fmax(E[a * 3 + a], 1e-6), 1e32); A.diag[m + 3 * p + a] = dg; }
-            else dg = A.diag[m + 3 * p + a];
-            E[a * 3 + a] += dg / radius;
-            gmax_p = fmax(gmax_p, fabs(gv[a] / A.scale[m + 3 * p + a]));
-        }
-        double L[9];
-        bool ok = true;
-        double r0 = 0, r1 = 0, r2 = 0;   // reciprocals of the diagonal of L (rsqrt + Newton: no division on the chain)
-        {
-            double d = E[0];
-            ok = ok && (d > 0.0); r0 = rsqrt_nr(ok ? d : 1.0);
-            L[3] = E[3] * r0; L[6] = E[6] * r0;
-            d = E[4] - L[3] * L[3];
-            ok = ok && (d > 0.0); r1 = rsqrt_nr(ok ? d : 1.0);
-            L[7] = (E[7] - L[6] * L[3]) * r1;
-            d = E[8] - L[6] * L[6] - L[7] * L[7];
-            ok = ok && (d > 0.0); r2 = rsqrt_nr(ok ? d : 1.0);
-        }
-        double Ei[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (!ok) atomicOr(chol_flag, 1);   // the step is invalid: the solve kernel stops, nothing below is used
-        else {
-#pragma unroll
-            for (int cI = 0; cI < 3; cI++) {
-                double q0 = (cI == 0) ? 1.0 : 0.0, q1 = (cI == 1) ? 1.0 : 0.0, q2 = (cI == 2) ? 1.0 : 0.0;
-                q0 = q0 * r0;
-                q1 = (q1 - L[3] * q0) * r1;
-                q2 = (q2 - L[6] * q0 - L[7] * q1) * r2;
-                q2 = q2 * r2;
-                q1 = (q1 - L[7] * q2) * r1;
-                q0 = (q0 - L[6] * q2 - L[3] * q1) * r0;
-                Ei[0 * 3 + cI] = q0; Ei[1 * 3 + cI] = q1; Ei[2 * 3 + cI] = q2;
-            }
-        }
+        double Ei[9], gv[3];
+        if (!bam_point_block(A, st, Jb, resb, p, st.first != 0, true, sSp + tid * 3, Ei, gv, gmax_p))
+            atomicOr(chol_flag, 1);   // the step is invalid: the solve kernel stops, nothing below is used
 #pragma unroll
         for (int k = 0; k < 9; k++) { A.Einv[(size_t)p * 9 + k] = Ei[k]; sEi[tid * 9 + k] = Ei[k]; }
 #pragma unroll
@@ -1048,46 +1100,16 @@ __device__ inline void bam_point_role(const BAArgs& A, const BAGState& st, int* 
     // ---- phase 2: K-columns of cameras that do not see a point stay zero (Yt / Wt are cleared once per solve)
     for (int e = eb0 + tid; e < eb1; e += BM_T) {
         const int4 rec = A.erec[e];   // (observation, camera, point, dup flag) in one load
-        const int flag = rec.w;
-        if (flag == 2) continue;   // a later observation of the same (point, camera): folded into the first one
-        const int i = rec.x, c = rec.y, pp = rec.z;
-        const double* Jr = Jb + (size_t)i * 18;
-        double jc[12], jp[6];
-#pragma unroll
-        for (int k = 0; k < 12; k++) jc[k] = Jr[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) jp[k] = Jr[12 + k];
-        double w[18];
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-#pragma unroll
-            for (int b = 0; b < 3; b++) w[a * 3 + b] = jc[a] * jp[b] + jc[6 + a] * jp[3 + b];
-        }
-        if (flag == 1) {
-            for (int e2 = e + 1; e2 < A.pobs_start[pp + 1]; e2++) {
-                const int i2 = A.pobs_list[e2];
-                if (A.cam_idx[i2] != c) continue;
-                const double* J2 = Jb + (size_t)i2 * 18;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int b = 0; b < 3; b++) w[a * 3 + b] += J2[a] * J2[12 + b] + J2[6 + a] * J2[15 + b];
-                }
-            }
-        }
-        const double* Ei = sEi + (pp - p0) * 9;
-        double ei[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) ei[k] = Ei[k];
+        if (rec.w == 2) continue;     // a later observation of the same (point, camera): folded into the first one
+        const int c = rec.y, pp = rec.z;
+        double w[18], y[18];
+        bam_obs_wy(A, Jb, e, rec, sEi + (pp - p0) * 9, w, y);
 #pragma unroll
         for (int a = 0; a < 6; a++) {
             double* wp = &A.Wd[(size_t)(6 * c + a) * krows + 3 * pp];
             double* yp = &A.Yd[(size_t)(6 * c + a) * krows + 3 * pp];
 #pragma unroll
-            for (int b = 0; b < 3; b++) {
-                wp[b] = w[a * 3 + b];
-                yp[b] = w[a * 3] * ei[0 * 3 + b] + w[a * 3 + 1] * ei[1 * 3 + b] + w[a * 3 + 2] * ei[2 * 3 + b];
-            }
+            for (int b = 0; b < 3; b++) { wp[b] = w[a * 3 + b]; yp[b] = y[a * 3 + b]; }
         }
     }
     PSTAMP(7);
@@ -1122,6 +1144,144 @@ __global__ __launch_bounds__(BM_T) void k_bam_campoint(BAArgs A, const BAGState*
     bam_campoint_role(A, st_in, st_out, decide != 0, part4, nbp, chol_flag, cam_blocks, Ublk, rhsblk, part_gmax, blockIdx.x, swork);
 }
 
+// One wavefront's 16x16 tile of Y^T [W | g] over nk blocks of 16 k: pa / pb = the lane's row of the K-contiguous operands (global memory or
+// LDS, 16-byte aligned) at its first k (+ 4 * (lane >> 4)). In MFMA q of a block, lane group g supplies k = 4 g + q for both operands; the
+// blocks go in ascending k, four at a time with all loads first. This is THE order of the Schur sum: every form of the chain uses it.
+__device__ inline v4d ld_v4d(const double* p) {
+    const double2 lo = *(const double2*)p, hi = *(const double2*)(p + 2);
+    return v4d{lo.x, lo.y, hi.x, hi.y};
+}
+__device__ inline v4d schur_tile_mfma(const double* pa, const double* pb, int nk_) {
+    v4d acc = {0, 0, 0, 0};
+    const int nk = __builtin_amdgcn_readfirstlane(nk_);
+    int kb = 0;
+    for (; kb + 4 <= nk; kb += 4) {   // 4 K-blocks (64 k): 8 x 32-byte loads per lane in flight, then 16 MFMAs
+        v4d a4[4], b4[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) { a4[u] = ld_v4d(pa + 16 * u); b4[u] = ld_v4d(pb + 16 * u); }
+        pa += 64; pb += 64;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[u][q], b4[u][q], acc, 0, 0, 0);
+        }
+    }
+    for (; kb < nk; kb++) {
+        const v4d a4 = ld_v4d(pa), b4 = ld_v4d(pb);
+        pa += 16; pb += 16;
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[q], b4[q], acc, 0, 0, 0);
+    }
+    return acc;   // D[row = (lane>>4) + 4*reg][col = lane&15]
+}
+
+// P|G role (k_bam_pointgemm, iterations >= 1 of the single chain): ONE block per K-slice of the Schur product, rows
+// [s kper, min(krows, (s + 1) kper)). The block runs the point phase for every point with a row in its slice, writes the observations' blocks
+// of Yt and [Wt | g] into LDS instead of HBM and multiplies them there: wavefront w takes tile w (tiles_r tiles_c <= 4 = BM_NW) over the
+// block's K range with schur_tile_mfma and stores its raw accumulators to Gpart[s]; the solve adds the slices in the order the G kernel
+// adds them. No block reads what another block of the launch writes. A point whose three rows straddle a slice boundary is computed by
+// both blocks (same expressions, same bits); its global results are written by the slice that owns row 3p.
+// LDS: Yl[ldw][stride] | Wl[ldw][stride] | E^-1 of the slice's points [kper / 3 + 2][9]; stride = kper + 2 doubles: rows 16 B aligned, the 16
+// rows a lane group reads at one k fall into 16 different bank quads.
+__host__ __device__ inline int bam_slice_stride(int kper) { return kper + 2; }
+__host__ __device__ inline int bam_slice_points(int kper) { return kper / 3 + 2; }
+__host__ __device__ inline size_t bam_slice_lds(int ldw, int kper) {
+    return ((size_t)2 * ldw * bam_slice_stride(kper) + (size_t)9 * bam_slice_points(kper)) * sizeof(double);
+}
+__device__ inline void bam_slice_role(const BAArgs& A, const BAGState& st, int* __restrict__ chol_flag, int sl, double* __restrict__ part_gmax,
+                                      double* lds) {
+    __shared__ double red[BM_NW];
+    if (st.done) return;
+    const double* Jb = A.J + (size_t)st.cur * A.nobs * 18;
+    const double* resb = A.res + (size_t)st.cur * A.nobs * 2;
+    const int m = 6 * A.nc, ldw = A.ldw, kper = A.kper, stride = bam_slice_stride(kper);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int k0 = sl * kper, k1 = min(A.krows, k0 + kper);
+    const int p0 = k0 / 3, p1 = min(A.np, (k1 + 2) / 3);   // the points with a row in [k0, k1)
+    double* Yl = lds;
+    double* Wl = Yl + (size_t)ldw * stride;
+    double* sEi = Wl + (size_t)ldw * stride;
+    // K-columns of cameras that do not see a point, the pad rows >= 3 np, Yt's column m and the columns > m are zero
+    for (int i = tid; i < ldw * stride; i += BM_T) { Yl[i] = 0.0; Wl[i] = 0.0; }
+    __syncthreads();
+    // ---- phase 1: one thread per point (at most kper / 3 + 2 <= BM_T)
+    const int p = p0 + tid;
+    double gmax_p = 0;
+    if (p < p1) {
+        const bool owner = 3 * p >= k0;   // (3 p < k1 holds for every point of the slice)
+        double Ei[9], gv[3], g_own = 0;
+        if (!bam_point_block(A, st, Jb, resb, p, false, owner, nullptr, Ei, gv, g_own))
+            *chol_flag = 1;   // the step is invalid (any block may say so: the same value): the solve stops, nothing below is used
+#pragma unroll
+        for (int k = 0; k < 9; k++) sEi[tid * 9 + k] = Ei[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int kr = 3 * p + k - k0;
+            if (kr >= 0 && kr < k1 - k0) Wl[(size_t)m * stride + kr] = gv[k];
+        }
+        if (owner) {
+            gmax_p = g_own;
+#pragma unroll
+            for (int k = 0; k < 9; k++) A.Einv[(size_t)p * 9 + k] = Ei[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) A.gp[(size_t)p * 3 + k] = gv[k];
+        }
+    }
+    gmax_p = wave_max_f64(gmax_p);
+    if (lane == 0) red[wid] = gmax_p;
+    __syncthreads();   // E^-1 in LDS
+    if (tid == 0) part_gmax[sl] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    // ---- phase 2: one thread per observation of the slice's points (a contiguous range of erec)
+    const int eb0 = A.pobs_start[p0], eb1 = A.pobs_start[p1];
+    for (int e = eb0 + tid; e < eb1; e += BM_T) {
+        const int4 rec = A.erec[e];
+        if (rec.w == 2) continue;
+        const int c = rec.y, pp = rec.z;
+        double w[18], y[18];
+        bam_obs_wy(A, Jb, e, rec, sEi + (pp - p0) * 9, w, y);
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            const int kr = 3 * pp + b - k0;
+            if (kr < 0 || kr >= k1 - k0) continue;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+                Wl[(size_t)(6 * c + a) * stride + kr] = w[a * 3 + b];
+                Yl[(size_t)(6 * c + a) * stride + kr] = y[a * 3 + b];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 3: wavefront = tile
+    const int tc = A.tiles_c;
+    if (wid < A.tiles_r * tc) {
+        const int ti = wid / tc, tj = wid - ti * tc;
+        const double* pa = Yl + (size_t)(ti * 16 + (lane & 15)) * stride + 4 * (lane >> 4);
+        const double* pb = Wl + (size_t)(tj * 16 + (lane & 15)) * stride + 4 * (lane >> 4);
+        const v4d acc = schur_tile_mfma(pa, pb, (k1 - k0) / 16);
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            A.Gpart[((size_t)sl * A.gp_rows + ti * 16 + (lane >> 4) + 4 * r) * ldw + tj * 16 + (lane & 15)] = acc[r];
+    }
+}
+
+// C | P|G kernel of iterations >= 1: blocks [0, nc): C role; blocks [nc, nc + kslices): P|G role. Every block takes the decision on the
+// previous step itself, as in k_bam_campoint.
+__global__ __launch_bounds__(BM_T) void k_bam_pointgemm(BAArgs A, const BAGState* st_in, BAGState* st_out, const double* part4, int nbp,
+                                                        int* chol_flag, double* Ublk, double* rhsblk, double* part_gmax) { BACKEND_PRIO();
+    extern __shared__ __attribute__((aligned(16))) double dyn[];   // max(bam_slice_lds, BM_WORK doubles): a slice's tiles or a camera's accumulators
+    __shared__ BAGState ss;
+    __shared__ double ssc[8];
+    const int bid = blockIdx.x;
+    if (threadIdx.x == 0) {
+        ss = *st_in;
+        if (!ss.done) bam_decide(ss, part4, nbp);
+        if (bid == 0) *st_out = ss;
+    }
+    __syncthreads();
+    if (bid < A.nc) bam_cam_role(A, ss, bid, Ublk, rhsblk, dyn, ssc);
+    else bam_slice_role(A, ss, chol_flag, bid - A.nc, part_gmax, dyn);
+}
+
 // G: Schur contraction  G = Yt^T [Wt | g]  on FP64 MFMA: BG_H blocks per 16x16 tile, one wavefront per K-slice, the slices
 // of a block are summed in slice order through LDS; the solve kernel adds the BG_H partials (fixed summation order).
 constexpr int BG_W = 4, BG_H = 2;
@@ -1134,28 +1294,9 @@ __device__ inline void bam_gemm_role(const BAArgs& A, const BAGState* st, int bi
     const int ti = tile / tc, tj = tile - ti * tc;
     const int kper = A.kper;   // multiple of 16; BG_H * BG_W * kper >= krows
     const int k0 = min(krows, (half * BG_W + wv) * kper), k1 = min(krows, k0 + kper);
-    v4d acc = {0, 0, 0, 0};
     const double* pa = A.Yd + (size_t)(ti * 16 + (lane & 15)) * krows + 4 * (lane >> 4) + k0;
     const double* pb = A.Wd + (size_t)(tj * 16 + (lane & 15)) * krows + 4 * (lane >> 4) + k0;
-    const int nk = __builtin_amdgcn_readfirstlane((k1 - k0) / 16);
-    int kb = 0;
-    for (; kb + 4 <= nk; kb += 4) {
-        v4d a4[4], b4[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) { a4[u] = *(const v4d*)(pa + 16 * u); b4[u] = *(const v4d*)(pb + 16 * u); }
-        pa += 64; pb += 64;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[u][q], b4[u][q], acc, 0, 0, 0);
-        }
-    }
-    for (; kb < nk; kb++) {
-        const v4d a4 = *(const v4d*)pa, b4 = *(const v4d*)pb;
-        pa += 16; pb += 16;
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[q], b4[q], acc, 0, 0, 0);
-    }
+    const v4d acc = schur_tile_mfma(pa, pb, (k1 - k0) / 16);
 #pragma unroll
     for (int r = 0; r < 4; r++) sacc[(wv * 4 + r) * 64 + lane] = acc[r];
     __syncthreads();
@@ -1178,20 +1319,26 @@ __global__ __launch_bounds__(64 * BG_W) void k_bam_gemm(BAArgs A, const BAGState
 // S: loop-top tests, reduced camera system [S | rhs row] in LDS, right-looking Cholesky with the forward substitution
 // folded in as row m (two barriers per column), backward substitution in registers of wavefront 0 -> step_c; rotation
 // constants of the candidate cameras.
-__device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* __restrict__ chol_flag, const double* __restrict__ part_cost,
-                                      int nbo, const double* __restrict__ part_gmax, int nbp, const double* __restrict__ Ublk,
-                                      const double* __restrict__ rhsblk, double* __restrict__ candrot) {
+// The role reads the state the C|P launch left in st_in and nothing another block of its own launch writes, so any number of
+// blocks may run it side by side on their own LDS and arrive at the same bits; only a `writer` block stores what later
+// launches read (the state to st_out, A.step[0..m), A.diag[0..m), candrot). Returns the block's LDS copy of the state when
+// the step is valid (then S[0..m) holds the camera step and, if given, candrot_l the candidate cameras), else nullptr.
+__device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState* st_in, BAGState* st_out, bool writer,
+                                                 const int* __restrict__ chol_flag, const double* __restrict__ part_cost,
+                                                 int nbo, const double* __restrict__ part_gmax, int nbp, const double* __restrict__ Ublk,
+                                                 const double* __restrict__ rhsblk, double* __restrict__ candrot, double* candrot_l, int gslices) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     __shared__ double red[3 * BM_NW];
-    __shared__ BAGState ss;   // LDS copy of the state: read here, written through to global memory by thread 0
+    __shared__ BAGState ss;   // LDS copy of the state: read and updated here, stored to st_out by thread 0 of a writer block on every way out
     __shared__ int sfail;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int tx = tid & 15, ty = tid >> 4;
     unsigned long long t_prev = __builtin_readcyclecounter();
-#define SSTAMP(k) do { if (A.stamps && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); A.stamps[k] += t_ - t_prev; t_prev = t_; } } while (0)
-    if (tid == 0) { ss = *st; sfail = 0; }
+#define SSTAMP(k) do { if (A.stamps && writer && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); A.stamps[k] += t_ - t_prev; t_prev = t_; } } while (0)
+#define SPUBLISH() do { if (writer && tid == 0) *st_out = ss; } while (0)
+    if (tid == 0) { ss = *st_in; sfail = 0; }
     __syncthreads();
-    if (ss.done) return;
+    if (ss.done) { SPUBLISH(); return nullptr; }
     const int nc = A.nc, m = 6 * nc, n = m + 3 * A.np;
     double* S = dyn; double* dg = dyn + (size_t)(m + 1) * m;   // S: (m+1) x m, row m = right-hand side; dg: 1 / diagonal of L
     const double* x = A.x + (size_t)ss.cur * n;
@@ -1207,10 +1354,10 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
         if (tid == 0) {
             if (ss.first) {   // cost of the starting point (E0); later x_cost is the accepted candidate's cost
                 const double c = (red[BM_NW] + red[BM_NW + 1]) + (red[BM_NW + 2] + red[BM_NW + 3]);
-                ss.x_cost = st->x_cost = c;
-                ss.initial_cost = st->initial_cost = c;
+                ss.x_cost = c;
+                ss.initial_cost = c;
             }
-            ss.gmax = st->gmax = fmax(fmax(red[2 * BM_NW], red[2 * BM_NW + 1]), fmax(red[2 * BM_NW + 2], red[2 * BM_NW + 3]));
+            ss.gmax = fmax(fmax(red[2 * BM_NW], red[2 * BM_NW + 1]), fmax(red[2 * BM_NW + 2], red[2 * BM_NW + 3]));
         }
     }
     if (tid == 0) {
@@ -1218,11 +1365,11 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
         if (ss.iter >= ss.max_iterations) term = 0;
         else if (ss.gmax >= 0 && ss.gmax <= 1e-10) term = 2;
         else if (ss.radius < 1e-32) term = 4;
-        if (term >= 0) { ss.done = st->done = 1; ss.termination = st->termination = term; }
-        st->step_valid = 0;
+        if (term >= 0) { ss.done = 1; ss.termination = term; }
+        ss.step_valid = 0;
     }
     __syncthreads();
-    if (ss.done) return;
+    if (ss.done) { SPUBLISH(); return nullptr; }
     SSTAMP(16);
     // ---- S = blockdiag(U_c) + D2_c - Yt^T Wt (lower triangle), row m = rhs_c - Yt^T g
     {
@@ -1235,12 +1382,29 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
                 else v = rhsblk[b];
                 // row m (the right-hand side) takes column m of G: (Yt^T g)[b]
                 const size_t gi = (a < m) ? (size_t)a * A.ldw + b : (size_t)b * A.ldw + m;
-                double g = A.Gpart[gi];
+                double g;
+                if (gslices) {   // Gpart = one raw partial per K-slice (k_bam_pointgemm): the G kernel's order, BG_W slices per half, slice by slice
+                    double hsum[BG_H];
 #pragma unroll
-                for (int h = 1; h < BG_H; h++) g += A.Gpart[(size_t)h * A.gp_rows * A.ldw + gi];
+                    for (int h = 0; h < BG_H; h++) {
+#pragma unroll
+                        for (int w = 0; w < BG_W; w++) {
+                            const int sl = h * BG_W + w;
+                            const double v = sl < gslices ? A.Gpart[(size_t)sl * A.gp_rows * A.ldw + gi] : 0.0;   // an empty slice adds +0.0, as its idle wavefront did
+                            hsum[h] = w == 0 ? v : hsum[h] + v;
+                        }
+                    }
+                    g = hsum[0];
+#pragma unroll
+                    for (int h = 1; h < BG_H; h++) g += hsum[h];
+                } else {         // Gpart = one partial per half (k_bam_gemm)
+                    g = A.Gpart[gi];
+#pragma unroll
+                    for (int h = 1; h < BG_H; h++) g += A.Gpart[(size_t)h * A.gp_rows * A.ldw + gi];
+                }
                 if (a == b) {
                     double d2;
-                    if (!reuse) { d2 = fmin(fmax(v, 1e-6), 1e32); A.diag[a] = d2; }
+                    if (!reuse) { d2 = fmin(fmax(v, 1e-6), 1e32); if (writer) A.diag[a] = d2; }
                     else d2 = A.diag[a];
                     v += d2 / radius;
                 }
@@ -1249,7 +1413,7 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
         }
     }
     __syncthreads();
-    if (*chol_flag) return;   // a point block was not positive definite: invalid step (step_valid stays 0)
+    if (*chol_flag) { SPUBLISH(); return nullptr; }   // a point block was not positive definite: invalid step (step_valid stays 0)
     SSTAMP(17);
     // Blocked right-looking Cholesky, block = one camera (6 columns). Per block: (a) one thread factors the 6x6 diagonal
     // block in registers (the only serial chain: 6 x sqrt + reciprocal), (b) one thread per row below solves its 6 entries
@@ -1333,7 +1497,7 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
         }
         __syncthreads();
     }
-    if (sfail) return;
+    if (sfail) { SPUBLISH(); return nullptr; }
     SSTAMP(18);
     if (wid == 0) {
         // L^T x = y by camera blocks from the last one up, in wavefront 0 (LDS ordering only, no block barrier): every lane
@@ -1371,7 +1535,7 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
             }
             WAVE_SYNC();
         }
-        for (int k = lane; k < m; k += 64) { const double v = -ys[k]; A.step[k] = v; S[k] = v; }   // the LM step is the negated solution
+        for (int k = lane; k < m; k += 64) { const double v = -ys[k]; if (writer) A.step[k] = v; S[k] = v; }   // the LM step is the negated solution
         WAVE_SYNC();
         SSTAMP(19);
         if (lane < nc) {   // candidate cameras and their rotation constants, once per camera instead of once per observation
@@ -1380,26 +1544,37 @@ __device__ inline void bam_solve_role(const BAArgs& A, BAGState* st, const int* 
             for (int k = 0; k < 6; k++) cx[k] = x[6 * lane + k] + S[6 * lane + k] * A.scale[6 * lane + k];
             CamRot cr;
             cam_rot_setup(cx, cr);
-            double* o = candrot + 16 * lane;
+            const double cv[7] = {cr.ct, cr.st, cr.ti, cr.w0, cr.w1, cr.w2, (double)cr.big};
+            if (writer) {
+                double* o = candrot + 16 * lane;
 #pragma unroll
-            for (int k = 0; k < 6; k++) o[k] = cx[k];
-            o[6] = cr.ct; o[7] = cr.st; o[8] = cr.ti; o[9] = cr.w0; o[10] = cr.w1; o[11] = cr.w2; o[12] = (double)cr.big;
+                for (int k = 0; k < 6; k++) o[k] = cx[k];
+#pragma unroll
+                for (int k = 0; k < 7; k++) o[6 + k] = cv[k];
+            }
+            if (candrot_l) {
+                double* o = candrot_l + 16 * lane;
+#pragma unroll
+                for (int k = 0; k < 6; k++) o[k] = cx[k];
+#pragma unroll
+                for (int k = 0; k < 7; k++) o[6 + k] = cv[k];
+            }
         }
-        if (lane == 0) st->step_valid = 1;
+        if (lane == 0) ss.step_valid = 1;
         SSTAMP(20);
     }
+    __syncthreads();   // the step, the candidate cameras and step_valid of wavefront 0 are in LDS
+    SPUBLISH();
+    return &ss;
+#undef SPUBLISH
 #undef SSTAMP
-}
-
-__global__ __launch_bounds__(BM_T) void k_bam_solve(BAArgs A, BAGState* st, const int* chol_flag, const double* part_cost, int nbo,
-                                                    const double* part_gmax, int nbp, const double* Ublk, const double* rhsblk,
-                                                    double* candrot) { BACKEND_PRIO();
-    bam_solve_role(A, st, chol_flag, part_cost, nbo, part_gmax, nbp, Ublk, rhsblk, candrot);
 }
 
 // B: one block per BM_PB points. Phase A, per observation: Jp^T (Jc y_c); phase B, per point: back-substitution and the
 // candidate point; phase C, per observation: model-cost-change and candidate-cost terms. Partials per block, fixed order.
-__device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, const double* __restrict__ candrot,
+// st, step_c (the camera step, m doubles) and candrot are what the solve left: in global memory after a launch of its own, in
+// the block's LDS when the solve ran in this block (k_bam_solveback).
+__device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, const double* step_c, const double* candrot,
                                         double* __restrict__ tmp3, double* __restrict__ part4, int bid) {
     __shared__ double red[4 * BM_NW];
     __shared__ double sP[BM_PB * 6];   // per point of the block: step (3), candidate point (3)
@@ -1425,7 +1600,7 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
         const double* Jr = Jb + (size_t)i * 18;
         double jy0 = 0, jy1 = 0;   // y_c = -step_c
 #pragma unroll
-        for (int a = 0; a < 6; a++) { const double yc = -A.step[6 * c + a]; jy0 += Jr[a] * yc; jy1 += Jr[6 + a] * yc; }
+        for (int a = 0; a < 6; a++) { const double yc = -step_c[6 * c + a]; jy0 += Jr[a] * yc; jy1 += Jr[6 + a] * yc; }
 #pragma unroll
         for (int a = 0; a < 3; a++) tmp3[(size_t)e * 3 + a] = Jr[12 + a] * jy0 + Jr[15 + a] * jy1;
     }
@@ -1460,7 +1635,7 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
         const double* Jr = Jb + (size_t)i * 18;
         double sc[6], sp[3], xp[3];
 #pragma unroll
-        for (int k = 0; k < 6; k++) sc[k] = A.step[6 * c + k];
+        for (int k = 0; k < 6; k++) sc[k] = step_c[6 * c + k];
 #pragma unroll
         for (int k = 0; k < 3; k++) { sp[k] = sP[pl * 6 + k]; xp[k] = sP[pl * 6 + 3 + k]; }
 #pragma unroll
@@ -1498,7 +1673,7 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
     BSTAMP(12);
     if (bid == 0) {   // camera part of the candidate and of the step norm
         for (int i = tid; i < m; i += BM_T) {
-            const double d = A.step[i] * A.scale[i];
+            const double d = step_c[i] * A.scale[i];
             cand[i] = x[i] + d;
             dn2 += d * d;
             xn2 += x[i] * x[i];
@@ -1517,8 +1692,22 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
 #undef BSTAMP
 }
 
-__global__ __launch_bounds__(BM_T) void k_bam_backsub(BAArgs A, const BAGState* st, const double* candrot, double* tmp3, double* part4) { BACKEND_PRIO();
-    bam_backsub_role(A, st, candrot, tmp3, part4, blockIdx.x);
+// S|B: every back-substitution block first solves the reduced camera system itself, on its own LDS (the redundancy trick of
+// the decision in k_bam_campoint: same inputs of earlier launches, same arithmetic, same bits in every block, nothing to wait
+// for), then continues with its points; the step, the candidate cameras and the state never leave LDS on the way. Block 0
+// publishes them for the launches that follow; the state goes to st_out, not back to st_in, because a block that starts late
+// must still read what the C|P launch wrote.
+// dynamic LDS: [S (m+1) x m | dg m | candrot 16 nc]
+__global__ __launch_bounds__(BM_T) void k_bam_solveback(BAArgs A, const BAGState* st_in, BAGState* st_out, const int* chol_flag,
+                                                        const double* part_cost, int nbo, const double* part_gmax, int ngm,
+                                                        const double* Ublk, const double* rhsblk, double* candrot, double* tmp3,
+                                                        double* part4, int gslices) { BACKEND_PRIO();
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    const int m = 6 * A.nc;
+    double* candrot_l = dyn + (size_t)(m + 1) * m + m;
+    const BAGState* ss = bam_solve_role(A, st_in, st_out, blockIdx.x == 0, chol_flag, part_cost, nbo, part_gmax, ngm, Ublk, rhsblk, candrot, candrot_l, gslices);
+    if (!ss) return;   // block-uniform: terminated or invalid step
+    bam_backsub_role(A, ss, dyn, candrot_l, tmp3, part4, blockIdx.x);
 }
 
 // F: decision on the last step, results
@@ -1552,46 +1741,54 @@ __global__ __launch_bounds__(BM_T) void k_bam_finish(BAArgs A, const BAGState* s
 }
 
 hipError_t launch_ba_multi(hipStream_t s, const BAArgs& A, void* d_state, double* d_part) {
-    BAGState* st2[2] = {(BAGState*)d_state, (BAGState*)((char*)d_state + 256)};   // double-buffered state
+    // two copies of the state, each written by one kind of launch and read by the other: sa by E0 and C|P (the decision), sb by S|B
+    BAGState* sa = (BAGState*)d_state;
+    BAGState* sb = (BAGState*)((char*)d_state + 256);
     int* chol_flags = (int*)((char*)d_state + 512);                                // one "point block not SPD" flag per iteration
     static_assert(sizeof(BAGState) <= 256, "BAGState");
     const int nbo = (A.nobs + BM_T - 1) / BM_T, nbp = (A.np + BM_PB - 1) / BM_PB, m = 6 * A.nc;
     double* part_cost = d_part;                 // nbo
-    double* part_gmax = part_cost + nbo;        // nbp
-    double* part4 = part_gmax + nbp;            // nbp * 4
+    double* part_gmax = part_cost + nbo;        // nbp (first iteration, fallback) or kslices <= 8 (k_bam_pointgemm)
+    double* part4 = part_gmax + nbp + 8;        // nbp * 4
     double* Ublk = part4 + 4 * nbp;             // nc * 36
     double* rhsblk = Ublk + 36 * A.nc;          // nc * 6
     double* candrot = rhsblk + 6 * A.nc;        // nc * 16
     double* tmp3 = candrot + 16 * A.nc;         // nobs * 3
-    const size_t shm = ((size_t)(m + 1) * m + (size_t)m) * sizeof(double);
-    if (A.max_iterations > BA_MAX_ITERATIONS) return hipErrorInvalidValue;
+    const size_t shm = ((size_t)(m + 1) * m + (size_t)m + (size_t)16 * A.nc) * sizeof(double);   // k_bam_solveback: [S | dg | candrot]
+    if (A.max_iterations > BA_MAX_ITERATIONS || shm > 150 * 1024) return hipErrorInvalidValue;
     ProfScope ps(K_BA_LM, s);
     const int tiles = A.tiles_r * A.tiles_c;
-    // launches: E0 (+ the clear of Yt | Wt), then per iteration C|P (with the decision on the previous step) -> G -> S -> B, then F
+    // From the second iteration on the point blocks multiply their own rows (k_bam_pointgemm) when a wavefront per tile fits a block, a
+    // K-slice of Yt | Wt fits its LDS and a thread per point of a slice fits its threads; else every iteration runs C|P -> G.
+    const size_t shm_pg = std::max(bam_slice_lds(A.ldw, A.kper), (size_t)BM_WORK * sizeof(double));
+    const bool fused = tiles <= BM_NW && A.kslices <= BG_H * BG_W && shm_pg <= 150 * 1024 && bam_slice_points(A.kper) <= BM_T;
+    // launches: E0 (+ the clear of Yt | Wt), then C -> P -> G -> S|B, then per iteration C|P|G (fallback: C|P -> G), both with the decision
+    // on the previous step, -> S|B, then F
     const int clear_blocks = (int)std::min<size_t>(64, ((size_t)A.krows * A.ldw + 4 * BM_T - 1) / (4 * BM_T));
     { ProfScope p_(K_BAM_EVAL0, s);
-    hipLaunchKernelGGL(k_bam_eval0, dim3(nbo + clear_blocks), dim3(BM_T), 0, s, A, st2[1], chol_flags, part_cost, nbo); }
+    hipLaunchKernelGGL(k_bam_eval0, dim3(nbo + clear_blocks), dim3(BM_T), 0, s, A, sa, chol_flags, part_cost, nbo); }
     for (int it = 0; it < A.max_iterations; it++) {
-        BAGState* sin = st2[it & 1];
-        BAGState* sc = st2[(it + 1) & 1];   // the state of this iteration
         int* cf = chol_flags + it;
         if (it == 0) {   // the point kernel needs the camera scales of the C kernel in the first iteration
             ProfScope p_(K_BAM_CAMPOINT, s);
-            hipLaunchKernelGGL(k_bam_campoint, dim3(A.nc), dim3(BM_T), 0, s, A, sc, sc, 0, part4, nbp, cf, A.nc, Ublk, rhsblk, part_gmax);
-            hipLaunchKernelGGL(k_bam_campoint, dim3(nbp), dim3(BM_T), 0, s, A, sc, sc, 0, part4, nbp, cf, 0, Ublk, rhsblk, part_gmax);
+            hipLaunchKernelGGL(k_bam_campoint, dim3(A.nc), dim3(BM_T), 0, s, A, sa, sa, 0, part4, nbp, cf, A.nc, Ublk, rhsblk, part_gmax);
+            hipLaunchKernelGGL(k_bam_campoint, dim3(nbp), dim3(BM_T), 0, s, A, sa, sa, 0, part4, nbp, cf, 0, Ublk, rhsblk, part_gmax);
+        } else if (fused) {
+            ProfScope p_(K_BAM_POINTGEMM, s);
+            hipLaunchKernelGGL(k_bam_pointgemm, dim3(A.nc + A.kslices), dim3(BM_T), shm_pg, s, A, sb, sa, part4, nbp, cf, Ublk, rhsblk, part_gmax);
         } else {
             ProfScope p_(K_BAM_CAMPOINT, s);
-            hipLaunchKernelGGL(k_bam_campoint, dim3(A.nc + nbp), dim3(BM_T), 0, s, A, sin, sc, 1, part4, nbp, cf, A.nc, Ublk, rhsblk, part_gmax);
+            hipLaunchKernelGGL(k_bam_campoint, dim3(A.nc + nbp), dim3(BM_T), 0, s, A, sb, sa, 1, part4, nbp, cf, A.nc, Ublk, rhsblk, part_gmax);
         }
-        { ProfScope p_(K_BAM_GEMM, s);
-        hipLaunchKernelGGL(k_bam_gemm, dim3(tiles * BG_H), dim3(64 * BG_W), 0, s, A, sc); }
-        { ProfScope p_(K_BAM_SOLVE, s);
-        hipLaunchKernelGGL(k_bam_solve, dim3(1), dim3(BM_T), shm, s, A, sc, cf, part_cost, nbo, part_gmax, nbp, Ublk, rhsblk, candrot); }
-        { ProfScope p_(K_BAM_BACKSUB, s);
-        hipLaunchKernelGGL(k_bam_backsub, dim3(nbp), dim3(BM_T), 0, s, A, sc, candrot, tmp3, part4); }
+        const bool sliced = fused && it > 0;
+        if (!sliced) { ProfScope p_(K_BAM_GEMM, s);
+        hipLaunchKernelGGL(k_bam_gemm, dim3(tiles * BG_H), dim3(64 * BG_W), 0, s, A, sa); }
+        { ProfScope p_(K_BAM_SOLVEBACK, s);
+        hipLaunchKernelGGL(k_bam_solveback, dim3(nbp), dim3(BM_T), shm, s, A, sa, sb, cf, part_cost, nbo, part_gmax, sliced ? A.kslices : nbp, Ublk,
+                           rhsblk, candrot, tmp3, part4, sliced ? A.kslices : 0); }
     }
     { ProfScope p_(K_BAM_FINISH, s);
-    hipLaunchKernelGGL(k_bam_finish, dim3(1), dim3(BM_T), 0, s, A, st2[A.max_iterations & 1], part4, nbp); }
+    hipLaunchKernelGGL(k_bam_finish, dim3(1), dim3(BM_T), 0, s, A, sb, part4, nbp); }
     return hipGetLastError();
 }
 
@@ -1641,13 +1838,14 @@ __global__ __launch_bounds__(64 * BG_W) void k_bamB_gemm(const BAProb* __restric
 __global__ __launch_bounds__(BM_T) void k_bamB_solve(const BAProb* __restrict__ probs, int it) { BACKEND_PRIO();
     const BAProb& P = probs[blockIdx.x];
     const BAArgs A = P.A;   // by value (uniform address -> scalar loads once); a reference would be re-read after every store: 29 -> 57 us for k_bamB_campoint
-    bam_solve_role(A, (BAGState*)P.st2[(it + 1) & 1], P.chol_flags + it, P.part_cost, P.nbo, P.part_gmax, P.nbp, P.Ublk, P.rhsblk, P.candrot);
+    BAGState* st = (BAGState*)P.st2[(it + 1) & 1];   // one block per problem: the state is updated in place
+    bam_solve_role(A, st, st, true, P.chol_flags + it, P.part_cost, P.nbo, P.part_gmax, P.nbp, P.Ublk, P.rhsblk, P.candrot, nullptr, 0);
 }
 __global__ __launch_bounds__(BM_T) void k_bamB_backsub(const BAProb* __restrict__ probs, int it) { BACKEND_PRIO();
     const BAProb& P = probs[blockIdx.y];
     if ((int)blockIdx.x >= P.nbp) return;
     const BAArgs A = P.A;   // by value (uniform address -> scalar loads once); a reference would be re-read after every store: 29 -> 57 us for k_bamB_campoint
-    bam_backsub_role(A, (const BAGState*)P.st2[(it + 1) & 1], P.candrot, P.tmp3, P.part4, blockIdx.x);
+    bam_backsub_role(A, (const BAGState*)P.st2[(it + 1) & 1], A.step, P.candrot, P.tmp3, P.part4, blockIdx.x);
 }
 __global__ __launch_bounds__(BM_T) void k_bamB_finish(const BAProb* __restrict__ probs, int max_it) { BACKEND_PRIO();
     const BAProb& P = probs[blockIdx.x];
@@ -1700,7 +1898,9 @@ hipError_t launch_ba_lm(hipStream_t s, const BAArgs& A) {
 
 // LDS opt-in (150 KB reduced camera system) per device; see frontend_prepare_device()
 hipError_t backend_prepare_device() {
-    hipError_t e = hipFuncSetAttribute((const void*)k_bam_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)k_bam_solveback, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_bam_pointgemm, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)k_bamB_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (e != hipSuccess) return e;

@@ -7,18 +7,23 @@
 namespace pmv {
 
 enum KernelId { K_PAD0 = 0, K_PYRDOWN, K_LK, K_GFTT_CAND, K_GFTT_PICK, K_ST_RESP, K_ST_SELECT, K_PNP_HYP, K_PNP_REFIT,
-                K_BA_LM, K_BA_RESID, K_TRI_DLT, K_BAM_EVAL0, K_BAM_CAMPOINT, K_BAM_GEMM, K_BAM_SOLVE, K_BAM_BACKSUB, K_BAM_FINISH, K_FIVEPOINT, K_PAD0_BGR, K_COUNT };
+                K_BA_LM, K_BA_RESID, K_TRI_DLT, K_BAM_EVAL0, K_BAM_CAMPOINT, K_BAM_GEMM, K_BAM_SOLVE, K_BAM_BACKSUB, K_BAM_FINISH, K_FIVEPOINT, K_BAM_SOLVEBACK, K_BAM_POINTGEMM, K_PAD0_BGR, K_COUNT };
 
 inline const char* kernel_name(int id) {
     static const char* n[K_COUNT] = {"k_pad_level0", "k_pyrdown", "k_lk", "k_gftt_cand", "k_gftt_pick", "k_st_resp", "k_st_select",
                                      "k_pnp_hyp", "k_pnp_select_refit", "ba_lm_chain", "k_ba_residuals", "k_tri_dlt",
-                                     "k_bam_eval0", "k_bam_campoint", "k_bam_gemm", "k_bam_solve", "k_bam_backsub", "k_bam_finish", "k_fivepoint_hyp+score", "k_pad_level0_bgr"};
+                                     "k_bam_eval0", "k_bam_campoint", "k_bam_gemm", "k_bam_solve", "k_bam_backsub", "k_bam_finish", "k_fivepoint_hyp+score", "k_bam_solveback", "k_bam_pointgemm", "k_pad_level0_bgr"};
     return (id >= 0 && id < K_COUNT) ? n[id] : "?";
 }
 
 // "ba_lm_chain" times one whole LM solve: the chain of k_bam_* launches (or k_ba_lm in single-workgroup mode); every other
 // class is exactly one kernel per launch. The k_bam_* classes time the kernels of the chain one by one; they are recorded only
 // when their bit is selected explicitly (pmv_prof_select): events between the launches of a chain lengthen the chain itself.
+// k_bam_solveback (the solve and the back-substitution in one launch) took the place of k_bam_solve and k_bam_backsub in the single
+// chain, k_bam_pointgemm (cameras | points with the Schur product) that of k_bam_campoint and k_bam_gemm from the second iteration on;
+// they are recorded whenever any kernel of the chain is selected, so a caller that names the older classes still sees the whole chain.
+inline bool chain_fused(int id) { return id == K_BAM_SOLVEBACK || id == K_BAM_POINTGEMM; }
+inline bool in_chain(int id) { return (id >= K_BAM_EVAL0 && id <= K_BAM_FINISH) || chain_fused(id); }
 struct Profiler {
     static constexpr int CHUNK = 8192;       // the event pool of a class grows by this many launches at a time ...
     static constexpr int CAP = 1 << 20;      // ... up to this many launches between resets (beyond it: counted in `dropped`)
@@ -50,7 +55,8 @@ struct ProfScope {
     hipEvent_t* e = nullptr;
     hipStream_t s;
     ProfScope(int id, hipStream_t stream) : s(stream) {
-        if (tl_prof && tl_prof->enabled && ((tl_prof->mask >> id) & 1u) && (id < K_BAM_EVAL0 || id > K_BAM_FINISH || tl_prof->chain_detail)) {
+        const bool chain = in_chain(id);
+        if (tl_prof && tl_prof->enabled && (chain ? tl_prof->chain_detail && (((tl_prof->mask >> id) & 1u) || chain_fused(id)) : ((tl_prof->mask >> id) & 1u) != 0)) {
             e = tl_prof->next(id);
             if (e) (void)hipEventRecord(e[0], s);
         }
