@@ -9,6 +9,7 @@
  *   pmv_detect_gftt                        cv::goodFeaturesToTrack per grid cell         (OpenCVGoodFeatureExtractor.cpp:7,
  *                                          called from OdometryPipeline.cpp:357 / :450)  -> BaseFeatureExtractor.h:21
  *   pmv_detect_gftt_frame                  cv::goodFeaturesToTrack on the whole frame or one region of any size, one call per frame
+ *   pmv_detect_gftt_refill                 the same with the keep-away mask made on the device from the caller's track list (setMask)
  *   pmv_detect_gftt_ex                     cv::goodFeaturesToTrack with the caller's mask, blockSize, useHarrisDetector, k (a KLT front end
  *                                          of the caller's own; the reference passes cv::Mat(), 3, 3, false, 0.04)
  *   pmv_corner_subpix                      cv::cornerSubPix on level 0 of a slot (the step between the detector and LK in the caller's own
@@ -364,9 +365,9 @@ int pmv_debug_gftt_general(pmv_ctx* ctx, int on);
  *   detectors.
  * The device buffers are made by the first frame call on a context, sized for max_w x max_h (a flat plateau makes every pixel a record).
  * pmv_detect_gftt and pmv_detect_gftt_ex keep their 255x255 cells and every refusal: this is a new entry point, not a lifted limit.
- * Out of scope: Sobel apertures other than 3; building the keep-away mask on the device from a track list (cv::circle's rasterisation) -
- *   the mask still comes from the host; more than PMV_GFTT_FRAME_MAX_CORNERS corners; the whole-sequence drivers (pmv_pipeline_run*) and
- *   bench.py do not call this. */
+ * Out of scope: Sobel apertures other than 3; more than PMV_GFTT_FRAME_MAX_CORNERS corners; the whole-sequence drivers (pmv_pipeline_run*)
+ *   and bench.py do not call this. Building the keep-away mask on the device from a track list (cv::circle's rasterisation) is
+ *   pmv_detect_gftt_refill below. */
 #define PMV_GFTT_FRAME_MAX_CORNERS 16384
 int pmv_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
                           const uint8_t* mask, int mask_stride, int* out_xy, int out_cap, int* out_count);
@@ -374,6 +375,52 @@ int pmv_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int m
  * made for those rounds, records above the threshold in the last request served, of those the number kept off-chip, on-chip record
  * capacity of the selection kernel}. */
 int pmv_debug_gftt_frame_stats(pmv_ctx* ctx, long long* out6);
+/* The refill of a KLT loop in one call: FeatureTracker::setMask on the caller's tracks, then pmv_detect_gftt_frame with that mask. The
+ * tracks are sorted, walked and thinned, the keep-away mask is painted in HBM and the detector reads it there: no w x h buffer is written
+ * by the host or crosses the bus (unless the caller has a base mask of its own), and there is one wait.
+ *   track_xy: n_tracks (x, y) float pairs, frame coordinates. The integer position of a track is (cvRound(x), cvRound(y)), round half to
+ *     even, as cv's Point2f -> Point conversion.
+ *   Order: priority descending, then index ascending - one of the orders setMask's std::sort may give among equal priorities.
+ *     track_prio_or_null: any int32 per track (a track's age); NULL = all equal, the caller's order.
+ *   Walk: track i is kept (out_keep[i] = 1, else 0) when the mask byte at its position is 255 - the base byte, exactly as setMask tests
+ *     `== 255`; 255 everywhere without a base mask - and its position lies in no disc of a track kept earlier in the order.
+ *   Disc: a kept track clears cv::circle(mask, pt, radius, 0, -1): the Circle() loop of OpenCV 3.4 (fill, LINE_8, shift 0), clipped to the
+ *     frame; radius 0 is the centre pixel. It is NOT x^2 + y^2 <= r^2 by definition: the kernels test |dy| <= radius and |dx| <= hw[|dy|],
+ *     hw = the widest span of that loop per row offset, computed on the host.
+ *   Final mask: 0 inside any kept disc, else the base byte (255 without a base mask).
+ *   out_keep depends on the track geometry and on the base bytes under the n positions only, not on the region: a track outside the
+ *     region still suppresses tracks inside it. Only painting and detection are restricted to the region.
+ *   Detection: exactly pmv_detect_gftt_frame with that mask (non-zero = allowed) - the same roi4_or_null, max_corners, p, out_xy, out_cap
+ *     and out_count, region rule, cap rule, overflow rule and bytes. The yardstick is refill_twin_mask (tests/twin/refill_twin.cpp) for
+ *     out_keep and the mask, and gftt_twin_cell with that mask and the region as its cell for the corners.
+ *   base_mask_or_null: host memory of the frame's size, base_stride bytes per row. The host reads the n bytes under the tracks (n flag
+ *     bytes go to the device) and packs the region's sub-view as pmv_detect_gftt_frame packs its mask. Without one nothing of the
+ *     region's size is allocated in pinned memory, written by the host or copied.
+ *   Kernels: k_track_select (one workgroup: keys and positions in LDS, the sorting network and the chunked walk of k_gftt_pick_frame),
+ *     k_track_paint (every dword of the packed mask written once by its owner), then the general pass 1 and pass 2 of
+ *     pmv_detect_gftt_frame; booked under k_gftt_pick and k_gftt_cand.
+ * Errors (nothing is written and nothing is clamped on any of them): every refusal of pmv_detect_gftt_frame, with the same codes and in
+ *   the same order (base_mask_or_null and base_stride in the place of mask and mask_stride); then
+ *   PMV_ERR_INVALID - null out_keep, or null track_xy with n_tracks > 0; radius outside 0..PMV_REFILL_MAX_RADIUS; a coordinate that is
+ *     not finite or beyond 1e6; a track whose rounded position lies outside the frame (cv reads out of bounds there; the message names the
+ *     point and the frame size);
+ *   PMV_ERR_CAPACITY - n_tracks < 0 or above min(max_tracks, PMV_REFILL_MAX_TRACKS).
+ *   n_tracks == 0 is legal: the mask is the base mask, or all 255.
+ * The buffers are made by the first refill call on a context. The call is not logged by pmv_record_enable.
+ * Out of scope: non-filled or anti-aliased circles; a per-track radius; returning the mask outside pmv_debug_refill_mask; feeding the
+ *   kept tracks onward on the device; the whole-sequence drivers (pmv_pipeline_run*) and bench.py do not call this. */
+#define PMV_REFILL_MAX_TRACKS 8192
+#define PMV_REFILL_MAX_RADIUS 255
+int pmv_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
+                           const float* track_xy, const int* track_prio_or_null, int n_tracks, int radius,
+                           const uint8_t* base_mask_or_null, int base_stride,
+                           uint8_t* out_keep, int* out_xy, int out_cap, int* out_count);
+/* diagnostic: the packed mask of the region of the last pmv_detect_gftt_refill call on this context (not a session call), *w x *h tight
+ * bytes into out (cap bytes; PMV_ERR_CAPACITY if too small, PMV_ERR_INVALID before the first refill call). */
+int pmv_debug_refill_mask(pmv_ctx* ctx, uint8_t* out, long long cap, int* w, int* h);
+/* diagnostic: out4 = {single refill calls, session rounds that held at least one refill request, select + paint launch pairs made for
+ * those rounds, bytes of mask copied host -> device by refill calls since the context was created (0 unless a base mask was given)}. */
+int pmv_debug_refill_stats(pmv_ctx* ctx, long long* out4);
 /* Same geometry; out_score: n_cells * max_per_cell doubles (the reference fills Feature::score). max_per_cell <= 0 returns no
  * features (ShiTomasiFeatureExtractor.cpp:37-44). */
 int pmv_detect_shitomasi(pmv_ctx* ctx, int slot, const int* cells, int n_cells, int max_per_cell, double quality,
@@ -885,6 +932,15 @@ int pmv_batch_detect_gftt_ex(pmv_ctx* ctx, int slot, const int* cells, int n_cel
  * the call returns; record space grows to the largest round seen. */
 int pmv_batch_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
                                 const uint8_t* mask, int mask_stride, int* out_xy, int out_cap, int* out_count);
+/* pmv_detect_gftt_refill as a session call: the same arguments, bytes and status codes. It is a frame request that carries a track list:
+ * it joins the frame groups of its round under the rules above with has-mask = true, and the round makes ONE k_track_select and ONE
+ * k_track_paint launch for all its refill requests, in front of the frame launches - each request names its own n, radius, half-width
+ * table and mask offset. A round without refill requests launches and allocates exactly what it did before. The track list and the base
+ * mask are read before the call returns. */
+int pmv_batch_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
+                                 const float* track_xy, const int* track_prio_or_null, int n_tracks, int radius,
+                                 const uint8_t* base_mask_or_null, int base_stride,
+                                 uint8_t* out_keep, int* out_xy, int out_cap, int* out_count);
 /* pmv_corner_subpix as a session call: the same arguments, bits and status codes. It is served by the detector combiner: requests of a
  * round that agree in the six parameters share ONE launch, whatever their slots and declared frame sizes (every point's record names its
  * geometry); a round without such requests launches exactly what it launched before. A round's result block holds at least

@@ -186,6 +186,7 @@ ABI_SYMBOLS = [
     "pmv_detect_gftt", "pmv_detect_shitomasi", "pmv_detect_fast", "pmv_knn_match", "pmv_debug_gftt_response", "pmv_debug_shitomasi_response",
     "pmv_detect_gftt_ex", "pmv_debug_gftt_response_ex", "pmv_debug_gftt_general", "pmv_batch_detect_gftt_ex",
     "pmv_detect_gftt_frame", "pmv_batch_detect_gftt_frame", "pmv_debug_gftt_frame_stats",
+    "pmv_detect_gftt_refill", "pmv_batch_detect_gftt_refill", "pmv_debug_refill_mask", "pmv_debug_refill_stats",
     "pmv_corner_subpix", "pmv_batch_corner_subpix", "pmv_debug_subpix_launches",
     "pmv_frames_clahe", "pmv_batch_frame_upload_clahe", "pmv_debug_clahe_launches",
     "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
@@ -207,6 +208,8 @@ ABI_SYMBOLS = [
 
 GFTT_UNLIMITED_CAP = 4096   # PMV_GFTT_UNLIMITED_CAP of include/pmv_hip.h
 GFTT_FRAME_MAX_CORNERS = 16384   # PMV_GFTT_FRAME_MAX_CORNERS of include/pmv_hip.h
+REFILL_MAX_TRACKS = 8192   # PMV_REFILL_MAX_TRACKS of include/pmv_hip.h
+REFILL_MAX_RADIUS = 255    # PMV_REFILL_MAX_RADIUS of include/pmv_hip.h
 
 
 class PipelineParams(C.Structure):
@@ -500,6 +503,7 @@ class Context:
                                      max_ba_points, max_ba_obs)
         if rc != 0:
             raise PmvError(rc, self.lib.pmv_last_error(None).decode())
+        self.max_pixels = int(max_w) * int(max_h)   # the largest region a diagnostic may hand back (debug_refill_mask)
 
     def close(self):
         if self.h:
@@ -722,6 +726,66 @@ class Context:
         GFTT_FRAME_MAX_CORNERS without a limit) is the list's capacity - more corners than that raise PmvError (PMV_ERR_OVERFLOW). With a
         mask of a frame that is smaller than the mask's array, pass roi."""
         return self._gftt_frame(self.lib.pmv_detect_gftt_frame, self._ck, slot, max_corners, quality, min_dist, mask, block_size, use_harris, k, roi, out_cap)
+
+    def _gftt_refill(self, fn, ck, slot, max_corners, tracks, radius, priorities, base_mask, quality, min_dist, block_size, use_harris, k, roi, out_cap):
+        if out_cap is None:
+            out_cap = int(max_corners) if max_corners > 0 else GFTT_FRAME_MAX_CORNERS
+        tracks = np.ascontiguousarray(tracks, np.float32)
+        if tracks.size and (tracks.ndim != 2 or tracks.shape[1] != 2):
+            raise ValueError("detect_gftt_refill: tracks must be an (n, 2) float32 array")
+        n = tracks.size // 2
+        pptr = None
+        if priorities is not None:
+            priorities = np.ascontiguousarray(priorities, np.int32).reshape(-1)
+            if priorities.size != n:
+                raise ValueError("detect_gftt_refill: one priority per track")
+            pptr = _p(priorities, _i32p)
+        keep = np.zeros(max(n, 1), np.uint8)
+        xy = np.zeros((max(int(out_cap), 1), 2), np.int32)
+        cnt = C.c_int(0)
+        p = GfttParams(float(quality), float(min_dist), int(block_size), 1 if use_harris else 0, float(k))
+        rptr = None
+        if roi is not None:
+            roi = np.ascontiguousarray(roi, np.int32).reshape(-1)
+            if roi.size != 4:
+                raise ValueError("detect_gftt_refill: roi is (x0, y0, w, h)")
+            rptr = _p(roi, _i32p)
+        mptr, mstride = None, 0
+        if base_mask is not None:
+            # passed in place with its own row stride: the library reads the bytes under the tracks and under the region
+            if not isinstance(base_mask, np.ndarray) or base_mask.dtype != np.uint8 or base_mask.ndim != 2 or (base_mask.shape[1] > 1 and base_mask.strides[1] != 1):
+                raise ValueError("detect_gftt_refill: base_mask must be an (h, w) uint8 array whose rows are contiguous (any row stride)")
+            mptr = C.cast(C.c_void_p(base_mask.ctypes.data), _u8p)
+            mstride = int(base_mask.strides[0]) if base_mask.shape[0] > 1 else max(int(base_mask.strides[0]), base_mask.shape[1])
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, C.POINTER(GfttParams), _f32p, _i32p, C.c_int, C.c_int, _u8p, C.c_int, _u8p, _i32p, C.c_int, C.POINTER(C.c_int)]
+        ck(fn(self.h, int(slot), rptr, int(max_corners), C.byref(p), _p(tracks, _f32p) if n else None, pptr, n, int(radius), mptr, mstride, _p(keep, _u8p), _p(xy, _i32p),
+              int(out_cap), C.byref(cnt)))
+        return keep[:n].copy(), xy[: cnt.value].copy()
+
+    def detect_gftt_refill(self, slot, max_corners, tracks, radius, priorities=None, base_mask=None, quality=0.01, min_dist=5.0, block_size=3, use_harris=False, k=0.04,
+                           roi=None, out_cap=None):
+        """pmv_detect_gftt_refill: FeatureTracker::setMask on `tracks` ((n, 2) float32 frame coordinates; priorities: None or n int32, higher
+        first) with cv::circle's `radius`, then detect_gftt_frame with that mask - the mask is made on the device. base_mask: None or an
+        (h, w) uint8 array of the frame's size (a track on a byte other than 255 is dropped; 0 = not allowed for the detector).
+        Returns (keep (n,) uint8, corners (m, 2) int32 region-local in cv's order)."""
+        return self._gftt_refill(self.lib.pmv_detect_gftt_refill, self._ck, slot, max_corners, tracks, radius, priorities, base_mask, quality, min_dist, block_size,
+                                 use_harris, k, roi, out_cap)
+
+    def debug_refill_mask(self):
+        """pmv_debug_refill_mask: the (h, w) uint8 mask of the region of the last detect_gftt_refill call of this context"""
+        out = np.zeros(self.max_pixels, np.uint8)
+        w, h = C.c_int(0), C.c_int(0)
+        self.lib.pmv_debug_refill_mask.argtypes = [C.c_void_p, _u8p, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._ck(self.lib.pmv_debug_refill_mask(self.h, _p(out, _u8p), out.size, C.byref(w), C.byref(h)))
+        return out[: w.value * h.value].reshape(h.value, w.value).copy()
+
+    def debug_refill_stats(self):
+        """pmv_debug_refill_stats: [single refill calls, session rounds with a refill request, select + paint launch pairs made for them, bytes
+        of mask copied host -> device by refill calls]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_refill_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_refill_stats(self.h, out))
+        return [int(v) for v in out]
 
     def debug_gftt_frame_stats(self):
         """pmv_debug_gftt_frame_stats: [frame calls of the single entry point, session rounds with a frame request, launch pairs made for them,
@@ -1307,6 +1371,12 @@ class Context:
     def batch_detect_gftt_frame(self, slot, max_corners, quality=0.01, min_dist=5.0, mask=None, block_size=3, use_harris=False, k=0.04, roi=None, out_cap=None):
         """pmv_batch_detect_gftt_frame: detect_gftt_frame as a session call (same arguments, same array)"""
         return self._gftt_frame(self.lib.pmv_batch_detect_gftt_frame, self._ckt, slot, max_corners, quality, min_dist, mask, block_size, use_harris, k, roi, out_cap)
+
+    def batch_detect_gftt_refill(self, slot, max_corners, tracks, radius, priorities=None, base_mask=None, quality=0.01, min_dist=5.0, block_size=3, use_harris=False,
+                                 k=0.04, roi=None, out_cap=None):
+        """pmv_batch_detect_gftt_refill: detect_gftt_refill as a session call (same arguments, same arrays)"""
+        return self._gftt_refill(self.lib.pmv_batch_detect_gftt_refill, self._ckt, slot, max_corners, tracks, radius, priorities, base_mask, quality, min_dist,
+                                 block_size, use_harris, k, roi, out_cap)
 
     def batch_corner_subpix(self, slot, xy, win=(5, 5), zero_zone=(-1, -1), max_iter=30, eps=0.01, return_info=False):
         """pmv_batch_corner_subpix: corner_subpix as a session call (same arguments, same arrays)"""

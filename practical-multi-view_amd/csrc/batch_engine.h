@@ -50,6 +50,12 @@ int engine_detect_gftt_ex(BatchEngine* E, const char* who, int slot, const int* 
 // layout share ONE pass-1 and ONE pass-2 launch: each has its own record list, pass 2 runs one workgroup per request.
 int engine_detect_gftt_frame(BatchEngine* E, const char* who, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const uint8_t* mask,
                              int mask_stride, int* out_xy, int out_cap, int* out_count);
+// pmv_detect_gftt_refill's contract: a frame request that carries a track list (read, like the base mask, by the combiner before the call
+// returns). It joins the frame groups with has-mask = true; the refill requests of a round share ONE k_track_select and ONE k_track_paint
+// launch in front of the frame launches.
+int engine_detect_gftt_refill(BatchEngine* E, const char* who, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const float* track_xy,
+                              const int* track_prio_or_null, int n_tracks, int radius, const uint8_t* base_mask_or_null, int base_stride, uint8_t* out_keep,
+                              int* out_xy, int out_cap, int* out_count);
 // pmv_corner_subpix's contract: a request of the detector combiner. Requests of a round that agree in the six parameters share one
 // launch, whatever their slots and frame sizes.
 int engine_corner_subpix(BatchEngine* E, const char* who, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags);

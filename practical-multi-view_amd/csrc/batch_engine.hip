@@ -76,6 +76,12 @@ struct DetReq : Req {
     // filled by the combiner: the first entry of its record list among the round's, its index in its group
     int roi[4] = {0, 0, 0, 0};
     size_t list_off = 0;
+    // pmv_batch_detect_gftt_refill: a frame request whose mask is painted on the device from these tracks (`mask` = the base mask or null);
+    // filled by the combiner: the first entry of its tracks in the round's refill block
+    int refill = 0, n_trk = 0, radius = 0;
+    const float* trk_xy = nullptr; const int* trk_prio = nullptr; uint8_t* out_keep = nullptr;
+    size_t trk_off = 0;
+    bool has_mask() const { return mask != nullptr || refill != 0; }
 };
 struct SubpixReq : Req {      // Q_SUBPIX: one pmv_batch_corner_subpix call; p's zero zone is the effective one (subpix_zero_zone)
     int slot, n;
@@ -131,6 +137,9 @@ struct Combiner {
     // groups' blocks (gftt_frame_block) in mapped pinned memory, the regions' packed masks, and in HBM the record lists, the key lists of the
     // selection's slower path (one entry per pixel of the round's regions) and the (maximum, count) pairs
     HScratch h_gfr, h_gfr_mask; DScratch d_gfr_mask, d_gfr_val, d_gfr_idx, d_gfr_keys, d_gfr_info;
+    // refill requests of a round (detector combiner, made by the first round that has one): the round's refill_block in mapped pinned
+    // memory, the kept lists and their counts in HBM
+    HScratch h_refill; DScratch d_refill_kept, d_refill_nkept;
     // corner sub-pixel requests of a round (detector combiner, made by the first round that has one): [point records | positions | updates |
     // flags] in one mapped pinned block; the weight tables of the round's parameter groups, pinned mirror and HBM copy
     HScratch h_spx, h_spx_tab; DScratch d_spx_tab;
@@ -544,6 +553,9 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     struct FGroup { DetReq* key; PyrLayout L; std::vector<DetReq*> reqs; int grid_x = 0; size_t info_base = 0; GfttFrameBlock B{}; };
     std::vector<FGroup> fgroups;
     size_t f_pix = 0, f_mask = 0, f_n = 0;
+    // refill requests: their number, their track entries, the bytes of the regions that are painted from 255 (they lie behind the uploaded
+    // masks and are not copied), the largest region
+    size_t rf_n = 0, rf_trk = 0, rf_plain = 0, rf_max = 0;
     for (DetReq* r : fr) {
         if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
         const PyrLayout& Lr = ctx->slot_layout[r->slot];
@@ -552,13 +564,15 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             continue;
         }
         const size_t pix = (size_t)r->roi[2] * r->roi[3];
-        if (r->mask && f_mask + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
-        if (r->mask) f_mask += pix;
+        if (r->has_mask() && f_mask + rf_plain + pix + (r->refill ? 8 : 0) > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
+        if (r->mask) f_mask += pix + (r->refill ? 6 : 0);   // (a refill request's bytes begin and end at a multiple of 4)
+        else if (r->refill) rf_plain += (pix + 3) & ~(size_t)3;
+        if (r->refill) { r->trk_off = rf_trk; rf_trk += refill_pad(r->n_trk); rf_n++; rf_max = std::max(rf_max, pix); }
         FGroup* g = nullptr;
         for (FGroup& x : fgroups) {
             const DetReq* k = x.key;
             if (k->max_per_cell == r->max_per_cell && k->unlimited == r->unlimited && k->quality == r->quality && k->min_dist == r->min_dist && k->ext == r->ext &&
-                k->block_size == r->block_size && k->use_harris == r->use_harris && k->k == r->k && (k->mask != nullptr) == (r->mask != nullptr) &&
+                k->block_size == r->block_size && k->use_harris == r->use_harris && k->k == r->k && k->has_mask() == r->has_mask() &&
                 x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
         }
         if (!g) { fgroups.push_back(FGroup{r, Lr, {}}); g = &fgroups.back(); }
@@ -574,7 +588,16 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
         EK(C.h_gfr.ensure(need.bytes() + 64));
         EK(C.d_gfr_val.ensure(f_pix * sizeof(float))); EK(C.d_gfr_idx.ensure(f_pix * sizeof(unsigned))); EK(C.d_gfr_keys.ensure(f_pix * sizeof(unsigned long long)));
         EK(C.d_gfr_info.ensure(f_n * 2 * sizeof(unsigned)));
-        if (f_mask) { EK(C.h_gfr_mask.ensure(f_mask + 64)); EK(C.d_gfr_mask.ensure(f_mask + 64)); }
+        if (f_mask) EK(C.h_gfr_mask.ensure(f_mask + 64));
+        if (f_mask || rf_plain) EK(C.d_gfr_mask.ensure(f_mask + rf_plain + (rf_n ? 4 : 0) + 64));
+        RefillBlock T{};
+        if (rf_n) {
+            Carve rneed;
+            refill_block(rneed, rf_n, rf_trk);
+            EK(C.h_refill.ensure(rneed.bytes() + 64)); EK(C.d_refill_kept.ensure((rf_trk + 4) * sizeof(unsigned))); EK(C.d_refill_nkept.ensure(rf_n * sizeof(int)));
+            Carve rc = carve_of(C.h_refill);
+            T = refill_block(rc, rf_n, rf_trk);
+        }
         Carve c = carve_of(C.h_gfr);
         size_t mpos = 0, ibase = 0;
         for (FGroup& g : fgroups) {
@@ -583,15 +606,32 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             ibase += g.reqs.size();
             for (size_t i = 0; i < g.reqs.size(); i++) {
                 DetReq* r = g.reqs[i];
+                if (r->refill && r->mask) mpos = (mpos + 3) & ~(size_t)3;   // (the painting owns aligned dwords of a refill request's bytes)
+                const size_t m0 = mpos;
                 mpos = gftt_frame_record(g.B.rec.h + i * CELL_STRIDE, r->roi, r->slot, r->list_off, (uint8_t*)C.h_gfr_mask.p, mpos, r->mask, r->mask_stride);
+                if (r->refill && r->mask) { ctx->refill_stats[3] += (long long)(mpos - m0); mpos = (mpos + 3) & ~(size_t)3; }
             }
         }
-        if (f_mask) EK(hipMemcpyAsync(C.d_gfr_mask.p, C.h_gfr_mask.p, f_mask, hipMemcpyHostToDevice, s));
+        if (mpos) EK(hipMemcpyAsync(C.d_gfr_mask.p, C.h_gfr_mask.p, mpos, hipMemcpyHostToDevice, s));
+        if (rf_n) {   // the regions painted from 255 follow the uploaded bytes; then ONE select and ONE paint launch for the round's refill requests
+            size_t ppos = (mpos + 3) & ~(size_t)3, ri = 0;
+            for (FGroup& g : fgroups)
+                for (size_t i = 0; i < g.reqs.size(); i++) {
+                    DetReq* r = g.reqs[i];
+                    if (!r->refill) continue;
+                    int* rec = g.B.rec.h + i * CELL_STRIDE;
+                    if (!r->mask) { rec[5] = (int)ppos; ppos += ((size_t)r->roi[2] * r->roi[3] + 3) & ~(size_t)3; }
+                    refill_fill(T, ri++, r->trk_off, r->roi, (size_t)(unsigned)rec[5], r->trk_xy, r->trk_prio, r->n_trk, r->radius, r->mask, r->mask_stride);
+                }
+            EK(launch_track_refill(s, T.rec.d, (int)rf_n, rf_max, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, (unsigned*)C.d_refill_kept.p, (int*)C.d_refill_nkept.p,
+                                   (uint8_t*)C.d_gfr_mask.p));
+            ctx->refill_stats[1]++; ctx->refill_stats[2]++;
+        }
         for (FGroup& g : fgroups) {
             const DetReq* k = g.key;
             const GfttExt X = gftt_ext(k->block_size, k->use_harris, k->k);
             EK(launch_gftt_frame(s, ctx->d_slots, g.L, g.B.rec.d, (int)g.reqs.size(), g.grid_x, k->max_per_cell, k->quality, k->min_dist, k->unlimited, k->ext ? &X : nullptr,
-                                 k->mask ? (const uint8_t*)C.d_gfr_mask.p : nullptr, (float*)C.d_gfr_val.p, (unsigned*)C.d_gfr_idx.p, (unsigned*)C.d_gfr_info.p + 2 * g.info_base,
+                                 k->has_mask() ? (const uint8_t*)C.d_gfr_mask.p : nullptr, (float*)C.d_gfr_val.p, (unsigned*)C.d_gfr_idx.p, (unsigned*)C.d_gfr_info.p + 2 * g.info_base,
                                  (unsigned long long*)C.d_gfr_keys.p, g.B.xy.d, g.B.count.d, g.B.stats.d));
             ctx->gftt_frame_stats[2]++;
         }
@@ -657,7 +697,11 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             DetReq* r = g.reqs[i];
             const int n = g.B.count.h[i];
             ctx->gftt_frame_stats[3] = g.B.stats.h[2 * i]; ctx->gftt_frame_stats[4] = g.B.stats.h[2 * i + 1];
-            if (n < 0) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "pmv_batch_detect_gftt_frame: more than out_cap = %d corners with max_corners <= 0 (no limit)", r->max_per_cell); continue; }
+            if (n < 0) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "%s: more than out_cap = %d corners with max_corners <= 0 (no limit)", r->refill ? "pmv_batch_detect_gftt_refill" : "pmv_batch_detect_gftt_frame", r->max_per_cell); continue; }
+            if (r->refill) {
+                Carve rc = carve_of(C.h_refill);
+                memcpy(r->out_keep, refill_block(rc, rf_n, rf_trk).keep.h + r->trk_off, (size_t)r->n_trk);
+            }
             memcpy(r->out_xy, g.B.xy.h + i * (size_t)r->max_per_cell * 2, (size_t)n * 8);
             *r->out_count = n;
         }
@@ -1123,6 +1167,23 @@ int engine_detect_gftt_frame(BatchEngine* E, const char* who, int slot, const in
     r.ext = p->block_size != 3 || p->use_harris || mask || ctx->gftt_general;   // the general pass-1 kernel, as in the single call
     r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
     r.mask = mask; r.mask_stride = mask_stride;
+    return submit(ctx, E->queue[R_DET], &r);
+}
+
+int engine_detect_gftt_refill(BatchEngine* E, const char* who, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const float* track_xy,
+                              const int* track_prio_or_null, int n_tracks, int radius, const uint8_t* base_mask_or_null, int base_stride, uint8_t* out_keep,
+                              int* out_xy, int out_cap, int* out_count) {
+    pmv_ctx* ctx = E->ctx;
+    DetReq r;
+    int cap = 0;
+    if (const int rc = gftt_frame_check(ctx, who, false, slot, roi4_or_null, max_corners, p, base_mask_or_null, base_stride, out_xy, out_cap, out_count, r.roi, &cap)) return rc;
+    if (const int rc = refill_check(ctx, who, slot, track_xy, n_tracks, radius, out_keep)) return rc;
+    r.kind = Q_GFTT_FRAME; r.slot = slot; r.cells = r.roi; r.n_cells = 1; r.unlimited = max_corners <= 0; r.max_per_cell = cap;
+    r.quality = p->quality; r.min_dist = p->min_dist; r.out_xy = out_xy; r.out_score = nullptr; r.out_count = out_count; r.ring_round = -1;
+    r.ext = 1;   // there is a mask: the general pass-1 kernel, as in the single call
+    r.block_size = p->block_size; r.use_harris = p->use_harris ? 1 : 0; r.k = p->use_harris ? p->k : 0.0;
+    r.mask = base_mask_or_null; r.mask_stride = base_stride;
+    r.refill = 1; r.n_trk = n_tracks; r.radius = radius; r.trk_xy = track_xy; r.trk_prio = track_prio_or_null; r.out_keep = out_keep;
     return submit(ctx, E->queue[R_DET], &r);
 }
 

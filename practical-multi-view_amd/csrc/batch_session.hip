@@ -498,6 +498,14 @@ int pmv_batch_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null,
     return engine_detect_gftt_frame(S->eng, "pmv_batch_detect_gftt_frame", slot, roi4_or_null, max_corners, p, mask, mask_stride, out_xy, out_cap, out_count);
 }
 
+int pmv_batch_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const float* track_xy,
+                                 const int* track_prio_or_null, int n_tracks, int radius, const uint8_t* base_mask_or_null, int base_stride, uint8_t* out_keep,
+                                 int* out_xy, int out_cap, int* out_count) {
+    SESSION("pmv_batch_detect_gftt_refill");
+    return engine_detect_gftt_refill(S->eng, "pmv_batch_detect_gftt_refill", slot, roi4_or_null, max_corners, p, track_xy, track_prio_or_null, n_tracks, radius,
+                                     base_mask_or_null, base_stride, out_keep, out_xy, out_cap, out_count);
+}
+
 int pmv_batch_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix_params* p, uint8_t* out_iters, uint8_t* out_flags) {
     SESSION("pmv_batch_corner_subpix");
     return engine_corner_subpix(S->eng, "pmv_batch_corner_subpix", slot, xy, n, p, out_iters, out_flags);

@@ -97,6 +97,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(nullptr, "%s: %s", #x, hipGetErrorString(e_)); pmv_ctx_destroy(c); return PMV_ERR_HIP; } } while (0)
     CK(hipSetDevice(device));
     CK(frontend_prepare_device());
+    CK(refill_prepare_device());
     CK(backend_prepare_device());
     CK(hipStreamCreateWithFlags(&c->s_front, hipStreamNonBlocking));
     CK(hipStreamCreateWithFlags(&c->s_back, hipStreamNonBlocking));
@@ -751,6 +752,34 @@ size_t pmv::gftt_frame_record(int* rec, const int* roi4, int slot, size_t list_o
     rec[6] = (int)(unsigned)(list_off & 0xffffffffu); rec[7] = (int)(unsigned)(list_off >> 32);
     return mask ? gftt_pack_mask(dst, pos, rec, roi4, 1, mask, mask_stride) : pos;
 }
+int pmv::refill_check(pmv_ctx* ctx, const char* who, int slot, const float* track_xy, int n_tracks, int radius, const uint8_t* out_keep) {   // after gftt_frame_check: the slot is valid
+    static_assert(PMV_REFILL_MAX_TRACKS == REFILL_MAX_TRACKS && PMV_REFILL_MAX_RADIUS == REFILL_MAX_RADIUS, "the header's limits are the kernels'");
+    REQ(out_keep && (track_xy || n_tracks <= 0), PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(radius >= 0 && radius <= PMV_REFILL_MAX_RADIUS, PMV_ERR_INVALID, "%s: radius = %d is outside 0..%d", who, radius, PMV_REFILL_MAX_RADIUS);
+    const int max_n = std::min(ctx->max_tracks, PMV_REFILL_MAX_TRACKS);
+    REQ(n_tracks >= 0 && n_tracks <= max_n, PMV_ERR_CAPACITY, "%s: n_tracks = %d is outside 0..%d (max_tracks, PMV_REFILL_MAX_TRACKS)", who, n_tracks, max_n);
+    const PyrLayout& L = ctx->slot_layout[slot];
+    for (int i = 0; i < n_tracks; i++) {   // (a NaN fails the comparison too)
+        const float x = track_xy[2 * i], y = track_xy[2 * i + 1];
+        REQ(fabsf(x) <= 1e6f && fabsf(y) <= 1e6f, PMV_ERR_INVALID, "%s: track %d (%g, %g) is not finite or beyond 1e6", who, i, (double)x, (double)y);
+        const long px = lrintf(x), py = lrintf(y);   // cvRound: half to even
+        REQ(px >= 0 && px < L.w[0] && py >= 0 && py < L.h[0], PMV_ERR_INVALID, "%s: track %d rounds to the point (%ld, %ld), outside the %dx%d frame", who, i, px, py, L.w[0], L.h[0]);
+    }
+    return PMV_OK;
+}
+void pmv::refill_fill(const RefillBlock& B, size_t i, size_t trk_off, const int* roi4, size_t mask_off, const float* track_xy, const int* track_prio_or_null, int n_tracks,
+                      int radius, const uint8_t* base_mask_or_null, int base_stride) {
+    RefillRec& R = B.rec.h[i];
+    R = RefillRec{n_tracks, radius, (int)trk_off, roi4[0], roi4[1], roi4[2], roi4[3], (unsigned)mask_off, base_mask_or_null ? 1 : 0, {0, 0, 0}};
+    unsigned* pos = B.pos.h + trk_off; int* prio = B.prio.h + trk_off; uint8_t* flag = B.flag.h + trk_off;
+    for (int t = 0; t < n_tracks; t++) {
+        const int x = (int)lrintf(track_xy[2 * t]), y = (int)lrintf(track_xy[2 * t + 1]);
+        pos[t] = ((unsigned)y << 16) | (unsigned)x;
+        prio[t] = track_prio_or_null ? track_prio_or_null[t] : 0;
+        flag[t] = base_mask_or_null ? base_mask_or_null[(size_t)y * (size_t)base_stride + x] == 255 : 1;   // setMask tests `== 255`
+    }
+    refill_halfwidths(radius, B.hw.h + i * REFILL_HW);
+}
 int pmv::shitomasi_nothing(pmv_ctx* ctx, const int* cells, int n_cells, int* out_count) {   // ShiTomasiFeatureExtractor.cpp:37-44: `if (i >= max) break` before the first feature
     REQ(cells && out_count && n_cells >= 1 && n_cells <= MAX_CELLS, PMV_ERR_INVALID, "pmv_detect_shitomasi: bad argument");
     for (int i = 0; i < n_cells; i++) out_count[i] = 0;
@@ -903,6 +932,64 @@ int pmv_debug_gftt_frame_stats(pmv_ctx* ctx, long long* out6) {
     REQ(ctx && out6, PMV_ERR_INVALID, "pmv_debug_gftt_frame_stats: null argument");
     for (int i = 0; i < 5; i++) out6[i] = ctx->gftt_frame_stats[i].load();
     out6[5] = GFTT_FRAME_ONCHIP;
+    return PMV_OK;
+}
+// pmv_detect_gftt_frame with the mask made on the device from the caller's tracks: k_track_select and k_track_paint in front of the frame
+// kernels (the general pass 1: there is a mask), one wait. Only a base mask crosses the bus, packed as gftt_frame_record packs a mask.
+int pmv_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p, const float* track_xy,
+                           const int* track_prio_or_null, int n_tracks, int radius, const uint8_t* base_mask_or_null, int base_stride, uint8_t* out_keep,
+                           int* out_xy, int out_cap, int* out_count) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_detect_gftt_refill: null argument");
+    int roi[4], cap;
+    if (const int rc = gftt_frame_check(ctx, "pmv_detect_gftt_refill", true, slot, roi4_or_null, max_corners, p, base_mask_or_null, base_stride, out_xy, out_cap, out_count, roi, &cap)) return rc;
+    if (const int rc = refill_check(ctx, "pmv_detect_gftt_refill", slot, track_xy, n_tracks, radius, out_keep)) return rc;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const PyrLayout& L = ctx->slot_layout[slot];
+    const size_t pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3];
+    Carve need, rneed;
+    gftt_frame_block(need, 1, PMV_GFTT_FRAME_MAX_CORNERS);
+    refill_block(rneed, 1, PMV_REFILL_MAX_TRACKS);
+    CKC(ctx->h_gfr.ensure(need.bytes() + 64)); CKC(ctx->h_refill.ensure(rneed.bytes() + 64));
+    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
+    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
+    CKC(ctx->d_gfr_mask.ensure(pix + 64));   // (a dword of the painting may end behind the region's last byte)
+    CKC(ctx->d_refill_kept.ensure((size_t)PMV_REFILL_MAX_TRACKS * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(sizeof(int)));
+    if (base_mask_or_null) CKC(ctx->h_gfr_mask.ensure(pix));
+    Carve c = carve_of(ctx->h_gfr), rc2 = carve_of(ctx->h_refill);
+    const GfttFrameBlock B = gftt_frame_block(c, 1, (size_t)cap);
+    const RefillBlock T = refill_block(rc2, 1, refill_pad(n_tracks));
+    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, ctx->h_gfr_mask, 0, base_mask_or_null, base_stride);   // (mask offset 0 either way)
+    refill_fill(T, 0, 0, roi, 0, track_xy, track_prio_or_null, n_tracks, radius, base_mask_or_null, base_stride);
+    if (base_mask_or_null) { CKC(hipMemcpyAsync(ctx->d_gfr_mask, ctx->h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front)); ctx->refill_stats[3] += (long long)nb; }
+    CKC(launch_track_refill(ctx->s_front, T.rec.d, 1, rpix, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    const GfttExt X = gftt_ext(p->block_size, p->use_harris, p->k);
+    CKC(launch_gftt_frame(ctx->s_front, ctx->d_slots, L, B.rec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p->quality, p->min_dist, max_corners <= 0, &X, ctx->d_gfr_mask.get(),
+                          ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    ctx->refill_stats[0]++; ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];
+    const int n = B.count.h[0];
+    REQ(n >= 0, PMV_ERR_OVERFLOW, "pmv_detect_gftt_refill: more than out_cap = %d corners with max_corners <= 0 (no limit)", out_cap);
+    memcpy(out_keep, T.keep.h, (size_t)n_tracks);
+    memcpy(out_xy, B.xy.h, (size_t)n * 8);
+    *out_count = n;
+    return PMV_OK;
+}
+// diagnostic: the packed region mask the last pmv_detect_gftt_refill of this context painted (w * h tight bytes)
+int pmv_debug_refill_mask(pmv_ctx* ctx, uint8_t* out, long long cap, int* w, int* h) {
+    REQ(ctx && out && w && h, PMV_ERR_INVALID, "pmv_debug_refill_mask: null argument");
+    const long long nb = (long long)ctx->refill_last[0] * ctx->refill_last[1];
+    REQ(nb > 0, PMV_ERR_INVALID, "pmv_debug_refill_mask: no pmv_detect_gftt_refill call has been made on this context");
+    REQ(cap >= nb, PMV_ERR_CAPACITY, "pmv_debug_refill_mask: cap = %lld is below the %dx%d region's %lld bytes", cap, ctx->refill_last[0], ctx->refill_last[1], nb);
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    CKC(hipMemcpy(out, ctx->d_gfr_mask, (size_t)nb, hipMemcpyDeviceToHost));
+    *w = ctx->refill_last[0]; *h = ctx->refill_last[1];
+    return PMV_OK;
+}
+int pmv_debug_refill_stats(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_refill_stats: null argument");
+    for (int i = 0; i < 4; i++) out4[i] = ctx->refill_stats[i].load();
     return PMV_OK;
 }
 // diagnostic: on != 0 sends the default arguments of pmv_detect_gftt_ex through the general kernels as well (no result changes)

@@ -6,6 +6,7 @@
 //     pmv_detect_gftt_ex (block size 1..15, Harris, mask): the b*b-term double sum in raster order of tests/twin/gftt_twin.cpp.
 #include "pmv_device.h"
 #include "pmv_prof.h"
+#include "pmv_gfsort.h"
 #include <float.h>
 
 namespace pmv {
@@ -1923,7 +1924,6 @@ hipError_t launch_gftt_response_ex(hipStream_t s, const uint8_t* slots, const Py
 // than 8 tile rows blockIdx.x = tile row no longer says which. The launch is (8 * ceil(tiles_y / 8) * tiles_x, requests): its x extent is a
 // multiple of 8, so workgroup (b, r) runs on XCD b % 8 whatever r, and the k = b / 8-th workgroup of XCD x takes tile row x + 8 * (k /
 // tiles_x), column k % tiles_x: row t of every request lands on XCD t % 8. Workgroups past a request's last row leave at once.
-constexpr int GF_T = 1024;        // threads of the selection workgroup
 constexpr int GF_CAP = GFTT_FRAME_ONCHIP;   // records it sorts on chip: 128 KiB of the CU's 160 KiB of LDS as 64-bit keys
 constexpr size_t GF_LDS = (size_t)GF_CAP * 8 + (size_t)(2 * GF_T + 32) * 4;   // keys | survivors of a chunk | its accepted corners | counters
 __device__ __forceinline__ size_t gf_list_off(const int* __restrict__ r) { return (size_t)(unsigned)r[6] | ((size_t)(unsigned)r[7] << 32); }
@@ -1989,45 +1989,6 @@ __global__ __launch_bounds__(256) void k_gftt_cand_general_frame(const uint8_t* 
 //   distances: dx * dx + dy * dy is an integer, (double)d2 < min_dist^2 <=> d2 < ceil(min_dist^2); frames up to 32767 x 32767 keep it in an int.
 // out_count[request]: the number of corners, or -1 for a no-limit request (cap + 1 corners were looked for) that has more than cap.
 // stats: (records above the threshold, of those kept in HBM) per request.
-__device__ __forceinline__ void gf_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-// comparator q of a stage whose comparators span 2 << lh keys: (i, i + half), or in a flip stage (i, mirror image of i in its block)
-__device__ __forceinline__ void gf_cmpx(unsigned long long* keys, int n, int q, int lh, bool flip) {
-    const int half = 1 << lh;
-    const int i = ((q >> lh) << (lh + 1)) | (q & (half - 1));
-    const int l = flip ? (i ^ (2 * half - 1)) : (i + half);
-    if (l < n) {
-        const unsigned long long a = keys[i], b = keys[l];
-        if (a < b) { keys[i] = b; keys[l] = a; }
-    }
-}
-template <bool ONCHIP> __device__ __forceinline__ void gf_sort(unsigned long long* keys, int n, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    int ln2 = 1;
-    while ((1 << ln2) < n) ln2++;
-    const int pairs = 1 << (ln2 - 1);
-    for (int lk = 1; lk <= ln2; lk++) {              // merges of blocks of 2^lk keys: flip (lh = lk - 1), then lh = lk - 2 .. 0
-        int lh = lk - 1;
-        if (ONCHIP) {
-            for (; lh >= 10; lh--) {                 // comparators that cross the 1024-key blocks
-                for (int q = tid; q < pairs; q += GF_T) gf_cmpx(keys, n, q, lh, lh == lk - 1);
-                __syncthreads();
-            }
-            for (int b = wave; b * 1024 < n; b += GF_T / 64) {   // block b, 512 comparators a stage, is wavefront b % 16's in every such stage
-                for (int l2 = lh; l2 >= 0; l2--) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) gf_cmpx(keys, n, b * 512 + e * 64 + lane, l2, l2 == lk - 1);
-                    gf_wave_sync();
-                }
-            }
-            if (lk >= 10 || lk == ln2) __syncthreads();   // (merges below 1024 keys stay inside the blocks: nothing to wait for)
-        } else {
-            for (; lh >= 0; lh--) {
-                for (int q = tid; q < pairs; q += GF_T) gf_cmpx(keys, n, q, lh, lh == lk - 1);
-                __syncthreads();
-            }
-        }
-    }
-}
 // step 3 for min_dist >= 1; returns the number of accepted corners (<= limit), their (y << 16) | x in ((unsigned*)keys)[0 .. ), visible to all
 __device__ __forceinline__ int gf_walk(unsigned long long* keys, int n, int limit, int md2i, unsigned* s_surv, unsigned* s_new, unsigned* s_w, int tid) {
     const int lane = tid & 63, wave = tid >> 6;

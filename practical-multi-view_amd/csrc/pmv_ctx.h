@@ -96,6 +96,16 @@ struct pmv_ctx {
     // pmv_debug_gftt_frame_stats: frame calls served by the single entry point | session rounds with a frame request | launch pairs made for
     // them | records above the threshold in the last request served | of those kept off-chip
     std::atomic<long long> gftt_frame_stats[5];
+    // pmv_detect_gftt_refill, made by the first call (a context that never makes one pays nothing): the request's tracks in mapped pinned
+    // memory (refill_block at one request of PMV_REFILL_MAX_TRACKS tracks) and, in HBM, the kept list with its count. The region's mask is
+    // painted into d_gfr_mask, where pass 1 of the frame call reads it; h_gfr_mask is touched only when the caller gives a base mask.
+    pmv::Buf<uint8_t> h_refill{pmv::MEM_MAPPED};
+    pmv::Buf<unsigned> d_refill_kept;
+    pmv::Buf<int> d_refill_nkept;
+    int refill_last[2] = {0, 0};         // width and height of the region of the last single refill call (pmv_debug_refill_mask)
+    // pmv_debug_refill_stats: single refill calls | session rounds with a refill request | select + paint launch pairs made for them | bytes of
+    // mask copied host -> device by refill calls (base masks only)
+    std::atomic<long long> refill_stats[4];
     // pmv_corner_subpix, made by the first call (a context that never makes one pays nothing): one mapped pinned block [point records nt x 16 |
     // positions 2 nt floats | updates nt bytes | flags nt bytes], nt = max_tracks, and the weight table in HBM with the window and (effective)
     // zero zone it was computed for - a caller keeps its parameters, so the table crosses the bus once
@@ -207,6 +217,9 @@ int gftt_frame_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, cons
                      int mask_stride, const int* out_xy, int out_cap, const int* out_count, int* roi4, int* cap);
 // a frame request's device record at list entry `list_off`; with a mask its region's bytes go behind byte `pos` of dst (returns the new end)
 size_t gftt_frame_record(int* rec, const int* roi4, int slot, size_t list_off, uint8_t* dst, size_t pos, const uint8_t* mask, int mask_stride);
+// pmv_detect_gftt_refill / pmv_batch_detect_gftt_refill, after gftt_frame_check (with the base mask as its mask): the checks of the track
+// list, the radius and out_keep (`who` names the call in the messages)
+int refill_check(pmv_ctx* ctx, const char* who, int slot, const float* track_xy, int n_tracks, int radius, const uint8_t* out_keep);
 // pmv_corner_subpix / pmv_batch_corner_subpix: every check of the contract, in its order (`who` names the call in the messages)
 int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p);
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
@@ -253,6 +266,16 @@ struct GfttFrameBlock { Carved<int> rec, count, stats, xy; };
 inline GfttFrameBlock gftt_frame_block(Carve& c, size_t n_req, size_t cap) {
     return {c.take<int>(n_req * CELL_STRIDE), c.take<int>(n_req), c.take<int>(2 * n_req), c.take<int>(2 * n_req * cap, 16)};
 }
+// tables of a launch of n_req refill requests with n_trk track entries in all (the sum of the requests' refill_pad(n)):
+// [request records | positions | priorities | base flags | half-width tables | keep bytes]
+struct RefillBlock { Carved<RefillRec> rec; Carved<unsigned> pos; Carved<int> prio; Carved<uint8_t> flag, hw, keep; };
+inline RefillBlock refill_block(Carve& c, size_t n_req, size_t n_trk) {
+    return {c.take<RefillRec>(n_req, 16), c.take<unsigned>(n_trk), c.take<int>(n_trk), c.take<uint8_t>(n_trk), c.take<uint8_t>(n_req * REFILL_HW), c.take<uint8_t>(n_trk, 4)};
+}
+// request i of a refill block: its record (tracks at entry trk_off, region roi4, packed mask at byte mask_off), the rounded positions, the
+// priorities (null: all equal), the flag of every track (the base byte under it is 255; no base mask: all set) and the half-width table
+void refill_fill(const RefillBlock& B, size_t i, size_t trk_off, const int* roi4, size_t mask_off, const float* track_xy, const int* track_prio_or_null, int n_tracks,
+                 int radius, const uint8_t* base_mask_or_null, int base_stride);
 hipError_t frontend_prepare_device();   // per-device kernel attributes (LDS opt-in), called with the context's device current
 hipError_t backend_prepare_device();
 }

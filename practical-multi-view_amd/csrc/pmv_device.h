@@ -288,6 +288,36 @@ hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayou
                              double min_dist, int unlimited, const GfttExt* X, const uint8_t* d_mask, float* d_val, unsigned* d_idx, unsigned* d_info,
                              unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats);
 
+// ---- keep-away mask of a track list (frontend_refill.hip) ----------------------------------------------------------
+// pmv_detect_gftt_refill / pmv_batch_detect_gftt_refill: FeatureTracker::setMask on the device. One record per request; the tables of a
+// launch (positions, priorities, flags, keep bytes, kept lists) hold the requests' tracks one after the other, each request's share
+// starting at a multiple of four entries (refill_pad(n) entries long).
+constexpr int REFILL_MAX_TRACKS = 8192;    // = PMV_REFILL_MAX_TRACKS: keys and positions of a request stay in LDS
+constexpr int REFILL_MAX_RADIUS = 255;     // = PMV_REFILL_MAX_RADIUS: a half-width fits a byte
+constexpr int REFILL_HW = 256;             // bytes of a request's half-width table
+struct __attribute__((aligned(16))) RefillRec {
+    int n, radius;                // tracks, cv::circle's radius
+    int trk_off;                  // first entry of the request in the launch's per-track tables (a multiple of 4)
+    int x0, y0, cw, ch;           // the region that is painted (frame coordinates)
+    unsigned mask_off;            // byte offset of the region's packed mask (cw * ch bytes) in the mask buffer, a multiple of 4
+    int has_base;                 // the packed mask holds the caller's base bytes (else it is painted from 255)
+    int reserved[3];
+};
+static_assert(sizeof(RefillRec) == 48, "RefillRec: one 48-byte record per request");
+inline size_t refill_pad(int n) { return ((size_t)n + 3) & ~(size_t)3; }
+// cv::circle(.., radius, .., -1)'s rows as half-widths: out[d], d = 0 .. radius, is the widest span Circle()'s loop paints at row offset d;
+// out[d] for d above the radius = 255 (never read as a width: the kernels test the row offset first). Computed on the HOST by the literal
+// loop (OpenCV 3.4 drawing.cpp, fill, LINE_8, shift 0) and handed to the kernels, the policy of subpix_table.
+void refill_halfwidths(int radius, uint8_t out[REFILL_HW]);
+// k_track_select (one workgroup per request) then k_track_paint (grid over the largest packed region x requests) over n_req records in
+// device-visible memory. d_pos: (y << 16) | x per track; d_prio: int priorities; d_flag: non-zero = the base byte under the track is 255;
+// d_hw: REFILL_HW bytes per request. Outputs: d_keep (one byte per track, input order; device-visible), d_kept / d_nkept (the kept
+// positions in rank order and their number: HBM, read by the painting) and the requests' packed masks in d_mask (which holds the base
+// bytes of the requests that have some). max_bytes = the largest cw * ch among the requests. Booked under K_GFTT_PICK and K_GFTT_CAND.
+hipError_t launch_track_refill(hipStream_t s, const RefillRec* d_recs, int n_req, size_t max_bytes, const unsigned* d_pos, const int* d_prio, const uint8_t* d_flag,
+                               const uint8_t* d_hw, uint8_t* d_keep, unsigned* d_kept, int* d_nkept, uint8_t* d_mask);
+hipError_t refill_prepare_device();   // LDS opt-in of k_track_select, per device (see frontend_prepare_device)
+
 // ---- corner sub-pixel refinement (frontend_subpix.hip) -----------------------------------------------------------
 // pmv_corner_subpix / pmv_batch_corner_subpix: one point of a launch names its frame slot and, in the table form, its entry of the geometry
 // table, as LK's track records do: one launch serves points of several slots and frame sizes. Results go to the record's own index.
