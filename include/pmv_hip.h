@@ -408,7 +408,7 @@ int pmv_debug_gftt_frame_stats(pmv_ctx* ctx, long long* out6);
  *   n_tracks == 0 is legal: the mask is the base mask, or all 255.
  * The buffers are made by the first refill call on a context. The call is not logged by pmv_record_enable.
  * Out of scope: non-filled or anti-aliased circles; a per-track radius; returning the mask outside pmv_debug_refill_mask; feeding the
- *   kept tracks onward on the device; the whole-sequence drivers (pmv_pipeline_run*) and bench.py do not call this. */
+ *   kept tracks onward on the device (that is pmv_klt_step below, which runs these kernels inside its chain); the whole-sequence drivers (pmv_pipeline_run*) and bench.py do not call this. */
 #define PMV_REFILL_MAX_TRACKS 8192
 #define PMV_REFILL_MAX_RADIUS 255
 int pmv_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int max_corners, const pmv_gftt_params* p,
@@ -716,6 +716,68 @@ int pmv_debug_fundamental_r(void);
 /* diagnostic: out3 = {k_fundamental_ransac launches, k_essential_ransac launches, rounds that made both} of the five-point combiner's
  * whole-RANSAC rounds (pmv_batch_find_fundamental_mat, pmv_batch_find_essential_mat, device_fivepoint = 2) since the context was created. */
 int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3);
+
+/* ---- A device-resident KLT tracker: one call per frame, the tracks stay in HBM ------------------------------------------------------------
+ * A tracker lives in the context and holds n <= target tracks, each an (id, age, xy) triple - xy float32 in the coordinates of the frame the
+ * last step ran on - and next_id. A new tracker is empty with next_id = 0. pmv_klt_step runs the per-frame chain of a VINS-style front end
+ * in ONE call; it is defined as a composition, bit for bit, of the single calls above plus the small policy stated here. No arithmetic of
+ * LK, the F RANSAC, setMask, the detector or cornerSubPix changes; LK's parameters come from the context (pmv_set_lk_params).
+ * The seven stages, n0 = the state's n ("=" means the same bytes):
+ *   1. Track (skipped when n0 = 0; prev_slot is then ignored): fb_max_dist >= 0 - the outputs of pmv_lk_track_fb(prev_slot, cur_slot, state
+ *      xy, flags 0); else those of pmv_lk_track_ex(.., flags 0). The launch uses the identity track order; the order changes no result.
+ *   2. Filter: track i survives iff status[i] == 1, with fb on also back_status[i] == 1 and dx * dx + dy * dy <= thr2 (dx = back.x - prev.x,
+ *      dy likewise; both products and the sum float32 operations without contraction; thr2 = (float)(fb_max_dist * fb_max_dist), computed
+ *      on the host), and its forward position is inside the border: ix = lrintf(x), iy = lrintf(y) (round half to even),
+ *      border <= ix < w - border and border <= iy < h - border. Stable compaction; survivors get age += 1; their count is n1.
+ *   3. rejectWithF (only if reject_f and n1 >= 15): pmv_find_fundamental_mat(prev xy of the survivors, cur xy of the survivors, n1,
+ *      f_threshold, f_confidence); tracks with mask 0 go. No model: cv's status is all zero, so ALL go, as the VINS loop does with cv's
+ *      output. Otherwise nothing happens and counts[5] = -1. Stable compaction; the count is n2.
+ *   4. Thin: out_keep of pmv_detect_gftt_refill(cur_slot, roi NULL, .., the n2 cur positions in list order, prio NULL, n2, radius, base
+ *      NULL) - the list is age-descending by construction, so this is setMask's order. Tracks not kept go; the count is n3.
+ *   5. Refill (only if target - n3 > 0): the corners of the same refill call with max_corners = target - n3 (out_keep does not depend on
+ *      max_corners); m corners, positions (float)x, (float)y.
+ *   6. Refine (only if subpix and m > 0): pmv_corner_subpix(cur_slot, the m corners, subpix_params).
+ *   7. Append: the m new tracks come after the survivors, in detector order, with ids next_id .. next_id + m - 1 and age 1; next_id += m.
+ * Outputs: *out_n = n3 + m <= target; the list in out_ids, out_ages, out_xy (2 floats a track); out_prev_xy (may be NULL): the position in
+ *   the previous frame, for a new track its own xy; out_counts8 = {n0, n1, n2, n3, m, f_found (-1 not run / 0 / 1), f_samples_drawn, 0}.
+ *   The state becomes the output.
+ * pmv_klt_set_tracks replaces the state (n in 0..target, else PMV_ERR_CAPACITY; a null array with n > 0, next_id < 0 or a coordinate that
+ *   is not finite or beyond 1e6 in magnitude: PMV_ERR_INVALID; the state is kept on an error); pmv_klt_get_tracks reads it (cap < n:
+ *   PMV_ERR_CAPACITY).
+ * Device side: the kernels hand the counts to each other through device memory, the host never learns the intermediate lists. With reject_f
+ *   = 0 a step waits ONCE; with reject_f = 1 at most twice - the first wait reads the single word n1, because the F kernel's iteration
+ *   table (libm's pow and log) depends on it. Only request records, that table and the result block cross the bus. The scratch of a step
+ *   is the tracker's own or the context's and is rewritten by every step: single calls between two steps return their usual bytes and do
+ *   not disturb the next step, and neither do other trackers of the context.
+ * Errors (nothing is written, nothing is clamped, the state is unchanged): PMV_ERR_INVALID - a null argument, an unknown id; at
+ *   pmv_klt_create target < 1, border outside 0..64, fb_max_dist not finite or above 1e3, reject_f or subpix other than 0 / 1, radius
+ *   outside 0..PMV_REFILL_MAX_RADIUS, and the parameter errors of pmv_find_fundamental_mat (if reject_f), pmv_detect_gftt_frame and
+ *   pmv_corner_subpix (if subpix), each with that call's code and wording; PMV_ERR_CAPACITY - target above min(max_tracks,
+ *   PMV_REFILL_MAX_TRACKS), a 17th tracker, out_cap < target; the slot errors of pmv_lk_track and pmv_detect_gftt_frame (range, empty
+ *   slot, differing sizes, open bracket). pmv_ctx_destroy frees the trackers that are left. Not logged by pmv_record_enable; legal during
+ *   a batch session under the caller's slot rule, like the other single calls.
+ * Out of scope: the session form (pmv_batch_klt_*), a region or base mask, an initial-flow prediction, per-track radius, LMedS or 8-point
+ *   for n1 < 15, undistorting points before F (callers with a lens remap the frames first), id wrap-around. */
+#define PMV_KLT_MAX_TRACKERS 16
+typedef struct pmv_klt_params {
+    int    target;          /* MAX_CNT: tracks wanted after a step; 1 .. min(ctx max_tracks, PMV_REFILL_MAX_TRACKS) */
+    int    border;          /* BORDER_SIZE of inBorder; 0 .. 64 */
+    double fb_max_dist;     /* < 0: no backward pass (pmv_lk_track_ex); else finite, 0 .. 1e3: forward-backward check */
+    int    reject_f;        /* 0 / 1 */
+    double f_threshold, f_confidence;   /* as pmv_find_fundamental_mat; read only if reject_f */
+    int    radius;          /* setMask's circle radius, 0 .. PMV_REFILL_MAX_RADIUS */
+    pmv_gftt_params gftt;   /* the detector's arguments, as pmv_detect_gftt_frame */
+    int    subpix;          /* 0 / 1: refine the new corners */
+    pmv_subpix_params subpix_params;    /* read only if subpix */
+} pmv_klt_params;
+int pmv_klt_create(pmv_ctx* ctx, const pmv_klt_params* p, int* out_id);
+int pmv_klt_destroy(pmv_ctx* ctx, int id);
+int pmv_klt_set_tracks(pmv_ctx* ctx, int id, const int* ids, const int* ages, const float* xy, int n, int next_id);
+int pmv_klt_get_tracks(pmv_ctx* ctx, int id, int* ids, int* ages, float* xy, int cap, int* out_n);
+int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null,
+                 int out_cap, int* out_n, int* out_counts8);
+/* diagnostic: out4 = {steps, host waits inside steps, kernel launches inside steps, trackers alive} since the context was created */
+int pmv_debug_klt_stats(pmv_ctx* ctx, long long* out4);
 
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those

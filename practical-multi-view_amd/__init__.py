@@ -51,6 +51,75 @@ class ClaheParams(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
 
 
+KLT_MAX_TRACKERS = 16   # PMV_KLT_MAX_TRACKERS of include/pmv_hip.h
+
+
+class KltParams(C.Structure):
+    """pmv_klt_params of include/pmv_hip.h"""
+    _fields_ = [("target", C.c_int), ("border", C.c_int), ("fb_max_dist", C.c_double), ("reject_f", C.c_int), ("f_threshold", C.c_double),
+                ("f_confidence", C.c_double), ("radius", C.c_int), ("gftt", GfttParams), ("subpix", C.c_int), ("subpix_params", SubpixParams)]
+
+
+def klt_params(target=150, border=1, fb_max_dist=0.5, reject_f=True, f_threshold=1.0, f_confidence=0.99, radius=10, quality=0.01, min_dist=10.0, block_size=3,
+               use_harris=False, k=0.04, subpix=False, subpix_win=(5, 5), subpix_zero_zone=(-1, -1), subpix_max_iter=30, subpix_eps=0.01):
+    """a KltParams from keywords; the defaults are a VINS-style front end's (MAX_CNT 150, BORDER_SIZE 1, F_THRESHOLD 1.0, MIN_DIST 10).
+    fb_max_dist None or negative: no backward pass."""
+    return KltParams(int(target), int(border), -1.0 if fb_max_dist is None else float(fb_max_dist), int(reject_f), float(f_threshold), float(f_confidence), int(radius),
+                     GfttParams(float(quality), float(min_dist), int(block_size), 1 if use_harris else 0, float(k)), int(subpix),
+                     SubpixParams(int(subpix_win[0]), int(subpix_win[1]), int(subpix_zero_zone[0]), int(subpix_zero_zone[1]), int(subpix_max_iter), float(subpix_eps)))
+
+
+class KltTracker:
+    """A tracker of Context.klt_create. The state - ids, ages, positions - lives in device memory; step() returns the new list."""
+
+    def __init__(self, ctx, tid, target):
+        self.ctx, self.id, self.target = ctx, tid, target
+
+    def step(self, prev_slot, cur_slot):
+        """pmv_klt_step: (ids (n,) int32, ages (n,) int32, xy (n, 2) float32, prev_xy (n, 2) float32, counts (8,) int32 = n0, n1, n2, n3, m,
+        f_found (-1: not run), f_samples_drawn, 0)"""
+        ctx, cap = self.ctx, self.target
+        ids, ages = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        xy, prev = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        counts = np.zeros(8, np.int32)
+        n = C.c_int(0)
+        fn = ctx.lib.pmv_klt_step
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, C.c_int, C.POINTER(C.c_int), _i32p]
+        ctx._ck(fn(ctx.h, self.id, int(prev_slot), int(cur_slot), _p(ids, _i32p), _p(ages, _i32p), _p(xy, _f32p), _p(prev, _f32p), cap, C.byref(n), _p(counts, _i32p)))
+        k = n.value
+        return ids[:k].copy(), ages[:k].copy(), xy[:k].copy(), prev[:k].copy(), counts
+
+    def set_tracks(self, ids, ages, xy, next_id):
+        """pmv_klt_set_tracks: replace the state"""
+        ids, ages = np.ascontiguousarray(ids, np.int32).reshape(-1), np.ascontiguousarray(ages, np.int32).reshape(-1)
+        xy = np.ascontiguousarray(xy, np.float32)
+        if xy.size and (xy.ndim != 2 or xy.shape[1] != 2):
+            raise ValueError("set_tracks: xy must be an (n, 2) float32 array")
+        n = xy.size // 2
+        if ids.size != n or ages.size != n:
+            raise ValueError("set_tracks: one id and one age per track")
+        fn = self.ctx.lib.pmv_klt_set_tracks
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_int]
+        self.ctx._ck(fn(self.ctx.h, self.id, _p(ids, _i32p) if n else None, _p(ages, _i32p) if n else None, _p(xy, _f32p) if n else None, n, int(next_id)))
+
+    def get_tracks(self):
+        """pmv_klt_get_tracks: (ids, ages, xy) of the state"""
+        cap = self.target
+        ids, ages, xy = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32)
+        n = C.c_int(0)
+        fn = self.ctx.lib.pmv_klt_get_tracks
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.POINTER(C.c_int)]
+        self.ctx._ck(fn(self.ctx.h, self.id, _p(ids, _i32p), _p(ages, _i32p), _p(xy, _f32p), cap, C.byref(n)))
+        return ids[: n.value].copy(), ages[: n.value].copy(), xy[: n.value].copy()
+
+    def close(self):
+        """pmv_klt_destroy"""
+        if self.id is not None and self.ctx.h:
+            self.ctx.lib.pmv_klt_destroy.argtypes = [C.c_void_p, C.c_int]
+            self.ctx._ck(self.ctx.lib.pmv_klt_destroy(self.ctx.h, self.id))
+        self.id = None
+
+
 def _clahe_params(who, clip_limit, tiles):
     # refused before the library is touched: what the struct cannot hold as the caller meant it
     if isinstance(clip_limit, (bool, np.bool_)) or not isinstance(clip_limit, (int, float, np.integer, np.floating)):
@@ -195,6 +264,7 @@ ABI_SYMBOLS = [
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
+    "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -1091,6 +1161,23 @@ class Context:
         """cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence, mask) for n >= 15 float32 correspondences, the whole RANSAC in one
         launch (a KLT loop's rejectWithF): (found, F (3, 3), mask (n,), samples drawn); found False = no model (F zeros, mask all 0)"""
         return self._find_fundamental(self.lib.pmv_find_fundamental_mat, self._ck, (), p1, p2, threshold, confidence)
+
+    # ---- device-resident KLT tracker ----
+    def klt_create(self, **params):
+        """pmv_klt_create: a KltTracker whose track list stays on the device; one step() per frame runs LK (forward-backward), the filter,
+        rejectWithF, setMask thinning, the masked detection, the optional sub-pixel refinement and the append. Keywords: klt_params()'s."""
+        p = klt_params(**params)
+        tid = C.c_int(-1)
+        self.lib.pmv_klt_create.argtypes = [C.c_void_p, C.POINTER(KltParams), C.POINTER(C.c_int)]
+        self._ck(self.lib.pmv_klt_create(self.h, C.byref(p), C.byref(tid)))
+        return KltTracker(self, tid.value, p.target)
+
+    def debug_klt_stats(self):
+        """pmv_debug_klt_stats: [steps, host waits inside steps, kernel launches inside steps, trackers alive]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_klt_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_klt_stats(self.h, out))
+        return [int(v) for v in out]
 
     # ---- call log (teacher-forced replay) ----
     def record_enable(self, on=True):

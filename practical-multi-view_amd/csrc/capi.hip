@@ -142,6 +142,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->clahe_launches) a.store(0);
     for (auto& a : c->remap_launches) a.store(0);
     for (auto& a : c->preproc_launches) a.store(0);
+    for (auto& a : c->klt_stats) a.store(0);
     int rc = backend_create(c);
     if (rc != PMV_OK) { snprintf(g_create_err, sizeof(g_create_err), "%s", c->err); pmv_ctx_destroy(c); return rc; }
 #undef CK
@@ -158,6 +159,7 @@ void pmv_ctx_destroy(pmv_ctx* c) {
     batch_ingest_destroy(c->bingest);
     if (c->s_front) hipStreamSynchronize(c->s_front);
     if (c->s_back) hipStreamSynchronize(c->s_back);
+    klt_destroy_all(c);
     backend_destroy(c);
     c->prof.destroy();
     if (c->s_front) hipStreamDestroy(c->s_front);
@@ -800,11 +802,15 @@ size_t pmv::gftt_pack_mask(uint8_t* dst, size_t pos, int* cell_recs, const int* 
     }
     return pos;
 }
-int pmv::subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p) {
-    REQ(p && (n == 0 || xy), PMV_ERR_INVALID, "%s: null argument", who);
+int pmv::subpix_params_check(pmv_ctx* ctx, const char* who, const pmv_subpix_params* p) {
     REQ(p->win_w >= 1 && p->win_w <= SUBPIX_MAX_WIN && p->win_h >= 1 && p->win_h <= SUBPIX_MAX_WIN, PMV_ERR_INVALID, "%s: win = (%d, %d) is outside 1..%d", who, p->win_w, p->win_h, SUBPIX_MAX_WIN);
     REQ(p->max_iter >= 1 && p->max_iter <= 100, PMV_ERR_INVALID, "%s: max_iter = %d is outside 1..100", who, p->max_iter);
     REQ(p->eps >= 0.0 && std::isfinite(p->eps), PMV_ERR_INVALID, "%s: eps = %g is negative or not finite", who, p->eps);   // (a NaN fails the comparison too)
+    return PMV_OK;
+}
+int pmv::subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p) {
+    REQ(p && (n == 0 || xy), PMV_ERR_INVALID, "%s: null argument", who);
+    if (const int rc_ = subpix_params_check(ctx, who, p)) return rc_;
     REQ(n >= 0 && n <= ctx->max_tracks, PMV_ERR_CAPACITY, "%s: n=%d exceeds max_tracks=%d", who, n, ctx->max_tracks);
     REQ(slot >= 0 && slot < ctx->n_slots, PMV_ERR_CAPACITY, "%s: slot out of range", who);
     if (const int rc_ = bracket ? slot_ready(ctx, slot, ctx->ingest, 0, ctx->s_front) : slot_ready(ctx, slot)) return rc_;

@@ -2046,7 +2046,7 @@ __device__ __forceinline__ int gf_walk(unsigned long long* keys, int n, int limi
 __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict__ recs, const float* __restrict__ cand_val, const unsigned* __restrict__ cand_idx,
                                                           const unsigned* __restrict__ info, unsigned long long* __restrict__ gkeys, int cap, double quality,
                                                           double min_dist, int unlimited, int* __restrict__ out_xy, int* __restrict__ out_count,
-                                                          int* __restrict__ stats) {
+                                                          int* __restrict__ stats, const int* __restrict__ cap_dev) {
     extern __shared__ unsigned long long gf_lds[];
     unsigned long long* lkey = gf_lds;                    // [GF_CAP]
     unsigned* s_surv = (unsigned*)(lkey + GF_CAP);        // [GF_T]
@@ -2087,7 +2087,11 @@ __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict_
     const bool use_dist = min_dist >= 1.0;
     const double md2 = min_dist * min_dist;
     const int md2i = (int)(md2 < 2.0e9 ? ceil(md2) : 2.0e9);
-    const int limit = unlimited ? cap + 1 : cap;
+    // cap_dev (the tracker's chain): the number of corners wanted is known only on the device - clamped to the list's capacity `cap`, which
+    // still places the list; 0 selects nothing
+    int want = cap;
+    if (cap_dev) { const int c = *cap_dev; want = c < 0 ? 0 : (c < cap ? c : cap); }
+    const int limit = unlimited ? want + 1 : want;
     int na;
     if (n <= GF_CAP) {
         if (n > 1) gf_sort<true>(lkey, n, tid);
@@ -2099,7 +2103,7 @@ __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict_
         na = use_dist ? gf_walk(gk, n, limit, md2i, s_surv, s_new, s_w, tid) : (n < limit ? n : limit);
     }
     const unsigned long long* keys = n <= GF_CAP ? lkey : gk;
-    const bool over = unlimited && na > cap;
+    const bool over = unlimited && na > want;
     if (!over)
         for (int i = tid; i < na; i += GF_T) {
             typedef unsigned __attribute__((may_alias)) acc_t;
@@ -2112,7 +2116,7 @@ __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict_
 int gftt_frame_grid_x(int w, int h) { const int tx = (w + 31) / 32, ty = (h + 31) / 32; return 8 * ((ty + 7) / 8) * tx; }
 hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_recs, int n_req, int grid_x, int cap, double quality,
                              double min_dist, int unlimited, const GfttExt* X, const uint8_t* d_mask, float* d_val, unsigned* d_idx, unsigned* d_info,
-                             unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats) {
+                             unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats, const int* d_cap) {
     if (!slots || !d_recs || !d_val || !d_idx || !d_info || !d_keys || !d_out_xy || !d_out_count || !d_stats || n_req < 1 || n_req > 65535 || grid_x < 8 || (grid_x & 7) ||
         cap < 1 || cap > GF_CAP || (X && !gftt_ext_ok(*X)) || (d_mask && !X)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(d_info, 0, 2 * sizeof(unsigned) * n_req, s);
@@ -2122,7 +2126,7 @@ hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayou
     else hipLaunchKernelGGL(k_gftt_cand_frame, dim3(grid_x, n_req), dim3(256), 0, s, slots, L, d_recs, d_val, d_idx, d_info, quality); }
     ProfScope ps2(K_GFTT_PICK, s);
     hipLaunchKernelGGL(k_gftt_pick_frame, dim3(n_req), dim3(GF_T), GF_LDS, s, d_recs, d_val, d_idx, d_info, d_keys, cap, quality, min_dist, unlimited, d_out_xy,
-                       d_out_count, d_stats);
+                       d_out_count, d_stats, d_cap);
     return hipGetLastError();
 }
 

@@ -1,0 +1,486 @@
+// pmv_klt_*: a KLT tracker that lives in the context (contract: include/pmv_hip.h). The track list (id, age, position) stays in device memory
+// from frame to frame; pmv_klt_step enqueues the whole per-frame chain on the front-end stream - forward-backward LK, filter, rejectWithF,
+// setMask thinning, masked detection, sub-pixel refinement, append - and waits once (twice with rejectWithF: the host needs n1 for libm's
+// iteration table). The existing kernels run as they are, on the tracker's device buffers; the three kernels here are the glue that the
+// host did between the single calls: each is ONE 1024-thread workgroup that compacts a list in order (wave ballots, a prefix over the
+// wavefronts in LDS, chunks of 1024 tracks) and leaves its count in device memory, where the launches behind it read it - the n of the
+// refill record, the cap of the selection pass, the point count of the sub-pixel launch. Every count read from device memory is clamped to
+// its buffer's capacity before it bounds a loop.
+#include "pmv_ctx.h"
+#include "backend.h"
+#include "vo_pipeline.h"
+#include <cmath>
+#include <cstring>
+
+namespace pmv {
+
+namespace {
+
+constexpr int KT = 1024, KW = KT / 64;
+// counts of a step in device memory: n0, n1, n2, n3, corners wanted (target - n3), corners found (k_gftt_pick_frame's count), its two statistics
+enum { C_N0 = 0, C_N1, C_N2, C_N3, C_WANT, C_M, C_STAT0, C_STAT1, C_COUNT = 16 };
+
+struct KltList { int* id; int* age; float* prev; float* cur; };                     // a track list on its way through the chain
+struct KltRefillIn { unsigned* pos; int* prio; uint8_t* flag; RefillRec* rec; };    // what k_track_select reads (pos null: not written)
+
+// Stable compaction of the items i < n with pred(i), by the whole workgroup: emit(i, o) is called once per survivor with its place o.
+// Returns the number of survivors (in every thread). n is uniform over the workgroup; s_w: KW words of LDS.
+template <class Pred, class Emit>
+__device__ __forceinline__ int klt_compact(int n, unsigned* s_w, Pred pred, Emit emit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int done = 0;
+    for (int base = 0; base < n; base += KT) {
+        const int i = base + tid;
+        const bool p = i < n && pred(i);
+        const unsigned long long bal = __ballot(p);
+        if (lane == 0) s_w[wave] = (unsigned)__popcll(bal);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w2 = 0; w2 < KW; w2++) { const int c = (int)s_w[w2]; off += w2 < wave ? c : 0; tot += c; }
+        if (p) emit(i, done + off + __popcll(bal & ((1ull << lane) - 1ull)));
+        __syncthreads();   // (the next chunk rewrites the wavefronts' counts)
+        done += tot;
+    }
+    return done;
+}
+// the rounded position as k_track_select takes it: cvRound (half to even); the track passed the border test, so it lies inside the frame
+__device__ __forceinline__ void klt_refill_in(const KltRefillIn& rf, int o, float x, float y) {
+    rf.pos[o] = ((unsigned)__float2int_rn(y) << 16) | (unsigned)__float2int_rn(x);
+    rf.prio[o] = 0;
+    rf.flag[o] = 1;
+}
+__device__ __forceinline__ int klt_clamp(int v, int hi) { return v < 0 ? 0 : (v < hi ? v : hi); }
+
+// Stage 2: the status bytes, the forward-backward distance and inBorder, then the compaction of (id, age + 1, prev xy, cur xy). n1 goes to
+// the counts, to the refill record (a chain without rejectWithF goes on with k_track_select) and to the host's word in mapped pinned memory.
+struct KltFilterArgs {
+    int n0, fb, border, w, h;
+    float thr2;
+    const int* id; const int* age; const float* prev; const float* fwd; const float* back; const uint8_t* st; const uint8_t* bst;
+    KltList out; KltRefillIn rf;
+    int* cnt; int* h_n1;
+};
+__global__ __launch_bounds__(KT) void k_klt_filter(KltFilterArgs A) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    const float lo = (float)A.border, hx = (float)(A.w - A.border), hy = (float)(A.h - A.border);
+    const int n1 = klt_compact(A.n0, s_w,
+        [&](int i) {
+            bool ok = A.st[i] == 1;
+            if (A.fb) {
+                const float dx = __fsub_rn(A.back[2 * i], A.prev[2 * i]), dy = __fsub_rn(A.back[2 * i + 1], A.prev[2 * i + 1]);
+                ok = ok && A.bst[i] == 1 && __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= A.thr2;
+            }
+            // rintf: half to even; the comparison in float is lrintf's in int for every finite value, and a NaN fails it
+            const float rx = rintf(A.fwd[2 * i]), ry = rintf(A.fwd[2 * i + 1]);
+            return ok && rx >= lo && rx < hx && ry >= lo && ry < hy;
+        },
+        [&](int i, int o) {
+            const float x = A.fwd[2 * i], y = A.fwd[2 * i + 1];
+            A.out.id[o] = A.id[i]; A.out.age[o] = A.age[i] + 1;
+            A.out.prev[2 * o] = A.prev[2 * i]; A.out.prev[2 * o + 1] = A.prev[2 * i + 1];
+            A.out.cur[2 * o] = x; A.out.cur[2 * o + 1] = y;
+            klt_refill_in(A.rf, o, x, y);
+        });
+    if (threadIdx.x == 0) {
+        A.cnt[C_N0] = A.n0; A.cnt[C_N1] = n1; A.cnt[C_N2] = n1;
+        A.rf.rec->n = n1;
+        *A.h_n1 = n1;
+        __threadfence_system();
+    }
+}
+
+// Stages 3 and 4: the same compaction driven by a byte mask - the F mask (then it also writes what k_track_select reads and the n of the
+// refill record) or the keep bytes (then it leaves the number of corners wanted, target - n3, for the selection pass).
+struct KltCompactArgs {
+    KltList in, out;
+    const uint8_t* mask; const int* n_in;
+    int cap, cnt_out, target;       // cnt_out: the count's place (C_N2 or C_N3); target > 0: C_WANT is written too
+    KltRefillIn rf;
+    int* cnt;
+};
+__global__ __launch_bounds__(KT) void k_klt_compact(KltCompactArgs A) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    const int n = klt_clamp(*A.n_in, A.cap);
+    const int no = klt_compact(n, s_w,
+        [&](int i) { return A.mask[i] != 0; },
+        [&](int i, int o) {
+            const float x = A.in.cur[2 * i], y = A.in.cur[2 * i + 1];
+            A.out.id[o] = A.in.id[i]; A.out.age[o] = A.in.age[i];
+            A.out.prev[2 * o] = A.in.prev[2 * i]; A.out.prev[2 * o + 1] = A.in.prev[2 * i + 1];
+            A.out.cur[2 * o] = x; A.out.cur[2 * o + 1] = y;
+            if (A.rf.pos) klt_refill_in(A.rf, o, x, y);
+        });
+    if (threadIdx.x == 0) {
+        A.cnt[A.cnt_out] = no;
+        if (A.rf.pos) A.rf.rec->n = no;
+        if (A.target > 0) A.cnt[C_WANT] = klt_clamp(A.target - no, A.target);
+    }
+}
+
+// Stage 7: survivors, then the m new tracks in detector order (ids next_id .., age 1, prev = their own position), into the state and into
+// the result block in mapped pinned memory; the completion word is the last store.
+struct KltAppendArgs {
+    KltList in;
+    const int* cnt; const int* ixy; const float* sp_xy; const int* f_info;   // sp_xy: the refined corners or null; f_info: (found, drawn) or null
+    int n0, next_id, target;
+    unsigned seq;
+    int* s_id; int* s_age; float* s_xy;
+    int* r_hdr; int* r_id; int* r_age; float* r_xy; float* r_prev;
+};
+__global__ __launch_bounds__(KT) void k_klt_append(KltAppendArgs A) {
+    BACKEND_PRIO();
+    const int tid = threadIdx.x;
+    const int n3 = klt_clamp(A.cnt[C_N3], A.target), m = klt_clamp(A.cnt[C_M], A.target - n3);
+    for (int i = tid; i < n3; i += KT) {
+        const int id = A.in.id[i], age = A.in.age[i];
+        const float x = A.in.cur[2 * i], y = A.in.cur[2 * i + 1];
+        A.s_id[i] = id; A.s_age[i] = age; A.s_xy[2 * i] = x; A.s_xy[2 * i + 1] = y;
+        A.r_id[i] = id; A.r_age[i] = age; A.r_xy[2 * i] = x; A.r_xy[2 * i + 1] = y;
+        A.r_prev[2 * i] = A.in.prev[2 * i]; A.r_prev[2 * i + 1] = A.in.prev[2 * i + 1];
+    }
+    for (int j = tid; j < m; j += KT) {
+        const int o = n3 + j, id = A.next_id + j;
+        const float x = A.sp_xy ? A.sp_xy[2 * j] : (float)A.ixy[2 * j], y = A.sp_xy ? A.sp_xy[2 * j + 1] : (float)A.ixy[2 * j + 1];
+        A.s_id[o] = id; A.s_age[o] = 1; A.s_xy[2 * o] = x; A.s_xy[2 * o + 1] = y;
+        A.r_id[o] = id; A.r_age[o] = 1; A.r_xy[2 * o] = x; A.r_xy[2 * o + 1] = y;
+        A.r_prev[2 * o] = x; A.r_prev[2 * o + 1] = y;
+    }
+    if (tid == 0) {
+        A.r_hdr[0] = A.n0; A.r_hdr[1] = A.cnt[C_N1]; A.r_hdr[2] = A.cnt[C_N2]; A.r_hdr[3] = n3; A.r_hdr[4] = m;
+        A.r_hdr[5] = A.f_info ? A.f_info[0] : -1; A.r_hdr[6] = A.f_info ? A.f_info[1] : 0; A.r_hdr[7] = 0;
+        A.r_hdr[8] = n3 + m;
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store((unsigned*)(A.r_hdr + 9), A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- the tracker's blocks, each described once ---------------------------------------------------------------------------------------
+// device block: state | identity order | LK results | the two lists of the chain | refill tables | F result | counts | corners | refined corners
+struct KltDev {
+    Carved<int> s_id, s_age; Carved<float> s_xy;
+    Carved<int> order;
+    Carved<float> lk_xy, lk_err, bk_xy, bk_err; Carved<uint8_t> lk_st, bk_st;
+    Carved<int> l_id[2], l_age[2]; Carved<float> l_prev[2], l_cur[2];
+    Carved<unsigned> pos; Carved<int> prio; Carved<uint8_t> flag, keep;
+    Carved<char> f_out;
+    Carved<int> cnt, ixy;
+    Carved<float> sp_xy; Carved<uint8_t> sp_it, sp_fl;
+};
+KltDev klt_dev_block(Carve& c, size_t cap) {
+    KltDev D;
+    const size_t cp = refill_pad((int)cap), c8 = (cap + 7) / 8 * 8;
+    D.s_id = c.take<int>(cap, 16); D.s_age = c.take<int>(cap, 16); D.s_xy = c.take<float>(2 * cap, 16);
+    D.order = c.take<int>(c8, 16);
+    D.lk_xy = c.take<float>(2 * cap, 16); D.lk_err = c.take<float>(cap, 16); D.bk_xy = c.take<float>(2 * cap, 16); D.bk_err = c.take<float>(cap, 16);
+    D.lk_st = c.take<uint8_t>(cap, 16); D.bk_st = c.take<uint8_t>(cap, 16);
+    for (int k = 0; k < 2; k++) {
+        D.l_id[k] = c.take<int>(cap, 16); D.l_age[k] = c.take<int>(cap, 16); D.l_prev[k] = c.take<float>(2 * cap, 16); D.l_cur[k] = c.take<float>(2 * cap, 16);
+    }
+    D.pos = c.take<unsigned>(cp, 16); D.prio = c.take<int>(cp, 16); D.flag = c.take<uint8_t>(cp, 16); D.keep = c.take<uint8_t>(cp, 16);
+    D.f_out = c.take<char>(ESS_OUT_HDR + cap, 64);
+    D.cnt = c.take<int>(C_COUNT, 64); D.ixy = c.take<int>(2 * cap, 16);
+    D.sp_xy = c.take<float>(2 * cap, 16); D.sp_it = c.take<uint8_t>(cap, 16); D.sp_fl = c.take<uint8_t>(cap, 16);
+    return D;
+}
+// record block, pinned mirror and device copy: refill record | half-width table | frame request || F problem | F iteration table. The
+// front part goes up with every step, the part behind `front` only in front of a k_fundamental_ransac launch.
+struct KltRecs { Carved<RefillRec> rrec; Carved<uint8_t> hw; Carved<int> grec; size_t front; Carved<char> fprob; Carved<double> ftab; };
+KltRecs klt_rec_block(Carve& c, size_t cap) {
+    KltRecs R;
+    R.rrec = c.take<RefillRec>(1, 16); R.hw = c.take<uint8_t>(REFILL_HW, 16); R.grec = c.take<int>(CELL_STRIDE, 16);
+    c.skip_to(64);
+    R.front = c.bytes();
+    R.fprob = c.take<char>(ESS_HDR, 64); R.ftab = c.take<double>(cap + 2, 16);
+    return R;
+}
+// result block (mapped pinned): n1's word | header (counts8, out_n, completion word) | ids | ages | xy | prev xy
+struct KltRes { Carved<int> n1, hdr, id, age; Carved<float> xy, prev; };
+KltRes klt_res_block(Carve& c, size_t cap) {
+    KltRes R;
+    R.n1 = c.take<int>(16, 64); R.hdr = c.take<int>(16, 64);
+    R.id = c.take<int>(cap, 16); R.age = c.take<int>(cap, 16); R.xy = c.take<float>(2 * cap, 16); R.prev = c.take<float>(2 * cap, 16);
+    return R;
+}
+
+}  // namespace
+
+struct KltTracker {
+    pmv_klt_params p;
+    int cap = 0, n = 0, next_id = 0;
+    unsigned seq = 0;
+    float thr2 = 0.f;
+    Buf<uint8_t> d_mem, d_rec, h_rec{MEM_PINNED}, h_res{MEM_MAPPED};
+    KltDev D; KltRecs R; KltRes O;
+};
+
+void klt_destroy_all(pmv_ctx* ctx) {
+    for (auto& t : ctx->klt) { delete t; t = nullptr; }
+}
+
+}  // namespace pmv
+
+using namespace pmv;
+
+#define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
+#define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
+
+static int klt_find(pmv_ctx* ctx, const char* who, int id, KltTracker** out) {
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    REQ(id >= 0 && id < PMV_KLT_MAX_TRACKERS && ctx->klt[id], PMV_ERR_INVALID, "%s: tracker %d does not exist (pmv_klt_create)", who, id);
+    *out = ctx->klt[id];
+    return PMV_OK;
+}
+
+extern "C" {
+
+int pmv_klt_create(pmv_ctx* ctx, const pmv_klt_params* p, int* out_id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_create: null argument");
+    REQ(p && out_id, PMV_ERR_INVALID, "pmv_klt_create: null argument");
+    const int max_n = std::min(ctx->max_tracks, PMV_REFILL_MAX_TRACKS);
+    REQ(p->target >= 1, PMV_ERR_INVALID, "pmv_klt_create: target = %d is below 1", p->target);
+    REQ(p->target <= max_n, PMV_ERR_CAPACITY, "pmv_klt_create: target = %d is above %d (max_tracks, PMV_REFILL_MAX_TRACKS)", p->target, max_n);
+    REQ(p->border >= 0 && p->border <= 64, PMV_ERR_INVALID, "pmv_klt_create: border = %d is outside 0..64", p->border);
+    REQ(p->fb_max_dist < 0.0 || p->fb_max_dist <= 1e3, PMV_ERR_INVALID, "pmv_klt_create: fb_max_dist = %g is not finite or above 1e3", p->fb_max_dist);   // (a NaN fails both)
+    REQ(p->reject_f == 0 || p->reject_f == 1, PMV_ERR_INVALID, "pmv_klt_create: reject_f = %d is neither 0 nor 1", p->reject_f);
+    REQ(p->subpix == 0 || p->subpix == 1, PMV_ERR_INVALID, "pmv_klt_create: subpix = %d is neither 0 nor 1", p->subpix);
+    REQ(p->radius >= 0 && p->radius <= PMV_REFILL_MAX_RADIUS, PMV_ERR_INVALID, "pmv_klt_create: radius = %d is outside 0..%d", p->radius, PMV_REFILL_MAX_RADIUS);
+    int dummy_i = 0;
+    if (p->reject_f) {   // the rules of the call the fields belong to, on 15 points at the origin
+        static const float zeros[30] = {};
+        double f9[9]; uint8_t m15[15];
+        if (const int rc = fundamental_check(ctx, "pmv_klt_create", zeros, zeros, 15, p->f_threshold, p->f_confidence, f9, m15, &dummy_i, &dummy_i)) return rc;
+    }
+    if (const int rc = gftt_ex_check(ctx, "pmv_klt_create", &p->gftt, &dummy_i, &dummy_i)) return rc;
+    if (p->subpix) if (const int rc = subpix_params_check(ctx, "pmv_klt_create", &p->subpix_params)) return rc;
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    int id = 0;
+    while (id < PMV_KLT_MAX_TRACKERS && ctx->klt[id]) id++;
+    REQ(id < PMV_KLT_MAX_TRACKERS, PMV_ERR_CAPACITY, "pmv_klt_create: the context holds %d trackers already (pmv_klt_destroy one)", PMV_KLT_MAX_TRACKERS);
+    CKC(hipSetDevice(ctx->device));
+    KltTracker* t = new KltTracker();
+    t->p = *p; t->cap = p->target;
+    t->thr2 = p->fb_max_dist >= 0.0 ? (float)(p->fb_max_dist * p->fb_max_dist) : 0.f;
+    const size_t cap = (size_t)t->cap;
+    Carve nd, nr, no;
+    klt_dev_block(nd, cap); klt_rec_block(nr, cap); klt_res_block(no, cap);
+    hipError_t e = t->d_mem.ensure(nd.bytes() + 64);
+    if (e == hipSuccess) e = t->d_rec.ensure(nr.bytes() + 64);
+    if (e == hipSuccess) e = t->h_rec.ensure(nr.bytes() + 64);
+    if (e == hipSuccess) e = t->h_res.ensure(no.bytes() + 64);
+    if (e == hipSuccess) e = hipMemset(t->d_mem, 0, nd.bytes());
+    if (e == hipSuccess) {
+        Carve cd(nullptr, t->d_mem.p, t->d_mem.cap), cr(t->h_rec.p, t->d_rec.p, t->h_rec.cap), co = carve_of(t->h_res);
+        t->D = klt_dev_block(cd, cap); t->R = klt_rec_block(cr, cap); t->O = klt_res_block(co, cap);
+        memset(t->h_rec, 0, nr.bytes()); memset(t->h_res, 0, no.bytes());
+        refill_halfwidths(p->radius, t->R.hw.h);
+        std::vector<int> order((cap + 7) / 8 * 8);   // the identity: a block beyond the launch's n leaves at once
+        for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
+        e = hipMemcpy(t->D.order.d, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { delete t; set_err(ctx, "pmv_klt_create: %s", hipGetErrorString(e)); return PMV_ERR_HIP; }
+    ctx->klt[id] = t;
+    *out_id = id;
+    return PMV_OK;
+}
+
+int pmv_klt_destroy(pmv_ctx* ctx, int id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_destroy: null argument");
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    REQ(id >= 0 && id < PMV_KLT_MAX_TRACKERS && ctx->klt[id], PMV_ERR_INVALID, "pmv_klt_destroy: tracker %d does not exist", id);
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    delete ctx->klt[id];
+    ctx->klt[id] = nullptr;
+    return PMV_OK;
+}
+
+int pmv_klt_set_tracks(pmv_ctx* ctx, int id, const int* ids, const int* ages, const float* xy, int n, int next_id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_set_tracks: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_set_tracks", id, &t)) return rc;
+    REQ(n >= 0 && n <= t->cap, PMV_ERR_CAPACITY, "pmv_klt_set_tracks: n = %d is outside 0..%d (the tracker's target)", n, t->cap);
+    REQ(n == 0 || (ids && ages && xy), PMV_ERR_INVALID, "pmv_klt_set_tracks: null argument");
+    REQ(next_id >= 0, PMV_ERR_INVALID, "pmv_klt_set_tracks: next_id = %d is negative", next_id);
+    for (int i = 0; i < 2 * n; i++)   // (a NaN fails the comparison too)
+        REQ(fabsf(xy[i]) <= 1e6f, PMV_ERR_INVALID, "pmv_klt_set_tracks: track %d (%g, %g) is not finite or beyond 1e6", i / 2, (double)xy[i & ~1], (double)xy[i | 1]);
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    if (n > 0) {
+        CKC(hipMemcpy(t->D.s_id.d, ids, (size_t)n * 4, hipMemcpyHostToDevice));
+        CKC(hipMemcpy(t->D.s_age.d, ages, (size_t)n * 4, hipMemcpyHostToDevice));
+        CKC(hipMemcpy(t->D.s_xy.d, xy, (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    t->n = n; t->next_id = next_id;
+    return PMV_OK;
+}
+
+int pmv_klt_get_tracks(pmv_ctx* ctx, int id, int* ids, int* ages, float* xy, int cap, int* out_n) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_get_tracks: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_get_tracks", id, &t)) return rc;
+    REQ(out_n && (t->n == 0 || (ids && ages && xy)), PMV_ERR_INVALID, "pmv_klt_get_tracks: null argument");
+    REQ(cap >= t->n, PMV_ERR_CAPACITY, "pmv_klt_get_tracks: cap = %d is below the %d tracks held", cap, t->n);
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));
+    if (t->n > 0) {
+        CKC(hipMemcpy(ids, t->D.s_id.d, (size_t)t->n * 4, hipMemcpyDeviceToHost));
+        CKC(hipMemcpy(ages, t->D.s_age.d, (size_t)t->n * 4, hipMemcpyDeviceToHost));
+        CKC(hipMemcpy(xy, t->D.s_xy.d, (size_t)t->n * 8, hipMemcpyDeviceToHost));
+    }
+    *out_n = t->n;
+    return PMV_OK;
+}
+
+int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, int out_cap, int* out_n,
+                 int* out_counts8) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_step: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_step", id, &t)) return rc;
+    REQ(out_ids && out_ages && out_xy && out_n && out_counts8, PMV_ERR_INVALID, "pmv_klt_step: null argument");
+    REQ(out_cap >= t->cap, PMV_ERR_CAPACITY, "pmv_klt_step: out_cap = %d is below the tracker's target %d", out_cap, t->cap);
+    const pmv_klt_params& p = t->p;
+    const int n0 = t->n, cap = t->cap;
+    const bool fb = p.fb_max_dist >= 0.0;
+    // the slot rules of the calls the stages are: LK's for the pair (only when something is tracked), the frame detector's for cur_slot
+    if (n0 > 0)
+        if (const int rc = lk_check(ctx, true, prev_slot, cur_slot, out_xy, n0, out_xy, (const uint8_t*)out_ids, out_xy)) return rc;
+    int roi[4], gcap;
+    if (const int rc = gftt_frame_check(ctx, "pmv_klt_step", true, cur_slot, nullptr, cap, &p.gftt, nullptr, 0, out_ids, cap, out_n, roi, &gcap)) return rc;
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const PyrLayout& L = ctx->slot_layout[cur_slot];
+    const size_t pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3];
+    // the context's scratch of the refill and frame calls (rewritten by every call and every step)
+    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
+    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
+    CKC(ctx->d_gfr_mask.ensure(pix + 64));
+    CKC(ctx->d_refill_kept.ensure((size_t)PMV_REFILL_MAX_TRACKS * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(sizeof(int)));
+    SubpixArgs SA{};
+    if (p.subpix) {   // the weight table, as pmv_corner_subpix keeps it
+        const pmv_subpix_params* sp = &p.subpix_params;
+        CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
+        int zw, zh;
+        subpix_zero_zone(sp, &zw, &zh);
+        const int key[4] = {sp->win_w, sp->win_h, zw, zh};
+        if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
+            CKC(hipStreamSynchronize(ctx->s_front));
+            subpix_table(sp->win_w, sp->win_h, zw, zh, ctx->h_subpix_tab);
+            CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * sp->win_w + 1) * (2 * sp->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
+            memcpy(ctx->subpix_tab_key, key, sizeof(key));
+        }
+        SA = SubpixArgs{sp->win_w, sp->win_h, sp->max_iter, sp->eps * sp->eps};
+    }
+    hipStream_t s = ctx->s_front;
+    const KltDev& D = t->D; const KltRecs& R = t->R; const KltRes& O = t->O;
+    long long launches = 0, waits = 0;
+    // records: the refill request (its n is written by the kernels), the frame request
+    *R.rrec.h = RefillRec{0, p.radius, 0, roi[0], roi[1], roi[2], roi[3], 0u, 0, {0, 0, 0}};
+    gftt_frame_record(R.grec.h, roi, cur_slot, 0, nullptr, 0, nullptr, 0);
+    CKC(hipMemcpyAsync(t->d_rec, t->h_rec, R.front, hipMemcpyHostToDevice, s));
+    const KltRefillIn rf{D.pos.d, D.prio.d, D.flag.d, R.rrec.d};
+    KltList lst[2];
+    for (int k = 0; k < 2; k++) lst[k] = KltList{D.l_id[k].d, D.l_age[k].d, D.l_prev[k].d, D.l_cur[k].d};
+    // 1. track
+    if (n0 > 0) {
+        const PyrLayout& Lp = ctx->slot_layout[prev_slot];
+        CKC(launch_lk_ex(s, ctx->d_slots + (size_t)prev_slot * Lp.slot_bytes, ctx->d_slots + (size_t)cur_slot * Lp.slot_bytes, Lp, D.s_xy.d, nullptr, D.order.d, (n0 + 7) / 8 * 8,
+                         n0, fb ? LKX_FB : 0, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
+        launches++;
+    }
+    // 2. filter
+    {
+        KltFilterArgs A{n0, fb ? 1 : 0, p.border, L.w[0], L.h[0], t->thr2, D.s_id.d, D.s_age.d, D.s_xy.d, D.lk_xy.d, D.bk_xy.d, D.lk_st.d, D.bk_st.d, lst[0], rf, D.cnt.d, O.n1.d};
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_filter, dim3(1), dim3(KT), 0, s, A);
+        CKC(hipGetLastError());
+        launches++;
+    }
+    // 3. rejectWithF: the host reads n1 (the iteration table is libm's) and sends the table with the launches of the second half
+    int cur = 0;
+    bool f_ran = false;
+    if (p.reject_f && n0 >= 15) {
+        CKC(hipStreamSynchronize(s));
+        waits++;
+        const int n1 = *O.n1.h;
+        REQ(n1 >= 0 && n1 <= n0, PMV_ERR_HIP, "pmv_klt_step: the filter left n1 = %d of %d tracks", n1, n0);
+        if (n1 >= 15) {
+            FundamentalProblem P;
+            P.p1 = lst[0].prev; P.p2 = lst[0].cur; P.iters = R.ftab.d; P.out = D.f_out.d;
+            P.n = n1; P.max_iters = 1000; P.thr = (float)(p.f_threshold * p.f_threshold); P.done_seq = 1;
+            memset(R.fprob.h, 0, ESS_HDR);
+            memcpy(R.fprob.h, &P, sizeof(P));
+            vo::ransac_iters_table(n1, p.f_confidence, 7, R.ftab.h + 1, R.ftab.h);
+            const size_t fbytes = (size_t)((const char*)(R.ftab.h + n1 + 2) - R.fprob.h);
+            CKC(hipMemcpyAsync((char*)t->d_rec.p + R.fprob.off, R.fprob.h, fbytes, hipMemcpyHostToDevice, s));
+            CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)R.fprob.d, 1));
+            KltCompactArgs A{lst[0], lst[1], (const uint8_t*)(D.f_out.d + ESS_OUT_HDR), D.cnt.d + C_N1, cap, C_N2, 0, rf, D.cnt.d};
+            ProfScope ps(K_GFTT_PICK, s);
+            hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
+            CKC(hipGetLastError());
+            launches += 2;
+            cur = 1; f_ran = true;
+        }
+    }
+    // 4. thin: setMask's walk and painting on the list, then the compaction by its keep bytes, which leaves the number of corners wanted
+    CKC(launch_track_refill(s, R.rrec.d, 1, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    launches += 2;
+    {
+        KltCompactArgs A{lst[cur], lst[cur ^ 1], D.keep.d, D.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, D.cnt.d};
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
+        CKC(hipGetLastError());
+        launches++;
+        cur ^= 1;
+    }
+    // 5. refill: the frame call's two passes with the painted mask; the selection takes its cap from the counts
+    const GfttExt X = gftt_ext(p.gftt.block_size, p.gftt.use_harris, p.gftt.k);
+    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p.gftt.quality, p.gftt.min_dist, 0, &X, ctx->d_gfr_mask.get(), ctx->d_gfr_val,
+                          ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, D.ixy.d, D.cnt.d + C_M, D.cnt.d + C_STAT0, D.cnt.d + C_WANT));
+    launches += 2;
+    // 6. refine
+    if (p.subpix) {
+        CKC(launch_corner_subpix_dev(s, ctx->d_slots, L, D.ixy.d, cur_slot, cap, D.cnt.d + C_M, ctx->d_subpix_tab, SA, D.sp_xy.d, D.sp_it.d, D.sp_fl.d));
+        launches++;
+    }
+    // 7. append
+    if (++t->seq == 0) t->seq = 1;
+    O.hdr.h[9] = 0;
+    {
+        KltAppendArgs A{lst[cur], D.cnt.d, D.ixy.d, p.subpix ? D.sp_xy.d : nullptr, f_ran ? (const int*)(D.f_out.d + ESS_OUT_INFO) : nullptr, n0, t->next_id, cap, t->seq,
+                        D.s_id.d, D.s_age.d, D.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d};
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_append, dim3(1), dim3(KT), 0, s, A);
+        CKC(hipGetLastError());
+        launches++;
+    }
+    CKC(hipStreamSynchronize(s));
+    waits++;
+    const int* hdr = O.hdr.h;
+    const int n = hdr[8], m = hdr[4];
+    REQ((unsigned)hdr[9] == t->seq && n >= 0 && n <= cap && m >= 0 && m <= n, PMV_ERR_HIP, "pmv_klt_step: the result block is incomplete (n = %d, m = %d)", n, m);
+    memcpy(out_ids, O.id.h, (size_t)n * 4);
+    memcpy(out_ages, O.age.h, (size_t)n * 4);
+    memcpy(out_xy, O.xy.h, (size_t)n * 8);
+    if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null, O.prev.h, (size_t)n * 8);
+    memcpy(out_counts8, hdr, 8 * sizeof(int));
+    *out_n = n;
+    t->n = n; t->next_id += m;
+    ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask is this step's now)
+    ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches;
+    return PMV_OK;
+}
+
+int pmv_debug_klt_stats(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_klt_stats: null argument");
+    for (int i = 0; i < 3; i++) out4[i] = ctx->klt_stats[i].load();
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    long long alive = 0;
+    for (const auto* t : ctx->klt) alive += t != nullptr;
+    out4[3] = alive;
+    return PMV_OK;
+}
+
+}  // extern "C"

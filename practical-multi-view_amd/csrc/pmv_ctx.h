@@ -21,6 +21,7 @@ enum SlotState : uint8_t { SLOT_EMPTY = 0, SLOT_STAGED, SLOT_BUILT };   // SLOT_
 constexpr int MAX_CELLS = 64;       // 1920x1080 -> 8x5 = 40 cells of 255x255
 constexpr int MAX_PER_CELL = 4096;    // also the capacity of an "unlimited" (max_per_cell <= 0) goodFeaturesToTrack call
 struct BackendBuffers;              // PnP / BA device workspaces (backend.hip)
+struct KltTracker;                  // a device-resident KLT tracker (frontend_klt.hip)
 }
 
 // In-memory log of the back-end plugin calls (pmv_record_*): every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates
@@ -135,6 +136,11 @@ struct pmv_ctx {
     pmv::Buf<uint8_t> h_remap{pmv::MEM_PINNED}, d_remap, d_remap_scratch;
     // pmv_debug_remap_launches: k_remap launches of pmv_frames_remap | session upload rounds with a remap request | k_remap launches made for them
     std::atomic<long long> remap_launches[3];
+    // pmv_klt_create (frontend_klt.hip): the trackers of the context, id = index; each owns its state and its chain's buffers. klt_mu guards
+    // the table. pmv_debug_klt_stats: steps | host waits inside steps | kernel launches inside steps
+    pmv::KltTracker* klt[PMV_KLT_MAX_TRACKERS] = {};
+    std::mutex klt_mu;
+    std::atomic<long long> klt_stats[3];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -222,6 +228,8 @@ size_t gftt_frame_record(int* rec, const int* roi4, int slot, size_t list_off, u
 int refill_check(pmv_ctx* ctx, const char* who, int slot, const float* track_xy, int n_tracks, int radius, const uint8_t* out_keep);
 // pmv_corner_subpix / pmv_batch_corner_subpix: every check of the contract, in its order (`who` names the call in the messages)
 int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p);
+int subpix_params_check(pmv_ctx* ctx, const char* who, const pmv_subpix_params* p);   // its window, iteration and eps rules alone (p is not null)
+void klt_destroy_all(pmv_ctx* ctx);   // frees the trackers that are left (pmv_ctx_destroy, after the streams were synchronised)
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
 inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
     const bool on = p->zero_w >= 0 && p->zero_h >= 0 && 2 * p->zero_w + 1 < 2 * p->win_w + 1 && 2 * p->zero_h + 1 < 2 * p->win_h + 1;
