@@ -779,6 +779,42 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
 /* diagnostic: out4 = {steps, host waits inside steps, kernel launches inside steps, trackers alive} since the context was created */
 int pmv_debug_klt_stats(pmv_ctx* ctx, long long* out4);
 
+/* ---- A group of trackers in one call: pmv_klt_step_many ------------------------------------------------------------------------------------
+ * A step is 8-10 short, serially dependent launches and one or two host waits; a caller with several cameras (a stereo pair, a rig, sequences
+ * replayed side by side) pays that once per camera with pmv_klt_step. pmv_klt_step_many steps n_trk trackers of the context through ONE chain
+ * of launches.
+ * Result definition: tracker j of the call is ids[j]. Its lists start at track j * out_stride of out_ids / out_ages / out_xy / out_prev_xy
+ *   (xy: 2 floats a track), its count is out_n[j] and its counts are out_counts8[8 j .. 8 j + 7]. For every j the outputs and the tracker's
+ *   new state are, byte for byte, what pmv_klt_step(ctx, ids[j], prev_slots[j], cur_slots[j], ..) returns from the same state. Trackers are
+ *   independent: the order within the group changes nothing, and two trackers may name the same slots. No arithmetic of any stage changes.
+ * Per tracker: target, border, fb_max_dist (on or off), reject_f, f_threshold, f_confidence, radius and the length of the list may differ
+ *   from tracker to tracker; an empty tracker may sit next to full ones.
+ * Launch-wide: the five fields of gftt, subpix and (if subpix) subpix_params are arguments of the detector's and the refinement's one launch
+ *   and must be equal over the group; all cur_slots must hold frames of one size (and so do the prev_slots of the trackers that track, by
+ *   pmv_klt_step's own slot rule). A difference is PMV_ERR_INVALID; the message names the first tracker that differs from tracker 0 and the
+ *   field. Every pmv_set_lk_params setting is served.
+ * Errors (nothing is written, nothing is clamped, no tracker of the group changes its state): PMV_ERR_INVALID - a null argument
+ *   (out_prev_xy may be NULL), n_trk < 1, an unknown id, an id named twice; PMV_ERR_CAPACITY - n_trk > PMV_KLT_MAX_TRACKERS, out_stride
+ *   below the largest target of the group; the slot errors of pmv_klt_step for whichever tracker they hit (the message says which). The
+ *   host updates n and next_id of the trackers only after the last wait, once every tracker's result block is complete; an incomplete
+ *   block is PMV_ERR_HIP and updates nothing.
+ * Device side: the launches and waits of a call do not depend on n_trk - at most 12 launches (a step's chain plus one kernel that writes
+ *   LK's records in device memory from the trackers' states, so no position crosses the bus on the way in) and at most two waits, one when no
+ *   tracker of the group has reject_f = 1 and 15 tracks. The first wait reads the n_trk words n1; the F problems and iteration tables of
+ *   the trackers with n1 >= 15 go up in one copy and run in one launch, the others pass their list through. The filter, the two
+ *   compactions and the append run one workgroup per tracker on per-tracker argument records; the detector's record lists, the painted
+ *   masks and the kept lists are per-tracker shares of the context's scratch, which the call grows as needed.
+ * Mixing: a tracker may be stepped by pmv_klt_step and pmv_klt_step_many in any mixture; single calls between many-calls return their usual
+ *   bytes. Legal during a batch session under the caller's slot rule; the call keeps a one-entry geometry table of its own and does not
+ *   touch the session's. The first three counters of pmv_debug_klt_stats count pmv_klt_step only; many-calls are counted by
+ *   pmv_debug_klt_many_stats; pmv_debug_refill_stats does not move.
+ * Out of scope: the session form (pmv_batch_klt_*, which can be laid over this call), groups with mixed frame sizes, detector arguments or
+ *   refinement arguments, more than PMV_KLT_MAX_TRACKERS trackers, and everything pmv_klt_step lists. */
+int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, int* out_ids, int* out_ages, float* out_xy,
+                      float* out_prev_xy_or_null, int out_stride, int* out_n /* n_trk */, int* out_counts8 /* 8 * n_trk */);
+/* diagnostic: out4 = {many-calls, trackers stepped by them, host waits inside them, kernel launches inside them} since the context was created */
+int pmv_debug_klt_many_stats(pmv_ctx* ctx, long long* out4);
+
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those
  * made from inside pmv_pipeline_run) appends one blob holding its inputs and outputs, so that a test can replay the calls

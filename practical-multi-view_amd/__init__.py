@@ -265,6 +265,7 @@ ABI_SYMBOLS = [
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
+    "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -1177,6 +1178,36 @@ class Context:
         out = (C.c_longlong * 4)()
         self.lib.pmv_debug_klt_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         self._ck(self.lib.pmv_debug_klt_stats(self.h, out))
+        return [int(v) for v in out]
+
+    def klt_step_many(self, trackers, prev_slots, cur_slots):
+        """pmv_klt_step_many: the trackers of this context stepped through one chain of launches; a list of KltTracker.step's 5-tuples, one per
+        tracker, each byte for byte what its own step(prev_slots[j], cur_slots[j]) returns. The detector's and the refinement's arguments
+        must be equal over the group and all frames of one size."""
+        trackers = list(trackers)
+        for t in trackers:
+            if not isinstance(t, KltTracker) or t.ctx is not self or t.id is None:
+                raise ValueError("klt_step_many: every tracker must be an open KltTracker of this context")
+        k = len(trackers)
+        prev_slots, cur_slots = np.ascontiguousarray(prev_slots, np.int32).reshape(-1), np.ascontiguousarray(cur_slots, np.int32).reshape(-1)
+        if prev_slots.size != k or cur_slots.size != k:
+            raise ValueError("klt_step_many: one prev_slot and one cur_slot per tracker")
+        ids = np.asarray([t.id for t in trackers], np.int32)
+        stride = max([t.target for t in trackers], default=1)
+        o_ids, o_ages = np.zeros((max(k, 1), stride), np.int32), np.zeros((max(k, 1), stride), np.int32)
+        o_xy, o_prev = np.zeros((max(k, 1), stride, 2), np.float32), np.zeros((max(k, 1), stride, 2), np.float32)
+        o_n, counts = np.zeros(max(k, 1), np.int32), np.zeros((max(k, 1), 8), np.int32)
+        fn = self.lib.pmv_klt_step_many
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p, C.c_int, _i32p, _i32p]
+        self._ck(fn(self.h, k, _p(ids, _i32p), _p(prev_slots, _i32p), _p(cur_slots, _i32p), _p(o_ids, _i32p), _p(o_ages, _i32p), _p(o_xy, _f32p), _p(o_prev, _f32p), stride,
+                    _p(o_n, _i32p), _p(counts, _i32p)))
+        return [(o_ids[j, :o_n[j]].copy(), o_ages[j, :o_n[j]].copy(), o_xy[j, :o_n[j]].copy(), o_prev[j, :o_n[j]].copy(), counts[j].copy()) for j in range(k)]
+
+    def debug_klt_many_stats(self):
+        """pmv_debug_klt_many_stats: [many-calls, trackers stepped by them, host waits inside them, kernel launches inside them]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_klt_many_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_klt_many_stats(self.h, out))
         return [int(v) for v in out]
 
     # ---- call log (teacher-forced replay) ----

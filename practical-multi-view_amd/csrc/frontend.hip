@@ -2043,6 +2043,9 @@ __device__ __forceinline__ int gf_walk(unsigned long long* keys, int n, int limi
     return na;
 }
 
+// PER_REQ (a group of trackers, more than one request with cap_dev): cap_dev holds one word per request; otherwise the one word of the
+// single request - the form every single call and a lone tracker's step launch, whose code is what it was
+template <bool PER_REQ>
 __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict__ recs, const float* __restrict__ cand_val, const unsigned* __restrict__ cand_idx,
                                                           const unsigned* __restrict__ info, unsigned long long* __restrict__ gkeys, int cap, double quality,
                                                           double min_dist, int unlimited, int* __restrict__ out_xy, int* __restrict__ out_count,
@@ -2090,7 +2093,7 @@ __global__ __launch_bounds__(GF_T) void k_gftt_pick_frame(const int* __restrict_
     // cap_dev (the tracker's chain): the number of corners wanted is known only on the device - clamped to the list's capacity `cap`, which
     // still places the list; 0 selects nothing
     int want = cap;
-    if (cap_dev) { const int c = *cap_dev; want = c < 0 ? 0 : (c < cap ? c : cap); }
+    if (cap_dev) { const int c = PER_REQ ? cap_dev[req] : *cap_dev; want = c < 0 ? 0 : (c < cap ? c : cap); }
     const int limit = unlimited ? want + 1 : want;
     int na;
     if (n <= GF_CAP) {
@@ -2125,8 +2128,12 @@ hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayou
     if (X) hipLaunchKernelGGL(k_gftt_cand_general_frame, dim3(grid_x, n_req), dim3(256), gfttg_lds_bytes(X->bs), s, slots, L, d_recs, d_val, d_idx, d_info, quality, *X, d_mask);
     else hipLaunchKernelGGL(k_gftt_cand_frame, dim3(grid_x, n_req), dim3(256), 0, s, slots, L, d_recs, d_val, d_idx, d_info, quality); }
     ProfScope ps2(K_GFTT_PICK, s);
-    hipLaunchKernelGGL(k_gftt_pick_frame, dim3(n_req), dim3(GF_T), GF_LDS, s, d_recs, d_val, d_idx, d_info, d_keys, cap, quality, min_dist, unlimited, d_out_xy,
-                       d_out_count, d_stats, d_cap);
+    if (d_cap && n_req > 1)
+        hipLaunchKernelGGL(k_gftt_pick_frame<true>, dim3(n_req), dim3(GF_T), GF_LDS, s, d_recs, d_val, d_idx, d_info, d_keys, cap, quality, min_dist, unlimited, d_out_xy,
+                           d_out_count, d_stats, d_cap);
+    else
+        hipLaunchKernelGGL(k_gftt_pick_frame<false>, dim3(n_req), dim3(GF_T), GF_LDS, s, d_recs, d_val, d_idx, d_info, d_keys, cap, quality, min_dist, unlimited, d_out_xy,
+                           d_out_count, d_stats, d_cap);
     return hipGetLastError();
 }
 
@@ -2283,7 +2290,8 @@ hipError_t launch_shitomasi(hipStream_t s, const uint8_t* slots, const PyrLayout
 // called by pmv_ctx_create after hipSetDevice, so a second context on another GPU of the same process is set up as well.
 hipError_t frontend_prepare_device() {
     if (hipError_t e = hipFuncSetAttribute((const void*)k_st_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST_SELECT_SHM)) return e;
-    return hipFuncSetAttribute((const void*)k_gftt_pick_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS);
+    if (hipError_t e = hipFuncSetAttribute((const void*)k_gftt_pick_frame<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS)) return e;
+    return hipFuncSetAttribute((const void*)k_gftt_pick_frame<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS);
 }
 
 }  // namespace pmv

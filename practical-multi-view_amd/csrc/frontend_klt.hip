@@ -6,6 +6,10 @@
 // wavefronts in LDS, chunks of 1024 tracks) and leaves its count in device memory, where the launches behind it read it - the n of the
 // refill record, the cap of the selection pass, the point count of the sub-pixel launch. Every count read from device memory is clamped to
 // its buffer's capacity before it bounds a loop.
+// pmv_klt_step_many steps a group of trackers through ONE such chain: the same three bodies as a grid over the trackers (blockIdx.x selects a
+// per-tracker argument record in device memory), LK as one batched launch whose records k_klt_lk_records writes from the trackers' states,
+// and the multi-request forms of the refill, frame and F launches. pmv_klt_step keeps its own argument form: a group of one is ~25 us slower
+// (DESIGN.md §4).
 #include "pmv_ctx.h"
 #include "backend.h"
 #include "vo_pipeline.h"
@@ -60,9 +64,7 @@ struct KltFilterArgs {
     KltList out; KltRefillIn rf;
     int* cnt; int* h_n1;
 };
-__global__ __launch_bounds__(KT) void k_klt_filter(KltFilterArgs A) {
-    __shared__ unsigned s_w[KW];
-    BACKEND_PRIO();
+__device__ __forceinline__ void klt_filter(const KltFilterArgs& A, unsigned* s_w) {
     const float lo = (float)A.border, hx = (float)(A.w - A.border), hy = (float)(A.h - A.border);
     const int n1 = klt_compact(A.n0, s_w,
         [&](int i) {
@@ -89,22 +91,27 @@ __global__ __launch_bounds__(KT) void k_klt_filter(KltFilterArgs A) {
         __threadfence_system();
     }
 }
+__global__ __launch_bounds__(KT) void k_klt_filter(KltFilterArgs A) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    klt_filter(A, s_w);
+}
 
 // Stages 3 and 4: the same compaction driven by a byte mask - the F mask (then it also writes what k_track_select reads and the n of the
 // refill record) or the keep bytes (then it leaves the number of corners wanted, target - n3, for the selection pass).
 struct KltCompactArgs {
     KltList in, out;
     const uint8_t* mask; const int* n_in;
-    int cap, cnt_out, target;       // cnt_out: the count's place (C_N2 or C_N3); target > 0: C_WANT is written too
+    int cap, cnt_out, target;       // cnt_out: the count's place (C_N2 or C_N3); target > 0: *want is written too
     KltRefillIn rf;
-    int* cnt;
+    int* cnt; int* want;            // want: the selection pass's word of this tracker (the step's own C_WANT, or the group's table)
 };
-__global__ __launch_bounds__(KT) void k_klt_compact(KltCompactArgs A) {
-    __shared__ unsigned s_w[KW];
-    BACKEND_PRIO();
+// PASS (a group's rejectWithF stage): a null mask keeps every track - the tracker has no F stage in this call and its list goes through
+template <bool PASS>
+__device__ __forceinline__ void klt_compact_by(const KltCompactArgs& A, unsigned* s_w) {
     const int n = klt_clamp(*A.n_in, A.cap);
     const int no = klt_compact(n, s_w,
-        [&](int i) { return A.mask[i] != 0; },
+        [&](int i) { return (PASS && !A.mask) || A.mask[i] != 0; },
         [&](int i, int o) {
             const float x = A.in.cur[2 * i], y = A.in.cur[2 * i + 1];
             A.out.id[o] = A.in.id[i]; A.out.age[o] = A.in.age[i];
@@ -115,24 +122,28 @@ __global__ __launch_bounds__(KT) void k_klt_compact(KltCompactArgs A) {
     if (threadIdx.x == 0) {
         A.cnt[A.cnt_out] = no;
         if (A.rf.pos) A.rf.rec->n = no;
-        if (A.target > 0) A.cnt[C_WANT] = klt_clamp(A.target - no, A.target);
+        if (A.target > 0) *A.want = klt_clamp(A.target - no, A.target);
     }
+}
+__global__ __launch_bounds__(KT) void k_klt_compact(KltCompactArgs A) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    klt_compact_by<false>(A, s_w);
 }
 
 // Stage 7: survivors, then the m new tracks in detector order (ids next_id .., age 1, prev = their own position), into the state and into
 // the result block in mapped pinned memory; the completion word is the last store.
 struct KltAppendArgs {
     KltList in;
-    const int* cnt; const int* ixy; const float* sp_xy; const int* f_info;   // sp_xy: the refined corners or null; f_info: (found, drawn) or null
+    const int* cnt; const int* m; const int* ixy; const float* sp_xy; const int* f_info;   // m: the selection pass's count; sp_xy: the refined corners or null; f_info: (found, drawn) or null
     int n0, next_id, target;
     unsigned seq;
     int* s_id; int* s_age; float* s_xy;
     int* r_hdr; int* r_id; int* r_age; float* r_xy; float* r_prev;
 };
-__global__ __launch_bounds__(KT) void k_klt_append(KltAppendArgs A) {
-    BACKEND_PRIO();
+__device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
     const int tid = threadIdx.x;
-    const int n3 = klt_clamp(A.cnt[C_N3], A.target), m = klt_clamp(A.cnt[C_M], A.target - n3);
+    const int n3 = klt_clamp(A.cnt[C_N3], A.target), m = klt_clamp(*A.m, A.target - n3);
     for (int i = tid; i < n3; i += KT) {
         const int id = A.in.id[i], age = A.in.age[i];
         const float x = A.in.cur[2 * i], y = A.in.cur[2 * i + 1];
@@ -155,6 +166,62 @@ __global__ __launch_bounds__(KT) void k_klt_append(KltAppendArgs A) {
     __threadfence_system();
     __syncthreads();
     if (tid == 0) __hip_atomic_store((unsigned*)(A.r_hdr + 9), A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__global__ __launch_bounds__(KT) void k_klt_append(KltAppendArgs A) {
+    BACKEND_PRIO();
+    klt_append(A);
+}
+
+// ---- pmv_klt_step_many: the same three stages as a grid over the trackers of a group ----------------------------------------------------
+// blockIdx.x selects the tracker's argument record in device memory, which holds what the Klt*Args hold; one workgroup serves one tracker and
+// no workgroup waits for another. What the host learns only after the first wait does not change the records: `cur` (which of the two lists
+// holds the group's tracks: 1 once a rejectWithF stage has been launched for the group) is a launch argument, and f_run (one word per
+// tracker, null when the group made no F launch) says whose F stage ran.
+struct KltManyRec {
+    KltFilterArgs filter;
+    KltCompactArgs by_f, by_keep;    // in / out: set by the kernel from lst[cur], lst[cur ^ 1]
+    KltAppendArgs append;            // in: lst[cur]; f_info: set by the kernel
+    KltList lst[2];
+    const int* f_info;               // (found, drawn) of the tracker's F result block
+    unsigned long long prev_off, next_off;   // byte offsets of the tracker's two frame slots
+    int lk_base, lk_flags;           // first index of the tracker's share of the launch's LK records and results; LKX_FB or 0
+};
+// LK's records for the whole group, written where the tracks are: block lk_base + i tracks state position i of its tracker (geometry entry 0
+// of the call's own one-entry table). The host sized the shares from the n0 it holds; `total` = their sum bounds every store.
+__global__ __launch_bounds__(KT) void k_klt_lk_records(const KltManyRec* __restrict__ recs, LKBlock* __restrict__ blocks, LKExt* __restrict__ ext, int total) {
+    BACKEND_PRIO();
+    const KltManyRec& R = recs[blockIdx.x];
+    const int base = R.lk_base, n0 = klt_clamp(R.filter.n0, total - base);
+    const float* __restrict__ xy = R.filter.prev;
+    for (int i = threadIdx.x; i < n0; i += KT) {
+        LKBlock b;
+        b.prev_off = R.prev_off; b.next_off = R.next_off; b.x = xy[2 * i]; b.y = xy[2 * i + 1]; b.track = base + i; b.geom = 0;
+        blocks[base + i] = b;
+        ext[base + i] = LKExt{0.f, 0.f, R.lk_flags, 0};
+    }
+}
+__global__ __launch_bounds__(KT) void k_klt_filter_many(const KltManyRec* __restrict__ recs) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    const KltFilterArgs A = recs[blockIdx.x].filter;
+    klt_filter(A, s_w);
+}
+__global__ __launch_bounds__(KT) void k_klt_compact_many(const KltManyRec* __restrict__ recs, int by_keep, int cur, const int* __restrict__ f_run) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    const KltManyRec& R = recs[blockIdx.x];
+    KltCompactArgs A = by_keep ? R.by_keep : R.by_f;
+    A.in = R.lst[cur & 1]; A.out = R.lst[(cur & 1) ^ 1];
+    if (!by_keep && !f_run[blockIdx.x]) A.mask = nullptr;
+    klt_compact_by<true>(A, s_w);
+}
+__global__ __launch_bounds__(KT) void k_klt_append_many(const KltManyRec* __restrict__ recs, int cur, const int* __restrict__ f_run) {
+    BACKEND_PRIO();
+    const KltManyRec& R = recs[blockIdx.x];
+    KltAppendArgs A = R.append;
+    A.in = R.lst[cur & 1];
+    A.f_info = f_run && f_run[blockIdx.x] ? R.f_info : nullptr;
+    klt_append(A);
 }
 
 // ---- the tracker's blocks, each described once ---------------------------------------------------------------------------------------
@@ -216,8 +283,54 @@ struct KltTracker {
     KltDev D; KltRecs R; KltRes O;
 };
 
+namespace {
+// ---- the blocks of a group (pmv_klt_step_many), each described once; n = trackers, sum = the sum of their targets, pad = the sum of their
+// refill_pad(target), cap = the largest target ---------------------------------------------------------------------------------------------
+// record block, pinned mirror and device copy: argument records | refill records | half-width tables | frame requests | the sub-pixel
+// launch's slots | the call's one-entry geometry table || F flags | F problems | F iteration tables. The front part goes up with every call,
+// the used part behind `front` only in front of a k_fundamental_ransac launch.
+struct KltGroupRecs {
+    Carved<KltManyRec> rec; Carved<RefillRec> rrec; Carved<uint8_t> hw; Carved<int> grec, slots; Carved<PyrLayout> geom; size_t front;
+    Carved<int> f_run; Carved<FundamentalProblem> fprob; Carved<double> ftab;
+};
+KltGroupRecs klt_group_recs(Carve& c, size_t n, size_t sum) {
+    KltGroupRecs R;
+    R.rec = c.take<KltManyRec>(n, 64); R.rrec = c.take<RefillRec>(n, 16); R.hw = c.take<uint8_t>(n * REFILL_HW, 16); R.grec = c.take<int>(n * CELL_STRIDE, 16);
+    R.slots = c.take<int>(n, 16); R.geom = c.take<PyrLayout>(1, 64);
+    c.skip_to(64);
+    R.front = c.bytes();
+    R.f_run = c.take<int>(n, 64); R.fprob = c.take<FundamentalProblem>(n, 64); R.ftab = c.take<double>(sum + 2 * n, 16);
+    return R;
+}
+// device block: LK records and results of the one launch | refill tables | the selection pass's words (found, statistics, wanted) | corners |
+// refined corners - each tracker's share starts where the host's record says
+struct KltGroupDev {
+    Carved<LKBlock> lkb; Carved<LKExt> lkx;
+    Carved<float> lk_xy, lk_err, bk_xy, bk_err; Carved<uint8_t> lk_st, bk_st;
+    Carved<unsigned> pos; Carved<int> prio; Carved<uint8_t> flag, keep;
+    Carved<int> m, stat, want, ixy;
+    Carved<float> sp_xy; Carved<uint8_t> sp_it, sp_fl;
+};
+KltGroupDev klt_group_dev(Carve& c, size_t n, size_t sum, size_t pad, size_t cap) {
+    KltGroupDev D;
+    D.lkb = c.take<LKBlock>(sum, 64); D.lkx = c.take<LKExt>(sum, 16);
+    D.lk_xy = c.take<float>(2 * sum, 16); D.lk_err = c.take<float>(sum, 16); D.bk_xy = c.take<float>(2 * sum, 16); D.bk_err = c.take<float>(sum, 16);
+    D.lk_st = c.take<uint8_t>(sum, 16); D.bk_st = c.take<uint8_t>(sum, 16);
+    D.pos = c.take<unsigned>(pad, 16); D.prio = c.take<int>(pad, 16); D.flag = c.take<uint8_t>(pad, 16); D.keep = c.take<uint8_t>(pad, 16);
+    D.m = c.take<int>(n, 16); D.stat = c.take<int>(2 * n, 16); D.want = c.take<int>(n, 16); D.ixy = c.take<int>(2 * n * cap, 16);
+    D.sp_xy = c.take<float>(2 * n * cap, 16); D.sp_it = c.take<uint8_t>(n * cap, 16); D.sp_fl = c.take<uint8_t>(n * cap, 16);
+    return D;
+}
+}  // namespace
+
+struct KltGroup {
+    Buf<uint8_t> d_rec, h_rec{MEM_PINNED}, d_mem;
+};
+
 void klt_destroy_all(pmv_ctx* ctx) {
     for (auto& t : ctx->klt) { delete t; t = nullptr; }
+    delete ctx->klt_group;
+    ctx->klt_group = nullptr;
 }
 
 }  // namespace pmv
@@ -416,7 +529,7 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
             const size_t fbytes = (size_t)((const char*)(R.ftab.h + n1 + 2) - R.fprob.h);
             CKC(hipMemcpyAsync((char*)t->d_rec.p + R.fprob.off, R.fprob.h, fbytes, hipMemcpyHostToDevice, s));
             CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)R.fprob.d, 1));
-            KltCompactArgs A{lst[0], lst[1], (const uint8_t*)(D.f_out.d + ESS_OUT_HDR), D.cnt.d + C_N1, cap, C_N2, 0, rf, D.cnt.d};
+            KltCompactArgs A{lst[0], lst[1], (const uint8_t*)(D.f_out.d + ESS_OUT_HDR), D.cnt.d + C_N1, cap, C_N2, 0, rf, D.cnt.d, D.cnt.d + C_WANT};
             ProfScope ps(K_GFTT_PICK, s);
             hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
             CKC(hipGetLastError());
@@ -428,7 +541,7 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
     CKC(launch_track_refill(s, R.rrec.d, 1, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
     launches += 2;
     {
-        KltCompactArgs A{lst[cur], lst[cur ^ 1], D.keep.d, D.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, D.cnt.d};
+        KltCompactArgs A{lst[cur], lst[cur ^ 1], D.keep.d, D.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, D.cnt.d, D.cnt.d + C_WANT};
         ProfScope ps(K_GFTT_PICK, s);
         hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
         CKC(hipGetLastError());
@@ -449,7 +562,7 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
     if (++t->seq == 0) t->seq = 1;
     O.hdr.h[9] = 0;
     {
-        KltAppendArgs A{lst[cur], D.cnt.d, D.ixy.d, p.subpix ? D.sp_xy.d : nullptr, f_ran ? (const int*)(D.f_out.d + ESS_OUT_INFO) : nullptr, n0, t->next_id, cap, t->seq,
+        KltAppendArgs A{lst[cur], D.cnt.d, D.cnt.d + C_M, D.ixy.d, p.subpix ? D.sp_xy.d : nullptr, f_ran ? (const int*)(D.f_out.d + ESS_OUT_INFO) : nullptr, n0, t->next_id, cap, t->seq,
                         D.s_id.d, D.s_age.d, D.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d};
         ProfScope ps(K_GFTT_PICK, s);
         hipLaunchKernelGGL(k_klt_append, dim3(1), dim3(KT), 0, s, A);
@@ -470,6 +583,245 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
     t->n = n; t->next_id += m;
     ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask is this step's now)
     ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches;
+    return PMV_OK;
+}
+
+// a check of a single call failed for tracker j of a group: its message, with the tracker named behind it
+static int klt_many_blame(pmv_ctx* ctx, int rc, int j, int id) {
+    char msg[400];
+    snprintf(msg, sizeof(msg), "%s", thread_error());
+    set_err(ctx, "%s (tracker %d of the group, id %d)", msg, j, id);
+    return rc;
+}
+
+int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, int* out_ids, int* out_ages, float* out_xy,
+                      float* out_prev_xy_or_null, int out_stride, int* out_n, int* out_counts8) {
+    const char* who = "pmv_klt_step_many";
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_step_many: null argument");
+    REQ(n_trk >= 1, PMV_ERR_INVALID, "%s: n_trk = %d is below 1", who, n_trk);
+    REQ(n_trk <= PMV_KLT_MAX_TRACKERS, PMV_ERR_CAPACITY, "%s: n_trk = %d is above %d (PMV_KLT_MAX_TRACKERS)", who, n_trk, PMV_KLT_MAX_TRACKERS);
+    REQ(ids && prev_slots && cur_slots && out_ids && out_ages && out_xy && out_n && out_counts8, PMV_ERR_INVALID, "%s: null argument", who);
+    KltTracker* T[PMV_KLT_MAX_TRACKERS];
+    int cap_max = 0;
+    for (int j = 0; j < n_trk; j++) {
+        if (const int rc = klt_find(ctx, who, ids[j], &T[j])) return klt_many_blame(ctx, rc, j, ids[j]);
+        for (int i = 0; i < j; i++) REQ(ids[i] != ids[j], PMV_ERR_INVALID, "%s: tracker id %d is named twice (trackers %d and %d of the group)", who, ids[j], i, j);
+        cap_max = std::max(cap_max, T[j]->cap);
+    }
+    REQ(out_stride >= cap_max, PMV_ERR_CAPACITY, "%s: out_stride = %d is below the largest target of the group, %d", who, out_stride, cap_max);
+    // the launch-wide fields: arguments of the detector's and the refinement's one launch
+    const pmv_klt_params& p0 = T[0]->p;
+    for (int j = 1; j < n_trk; j++) {
+        const pmv_klt_params& p = T[j]->p;
+        const char* field = p.gftt.quality != p0.gftt.quality ? "gftt.quality" : p.gftt.min_dist != p0.gftt.min_dist ? "gftt.min_dist"
+                          : p.gftt.block_size != p0.gftt.block_size ? "gftt.block_size" : p.gftt.use_harris != p0.gftt.use_harris ? "gftt.use_harris"
+                          : p.gftt.k != p0.gftt.k ? "gftt.k" : p.subpix != p0.subpix ? "subpix" : nullptr;
+        if (!field && p0.subpix) {
+            const pmv_subpix_params &a = p.subpix_params, &b = p0.subpix_params;
+            if (a.win_w != b.win_w || a.win_h != b.win_h || a.zero_w != b.zero_w || a.zero_h != b.zero_h || a.max_iter != b.max_iter || a.eps != b.eps) field = "subpix_params";
+        }
+        REQ(!field, PMV_ERR_INVALID, "%s: tracker %d of the group (id %d) differs from tracker 0 in %s, which is an argument of the group's one launch", who, j, ids[j], field);
+    }
+    // the slot rules of pmv_klt_step, for every tracker; then one frame size for the group
+    int roi[4] = {0, 0, 0, 0}, sum_cap = 0, sum_n0 = 0;
+    size_t sum_pad = 0;
+    bool any_f = false;
+    for (int j = 0; j < n_trk; j++) {
+        const KltTracker* t = T[j];
+        int r[4], gcap;
+        if (t->n > 0)
+            if (const int rc = lk_check(ctx, true, prev_slots[j], cur_slots[j], out_xy, t->n, out_xy, (const uint8_t*)out_ids, out_xy)) return klt_many_blame(ctx, rc, j, ids[j]);
+        if (const int rc = gftt_frame_check(ctx, who, true, cur_slots[j], nullptr, t->cap, &t->p.gftt, nullptr, 0, out_ids, t->cap, out_n, r, &gcap))
+            return klt_many_blame(ctx, rc, j, ids[j]);
+        if (j == 0) memcpy(roi, r, sizeof(roi));
+        REQ(r[2] == roi[2] && r[3] == roi[3], PMV_ERR_INVALID, "%s: tracker %d of the group (id %d) differs from tracker 0 in the frame size of its cur_slot (%dx%d, not %dx%d)", who,
+            j, ids[j], r[2], r[3], roi[2], roi[3]);
+        sum_cap += t->cap; sum_n0 += t->n; sum_pad += refill_pad(t->cap);
+        any_f = any_f || (t->p.reject_f && t->n >= 15);
+    }
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    const PyrLayout& L = ctx->slot_layout[cur_slots[0]];
+    const size_t n = (size_t)n_trk, pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3], mstride = (rpix + 3) & ~(size_t)3, lists = std::max(pix, n * rpix);
+    REQ(n * mstride + 64 <= 0xffffffffull, PMV_ERR_CAPACITY, "%s: the group's %d masks of %zu bytes do not fit a 32-bit offset", who, n_trk, rpix);
+    // the context's scratch of the refill and frame calls, one share per tracker
+    CKC(ctx->d_gfr_val.ensure(lists * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(lists * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(lists * sizeof(unsigned long long)));
+    CKC(ctx->d_gfr_info.ensure(2 * n * sizeof(unsigned)));
+    CKC(ctx->d_gfr_mask.ensure(std::max(pix, n * mstride) + 64));
+    CKC(ctx->d_refill_kept.ensure(std::max((size_t)PMV_REFILL_MAX_TRACKS, sum_pad) * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(n * sizeof(int)));
+    const pmv_klt_params& p = p0;
+    SubpixArgs SA{};
+    if (p.subpix) {   // the weight table, as pmv_corner_subpix keeps it
+        const pmv_subpix_params* sp = &p.subpix_params;
+        CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
+        int zw, zh;
+        subpix_zero_zone(sp, &zw, &zh);
+        const int key[4] = {sp->win_w, sp->win_h, zw, zh};
+        if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
+            CKC(hipStreamSynchronize(ctx->s_front));
+            subpix_table(sp->win_w, sp->win_h, zw, zh, ctx->h_subpix_tab);
+            CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * sp->win_w + 1) * (2 * sp->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
+            memcpy(ctx->subpix_tab_key, key, sizeof(key));
+        }
+        SA = SubpixArgs{sp->win_w, sp->win_h, sp->max_iter, sp->eps * sp->eps};
+    }
+    // the group's own blocks, grown to the largest group seen
+    if (!ctx->klt_group) ctx->klt_group = new KltGroup();
+    KltGroup* G = ctx->klt_group;
+    Carve nr, nd;
+    klt_group_recs(nr, n, (size_t)sum_cap); klt_group_dev(nd, n, (size_t)sum_cap, sum_pad, (size_t)cap_max);
+    hipStream_t s = ctx->s_front;
+    if (nr.bytes() + 64 > G->d_rec.cap || nd.bytes() + 64 > G->d_mem.cap) CKC(hipStreamSynchronize(s));   // (nothing of an earlier call reads the old blocks)
+    CKC(G->d_rec.ensure(nr.bytes() + 64)); CKC(G->h_rec.ensure(nr.bytes() + 64)); CKC(G->d_mem.ensure(nd.bytes() + 64));
+    Carve cr(G->h_rec.p, G->d_rec.p, G->h_rec.cap), cd(nullptr, G->d_mem.p, G->d_mem.cap);
+    const KltGroupRecs R = klt_group_recs(cr, n, (size_t)sum_cap);
+    const KltGroupDev D = klt_group_dev(cd, n, (size_t)sum_cap, sum_pad, (size_t)cap_max);
+    long long launches = 0, waits = 0;
+    // records: per tracker its arguments, its refill request (n is written by the kernels) and its frame request; the geometry entry
+    const unsigned long long pitch = ctx->cap.slot_bytes;
+    *R.geom.h = L;
+    size_t lk_base = 0, pad_off = 0;
+    for (int j = 0; j < n_trk; j++) {
+        KltTracker* t = T[j];
+        const pmv_klt_params& q = t->p;
+        const KltDev& TD = t->D; const KltRes& O = t->O;
+        const int cap = t->cap, n0 = t->n;
+        const bool fb = q.fb_max_dist >= 0.0;
+        R.rrec.h[j] = RefillRec{0, q.radius, (int)pad_off, roi[0], roi[1], roi[2], roi[3], (unsigned)((size_t)j * mstride), 0, {0, 0, 0}};
+        memcpy(R.hw.h + (size_t)j * REFILL_HW, t->R.hw.h, REFILL_HW);
+        int* g = R.grec.h + (size_t)j * CELL_STRIDE;
+        gftt_frame_record(g, roi, cur_slots[j], (size_t)j * rpix, nullptr, 0, nullptr, 0);
+        g[5] = (int)(unsigned)((size_t)j * mstride);
+        R.slots.h[j] = cur_slots[j];
+        if (++t->seq == 0) t->seq = 1;
+        O.hdr.h[9] = 0;
+        KltManyRec& M = R.rec.h[j];
+        memset(&M, 0, sizeof(M));
+        const KltRefillIn rf{D.pos.d + pad_off, D.prio.d + pad_off, D.flag.d + pad_off, R.rrec.d + j};
+        for (int k = 0; k < 2; k++) M.lst[k] = KltList{TD.l_id[k].d, TD.l_age[k].d, TD.l_prev[k].d, TD.l_cur[k].d};
+        M.filter = KltFilterArgs{n0, fb ? 1 : 0, q.border, L.w[0], L.h[0], t->thr2, TD.s_id.d, TD.s_age.d, TD.s_xy.d, D.lk_xy.d + 2 * lk_base, D.bk_xy.d + 2 * lk_base,
+                                 D.lk_st.d + lk_base, D.bk_st.d + lk_base, M.lst[0], rf, TD.cnt.d, O.n1.d};
+        M.by_f = KltCompactArgs{M.lst[0], M.lst[1], (const uint8_t*)(TD.f_out.d + ESS_OUT_HDR), TD.cnt.d + C_N1, cap, C_N2, 0, rf, TD.cnt.d, D.want.d + j};
+        M.by_keep = KltCompactArgs{M.lst[0], M.lst[1], D.keep.d + pad_off, TD.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, TD.cnt.d, D.want.d + j};
+        M.append = KltAppendArgs{M.lst[0], TD.cnt.d, D.m.d + j, D.ixy.d + (size_t)2 * j * cap_max, q.subpix ? D.sp_xy.d + (size_t)2 * j * cap_max : nullptr, nullptr, n0, t->next_id, cap,
+                                 t->seq, TD.s_id.d, TD.s_age.d, TD.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d};
+        M.f_info = (const int*)(TD.f_out.d + ESS_OUT_INFO);
+        M.prev_off = (unsigned long long)(n0 > 0 ? prev_slots[j] : cur_slots[j]) * pitch; M.next_off = (unsigned long long)cur_slots[j] * pitch;
+        M.lk_base = (int)lk_base; M.lk_flags = fb ? LKX_FB : 0;
+        lk_base += (size_t)n0; pad_off += refill_pad(cap);
+    }
+    CKC(hipMemcpyAsync(G->d_rec, G->h_rec, R.front, hipMemcpyHostToDevice, s));
+    // 1. track: the records are written on the device, where the positions are, and the whole group is one launch
+    if (sum_n0 > 0) {
+        {
+            ProfScope ps(K_GFTT_PICK, s);
+            hipLaunchKernelGGL(k_klt_lk_records, dim3(n_trk), dim3(KT), 0, s, R.rec.d, D.lkb.d, D.lkx.d, sum_n0);
+            CKC(hipGetLastError());
+        }
+        CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx.d, sum_n0, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
+                               D.bk_err.d));
+        launches += 2;
+    }
+    // 2. filter
+    {
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_filter_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d);
+        CKC(hipGetLastError());
+        launches++;
+    }
+    // 3. rejectWithF: the host reads every n1 (the iteration tables are libm's); one copy and one launch serve the trackers that have the stage
+    int cur = 0;
+    const int* f_run = nullptr;
+    if (any_f) {
+        CKC(hipStreamSynchronize(s));
+        waits++;
+        int n_f = 0;
+        size_t tab = 0;
+        for (int j = 0; j < n_trk; j++) {
+            const KltTracker* t = T[j];
+            R.f_run.h[j] = 0;
+            if (!(t->p.reject_f && t->n >= 15)) continue;
+            const int n1 = *t->O.n1.h;
+            REQ(n1 >= 0 && n1 <= t->n, PMV_ERR_HIP, "%s: the filter left n1 = %d of %d tracks (tracker %d of the group)", who, n1, t->n, j);
+            if (n1 < 15) continue;
+            FundamentalProblem P;
+            P.p1 = t->D.l_prev[0].d; P.p2 = t->D.l_cur[0].d; P.iters = R.ftab.d + tab; P.out = t->D.f_out.d;
+            P.n = n1; P.max_iters = 1000; P.thr = (float)(t->p.f_threshold * t->p.f_threshold); P.done_seq = 1;
+            R.fprob.h[n_f++] = P;
+            vo::ransac_iters_table(n1, t->p.f_confidence, 7, R.ftab.h + tab + 1, R.ftab.h + tab);
+            tab += (size_t)n1 + 2;
+            R.f_run.h[j] = 1;
+        }
+        if (n_f > 0) {
+            const size_t b0 = R.f_run.off, b1 = R.ftab.off + tab * sizeof(double);
+            CKC(hipMemcpyAsync((char*)G->d_rec.p + b0, (const char*)G->h_rec.p + b0, b1 - b0, hipMemcpyHostToDevice, s));
+            CKC(launch_fundamental_ransac(s, R.fprob.d, n_f));
+            f_run = R.f_run.d;
+            ProfScope ps(K_GFTT_PICK, s);
+            hipLaunchKernelGGL(k_klt_compact_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, 0, 0, f_run);
+            CKC(hipGetLastError());
+            launches += 2;
+            cur = 1;
+        }
+    }
+    // 4. thin
+    CKC(launch_track_refill(s, R.rrec.d, n_trk, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    launches += 2;
+    {
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_compact_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, 1, cur, f_run);
+        CKC(hipGetLastError());
+        launches++;
+        cur ^= 1;
+    }
+    // 5. refill: every tracker's selection takes its cap from its own word
+    const GfttExt X = gftt_ext(p.gftt.block_size, p.gftt.use_harris, p.gftt.k);
+    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, n_trk, gftt_frame_grid_x(roi[2], roi[3]), cap_max, p.gftt.quality, p.gftt.min_dist, 0, &X, ctx->d_gfr_mask.get(),
+                          ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, D.ixy.d, D.m.d, D.stat.d, D.want.d));
+    launches += 2;
+    // 6. refine
+    if (p.subpix) {
+        CKC(launch_corner_subpix_dev(s, ctx->d_slots, L, D.ixy.d, 0, cap_max, D.m.d, ctx->d_subpix_tab, SA, D.sp_xy.d, D.sp_it.d, D.sp_fl.d, R.slots.d, n_trk));
+        launches++;
+    }
+    // 7. append: every workgroup stores its tracker's completion word last
+    {
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_append_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, cur, f_run);
+        CKC(hipGetLastError());
+        launches++;
+    }
+    CKC(hipStreamSynchronize(s));
+    waits++;
+    for (int j = 0; j < n_trk; j++) {
+        const KltTracker* t = T[j];
+        const int* hdr = t->O.hdr.h;
+        const int nn = hdr[8], m = hdr[4];
+        REQ((unsigned)hdr[9] == t->seq && nn >= 0 && nn <= t->cap && m >= 0 && m <= nn, PMV_ERR_HIP, "%s: the result block of tracker %d of the group is incomplete (n = %d, m = %d)",
+            who, j, nn, m);
+    }
+    for (int j = 0; j < n_trk; j++) {
+        KltTracker* t = T[j];
+        const KltRes& O = t->O;
+        const int* hdr = O.hdr.h;
+        const int nn = hdr[8], m = hdr[4];
+        const size_t o = (size_t)j * out_stride;
+        memcpy(out_ids + o, O.id.h, (size_t)nn * 4);
+        memcpy(out_ages + o, O.age.h, (size_t)nn * 4);
+        memcpy(out_xy + 2 * o, O.xy.h, (size_t)nn * 8);
+        if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null + 2 * o, O.prev.h, (size_t)nn * 8);
+        memcpy(out_counts8 + 8 * j, hdr, 8 * sizeof(int));
+        out_n[j] = nn;
+        t->n = nn; t->next_id += m;
+    }
+    ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask at the front is tracker 0's)
+    ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches;
+    return PMV_OK;
+}
+
+int pmv_debug_klt_many_stats(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_klt_many_stats: null argument");
+    for (int i = 0; i < 4; i++) out4[i] = ctx->klt_many_stats[i].load();
     return PMV_OK;
 }
 

@@ -124,11 +124,14 @@ __device__ __forceinline__ SpResult sp_refine(const uint8_t* __restrict__ slot, 
 
 // TABLE: the records' geometry is an entry of the context's table (the batch engine: one launch for points of any slots and frame sizes);
 // otherwise every record has the geometry L1 (the single call). The same function does the work: the bytes are the same.
-template <bool TABLE>
+// GROUP (a group of trackers): blockIdx.y is the request - its count word n_dev[request], its frame slot req_slots[request], its share of n
+// points in ixy and in the outputs. Every other form is the one request it was, and its code is what it was.
+template <bool TABLE, bool GROUP = false>
 __global__ __launch_bounds__(SP_T) void k_corner_subpix(const uint8_t* __restrict__ slots, const PyrLayout* __restrict__ geom, PyrLayout L1,
                                                         const SubpixRec* __restrict__ recs, int n, const float* __restrict__ table, SubpixArgs A,
                                                         float* __restrict__ out_xy, uint8_t* __restrict__ out_iters, uint8_t* __restrict__ out_flags,
-                                                        const int* __restrict__ n_dev, const int* __restrict__ ixy, int ixy_slot) {
+                                                        const int* __restrict__ n_dev, const int* __restrict__ ixy, int ixy_slot,
+                                                        const int* __restrict__ req_slots) {
     extern __shared__ float sp_lds[];
     BACKEND_PRIO();
     const int WW = 2 * A.win_w + 1, WH = 2 * A.win_h + 1;
@@ -136,13 +139,14 @@ __global__ __launch_bounds__(SP_T) void k_corner_subpix(const uint8_t* __restric
     for (int i = threadIdx.x; i < WW * WH; i += SP_T) sM[i] = table[i];
     __syncthreads();                                             // the only workgroup barrier, before any wavefront can leave
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int pt = blockIdx.x * SP_WAVES + wave;
     // n_dev / ixy (launch_corner_subpix_dev): the count comes from device memory, clamped to the grid's n, and the points are int corners
+    const int in_req = blockIdx.x * SP_WAVES + wave;
     int n_pts = n;
-    if (n_dev) { const int c = *n_dev; n_pts = c < 0 ? 0 : (c < n ? c : n); }
-    if (pt >= n_pts) return;
+    if (n_dev) { const int c = GROUP ? n_dev[blockIdx.y] : *n_dev; n_pts = c < 0 ? 0 : (c < n ? c : n); }
+    if (in_req >= n_pts) return;
+    const size_t pt = GROUP ? (size_t)blockIdx.y * n + in_req : (size_t)in_req;
     float* P = sp_lds + WW * WH + wave * (WW + 2) * (WH + 2);    // [(WW + 2) * (WH + 2)] this wavefront's patch
-    const SubpixRec r = ixy ? SubpixRec{(float)ixy[2 * (size_t)pt], (float)ixy[2 * (size_t)pt + 1], ixy_slot, 0} : recs[pt];
+    const SubpixRec r = ixy ? SubpixRec{(float)ixy[2 * pt], (float)ixy[2 * pt + 1], GROUP ? req_slots[blockIdx.y] : ixy_slot, 0} : recs[pt];
     const float tx = sp_uniform(r.x), ty = sp_uniform(r.y);
     const int slot = __builtin_amdgcn_readfirstlane(r.slot);
     SpResult R;
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(SP_T) void k_corner_subpix(const uint8_t* __restric
     } else
         R = sp_refine<const PyrLayout&>(slots + (size_t)slot * L1.slot_bytes, L1, tx, ty, A, sM, P, lane);
     if (lane == 0) {
-        out_xy[2 * (size_t)pt] = R.x; out_xy[2 * (size_t)pt + 1] = R.y;
+        out_xy[2 * pt] = R.x; out_xy[2 * pt + 1] = R.y;
         out_iters[pt] = (uint8_t)R.updates; out_flags[pt] = (uint8_t)R.flags;
     }
 }
@@ -187,7 +191,7 @@ hipError_t launch_corner_subpix(hipStream_t s, const uint8_t* slots, const PyrLa
     if (!slots || !d_recs || !d_table || !d_out_xy || !d_out_iters || !d_out_flags || n < 1 || !sp_args_ok(A)) return hipErrorInvalidValue;
     ProfScope ps(K_GFTT_PICK, s);
     hipLaunchKernelGGL(k_corner_subpix<false>, dim3((n + SP_WAVES - 1) / SP_WAVES), dim3(SP_T), sp_lds_bytes(A), s, slots, (const PyrLayout*)nullptr, L, d_recs, n, d_table, A,
-                       d_out_xy, d_out_iters, d_out_flags, (const int*)nullptr, (const int*)nullptr, 0);
+                       d_out_xy, d_out_iters, d_out_flags, (const int*)nullptr, (const int*)nullptr, 0, (const int*)nullptr);
     return hipGetLastError();
 }
 
@@ -196,16 +200,21 @@ hipError_t launch_corner_subpix_geom(hipStream_t s, const uint8_t* slots, const 
     if (!slots || !d_geom || !d_recs || !d_table || !d_out_xy || !d_out_iters || !d_out_flags || n < 1 || !sp_args_ok(A)) return hipErrorInvalidValue;
     ProfScope ps(K_GFTT_PICK, s);
     hipLaunchKernelGGL(k_corner_subpix<true>, dim3((n + SP_WAVES - 1) / SP_WAVES), dim3(SP_T), sp_lds_bytes(A), s, slots, d_geom, PyrLayout{}, d_recs, n, d_table, A,
-                       d_out_xy, d_out_iters, d_out_flags, (const int*)nullptr, (const int*)nullptr, 0);
+                       d_out_xy, d_out_iters, d_out_flags, (const int*)nullptr, (const int*)nullptr, 0, (const int*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_corner_subpix_dev(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_ixy, int slot, int n_cap, const int* d_n, const float* d_table,
-                                    const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags) {
-    if (!slots || !d_ixy || !d_n || !d_table || !d_out_xy || !d_out_iters || !d_out_flags || n_cap < 1 || slot < 0 || !sp_args_ok(A)) return hipErrorInvalidValue;
+                                    const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags, const int* d_req_slots, int n_req) {
+    if (!slots || !d_ixy || !d_n || !d_table || !d_out_xy || !d_out_iters || !d_out_flags || n_cap < 1 || (!d_req_slots && slot < 0) || n_req < 1 || n_req > 65535 ||
+        (n_req > 1 && !d_req_slots) || !sp_args_ok(A)) return hipErrorInvalidValue;
     ProfScope ps(K_GFTT_PICK, s);
-    hipLaunchKernelGGL(k_corner_subpix<false>, dim3((n_cap + SP_WAVES - 1) / SP_WAVES), dim3(SP_T), sp_lds_bytes(A), s, slots, (const PyrLayout*)nullptr, L,
-                       (const SubpixRec*)nullptr, n_cap, d_table, A, d_out_xy, d_out_iters, d_out_flags, d_n, d_ixy, slot);
+    if (d_req_slots)
+        hipLaunchKernelGGL((k_corner_subpix<false, true>), dim3((n_cap + SP_WAVES - 1) / SP_WAVES, n_req), dim3(SP_T), sp_lds_bytes(A), s, slots, (const PyrLayout*)nullptr, L,
+                           (const SubpixRec*)nullptr, n_cap, d_table, A, d_out_xy, d_out_iters, d_out_flags, d_n, d_ixy, slot, d_req_slots);
+    else
+        hipLaunchKernelGGL(k_corner_subpix<false>, dim3((n_cap + SP_WAVES - 1) / SP_WAVES), dim3(SP_T), sp_lds_bytes(A), s, slots, (const PyrLayout*)nullptr, L,
+                           (const SubpixRec*)nullptr, n_cap, d_table, A, d_out_xy, d_out_iters, d_out_flags, d_n, d_ixy, slot, (const int*)nullptr);
     return hipGetLastError();
 }
 

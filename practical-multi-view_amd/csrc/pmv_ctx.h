@@ -22,6 +22,7 @@ constexpr int MAX_CELLS = 64;       // 1920x1080 -> 8x5 = 40 cells of 255x255
 constexpr int MAX_PER_CELL = 4096;    // also the capacity of an "unlimited" (max_per_cell <= 0) goodFeaturesToTrack call
 struct BackendBuffers;              // PnP / BA device workspaces (backend.hip)
 struct KltTracker;                  // a device-resident KLT tracker (frontend_klt.hip)
+struct KltGroup;                    // what a pmv_klt_step_many call keeps in the context (frontend_klt.hip)
 }
 
 // In-memory log of the back-end plugin calls (pmv_record_*): every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates
@@ -141,6 +142,11 @@ struct pmv_ctx {
     pmv::KltTracker* klt[PMV_KLT_MAX_TRACKERS] = {};
     std::mutex klt_mu;
     std::atomic<long long> klt_stats[3];
+    // pmv_klt_step_many: the group's record block, its shares of per-launch tables and its argument records, made by the first many-call and
+    // grown to the largest group seen (freed by klt_destroy_all). pmv_debug_klt_many_stats: many-calls | trackers stepped by them | host
+    // waits inside them | kernel launches inside them
+    pmv::KltGroup* klt_group = nullptr;
+    std::atomic<long long> klt_many_stats[4];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;

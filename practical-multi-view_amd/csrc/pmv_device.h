@@ -287,8 +287,8 @@ constexpr int GFTT_FRAME_ONCHIP = 16384;   // records the selection kernel sorts
 hipError_t launch_gftt_frame(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_recs, int n_req, int grid_x, int cap, double quality,
                              double min_dist, int unlimited, const GfttExt* X, const uint8_t* d_mask, float* d_val, unsigned* d_idx, unsigned* d_info,
                              unsigned long long* d_keys, int* d_out_xy, int* d_out_count, int* d_stats, const int* d_cap = nullptr);
-// d_cap (the tracker's chain, n_req = 1): the number of corners wanted, read by the selection from device memory and clamped to 0 .. cap;
-// `cap` stays the capacity of the list. Null: cap itself, as ever.
+// d_cap (the tracker's chain): one word per request, the number of corners wanted, read by the selection from device memory and clamped to
+// 0 .. cap; `cap` stays the capacity of every request's list. Null: cap itself, as ever.
 
 // ---- keep-away mask of a track list (frontend_refill.hip) ----------------------------------------------------------
 // pmv_detect_gftt_refill / pmv_batch_detect_gftt_refill: FeatureTracker::setMask on the device. One record per request; the tables of a
@@ -337,8 +337,10 @@ hipError_t launch_corner_subpix(hipStream_t s, const uint8_t* slots, const PyrLa
                                 float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
 // The tracker's chain: the grid is sized for n_cap points, the point count is read from *d_n (clamped to 0 .. n_cap; a wavefront beyond it
 // leaves at once) and point i is the detector's corner ((float)d_ixy[2 i], (float)d_ixy[2 i + 1]) of frame slot `slot`.
+// With d_req_slots (a group of trackers): n_req requests of n_cap points each, one after the other in d_ixy and in the outputs; request r reads
+// its count from d_n[r] and its frame slot from d_req_slots[r] (`slot` is ignored). Null, n_req = 1: the one request above.
 hipError_t launch_corner_subpix_dev(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const int* d_ixy, int slot, int n_cap, const int* d_n, const float* d_table,
-                                    const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
+                                    const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags, const int* d_req_slots = nullptr, int n_req = 1);
 hipError_t launch_corner_subpix_geom(hipStream_t s, const uint8_t* slots, const PyrLayout* d_geom, const SubpixRec* d_recs, int n, const float* d_table,
                                      const SubpixArgs& A, float* d_out_xy, uint8_t* d_out_iters, uint8_t* d_out_flags);
 
