@@ -780,8 +780,8 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
 int pmv_debug_klt_stats(pmv_ctx* ctx, long long* out4);
 
 /* ---- A group of trackers in one call: pmv_klt_step_many ------------------------------------------------------------------------------------
- * A step is 8-10 short, serially dependent launches and one or two host waits; a caller with several cameras (a stereo pair, a rig, sequences
- * replayed side by side) pays that once per camera with pmv_klt_step. pmv_klt_step_many steps n_trk trackers of the context through ONE chain
+ * A step is 8-10 short, serially dependent launches and one or two host waits; a caller with several cameras (a rig, sequences replayed side by
+ * side; left and right of a stereo rig share ONE list: pmv_klt_step_stereo below) pays that once per camera with pmv_klt_step. pmv_klt_step_many steps n_trk trackers of the context through ONE chain
  * of launches.
  * Result definition: tracker j of the call is ids[j]. Its lists start at track j * out_stride of out_ids / out_ages / out_xy / out_prev_xy
  *   (xy: 2 floats a track), its count is out_n[j] and its counts are out_counts8[8 j .. 8 j + 7]. For every j the outputs and the tracker's
@@ -814,6 +814,62 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
                       float* out_prev_xy_or_null, int out_stride, int* out_n /* n_trk */, int* out_counts8 /* 8 * n_trk */);
 /* diagnostic: out4 = {many-calls, trackers stepped by them, host waits inside them, kernel launches inside them} since the context was created */
 int pmv_debug_klt_many_stats(pmv_ctx* ctx, long long* out4);
+
+/* ---- Stereo matches in the tracker step: left-to-right LK as stage 8 ----------------------------------------------------------------------
+ * A stereo front end of the VINS kind (FeatureTracker::trackImage with a second image) keeps ONE list, on the left camera; after the refill
+ * it runs LK from the current left frame into the current right frame for every track of the list, new corners included, and LK back, and a
+ * track gets a right observation iff both passes succeed and the round trip ends near its start. pmv_klt_step_stereo is pmv_klt_step with
+ * that as a stage 8 behind the append, in the same call and with no additional wait; pmv_klt_step and pmv_klt_step_many are unchanged.
+ * Result definition: let (ids, ages, xy, prev_xy, counts8, n) be what pmv_klt_step(ctx, id, prev_slot, cur_slot, ..) returns from the
+ *   tracker's state. The stereo step returns exactly those bytes and leaves exactly that state (the right observations are not state),
+ *   except counts8[7], and in addition, for i < n:
+ *   Back check on (the stereo setting's fb_max_dist >= 0): (rxy, st, err, back, bst, berr) = the outputs of pmv_lk_track_fb(ctx, cur_slot,
+ *     right_slot, xy, n, flags 0) under the context's pmv_set_lk_params; ok[i] = st[i] == 1 && bst[i] == 1 && dx * dx + dy * dy <= thr2 &&
+ *     inBorder(rxy[i]), with dx = back.x - xy.x, dy likewise, both products and the sum float32 operations without contraction, thr2 =
+ *     (float)(fb_max_dist * fb_max_dist) computed on the host, and inBorder stage 2's rule (lrintf, round half to even) with the stereo
+ *     setting's border and the right frame's size. This is stage 2's arithmetic, run by stage 2's code.
+ *   Back check off (fb_max_dist < 0): the outputs are those of pmv_lk_track_ex(.., flags 0); ok[i] = st[i] == 1 && inBorder(rxy[i]).
+ *   out_right_xy[2 i .. 2 i + 1] = the bits of rxy[i] for every i < n, matched or not; out_right_status[i] = ok[i] as 0 or 1; counts8[7] =
+ *     the number of matched tracks (0 in pmv_klt_step, which stays so). The arrays are aligned with the left list: a caller pairs by index.
+ *   n == 0: nothing is written to the right arrays and counts8[7] = 0.
+ * Two differences from the VINS loop: the backward pass of pmv_lk_track_fb starts at the left position (its initial-flow second trip),
+ *   while the VINS stereo reverse pass starts at the right position; and VINS applies no border test when its back check is off, this stage
+ *   applies one.
+ * pmv_klt_set_stereo gives a tracker its stereo setting (NULL turns it off, which is the default; it may change between steps);
+ *   pmv_klt_get_stereo reads it (*out_on = 0 / 1; *out = the last setting given, zeros if none).
+ * pmv_klt_step_many_stereo: tracker j is byte for byte its own pmv_klt_step_stereo. right_slots[j] < 0 means tracker j has no right frame
+ *   in this call (a mono camera in a rig next to a stereo pair): it gets the bytes of pmv_klt_step, right status all 0 and counts8[7] = 0,
+ *   its right xy are not written and it needs no stereo setting. fb_max_dist and border may differ from tracker to tracker; the right
+ *   frames have the size of the group's current frames. Tracker j's right arrays start at track j * out_stride, like its left lists.
+ * Device side: no additional wait - a stereo step waits as often as pmv_klt_step from the same state (once, twice with reject_f), a stereo
+ *   many-call at most twice; the launches of stage 8 are enqueued behind the append. The length of the list after the append is known only
+ *   on the device: the LK launch of stage 8 is sized by the bound (target; in the many form the sum of the targets of the trackers with a
+ *   right slot) and reads the count the append left in device memory; workgroups beyond it leave at once. Stage 8 adds at most 3 launches to
+ *   a step and at most 3 to a many-call, whatever n_trk is. Its scratch is the LK result arrays of stage 1, free again by then: single
+ *   calls between two steps return their usual bytes.
+ * Errors (nothing is written, nothing is clamped, no tracker's state changes): PMV_ERR_INVALID - a null out_right_xy or out_right_status
+ *   (or right_slots); a stereo step on a tracker without a stereo setting (the message says so); at pmv_klt_set_stereo fb_max_dist not
+ *   finite (either infinity included) or above 1e3, border outside 0..64 (the old setting is kept). The slot errors of pmv_lk_track for the pair (cur_slot,
+ *   right_slot) - range, empty slot, differing sizes, open bracket - with that call's code, checked before anything is launched, since n
+ *   is unknown then; in the many form the message names the tracker. Everything pmv_klt_step and pmv_klt_step_many refuse is refused in the
+ *   same words. The last kernel of the chain is the stereo one and writes the completion word the host checks: an incomplete result block
+ *   is PMV_ERR_HIP and n and next_id are not updated.
+ * Counters: stereo calls do not move pmv_debug_klt_stats or pmv_debug_klt_many_stats; pmv_debug_klt_stereo_stats counts them.
+ * Out of scope: the session form, a backward pass without the initial guess, a right frame of another size or pyramid depth, an epipolar
+ *   band or a disparity prior, normalised coordinates and velocities, compacted right lists, right positions as tracker state. */
+typedef struct pmv_klt_stereo_params {
+    double fb_max_dist;     /* finite; < 0: no backward pass, else 0 .. 1e3 */
+    int    border;          /* 0 .. 64 */
+} pmv_klt_stereo_params;
+int pmv_klt_set_stereo(pmv_ctx* ctx, int id, const pmv_klt_stereo_params* p_or_null);
+int pmv_klt_get_stereo(pmv_ctx* ctx, int id, pmv_klt_stereo_params* out, int* out_on);
+int pmv_klt_step_stereo(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int right_slot, int* out_ids, int* out_ages, float* out_xy,
+                        float* out_prev_xy_or_null, float* out_right_xy, uint8_t* out_right_status, int out_cap, int* out_n, int* out_counts8);
+int pmv_klt_step_many_stereo(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, const int* right_slots,
+                             int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, float* out_right_xy,
+                             uint8_t* out_right_status, int out_stride, int* out_n /* n_trk */, int* out_counts8 /* 8 * n_trk */);
+/* diagnostic: out4 = {stereo steps, stereo many-calls, host waits inside both, kernel launches inside both} since the context was created */
+int pmv_debug_klt_stereo_stats(pmv_ctx* ctx, long long* out4);
 
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those

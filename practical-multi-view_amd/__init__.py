@@ -69,6 +69,11 @@ def klt_params(target=150, border=1, fb_max_dist=0.5, reject_f=True, f_threshold
                      SubpixParams(int(subpix_win[0]), int(subpix_win[1]), int(subpix_zero_zone[0]), int(subpix_zero_zone[1]), int(subpix_max_iter), float(subpix_eps)))
 
 
+class KltStereoParams(C.Structure):
+    """pmv_klt_stereo_params of include/pmv_hip.h"""
+    _fields_ = [("fb_max_dist", C.c_double), ("border", C.c_int)]
+
+
 class KltTracker:
     """A tracker of Context.klt_create. The state - ids, ages, positions - lives in device memory; step() returns the new list."""
 
@@ -88,6 +93,41 @@ class KltTracker:
         ctx._ck(fn(ctx.h, self.id, int(prev_slot), int(cur_slot), _p(ids, _i32p), _p(ages, _i32p), _p(xy, _f32p), _p(prev, _f32p), cap, C.byref(n), _p(counts, _i32p)))
         k = n.value
         return ids[:k].copy(), ages[:k].copy(), xy[:k].copy(), prev[:k].copy(), counts
+
+    def set_stereo(self, fb_max_dist=0.5, border=1):
+        """pmv_klt_set_stereo: the setting of step_stereo's stage 8 - the forward-backward distance of the left-to-right LK (negative: no
+        backward pass) and the border of the right frame. fb_max_dist=None turns the setting off."""
+        fn = self.ctx.lib.pmv_klt_set_stereo
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(KltStereoParams)]
+        if fb_max_dist is None:
+            self.ctx._ck(fn(self.ctx.h, self.id, None))
+            return
+        p = KltStereoParams(float(fb_max_dist), int(border))
+        self.ctx._ck(fn(self.ctx.h, self.id, C.byref(p)))
+
+    def get_stereo(self):
+        """pmv_klt_get_stereo: (fb_max_dist, border) of the stereo setting, or None when it is off"""
+        p, on = KltStereoParams(), C.c_int(0)
+        fn = self.ctx.lib.pmv_klt_get_stereo
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(KltStereoParams), C.POINTER(C.c_int)]
+        self.ctx._ck(fn(self.ctx.h, self.id, C.byref(p), C.byref(on)))
+        return (p.fb_max_dist, p.border) if on.value else None
+
+    def step_stereo(self, prev_slot, cur_slot, right_slot):
+        """pmv_klt_step_stereo: step()'s 5-tuple (counts[7] = the number of matched tracks), then right_xy (n, 2) float32 - where LK from
+        cur_slot into right_slot put every track of the list - and right_status (n,) uint8, 1 for the tracks that have a right observation"""
+        ctx, cap = self.ctx, self.target
+        ids, ages = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        xy, prev, rxy = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        rst = np.zeros(cap, np.uint8)
+        counts = np.zeros(8, np.int32)
+        n = C.c_int(0)
+        fn = ctx.lib.pmv_klt_step_stereo
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, _f32p, _u8p, C.c_int, C.POINTER(C.c_int), _i32p]
+        ctx._ck(fn(ctx.h, self.id, int(prev_slot), int(cur_slot), int(right_slot), _p(ids, _i32p), _p(ages, _i32p), _p(xy, _f32p), _p(prev, _f32p), _p(rxy, _f32p),
+                   _p(rst, _u8p), cap, C.byref(n), _p(counts, _i32p)))
+        k = n.value
+        return ids[:k].copy(), ages[:k].copy(), xy[:k].copy(), prev[:k].copy(), counts, rxy[:k].copy(), rst[:k].copy()
 
     def set_tracks(self, ids, ages, xy, next_id):
         """pmv_klt_set_tracks: replace the state"""
@@ -266,6 +306,7 @@ ABI_SYMBOLS = [
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
+    "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -1202,6 +1243,39 @@ class Context:
         self._ck(fn(self.h, k, _p(ids, _i32p), _p(prev_slots, _i32p), _p(cur_slots, _i32p), _p(o_ids, _i32p), _p(o_ages, _i32p), _p(o_xy, _f32p), _p(o_prev, _f32p), stride,
                     _p(o_n, _i32p), _p(counts, _i32p)))
         return [(o_ids[j, :o_n[j]].copy(), o_ages[j, :o_n[j]].copy(), o_xy[j, :o_n[j]].copy(), o_prev[j, :o_n[j]].copy(), counts[j].copy()) for j in range(k)]
+
+    def klt_step_many_stereo(self, trackers, prev_slots, cur_slots, right_slots):
+        """pmv_klt_step_many_stereo: klt_step_many with stage 8 - a list of KltTracker.step_stereo's 7-tuples, one per tracker, each byte for
+        byte what its own step_stereo returns. right_slots[j] < 0: tracker j has no right frame in this call - step()'s bytes, right_status
+        all 0 and right_xy zeros."""
+        trackers = list(trackers)
+        for t in trackers:
+            if not isinstance(t, KltTracker) or t.ctx is not self or t.id is None:
+                raise ValueError("klt_step_many_stereo: every tracker must be an open KltTracker of this context")
+        k = len(trackers)
+        prev_slots, cur_slots = np.ascontiguousarray(prev_slots, np.int32).reshape(-1), np.ascontiguousarray(cur_slots, np.int32).reshape(-1)
+        right_slots = np.ascontiguousarray(right_slots, np.int32).reshape(-1)
+        if prev_slots.size != k or cur_slots.size != k or right_slots.size != k:
+            raise ValueError("klt_step_many_stereo: one prev_slot, one cur_slot and one right_slot per tracker")
+        ids = np.asarray([t.id for t in trackers], np.int32)
+        stride = max([t.target for t in trackers], default=1)
+        o_ids, o_ages = np.zeros((max(k, 1), stride), np.int32), np.zeros((max(k, 1), stride), np.int32)
+        o_xy, o_prev, o_rxy = (np.zeros((max(k, 1), stride, 2), np.float32) for _ in range(3))
+        o_rst = np.zeros((max(k, 1), stride), np.uint8)
+        o_n, counts = np.zeros(max(k, 1), np.int32), np.zeros((max(k, 1), 8), np.int32)
+        fn = self.lib.pmv_klt_step_many_stereo
+        fn.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p, _f32p, _u8p, C.c_int, _i32p, _i32p]
+        self._ck(fn(self.h, k, _p(ids, _i32p), _p(prev_slots, _i32p), _p(cur_slots, _i32p), _p(right_slots, _i32p), _p(o_ids, _i32p), _p(o_ages, _i32p), _p(o_xy, _f32p),
+                    _p(o_prev, _f32p), _p(o_rxy, _f32p), _p(o_rst, _u8p), stride, _p(o_n, _i32p), _p(counts, _i32p)))
+        return [(o_ids[j, :o_n[j]].copy(), o_ages[j, :o_n[j]].copy(), o_xy[j, :o_n[j]].copy(), o_prev[j, :o_n[j]].copy(), counts[j].copy(), o_rxy[j, :o_n[j]].copy(),
+                 o_rst[j, :o_n[j]].copy()) for j in range(k)]
+
+    def debug_klt_stereo_stats(self):
+        """pmv_debug_klt_stereo_stats: [stereo steps, stereo many-calls, host waits inside both, kernel launches inside both]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_klt_stereo_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_klt_stereo_stats(self.h, out))
+        return [int(v) for v in out]
 
     def debug_klt_many_stats(self):
         """pmv_debug_klt_many_stats: [many-calls, trackers stepped by them, host waits inside them, kernel launches inside them]"""

@@ -1221,6 +1221,15 @@ __global__ __launch_bounds__(LK_T) void k_lk_ex(const uint8_t* __restrict__ prev
     if (flags & LKX_INIT) { ix = init_xy[2 * t]; iy = init_xy[2 * t + 1]; }
     lk_track_ex<LK_T, GENERAL, const PyrLayout&>(prevS, nextS, L, uniform_f32(prev_xy[2 * t]), uniform_f32(prev_xy[2 * t + 1]), uniform_f32(ix), uniform_f32(iy), flags, P, t, O);
 }
+// the device-counted form (stage 8 of a stereo KLT step): the launch is sized by a bound n_cap, the count is a word an earlier kernel of the
+// chain left in device memory. Identity order, no initial flow; a block at or beyond the count leaves before it touches LDS or the frames.
+template <bool GENERAL>
+__global__ __launch_bounds__(LK_T) void k_lk_ex_dev(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, PyrLayout L,
+                                                    const float* __restrict__ prev_xy, const int* __restrict__ n_dev, int n_cap, int flags, LKParams P, LKExOut O) {
+    const int t = blockIdx.x, n = __builtin_amdgcn_readfirstlane(*n_dev);
+    if (t >= n || t >= n_cap) return;   // (a negative count serves nobody)
+    lk_track_ex<LK_T, GENERAL, const PyrLayout&>(prevS, nextS, L, uniform_f32(prev_xy[2 * t]), uniform_f32(prev_xy[2 * t + 1]), 0.f, 0.f, flags, P, t, O);
+}
 // the batched form: ext[b] belongs to blocks[b]
 template <bool GENERAL>
 __global__ __launch_bounds__(LKB_T) void k_lk_batch_ex(const uint8_t* __restrict__ slots, const LKBlock* __restrict__ blocks, const LKExt* __restrict__ ext,
@@ -1228,6 +1237,7 @@ __global__ __launch_bounds__(LKB_T) void k_lk_batch_ex(const uint8_t* __restrict
     for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {   // as k_lk_batch
         const LKBlock bk = blocks[b];
         const LKExt ex = ext[b];
+        if (__builtin_amdgcn_readfirstlane(ex.flags) & LKX_VOID) continue;   // workgroup-uniform: a record beyond its list's device-side count
         lk_track_ex<LKB_T, GENERAL, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), uniform_f32(bk.x), uniform_f32(bk.y),
                                                 uniform_f32(ex.ix), uniform_f32(ex.iy), __builtin_amdgcn_readfirstlane(ex.flags), P,
                                                 __builtin_amdgcn_readfirstlane(bk.track), O);
@@ -1304,6 +1314,20 @@ hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* 
     }
     ProfScope ps(K_LK, s);
     hipLaunchKernelGGL(k_lk_ex<false>, dim3(n_blocks), dim3(LK_T), 0, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O);
+    return hipGetLastError();
+}
+hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const int* d_n, int n_cap,
+                            int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, float* d_back_xy, uint8_t* d_back_status, float* d_back_err) {
+    if (n_cap <= 0) return hipSuccess;
+    if (!prev_slot || !next_slot || !d_prev_xy || !d_n || L.n_levels < 1 || L.n_levels > MAX_LEVELS || (flags & ~LKX_FB) ||
+        !lk_ex_args_ok(flags, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
+    const bool general = lk_use_general(P);
+    if (general && !lk_params_ok(P)) return hipErrorInvalidValue;
+    const LKExOut O{d_out_xy, d_status, d_err, nullptr, d_back_xy, d_back_status, d_back_err};
+    ProfScope ps(K_LK, s);
+    if (general) {
+        hipLaunchKernelGGL(k_lk_ex_dev<true>, dim3(n_cap), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_n, n_cap, flags, P, O);
+    } else hipLaunchKernelGGL(k_lk_ex_dev<false>, dim3(n_cap), dim3(LK_T), 0, s, prev_slot, next_slot, L, d_prev_xy, d_n, n_cap, flags, P, O);
     return hipGetLastError();
 }
 hipError_t launch_lk_batch_ex(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, const LKExt* d_ext, int n_blocks, const PyrLayout* d_geom, const LKParams& P,

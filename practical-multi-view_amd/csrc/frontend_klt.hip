@@ -10,6 +10,9 @@
 // per-tracker argument record in device memory), LK as one batched launch whose records k_klt_lk_records writes from the trackers' states,
 // and the multi-request forms of the refill, frame and F launches. pmv_klt_step keeps its own argument form: a group of one is ~25 us slower
 // (DESIGN.md §4).
+// pmv_klt_step_stereo / pmv_klt_step_many_stereo append a stage 8 behind the append and in front of the final wait: LK from the current left
+// into the right frame for the list the step returns, in a launch sized by the bound (target) whose workgroups read the list's length from
+// device memory, then one workgroup per tracker that applies stage 2's rule to the result and ends the chain with its own completion word.
 #include "pmv_ctx.h"
 #include "backend.h"
 #include "vo_pipeline.h"
@@ -22,7 +25,8 @@ namespace {
 
 constexpr int KT = 1024, KW = KT / 64;
 // counts of a step in device memory: n0, n1, n2, n3, corners wanted (target - n3), corners found (k_gftt_pick_frame's count), its two statistics
-enum { C_N0 = 0, C_N1, C_N2, C_N3, C_WANT, C_M, C_STAT0, C_STAT1, C_COUNT = 16 };
+// (C_NOUT: the length of the list after the append, left only by a stereo step - stage 8 reads it)
+enum { C_N0 = 0, C_N1, C_N2, C_N3, C_WANT, C_M, C_STAT0, C_STAT1, C_NOUT, C_COUNT = 16 };
 
 struct KltList { int* id; int* age; float* prev; float* cur; };                     // a track list on its way through the chain
 struct KltRefillIn { unsigned* pos; int* prio; uint8_t* flag; RefillRec* rec; };    // what k_track_select reads (pos null: not written)
@@ -64,19 +68,23 @@ struct KltFilterArgs {
     KltList out; KltRefillIn rf;
     int* cnt; int* h_n1;
 };
-__device__ __forceinline__ void klt_filter(const KltFilterArgs& A, unsigned* s_w) {
+// The rule of stages 2 and 8 for track i of A (KltFilterArgs or KltStereoArgs: fb, border, w, h, thr2, prev, fwd, back, st, bst): LK's status
+// bytes, the round trip back to `prev` within thr2, the forward position inside the border.
+template <class Args>
+__device__ __forceinline__ bool klt_track_ok(const Args& A, int i) {
     const float lo = (float)A.border, hx = (float)(A.w - A.border), hy = (float)(A.h - A.border);
+    bool ok = A.st[i] == 1;
+    if (A.fb) {
+        const float dx = __fsub_rn(A.back[2 * i], A.prev[2 * i]), dy = __fsub_rn(A.back[2 * i + 1], A.prev[2 * i + 1]);
+        ok = ok && A.bst[i] == 1 && __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= A.thr2;
+    }
+    // rintf: half to even; the comparison in float is lrintf's in int for every finite value, and a NaN fails it
+    const float rx = rintf(A.fwd[2 * i]), ry = rintf(A.fwd[2 * i + 1]);
+    return ok && rx >= lo && rx < hx && ry >= lo && ry < hy;
+}
+__device__ __forceinline__ void klt_filter(const KltFilterArgs& A, unsigned* s_w) {
     const int n1 = klt_compact(A.n0, s_w,
-        [&](int i) {
-            bool ok = A.st[i] == 1;
-            if (A.fb) {
-                const float dx = __fsub_rn(A.back[2 * i], A.prev[2 * i]), dy = __fsub_rn(A.back[2 * i + 1], A.prev[2 * i + 1]);
-                ok = ok && A.bst[i] == 1 && __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= A.thr2;
-            }
-            // rintf: half to even; the comparison in float is lrintf's in int for every finite value, and a NaN fails it
-            const float rx = rintf(A.fwd[2 * i]), ry = rintf(A.fwd[2 * i + 1]);
-            return ok && rx >= lo && rx < hx && ry >= lo && ry < hy;
-        },
+        [&](int i) { return klt_track_ok(A, i); },
         [&](int i, int o) {
             const float x = A.fwd[2 * i], y = A.fwd[2 * i + 1];
             A.out.id[o] = A.id[i]; A.out.age[o] = A.age[i] + 1;
@@ -140,6 +148,7 @@ struct KltAppendArgs {
     unsigned seq;
     int* s_id; int* s_age; float* s_xy;
     int* r_hdr; int* r_id; int* r_age; float* r_xy; float* r_prev;
+    int* n_out;                     // a stereo step: the device's copy of n3 + m (C_NOUT), else null
 };
 __device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
     const int tid = threadIdx.x;
@@ -162,6 +171,7 @@ __device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
         A.r_hdr[0] = A.n0; A.r_hdr[1] = A.cnt[C_N1]; A.r_hdr[2] = A.cnt[C_N2]; A.r_hdr[3] = n3; A.r_hdr[4] = m;
         A.r_hdr[5] = A.f_info ? A.f_info[0] : -1; A.r_hdr[6] = A.f_info ? A.f_info[1] : 0; A.r_hdr[7] = 0;
         A.r_hdr[8] = n3 + m;
+        if (A.n_out) *A.n_out = n3 + m;
     }
     __threadfence_system();
     __syncthreads();
@@ -170,6 +180,43 @@ __device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
 __global__ __launch_bounds__(KT) void k_klt_append(KltAppendArgs A) {
     BACKEND_PRIO();
     klt_append(A);
+}
+
+// Stage 8 (pmv_klt_step_stereo): LK took the list after the append from the current left frame into the right frame (prev = the left
+// positions, which are the state; fwd / back / st / bst = that launch's results, indexed like the list). The rule is stage 2's, with the
+// stereo setting's threshold and border; right xy and status go to the result block for every track of the list, the number of matched
+// tracks to counts8[7], and the stereo completion word (header word 10) is the last store of the chain. on = 0: the tracker has no right
+// frame in this call (a many-call) - only the count, 0, and the word are written.
+struct KltStereoArgs {
+    const int* n;                   // the append's C_NOUT
+    int cap, on, fb, border, w, h;
+    float thr2;
+    const float* prev; const float* fwd; const float* back; const uint8_t* st; const uint8_t* bst;
+    unsigned seq;
+    int* r_hdr; float* r_rxy; uint8_t* r_rst;
+};
+__device__ __forceinline__ void klt_stereo(const KltStereoArgs& A, unsigned* s_w) {
+    int matched = 0;
+    if (A.on) {
+        const int n = klt_clamp(*A.n, A.cap);
+        matched = klt_compact(n, s_w,
+            [&](int i) {   // (called once per track: the outputs of the unmatched tracks are written here too)
+                const bool ok = klt_track_ok(A, i);
+                A.r_rxy[2 * i] = A.fwd[2 * i]; A.r_rxy[2 * i + 1] = A.fwd[2 * i + 1];
+                A.r_rst[i] = ok ? 1 : 0;
+                return ok;
+            },
+            [](int, int) {});
+    }
+    if (threadIdx.x == 0) A.r_hdr[7] = matched;
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store((unsigned*)(A.r_hdr + 10), A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__global__ __launch_bounds__(KT) void k_klt_stereo(KltStereoArgs A) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    klt_stereo(A, s_w);
 }
 
 // ---- pmv_klt_step_many: the same three stages as a grid over the trackers of a group ----------------------------------------------------
@@ -185,6 +232,11 @@ struct KltManyRec {
     const int* f_info;               // (found, drawn) of the tracker's F result block
     unsigned long long prev_off, next_off;   // byte offsets of the tracker's two frame slots
     int lk_base, lk_flags;           // first index of the tracker's share of the launch's LK records and results; LKX_FB or 0
+    // a stereo many-call (stereo.on): stage 8's arguments, the right frame slot, and the tracker's share of stage 8's one LK launch - `cap`
+    // records from st_base on, sized by the bound since the count is the device's
+    KltStereoArgs stereo;
+    unsigned long long right_off;
+    int st_base, st_flags;
 };
 // LK's records for the whole group, written where the tracks are: block lk_base + i tracks state position i of its tracker (geometry entry 0
 // of the call's own one-entry table). The host sized the shares from the n0 it holds; `total` = their sum bounds every store.
@@ -199,6 +251,28 @@ __global__ __launch_bounds__(KT) void k_klt_lk_records(const KltManyRec* __restr
         blocks[base + i] = b;
         ext[base + i] = LKExt{0.f, 0.f, R.lk_flags, 0};
     }
+}
+// Stage 8's records: block st_base + i tracks position i of the tracker's list after the append, from its current left frame into its right
+// frame; the records at and beyond the list's count (C_NOUT) are void. `total` = the sum of the shares bounds every store.
+__global__ __launch_bounds__(KT) void k_klt_stereo_records(const KltManyRec* __restrict__ recs, LKBlock* __restrict__ blocks, LKExt* __restrict__ ext, int total) {
+    BACKEND_PRIO();
+    const KltManyRec& R = recs[blockIdx.x];
+    if (!R.stereo.on) return;
+    const int base = R.st_base, share = klt_clamp(R.stereo.cap, total - base), n = klt_clamp(*R.stereo.n, share);
+    const float* __restrict__ xy = R.stereo.prev;
+    for (int i = threadIdx.x; i < share; i += KT) {
+        LKBlock b;
+        b.prev_off = R.next_off; b.next_off = R.right_off; b.track = base + i; b.geom = 0;
+        b.x = i < n ? xy[2 * i] : 0.f; b.y = i < n ? xy[2 * i + 1] : 0.f;
+        blocks[base + i] = b;
+        ext[base + i] = LKExt{0.f, 0.f, i < n ? R.st_flags : LKX_VOID, 0};
+    }
+}
+__global__ __launch_bounds__(KT) void k_klt_stereo_many(const KltManyRec* __restrict__ recs) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    const KltStereoArgs A = recs[blockIdx.x].stereo;
+    klt_stereo(A, s_w);
 }
 __global__ __launch_bounds__(KT) void k_klt_filter_many(const KltManyRec* __restrict__ recs) {
     __shared__ unsigned s_w[KW];
@@ -263,12 +337,14 @@ KltRecs klt_rec_block(Carve& c, size_t cap) {
     R.fprob = c.take<char>(ESS_HDR, 64); R.ftab = c.take<double>(cap + 2, 16);
     return R;
 }
-// result block (mapped pinned): n1's word | header (counts8, out_n, completion word) | ids | ages | xy | prev xy
-struct KltRes { Carved<int> n1, hdr, id, age; Carved<float> xy, prev; };
+// result block (mapped pinned): n1's word | header (counts8, out_n, completion word, stereo completion word) | ids | ages | xy | prev xy |
+// right xy | right status (the last two are written by stereo steps only)
+struct KltRes { Carved<int> n1, hdr, id, age; Carved<float> xy, prev, right_xy; Carved<uint8_t> right_st; };
 KltRes klt_res_block(Carve& c, size_t cap) {
     KltRes R;
     R.n1 = c.take<int>(16, 64); R.hdr = c.take<int>(16, 64);
     R.id = c.take<int>(cap, 16); R.age = c.take<int>(cap, 16); R.xy = c.take<float>(2 * cap, 16); R.prev = c.take<float>(2 * cap, 16);
+    R.right_xy = c.take<float>(2 * cap, 16); R.right_st = c.take<uint8_t>(cap, 16);
     return R;
 }
 
@@ -279,6 +355,9 @@ struct KltTracker {
     int cap = 0, n = 0, next_id = 0;
     unsigned seq = 0;
     float thr2 = 0.f;
+    bool st_on = false;             // pmv_klt_set_stereo: the setting of stage 8 and its thr2
+    pmv_klt_stereo_params st{};
+    float st_thr2 = 0.f;
     Buf<uint8_t> d_mem, d_rec, h_rec{MEM_PINNED}, h_res{MEM_MAPPED};
     KltDev D; KltRecs R; KltRes O;
 };
@@ -447,13 +526,19 @@ int pmv_klt_get_tracks(pmv_ctx* ctx, int id, int* ids, int* ages, float* xy, int
     return PMV_OK;
 }
 
-int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, int out_cap, int* out_n,
-                 int* out_counts8) {
+}  // extern "C"
+
+// pmv_klt_step and, with `right`, pmv_klt_step_stereo: the same chain, refused in the same words; the stereo form appends stage 8
+struct KltRightOut { int slot; float* xy; uint8_t* st; };
+static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, int out_cap, int* out_n,
+                        int* out_counts8, const KltRightOut* right) {
     REQ(ctx, PMV_ERR_INVALID, "pmv_klt_step: null argument");
     KltTracker* t;
     if (const int rc = klt_find(ctx, "pmv_klt_step", id, &t)) return rc;
     REQ(out_ids && out_ages && out_xy && out_n && out_counts8, PMV_ERR_INVALID, "pmv_klt_step: null argument");
+    REQ(!right || (right->xy && right->st), PMV_ERR_INVALID, "pmv_klt_step_stereo: null argument");
     REQ(out_cap >= t->cap, PMV_ERR_CAPACITY, "pmv_klt_step: out_cap = %d is below the tracker's target %d", out_cap, t->cap);
+    REQ(!right || t->st_on, PMV_ERR_INVALID, "pmv_klt_step_stereo: tracker %d has no stereo setting (pmv_klt_set_stereo)", id);
     const pmv_klt_params& p = t->p;
     const int n0 = t->n, cap = t->cap;
     const bool fb = p.fb_max_dist >= 0.0;
@@ -462,6 +547,9 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
         if (const int rc = lk_check(ctx, true, prev_slot, cur_slot, out_xy, n0, out_xy, (const uint8_t*)out_ids, out_xy)) return rc;
     int roi[4], gcap;
     if (const int rc = gftt_frame_check(ctx, "pmv_klt_step", true, cur_slot, nullptr, cap, &p.gftt, nullptr, 0, out_ids, cap, out_n, roi, &gcap)) return rc;
+    // stage 8's LK pair, before anything is launched: the length of the list it tracks is known only on the device
+    if (right)
+        if (const int rc = lk_check(ctx, true, cur_slot, right->slot, nullptr, 0, nullptr, nullptr, nullptr)) return rc;
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
     const PyrLayout& L = ctx->slot_layout[cur_slot];
@@ -560,31 +648,87 @@ int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids
     }
     // 7. append
     if (++t->seq == 0) t->seq = 1;
-    O.hdr.h[9] = 0;
+    O.hdr.h[9] = 0; O.hdr.h[10] = 0;
     {
         KltAppendArgs A{lst[cur], D.cnt.d, D.cnt.d + C_M, D.ixy.d, p.subpix ? D.sp_xy.d : nullptr, f_ran ? (const int*)(D.f_out.d + ESS_OUT_INFO) : nullptr, n0, t->next_id, cap, t->seq,
-                        D.s_id.d, D.s_age.d, D.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d};
+                        D.s_id.d, D.s_age.d, D.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d, right ? D.cnt.d + C_NOUT : nullptr};
         ProfScope ps(K_GFTT_PICK, s);
         hipLaunchKernelGGL(k_klt_append, dim3(1), dim3(KT), 0, s, A);
         CKC(hipGetLastError());
         launches++;
+    }
+    // 8. stereo: the new state from the current left frame into the right frame - `cap` workgroups, of which the device's count work (the LK
+    // result arrays of stage 1 are free again) - then the rule, which ends the chain with its own completion word
+    if (right) {
+        const bool sfb = t->st.fb_max_dist >= 0.0;
+        CKC(launch_lk_ex_dev(s, ctx->d_slots + (size_t)cur_slot * L.slot_bytes, ctx->d_slots + (size_t)right->slot * L.slot_bytes, L, D.s_xy.d, D.cnt.d + C_NOUT, cap,
+                             sfb ? LKX_FB : 0, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
+        KltStereoArgs A{D.cnt.d + C_NOUT, cap, 1, sfb ? 1 : 0, t->st.border, L.w[0], L.h[0], t->st_thr2, D.s_xy.d, D.lk_xy.d, D.bk_xy.d, D.lk_st.d, D.bk_st.d, t->seq,
+                        O.hdr.d, O.right_xy.d, O.right_st.d};
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_stereo, dim3(1), dim3(KT), 0, s, A);
+        CKC(hipGetLastError());
+        launches += 2;
     }
     CKC(hipStreamSynchronize(s));
     waits++;
     const int* hdr = O.hdr.h;
     const int n = hdr[8], m = hdr[4];
     REQ((unsigned)hdr[9] == t->seq && n >= 0 && n <= cap && m >= 0 && m <= n, PMV_ERR_HIP, "pmv_klt_step: the result block is incomplete (n = %d, m = %d)", n, m);
+    REQ(!right || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= n), PMV_ERR_HIP, "pmv_klt_step_stereo: the result block is incomplete (n = %d, matched = %d)", n, hdr[7]);
     memcpy(out_ids, O.id.h, (size_t)n * 4);
     memcpy(out_ages, O.age.h, (size_t)n * 4);
     memcpy(out_xy, O.xy.h, (size_t)n * 8);
     if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null, O.prev.h, (size_t)n * 8);
     memcpy(out_counts8, hdr, 8 * sizeof(int));
     *out_n = n;
+    if (right) {
+        memcpy(right->xy, O.right_xy.h, (size_t)n * 8);
+        memcpy(right->st, O.right_st.h, (size_t)n);
+    }
     t->n = n; t->next_id += m;
     ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask is this step's now)
-    ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches;
+    if (right) { ctx->klt_stereo_stats[0]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
+    else { ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches; }
     return PMV_OK;
 }
+
+extern "C" {
+
+int pmv_klt_step(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, int out_cap, int* out_n,
+                 int* out_counts8) {
+    return klt_step_run(ctx, id, prev_slot, cur_slot, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_cap, out_n, out_counts8, nullptr);
+}
+
+int pmv_klt_step_stereo(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int right_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null,
+                        float* out_right_xy, uint8_t* out_right_status, int out_cap, int* out_n, int* out_counts8) {
+    const KltRightOut right{right_slot, out_right_xy, out_right_status};
+    return klt_step_run(ctx, id, prev_slot, cur_slot, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_cap, out_n, out_counts8, &right);
+}
+
+int pmv_klt_set_stereo(pmv_ctx* ctx, int id, const pmv_klt_stereo_params* p_or_null) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_set_stereo: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_set_stereo", id, &t)) return rc;
+    if (!p_or_null) { t->st_on = false; return PMV_OK; }
+    const pmv_klt_stereo_params& p = *p_or_null;
+    REQ(std::isfinite(p.fb_max_dist) && p.fb_max_dist <= 1e3, PMV_ERR_INVALID, "pmv_klt_set_stereo: fb_max_dist = %g is not finite or above 1e3", p.fb_max_dist);
+    REQ(p.border >= 0 && p.border <= 64, PMV_ERR_INVALID, "pmv_klt_set_stereo: border = %d is outside 0..64", p.border);
+    t->st = p; t->st_on = true;
+    t->st_thr2 = p.fb_max_dist >= 0.0 ? (float)(p.fb_max_dist * p.fb_max_dist) : 0.f;
+    return PMV_OK;
+}
+
+int pmv_klt_get_stereo(pmv_ctx* ctx, int id, pmv_klt_stereo_params* out, int* out_on) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_get_stereo: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_get_stereo", id, &t)) return rc;
+    REQ(out && out_on, PMV_ERR_INVALID, "pmv_klt_get_stereo: null argument");
+    *out = t->st; *out_on = t->st_on ? 1 : 0;
+    return PMV_OK;
+}
+
+}  // extern "C"
 
 // a check of a single call failed for tracker j of a group: its message, with the tracker named behind it
 static int klt_many_blame(pmv_ctx* ctx, int rc, int j, int id) {
@@ -594,13 +738,16 @@ static int klt_many_blame(pmv_ctx* ctx, int rc, int j, int id) {
     return rc;
 }
 
-int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, int* out_ids, int* out_ages, float* out_xy,
-                      float* out_prev_xy_or_null, int out_stride, int* out_n, int* out_counts8) {
+// pmv_klt_step_many and, with `right`, pmv_klt_step_many_stereo (right->slots[j] < 0: tracker j has no right frame in this call)
+struct KltRightManyOut { const int* slots; float* xy; uint8_t* st; };
+static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, int* out_ids, int* out_ages, float* out_xy,
+                             float* out_prev_xy_or_null, int out_stride, int* out_n, int* out_counts8, const KltRightManyOut* right) {
     const char* who = "pmv_klt_step_many";
     REQ(ctx, PMV_ERR_INVALID, "pmv_klt_step_many: null argument");
     REQ(n_trk >= 1, PMV_ERR_INVALID, "%s: n_trk = %d is below 1", who, n_trk);
     REQ(n_trk <= PMV_KLT_MAX_TRACKERS, PMV_ERR_CAPACITY, "%s: n_trk = %d is above %d (PMV_KLT_MAX_TRACKERS)", who, n_trk, PMV_KLT_MAX_TRACKERS);
     REQ(ids && prev_slots && cur_slots && out_ids && out_ages && out_xy && out_n && out_counts8, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(!right || (right->slots && right->xy && right->st), PMV_ERR_INVALID, "pmv_klt_step_many_stereo: null argument");
     KltTracker* T[PMV_KLT_MAX_TRACKERS];
     int cap_max = 0;
     for (int j = 0; j < n_trk; j++) {
@@ -638,6 +785,17 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
             j, ids[j], r[2], r[3], roi[2], roi[3]);
         sum_cap += t->cap; sum_n0 += t->n; sum_pad += refill_pad(t->cap);
         any_f = any_f || (t->p.reject_f && t->n >= 15);
+    }
+    // stage 8's LK pairs, before anything is launched: the lengths of the lists it tracks are known only on the device
+    int sum_st = 0;
+    for (int j = 0; right && j < n_trk; j++) {
+        if (right->slots[j] < 0) continue;
+        if (!T[j]->st_on) {
+            set_err(ctx, "pmv_klt_step_many_stereo: tracker %d has no stereo setting (pmv_klt_set_stereo)", ids[j]);
+            return klt_many_blame(ctx, PMV_ERR_INVALID, j, ids[j]);
+        }
+        if (const int rc = lk_check(ctx, true, cur_slots[j], right->slots[j], nullptr, 0, nullptr, nullptr, nullptr)) return klt_many_blame(ctx, rc, j, ids[j]);
+        sum_st += T[j]->cap;
     }
     tl_prof = &ctx->prof;
     CKC(hipSetDevice(ctx->device));
@@ -680,7 +838,7 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
     // records: per tracker its arguments, its refill request (n is written by the kernels) and its frame request; the geometry entry
     const unsigned long long pitch = ctx->cap.slot_bytes;
     *R.geom.h = L;
-    size_t lk_base = 0, pad_off = 0;
+    size_t lk_base = 0, pad_off = 0, st_base = 0;
     for (int j = 0; j < n_trk; j++) {
         KltTracker* t = T[j];
         const pmv_klt_params& q = t->p;
@@ -694,7 +852,7 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
         g[5] = (int)(unsigned)((size_t)j * mstride);
         R.slots.h[j] = cur_slots[j];
         if (++t->seq == 0) t->seq = 1;
-        O.hdr.h[9] = 0;
+        O.hdr.h[9] = 0; O.hdr.h[10] = 0;
         KltManyRec& M = R.rec.h[j];
         memset(&M, 0, sizeof(M));
         const KltRefillIn rf{D.pos.d + pad_off, D.prio.d + pad_off, D.flag.d + pad_off, R.rrec.d + j};
@@ -704,11 +862,19 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
         M.by_f = KltCompactArgs{M.lst[0], M.lst[1], (const uint8_t*)(TD.f_out.d + ESS_OUT_HDR), TD.cnt.d + C_N1, cap, C_N2, 0, rf, TD.cnt.d, D.want.d + j};
         M.by_keep = KltCompactArgs{M.lst[0], M.lst[1], D.keep.d + pad_off, TD.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, TD.cnt.d, D.want.d + j};
         M.append = KltAppendArgs{M.lst[0], TD.cnt.d, D.m.d + j, D.ixy.d + (size_t)2 * j * cap_max, q.subpix ? D.sp_xy.d + (size_t)2 * j * cap_max : nullptr, nullptr, n0, t->next_id, cap,
-                                 t->seq, TD.s_id.d, TD.s_age.d, TD.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d};
+                                 t->seq, TD.s_id.d, TD.s_age.d, TD.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d, right ? TD.cnt.d + C_NOUT : nullptr};
         M.f_info = (const int*)(TD.f_out.d + ESS_OUT_INFO);
         M.prev_off = (unsigned long long)(n0 > 0 ? prev_slots[j] : cur_slots[j]) * pitch; M.next_off = (unsigned long long)cur_slots[j] * pitch;
         M.lk_base = (int)lk_base; M.lk_flags = fb ? LKX_FB : 0;
         lk_base += (size_t)n0; pad_off += refill_pad(cap);
+        if (right) {   // stage 8: the tracker's share of the bound-sized launch; the LK result arrays of stage 1 are free again by then
+            const bool on = right->slots[j] >= 0, sfb = on && t->st.fb_max_dist >= 0.0;
+            M.stereo = KltStereoArgs{TD.cnt.d + C_NOUT, cap, on ? 1 : 0, sfb ? 1 : 0, t->st.border, L.w[0], L.h[0], t->st_thr2, TD.s_xy.d, D.lk_xy.d + 2 * st_base,
+                                     D.bk_xy.d + 2 * st_base, D.lk_st.d + st_base, D.bk_st.d + st_base, t->seq, O.hdr.d, O.right_xy.d, O.right_st.d};
+            M.right_off = (unsigned long long)(on ? right->slots[j] : cur_slots[j]) * pitch;
+            M.st_base = (int)st_base; M.st_flags = sfb ? LKX_FB : 0;
+            if (on) st_base += (size_t)cap;
+        }
     }
     CKC(hipMemcpyAsync(G->d_rec, G->h_rec, R.front, hipMemcpyHostToDevice, s));
     // 1. track: the records are written on the device, where the positions are, and the whole group is one launch
@@ -791,6 +957,24 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
         CKC(hipGetLastError());
         launches++;
     }
+    // 8. stereo: the records of every share from the lists and counts the append left, one LK launch over the sum of the bounds (a record
+    // beyond its list's count is void), then the rule; every workgroup of it stores its tracker's stereo completion word last
+    if (right) {
+        if (sum_st > 0) {
+            {
+                ProfScope ps(K_GFTT_PICK, s);
+                hipLaunchKernelGGL(k_klt_stereo_records, dim3(n_trk), dim3(KT), 0, s, R.rec.d, D.lkb.d, D.lkx.d, sum_st);
+                CKC(hipGetLastError());
+            }
+            CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx.d, sum_st, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
+                                   D.bk_err.d));
+            launches += 2;
+        }
+        ProfScope ps(K_GFTT_PICK, s);
+        hipLaunchKernelGGL(k_klt_stereo_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d);
+        CKC(hipGetLastError());
+        launches++;
+    }
     CKC(hipStreamSynchronize(s));
     waits++;
     for (int j = 0; j < n_trk; j++) {
@@ -799,6 +983,8 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
         const int nn = hdr[8], m = hdr[4];
         REQ((unsigned)hdr[9] == t->seq && nn >= 0 && nn <= t->cap && m >= 0 && m <= nn, PMV_ERR_HIP, "%s: the result block of tracker %d of the group is incomplete (n = %d, m = %d)",
             who, j, nn, m);
+        REQ(!right || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= nn), PMV_ERR_HIP,
+            "pmv_klt_step_many_stereo: the result block of tracker %d of the group is incomplete (n = %d, matched = %d)", j, nn, hdr[7]);
     }
     for (int j = 0; j < n_trk; j++) {
         KltTracker* t = T[j];
@@ -812,10 +998,36 @@ int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_s
         if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null + 2 * o, O.prev.h, (size_t)nn * 8);
         memcpy(out_counts8 + 8 * j, hdr, 8 * sizeof(int));
         out_n[j] = nn;
+        if (right) {
+            if (right->slots[j] >= 0) {
+                memcpy(right->xy + 2 * o, O.right_xy.h, (size_t)nn * 8);
+                memcpy(right->st + o, O.right_st.h, (size_t)nn);
+            } else memset(right->st + o, 0, (size_t)nn);
+        }
         t->n = nn; t->next_id += m;
     }
     ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask at the front is tracker 0's)
-    ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches;
+    if (right) { ctx->klt_stereo_stats[1]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
+    else { ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches; }
+    return PMV_OK;
+}
+
+extern "C" {
+
+int pmv_klt_step_many(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, int* out_ids, int* out_ages, float* out_xy,
+                      float* out_prev_xy_or_null, int out_stride, int* out_n, int* out_counts8) {
+    return klt_step_many_run(ctx, n_trk, ids, prev_slots, cur_slots, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_stride, out_n, out_counts8, nullptr);
+}
+
+int pmv_klt_step_many_stereo(pmv_ctx* ctx, int n_trk, const int* ids, const int* prev_slots, const int* cur_slots, const int* right_slots, int* out_ids, int* out_ages,
+                             float* out_xy, float* out_prev_xy_or_null, float* out_right_xy, uint8_t* out_right_status, int out_stride, int* out_n, int* out_counts8) {
+    const KltRightManyOut right{right_slots, out_right_xy, out_right_status};
+    return klt_step_many_run(ctx, n_trk, ids, prev_slots, cur_slots, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_stride, out_n, out_counts8, &right);
+}
+
+int pmv_debug_klt_stereo_stats(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_klt_stereo_stats: null argument");
+    for (int i = 0; i < 4; i++) out4[i] = ctx->klt_stereo_stats[i].load();
     return PMV_OK;
 }
 

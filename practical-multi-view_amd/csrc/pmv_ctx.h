@@ -147,6 +147,9 @@ struct pmv_ctx {
     // waits inside them | kernel launches inside them
     pmv::KltGroup* klt_group = nullptr;
     std::atomic<long long> klt_many_stats[4];
+    // pmv_debug_klt_stereo_stats: stereo steps | stereo many-calls | host waits inside both | kernel launches inside both (the counters above
+    // do not move for stereo calls)
+    std::atomic<long long> klt_stereo_stats[4];
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;

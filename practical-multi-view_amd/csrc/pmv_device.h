@@ -168,7 +168,9 @@ static_assert(sizeof(LKBlock) == 32, "LKBlock: one 32-byte record per workgroup"
 // The extended calls (pmv_lk_track_ex / _fb): the two cv flag values, and the forward-backward mode as an internal third bit. A workgroup of
 // the extended batch kernels reads, next to its LKBlock, the record of the same index in a second array: LKBlock keeps its 32 bytes and
 // k_lk_batch its records. An LKX_FB record's back results go to index `track` of the launch's three back arrays.
-constexpr int LKX_INIT = 4, LKX_EIG = 8, LKX_FB = 0x100;
+// LKX_VOID (k_lk_batch_ex only): the record is beyond its list's count, which only the device knew when the launch was sized - its
+// workgroup leaves without a load from the frames or a store. Set by k_klt_stereo_records alone.
+constexpr int LKX_INIT = 4, LKX_EIG = 8, LKX_FB = 0x100, LKX_VOID = 0x200;
 struct __attribute__((aligned(16))) LKExt {
     float ix, iy;      // where the top level's search starts (level-0 coordinates), read with LKX_INIT
     int flags;         // LKX_*
@@ -212,6 +214,10 @@ hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* nex
 hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const float* d_init_xy,
                         const int* d_order, int n_blocks, int n, int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work,
                         float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
+// The same launch sized by a bound: n_cap workgroups, of which those below *d_n (device memory, read by every workgroup) track d_prev_xy[i] in
+// identity order; flags: LKX_FB or 0. The count never reaches the host.
+hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const int* d_n, int n_cap,
+                            int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
 // d_work (optional), per track: LK iterations executed over all levels | (level passes that iterated) << 8 - what the track cost. The
 // roofline's OPS_lk is summed from these on the host (three atomics per track on shared counters cost the batched launch 14 % of the
 // whole run's throughput: every wavefront of the chip ended on the same three L2 lines).
