@@ -927,6 +927,7 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
                 lk.unlock();
                 std::this_thread::sleep_for(std::chrono::microseconds(E->linger_us));
                 lk.lock();
+                if (Q->pending.empty()) { if (Q->stop) return; continue; }   // another lane of the class lingered too and took them: no empty round
             }
             batch.swap(Q->pending);
             if (role == R_LK) take_what_fits(Q, batch, E->cap_tracks, [](Req* r) { return r->kind == Q_KNN ? (size_t)((KnnReq*)r)->n : (size_t)((LKReq*)r)->n; });
