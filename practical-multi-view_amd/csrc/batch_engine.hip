@@ -133,13 +133,9 @@ struct Combiner {
     // masks of the extended GFTT requests of a round (detector combiner, made by the first round that has one): the cells' mask sub-views
     // packed one after the other, pinned mirror and HBM copy
     HScratch h_gmask; DScratch d_gmask;
-    // whole-frame GFTT requests of a round (detector combiner, made by the first round that has one, grown to the largest round seen): the
-    // groups' blocks (gftt_frame_block) in mapped pinned memory, the regions' packed masks, and in HBM the record lists, the key lists of the
-    // selection's slower path (one entry per pixel of the round's regions) and the (maximum, count) pairs
-    HScratch h_gfr, h_gfr_mask; DScratch d_gfr_mask, d_gfr_val, d_gfr_idx, d_gfr_keys, d_gfr_info;
-    // refill requests of a round (detector combiner, made by the first round that has one): the round's refill_block in mapped pinned
-    // memory, the kept lists and their counts in HBM
-    HScratch h_refill; DScratch d_refill_kept, d_refill_nkept;
+    // whole-frame GFTT and refill requests of a round (detector combiner, made by the first round that has one, grown to the largest round
+    // seen): the groups' blocks one after the other, one list entry per pixel of the round's regions
+    FrameDetScratch fds{GROW_SLACK, MEM_MAPPED};
     // corner sub-pixel requests of a round (detector combiner, made by the first round that has one): [point records | positions | updates |
     // flags] in one mapped pinned block; the weight tables of the round's parameter groups, pinned mirror and HBM copy
     HScratch h_spx, h_spx_tab; DScratch d_spx_tab;
@@ -439,63 +435,58 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
 // ---- detectors --------------------------------------------------------------------------------------------------------------------
 // result block of a round's detector launches, written by the kernels through the mapped alias: [xy | score | count | overflow flags]
 struct DetBlock { Carved<int> xy; Carved<double> score; Carved<int> count, flags; };
-DetBlock det_block(const Combiner& C, size_t tot_out, size_t tot_cells) {
-    Carve c = carve_of(C.h_det);
-    return {c.take<int>(2 * tot_out), c.take<double>(tot_out), c.take<int>(tot_cells), c.take<int>(1)};
-}
-void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    pmv_ctx* ctx = E->ctx;
-    hipStream_t s = C.s;
-    std::vector<DetReq*> det;
-    std::vector<SubpixReq*> spx;   // (corner sub-pixel requests: the same role, the same round, one more launch per parameter set)
-    std::vector<DetReq*> fr;       // (whole-frame GFTT requests: one more launch pair per parameter set)
-    for (Req* r : batch) { if (r->kind == Q_SUBPIX) spx.push_back((SubpixReq*)r); else if (r->kind == Q_GFTT_FRAME) fr.push_back((DetReq*)r); else det.push_back((DetReq*)r); }
-    // ---- detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
-    // geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
-    // FAST (grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
-    // its score maps are sized by the pixels of the round (d_fast_score), the cell record's offset into them stays within int.
-    // Extended GFTT requests (ext) also agree in block size, response kind, k and has-mask; a round without one launches what it always did.
+// The detector role serves three request families in one round: they share the stream and the round's one wait, nothing else. Each family
+// forms its groups, sizes its scratch and enqueues its launches (enqueue: false after a failed runtime call, which has failed the whole
+// batch - EKF), keeps what it carved, and scatters its results after the wait (collect). A family without a request adds nothing.
+#define EKF(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail_all(batch, PMV_ERR_HIP, #x, e_); return false; } } while (0)
+
+// ---- cell detectors: requests with the same parameters AND the same frame geometry share a launch (cells of several frames); the
+// geometry is the one actually staged in each request's slot (KITTI 00-02, 03 and 04-10 have three different sizes)
+// FAST (grouped by threshold, non-max flag and max_per_cell) keeps a score byte per pixel of its cells, which may be whole frames:
+// its score maps are sized by the pixels of the round (d_fast_score), the cell record's offset into them stays within int.
+// Extended GFTT requests (ext) also agree in block size, response kind, k and has-mask; a round without one launches what it always did.
+struct DetCells {
     struct Group { int kind, max_per_cell, unlimited; double quality, min_dist; PyrLayout L; std::vector<DetReq*> reqs; int n_cells = 0; size_t out_off = 0; int max_pix = 0;
                    int ext = 0, block_size = 3, use_harris = 0; double k = 0.0; bool has_mask = false; };
-    std::vector<Group> groups;
-    size_t fast_pix = 0, mask_bytes = 0;
-    for (DetReq* r : det) {
-        if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
-        const PyrLayout& Lr = ctx->slot_layout[r->slot];
-        if (r->kind == Q_FAST) {
-            size_t pix = 0;
-            for (int i = 0; i < r->n_cells; i++) pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
-            if (fast_pix + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch FAST: the cells of the round cover more than 2^31 pixels"); continue; }
-            fast_pix += pix;
+    std::vector<DetReq*> reqs; std::vector<Group> groups;
+    DetBlock D{};
+    bool enqueue(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+        pmv_ctx* ctx = E->ctx; hipStream_t s = C.s;
+        size_t fast_pix = 0, mask_bytes = 0;
+        for (DetReq* r : reqs) {
+            if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
+            const PyrLayout& Lr = ctx->slot_layout[r->slot];
+            if (r->kind == Q_FAST) {
+                size_t pix = 0;
+                for (int i = 0; i < r->n_cells; i++) pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
+                if (fast_pix + pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch FAST: the cells of the round cover more than 2^31 pixels"); continue; }
+                fast_pix += pix;
+            }
+            size_t mask_pix = 0;
+            if (r->mask) for (int i = 0; i < r->n_cells; i++) mask_pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
+            if (mask_bytes + mask_pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
+            mask_bytes += mask_pix;
+            Group* g = nullptr;
+            for (Group& x : groups)
+                if (x.kind == r->kind && x.max_per_cell == r->max_per_cell && x.unlimited == r->unlimited && x.quality == r->quality && x.min_dist == r->min_dist &&
+                    x.ext == r->ext && (!r->ext || (x.block_size == r->block_size && x.use_harris == r->use_harris && x.k == r->k && x.has_mask == (r->mask != nullptr))) &&
+                    x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
+            if (!g) {
+                groups.push_back(Group{r->kind, r->max_per_cell, r->unlimited, r->quality, r->min_dist, Lr, {}, 0, 0});
+                g = &groups.back();
+                if (r->ext) { g->ext = 1; g->block_size = r->block_size; g->use_harris = r->use_harris; g->k = r->k; g->has_mask = r->mask != nullptr; }
+            }
+            r->cell_base = g->n_cells; g->n_cells += r->n_cells; g->reqs.push_back(r);
         }
-        size_t mask_pix = 0;
-        if (r->mask) for (int i = 0; i < r->n_cells; i++) mask_pix += (size_t)r->cells[4 * i + 2] * r->cells[4 * i + 3];
-        if (mask_bytes + mask_pix > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
-        mask_bytes += mask_pix;
-        Group* g = nullptr;
-        for (Group& x : groups)
-            if (x.kind == r->kind && x.max_per_cell == r->max_per_cell && x.unlimited == r->unlimited && x.quality == r->quality && x.min_dist == r->min_dist &&
-                x.ext == r->ext && (!r->ext || (x.block_size == r->block_size && x.use_harris == r->use_harris && x.k == r->k && x.has_mask == (r->mask != nullptr))) &&
-                x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
-        if (!g) {
-            groups.push_back(Group{r->kind, r->max_per_cell, r->unlimited, r->quality, r->min_dist, Lr, {}, 0, 0});
-            g = &groups.back();
-            if (r->ext) { g->ext = 1; g->block_size = r->block_size; g->use_harris = r->use_harris; g->k = r->k; g->has_mask = r->mask != nullptr; }
-        }
-        r->cell_base = g->n_cells;
-        g->n_cells += r->n_cells;
-        g->reqs.push_back(r);
-    }
-    size_t tot_cells = 0, tot_out = 0;
-    for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; }
-    if (!det.empty()) {   // (a round of sub-pixel requests alone has no detector launch)
+        if (reqs.empty()) return true;   // (a round of frame or sub-pixel requests alone has no cell launch)
+        size_t tot_cells = 0, tot_out = 0;
         size_t eig_cells = 0;   // cells of the GFTT / ShiTomasi groups: the response, cell-maximum and spill areas are theirs alone
-        for (Group& g : groups) if (g.kind != Q_FAST) eig_cells += g.n_cells;
+        for (Group& g : groups) { g.out_off = tot_out; tot_cells += g.n_cells; tot_out += (size_t)g.n_cells * g.max_per_cell; if (g.kind != Q_FAST) eig_cells += g.n_cells; }
         const size_t cells_bytes = tot_cells * CELL_STRIDE * 4;
-        EK(C.h_cells.ensure(cells_bytes + 64));   // (+ the stage-in job of a round with FAST cells)
-        EK(C.d_eig.ensure(eig_cells * CELL_PIX * sizeof(double))); EK(C.d_cellmax.ensure(eig_cells * 8)); EK(C.d_spill.ensure(eig_cells * CELL_PIX * 4));
-        EK(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // (det_block)
-        if (mask_bytes) { EK(C.h_gmask.ensure(mask_bytes + 64)); EK(C.d_gmask.ensure(mask_bytes + 64)); }
+        EKF(C.h_cells.ensure(cells_bytes + 64));   // (+ the stage-in job of a round with FAST cells)
+        EKF(C.d_eig.ensure(eig_cells * CELL_PIX * sizeof(double))); EKF(C.d_cellmax.ensure(eig_cells * 8)); EKF(C.d_spill.ensure(eig_cells * CELL_PIX * 4));
+        EKF(C.h_det.ensure(tot_out * 16 + tot_cells * 4 + 64));   // (det_block)
+        if (mask_bytes) { EKF(C.h_gmask.ensure(mask_bytes + 64)); EKF(C.d_gmask.ensure(mask_bytes + 64)); }
         int* hc = (int*)C.h_cells.p;
         size_t cpos = 0, fpos = 0, mpos = 0;
         for (Group& g : groups)
@@ -508,114 +499,130 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                     for (int* d = recs; d < recs + (size_t)r->n_cells * CELL_STRIDE; d += CELL_STRIDE) { d[5] = (int)fpos; fpos += (size_t)d[2] * d[3]; g.max_pix = std::max(g.max_pix, d[2] * d[3]); }
                 cpos += (size_t)r->n_cells;
             }
-        if (mask_bytes) EK(hipMemcpyAsync(C.d_gmask.p, C.h_gmask.p, mask_bytes, hipMemcpyHostToDevice, s));
+        if (mask_bytes) EKF(hipMemcpyAsync(C.d_gmask.p, C.h_gmask.p, mask_bytes, hipMemcpyHostToDevice, s));
         if (fast_pix > 0) {
             // every thread of k_fast_score reads its cell record: the records of the round go to HBM by one gather (no DMA call)
-            EK(C.d_cells.ensure(cells_bytes + 64)); EK(C.d_fast_score.ensure(fast_pix + 64));
+            EKF(C.d_cells.ensure(cells_bytes + 64)); EKF(C.d_fast_score.ensure(fast_pix + 64));
             StageJob* job = (StageJob*)((char*)C.h_cells.p + ((cells_bytes + 15) & ~(size_t)15));
             *job = StageJob{C.h_cells.dev, (char*)C.d_cells.p, (unsigned)cells_bytes, 0};
             hipLaunchKernelGGL(k_stage_in, dim3(1, 1), dim3(256), 0, s, (const StageJob*)(C.h_cells.dev + ((cells_bytes + 15) & ~(size_t)15)));
-            EK(hipGetLastError());
+            EKF(hipGetLastError());
         }
-        EK(hipMemsetAsync(C.d_flags, 0, 16, s));
-        {
-            int need_ring = -1;
-            for (DetReq* r : det) if (r->rc == PMV_OK) need_ring = std::max(need_ring, r->ring_round);
-            if (need_ring >= 0) EK(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
-        }
+        EKF(hipMemsetAsync(C.d_flags, 0, 16, s));
+        int need_ring = -1;
+        for (DetReq* r : reqs) if (r->rc == PMV_OK) need_ring = std::max(need_ring, r->ring_round);
+        if (need_ring >= 0) EKF(batch_ingest_wait_gpu(ctx->bingest, s, need_ring));
         size_t c0 = 0, e0 = 0;   // first cell of the group among all cells of the round / among those with a response area (c0 = e0 in a round without FAST)
-        const DetBlock D = det_block(C, tot_out, tot_cells);
+        Carve c = carve_of(C.h_det);
+        D = DetBlock{c.take<int>(2 * tot_out), c.take<double>(tot_out), c.take<int>(tot_cells), c.take<int>(1)};
         for (Group& g : groups) {
             const int* dc = (const int*)C.h_cells.dev + c0 * CELL_STRIDE;
             int* dxy = D.xy.d + g.out_off * 2;
             double* dsc = D.score.d + g.out_off;
             int* dcnt = D.count.d + c0;
             if (g.kind == Q_GFTT && g.ext)
-                EK(launch_gftt_ex(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, gftt_ext(g.block_size, g.use_harris, g.k),
-                                  g.has_mask ? (const uint8_t*)C.d_gmask.p : nullptr, (float*)C.d_eig.p + e0 * CELL_PIX, (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt,
-                                  C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+                EKF(launch_gftt_ex(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, gftt_ext(g.block_size, g.use_harris, g.k),
+                                   g.has_mask ? (const uint8_t*)C.d_gmask.p : nullptr, (float*)C.d_eig.p + e0 * CELL_PIX, (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt,
+                                   C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
             else if (g.kind == Q_GFTT)
-                EK(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + e0 * CELL_PIX,
-                               (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+                EKF(launch_gftt(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, g.min_dist, g.unlimited, (float*)C.d_eig.p + e0 * CELL_PIX,
+                                (unsigned*)C.d_cellmax.p + 2 * e0, dxy, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
             else if (g.kind == Q_SHITOMASI)
-                EK(launch_shitomasi(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, (double*)C.d_eig.p + e0 * CELL_PIX,
-                                    (unsigned long long*)C.d_cellmax.p + e0, dxy, dsc, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
+                EKF(launch_shitomasi(s, ctx->d_slots, g.L, dc, g.n_cells, g.max_per_cell, g.quality, (double*)C.d_eig.p + e0 * CELL_PIX,
+                                     (unsigned long long*)C.d_cellmax.p + e0, dxy, dsc, dcnt, C.d_flags, (unsigned*)C.d_spill.p + e0 * CELL_PIX));
             else   // FAST: records from HBM, float responses in the group's share of the score block
-                EK(launch_fast(s, ctx->d_slots, g.L, (const int*)C.d_cells.p + c0 * CELL_STRIDE, g.n_cells, g.max_pix, g.max_per_cell, (int)g.quality, (int)g.min_dist,
-                               (uint8_t*)C.d_fast_score.p, dxy, (float*)dsc, dcnt));
+                EKF(launch_fast(s, ctx->d_slots, g.L, (const int*)C.d_cells.p + c0 * CELL_STRIDE, g.n_cells, g.max_pix, g.max_per_cell, (int)g.quality, (int)g.min_dist,
+                                (uint8_t*)C.d_fast_score.p, dxy, (float*)dsc, dcnt));
             c0 += g.n_cells;
             if (g.kind != Q_FAST) e0 += g.n_cells;
         }
-        EK(hipMemcpyAsync(D.flags.h, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
+        EKF(hipMemcpyAsync(D.flags.h, C.d_flags, 4, hipMemcpyDeviceToHost, s));   // (the kernels set the bits with atomics: device memory)
+        return true;
     }
-    // ---- whole-frame GFTT: requests that agree in every argument but the slot, the region and the mask's bytes, on frames of one layout,
-    // share ONE pass-1 and ONE pass-2 launch (launch_gftt_frame). A round without such a request adds nothing here.
-    struct FGroup { DetReq* key; PyrLayout L; std::vector<DetReq*> reqs; int grid_x = 0; size_t info_base = 0; GfttFrameBlock B{}; };
-    std::vector<FGroup> fgroups;
-    size_t f_pix = 0, f_mask = 0, f_n = 0;
-    // refill requests: their number, their track entries, the bytes of the regions that are painted from 255 (they lie behind the uploaded
-    // masks and are not copied), the largest region
-    size_t rf_n = 0, rf_trk = 0, rf_plain = 0, rf_max = 0;
-    for (DetReq* r : fr) {
-        if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
-        const PyrLayout& Lr = ctx->slot_layout[r->slot];
-        if (r->roi[0] + r->roi[2] > Lr.w[0] || r->roi[1] + r->roi[3] > Lr.h[0]) {   // (the slot was re-used since the call's check)
-            r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch GFTT: region (%d,%d,%d,%d) is not inside the %dx%d frame", r->roi[0], r->roi[1], r->roi[2], r->roi[3], Lr.w[0], Lr.h[0]);
-            continue;
+    void collect() {
+        if (reqs.empty()) return;
+        const int flags = *D.flags.h;
+        size_t c0 = 0;
+        for (Group& g : groups) {
+            for (DetReq* r : g.reqs) {
+                if (g.kind == Q_GFTT && (flags & 4)) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "more corners than the no-limit capacity in a cell (batched launch)"); continue; }
+                const size_t o = g.out_off + (size_t)r->cell_base * g.max_per_cell;
+                memcpy(r->out_xy, D.xy.h + o * 2, (size_t)r->n_cells * g.max_per_cell * 8);
+                if (r->out_score) memcpy(r->out_score, D.score.h + o, (size_t)r->n_cells * g.max_per_cell * 8);
+                if (g.kind == Q_FAST) memcpy(r->out_resp, (const float*)(D.score.h + g.out_off) + (size_t)r->cell_base * g.max_per_cell, (size_t)r->n_cells * g.max_per_cell * 4);
+                memcpy(r->out_count, D.count.h + c0 + r->cell_base, (size_t)r->n_cells * 4);
+            }
+            c0 += g.n_cells;
         }
-        const size_t pix = (size_t)r->roi[2] * r->roi[3];
-        if (r->has_mask() && f_mask + rf_plain + pix + (r->refill ? 8 : 0) > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
-        if (r->mask) f_mask += pix + (r->refill ? 6 : 0);   // (a refill request's bytes begin and end at a multiple of 4)
-        else if (r->refill) rf_plain += (pix + 3) & ~(size_t)3;
-        if (r->refill) { r->trk_off = rf_trk; rf_trk += refill_pad(r->n_trk); rf_n++; rf_max = std::max(rf_max, pix); }
-        FGroup* g = nullptr;
-        for (FGroup& x : fgroups) {
-            const DetReq* k = x.key;
-            if (k->max_per_cell == r->max_per_cell && k->unlimited == r->unlimited && k->quality == r->quality && k->min_dist == r->min_dist && k->ext == r->ext &&
-                k->block_size == r->block_size && k->use_harris == r->use_harris && k->k == r->k && k->has_mask() == r->has_mask() &&
-                x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
-        }
-        if (!g) { fgroups.push_back(FGroup{r, Lr, {}}); g = &fgroups.back(); }
-        r->list_off = f_pix;
-        f_pix += pix;
-        f_n++;
-        g->grid_x = std::max(g->grid_x, gftt_frame_grid_x(r->roi[2], r->roi[3]));
-        g->reqs.push_back(r);
     }
-    if (!fgroups.empty()) {
-        Carve need;
-        for (FGroup& g : fgroups) gftt_frame_block(need, g.reqs.size(), (size_t)g.key->max_per_cell);
-        EK(C.h_gfr.ensure(need.bytes() + 64));
-        EK(C.d_gfr_val.ensure(f_pix * sizeof(float))); EK(C.d_gfr_idx.ensure(f_pix * sizeof(unsigned))); EK(C.d_gfr_keys.ensure(f_pix * sizeof(unsigned long long)));
-        EK(C.d_gfr_info.ensure(f_n * 2 * sizeof(unsigned)));
-        if (f_mask) EK(C.h_gfr_mask.ensure(f_mask + 64));
-        if (f_mask || rf_plain) EK(C.d_gfr_mask.ensure(f_mask + rf_plain + (rf_n ? 4 : 0) + 64));
-        RefillBlock T{};
+};
+
+// ---- whole-frame GFTT and refill: requests that agree in every argument but the slot, the region and the mask's bytes, on frames of one
+// layout, share ONE pass-1 and ONE pass-2 launch (launch_gftt_frame); the round's refill requests share ONE select and ONE paint launch in
+// front of them. The scratch is the combiner's FrameDetScratch.
+struct DetFrames {
+    struct Group { DetReq* key; PyrLayout L; std::vector<DetReq*> reqs; int grid_x = 0; size_t info_base = 0; GfttFrameBlock B{}; };
+    std::vector<DetReq*> reqs; std::vector<Group> groups;
+    RefillBlock T{}; pmv_ctx* ctx = nullptr;   // T: the round's refill tables (a round with a refill request)
+    bool enqueue(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+        ctx = E->ctx; hipStream_t s = C.s; FrameDetScratch& S = C.fds;
+        size_t f_pix = 0, f_mask = 0, f_n = 0;
+        // refill requests: their number, their track entries, the bytes of the regions that are painted from 255 (they lie behind the uploaded
+        // masks and are not copied), the largest region
+        size_t rf_n = 0, rf_trk = 0, rf_plain = 0, rf_max = 0;
+        for (DetReq* r : reqs) {
+            if (!admit_frames(ctx, r, "detect", r->slot, -1, nullptr)) continue;
+            const PyrLayout& Lr = ctx->slot_layout[r->slot];
+            if (r->roi[0] + r->roi[2] > Lr.w[0] || r->roi[1] + r->roi[3] > Lr.h[0]) {   // (the slot was re-used since the call's check)
+                r->rc = PMV_ERR_INVALID; snprintf(r->err, sizeof(r->err), "batch GFTT: region (%d,%d,%d,%d) is not inside the %dx%d frame", r->roi[0], r->roi[1], r->roi[2], r->roi[3], Lr.w[0], Lr.h[0]);
+                continue;
+            }
+            const size_t pix = (size_t)r->roi[2] * r->roi[3];
+            if (r->has_mask() && f_mask + rf_plain + pix + (r->refill ? 8 : 0) > (size_t)INT_MAX) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch GFTT: the masks of the round cover more than 2^31 pixels"); continue; }
+            if (r->mask) f_mask += pix + (r->refill ? 6 : 0);   // (a refill request's bytes begin and end at a multiple of 4)
+            else if (r->refill) rf_plain += (pix + 3) & ~(size_t)3;
+            if (r->refill) { r->trk_off = rf_trk; rf_trk += refill_pad(r->n_trk); rf_n++; rf_max = std::max(rf_max, pix); }
+            Group* g = nullptr;
+            for (Group& x : groups) {
+                const DetReq* k = x.key;
+                if (k->max_per_cell == r->max_per_cell && k->unlimited == r->unlimited && k->quality == r->quality && k->min_dist == r->min_dist && k->ext == r->ext &&
+                    k->block_size == r->block_size && k->use_harris == r->use_harris && k->k == r->k && k->has_mask() == r->has_mask() &&
+                    x.L.w[0] == Lr.w[0] && x.L.h[0] == Lr.h[0] && x.L.n_levels == Lr.n_levels) { g = &x; break; }
+            }
+            if (!g) { groups.push_back(Group{r, Lr, {}}); g = &groups.back(); }
+            r->list_off = f_pix; f_pix += pix; f_n++;
+            g->grid_x = std::max(g->grid_x, gftt_frame_grid_x(r->roi[2], r->roi[3]));
+            g->reqs.push_back(r);
+        }
+        if (groups.empty()) return true;
+        Carve need, rneed;
+        for (Group& g : groups) gftt_frame_block(need, g.reqs.size(), (size_t)g.key->max_per_cell);
+        EKF(S.lists(f_pix, f_n, need.bytes()));
+        // (the round's bytes with this engine's 64 of slack behind every scratch block; the painting owns whole dwords)
+        EKF(S.masks(f_mask || rf_plain ? f_mask + rf_plain + (rf_n ? 4 : 0) + 64 : 0, f_mask ? f_mask + 64 : 0));
         if (rf_n) {
-            Carve rneed;
             refill_block(rneed, rf_n, rf_trk);
-            EK(C.h_refill.ensure(rneed.bytes() + 64)); EK(C.d_refill_kept.ensure((rf_trk + 4) * sizeof(unsigned))); EK(C.d_refill_nkept.ensure(rf_n * sizeof(int)));
-            Carve rc = carve_of(C.h_refill);
+            EKF(S.refill(rf_trk + 4, rf_n, rneed.bytes()));
+            Carve rc = carve_of(S.h_refill);
             T = refill_block(rc, rf_n, rf_trk);
         }
-        Carve c = carve_of(C.h_gfr);
+        Carve c = carve_of(S.h_gfr);
         size_t mpos = 0, ibase = 0;
-        for (FGroup& g : fgroups) {
+        for (Group& g : groups) {
             g.B = gftt_frame_block(c, g.reqs.size(), (size_t)g.key->max_per_cell);
-            g.info_base = ibase;
-            ibase += g.reqs.size();
+            g.info_base = ibase; ibase += g.reqs.size();
             for (size_t i = 0; i < g.reqs.size(); i++) {
                 DetReq* r = g.reqs[i];
                 if (r->refill && r->mask) mpos = (mpos + 3) & ~(size_t)3;   // (the painting owns aligned dwords of a refill request's bytes)
                 const size_t m0 = mpos;
-                mpos = gftt_frame_record(g.B.rec.h + i * CELL_STRIDE, r->roi, r->slot, r->list_off, (uint8_t*)C.h_gfr_mask.p, mpos, r->mask, r->mask_stride);
+                mpos = gftt_frame_record(g.B.rec.h + i * CELL_STRIDE, r->roi, r->slot, r->list_off, S.h_gfr_mask, mpos, r->mask, r->mask_stride);
                 if (r->refill && r->mask) { ctx->refill_stats[3] += (long long)(mpos - m0); mpos = (mpos + 3) & ~(size_t)3; }
             }
         }
-        if (mpos) EK(hipMemcpyAsync(C.d_gfr_mask.p, C.h_gfr_mask.p, mpos, hipMemcpyHostToDevice, s));
+        if (mpos) EKF(hipMemcpyAsync(S.d_gfr_mask, S.h_gfr_mask, mpos, hipMemcpyHostToDevice, s));
         if (rf_n) {   // the regions painted from 255 follow the uploaded bytes; then ONE select and ONE paint launch for the round's refill requests
             size_t ppos = (mpos + 3) & ~(size_t)3, ri = 0;
-            for (FGroup& g : fgroups)
+            for (Group& g : groups)
                 for (size_t i = 0; i < g.reqs.size(); i++) {
                     DetReq* r = g.reqs[i];
                     if (!r->refill) continue;
@@ -623,47 +630,63 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                     if (!r->mask) { rec[5] = (int)ppos; ppos += ((size_t)r->roi[2] * r->roi[3] + 3) & ~(size_t)3; }
                     refill_fill(T, ri++, r->trk_off, r->roi, (size_t)(unsigned)rec[5], r->trk_xy, r->trk_prio, r->n_trk, r->radius, r->mask, r->mask_stride);
                 }
-            EK(launch_track_refill(s, T.rec.d, (int)rf_n, rf_max, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, (unsigned*)C.d_refill_kept.p, (int*)C.d_refill_nkept.p,
-                                   (uint8_t*)C.d_gfr_mask.p));
+            EKF(launch_track_refill(s, T.rec.d, (int)rf_n, rf_max, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, S.d_refill_kept, S.d_refill_nkept, S.d_gfr_mask));
             ctx->refill_stats[1]++; ctx->refill_stats[2]++;
         }
-        for (FGroup& g : fgroups) {
+        for (Group& g : groups) {
             const DetReq* k = g.key;
             const GfttExt X = gftt_ext(k->block_size, k->use_harris, k->k);
-            EK(launch_gftt_frame(s, ctx->d_slots, g.L, g.B.rec.d, (int)g.reqs.size(), g.grid_x, k->max_per_cell, k->quality, k->min_dist, k->unlimited, k->ext ? &X : nullptr,
-                                 k->has_mask() ? (const uint8_t*)C.d_gfr_mask.p : nullptr, (float*)C.d_gfr_val.p, (unsigned*)C.d_gfr_idx.p, (unsigned*)C.d_gfr_info.p + 2 * g.info_base,
-                                 (unsigned long long*)C.d_gfr_keys.p, g.B.xy.d, g.B.count.d, g.B.stats.d));
+            EKF(launch_gftt_frame(s, ctx->d_slots, g.L, g.B.rec.d, (int)g.reqs.size(), g.grid_x, k->max_per_cell, k->quality, k->min_dist, k->unlimited, k->ext ? &X : nullptr,
+                                  k->has_mask() ? S.d_gfr_mask.get() : nullptr, S.d_gfr_val, S.d_gfr_idx, S.d_gfr_info + 2 * g.info_base, S.d_gfr_keys, g.B.xy.d, g.B.count.d,
+                                  g.B.stats.d));
             ctx->gftt_frame_stats[2]++;
         }
         ctx->gftt_frame_stats[1]++;
+        return true;
     }
-    // ---- corner sub-pixel refinement: requests that agree in the six parameters share ONE launch, whatever their slots and frame sizes -
-    // every point's record names its slot and its entry of the geometry table. A round without such a request adds nothing here.
-    struct SGroup { pmv_subpix_params p; std::vector<SubpixReq*> reqs; int n = 0, base = 0; };
-    std::vector<SGroup> sgroups;
-    size_t spx_total = 0;
-    for (SubpixReq* r : spx) {
-        if (!admit_frames(ctx, r, "corner subpix", r->slot, -1, &r->geom)) continue;
-        if (spx_total + (size_t)r->n > E->cap_tracks) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch corner subpix: more points than n_seq * max_tracks in a round"); continue; }
-        SGroup* g = nullptr;
-        for (SGroup& x : sgroups)
-            if (x.p.win_w == r->p.win_w && x.p.win_h == r->p.win_h && x.p.zero_w == r->p.zero_w && x.p.zero_h == r->p.zero_h && x.p.max_iter == r->p.max_iter && x.p.eps == r->p.eps) { g = &x; break; }
-        if (!g) { sgroups.push_back(SGroup{r->p, {}, 0, 0}); g = &sgroups.back(); }
-        g->reqs.push_back(r);
-        g->n += r->n;
-        spx_total += (size_t)r->n;
+    void collect() {
+        for (Group& g : groups)
+            for (size_t i = 0; i < g.reqs.size(); i++) {
+                DetReq* r = g.reqs[i];
+                const int n = g.B.count.h[i];
+                ctx->gftt_frame_stats[3] = g.B.stats.h[2 * i]; ctx->gftt_frame_stats[4] = g.B.stats.h[2 * i + 1];   // (of the last request served)
+                if (n < 0) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "%s: more than out_cap = %d corners with max_corners <= 0 (no limit)", r->refill ? "pmv_batch_detect_gftt_refill" : "pmv_batch_detect_gftt_frame", r->max_per_cell); continue; }
+                if (r->refill) memcpy(r->out_keep, T.keep.h + r->trk_off, (size_t)r->n_trk);
+                memcpy(r->out_xy, g.B.xy.h + i * (size_t)r->max_per_cell * 2, (size_t)n * 8);
+                *r->out_count = n;
+            }
     }
-    if (spx_total > 0) {
-        const size_t tab_bytes = sgroups.size() * SUBPIX_TABLE_MAX * sizeof(float);
+};
+
+// ---- corner sub-pixel refinement: requests that agree in the six parameters share ONE launch, whatever their slots and frame sizes -
+// every point's record names its slot and its entry of the geometry table. The round's weight tables are its own (one per group).
+struct DetSubpix {
+    struct Group { pmv_subpix_params p; std::vector<SubpixReq*> reqs; int n = 0, base = 0; };
+    std::vector<SubpixReq*> reqs; std::vector<Group> groups;
+    SubpixBlock S{};
+    bool enqueue(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+        pmv_ctx* ctx = E->ctx; hipStream_t s = C.s;
+        size_t total = 0;
+        for (SubpixReq* r : reqs) {
+            if (!admit_frames(ctx, r, "corner subpix", r->slot, -1, &r->geom)) continue;
+            if (total + (size_t)r->n > E->cap_tracks) { r->rc = PMV_ERR_CAPACITY; snprintf(r->err, sizeof(r->err), "batch corner subpix: more points than n_seq * max_tracks in a round"); continue; }
+            Group* g = nullptr;
+            for (Group& x : groups)
+                if (x.p.win_w == r->p.win_w && x.p.win_h == r->p.win_h && x.p.zero_w == r->p.zero_w && x.p.zero_h == r->p.zero_h && x.p.max_iter == r->p.max_iter && x.p.eps == r->p.eps) { g = &x; break; }
+            if (!g) { groups.push_back(Group{r->p, {}, 0, 0}); g = &groups.back(); }
+            g->reqs.push_back(r); g->n += r->n; total += (size_t)r->n;
+        }
+        if (total == 0) { groups.clear(); return true; }
+        const size_t tab_bytes = groups.size() * SUBPIX_TABLE_MAX * sizeof(float);
         Carve spx_need;
-        subpix_block(spx_need, spx_total);
-        EK(C.h_spx.ensure(spx_need.bytes() + 64)); EK(C.h_spx_tab.ensure(tab_bytes)); EK(C.d_spx_tab.ensure(tab_bytes));
+        subpix_block(spx_need, total);
+        EKF(C.h_spx.ensure(spx_need.bytes() + 64)); EKF(C.h_spx_tab.ensure(tab_bytes)); EKF(C.d_spx_tab.ensure(tab_bytes));
         Carve c = carve_of(C.h_spx);
-        const SubpixBlock S = subpix_block(c, spx_total);
+        S = subpix_block(c, total);
         SubpixRec* rec = S.rec.h;
         int pos = 0;
-        for (size_t gi = 0; gi < sgroups.size(); gi++) {
-            SGroup& g = sgroups[gi];
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            Group& g = groups[gi];
             g.base = pos;
             for (SubpixReq* r : g.reqs) {
                 r->base = pos;
@@ -671,59 +694,36 @@ void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
             }
             subpix_table(g.p.win_w, g.p.win_h, g.p.zero_w, g.p.zero_h, (float*)C.h_spx_tab.p + gi * SUBPIX_TABLE_MAX);
         }
-        EK(hipMemcpyAsync(C.d_spx_tab.p, C.h_spx_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        for (size_t gi = 0; gi < sgroups.size(); gi++) {
-            const SGroup& g = sgroups[gi];
+        EKF(hipMemcpyAsync(C.d_spx_tab.p, C.h_spx_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            const Group& g = groups[gi];
             const SubpixArgs A{g.p.win_w, g.p.win_h, g.p.max_iter, g.p.eps * g.p.eps};
-            EK(launch_corner_subpix_geom(s, ctx->d_slots, ctx->d_geom, S.rec.d + g.base, g.n, (const float*)C.d_spx_tab.p + gi * SUBPIX_TABLE_MAX, A,
-                                         S.xy.d + 2 * (size_t)g.base, S.iters.d + g.base, S.flags.d + g.base));
+            EKF(launch_corner_subpix_geom(s, ctx->d_slots, ctx->d_geom, S.rec.d + g.base, g.n, (const float*)C.d_spx_tab.p + gi * SUBPIX_TABLE_MAX, A,
+                                          S.xy.d + 2 * (size_t)g.base, S.iters.d + g.base, S.flags.d + g.base));
             ctx->subpix_launches[2]++;
         }
         ctx->subpix_launches[1]++;
+        return true;
     }
-    SYNC_TIMED(C);
-    if (spx_total > 0) {
-        Carve c = carve_of(C.h_spx);
-        const SubpixBlock S = subpix_block(c, spx_total);
-        for (SGroup& g : sgroups)
+    void collect() {
+        for (Group& g : groups)
             for (SubpixReq* r : g.reqs) {
                 memcpy(r->xy, S.xy.h + (size_t)2 * r->base, (size_t)r->n * 8);
                 if (r->iters_out) memcpy(r->iters_out, S.iters.h + r->base, (size_t)r->n);
                 if (r->flags_out) memcpy(r->flags_out, S.flags.h + r->base, (size_t)r->n);
             }
     }
-    for (FGroup& g : fgroups)
-        for (size_t i = 0; i < g.reqs.size(); i++) {
-            DetReq* r = g.reqs[i];
-            const int n = g.B.count.h[i];
-            ctx->gftt_frame_stats[3] = g.B.stats.h[2 * i]; ctx->gftt_frame_stats[4] = g.B.stats.h[2 * i + 1];
-            if (n < 0) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "%s: more than out_cap = %d corners with max_corners <= 0 (no limit)", r->refill ? "pmv_batch_detect_gftt_refill" : "pmv_batch_detect_gftt_frame", r->max_per_cell); continue; }
-            if (r->refill) {
-                Carve rc = carve_of(C.h_refill);
-                memcpy(r->out_keep, refill_block(rc, rf_n, rf_trk).keep.h + r->trk_off, (size_t)r->n_trk);
-            }
-            memcpy(r->out_xy, g.B.xy.h + i * (size_t)r->max_per_cell * 2, (size_t)n * 8);
-            *r->out_count = n;
-        }
-    if (!det.empty()) {
-        const DetBlock D = det_block(C, tot_out, tot_cells);
-        const int flags = *D.flags.h;
-        const int* hxy = D.xy.h;
-        const double* hsc = D.score.h;
-        const int* hcnt = D.count.h;
-        size_t c0 = 0;
-        for (Group& g : groups) {
-            for (DetReq* r : g.reqs) {
-                if (g.kind == Q_GFTT && (flags & 4)) { r->rc = PMV_ERR_OVERFLOW; snprintf(r->err, sizeof(r->err), "more corners than the no-limit capacity in a cell (batched launch)"); continue; }
-                const size_t o = g.out_off + (size_t)r->cell_base * g.max_per_cell;
-                memcpy(r->out_xy, hxy + o * 2, (size_t)r->n_cells * g.max_per_cell * 8);
-                if (r->out_score) memcpy(r->out_score, hsc + o, (size_t)r->n_cells * g.max_per_cell * 8);
-                if (g.kind == Q_FAST) memcpy(r->out_resp, (const float*)(hsc + g.out_off) + (size_t)r->cell_base * g.max_per_cell, (size_t)r->n_cells * g.max_per_cell * 4);
-                memcpy(r->out_count, hcnt + c0 + r->cell_base, (size_t)r->n_cells * 4);
-            }
-            c0 += g.n_cells;
-        }
-    }
+};
+#undef EKF
+
+void process_det(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
+    DetCells cells; DetFrames frames; DetSubpix subpix;
+    for (Req* r : batch) { if (r->kind == Q_SUBPIX) subpix.reqs.push_back((SubpixReq*)r); else if (r->kind == Q_GFTT_FRAME) frames.reqs.push_back((DetReq*)r); else cells.reqs.push_back((DetReq*)r); }
+    if (!cells.enqueue(E, C, batch) || !frames.enqueue(E, C, batch) || !subpix.enqueue(E, C, batch)) return;
+    SYNC_TIMED(C);
+    subpix.collect();
+    frames.collect();   // (gftt_frame_stats[3..4]: the last request served)
+    cells.collect();
 }
 
 // ---- back-end classes: the callers prepared their inputs in their slot's pinned block; one gather kernel pulls them into HBM ----

@@ -916,18 +916,17 @@ int pmv_detect_gftt_frame(pmv_ctx* ctx, int slot, const int* roi4_or_null, int m
     const size_t pix = (size_t)ctx->max_w * ctx->max_h;
     Carve need;
     gftt_frame_block(need, 1, PMV_GFTT_FRAME_MAX_CORNERS);
-    CKC(ctx->h_gfr.ensure(need.bytes() + 64));
-    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
-    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
-    if (mask) { CKC(ctx->h_gfr_mask.ensure(pix)); CKC(ctx->d_gfr_mask.ensure(pix)); }
-    Carve c = carve_of(ctx->h_gfr);
+    FrameDetScratch& S = ctx->fds;
+    CKC(S.lists(pix, 1, need.bytes()));
+    if (mask) CKC(S.masks(pix, pix));
+    Carve c = carve_of(S.h_gfr);
     const GfttFrameBlock B = gftt_frame_block(c, 1, (size_t)cap);
-    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, ctx->h_gfr_mask, 0, mask, mask_stride);
-    if (mask) CKC(hipMemcpyAsync(ctx->d_gfr_mask, ctx->h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front));
+    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, S.h_gfr_mask, 0, mask, mask_stride);
+    if (mask) CKC(hipMemcpyAsync(S.d_gfr_mask, S.h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front));
     const bool general = p->block_size != 3 || p->use_harris || mask || ctx->gftt_general;
     const GfttExt X = gftt_ext(p->block_size, p->use_harris, p->k);
     CKC(launch_gftt_frame(ctx->s_front, ctx->d_slots, L, B.rec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p->quality, p->min_dist, max_corners <= 0, general ? &X : nullptr,
-                          mask ? ctx->d_gfr_mask.get() : nullptr, ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
+                          mask ? S.d_gfr_mask.get() : nullptr, S.d_gfr_val, S.d_gfr_idx, S.d_gfr_info, S.d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
     CKC(hipStreamSynchronize(ctx->s_front));
     ctx->gftt_frame_stats[0]++; ctx->gftt_frame_stats[3] = B.stats.h[0]; ctx->gftt_frame_stats[4] = B.stats.h[1];
     const int n = B.count.h[0];
@@ -958,22 +957,20 @@ int pmv_detect_gftt_refill(pmv_ctx* ctx, int slot, const int* roi4_or_null, int 
     Carve need, rneed;
     gftt_frame_block(need, 1, PMV_GFTT_FRAME_MAX_CORNERS);
     refill_block(rneed, 1, PMV_REFILL_MAX_TRACKS);
-    CKC(ctx->h_gfr.ensure(need.bytes() + 64)); CKC(ctx->h_refill.ensure(rneed.bytes() + 64));
-    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
-    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
-    CKC(ctx->d_gfr_mask.ensure(pix + 64));   // (a dword of the painting may end behind the region's last byte)
-    CKC(ctx->d_refill_kept.ensure((size_t)PMV_REFILL_MAX_TRACKS * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(sizeof(int)));
-    if (base_mask_or_null) CKC(ctx->h_gfr_mask.ensure(pix));
-    Carve c = carve_of(ctx->h_gfr), rc2 = carve_of(ctx->h_refill);
+    FrameDetScratch& S = ctx->fds;
+    CKC(S.lists(pix, 1, need.bytes()));
+    CKC(S.masks(pix + S.PAINT_SLACK, base_mask_or_null ? pix : 0));
+    CKC(S.refill(PMV_REFILL_MAX_TRACKS, 1, rneed.bytes()));
+    Carve c = carve_of(S.h_gfr), rc2 = carve_of(S.h_refill);
     const GfttFrameBlock B = gftt_frame_block(c, 1, (size_t)cap);
     const RefillBlock T = refill_block(rc2, 1, refill_pad(n_tracks));
-    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, ctx->h_gfr_mask, 0, base_mask_or_null, base_stride);   // (mask offset 0 either way)
+    const size_t nb = gftt_frame_record(B.rec.h, roi, slot, 0, S.h_gfr_mask, 0, base_mask_or_null, base_stride);   // (mask offset 0 either way)
     refill_fill(T, 0, 0, roi, 0, track_xy, track_prio_or_null, n_tracks, radius, base_mask_or_null, base_stride);
-    if (base_mask_or_null) { CKC(hipMemcpyAsync(ctx->d_gfr_mask, ctx->h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front)); ctx->refill_stats[3] += (long long)nb; }
-    CKC(launch_track_refill(ctx->s_front, T.rec.d, 1, rpix, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    if (base_mask_or_null) { CKC(hipMemcpyAsync(S.d_gfr_mask, S.h_gfr_mask, nb, hipMemcpyHostToDevice, ctx->s_front)); ctx->refill_stats[3] += (long long)nb; }
+    CKC(launch_track_refill(ctx->s_front, T.rec.d, 1, rpix, T.pos.d, T.prio.d, T.flag.d, T.hw.d, T.keep.d, S.d_refill_kept, S.d_refill_nkept, S.d_gfr_mask));
     const GfttExt X = gftt_ext(p->block_size, p->use_harris, p->k);
-    CKC(launch_gftt_frame(ctx->s_front, ctx->d_slots, L, B.rec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p->quality, p->min_dist, max_corners <= 0, &X, ctx->d_gfr_mask.get(),
-                          ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
+    CKC(launch_gftt_frame(ctx->s_front, ctx->d_slots, L, B.rec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p->quality, p->min_dist, max_corners <= 0, &X, S.d_gfr_mask.get(),
+                          S.d_gfr_val, S.d_gfr_idx, S.d_gfr_info, S.d_gfr_keys, B.xy.d, B.count.d, B.stats.d));
     CKC(hipStreamSynchronize(ctx->s_front));
     ctx->refill_stats[0]++; ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];
     const int n = B.count.h[0];
@@ -991,7 +988,7 @@ int pmv_debug_refill_mask(pmv_ctx* ctx, uint8_t* out, long long cap, int* w, int
     REQ(cap >= nb, PMV_ERR_CAPACITY, "pmv_debug_refill_mask: cap = %lld is below the %dx%d region's %lld bytes", cap, ctx->refill_last[0], ctx->refill_last[1], nb);
     CKC(hipSetDevice(ctx->device));
     CKC(hipStreamSynchronize(ctx->s_front));
-    CKC(hipMemcpy(out, ctx->d_gfr_mask, (size_t)nb, hipMemcpyDeviceToHost));
+    CKC(hipMemcpy(out, ctx->fds.d_gfr_mask, (size_t)nb, hipMemcpyDeviceToHost));
     *w = ctx->refill_last[0]; *h = ctx->refill_last[1];
     return PMV_OK;
 }
@@ -1017,21 +1014,13 @@ int pmv_corner_subpix(pmv_ctx* ctx, int slot, float* xy, int n, const pmv_subpix
     const size_t nt = (size_t)ctx->max_tracks;
     Carve spx_need, spx;
     subpix_block(spx_need, nt);
-    CKC(ctx->h_subpix.ensure(spx_need.bytes() + 64)); CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
-    int zw, zh;
-    subpix_zero_zone(p, &zw, &zh);
-    const int key[4] = {p->win_w, p->win_h, zw, zh};
-    if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
-        CKC(hipStreamSynchronize(ctx->s_front));   // (the pinned mirror may still be on its way from the last change)
-        subpix_table(p->win_w, p->win_h, zw, zh, ctx->h_subpix_tab);
-        CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * p->win_w + 1) * (2 * p->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
-        memcpy(ctx->subpix_tab_key, key, sizeof(key));
-    }
+    CKC(ctx->h_subpix.ensure(spx_need.bytes() + 64));
+    SubpixArgs A;
+    CKC(subpix_table_ready(ctx, p, &A));
     spx = carve_of(ctx->h_subpix);
     const SubpixBlock S = subpix_block(spx, nt);   // at max_tracks points (the engine's round carves the same block at its round's points)
     SubpixRec* rec = S.rec.h;
     for (int i = 0; i < n; i++) rec[i] = SubpixRec{xy[2 * i], xy[2 * i + 1], slot, 0};
-    const SubpixArgs A{p->win_w, p->win_h, p->max_iter, p->eps * p->eps};
     CKC(launch_corner_subpix(ctx->s_front, ctx->d_slots, ctx->slot_layout[slot], S.rec.d, n, ctx->d_subpix_tab, A, S.xy.d, S.iters.d, S.flags.d));
     ctx->subpix_launches[0]++;
     CKC(hipStreamSynchronize(ctx->s_front));

@@ -9,7 +9,9 @@
 // pmv_klt_step_many steps a group of trackers through ONE such chain: the same three bodies as a grid over the trackers (blockIdx.x selects a
 // per-tracker argument record in device memory), LK as one batched launch whose records k_klt_lk_records writes from the trackers' states,
 // and the multi-request forms of the refill, frame and F launches. pmv_klt_step keeps its own argument form: a group of one is ~25 us slower
-// (DESIGN.md §4).
+// (DESIGN.md §4). What the stage kernels of a tracker are given is described ONCE, by klt_stage_args: it fills a KltManyRec from the tracker
+// and from where its parts of the per-launch tables live (KltShares); the many-call stores that record in its block, the single step passes
+// the record's members as kernel arguments. klt_launch, klt_f_problem, klt_result_check, klt_result_copy and klt_book are shared too.
 // pmv_klt_step_stereo / pmv_klt_step_many_stereo append a stage 8 behind the append and in front of the final wait: LK from the current left
 // into the right frame for the list the step returns, in a launch sized by the bound (target) whose workgroups read the list's length from
 // device memory, then one workgroup per tracker that applies stage 2's rule to the result and ends the chain with its own completion word.
@@ -528,8 +530,111 @@ int pmv_klt_get_tracks(pmv_ctx* ctx, int id, int* ids, int* ages, float* xy, int
 
 }  // extern "C"
 
-// pmv_klt_step and, with `right`, pmv_klt_step_stereo: the same chain, refused in the same words; the stereo form appends stage 8
+// ---- what pmv_klt_step and pmv_klt_step_many share on the host ------------------------------------------------------------------------
+// Where a tracker's parts of a chain's per-launch tables live: its own buffers in a single step, its shares of the group's blocks in a
+// many-call.
+struct KltLkOut { float* xy; float* bk_xy; uint8_t* st; uint8_t* bk_st; };   // what the stage kernels read of an LK launch's results
+struct KltShares {
+    KltLkOut lk; KltRefillIn rf; uint8_t* keep;   // stage 1's results for the tracker's state | what k_track_select reads, with the refill record | the keep bytes it leaves
+    int* want; int* m; int* stat;                 // the selection pass's words: corners wanted, corners found, its two statistics
+    int* ixy; float* sp_xy;                       // the corner list and the refined corners
+    unsigned long long prev_off, next_off; int lk_base;   // a many-call: byte offsets of the two frame slots, first index of the share of stage 1's LK records
+    // a stereo call: stage 8's results (the LK result arrays of stage 1 are free again by then), whether the tracker has a right frame in this
+    // call, and for a many-call the right slot's offset and the share's first index
+    bool stereo; int right_on; KltLkOut st; unsigned long long right_off; int st_base;
+};
+// THE description of what the stage kernels of tracker t are given in its next chain, which begins here: the completion words are armed
+// before anything is launched. The many-call stores the record in its block, the single step passes its members as kernel arguments.
+// by_keep.in / out and append.in are written for list 0 and append.f_info is null: which list holds the tracks and whether F ran is known
+// after stage 3 - k_klt_compact_many and k_klt_append_many patch them on the device, klt_step_run on the host.
+static KltManyRec klt_stage_args(KltTracker* t, const PyrLayout& L, const KltShares& sh) {
+    if (++t->seq == 0) t->seq = 1;
+    t->O.hdr.h[9] = 0; t->O.hdr.h[10] = 0;
+    const pmv_klt_params& p = t->p;
+    const KltDev& D = t->D; const KltRes& O = t->O;
+    const bool fb = p.fb_max_dist >= 0.0;
+    int* cnt = D.cnt.d;
+    KltManyRec M{};
+    for (int k = 0; k < 2; k++) { M.lst[k].id = D.l_id[k].d; M.lst[k].age = D.l_age[k].d; M.lst[k].prev = D.l_prev[k].d; M.lst[k].cur = D.l_cur[k].d; }
+    KltFilterArgs& F = M.filter;
+    F.n0 = t->n; F.fb = fb ? 1 : 0; F.border = p.border; F.w = L.w[0]; F.h = L.h[0]; F.thr2 = t->thr2;
+    F.id = D.s_id.d; F.age = D.s_age.d; F.prev = D.s_xy.d; F.fwd = sh.lk.xy; F.back = sh.lk.bk_xy; F.st = sh.lk.st; F.bst = sh.lk.bk_st;
+    F.out = M.lst[0]; F.rf = sh.rf; F.cnt = cnt; F.h_n1 = O.n1.d;
+    KltCompactArgs& BF = M.by_f;
+    BF.in = M.lst[0]; BF.out = M.lst[1]; BF.mask = (const uint8_t*)(D.f_out.d + ESS_OUT_HDR); BF.n_in = cnt + C_N1;
+    BF.cap = t->cap; BF.cnt_out = C_N2; BF.target = 0; BF.rf = sh.rf; BF.cnt = cnt; BF.want = sh.want;
+    KltCompactArgs& BK = M.by_keep;   // (rf stays null: nothing is written for k_track_select)
+    BK.in = M.lst[0]; BK.out = M.lst[1]; BK.mask = sh.keep; BK.n_in = cnt + C_N2;
+    BK.cap = t->cap; BK.cnt_out = C_N3; BK.target = t->cap; BK.cnt = cnt; BK.want = sh.want;
+    KltAppendArgs& A = M.append;
+    A.in = M.lst[0]; A.cnt = cnt; A.m = sh.m; A.ixy = sh.ixy; A.sp_xy = p.subpix ? sh.sp_xy : nullptr; A.f_info = nullptr;
+    A.n0 = t->n; A.next_id = t->next_id; A.target = t->cap; A.seq = t->seq; A.s_id = D.s_id.d; A.s_age = D.s_age.d; A.s_xy = D.s_xy.d;
+    A.r_hdr = O.hdr.d; A.r_id = O.id.d; A.r_age = O.age.d; A.r_xy = O.xy.d; A.r_prev = O.prev.d; A.n_out = sh.stereo ? cnt + C_NOUT : nullptr;
+    M.f_info = (const int*)(D.f_out.d + ESS_OUT_INFO);
+    M.prev_off = sh.prev_off; M.next_off = sh.next_off; M.lk_base = sh.lk_base; M.lk_flags = fb ? LKX_FB : 0;
+    if (sh.stereo) {
+        const bool sfb = sh.right_on && t->st.fb_max_dist >= 0.0;
+        KltStereoArgs& S = M.stereo;
+        S.n = cnt + C_NOUT; S.cap = t->cap; S.on = sh.right_on ? 1 : 0; S.fb = sfb ? 1 : 0; S.border = t->st.border; S.w = L.w[0]; S.h = L.h[0]; S.thr2 = t->st_thr2;
+        S.prev = D.s_xy.d; S.fwd = sh.st.xy; S.back = sh.st.bk_xy; S.st = sh.st.st; S.bst = sh.st.bk_st;
+        S.seq = t->seq; S.r_hdr = O.hdr.d; S.r_rxy = O.right_xy.d; S.r_rst = O.right_st.d;
+        M.right_off = sh.right_off; M.st_base = sh.st_base; M.st_flags = sfb ? LKX_FB : 0;
+    }
+    return M;
+}
+// one launch of a glue kernel (KT threads per workgroup), booked under the detector's selection class
+template <class... P, class... A> static hipError_t klt_launch(void (*kernel)(P...), int grid, hipStream_t s, A... args) {
+    ProfScope ps(K_GFTT_PICK, s);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(KT), 0, s, args...);
+    return hipGetLastError();
+}
+// rejectWithF's problem for the n1 tracks the filter left in the tracker's list 0, and libm's iteration table (n1 + 2 doubles) at tab_h
+static FundamentalProblem klt_f_problem(const KltTracker* t, int n1, double* tab_h, const double* tab_d) {
+    FundamentalProblem P;
+    P.p1 = t->D.l_prev[0].d; P.p2 = t->D.l_cur[0].d; P.iters = tab_d; P.out = t->D.f_out.d;
+    P.n = n1; P.max_iters = 1000; P.thr = (float)(t->p.f_threshold * t->p.f_threshold); P.done_seq = 1;
+    vo::ransac_iters_table(n1, t->p.f_confidence, 7, tab_h + 1, tab_h);
+    return P;
+}
+// after the final wait: the header of the tracker's result block (`who`: pmv_klt_step or pmv_klt_step_many; j >= 0: tracker j of a group)
+static int klt_result_check(pmv_ctx* ctx, const KltTracker* t, bool stereo, const char* who, int j) {
+    const int* hdr = t->O.hdr.h;
+    const int n = hdr[8], m = hdr[4];
+    char of[48] = "";
+    if (j >= 0) snprintf(of, sizeof(of), " of tracker %d of the group", j);
+    REQ((unsigned)hdr[9] == t->seq && n >= 0 && n <= t->cap && m >= 0 && m <= n, PMV_ERR_HIP, "%s: the result block%s is incomplete (n = %d, m = %d)", who, of, n, m);
+    REQ(!stereo || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= n), PMV_ERR_HIP, "%s_stereo: the result block%s is incomplete (n = %d, matched = %d)", who, of, n,
+        hdr[7]);
+    return PMV_OK;
+}
+// ... and the copy-out of a checked block to the caller's arrays, which begin at the tracker's place; the state's length and next id follow
+// it. right: null in a call without stage 8; slot < 0: the tracker has no right frame in this (many-)call - status zeros, xy untouched.
 struct KltRightOut { int slot; float* xy; uint8_t* st; };
+static void klt_result_copy(KltTracker* t, int* ids, int* ages, float* xy, float* prev_xy_or_null, int* out_n, int* counts8, const KltRightOut* right) {
+    const KltRes& O = t->O;
+    const int n = O.hdr.h[8], m = O.hdr.h[4];
+    memcpy(ids, O.id.h, (size_t)n * 4);
+    memcpy(ages, O.age.h, (size_t)n * 4);
+    memcpy(xy, O.xy.h, (size_t)n * 8);
+    if (prev_xy_or_null) memcpy(prev_xy_or_null, O.prev.h, (size_t)n * 8);
+    memcpy(counts8, O.hdr.h, 8 * sizeof(int));
+    *out_n = n;
+    if (right && right->slot >= 0) {
+        memcpy(right->xy, O.right_xy.h, (size_t)n * 8);
+        memcpy(right->st, O.right_st.h, (size_t)n);
+    } else if (right) memset(right->st, 0, (size_t)n);
+    t->n = n; t->next_id += m;
+}
+// the closing statistics of a step (n_trk = 0) or of a many-call on n_trk trackers; the mask at the front of the scratch is now the region's
+// of this call (a group's: tracker 0's)
+static void klt_book(pmv_ctx* ctx, const int* roi, int n_trk, bool stereo, long long waits, long long launches) {
+    ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];
+    if (stereo) { ctx->klt_stereo_stats[n_trk ? 1 : 0]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
+    else if (n_trk) { ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches; }
+    else { ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches; }
+}
+
+// pmv_klt_step and, with `right`, pmv_klt_step_stereo: the same chain, refused in the same words; the stereo form appends stage 8
 static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* out_ids, int* out_ages, float* out_xy, float* out_prev_xy_or_null, int out_cap, int* out_n,
                         int* out_counts8, const KltRightOut* right) {
     REQ(ctx, PMV_ERR_INVALID, "pmv_klt_step: null argument");
@@ -541,7 +646,6 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
     REQ(!right || t->st_on, PMV_ERR_INVALID, "pmv_klt_step_stereo: tracker %d has no stereo setting (pmv_klt_set_stereo)", id);
     const pmv_klt_params& p = t->p;
     const int n0 = t->n, cap = t->cap;
-    const bool fb = p.fb_max_dist >= 0.0;
     // the slot rules of the calls the stages are: LK's for the pair (only when something is tracked), the frame detector's for cur_slot
     if (n0 > 0)
         if (const int rc = lk_check(ctx, true, prev_slot, cur_slot, out_xy, n0, out_xy, (const uint8_t*)out_ids, out_xy)) return rc;
@@ -550,30 +654,14 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
     // stage 8's LK pair, before anything is launched: the length of the list it tracks is known only on the device
     if (right)
         if (const int rc = lk_check(ctx, true, cur_slot, right->slot, nullptr, 0, nullptr, nullptr, nullptr)) return rc;
-    tl_prof = &ctx->prof;
-    CKC(hipSetDevice(ctx->device));
+    tl_prof = &ctx->prof; CKC(hipSetDevice(ctx->device));
     const PyrLayout& L = ctx->slot_layout[cur_slot];
     const size_t pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3];
-    // the context's scratch of the refill and frame calls (rewritten by every call and every step)
-    CKC(ctx->d_gfr_val.ensure(pix * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(pix * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(pix * sizeof(unsigned long long)));
-    CKC(ctx->d_gfr_info.ensure(2 * sizeof(unsigned)));
-    CKC(ctx->d_gfr_mask.ensure(pix + 64));
-    CKC(ctx->d_refill_kept.ensure((size_t)PMV_REFILL_MAX_TRACKS * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(sizeof(int)));
+    // the context's scratch of the refill and frame calls (rewritten by every call and every step); records and results are the tracker's
+    FrameDetScratch& S = ctx->fds;
+    CKC(S.lists(pix, 1)); CKC(S.masks(pix + S.PAINT_SLACK, 0)); CKC(S.refill(PMV_REFILL_MAX_TRACKS, 1));
     SubpixArgs SA{};
-    if (p.subpix) {   // the weight table, as pmv_corner_subpix keeps it
-        const pmv_subpix_params* sp = &p.subpix_params;
-        CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
-        int zw, zh;
-        subpix_zero_zone(sp, &zw, &zh);
-        const int key[4] = {sp->win_w, sp->win_h, zw, zh};
-        if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
-            CKC(hipStreamSynchronize(ctx->s_front));
-            subpix_table(sp->win_w, sp->win_h, zw, zh, ctx->h_subpix_tab);
-            CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * sp->win_w + 1) * (2 * sp->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
-            memcpy(ctx->subpix_tab_key, key, sizeof(key));
-        }
-        SA = SubpixArgs{sp->win_w, sp->win_h, sp->max_iter, sp->eps * sp->eps};
-    }
+    if (p.subpix) CKC(subpix_table_ready(ctx, &p.subpix_params, &SA));
     hipStream_t s = ctx->s_front;
     const KltDev& D = t->D; const KltRecs& R = t->R; const KltRes& O = t->O;
     long long launches = 0, waits = 0;
@@ -581,115 +669,73 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
     *R.rrec.h = RefillRec{0, p.radius, 0, roi[0], roi[1], roi[2], roi[3], 0u, 0, {0, 0, 0}};
     gftt_frame_record(R.grec.h, roi, cur_slot, 0, nullptr, 0, nullptr, 0);
     CKC(hipMemcpyAsync(t->d_rec, t->h_rec, R.front, hipMemcpyHostToDevice, s));
-    const KltRefillIn rf{D.pos.d, D.prio.d, D.flag.d, R.rrec.d};
-    KltList lst[2];
-    for (int k = 0; k < 2; k++) lst[k] = KltList{D.l_id[k].d, D.l_age[k].d, D.l_prev[k].d, D.l_cur[k].d};
+    // the stage arguments, from the tracker's own buffers
+    KltShares sh{};
+    sh.lk = KltLkOut{D.lk_xy.d, D.bk_xy.d, D.lk_st.d, D.bk_st.d};
+    sh.rf = KltRefillIn{D.pos.d, D.prio.d, D.flag.d, R.rrec.d};
+    sh.keep = D.keep.d; sh.want = D.cnt.d + C_WANT; sh.m = D.cnt.d + C_M; sh.stat = D.cnt.d + C_STAT0; sh.ixy = D.ixy.d; sh.sp_xy = D.sp_xy.d;
+    sh.stereo = right != nullptr; sh.right_on = 1; sh.st = sh.lk;
+    KltManyRec M = klt_stage_args(t, L, sh);
     // 1. track
     if (n0 > 0) {
         const PyrLayout& Lp = ctx->slot_layout[prev_slot];
         CKC(launch_lk_ex(s, ctx->d_slots + (size_t)prev_slot * Lp.slot_bytes, ctx->d_slots + (size_t)cur_slot * Lp.slot_bytes, Lp, D.s_xy.d, nullptr, D.order.d, (n0 + 7) / 8 * 8,
-                         n0, fb ? LKX_FB : 0, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
+                         n0, M.lk_flags, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
         launches++;
     }
     // 2. filter
-    {
-        KltFilterArgs A{n0, fb ? 1 : 0, p.border, L.w[0], L.h[0], t->thr2, D.s_id.d, D.s_age.d, D.s_xy.d, D.lk_xy.d, D.bk_xy.d, D.lk_st.d, D.bk_st.d, lst[0], rf, D.cnt.d, O.n1.d};
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_filter, dim3(1), dim3(KT), 0, s, A);
-        CKC(hipGetLastError());
-        launches++;
-    }
+    CKC(klt_launch(k_klt_filter, 1, s, M.filter)); launches++;
     // 3. rejectWithF: the host reads n1 (the iteration table is libm's) and sends the table with the launches of the second half
-    int cur = 0;
-    bool f_ran = false;
+    int cur = 0; bool f_ran = false;
     if (p.reject_f && n0 >= 15) {
         CKC(hipStreamSynchronize(s));
         waits++;
         const int n1 = *O.n1.h;
         REQ(n1 >= 0 && n1 <= n0, PMV_ERR_HIP, "pmv_klt_step: the filter left n1 = %d of %d tracks", n1, n0);
         if (n1 >= 15) {
-            FundamentalProblem P;
-            P.p1 = lst[0].prev; P.p2 = lst[0].cur; P.iters = R.ftab.d; P.out = D.f_out.d;
-            P.n = n1; P.max_iters = 1000; P.thr = (float)(p.f_threshold * p.f_threshold); P.done_seq = 1;
+            const FundamentalProblem P = klt_f_problem(t, n1, R.ftab.h, R.ftab.d);
             memset(R.fprob.h, 0, ESS_HDR);
             memcpy(R.fprob.h, &P, sizeof(P));
-            vo::ransac_iters_table(n1, p.f_confidence, 7, R.ftab.h + 1, R.ftab.h);
             const size_t fbytes = (size_t)((const char*)(R.ftab.h + n1 + 2) - R.fprob.h);
             CKC(hipMemcpyAsync((char*)t->d_rec.p + R.fprob.off, R.fprob.h, fbytes, hipMemcpyHostToDevice, s));
             CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)R.fprob.d, 1));
-            KltCompactArgs A{lst[0], lst[1], (const uint8_t*)(D.f_out.d + ESS_OUT_HDR), D.cnt.d + C_N1, cap, C_N2, 0, rf, D.cnt.d, D.cnt.d + C_WANT};
-            ProfScope ps(K_GFTT_PICK, s);
-            hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
-            CKC(hipGetLastError());
-            launches += 2;
-            cur = 1; f_ran = true;
+            CKC(klt_launch(k_klt_compact, 1, s, M.by_f));
+            launches += 2; cur = 1; f_ran = true;
         }
     }
+    // what the many-kernels decide on the device: the later stages read the list the tracks are in now, and F's info only if F ran
+    M.by_keep.in = M.lst[cur]; M.by_keep.out = M.lst[cur ^ 1];
+    M.append.in = M.lst[cur ^ 1];
+    M.append.f_info = f_ran ? M.f_info : nullptr;
     // 4. thin: setMask's walk and painting on the list, then the compaction by its keep bytes, which leaves the number of corners wanted
-    CKC(launch_track_refill(s, R.rrec.d, 1, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    CKC(launch_track_refill(s, R.rrec.d, 1, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, S.d_refill_kept, S.d_refill_nkept, S.d_gfr_mask));
     launches += 2;
-    {
-        KltCompactArgs A{lst[cur], lst[cur ^ 1], D.keep.d, D.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, D.cnt.d, D.cnt.d + C_WANT};
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_compact, dim3(1), dim3(KT), 0, s, A);
-        CKC(hipGetLastError());
-        launches++;
-        cur ^= 1;
-    }
+    CKC(klt_launch(k_klt_compact, 1, s, M.by_keep)); launches++;
     // 5. refill: the frame call's two passes with the painted mask; the selection takes its cap from the counts
     const GfttExt X = gftt_ext(p.gftt.block_size, p.gftt.use_harris, p.gftt.k);
-    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p.gftt.quality, p.gftt.min_dist, 0, &X, ctx->d_gfr_mask.get(), ctx->d_gfr_val,
-                          ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, D.ixy.d, D.cnt.d + C_M, D.cnt.d + C_STAT0, D.cnt.d + C_WANT));
+    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, 1, gftt_frame_grid_x(roi[2], roi[3]), cap, p.gftt.quality, p.gftt.min_dist, 0, &X, S.d_gfr_mask.get(), S.d_gfr_val,
+                          S.d_gfr_idx, S.d_gfr_info, S.d_gfr_keys, D.ixy.d, sh.m, sh.stat, sh.want));
     launches += 2;
     // 6. refine
     if (p.subpix) {
-        CKC(launch_corner_subpix_dev(s, ctx->d_slots, L, D.ixy.d, cur_slot, cap, D.cnt.d + C_M, ctx->d_subpix_tab, SA, D.sp_xy.d, D.sp_it.d, D.sp_fl.d));
+        CKC(launch_corner_subpix_dev(s, ctx->d_slots, L, D.ixy.d, cur_slot, cap, sh.m, ctx->d_subpix_tab, SA, D.sp_xy.d, D.sp_it.d, D.sp_fl.d));
         launches++;
     }
     // 7. append
-    if (++t->seq == 0) t->seq = 1;
-    O.hdr.h[9] = 0; O.hdr.h[10] = 0;
-    {
-        KltAppendArgs A{lst[cur], D.cnt.d, D.cnt.d + C_M, D.ixy.d, p.subpix ? D.sp_xy.d : nullptr, f_ran ? (const int*)(D.f_out.d + ESS_OUT_INFO) : nullptr, n0, t->next_id, cap, t->seq,
-                        D.s_id.d, D.s_age.d, D.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d, right ? D.cnt.d + C_NOUT : nullptr};
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_append, dim3(1), dim3(KT), 0, s, A);
-        CKC(hipGetLastError());
-        launches++;
-    }
+    CKC(klt_launch(k_klt_append, 1, s, M.append)); launches++;
     // 8. stereo: the new state from the current left frame into the right frame - `cap` workgroups, of which the device's count work (the LK
     // result arrays of stage 1 are free again) - then the rule, which ends the chain with its own completion word
     if (right) {
-        const bool sfb = t->st.fb_max_dist >= 0.0;
         CKC(launch_lk_ex_dev(s, ctx->d_slots + (size_t)cur_slot * L.slot_bytes, ctx->d_slots + (size_t)right->slot * L.slot_bytes, L, D.s_xy.d, D.cnt.d + C_NOUT, cap,
-                             sfb ? LKX_FB : 0, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
-        KltStereoArgs A{D.cnt.d + C_NOUT, cap, 1, sfb ? 1 : 0, t->st.border, L.w[0], L.h[0], t->st_thr2, D.s_xy.d, D.lk_xy.d, D.bk_xy.d, D.lk_st.d, D.bk_st.d, t->seq,
-                        O.hdr.d, O.right_xy.d, O.right_st.d};
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_stereo, dim3(1), dim3(KT), 0, s, A);
-        CKC(hipGetLastError());
+                             M.st_flags, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
+        CKC(klt_launch(k_klt_stereo, 1, s, M.stereo));
         launches += 2;
     }
     CKC(hipStreamSynchronize(s));
     waits++;
-    const int* hdr = O.hdr.h;
-    const int n = hdr[8], m = hdr[4];
-    REQ((unsigned)hdr[9] == t->seq && n >= 0 && n <= cap && m >= 0 && m <= n, PMV_ERR_HIP, "pmv_klt_step: the result block is incomplete (n = %d, m = %d)", n, m);
-    REQ(!right || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= n), PMV_ERR_HIP, "pmv_klt_step_stereo: the result block is incomplete (n = %d, matched = %d)", n, hdr[7]);
-    memcpy(out_ids, O.id.h, (size_t)n * 4);
-    memcpy(out_ages, O.age.h, (size_t)n * 4);
-    memcpy(out_xy, O.xy.h, (size_t)n * 8);
-    if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null, O.prev.h, (size_t)n * 8);
-    memcpy(out_counts8, hdr, 8 * sizeof(int));
-    *out_n = n;
-    if (right) {
-        memcpy(right->xy, O.right_xy.h, (size_t)n * 8);
-        memcpy(right->st, O.right_st.h, (size_t)n);
-    }
-    t->n = n; t->next_id += m;
-    ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask is this step's now)
-    if (right) { ctx->klt_stereo_stats[0]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
-    else { ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches; }
+    if (const int rc = klt_result_check(ctx, t, right != nullptr, "pmv_klt_step", -1)) return rc;
+    klt_result_copy(t, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_n, out_counts8, right);
+    klt_book(ctx, roi, 0, right != nullptr, waits, launches);
     return PMV_OK;
 }
 
@@ -797,32 +843,16 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
         if (const int rc = lk_check(ctx, true, cur_slots[j], right->slots[j], nullptr, 0, nullptr, nullptr, nullptr)) return klt_many_blame(ctx, rc, j, ids[j]);
         sum_st += T[j]->cap;
     }
-    tl_prof = &ctx->prof;
-    CKC(hipSetDevice(ctx->device));
+    tl_prof = &ctx->prof; CKC(hipSetDevice(ctx->device));
     const PyrLayout& L = ctx->slot_layout[cur_slots[0]];
-    const size_t n = (size_t)n_trk, pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3], mstride = (rpix + 3) & ~(size_t)3, lists = std::max(pix, n * rpix);
+    const size_t n = (size_t)n_trk, pix = (size_t)ctx->max_w * ctx->max_h, rpix = (size_t)roi[2] * roi[3], mstride = (rpix + 3) & ~(size_t)3;
     REQ(n * mstride + 64 <= 0xffffffffull, PMV_ERR_CAPACITY, "%s: the group's %d masks of %zu bytes do not fit a 32-bit offset", who, n_trk, rpix);
-    // the context's scratch of the refill and frame calls, one share per tracker
-    CKC(ctx->d_gfr_val.ensure(lists * sizeof(float))); CKC(ctx->d_gfr_idx.ensure(lists * sizeof(unsigned))); CKC(ctx->d_gfr_keys.ensure(lists * sizeof(unsigned long long)));
-    CKC(ctx->d_gfr_info.ensure(2 * n * sizeof(unsigned)));
-    CKC(ctx->d_gfr_mask.ensure(std::max(pix, n * mstride) + 64));
-    CKC(ctx->d_refill_kept.ensure(std::max((size_t)PMV_REFILL_MAX_TRACKS, sum_pad) * sizeof(unsigned))); CKC(ctx->d_refill_nkept.ensure(n * sizeof(int)));
+    // the context's scratch of the refill and frame calls, one share per tracker; records and results are the group's and the trackers'
+    FrameDetScratch& S = ctx->fds;
+    CKC(S.lists(std::max(pix, n * rpix), n)); CKC(S.masks(std::max(pix, n * mstride) + S.PAINT_SLACK, 0)); CKC(S.refill(std::max((size_t)PMV_REFILL_MAX_TRACKS, sum_pad), n));
     const pmv_klt_params& p = p0;
     SubpixArgs SA{};
-    if (p.subpix) {   // the weight table, as pmv_corner_subpix keeps it
-        const pmv_subpix_params* sp = &p.subpix_params;
-        CKC(ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float))); CKC(ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float)));
-        int zw, zh;
-        subpix_zero_zone(sp, &zw, &zh);
-        const int key[4] = {sp->win_w, sp->win_h, zw, zh};
-        if (memcmp(key, ctx->subpix_tab_key, sizeof(key)) != 0) {
-            CKC(hipStreamSynchronize(ctx->s_front));
-            subpix_table(sp->win_w, sp->win_h, zw, zh, ctx->h_subpix_tab);
-            CKC(hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * sp->win_w + 1) * (2 * sp->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front));
-            memcpy(ctx->subpix_tab_key, key, sizeof(key));
-        }
-        SA = SubpixArgs{sp->win_w, sp->win_h, sp->max_iter, sp->eps * sp->eps};
-    }
+    if (p.subpix) CKC(subpix_table_ready(ctx, &p.subpix_params, &SA));
     // the group's own blocks, grown to the largest group seen
     if (!ctx->klt_group) ctx->klt_group = new KltGroup();
     KltGroup* G = ctx->klt_group;
@@ -841,68 +871,47 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
     size_t lk_base = 0, pad_off = 0, st_base = 0;
     for (int j = 0; j < n_trk; j++) {
         KltTracker* t = T[j];
-        const pmv_klt_params& q = t->p;
-        const KltDev& TD = t->D; const KltRes& O = t->O;
-        const int cap = t->cap, n0 = t->n;
-        const bool fb = q.fb_max_dist >= 0.0;
-        R.rrec.h[j] = RefillRec{0, q.radius, (int)pad_off, roi[0], roi[1], roi[2], roi[3], (unsigned)((size_t)j * mstride), 0, {0, 0, 0}};
+        R.rrec.h[j] = RefillRec{0, t->p.radius, (int)pad_off, roi[0], roi[1], roi[2], roi[3], (unsigned)((size_t)j * mstride), 0, {0, 0, 0}};
         memcpy(R.hw.h + (size_t)j * REFILL_HW, t->R.hw.h, REFILL_HW);
         int* g = R.grec.h + (size_t)j * CELL_STRIDE;
         gftt_frame_record(g, roi, cur_slots[j], (size_t)j * rpix, nullptr, 0, nullptr, 0);
         g[5] = (int)(unsigned)((size_t)j * mstride);
         R.slots.h[j] = cur_slots[j];
-        if (++t->seq == 0) t->seq = 1;
-        O.hdr.h[9] = 0; O.hdr.h[10] = 0;
-        KltManyRec& M = R.rec.h[j];
-        memset(&M, 0, sizeof(M));
-        const KltRefillIn rf{D.pos.d + pad_off, D.prio.d + pad_off, D.flag.d + pad_off, R.rrec.d + j};
-        for (int k = 0; k < 2; k++) M.lst[k] = KltList{TD.l_id[k].d, TD.l_age[k].d, TD.l_prev[k].d, TD.l_cur[k].d};
-        M.filter = KltFilterArgs{n0, fb ? 1 : 0, q.border, L.w[0], L.h[0], t->thr2, TD.s_id.d, TD.s_age.d, TD.s_xy.d, D.lk_xy.d + 2 * lk_base, D.bk_xy.d + 2 * lk_base,
-                                 D.lk_st.d + lk_base, D.bk_st.d + lk_base, M.lst[0], rf, TD.cnt.d, O.n1.d};
-        M.by_f = KltCompactArgs{M.lst[0], M.lst[1], (const uint8_t*)(TD.f_out.d + ESS_OUT_HDR), TD.cnt.d + C_N1, cap, C_N2, 0, rf, TD.cnt.d, D.want.d + j};
-        M.by_keep = KltCompactArgs{M.lst[0], M.lst[1], D.keep.d + pad_off, TD.cnt.d + C_N2, cap, C_N3, cap, KltRefillIn{nullptr, nullptr, nullptr, nullptr}, TD.cnt.d, D.want.d + j};
-        M.append = KltAppendArgs{M.lst[0], TD.cnt.d, D.m.d + j, D.ixy.d + (size_t)2 * j * cap_max, q.subpix ? D.sp_xy.d + (size_t)2 * j * cap_max : nullptr, nullptr, n0, t->next_id, cap,
-                                 t->seq, TD.s_id.d, TD.s_age.d, TD.s_xy.d, O.hdr.d, O.id.d, O.age.d, O.xy.d, O.prev.d, right ? TD.cnt.d + C_NOUT : nullptr};
-        M.f_info = (const int*)(TD.f_out.d + ESS_OUT_INFO);
-        M.prev_off = (unsigned long long)(n0 > 0 ? prev_slots[j] : cur_slots[j]) * pitch; M.next_off = (unsigned long long)cur_slots[j] * pitch;
-        M.lk_base = (int)lk_base; M.lk_flags = fb ? LKX_FB : 0;
-        lk_base += (size_t)n0; pad_off += refill_pad(cap);
-        if (right) {   // stage 8: the tracker's share of the bound-sized launch; the LK result arrays of stage 1 are free again by then
-            const bool on = right->slots[j] >= 0, sfb = on && t->st.fb_max_dist >= 0.0;
-            M.stereo = KltStereoArgs{TD.cnt.d + C_NOUT, cap, on ? 1 : 0, sfb ? 1 : 0, t->st.border, L.w[0], L.h[0], t->st_thr2, TD.s_xy.d, D.lk_xy.d + 2 * st_base,
-                                     D.bk_xy.d + 2 * st_base, D.lk_st.d + st_base, D.bk_st.d + st_base, t->seq, O.hdr.d, O.right_xy.d, O.right_st.d};
-            M.right_off = (unsigned long long)(on ? right->slots[j] : cur_slots[j]) * pitch;
-            M.st_base = (int)st_base; M.st_flags = sfb ? LKX_FB : 0;
-            if (on) st_base += (size_t)cap;
+        // the stage arguments, from the tracker's shares of the group's tables
+        KltShares sh{};
+        sh.lk = KltLkOut{D.lk_xy.d + 2 * lk_base, D.bk_xy.d + 2 * lk_base, D.lk_st.d + lk_base, D.bk_st.d + lk_base};
+        sh.rf = KltRefillIn{D.pos.d + pad_off, D.prio.d + pad_off, D.flag.d + pad_off, R.rrec.d + j};
+        sh.keep = D.keep.d + pad_off; sh.want = D.want.d + j; sh.m = D.m.d + j; sh.stat = D.stat.d + 2 * j;
+        sh.ixy = D.ixy.d + (size_t)2 * j * cap_max; sh.sp_xy = D.sp_xy.d + (size_t)2 * j * cap_max;
+        sh.prev_off = (unsigned long long)(t->n > 0 ? prev_slots[j] : cur_slots[j]) * pitch; sh.next_off = (unsigned long long)cur_slots[j] * pitch;
+        sh.lk_base = (int)lk_base;
+        lk_base += (size_t)t->n; pad_off += refill_pad(t->cap);
+        if (right) {   // stage 8: the tracker's share of the bound-sized launch
+            const bool on = right->slots[j] >= 0;
+            sh.stereo = true; sh.right_on = on ? 1 : 0;
+            sh.st = KltLkOut{D.lk_xy.d + 2 * st_base, D.bk_xy.d + 2 * st_base, D.lk_st.d + st_base, D.bk_st.d + st_base};
+            sh.right_off = (unsigned long long)(on ? right->slots[j] : cur_slots[j]) * pitch;
+            sh.st_base = (int)st_base;
+            if (on) st_base += (size_t)t->cap;
         }
+        R.rec.h[j] = klt_stage_args(t, L, sh);
     }
     CKC(hipMemcpyAsync(G->d_rec, G->h_rec, R.front, hipMemcpyHostToDevice, s));
     // 1. track: the records are written on the device, where the positions are, and the whole group is one launch
     if (sum_n0 > 0) {
-        {
-            ProfScope ps(K_GFTT_PICK, s);
-            hipLaunchKernelGGL(k_klt_lk_records, dim3(n_trk), dim3(KT), 0, s, R.rec.d, D.lkb.d, D.lkx.d, sum_n0);
-            CKC(hipGetLastError());
-        }
+        CKC(klt_launch(k_klt_lk_records, n_trk, s, R.rec.d, D.lkb.d, D.lkx.d, sum_n0));
         CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx.d, sum_n0, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
                                D.bk_err.d));
         launches += 2;
     }
     // 2. filter
-    {
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_filter_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d);
-        CKC(hipGetLastError());
-        launches++;
-    }
+    CKC(klt_launch(k_klt_filter_many, n_trk, s, R.rec.d)); launches++;
     // 3. rejectWithF: the host reads every n1 (the iteration tables are libm's); one copy and one launch serve the trackers that have the stage
-    int cur = 0;
-    const int* f_run = nullptr;
+    int cur = 0; const int* f_run = nullptr;
     if (any_f) {
         CKC(hipStreamSynchronize(s));
         waits++;
-        int n_f = 0;
-        size_t tab = 0;
+        int n_f = 0; size_t tab = 0;
         for (int j = 0; j < n_trk; j++) {
             const KltTracker* t = T[j];
             R.f_run.h[j] = 0;
@@ -910,11 +919,7 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
             const int n1 = *t->O.n1.h;
             REQ(n1 >= 0 && n1 <= t->n, PMV_ERR_HIP, "%s: the filter left n1 = %d of %d tracks (tracker %d of the group)", who, n1, t->n, j);
             if (n1 < 15) continue;
-            FundamentalProblem P;
-            P.p1 = t->D.l_prev[0].d; P.p2 = t->D.l_cur[0].d; P.iters = R.ftab.d + tab; P.out = t->D.f_out.d;
-            P.n = n1; P.max_iters = 1000; P.thr = (float)(t->p.f_threshold * t->p.f_threshold); P.done_seq = 1;
-            R.fprob.h[n_f++] = P;
-            vo::ransac_iters_table(n1, t->p.f_confidence, 7, R.ftab.h + tab + 1, R.ftab.h + tab);
+            R.fprob.h[n_f++] = klt_f_problem(t, n1, R.ftab.h + tab, R.ftab.d + tab);
             tab += (size_t)n1 + 2;
             R.f_run.h[j] = 1;
         }
@@ -923,27 +928,18 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
             CKC(hipMemcpyAsync((char*)G->d_rec.p + b0, (const char*)G->h_rec.p + b0, b1 - b0, hipMemcpyHostToDevice, s));
             CKC(launch_fundamental_ransac(s, R.fprob.d, n_f));
             f_run = R.f_run.d;
-            ProfScope ps(K_GFTT_PICK, s);
-            hipLaunchKernelGGL(k_klt_compact_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, 0, 0, f_run);
-            CKC(hipGetLastError());
-            launches += 2;
-            cur = 1;
+            CKC(klt_launch(k_klt_compact_many, n_trk, s, R.rec.d, 0, 0, f_run));
+            launches += 2; cur = 1;
         }
     }
     // 4. thin
-    CKC(launch_track_refill(s, R.rrec.d, n_trk, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, ctx->d_refill_kept, ctx->d_refill_nkept, ctx->d_gfr_mask));
+    CKC(launch_track_refill(s, R.rrec.d, n_trk, rpix, D.pos.d, D.prio.d, D.flag.d, R.hw.d, D.keep.d, S.d_refill_kept, S.d_refill_nkept, S.d_gfr_mask));
     launches += 2;
-    {
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_compact_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, 1, cur, f_run);
-        CKC(hipGetLastError());
-        launches++;
-        cur ^= 1;
-    }
+    CKC(klt_launch(k_klt_compact_many, n_trk, s, R.rec.d, 1, cur, f_run)); launches++; cur ^= 1;
     // 5. refill: every tracker's selection takes its cap from its own word
     const GfttExt X = gftt_ext(p.gftt.block_size, p.gftt.use_harris, p.gftt.k);
-    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, n_trk, gftt_frame_grid_x(roi[2], roi[3]), cap_max, p.gftt.quality, p.gftt.min_dist, 0, &X, ctx->d_gfr_mask.get(),
-                          ctx->d_gfr_val, ctx->d_gfr_idx, ctx->d_gfr_info, ctx->d_gfr_keys, D.ixy.d, D.m.d, D.stat.d, D.want.d));
+    CKC(launch_gftt_frame(s, ctx->d_slots, L, R.grec.d, n_trk, gftt_frame_grid_x(roi[2], roi[3]), cap_max, p.gftt.quality, p.gftt.min_dist, 0, &X, S.d_gfr_mask.get(),
+                          S.d_gfr_val, S.d_gfr_idx, S.d_gfr_info, S.d_gfr_keys, D.ixy.d, D.m.d, D.stat.d, D.want.d));
     launches += 2;
     // 6. refine
     if (p.subpix) {
@@ -951,64 +947,29 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
         launches++;
     }
     // 7. append: every workgroup stores its tracker's completion word last
-    {
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_append_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d, cur, f_run);
-        CKC(hipGetLastError());
-        launches++;
-    }
+    CKC(klt_launch(k_klt_append_many, n_trk, s, R.rec.d, cur, f_run)); launches++;
     // 8. stereo: the records of every share from the lists and counts the append left, one LK launch over the sum of the bounds (a record
     // beyond its list's count is void), then the rule; every workgroup of it stores its tracker's stereo completion word last
     if (right) {
         if (sum_st > 0) {
-            {
-                ProfScope ps(K_GFTT_PICK, s);
-                hipLaunchKernelGGL(k_klt_stereo_records, dim3(n_trk), dim3(KT), 0, s, R.rec.d, D.lkb.d, D.lkx.d, sum_st);
-                CKC(hipGetLastError());
-            }
+            CKC(klt_launch(k_klt_stereo_records, n_trk, s, R.rec.d, D.lkb.d, D.lkx.d, sum_st));
             CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx.d, sum_st, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
                                    D.bk_err.d));
             launches += 2;
         }
-        ProfScope ps(K_GFTT_PICK, s);
-        hipLaunchKernelGGL(k_klt_stereo_many, dim3(n_trk), dim3(KT), 0, s, R.rec.d);
-        CKC(hipGetLastError());
-        launches++;
+        CKC(klt_launch(k_klt_stereo_many, n_trk, s, R.rec.d)); launches++;
     }
     CKC(hipStreamSynchronize(s));
     waits++;
+    for (int j = 0; j < n_trk; j++)
+        if (const int rc = klt_result_check(ctx, T[j], right != nullptr, who, j)) return rc;
     for (int j = 0; j < n_trk; j++) {
-        const KltTracker* t = T[j];
-        const int* hdr = t->O.hdr.h;
-        const int nn = hdr[8], m = hdr[4];
-        REQ((unsigned)hdr[9] == t->seq && nn >= 0 && nn <= t->cap && m >= 0 && m <= nn, PMV_ERR_HIP, "%s: the result block of tracker %d of the group is incomplete (n = %d, m = %d)",
-            who, j, nn, m);
-        REQ(!right || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= nn), PMV_ERR_HIP,
-            "pmv_klt_step_many_stereo: the result block of tracker %d of the group is incomplete (n = %d, matched = %d)", j, nn, hdr[7]);
-    }
-    for (int j = 0; j < n_trk; j++) {
-        KltTracker* t = T[j];
-        const KltRes& O = t->O;
-        const int* hdr = O.hdr.h;
-        const int nn = hdr[8], m = hdr[4];
         const size_t o = (size_t)j * out_stride;
-        memcpy(out_ids + o, O.id.h, (size_t)nn * 4);
-        memcpy(out_ages + o, O.age.h, (size_t)nn * 4);
-        memcpy(out_xy + 2 * o, O.xy.h, (size_t)nn * 8);
-        if (out_prev_xy_or_null) memcpy(out_prev_xy_or_null + 2 * o, O.prev.h, (size_t)nn * 8);
-        memcpy(out_counts8 + 8 * j, hdr, 8 * sizeof(int));
-        out_n[j] = nn;
-        if (right) {
-            if (right->slots[j] >= 0) {
-                memcpy(right->xy + 2 * o, O.right_xy.h, (size_t)nn * 8);
-                memcpy(right->st + o, O.right_st.h, (size_t)nn);
-            } else memset(right->st + o, 0, (size_t)nn);
-        }
-        t->n = nn; t->next_id += m;
+        const KltRightOut r{right ? right->slots[j] : -1, right ? right->xy + 2 * o : nullptr, right ? right->st + o : nullptr};
+        klt_result_copy(T[j], out_ids + o, out_ages + o, out_xy + 2 * o, out_prev_xy_or_null ? out_prev_xy_or_null + 2 * o : nullptr, out_n + j, out_counts8 + 8 * j,
+                        right ? &r : nullptr);
     }
-    ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];   // (the painted mask at the front is tracker 0's)
-    if (right) { ctx->klt_stereo_stats[1]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
-    else { ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches; }
+    klt_book(ctx, roi, n_trk, right != nullptr, waits, launches);
     return PMV_OK;
 }
 

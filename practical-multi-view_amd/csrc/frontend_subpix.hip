@@ -5,9 +5,10 @@
 // workgroup. The loop is wave-uniform: the position, the determinant and the stop tests are the same bits in every lane, so a corner that
 // converges leaves the loop as a whole wavefront and no workgroup barrier sits inside it. Nothing but the level-0 bytes is read from HBM
 // inside the loop, nothing is written before the end, and there are no atomics.
-#include "pmv_device.h"
+#include "pmv_ctx.h"
 #include "pmv_prof.h"
 #include <float.h>
+#include <string.h>
 
 namespace pmv {
 
@@ -184,6 +185,24 @@ void subpix_table(int win_w, int win_h, int zero_w, int zero_h, float* out) {
     if (zero_w >= 0 && zero_h >= 0 && 2 * zero_w + 1 < WW && 2 * zero_h + 1 < WH)
         for (int i = win_h - zero_h; i <= win_h + zero_h; i++)
             for (int j = win_w - zero_w; j <= win_w + zero_w; j++) out[i * WW + j] = 0.f;
+}
+
+// The context's weight table (d_subpix_tab) for p, and the launch arguments that go with it. The table is kept with the window and the
+// (effective) zero zone it was computed for: a caller keeps its parameters, so it crosses the bus once. On another key the front-end stream is
+// waited for first - the pinned mirror may still be on its way from the last change, and a launch in flight may still read the old table.
+hipError_t subpix_table_ready(pmv_ctx* ctx, const pmv_subpix_params* p, SubpixArgs* A) {
+    hipError_t e = ctx->h_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float));
+    if (!e) e = ctx->d_subpix_tab.ensure(SUBPIX_TABLE_MAX * sizeof(float));
+    int zw, zh;
+    subpix_zero_zone(p, &zw, &zh);
+    const int key[4] = {p->win_w, p->win_h, zw, zh};
+    *A = SubpixArgs{p->win_w, p->win_h, p->max_iter, p->eps * p->eps};
+    if (e != hipSuccess || memcmp(key, ctx->subpix_tab_key, sizeof(key)) == 0) return e;
+    if ((e = hipStreamSynchronize(ctx->s_front)) != hipSuccess) return e;
+    subpix_table(p->win_w, p->win_h, zw, zh, ctx->h_subpix_tab);
+    e = hipMemcpyAsync(ctx->d_subpix_tab, ctx->h_subpix_tab, (size_t)(2 * p->win_w + 1) * (2 * p->win_h + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->s_front);
+    if (e == hipSuccess) memcpy(ctx->subpix_tab_key, key, sizeof(key));
+    return e;
 }
 
 hipError_t launch_corner_subpix(hipStream_t s, const uint8_t* slots, const PyrLayout& L, const SubpixRec* d_recs, int n, const float* d_table, const SubpixArgs& A,

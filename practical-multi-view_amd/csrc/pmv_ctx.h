@@ -23,6 +23,44 @@ constexpr int MAX_PER_CELL = 4096;    // also the capacity of an "unlimited" (ma
 struct BackendBuffers;              // PnP / BA device workspaces (backend.hip)
 struct KltTracker;                  // a device-resident KLT tracker (frontend_klt.hip)
 struct KltGroup;                    // what a pmv_klt_step_many call keeps in the context (frontend_klt.hip)
+
+// The scratch of the launches that serve whole-frame detector requests (launch_gftt_frame) and the refill in front of them
+// (launch_track_refill): one per owner - the context for its single calls and its KLT steps (GROW_EXACT), the engine's detector combiner for
+// its rounds (GROW_SLACK). A launch serves n_req requests; every part is made by the first caller that asks for it and grown to the largest
+// launch seen. h_gfr, h_refill: the launch's gftt_frame_block and refill_block (mapped pinned, carved below). d_gfr_val, _idx: the record
+// lists (value, pixel index); _keys: the key list of the selection's slower path; _info: one (maximum, count) pair per request. d_gfr_mask:
+// the regions' packed masks, where the refill paints them and pass 1 reads them; h_gfr_mask: the host's mirror (`mirror`: pinned where a
+// copy call reads it, mapped in the engine, whose scratch is of one kind). d_refill_kept, _nkept: k_track_select's kept lists and counts.
+struct FrameDetScratch {
+    Buf<uint8_t> h_gfr, h_refill, d_gfr_mask, h_gfr_mask;
+    Buf<float> d_gfr_val; Buf<unsigned> d_gfr_idx, d_gfr_info, d_refill_kept; Buf<unsigned long long> d_gfr_keys; Buf<int> d_refill_nkept;
+    static constexpr size_t PAINT_SLACK = 64;   // asked for behind a painted mask's regions: a dword of the painting may end behind a region's last byte
+    static constexpr size_t BLOCK_SLACK = 64;   // behind a mapped block: the carvers align their parts
+    FrameDetScratch(MemGrow g, MemKind mirror) : h_gfr(MEM_MAPPED, g), h_refill(MEM_MAPPED, g), d_gfr_mask(MEM_DEVICE, g), h_gfr_mask(mirror, g), d_gfr_val(MEM_DEVICE, g),
+        d_gfr_idx(MEM_DEVICE, g), d_gfr_info(MEM_DEVICE, g), d_refill_kept(MEM_DEVICE, g), d_gfr_keys(MEM_DEVICE, g), d_refill_nkept(MEM_DEVICE, g) {}
+    // in front of launch_gftt_frame. entries: the pixels of the launch's regions - a flat positive plateau makes every pixel a record, so no
+    // smaller list is safe; the context passes at least max_w * max_h, so that its single calls allocate once. block_bytes: the bytes of the
+    // launch's gftt_frame_block, 0 when the caller keeps records and results in buffers of its own (the KLT steps).
+    hipError_t lists(size_t entries, size_t n_req, size_t block_bytes = 0) {
+        hipError_t e = block_bytes ? h_gfr.ensure(block_bytes + BLOCK_SLACK) : hipSuccess;
+        if (!e) e = d_gfr_val.ensure(entries * sizeof(float)); if (!e) e = d_gfr_idx.ensure(entries * sizeof(unsigned));
+        if (!e) e = d_gfr_keys.ensure(entries * sizeof(unsigned long long));
+        return e ? e : d_gfr_info.ensure(n_req * 2 * sizeof(unsigned));
+    }
+    // in front of a launch that reads a mask. device_bytes: the packed regions, uploaded or painted (then + PAINT_SLACK); host_mirror_bytes:
+    // what the caller packs on the host - 0 without a host mask, and a call without one makes no mirror
+    hipError_t masks(size_t device_bytes, size_t host_mirror_bytes) {
+        const hipError_t e = d_gfr_mask.ensure(device_bytes);
+        return e ? e : h_gfr_mask.ensure(host_mirror_bytes);
+    }
+    // in front of launch_track_refill. kept_entries: the track entries of the launch (the sum of the requests' refill_pad(n)); the context
+    // passes at least PMV_REFILL_MAX_TRACKS, the most a single request holds. block_bytes: of the launch's refill_block, as for lists().
+    hipError_t refill(size_t kept_entries, size_t n_req, size_t block_bytes = 0) {
+        hipError_t e = block_bytes ? h_refill.ensure(block_bytes + BLOCK_SLACK) : hipSuccess;
+        if (!e) e = d_refill_kept.ensure(kept_entries * sizeof(unsigned));
+        return e ? e : d_refill_nkept.ensure(n_req * sizeof(int));
+    }
+};
 }
 
 // In-memory log of the back-end plugin calls (pmv_record_*): every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates
@@ -87,23 +125,11 @@ struct pmv_ctx {
     // bytes under the cells cross the bus. MAX_CELLS * CELL_PIX bytes each, made by the first extended call with a mask.
     pmv::Buf<uint8_t> h_gmask{pmv::MEM_PINNED}, d_gmask;
     int gftt_general = 0;                // pmv_debug_gftt_general
-    // pmv_detect_gftt_frame, made by the first call (a context that never makes one pays nothing): the request's block in mapped pinned
-    // memory (gftt_frame_block at one request of PMV_GFTT_FRAME_MAX_CORNERS corners), the region's packed mask (pinned mirror and HBM copy)
-    // and, in HBM, the record list (value, pixel index), the key list of the selection's slower path and the (maximum, count) pair - the
-    // lists sized for max_w x max_h, since a flat positive plateau makes every pixel a record
-    pmv::Buf<uint8_t> h_gfr{pmv::MEM_MAPPED}, h_gfr_mask{pmv::MEM_PINNED}, d_gfr_mask;
-    pmv::Buf<float> d_gfr_val;
-    pmv::Buf<unsigned> d_gfr_idx, d_gfr_info;
-    pmv::Buf<unsigned long long> d_gfr_keys;
+    // pmv_detect_gftt_frame, pmv_detect_gftt_refill and stages 4 and 5 of the pmv_klt_step* calls: their scratch, rewritten by every call
+    pmv::FrameDetScratch fds{pmv::GROW_EXACT, pmv::MEM_PINNED};
     // pmv_debug_gftt_frame_stats: frame calls served by the single entry point | session rounds with a frame request | launch pairs made for
     // them | records above the threshold in the last request served | of those kept off-chip
     std::atomic<long long> gftt_frame_stats[5];
-    // pmv_detect_gftt_refill, made by the first call (a context that never makes one pays nothing): the request's tracks in mapped pinned
-    // memory (refill_block at one request of PMV_REFILL_MAX_TRACKS tracks) and, in HBM, the kept list with its count. The region's mask is
-    // painted into d_gfr_mask, where pass 1 of the frame call reads it; h_gfr_mask is touched only when the caller gives a base mask.
-    pmv::Buf<uint8_t> h_refill{pmv::MEM_MAPPED};
-    pmv::Buf<unsigned> d_refill_kept;
-    pmv::Buf<int> d_refill_nkept;
     int refill_last[2] = {0, 0};         // width and height of the region of the last single refill call (pmv_debug_refill_mask)
     // pmv_debug_refill_stats: single refill calls | session rounds with a refill request | select + paint launch pairs made for them | bytes of
     // mask copied host -> device by refill calls (base masks only)
@@ -238,6 +264,8 @@ int refill_check(pmv_ctx* ctx, const char* who, int slot, const float* track_xy,
 // pmv_corner_subpix / pmv_batch_corner_subpix: every check of the contract, in its order (`who` names the call in the messages)
 int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const float* xy, int n, const pmv_subpix_params* p);
 int subpix_params_check(pmv_ctx* ctx, const char* who, const pmv_subpix_params* p);   // its window, iteration and eps rules alone (p is not null)
+// the context's weight table made ready for p on the front-end stream, and *A the launch arguments for p (frontend_subpix.hip)
+hipError_t subpix_table_ready(pmv_ctx* ctx, const pmv_subpix_params* p, SubpixArgs* A);
 void klt_destroy_all(pmv_ctx* ctx);   // frees the trackers that are left (pmv_ctx_destroy, after the streams were synchronised)
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
 inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
