@@ -18,6 +18,8 @@
  *                                          in front of the pyramid; the reference tracks the plain gray image, Frame.cpp:40-41)
  *   pmv_frames_remap                       cv::remap(INTER_LINEAR, BORDER_CONSTANT) on level 0 of slots: the lens undistortion every camera but a
  *                                          rectified one needs in front of everything else (the reference takes K alone: a pinhole camera)
+ *   pmv_undistort_points                   cv::undistortPoints(src, dst, K, dist): the lift of tracked pixels onto the normalised image plane
+ *                                          (a VINS-style front end's liftProjective; also stage 9 of the tracker step, pmv_klt_set_observe)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -290,6 +292,43 @@ int pmv_debug_mem_live(long long* out2);
  * Errors: PMV_ERR_INVALID - a null K9, dist8, map_x or map_y, a singular newK R, w or h < 1. */
 int pmv_undistort_map_build(const double* K9, const double* dist8, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x,
                             float* map_y);
+
+/* ---- cameras and cv::undistortPoints: tracked pixels onto the normalised image plane -----------------------------------------------------
+ * A VINS-style tracker tracks in the raw image and lifts the few hundred points, not the frame. A camera object holds the intrinsics and the
+ * distortion coefficients of pmv_undistort_map_build's model; pmv_undistort_points is cv::undistortPoints(src CV_32FC2, dst, K, dist) with
+ * no R and no P, as a single call; the tracker step uses the same lift (pmv_klt_set_observe below).
+ * Result definition: for point i < n, (u, v) = xy[2 i .. 2 i + 1]; all arithmetic in double, IEEE + - * / only, without contraction, operand
+ *   order as written; ifx = 1.0 / fx and ify = 1.0 / fy are computed once on the host at pmv_camera_create and kept in the camera record:
+ *     x0 = ((double)u - cx) * ifx;  y0 = ((double)v - cy) * ify;  x = x0;  y = y0;
+ *     repeat iters times:
+ *         r2     = x*x + y*y
+ *         icdist = (1 + ((k6*r2 + k5)*r2 + k4)*r2) / (1 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *         dX     = 2*p1*x*y + p2*(r2 + 2*x*x)
+ *         dY     = p1*(r2 + 2*y*y) + 2*p2*x*y
+ *         x = (x0 - dX) * icdist;  y = (y0 - dY) * icdist
+ *   out_ok[i] = 1 iff x and y are finite after the last iteration and still finite after rounding to float; then out_xy[2 i .. 2 i + 1] =
+ *   ((float)x, (float)y). Otherwise out_ok[i] = 0 and out_xy = (0, 0): cv would return NaN, and the device's NaN bits are not the host's, so
+ *   no NaN is ever written. This is the fixed-point inverse of the forward model pmv_undistort_map_build states, as OpenCV 3.4's
+ *   undistortPoints iterates it (cv's default is iters = 5); parity with a real OpenCV is unpinned. The device equals the CPU restatement
+ *   tests/twin/lift_twin.cpp bit for bit.
+ * Device side: the cameras live in one small device table of the context, made by the first pmv_camera_create and released with the last
+ *   camera. pmv_undistort_points is one launch on the front-end stream (one lane per point, FP64, the camera record read as uniform loads)
+ *   and one wait; n == 0 is legal and launches nothing.
+ * Errors (nothing is written, nothing is clamped): PMV_ERR_INVALID - a null argument; fx or fy zero or not finite; any parameter not finite;
+ *   iters outside 1..50; an unknown camera id; a coordinate that is not finite or beyond 1e6 in magnitude (the message names the point);
+ *   destroying a camera that a tracker's observation setting names. PMV_ERR_CAPACITY - a 17th camera; n < 0 or n above max_tracks.
+ *   pmv_ctx_destroy frees the cameras that are left.
+ * Out of scope: cv::fisheye and other camera models; the R / P arguments of undistortPoints; thin-prism and tilt coefficients (not built: a
+ *   camera has the 8 coefficients below); the session form (pmv_batch_*); a forward distort_points call. */
+#define PMV_MAX_CAMERAS 16
+typedef struct pmv_camera_params {
+    double fx, fy, cx, cy;
+    double dist[8];         /* k1, k2, p1, p2, k3, k4, k5, k6: the order of pmv_undistort_map_build */
+    int    iters;           /* fixed-point iterations, 1 .. 50; cv's default is 5 */
+} pmv_camera_params;
+int pmv_camera_create(pmv_ctx* ctx, const pmv_camera_params* p, int* out_id);
+int pmv_camera_destroy(pmv_ctx* ctx, int id);
+int pmv_undistort_points(pmv_ctx* ctx, int cam_id, const float* xy, int n, float* out_xy, uint8_t* out_ok);
 
 /* ---- feature extraction ------------------------------------------------------------------------ */
 /* cells: n_cells * 4 ints (x0, y0, w, h), each <= 255x255, sub-views of the frame in `slot`.
@@ -757,7 +796,8 @@ int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3);
  *   slot, differing sizes, open bracket). pmv_ctx_destroy frees the trackers that are left. Not logged by pmv_record_enable; legal during
  *   a batch session under the caller's slot rule, like the other single calls.
  * Out of scope: the session form (pmv_batch_klt_*), a region or base mask, an initial-flow prediction, per-track radius, LMedS or 8-point
- *   for n1 < 15, undistorting points before F (callers with a lens remap the frames first), id wrap-around. */
+ *   for n1 < 15, undistorting points before F by a field of pmv_klt_params (the observation setting does it: undistorted_f of
+ *   pmv_klt_set_observe below), id wrap-around. */
 #define PMV_KLT_MAX_TRACKERS 16
 typedef struct pmv_klt_params {
     int    target;          /* MAX_CNT: tracks wanted after a step; 1 .. min(ctx max_tracks, PMV_REFILL_MAX_TRACKS) */
@@ -856,7 +896,8 @@ int pmv_debug_klt_many_stats(pmv_ctx* ctx, long long* out4);
  *   is PMV_ERR_HIP and n and next_id are not updated.
  * Counters: stereo calls do not move pmv_debug_klt_stats or pmv_debug_klt_many_stats; pmv_debug_klt_stereo_stats counts them.
  * Out of scope: the session form, a backward pass without the initial guess, a right frame of another size or pyramid depth, an epipolar
- *   band or a disparity prior, normalised coordinates and velocities, compacted right lists, right positions as tracker state. */
+ *   band or a disparity prior, compacted right lists, right positions as tracker state (normalised coordinates and velocities: the
+ *   observation setting below). */
 typedef struct pmv_klt_stereo_params {
     double fb_max_dist;     /* finite; < 0: no backward pass, else 0 .. 1e3 */
     int    border;          /* 0 .. 64 */
@@ -870,6 +911,63 @@ int pmv_klt_step_many_stereo(pmv_ctx* ctx, int n_trk, const int* ids, const int*
                              uint8_t* out_right_status, int out_stride, int* out_n /* n_trk */, int* out_counts8 /* 8 * n_trk */);
 /* diagnostic: out4 = {stereo steps, stereo many-calls, host waits inside both, kernel launches inside both} since the context was created */
 int pmv_debug_klt_stereo_stats(pmv_ctx* ctx, long long* out4);
+
+/* ---- Normalised observations and velocities from the tracker step: the lift as stage 9 -------------------------------------------------------
+ * A VIO or VO back end consumes, per track, (id, x, y, 1, u, v, vx, vy): the position on the normalised image plane through the camera's
+ * distortion model and its velocity there; a stereo back end also the normalised right observation. A tracker with an observation setting
+ * returns them from the same step call, with at most one launch more and no additional wait, and can run stage 3 on undistorted points as
+ * FeatureTracker::rejectWithF does. The setting is off by default; with it off every step form makes the launches, waits and bytes it
+ * makes without this section. No step entry point gets a new signature: pmv_klt_step, pmv_klt_step_stereo, pmv_klt_step_many and
+ * pmv_klt_step_many_stereo stay as they are, and the observations are read afterwards with pmv_klt_get_observations.
+ * pmv_klt_set_observe gives a tracker its setting (NULL turns it off; it may change between steps, dt for example; a bad value keeps the old
+ *   setting); pmv_klt_get_observe reads it (*out_on = 0 / 1; *out = the last setting given, zeros if none). In a group the cameras, dt and on /
+ *   off may differ from tracker to tracker.
+ * Result definition of stage 9: a pure function of what the step returns - (ages, xy, prev_xy, n) and in a stereo call (right_xy,
+ *   right_status) - with lift = pmv_undistort_points' rule for one point (result (0, 0) and ok 0 where it refuses). For i < n:
+ *     (un, ok) = lift(cam_id, xy[i]); (pun, pok) = lift(cam_id, prev_xy[i]); out_un_xy[i] = un; out_ok[i] = ok.
+ *     ages[i] > 1 && ok && pok: vel.x = (float)((double)(un.x - pun.x) / dt), vel.y likewise - the subtraction is one float32 operation on
+ *       the lifts already rounded to float32 (VINS keeps them as Point2f), the division is in double. Otherwise vel = (0, 0): a new track,
+ *       whose prev_xy is its own xy, has no velocity. Lifting prev_xy again gives the bits of the previous step's un (the same function of
+ *       the same float), so no per-track state is added.
+ *     In a stereo call with right_cam_id >= 0 and, in the many form, right_slots[j] >= 0: (run, rok) = lift(right_cam_id, right_xy[i]);
+ *       out_right_un_xy[i] = run; out_right_ok[i] = right_status[i] && rok - unmatched tracks are lifted too and get ok 0. Otherwise
+ *       out_right_ok is all 0 and the right xy are not written.
+ *   The step's own outputs and the tracker's state are byte for byte those of the same step with the setting off.
+ * pmv_klt_get_observations copies the observations of the tracker's last step out of its result block - a host copy, no device work;
+ *   *out_n = n of that step; the two right arrays may be NULL. PMV_ERR_INVALID if the tracker's last step ran with the setting off, or if it
+ *   has not stepped since pmv_klt_create or pmv_klt_set_tracks (the message says which); PMV_ERR_CAPACITY for cap < n.
+ * rejectWithF on undistorted points (undistorted_f = 1): stage 3, which still runs only for reject_f and n1 >= 15, takes as its two point
+ *   sets the virtual-camera points of VINS instead of the pixels. For survivor i and both its previous and its current position, with
+ *   (xd, yd) the double pair of the lift BEFORE its rounding to float and w, h the frame size:
+ *     q = ((float)(f_focal * xd + w / 2.0), (float)(f_focal * yd + h / 2.0)), the product and the sum separate double operations.
+ *   If either of the track's two lifts is not finite, both of its points are (0, 0); it goes or stays by F's mask like any other.
+ *   pmv_find_fundamental_mat's arithmetic on those float points, f_threshold, the mask, the compaction and counts8[5..6] are unchanged.
+ * Device side: the observe kernel is the last of the chain (behind the append, or behind stage 8) and writes its own completion word, which
+ *   the host checks only for trackers with the setting on: an incomplete block is PMV_ERR_HIP and n and next_id are not updated. One
+ *   workgroup per tracker; a many-call makes one observe launch whatever n_trk is, and a tracker of the group with the setting off leaves at
+ *   once. The lift for stage 3 is one more launch, sized by n0 and enqueued before the host's wait for n1, so it runs under that wait; its
+ *   scratch is the LK result arrays of stage 1, free by then. pmv_debug_klt_observe_stats counts; the other klt counters count these
+ *   launches with the rest of the call's.
+ * Errors (nothing is written, the old setting is kept): PMV_ERR_INVALID - a null argument, an unknown tracker, a cam_id that is no camera,
+ *   a right_cam_id that is neither -1 nor a camera, dt not finite or not above 0, undistorted_f other than 0 / 1, with undistorted_f a
+ *   f_focal not finite or not above 0. A camera named by a setting cannot be destroyed until the setting is cleared.
+ * Out of scope: right-camera velocities (they need right positions as tracker state, which the stereo section excludes); the session form
+ *   (pmv_batch_*); an undistorted_f that lifts through a camera other than cam_id; cv::fisheye and other camera models, R / P, thin-prism
+ *   and tilt coefficients and a forward distort_points call, as for pmv_undistort_points. */
+typedef struct pmv_klt_observe_params {
+    int    cam_id;          /* the left camera */
+    int    right_cam_id;    /* the right camera, or -1: no normalised right observations */
+    double dt;              /* seconds between the previous and this frame; finite, > 0 */
+    int    undistorted_f;   /* 0 / 1: stage 3 runs on lifted points */
+    double f_focal;         /* the virtual focal length of that stage (VINS: 460); finite, > 0; read only if undistorted_f */
+} pmv_klt_observe_params;
+int pmv_klt_set_observe(pmv_ctx* ctx, int id, const pmv_klt_observe_params* p_or_null);   /* NULL: off (the default) */
+int pmv_klt_get_observe(pmv_ctx* ctx, int id, pmv_klt_observe_params* out, int* out_on);
+int pmv_klt_get_observations(pmv_ctx* ctx, int id, float* out_un_xy, float* out_vel, uint8_t* out_ok, float* out_right_un_xy_or_null,
+                             uint8_t* out_right_ok_or_null, int cap, int* out_n);
+/* diagnostic: out4 = {step calls with the setting on, observe launches, lift-for-F launches, host waits inside those calls} since the context
+ * was created */
+int pmv_debug_klt_observe_stats(pmv_ctx* ctx, long long* out4);
 
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those

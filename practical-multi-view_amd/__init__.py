@@ -74,6 +74,28 @@ class KltStereoParams(C.Structure):
     _fields_ = [("fb_max_dist", C.c_double), ("border", C.c_int)]
 
 
+class CameraParams(C.Structure):
+    """pmv_camera_params of include/pmv_hip.h"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8), ("iters", C.c_int)]
+
+
+def camera_params(fx, fy, cx, cy, dist=(), iters=5):
+    """a CameraParams from keywords; dist: up to 8 coefficients (k1, k2, p1, p2, k3, k4, k5, k6), the missing ones 0"""
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if d.size > 8:
+        raise ValueError(f"camera_params: at most 8 distortion coefficients (k1, k2, p1, p2, k3, k4, k5, k6), got {d.size}")
+    p = CameraParams(float(fx), float(fy), float(cx), float(cy))
+    for k, v in enumerate(d):
+        p.dist[k] = float(v)
+    p.iters = int(iters)
+    return p
+
+
+class KltObserveParams(C.Structure):
+    """pmv_klt_observe_params of include/pmv_hip.h"""
+    _fields_ = [("cam_id", C.c_int), ("right_cam_id", C.c_int), ("dt", C.c_double), ("undistorted_f", C.c_int), ("f_focal", C.c_double)]
+
+
 class KltTracker:
     """A tracker of Context.klt_create. The state - ids, ages, positions - lives in device memory; step() returns the new list."""
 
@@ -128,6 +150,39 @@ class KltTracker:
                    _p(rst, _u8p), cap, C.byref(n), _p(counts, _i32p)))
         k = n.value
         return ids[:k].copy(), ages[:k].copy(), xy[:k].copy(), prev[:k].copy(), counts, rxy[:k].copy(), rst[:k].copy()
+
+    def set_observe(self, cam_id, right_cam_id=-1, dt=1.0, undistorted_f=False, f_focal=460.0):
+        """pmv_klt_set_observe: the setting of stage 9 - the left camera (Context.camera_create), the right camera or -1, the seconds between
+        the previous and this frame - and of stage 3 on undistorted points (undistorted_f, f_focal). cam_id=None turns the setting off."""
+        fn = self.ctx.lib.pmv_klt_set_observe
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(KltObserveParams)]
+        if cam_id is None:
+            self.ctx._ck(fn(self.ctx.h, self.id, None))
+            return
+        p = KltObserveParams(int(cam_id), int(right_cam_id), float(dt), int(undistorted_f), float(f_focal))
+        self.ctx._ck(fn(self.ctx.h, self.id, C.byref(p)))
+
+    def get_observe(self):
+        """pmv_klt_get_observe: dict(cam_id, right_cam_id, dt, undistorted_f, f_focal) of the observation setting, or None when it is off"""
+        p, on = KltObserveParams(), C.c_int(0)
+        fn = self.ctx.lib.pmv_klt_get_observe
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(KltObserveParams), C.POINTER(C.c_int)]
+        self.ctx._ck(fn(self.ctx.h, self.id, C.byref(p), C.byref(on)))
+        return dict(cam_id=p.cam_id, right_cam_id=p.right_cam_id, dt=p.dt, undistorted_f=bool(p.undistorted_f), f_focal=p.f_focal) if on.value else None
+
+    def get_observations(self):
+        """pmv_klt_get_observations, after a step with the observation setting on: (un_xy (n, 2) float32 - the list's positions on the
+        normalised image plane, vel (n, 2) float32 - their velocities there, ok (n,) uint8, right_un_xy (n, 2) float32, right_ok (n,) uint8);
+        without right observations in that step right_ok is all 0 and right_un_xy zeros"""
+        cap = self.target
+        un, vel, run = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        ok, rok = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        n = C.c_int(0)
+        fn = self.ctx.lib.pmv_klt_get_observations
+        fn.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _u8p, _f32p, _u8p, C.c_int, C.POINTER(C.c_int)]
+        self.ctx._ck(fn(self.ctx.h, self.id, _p(un, _f32p), _p(vel, _f32p), _p(ok, _u8p), _p(run, _f32p), _p(rok, _u8p), cap, C.byref(n)))
+        k = n.value
+        return un[:k].copy(), vel[:k].copy(), ok[:k].copy(), run[:k].copy(), rok[:k].copy()
 
     def set_tracks(self, ids, ages, xy, next_id):
         """pmv_klt_set_tracks: replace the state"""
@@ -307,6 +362,8 @@ ABI_SYMBOLS = [
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
+    "pmv_camera_create", "pmv_camera_destroy", "pmv_undistort_points",
+    "pmv_klt_set_observe", "pmv_klt_get_observe", "pmv_klt_get_observations", "pmv_debug_klt_observe_stats",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -1276,6 +1333,40 @@ class Context:
         self.lib.pmv_debug_klt_stereo_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         self._ck(self.lib.pmv_debug_klt_stereo_stats(self.h, out))
         return [int(v) for v in out]
+
+    def debug_klt_observe_stats(self):
+        """pmv_debug_klt_observe_stats: [step calls with the observation setting on, observe launches, lift-for-F launches, host waits inside
+        those calls]"""
+        out = (C.c_longlong * 4)()
+        self.lib.pmv_debug_klt_observe_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self._ck(self.lib.pmv_debug_klt_observe_stats(self.h, out))
+        return [int(v) for v in out]
+
+    def camera_create(self, **params):
+        """pmv_camera_create: the id of a camera of this context. Keywords: camera_params()'s (fx, fy, cx, cy, dist, iters)."""
+        p = camera_params(**params)
+        out = C.c_int(-1)
+        self.lib.pmv_camera_create.argtypes = [C.c_void_p, C.POINTER(CameraParams), C.POINTER(C.c_int)]
+        self._ck(self.lib.pmv_camera_create(self.h, C.byref(p), C.byref(out)))
+        return out.value
+
+    def camera_destroy(self, cam_id):
+        self.lib.pmv_camera_destroy.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.lib.pmv_camera_destroy(self.h, int(cam_id)))
+
+    def undistort_points(self, cam_id, xy):
+        """pmv_undistort_points: cv::undistortPoints(xy, K, dist) through camera cam_id - (un_xy (n, 2) float32 on the normalised image plane,
+        ok (n,) uint8; a point whose lift is not finite has ok 0 and un_xy (0, 0))"""
+        xy = np.ascontiguousarray(xy, np.float32)
+        if xy.size and (xy.ndim != 2 or xy.shape[1] != 2):
+            raise ValueError("undistort_points: xy must be an (n, 2) float32 array")
+        n = xy.size // 2
+        out, ok = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        src = xy if n else np.zeros((1, 2), np.float32)
+        fn = self.lib.pmv_undistort_points
+        fn.argtypes = [C.c_void_p, C.c_int, _f32p, C.c_int, _f32p, _u8p]
+        self._ck(fn(self.h, int(cam_id), _p(src, _f32p), n, _p(out, _f32p), _p(ok, _u8p)))
+        return out[:n].copy(), ok[:n].copy()
 
     def debug_klt_many_stats(self):
         """pmv_debug_klt_many_stats: [many-calls, trackers stepped by them, host waits inside them, kernel launches inside them]"""

@@ -145,6 +145,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->klt_stats) a.store(0);
     for (auto& a : c->klt_many_stats) a.store(0);
     for (auto& a : c->klt_stereo_stats) a.store(0);
+    for (auto& a : c->klt_observe_stats) a.store(0);
     int rc = backend_create(c);
     if (rc != PMV_OK) { snprintf(g_create_err, sizeof(g_create_err), "%s", c->err); pmv_ctx_destroy(c); return rc; }
 #undef CK

@@ -15,7 +15,13 @@
 // pmv_klt_step_stereo / pmv_klt_step_many_stereo append a stage 8 behind the append and in front of the final wait: LK from the current left
 // into the right frame for the list the step returns, in a launch sized by the bound (target) whose workgroups read the list's length from
 // device memory, then one workgroup per tracker that applies stage 2's rule to the result and ends the chain with its own completion word.
+// A tracker with an observation setting (pmv_klt_set_observe) gets a stage 9 behind that: one workgroup per tracker lifts the list the step
+// returns onto the normalised image plane (lift_point, pmv_lift.h), forms the velocities and lifts the right observations of a stereo call,
+// and ends the chain with a third completion word; with undistorted_f one more launch, enqueued under the wait for n1, writes stage 3's two
+// point sets as virtual-camera points into the LK result arrays of stage 1, which are free by then. A step with the setting off makes
+// neither launch and reads none of this.
 #include "pmv_ctx.h"
+#include "pmv_lift.h"
 #include "backend.h"
 #include "vo_pipeline.h"
 #include <cmath>
@@ -221,6 +227,80 @@ __global__ __launch_bounds__(KT) void k_klt_stereo(KltStereoArgs A) {
     klt_stereo(A, s_w);
 }
 
+// Stage 9 (pmv_klt_set_observe): the list after the append - ages and xy are the state, the previous position of a survivor lies in the list
+// the append read, a new track (age 1, at and beyond n3) has none - lifted through the tracker's camera; the velocity is the float32 difference of
+// the two rounded lifts over dt, divided in double. right: a stereo call whose tracker has a right camera and a right frame - stage 8's
+// positions (S.fwd) are lifted through the right camera and stage 8's rule is asked again for the status. Everything goes to the result
+// block; the observe completion word (header word 11) is the last store of the chain.
+struct KltObserveArgs {
+    int on, cap, right;
+    const int* cnt;                 // C_N3 and the append's C_NOUT
+    const int* age; const float* xy; const float* prev;
+    const LiftCam* cam; const LiftCam* rcam;
+    double dt;
+    unsigned seq;
+    int* r_hdr; float* r_un; float* r_vel; uint8_t* r_ok; float* r_run; uint8_t* r_rok;
+};
+__device__ __forceinline__ void klt_observe(const KltObserveArgs& A, const KltStereoArgs& S) {
+    const int n = klt_clamp(A.cnt[C_NOUT], A.cap), n3 = klt_clamp(A.cnt[C_N3], n);
+    const LiftCam cam = *A.cam;
+    for (int i = threadIdx.x; i < n; i += KT) {
+        float ux, uy, vx = 0.f, vy = 0.f;
+        const bool ok = lift_point_f(cam, A.xy[2 * i], A.xy[2 * i + 1], &ux, &uy);
+        if (i < n3 && A.age[i] > 1 && ok) {
+            float px, py;
+            if (lift_point_f(cam, A.prev[2 * i], A.prev[2 * i + 1], &px, &py)) {
+                vx = (float)((double)__fsub_rn(ux, px) / A.dt); vy = (float)((double)__fsub_rn(uy, py) / A.dt);
+            }
+        }
+        A.r_un[2 * i] = ux; A.r_un[2 * i + 1] = uy; A.r_ok[i] = ok ? 1 : 0;
+        A.r_vel[2 * i] = vx; A.r_vel[2 * i + 1] = vy;
+    }
+    if (A.right) {
+        const LiftCam rcam = *A.rcam;
+        for (int i = threadIdx.x; i < n; i += KT) {
+            float rx, ry;
+            const bool rok = lift_point_f(rcam, S.fwd[2 * i], S.fwd[2 * i + 1], &rx, &ry);
+            A.r_run[2 * i] = rx; A.r_run[2 * i + 1] = ry;
+            A.r_rok[i] = klt_track_ok(S, i) && rok ? 1 : 0;
+        }
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store((unsigned*)(A.r_hdr + 11), A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__global__ __launch_bounds__(KT) void k_klt_observe(KltObserveArgs A, KltStereoArgs S) {
+    BACKEND_PRIO();
+    klt_observe(A, S);
+}
+
+// Stage 3 on undistorted points (the observation setting's undistorted_f): for the n1 survivors the filter left in list 0, previous and
+// current position as points of the virtual camera, q = ((float)(f xd + w / 2), (float)(f yd + h / 2)) of the lift's doubles (product and
+// sum separate double operations; hw = w / 2.0, hh = h / 2.0 from the host); a track with a lift that is not finite gets (0, 0) twice. One
+// lane per survivor; the launch is sized by n0 (= cap, which also bounds p1 and p2) and reads n1 from the counts.
+struct KltLiftFArgs {
+    int on, cap;
+    const int* n1;
+    const float* prev; const float* cur;
+    const LiftCam* cam;
+    double f, hw, hh;
+    float* p1; float* p2;
+};
+__device__ __forceinline__ void klt_lift_f(const KltLiftFArgs& A, int chunk) {
+    const int n1 = klt_clamp(*A.n1, A.cap), i = chunk * KT + (int)threadIdx.x;
+    if (i >= n1) return;
+    const LiftCam cam = *A.cam;
+    double ax, ay, bx, by;
+    const bool oka = lift_point(cam, A.prev[2 * i], A.prev[2 * i + 1], &ax, &ay), okb = lift_point(cam, A.cur[2 * i], A.cur[2 * i + 1], &bx, &by);
+    const bool ok = oka && okb;
+    A.p1[2 * i] = ok ? (float)(A.f * ax + A.hw) : 0.f; A.p1[2 * i + 1] = ok ? (float)(A.f * ay + A.hh) : 0.f;
+    A.p2[2 * i] = ok ? (float)(A.f * bx + A.hw) : 0.f; A.p2[2 * i + 1] = ok ? (float)(A.f * by + A.hh) : 0.f;
+}
+__global__ __launch_bounds__(KT) void k_klt_lift_f(KltLiftFArgs A) {
+    BACKEND_PRIO();
+    klt_lift_f(A, blockIdx.x);
+}
+
 // ---- pmv_klt_step_many: the same three stages as a grid over the trackers of a group ----------------------------------------------------
 // blockIdx.x selects the tracker's argument record in device memory, which holds what the Klt*Args hold; one workgroup serves one tracker and
 // no workgroup waits for another. What the host learns only after the first wait does not change the records: `cur` (which of the two lists
@@ -239,6 +319,10 @@ struct KltManyRec {
     KltStereoArgs stereo;
     unsigned long long right_off;
     int st_base, st_flags;
+    // a tracker with an observation setting (observe.on): stage 9's arguments (prev: set by the kernel from lst[cur]) and, with
+    // undistorted_f in a call that may run the tracker's F stage (lift_f.on), those of the lift in front of stage 3
+    KltObserveArgs observe;
+    KltLiftFArgs lift_f;
 };
 // LK's records for the whole group, written where the tracks are: block lk_base + i tracks state position i of its tracker (geometry entry 0
 // of the call's own one-entry table). The host sized the shares from the n0 it holds; `total` = their sum bounds every store.
@@ -275,6 +359,22 @@ __global__ __launch_bounds__(KT) void k_klt_stereo_many(const KltManyRec* __rest
     BACKEND_PRIO();
     const KltStereoArgs A = recs[blockIdx.x].stereo;
     klt_stereo(A, s_w);
+}
+// gx workgroups per tracker: workgroup b serves chunk b % gx of tracker b / gx
+__global__ __launch_bounds__(KT) void k_klt_lift_f_many(const KltManyRec* __restrict__ recs, int gx) {
+    BACKEND_PRIO();
+    const KltLiftFArgs A = recs[blockIdx.x / gx].lift_f;
+    if (!A.on) return;
+    klt_lift_f(A, blockIdx.x % gx);
+}
+__global__ __launch_bounds__(KT) void k_klt_observe_many(const KltManyRec* __restrict__ recs, int cur) {
+    BACKEND_PRIO();
+    const KltManyRec& R = recs[blockIdx.x];
+    KltObserveArgs A = R.observe;
+    if (!A.on) return;
+    A.prev = R.lst[cur & 1].prev;
+    const KltStereoArgs S = R.stereo;
+    klt_observe(A, S);
 }
 __global__ __launch_bounds__(KT) void k_klt_filter_many(const KltManyRec* __restrict__ recs) {
     __shared__ unsigned s_w[KW];
@@ -339,14 +439,21 @@ KltRecs klt_rec_block(Carve& c, size_t cap) {
     R.fprob = c.take<char>(ESS_HDR, 64); R.ftab = c.take<double>(cap + 2, 16);
     return R;
 }
-// result block (mapped pinned): n1's word | header (counts8, out_n, completion word, stereo completion word) | ids | ages | xy | prev xy |
-// right xy | right status (the last two are written by stereo steps only)
-struct KltRes { Carved<int> n1, hdr, id, age; Carved<float> xy, prev, right_xy; Carved<uint8_t> right_st; };
+// result block (mapped pinned): n1's word | header (counts8, out_n, completion word, stereo completion word, observe completion word) | ids |
+// ages | xy | prev xy | right xy | right status (the last two are written by stereo steps only) | normalised xy | velocities | lift ok |
+// normalised right xy | right observation ok (the last five are written by stage 9 only, the last two of them in stereo calls only; a
+// tracker in a group has the same block: the group keeps no result block of its own)
+struct KltRes {
+    Carved<int> n1, hdr, id, age; Carved<float> xy, prev, right_xy; Carved<uint8_t> right_st;
+    Carved<float> un_xy, vel; Carved<uint8_t> un_ok; Carved<float> right_un; Carved<uint8_t> right_un_ok;
+};
 KltRes klt_res_block(Carve& c, size_t cap) {
     KltRes R;
     R.n1 = c.take<int>(16, 64); R.hdr = c.take<int>(16, 64);
     R.id = c.take<int>(cap, 16); R.age = c.take<int>(cap, 16); R.xy = c.take<float>(2 * cap, 16); R.prev = c.take<float>(2 * cap, 16);
     R.right_xy = c.take<float>(2 * cap, 16); R.right_st = c.take<uint8_t>(cap, 16);
+    R.un_xy = c.take<float>(2 * cap, 16); R.vel = c.take<float>(2 * cap, 16); R.un_ok = c.take<uint8_t>(cap, 16);
+    R.right_un = c.take<float>(2 * cap, 16); R.right_un_ok = c.take<uint8_t>(cap, 16);
     return R;
 }
 
@@ -360,6 +467,13 @@ struct KltTracker {
     bool st_on = false;             // pmv_klt_set_stereo: the setting of stage 8 and its thr2
     pmv_klt_stereo_params st{};
     float st_thr2 = 0.f;
+    bool obs_on = false;            // pmv_klt_set_observe: the setting of stage 9 and the device table entries of its cameras
+    pmv_klt_observe_params obs{};
+    const LiftCam* obs_cam = nullptr; const LiftCam* obs_rcam = nullptr;
+    // what pmv_klt_get_observations finds: 0 no step since pmv_klt_create / pmv_klt_set_tracks, 1 the last step ran with the setting off,
+    // 2 with it on - then obs_right says whether that step wrote right observations (armed: of the chain in flight)
+    int obs_state = 0;
+    bool obs_right = false, obs_right_armed = false;
     Buf<uint8_t> d_mem, d_rec, h_rec{MEM_PINNED}, h_res{MEM_MAPPED};
     KltDev D; KltRecs R; KltRes O;
 };
@@ -407,6 +521,13 @@ KltGroupDev klt_group_dev(Carve& c, size_t n, size_t sum, size_t pad, size_t cap
 struct KltGroup {
     Buf<uint8_t> d_rec, h_rec{MEM_PINNED}, d_mem;
 };
+
+bool klt_camera_in_use(pmv_ctx* ctx, int cam_id) {
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    for (const auto* t : ctx->klt)
+        if (t && t->obs_on && (t->obs.cam_id == cam_id || t->obs.right_cam_id == cam_id)) return true;
+    return false;
+}
 
 void klt_destroy_all(pmv_ctx* ctx) {
     for (auto& t : ctx->klt) { delete t; t = nullptr; }
@@ -507,7 +628,7 @@ int pmv_klt_set_tracks(pmv_ctx* ctx, int id, const int* ids, const int* ages, co
         CKC(hipMemcpy(t->D.s_age.d, ages, (size_t)n * 4, hipMemcpyHostToDevice));
         CKC(hipMemcpy(t->D.s_xy.d, xy, (size_t)n * 8, hipMemcpyHostToDevice));
     }
-    t->n = n; t->next_id = next_id;
+    t->n = n; t->next_id = next_id; t->obs_state = 0;
     return PMV_OK;
 }
 
@@ -545,7 +666,7 @@ struct KltShares {
 };
 // THE description of what the stage kernels of tracker t are given in its next chain, which begins here: the completion words are armed
 // before anything is launched. The many-call stores the record in its block, the single step passes its members as kernel arguments.
-// by_keep.in / out and append.in are written for list 0 and append.f_info is null: which list holds the tracks and whether F ran is known
+// by_keep.in / out, append.in and observe.prev are written for list 0 and append.f_info is null: which list holds the tracks and whether F ran is known
 // after stage 3 - k_klt_compact_many and k_klt_append_many patch them on the device, klt_step_run on the host.
 static KltManyRec klt_stage_args(KltTracker* t, const PyrLayout& L, const KltShares& sh) {
     if (++t->seq == 0) t->seq = 1;
@@ -580,6 +701,22 @@ static KltManyRec klt_stage_args(KltTracker* t, const PyrLayout& L, const KltSha
         S.seq = t->seq; S.r_hdr = O.hdr.d; S.r_rxy = O.right_xy.d; S.r_rst = O.right_st.d;
         M.right_off = sh.right_off; M.st_base = sh.st_base; M.st_flags = sfb ? LKX_FB : 0;
     }
+    if (t->obs_on) {
+        t->O.hdr.h[11] = 0;
+        A.n_out = cnt + C_NOUT;
+        KltObserveArgs& V = M.observe;
+        V.on = 1; V.cap = t->cap; V.right = sh.stereo && sh.right_on && t->obs_rcam ? 1 : 0;
+        V.cnt = cnt; V.age = D.s_age.d; V.xy = D.s_xy.d; V.prev = M.lst[0].prev;
+        V.cam = t->obs_cam; V.rcam = t->obs_rcam; V.dt = t->obs.dt; V.seq = t->seq;
+        V.r_hdr = O.hdr.d; V.r_un = O.un_xy.d; V.r_vel = O.vel.d; V.r_ok = O.un_ok.d; V.r_run = O.right_un.d; V.r_rok = O.right_un_ok.d;
+        t->obs_right_armed = V.right != 0;
+        if (t->obs.undistorted_f && p.reject_f && t->n >= 15) {   // the F stage may run: its points are written under the wait for n1
+            KltLiftFArgs& Q = M.lift_f;
+            Q.on = 1; Q.cap = t->n; Q.n1 = cnt + C_N1; Q.prev = D.l_prev[0].d; Q.cur = D.l_cur[0].d; Q.cam = t->obs_cam;
+            Q.f = t->obs.f_focal; Q.hw = L.w[0] / 2.0; Q.hh = L.h[0] / 2.0;
+            Q.p1 = sh.lk.xy; Q.p2 = sh.lk.bk_xy;   // stage 1's results are consumed by the filter; a share holds 2 n0 floats each
+        }
+    }
     return M;
 }
 // one launch of a glue kernel (KT threads per workgroup), booked under the detector's selection class
@@ -588,10 +725,11 @@ template <class... P, class... A> static hipError_t klt_launch(void (*kernel)(P.
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(KT), 0, s, args...);
     return hipGetLastError();
 }
-// rejectWithF's problem for the n1 tracks the filter left in the tracker's list 0, and libm's iteration table (n1 + 2 doubles) at tab_h
-static FundamentalProblem klt_f_problem(const KltTracker* t, int n1, double* tab_h, const double* tab_d) {
+// rejectWithF's problem for the n1 tracks the filter left in the tracker's list 0 - their pixels, or with Q.on the virtual-camera points
+// k_klt_lift_f wrote - and libm's iteration table (n1 + 2 doubles) at tab_h
+static FundamentalProblem klt_f_problem(const KltTracker* t, const KltLiftFArgs& Q, int n1, double* tab_h, const double* tab_d) {
     FundamentalProblem P;
-    P.p1 = t->D.l_prev[0].d; P.p2 = t->D.l_cur[0].d; P.iters = tab_d; P.out = t->D.f_out.d;
+    P.p1 = Q.on ? Q.p1 : t->D.l_prev[0].d; P.p2 = Q.on ? Q.p2 : t->D.l_cur[0].d; P.iters = tab_d; P.out = t->D.f_out.d;
     P.n = n1; P.max_iters = 1000; P.thr = (float)(t->p.f_threshold * t->p.f_threshold); P.done_seq = 1;
     vo::ransac_iters_table(n1, t->p.f_confidence, 7, tab_h + 1, tab_h);
     return P;
@@ -605,6 +743,7 @@ static int klt_result_check(pmv_ctx* ctx, const KltTracker* t, bool stereo, cons
     REQ((unsigned)hdr[9] == t->seq && n >= 0 && n <= t->cap && m >= 0 && m <= n, PMV_ERR_HIP, "%s: the result block%s is incomplete (n = %d, m = %d)", who, of, n, m);
     REQ(!stereo || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= n), PMV_ERR_HIP, "%s_stereo: the result block%s is incomplete (n = %d, matched = %d)", who, of, n,
         hdr[7]);
+    REQ(!t->obs_on || (unsigned)hdr[11] == t->seq, PMV_ERR_HIP, "%s: the observations of the result block%s are incomplete (n = %d)", who, of, n);
     return PMV_OK;
 }
 // ... and the copy-out of a checked block to the caller's arrays, which begin at the tracker's place; the state's length and next id follow
@@ -624,11 +763,14 @@ static void klt_result_copy(KltTracker* t, int* ids, int* ages, float* xy, float
         memcpy(right->st, O.right_st.h, (size_t)n);
     } else if (right) memset(right->st, 0, (size_t)n);
     t->n = n; t->next_id += m;
+    t->obs_state = t->obs_on ? 2 : 1; t->obs_right = t->obs_on && t->obs_right_armed;
 }
 // the closing statistics of a step (n_trk = 0) or of a many-call on n_trk trackers; the mask at the front of the scratch is now the region's
 // of this call (a group's: tracker 0's)
-static void klt_book(pmv_ctx* ctx, const int* roi, int n_trk, bool stereo, long long waits, long long launches) {
+struct KltObserveBook { bool on; int observe, lift; };   // a tracker of the call has an observation setting | the launches made for stage 9 | for stage 3
+static void klt_book(pmv_ctx* ctx, const int* roi, int n_trk, bool stereo, long long waits, long long launches, const KltObserveBook& ob) {
     ctx->refill_last[0] = roi[2]; ctx->refill_last[1] = roi[3];
+    if (ob.on) { ctx->klt_observe_stats[0]++; ctx->klt_observe_stats[1] += ob.observe; ctx->klt_observe_stats[2] += ob.lift; ctx->klt_observe_stats[3] += waits; }
     if (stereo) { ctx->klt_stereo_stats[n_trk ? 1 : 0]++; ctx->klt_stereo_stats[2] += waits; ctx->klt_stereo_stats[3] += launches; }
     else if (n_trk) { ctx->klt_many_stats[0]++; ctx->klt_many_stats[1] += n_trk; ctx->klt_many_stats[2] += waits; ctx->klt_many_stats[3] += launches; }
     else { ctx->klt_stats[0]++; ctx->klt_stats[1] += waits; ctx->klt_stats[2] += launches; }
@@ -685,15 +827,18 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
     }
     // 2. filter
     CKC(klt_launch(k_klt_filter, 1, s, M.filter)); launches++;
-    // 3. rejectWithF: the host reads n1 (the iteration table is libm's) and sends the table with the launches of the second half
+    // 3. rejectWithF: the host reads n1 (the iteration table is libm's) and sends the table with the launches of the second half; with
+    // undistorted_f the lift of the survivors runs under that wait
+    KltObserveBook ob{t->obs_on, 0, 0};
     int cur = 0; bool f_ran = false;
     if (p.reject_f && n0 >= 15) {
+        if (M.lift_f.on) { CKC(klt_launch(k_klt_lift_f, (n0 + KT - 1) / KT, s, M.lift_f)); launches++; ob.lift++; }
         CKC(hipStreamSynchronize(s));
         waits++;
         const int n1 = *O.n1.h;
         REQ(n1 >= 0 && n1 <= n0, PMV_ERR_HIP, "pmv_klt_step: the filter left n1 = %d of %d tracks", n1, n0);
         if (n1 >= 15) {
-            const FundamentalProblem P = klt_f_problem(t, n1, R.ftab.h, R.ftab.d);
+            const FundamentalProblem P = klt_f_problem(t, M.lift_f, n1, R.ftab.h, R.ftab.d);
             memset(R.fprob.h, 0, ESS_HDR);
             memcpy(R.fprob.h, &P, sizeof(P));
             const size_t fbytes = (size_t)((const char*)(R.ftab.h + n1 + 2) - R.fprob.h);
@@ -731,11 +876,16 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
         CKC(klt_launch(k_klt_stereo, 1, s, M.stereo));
         launches += 2;
     }
+    // 9. observe: the lifts and velocities of the list the step returns; then this kernel ends the chain
+    if (M.observe.on) {
+        M.observe.prev = M.lst[cur ^ 1].prev;
+        CKC(klt_launch(k_klt_observe, 1, s, M.observe, M.stereo)); launches++; ob.observe++;
+    }
     CKC(hipStreamSynchronize(s));
     waits++;
     if (const int rc = klt_result_check(ctx, t, right != nullptr, "pmv_klt_step", -1)) return rc;
     klt_result_copy(t, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_n, out_counts8, right);
-    klt_book(ctx, roi, 0, right != nullptr, waits, launches);
+    klt_book(ctx, roi, 0, right != nullptr, waits, launches, ob);
     return PMV_OK;
 }
 
@@ -819,8 +969,12 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
     int roi[4] = {0, 0, 0, 0}, sum_cap = 0, sum_n0 = 0;
     size_t sum_pad = 0;
     bool any_f = false;
+    KltObserveBook ob{false, 0, 0};
+    int lift_n0 = 0;   // the largest n0 among the trackers whose F stage takes lifted points
     for (int j = 0; j < n_trk; j++) {
         const KltTracker* t = T[j];
+        ob.on = ob.on || t->obs_on;
+        if (t->obs_on && t->obs.undistorted_f && t->p.reject_f && t->n >= 15) lift_n0 = std::max(lift_n0, t->n);
         int r[4], gcap;
         if (t->n > 0)
             if (const int rc = lk_check(ctx, true, prev_slots[j], cur_slots[j], out_xy, t->n, out_xy, (const uint8_t*)out_ids, out_xy)) return klt_many_blame(ctx, rc, j, ids[j]);
@@ -909,6 +1063,10 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
     // 3. rejectWithF: the host reads every n1 (the iteration tables are libm's); one copy and one launch serve the trackers that have the stage
     int cur = 0; const int* f_run = nullptr;
     if (any_f) {
+        if (lift_n0 > 0) {
+            const int gx = (lift_n0 + KT - 1) / KT;
+            CKC(klt_launch(k_klt_lift_f_many, n_trk * gx, s, R.rec.d, gx)); launches++; ob.lift++;
+        }
         CKC(hipStreamSynchronize(s));
         waits++;
         int n_f = 0; size_t tab = 0;
@@ -919,7 +1077,7 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
             const int n1 = *t->O.n1.h;
             REQ(n1 >= 0 && n1 <= t->n, PMV_ERR_HIP, "%s: the filter left n1 = %d of %d tracks (tracker %d of the group)", who, n1, t->n, j);
             if (n1 < 15) continue;
-            R.fprob.h[n_f++] = klt_f_problem(t, n1, R.ftab.h + tab, R.ftab.d + tab);
+            R.fprob.h[n_f++] = klt_f_problem(t, R.rec.h[j].lift_f, n1, R.ftab.h + tab, R.ftab.d + tab);
             tab += (size_t)n1 + 2;
             R.f_run.h[j] = 1;
         }
@@ -959,6 +1117,8 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
         }
         CKC(klt_launch(k_klt_stereo_many, n_trk, s, R.rec.d)); launches++;
     }
+    // 9. observe: one workgroup per tracker; those of the trackers with the setting store their observe completion word last
+    if (ob.on) { CKC(klt_launch(k_klt_observe_many, n_trk, s, R.rec.d, cur)); launches++; ob.observe++; }
     CKC(hipStreamSynchronize(s));
     waits++;
     for (int j = 0; j < n_trk; j++)
@@ -969,7 +1129,7 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
         klt_result_copy(T[j], out_ids + o, out_ages + o, out_xy + 2 * o, out_prev_xy_or_null ? out_prev_xy_or_null + 2 * o : nullptr, out_n + j, out_counts8 + 8 * j,
                         right ? &r : nullptr);
     }
-    klt_book(ctx, roi, n_trk, right != nullptr, waits, launches);
+    klt_book(ctx, roi, n_trk, right != nullptr, waits, launches, ob);
     return PMV_OK;
 }
 
@@ -984,6 +1144,61 @@ int pmv_klt_step_many_stereo(pmv_ctx* ctx, int n_trk, const int* ids, const int*
                              float* out_xy, float* out_prev_xy_or_null, float* out_right_xy, uint8_t* out_right_status, int out_stride, int* out_n, int* out_counts8) {
     const KltRightManyOut right{right_slots, out_right_xy, out_right_status};
     return klt_step_many_run(ctx, n_trk, ids, prev_slots, cur_slots, out_ids, out_ages, out_xy, out_prev_xy_or_null, out_stride, out_n, out_counts8, &right);
+}
+
+int pmv_klt_set_observe(pmv_ctx* ctx, int id, const pmv_klt_observe_params* p_or_null) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_set_observe: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_set_observe", id, &t)) return rc;
+    if (!p_or_null) { t->obs_on = false; return PMV_OK; }
+    const pmv_klt_observe_params& p = *p_or_null;
+    const LiftCam* cam = camera_entry(ctx, p.cam_id);
+    REQ(cam, PMV_ERR_INVALID, "pmv_klt_set_observe: cam_id = %d: the camera does not exist (pmv_camera_create)", p.cam_id);
+    const LiftCam* rcam = p.right_cam_id == -1 ? nullptr : camera_entry(ctx, p.right_cam_id);
+    REQ(p.right_cam_id == -1 || rcam, PMV_ERR_INVALID, "pmv_klt_set_observe: right_cam_id = %d is neither -1 nor a camera (pmv_camera_create)", p.right_cam_id);
+    REQ(std::isfinite(p.dt) && p.dt > 0.0, PMV_ERR_INVALID, "pmv_klt_set_observe: dt = %g is not finite or not above 0", p.dt);
+    REQ(p.undistorted_f == 0 || p.undistorted_f == 1, PMV_ERR_INVALID, "pmv_klt_set_observe: undistorted_f = %d is neither 0 nor 1", p.undistorted_f);
+    REQ(!p.undistorted_f || (std::isfinite(p.f_focal) && p.f_focal > 0.0), PMV_ERR_INVALID, "pmv_klt_set_observe: f_focal = %g is not finite or not above 0", p.f_focal);
+    t->obs = p; t->obs_on = true; t->obs_cam = cam; t->obs_rcam = rcam;
+    return PMV_OK;
+}
+
+int pmv_klt_get_observe(pmv_ctx* ctx, int id, pmv_klt_observe_params* out, int* out_on) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_get_observe: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_get_observe", id, &t)) return rc;
+    REQ(out && out_on, PMV_ERR_INVALID, "pmv_klt_get_observe: null argument");
+    *out = t->obs; *out_on = t->obs_on ? 1 : 0;
+    return PMV_OK;
+}
+
+// a host copy out of the tracker's result block: no device work
+int pmv_klt_get_observations(pmv_ctx* ctx, int id, float* out_un_xy, float* out_vel, uint8_t* out_ok, float* out_right_un_xy_or_null, uint8_t* out_right_ok_or_null, int cap,
+                             int* out_n) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_get_observations: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_get_observations", id, &t)) return rc;
+    REQ(out_un_xy && out_vel && out_ok && out_n, PMV_ERR_INVALID, "pmv_klt_get_observations: null argument");
+    REQ(t->obs_state != 0, PMV_ERR_INVALID, "pmv_klt_get_observations: tracker %d has not stepped since pmv_klt_create or pmv_klt_set_tracks", id);
+    REQ(t->obs_state == 2, PMV_ERR_INVALID, "pmv_klt_get_observations: the last step of tracker %d ran with the observation setting off (pmv_klt_set_observe)", id);
+    const int n = t->n;
+    REQ(cap >= n, PMV_ERR_CAPACITY, "pmv_klt_get_observations: cap = %d is below the %d tracks of the last step", cap, n);
+    const KltRes& O = t->O;
+    memcpy(out_un_xy, O.un_xy.h, (size_t)n * 8);
+    memcpy(out_vel, O.vel.h, (size_t)n * 8);
+    memcpy(out_ok, O.un_ok.h, (size_t)n);
+    if (t->obs_right) {
+        if (out_right_un_xy_or_null) memcpy(out_right_un_xy_or_null, O.right_un.h, (size_t)n * 8);
+        if (out_right_ok_or_null) memcpy(out_right_ok_or_null, O.right_un_ok.h, (size_t)n);
+    } else if (out_right_ok_or_null) memset(out_right_ok_or_null, 0, (size_t)n);
+    *out_n = n;
+    return PMV_OK;
+}
+
+int pmv_debug_klt_observe_stats(pmv_ctx* ctx, long long* out4) {
+    REQ(ctx && out4, PMV_ERR_INVALID, "pmv_debug_klt_observe_stats: null argument");
+    for (int i = 0; i < 4; i++) out4[i] = ctx->klt_observe_stats[i].load();
+    return PMV_OK;
 }
 
 int pmv_debug_klt_stereo_stats(pmv_ctx* ctx, long long* out4) {

@@ -5,6 +5,7 @@
 #include "pmv_mem.h"
 #include "pmv_block.h"
 #include "pmv_prof.h"
+#include "pmv_lift.h"
 #include "../../include/pmv_hip.h"
 #include <algorithm>
 #include <utility>
@@ -176,6 +177,17 @@ struct pmv_ctx {
     // pmv_debug_klt_stereo_stats: stereo steps | stereo many-calls | host waits inside both | kernel launches inside both (the counters above
     // do not move for stereo calls)
     std::atomic<long long> klt_stereo_stats[4];
+    // pmv_debug_klt_observe_stats: step calls (of any form) in which a tracker's observation setting was on | k_klt_observe[_many] launches |
+    // k_klt_lift_f[_many] launches | host waits inside those calls
+    std::atomic<long long> klt_observe_stats[4];
+    // pmv_camera_create (frontend_lift.hip): at most PMV_MAX_CAMERAS cameras, id = index; d_cams is their device table (LiftCam entries),
+    // made by the first create and released with the last camera, like h_lift, the mapped pinned block of pmv_undistort_points [points |
+    // lifted points | ok bytes], max_tracks of each, made by the first such call. cam_mu guards the table.
+    bool cam_used[PMV_MAX_CAMERAS] = {};
+    pmv_camera_params cam_params[PMV_MAX_CAMERAS] = {};
+    pmv::Buf<pmv::LiftCam> d_cams;
+    pmv::Buf<uint8_t> h_lift{pmv::MEM_MAPPED};
+    std::mutex cam_mu;
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
     pmv::BackendBuffers* be_ahead = nullptr;
@@ -266,6 +278,8 @@ int subpix_check(pmv_ctx* ctx, const char* who, bool bracket, int slot, const fl
 int subpix_params_check(pmv_ctx* ctx, const char* who, const pmv_subpix_params* p);   // its window, iteration and eps rules alone (p is not null)
 // the context's weight table made ready for p on the front-end stream, and *A the launch arguments for p (frontend_subpix.hip)
 hipError_t subpix_table_ready(pmv_ctx* ctx, const pmv_subpix_params* p, SubpixArgs* A);
+const LiftCam* camera_entry(pmv_ctx* ctx, int id);   // the device table entry of camera `id`, or null when there is none (frontend_lift.hip)
+bool klt_camera_in_use(pmv_ctx* ctx, int cam_id);    // a tracker's observation setting names the camera (frontend_klt.hip)
 void klt_destroy_all(pmv_ctx* ctx);   // frees the trackers that are left (pmv_ctx_destroy, after the streams were synchronised)
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
 inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {
