@@ -20,6 +20,8 @@
  *                                          rectified one needs in front of everything else (the reference takes K alone: a pinhole camera)
  *   pmv_undistort_points                   cv::undistortPoints(src, dst, K, dist): the lift of tracked pixels onto the normalised image plane
  *                                          (a VINS-style front end's liftProjective; also stage 9 of the tracker step, pmv_klt_set_observe)
+ *   pmv_project_points                     cv::projectPoints without rvec / tvec: points of the camera frame onto the image (a VINS-style
+ *                                          front end's spaceToPlane: where known landmarks should appear, as LK's initial flow)
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -319,7 +321,8 @@ int pmv_undistort_map_build(const double* K9, const double* dist8, const double*
  *   destroying a camera that a tracker's observation setting names. PMV_ERR_CAPACITY - a 17th camera; n < 0 or n above max_tracks.
  *   pmv_ctx_destroy frees the cameras that are left.
  * Out of scope: cv::fisheye and other camera models; the R / P arguments of undistortPoints; thin-prism and tilt coefficients (not built: a
- *   camera has the 8 coefficients below); the session form (pmv_batch_*); a forward distort_points call. */
+ *   camera has the 8 coefficients below); the session form (pmv_batch_*); a forward distort_points call on normalised points (the forward
+ *   model as a call is pmv_project_points below, from points of the camera frame). */
 #define PMV_MAX_CAMERAS 16
 typedef struct pmv_camera_params {
     double fx, fy, cx, cy;
@@ -329,6 +332,26 @@ typedef struct pmv_camera_params {
 int pmv_camera_create(pmv_ctx* ctx, const pmv_camera_params* p, int* out_id);
 int pmv_camera_destroy(pmv_ctx* ctx, int id);
 int pmv_undistort_points(pmv_ctx* ctx, int cam_id, const float* xy, int n, float* out_xy, uint8_t* out_ok);
+/* ---- cv::projectPoints without rvec and tvec: points of the camera frame onto the image ---------------------------------------------------
+ * The forward direction of the lift above, through the same camera object: where a landmark the back end knows should appear in the next
+ * frame (VINS: setPrediction / spaceToPlane). The pixels are meant as the initial flow of pmv_lk_track_ex / pmv_lk_track_fb_levels.
+ * Result definition: for point i < n, (X, Y, Z) = xyz[3 i .. 3 i + 2] in the camera frame; all arithmetic in double, IEEE + - * / only, without
+ *   contraction, operand order as written; fx and fy are the caller's own values (not 1 / ifx):
+ *     x = X / Z;  y = Y / Z;  r2 = x*x + y*y
+ *     kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *     xd = x*kr + (2*p1*x*y + p2*(r2 + 2*x*x));  yd = y*kr + (p1*(r2 + 2*y*y) + 2*p2*x*y)
+ *     u = fx*xd + cx;  v = fy*yd + cy
+ *   out_ok[i] = 1 iff X, Y and Z are finite, Z > 0, u and v are finite before and after their rounding to float, and |(float)u|, |(float)v| <=
+ *   1e6 (the bound pmv_lk_track_ex puts on an initial flow); then out_xy[2 i .. 2 i + 1] = ((float)u, (float)v). Otherwise out_ok[i] = 0 and
+ *   out_xy = (0, 0); no NaN is ever written. The pixel may lie outside the frame: that is the tracker's business. [mem: cv::projectPoints;
+ *   parity with a real OpenCV is unpinned, like the lift.] The device equals the CPU restatement tests/twin/project_twin.cpp bit for bit.
+ * Device side: one launch on the front-end stream (one lane per point, FP64, the camera record read as uniform loads) and one wait; n == 0 is
+ *   legal and launches nothing. The call's block is made by the first call and released with the last camera.
+ * Errors (nothing is written): PMV_ERR_INVALID - a null argument, an unknown camera id. PMV_ERR_CAPACITY - n < 0 or n above max_tracks. A
+ *   coordinate of any value, NaN and infinities included, is no error: the point comes back with ok 0.
+ * Out of scope: rvec / tvec (transform the points first), the Jacobian output, cv::fisheye and other camera models, thin-prism and tilt
+ *   coefficients, the session form. */
+int pmv_project_points(pmv_ctx* ctx, int cam_id, const double* xyz /* 3 n, camera frame */, int n, float* out_xy, uint8_t* out_ok);
 
 /* ---- feature extraction ------------------------------------------------------------------------ */
 /* cells: n_cells * 4 ints (x0, y0, w, h), each <= 255x255, sub-views of the frame in `slot`.
@@ -608,6 +631,25 @@ int pmv_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* pre
  * a track counts once. */
 int pmv_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
                     uint8_t* out_status, float* out_err, float* back_xy, uint8_t* back_status, float* back_err);
+/* cv's maxLevel as a per-call argument on pyramids that are already built: pmv_lk_track_fb, except that the forward pass starts at level
+ * min(fwd_top_level, L - 1) and the backward pass at level min(back_top_level, L - 1), L = the slots' level count (pmv_frame_num_levels + 1).
+ * Levels 0 .. top of a pyramid are the same images whatever depth was built, so a pass is cv::calcOpticalFlowPyrLK with maxLevel = min(top,
+ * the context's max_level) on the same frames; max_level of pmv_set_lk_params stays the depth that is BUILT, and no slot is emptied. The use:
+ * a guess that is already close (a landmark projected with pmv_project_points, a back check that starts at the known position) needs the
+ * upper levels no more - VINS tracks predicted points and runs its reverse check on two levels (top = 1) instead of four.
+ *   -1 means L - 1: with (-1, -1) every output holds the bytes of pmv_lk_track_fb.
+ *   All three back outputs NULL: the call is forward only and returns the bytes of pmv_lk_track_ex at that level (back_top_level is
+ *     checked, then ignored). One or two of them NULL: PMV_ERR_INVALID.
+ *   Errors (nothing is written): those of pmv_lk_track_fb; PMV_ERR_INVALID - a level outside -1 .. 4. Nothing is clamped except by L.
+ *   Device side: the same ONE launch of the extended kernels (k_lk_ex, both forms) and one wait; the level is a workgroup-uniform launch
+ *     argument of the two device functions behind their EX template parameter, so k_lk, k_lk_batch and the two general plain kernels are
+ *     the code they were. pmv_lk_counters counts the level passes that ran.
+ *   The CPU yardstick is the existing twin, tests/twin/lkx_twin.cpp, with max_level = min(top, the context's max_level).
+ *   Out of scope: the session form (pmv_batch_*), a per-track level. Inside the tracker step the levels are capped only by a pending
+ *     prediction (pmv_klt_set_prediction); stereo stage 8 walks every level of the slot. */
+int pmv_lk_track_fb_levels(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy /* in/out */, int flags,
+                           int fwd_top_level, int back_top_level, uint8_t* out_status, float* out_err,
+                           float* back_xy_or_null, uint8_t* back_status_or_null, float* back_err_or_null);
 /* diagnostic: on != 0 sends the default window (32) through the general kernels as well, so that a test can compare the two code paths.
  * It changes no result. */
 int pmv_debug_lk_general(pmv_ctx* ctx, int on);
@@ -795,7 +837,8 @@ int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3);
  *   PMV_REFILL_MAX_TRACKS), a 17th tracker, out_cap < target; the slot errors of pmv_lk_track and pmv_detect_gftt_frame (range, empty
  *   slot, differing sizes, open bracket). pmv_ctx_destroy frees the trackers that are left. Not logged by pmv_record_enable; legal during
  *   a batch session under the caller's slot rule, like the other single calls.
- * Out of scope: the session form (pmv_batch_klt_*), a region or base mask, an initial-flow prediction, per-track radius, LMedS or 8-point
+ * Out of scope: the session form (pmv_batch_klt_*), a region or base mask, an initial-flow prediction as a field of pmv_klt_params (it is a
+ *   one-shot setting of its own: pmv_klt_set_prediction below), per-track radius, LMedS or 8-point
  *   for n1 < 15, undistorting points before F by a field of pmv_klt_params (the observation setting does it: undistorted_f of
  *   pmv_klt_set_observe below), id wrap-around. */
 #define PMV_KLT_MAX_TRACKERS 16
@@ -839,7 +882,8 @@ int pmv_debug_klt_stats(pmv_ctx* ctx, long long* out4);
  *   host updates n and next_id of the trackers only after the last wait, once every tracker's result block is complete; an incomplete
  *   block is PMV_ERR_HIP and updates nothing.
  * Device side: the launches and waits of a call do not depend on n_trk - at most 12 launches (a step's chain plus one kernel that writes
- *   LK's records in device memory from the trackers' states, so no position crosses the bus on the way in) and at most two waits, one when no
+ *   LK's records in device memory from the trackers' states, so no position crosses the bus on the way in; one more, LK's gated second
+ *   launch, in a call in which a tracker has a pending prediction: pmv_klt_set_prediction below) and at most two waits, one when no
  *   tracker of the group has reject_f = 1 and 15 tracks. The first wait reads the n_trk words n1; the F problems and iteration tables of
  *   the trackers with n1 >= 15 go up in one copy and run in one launch, the others pass their list through. The filter, the two
  *   compactions and the append run one workgroup per tracker on per-tracker argument records; the detector's record lists, the painted
@@ -968,6 +1012,50 @@ int pmv_klt_get_observations(pmv_ctx* ctx, int id, float* out_un_xy, float* out_
 /* diagnostic: out4 = {step calls with the setting on, observe launches, lift-for-F launches, host waits inside those calls} since the context
  * was created */
 int pmv_debug_klt_observe_stats(pmv_ctx* ctx, long long* out4);
+
+/* ---- Predicted positions in the tracker step: projected guesses, capped LK levels ---------------------------------------------------------
+ * When the back end has a pose and landmarks, a VINS-style front end projects them into the new image (setPrediction, spaceToPlane), runs
+ * LK from those guesses on two pyramid levels instead of four, falls back to the full pyramid only if fewer than 10 points succeed, and
+ * always runs its reverse check on two levels (FeatureTracker::trackImage, hasPrediction). pmv_klt_set_prediction gives a tracker such a
+ * prediction: points in the camera frame of the NEW image, keyed by track id. It is one-shot: the tracker's next step that succeeds,
+ * through any of the four step entry points, consumes it; a refused step leaves it pending; NULL or n = 0 clears it; pmv_klt_set_tracks
+ * leaves it pending (the join is by id). No step entry point gets a new signature, and a tracker with no pending prediction makes the
+ * launches, waits and bytes it makes without this section.
+ * Result definition of a consuming step: only stage 1 changes; stages 2 to 9 are untouched. For track i of the state (n0 tracks, positions xy):
+ *     guess[i] = pmv_project_points(cam_id, xyz[k]) if ids[k] equals the track's id and that projection is ok, else xy[i];
+ *     joined   = the number of tracks of the first kind;
+ *     A        = the outputs of pmv_lk_track_fb_levels(prev_slot, cur_slot, xy, next_xy = guess, PMV_LK_USE_INITIAL_FLOW, top_level,
+ *                back_top_level, ..), forward only (three null back outputs) when the tracker's fb_max_dist < 0;
+ *     succ     = the number of i with A's forward status equal to 1;
+ *     succ < min_succ: A = the outputs of pmv_lk_track_fb_levels(.., flags 0, -1, back_top_level, ..) and fell_back = 1.
+ *   Stage 2 filters A exactly as it filters stage 1's outputs in any other step. With n0 = 0 the prediction is consumed with {1, 0, 0, 0}.
+ *   out_counts8 keeps its meaning, and all eight words are taken. pmv_klt_get_prediction_result returns {consumed, joined, succ, fell_back}
+ *   of the tracker's last step - a host copy; {0, 0, 0, 0} after a step that had no prediction to consume and before the first step.
+ *   Ids that no track has, and tracks without an entry, are no error; the order of the list changes nothing. A point of any value is
+ *   legal: one that pmv_project_points refuses (not finite, Z <= 0, beyond 1e6) simply predicts nothing.
+ * Device side: no additional wait; at most 2 more launches in a single step and at most 2 more in a many-call, whatever n_trk is (a single
+ *   step makes 2 more, a many-call 1). The join and projection kernel runs one workgroup per tracker (k_klt_predict; in a group it is folded
+ *   into the kernel that writes LK's records): a binary search per track in the prediction list, which the host sorts once at
+ *   pmv_klt_set_prediction, project_point for a hit, the guess into the initial-flow array or the LK record, and the tracker's success word
+ *   zeroed. The predicted LK launch counts its forward successes into that word - one integer atomic add by one lane of a workgroup, whose
+ *   sum does not depend on the order of the workgroups, so the bytes are deterministic. The fall-back is a second LK launch of the same
+ *   size, n0, whose workgroups read the word first and leave at once when succ >= min_succ - a workgroup-uniform decision; it never counts
+ *   from the result arrays, which other workgroups of the same launch are overwriting. In a group, trackers with and without a pending
+ *   prediction mix freely, and their settings may differ. pmv_debug_klt_stats and its siblings count the new launches with the call's.
+ * Errors (the old state is kept - a pending prediction stays pending - and nothing is written): PMV_ERR_INVALID - a null argument with n >
+ *   0, an unknown tracker, n < 0, an id named twice (the message names it), top_level outside 0..4, back_top_level outside -1..4, a cam_id
+ *   that is no camera, min_succ < 0; PMV_ERR_CAPACITY - n above PMV_REFILL_MAX_TRACKS. A camera named by a pending prediction cannot be
+ *   destroyed until the prediction is consumed or cleared.
+ * Out of scope: the session form; camera models other than pmv_camera_params'; a level per track; back_top_level for steps without a
+ *   prediction; stereo stage 8 at a capped level; rvec / tvec (the caller transforms the landmarks into the camera frame). */
+typedef struct pmv_klt_predict_params {
+    int cam_id;           /* the camera that projects the points */
+    int top_level;        /* the predicted forward pass starts at min(top_level, L - 1); 0 .. 4 (VINS: 1) */
+    int back_top_level;   /* the backward pass of the consuming step; -1: the pyramid's top, else 0 .. 4 (VINS: 1) */
+    int min_succ;         /* fall back if fewer forward status-1 tracks; >= 0 (VINS: 10) */
+} pmv_klt_predict_params;
+int pmv_klt_set_prediction(pmv_ctx* ctx, int id, const pmv_klt_predict_params* p_or_null, const int* ids, const double* xyz /* 3 n */, int n);
+int pmv_klt_get_prediction_result(pmv_ctx* ctx, int id, int* out4);   /* {consumed, joined, succ, fell_back} of the last step; a host copy */
 
 /* ---- call log (parity tooling) -------------------------------------------------------------------------------------------
  * While recording is on, every pmv_pnp_ransac / pmv_ba_solve / pmv_triangulate_candidates call of this context (also those

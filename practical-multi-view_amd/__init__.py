@@ -96,6 +96,11 @@ class KltObserveParams(C.Structure):
     _fields_ = [("cam_id", C.c_int), ("right_cam_id", C.c_int), ("dt", C.c_double), ("undistorted_f", C.c_int), ("f_focal", C.c_double)]
 
 
+class KltPredictParams(C.Structure):
+    """pmv_klt_predict_params of include/pmv_hip.h"""
+    _fields_ = [("cam_id", C.c_int), ("top_level", C.c_int), ("back_top_level", C.c_int), ("min_succ", C.c_int)]
+
+
 class KltTracker:
     """A tracker of Context.klt_create. The state - ids, ages, positions - lives in device memory; step() returns the new list."""
 
@@ -183,6 +188,34 @@ class KltTracker:
         self.ctx._ck(fn(self.ctx.h, self.id, _p(un, _f32p), _p(vel, _f32p), _p(ok, _u8p), _p(run, _f32p), _p(rok, _u8p), cap, C.byref(n)))
         k = n.value
         return un[:k].copy(), vel[:k].copy(), ok[:k].copy(), run[:k].copy(), rok[:k].copy()
+
+    def set_prediction(self, cam_id, ids=None, xyz=None, top_level=1, back_top_level=1, min_succ=10):
+        """pmv_klt_set_prediction: a one-shot prediction for the tracker's next step - xyz (n, 3) float64, the points with track ids `ids` in
+        the frame of camera cam_id (Context.camera_create) at the NEW image. The step projects them, starts LK of the tracks they belong to
+        there on pyramid levels 0 .. top_level, runs its backward pass on levels 0 .. back_top_level (-1: all) and falls back to the full
+        pyramid if fewer than min_succ tracks succeed. cam_id=None (or no point) clears a pending prediction."""
+        fn = self.ctx.lib.pmv_klt_set_prediction
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(KltPredictParams), _i32p, C.POINTER(C.c_double), C.c_int]
+        if cam_id is None:
+            self.ctx._ck(fn(self.ctx.h, self.id, None, None, None, 0))
+            return
+        ids = np.ascontiguousarray(ids if ids is not None else [], np.int32).reshape(-1)
+        xyz = np.ascontiguousarray(xyz if xyz is not None else np.zeros((0, 3)), np.float64)
+        if xyz.size and (xyz.ndim != 2 or xyz.shape[1] != 3):
+            raise ValueError("set_prediction: xyz must be an (n, 3) float64 array")
+        n = xyz.size // 3
+        if ids.size != n:
+            raise ValueError("set_prediction: one id per point")
+        p = KltPredictParams(int(cam_id), int(top_level), int(back_top_level), int(min_succ))
+        self.ctx._ck(fn(self.ctx.h, self.id, C.byref(p), _p(ids, _i32p) if n else None, _p(xyz, C.POINTER(C.c_double)) if n else None, n))
+
+    def get_prediction_result(self):
+        """pmv_klt_get_prediction_result: dict(consumed, joined, succ, fell_back) of the tracker's last step"""
+        out = (C.c_int * 4)()
+        fn = self.ctx.lib.pmv_klt_get_prediction_result
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        self.ctx._ck(fn(self.ctx.h, self.id, out))
+        return dict(consumed=int(out[0]), joined=int(out[1]), succ=int(out[2]), fell_back=int(out[3]))
 
     def set_tracks(self, ids, ages, xy, next_id):
         """pmv_klt_set_tracks: replace the state"""
@@ -356,14 +389,15 @@ ABI_SYMBOLS = [
     "pmv_remap_map_create", "pmv_remap_map_destroy", "pmv_frames_remap", "pmv_debug_remap_launches", "pmv_batch_frame_upload_remap", "pmv_undistort_map_build",
     "pmv_set_frame_preproc", "pmv_get_frame_preproc", "pmv_debug_preproc_launches",
     "pmv_debug_mem_live",
-    "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
+    "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_lk_track_fb_levels", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
-    "pmv_camera_create", "pmv_camera_destroy", "pmv_undistort_points",
+    "pmv_camera_create", "pmv_camera_destroy", "pmv_undistort_points", "pmv_project_points",
     "pmv_klt_set_observe", "pmv_klt_get_observe", "pmv_klt_get_observations", "pmv_debug_klt_observe_stats",
+    "pmv_klt_set_prediction", "pmv_klt_get_prediction_result",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
     "pmv_prof_enable", "pmv_prof_select", "pmv_prof_kernel_count", "pmv_lk_counters", "pmv_prof_kernel_name", "pmv_prof_read",
     "pmv_pipeline_run", "pmv_pipeline_run_streamed", "pmv_pipeline_run_batch", "pmv_pipeline_run_batch_streamed", "pmv_batch_ingest_stats", "pmv_batch_stats", "pmv_debug_batch_launches", "pmv_pipeline_free", "pmv_pipeline_release", "pmv_pipeline_drain", "pmv_pipeline_num_poses", "pmv_pipeline_get_poses", "pmv_pipeline_num_frames",
@@ -1068,7 +1102,7 @@ class Context:
     def lk_track(self, prev_slot, next_slot, prev_xy):
         return self._lk_track(self.lib.pmv_lk_track, self._ck, prev_slot, next_slot, prev_xy)
 
-    def _lk_ex(self, fn, ck, fb, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals):
+    def _lk_ex(self, fn, ck, fb, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals, levels=None):
         p = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
         n = p.shape[0]
         flags = (LK_USE_INITIAL_FLOW if init_xy is not None else 0) | (LK_GET_MIN_EIGENVALS if min_eigenvals else 0)
@@ -1079,6 +1113,10 @@ class Context:
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32)
         args = [self.h, int(prev_slot), int(next_slot), _p(p, _f32p), n, _p(nxt, _f32p), flags, _p(st, _u8p), _p(err, _f32p)]
+        if levels is not None:   # pmv_lk_track_fb_levels: the two top levels sit behind `flags`; forward only = three null back outputs
+            args[7:7] = [int(levels[0]), int(levels[1])]
+            if not fb:
+                args += [None, None, None]
         if not fb:
             ck(fn(*args))
             return nxt, st, err
@@ -1097,6 +1135,13 @@ class Context:
         """pmv_lk_track_fb: lk_track_ex and, in the same launch, every tracked point back into the first frame. Returns
         (xy, status, err, back_xy, back_status, back_err); thresholding |back_xy - prev_xy| is the caller's policy."""
         return self._lk_ex(self.lib.pmv_lk_track_fb, self._ck, True, prev_slot, next_slot, prev_xy, init_xy, min_eigenvals)
+
+    def lk_track_fb_levels(self, prev_slot, next_slot, prev_xy, init_xy=None, min_eigenvals=False, fwd_top_level=-1, back_top_level=-1, back=True):
+        """pmv_lk_track_fb_levels: lk_track_fb whose forward / backward pass starts at pyramid level min(top, levels - 1) of the slots as
+        they are built (cv's maxLevel per call); -1 = the top. back=False: forward only, (xy, status, err) as lk_track_ex."""
+        fn = self.lib.pmv_lk_track_fb_levels
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _u8p, _f32p, _f32p, _u8p, _f32p]
+        return self._lk_ex(fn, self._ck, bool(back), prev_slot, next_slot, prev_xy, init_xy, min_eigenvals, levels=(fwd_top_level, back_top_level))
 
     def set_lk_params(self, win=32, max_level=4, max_iter=30, eps=0.01, min_eig=1e-4):
         """cv::calcOpticalFlowPyrLK's winSize (square), maxLevel, criteria and minEigThreshold for every pyramid built and every LK call
@@ -1366,6 +1411,20 @@ class Context:
         fn = self.lib.pmv_undistort_points
         fn.argtypes = [C.c_void_p, C.c_int, _f32p, C.c_int, _f32p, _u8p]
         self._ck(fn(self.h, int(cam_id), _p(src, _f32p), n, _p(out, _f32p), _p(ok, _u8p)))
+        return out[:n].copy(), ok[:n].copy()
+
+    def project_points(self, cam_id, xyz):
+        """pmv_project_points: cv::projectPoints(xyz, rvec = tvec = 0, K, dist) through camera cam_id - (xy (n, 2) float32 pixels, ok (n,)
+        uint8; a point that is not finite, not in front of the camera or lands beyond 1e6 has ok 0 and xy (0, 0))"""
+        xyz = np.ascontiguousarray(xyz, np.float64)
+        if xyz.size and (xyz.ndim != 2 or xyz.shape[1] != 3):
+            raise ValueError("project_points: xyz must be an (n, 3) float64 array")
+        n = xyz.size // 3
+        out, ok = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        src = xyz if n else np.zeros((1, 3), np.float64)
+        fn = self.lib.pmv_project_points
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, _f32p, _u8p]
+        self._ck(fn(self.h, int(cam_id), _p(src, C.POINTER(C.c_double)), n, _p(out, _f32p), _p(ok, _u8p)))
         return out[:n].copy(), ok[:n].copy()
 
     def debug_klt_many_stats(self):

@@ -395,7 +395,7 @@ void process_lk(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
                 b.track = r->base + (int)k; b.x = r->prev_xy[2 * k]; b.y = r->prev_xy[2 * k + 1]; b.geom = r->geom;
                 LKExt& x = hext[bpos++];
                 const bool init = (r->flags & LKX_INIT) != 0;
-                x.ix = init ? r->out_xy[2 * k] : 0.f; x.iy = init ? r->out_xy[2 * k + 1] : 0.f; x.flags = r->flags; x.reserved = 0;
+                x.ix = init ? r->out_xy[2 * k] : 0.f; x.iy = init ? r->out_xy[2 * k + 1] : 0.f; x.flags = r->flags; x.opt = 0;
             }
         const LKParams P = lk_launch_params(ctx);
         const LkBackBlock back = back_block(C, cap);

@@ -638,10 +638,13 @@ int pmv_lk_track(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_x
     return PMV_OK;
 }
 
-// pmv_lk_track_ex and pmv_lk_track_fb: pmv_lk_track's steps around ONE launch of the extended kernels
+// pmv_lk_track_ex, pmv_lk_track_fb and pmv_lk_track_fb_levels: pmv_lk_track's steps around ONE launch of the extended kernels; top_f / top_b:
+// the level caps of the two trips, -1 = the slot's top level
 static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
-                        bool fb, float* back_xy, uint8_t* back_status, float* back_err) {
+                        bool fb, float* back_xy, uint8_t* back_status, float* back_err, int top_f = -1, int top_b = -1) {
     REQ(ctx, PMV_ERR_INVALID, "%s: null argument", who);
+    REQ(top_f >= -1 && top_f < MAX_LEVELS && top_b >= -1 && top_b < MAX_LEVELS, PMV_ERR_INVALID, "%s: fwd_top_level = %d, back_top_level = %d: outside -1..%d", who, top_f,
+        top_b, MAX_LEVELS - 1);
     if (const int rc_ = lkx_check(ctx, who, true, prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, fb, back_xy, back_status, back_err)) return rc_;
     const PyrLayout& L = ctx->slot_layout[prev_slot];
     if (n == 0) return PMV_OK;
@@ -661,7 +664,7 @@ static int lk_single_ex(pmv_ctx* ctx, const char* who, int prev_slot, int next_s
     const LKParams P = lk_launch_params(ctx);
     CKC(launch_lk_ex(ctx->s_front, ctx->d_slots + (size_t)prev_slot * L.slot_bytes, ctx->d_slots + (size_t)next_slot * L.slot_bytes, L, ctx->d_prev_xy,
                      init.d, (const int*)(ctx->d_prev_xy + (size_t)2 * n), nb, n, flags | (fb ? LKX_FB : 0), P, ctx->h_out_xy.dm(), ctx->h_status.dm(),
-                     ctx->h_err.dm(), ctx->h_work.dm(), back.xy.d, back.status.d, back.err.d));
+                     ctx->h_err.dm(), ctx->h_work.dm(), back.xy.d, back.status.d, back.err.d, top_f, top_b));
     CKC(hipStreamSynchronize(ctx->s_front));
     memcpy(next_xy, ctx->h_out_xy, (size_t)n * 8);
     memcpy(out_status, ctx->h_status, (size_t)n);
@@ -680,6 +683,14 @@ int pmv_lk_track_ex(pmv_ctx* ctx, int prev_slot, int next_slot, const float* pre
 int pmv_lk_track_fb(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, uint8_t* out_status, float* out_err,
                     float* back_xy, uint8_t* back_status, float* back_err) {
     return lk_single_ex(ctx, "pmv_lk_track_fb", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, true, back_xy, back_status, back_err);
+}
+int pmv_lk_track_fb_levels(pmv_ctx* ctx, int prev_slot, int next_slot, const float* prev_xy, int n, float* next_xy, int flags, int fwd_top_level, int back_top_level,
+                           uint8_t* out_status, float* out_err, float* back_xy_or_null, uint8_t* back_status_or_null, float* back_err_or_null) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_lk_track_fb_levels: null argument");
+    const int n_back = (back_xy_or_null ? 1 : 0) + (back_status_or_null ? 1 : 0) + (back_err_or_null ? 1 : 0);
+    REQ(n_back == 0 || n_back == 3, PMV_ERR_INVALID, "pmv_lk_track_fb_levels: %d of the three back outputs are null (all three: forward only; none: the back check)", 3 - n_back);
+    return lk_single_ex(ctx, "pmv_lk_track_fb_levels", prev_slot, next_slot, prev_xy, n, next_xy, flags, out_status, out_err, n_back == 3, back_xy_or_null, back_status_or_null,
+                        back_err_or_null, fwd_top_level, back_top_level);
 }
 
 }  // extern "C"

@@ -563,12 +563,14 @@ __device__ inline void stage_J(uint8_t* sJ, const uint8_t* Jorg, int js, int tx0
 struct LKResult { float x, y, err; int status, n_iter, n_lev; };
 // LRef: const PyrLayout& (k_lk: the launch's by-value geometry) or GeomEntry& (k_lk_batch: the track's entry of the geometry table)
 // EX (pmv_lk_track_ex / _fb, the k_lk*_ex kernels): `flags` of LKX_INIT - the top level's search starts at (ix0, iy0) * 2^-level instead of
-// the template position - and LKX_EIG - err = the level's minEig, stored before the threshold test, and no final residual. The plain
-// instantiations (EX = false) never look at the three arguments: they generate the code they generated without them.
+// the template position - and LKX_EIG - err = the level's minEig, stored before the threshold test, and no final residual.
+// `top` (EX only; pmv_lk_track_fb_levels): the walk starts at level min(top, n_levels - 1) instead of the slot's top level, -1 = no cap: cv's
+// maxLevel argument on a pyramid that is already built (levels 0 .. top are the same images whatever depth was built).
+// The plain instantiations (EX = false) never look at the four arguments: they generate the code they generated without them.
 template <int T, bool STAMPS, class LRef, bool EX = false>
 __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
                                                    const float px0, const float py0, const LKParams& P, const bool stamp_on,
-                                                   const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0) {
+                                                   const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0, const int top = -1) {
     constexpr int NPRE = 4;                       // I tiles staged per group (all levels of a 4-level pyramid at once)
     constexpr int SI_BYTES = 35 * SI_STRIDE + 8;   // + two dwords: the aligned loads of the last row may touch the first
     __shared__ __attribute__((aligned(16))) uint8_t sIall[NPRE * SI_BYTES];
@@ -588,7 +590,8 @@ __device__ __forceinline__ LKResult lk_track_block(const uint8_t* __restrict__ p
     int status = 1;
     int slot = 0;
     int n_iter = 0, n_lev = 0;   // work counters for the roofline's measured OPS_lk
-    const int ml = L.n_levels - 1;
+    int ml = L.n_levels - 1;
+    if constexpr (EX) { if (top >= 0 && top < ml) ml = top; }   // workgroup-uniform
     unsigned long long t_prev = __builtin_readcyclecounter();
     const unsigned long long wall0 = (STAMPS && P.stamps && stamp_on) ? wall_clock64() : 0ull;   // 100 MHz: calibrates the cycle counter of the stamps
 #define LSTAMP(k) do { if (STAMPS && P.stamps && stamp_on && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); atomicAdd(&P.stamps[k], t_ - t_prev); t_prev = t_; } } while (0)
@@ -969,11 +972,11 @@ __host__ __device__ inline LKGLds lkg_lds(int win) {
 }
 // One track through all pyramid levels, executed by one whole T-thread workgroup (T = 256: k_lk_general, T = 64: k_lk_batch_general);
 // every thread returns the same results. The arithmetic is orc_lk.cpp:92-209 with W = P.win.
-// EX, ix0, iy0, flags: as lk_track_block.
+// EX, ix0, iy0, flags, top: as lk_track_block.
 template <int T, class LRef, bool EX = false>
 __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, LRef L,
                                                      const float px0, const float py0, const LKParams& P,
-                                                     const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0) {
+                                                     const float ix0 = 0.f, const float iy0 = 0.f, const int flags = 0, const int top = -1) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lkg_smem[];
     const int W = __builtin_amdgcn_readfirstlane(P.win);
     const LKGLds G = lkg_lds(W);
@@ -992,7 +995,8 @@ __device__ __forceinline__ LKResult lk_track_general(const uint8_t* __restrict__
     const float FLT_SCALE = 1.f / (1 << 20);
     float outx = 0.f, outy = 0.f, err = 0.f;
     int status = 1, slot = 0, n_iter = 0, n_lev = 0;
-    const int ml = L.n_levels - 1;
+    int ml = L.n_levels - 1;
+    if constexpr (EX) { if (top >= 0 && top < ml) ml = top; }   // workgroup-uniform
     int tx0 = 0, ty0 = 0, tile_level = -1;
 
     for (int level = ml; level >= 0; level--) {
@@ -1179,19 +1183,29 @@ __global__ __launch_bounds__(LKB_T) void k_lk_batch_general(const uint8_t* __res
 // mode: the workgroup that took the track forward takes the result back into the first frame, slot pointers swapped, the original position
 // as its initial flow. ONE call site of the tracker in a two-trip loop; the second trip is a workgroup-uniform decision (flags and the
 // forward status are the same in every lane). A track whose forward status is 0 makes no second trip: back status 0, back err 0, back
-// position = the bits of its forward position.
-struct LKExOut { float* xy; uint8_t* status; float* err; uint16_t* work; float* back_xy; uint8_t* back_status; float* back_err; };
+// position = the bits of its forward position. top_f / top_b: the level cap (`top` of the two device functions) of the forward and of the
+// backward trip; -1 = the slot's top level. pred_slot / pred_mode (a predicted tracker step, pmv_device.h: LKP_*): the (successes, successes
+// wanted) pair O.pred[2 slot ..] - a gated workgroup reads it before anything else and leaves when the first pass had successes enough (the
+// same words in every lane: a workgroup-uniform decision, like the count of k_lk_ex_dev); a counting one adds its forward status, an integer
+// atomic by one lane, whose sum does not depend on the order of the workgroups.
+struct LKExOut { float* xy; uint8_t* status; float* err; uint16_t* work; float* back_xy; uint8_t* back_status; float* back_err; int* pred; int n_pred; };
 __device__ __forceinline__ float uniform_f32(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 template <int T, bool GENERAL, class LRef>
 __device__ __forceinline__ void lk_track_ex(const uint8_t* a, const uint8_t* b, LRef L, float px, float py, float ix, float iy, int flags,
-                                            const LKParams& P, const int t, const LKExOut& O) {
+                                            const LKParams& P, const int t, const LKExOut& O, const int top_f = -1, const int top_b = -1,
+                                            const int pred_slot = -1, const int pred_mode = LKP_NONE) {
+    const bool pred_on = pred_mode != LKP_NONE && O.pred && pred_slot >= 0 && pred_slot < O.n_pred;   // (a slot outside the table serves nobody)
+    if (pred_on && pred_mode == LKP_GATE) {
+        const int* const g = O.pred + 2 * pred_slot;
+        if (__builtin_amdgcn_readfirstlane(g[0]) >= __builtin_amdgcn_readfirstlane(g[1])) return;
+    }
     const bool fb = (flags & LKX_FB) != 0;
-    int n_iter = 0, n_lev = 0;
+    int n_iter = 0, n_lev = 0, top = top_f;
 #pragma nounroll
     for (int trip = 0; trip < 2; trip++) {
         LKResult r;
-        if constexpr (GENERAL) r = lk_track_general<T, LRef, true>(a, b, L, px, py, P, ix, iy, flags);
-        else r = lk_track_block<T, false, LRef, true>(a, b, L, px, py, P, false, ix, iy, flags);
+        if constexpr (GENERAL) r = lk_track_general<T, LRef, true>(a, b, L, px, py, P, ix, iy, flags, top);
+        else r = lk_track_block<T, false, LRef, true>(a, b, L, px, py, P, false, ix, iy, flags, top);
         n_iter += r.n_iter; n_lev += r.n_lev;
         if (trip == 1) {
             if (threadIdx.x == 0) { O.back_xy[2 * t] = r.x; O.back_xy[2 * t + 1] = r.y; O.back_status[t] = (uint8_t)r.status; O.back_err[t] = r.err; }
@@ -1200,11 +1214,13 @@ __device__ __forceinline__ void lk_track_ex(const uint8_t* a, const uint8_t* b, 
         if (threadIdx.x == 0) {
             O.xy[2 * t] = r.x; O.xy[2 * t + 1] = r.y; O.status[t] = (uint8_t)r.status; O.err[t] = r.err;
             if (fb && !r.status) { O.back_xy[2 * t] = r.x; O.back_xy[2 * t + 1] = r.y; O.back_status[t] = 0; O.back_err[t] = 0.f; }
+            if (pred_on && pred_mode == LKP_COUNT && r.status) atomicAdd(O.pred + 2 * pred_slot, 1);
         }
         if (!fb || !r.status) break;   // workgroup-uniform
         const uint8_t* const a0 = a; a = b; b = a0;
         ix = px; iy = py; px = r.x; py = r.y;
         flags = LKX_INIT | (flags & LKX_EIG);
+        top = top_b;
         __syncthreads();   // the forward trip is done with the tiles
     }
     // both directions in the track's one work word: 8 bits of iterations (saturating), <= 10 level passes
@@ -1214,12 +1230,12 @@ __device__ __forceinline__ void lk_track_ex(const uint8_t* a, const uint8_t* b, 
 template <bool GENERAL>
 __global__ __launch_bounds__(LK_T) void k_lk_ex(const uint8_t* __restrict__ prevS, const uint8_t* __restrict__ nextS, PyrLayout L,
                                                 const float* __restrict__ prev_xy, const float* __restrict__ init_xy, const int* __restrict__ order,
-                                                int n, int flags, LKParams P, LKExOut O) {
+                                                int n, int flags, LKParams P, LKExOut O, int top_f, int top_b, int pred_mode) {
     const int t = order[blockIdx.x];   // as k_lk
     if (t < 0 || t >= n) return;
     float ix = 0.f, iy = 0.f;
     if (flags & LKX_INIT) { ix = init_xy[2 * t]; iy = init_xy[2 * t + 1]; }
-    lk_track_ex<LK_T, GENERAL, const PyrLayout&>(prevS, nextS, L, uniform_f32(prev_xy[2 * t]), uniform_f32(prev_xy[2 * t + 1]), uniform_f32(ix), uniform_f32(iy), flags, P, t, O);
+    lk_track_ex<LK_T, GENERAL, const PyrLayout&>(prevS, nextS, L, uniform_f32(prev_xy[2 * t]), uniform_f32(prev_xy[2 * t + 1]), uniform_f32(ix), uniform_f32(iy), flags, P, t, O, top_f, top_b, 0, pred_mode);
 }
 // the device-counted form (stage 8 of a stereo KLT step): the launch is sized by a bound n_cap, the count is a word an earlier kernel of the
 // chain left in device memory. Identity order, no initial flow; a block at or beyond the count leaves before it touches LDS or the frames.
@@ -1238,9 +1254,11 @@ __global__ __launch_bounds__(LKB_T) void k_lk_batch_ex(const uint8_t* __restrict
         const LKBlock bk = blocks[b];
         const LKExt ex = ext[b];
         if (__builtin_amdgcn_readfirstlane(ex.flags) & LKX_VOID) continue;   // workgroup-uniform: a record beyond its list's device-side count
+        const int opt = __builtin_amdgcn_readfirstlane(ex.opt);   // lkext_opt(..): 0 = no cap, no pair
         lk_track_ex<LKB_T, GENERAL, GeomEntry&>(slots + bk.prev_off, slots + bk.next_off, geom_entry(geom, bk.geom), uniform_f32(bk.x), uniform_f32(bk.y),
                                                 uniform_f32(ex.ix), uniform_f32(ex.iy), __builtin_amdgcn_readfirstlane(ex.flags), P,
-                                                __builtin_amdgcn_readfirstlane(bk.track), O);
+                                                __builtin_amdgcn_readfirstlane(bk.track), O, (opt & 15) - 1, ((opt >> 4) & 15) - 1, ((opt >> 8) & 0xfffff) - 1,
+                                                (opt >> 28) & 3);
         __syncthreads();
     }
 }
@@ -1301,19 +1319,20 @@ static bool lk_ex_args_ok(int flags, const float* d_xy, const uint8_t* d_status,
 }
 hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const float* d_init_xy,
                         const int* d_order, int n_blocks, int n, int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work,
-                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err) {
+                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err, int top_f, int top_b, int* d_pred, int pred_mode) {
     if (n <= 0) return hipSuccess;
     if (!prev_slot || !next_slot || !d_prev_xy || !d_order || n_blocks < n || L.n_levels < 1 || L.n_levels > MAX_LEVELS || ((flags & LKX_INIT) && !d_init_xy) ||
+        top_f < -1 || top_f >= MAX_LEVELS || top_b < -1 || top_b >= MAX_LEVELS || pred_mode < LKP_NONE || pred_mode > LKP_GATE || (pred_mode != LKP_NONE && !d_pred) ||
         !lk_ex_args_ok(flags, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
-    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err};
+    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err, d_pred, d_pred ? 1 : 0};
     if (lk_use_general(P)) {
         if (!lk_params_ok(P)) return hipErrorInvalidValue;
         ProfScope ps(K_LK, s);
-        hipLaunchKernelGGL(k_lk_ex<true>, dim3(n_blocks), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O);
+        hipLaunchKernelGGL(k_lk_ex<true>, dim3(n_blocks), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O, top_f, top_b, pred_mode);
         return hipGetLastError();
     }
     ProfScope ps(K_LK, s);
-    hipLaunchKernelGGL(k_lk_ex<false>, dim3(n_blocks), dim3(LK_T), 0, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O);
+    hipLaunchKernelGGL(k_lk_ex<false>, dim3(n_blocks), dim3(LK_T), 0, s, prev_slot, next_slot, L, d_prev_xy, d_init_xy, d_order, n, flags, P, O, top_f, top_b, pred_mode);
     return hipGetLastError();
 }
 hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const int* d_n, int n_cap,
@@ -1323,7 +1342,7 @@ hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8
         !lk_ex_args_ok(flags, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
     const bool general = lk_use_general(P);
     if (general && !lk_params_ok(P)) return hipErrorInvalidValue;
-    const LKExOut O{d_out_xy, d_status, d_err, nullptr, d_back_xy, d_back_status, d_back_err};
+    const LKExOut O{d_out_xy, d_status, d_err, nullptr, d_back_xy, d_back_status, d_back_err, nullptr, 0};
     ProfScope ps(K_LK, s);
     if (general) {
         hipLaunchKernelGGL(k_lk_ex_dev<true>, dim3(n_cap), dim3(LK_T), (size_t)lkg_lds(P.win).total, s, prev_slot, next_slot, L, d_prev_xy, d_n, n_cap, flags, P, O);
@@ -1331,11 +1350,12 @@ hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8
     return hipGetLastError();
 }
 hipError_t launch_lk_batch_ex(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, const LKExt* d_ext, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
-                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err) {
+                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err,
+                              int* d_pred, int n_pred) {
     if (n_blocks <= 0) return hipSuccess;
     // (the records carry the flags: a launch that may hold LKX_FB records needs the three back arrays)
     if (!slots || !d_blocks || !d_ext || !d_geom || !lk_ex_args_ok(LKX_FB, d_out_xy, d_status, d_err, d_back_xy, d_back_status, d_back_err)) return hipErrorInvalidValue;
-    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err};
+    const LKExOut O{d_out_xy, d_status, d_err, d_work, d_back_xy, d_back_status, d_back_err, d_pred, d_pred && n_pred > 0 ? n_pred : 0};
     ProfScope ps(K_LK, s);
     if (lk_use_general(P)) {
         if (!lk_params_ok(P)) return hipErrorInvalidValue;

@@ -20,12 +20,20 @@
 // and ends the chain with a third completion word; with undistorted_f one more launch, enqueued under the wait for n1, writes stage 3's two
 // point sets as virtual-camera points into the LK result arrays of stage 1, which are free by then. A step with the setting off makes
 // neither launch and reads none of this.
+// A tracker with a pending prediction (pmv_klt_set_prediction) runs stage 1 from projected guesses: one workgroup per tracker joins the
+// state's ids against the prediction list (sorted once on the host; a binary search per track), projects the hits (project_point,
+// pmv_lift.h) and zeroes the tracker's success word - k_klt_predict in a single step, folded into k_klt_lk_records in a group; LK then runs
+// from the guesses on the capped levels and counts its forward successes into that word, and a second LK launch of the same size, whose
+// workgroups read the word first and leave at once when the predicted pass had successes enough, is the fall-back to the full pyramid. Two
+// launches more in a single step, one more in a group, no wait more; a call without a pending prediction launches what it launched before.
 #include "pmv_ctx.h"
 #include "pmv_lift.h"
 #include "backend.h"
 #include "vo_pipeline.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 namespace pmv {
 
@@ -34,7 +42,8 @@ namespace {
 constexpr int KT = 1024, KW = KT / 64;
 // counts of a step in device memory: n0, n1, n2, n3, corners wanted (target - n3), corners found (k_gftt_pick_frame's count), its two statistics
 // (C_NOUT: the length of the list after the append, left only by a stereo step - stage 8 reads it)
-enum { C_N0 = 0, C_N1, C_N2, C_N3, C_WANT, C_M, C_STAT0, C_STAT1, C_NOUT, C_COUNT = 16 };
+// (C_JOINED, C_SUCC, C_MINSUCC: a predicted step - tracks that got a projected guess, and the (successes, successes wanted) pair of its LK launches)
+enum { C_N0 = 0, C_N1, C_N2, C_N3, C_WANT, C_M, C_STAT0, C_STAT1, C_NOUT, C_JOINED, C_SUCC, C_MINSUCC, C_COUNT = 16 };
 
 struct KltList { int* id; int* age; float* prev; float* cur; };                     // a track list on its way through the chain
 struct KltRefillIn { unsigned* pos; int* prio; uint8_t* flag; RefillRec* rec; };    // what k_track_select reads (pos null: not written)
@@ -157,6 +166,7 @@ struct KltAppendArgs {
     int* s_id; int* s_age; float* s_xy;
     int* r_hdr; int* r_id; int* r_age; float* r_xy; float* r_prev;
     int* n_out;                     // a stereo step: the device's copy of n3 + m (C_NOUT), else null
+    const int* joined; const int* pred;   // a predicted step: C_JOINED and the (successes, wanted) pair of stage 1, else null
 };
 __device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
     const int tid = threadIdx.x;
@@ -179,6 +189,7 @@ __device__ __forceinline__ void klt_append(const KltAppendArgs& A) {
         A.r_hdr[0] = A.n0; A.r_hdr[1] = A.cnt[C_N1]; A.r_hdr[2] = A.cnt[C_N2]; A.r_hdr[3] = n3; A.r_hdr[4] = m;
         A.r_hdr[5] = A.f_info ? A.f_info[0] : -1; A.r_hdr[6] = A.f_info ? A.f_info[1] : 0; A.r_hdr[7] = 0;
         A.r_hdr[8] = n3 + m;
+        A.r_hdr[12] = A.pred ? *A.joined : 0; A.r_hdr[13] = A.pred ? A.pred[0] : 0; A.r_hdr[14] = A.pred && A.pred[0] < A.pred[1] ? 1 : 0;
         if (A.n_out) *A.n_out = n3 + m;
     }
     __threadfence_system();
@@ -301,6 +312,44 @@ __global__ __launch_bounds__(KT) void k_klt_lift_f(KltLiftFArgs A) {
     klt_lift_f(A, blockIdx.x);
 }
 
+// Stage 1 of a predicted step (pmv_klt_set_prediction): the guess of state track i < n0 is the projection of the prediction point with the
+// track's id, where the list (n_list entries, ids ascending) has one and project_point accepts it, else the track's own position. emit(i,
+// gx, gy) takes it: the initial-flow array of the single step, the LK record of a group. The workgroup leaves the number of projected guesses
+// in *joined and arms the pair of the LK launches: no success yet, min_succ wanted. n0 and n_list are the host's.
+struct KltPredictArgs {
+    int on, n_list, top, back_top, min_succ, slot;   // slot: the tracker's pair in a group's table (0 in a single step)
+    const int* ids; const double* xyz; const LiftCam* cam;
+    int* pred; int* joined;
+    float* guess;                   // a single step: 2 n0 floats
+};
+template <class Emit>
+__device__ __forceinline__ void klt_predict(const KltPredictArgs& P, int n0, const int* __restrict__ id, const float* __restrict__ xy, unsigned* s_w, Emit emit) {
+    const LiftCam cam = *P.cam;
+    if (threadIdx.x == 0) s_w[0] = 0u;
+    __syncthreads();
+    unsigned mine = 0;
+    for (int i = threadIdx.x; i < n0; i += KT) {
+        float gx = xy[2 * i], gy = xy[2 * i + 1];
+        const int want = id[i];
+        int lo = 0, hi = P.n_list;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (P.ids[mid] < want) lo = mid + 1; else hi = mid; }
+        if (lo < P.n_list && P.ids[lo] == want) {
+            float u, v;
+            if (project_point(cam, P.xyz[3 * lo], P.xyz[3 * lo + 1], P.xyz[3 * lo + 2], &u, &v)) { gx = u; gy = v; mine++; }
+        }
+        emit(i, gx, gy);
+    }
+    if (mine) atomicAdd(&s_w[0], mine);
+    __syncthreads();
+    if (threadIdx.x == 0) { *P.joined = (int)s_w[0]; P.pred[0] = 0; P.pred[1] = P.min_succ; }
+    __syncthreads();   // (s_w is the caller's again)
+}
+__global__ __launch_bounds__(KT) void k_klt_predict(KltPredictArgs P, int n0, const int* __restrict__ id, const float* __restrict__ xy) {
+    __shared__ unsigned s_w[KW];
+    BACKEND_PRIO();
+    klt_predict(P, n0, id, xy, s_w, [&](int i, float gx, float gy) { P.guess[2 * i] = gx; P.guess[2 * i + 1] = gy; });
+}
+
 // ---- pmv_klt_step_many: the same three stages as a grid over the trackers of a group ----------------------------------------------------
 // blockIdx.x selects the tracker's argument record in device memory, which holds what the Klt*Args hold; one workgroup serves one tracker and
 // no workgroup waits for another. What the host learns only after the first wait does not change the records: `cur` (which of the two lists
@@ -323,19 +372,39 @@ struct KltManyRec {
     // undistorted_f in a call that may run the tracker's F stage (lift_f.on), those of the lift in front of stage 3
     KltObserveArgs observe;
     KltLiftFArgs lift_f;
+    // a tracker with a pending prediction and tracks (predict.on): what k_klt_lk_records joins and projects for its share of the records
+    KltPredictArgs predict;
 };
 // LK's records for the whole group, written where the tracks are: block lk_base + i tracks state position i of its tracker (geometry entry 0
 // of the call's own one-entry table). The host sized the shares from the n0 it holds; `total` = their sum bounds every store.
-__global__ __launch_bounds__(KT) void k_klt_lk_records(const KltManyRec* __restrict__ recs, LKBlock* __restrict__ blocks, LKExt* __restrict__ ext, int total) {
+// ext2 (a call in which a tracker has a pending prediction, else null): the records of the fall-back launch over the same blocks - void for a
+// tracker without a prediction, gated by the tracker's pair for one with; the first launch's records of such a tracker start at the guesses
+// on the capped levels and count.
+__global__ __launch_bounds__(KT) void k_klt_lk_records(const KltManyRec* __restrict__ recs, LKBlock* __restrict__ blocks, LKExt* __restrict__ ext, LKExt* __restrict__ ext2,
+                                                       int total) {
+    __shared__ unsigned s_w[KW];
     BACKEND_PRIO();
     const KltManyRec& R = recs[blockIdx.x];
     const int base = R.lk_base, n0 = klt_clamp(R.filter.n0, total - base);
     const float* __restrict__ xy = R.filter.prev;
-    for (int i = threadIdx.x; i < n0; i += KT) {
+    auto block_of = [&](int i) {
         LKBlock b;
         b.prev_off = R.prev_off; b.next_off = R.next_off; b.x = xy[2 * i]; b.y = xy[2 * i + 1]; b.track = base + i; b.geom = 0;
         blocks[base + i] = b;
+    };
+    if (R.predict.on && ext2) {   // workgroup-uniform
+        const KltPredictArgs P = R.predict;
+        klt_predict(P, n0, R.filter.id, xy, s_w, [&](int i, float gx, float gy) {
+            block_of(i);
+            ext[base + i] = LKExt{gx, gy, R.lk_flags | LKX_INIT, lkext_opt(P.top, P.back_top, P.slot, LKP_COUNT)};
+            ext2[base + i] = LKExt{0.f, 0.f, R.lk_flags, lkext_opt(-1, P.back_top, P.slot, LKP_GATE)};
+        });
+        return;
+    }
+    for (int i = threadIdx.x; i < n0; i += KT) {
+        block_of(i);
         ext[base + i] = LKExt{0.f, 0.f, R.lk_flags, 0};
+        if (ext2) ext2[base + i] = LKExt{0.f, 0.f, LKX_VOID, 0};
     }
 }
 // Stage 8's records: block st_base + i tracks position i of the tracker's list after the append, from its current left frame into its right
@@ -411,6 +480,7 @@ struct KltDev {
     Carved<char> f_out;
     Carved<int> cnt, ixy;
     Carved<float> sp_xy; Carved<uint8_t> sp_it, sp_fl;
+    Carved<float> pr_guess;         // the initial flow of a predicted single step
 };
 KltDev klt_dev_block(Carve& c, size_t cap) {
     KltDev D;
@@ -426,8 +496,11 @@ KltDev klt_dev_block(Carve& c, size_t cap) {
     D.f_out = c.take<char>(ESS_OUT_HDR + cap, 64);
     D.cnt = c.take<int>(C_COUNT, 64); D.ixy = c.take<int>(2 * cap, 16);
     D.sp_xy = c.take<float>(2 * cap, 16); D.sp_it = c.take<uint8_t>(cap, 16); D.sp_fl = c.take<uint8_t>(cap, 16);
+    D.pr_guess = c.take<float>(2 * cap, 16);
     return D;
 }
+// the prediction list of a tracker in device memory: [n ids, ascending | their n points, 3 doubles each, 16-byte aligned]
+inline size_t klt_pr_xyz_off(size_t n) { return (n * sizeof(int) + 15) & ~(size_t)15; }
 // record block, pinned mirror and device copy: refill record | half-width table | frame request || F problem | F iteration table. The
 // front part goes up with every step, the part behind `front` only in front of a k_fundamental_ransac launch.
 struct KltRecs { Carved<RefillRec> rrec; Carved<uint8_t> hw; Carved<int> grec; size_t front; Carved<char> fprob; Carved<double> ftab; };
@@ -474,6 +547,14 @@ struct KltTracker {
     // 2 with it on - then obs_right says whether that step wrote right observations (armed: of the chain in flight)
     int obs_state = 0;
     bool obs_right = false, obs_right_armed = false;
+    // pmv_klt_set_prediction: the pending prediction - its setting, its camera's device table entry, the list in device memory [ids ascending |
+    // their points, 3 doubles each] - and {consumed, joined, succ, fell_back} of the last step
+    bool pr_on = false;
+    pmv_klt_predict_params pr{};
+    const LiftCam* pr_cam = nullptr;
+    int pr_n = 0;
+    Buf<uint8_t> d_pr;
+    int pr_res[4] = {0, 0, 0, 0};
     Buf<uint8_t> d_mem, d_rec, h_rec{MEM_PINNED}, h_res{MEM_MAPPED};
     KltDev D; KltRecs R; KltRes O;
 };
@@ -505,6 +586,7 @@ struct KltGroupDev {
     Carved<unsigned> pos; Carved<int> prio; Carved<uint8_t> flag, keep;
     Carved<int> m, stat, want, ixy;
     Carved<float> sp_xy; Carved<uint8_t> sp_it, sp_fl;
+    Carved<LKExt> lkx2; Carved<int> pred;   // predicted steps: the fall-back launch's records, the trackers' (successes, wanted) pairs
 };
 KltGroupDev klt_group_dev(Carve& c, size_t n, size_t sum, size_t pad, size_t cap) {
     KltGroupDev D;
@@ -514,6 +596,7 @@ KltGroupDev klt_group_dev(Carve& c, size_t n, size_t sum, size_t pad, size_t cap
     D.pos = c.take<unsigned>(pad, 16); D.prio = c.take<int>(pad, 16); D.flag = c.take<uint8_t>(pad, 16); D.keep = c.take<uint8_t>(pad, 16);
     D.m = c.take<int>(n, 16); D.stat = c.take<int>(2 * n, 16); D.want = c.take<int>(n, 16); D.ixy = c.take<int>(2 * n * cap, 16);
     D.sp_xy = c.take<float>(2 * n * cap, 16); D.sp_it = c.take<uint8_t>(n * cap, 16); D.sp_fl = c.take<uint8_t>(n * cap, 16);
+    D.lkx2 = c.take<LKExt>(sum, 16); D.pred = c.take<int>(2 * n, 16);
     return D;
 }
 }  // namespace
@@ -526,6 +609,13 @@ bool klt_camera_in_use(pmv_ctx* ctx, int cam_id) {
     std::lock_guard<std::mutex> lk(ctx->klt_mu);
     for (const auto* t : ctx->klt)
         if (t && t->obs_on && (t->obs.cam_id == cam_id || t->obs.right_cam_id == cam_id)) return true;
+    return false;
+}
+
+bool klt_camera_predicted(pmv_ctx* ctx, int cam_id) {
+    std::lock_guard<std::mutex> lk(ctx->klt_mu);
+    for (const auto* t : ctx->klt)
+        if (t && t->pr_on && t->pr.cam_id == cam_id) return true;
     return false;
 }
 
@@ -663,6 +753,7 @@ struct KltShares {
     // a stereo call: stage 8's results (the LK result arrays of stage 1 are free again by then), whether the tracker has a right frame in this
     // call, and for a many-call the right slot's offset and the share's first index
     bool stereo; int right_on; KltLkOut st; unsigned long long right_off; int st_base;
+    int* pred; int pred_slot;                     // a predicted step: the tracker's (successes, wanted) pair and its index in the launch's table
 };
 // THE description of what the stage kernels of tracker t are given in its next chain, which begins here: the completion words are armed
 // before anything is launched. The many-call stores the record in its block, the single step passes its members as kernel arguments.
@@ -693,6 +784,13 @@ static KltManyRec klt_stage_args(KltTracker* t, const PyrLayout& L, const KltSha
     A.r_hdr = O.hdr.d; A.r_id = O.id.d; A.r_age = O.age.d; A.r_xy = O.xy.d; A.r_prev = O.prev.d; A.n_out = sh.stereo ? cnt + C_NOUT : nullptr;
     M.f_info = (const int*)(D.f_out.d + ESS_OUT_INFO);
     M.prev_off = sh.prev_off; M.next_off = sh.next_off; M.lk_base = sh.lk_base; M.lk_flags = fb ? LKX_FB : 0;
+    if (t->pr_on && t->n > 0) {   // (with no track the prediction is consumed on the host alone)
+        KltPredictArgs& Q = M.predict;
+        Q.on = 1; Q.n_list = t->pr_n; Q.top = t->pr.top_level; Q.back_top = t->pr.back_top_level; Q.min_succ = t->pr.min_succ; Q.slot = sh.pred_slot;
+        Q.ids = (const int*)t->d_pr.p; Q.xyz = (const double*)((const uint8_t*)t->d_pr.p + klt_pr_xyz_off((size_t)t->pr_n)); Q.cam = t->pr_cam;
+        Q.pred = sh.pred; Q.joined = cnt + C_JOINED; Q.guess = D.pr_guess.d;
+        A.joined = Q.joined; A.pred = Q.pred;
+    }
     if (sh.stereo) {
         const bool sfb = sh.right_on && t->st.fb_max_dist >= 0.0;
         KltStereoArgs& S = M.stereo;
@@ -744,6 +842,8 @@ static int klt_result_check(pmv_ctx* ctx, const KltTracker* t, bool stereo, cons
     REQ(!stereo || ((unsigned)hdr[10] == t->seq && hdr[7] >= 0 && hdr[7] <= n), PMV_ERR_HIP, "%s_stereo: the result block%s is incomplete (n = %d, matched = %d)", who, of, n,
         hdr[7]);
     REQ(!t->obs_on || (unsigned)hdr[11] == t->seq, PMV_ERR_HIP, "%s: the observations of the result block%s are incomplete (n = %d)", who, of, n);
+    REQ(hdr[12] >= 0 && hdr[12] <= hdr[0] && hdr[13] >= 0 && hdr[13] <= hdr[0], PMV_ERR_HIP, "%s: the prediction words of the result block%s are out of range (joined = %d, succ = %d of %d)",
+        who, of, hdr[12], hdr[13], hdr[0]);
     return PMV_OK;
 }
 // ... and the copy-out of a checked block to the caller's arrays, which begin at the tracker's place; the state's length and next id follow
@@ -763,6 +863,9 @@ static void klt_result_copy(KltTracker* t, int* ids, int* ages, float* xy, float
         memcpy(right->st, O.right_st.h, (size_t)n);
     } else if (right) memset(right->st, 0, (size_t)n);
     t->n = n; t->next_id += m;
+    // the step succeeded: a pending prediction is consumed by it (with no track to join: {1, 0, 0, 0}, the header words are 0 then)
+    t->pr_res[0] = t->pr_on ? 1 : 0; t->pr_res[1] = t->pr_on ? O.hdr.h[12] : 0; t->pr_res[2] = t->pr_on ? O.hdr.h[13] : 0; t->pr_res[3] = t->pr_on ? O.hdr.h[14] : 0;
+    t->pr_on = false;
     t->obs_state = t->obs_on ? 2 : 1; t->obs_right = t->obs_on && t->obs_right_armed;
 }
 // the closing statistics of a step (n_trk = 0) or of a many-call on n_trk trackers; the mask at the front of the scratch is now the region's
@@ -817,13 +920,28 @@ static int klt_step_run(pmv_ctx* ctx, int id, int prev_slot, int cur_slot, int* 
     sh.rf = KltRefillIn{D.pos.d, D.prio.d, D.flag.d, R.rrec.d};
     sh.keep = D.keep.d; sh.want = D.cnt.d + C_WANT; sh.m = D.cnt.d + C_M; sh.stat = D.cnt.d + C_STAT0; sh.ixy = D.ixy.d; sh.sp_xy = D.sp_xy.d;
     sh.stereo = right != nullptr; sh.right_on = 1; sh.st = sh.lk;
+    sh.pred = D.cnt.d + C_SUCC; sh.pred_slot = 0;
     KltManyRec M = klt_stage_args(t, L, sh);
-    // 1. track
+    // 1. track; with a pending prediction from the projected guesses on the capped levels, counting the forward successes, and then the
+    // gated launch over the full pyramid, whose workgroups leave at once unless the successes fell short
     if (n0 > 0) {
         const PyrLayout& Lp = ctx->slot_layout[prev_slot];
-        CKC(launch_lk_ex(s, ctx->d_slots + (size_t)prev_slot * Lp.slot_bytes, ctx->d_slots + (size_t)cur_slot * Lp.slot_bytes, Lp, D.s_xy.d, nullptr, D.order.d, (n0 + 7) / 8 * 8,
-                         n0, M.lk_flags, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d, D.bk_err.d));
-        launches++;
+        const uint8_t* const ps = ctx->d_slots + (size_t)prev_slot * Lp.slot_bytes;
+        const uint8_t* const cs = ctx->d_slots + (size_t)cur_slot * Lp.slot_bytes;
+        const int nb = (n0 + 7) / 8 * 8;
+        if (M.predict.on) {
+            const KltPredictArgs& Q = M.predict;
+            CKC(klt_launch(k_klt_predict, 1, s, Q, n0, (const int*)D.s_id.d, (const float*)D.s_xy.d));
+            CKC(launch_lk_ex(s, ps, cs, Lp, D.s_xy.d, Q.guess, D.order.d, nb, n0, M.lk_flags | LKX_INIT, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d,
+                             D.bk_st.d, D.bk_err.d, Q.top, Q.back_top, Q.pred, LKP_COUNT));
+            CKC(launch_lk_ex(s, ps, cs, Lp, D.s_xy.d, nullptr, D.order.d, nb, n0, M.lk_flags, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
+                             D.bk_err.d, -1, Q.back_top, Q.pred, LKP_GATE));
+            launches += 3;
+        } else {
+            CKC(launch_lk_ex(s, ps, cs, Lp, D.s_xy.d, nullptr, D.order.d, nb, n0, M.lk_flags, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
+                             D.bk_err.d));
+            launches++;
+        }
     }
     // 2. filter
     CKC(klt_launch(k_klt_filter, 1, s, M.filter)); launches++;
@@ -912,6 +1030,53 @@ int pmv_klt_set_stereo(pmv_ctx* ctx, int id, const pmv_klt_stereo_params* p_or_n
     REQ(p.border >= 0 && p.border <= 64, PMV_ERR_INVALID, "pmv_klt_set_stereo: border = %d is outside 0..64", p.border);
     t->st = p; t->st_on = true;
     t->st_thr2 = p.fb_max_dist >= 0.0 ? (float)(p.fb_max_dist * p.fb_max_dist) : 0.f;
+    return PMV_OK;
+}
+
+int pmv_klt_set_prediction(pmv_ctx* ctx, int id, const pmv_klt_predict_params* p_or_null, const int* ids, const double* xyz, int n) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_set_prediction: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_set_prediction", id, &t)) return rc;
+    if (!p_or_null || n == 0) { t->pr_on = false; return PMV_OK; }
+    const pmv_klt_predict_params& p = *p_or_null;
+    REQ(n > 0, PMV_ERR_INVALID, "pmv_klt_set_prediction: n = %d is negative", n);
+    REQ(n <= PMV_REFILL_MAX_TRACKS, PMV_ERR_CAPACITY, "pmv_klt_set_prediction: n = %d is above %d (PMV_REFILL_MAX_TRACKS)", n, PMV_REFILL_MAX_TRACKS);
+    REQ(ids && xyz, PMV_ERR_INVALID, "pmv_klt_set_prediction: null argument");
+    const LiftCam* cam = camera_entry(ctx, p.cam_id);
+    REQ(cam, PMV_ERR_INVALID, "pmv_klt_set_prediction: cam_id = %d: the camera does not exist (pmv_camera_create)", p.cam_id);
+    REQ(p.top_level >= 0 && p.top_level < MAX_LEVELS, PMV_ERR_INVALID, "pmv_klt_set_prediction: top_level = %d is outside 0..%d", p.top_level, MAX_LEVELS - 1);
+    REQ(p.back_top_level >= -1 && p.back_top_level < MAX_LEVELS, PMV_ERR_INVALID, "pmv_klt_set_prediction: back_top_level = %d is outside -1..%d", p.back_top_level, MAX_LEVELS - 1);
+    REQ(p.min_succ >= 0, PMV_ERR_INVALID, "pmv_klt_set_prediction: min_succ = %d is negative", p.min_succ);
+    // the list sorted by id, once: the kernels search it. A point of any value is legal (one that cannot be projected predicts nothing).
+    std::vector<int> order((size_t)n);
+    for (int i = 0; i < n; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return ids[a] < ids[b]; });
+    for (int i = 1; i < n; i++)
+        REQ(ids[order[(size_t)i]] != ids[order[(size_t)i - 1]], PMV_ERR_INVALID, "pmv_klt_set_prediction: id %d is named twice (entries %d and %d)", ids[order[(size_t)i]],
+            std::min(order[(size_t)i - 1], order[(size_t)i]), std::max(order[(size_t)i - 1], order[(size_t)i]));
+    const size_t xoff = klt_pr_xyz_off((size_t)n), bytes = xoff + (size_t)n * 3 * sizeof(double);
+    std::vector<uint8_t> host(bytes, 0);
+    int* hid = (int*)host.data(); double* hx = (double*)(host.data() + xoff);
+    for (int i = 0; i < n; i++) {
+        const int k = order[(size_t)i];
+        hid[i] = ids[k]; hx[3 * i] = xyz[3 * k]; hx[3 * i + 1] = xyz[3 * k + 1]; hx[3 * i + 2] = xyz[3 * k + 2];
+    }
+    CKC(hipSetDevice(ctx->device));
+    CKC(hipStreamSynchronize(ctx->s_front));   // (no chain in flight reads the old list)
+    if (bytes > t->d_pr.cap) t->pr_on = false;   // (growing frees the old list first: should that fail, nothing is pending)
+    CKC(t->d_pr.ensure(bytes));
+    t->pr_on = false;
+    CKC(hipMemcpy(t->d_pr.p, host.data(), bytes, hipMemcpyHostToDevice));
+    t->pr = p; t->pr_cam = cam; t->pr_n = n; t->pr_on = true;
+    return PMV_OK;
+}
+
+int pmv_klt_get_prediction_result(pmv_ctx* ctx, int id, int* out4) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_klt_get_prediction_result: null argument");
+    KltTracker* t;
+    if (const int rc = klt_find(ctx, "pmv_klt_get_prediction_result", id, &t)) return rc;
+    REQ(out4, PMV_ERR_INVALID, "pmv_klt_get_prediction_result: null argument");
+    memcpy(out4, t->pr_res, sizeof(t->pr_res));
     return PMV_OK;
 }
 
@@ -1023,6 +1188,7 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
     const unsigned long long pitch = ctx->cap.slot_bytes;
     *R.geom.h = L;
     size_t lk_base = 0, pad_off = 0, st_base = 0;
+    bool any_pred = false;   // a tracker of the group has a pending prediction and tracks: the records carry it, and the gated launch follows
     for (int j = 0; j < n_trk; j++) {
         KltTracker* t = T[j];
         R.rrec.h[j] = RefillRec{0, t->p.radius, (int)pad_off, roi[0], roi[1], roi[2], roi[3], (unsigned)((size_t)j * mstride), 0, {0, 0, 0}};
@@ -1039,6 +1205,8 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
         sh.ixy = D.ixy.d + (size_t)2 * j * cap_max; sh.sp_xy = D.sp_xy.d + (size_t)2 * j * cap_max;
         sh.prev_off = (unsigned long long)(t->n > 0 ? prev_slots[j] : cur_slots[j]) * pitch; sh.next_off = (unsigned long long)cur_slots[j] * pitch;
         sh.lk_base = (int)lk_base;
+        sh.pred = D.pred.d + 2 * j; sh.pred_slot = j;
+        any_pred = any_pred || (t->pr_on && t->n > 0);
         lk_base += (size_t)t->n; pad_off += refill_pad(t->cap);
         if (right) {   // stage 8: the tracker's share of the bound-sized launch
             const bool on = right->slots[j] >= 0;
@@ -1053,10 +1221,15 @@ static int klt_step_many_run(pmv_ctx* ctx, int n_trk, const int* ids, const int*
     CKC(hipMemcpyAsync(G->d_rec, G->h_rec, R.front, hipMemcpyHostToDevice, s));
     // 1. track: the records are written on the device, where the positions are, and the whole group is one launch
     if (sum_n0 > 0) {
-        CKC(klt_launch(k_klt_lk_records, n_trk, s, R.rec.d, D.lkb.d, D.lkx.d, sum_n0));
+        CKC(klt_launch(k_klt_lk_records, n_trk, s, R.rec.d, D.lkb.d, D.lkx.d, any_pred ? D.lkx2.d : (LKExt*)nullptr, sum_n0));
         CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx.d, sum_n0, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d, D.bk_st.d,
-                               D.bk_err.d));
+                               D.bk_err.d, any_pred ? D.pred.d : nullptr, n_trk));
         launches += 2;
+        if (any_pred) {   // the fall-back over the full pyramid: every workgroup of a tracker whose predicted pass had successes enough leaves at once
+            CKC(launch_lk_batch_ex(s, ctx->d_slots, D.lkb.d, D.lkx2.d, sum_n0, R.geom.d, lk_launch_params(ctx), D.lk_xy.d, D.lk_st.d, D.lk_err.d, nullptr, D.bk_xy.d,
+                                   D.bk_st.d, D.bk_err.d, D.pred.d, n_trk));
+            launches++;
+        }
     }
     // 2. filter
     CKC(klt_launch(k_klt_filter_many, n_trk, s, R.rec.d)); launches++;

@@ -182,11 +182,13 @@ struct pmv_ctx {
     std::atomic<long long> klt_observe_stats[4];
     // pmv_camera_create (frontend_lift.hip): at most PMV_MAX_CAMERAS cameras, id = index; d_cams is their device table (LiftCam entries),
     // made by the first create and released with the last camera, like h_lift, the mapped pinned block of pmv_undistort_points [points |
-    // lifted points | ok bytes], max_tracks of each, made by the first such call. cam_mu guards the table.
+    // lifted points | ok bytes], max_tracks of each, made by the first such call, and h_proj, the block of pmv_project_points [camera-frame
+    // points (3 doubles) | pixels | ok bytes]. cam_mu guards the table.
     bool cam_used[PMV_MAX_CAMERAS] = {};
     pmv_camera_params cam_params[PMV_MAX_CAMERAS] = {};
     pmv::Buf<pmv::LiftCam> d_cams;
     pmv::Buf<uint8_t> h_lift{pmv::MEM_MAPPED};
+    pmv::Buf<uint8_t> h_proj{pmv::MEM_MAPPED};
     std::mutex cam_mu;
     pmv::BackendBuffers* be = nullptr;
     // second back-end lane (own workspace + stream) for work a helper thread runs ahead of the back-end: pmv_triangulate_candidates_ahead
@@ -280,6 +282,7 @@ int subpix_params_check(pmv_ctx* ctx, const char* who, const pmv_subpix_params* 
 hipError_t subpix_table_ready(pmv_ctx* ctx, const pmv_subpix_params* p, SubpixArgs* A);
 const LiftCam* camera_entry(pmv_ctx* ctx, int id);   // the device table entry of camera `id`, or null when there is none (frontend_lift.hip)
 bool klt_camera_in_use(pmv_ctx* ctx, int cam_id);    // a tracker's observation setting names the camera (frontend_klt.hip)
+bool klt_camera_predicted(pmv_ctx* ctx, int cam_id); // a tracker's pending prediction names the camera (frontend_klt.hip)
 void klt_destroy_all(pmv_ctx* ctx);   // frees the trackers that are left (pmv_ctx_destroy, after the streams were synchronised)
 // the zero zone as cv::cornerSubPix applies it: (-1, -1) unless it lies strictly inside the window
 inline void subpix_zero_zone(const pmv_subpix_params* p, int* zw, int* zh) {

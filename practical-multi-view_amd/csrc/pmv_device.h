@@ -171,17 +171,26 @@ static_assert(sizeof(LKBlock) == 32, "LKBlock: one 32-byte record per workgroup"
 // LKX_VOID (k_lk_batch_ex only): the record is beyond its list's count, which only the device knew when the launch was sized - its
 // workgroup leaves without a load from the frames or a store. Set by k_klt_stereo_records alone.
 constexpr int LKX_INIT = 4, LKX_EIG = 8, LKX_FB = 0x100, LKX_VOID = 0x200;
+// `opt` of a record, 0 = none of it: the level caps of the two trips (pmv_lk_track_fb_levels' top levels, -1 = the slot's top) and the record's
+// part in a predicted tracker step (pmv_klt_set_prediction) - `slot` names a (successes, successes wanted) pair of the launch's table d_pred:
+// an LKP_COUNT record adds its forward status to the pair's first word, an LKP_GATE record reads the pair first and leaves at once when the
+// first word has reached the second.
+constexpr int LKP_NONE = 0, LKP_COUNT = 1, LKP_GATE = 2;
+constexpr int lkext_opt(int top_f, int top_b, int slot, int mode) { return (top_f + 1) | ((top_b + 1) << 4) | ((slot + 1) << 8) | (mode << 28); }
 struct __attribute__((aligned(16))) LKExt {
     float ix, iy;      // where the top level's search starts (level-0 coordinates), read with LKX_INIT
     int flags;         // LKX_*
-    int reserved;
+    int opt;           // lkext_opt(..)
 };
 static_assert(sizeof(LKExt) == 16, "LKExt: one 16-byte record per workgroup");
+static_assert(MAX_LEVELS + 1 <= 16, "lkext_opt: four bits per level cap");
 // d_geom: the geometry table in device memory; every record's `geom` is an entry of it (the caller's business, on the host)
 hipError_t launch_lk_batch(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
                            float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
+// d_pred: n_pred (successes, successes wanted) pairs in device memory, named by the records' `opt`; null: no record names one
 hipError_t launch_lk_batch_ex(hipStream_t s, const uint8_t* slots, const LKBlock* d_blocks, const LKExt* d_ext, int n_blocks, const PyrLayout* d_geom, const LKParams& P,
-                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
+                              float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work, float* d_back_xy, uint8_t* d_back_status, float* d_back_err,
+                              int* d_pred = nullptr, int n_pred = 0);
 hipError_t launch_bgr2gray(hipStream_t s, const uint8_t* d_bgr, int w, int h, int stride, uint8_t* d_gray);   // cv::cvtColor(BGR2GRAY), 8-bit
 // one entry of a slot-list pyramid build (the feeder): destination slot and, for level 0, the device-visible address of the tight gray
 // frame (HBM landing area or mapped pinned host memory), null = already staged in the slot; `geom` = the frame's entry of the geometry table
@@ -211,9 +220,13 @@ hipError_t launch_lk(hipStream_t s, const uint8_t* prev_slot, const uint8_t* nex
                      const float* d_prev_xy, const int* d_order, int n_blocks, int n, const LKParams& P, float* d_out_xy,
                      uint8_t* d_status, float* d_err, uint16_t* d_work = nullptr);
 // One launch of the extended form: `flags` (LKX_*) holds for every track, d_init_xy is read with LKX_INIT, the back arrays are written with LKX_FB.
+// top_f / top_b (pmv_lk_track_fb_levels): the forward / backward trip starts at level min(top, L.n_levels - 1); -1 = the slot's top level.
+// pred_mode (LKP_*; a predicted tracker step): d_pred is one (successes, successes wanted) pair - LKP_COUNT: every track adds its forward status
+// to the first word; LKP_GATE: every workgroup reads the pair first and leaves at once when the first word has reached the second.
 hipError_t launch_lk_ex(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const float* d_init_xy,
                         const int* d_order, int n_blocks, int n, int flags, const LKParams& P, float* d_out_xy, uint8_t* d_status, float* d_err, uint16_t* d_work,
-                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err);
+                        float* d_back_xy, uint8_t* d_back_status, float* d_back_err, int top_f = -1, int top_b = -1, int* d_pred = nullptr,
+                        int pred_mode = LKP_NONE);
 // The same launch sized by a bound: n_cap workgroups, of which those below *d_n (device memory, read by every workgroup) track d_prev_xy[i] in
 // identity order; flags: LKX_FB or 0. The count never reaches the host.
 hipError_t launch_lk_ex_dev(hipStream_t s, const uint8_t* prev_slot, const uint8_t* next_slot, const PyrLayout& L, const float* d_prev_xy, const int* d_n, int n_cap,
