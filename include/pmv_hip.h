@@ -22,6 +22,8 @@
  *                                          (a VINS-style front end's liftProjective; also stage 9 of the tracker step, pmv_klt_set_observe)
  *   pmv_project_points                     cv::projectPoints without rvec / tvec: points of the camera frame onto the image (a VINS-style
  *                                          front end's spaceToPlane: where known landmarks should appear, as LK's initial flow)
+ *   pmv_camera_create_fisheye              a camera of cv::fisheye's equidistant model (Kalibr "equidistant") for the two calls above and the
+ *                                          tracker step; pmv_fisheye_map_build is cv::fisheye::initUndistortRectifyMap for pmv_frames_remap
  *   pmv_detect_shitomasi                   ShiTomasiFeatureExtractor::extractFeatures    (ShiTomasiFeatureExtractor.cpp:5-75,
  *                                          Frame.cpp:58-86,119-138)                      -> BaseFeatureExtractor.h:21
  *   pmv_lk_track                           cv::calcOpticalFlowPyrLK                      (OpenCVLucasKanadeFM.cpp:15) -> BaseFeatureMatcher.h:22
@@ -289,8 +291,8 @@ int pmv_debug_mem_live(long long* out2);
  *   r2 = x^2 + y^2; kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2); xd = x kr + p1 (2xy) + p2 (r2 + 2x^2);
  *   yd = y kr + p1 (r2 + 2y^2) + p2 (2xy); map_x = (float)(fx xd + cx), map_y = (float)(fy yd + cy) with K's fx, fy, cx, cy.
  *   cv walks the ray incrementally along a row, so its last double bits differ: this helper is held to a tolerance (one float ulp of the
- *   coordinate), not to bits; the bits that matter are those of pmv_frames_remap given the float maps. cv::fisheye models are out of scope
- *   (a caller's own float maps serve them).
+ *   coordinate), not to bits; the bits that matter are those of pmv_frames_remap given the float maps. The maps of a cv::fisheye camera are
+ *   pmv_fisheye_map_build's (below, with pmv_camera_create_fisheye).
  * Errors: PMV_ERR_INVALID - a null K9, dist8, map_x or map_y, a singular newK R, w or h < 1. */
 int pmv_undistort_map_build(const double* K9, const double* dist8, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x,
                             float* map_y);
@@ -320,7 +322,9 @@ int pmv_undistort_map_build(const double* K9, const double* dist8, const double*
  *   iters outside 1..50; an unknown camera id; a coordinate that is not finite or beyond 1e6 in magnitude (the message names the point);
  *   destroying a camera that a tracker's observation setting names. PMV_ERR_CAPACITY - a 17th camera; n < 0 or n above max_tracks.
  *   pmv_ctx_destroy frees the cameras that are left.
- * Out of scope: cv::fisheye and other camera models; the R / P arguments of undistortPoints; thin-prism and tilt coefficients (not built: a
+ * A camera of pmv_camera_create_fisheye (the equidistant model, below) is lifted by that model's own statement, given there.
+ * Out of scope: camera models other than this one and cv::fisheye's equidistant one (skew and the omnidirectional model among them); the
+ *   R / P arguments of undistortPoints; thin-prism and tilt coefficients (not built: a
  *   camera has the 8 coefficients below); the session form (pmv_batch_*); a forward distort_points call on normalised points (the forward
  *   model as a call is pmv_project_points below, from points of the camera frame). */
 #define PMV_MAX_CAMERAS 16
@@ -349,9 +353,70 @@ int pmv_undistort_points(pmv_ctx* ctx, int cam_id, const float* xy, int n, float
  *   legal and launches nothing. The call's block is made by the first call and released with the last camera.
  * Errors (nothing is written): PMV_ERR_INVALID - a null argument, an unknown camera id. PMV_ERR_CAPACITY - n < 0 or n above max_tracks. A
  *   coordinate of any value, NaN and infinities included, is no error: the point comes back with ok 0.
- * Out of scope: rvec / tvec (transform the points first), the Jacobian output, cv::fisheye and other camera models, thin-prism and tilt
- *   coefficients, the session form. */
+ * A camera of pmv_camera_create_fisheye (below) is projected by the equidistant model's forward statement, given there.
+ * Out of scope: rvec / tvec (transform the points first), the Jacobian output, camera models other than this one and cv::fisheye's
+ *   equidistant one, skew, thin-prism and tilt coefficients, the session form. */
 int pmv_project_points(pmv_ctx* ctx, int cam_id, const double* xyz /* 3 n, camera frame */, int n, float* out_xy, uint8_t* out_ok);
+/* ---- cv::fisheye cameras: the equidistant model (Kannala-Brandt, Kalibr "equidistant") ----------------------------------------------------
+ * The wide-angle cameras of VIO rigs are calibrated with this model (VINS-Fusion and OpenVINS read it next to the radial-tangential one).
+ * pmv_camera_create_fisheye makes a camera of it in the same table as pmv_camera_create; its id is a camera id wherever one is taken -
+ * pmv_undistort_points, pmv_project_points, pmv_klt_set_observe (cam_id, right_cam_id, undistorted_f; every step form, single and group)
+ * and pmv_klt_set_prediction - and pmv_camera_destroy frees it. A rig may mix models: a fisheye left and a radial-tangential right camera,
+ * or a group of trackers with different cameras. No launch and no wait is added anywhere: the model is one field of the camera record, the
+ * same for every lane of a launch, and a step with a fisheye camera is the same chain as a step with a radial-tangential one.
+ * Arithmetic: double, IEEE + - * / only, without contraction, operand order as written, plus the correctly rounded double square root. The
+ *   model needs atan (forward) and tan (inverse); no math library's are the same on the device and the host, so the library states its own
+ *   in + - * /, comparisons and literal constants (pmv_atan, pmv_tan in csrc/pmv_lift.h; derived by scripts/derive_atan_tan.py):
+ *     pmv_atan on [0, inf): the argument goes to |t| <= 7/16 by atan x = atan c + atan((x - c) / (1 + c x)), c = 0.5, 1, 1.5 (breakpoints
+ *       7/16, 11/16, 19/16) and atan x = pi/2 - atan(1 / x) from 39/16; there atan t = t - t (z A(z)), z = t t, A of degree 13.
+ *     pmv_tan on [0, pi/2], pi/2 the double 0x1.921fb54442d18p+0: up to pi/4 tan x = x + x (z T(z)), z = x x, T of degree 16; beyond pi/4
+ *       the reciprocal of the tangent of the complement, the complement formed with a two-part pi/2.
+ *   Both are within 2^-40 of the true function, relative, over the whole domain (tests/test_fisheye_twin.py holds them to that against
+ *   mpmath at 50 digits; the measured maxima, far smaller, are in DESIGN.md section 4), so the float results are those of an exact atan /
+ *   tan in all but about one case in 10^5.
+ * Forward (pmv_project_points; cv::fisheye::projectPoints without rvec / tvec, skew 0), PI_2 = 0x1.921fb54442d18p+0:
+ *     a = X / Z;  b = Y / Z;  r2 = a*a + b*b;  r = sqrt(r2);  t = pmv_atan(r)
+ *     t2 = t*t;  t4 = t2*t2;  t6 = t4*t2;  t8 = t4*t4
+ *     td = t * (1 + k1*t2 + k2*t4 + k3*t6 + k4*t8)          (sums left to right)
+ *     s  = r > 1e-8 ? td / r : 1.0
+ *     u  = fx*(a*s) + cx;  v = fy*(b*s) + cy
+ *   out_ok and the refusal (0, 0) are pmv_project_points' own - X, Y, Z finite, Z > 0, u and v finite before and after their rounding to
+ *   float and within 1e6 - and in addition r must be finite.
+ * Inverse (pmv_undistort_points; cv::fisheye::undistortPoints without R / P):
+ *     px = ((double)u - cx) * ifx;  py = ((double)v - cy) * ify
+ *     td = sqrt(px*px + py*py);  if (td > PI_2) td = PI_2
+ *     if (td > 1e-8):
+ *         t = td;  converged = false
+ *         repeat at most 10 times:
+ *             t2 .. t8 as above
+ *             fix = (t*(1 + k1*t2 + k2*t4 + k3*t6 + k4*t8) - td) / (1 + 3*k1*t2 + 5*k2*t4 + 7*k3*t6 + 9*k4*t8)
+ *             t = t - fix
+ *             if (fabs(fix) < 1e-8) { converged = true; break }
+ *         good = converged && t >= 0 && t <= PI_2
+ *         s = pmv_tan(t) / td                                 (evaluated only when good)
+ *     else: s = 1.0, good = true
+ *     x = px*s;  y = py*s
+ *   out_ok = good and x, y finite, and still finite after rounding to float; a refused point is (0, 0) and no NaN is ever written.
+ *   Differences from OpenCV: a point that did not converge, or whose angle left [0, pi/2], is refused with ok = 0 and (0, 0) - it is not
+ *   returned as a sentinel, and a negative angle is not mirrored; skew is not taken. Parity with a real OpenCV is unpinned, as for the
+ *   radial-tangential lift. The device equals the CPU restatement tests/twin/fisheye_twin.cpp bit for bit.
+ * pmv_fisheye_map_build is cv::fisheye::initUndistortRectifyMap(K, k, R, newK, Size(w, h), CV_32FC1) on the host, in the shape of
+ *   pmv_undistort_map_build: (X, Y, W) = (newK R)^-1 (j, i, 1) by adjugate and determinant, then the forward statement above on (X, Y, W)
+ *   with K's fx, fy, cx, cy (the same function the kernels run, compiled for the host). A pixel the statement refuses gets (-1, -1), which
+ *   is the border under pmv_frames_remap. The maps go to pmv_remap_map_create and through it to pmv_frames_remap,
+ *   pmv_batch_frame_upload_remap and pmv_set_frame_preproc.
+ * Errors (nothing is written): pmv_camera_create_fisheye - those of pmv_camera_create: PMV_ERR_INVALID for a null argument, fx or fy zero
+ *   or not finite, any parameter not finite (the message names it, k[2]); PMV_ERR_CAPACITY for a 17th camera of either model.
+ *   pmv_fisheye_map_build - PMV_ERR_INVALID for a null K9, k4, map_x or map_y, a singular newK R, w or h < 1.
+ * Out of scope: skew; the R / P arguments of cv::fisheye::undistortPoints; a Jacobian output; the session form (pmv_batch_*); the
+ *   omnidirectional (Mei) model. */
+typedef struct pmv_fisheye_params {
+    double fx, fy, cx, cy;
+    double k[4];            /* k1, k2, k3, k4 of theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) */
+} pmv_fisheye_params;
+int pmv_camera_create_fisheye(pmv_ctx* ctx, const pmv_fisheye_params* p, int* out_id);
+int pmv_fisheye_map_build(const double* K9, const double* k4, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x,
+                          float* map_y);
 
 /* ---- feature extraction ------------------------------------------------------------------------ */
 /* cells: n_cells * 4 ints (x0, y0, w, h), each <= 255x255, sub-views of the frame in `slot`.
@@ -996,8 +1061,9 @@ int pmv_debug_klt_stereo_stats(pmv_ctx* ctx, long long* out4);
  *   a right_cam_id that is neither -1 nor a camera, dt not finite or not above 0, undistorted_f other than 0 / 1, with undistorted_f a
  *   f_focal not finite or not above 0. A camera named by a setting cannot be destroyed until the setting is cleared.
  * Out of scope: right-camera velocities (they need right positions as tracker state, which the stereo section excludes); the session form
- *   (pmv_batch_*); an undistorted_f that lifts through a camera other than cam_id; cv::fisheye and other camera models, R / P, thin-prism
- *   and tilt coefficients and a forward distort_points call, as for pmv_undistort_points. */
+ *   (pmv_batch_*); an undistorted_f that lifts through a camera other than cam_id; camera models other than the two of pmv_camera_create and
+ *   pmv_camera_create_fisheye (cv::fisheye's skew among them), R / P, thin-prism and tilt coefficients and a forward distort_points call,
+ *   as for pmv_undistort_points. */
 typedef struct pmv_klt_observe_params {
     int    cam_id;          /* the left camera */
     int    right_cam_id;    /* the right camera, or -1: no normalised right observations */
@@ -1046,7 +1112,7 @@ int pmv_debug_klt_observe_stats(pmv_ctx* ctx, long long* out4);
  *   0, an unknown tracker, n < 0, an id named twice (the message names it), top_level outside 0..4, back_top_level outside -1..4, a cam_id
  *   that is no camera, min_succ < 0; PMV_ERR_CAPACITY - n above PMV_REFILL_MAX_TRACKS. A camera named by a pending prediction cannot be
  *   destroyed until the prediction is consumed or cleared.
- * Out of scope: the session form; camera models other than pmv_camera_params'; a level per track; back_top_level for steps without a
+ * Out of scope: the session form; camera models other than the two of pmv_camera_create and pmv_camera_create_fisheye; a level per track; back_top_level for steps without a
  *   prediction; stereo stage 8 at a capped level; rvec / tvec (the caller transforms the landmarks into the camera frame). */
 typedef struct pmv_klt_predict_params {
     int cam_id;           /* the camera that projects the points */

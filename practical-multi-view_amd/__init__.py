@@ -91,6 +91,23 @@ def camera_params(fx, fy, cx, cy, dist=(), iters=5):
     return p
 
 
+class FisheyeParams(C.Structure):
+    """pmv_fisheye_params of include/pmv_hip.h"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 4)]
+
+
+def fisheye_params(fx, fy, cx, cy, k=()):
+    """a FisheyeParams from keywords; k: up to 4 coefficients (k1, k2, k3, k4) of the equidistant model (cv::fisheye, Kalibr "equidistant"),
+    the missing ones 0"""
+    d = np.asarray(k, np.float64).reshape(-1)
+    if d.size > 4:
+        raise ValueError(f"fisheye_params: at most 4 distortion coefficients (k1, k2, k3, k4), got {d.size}")
+    p = FisheyeParams(float(fx), float(fy), float(cx), float(cy))
+    for i, v in enumerate(d):
+        p.k[i] = float(v)
+    return p
+
+
 class KltObserveParams(C.Structure):
     """pmv_klt_observe_params of include/pmv_hip.h"""
     _fields_ = [("cam_id", C.c_int), ("right_cam_id", C.c_int), ("dt", C.c_double), ("undistorted_f", C.c_int), ("f_focal", C.c_double)]
@@ -361,6 +378,41 @@ def undistort_map(K, dist, size, R=None, new_K=None):
     return mx, my
 
 
+def fisheye_map_build(K, k, size, R=None, new_K=None):
+    """pmv_fisheye_map_build: the (map_x, map_y) float32 (h, w) maps of cv::fisheye::initUndistortRectifyMap(K, k, R, new_K, size, CV_32FC1),
+    on the host. k: up to 4 coefficients (k1, k2, k3, k4), the missing ones 0; size = (w, h); R None = identity, new_K None = K. A pixel whose
+    ray the model refuses has (-1, -1)."""
+    def mat(m, name):
+        a = np.ascontiguousarray(m, np.float64)
+        if a.shape != (3, 3):
+            raise ValueError(f"fisheye_map_build: {name} is 3 x 3, got shape {a.shape}")
+        return a
+    Km = mat(K, "K")
+    d = np.asarray(k, np.float64).reshape(-1)
+    if d.size > 4:
+        raise ValueError(f"fisheye_map_build: at most 4 distortion coefficients (k1, k2, k3, k4), got {d.size}")
+    k4 = np.zeros(4, np.float64)
+    k4[:d.size] = d
+    try:
+        w, h = size
+    except (TypeError, ValueError):
+        raise ValueError(f"fisheye_map_build: size is (w, h), got {size!r}") from None
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"fisheye_map_build: size {size!r}")
+    Rm = None if R is None else mat(R, "R")
+    Nm = None if new_K is None else mat(new_K, "new_K")
+    mx, my = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    lib = load_library()
+    _f32p = C.POINTER(C.c_float)
+    lib.pmv_fisheye_map_build.argtypes = [_f64p, _f64p, _f64p, _f64p, C.c_int, C.c_int, _f32p, _f32p]
+    rc = lib.pmv_fisheye_map_build(_p(Km, _f64p), _p(k4, _f64p), None if Rm is None else _p(Rm, _f64p), None if Nm is None else _p(Nm, _f64p), w, h,
+                                   _p(mx, _f32p), _p(my, _f32p))
+    if rc != 0:
+        raise PmvError(rc, lib.pmv_last_error(None).decode())
+    return mx, my
+
+
 def mem_live():
     """pmv_debug_mem_live: (device bytes, pinned host bytes) the library holds right now, over every context of the process"""
     lib = load_library()
@@ -396,6 +448,7 @@ ABI_SYMBOLS = [
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
     "pmv_camera_create", "pmv_camera_destroy", "pmv_undistort_points", "pmv_project_points",
+    "pmv_camera_create_fisheye", "pmv_fisheye_map_build",
     "pmv_klt_set_observe", "pmv_klt_get_observe", "pmv_klt_get_observations", "pmv_debug_klt_observe_stats",
     "pmv_klt_set_prediction", "pmv_klt_get_prediction_result",
     "pmv_record_enable", "pmv_record_count", "pmv_record_size", "pmv_record_get",
@@ -1393,6 +1446,15 @@ class Context:
         out = C.c_int(-1)
         self.lib.pmv_camera_create.argtypes = [C.c_void_p, C.POINTER(CameraParams), C.POINTER(C.c_int)]
         self._ck(self.lib.pmv_camera_create(self.h, C.byref(p), C.byref(out)))
+        return out.value
+
+    def camera_create_fisheye(self, fx, fy, cx, cy, k=()):
+        """pmv_camera_create_fisheye: the id of a camera of the equidistant model (cv::fisheye, Kalibr "equidistant"); it is a camera id like
+        camera_create's wherever one is taken, and camera_destroy frees it."""
+        p = fisheye_params(fx, fy, cx, cy, k)
+        out = C.c_int(-1)
+        self.lib.pmv_camera_create_fisheye.argtypes = [C.c_void_p, C.POINTER(FisheyeParams), C.POINTER(C.c_int)]
+        self._ck(self.lib.pmv_camera_create_fisheye(self.h, C.byref(p), C.byref(out)))
         return out.value
 
     def camera_destroy(self, cam_id):

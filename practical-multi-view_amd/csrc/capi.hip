@@ -572,6 +572,14 @@ int pmv_undistort_map_build(const double* K9, const double* dist8, const double*
     REQ(undistort_map(K9, dist8, R9_or_null, newK9_or_null, w, h, map_x, map_y), PMV_ERR_INVALID, "pmv_undistort_map_build: newK R is singular");
     return PMV_OK;
 }
+// cv::fisheye::initUndistortRectifyMap(.., CV_32FC1) on the host, in the same shape
+int pmv_fisheye_map_build(const double* K9, const double* k4, const double* R9_or_null, const double* newK9_or_null, int w, int h, float* map_x, float* map_y) {
+    pmv_ctx* ctx = nullptr;
+    REQ(K9 && k4 && map_x && map_y, PMV_ERR_INVALID, "pmv_fisheye_map_build: null argument");
+    REQ(w >= 1 && h >= 1, PMV_ERR_INVALID, "pmv_fisheye_map_build: size %dx%d", w, h);
+    REQ(fisheye_map(K9, k4, R9_or_null, newK9_or_null, w, h, map_x, map_y), PMV_ERR_INVALID, "pmv_fisheye_map_build: newK R is singular");
+    return PMV_OK;
+}
 
 }  // extern "C"
 

@@ -2,7 +2,8 @@
 // table of LiftCam entries, made by the first pmv_camera_create and released with the last camera - and cv::undistortPoints as a single
 // call: one launch of k_undistort_points on the front-end stream and one wait. The arithmetic is lift_point's (pmv_lift.h), which the
 // tracker's stages 3 and 9 call too (frontend_klt.hip). pmv_project_points is the forward direction in the same shape: one launch of
-// k_project_points (project_point, pmv_lift.h) and one wait.
+// k_project_points (project_point, pmv_lift.h) and one wait. A camera is of the radial-tangential model (pmv_camera_create) or of
+// cv::fisheye's equidistant one (pmv_camera_create_fisheye): one field of its LiftCam entry, which the two device functions branch on.
 #include "pmv_ctx.h"
 #include "pmv_lift.h"
 #include <cmath>
@@ -65,6 +66,21 @@ using namespace pmv;
 #define CKC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(ctx, "%s: %s", #x, hipGetErrorString(e_)); return PMV_ERR_HIP; } } while (0)
 #define REQ(cond, code, ...) do { if (!(cond)) { set_err(ctx, __VA_ARGS__); return code; } } while (0)
 
+// a validated camera record into the first free entry of the table (both constructors end here); `radtan` is what cam_params keeps for it
+static int camera_place(pmv_ctx* ctx, const char* who, const LiftCam& c, const pmv_camera_params& radtan, int* out_id) {
+    std::lock_guard<std::mutex> lk(ctx->cam_mu);
+    int id = 0;
+    while (id < PMV_MAX_CAMERAS && ctx->cam_used[id]) id++;
+    REQ(id < PMV_MAX_CAMERAS, PMV_ERR_CAPACITY, "%s: the context holds %d cameras already (pmv_camera_destroy one)", who, PMV_MAX_CAMERAS);
+    CKC(hipSetDevice(ctx->device));
+    CKC(ctx->d_cams.ensure(PMV_MAX_CAMERAS * sizeof(LiftCam)));
+    CKC(hipMemcpy(ctx->d_cams.get() + id, &c, sizeof(c), hipMemcpyHostToDevice));   // (no launch in flight reads a free entry)
+    ctx->cam_used[id] = true;
+    ctx->cam_params[id] = radtan;
+    *out_id = id;
+    return PMV_OK;
+}
+
 extern "C" {
 
 int pmv_camera_create(pmv_ctx* ctx, const pmv_camera_params* p, int* out_id) {
@@ -79,17 +95,21 @@ int pmv_camera_create(pmv_ctx* ctx, const pmv_camera_params* p, int* out_id) {
     c.k1 = p->dist[0]; c.k2 = p->dist[1]; c.p1 = p->dist[2]; c.p2 = p->dist[3]; c.k3 = p->dist[4]; c.k4 = p->dist[5]; c.k5 = p->dist[6]; c.k6 = p->dist[7];
     c.iters = p->iters;
     REQ(std::isfinite(c.ifx) && std::isfinite(c.ify), PMV_ERR_INVALID, "pmv_camera_create: 1 / fx or 1 / fy is not finite (fx = %g, fy = %g)", p->fx, p->fy);
-    std::lock_guard<std::mutex> lk(ctx->cam_mu);
-    int id = 0;
-    while (id < PMV_MAX_CAMERAS && ctx->cam_used[id]) id++;
-    REQ(id < PMV_MAX_CAMERAS, PMV_ERR_CAPACITY, "pmv_camera_create: the context holds %d cameras already (pmv_camera_destroy one)", PMV_MAX_CAMERAS);
-    CKC(hipSetDevice(ctx->device));
-    CKC(ctx->d_cams.ensure(PMV_MAX_CAMERAS * sizeof(LiftCam)));
-    CKC(hipMemcpy(ctx->d_cams.get() + id, &c, sizeof(c), hipMemcpyHostToDevice));   // (no launch in flight reads a free entry)
-    ctx->cam_used[id] = true;
-    ctx->cam_params[id] = *p;
-    *out_id = id;
-    return PMV_OK;
+    return camera_place(ctx, "pmv_camera_create", c, *p, out_id);
+}
+
+int pmv_camera_create_fisheye(pmv_ctx* ctx, const pmv_fisheye_params* p, int* out_id) {
+    REQ(ctx, PMV_ERR_INVALID, "pmv_camera_create_fisheye: null argument");
+    REQ(p && out_id, PMV_ERR_INVALID, "pmv_camera_create_fisheye: null argument");
+    REQ(std::isfinite(p->fx) && std::isfinite(p->fy) && p->fx != 0.0 && p->fy != 0.0, PMV_ERR_INVALID, "pmv_camera_create_fisheye: fx = %g, fy = %g: zero or not finite", p->fx, p->fy);
+    REQ(std::isfinite(p->cx) && std::isfinite(p->cy), PMV_ERR_INVALID, "pmv_camera_create_fisheye: cx = %g, cy = %g: not finite", p->cx, p->cy);
+    for (int k = 0; k < 4; k++) REQ(std::isfinite(p->k[k]), PMV_ERR_INVALID, "pmv_camera_create_fisheye: k[%d] = %g is not finite", k, p->k[k]);
+    LiftCam c{};
+    c.cx = p->cx; c.cy = p->cy; c.ifx = 1.0 / p->fx; c.ify = 1.0 / p->fy; c.fx = p->fx; c.fy = p->fy;
+    c.k1 = p->k[0]; c.k2 = p->k[1]; c.k3 = p->k[2]; c.k4 = p->k[3];
+    c.iters = 10; c.model = LIFT_FISHEYE;   // (the Newton loop's bound is fisheye_lift's own; iters is not read)
+    REQ(std::isfinite(c.ifx) && std::isfinite(c.ify), PMV_ERR_INVALID, "pmv_camera_create_fisheye: 1 / fx or 1 / fy is not finite (fx = %g, fy = %g)", p->fx, p->fy);
+    return camera_place(ctx, "pmv_camera_create_fisheye", c, pmv_camera_params{}, out_id);   // (no radial-tangential record goes with the entry)
 }
 
 int pmv_camera_destroy(pmv_ctx* ctx, int id) {

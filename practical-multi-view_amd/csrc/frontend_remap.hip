@@ -13,6 +13,7 @@
 // pmv_set_frame_preproc (the feeder, ingest_batch.hip) runs the same gather as k_remap_src: its taps come from the round's landing buffer,
 // not from a slot, so it writes level 0 of the slot directly and needs neither the scratch frame nor the list-form level-0 pass.
 #include "pmv_device.h"
+#include "pmv_lift.h"
 #include "pmv_prof.h"
 #include <climits>
 #include <cmath>
@@ -149,7 +150,8 @@ void remap_pack(const float* map_x, const float* map_y, int w, int h, uint8_t* o
     }
 }
 
-bool undistort_map(const double* K, const double* dist, const double* R, const double* newK, int w, int h, float* map_x, float* map_y) {
+// (newK R)^-1 by adjugate and determinant, for the two map builders; false when newK R is singular
+static bool map_ray_matrix(const double* K, const double* R, const double* newK, double* iR) {
     const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     const double* Rm = R ? R : I;
     const double* N = newK ? newK : K;
@@ -160,9 +162,16 @@ bool undistort_map(const double* K, const double* dist, const double* R, const d
     const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
     const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
     if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
-    const double iR[9] = {c00 / det, (A[2] * A[7] - A[1] * A[8]) / det, (A[1] * A[5] - A[2] * A[4]) / det,
-                          c01 / det, (A[0] * A[8] - A[2] * A[6]) / det, (A[2] * A[3] - A[0] * A[5]) / det,
-                          c02 / det, (A[1] * A[6] - A[0] * A[7]) / det, (A[0] * A[4] - A[1] * A[3]) / det};
+    const double inv[9] = {c00 / det, (A[2] * A[7] - A[1] * A[8]) / det, (A[1] * A[5] - A[2] * A[4]) / det,
+                           c01 / det, (A[0] * A[8] - A[2] * A[6]) / det, (A[2] * A[3] - A[0] * A[5]) / det,
+                           c02 / det, (A[1] * A[6] - A[0] * A[7]) / det, (A[0] * A[4] - A[1] * A[3]) / det};
+    for (int k = 0; k < 9; k++) iR[k] = inv[k];
+    return true;
+}
+
+bool undistort_map(const double* K, const double* dist, const double* R, const double* newK, int w, int h, float* map_x, float* map_y) {
+    double iR[9];
+    if (!map_ray_matrix(K, R, newK, iR)) return false;
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4], k4 = dist[5], k5 = dist[6], k6 = dist[7];
     for (int i = 0; i < h; i++)
@@ -175,6 +184,26 @@ bool undistort_map(const double* K, const double* dist, const double* R, const d
             const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2;
             map_x[(size_t)i * w + j] = (float)(fx * xd + cx);
             map_y[(size_t)i * w + j] = (float)(fy * yd + cy);
+        }
+    return true;
+}
+
+// cv::fisheye::initUndistortRectifyMap: the ray of every pixel as above, then fisheye_project (pmv_lift.h, the one statement of the forward
+// model, here on the host); a pixel it refuses gets (-1, -1), the border under pmv_frames_remap
+bool fisheye_map(const double* K, const double* k4, const double* R, const double* newK, int w, int h, float* map_x, float* map_y) {
+    double iR[9];
+    if (!map_ray_matrix(K, R, newK, iR)) return false;
+    LiftCam c{};
+    c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5]; c.ifx = 1.0 / c.fx; c.ify = 1.0 / c.fy;
+    c.k1 = k4[0]; c.k2 = k4[1]; c.k3 = k4[2]; c.k4 = k4[3];
+    c.iters = 10; c.model = LIFT_FISHEYE;
+    for (int i = 0; i < h; i++)
+        for (int j = 0; j < w; j++) {
+            const double X = iR[0] * j + iR[1] * i + iR[2], Y = iR[3] * j + iR[4] * i + iR[5], W = iR[6] * j + iR[7] * i + iR[8];
+            float u, v;
+            const bool ok = fisheye_project(c, X, Y, W, &u, &v);
+            map_x[(size_t)i * w + j] = ok ? u : -1.f;
+            map_y[(size_t)i * w + j] = ok ? v : -1.f;
         }
     return true;
 }

@@ -412,6 +412,9 @@ size_t remap_map_bytes(int w, int h);
 void remap_pack(const float* map_x, const float* map_y, int w, int h, uint8_t* out);
 // cv::initUndistortRectifyMap(K, dist8, R or identity, newK or K, (w, h), CV_32FC1), evaluated per pixel in double; false: newK R is singular
 bool undistort_map(const double* K, const double* dist8, const double* R, const double* newK, int w, int h, float* map_x, float* map_y);
+// cv::fisheye::initUndistortRectifyMap(K, k4, R or identity, newK or K, (w, h), CV_32FC1) in the same manner, through fisheye_project
+// (pmv_lift.h) on the host; a pixel the projection refuses gets (-1, -1); false: newK R is singular
+bool fisheye_map(const double* K, const double* k4, const double* R, const double* newK, int w, int h, float* map_x, float* map_y);
 // k_remap over n records in device-visible memory; d_geom[record.geom] (device memory) is the record's frame. max_w, max_h: the largest
 // level-0 width and height among the records - they size the grid; a thread beyond its own frame leaves before its first load. Booked under
 // the level-0 profiling class.
