@@ -96,28 +96,26 @@ struct FivePointProblem {
     int n, n_hyp; float thr;
 };
 hipError_t launch_fivepoint_batch(hipStream_t s, const FivePointProblem* d_probs, int n_probs, int max_hyp);
-// one whole cv::findEssentialMat RANSAC (k_essential_ransac, backend_fivepoint.hip): one workgroup runs the adaptive loop of one request
-struct EssentialProblem {
-    const double* q1; const double* q2;   // device: n normalised points (x, y) each
-    const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^5), -inf where RANSACUpdateNumIters returns 0]
-    char* out;                            // mapped pinned result block: [WholeResultHdr (E, found, samples drawn, best count, done_seq) | mask n bytes]
+// one whole RANSAC request (pmv_ransac.h): one workgroup runs the adaptive loop of one cv::findEssentialMat (k_essential_ransac,
+// backend_fivepoint.hip; Pt = double) or cv::findFundamentalMat call (k_fundamental_ransac, backend_fundamental.hip; Pt = float)
+template <class Pt> struct WholeProblem {
+    const Pt* p1; const Pt* p2;           // device: n points (x, y) each - normalised for E, pixel positions for F
+    const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^S), -inf where RANSACUpdateNumIters returns 0], S = 5 or 7
+    char* out;                            // mapped pinned result block: [WholeResultHdr (E or F, found, samples drawn, best count, done_seq) | mask n bytes]
     int n, max_iters; float thr;
     unsigned done_seq;                    // != 0; the kernel's last store, into WholeResultHdr::done (the caller waits for it)
 };
-static_assert(sizeof(EssentialProblem) <= ESS_HDR, "the record is the header of the input block");
+using EssentialProblem = WholeProblem<double>;
+using FundamentalProblem = WholeProblem<float>;
+static_assert(sizeof(WholeProblem<double>) <= ESS_HDR, "the record is the header of the input block");
+// the record of a request of n points with cv's iteration cap and the threshold in the points' unit
+template <class Pt> inline WholeProblem<Pt> whole_problem(const Pt* p1, const Pt* p2, const double* iters, char* out, int n, double threshold, unsigned done_seq) {
+    return WholeProblem<Pt>{p1, p2, iters, out, n, 1000, (float)(threshold * threshold), done_seq};
+}
 constexpr int ESS_MAX_WAVES = 16;   // hypotheses per in-kernel round at most (wavefronts of the workgroup)
 constexpr int ESS_DEFAULT_WAVES = 8;   // R of DESIGN.md §4: 8 x 6.2 KB = 49 KB of LDS, three workgroups per CU
 int essential_round_width();        // hypotheses per in-kernel round (PMV_ESSENTIAL_R overrides the default, 1..ESS_MAX_WAVES)
 hipError_t launch_essential_ransac(hipStream_t s, const EssentialProblem* d_probs, int n_probs);
-// one whole cv::findFundamentalMat RANSAC (k_fundamental_ransac, backend_fundamental.hip): one workgroup runs the adaptive loop of one request
-struct FundamentalProblem {
-    const float* p1; const float* p2;     // device: n pixel positions (x, y) each
-    const double* iters;                  // device: the table of EssentialProblem::iters for 7 model points
-    char* out;                            // mapped pinned result block in EssentialProblem::out's layout, F in the place of E
-    int n, max_iters; float thr;
-    unsigned done_seq;                    // != 0; the kernel's last store, as EssentialProblem::done_seq
-};
-static_assert(sizeof(FundamentalProblem) <= ESS_HDR, "the record is the header of the input block");
 constexpr int FUND_MAX_R = 64;       // hypotheses per in-kernel round at most (one lane of a wavefront each)
 constexpr int FUND_DEFAULT_R = 64;   // R of DESIGN.md §4 (measured: the widest round is the fastest on eight of nine ubench rows)
 int fundamental_round_width();       // hypotheses per in-kernel round (PMV_FUNDAMENTAL_R overrides the default, 1..FUND_MAX_R)

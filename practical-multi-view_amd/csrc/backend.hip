@@ -619,6 +619,35 @@ int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const doubl
 
 }  // extern "C"
 
+// ---- the two whole-RANSAC calls (pmv_ransac.h): what their prepare halves and their single calls share --------------------------------------
+// The tail of either *_prepare, once the points and the iteration table stand in b's pinned block by L: the record points into the device
+// in-block d_in and at the mapped result block, takes the set's next sequence number, whose word it clears, and goes into the in-block
+template <class Pt> static void whole_record(BackendBuffers* b, char* d_in, const WholeLayout& L, int n, double threshold, WholeProblem<Pt>* P) {
+    if (++b->done_seq == 0) b->done_seq = 1;
+    *P = whole_problem((const Pt*)(d_in + L.p1), (const Pt*)(d_in + L.p2), (const double*)(d_in + L.iters), b->h_stage.dm() + L.out, n, threshold, b->done_seq);
+    *whole_done_word(b, L) = 0;
+    *(WholeProblem<Pt>*)((char*)b->h_stage + L.rec) = *P;
+}
+// A checked single call on the context's own set: prepare (either *_prepare, bound to the call's arguments), stage-in into the set's d_in,
+// one workgroup of `launch`, the wait for the request's completion word, the copy-out
+template <class Pt, class Prepare>
+static int whole_single(pmv_ctx* ctx, Prepare prepare, Buf<char> BackendBuffers::*d_in, hipError_t (*launch)(hipStream_t, const WholeProblem<Pt>*, int), int n,
+                        double* M9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    BackendBuffers* b = ctx->be;
+    hipStream_t s = ctx->s_back;
+    WholeProblem<Pt> P;
+    WholeLayout L;
+    if (const int rc = prepare(b, &P, &L)) return rc;
+    char* d = b->*d_in;
+    CKC(stage_block(s, b->h_stage.dm(), d, L.in_bytes, 8));
+    CKC(launch(s, (const WholeProblem<Pt>*)d, 1));
+    if (const int rc = wait_done_word(ctx, s, whole_done_word(b, L), P.done_seq, back_wait_by_word())) return rc;
+    whole_finish(b, n, L, M9, mask, out_found, out_samples_drawn);
+    return PMV_OK;
+}
+
 // ---- whole findEssentialMat RANSAC on the device (k_essential_ransac): check / prepare / finish -----------------------------------------
 int pmv::essential_check(pmv_ctx* ctx, const char* who, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold,
                          double* E9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
@@ -645,16 +674,7 @@ int pmv::essential_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* p1, co
     }
     threshold /= (fx + fy) / 2;
     vo::five_point_iters_table(n, prob, h_it + 1, h_it);
-    P->q1 = (const double*)(b->d_ess_in + L.p1);
-    P->q2 = (const double*)(b->d_ess_in + L.p2);
-    P->iters = (const double*)(b->d_ess_in + L.iters);
-    P->out = b->h_stage.dm() + L.out;
-    P->n = n; P->max_iters = 1000;
-    P->thr = (float)(threshold * threshold);
-    if (++b->done_seq == 0) b->done_seq = 1;
-    P->done_seq = b->done_seq;
-    *whole_done_word(b, L) = 0;
-    *(EssentialProblem*)(hs + L.rec) = *P;
+    whole_record(b, b->d_ess_in, L, n, threshold, P);
     *Lout = L;
     return PMV_OK;
 }
@@ -704,16 +724,7 @@ int pmv::fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, c
     memcpy(hs + L.p1, p1, (size_t)n * 8);
     memcpy(hs + L.p2, p2, (size_t)n * 8);
     vo::ransac_iters_table(n, confidence, 7, h_it + 1, h_it);
-    P->p1 = (const float*)(b->d_fund_in + L.p1);
-    P->p2 = (const float*)(b->d_fund_in + L.p2);
-    P->iters = (const double*)(b->d_fund_in + L.iters);
-    P->out = b->h_stage.dm() + L.out;
-    P->n = n; P->max_iters = 1000;
-    P->thr = (float)(threshold * threshold);
-    if (++b->done_seq == 0) b->done_seq = 1;
-    P->done_seq = b->done_seq;
-    *whole_done_word(b, L) = 0;
-    *(FundamentalProblem*)(hs + L.rec) = *P;
+    whole_record(b, b->d_fund_in, L, n, threshold, P);
     *Lout = L;
     return PMV_OK;
 }
@@ -725,18 +736,8 @@ int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_x
     if (const int rc = essential_check(ctx, "pmv_find_essential_mat", p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn)) return rc;
     *out_found = 0; *out_samples_drawn = 0;
     if (n < 5) { memset(mask, 0, (size_t)n); return PMV_OK; }   // fewer points than a sample: no model
-    tl_prof = &ctx->prof;
-    CKC(hipSetDevice(ctx->device));
-    BackendBuffers* b = ctx->be;
-    hipStream_t s = ctx->s_back;
-    EssentialProblem P;
-    WholeLayout L;
-    if (const int rc = essential_prepare(ctx, b, p1_xy, p2_xy, n, K, prob, threshold, &P, &L)) return rc;
-    CKC(stage_block(s, b->h_stage.dm(), b->d_ess_in, L.in_bytes, 8));
-    CKC(launch_essential_ransac(s, (const EssentialProblem*)b->d_ess_in, 1));
-    if (const int rc = wait_done_word(ctx, s, whole_done_word(b, L), P.done_seq, back_wait_by_word())) return rc;
-    whole_finish(b, n, L, E9, mask, out_found, out_samples_drawn);
-    return PMV_OK;
+    const auto prepare = [&](BackendBuffers* b, EssentialProblem* P, WholeLayout* L) { return essential_prepare(ctx, b, p1_xy, p2_xy, n, K, prob, threshold, P, L); };
+    return whole_single(ctx, prepare, &BackendBuffers::d_ess_in, launch_essential_ransac, n, E9, mask, out_found, out_samples_drawn);
 }
 
 int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3, uint8_t* mask,
@@ -765,18 +766,8 @@ int pmv_recover_pose(pmv_ctx* ctx, const double* E9, const double* p1_xy, const 
 int pmv_find_fundamental_mat(pmv_ctx* ctx, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
                              int* out_found, int* out_samples_drawn) {
     if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
-    tl_prof = &ctx->prof;
-    CKC(hipSetDevice(ctx->device));
-    BackendBuffers* b = ctx->be;
-    hipStream_t s = ctx->s_back;
-    FundamentalProblem P;
-    WholeLayout L;
-    if (const int rc = fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, &P, &L)) return rc;
-    CKC(stage_block(s, b->h_stage.dm(), b->d_fund_in, L.in_bytes, 8));
-    CKC(launch_fundamental_ransac(s, (const FundamentalProblem*)b->d_fund_in, 1));
-    if (const int rc = wait_done_word(ctx, s, whole_done_word(b, L), P.done_seq, back_wait_by_word())) return rc;
-    whole_finish(b, n, L, F9, mask, out_found, out_samples_drawn);
-    return PMV_OK;
+    const auto prepare = [&](BackendBuffers* b, FundamentalProblem* P, WholeLayout* L) { return fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, P, L); };
+    return whole_single(ctx, prepare, &BackendBuffers::d_fund_in, launch_fundamental_ransac, n, F9, mask, out_found, out_samples_drawn);
 }
 
 int pmv_debug_fundamental_iters_table(int n, double confidence, double* out_denoms, double* out_num) {

@@ -16,6 +16,7 @@
 #include "backend.h"
 #include "pmv_prof.h"
 #include "pmv_dense.h"
+#include "pmv_ransac.h"
 #include <float.h>
 #include <cstdlib>
 
@@ -356,147 +357,46 @@ __global__ __launch_bounds__(64) void k_fivepoint_score(const FivePointProblem* 
 }
 
 // ---- the whole adaptive RANSAC of one cv::findEssentialMat call in ONE workgroup (pmv_find_essential_mat) ---------------------------------
-// R wavefronts = R hypotheses per in-kernel round. A round: thread 0 draws the next min(R, niters - iter) 5-subsets from the request's MWC
-// stream (vo_fivepoint.cpp:draw_subset, integer arithmetic); lane 0 of wave w solves hypothesis w with fp_essentials on the wave's own FP_WS
-// doubles of LDS; all waves score the round's (hypothesis, model) pairs (the k_fivepoint_score expression, wave-reduced counts); thread 0
-// replays find_essential_mat's bookkeeping in sample order - count > max(maxGood, 4), best E, maxGood, the niters update - and drops the
-// speculative samples past niters. No host round trip per round, and a request is over when ITS loop is: the last store of the workgroup
-// is the request's sequence number in its mapped pinned result block, which is what its caller waits for.
-// RANSACUpdateNumIters calls pow and log; the device's libm is not glibc's, so the host tabulates both per inlier count (EssentialProblem::iters)
-// and the kernel evaluates only the final expression: IEEE multiply, divide, compare, round-half-even.
-struct EssShared {
-    double best[9];
-    unsigned long long rng;
-    int idx[ESS_MAX_WAVES * 5], nm[ESS_MAX_WAVES], counts[ESS_MAX_WAVES * 10];
-    int iter, niters, max_good, drawn;
+// pmv_ransac.h's round structure with EMEstimatorCallback as the model: R wavefronts = R hypotheses per in-kernel round, lane 0 of wave w
+// solves hypothesis w with fp_essentials on the wave's own FP_WS doubles of LDS (samples at 750 and 760, models at 660); the error is the
+// k_fivepoint_score expression; checkSubset is the callback's default, so every draw is taken (vo_fivepoint.cpp:draw_subset).
+struct EssModel {
+    using Problem = EssentialProblem;
+    static constexpr int S = 5, MODELS = 10, MAX_R = ESS_MAX_WAVES, MAX_ATTEMPTS = 1;
+    struct Extra {};
+    using Shared = WholeShared<EssModel>;
+    __device__ static bool direct(int n) { return n == 5; }
+    __device__ static bool subset_ok(const Problem&, const int*, Extra&) { return true; }
+    // five_point_kernel on the points idx[0..4] (null: the first five) in the workspace ws; returns the number of models at ws + 660
+    __device__ static int solve_on(const Problem& P, const int* idx, double* ws) {
+        double* s1 = ws + 750; double* s2 = ws + 760;
+        #pragma unroll 1
+        for (int i = 0; i < 5; i++) {
+            const int k = idx ? idx[i] : i;
+            s1[2 * i] = P.p1[2 * k]; s1[2 * i + 1] = P.p1[2 * k + 1];
+            s2[2 * i] = P.p2[2 * k]; s2[2 * i + 1] = P.p2[2 * k + 1];
+        }
+        return fp_essentials(s1, s2, ws + 660, ws);
+    }
+    __device__ static bool solve_direct(const Problem& P, double* ws, Shared& sh) {
+        if (solve_on(P, nullptr, ws) == 0) return false;
+        #pragma unroll 1
+        for (int k = 0; k < 9; k++) sh.best[k] = ws[660 + k];
+        return true;
+    }
+    __device__ static void solve(const Problem& P, double* ws, Shared& sh, int R, int nh) {
+        const int wave = (int)threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) sh.nm[wave] = wave < nh ? solve_on(P, sh.idx + 5 * wave, ws + wave * FP_WS) : 0;
+    }
+    __device__ static double model(const double* ws, int R, int b, int mi, int k) { return ws[b * FP_WS + 660 + 9 * mi + k]; }
+    __device__ static float error(const double* E, const double* __restrict__ q1, const double* __restrict__ q2, int i) { return fp_sampson(E, q1, q2, i); }
 };
-__device__ inline int ess_update_iters(const double* __restrict__ tab, int good, int max_iters) {
-    const double num = tab[0], denom = tab[1 + good];
-    return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
-__device__ inline unsigned ess_rng_next(unsigned long long& st) { st = (unsigned long long)(unsigned)st * 4164903690U + (unsigned)(st >> 32); return (unsigned)st; }
 
 __global__ __launch_bounds__(64 * ESS_MAX_WAVES) void k_essential_ransac(const EssentialProblem* __restrict__ probs) { BACKEND_PRIO();
-    extern __shared__ double ess_lds[];   // R solver workspaces of FP_WS doubles, then EssShared
-    const int R = (int)(blockDim.x >> 6), tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    extern __shared__ double ess_lds[];   // R solver workspaces of FP_WS doubles, then the shared block
+    const int R = (int)(blockDim.x >> 6);
     const EssentialProblem P = probs[blockIdx.x];
-    double* ws = ess_lds + wave * FP_WS;
-    EssShared& sh = *(EssShared*)(ess_lds + R * FP_WS);
-    const int n = P.n;
-    if (tid == 0) { sh.iter = 0; sh.niters = P.max_iters; sh.max_good = 0; sh.drawn = 0; sh.rng = ~0ull; }
-    __syncthreads();
-    if (n == 5) {   // one solve without RANSAC: the first model wins, every point is an inlier
-        if (tid == 0) {
-            double* s1 = ws + 750; double* s2 = ws + 760;
-            #pragma unroll 1
-            for (int k = 0; k < 10; k++) { s1[k] = P.q1[k]; s2[k] = P.q2[k]; }
-            const int nm = fp_essentials(s1, s2, ws + 660, ws);
-            if (nm > 0) {
-                #pragma unroll 1
-                for (int k = 0; k < 9; k++) sh.best[k] = ws[660 + k];
-                sh.max_good = 5;
-            }
-        }
-        __syncthreads();
-    } else {
-        for (;;) {
-            const int iter = sh.iter, niters = sh.niters;   // (written by thread 0 before the barrier that ended the previous round)
-            if (iter >= niters) break;
-            const int nb = min(R, niters - iter);
-            if (tid == 0) {
-                unsigned long long st = sh.rng;
-                #pragma unroll 1
-                for (int b = 0; b < nb; b++) {
-                    int* idx = sh.idx + 5 * b;
-                    #pragma unroll 1
-                    for (int i = 0; i < 5;) {
-                        const int v = (int)(ess_rng_next(st) % (unsigned)n);
-                        idx[i] = v;
-                        int j = 0;
-                        #pragma unroll 1
-                        for (; j < i; j++) if (v == idx[j]) break;
-                        if (j == i) i++;
-                    }
-                }
-                sh.rng = st;
-            }
-            __syncthreads();
-            if (lane == 0) {
-                int nm = 0;
-                if (wave < nb) {
-                    double* s1 = ws + 750; double* s2 = ws + 760;
-                    #pragma unroll 1
-                    for (int i = 0; i < 5; i++) {
-                        const int k = sh.idx[5 * wave + i];
-                        s1[2 * i] = P.q1[2 * k]; s1[2 * i + 1] = P.q1[2 * k + 1];
-                        s2[2 * i] = P.q2[2 * k]; s2[2 * i + 1] = P.q2[2 * k + 1];
-                    }
-                    nm = fp_essentials(s1, s2, ws + 660, ws);
-                }
-                sh.nm[wave] = nm;
-            }
-            __syncthreads();
-            #pragma unroll 1
-            for (int p = wave; p < nb * 10; p += R) {
-                const int b = p / 10, mi = p - 10 * b;
-                if (mi >= sh.nm[b]) continue;   // (uniform over the wave)
-                const double* Em = ess_lds + b * FP_WS + 660 + 9 * mi;
-                double E[9];
-#pragma unroll
-                for (int k = 0; k < 9; k++) E[k] = Em[k];
-                int good = 0;
-                #pragma unroll 1
-                for (int i = lane; i < n; i += 64) good += fp_sampson(E, P.q1, P.q2, i) <= P.thr;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) good += __shfl_xor(good, o, 64);
-                if (lane == 0) sh.counts[p] = good;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int it = iter, ni = niters, mg = sh.max_good;
-                #pragma unroll 1
-                for (int b = 0; b < nb && it < ni; b++, it++) {
-                    #pragma unroll 1
-                    for (int mi = 0; mi < sh.nm[b]; mi++) {
-                        const int c = sh.counts[10 * b + mi];
-                        if (c > max(mg, 4)) {
-                            const double* Em = ess_lds + b * FP_WS + 660 + 9 * mi;
-                            #pragma unroll 1
-                            for (int k = 0; k < 9; k++) sh.best[k] = Em[k];
-                            mg = c;
-                            ni = ess_update_iters(P.iters, mg, ni);
-                        }
-                    }
-                }
-                sh.drawn += it - iter;
-                sh.iter = it; sh.niters = ni; sh.max_good = mg;
-            }
-            __syncthreads();
-        }
-    }
-    // result block: mask of the best model (err <= thr, recomputed once), E, found, samples drawn; the sequence number last
-    const bool found = sh.max_good > 0;
-    uint8_t* mask = (uint8_t*)(P.out + ESS_OUT_HDR);
-    if (found && n > 5) {
-        double E[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) E[k] = sh.best[k];
-        #pragma unroll 1
-        for (int i = tid; i < n; i += (int)blockDim.x) mask[i] = (uint8_t)(fp_sampson(E, P.q1, P.q2, i) <= P.thr);
-    } else {
-        #pragma unroll 1
-        for (int i = tid; i < n; i += (int)blockDim.x) mask[i] = found ? 1 : 0;
-    }
-    if (tid == 0) {
-        double* Eo = (double*)P.out;
-        #pragma unroll 1
-        for (int k = 0; k < 9; k++) Eo[k] = found ? sh.best[k] : 0.0;
-        int* info = (int*)(P.out + ESS_OUT_INFO);
-        info[0] = found ? 1 : 0; info[1] = sh.drawn; info[2] = sh.max_good;
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store((unsigned*)(P.out + ESS_OUT_DONE), P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    whole_ransac<EssModel>(P, ess_lds, *(EssModel::Shared*)(ess_lds + R * FP_WS), R, R);
 }
 
 int essential_round_width() {
@@ -508,9 +408,9 @@ hipError_t launch_essential_ransac(hipStream_t s, const EssentialProblem* d_prob
     if (n_probs <= 0) return hipSuccess;
     if (!d_probs) return hipErrorInvalidValue;
     const int R = essential_round_width();
-    const size_t lds = (size_t)R * FP_WS * sizeof(double) + sizeof(EssShared);
+    const size_t lds = (size_t)R * FP_WS * sizeof(double) + sizeof(EssModel::Shared);
     if (lds > 64 * 1024) {   // (above the default limit of a workgroup; the CU has 160 KiB)
-        static const hipError_t attr = hipFuncSetAttribute((const void*)k_essential_ransac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)ESS_MAX_WAVES * FP_WS * sizeof(double) + sizeof(EssShared)));
+        static const hipError_t attr = hipFuncSetAttribute((const void*)k_essential_ransac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)ESS_MAX_WAVES * FP_WS * sizeof(double) + sizeof(EssModel::Shared)));
         if (attr != hipSuccess) return attr;
     }
     ProfScope ps(K_FIVEPOINT, s);

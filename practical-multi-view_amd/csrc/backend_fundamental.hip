@@ -1,11 +1,8 @@
 // gfx950 fundamental-matrix RANSAC: cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence, mask) for n >= 15 correspondences
 // (pmv_find_fundamental_mat, include/pmv_hip.h), the rejectWithF of a KLT loop.
-// k_fundamental_ransac: the whole adaptive RANSAC of one call in ONE workgroup, in the round structure of k_essential_ransac
-// (backend_fivepoint.hip): thread 0 draws the next min(R, niters - iter) 7-subsets from the call's MWC stream (getSubset with
-// FMEstimatorCallback::checkSubset: the collinearity test on the last point, up to 10000 attempts per subset), the seven-point solver runs,
-// all waves score the round's (hypothesis, model) pairs with wave-reduced counts, thread 0 replays the bookkeeping in sample order - count >
-// max(maxGood, 6), best F, maxGood, the niters update - and drops the speculative samples past niters. The last store of the workgroup is
-// the request's sequence number in its mapped pinned result block (ESS_OUT_HDR layout), which is what its caller waits for.
+// k_fundamental_ransac: the whole adaptive RANSAC of one call in ONE workgroup, in the round structure that pmv_ransac.h states for it and
+// for k_essential_ransac (backend_fivepoint.hip); this file holds what FMEstimatorCallback holds: checkSubset (the collinearity test on the
+// subset's last point, up to 10000 attempts per subset), the seven-point solver and the error.
 // What differs from the five-point kernel follows from the size of the solver (a 7x9 elimination, a cubic, up to three 3x3 builds: ~10^3
 // dependent FP64 operations instead of ~10^5): ONE LANE solves one hypothesis, so a round holds up to 64 of them, and their workspaces
 // (FD_WS doubles each) are interleaved in LDS - element k of hypothesis h at k * R + h - so that the lanes of a wave, which all execute the
@@ -13,10 +10,11 @@
 // lane of a half-wave on the same bank). As locals the arrays would be indexed dynamically, i.e. scratch memory (backend_fivepoint.hip:120);
 // no loop of the solver is unrolled.
 // Every solver statement is tests/twin/fundamental_twin.cpp's, in its order: IEEE + - * / sqrt only (-ffp-contract=off, no fast-math), so
-// found, F, the mask and the sample count are the twin's bits. pow and log of RANSACUpdateNumIters stay on the host (FundamentalProblem::iters).
+// found, F, the mask and the sample count are the twin's bits.
 #include "pmv_ctx.h"
 #include "backend.h"
 #include "pmv_prof.h"
+#include "pmv_ransac.h"
 #include <float.h>
 #include <atomic>
 #include <cstdlib>
@@ -27,23 +25,6 @@ namespace {
 
 constexpr int FD_WS = 108;           // doubles per hypothesis: A 7x9 at 0 | f1 at 63 | f2 at 72 | up to three models at 81
 constexpr int FD_THREADS = 512;      // 8 waves score; the lanes of wave 0 solve
-constexpr int FD_MAX_ATTEMPTS = 10000;
-
-struct FundShared {
-    double best[9];
-    unsigned long long rng;
-    int idx[FUND_MAX_R * 7], nm[FUND_MAX_R], counts[FUND_MAX_R * 3];
-    unsigned char cp[FUND_MAX_R * 9];   // column permutations of the eliminations, interleaved like the workspaces
-    float sp[28];                       // the points of the subset thread 0 is testing: image 1, then image 2
-    int iter, niters, max_good, drawn, fail_at;
-};
-static_assert((size_t)FUND_MAX_R * FD_WS * sizeof(double) + sizeof(FundShared) <= 64 * 1024, "the workgroup's LDS stays within the default limit");
-
-__device__ inline unsigned fd_rng_next(unsigned long long& st) { st = (unsigned long long)(unsigned)st * 4164903690U + (unsigned)(st >> 32); return (unsigned)st; }
-__device__ inline int fd_update_iters(const double* __restrict__ tab, int good, int max_iters) {
-    const double num = tab[0], denom = tab[1 + good];
-    return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
 
 // haveCollinearPoints on the subset's last point: against every pair (j, k < j) of the earlier ones; q: the subset's 7 points (x, y)
 __device__ inline bool fd_last_point_collinear(const float* q) {
@@ -267,116 +248,42 @@ __device__ inline float fd_error(const double* F, const float* __restrict__ p1, 
     return (float)(e1 < e2 ? e2 : e1);
 }
 
+// FMEstimatorCallback as pmv_ransac.h's model: one lane per hypothesis on the interleaved workspaces, checkSubset on the subset's last point
+struct FundModel {
+    using Problem = FundamentalProblem;
+    static constexpr int S = 7, MODELS = 3, MAX_R = FUND_MAX_R, MAX_ATTEMPTS = 10000;
+    struct Extra {
+        alignas(8) float sp[28];            // the points of the subset thread 0 is testing: image 1, then image 2 (aligned: a point is one ds_read_b64)
+        unsigned char cp[FUND_MAX_R * 9];   // column permutations of the eliminations, interleaved like the workspaces
+    };
+    using Shared = WholeShared<FundModel>;
+    __device__ static bool direct(int) { return false; }   // (fundamental_check: n >= 15)
+    __device__ static bool solve_direct(const Problem&, double*, Shared&) { return false; }
+    __device__ static bool subset_ok(const Problem& P, const int* idx, Extra& x) {
+        // the subset's points first, all loads in flight together: the test below then runs on LDS instead of waiting for global
+        // memory once per pair (measured: ~10 us per subset before, which made the draw the longest part of a round)
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+            const float2 a = ((const float2*)P.p1)[idx[i]], c = ((const float2*)P.p2)[idx[i]];
+            x.sp[2 * i] = a.x; x.sp[2 * i + 1] = a.y; x.sp[14 + 2 * i] = c.x; x.sp[15 + 2 * i] = c.y;
+        }
+        return !fd_last_point_collinear(x.sp) && !fd_last_point_collinear(x.sp + 14);
+    }
+    __device__ static void solve(const Problem& P, double* ws, Shared& sh, int R, int nh) {
+        const int tid = (int)threadIdx.x;
+        if (tid < nh) sh.nm[tid] = fd_seven_point(P.p1, P.p2, sh.idx + 7 * tid, ws, sh.x.cp, R, tid);
+    }
+    __device__ static double model(const double* ws, int R, int b, int mi, int k) { return ws[(81 + 9 * mi + k) * R + b]; }
+    __device__ static float error(const double* F, const float* __restrict__ p1, const float* __restrict__ p2, int i) { return fd_error(F, p1, p2, i); }
+};
+static_assert((size_t)FUND_MAX_R * FD_WS * sizeof(double) + sizeof(FundModel::Shared) <= 64 * 1024, "the workgroup's LDS stays within the default limit");
+
 }  // namespace
 
 __global__ __launch_bounds__(FD_THREADS) void k_fundamental_ransac(const FundamentalProblem* __restrict__ probs, int R) { BACKEND_PRIO();
-    extern __shared__ __attribute__((aligned(16))) double fund_lds[];   // R interleaved solver workspaces of FD_WS doubles, then FundShared
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    constexpr int NW = FD_THREADS / 64;
+    extern __shared__ __attribute__((aligned(16))) double fund_lds[];   // R interleaved solver workspaces of FD_WS doubles, then the shared block
     const FundamentalProblem P = probs[blockIdx.x];
-    double* ws = fund_lds;
-    FundShared& sh = *(FundShared*)(fund_lds + R * FD_WS);
-    const int n = P.n;
-    if (tid == 0) { sh.iter = 0; sh.niters = P.max_iters; sh.max_good = 0; sh.drawn = 0; sh.rng = ~0ull; }
-    __syncthreads();
-    for (;;) {
-        const int iter = sh.iter, niters = sh.niters;   // (written by thread 0 before the barrier that ended the previous round)
-        if (iter >= niters) break;
-        const int nb = min(R, niters - iter);
-        if (tid == 0) {   // the round's subsets; fail_at: the first sample of the round for which getSubset ran out of attempts (nb: none)
-            unsigned long long st = sh.rng;
-            int fail_at = nb;
-            #pragma unroll 1
-            for (int b = 0; b < nb; b++) {
-                int* idx = sh.idx + 7 * b;
-                int attempt = 0;
-                #pragma unroll 1
-                for (; attempt < FD_MAX_ATTEMPTS; attempt++) {
-                    #pragma unroll 1
-                    for (int i = 0; i < 7;) {
-                        const int v = (int)(fd_rng_next(st) % (unsigned)n);
-                        idx[i] = v;
-                        int j = 0;
-                        #pragma unroll 1
-                        for (; j < i; j++) if (v == idx[j]) break;
-                        if (j == i) i++;
-                    }
-                    // the subset's points first, all loads in flight together: the test below then runs on LDS instead of waiting for global
-                    // memory once per pair (measured: ~10 us per subset before, which made the draw the longest part of a round)
-#pragma unroll
-                    for (int i = 0; i < 7; i++) {
-                        const float2 a = ((const float2*)P.p1)[idx[i]], c = ((const float2*)P.p2)[idx[i]];
-                        sh.sp[2 * i] = a.x; sh.sp[2 * i + 1] = a.y; sh.sp[14 + 2 * i] = c.x; sh.sp[15 + 2 * i] = c.y;
-                    }
-                    if (!fd_last_point_collinear(sh.sp) && !fd_last_point_collinear(sh.sp + 14)) break;
-                }
-                if (attempt == FD_MAX_ATTEMPTS) { fail_at = b; break; }
-            }
-            sh.rng = st; sh.fail_at = fail_at;
-        }
-        __syncthreads();
-        const int nh = sh.fail_at;   // hypotheses to solve and score: the samples in front of a failed draw
-        if (tid < nh) sh.nm[tid] = fd_seven_point(P.p1, P.p2, sh.idx + 7 * tid, ws, sh.cp, R, tid);
-        __syncthreads();
-        #pragma unroll 1
-        for (int p = wave; p < nh * 3; p += NW) {
-            const int b = p / 3, mi = p - 3 * b;
-            if (mi >= sh.nm[b]) continue;   // (uniform over the wave)
-            double F[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) F[k] = ws[(81 + 9 * mi + k) * R + b];
-            int good = 0;
-            #pragma unroll 1
-            for (int i = lane; i < n; i += 64) good += fd_error(F, P.p1, P.p2, i) <= P.thr;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) good += __shfl_xor(good, o, 64);
-            if (lane == 0) sh.counts[p] = good;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int it = iter, ni = niters, mg = sh.max_good;
-            #pragma unroll 1
-            for (int b = 0; b < nb && it < ni; b++, it++) {
-                if (b == nh) { ni = it; break; }   // getSubset failed for this sample: the loop ends here (at sample 0 without a model)
-                #pragma unroll 1
-                for (int mi = 0; mi < sh.nm[b]; mi++) {
-                    const int c = sh.counts[3 * b + mi];
-                    if (c > max(mg, 6)) {
-                        #pragma unroll 1
-                        for (int k = 0; k < 9; k++) sh.best[k] = ws[(81 + 9 * mi + k) * R + b];
-                        mg = c;
-                        ni = fd_update_iters(P.iters, mg, ni);
-                    }
-                }
-            }
-            sh.drawn += it - iter;
-            sh.iter = it; sh.niters = ni; sh.max_good = mg;
-        }
-        __syncthreads();
-    }
-    // result block: mask of the best model (err <= thr, recomputed once), F, found, samples drawn; the sequence number last
-    const bool found = sh.max_good > 0;
-    uint8_t* mask = (uint8_t*)(P.out + ESS_OUT_HDR);
-    if (found) {
-        double F[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) F[k] = sh.best[k];
-        #pragma unroll 1
-        for (int i = tid; i < n; i += FD_THREADS) mask[i] = (uint8_t)(fd_error(F, P.p1, P.p2, i) <= P.thr);
-    } else {
-        #pragma unroll 1
-        for (int i = tid; i < n; i += FD_THREADS) mask[i] = 0;
-    }
-    if (tid == 0) {
-        double* Fo = (double*)P.out;
-        #pragma unroll 1
-        for (int k = 0; k < 9; k++) Fo[k] = found ? sh.best[k] : 0.0;
-        int* info = (int*)(P.out + ESS_OUT_INFO);
-        info[0] = found ? 1 : 0; info[1] = sh.drawn; info[2] = sh.max_good;
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store((unsigned*)(P.out + ESS_OUT_DONE), P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    whole_ransac<FundModel>(P, fund_lds, *(FundModel::Shared*)(fund_lds + R * FD_WS), R, FD_THREADS / 64);
 }
 
 namespace {
@@ -395,7 +302,7 @@ hipError_t launch_fundamental_ransac(hipStream_t s, const FundamentalProblem* d_
     if (n_probs <= 0) return hipSuccess;
     if (!d_probs) return hipErrorInvalidValue;
     const int R = fundamental_round_width();
-    const size_t lds = (size_t)R * FD_WS * sizeof(double) + sizeof(FundShared);
+    const size_t lds = (size_t)R * FD_WS * sizeof(double) + sizeof(FundModel::Shared);
     ProfScope ps(K_FIVEPOINT, s);
     hipLaunchKernelGGL(k_fundamental_ransac, dim3(n_probs), dim3(FD_THREADS), lds, s, d_probs, R);
     return hipGetLastError();

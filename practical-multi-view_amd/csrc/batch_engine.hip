@@ -100,8 +100,9 @@ struct FPReq : Req { BackendBuffers* b; FivePointProblem P; FivePointLayout L; }
 // from the submit until the combiner has released the record after the round, and the seq's next call of that kind waits for that before it
 // fills the record again.
 struct WholeReq : Req { BackendBuffers* b = nullptr; WholeLayout L{}; std::atomic<int> inflight{0}; };
-struct EssReq : WholeReq { EssentialProblem P; };
-struct FundReq : WholeReq { FundamentalProblem P; };
+template <class Pt> struct WholeReqOf : WholeReq { WholeProblem<Pt> P; };
+using EssReq = WholeReqOf<double>;
+using FundReq = WholeReqOf<float>;
 
 // per-round scratch of a combiner: grows with slack (GROW_SLACK), in HBM or in mapped pinned memory (.dev = the address kernels use)
 struct DScratch : Growable { DScratch() : Growable(MEM_DEVICE, GROW_SLACK) {} };
@@ -1308,44 +1309,41 @@ static int wait_whole(pmv_ctx* ctx, WholeReq& r, volatile unsigned* word, unsign
     }
 }
 
-// pmv_find_essential_mat's contract through the five-point combiner. The caller waits for whichever comes first: the completion word that
+// pmv_find_essential_mat's or pmv_find_fundamental_mat's contract through the five-point combiner, behind the call's argument check: the
+// request is one workgroup of the round's launch of its kind. The caller waits for whichever comes first: the completion word that
 // its own workgroup stores last into the seq's pinned result block, or the combiner's done flag after the round's stream sync (the only
 // one a failed launch gives). After the word the workgroup touches nothing of the seq's blocks any more, so the seq's next call may use them
 // while the round's other workgroups are still running; only the request record stays taken until the combiner has released it.
+// prepare: either *_prepare, bound to the call's arguments.
+template <class Pt, class Prepare>
+static int engine_whole(BatchEngine* E, WholeReqOf<Pt>& r, int kind, int seq, Prepare prepare, int n, double* M9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
+    r.kind = kind; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
+    if (const int rc = prepare(r.b, &r.P, &r.L)) return rc;
+    r.done.store(0, std::memory_order_relaxed);
+    r.inflight.store(1, std::memory_order_release);
+    enqueue(E->queue[R_FP], &r);
+    if (const int rc = wait_whole(E->ctx, r, whole_done_word(r.b, r.L), r.P.done_seq)) return rc;
+    whole_finish(r.b, n, r.L, M9, mask, out_found, out_samples_drawn);
+    return PMV_OK;
+}
+
 int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
                      uint8_t* mask, int* out_found, int* out_samples_drawn) {
     pmv_ctx* ctx = E->ctx;
     if (const int rc = essential_check(ctx, "pmv_find_essential_mat", p1_xy, p2_xy, n, K, prob, threshold, E9, mask, out_found, out_samples_drawn)) return rc;
     *out_found = 0; *out_samples_drawn = 0;
     if (n < 5) { memset(mask, 0, (size_t)n); return PMV_OK; }
-    EssReq& r = E->ess[(size_t)seq];
-    futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
-    r.kind = Q_ESSENTIAL; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
-    if (const int rc = essential_prepare(ctx, r.b, p1_xy, p2_xy, n, K, prob, threshold, &r.P, &r.L)) return rc;
-    r.done.store(0, std::memory_order_relaxed);
-    r.inflight.store(1, std::memory_order_release);
-    enqueue(E->queue[R_FP], &r);
-    if (const int rc = wait_whole(ctx, r, whole_done_word(r.b, r.L), r.P.done_seq)) return rc;
-    whole_finish(r.b, n, r.L, E9, mask, out_found, out_samples_drawn);
-    return PMV_OK;
+    const auto prepare = [&](BackendBuffers* b, EssentialProblem* P, WholeLayout* L) { return essential_prepare(ctx, b, p1_xy, p2_xy, n, K, prob, threshold, P, L); };
+    return engine_whole(E, E->ess[(size_t)seq], Q_ESSENTIAL, seq, prepare, n, E9, mask, out_found, out_samples_drawn);
 }
 
-// pmv_find_fundamental_mat's contract through the five-point combiner, in engine_essential's form: the request is one workgroup of the round's
-// k_fundamental_ransac launch and its caller returns with its own completion word.
 int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
                        int* out_found, int* out_samples_drawn) {
     pmv_ctx* ctx = E->ctx;
     if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
-    FundReq& r = E->fund[(size_t)seq];
-    futex_wait_while(&r.inflight, 1);   // the round of this seq's previous call is still in flight: its combiner has yet to release the record
-    r.kind = Q_FUNDAMENTAL; r.rc = PMV_OK; r.err[0] = 0; r.b = E->slots[(size_t)seq];
-    if (const int rc = fundamental_prepare(ctx, r.b, p1_xy, p2_xy, n, threshold, confidence, &r.P, &r.L)) return rc;
-    r.done.store(0, std::memory_order_relaxed);
-    r.inflight.store(1, std::memory_order_release);
-    enqueue(E->queue[R_FP], &r);
-    if (const int rc = wait_whole(ctx, r, whole_done_word(r.b, r.L), r.P.done_seq)) return rc;
-    whole_finish(r.b, n, r.L, F9, mask, out_found, out_samples_drawn);
-    return PMV_OK;
+    const auto prepare = [&](BackendBuffers* b, FundamentalProblem* P, WholeLayout* L) { return fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, P, L); };
+    return engine_whole(E, E->fund[(size_t)seq], Q_FUNDAMENTAL, seq, prepare, n, F9, mask, out_found, out_samples_drawn);
 }
 
 }  // namespace pmv

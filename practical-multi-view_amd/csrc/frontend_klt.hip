@@ -826,11 +826,8 @@ template <class... P, class... A> static hipError_t klt_launch(void (*kernel)(P.
 // rejectWithF's problem for the n1 tracks the filter left in the tracker's list 0 - their pixels, or with Q.on the virtual-camera points
 // k_klt_lift_f wrote - and libm's iteration table (n1 + 2 doubles) at tab_h
 static FundamentalProblem klt_f_problem(const KltTracker* t, const KltLiftFArgs& Q, int n1, double* tab_h, const double* tab_d) {
-    FundamentalProblem P;
-    P.p1 = Q.on ? Q.p1 : t->D.l_prev[0].d; P.p2 = Q.on ? Q.p2 : t->D.l_cur[0].d; P.iters = tab_d; P.out = t->D.f_out.d;
-    P.n = n1; P.max_iters = 1000; P.thr = (float)(t->p.f_threshold * t->p.f_threshold); P.done_seq = 1;
     vo::ransac_iters_table(n1, t->p.f_confidence, 7, tab_h + 1, tab_h);
-    return P;
+    return whole_problem<float>(Q.on ? Q.p1 : t->D.l_prev[0].d, Q.on ? Q.p2 : t->D.l_cur[0].d, tab_d, t->D.f_out.d, n1, t->p.f_threshold, 1);
 }
 // after the final wait: the header of the tracker's result block (`who`: pmv_klt_step or pmv_klt_step_many; j >= 0: tracker j of a group)
 static int klt_result_check(pmv_ctx* ctx, const KltTracker* t, bool stereo, const char* who, int j) {
