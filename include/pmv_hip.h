@@ -34,6 +34,7 @@
  *   pmv_triangulate_candidates             cv::recoverPose (triangulation + cheirality)  (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_find_essential_mat                 cv::findEssentialMat (the whole RANSAC)       (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
  *   pmv_find_fundamental_mat               cv::findFundamentalMat, FM_RANSAC (a KLT loop's rejectWithF; not a call of the reference)
+ *   pmv_find_homography                    cv::findHomography, RANSAC with its refit (planar scenes, pure rotations; not a call of the reference)
  *   pmv_recover_pose                       cv::recoverPose (the whole call)              (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_ba_residuals / pmv_ba_solve        ProjectionResidual + ceres::Solve             (ProjectionResidual.h:38-58,
  *                                          CeresBundleAdjustment.cpp:50-61)              -> BaseOptimizer.h:15
@@ -863,6 +864,55 @@ int pmv_debug_fundamental_r(void);
  * whole-RANSAC rounds (pmv_batch_find_fundamental_mat, pmv_batch_find_essential_mat, device_fivepoint = 2) since the context was created. */
 int pmv_debug_whole_rounds(pmv_ctx* ctx, long long* out3);
 
+/* ---- homography RANSAC with cv's refit: the planar / rotation-only counterpart of E and F -----------------------------------------------------
+ * cv::findHomography(points1, points2, cv::RANSAC, threshold, mask, maxIters, confidence) for n >= 4 correspondences: what a caller estimates
+ * beside E or F on a planar scene or a near-pure rotation, where those are degenerate, to compare the supports. p1_xy, p2_xy: n pixel positions
+ * (x, y) as float32 (cv converts its input to CV_32F; the LK calls and the KLT step return float32); H9 row-major, maps image 1 to image 2, H9[8]
+ * = 1; mask n bytes; *out_samples_drawn = RANSAC iterations made. *out_found 0 = no model (cv returns an empty Mat): H9 untouched, mask all 0.
+ * The adaptive RANSAC and the refit run in ONE launch, one workgroup per call (k_homography_ransac); the result has the bits of
+ * tests/twin/homography_twin.cpp.
+ * [mem: OpenCV 3.4 fundam.cpp, ptsetreg.cpp, lmsolver.cpp; parity with a real OpenCV unpinned like the rest - tests/twin/homography_twin.cpp is
+ * the CPU restatement that fixes the bits]
+ *   Branch by n. n == 4: one runKernel on the four points without RANSAC; the mask is all 1, 0 samples drawn, no refit; no model from it:
+ *     found 0. n < 4 is PMV_ERR_DEGENERATE (cv asserts); n < 0 or n > max_tracks: PMV_ERR_CAPACITY. LMEDS, RHO and method 0 are not built.
+ *   Sampling: RANSACPointSetRegistrator::getSubset with 4 model points, rng = cv::RNG((uint64)-1) per call, a draw is rng % n, duplicates are
+ *     redrawn, up to 10000 attempts per subset. checkSubset refuses a subset if haveCollinearPoints holds for either image (only the LAST point
+ *     is tested, as for pmv_find_fundamental_mat) or if the four-point orientation test fails: for the triples {0,1,2}, {0,1,3}, {0,2,3},
+ *     {1,2,3} the 3x3 determinants of the homogeneous points (doubles from the floats) of image 1 and image 2 must not have opposite signs.
+ *     No subset at iteration 0: no model, 0 samples drawn; at a later iteration: the loop ends there.
+ *   Four-point solver (runKernel): cv's normalisation - centroids, then count / (sum of absolute deviations) per axis, no model if a sum is
+ *     < DBL_EPSILON - and its two rows per point [X, Y, 1, 0, 0, 0, -xX, -xY, -x], [0, 0, 0, X, Y, 1, -yX, -yY, -y]; the null vector of the 8x9
+ *     system by Gauss-Jordan with complete pivoting, normalised to unit length (cv: the least eigenvector of LtL; the twin's first fixed
+ *     choice); H = invHnorm H0 Hnorm2 scaled by 1 / H[8], H[8] = 1. H[8] == 0 or not a number: the model is dropped (cv divides unguarded).
+ *   Error and inliers (computeError): float32 throughout - the nine entries cast to float, ww = 1.f / (H6 x + H7 y + 1.f), err = dx dx + dy dy;
+ *     inlier iff err <= (float)(threshold * threshold). A model becomes the best iff its count > max(maxGood, 3); then niters =
+ *     RANSACUpdateNumIters(confidence, (n - count) / n, 4, niters), starting from max_iters, with pow and log on the host
+ *     (pmv_debug_homography_iters_table).
+ *   Refit (only with a model and n > 4; the mask is the RANSAC model's and is not recomputed): runKernel on the inliers - the 9x9 LtL and the
+ *     eigenvector of its smallest eigenvalue by cv's JacobiImpl_, with hypot written as |a| sqrt(1 + (b / a)^2) (the twin's second fixed
+ *     choice); H stays the RANSAC model where that gives none - then LMSolver with at most 10 iterations on the 8 free entries with
+ *     HomographyRefineCallback's residuals and Jacobian in double, cv's damping rule (Rlo 0.25, Rhi 0.75, the lambda / nu updates,
+ *     invert(A, DECOMP_EIG) at lambda == 0), the step from solve(Ap, v, d, DECOMP_EIG) by the same Jacobi routine, over at |d|inf <
+ *     FLT_EPSILON or |r|inf < FLT_EPSILON. Every sum over the inliers (centroids, deviations, LtL, JtJ, Jtr, S, Sd) is taken in the twin's
+ *     order, its third fixed choice: 64 partial sums, point i in partial sum i mod 64 in increasing i, then the xor butterfly 32, 16, .. 1.
+ *   Errors: null pointers, a threshold that is not positive and finite (cv substitutes 3; here it is refused), a confidence outside (0, 1),
+ *     max_iters outside 1..10000, a coordinate that is not finite or beyond 1e6 in magnitude (the message names the point): PMV_ERR_INVALID.
+ *     On an error nothing is written and nothing is clamped. Not logged by pmv_record_enable; the whole-sequence drivers and pmv_klt_step do
+ *     not call this. The call shares the staging blocks of pmv_find_fundamental_mat. */
+int pmv_find_homography(pmv_ctx* ctx, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9,
+                        uint8_t* mask, int* out_found, int* out_samples_drawn);
+/* diagnostic, ctx-free: pmv_debug_essential_iters_table for the 4 model points of pmv_find_homography: *out_num = log(1 - confidence),
+ * out_denoms[g] = log(1 - (1 - (n - g) / n)^4) for g = 0..n (n + 1 doubles; -infinity where RANSACUpdateNumIters returns 0 before its
+ * logarithms). n < 0 or a null pointer: PMV_ERR_INVALID. */
+int pmv_debug_homography_iters_table(int n, double confidence, double* out_denoms, double* out_num);
+/* diagnostic, ctx-free: the argument rules of pmv_find_homography for a context of max_tracks, in its order and with its codes; reads the
+ * points, writes nothing but out_message256 (optional: the message the call would leave, 256 bytes). */
+int pmv_debug_homography_check(int max_tracks, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                               const double* H9, const uint8_t* mask, const int* out_found, const int* out_samples_drawn, char* out_message256);
+/* diagnostic: out2 = {k_homography_ransac launches, requests they served} since the context was created (pmv_find_homography: one each;
+ * pmv_batch_find_homography: one launch per round of the five-point combiner that holds such requests). */
+int pmv_debug_homography_launches(pmv_ctx* ctx, long long* out2);
+
 /* ---- A device-resident KLT tracker: one call per frame, the tracks stay in HBM ------------------------------------------------------------
  * A tracker lives in the context and holds n <= target tracks, each an (id, age, xy) triple - xy float32 in the coordinates of the frame the
  * last step ran on - and next_id. A new tracker is empty with next_id = 0. pmv_klt_step runs the per-frame chain of a VINS-style front end
@@ -1384,6 +1434,14 @@ int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double
  * call per seq and call, as for pmv_batch_find_essential_mat. */
 int pmv_batch_find_fundamental_mat(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence,
                                    double* F9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+/* pmv_find_homography for a seq, argument for argument (its rules: n >= 4 else PMV_ERR_DEGENERATE, n <= max_tracks else PMV_ERR_CAPACITY,
+ * the no-model convention) with `seq` (0 .. n_seq - 1, else PMV_ERR_INVALID) after the context; the bits of the single call. A request of the
+ * five-point combiner: a round serves all its homography requests with ONE k_homography_ransac launch, one workgroup per request, beside the
+ * launches for the round's fundamental and essential requests (pmv_debug_whole_rounds does not count it: pmv_debug_homography_launches),
+ * and a call returns as soon as ITS request is complete. One outstanding call per seq and call, as for pmv_batch_find_essential_mat; the
+ * seq's fundamental and homography calls share their staging blocks, so one of the two at a time. */
+int pmv_batch_find_homography(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                              double* H9, uint8_t* mask, int* out_found, int* out_samples_drawn);
 /* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds (+ 1 for a
  * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation; + 1 for a round with
  * pmv_batch_frame_upload_remap requests: the launch from the remap scratch), and the

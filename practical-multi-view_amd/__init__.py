@@ -444,6 +444,7 @@ ABI_SYMBOLS = [
     "pmv_lk_track", "pmv_lk_track_ex", "pmv_lk_track_fb", "pmv_lk_track_fb_levels", "pmv_set_lk_params", "pmv_get_lk_params", "pmv_debug_lk_general", "pmv_set_ba_mode", "pmv_pnp_ransac", "pmv_debug_pnp_hypotheses", "pmv_debug_ba_stamps", "pmv_debug_lk_stamps", "pmv_ba_residuals", "pmv_ba_solve", "pmv_triangulate_candidates", "pmv_triangulate_candidates_ahead", "pmv_fivepoint_hypotheses",
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
+    "pmv_find_homography", "pmv_debug_homography_iters_table", "pmv_debug_homography_check", "pmv_debug_homography_launches",
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
@@ -458,7 +459,7 @@ ABI_SYMBOLS = [
     "pmv_batch_open", "pmv_batch_close", "pmv_batch_frame_upload", "pmv_batch_upload_stats", "pmv_batch_upload_rounds",
     "pmv_batch_lk_track", "pmv_batch_lk_track_ex", "pmv_batch_lk_track_fb", "pmv_batch_knn_match", "pmv_batch_detect_gftt", "pmv_batch_detect_shitomasi", "pmv_batch_detect_fast",
     "pmv_batch_pnp_ransac", "pmv_batch_ba_solve", "pmv_batch_triangulate_candidates", "pmv_batch_fivepoint_hypotheses",
-    "pmv_batch_find_essential_mat", "pmv_batch_recover_pose", "pmv_batch_find_fundamental_mat",
+    "pmv_batch_find_essential_mat", "pmv_batch_recover_pose", "pmv_batch_find_fundamental_mat", "pmv_batch_find_homography",
 ]
 
 
@@ -1359,6 +1360,31 @@ class Context:
         launch (a KLT loop's rejectWithF): (found, F (3, 3), mask (n,), samples drawn); found False = no model (F zeros, mask all 0)"""
         return self._find_fundamental(self.lib.pmv_find_fundamental_mat, self._ck, (), p1, p2, threshold, confidence)
 
+    def _find_homography(self, call, ck, head, p1, p2, threshold, confidence, max_iters):
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        if p1.shape != p2.shape:
+            raise ValueError(f"p1 {p1.shape} and p2 {p2.shape}: one (x, y) pair per correspondence in each")
+        n = p1.shape[0]
+        H = np.zeros(9, np.float64)
+        mask = np.zeros(n, np.uint8)
+        found, drawn = C.c_int(), C.c_int()
+        ck(call(self.h, *head, _p(p1, _f32p), _p(p2, _f32p), n, C.c_double(threshold), C.c_double(confidence), int(max_iters), _p(H, _f64p), _p(mask, _u8p),
+                C.byref(found), C.byref(drawn)))
+        return bool(found.value), H.reshape(3, 3), mask, drawn.value
+
+    def find_homography(self, p1, p2, threshold=3.0, confidence=0.995, max_iters=2000):
+        """cv::findHomography(p1, p2, cv::RANSAC, threshold, mask, max_iters, confidence) for n >= 4 float32 correspondences, the RANSAC and cv's
+        refit on the inliers in one launch: (found, H (3, 3) image 1 -> image 2, mask (n,), samples drawn); found False = no model (H zeros,
+        mask all 0). The defaults are cv's."""
+        return self._find_homography(self.lib.pmv_find_homography, self._ck, (), p1, p2, threshold, confidence, max_iters)
+
+    def homography_launches(self):
+        """(k_homography_ransac launches, requests they served) since the context was created"""
+        out = (C.c_longlong * 2)()
+        self._ck(self.lib.pmv_debug_homography_launches(self.h, out))
+        return int(out[0]), int(out[1])
+
     # ---- device-resident KLT tracker ----
     def klt_create(self, **params):
         """pmv_klt_create: a KltTracker whose track list stays on the device; one step() per frame runs LK (forward-backward), the filter,
@@ -1825,6 +1851,10 @@ class Context:
     def batch_find_fundamental_mat(self, seq, p1, p2, threshold=1.0, confidence=0.99):
         """find_fundamental_mat for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""
         return self._find_fundamental(self.lib.pmv_batch_find_fundamental_mat, self._ckt, (int(seq),), p1, p2, threshold, confidence)
+
+    def batch_find_homography(self, seq, p1, p2, threshold=3.0, confidence=0.995, max_iters=2000):
+        """find_homography for sequence `seq` of the session: returns when its own request is complete, not when its round's launch is"""
+        return self._find_homography(self.lib.pmv_batch_find_homography, self._ckt, (int(seq),), p1, p2, threshold, confidence, max_iters)
 
     def batch_recover_pose(self, seq, E, p1, p2, K, mask):
         return self._recover_pose(self.lib.pmv_batch_recover_pose, self._ckt, (int(seq),), E, p1, p2, K, mask)

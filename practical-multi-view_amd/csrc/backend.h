@@ -97,10 +97,11 @@ struct FivePointProblem {
 };
 hipError_t launch_fivepoint_batch(hipStream_t s, const FivePointProblem* d_probs, int n_probs, int max_hyp);
 // one whole RANSAC request (pmv_ransac.h): one workgroup runs the adaptive loop of one cv::findEssentialMat (k_essential_ransac,
-// backend_fivepoint.hip; Pt = double) or cv::findFundamentalMat call (k_fundamental_ransac, backend_fundamental.hip; Pt = float)
+// backend_fivepoint.hip; Pt = double), cv::findFundamentalMat call (k_fundamental_ransac, backend_fundamental.hip; Pt = float) or
+// cv::findHomography call (k_homography_ransac, backend_homography.hip; Pt = float, the blocks of the fundamental call)
 template <class Pt> struct WholeProblem {
     const Pt* p1; const Pt* p2;           // device: n points (x, y) each - normalised for E, pixel positions for F
-    const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^S), -inf where RANSACUpdateNumIters returns 0], S = 5 or 7
+    const double* iters;                  // device: [log(1 - prob) | for g = 0..n inliers: log(1 - (1 - (n - g) / n)^S), -inf where RANSACUpdateNumIters returns 0], S = 5, 7 or 4
     char* out;                            // mapped pinned result block: [WholeResultHdr (E or F, found, samples drawn, best count, done_seq) | mask n bytes]
     int n, max_iters; float thr;
     unsigned done_seq;                    // != 0; the kernel's last store, into WholeResultHdr::done (the caller waits for it)
@@ -108,9 +109,10 @@ template <class Pt> struct WholeProblem {
 using EssentialProblem = WholeProblem<double>;
 using FundamentalProblem = WholeProblem<float>;
 static_assert(sizeof(WholeProblem<double>) <= ESS_HDR, "the record is the header of the input block");
-// the record of a request of n points with cv's iteration cap and the threshold in the points' unit
-template <class Pt> inline WholeProblem<Pt> whole_problem(const Pt* p1, const Pt* p2, const double* iters, char* out, int n, double threshold, unsigned done_seq) {
-    return WholeProblem<Pt>{p1, p2, iters, out, n, 1000, (float)(threshold * threshold), done_seq};
+// the record of a request of n points with the iteration cap (cv's 1000 for E and F, the caller's maxIters for H) and the threshold in the points' unit
+constexpr int WHOLE_MAX_ITERS = 1000;
+template <class Pt> inline WholeProblem<Pt> whole_problem(const Pt* p1, const Pt* p2, const double* iters, char* out, int n, double threshold, int max_iters, unsigned done_seq) {
+    return WholeProblem<Pt>{p1, p2, iters, out, n, max_iters, (float)(threshold * threshold), done_seq};
 }
 constexpr int ESS_MAX_WAVES = 16;   // hypotheses per in-kernel round at most (wavefronts of the workgroup)
 constexpr int ESS_DEFAULT_WAVES = 8;   // R of DESIGN.md §4: 8 x 6.2 KB = 49 KB of LDS, three workgroups per CU
@@ -121,6 +123,10 @@ constexpr int FUND_DEFAULT_R = 64;   // R of DESIGN.md §4 (measured: the widest
 int fundamental_round_width();       // hypotheses per in-kernel round (PMV_FUNDAMENTAL_R overrides the default, 1..FUND_MAX_R)
 void fundamental_set_round_width(int r);   // pmv_debug_set_fundamental_r: r in 1..FUND_MAX_R from the next launch on, 0 = back to the above
 hipError_t launch_fundamental_ransac(hipStream_t s, const FundamentalProblem* d_probs, int n_probs);
+using HomographyProblem = WholeProblem<float>;   // (the record and the blocks of a fundamental request: fundamental_layout, d_fund_in)
+constexpr int HG_R = 64;             // hypotheses per in-kernel round (one lane of a wavefront each)
+constexpr int HG_MAX_ITERS = 10000;  // pmv_find_homography's max_iters at most
+hipError_t launch_homography_ransac(hipStream_t s, const HomographyProblem* d_probs, int n_probs);
 // one two-view problem of a batched DLT launch
 struct DltProblem { const double* P1x4; const double* q1; const double* q2; const uint8_t* mask_in; double* Q; uint8_t* mask; int n; };
 hipError_t launch_tri_dlt_batch(hipStream_t s, const DltProblem* d_probs, int n_probs, int max_n);
@@ -168,6 +174,14 @@ int fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const f
                       uint8_t* mask, int* out_found, int* out_samples_drawn);
 int fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence,
                         FundamentalProblem* P, WholeLayout* L);
+// whole findHomography: argument rules of pmv_find_homography (outputs untouched on error; homography_args_check is their ctx-free statement,
+// err: the message, 256 bytes); prepare is fundamental_prepare's with 4 model points and the caller's iteration cap
+int homography_args_check(int max_tracks, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                          const double* H9, const uint8_t* mask, const int* out_found, const int* out_samples_drawn, char* err);
+int homography_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9,
+                     uint8_t* mask, int* out_found, int* out_samples_drawn);
+int homography_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                       HomographyProblem* P, WholeLayout* L);
 // cv::recoverPose around a DLT launch: `dlt` is pmv_triangulate_candidates' contract on the caller's workspace set; PMV_OK or its error
 int recover_pose_check(pmv_ctx* ctx, const char* who, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9,
                        double* t3, uint8_t* mask, double* tri4n, int* out_good);

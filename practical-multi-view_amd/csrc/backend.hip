@@ -622,9 +622,9 @@ int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const doubl
 // ---- the two whole-RANSAC calls (pmv_ransac.h): what their prepare halves and their single calls share --------------------------------------
 // The tail of either *_prepare, once the points and the iteration table stand in b's pinned block by L: the record points into the device
 // in-block d_in and at the mapped result block, takes the set's next sequence number, whose word it clears, and goes into the in-block
-template <class Pt> static void whole_record(BackendBuffers* b, char* d_in, const WholeLayout& L, int n, double threshold, WholeProblem<Pt>* P) {
+template <class Pt> static void whole_record(BackendBuffers* b, char* d_in, const WholeLayout& L, int n, double threshold, int max_iters, WholeProblem<Pt>* P) {
     if (++b->done_seq == 0) b->done_seq = 1;
-    *P = whole_problem((const Pt*)(d_in + L.p1), (const Pt*)(d_in + L.p2), (const double*)(d_in + L.iters), b->h_stage.dm() + L.out, n, threshold, b->done_seq);
+    *P = whole_problem((const Pt*)(d_in + L.p1), (const Pt*)(d_in + L.p2), (const double*)(d_in + L.iters), b->h_stage.dm() + L.out, n, threshold, max_iters, b->done_seq);
     *whole_done_word(b, L) = 0;
     *(WholeProblem<Pt>*)((char*)b->h_stage + L.rec) = *P;
 }
@@ -674,7 +674,7 @@ int pmv::essential_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* p1, co
     }
     threshold /= (fx + fy) / 2;
     vo::five_point_iters_table(n, prob, h_it + 1, h_it);
-    whole_record(b, b->d_ess_in, L, n, threshold, P);
+    whole_record(b, b->d_ess_in, L, n, threshold, WHOLE_MAX_ITERS, P);
     *Lout = L;
     return PMV_OK;
 }
@@ -710,23 +710,59 @@ int pmv::fundamental_check(pmv_ctx* ctx, const char* who, const float* p1_xy, co
 }
 // fundamental_layout: pinned in-block [FundamentalProblem | p1 2n floats | p2 2n floats | log(1 - confidence), n + 1 denominators], out-block
 // as essential_prepare's with F in the place of E
-int pmv::fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, const float* p2, int n, double threshold, double confidence,
-                             FundamentalProblem* P, WholeLayout* Lout) {
+// (for the model points and the iteration cap of either call on float points)
+static int float_points_prepare(pmv_ctx* ctx, BackendBuffers* b, const char* who, const float* p1, const float* p2, int n, double threshold, double confidence,
+                                int model_points, int max_iters, WholeProblem<float>* P, WholeLayout* Lout) {
     const size_t fund_in_bytes = fund_in_cap((size_t)ctx->max_tracks);
     if (b->d_fund_in.cap < fund_in_bytes) {   // the set's first such call: a session caller's thread has not chosen the context's device yet
         CKC(hipSetDevice(ctx->device));
         CKC(b->d_fund_in.ensure(fund_in_bytes));
     }
     const WholeLayout L = fundamental_layout((size_t)n);
-    REQ(L.in_bytes <= b->d_fund_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_find_fundamental_mat: n=%d does not fit the staging blocks", n);
+    REQ(L.in_bytes <= b->d_fund_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "%s: n=%d does not fit the staging blocks", who, n);
     char* hs = (char*)b->h_stage;
     double* h_it = (double*)(hs + L.iters);
     memcpy(hs + L.p1, p1, (size_t)n * 8);
     memcpy(hs + L.p2, p2, (size_t)n * 8);
-    vo::ransac_iters_table(n, confidence, 7, h_it + 1, h_it);
-    whole_record(b, b->d_fund_in, L, n, threshold, P);
+    vo::ransac_iters_table(n, confidence, model_points, h_it + 1, h_it);
+    whole_record(b, b->d_fund_in, L, n, threshold, max_iters, P);
     *Lout = L;
     return PMV_OK;
+}
+int pmv::fundamental_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, const float* p2, int n, double threshold, double confidence,
+                             FundamentalProblem* P, WholeLayout* Lout) {
+    return float_points_prepare(ctx, b, "pmv_find_fundamental_mat", p1, p2, n, threshold, confidence, 7, WHOLE_MAX_ITERS, P, Lout);
+}
+
+// ---- whole findHomography RANSAC and refit on the device (k_homography_ransac): check / prepare; the blocks and whole_finish are F's ---------
+int pmv::homography_args_check(int max_tracks, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                               const double* H9, const uint8_t* mask, const int* out_found, const int* out_samples_drawn, char* err) {
+#define HREQ(cond, code, ...) do { if (!(cond)) { snprintf(err, 256, __VA_ARGS__); return code; } } while (0)
+    HREQ(p1_xy && p2_xy && H9 && mask && out_found && out_samples_drawn, PMV_ERR_INVALID, "%s: null argument", who);
+    HREQ(threshold > 0 && std::isfinite(threshold), PMV_ERR_INVALID, "%s: threshold = %g (a positive finite number of pixels)", who, threshold);
+    HREQ(confidence > 0 && confidence < 1, PMV_ERR_INVALID, "%s: confidence = %g outside (0, 1)", who, confidence);   // (a NaN fails the comparison too)
+    HREQ(max_iters >= 1 && max_iters <= HG_MAX_ITERS, PMV_ERR_INVALID, "%s: max_iters = %d outside 1..%d", who, max_iters, HG_MAX_ITERS);
+    HREQ(n >= 0 && n <= max_tracks, PMV_ERR_CAPACITY, "%s: n=%d (0..max_tracks=%d)", who, n, max_tracks);
+    HREQ(n >= 4, PMV_ERR_DEGENERATE, "%s: %d correspondences (a homography needs >= 4; cv asserts)", who, n);
+    for (int k = 0; k < 2; k++) {
+        const float* p = k ? p2_xy : p1_xy;
+        for (int i = 0; i < 2 * n; i++)
+            HREQ(fabsf(p[i]) <= 1e6f, PMV_ERR_INVALID, "%s: point %d of image %d (%g, %g) is not finite or beyond 1e6", who, i / 2, k + 1, (double)p[i & ~1], (double)p[i | 1]);
+    }
+#undef HREQ
+    return PMV_OK;
+}
+int pmv::homography_check(pmv_ctx* ctx, const char* who, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
+                          double* H9, uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    REQ(ctx, PMV_ERR_INVALID, "%s: null argument", who);
+    char err[256];
+    const int rc = homography_args_check(ctx->max_tracks, who, p1_xy, p2_xy, n, threshold, confidence, max_iters, H9, mask, out_found, out_samples_drawn, err);
+    if (rc != PMV_OK) set_err(ctx, "%s", err);
+    return rc;
+}
+int pmv::homography_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, const float* p2, int n, double threshold, double confidence, int max_iters,
+                            HomographyProblem* P, WholeLayout* Lout) {
+    return float_points_prepare(ctx, b, "pmv_find_homography", p1, p2, n, threshold, confidence, 4, max_iters, P, Lout);
 }
 
 extern "C" {
@@ -768,6 +804,35 @@ int pmv_find_fundamental_mat(pmv_ctx* ctx, const float* p1_xy, const float* p2_x
     if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
     const auto prepare = [&](BackendBuffers* b, FundamentalProblem* P, WholeLayout* L) { return fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, P, L); };
     return whole_single(ctx, prepare, &BackendBuffers::d_fund_in, launch_fundamental_ransac, n, F9, mask, out_found, out_samples_drawn);
+}
+
+int pmv_find_homography(pmv_ctx* ctx, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9, uint8_t* mask,
+                        int* out_found, int* out_samples_drawn) {
+    if (const int rc = homography_check(ctx, "pmv_find_homography", p1_xy, p2_xy, n, threshold, confidence, max_iters, H9, mask, out_found, out_samples_drawn)) return rc;
+    const auto prepare = [&](BackendBuffers* b, HomographyProblem* P, WholeLayout* L) { return homography_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, max_iters, P, L); };
+    const int rc = whole_single(ctx, prepare, &BackendBuffers::d_fund_in, launch_homography_ransac, n, H9, mask, out_found, out_samples_drawn);
+    if (rc == PMV_OK) { ctx->homography_launches[0]++; ctx->homography_launches[1]++; }
+    return rc;
+}
+
+int pmv_debug_homography_iters_table(int n, double confidence, double* out_denoms, double* out_num) {
+    if (n < 0 || !out_denoms || !out_num) return PMV_ERR_INVALID;
+    vo::ransac_iters_table(n, confidence, 4, out_denoms, out_num);
+    return PMV_OK;
+}
+
+int pmv_debug_homography_check(int max_tracks, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, const double* H9,
+                               const uint8_t* mask, const int* out_found, const int* out_samples_drawn, char* out_message256) {
+    char err[256] = "";
+    const int rc = homography_args_check(max_tracks, "pmv_find_homography", p1_xy, p2_xy, n, threshold, confidence, max_iters, H9, mask, out_found, out_samples_drawn, err);
+    if (out_message256) memcpy(out_message256, err, 256);
+    return rc;
+}
+
+int pmv_debug_homography_launches(pmv_ctx* ctx, long long* out2) {
+    if (!ctx || !out2) return PMV_ERR_INVALID;
+    for (int i = 0; i < 2; i++) out2[i] = ctx->homography_launches[i].load();
+    return PMV_OK;
 }
 
 int pmv_debug_fundamental_iters_table(int n, double confidence, double* out_denoms, double* out_num) {

@@ -390,6 +390,7 @@ struct EssModel {
     }
     __device__ static double model(const double* ws, int R, int b, int mi, int k) { return ws[b * FP_WS + 660 + 9 * mi + k]; }
     __device__ static float error(const double* E, const double* __restrict__ q1, const double* __restrict__ q2, int i) { return fp_sampson(E, q1, q2, i); }
+    __device__ static void finish(const Problem&, double*, Shared&) {}   // (cv has no refit for E)
 };
 
 __global__ __launch_bounds__(64 * ESS_MAX_WAVES) void k_essential_ransac(const EssentialProblem* __restrict__ probs) { BACKEND_PRIO();

@@ -26,21 +26,6 @@ namespace {
 constexpr int FD_WS = 108;           // doubles per hypothesis: A 7x9 at 0 | f1 at 63 | f2 at 72 | up to three models at 81
 constexpr int FD_THREADS = 512;      // 8 waves score; the lanes of wave 0 solve
 
-// haveCollinearPoints on the subset's last point: against every pair (j, k < j) of the earlier ones; q: the subset's 7 points (x, y)
-__device__ inline bool fd_last_point_collinear(const float* q) {
-    const float xi = q[12], yi = q[13];
-    #pragma unroll 1
-    for (int j = 0; j < 6; j++) {
-        const double dx1 = q[2 * j] - xi, dy1 = q[2 * j + 1] - yi;
-        #pragma unroll 1
-        for (int k = 0; k < j; k++) {
-            const double dx2 = q[2 * k] - xi, dy2 = q[2 * k + 1] - yi;
-            if (fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2))) return true;
-        }
-    }
-    return false;
-}
-
 __device__ inline double fd_cubic_at(double a1, double a2, double a3, double x) { return ((x + a1) * x + a2) * x + a3; }
 __device__ inline double fd_cubic_slope(double a1, double a2, double x) { return (3 * x + 2 * a1) * x + a2; }
 __device__ inline double fd_cubic_polish(double a1, double a2, double a3, double x) {
@@ -267,7 +252,7 @@ struct FundModel {
             const float2 a = ((const float2*)P.p1)[idx[i]], c = ((const float2*)P.p2)[idx[i]];
             x.sp[2 * i] = a.x; x.sp[2 * i + 1] = a.y; x.sp[14 + 2 * i] = c.x; x.sp[15 + 2 * i] = c.y;
         }
-        return !fd_last_point_collinear(x.sp) && !fd_last_point_collinear(x.sp + 14);
+        return !whole_last_point_collinear<7>(x.sp) && !whole_last_point_collinear<7>(x.sp + 14);
     }
     __device__ static void solve(const Problem& P, double* ws, Shared& sh, int R, int nh) {
         const int tid = (int)threadIdx.x;
@@ -275,6 +260,7 @@ struct FundModel {
     }
     __device__ static double model(const double* ws, int R, int b, int mi, int k) { return ws[(81 + 9 * mi + k) * R + b]; }
     __device__ static float error(const double* F, const float* __restrict__ p1, const float* __restrict__ p2, int i) { return fd_error(F, p1, p2, i); }
+    __device__ static void finish(const Problem&, double*, Shared&) {}   // (cv has no refit for F)
 };
 static_assert((size_t)FUND_MAX_R * FD_WS * sizeof(double) + sizeof(FundModel::Shared) <= 64 * 1024, "the workgroup's LDS stays within the default limit");
 

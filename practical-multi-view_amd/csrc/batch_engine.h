@@ -17,7 +17,7 @@ void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
 enum ReqKind {
     Q_LK = 0, Q_GFTT = 1 /* plain or, with the caller's goodFeaturesToTrack arguments, extended */, Q_SHITOMASI = 2, Q_FAST = 3,
     Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6, Q_GFTT_FRAME = 7 /* the detector combiner */,
-    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_WHOLE_FIRST = Q_ESSENTIAL
+    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_HOMOGRAPHY = 16, Q_WHOLE_FIRST = Q_ESSENTIAL
 };
 // ---- request entry points: one per plugin call, with the contract of the single call of the same name (include/pmv_hip.h) -------------
 // Who checks what. Each entry runs the check function of its single call (pmv_ctx.h, backend.h; bracket = false) and then forms its
@@ -80,4 +80,7 @@ int engine_essential(BatchEngine* E, int seq, const double* p1_xy, const double*
 // pmv_find_fundamental_mat's contract, in the same form: one workgroup of the round's k_fundamental_ransac launch
 int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, double* F9, uint8_t* mask,
                        int* out_found, int* out_samples_drawn);
+// pmv_find_homography's contract, in the same form: one workgroup of the round's k_homography_ransac launch
+int engine_homography(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9,
+                      uint8_t* mask, int* out_found, int* out_samples_drawn);
 }  // namespace pmv

@@ -94,7 +94,7 @@ struct PnPReq : Req { BackendBuffers* b; PnPProblem P; PnPLayout L; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; BaIoLayout L; int max_iterations; };
 struct DltReq : Req { BackendBuffers* b; DltProblem P; DltLayout L; };
 struct FPReq : Req { BackendBuffers* b; FivePointProblem P; FivePointLayout L; };
-// Q_ESSENTIAL, Q_FUNDAMENTAL: a whole findEssentialMat / findFundamentalMat. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
+// Q_ESSENTIAL, Q_FUNDAMENTAL, Q_HOMOGRAPHY: a whole findEssentialMat / findFundamentalMat / findHomography. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
 // before the round's launch ends (a round ends with its slowest request) - so the record cannot live on the caller's stack like the others:
 // the combiner's store into `done` after its stream sync would land in a dead frame. The engine owns one record per seq and kind; `inflight` is 1
 // from the submit until the combiner has released the record after the round, and the seq's next call of that kind waits for that before it
@@ -102,7 +102,7 @@ struct FPReq : Req { BackendBuffers* b; FivePointProblem P; FivePointLayout L; }
 struct WholeReq : Req { BackendBuffers* b = nullptr; WholeLayout L{}; std::atomic<int> inflight{0}; };
 template <class Pt> struct WholeReqOf : WholeReq { WholeProblem<Pt> P; };
 using EssReq = WholeReqOf<double>;
-using FundReq = WholeReqOf<float>;
+using FundReq = WholeReqOf<float>;   // (Q_FUNDAMENTAL and Q_HOMOGRAPHY: the same record)
 
 // per-round scratch of a combiner: grows with slack (GROW_SLACK), in HBM or in mapped pinned memory (.dev = the address kernels use)
 struct DScratch : Growable { DScratch() : Growable(MEM_DEVICE, GROW_SLACK) {} };
@@ -178,6 +178,7 @@ struct BatchEngine {
     std::vector<BackendBuffers*> slots;   // one back-end workspace set per concurrent sequence
     std::unique_ptr<EssReq[]> ess;        // one whole-findEssentialMat request record per concurrent sequence (see WholeReq)
     std::unique_ptr<FundReq[]> fund;      // ... and one whole-findFundamentalMat record
+    std::unique_ptr<FundReq[]> homog;     // ... and one whole-findHomography record
     // combiners (thread + stream) per class. Round 2, host-bound: 2 and 3 per class cost more host CPU (smaller batches) than they won in
     // latency (25.7k -> 23.3k -> 19.5k frames/s at B = 64). Round 3, with the track tables the host has headroom and the LK class is the one
     // that is busy all the time - a launch ends with its slowest track, so a single LK stream idles most SIMDs during every tail: PMV_BATCH_LANES
@@ -858,23 +859,28 @@ void process_fp_rounds(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
 // is desc_block's with both kinds of records. The fundamental launch goes first: its requests take a fraction
 // of a five-point request's time and would otherwise wait on the stream behind all of them. Each workgroup signals its own caller; the sync
 // below is the fallback (a failed launch releases everyone with an error) and what makes the records reusable.
+// The round's findHomography requests have the fundamental requests' record and blocks: they stand behind them in the same array and get
+// ONE k_homography_ransac launch, between the other two.
 void process_whole(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    std::vector<EssReq*> ess; std::vector<FundReq*> fund;
-    for (Req* r : batch) { if (r->kind == Q_ESSENTIAL) ess.push_back((EssReq*)r); else fund.push_back((FundReq*)r); }
-    const size_t ne = ess.size(), nf = fund.size();
+    std::vector<EssReq*> ess; std::vector<FundReq*> fund, homog;
+    for (Req* r : batch) { if (r->kind == Q_ESSENTIAL) ess.push_back((EssReq*)r); else (r->kind == Q_HOMOGRAPHY ? homog : fund).push_back((FundReq*)r); }
+    const size_t ne = ess.size(), nf = fund.size(), nh = homog.size();
+    fund.insert(fund.end(), homog.begin(), homog.end());
     DescBlock<EssentialProblem, FundamentalProblem> D;
-    EK(desc_block(C, ne, nf, D));
+    EK(desc_block(C, ne, nf + nh, D));
     for (size_t i = 0; i < ne; i++) {
         D.a.h[i] = ess[i]->P;
         D.jobs.h[i] = StageJob{(const char*)ess[i]->b->h_stage.dm(), ess[i]->b->d_ess_in, (unsigned)ess[i]->L.in_bytes, 0};
     }
-    for (size_t i = 0; i < nf; i++) {
+    for (size_t i = 0; i < nf + nh; i++) {
         D.b.h[i] = fund[i]->P;
         D.jobs.h[ne + i] = StageJob{(const char*)fund[i]->b->h_stage.dm(), fund[i]->b->d_fund_in, (unsigned)fund[i]->L.in_bytes, 0};
     }
-    EK(stage_in(C, D, ne + nf, 2));
+    EK(stage_in(C, D, ne + nf + nh, 2));
     EK(launch_fundamental_ransac(C.s, D.b.d, (int)nf));
+    EK(launch_homography_ransac(C.s, D.b.d + nf, (int)nh));
     EK(launch_essential_ransac(C.s, D.a.d, (int)ne));
+    if (nh) { E->ctx->homography_launches[0]++; E->ctx->homography_launches[1] += (long long)nh; }
     if (nf) E->ctx->whole_rounds[0]++;
     if (ne) E->ctx->whole_rounds[1]++;
     if (nf && ne) E->ctx->whole_rounds[2]++;
@@ -1032,6 +1038,7 @@ int batch_engine_get(pmv_ctx* ctx, int B, BatchEngine** out) {
     }
     E->ess.reset(new EssReq[(size_t)B]);
     E->fund.reset(new FundReq[(size_t)B]);
+    E->homog.reset(new FundReq[(size_t)B]);
     E->cap_tracks = (size_t)B * ctx->max_tracks;
     if (const char* e = getenv("PMV_BATCH_EXCLUSIVE")) E->exclusive = atoi(e) != 0;
     if (const char* e = getenv("PMV_LK_LPT")) E->lk_lpt = atoi(e) != 0;
@@ -1344,6 +1351,14 @@ int engine_fundamental(BatchEngine* E, int seq, const float* p1_xy, const float*
     if (const int rc = fundamental_check(ctx, "pmv_find_fundamental_mat", p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn)) return rc;
     const auto prepare = [&](BackendBuffers* b, FundamentalProblem* P, WholeLayout* L) { return fundamental_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, P, L); };
     return engine_whole(E, E->fund[(size_t)seq], Q_FUNDAMENTAL, seq, prepare, n, F9, mask, out_found, out_samples_drawn);
+}
+
+int engine_homography(BatchEngine* E, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9,
+                      uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    pmv_ctx* ctx = E->ctx;
+    if (const int rc = homography_check(ctx, "pmv_find_homography", p1_xy, p2_xy, n, threshold, confidence, max_iters, H9, mask, out_found, out_samples_drawn)) return rc;
+    const auto prepare = [&](BackendBuffers* b, HomographyProblem* P, WholeLayout* L) { return homography_prepare(ctx, b, p1_xy, p2_xy, n, threshold, confidence, max_iters, P, L); };
+    return engine_whole(E, E->homog[(size_t)seq], Q_HOMOGRAPHY, seq, prepare, n, H9, mask, out_found, out_samples_drawn);
 }
 
 }  // namespace pmv

@@ -575,6 +575,15 @@ int pmv_batch_find_fundamental_mat(pmv_ctx* ctx, int seq, const float* p1_xy, co
     return engine_fundamental(S->eng, seq, p1_xy, p2_xy, n, threshold, confidence, F9, mask, out_found, out_samples_drawn);
 }
 
+// findHomography of a seq: one workgroup of the round's k_homography_ransac launch (engine_homography)
+int pmv_batch_find_homography(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters, double* H9,
+                              uint8_t* mask, int* out_found, int* out_samples_drawn) {
+    SESSION("pmv_batch_find_homography");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_find_homography", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_homography(S->eng, seq, p1_xy, p2_xy, n, threshold, confidence, max_iters, H9, mask, out_found, out_samples_drawn);
+}
+
 int pmv_batch_recover_pose(pmv_ctx* ctx, int seq, const double* E9, const double* p1_xy, const double* p2_xy, int n, const double* K, double* R9, double* t3,
                            uint8_t* mask, double* tri4n, int* out_good) {
     SESSION("pmv_batch_recover_pose");

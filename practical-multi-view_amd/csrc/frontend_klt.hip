@@ -827,7 +827,7 @@ template <class... P, class... A> static hipError_t klt_launch(void (*kernel)(P.
 // k_klt_lift_f wrote - and libm's iteration table (n1 + 2 doubles) at tab_h
 static FundamentalProblem klt_f_problem(const KltTracker* t, const KltLiftFArgs& Q, int n1, double* tab_h, const double* tab_d) {
     vo::ransac_iters_table(n1, t->p.f_confidence, 7, tab_h + 1, tab_h);
-    return whole_problem<float>(Q.on ? Q.p1 : t->D.l_prev[0].d, Q.on ? Q.p2 : t->D.l_cur[0].d, tab_d, t->D.f_out.d, n1, t->p.f_threshold, 1);
+    return whole_problem<float>(Q.on ? Q.p1 : t->D.l_prev[0].d, Q.on ? Q.p2 : t->D.l_cur[0].d, tab_d, t->D.f_out.d, n1, t->p.f_threshold, WHOLE_MAX_ITERS, 1);
 }
 // after the final wait: the header of the tracker's result block (`who`: pmv_klt_step or pmv_klt_step_many; j >= 0: tracker j of a group)
 static int klt_result_check(pmv_ctx* ctx, const KltTracker* t, bool stereo, const char* who, int j) {

@@ -1,5 +1,6 @@
 // The round structure of a whole adaptive RANSAC in ONE workgroup - cv::RANSACPointSetRegistrator::run as one kernel body - stated once for
-// k_essential_ransac (backend_fivepoint.hip) and k_fundamental_ransac (backend_fundamental.hip), as cv's one registrator serves both estimators.
+// k_essential_ransac (backend_fivepoint.hip), k_fundamental_ransac (backend_fundamental.hip) and k_homography_ransac (backend_homography.hip),
+// as cv's one registrator serves all three estimators.
 // A round: thread 0 draws the next min(R, niters - iter) subsets from the request's MWC stream (getSubset: distinct indices, checkSubset, up
 // to MAX_ATTEMPTS attempts each); the model's solver runs on the round's hypotheses; all waves score the round's (hypothesis, model) pairs
 // with wave-reduced counts; thread 0 replays the registrator's bookkeeping in sample order - count > max(maxGood, S - 1), best model,
@@ -17,8 +18,11 @@
 //   solve              runKernel for the round's first nh subsets, called by every thread: models into the workspaces, their number into sh.nm
 //   model(ws, R, b, mi, k)   element k of model mi of hypothesis b in the workspaces
 //   error              computeError of one correspondence, as float32
+//   finish             what the caller of the registrator does with the best model before it hands it out, called by every thread behind the
+//                      mask: nothing for E and F, findHomography's refit on the inliers for H (it may replace sh.best)
 #pragma once
 #include "backend.h"
+#include <float.h>
 
 namespace pmv {
 
@@ -30,6 +34,22 @@ template <class M> struct WholeShared {
     int fail_at;   // the first sample of the round for which getSubset ran out of attempts (the round's length: none)
     typename M::Extra x;
 };
+
+// haveCollinearPoints on the last of a subset's S points (cv tests only that one): against every pair (j, k < j) of the earlier ones;
+// q: the subset's points (x, y)
+template <int S> __device__ inline bool whole_last_point_collinear(const float* q) {
+    const float xi = q[2 * (S - 1)], yi = q[2 * (S - 1) + 1];
+    #pragma unroll 1
+    for (int j = 0; j < S - 1; j++) {
+        const double dx1 = q[2 * j] - xi, dy1 = q[2 * j + 1] - yi;
+        #pragma unroll 1
+        for (int k = 0; k < j; k++) {
+            const double dx2 = q[2 * k] - xi, dy2 = q[2 * k + 1] - yi;
+            if (fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2))) return true;
+        }
+    }
+    return false;
+}
 
 __device__ inline unsigned whole_rng_next(unsigned long long& st) { st = (unsigned long long)(unsigned)st * 4164903690U + (unsigned)(st >> 32); return (unsigned)st; }
 // RANSACUpdateNumIters calls pow and log; the device's libm is not glibc's, so the host tabulates both per inlier count (WholeProblem::iters)
@@ -118,9 +138,9 @@ template <class M> __device__ void whole_ransac(const typename M::Problem& P, do
             __syncthreads();
         }
     }
-    // result block: mask of the best model (err <= thr, recomputed once), the model, found, samples drawn, best count. The request's sequence
-    // number is the workgroup's last store, behind a system fence and a barrier: its caller waits for that word alone and reads the block
-    // and reuses the request's buffers as soon as it sees it.
+    // result block: mask of the loop's best model (err <= thr, recomputed once), the model as M::finish leaves it, found, samples drawn, best
+    // count. The request's sequence number is the workgroup's last store, behind a system fence and a barrier: its caller waits for that word
+    // alone and reads the block and reuses the request's buffers as soon as it sees it.
     const bool found = sh.max_good > 0;
     uint8_t* mask = (uint8_t*)(P.out + ESS_OUT_HDR);
     if (found && !M::direct(n)) {
@@ -133,6 +153,7 @@ template <class M> __device__ void whole_ransac(const typename M::Problem& P, do
         #pragma unroll 1
         for (int i = tid; i < n; i += (int)blockDim.x) mask[i] = found ? 1 : 0;
     }
+    M::finish(P, workspaces, sh);
     if (tid == 0) {
         double* Mo = (double*)P.out;
         #pragma unroll 1
