@@ -1316,17 +1316,185 @@ __global__ __launch_bounds__(64 * BG_W) void k_bam_gemm(BAArgs A, const BAGState
     bam_gemm_role(A, st, blockIdx.x, swork);
 }
 
-// S: loop-top tests, reduced camera system [S | rhs row] in LDS, right-looking Cholesky with the forward substitution
-// folded in as row m (two barriers per column), backward substitution in registers of wavefront 0 -> step_c; rotation
-// constants of the candidate cameras.
+// The load front of a back-substitution block: everything the block reads that an earlier launch (or the host) wrote, for the thread's
+// point and for its first observation record (e = eb0 + tid; a block of BM_PB points seldom has more than BM_T records, and a thread's
+// later records are loaded where they are used). Three levels, each needing the one before: pobs_start and what the point index alone
+// addresses; the record; what the record addresses. k_bam_solveback issues each level behind a phase of the solve that has just waited for
+// memory anyway, so the trips run under the solve's arithmetic; k_bamB_backsub issues them back to back. Nothing here is written by the
+// S|B launch itself (that is A.step, candrot, A.diag, st_out, the cur ^ 1 halves of x, J, res, and part4).
+struct BsFront {
+    int eb0, eb1;        // the block's records
+    int ps0, ps1;        // the records of the thread's point (tid < BM_PB)
+    int4 rec;            // the thread's first record, if eb0 + tid < eb1
+    double J[18], res[2], ob[2], scc[6], scp[3];   // of that record: Jacobian rows, residual, observation, scales of its camera and point
+    double gp[3], Ei[9], xs[3], xo[3];             // of the point: gradient, E^-1, scales, coordinates
+    double cam_x, cam_s;                           // block 0, tid < 6 nc: camera parameter tid and its scale
+};
+__device__ __forceinline__ void bs_front_point(const BAArgs& A, int cur, int bid, BsFront& F) {
+    const int tid = threadIdx.x, m = 6 * A.nc, n = m + 3 * A.np;
+    const int p0 = bid * BM_PB, p1 = min(A.np, p0 + BM_PB), p = p0 + tid;
+    F.eb0 = A.pobs_start[p0]; F.eb1 = A.pobs_start[p1];
+    const double* x = A.x + (size_t)cur * n;
+    if (bid == 0 && tid < m) { F.cam_x = x[tid]; F.cam_s = A.scale[tid]; }   // (6 nc <= 132 < BM_T)
+    if (tid < BM_PB && p < p1) {
+        F.ps0 = A.pobs_start[p]; F.ps1 = A.pobs_start[p + 1];
+#pragma unroll
+        for (int a = 0; a < 3; a++) { F.gp[a] = A.gp[(size_t)p * 3 + a]; F.xs[a] = A.scale[m + 3 * p + a]; F.xo[a] = x[m + 3 * p + a]; }
+#pragma unroll
+        for (int k = 0; k < 9; k++) F.Ei[k] = A.Einv[(size_t)p * 9 + k];
+    }
+}
+__device__ __forceinline__ void bs_front_record(const BAArgs& A, BsFront& F) {
+    const int e = F.eb0 + (int)threadIdx.x;
+    if (e < F.eb1) F.rec = A.erec[e];
+}
+__device__ __forceinline__ void bs_front_rows(const BAArgs& A, int cur, BsFront& F) {
+    if (F.eb0 + (int)threadIdx.x >= F.eb1) return;
+    const int i = F.rec.x, c = F.rec.y;
+    const double* Jr = A.J + ((size_t)cur * A.nobs + i) * 18;
+    const double* rr = A.res + ((size_t)cur * A.nobs + i) * 2;
+#pragma unroll
+    for (int k = 0; k < 18; k++) F.J[k] = Jr[k];
+#pragma unroll
+    for (int k = 0; k < 2; k++) { F.res[k] = rr[k]; F.ob[k] = A.obs[2 * i + k]; }
+#pragma unroll
+    for (int k = 0; k < 6; k++) F.scc[k] = A.scale[6 * c + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) F.scp[k] = A.scale[6 * A.nc + 3 * F.rec.z + k];
+}
+
+// Element l < 21 of a 6x6 lower triangle in row-major order: (row, column).
+__device__ __forceinline__ void tri6_rc(int l, int& r, int& c) {
+    r = (l >= 1) + (l >= 3) + (l >= 6) + (l >= 10) + (l >= 15);
+    c = l - r * (r + 1) / 2;
+}
+// (row, column) of element e of a lower triangle in row-major order, e = row (row + 1) / 2 + column
+__device__ __forceinline__ void tri_rc(int e, int& r, int& c) {
+    int ii = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);   // then the exact fix-up
+    while ((ii + 1) * (ii + 2) / 2 <= e) ii++;
+    while (ii * (ii + 1) / 2 > e) ii--;
+    r = ii; c = e - ii * (ii + 1) / 2;
+}
+// Cholesky of one camera's 6x6 diagonal block in wavefront 0: lane l < 21 brings element l of the lower triangle (tri6_rc) in v, every lane
+// takes the 21 values by cross-lane reads and runs the pivot chain (the only serial chain of the factorisation: 6 x [rsqrt_nr, a multiply
+// per row, a multiply-subtract per trailing element]) on them, lane 0 stores the factor to S and the pivot reciprocals to dg. False if a
+// pivot is not positive. The expressions and their order per element are those of the one-thread form this replaces.
+__device__ __forceinline__ bool chol6_wave0(double v, double* S, int m, int j0, double* dg, int lane) {
+    double a[21];   // lower triangle, row-major: (i,k) -> i*(i+1)/2 + k
+#pragma unroll
+    for (int k = 0; k < 21; k++) a[k] = readlane_f64(v, k);
+    bool ok = true;
+    double r[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        const double d = a[j * (j + 1) / 2 + j];
+        ok = ok && (d > 0.0);
+        r[j] = rsqrt_nr(d);                      // pivot reciprocal; the diagonal of L itself is only kept for reference
+        a[j * (j + 1) / 2 + j] = d * r[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) a[i * (i + 1) / 2 + j] *= r[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+#pragma unroll
+            for (int k = j + 1; k <= i; k++) a[i * (i + 1) / 2 + k] -= a[i * (i + 1) / 2 + j] * a[k * (k + 1) / 2 + j];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+#pragma unroll
+            for (int k = 0; k <= i; k++) S[(size_t)(j0 + i) * m + j0 + k] = a[i * (i + 1) / 2 + k];
+            dg[j0 + i] = r[i];
+        }
+    }
+    return ok;
+}
+
+// S = blockdiag(U_c) + D2_c - Yt^T Wt (lower triangle), row m = rhs_c - Yt^T g, into LDS. A thread takes up to four elements at a time
+// (a 32 x 32 step of the 16 x 16 thread tile) and asks for all their inputs before the first sum, so the block pays one memory trip where
+// the element-by-element loop paid one per element; an element outside the triangle reads those of (m, 0) and stores nothing.
+// REUSE: the LM diagonal of a rejected step is read from A.diag (else this launch writes it: nobody reads it). SLICED: Gpart holds one raw
+// partial per K-slice (k_bam_pointgemm), summed in the G kernel's order, BG_W slices per half, slice by slice, an empty slice adding +0.0
+// as its idle wavefront did; else one partial per half (k_bam_gemm).
+template <bool REUSE, bool SLICED>
+__device__ __forceinline__ void bam_assemble_S(const BAArgs& A, double* S, int m, const double* __restrict__ Ublk, const double* __restrict__ rhsblk,
+                                               int gslices, double radius, bool writer, int tx, int ty) {
+    constexpr int NG = SLICED ? BG_H * BG_W : BG_H;
+    for (int a0 = ty; a0 <= m; a0 += 32) {
+        for (int b0 = tx; b0 < m && b0 <= a0 + 16; b0 += 32) {
+            bool on[4];
+            int ea[4], eb[4];
+            double u[4], rh[4], gpv[4][NG], dv[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int a = a0 + 16 * (q >> 1), b = b0 + 16 * (q & 1);
+                on[q] = a <= m && b < m && b <= a;
+                ea[q] = on[q] ? a : m; eb[q] = on[q] ? b : 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int a = ea[q], b = eb[q];
+                u[q] = Ublk[(a < m && a / 6 == b / 6) ? (a / 6) * 36 + (a % 6) * 6 + (b % 6) : 0];
+                rh[q] = rhsblk[b];
+                // row m (the right-hand side) takes column m of G: (Yt^T g)[b]
+                const size_t gi = (a < m) ? (size_t)a * A.ldw + b : (size_t)b * A.ldw + m;
+#pragma unroll
+                for (int s = 0; s < NG; s++) gpv[q][s] = A.Gpart[(size_t)(SLICED ? min(s, gslices - 1) : s) * A.gp_rows * A.ldw + gi];
+                dv[q] = REUSE ? A.diag[min(a, m - 1)] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                if (!on[q]) continue;
+                const int a = ea[q], b = eb[q];
+                double v;
+                if (a < m) v = (a / 6 == b / 6) ? u[q] : 0.0;
+                else v = rh[q];
+                double g;
+                if (SLICED) {
+                    double hsum[BG_H];
+#pragma unroll
+                    for (int h = 0; h < BG_H; h++) {
+#pragma unroll
+                        for (int w = 0; w < BG_W; w++) {
+                            const int sl = h * BG_W + w;
+                            const double gv = sl < gslices ? gpv[q][SLICED ? sl : 0] : 0.0;
+                            hsum[h] = w == 0 ? gv : hsum[h] + gv;
+                        }
+                    }
+                    g = hsum[0];
+#pragma unroll
+                    for (int h = 1; h < BG_H; h++) g += hsum[h];
+                } else {
+                    g = gpv[q][0];
+#pragma unroll
+                    for (int h = 1; h < BG_H; h++) g += gpv[q][h];
+                }
+                if (a == b) {
+                    double d2;
+                    if (!REUSE) { d2 = fmin(fmax(v, 1e-6), 1e32); if (writer) A.diag[a] = d2; }
+                    else d2 = dv[q];
+                    v += d2 / radius;
+                }
+                S[(size_t)a * m + b] = v - g;
+            }
+        }
+    }
+}
+
+// S: loop-top tests, reduced camera system [S | rhs row] in LDS, right-looking Cholesky by camera blocks with the forward substitution
+// folded in as row m (two barriers per camera, the next diagonal block factored while the trailing update runs), backward substitution
+// in registers of wavefront 0 -> step_c; rotation constants of the candidate cameras.
+// FUSED (k_bam_solveback): the block goes on with the back-substitution of points [BM_PB bid, ...) and its load front is issued here.
 // The role reads the state the C|P launch left in st_in and nothing another block of its own launch writes, so any number of
 // blocks may run it side by side on their own LDS and arrive at the same bits; only a `writer` block stores what later
 // launches read (the state to st_out, A.step[0..m), A.diag[0..m), candrot). Returns the block's LDS copy of the state when
 // the step is valid (then S[0..m) holds the camera step and, if given, candrot_l the candidate cameras), else nullptr.
-__device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState* st_in, BAGState* st_out, bool writer,
+template <bool FUSED>
+__device__ __forceinline__ const BAGState* bam_solve_role(const BAArgs& A, const BAGState* st_in, BAGState* st_out, bool writer,
                                                  const int* __restrict__ chol_flag, const double* __restrict__ part_cost,
                                                  int nbo, const double* __restrict__ part_gmax, int nbp, const double* __restrict__ Ublk,
-                                                 const double* __restrict__ rhsblk, double* __restrict__ candrot, double* candrot_l, int gslices) {
+                                                 const double* __restrict__ rhsblk, double* __restrict__ candrot, double* candrot_l, int gslices,
+                                                 BsFront& F, int bid) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     __shared__ double red[3 * BM_NW];
     __shared__ BAGState ss;   // LDS copy of the state: read and updated here, stored to st_out by thread 0 of a writer block on every way out
@@ -1339,14 +1507,32 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
     if (tid == 0) { ss = *st_in; sfail = 0; }
     __syncthreads();
     if (ss.done) { SPUBLISH(); return nullptr; }
+    SSTAMP(21);
     const int nc = A.nc, m = 6 * nc, n = m + 3 * A.np;
     double* S = dyn; double* dg = dyn + (size_t)(m + 1) * m;   // S: (m+1) x m, row m = right-hand side; dg: 1 / diagonal of L
     const double* x = A.x + (size_t)ss.cur * n;
+    // the load front: with the state known, everything that does not depend on this launch's own arithmetic is asked for here (or, where an
+    // address needs an earlier answer, behind the next phase that waits for memory): the inputs of the loop-top tests below, the flag of the
+    // point blocks, the current cameras of the candidate step, and the front of the block's back-substitution
+    const int cflag = *chol_flag;
+    double cam_x[6], cam_s[6];
+    if (tid < nc) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) { cam_x[k] = x[6 * tid + k]; cam_s[k] = A.scale[6 * tid + k]; }
+    }
+    if (FUSED) bs_front_point(A, ss.cur, bid, F);
     if (ss.need_eval) {   // block-uniform
+        // each thread's first element of the three lists is asked for at once (one trip, not one per list; m < BM_T: rhsblk has no second)
+        double q_r = 0, q_s = 1, q_g = 0, q_c = 0;
+        if (tid < m) { q_r = rhsblk[tid]; q_s = A.scale[tid]; }
+        if (tid < nbp) q_g = part_gmax[tid];
+        if (tid < nbo) q_c = part_cost[tid];
         double g = 0, cs = 0;
-        for (int i = tid; i < m; i += BM_T) g = fmax(g, fabs(rhsblk[i] / A.scale[i]));
-        for (int i = tid; i < nbp; i += BM_T) g = fmax(g, part_gmax[i]);
-        for (int i = tid; i < nbo; i += BM_T) cs += part_cost[i];
+        if (tid < m) g = fmax(g, fabs(q_r / q_s));
+        if (tid < nbp) g = fmax(g, q_g);
+        for (int i = tid + BM_T; i < nbp; i += BM_T) g = fmax(g, part_gmax[i]);
+        if (tid < nbo) cs += q_c;
+        for (int i = tid + BM_T; i < nbo; i += BM_T) cs += part_cost[i];
         cs = wave_sum_f64(cs);
         g = wave_max_f64(g);
         if (lane == 0) { red[BM_NW + wid] = cs; red[2 * BM_NW + wid] = g; }
@@ -1371,88 +1557,39 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
     __syncthreads();
     if (ss.done) { SPUBLISH(); return nullptr; }
     SSTAMP(16);
+    if (FUSED) bs_front_record(A, F);   // (pobs_start has arrived with the inputs of the tests above)
     // ---- S = blockdiag(U_c) + D2_c - Yt^T Wt (lower triangle), row m = rhs_c - Yt^T g
     {
         const double radius = ss.radius;
-        const bool reuse = ss.reuse_diag != 0;
-        for (int a = ty; a <= m; a += 16) {
-            for (int b = tx; b < m && b <= a; b += 16) {
-                double v;
-                if (a < m) v = (a / 6 == b / 6) ? Ublk[(a / 6) * 36 + (a % 6) * 6 + (b % 6)] : 0.0;
-                else v = rhsblk[b];
-                // row m (the right-hand side) takes column m of G: (Yt^T g)[b]
-                const size_t gi = (a < m) ? (size_t)a * A.ldw + b : (size_t)b * A.ldw + m;
-                double g;
-                if (gslices) {   // Gpart = one raw partial per K-slice (k_bam_pointgemm): the G kernel's order, BG_W slices per half, slice by slice
-                    double hsum[BG_H];
-#pragma unroll
-                    for (int h = 0; h < BG_H; h++) {
-#pragma unroll
-                        for (int w = 0; w < BG_W; w++) {
-                            const int sl = h * BG_W + w;
-                            const double v = sl < gslices ? A.Gpart[(size_t)sl * A.gp_rows * A.ldw + gi] : 0.0;   // an empty slice adds +0.0, as its idle wavefront did
-                            hsum[h] = w == 0 ? v : hsum[h] + v;
-                        }
-                    }
-                    g = hsum[0];
-#pragma unroll
-                    for (int h = 1; h < BG_H; h++) g += hsum[h];
-                } else {         // Gpart = one partial per half (k_bam_gemm)
-                    g = A.Gpart[gi];
-#pragma unroll
-                    for (int h = 1; h < BG_H; h++) g += A.Gpart[(size_t)h * A.gp_rows * A.ldw + gi];
-                }
-                if (a == b) {
-                    double d2;
-                    if (!reuse) { d2 = fmin(fmax(v, 1e-6), 1e32); if (writer) A.diag[a] = d2; }
-                    else d2 = A.diag[a];
-                    v += d2 / radius;
-                }
-                S[(size_t)a * m + b] = v - g;
-            }
-        }
+        if (ss.reuse_diag) { if (gslices) bam_assemble_S<true, true>(A, S, m, Ublk, rhsblk, gslices, radius, writer, tx, ty);
+                             else bam_assemble_S<true, false>(A, S, m, Ublk, rhsblk, gslices, radius, writer, tx, ty); }
+        else { if (gslices) bam_assemble_S<false, true>(A, S, m, Ublk, rhsblk, gslices, radius, writer, tx, ty);
+               else bam_assemble_S<false, false>(A, S, m, Ublk, rhsblk, gslices, radius, writer, tx, ty); }
     }
+    if (FUSED) bs_front_rows(A, ss.cur, F);   // (the records have arrived with the inputs of S)
     __syncthreads();
-    if (*chol_flag) { SPUBLISH(); return nullptr; }   // a point block was not positive definite: invalid step (step_valid stays 0)
+    if (cflag) { SPUBLISH(); return nullptr; }   // a point block was not positive definite: invalid step (step_valid stays 0)
     SSTAMP(17);
-    // Blocked right-looking Cholesky, block = one camera (6 columns). Per block: (a) one thread factors the 6x6 diagonal
+    // Blocked right-looking Cholesky, block = one camera (6 columns). Per block: (a) wavefront 0 factors the 6x6 diagonal
     // block in registers (the only serial chain: 6 x sqrt + reciprocal), (b) one thread per row below solves its 6 entries
     // against the block (multiplications by the pivot reciprocals), (c) rank-6 update of the trailing lower triangle.
     // Row m carries the right-hand side, so the forward substitution is part of (b)/(c). dg keeps the pivot reciprocals.
+    // Schedule: wavefront 0 holds the chain. With camera jb's diagonal block factored, (b) runs for all rows; after one barrier wavefront 0
+    // updates the 21 trailing elements that are camera jb + 1's diagonal block (the first 21 of the triangular order) in registers and
+    // factors them at once (chol6_wave0), while wavefronts 1..3 update the rest of the trailing part; a second barrier closes the camera.
+    // Every element of S goes through the operations it went through in the three-barrier form, in that order.
+    int tl_r, tl_c;                       // wavefront 0: (row, column) of element `lane` of a diagonal block
+    tri6_rc(min(lane, 20), tl_r, tl_c);
+    constexpr int TU_T = BM_T - 64;       // threads of the trailing update (wavefronts 1..3)
+    int tu_r = 0, tu_c = 0;               // their first element, 21 + (tid - 64), of the triangular order: the same for every camera
+    if (wid > 0) tri_rc(21 + tid - 64, tu_r, tu_c);
+    if (wid == 0) {
+        const double v = lane < 21 ? S[(size_t)tl_r * m + tl_c] : 0.0;
+        if (!chol6_wave0(v, S, m, 0, dg, lane) && lane == 0) sfail = 1;
+    }
+    __syncthreads();
     for (int jb = 0; jb < nc; jb++) {
         const int j0 = 6 * jb;
-        if (tid == 0) {
-            double a[21];   // lower triangle, row-major: (i,k) -> i*(i+1)/2 + k
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-#pragma unroll
-                for (int k = 0; k <= i; k++) a[i * (i + 1) / 2 + k] = S[(size_t)(j0 + i) * m + j0 + k];
-            }
-            bool ok = true;
-            double r[6];
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const double d = a[j * (j + 1) / 2 + j];
-                ok = ok && (d > 0.0);
-                r[j] = rsqrt_nr(d);                      // pivot reciprocal; the diagonal of L itself is only kept for reference
-                a[j * (j + 1) / 2 + j] = d * r[j];
-#pragma unroll
-                for (int i = j + 1; i < 6; i++) a[i * (i + 1) / 2 + j] *= r[j];
-#pragma unroll
-                for (int i = j + 1; i < 6; i++) {
-#pragma unroll
-                    for (int k = j + 1; k <= i; k++) a[i * (i + 1) / 2 + k] -= a[i * (i + 1) / 2 + j] * a[k * (k + 1) / 2 + j];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-#pragma unroll
-                for (int k = 0; k <= i; k++) S[(size_t)(j0 + i) * m + j0 + k] = a[i * (i + 1) / 2 + k];
-                dg[j0 + i] = r[i];
-            }
-            if (!ok) sfail = 1;
-        }
-        __syncthreads();
         if (sfail) break;   // block-uniform
         {
             const int i = j0 + 6 + tid;   // rows below the block, row m = right-hand side (at most 6*22 - 6 + 1 < BM_T rows)
@@ -1477,15 +1614,25 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
             }
         }
         __syncthreads();
-        {
-            const int r0 = j0 + 6;                 // first trailing row / column
-            const int nr = m - r0;                 // trailing columns; rows r0..m (nr + 1 rows)
-            const int total = nr * (nr + 1) / 2 + nr;   // lower triangle of the nr x nr block + the right-hand-side row
-            for (int e = tid; e < total; e += BM_T) {
-                int ii = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);   // row of the triangular index, then exact fix-up
-                while ((ii + 1) * (ii + 2) / 2 <= e) ii++;
-                while (ii * (ii + 1) / 2 > e) ii--;
-                int kk = e - ii * (ii + 1) / 2;
+        SSTAMP(22);
+        if (jb + 1 == nc) break;                   // the last camera: its panel was the right-hand-side row alone, nothing trails
+        const int r0 = j0 + 6;                     // first trailing row / column
+        const int nr = m - r0;                     // trailing columns; rows r0..m (nr + 1 rows)
+        const int total = nr * (nr + 1) / 2 + nr;  // lower triangle of the nr x nr block + the right-hand-side row
+        if (wid == 0) {                            // elements 0..20: the next diagonal block, updated and factored without a stop in LDS
+            double acc = 0.0;
+            if (lane < 21) {
+                const double* Li = S + (size_t)(r0 + tl_r) * m + j0;
+                const double* Lk = S + (size_t)(r0 + tl_c) * m + j0;
+                acc = S[(size_t)(r0 + tl_r) * m + r0 + tl_c];
+#pragma unroll
+                for (int t = 0; t < 6; t++) acc -= Li[t] * Lk[t];
+            }
+            if (!chol6_wave0(acc, S, m, r0, dg, lane) && lane == 0) sfail = 1;
+        } else {                                   // elements 21..: rows walked from the thread's first element, no index search
+            int ri = tu_r, ci = tu_c;
+            for (int e = 21 + tid - 64; e < total; e += TU_T) {
+                int ii = ri, kk = ci;
                 if (ii >= nr) { ii = nr; kk = e - nr * (nr + 1) / 2; }   // the last nr entries are the right-hand-side row
                 const double* Li = S + (size_t)(r0 + ii) * m + j0;
                 const double* Lk = S + (size_t)(r0 + kk) * m + j0;
@@ -1493,9 +1640,12 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
 #pragma unroll
                 for (int t = 0; t < 6; t++) acc -= Li[t] * Lk[t];
                 S[(size_t)(r0 + ii) * m + r0 + kk] = acc;
+                ci += TU_T;
+                while (ci > ri) { ci -= ri + 1; ri++; }
             }
         }
         __syncthreads();
+        SSTAMP(23);
     }
     if (sfail) { SPUBLISH(); return nullptr; }
     SSTAMP(18);
@@ -1541,7 +1691,7 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
         if (lane < nc) {   // candidate cameras and their rotation constants, once per camera instead of once per observation
             double cx[6];
 #pragma unroll
-            for (int k = 0; k < 6; k++) cx[k] = x[6 * lane + k] + S[6 * lane + k] * A.scale[6 * lane + k];
+            for (int k = 0; k < 6; k++) cx[k] = cam_x[k] + S[6 * lane + k] * cam_s[k];   // (tid = lane < nc: loaded in the front)
             CamRot cr;
             cam_rot_setup(cx, cr);
             const double cv[7] = {cr.ct, cr.st, cr.ti, cr.w0, cr.w1, cr.w2, (double)cr.big};
@@ -1574,8 +1724,12 @@ __device__ inline const BAGState* bam_solve_role(const BAArgs& A, const BAGState
 // candidate point; phase C, per observation: model-cost-change and candidate-cost terms. Partials per block, fixed order.
 // st, step_c (the camera step, m doubles) and candrot are what the solve left: in global memory after a launch of its own, in
 // the block's LDS when the solve ran in this block (k_bam_solveback).
-__device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, const double* step_c, const double* candrot,
-                                        double* __restrict__ tmp3, double* __restrict__ part4, int bid) {
+// F is the block's load front (bs_front_*), complete. tmp3, the three doubles per record that phase A hands to phase B (the only data of
+// the launch that one thread writes and another reads), stays in the block: in tmp3_l, tmp3_rows rows of LDS, if the block's records fit
+// (block-uniform), else in its rows of the global array; the expressions are the same either way.
+__device__ __forceinline__ void bam_backsub_role(const BAArgs& A, const BAGState* st, const double* step_c, const double* candrot,
+                                                 double* __restrict__ tmp3, double* __restrict__ part4, int bid, const BsFront& F,
+                                                 double* tmp3_l, int tmp3_rows) {
     __shared__ double red[4 * BM_NW];
     __shared__ double sP[BM_PB * 6];   // per point of the block: step (3), candidate point (3)
     if (st->done || !st->step_valid) return;
@@ -1584,7 +1738,6 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
 #define BSTAMP(k) do { if (A.stamps && bid == 0 && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); A.stamps[k] += t_ - t_prev; t_prev = t_; } } while (0)
     const int nc = A.nc, m = 6 * nc, n = m + 3 * A.np;
     const int cur = st->cur;
-    const double* x = A.x + (size_t)cur * n;
     double* cand = A.x + (size_t)(cur ^ 1) * n;
     const double* Jb = A.J + (size_t)cur * A.nobs * 18;          // r, J at the current point
     const double* resb = A.res + (size_t)cur * A.nobs * 2;
@@ -1592,34 +1745,56 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
     double* resn = A.res + (size_t)(cur ^ 1) * A.nobs * 2;
     const bool spec = st->iter + 1 < st->max_iterations;         // after the last iteration nobody reads them
     const int p0 = bid * BM_PB, p1 = min(A.np, p0 + BM_PB);
-    const int eb0 = A.pobs_start[p0], eb1 = A.pobs_start[p1];
+    const int eb0 = F.eb0, eb1 = F.eb1;
+    const bool t3_lds = eb1 - eb0 <= tmp3_rows;   // block-uniform
+    if (A.stamps && bid == 0 && tid == 0) { A.stamps[24] += 1; A.stamps[25] += t3_lds ? 1 : 0; }   // diagnostic: launches, of them with tmp3 in LDS
     double mc = 0, cc = 0, dn2 = 0, xn2 = 0;
     for (int e = eb0 + tid; e < eb1; e += BM_T) {
-        const int4 rec = A.erec[e];
+        const bool first = e == eb0 + tid;   // the record of the front
+        const int4 rec = first ? F.rec : A.erec[e];
         const int i = rec.x, c = rec.y;
-        const double* Jr = Jb + (size_t)i * 18;
+        double Jr[18];
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 18; k++) Jr[k] = F.J[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 18; k++) Jr[k] = Jb[(size_t)i * 18 + k];
+        }
         double jy0 = 0, jy1 = 0;   // y_c = -step_c
 #pragma unroll
         for (int a = 0; a < 6; a++) { const double yc = -step_c[6 * c + a]; jy0 += Jr[a] * yc; jy1 += Jr[6 + a] * yc; }
+        if (t3_lds) {
 #pragma unroll
-        for (int a = 0; a < 3; a++) tmp3[(size_t)e * 3 + a] = Jr[12 + a] * jy0 + Jr[15 + a] * jy1;
+            for (int a = 0; a < 3; a++) tmp3_l[(e - eb0) * 3 + a] = Jr[12 + a] * jy0 + Jr[15 + a] * jy1;
+        } else {
+#pragma unroll
+            for (int a = 0; a < 3; a++) tmp3[(size_t)e * 3 + a] = Jr[12 + a] * jy0 + Jr[15 + a] * jy1;
+        }
     }
     __syncthreads();
     BSTAMP(10);
     const int p = p0 + tid;
     if (tid < BM_PB && p < p1) {
-        double t3[3] = {A.gp[(size_t)p * 3], A.gp[(size_t)p * 3 + 1], A.gp[(size_t)p * 3 + 2]};
-        for (int e = A.pobs_start[p]; e < A.pobs_start[p + 1]; e++) {
+        double t3[3] = {F.gp[0], F.gp[1], F.gp[2]};
+        if (t3_lds) {
+            for (int e = F.ps0; e < F.ps1; e++) {
 #pragma unroll
-            for (int a = 0; a < 3; a++) t3[a] -= tmp3[(size_t)e * 3 + a];
+                for (int a = 0; a < 3; a++) t3[a] -= tmp3_l[(e - eb0) * 3 + a];
+            }
+        } else {
+            for (int e = F.ps0; e < F.ps1; e++) {
+#pragma unroll
+                for (int a = 0; a < 3; a++) t3[a] -= tmp3[(size_t)e * 3 + a];
+            }
         }
-        const double* Ei = A.Einv + (size_t)p * 9;
+        const double* Ei = F.Ei;
 #pragma unroll
         for (int a = 0; a < 3; a++) {
             const double sp = -(Ei[a * 3] * t3[0] + Ei[a * 3 + 1] * t3[1] + Ei[a * 3 + 2] * t3[2]);
             A.step[m + 3 * p + a] = sp;
-            const double d = sp * A.scale[m + 3 * p + a];
-            const double xo = x[m + 3 * p + a];
+            const double d = sp * F.xs[a];
+            const double xo = F.xo[a];
             xn2 += xo * xo;
             const double xp = xo + d;
             cand[m + 3 * p + a] = xp;
@@ -1630,9 +1805,29 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
     __syncthreads();
     BSTAMP(11);
     for (int e = eb0 + tid; e < eb1; e += BM_T) {
-        const int4 rec = A.erec[e];
+        const bool first = e == eb0 + tid;   // the record of the front
+        const int4 rec = first ? F.rec : A.erec[e];
         const int i = rec.x, c = rec.y, pl = rec.z - p0;
-        const double* Jr = Jb + (size_t)i * 18;
+        double Jr[18], rs[2], ob[2], scc[6], scp[3];
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 18; k++) Jr[k] = F.J[k];
+#pragma unroll
+            for (int k = 0; k < 2; k++) { rs[k] = F.res[k]; ob[k] = F.ob[k]; }
+#pragma unroll
+            for (int k = 0; k < 6; k++) scc[k] = F.scc[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) scp[k] = F.scp[k];
+        } else {   // all of the record's inputs in one go
+#pragma unroll
+            for (int k = 0; k < 18; k++) Jr[k] = Jb[(size_t)i * 18 + k];
+#pragma unroll
+            for (int k = 0; k < 2; k++) { rs[k] = resb[2 * i + k]; ob[k] = A.obs[2 * i + k]; }
+#pragma unroll
+            for (int k = 0; k < 6; k++) scc[k] = A.scale[6 * c + k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) scp[k] = A.scale[6 * A.nc + 3 * rec.z + k];
+        }
         double sc[6], sp[3], xp[3];
 #pragma unroll
         for (int k = 0; k < 6; k++) sc[k] = step_c[6 * c + k];
@@ -1645,7 +1840,7 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
             for (int k = 0; k < 6; k++) mr += Jr[rr * 6 + k] * sc[k];
 #pragma unroll
             for (int k = 0; k < 3; k++) mr += Jr[12 + rr * 3 + k] * sp[k];
-            mc -= mr * (resb[2 * i + rr] + mr / 2.0);
+            mc -= mr * (rs[rr] + mr / 2.0);
         }
         const double* o = candrot + 16 * c;
         CamRot cr;
@@ -1653,30 +1848,29 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
         double r[2], rho0, rho1;
         if (spec) {
             double Jc[12], Jp[6];
-            projection_residual_pre(cr, o, xp, A.obs[2 * i], A.obs[2 * i + 1], A.K, r, Jc, Jp, true);
+            projection_residual_pre(cr, o, xp, ob[0], ob[1], A.K, r, Jc, Jp, true);
             huber_rho(r[0] * r[0] + r[1] * r[1], A.huber, rho0, rho1);
             const double sr = sqrt(rho1);
             resn[2 * i] = r[0] * sr; resn[2 * i + 1] = r[1] * sr;
-            const double* scc = A.scale + 6 * c;
-            const double* scp = A.scale + 6 * A.nc + 3 * (pl + p0);
             double* Jo = Jn + (size_t)i * 18;
 #pragma unroll
             for (int k = 0; k < 12; k++) Jo[k] = Jc[k] * sr * scc[k % 6];
 #pragma unroll
             for (int k = 0; k < 6; k++) Jo[12 + k] = Jp[k] * sr * scp[k % 3];
         } else {
-            projection_residual_pre(cr, o, xp, A.obs[2 * i], A.obs[2 * i + 1], A.K, r, nullptr, nullptr, false);
+            projection_residual_pre(cr, o, xp, ob[0], ob[1], A.K, r, nullptr, nullptr, false);
             huber_rho(r[0] * r[0] + r[1] * r[1], A.huber, rho0, rho1);
         }
         cc += 0.5 * rho0;
     }
     BSTAMP(12);
     if (bid == 0) {   // camera part of the candidate and of the step norm
-        for (int i = tid; i < m; i += BM_T) {
-            const double d = step_c[i] * A.scale[i];
-            cand[i] = x[i] + d;
+        if (tid < m) {
+            const int i = tid;
+            const double d = step_c[i] * F.cam_s;
+            cand[i] = F.cam_x + d;
             dn2 += d * d;
-            xn2 += x[i] * x[i];
+            xn2 += F.cam_x * F.cam_x;
         }
     }
     mc = wave_sum_f64(mc); cc = wave_sum_f64(cc); dn2 = wave_sum_f64(dn2); xn2 = wave_sum_f64(xn2);
@@ -1697,17 +1891,19 @@ __device__ inline void bam_backsub_role(const BAArgs& A, const BAGState* st, con
 // for), then continues with its points; the step, the candidate cameras and the state never leave LDS on the way. Block 0
 // publishes them for the launches that follow; the state goes to st_out, not back to st_in, because a block that starts late
 // must still read what the C|P launch wrote.
-// dynamic LDS: [S (m+1) x m | dg m | candrot 16 nc]
+// dynamic LDS: [S (m+1) x m | dg m | candrot 16 nc | tmp3 3 tmp3_rows]
 __global__ __launch_bounds__(BM_T) void k_bam_solveback(BAArgs A, const BAGState* st_in, BAGState* st_out, const int* chol_flag,
                                                         const double* part_cost, int nbo, const double* part_gmax, int ngm,
                                                         const double* Ublk, const double* rhsblk, double* candrot, double* tmp3,
-                                                        double* part4, int gslices) { BACKEND_PRIO();
+                                                        double* part4, int gslices, int tmp3_rows) { BACKEND_PRIO();
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int m = 6 * A.nc;
     double* candrot_l = dyn + (size_t)(m + 1) * m + m;
-    const BAGState* ss = bam_solve_role(A, st_in, st_out, blockIdx.x == 0, chol_flag, part_cost, nbo, part_gmax, ngm, Ublk, rhsblk, candrot, candrot_l, gslices);
+    BsFront F = {};
+    const BAGState* ss = bam_solve_role<true>(A, st_in, st_out, blockIdx.x == 0, chol_flag, part_cost, nbo, part_gmax, ngm, Ublk, rhsblk, candrot, candrot_l,
+                                              gslices, F, blockIdx.x);
     if (!ss) return;   // block-uniform: terminated or invalid step
-    bam_backsub_role(A, ss, dyn, candrot_l, tmp3, part4, blockIdx.x);
+    bam_backsub_role(A, ss, dyn, candrot_l, tmp3, part4, blockIdx.x, F, candrot_l + 16 * A.nc, tmp3_rows);
 }
 
 // F: decision on the last step, results
@@ -1740,6 +1936,11 @@ __global__ __launch_bounds__(BM_T) void k_bam_finish(BAArgs A, const BAGState* s
     bam_finish_role(A, st_in, part4, nbp);
 }
 
+// Rows of tmp3 (3 doubles each) that a block of k_bam_solveback keeps in LDS: what the reduced camera system leaves of the 150 KB, at most
+// one per observation. A block with more records than that takes its rows of the global tmp3.
+static int bam_tmp3_lds_rows(size_t shm_solve, int nobs) {
+    return (int)std::min<size_t>((size_t)std::max(nobs, 0), (150 * 1024 - shm_solve) / (3 * sizeof(double)));
+}
 hipError_t launch_ba_multi(hipStream_t s, const BAArgs& A, void* d_state, double* d_part) {
     // two copies of the state, each written by one kind of launch and read by the other: sa by E0 and C|P (the decision), sb by S|B
     BAGState* sa = (BAGState*)d_state;
@@ -1754,8 +1955,10 @@ hipError_t launch_ba_multi(hipStream_t s, const BAArgs& A, void* d_state, double
     double* rhsblk = Ublk + 36 * A.nc;          // nc * 6
     double* candrot = rhsblk + 6 * A.nc;        // nc * 16
     double* tmp3 = candrot + 16 * A.nc;         // nobs * 3
-    const size_t shm = ((size_t)(m + 1) * m + (size_t)m + (size_t)16 * A.nc) * sizeof(double);   // k_bam_solveback: [S | dg | candrot]
-    if (A.max_iterations > BA_MAX_ITERATIONS || shm > 150 * 1024) return hipErrorInvalidValue;
+    const size_t shm_s = ((size_t)(m + 1) * m + (size_t)m + (size_t)16 * A.nc) * sizeof(double);   // k_bam_solveback: [S | dg | candrot | tmp3]
+    if (A.max_iterations > BA_MAX_ITERATIONS || shm_s > 150 * 1024) return hipErrorInvalidValue;
+    const int tmp3_rows = bam_tmp3_lds_rows(shm_s, A.nobs);
+    const size_t shm = shm_s + (size_t)tmp3_rows * 3 * sizeof(double);
     ProfScope ps(K_BA_LM, s);
     const int tiles = A.tiles_r * A.tiles_c;
     // From the second iteration on the point blocks multiply their own rows (k_bam_pointgemm) when a wavefront per tile fits a block, a
@@ -1785,7 +1988,7 @@ hipError_t launch_ba_multi(hipStream_t s, const BAArgs& A, void* d_state, double
         hipLaunchKernelGGL(k_bam_gemm, dim3(tiles * BG_H), dim3(64 * BG_W), 0, s, A, sa); }
         { ProfScope p_(K_BAM_SOLVEBACK, s);
         hipLaunchKernelGGL(k_bam_solveback, dim3(nbp), dim3(BM_T), shm, s, A, sa, sb, cf, part_cost, nbo, part_gmax, sliced ? A.kslices : nbp, Ublk,
-                           rhsblk, candrot, tmp3, part4, sliced ? A.kslices : 0); }
+                           rhsblk, candrot, tmp3, part4, sliced ? A.kslices : 0, tmp3_rows); }
     }
     { ProfScope p_(K_BAM_FINISH, s);
     hipLaunchKernelGGL(k_bam_finish, dim3(1), dim3(BM_T), 0, s, A, sb, part4, nbp); }
@@ -1839,13 +2042,20 @@ __global__ __launch_bounds__(BM_T) void k_bamB_solve(const BAProb* __restrict__ 
     const BAProb& P = probs[blockIdx.x];
     const BAArgs A = P.A;   // by value (uniform address -> scalar loads once); a reference would be re-read after every store: 29 -> 57 us for k_bamB_campoint
     BAGState* st = (BAGState*)P.st2[(it + 1) & 1];   // one block per problem: the state is updated in place
-    bam_solve_role(A, st, st, true, P.chol_flags + it, P.part_cost, P.nbo, P.part_gmax, P.nbp, P.Ublk, P.rhsblk, P.candrot, nullptr, 0);
+    BsFront F;   // (not used: the back-substitution is a launch of its own)
+    bam_solve_role<false>(A, st, st, true, P.chol_flags + it, P.part_cost, P.nbo, P.part_gmax, P.nbp, P.Ublk, P.rhsblk, P.candrot, nullptr, 0, F, 0);
 }
 __global__ __launch_bounds__(BM_T) void k_bamB_backsub(const BAProb* __restrict__ probs, int it) { BACKEND_PRIO();
     const BAProb& P = probs[blockIdx.y];
     if ((int)blockIdx.x >= P.nbp) return;
     const BAArgs A = P.A;   // by value (uniform address -> scalar loads once); a reference would be re-read after every store: 29 -> 57 us for k_bamB_campoint
-    bam_backsub_role(A, (const BAGState*)P.st2[(it + 1) & 1], A.step, P.candrot, P.tmp3, P.part4, blockIdx.x);
+    const BAGState* st = (const BAGState*)P.st2[(it + 1) & 1];
+    if (st->done || !st->step_valid) return;
+    BsFront F = {};
+    bs_front_point(A, st->cur, blockIdx.x, F);
+    bs_front_record(A, F);
+    bs_front_rows(A, st->cur, F);
+    bam_backsub_role(A, st, A.step, P.candrot, P.tmp3, P.part4, blockIdx.x, F, nullptr, -1);   // tmp3 through its global rows
 }
 __global__ __launch_bounds__(BM_T) void k_bamB_finish(const BAProb* __restrict__ probs, int max_it) { BACKEND_PRIO();
     const BAProb& P = probs[blockIdx.x];
