@@ -35,6 +35,7 @@
  *   pmv_find_essential_mat                 cv::findEssentialMat (the whole RANSAC)       (OpenCVFivePointTri.cpp:24) -> BaseTriangulator.h
  *   pmv_find_fundamental_mat               cv::findFundamentalMat, FM_RANSAC (a KLT loop's rejectWithF; not a call of the reference)
  *   pmv_find_homography                    cv::findHomography, RANSAC with its refit (planar scenes, pure rotations; not a call of the reference)
+ *   pmv_triangulate_tracks                 N-view DLT + Gauss-Newton + gates per track landmark (FeatureManager::triangulate of a VINS-style caller; not a call of the reference)
  *   pmv_recover_pose                       cv::recoverPose (the whole call)              (OpenCVFivePointTri.cpp:27) -> BaseTriangulator.h
  *   pmv_ba_residuals / pmv_ba_solve        ProjectionResidual + ceres::Solve             (ProjectionResidual.h:38-58,
  *                                          CeresBundleAdjustment.cpp:50-61)              -> BaseOptimizer.h:15
@@ -783,6 +784,60 @@ int pmv_triangulate_candidates(pmv_ctx* ctx, const double* q1, const double* q2,
 int pmv_triangulate_candidates_ahead(pmv_ctx* ctx, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
                                      double* out_Q, uint8_t* out_mask, int* out_good);
 
+/* ---- N-view triangulation of track landmarks: the link between the tracker's observations and pmv_klt_set_prediction / pmv_ba_solve ----------
+ * What FeatureManager::triangulate of a VINS-style estimator or cv::sfm::triangulatePoints does on the host: every landmark of a sliding
+ * window is triangulated from ALL its observations. obs_xy (n_obs x 2), cam_idx, pt_idx and n_obs are exactly the arrays of pmv_ba_solve: a
+ * caller hands the same arrays to both calls. P3x4: one general row-major projection matrix per camera, nc x 12 doubles - [R|t] for
+ * normalised observations, K[R|t] for pixels; its third row must give the depth, P[2].(X,1) (so a matrix scaled by -1, or pmv_ba_solve's own
+ * camera form with pz = -p[2], is not one: the Python helper projections_from_ba_cams makes the matrices of that form). out_xyz np x 3,
+ * out_status np bytes (PMV_TRI_* bits, 0 = accepted), out_err_or_null np doubles (the rms reprojection error over the landmark's views, in the
+ * observations' unit), *out_good = landmarks with status 0. ONE launch per call (k_tri_tracks: one lane per landmark, 64-lane workgroups),
+ * one copy in, results in a mapped pinned block behind a completion word, one wait; the result has the bits of
+ * tests/twin/tri_tracks_twin.cpp, the CPU restatement that fixes them.
+ *   Capacities: the context's BA caps - nc <= max_ba_cams, np <= max_ba_points, n_obs <= max_ba_obs, else PMV_ERR_CAPACITY (negative np or
+ *     n_obs too). np == 0 or n_obs == 0 is valid: nothing is launched, every landmark is FEW_VIEWS, *out_good = 0.
+ *   Lists: a landmark's observations are taken in order of appearance in the caller's arrays (a stable counting sort on the host during
+ *     stage-in); pt_idx need not be sorted; a camera may occur twice. Fewer than min_views observations: PMV_TRI_FEW_VIEWS.
+ *   DLT: per observation two rows, x P[8+k] - P[k] and y P[8+k] - P[4+k] (k = 0..3); AtA (4x4) accumulated row by row in list order from 0;
+ *     the eigenvector Qh of its smallest eigenvalue by the cyclic Jacobi of pmv_triangulate_candidates - the statement and the operation
+ *     order of that call's kernel, so a two-observation landmark whose first camera is [I|0] has its bits; X = Qh[0..2] / Qh[3].
+ *     Qh[3] == 0 or a non-finite X: PMV_TRI_DEGENERATE.
+ *   Refinement (refine_iters > 0): Gauss-Newton on sum |pi(P_i X) - obs_i|^2 over the three coordinates; JtJ and Jtr accumulated in list
+ *     order; the 3x3 system solved by the explicit adjugate over the determinant; a step is taken only if the new cost is strictly smaller,
+ *     and the first step that is not ends the refinement (the undamped step from the same X would be the same again). A zero or non-finite
+ *     determinant or a non-finite cost ends the refinement with the X it had.
+ *   Gates: all evaluated, no early exit, status bits OR-ed. FEW_VIEWS and DEGENERATE short-circuit: out_xyz = 0 and out_err = +inf for them.
+ *     Depth of view i is P_i[2].(X,1); it must lie in [min_depth, max_depth] in every view, else PMV_TRI_DEPTH. The reprojection error of a
+ *     view is the Euclidean distance in the observations' unit; a view whose error is not <= max_reproj: PMV_TRI_REPROJ (max_reproj = +inf:
+ *     no gate). Parallax: the camera centres C = -M^-1 p4 by the adjugate, computed once per call on the host and only if the gate is on (a
+ *     camera with det M == 0 is then PMV_ERR_INVALID; the message names the camera); the smallest cosine over pairs i < j of
+ *     (C_i - X).(C_j - X) / sqrt(|.|^2 |.|^2) must be <= cos(min_parallax_deg pi / 180) from the host's libm, else PMV_TRI_PARALLAX; a
+ *     non-finite cosine counts as no parallax. The device never evaluates a transcendental function.
+ *   Errors, each with its code and its message, nothing is written: null pointers (out_err_or_null and p_or_null may be null), nc < 1:
+ *     PMV_ERR_INVALID; cam_idx or pt_idx out of range (the message names the observation), non-finite P or obs, min_views < 2,
+ *     refine_iters outside 0..20, min_depth not finite or max_depth < min_depth, max_reproj <= 0 or NaN, min_parallax_deg outside [0, 180):
+ *     PMV_ERR_INVALID. Not logged by pmv_record_enable. */
+enum { PMV_TRI_OK = 0, PMV_TRI_FEW_VIEWS = 1, PMV_TRI_DEGENERATE = 2, PMV_TRI_DEPTH = 4, PMV_TRI_REPROJ = 8, PMV_TRI_PARALLAX = 16 };
+typedef struct pmv_tri_params {
+    int    min_views;         /* >= 2 */
+    int    refine_iters;      /* 0..20 Gauss-Newton iterations on the reprojection error behind the DLT; 0 = DLT only */
+    double min_depth, max_depth;   /* accepted depth in EVERY observing view; max_depth may be +inf */
+    double max_reproj;        /* largest accepted reprojection error of any view, in the observations' unit; +inf = no gate */
+    double min_parallax_deg;  /* the largest angle between two viewing rays at X must reach it; 0 = no gate */
+} pmv_tri_params;             /* NULL = {2, 0, 0.1, +inf, +inf, 0}: VINS-Mono's triangulate with its depth test */
+int pmv_triangulate_tracks(pmv_ctx* ctx, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                           const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good);
+/* diagnostic, ctx-free: the argument rules of pmv_triangulate_tracks for a context of the given BA caps, in its order and with its codes
+ * (the singular camera of the parallax gate included); reads the inputs, writes nothing but err256 (optional: the message the call would
+ * leave, 256 bytes). */
+int pmv_debug_tri_tracks_check(int max_cams, int max_points, int max_obs, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx,
+                               const int* pt_idx, int n_obs, int np, const pmv_tri_params* p_or_null, const double* out_xyz, const uint8_t* out_status,
+                               const double* out_err_or_null, const int* out_good, char* err256);
+/* diagnostic: out2 = {k_tri_tracks and k_tri_tracks_batch launches, requests they served} since the context was created
+ * (pmv_triangulate_tracks: one each, none for an empty problem; pmv_batch_triangulate_tracks: one launch per round of the DLT combiner that
+ * holds such requests). */
+int pmv_debug_tri_tracks_launches(pmv_ctx* ctx, long long* out2);
+
 /* ---- the two calls of the triangulator, whole (OpenCVFivePointTri.cpp:24-27) ------------------------------------------------------------
  * cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold, mask) (OpenCVFivePointTri.cpp:24). p1_xy, p2_xy: n pixel coordinates
  * (x, y) as doubles; K: 9 doubles, row-major; E9 row-major; mask n bytes; *out_samples_drawn = RANSAC iterations made. *out_found 0 = no
@@ -1442,6 +1497,13 @@ int pmv_batch_find_fundamental_mat(pmv_ctx* ctx, int seq, const float* p1_xy, co
  * seq's fundamental and homography calls share their staging blocks, so one of the two at a time. */
 int pmv_batch_find_homography(pmv_ctx* ctx, int seq, const float* p1_xy, const float* p2_xy, int n, double threshold, double confidence, int max_iters,
                               double* H9, uint8_t* mask, int* out_found, int* out_samples_drawn);
+/* pmv_triangulate_tracks for a seq, argument for argument (its rules, its capacities, its empty problems, which launch nothing and enter no
+ * round) with `seq` (0 .. n_seq - 1, else PMV_ERR_INVALID) after the context; the bits of the single call. A request of the DLT combiner:
+ * a round serves all its requests of this kind with ONE k_tri_tracks_batch launch, one row of 64-landmark workgroups per request, beside
+ * the launch for the round's pmv_batch_triangulate_candidates / pmv_batch_recover_pose requests; the requests are counted under the "dlt"
+ * role of pmv_batch_stats and the launches by pmv_debug_tri_tracks_launches. One outstanding call per seq and call. */
+int pmv_batch_triangulate_tracks(pmv_ctx* ctx, int seq, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
+                                 int np, const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good);
 /* out4 = {upload rounds, frames uploaded, level-0 launches, pyrDown launches} since pmv_batch_open: level-0 launches <= 2 x rounds (+ 1 for a
  * round with pmv_batch_frame_upload_clahe requests: the in-place launch behind the equalisation; + 1 for a round with
  * pmv_batch_frame_upload_remap requests: the launch from the remap scratch), and the

@@ -51,6 +51,39 @@ class ClaheParams(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
 
 
+class TriParams(C.Structure):
+    """pmv_tri_params of include/pmv_hip.h; the defaults are the call's (a null pointer): VINS-Mono's triangulate with its depth test"""
+    _fields_ = [("min_views", C.c_int), ("refine_iters", C.c_int), ("min_depth", C.c_double), ("max_depth", C.c_double), ("max_reproj", C.c_double),
+                ("min_parallax_deg", C.c_double)]
+
+    def __init__(self, min_views=2, refine_iters=0, min_depth=0.1, max_depth=float("inf"), max_reproj=float("inf"), min_parallax_deg=0.0):
+        super().__init__(int(min_views), int(refine_iters), float(min_depth), float(max_depth), float(max_reproj), float(min_parallax_deg))
+
+
+# status bits of pmv_triangulate_tracks (PMV_TRI_* of include/pmv_hip.h); 0 = accepted
+TRI_OK, TRI_FEW_VIEWS, TRI_DEGENERATE, TRI_DEPTH, TRI_REPROJ, TRI_PARALLAX = 0, 1, 2, 4, 8, 16
+
+
+def projections_from_ba_cams(cams, K=None):
+    """The projection matrices (nc, 3, 4) of pmv_triangulate_tracks for cameras in pmv_ba_solve's form, cam = [angle-axis w, c]: p = R(w) (X + c),
+    depth pz = -p[2], u = fx p[0] / pz + cx, v = fy p[1] / pz + cy. Their projections have zero ProjectionResidual for that form and their third
+    row gives pz. K (3, 3) for pixel observations; None for normalised ones (fx = fy = 1, cx = cy = 0)."""
+    cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 6)
+    Kd = np.eye(3) if K is None else np.ascontiguousarray(K, np.float64).reshape(3, 3)
+    Kn = np.array([[Kd[0, 0], 0.0, -Kd[0, 2]], [0.0, Kd[1, 1], -Kd[1, 2]], [0.0, 0.0, -1.0]])
+    out = np.zeros((len(cams), 3, 4))
+    for i, cam in enumerate(cams):
+        w, th2 = cam[:3], float(cam[:3] @ cam[:3])
+        Wx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+        if th2 > np.finfo(np.float64).eps:
+            th = np.sqrt(th2)
+            R = np.eye(3) + np.sin(th) / th * Wx + (1.0 - np.cos(th)) / th2 * (Wx @ Wx)
+        else:
+            R = np.eye(3) + Wx   # (the first-order form ProjectionResidual's rotation takes near zero)
+        out[i] = Kn @ np.c_[R, R @ cam[3:]]
+    return out
+
+
 KLT_MAX_TRACKERS = 16   # PMV_KLT_MAX_TRACKERS of include/pmv_hip.h
 
 
@@ -445,6 +478,7 @@ ABI_SYMBOLS = [
     "pmv_find_essential_mat", "pmv_recover_pose", "pmv_debug_essential_iters_table",
     "pmv_find_fundamental_mat", "pmv_debug_fundamental_iters_table", "pmv_debug_set_fundamental_r", "pmv_debug_fundamental_r", "pmv_debug_whole_rounds",
     "pmv_find_homography", "pmv_debug_homography_iters_table", "pmv_debug_homography_check", "pmv_debug_homography_launches",
+    "pmv_triangulate_tracks", "pmv_batch_triangulate_tracks", "pmv_debug_tri_tracks_check", "pmv_debug_tri_tracks_launches",
     "pmv_klt_create", "pmv_klt_destroy", "pmv_klt_set_tracks", "pmv_klt_get_tracks", "pmv_klt_step", "pmv_debug_klt_stats",
     "pmv_klt_step_many", "pmv_debug_klt_many_stats",
     "pmv_klt_set_stereo", "pmv_klt_get_stereo", "pmv_klt_step_stereo", "pmv_klt_step_many_stereo", "pmv_debug_klt_stereo_stats",
@@ -1385,6 +1419,37 @@ class Context:
         self._ck(self.lib.pmv_debug_homography_launches(self.h, out))
         return int(out[0]), int(out[1])
 
+    def _triangulate_tracks(self, call, ck, head, P3x4, obs_xy, cam_idx, pt_idx, n_points, params):
+        P = np.ascontiguousarray(P3x4, np.float64).reshape(-1, 12)
+        obs = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+        ci = np.ascontiguousarray(cam_idx, np.int32).reshape(-1)
+        pi = np.ascontiguousarray(pt_idx, np.int32).reshape(-1)
+        if not (len(obs) == len(ci) == len(pi)):
+            raise ValueError(f"obs_xy {obs.shape}, cam_idx {ci.shape} and pt_idx {pi.shape}: one entry per observation in each")
+        n_obs, n_pts = len(obs), int(n_points)
+        if params is not None and not isinstance(params, TriParams):
+            params = TriParams(**params)
+        xyz = np.zeros((max(n_pts, 0), 3), np.float64)
+        status = np.zeros(max(n_pts, 0), np.uint8)
+        err = np.zeros(max(n_pts, 0), np.float64)
+        good = C.c_int()
+        ck(call(self.h, *head, _p(P, _f64p), P.shape[0], _p(obs, _f64p), _p(ci, _i32p), _p(pi, _i32p), n_obs, n_pts, C.byref(params) if params is not None else None,
+                _p(xyz, _f64p), _p(status, _u8p), _p(err, _f64p), C.byref(good)))
+        return xyz, status, err, good.value
+
+    def triangulate_tracks(self, P3x4, obs_xy, cam_idx, pt_idx, n_points, params=None):
+        """pmv_triangulate_tracks: every landmark of a window from ALL its observations - N-view DLT, optional Gauss-Newton refinement, depth /
+        reprojection / parallax gates - in one launch. P3x4 (nc, 3, 4) general projection matrices whose third row gives the depth
+        (projections_from_ba_cams for pmv_ba_solve's cameras); obs_xy, cam_idx, pt_idx: the arrays of ba_solve; params: a TriParams, a dict of
+        its fields, or None for the call's defaults. Returns (xyz (n_points, 3), status (n_points,) of TRI_* bits, err (n_points,), good)."""
+        return self._triangulate_tracks(self.lib.pmv_triangulate_tracks, self._ck, (), P3x4, obs_xy, cam_idx, pt_idx, n_points, params)
+
+    def tri_tracks_launches(self):
+        """(k_tri_tracks / k_tri_tracks_batch launches, requests they served) since the context was created"""
+        out = (C.c_longlong * 2)()
+        self._ck(self.lib.pmv_debug_tri_tracks_launches(self.h, out))
+        return int(out[0]), int(out[1])
+
     # ---- device-resident KLT tracker ----
     def klt_create(self, **params):
         """pmv_klt_create: a KltTracker whose track list stays on the device; one step() per frame runs LK (forward-backward), the filter,
@@ -1840,6 +1905,10 @@ class Context:
 
     def batch_triangulate_candidates(self, seq, q1, q2, P1x4, mask_in):
         return self._triangulate_candidates(self.lib.pmv_batch_triangulate_candidates, self._ckt, (int(seq),), q1, q2, P1x4, mask_in)
+
+    def batch_triangulate_tracks(self, seq, P3x4, obs_xy, cam_idx, pt_idx, n_points, params=None):
+        """triangulate_tracks for sequence `seq` of the session: the round's requests of this kind share one launch"""
+        return self._triangulate_tracks(self.lib.pmv_batch_triangulate_tracks, self._ckt, (int(seq),), P3x4, obs_xy, cam_idx, pt_idx, n_points, params)
 
     def batch_fivepoint_hypotheses(self, seq, q1, q2, samples, thr):
         return self._fivepoint_hypotheses(self.lib.pmv_batch_fivepoint_hypotheses, self._ckt, (int(seq),), q1, q2, samples, thr)

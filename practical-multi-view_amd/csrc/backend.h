@@ -27,6 +27,7 @@ struct BackendBuffers {   // every buffer: one row of backend_alloc's table; fre
     Buf<char> d_fp_work;   // five-point round: [models FP_MAX_HYP x 90 doubles | n_models FP_MAX_HYP ints] (inputs share d_tri_in: fivepoint_layout)
     Buf<char> d_ess_in;    // whole findEssentialMat RANSAC: the in-block of essential_layout
     Buf<char> d_fund_in;   // whole findFundamentalMat RANSAC: the in-block of fundamental_layout; made by the set's first such call (fundamental_prepare)
+    Buf<char> d_tt_in;     // N-view triangulation: the in-block of tri_tracks_layout
     // single-copy transfers: one mapped pinned staging block (result blocks are written straight into it through .dm()) and one device
     // block per direction
     Buf<char> h_stage;
@@ -132,6 +133,22 @@ struct DltProblem { const double* P1x4; const double* q1; const double* q2; cons
 hipError_t launch_tri_dlt_batch(hipStream_t s, const DltProblem* d_probs, int n_probs, int max_n);
 hipError_t launch_tri_dlt(hipStream_t s, const double* d_P1x4, const double* d_q1, const double* d_q2, const uint8_t* d_mask_in, int n,
                           double* d_Q, uint8_t* d_mask);
+// one N-view triangulation request (k_tri_tracks / k_tri_tracks_batch, backend_tritracks.hip): one lane per landmark
+struct TriTracksProblem {
+    const double* P; const double* C;     // device: nc projection matrices (12 doubles each); nc camera centres (read with parallax_on only)
+    const double* obs; const int* cam;    // device: the observations re-ordered into per-landmark runs - (x, y) and camera of each
+    const int* start;                     // device: np + 1 run starts
+    unsigned* counter;                    // device: workgroups of this request that are done (0 when the launch starts)
+    char* out;                            // mapped pinned result block: [completion word, TT_OUT_HDR bytes | xyz 3 np | err np doubles | status np bytes]
+    double min_depth, max_depth, max_reproj, cos_thr;   // cos_thr: cos(min_parallax_deg) from the host's libm
+    int nc, np, min_views, refine_iters, parallax_on;
+    unsigned done_seq;                    // != 0; the request's last store, into the result block's completion word
+};
+static_assert(sizeof(TriTracksProblem) <= TT_HDR, "the record is the header of the input block");
+constexpr int TT_LDS_CAMS = 64;           // projection matrices and centres in LDS up to this many cameras (7.5 KB); beyond it through L2
+constexpr int TT_MAX_REFINE = 20;         // pmv_tri_params::refine_iters at most
+hipError_t launch_tri_tracks(hipStream_t s, const TriTracksProblem* d_rec, int np);
+hipError_t launch_tri_tracks_batch(hipStream_t s, const TriTracksProblem* d_probs, int n_probs, int max_np);
 
 // prepare / finish halves of the back-end entry points (backend.hip), shared by the single calls and the batch engine
 struct PnPProblem; struct DltProblem;
@@ -192,4 +209,19 @@ int dlt_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double*
                 DltLayout* L);
 void dlt_finish(pmv_ctx* ctx, BackendBuffers* b, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in,
                 const DltLayout& L, double* out_Q, uint8_t* out_mask, int* out_good);
+// N-view triangulation of track landmarks: argument rules of pmv_triangulate_tracks (outputs untouched on error; tri_tracks_args_check is
+// their ctx-free statement for a context of the given BA caps, err: the message, 256 bytes; p_or_null = null: the defaults). prepare groups
+// the observations by landmark (stable counting sort), computes the camera centres if the parallax gate is on (PMV_ERR_INVALID for a camera
+// with det M == 0), fills b's pinned block and the record and clears the completion word; finish reads the result block. A problem with
+// np == 0 or n_obs == 0 is not prepared: tri_tracks_empty writes its outputs.
+pmv_tri_params tri_tracks_defaults();
+int tri_tracks_args_check(int max_cams, int max_points, int max_obs, const char* who, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx,
+                          const int* pt_idx, int n_obs, int np, const pmv_tri_params* p_or_null, const double* out_xyz, const uint8_t* out_status,
+                          const int* out_good, char* err);
+int tri_tracks_check(pmv_ctx* ctx, const char* who, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                     const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, int* out_good);
+int tri_tracks_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
+                       int np, const pmv_tri_params* p_or_null, TriTracksProblem* P, TriTracksLayout* L);
+void tri_tracks_finish(BackendBuffers* b, int np, const TriTracksLayout& L, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good);
+void tri_tracks_empty(int np, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good);
 }  // namespace pmv

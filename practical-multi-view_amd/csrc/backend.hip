@@ -65,6 +65,7 @@ int backend_alloc(pmv_ctx* c, BackendBuffers** out) {
         {&b->d_tri_in, caps.tri_in, MEM_DEVICE}, {&b->d_tri_out, caps.tri_out, MEM_DEVICE},
         {&b->d_fp_work, (size_t)FP_MAX_HYP * (90 * 8 + 4) + 64, MEM_DEVICE},
         {&b->d_ess_in, caps.ess_in, MEM_DEVICE},
+        {&b->d_tt_in, caps.tt_in, MEM_DEVICE},
         {&b->h_stage, caps.h_stage, MEM_MAPPED},
     };
     hipError_t e = mem_alloc_table(rows, sizeof(rows) / sizeof(rows[0]));
@@ -765,7 +766,154 @@ int pmv::homography_prepare(pmv_ctx* ctx, BackendBuffers* b, const float* p1, co
     return float_points_prepare(ctx, b, "pmv_find_homography", p1, p2, n, threshold, confidence, 4, max_iters, P, Lout);
 }
 
+// ---- N-view triangulation of track landmarks (k_tri_tracks, backend_tritracks.hip): check / prepare / finish ------------------------------
+pmv_tri_params pmv::tri_tracks_defaults() { return pmv_tri_params{2, 0, 0.1, HUGE_VAL, HUGE_VAL, 0.0}; }
+// the centre C = -M^-1 p4 of one camera by the adjugate (the statement of tests/twin/tri_tracks_twin.cpp); false: det M == 0, C3 untouched
+static bool tri_centre(const double* p, double* C3) {
+    const double m00 = p[0], m01 = p[1], m02 = p[2], m10 = p[4], m11 = p[5], m12 = p[6], m20 = p[8], m21 = p[9], m22 = p[10];
+    const double a00 = m11 * m22 - m12 * m21, a01 = m02 * m21 - m01 * m22, a02 = m01 * m12 - m02 * m11;
+    const double a10 = m12 * m20 - m10 * m22, a11 = m00 * m22 - m02 * m20, a12 = m02 * m10 - m00 * m12;
+    const double a20 = m10 * m21 - m11 * m20, a21 = m01 * m20 - m00 * m21, a22 = m00 * m11 - m01 * m10;
+    const double det = m00 * a00 + m01 * a10 + m02 * a20;
+    if (det == 0) return false;
+    C3[0] = -(a00 * p[3] + a01 * p[7] + a02 * p[11]) / det;
+    C3[1] = -(a10 * p[3] + a11 * p[7] + a12 * p[11]) / det;
+    C3[2] = -(a20 * p[3] + a21 * p[7] + a22 * p[11]) / det;
+    return true;
+}
+int pmv::tri_tracks_args_check(int max_cams, int max_points, int max_obs, const char* who, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx,
+                               const int* pt_idx, int n_obs, int np, const pmv_tri_params* p_or_null, const double* out_xyz, const uint8_t* out_status,
+                               const int* out_good, char* err) {
+#define TREQ(cond, code, ...) do { if (!(cond)) { snprintf(err, 256, __VA_ARGS__); return code; } } while (0)
+    TREQ(P3x4 && out_good && (n_obs <= 0 || (obs_xy && cam_idx && pt_idx)) && (np <= 0 || (out_xyz && out_status)), PMV_ERR_INVALID, "%s: null argument", who);
+    const pmv_tri_params p = p_or_null ? *p_or_null : tri_tracks_defaults();
+    TREQ(p.min_views >= 2, PMV_ERR_INVALID, "%s: min_views = %d (at least 2)", who, p.min_views);
+    TREQ(p.refine_iters >= 0 && p.refine_iters <= TT_MAX_REFINE, PMV_ERR_INVALID, "%s: refine_iters = %d outside 0..%d", who, p.refine_iters, TT_MAX_REFINE);
+    TREQ(std::isfinite(p.min_depth), PMV_ERR_INVALID, "%s: min_depth = %g is not finite", who, p.min_depth);
+    TREQ(p.max_depth >= p.min_depth, PMV_ERR_INVALID, "%s: max_depth = %g below min_depth = %g", who, p.max_depth, p.min_depth);   // (a NaN fails the comparison too)
+    TREQ(p.max_reproj > 0, PMV_ERR_INVALID, "%s: max_reproj = %g (positive, +inf = no gate)", who, p.max_reproj);
+    TREQ(p.min_parallax_deg >= 0 && p.min_parallax_deg < 180, PMV_ERR_INVALID, "%s: min_parallax_deg = %g outside [0, 180)", who, p.min_parallax_deg);
+    TREQ(nc >= 1, PMV_ERR_INVALID, "%s: nc = %d (at least one camera)", who, nc);
+    TREQ(nc <= max_cams && np >= 0 && np <= max_points && n_obs >= 0 && n_obs <= max_obs, PMV_ERR_CAPACITY, "%s: nc=%d np=%d n_obs=%d exceed capacity %d/%d/%d", who,
+         nc, np, n_obs, max_cams, max_points, max_obs);
+    for (int i = 0; i < n_obs; i++)
+        TREQ(cam_idx[i] >= 0 && cam_idx[i] < nc && pt_idx[i] >= 0 && pt_idx[i] < np, PMV_ERR_INVALID, "%s: index out of range at observation %d (camera %d of %d, landmark %d of %d)",
+             who, i, cam_idx[i], nc, pt_idx[i], np);
+    for (int i = 0; i < 12 * nc; i++) TREQ(std::isfinite(P3x4[i]), PMV_ERR_INVALID, "%s: entry %d of the projection matrix of camera %d is not finite", who, i % 12, i / 12);
+    for (int i = 0; i < 2 * n_obs; i++) TREQ(std::isfinite(obs_xy[i]), PMV_ERR_INVALID, "%s: observation %d (%g, %g) is not finite", who, i / 2, obs_xy[i & ~1], obs_xy[i | 1]);
+    if (p.min_parallax_deg > 0)
+        for (int c = 0; c < nc; c++) {
+            double C3[3];
+            TREQ(tri_centre(P3x4 + 12 * c, C3), PMV_ERR_INVALID, "%s: camera %d has a singular left 3x3 block (det M == 0): no centre for the parallax gate", who, c);
+        }
+#undef TREQ
+    return PMV_OK;
+}
+int pmv::tri_tracks_check(pmv_ctx* ctx, const char* who, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                          const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, int* out_good) {
+    REQ(ctx, PMV_ERR_INVALID, "%s: null argument", who);
+    char err[256];
+    const int rc = tri_tracks_args_check(ctx->max_ba_cams, ctx->max_ba_points, ctx->max_ba_obs, who, P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, out_xyz,
+                                         out_status, out_good, err);
+    if (rc != PMV_OK) set_err(ctx, "%s", err);
+    return rc;
+}
+void pmv::tri_tracks_empty(int np, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good) {
+    for (int p = 0; p < np; p++) {
+        out_xyz[3 * p] = out_xyz[3 * p + 1] = out_xyz[3 * p + 2] = 0; out_status[p] = PMV_TRI_FEW_VIEWS;
+        if (out_err_or_null) out_err_or_null[p] = HUGE_VAL;
+    }
+    *out_good = 0;
+}
+// tri_tracks_layout: the record, P, the centres (zeros with the gate off), the observations in per-landmark runs, the run starts, the counter
+int pmv::tri_tracks_prepare(pmv_ctx* ctx, BackendBuffers* b, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
+                            int np, const pmv_tri_params* p_or_null, TriTracksProblem* P, TriTracksLayout* Lout) {
+    const pmv_tri_params p = p_or_null ? *p_or_null : tri_tracks_defaults();
+    const TriTracksLayout L = tri_tracks_layout((size_t)nc, (size_t)np, (size_t)n_obs);
+    REQ(L.in_bytes <= b->d_tt_in.cap && L.total <= b->h_stage.cap, PMV_ERR_CAPACITY, "pmv_triangulate_tracks: nc=%d np=%d n_obs=%d do not fit the staging blocks", nc, np, n_obs);
+    char* hs = (char*)b->h_stage;
+    double* h_C = (double*)(hs + L.C); double* h_obs = (double*)(hs + L.obs);
+    int* h_cam = (int*)(hs + L.cam); int* start = (int*)(hs + L.start);
+    memcpy(hs + L.P, P3x4, (size_t)nc * 96);
+    const bool parallax_on = p.min_parallax_deg > 0;
+    for (int c = 0; c < nc; c++) {
+        h_C[3 * c] = h_C[3 * c + 1] = h_C[3 * c + 2] = 0;
+        if (parallax_on) REQ(tri_centre(P3x4 + 12 * c, h_C + 3 * c), PMV_ERR_INVALID, "pmv_triangulate_tracks: camera %d has a singular left 3x3 block", c);
+    }
+    // the observations of a landmark, in order of appearance (stable counting sort)
+    std::fill(start, start + np + 1, 0);
+    for (int i = 0; i < n_obs; i++) start[pt_idx[i] + 1]++;
+    for (int q = 0; q < np; q++) start[q + 1] += start[q];
+    {
+        std::vector<int> fill(start, start + np);
+        for (int i = 0; i < n_obs; i++) {
+            const int o = fill[pt_idx[i]]++;
+            h_obs[2 * o] = obs_xy[2 * i]; h_obs[2 * o + 1] = obs_xy[2 * i + 1]; h_cam[o] = cam_idx[i];
+        }
+    }
+    memset(hs + L.counter, 0, 16);
+    char* d = b->d_tt_in;
+    if (++b->done_seq == 0) b->done_seq = 1;
+    P->P = (const double*)(d + L.P); P->C = (const double*)(d + L.C); P->obs = (const double*)(d + L.obs); P->cam = (const int*)(d + L.cam);
+    P->start = (const int*)(d + L.start); P->counter = (unsigned*)(d + L.counter);
+    P->out = b->h_stage.dm() + L.out;
+    P->min_depth = p.min_depth; P->max_depth = p.max_depth; P->max_reproj = p.max_reproj;
+    P->cos_thr = parallax_on ? std::cos(p.min_parallax_deg * M_PI / 180.0) : 1.0;
+    P->nc = nc; P->np = np; P->min_views = p.min_views; P->refine_iters = p.refine_iters; P->parallax_on = parallax_on ? 1 : 0;
+    P->done_seq = b->done_seq;
+    *(volatile unsigned*)(hs + L.done) = 0;
+    memset(hs + L.rec, 0, TT_HDR);
+    *(TriTracksProblem*)(hs + L.rec) = *P;
+    *Lout = L;
+    return PMV_OK;
+}
+void pmv::tri_tracks_finish(BackendBuffers* b, int np, const TriTracksLayout& L, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good) {
+    const char* hs = (const char*)b->h_stage;
+    memcpy(out_xyz, hs + L.xyz, (size_t)np * 24);
+    memcpy(out_status, hs + L.status, (size_t)np);
+    if (out_err_or_null) memcpy(out_err_or_null, hs + L.err, (size_t)np * 8);
+    int good = 0;
+    for (int q = 0; q < np; q++) good += out_status[q] == 0;
+    *out_good = good;
+}
+
 extern "C" {
+
+int pmv_triangulate_tracks(pmv_ctx* ctx, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                           const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good) {
+    if (const int rc = tri_tracks_check(ctx, "pmv_triangulate_tracks", P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, out_xyz, out_status, out_good)) return rc;
+    if (np == 0 || n_obs == 0) { tri_tracks_empty(np, out_xyz, out_status, out_err_or_null, out_good); return PMV_OK; }
+    tl_prof = &ctx->prof;
+    CKC(hipSetDevice(ctx->device));
+    BackendBuffers* b = ctx->be;
+    hipStream_t s = ctx->s_back;
+    TriTracksProblem P;
+    TriTracksLayout L;
+    if (const int rc = tri_tracks_prepare(ctx, b, P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, &P, &L)) return rc;
+    CKC(stage_block(s, b->h_stage.dm(), b->d_tt_in, L.in_bytes, 8));
+    CKC(launch_tri_tracks(s, (const TriTracksProblem*)(b->d_tt_in + L.rec), np));
+    ctx->tri_tracks_launches[0]++; ctx->tri_tracks_launches[1]++;
+    if (const int rc = wait_done_word(ctx, s, (volatile unsigned*)((char*)b->h_stage + L.done), P.done_seq, back_wait_by_word())) return rc;
+    tri_tracks_finish(b, np, L, out_xyz, out_status, out_err_or_null, out_good);
+    return PMV_OK;
+}
+
+int pmv_debug_tri_tracks_check(int max_cams, int max_points, int max_obs, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx,
+                               int n_obs, int np, const pmv_tri_params* p_or_null, const double* out_xyz, const uint8_t* out_status, const double* out_err_or_null,
+                               const int* out_good, char* err256) {
+    (void)out_err_or_null;
+    char err[256] = "";
+    const int rc = tri_tracks_args_check(max_cams, max_points, max_obs, "pmv_triangulate_tracks", P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, out_xyz,
+                                         out_status, out_good, err);
+    if (err256) memcpy(err256, err, 256);
+    return rc;
+}
+
+int pmv_debug_tri_tracks_launches(pmv_ctx* ctx, long long* out2) {
+    if (!ctx || !out2) return PMV_ERR_INVALID;
+    for (int i = 0; i < 2; i++) out2[i] = ctx->tri_tracks_launches[i].load();
+    return PMV_OK;
+}
 
 int pmv_find_essential_mat(pmv_ctx* ctx, const double* p1_xy, const double* p2_xy, int n, const double* K, double prob, double threshold, double* E9,
                            uint8_t* mask, int* out_found, int* out_samples_drawn) {

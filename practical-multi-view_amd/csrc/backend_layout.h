@@ -81,11 +81,27 @@ template <class Pt> inline WholeLayout whole_layout(size_t n) {
 }
 inline WholeLayout essential_layout(size_t n) { return whole_layout<double>(n); }
 inline WholeLayout fundamental_layout(size_t n) { return whole_layout<float>(n); }
+// ---- pmv_triangulate_tracks: d_tt_in mirrors the in-block [problem record TT_HDR | P 12 nc | camera centres 3 nc | observations re-ordered
+// into per-landmark runs: xy 2 n_obs doubles, cameras n_obs ints | run starts np + 1 ints | the workgroup counter, zero], out-block
+// [completion word in TT_OUT_HDR bytes | xyz 3 np | err np doubles | status np bytes] (the kernel derives the three tables from np) ----
+constexpr size_t TT_HDR = 128;        // bytes: the problem record in front of the input block
+constexpr size_t TT_OUT_HDR = 64, TT_OUT_DONE = 0;
+struct TriTracksLayout { size_t rec, P, C, obs, cam, start, counter, in_bytes, out, done, xyz, err, status, total; };
+inline TriTracksLayout tri_tracks_layout(size_t nc, size_t np, size_t n_obs) {
+    Carve c; TriTracksLayout L;
+    L.rec = c.take<char>(TT_HDR).off; L.P = c.take<double>(12 * nc).off; L.C = c.take<double>(3 * nc).off; L.obs = c.take<double>(2 * n_obs).off;
+    L.cam = c.take<int>(n_obs).off; L.start = c.take<int>(np + 1).off; L.counter = c.take<unsigned>(4, 16).off;
+    L.in_bytes = c.bytes();
+    L.out = c.take<char>(TT_OUT_HDR, 64).off; L.done = L.out + TT_OUT_DONE;
+    L.xyz = c.take<double>(3 * np).off; L.err = c.take<double>(np).off; L.status = c.take<uint8_t>(np).off;
+    L.total = c.bytes();
+    return L;
+}
 
 // ---- the blocks' sizes: the layouts at capacity plus the slack terms the allocation always had ----
 constexpr size_t BLOCK_SLACK = 64;   // behind every device block: the 16-byte granules of the stage-in copies may read past the last field
 inline size_t fund_in_cap(size_t max_tracks) { return fundamental_layout(max_tracks).in_bytes + BLOCK_SLACK; }   // d_fund_in, made lazily (fundamental_prepare)
-struct BackendCaps { size_t ba_io, pnp_in, pnp_out, tri_in, tri_out, ess_in, fund_in, h_stage; };
+struct BackendCaps { size_t ba_io, pnp_in, pnp_out, tri_in, tri_out, ess_in, fund_in, h_stage, tt_in; };
 inline BackendCaps backend_caps(int max_tracks, int max_ba_cams, int max_ba_points, int max_ba_obs) {
     constexpr size_t SLACK = BLOCK_SLACK;
     const size_t mt = (size_t)max_tracks;
@@ -96,6 +112,7 @@ inline BackendCaps backend_caps(int max_tracks, int max_ba_cams, int max_ba_poin
     const DltLayout dlt = dlt_layout(mt);
     const FivePointLayout fp = fivepoint_layout(mt, FP_MAX_HYP);
     const WholeLayout ess = essential_layout(mt);
+    const TriTracksLayout tt = tri_tracks_layout(nc, np, no);   // (every table grows with its own count: the largest is at the maxima)
     BackendCaps C;
     // the io block keeps the formula it always had: 24 bytes of index slack and 128 behind it more than ba_io_layout(nc, np, no).total needs
     // (the layout's alignment gap in front of the 16-byte records is at most 12 of them)
@@ -108,12 +125,14 @@ inline BackendCaps backend_caps(int max_tracks, int max_ba_cams, int max_ba_poin
     C.tri_out = dlt.total - dlt.out + SLACK;
     C.ess_in = ess.in_bytes + SLACK;
     C.fund_in = fund_in_cap(mt);
+    C.tt_in = tt.in_bytes + SLACK;
     // the staging block holds the largest in + out pair of any call. The first three terms are older than the single-copy blocks and no
     // layout needs them today; they stay because the block's size stays.
     const size_t pairs[] = {no * 18 * 8 + no * 2 * 8, n * 8 + no * 32 + (np + nc + 2) * 4, mt * 32 + MAX_HYP * 20 + 4096,
                             C.ba_io, C.pnp_in + C.pnp_out, C.tri_in + C.tri_out,
                             C.tri_in + (fp.total - fp.out) + 256,           // five-point round in + out
-                            C.ess_in + (ess.total - ess.out) + SLACK};      // whole findEssentialMat in + out (findFundamentalMat's is smaller)
+                            C.ess_in + (ess.total - ess.out) + SLACK,       // whole findEssentialMat in + out (findFundamentalMat's is smaller)
+                            tt.total + SLACK};                              // N-view triangulation in + out
     C.h_stage = 0;
     for (size_t v : pairs) C.h_stage = max2(C.h_stage, v);
     return C;

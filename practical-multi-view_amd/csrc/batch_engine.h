@@ -12,12 +12,13 @@ void batch_engine_destroy(pmv_ctx* ctx);
 // per combiner (LK, detectors, PnP, BA, DLT): counts10 = {launch rounds, requests} x 5; times15 (may be null) = seconds spent
 // {CPU time of the combiner thread, wall time processing batches, of that waiting for the GPU} x 5
 void batch_engine_stats(BatchEngine* E, long long* counts10, double* times15);
-// What a request asks for. Callers name Q_GFTT or Q_SHITOMASI as the `kind` of engine_detect; from Q_WHOLE_FIRST on the engine owns the
-// request record.
+// What a request asks for. Callers name Q_GFTT or Q_SHITOMASI as the `kind` of engine_detect; from Q_WHOLE_FIRST to Q_WHOLE_LAST the engine
+// owns the request record.
 enum ReqKind {
     Q_LK = 0, Q_GFTT = 1 /* plain or, with the caller's goodFeaturesToTrack arguments, extended */, Q_SHITOMASI = 2, Q_FAST = 3,
     Q_KNN = 4, Q_LK_EX = 5 /* both served by the LK combiners */, Q_SUBPIX = 6, Q_GFTT_FRAME = 7 /* the detector combiner */,
-    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_HOMOGRAPHY = 16, Q_WHOLE_FIRST = Q_ESSENTIAL
+    Q_PNP = 10, Q_BA = 11, Q_DLT = 12, Q_FIVEPOINT = 13, Q_ESSENTIAL = 14, Q_FUNDAMENTAL = 15, Q_HOMOGRAPHY = 16, Q_WHOLE_FIRST = Q_ESSENTIAL,
+    Q_WHOLE_LAST = Q_HOMOGRAPHY, Q_TRI_TRACKS = 17 /* served by the DLT combiner */
 };
 // ---- request entry points: one per plugin call, with the contract of the single call of the same name (include/pmv_hip.h) -------------
 // Who checks what. Each entry runs the check function of its single call (pmv_ctx.h, backend.h; bracket = false) and then forms its
@@ -71,6 +72,10 @@ int engine_ba(BatchEngine* E, int seq, double* cams, int nc, double* pts, int np
               const double* K, double huber, int max_iterations, pmv_ba_summary* summary = nullptr);
 int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const double* P1x4, const uint8_t* mask_in, double* out_Q,
                uint8_t* out_mask, int* out_good);
+// pmv_triangulate_tracks' contract: a request of the DLT combiner; a round serves all its requests of this kind with one k_tri_tracks_batch
+// launch, next to the k_tri_dlt_batch launch of its two-view ones. An empty problem (np == 0 or n_obs == 0) enters no round.
+int engine_tri_tracks(BatchEngine* E, int seq, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                      const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good);
 int engine_fivepoint(BatchEngine* E, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
                      int* n_models, int* counts);
 // pmv_find_essential_mat's contract: one workgroup of the round's k_essential_ransac launch; returns when the request's own completion word is

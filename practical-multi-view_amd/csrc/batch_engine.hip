@@ -93,6 +93,7 @@ struct SubpixReq : Req {      // Q_SUBPIX: one pmv_batch_corner_subpix call; p's
 struct PnPReq : Req { BackendBuffers* b; PnPProblem P; PnPLayout L; };
 struct BAReq : Req { BackendBuffers* b; BAArgs A; BaIoLayout L; int max_iterations; };
 struct DltReq : Req { BackendBuffers* b; DltProblem P; DltLayout L; };
+struct TriTracksReq : Req { BackendBuffers* b; TriTracksProblem P; TriTracksLayout L; };
 struct FPReq : Req { BackendBuffers* b; FivePointProblem P; FivePointLayout L; };
 // Q_ESSENTIAL, Q_FUNDAMENTAL, Q_HOMOGRAPHY: a whole findEssentialMat / findFundamentalMat / findHomography. Its caller returns as soon as the kernel's completion word of ITS request is seen, which may be long
 // before the round's launch ends (a round ends with its slowest request) - so the record cannot live on the caller's stack like the others:
@@ -824,18 +825,31 @@ void process_ba(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
     SYNC_TIMED(C);
 }
 
+// The two-view requests of a round share ONE k_tri_dlt_batch launch, its N-view requests (Q_TRI_TRACKS) ONE k_tri_tracks_batch launch behind
+// it, both behind one k_stage_in launch: the descriptor block is desc_block's with both kinds of records.
 void process_dlt(BatchEngine* E, Combiner& C, std::vector<Req*>& batch) {
-    DescBlock<DltProblem, char> D;
-    EK(desc_block(C, batch.size(), 0, D));
-    int max_n = 0;
-    for (size_t i = 0; i < batch.size(); i++) {
-        DltReq* r = (DltReq*)batch[i];
+    std::vector<DltReq*> dlt; std::vector<TriTracksReq*> tt;
+    for (Req* r : batch) { if (r->kind == Q_TRI_TRACKS) tt.push_back((TriTracksReq*)r); else dlt.push_back((DltReq*)r); }
+    const size_t nd = dlt.size(), nt = tt.size();
+    DescBlock<DltProblem, TriTracksProblem> D;
+    EK(desc_block(C, nd, nt, D));
+    int max_n = 0, max_np = 0;
+    for (size_t i = 0; i < nd; i++) {
+        DltReq* r = dlt[i];
         D.a.h[i] = r->P;
         D.jobs.h[i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tri_in, (unsigned)r->L.in_bytes, 0};
         max_n = std::max(max_n, r->P.n);
     }
-    EK(stage_in(C, D, batch.size(), 2));
-    EK(launch_tri_dlt_batch(C.s, D.a.d, (int)batch.size(), max_n));
+    for (size_t i = 0; i < nt; i++) {
+        TriTracksReq* r = tt[i];
+        D.b.h[i] = r->P;
+        D.jobs.h[nd + i] = StageJob{(const char*)r->b->h_stage.dm(), r->b->d_tt_in, (unsigned)r->L.in_bytes, 0};
+        max_np = std::max(max_np, r->P.np);
+    }
+    EK(stage_in(C, D, nd + nt, 2));
+    EK(launch_tri_dlt_batch(C.s, D.a.d, (int)nd, max_n));
+    EK(launch_tri_tracks_batch(C.s, D.b.d, (int)nt, max_np));
+    if (nt) { E->ctx->tri_tracks_launches[0]++; E->ctx->tri_tracks_launches[1] += (long long)nt; }
     SYNC_TIMED(C);
 }
 
@@ -957,7 +971,7 @@ void combiner_loop(BatchEngine* E, int role, int lane) {
         C->batches++; C->requests += (long)batch.size();
         for (Req* r : batch) {
             std::atomic<int>* w = &r->done;   // (after the store the owner may return and the request, which lives on its stack, is gone)
-            const bool engine_owned = r->kind >= Q_WHOLE_FIRST;
+            const bool engine_owned = r->kind >= Q_WHOLE_FIRST && r->kind <= Q_WHOLE_LAST;
             w->store(1, std::memory_order_release);
             futex_wake_one(w);
             if (engine_owned) {   // the record may be filled again from here on
@@ -1279,6 +1293,22 @@ int engine_dlt(BatchEngine* E, int seq, const double* q1, const double* q2, int 
     rc = submit(ctx, E->queue[R_DLT], &r);
     if (rc) return rc;
     dlt_finish(ctx, r.b, q1, q2, n, P1x4, mask_in, r.L, out_Q, out_mask, out_good);
+    return PMV_OK;
+}
+
+int engine_tri_tracks(BatchEngine* E, int seq, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs, int np,
+                      const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good) {
+    pmv_ctx* ctx = E->ctx;
+    int rc = tri_tracks_check(ctx, "pmv_triangulate_tracks", P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, out_xyz, out_status, out_good);
+    if (rc) return rc;
+    if (np == 0 || n_obs == 0) { tri_tracks_empty(np, out_xyz, out_status, out_err_or_null, out_good); return PMV_OK; }
+    TriTracksReq r;
+    r.kind = Q_TRI_TRACKS; r.b = E->slots[seq];
+    rc = tri_tracks_prepare(ctx, r.b, P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, &r.P, &r.L);
+    if (rc) return rc;
+    rc = submit(ctx, E->queue[R_DLT], &r);
+    if (rc) return rc;
+    tri_tracks_finish(r.b, np, r.L, out_xyz, out_status, out_err_or_null, out_good);
     return PMV_OK;
 }
 

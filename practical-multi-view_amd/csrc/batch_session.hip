@@ -548,6 +548,15 @@ int pmv_batch_triangulate_candidates(pmv_ctx* ctx, int seq, const double* q1, co
     return engine_dlt(S->eng, seq, q1, q2, n, P1x4, mask_in, out_Q, out_mask, out_good);
 }
 
+// N-view triangulation of a seq: one row of workgroups of the round's k_tri_tracks_batch launch (engine_tri_tracks)
+int pmv_batch_triangulate_tracks(pmv_ctx* ctx, int seq, const double* P3x4, int nc, const double* obs_xy, const int* cam_idx, const int* pt_idx, int n_obs,
+                                 int np, const pmv_tri_params* p_or_null, double* out_xyz, uint8_t* out_status, double* out_err_or_null, int* out_good) {
+    SESSION("pmv_batch_triangulate_tracks");
+    if (const int rc = seq_check(ctx, S, "pmv_batch_triangulate_tracks", seq)) return rc;
+    std::lock_guard<std::mutex> lk(S->seq_mu[(size_t)seq]);
+    return engine_tri_tracks(S->eng, seq, P3x4, nc, obs_xy, cam_idx, pt_idx, n_obs, np, p_or_null, out_xyz, out_status, out_err_or_null, out_good);
+}
+
 int pmv_batch_fivepoint_hypotheses(pmv_ctx* ctx, int seq, const double* q1, const double* q2, int n, const int* samples, int n_hyp, float thr, double* models,
                                    int* n_models, int* counts) {
     SESSION("pmv_batch_fivepoint_hypotheses");

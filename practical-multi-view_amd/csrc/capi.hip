@@ -139,6 +139,7 @@ int pmv_ctx_create(pmv_ctx** out, int device, int max_w, int max_h, int n_slots,
     for (auto& a : c->batch_launches) a.store(0);
     for (auto& a : c->whole_rounds) a.store(0);
     for (auto& a : c->homography_launches) a.store(0);
+    for (auto& a : c->tri_tracks_launches) a.store(0);
     for (auto& a : c->subpix_launches) a.store(0);
     for (auto& a : c->clahe_launches) a.store(0);
     for (auto& a : c->remap_launches) a.store(0);

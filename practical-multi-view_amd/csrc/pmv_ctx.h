@@ -97,6 +97,8 @@ struct pmv_ctx {
     std::atomic<long long> whole_rounds[3];
     // k_homography_ransac launches since the context was created and the requests they served (pmv_debug_homography_launches)
     std::atomic<long long> homography_launches[2];
+    // k_tri_tracks / k_tri_tracks_batch launches since the context was created and the requests they served (pmv_debug_tri_tracks_launches)
+    std::atomic<long long> tri_tracks_launches[2];
     // landing area of the synchronous calls' host frames on their way into the slots: TIGHT_FRAMES tight gray frames, or a third as many BGR ones (H2D copies are contiguous; k_pad_level0 takes
     // level 0 from here). A 2-D copy straight into the padded level is a DMA per image row: 128 x 1101 frames did not finish in 200 s.
     static constexpr int TIGHT_FRAMES = 64;
